@@ -6,9 +6,11 @@ transform of every coded TB (k_itdq), MC + residual add + clip + SCU-map update 
 dependency order (k_intra_l1 + the data-flow launch k_intra, which also carries the NEXT picture's residual pass), ADDB + ALF + border padding in one pass (k_addb_alf).  Pictures chain like a stream: picture k is predicted from pictures k-1 and k-2 (a 3-slot DPB
 ring), so steps are serially dependent exactly like a real decode.
 
-What the JSON line's figures are, all at the command line the driver uses (`--steps 20 --warmup 5` included):
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the headline: `value` / `kernel_only_fps` and `ms_per_step`
+(with `config`, and `per_rank` with N > 1).  `--dump-outputs DIR` writes the picture of the last timed step (dump_outputs).  Every other figure below takes
+runs of its own after the timed steps and comes with `--full` (which `--no-cpu-baseline` / `--no-end-to-end` / `--no-inter-classes` then trim):
   value / kernel_only_fps   the benchmark contract's number: the CU batches (the post-entropy records) are resident in HBM when the timed region starts; W warm-up
-                            pictures, then exactly K timed ones between two barrier + synchronize pairs.
+                            pictures, then exactly K timed ones between two barrier + synchronize pairs.  ms_per_step = the timed span / K.
   roofline                  the dominant kernel by HIP-event time against SURVEY 8(d)'s bytes of its pass, timed in a second loop of K pictures with every kernel alone
                             on the stream.  `traffic` comes from the committed counter passes (profiles/latest_pmc.json) and is dropped (null) when the kernel's sources
                             no longer hash to what those passes measured.
@@ -18,7 +20,8 @@ What the JSON line's figures are, all at the command line the driver uses (`--st
   cpu_baseline              the same batch through the reference's functions (oracle/_ref) or the CPU oracle on a bounded sample, + the reference decoder on a
                             real stream of the workload's shape.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20            # single GPU
+    python bench.py --gpus 1 --steps 200 --warmup 20            # single GPU, the headline only
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full     # ... and every secondary figure
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   # one rank per GPU
 
 With N > 1 the workload is BASELINE.json configs[4]: independent 4K Main streams cut into GOP-sized jobs that the ranks draw from one
@@ -159,6 +162,25 @@ def make_stream(wl, seed, n_batches):
     n_ctu = ((wl["w"] + 63) // 64) * ((wl["h"] + 63) // 64)
     alf = synth.gen_alf_params(rng, n_ctu, ctb_on_frac=1.0) if wl["alf"] else None     # all CTUs on
     return first, batches, alf
+
+
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs: float32 samples of the three planes (the row / column sums come on top: 0.2 MB at 8K)
+
+
+def dump_outputs(dec, pic, out_dir, prefix=""):
+    """--dump-outputs: the picture the last timed step decoded, as a caller of the path receives it (xgpu_pic_download: Y, U, V planes without padding),
+    written as out_dir/<prefix><plane>.npy - float32, the plane's rows at a fixed seeded choice of row indices (every row where the three planes fit in
+    DUMP_BUDGET_BYTES) - and <prefix><plane>_row_sums.npy / <prefix><plane>_col_sums.npy - float64, the sums over every sample of the plane."""
+    planes = dec.pic_download(pic)
+    os.makedirs(out_dir, exist_ok=True)
+    frac = min(1.0, DUMP_BUDGET_BYTES / (4 * sum(p.size for p in planes)))
+    for seed, (name, p) in enumerate(zip("yuv", planes)):
+        h = p.shape[0]
+        n = max(1, int(h * frac))
+        rows = np.arange(h) if n >= h else np.sort(np.random.default_rng(seed).choice(h, n, replace=False))
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), p[rows].astype(np.float32))
+        np.save(os.path.join(out_dir, f"{prefix}{name}_row_sums.npy"), p.sum(1, dtype=np.float64))
+        np.save(os.path.join(out_dir, f"{prefix}{name}_col_sums.npy"), p.sum(0, dtype=np.float64))
 
 
 def cpu_baseline(wl, first, batch, alf, budget_s=15.0):
@@ -612,11 +634,18 @@ def main():
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help=f"default: {DEFAULT_WORKLOAD} on one GPU, {DEFAULT_WORKLOAD_MULTI} with --gpus N > 1")
     ap.add_argument("--batches", type=int, default=4, help="distinct pictures' CU batches kept resident and cycled")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the batches-in -> YUV-out leg")
-    ap.add_argument("--no-inter-classes", action="store_true", help="skip the k_inter-by-CU-size leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the secondary figures: per-kernel times + roofline, the end-to-end leg, the k_inter-by-CU-size leg, several "
+                         "contexts, the multi-GPU streams leg, the CPU baseline with the bit-exactness check (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the picture the last timed step decoded to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the batches-in -> YUV-out leg")
+    ap.add_argument("--no-inter-classes", action="store_true", help="with --full: skip the k_inter-by-CU-size leg")
     ap.add_argument("--no-prepare", action="store_true", help="every picture's residual pass in front of its own k_inter (no xgpu_batch_prepare of the next picture)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched plainly (`python bench.py --gpus N`): this process becomes the launcher of N ranks, one per GPU, each running this
@@ -682,7 +711,7 @@ def main():
     # self-check, outside the timed region: the first batch decoded from the two start pictures exactly as the CPU leg does it
     # (src_main/xevdm.c:3136-3219: recon, deblock, ALF, pad); compared plane by plane, padding included, further down
     gpu_check = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         refs = {(0, 0): (slots[0], 0)}
         if two_lists:
             refs[(0, 1)] = (slots[1], 2 if wl.get("dmvr_frac") else -1)
@@ -718,6 +747,7 @@ def main():
             step(args.warmup + k, ahead)
         barrier()
         dt = time.perf_counter() - t0
+        last_k = args.warmup + args.steps - 1
     else:
         # world x steps pictures in jobs of GOP_PICTURES, drawn by the ranks from one queue (xevd_amd/workqueue.py: a counter in the
         # rendezvous store): a rank that is done asks for the next job, nobody waits for a fixed share
@@ -735,6 +765,7 @@ def main():
                 step(k, ahead)
                 k += 1
             mine += n
+        last_k = k - 1 if mine else None
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         dec.sync()
@@ -746,6 +777,38 @@ def main():
         g = [torch.zeros(2, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(g, torch.tensor([float(mine), my_dt], dtype=torch.float64))
         per_rank = [{"rank": r, "pictures": int(v[0].item()), "fps": round(float(v[0].item()) / max(float(v[1].item()), 1e-9), 2)} for r, v in enumerate(g)]
+
+    if args.dump_outputs and last_k is not None:
+        dump_outputs(dec, slots[(last_k + 2) % 3], args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "")
+
+    # the headline line's fields: frames/s of the timed steps
+    out = {
+        "metric": "frames/sec (bit-exact YUV) + achieved HBM GB/s",
+        "value": round(world * args.steps / dt, 2),
+        "unit": "frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * dt / args.steps, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "s16", "data": "synthetic",
+        "config": {"workload": args.workload, "width": wl["w"], "height": wl["h"], "bit_depth": wl["bd"],
+                   "profile": "Main (admvp 8-tap MC, IQT, ADDB, ALF on every CTU)" if wl["addb"] else "Baseline",
+                   "stream": ("2 reference lists, 50% bi-predicted CUs" if two_lists else "IPPP, 1 reference")
+                             + ", 90% inter / 10% intra CUs (5 Baseline modes), 60% coded, deblock on, quad-tree 64..4",
+                   "batches_resident": len(batches), "batch": batch_info,
+                   "residual_pass_ahead": bool(ahead and len(batches) > 1),
+                   "parallelism": (f"{world} ranks, one GPU each, drawing jobs of {GOP_PICTURES} pictures (closed GOPs of independent streams) from one host work "
+                                   "queue; no collective on the data path" if world > 1 else "1 stream on 1 GPU")},
+    }
+    if not args.full:
+        # a plain run: the headline and nothing else (the secondary figures take runs of their own: --full)
+        if rank == 0:
+            out.update({"per_rank": per_rank, "decoder": dec_mod, "kernel_only_fps": out["value"]})
+            print(json.dumps(out))
+        barrier()
+        dec.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # per-kernel durations with HIP events on the stream the kernels are launched on, same workload and steps - every kernel on the main stream, one after
     # the other (no residual pass queued ahead), so that each duration is the kernel's own
@@ -833,22 +896,7 @@ def main():
             traffic = None
         total_alg = float(np.mean([sum(v for k, v in a.items() if k != "alf" or wl["alf"]) for a in ab]))
         kern_s = max(sum(tim[k][0] for k in ("itdq", "inter", "dmvr", "affine", "intra", "dbk_v", "dbk_h", "alf", "pad")) * 1e-3 / args.steps, 1e-12)
-        out = {
-            "metric": "frames/sec (bit-exact YUV) + achieved HBM GB/s",
-            "value": round(world * args.steps / dt, 2),
-            "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "s16", "data": "synthetic",
-            "config": {"workload": args.workload, "width": wl["w"], "height": wl["h"], "bit_depth": wl["bd"],
-                       "profile": "Main (admvp 8-tap MC, IQT, ADDB, ALF on every CTU)" if wl["addb"] else "Baseline",
-                       "stream": ("2 reference lists, 50% bi-predicted CUs" if two_lists else "IPPP, 1 reference")
-                                 + ", 90% inter / 10% intra CUs (5 Baseline modes), 60% coded, deblock on, quad-tree 64..4",
-                       "batches_resident": len(batches), "batch": batch_info,
-                       "residual_pass_ahead": bool(ahead and len(batches) > 1),
-                       "parallelism": (f"{world} ranks, one GPU each, drawing jobs of {GOP_PICTURES} pictures (closed GOPs of independent streams) from one host work "
-                                       "queue; no collective on the data path" if world > 1 else "1 stream on 1 GPU")},
+        out.update({
             "roofline": {"bound": "hbm", "kernel": "addb_alf" if dom == "alf" and addb_alf else dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
                          "algorithmic_bytes_per_launch": int(bytes_per_launch), "avg_launch_us": round(avg_s * 1e6, 2),
@@ -874,7 +922,7 @@ def main():
             "end_to_end_fps": e2e["fps"],
             "end_to_end": e2e,
             "two_contexts": two_ctx,
-        }
+        })
         if not args.no_cpu_baseline and world == 1:      # the CPU leg runs on rank 0 of the single-GPU run only
             cpu_pic, out["cpu_baseline"] = cpu_baseline(wl, first, batches[0], alf)
             out["bit_exact"] = bool(all(np.array_equal(gpu_check[c], cpu_pic[c]) for c in range(3)))

@@ -7,7 +7,7 @@ cp xevd_amd/libxevd_hip.so /tmp/libxevd_hip_product.so
 cp tools/ab/libxevd_hip_$V.so xevd_amd/libxevd_hip.so
 timeout -k 5 600 python - <<PY
 import sys, ctypes as C, io, contextlib, json
-sys.argv = ["bench.py", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-end-to-end"]
+sys.argv = ["bench.py", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-end-to-end", "--full"]
 import bench
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):

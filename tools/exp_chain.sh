@@ -7,7 +7,7 @@ bash tools/exp_ab.sh cfg4_main_8k_10b_ra
 bash tools/exp_ab.sh cfg3_main_4k_10b_ra
 for n in 64 128 512 1024 100000; do
   for WL in cfg4_main_8k_10b_ra cfg3_main_4k_10b_ra cfg2_main_1080p_10b_ra; do
-  XEVD_HIP_CHAIN_WGS=$n timeout 600 python bench.py --steps 60 --workload $WL --no-cpu-baseline --no-end-to-end 2>/dev/null | python -c "
+  XEVD_HIP_CHAIN_WGS=$n timeout 600 python bench.py --steps 60 --workload $WL --no-cpu-baseline --no-end-to-end --full 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('$n $WL', d['value'], d['ms_per_step'], {k: v['avg_us'] for k, v in d['kernels'].items() if 'intra' in k})"
