@@ -19,6 +19,7 @@
  *   xgpu_pic_md5                  <- xevd_picbuf_signature / xevd_md5_imgb (picture signature)       src_base/xevd_util.c:985-1002, 1557-1572
  *   xgpu_pic_output               <- xevd_pull + the application's imgb_cpy_codec_to_out (crop fields xevd.c:2058-2069,
  *                                    bit-depth conversions app/xevd_app_util.h:441-552,656-700)
+ *   xgpu_pic_output_device        (no counterpart: the picture as YUV or R'G'B' into the caller's device memory)
  *
  * plus fine-grained shims with the reference's per-block function-table signatures
  * (XEVD_MC_L / XEVD_MC_C src_base/xevd_mc.h:47-49, XEVD_ITXB src_base/xevd_def.h:360, fn_recon :1466)
@@ -224,6 +225,46 @@ int  xgpu_pic_output(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, int out_b
 int  xgpu_pic_output_async(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, int out_bit_depth, int crop_l, int crop_r, int crop_t, int crop_b,
                            void *dst, size_t dst_size, int *ticket);
 int  xgpu_pic_output_wait(xgpu_ctx *ctx, int ticket);
+/* Output into device memory - for a consumer on the same GPU (a model, a metric), no staging buffer, no copy to the host.  The same crop and DRA as
+   xgpu_pic_output, then one of:
+     XGPU_OUT_YUV420P          xgpu_pic_output's bytes (k_output unchanged): dtype U8 with out_bit_depth 8, else U16 (out_bit_depth 0 = the coding depth)
+     XGPU_OUT_RGB_PLANAR       3 planes of H x W (R, G, B - or B, G, R with bgr), plane k at k * H * row_pitch
+     XGPU_OUT_RGB_INTERLEAVED  H rows of W x 3 elements
+   RGB: 4:2:0 chroma upsampled on the cropped chroma plane (edge-clamped) - NEAREST c[y>>1][x>>1], or LINEAR with quarter weights placed by
+   chroma_loc (H.273 ChromaSampleLocType 0..5), (sum + 8) >> 4 - then Y'CbCr -> R'G'B' with the matrix of `matrix` (H.273 MatrixCoefficients
+   1 BT.709, 4 FCC, 5 / 6 BT.601, 7 SMPTE 240M, 9 BT.2020 non-constant luminance; others XGPU_ERR_UNSUPPORTED) and limited / full range.
+   Integer outputs (U8: 8 bit, U16: the coding depth) are fixed point: coefficients round(k * (2^D - 1) / range * 2^S), S = 27 - D, channel =
+   clip((sum + 2^(S-1)) >> S, 0, 2^D - 1); float outputs evaluate the same formula in float32 with 2^D - 1 = 1, clipped to [0, 1] (F16 / BF16: that
+   value rounded to nearest even).  The exact contract: INTEGRATION.md section 8. */
+#define XGPU_OUT_YUV420P          0
+#define XGPU_OUT_RGB_PLANAR       1
+#define XGPU_OUT_RGB_INTERLEAVED  2
+#define XGPU_OUT_U8               0
+#define XGPU_OUT_U16              1
+#define XGPU_OUT_F16              2
+#define XGPU_OUT_BF16             3
+#define XGPU_OUT_F32              4
+#define XGPU_UPSAMPLE_NEAREST     0
+#define XGPU_UPSAMPLE_LINEAR      1
+typedef struct xgpu_output_format {
+    int layout;                /* XGPU_OUT_YUV420P | XGPU_OUT_RGB_PLANAR | XGPU_OUT_RGB_INTERLEAVED                                 */
+    int bgr;                   /* RGB layouts: channel order B, G, R                                                                 */
+    int dtype;                 /* XGPU_OUT_U8 | _U16 | _F16 | _BF16 | _F32 (YUV420P: U8 / U16 by out_bit_depth)                      */
+    int out_bit_depth;         /* YUV420P: as xgpu_pic_output (0 = the coding depth); RGB: 0 or the coding depth                      */
+    int matrix, full_range, chroma_loc, upsample;      /* H.273 MatrixCoefficients, video_full_range_flag, ChromaSampleLocType, XGPU_UPSAMPLE_* */
+    int crop[4];               /* left, right, top, bottom luma samples - even                                                        */
+    size_t row_pitch;          /* bytes between rows of a plane / of the interleaved image; 0 = tight (YUV420P: must be 0)            */
+} xgpu_output_format;
+/* bytes the format needs at d_dst (the last row tight); 0: invalid format for this context */
+size_t xgpu_pic_output_device_size(const xgpu_ctx *ctx, const xgpu_output_format *f);
+/* Non-blocking.  d_dst: device memory of the context's device, aligned to the element size, >= xgpu_pic_output_device_size bytes (checked - with
+   hipPointerGetAttributes - before anything is queued: XGPU_ERR_INVALID_ARGUMENT and no launch otherwise).  stream = NULL: the context's stream;
+   else the kernel runs on `stream` (a hipStream_t - e.g. torch.cuda.current_stream().cuda_stream) behind the picture's kernels, and the context's
+   stream waits for it before it touches the picture slot or the DRA tables again. */
+int    xgpu_pic_output_device(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, void *d_dst, size_t dst_size, void *stream);
+/* Host only, no context: the fixed-point coefficients the kernel uses for format `f` at coding depth `bit_depth` - coef = { cy, crv, cgu, cgv, cbu }
+   with `shift` = S (integer dtypes; zeros for float dtypes), fcoef = the float32 ones (2^D - 1 = 1).  0, or a negative code for an invalid format. */
+int    xgpu_output_coeffs(const xgpu_output_format *f, int bit_depth, int32_t coef[5], int *shift, float fcoef[5]);
 /* The picture signature on the device: the MD5 of every plane over its rows of width x 2 bytes of 16-bit samples (8-bit pictures too), as xevd_md5_imgb makes it
    (src_base/xevd_util.c:985-1002) and xevd_picbuf_check_signature compares it with the SEI (:1557-1572) - of the DRA-mapped picture when `dra` is given, which is
    what the Main decoder signs when the PPS names a DRA parameter set (src_main/xevdm.c:3256-3287).  digest[plane] = the 16 bytes of the SEI payload.  Blocking; the

@@ -25,7 +25,7 @@
  * tool_cm_init (context initialisation tables, neighbour-dependent contexts) and tool_adcc
  * (advanced coefficient coding) are parsed.
  * dquant_flag (QP deltas per quantisation group), tool_rpl (reference picture lists in SPS / slice headers, RPL-based marking) and tool_pocs
- * (POC from poc_lsb) are parsed.  SPS chroma QP mapping tables and cropping offsets are parsed, a VUI is skipped; 4:2:0, one slice per picture (with all of its
+ * (POC from poc_lsb) are parsed.  SPS chroma QP mapping tables, cropping offsets and the VUI (colour description handed out) are parsed; 4:2:0, one slice per picture (with all of its
  * tiles - uniform or explicit PPS tile grids, entry points in the slice header; explicit tile ids and arbitrary slices are refused), I / P / B slices incl. temporal layers (hierarchical sub-GOPs).
  * Conventions as xevd_hip.h: 0 / negative XEVD_ERR_* codes, nothing throws, one object per stream.
  */
@@ -80,6 +80,12 @@ typedef struct xhost_picture {
     int n_release;                         /* reference pictures unmarked before this one was stored (pic_marking_no_rpl) */
     int release_poc[32];
     xgpu_cu_batch batch;
+    /* colour description of the SPS's VUI (xevd_eco_vui, xevd_eco.c:1229-1304; code points as H.273).  Without a VUI, or for an element the VUI does not
+       signal: 0, 0, 2, 2, 2, 0 (unspecified) - the caller decides what "unspecified" means (xgpu_output_format.matrix refuses 2) */
+    int vui_present;                       /* vui_parameters_present_flag                                                       */
+    int video_full_range_flag;
+    int colour_primaries, transfer_characteristics, matrix_coefficients;
+    int chroma_sample_loc_type;            /* chroma_sample_loc_type_top_field (0..5)                                            */
 } xhost_picture;
 
 xhost_parser *xhost_parser_open(const uint8_t *bytes, size_t size);
@@ -200,6 +206,17 @@ typedef struct xhost_stream_params {
                                               log2_diff_ctu_size_max_suco_cb_size / log2_diff_max_suco_min_suco_cb_size (xevdm_util.c:1702-1727: the flag is sent for
                                               nodes with sides between 2^max(6 - max - min, 4) and 2^(6 - max))                                                       */
     int suco_diff_max, suco_diff_min;
+    /* VUI of the SPS (xevd_eco_vui syntax; all zero: no VUI, the bytes of a writer without these fields).  A VUI is written when any of vui_signal_type,
+       vui_colour_desc, vui_chroma_loc or vui_extra is set. */
+    int vui_signal_type;                   /* video_signal_type_present_flag (video_format 5) with video_full_range_flag = vui_full_range */
+    int vui_full_range;
+    int vui_colour_desc;                   /* colour_description_present_flag (implies vui_signal_type) with the three 8-bit code points below */
+    int vui_colour_primaries, vui_transfer_characteristics, vui_matrix_coefficients;
+    int vui_chroma_loc;                    /* chroma_loc_info_present_flag with the two types below (0..5)                     */
+    int vui_chroma_loc_top, vui_chroma_loc_bottom;
+    int vui_extra;                         /* the syntax a parser has to step over: aspect_ratio_idc 255 with 16-bit SAR words, overscan info, timing info
+                                              (32-bit tick and scale), one NAL HRD set with cpb_cnt_minus1 = 1, pic_struct_present_flag and a
+                                              bitstream-restriction block                                                       */
 } xhost_stream_params;
 
 /* ALF parameter set as it is coded in an APS NAL unit (XEVD_ALF_SLICE_PARAM after xevdm_eco_alf_aps_param) */

@@ -1,0 +1,71 @@
+"""Device-output rate: an 8K 10-bit picture converted into torch tensors by xgpu_pic_output_device (k_output_rgb / k_output), timed with torch
+events on the output stream (median of --iters launches after warm-up), against the plain device copy rate of the same run
+(xgpu_measure_copy_bw).  Bytes are algorithmic: 3 bytes of samples read per pixel (luma + two quarter-size chroma planes, 16 bit) and what the
+format writes.  Prints one line per form and a JSON line; --out also writes the JSON to a file.
+
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--out out/output_device.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=7680)
+    ap.add_argument("--height", type=int, default=4320)
+    ap.add_argument("--bit-depth", type=int, default=10)
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    from xevd_amd.decoder import XgpuDecoder
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_output_device: no GPU")
+    w, h, bd = a.width, a.height, a.bit_depth
+    rng = np.random.default_rng(0)
+    planes = [rng.integers(0, 1 << bd, (h, w)).astype(np.int16), rng.integers(0, 1 << bd, (h // 2, w // 2)).astype(np.int16),
+              rng.integers(0, 1 << bd, (h // 2, w // 2)).astype(np.int16)]
+    forms = [("rgb_u8_planar", dict(dtype=torch.uint8), 3),
+             ("rgb_u8_interleaved", dict(dtype=torch.uint8, channels_last=True), 3),
+             ("rgb_f16_planar", dict(dtype=torch.float16), 6),
+             ("yuv420p_u8", dict(layout="yuv420p", dtype=torch.uint8), 1.5)]
+    res = {"width": w, "height": h, "bit_depth": bd, "iters": a.iters, "forms": {}}
+    with XgpuDecoder(w, h, bd, device=0, max_pics=2) as dec:
+        pic = dec.pic_alloc()
+        dec.pic_upload(pic, planes)
+        copy_gbps = dec.measure_copy_bw(1 << 30, 20)
+        res["copy_gbps"] = copy_gbps
+        s = torch.cuda.Stream()      # a stream of its own: the conversion is queued on it directly (torch's default stream goes through a side stream)
+        torch.cuda.set_stream(s)
+        for name, kw, wbytes in forms:
+            out = dec.pic_output_tensor(pic, **kw)
+            for _ in range(5):
+                dec.pic_output_tensor(pic, out=out, **kw)
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]
+            torch.cuda._sleep(int(3e8))      # the GPU waits while the host queues every timed launch: the events then bracket device time only
+            for e0, e1 in ev:
+                e0.record(s)
+                dec.pic_output_tensor(pic, out=out, **kw)
+                e1.record(s)
+            torch.cuda.synchronize()
+            us = float(np.median([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]))
+            nbytes = int(w * h * (3 + wbytes))
+            gbps = nbytes / (us * 1e-6) / 1e9
+            res["forms"][name] = {"us": round(us, 2), "bytes": nbytes, "gbps": round(gbps, 1), "frac_copy": round(gbps / copy_gbps, 3)}
+            print(f"{name:20s} {us:9.1f} us  {nbytes / 1e6:7.1f} MB  {gbps:7.1f} GB/s  {gbps / copy_gbps:5.2f} of copy ({copy_gbps:.0f} GB/s)")
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -33,6 +33,28 @@ class DraLuts(C.Structure):
     _fields_ = [("luma_inv_scale_lut", C.c_void_p), ("chroma_inv_scale_lut", C.c_void_p * 2)]
 
 
+OUT_YUV420P, OUT_RGB_PLANAR, OUT_RGB_INTERLEAVED = 0, 1, 2
+OUT_U8, OUT_U16, OUT_F16, OUT_BF16, OUT_F32 = 0, 1, 2, 3, 4
+UPSAMPLE_NEAREST, UPSAMPLE_LINEAR = 0, 1
+
+
+class OutputFormat(C.Structure):
+    _fields_ = [("layout", C.c_int), ("bgr", C.c_int), ("dtype", C.c_int), ("out_bit_depth", C.c_int),
+                ("matrix", C.c_int), ("full_range", C.c_int), ("chroma_loc", C.c_int), ("upsample", C.c_int),
+                ("crop", C.c_int * 4), ("row_pitch", C.c_size_t)]
+
+
+def make_output_format(layout=OUT_RGB_PLANAR, dtype=OUT_U8, bgr=False, out_bit_depth=0, matrix=1, full_range=False, chroma_loc=0,
+                       upsample=UPSAMPLE_LINEAR, crop=(0, 0, 0, 0), row_pitch=0):
+    f = OutputFormat()
+    f.layout, f.bgr, f.dtype, f.out_bit_depth = int(layout), int(bool(bgr)), int(dtype), int(out_bit_depth)
+    f.matrix, f.full_range, f.chroma_loc, f.upsample = int(matrix), int(bool(full_range)), int(chroma_loc), int(upsample)
+    for i in range(4):
+        f.crop[i] = int(crop[i])
+    f.row_pitch = int(row_pitch)
+    return f
+
+
 class FrameParams(C.Structure):
     _fields_ = [
         ("pic", C.c_int), ("poc", C.c_int), ("num_refp", C.c_int * 2),
@@ -191,6 +213,9 @@ _EXPORTS = {
     "xgpu_pic_output_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "xgpu_pic_output_wait": (C.c_int, [C.c_void_p, C.c_int]),
     "xgpu_pic_md5": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "xgpu_pic_output_device_size": (C.c_size_t, [C.c_void_p, C.POINTER(OutputFormat)]),
+    "xgpu_pic_output_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_output_coeffs": (C.c_int, [C.POINTER(OutputFormat), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "xgpu_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "xgpu_host_free": (None, [C.c_void_p, C.c_void_p]),
     "xgpu_batch_wait_upload": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -230,10 +255,28 @@ def exported_names():
     return sorted(_EXPORTS)
 
 
+def _share_torch_hip_runtime():
+    """torch's ROCm wheel carries its own HIP runtime (torch/lib/libamdhip64.so, SONAME libamdhip64.so.7) and its libraries ask for it by that FILE
+    name.  Loaded after this library - which asks for libamdhip64.so.7 and gets ROCm's - torch maps a second runtime, and a second runtime in one
+    process finds no GPU.  So when torch is installed its runtime is mapped first (without importing torch): this library then binds to it by
+    SONAME, and torch finds it already there, in either import order."""
+    import importlib.util
+    import sys
+    if "torch" in sys.modules:
+        return                                   # torch's runtime is mapped already
+    spec = importlib.util.find_spec("torch")
+    if spec is None or not spec.submodule_search_locations:
+        return
+    rt = os.path.join(list(spec.submodule_search_locations)[0], "lib", "libamdhip64.so")
+    if os.path.exists(rt):
+        C.CDLL(rt, mode=C.RTLD_GLOBAL)
+
+
 def load():
     """Load the product library.  Fails loudly when it has not been built - there is no CPU fallback."""
     global _lib
     if _lib is None:
+        _share_torch_hip_runtime()
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "

@@ -81,7 +81,8 @@ __global__ __launch_bounds__(256) void k_output(const OutArgs p)
 }
 
 // raw16: the samples as they are, two bytes each whatever the coding depth (the bytes the picture signature is made of: xevd_md5_imgb hashes w x 2 bytes per row)
-void launch_output(xgpu_ctx *c, const DevPic &pic, const int32_t *d_dra, int out_bd, int crop_l, int crop_r, int crop_t, int crop_b, uint8_t *d_dst, bool raw16)
+void launch_output(xgpu_ctx *c, const DevPic &pic, const int32_t *d_dra, int out_bd, int crop_l, int crop_r, int crop_t, int crop_b, uint8_t *d_dst, bool raw16,
+                   hipStream_t s)
 {
     if (raw16) out_bd = c->sp.bit_depth_luma;
     OutArgs p;
@@ -107,5 +108,5 @@ void launch_output(xgpu_ctx *c, const DevPic &pic, const int32_t *d_dra, int out
     p.out8 = out_bd == 8 && !raw16;
     p.maxv = (1 << out_bd) - 1;
     p.dra = d_dra;
-    hipLaunchKernelGGL(k_output, dim3(rows), dim3(256), 0, c->stream, p);
+    hipLaunchKernelGGL(k_output, dim3(rows), dim3(256), 0, s ? s : c->stream, p);
 }

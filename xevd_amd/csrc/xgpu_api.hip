@@ -126,6 +126,7 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
     c->split_addb_alf = getenv("XEVD_HIP_SPLIT_ADDB_ALF") != NULL;      // measurement knob: ADDB and ALF as two kernels (the round-2 chain) instead of k_addb_alf
     for (int i = 0; i < 2; i++) { c->d_out[i] = NULL; c->out_caps[i] = 0; c->out_ready[i] = c->out_done[i] = 0; c->out_busy[i] = 0; }
     c->d_md5 = NULL; c->md5_ready = 0;
+    c->odev_ev[0] = c->odev_ev[1] = 0;
     c->out_next = 0;
     memset(c->t_ms, 0, sizeof(c->t_ms)); memset(c->t_n, 0, sizeof(c->t_n));
     // chroma QP mapping: caller table starts at qp = -6*(bdc-8); default = Baseline static table with the
@@ -212,6 +213,7 @@ void xgpu_close(xgpu_ctx *c)
     c->pool.clear();
     if (c->d_md5) (void)hipFree(c->d_md5);
     if (c->md5_ready) (void)hipEventDestroy(c->md5_ready);
+    for (int i = 0; i < 2; i++) if (c->odev_ev[i]) (void)hipEventDestroy(c->odev_ev[i]);
     for (int i = 0; i < 2; i++) { if (c->d_out[i]) (void)hipFree(c->d_out[i]); if (c->out_ready[i]) (void)hipEventDestroy(c->out_ready[i]); if (c->out_done[i]) (void)hipEventDestroy(c->out_done[i]); }
     if (c->d_dra) (void)hipFree(c->d_dra);
     if (c->d_ctb_flag) (void)hipFree(c->d_ctb_flag);
@@ -392,6 +394,177 @@ int xgpu_pic_output(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, int out_bit_
     int ticket = 0;
     const int rc = xgpu_pic_output_async(c, pic, dra, out_bit_depth, crop_l, crop_r, crop_t, crop_b, dst, dst_size, &ticket);
     return rc < 0 ? rc : xgpu_pic_output_wait(c, ticket);
+}
+
+// ------------------------------------------------------------------------------------------------ output into device memory
+// Kr, Kb of the supported H.273 MatrixCoefficients code points; false for the others (0 identity, 2 unspecified, 10 constant luminance, ...)
+static bool matrix_kr_kb(int m, double *kr, double *kb)
+{
+    switch (m) {
+    case 1: *kr = 0.2126; *kb = 0.0722; return true;      // BT.709
+    case 4: *kr = 0.30;   *kb = 0.11;   return true;      // FCC
+    case 5: case 6: *kr = 0.299; *kb = 0.114; return true;      // BT.601 (625 / 525)
+    case 7: *kr = 0.212;  *kb = 0.087;  return true;      // SMPTE 240M
+    case 9: *kr = 0.2627; *kb = 0.0593; return true;      // BT.2020 non-constant luminance
+    default: return false;
+    }
+}
+static int elem_size(int dtype) { return dtype == XGPU_OUT_U8 ? 1 : dtype == XGPU_OUT_F32 ? 4 : 2; }
+// the format alone (no picture size): 0 or a negative code, `why` says which field
+static int check_format(const xgpu_output_format *f, int bd, const char **why)
+{
+    *why = "format is NULL";
+    if (!f) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "crop offsets must be even and >= 0";
+    for (int i = 0; i < 4; i++) if (f->crop[i] < 0 || (f->crop[i] & 1)) return XGPU_ERR_INVALID_ARGUMENT;
+    if (f->layout == XGPU_OUT_YUV420P) {
+        const int obd = f->out_bit_depth ? f->out_bit_depth : bd;
+        *why = "YUV420P: out_bit_depth 8..16 with dtype U8 at 8 bit, U16 above, tight rows";
+        if (obd < 8 || obd > 16 || f->dtype != (obd == 8 ? XGPU_OUT_U8 : XGPU_OUT_U16) || f->row_pitch != 0) return XGPU_ERR_INVALID_ARGUMENT;
+        return XGPU_OK;
+    }
+    *why = "layout must be XGPU_OUT_YUV420P, _RGB_PLANAR or _RGB_INTERLEAVED";
+    if (f->layout != XGPU_OUT_RGB_PLANAR && f->layout != XGPU_OUT_RGB_INTERLEAVED) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "dtype must be one of XGPU_OUT_U8 .. XGPU_OUT_F32";
+    if (f->dtype < XGPU_OUT_U8 || f->dtype > XGPU_OUT_F32) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "RGB: out_bit_depth must be 0 or the coding depth";
+    if (f->out_bit_depth != 0 && f->out_bit_depth != bd) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "bgr, full_range: 0 or 1; chroma_loc 0..5; upsample XGPU_UPSAMPLE_NEAREST or _LINEAR; row_pitch a multiple of the element size";
+    if ((f->bgr | f->full_range) & ~1 || f->chroma_loc < 0 || f->chroma_loc > 5 || (f->upsample != XGPU_UPSAMPLE_NEAREST && f->upsample != XGPU_UPSAMPLE_LINEAR) ||
+        f->row_pitch % (size_t)elem_size(f->dtype))
+        return XGPU_ERR_INVALID_ARGUMENT;
+    double kr, kb;
+    *why = "matrix: supported MatrixCoefficients are 1, 4, 5, 6, 7 and 9";
+    if (!matrix_kr_kb(f->matrix, &kr, &kb)) return XGPU_ERR_UNSUPPORTED;
+    return XGPU_OK;
+}
+int xgpu_output_coeffs(const xgpu_output_format *f, int bit_depth, int32_t coef[5], int *shift, float fcoef[5])
+{
+    const char *why;
+    if (bit_depth < 8 || bit_depth > 12 || !coef || !shift || !fcoef) return XGPU_ERR_INVALID_ARGUMENT;
+    const int rc = check_format(f, bit_depth, &why);
+    if (rc < 0) return rc;
+    if (f->layout == XGPU_OUT_YUV420P) return XGPU_ERR_INVALID_ARGUMENT;
+    double kr, kb;
+    matrix_kr_kb(f->matrix, &kr, &kb);
+    const double kg = 1.0 - kr - kb;
+    const double yr = f->full_range ? (double)((1 << bit_depth) - 1) : (double)(219 << (bit_depth - 8));
+    const double cr = f->full_range ? (double)((1 << bit_depth) - 1) : (double)(224 << (bit_depth - 8));
+    // the same expressions, term for term, as tests/colour_ref.py (a different order of the double operations could round differently)
+    auto terms = [&](double m, double sc, double t[5]) {
+        t[0] = m / yr * sc;
+        t[1] = 2.0 * (1.0 - kr) * m / cr * sc;
+        t[2] = -(2.0 * kb * (1.0 - kb) / kg * m / cr * sc);
+        t[3] = -(2.0 * kr * (1.0 - kr) / kg * m / cr * sc);
+        t[4] = 2.0 * (1.0 - kb) * m / cr * sc;
+    };
+    double t[5];
+    terms(1.0, 1.0, t);
+    for (int i = 0; i < 5; i++) fcoef[i] = (float)t[i];
+    if (f->dtype != XGPU_OUT_U8 && f->dtype != XGPU_OUT_U16) {
+        for (int i = 0; i < 5; i++) coef[i] = 0;
+        *shift = 0;
+        return XGPU_OK;
+    }
+    const int d = f->dtype == XGPU_OUT_U8 ? 8 : bit_depth, sh = 27 - d;
+    terms((double)((1 << d) - 1), (double)(1 << sh), t);
+    for (int i = 0; i < 5; i++) coef[i] = (int32_t)round(t[i]);      // half away from zero; cgu and cgv are negated rounded magnitudes
+    *shift = sh;
+    return XGPU_OK;
+}
+static size_t device_size(const xgpu_ctx *c, const xgpu_output_format *f, const char **why)
+{
+    if (check_format(f, c->sp.bit_depth_luma, why) < 0) return 0;
+    *why = "crop leaves no picture";
+    if (!valid_output(c, 8, f->crop[0], f->crop[1], f->crop[2], f->crop[3])) return 0;
+    if (f->layout == XGPU_OUT_YUV420P)
+        return xgpu_pic_output_size(c, f->out_bit_depth ? f->out_bit_depth : c->sp.bit_depth_luma, f->crop[0], f->crop[1], f->crop[2], f->crop[3]);
+    const size_t w = c->sp.width - f->crop[0] - f->crop[1], h = c->sp.height - f->crop[2] - f->crop[3], es = elem_size(f->dtype);
+    const size_t row = f->layout == XGPU_OUT_RGB_PLANAR ? w * es : 3 * w * es;
+    const size_t pitch = f->row_pitch ? f->row_pitch : row;
+    *why = "row_pitch is shorter than a row";
+    if (pitch < row) return 0;
+    return (f->layout == XGPU_OUT_RGB_PLANAR ? 3 * h - 1 : h - 1) * pitch + row;      // the last row need not be followed by a pitch's worth of bytes
+}
+size_t xgpu_pic_output_device_size(const xgpu_ctx *c, const xgpu_output_format *f)
+{
+    const char *why;
+    return c ? device_size(c, f, &why) : 0;
+}
+int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, void *d_dst, size_t dst_size, void *stream)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    const char *why = "";
+    const size_t need = device_size(c, f, &why);
+    if (need == 0) {
+        snprintf(c->err, sizeof(c->err), "pic_output_device: invalid format: %s", why);
+        return f && f->layout != XGPU_OUT_YUV420P && check_format(f, c->sp.bit_depth_luma, &why) == XGPU_ERR_UNSUPPORTED ? XGPU_ERR_UNSUPPORTED : XGPU_ERR_INVALID_ARGUMENT;
+    }
+    const size_t es = f->layout == XGPU_OUT_YUV420P ? 1 : (size_t)elem_size(f->dtype);
+    if (dst_size < need || ((uintptr_t)d_dst % es)) {
+        snprintf(c->err, sizeof(c->err), "pic_output_device: destination of %zu bytes at %p, the format needs %zu bytes aligned to %zu", dst_size, d_dst, need, es);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    HIPCHK(c, hipSetDevice(c->sp.device));
+    // the destination must be device memory of this context's device, and the allocation must hold `need` bytes from d_dst on
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    const hipError_t pe = hipPointerGetAttributes(&at, d_dst);
+    if (pe != hipSuccess) (void)hipGetLastError();      // an unknown (host) pointer: not an error of the runtime's state
+    void *base = NULL;
+    size_t range = 0;
+    const bool dev = pe == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->sp.device;
+    if (dev && hipMemGetAddressRange(&base, &range, d_dst) != hipSuccess) { (void)hipGetLastError(); base = NULL; }
+    if (!dev || !base || (uint8_t *)d_dst + need > (uint8_t *)base + range) {
+        snprintf(c->err, sizeof(c->err), "pic_output_device: %p is not %zu bytes of device memory on device %d", d_dst, need, c->sp.device);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    if (dra) { const int rc = upload_dra(c, dra); if (rc < 0) return rc; }
+    hipStream_t s = c->stream;
+    if (stream) {
+        for (int i = 0; i < 2; i++)
+            if (!c->odev_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->odev_ev[i], hipEventDisableTiming));
+        s = (hipStream_t)stream;
+        HIPCHK(c, hipEventRecord(c->odev_ev[0], c->stream));      // the picture's kernels (and the DRA tables) -> the caller's stream
+        HIPCHK(c, hipStreamWaitEvent(s, c->odev_ev[0], 0));
+    }
+    const int *cr = f->crop;
+    const DevPic &p = dpic(c, pic);
+    if (f->layout == XGPU_OUT_YUV420P) {
+        launch_output(c, p, dra ? c->d_dra : NULL, f->out_bit_depth ? f->out_bit_depth : c->sp.bit_depth_luma, cr[0], cr[1], cr[2], cr[3], (uint8_t *)d_dst, false, s);
+    } else {
+        RgbOutArgs a;
+        memset(&a, 0, sizeof(a));
+        const int bd = c->sp.bit_depth_luma;
+        a.y = p.y + (size_t)cr[2] * p.s_l + cr[0];
+        a.u = p.u + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1);
+        a.v = p.v + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1);
+        a.sy = p.s_l; a.sc = p.s_c;
+        a.w = c->sp.width - cr[0] - cr[1]; a.h = c->sp.height - cr[2] - cr[3];
+        a.cw = a.w >> 1; a.ch = a.h >> 1;
+        a.dst = (uint8_t *)d_dst;
+        a.pitch = f->row_pitch ? f->row_pitch : (size_t)a.w * es * (f->layout == XGPU_OUT_RGB_PLANAR ? 1 : 3);
+        a.plane = a.pitch * a.h;
+        a.aligned = (((uintptr_t)d_dst | a.pitch | a.plane) & 15) == 0;
+        a.bgr = f->bgr;
+        (void)xgpu_output_coeffs(f, bd, a.coef, &a.shift, a.fcoef);
+        a.yo = f->full_range ? 0 : 16 << (bd - 8);
+        a.co = 1 << (bd - 1);
+        a.maxv = f->dtype == XGPU_OUT_U8 ? 255 : (1 << bd) - 1;
+        // ChromaSampleLocType: horizontally co-sited (0, 2, 4) / centred (1, 3, 5); vertically centred (0, 1), top (2, 3), bottom (4, 5)
+        static const int ve[3][2] = { { 1, 3 }, { 0, 4 }, { 2, 2 } }, vo[3][2] = { { 3, 1 }, { 2, 2 }, { 4, 0 } };
+        a.hc = f->chroma_loc & 1;
+        a.ve[0] = ve[f->chroma_loc >> 1][0]; a.ve[1] = ve[f->chroma_loc >> 1][1];
+        a.vo[0] = vo[f->chroma_loc >> 1][0]; a.vo[1] = vo[f->chroma_loc >> 1][1];
+        a.dra = dra ? c->d_dra : NULL;
+        launch_output_rgb(a, f->layout, f->dtype, f->upsample, s);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (stream) {
+        HIPCHK(c, hipEventRecord(c->odev_ev[1], s));      // the context's stream does not touch the slot or the DRA tables before the kernel is done
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->odev_ev[1], 0));
+    }
+    return XGPU_OK;
 }
 
 // The picture signature on the device (k_md5.hip): the planes packed as the signature's message behind the picture's kernels (k_output, samples as they are), the three

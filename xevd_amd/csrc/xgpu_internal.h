@@ -341,6 +341,7 @@ struct xgpu_ctx {
     hipEvent_t      out_ready[2], out_done[2];      // conversion kernel finished (kernel stream) / copy to the host finished (download stream)
     int             out_busy[2], out_next;
     int32_t        *d_dra;            // [3][1024] DRA inverse tables of the current output call
+    hipEvent_t      odev_ev[2];       // xgpu_pic_output_device on a caller's stream: picture ready on the context stream / the caller's kernel done (created at the first call)
     xgpu_frame_params fp;
     int             have_frame;
     TileMask        no_dbk;            // tile borders the deblocking of the current picture leaves alone (set by xgpu_batch_recon)
@@ -425,7 +426,25 @@ void launch_addb_fused(xgpu_ctx *c, const AddbArgs &a, const DevPic &src, const 
 void launch_alf(xgpu_ctx *c, const AlfArgs &a, const AddbArgs *deblock, const DevPic &src, const DevPic &dst);      // deblock != NULL: ADDB on SRC first, inside the same kernel
 void launch_pad(xgpu_ctx *c, const DevPic &p);
 void launch_copy_bw(xgpu_ctx *c, const void *src, void *dst, size_t bytes);
-void launch_output(xgpu_ctx *c, const DevPic &pic, const int32_t *d_dra, int out_bd, int crop_l, int crop_r, int crop_t, int crop_b, uint8_t *d_dst, bool raw16 = false);
+void launch_output(xgpu_ctx *c, const DevPic &pic, const int32_t *d_dra, int out_bd, int crop_l, int crop_r, int crop_t, int crop_b, uint8_t *d_dst, bool raw16 = false,
+                   hipStream_t s = nullptr);      // s = NULL: the context's stream
+// k_output_rgb.hip: the cropped picture as R'G'B' (xgpu_pic_output_device).  Everything the kernel needs, resolved on the host by xgpu_api.hip.
+struct RgbOutArgs {
+    const int16_t *y, *u, *v;       // first sample of the cropped area of every plane
+    int      sy, sc;                // plane strides in samples
+    int      w, h, cw, ch;          // cropped luma / chroma size
+    uint8_t *dst;
+    size_t   pitch, plane;          // bytes between rows / between the planes of the planar layout
+    int      aligned;               // dst, pitch and plane are multiples of 16 bytes: vector stores
+    int      bgr;
+    int      coef[5], shift;        // cy, crv, cgu, cgv, cbu and S of the integer outputs
+    float    fcoef[5];              // the same for the float outputs (2^D - 1 = 1)
+    int      yo, co, maxv;          // luma offset (16 << (B-8) or 0), chroma offset 2^(B-1), 2^D - 1
+    int      hc;                    // LINEAR: 1 = chroma horizontally between luma columns (ChromaSampleLocType 1, 3, 5)
+    int      ve[2], vo[2];          // LINEAR: vertical quarter weights of rows (i-1, i) for even luma rows, of (i, i+1) for odd ones
+    const int32_t *dra;             // [3][1024] DRA inverse tables, or NULL
+};
+void launch_output_rgb(const RgbOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 void launch_md5(xgpu_ctx *c, hipStream_t s, const uint8_t *d_msg, int w, int h, uint32_t *d_digest);      // k_md5.hip: the three planes packed back to back at d_msg -> d_digest[3][4]
 void launch_test_mc(xgpu_ctx *c, const int16_t *plane, int stride, int ref_x, int ref_y, int has_dx, int has_dy,
                     int gmv_x, int gmv_y, int16_t *pred, int w, int h, int bd, int luma);

@@ -96,6 +96,84 @@ class XgpuDecoder:
         self._chk(self.lib.xgpu_pic_output(self.ctx, pic, dl, bd, *crop, out.ctypes.data, n), "xgpu_pic_output")
         return out
 
+    @staticmethod
+    def _dra_luts(dra):
+        """(luma, cb, cr) inverse tables -> (byref(xgpu_dra_luts) or None, keepalive)"""
+        if dra is None:
+            return None, None
+        keep = [np.ascontiguousarray(t, np.int32) for t in dra]
+        assert all(t.size == 1024 for t in keep)
+        d = abi.DraLuts()
+        d.luma_inv_scale_lut = keep[0].ctypes.data
+        d.chroma_inv_scale_lut[0], d.chroma_inv_scale_lut[1] = keep[1].ctypes.data, keep[2].ctypes.data
+        return C.byref(d), (keep, d)
+
+    def pic_output_tensor(self, pic, layout="rgb", channels_last=False, dtype=None, matrix=1, full_range=False, chroma_loc=0, upsample="linear",
+                          crop=(0, 0, 0, 0), dra=None, out=None, bgr=False):
+        """The picture in device memory as a torch tensor on cuda:{device}, converted on the device (xgpu_pic_output_device) on torch's current
+        stream - no host round trip.  layout "rgb": [3, H, W] (channels_last: [H, W, 3]) R'G'B' (bgr: B, G, R) with dtype torch.uint8, torch.int16 /
+        torch.uint16 (values at the coding depth), torch.float16, torch.bfloat16 or torch.float32 (0..1), through `matrix` (H.273 MatrixCoefficients
+        1, 4, 5, 6, 7, 9), full_range, chroma_loc (ChromaSampleLocType 0..5) and upsample "linear" / "nearest"; layout "yuv420p": the bytes of
+        pic_output (1-D, uint8 for 8-bit output - dtype torch.uint8 - else 16-bit samples at the coding depth).  crop: (left, right, top, bottom), even.
+        out: a tensor to fill instead (its strides may pad the rows: row_pitch); it is also what is returned."""
+        import torch
+        dtype = torch.uint8 if dtype is None else dtype
+        codes = {torch.uint8: abi.OUT_U8, torch.int16: abi.OUT_U16, torch.float16: abi.OUT_F16, torch.bfloat16: abi.OUT_BF16, torch.float32: abi.OUT_F32}
+        if getattr(torch, "uint16", None) is not None:
+            codes[torch.uint16] = abi.OUT_U16
+        if dtype not in codes:
+            raise ValueError(f"unsupported output dtype {dtype}")
+        if upsample not in ("linear", "nearest"):
+            raise ValueError(f"upsample must be 'linear' or 'nearest', not {upsample!r}")
+        cl, cr, ct, cb = (int(v) for v in crop)
+        w, h = self.width - cl - cr, self.height - ct - cb
+        dev = torch.device("cuda", self.sp.device)
+        if layout == "yuv420p":
+            if codes[dtype] not in (abi.OUT_U8, abi.OUT_U16):
+                raise ValueError("yuv420p: dtype torch.uint8 (8-bit output) or a 16-bit integer type (the coding depth)")
+            fmt = abi.make_output_format(abi.OUT_YUV420P, codes[dtype], out_bit_depth=8 if codes[dtype] == abi.OUT_U8 else self.bit_depth, crop=crop)
+            n = self.lib.xgpu_pic_output_device_size(self.ctx, C.byref(fmt))
+            if n == 0:
+                raise ValueError(f"invalid output format: crop {crop}")
+            shape, strides = (n // dtype.itemsize,), (1,)
+        elif layout == "rgb":
+            shape = (h, w, 3) if channels_last else (3, h, w)
+            fmt = abi.make_output_format(abi.OUT_RGB_INTERLEAVED if channels_last else abi.OUT_RGB_PLANAR, codes[dtype], bgr=bgr, matrix=matrix, full_range=full_range,
+                                         chroma_loc=chroma_loc, upsample=abi.UPSAMPLE_LINEAR if upsample == "linear" else abi.UPSAMPLE_NEAREST, crop=crop)
+            strides = None
+        else:
+            raise ValueError(f"layout must be 'rgb' or 'yuv420p', not {layout!r}")
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
+            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+        st = out.stride()
+        if layout == "rgb":
+            pitch = st[0] if channels_last else st[1]          # elements between rows
+            if (channels_last and st[1:] != (3, 1)) or (not channels_last and (st[2] != 1 or st[0] != pitch * h)) or pitch < (3 * w if channels_last else w):
+                raise ValueError(f"out: strides {st} are not rows of {'W x 3' if channels_last else 'W'} elements {'' if channels_last else 'in planes of H rows '}")
+            fmt.row_pitch = pitch * dtype.itemsize
+        elif st != strides:
+            raise ValueError("out: must be contiguous")
+        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
+        if self.lib.xgpu_pic_output_device_size(self.ctx, C.byref(fmt)) == 0:
+            raise ValueError(f"invalid output format (matrix {matrix}, chroma_loc {chroma_loc}, crop {crop})")
+        nbytes = (sum((n - 1) * s for n, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
+        cur = torch.cuda.current_stream(dev)
+        run = cur
+        if cur.cuda_stream == 0:
+            # torch's default stream is the null stream, whose handle (0) means "the context's stream" to the C ABI: run on a side stream of torch's
+            # between two stream waits instead - the same order for everything queued on the default stream
+            if getattr(self, "_side", None) is None:
+                self._side = torch.cuda.Stream(device=dev)
+            run = self._side
+            run.wait_stream(cur)
+        self._chk(self.lib.xgpu_pic_output_device(self.ctx, pic, dl, C.byref(fmt), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
+                  "xgpu_pic_output_device")
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
     def pic_md5(self, pic, dra=None):
         """the picture signature made on the device (xgpu_pic_md5): [Y, U, V] digests of 16 bytes - the MD5 of every plane's 16-bit samples as the reference's
         xevd_md5_imgb makes it; with `dra` tables (as pic_output takes them) of the DRA-mapped picture"""

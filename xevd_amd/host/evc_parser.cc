@@ -244,6 +244,42 @@ struct xhost_parser {
         pos += 4 + len;
     }
 
+    // hrd_parameters (xevd_eco_hrd_parameters, xevd_eco.c:1211-1226): stepped over
+    static bool skip_hrd(BitReader &br)
+    {
+        const uint32_t cpb_cnt = br.ue() + 1;
+        if (br.overrun || cpb_cnt > 32) return false;
+        br.get(8);                                       // bit_rate_scale, cpb_size_scale
+        for (uint32_t i = 0; i < cpb_cnt; i++) { br.ue(); br.ue(); br.get1(); }      // bit_rate_value_minus1, cpb_size_value_minus1, cbr_flag
+        br.get(20);                                      // initial_cpb_removal_delay_length_minus1, cpb_removal_delay_length_minus1 (read twice), time_offset_length
+        return !br.overrun;
+    }
+    // vui_parameters (xevd_eco_vui, xevd_eco.c:1229-1304): every element is read, the colour description is kept
+    static bool parse_vui(BitReader &br, Sps &s)
+    {
+        if (br.get1() && br.get(8) == 255) br.get(32);   // aspect_ratio_info_present_flag, aspect_ratio_idc; EXTENDED_SAR: sar_width, sar_height (16 bits each)
+        if (br.get1()) br.get1();                        // overscan_info_present_flag, overscan_appropriate_flag
+        if (br.get1()) {                                 // video_signal_type_present_flag
+            br.get(3);                                   // video_format
+            s.full_range = br.get1();
+            if (br.get1()) { s.colour_primaries = (int)br.get(8); s.transfer = (int)br.get(8); s.matrix = (int)br.get(8); }      // colour_description_present_flag
+        }
+        if (br.get1()) {                                 // chroma_loc_info_present_flag
+            const uint32_t top = br.ue(), bottom = br.ue();
+            if (top > 5 || bottom > 5) return false;
+            s.chroma_loc = (int)top;
+        }
+        br.get1(); br.get1();                            // neutral_chroma_indication_flag, field_seq_flag
+        if (br.get1()) { br.get(32); br.get(32); br.get1(); }      // timing_info_present_flag: num_units_in_tick, time_scale, fixed_pic_rate_flag
+        const int nal_hrd = br.get1();
+        if (nal_hrd && !skip_hrd(br)) return false;
+        const int vcl_hrd = br.get1();
+        if (vcl_hrd && !skip_hrd(br)) return false;
+        if (nal_hrd || vcl_hrd) br.get1();               // low_delay_hrd_flag
+        br.get1();                                       // pic_struct_present_flag
+        if (br.get1()) { br.get1(); for (int i = 0; i < 6; i++) br.ue(); }      // bitstream_restriction_flag: motion_vectors_over_pic_boundaries_flag + six ue(v)
+        return !br.overrun;
+    }
     int parse_sps(BitReader &br)
     {
         Sps tmp = st.sps;                                // parsed into a copy and committed on success only: a damaged SPS leaves the active one intact
@@ -348,7 +384,9 @@ struct xhost_parser {
             }
             if (same) memcpy(s.cq[1], s.cq[0], sizeof(s.cq[0]));
         }
-        br.get1();      // vui_parameters_present_flag: the VUI (display metadata, xevd_eco.c:1226-1304) is the last SPS element and is not needed here
+        s.vui_present = br.get1();                       // vui_parameters_present_flag: the VUI is the last SPS element
+        s.full_range = 0; s.colour_primaries = s.transfer = s.matrix = 2; s.chroma_loc = 0;
+        if (s.vui_present && !parse_vui(br, s)) return fail("bad SPS: VUI");
         if (br.overrun || (s.width & 7) || (s.height & 7) || s.width <= 0 || s.height <= 0 || s.width > 16384 || s.height > 16384 ||
             s.bd_l < 8 || s.bd_l > 12 || s.bd_c < 8 || s.bd_c > 12 || s.max_num_ref_pics < 0 || s.max_num_ref_pics > XGPU_MAX_REFS) return fail("bad SPS");
         // a new geometry / bit depth invalidates every stored picture (their motion fields have the old SCU grid): drop the DPB and take
@@ -640,6 +678,9 @@ struct xhost_parser {
             for (int c = 0; c < 3; c++) out->dra_lut[c] = hd.dra.data() + 1024 * c;
         }
         for (int i = 0; i < 4; i++) out->crop[i] = st.sps.crop[i];
+        out->vui_present = st.sps.vui_present; out->video_full_range_flag = st.sps.full_range;
+        out->colour_primaries = st.sps.colour_primaries; out->transfer_characteristics = st.sps.transfer; out->matrix_coefficients = st.sps.matrix;
+        out->chroma_sample_loc_type = st.sps.chroma_loc;
         out->chroma_qp_table[0] = st.sps.cqt ? st.sps.cq[0] : nullptr; out->chroma_qp_table[1] = st.sps.cqt ? st.sps.cq[1] : nullptr;
         if (sh.alf_on) {
             if (!st.alf_finalise()) return fail("slice refers to an ALF parameter set that was not sent");

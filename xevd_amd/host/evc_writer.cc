@@ -62,9 +62,45 @@ struct xhost_writer {
                 for (int j = 0; j < sp.cqt_num_points[c]; j++) { bw.put((uint32_t)sp.cqt_delta_in[c][j], 6); bw.se(sp.cqt_delta_out[c][j]); }
             }
         }
-        bw.put1(0);                                      // no VUI
+        const bool signal = sp.vui_signal_type || sp.vui_colour_desc;
+        const bool vui = signal || sp.vui_chroma_loc || sp.vui_extra;
+        bw.put1(vui ? 1 : 0);                            // vui_parameters_present_flag
+        if (vui) write_vui(bw, signal);
         bw.align_zero();
         write_nal(out, NUT_SPS, 0, bw);
+    }
+    // vui_parameters (xevd_eco_vui, xevd_eco.c:1229-1304); with vui_extra every optional block a parser has to step over is present
+    void write_vui(BitWriter &bw, bool signal)
+    {
+        const bool x = sp.vui_extra != 0;
+        bw.put1(x);                                      // aspect_ratio_info_present_flag
+        if (x) { bw.put(255, 8); bw.put(0xA5C3, 16); bw.put(0x0001, 16); }      // EXTENDED_SAR, sar_width, sar_height
+        bw.put1(x);                                      // overscan_info_present_flag
+        if (x) bw.put1(1);                               // overscan_appropriate_flag
+        bw.put1(signal);                                 // video_signal_type_present_flag
+        if (signal) {
+            bw.put(5, 3);                                // video_format: unspecified
+            bw.put1(sp.vui_full_range ? 1 : 0);
+            bw.put1(sp.vui_colour_desc ? 1 : 0);
+            if (sp.vui_colour_desc) { bw.put((uint32_t)sp.vui_colour_primaries & 255, 8); bw.put((uint32_t)sp.vui_transfer_characteristics & 255, 8); bw.put((uint32_t)sp.vui_matrix_coefficients & 255, 8); }
+        }
+        bw.put1(sp.vui_chroma_loc ? 1 : 0);              // chroma_loc_info_present_flag
+        if (sp.vui_chroma_loc) { bw.ue((uint32_t)sp.vui_chroma_loc_top); bw.ue((uint32_t)sp.vui_chroma_loc_bottom); }
+        bw.put1(0);                                      // neutral_chroma_indication_flag
+        bw.put1(0);                                      // field_seq_flag
+        bw.put1(x);                                      // timing_info_present_flag
+        if (x) { bw.put(1001, 32); bw.put(0xEA600000u, 32); bw.put1(1); }      // num_units_in_tick, time_scale, fixed_pic_rate_flag
+        bw.put1(x);                                      // nal_hrd_parameters_present_flag
+        if (x) {                                         // hrd_parameters (xevd_eco.c:1211-1226) with two CPB specifications
+            bw.ue(1); bw.put(3, 4); bw.put(5, 4);        // cpb_cnt_minus1, bit_rate_scale, cpb_size_scale
+            for (int i = 0; i < 2; i++) { bw.ue(1000u * (i + 1) + 7); bw.ue(4000u * (i + 1)); bw.put1(i); }      // bit_rate_value_minus1, cpb_size_value_minus1, cbr_flag
+            bw.put(23, 5); bw.put(23, 5); bw.put(23, 5); bw.put(24, 5);      // the four 5-bit length fields
+        }
+        bw.put1(0);                                      // vcl_hrd_parameters_present_flag
+        if (x) bw.put1(1);                               // low_delay_hrd_flag
+        bw.put1(x);                                      // pic_struct_present_flag
+        bw.put1(x);                                      // bitstream_restriction_flag
+        if (x) { bw.put1(1); bw.ue(2); bw.ue(1); bw.ue(15); bw.ue(15); bw.ue(0); bw.ue(3); }      // motion_vectors_over_pic_boundaries .. max_dec_pic_buffering
     }
     void write_pps()
     {

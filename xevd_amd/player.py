@@ -61,9 +61,25 @@ class StreamDecoder:
         import numpy as np
         return all(hashlib.md5(np.ascontiguousarray(pl, "<i2").tobytes()).digest() == p["md5"][c] for c, pl in enumerate(planes))
 
-    def pictures(self, download=True, output_bit_depth=None):
+    @classmethod
+    def tensor_options(cls, p, options):
+        """the keyword arguments of XgpuDecoder.pic_output_tensor for picture p: matrix, range and chroma siting from the stream's VUI (a VUI that leaves
+        them unspecified, or none: BT.709, limited range, type 0), the conformance-window crop and DRA tables of the picture - `options` override all"""
+        col = p["colour"]
+        kw = {"matrix": 1, "full_range": False, "chroma_loc": 0, "dra": p["dra"]}
+        if col["vui_present"]:
+            kw["full_range"] = bool(col["full_range"])
+            kw["chroma_loc"] = col["chroma_sample_loc_type"]
+            if col["matrix_coefficients"] != 2:      # 2 = unspecified
+                kw["matrix"] = col["matrix_coefficients"]
+        kw.update(options)
+        return kw
+
+    def pictures(self, download=True, output_bit_depth=None, tensor=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
-        output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device"""
+        output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
+        tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
+        current stream, by default with the colour description of the stream's VUI (tensor_options) and the SPS crop when apply_crop is set"""
         q = queue.Queue(maxsize=self.prefetch)
         th = threading.Thread(target=self._producer, args=(q,), daemon=True)
         th.start()
@@ -86,7 +102,12 @@ class StreamDecoder:
                     p["_luma"][0].set()
                 dec.batch_destroy(hb)          # back to the pool; queued kernels keep reading it (same HIP stream)
             planes = None
-            if download and output_bit_depth is not None:
+            if tensor is not None:
+                kw = self.tensor_options(p, tensor)
+                kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
+                with self._lock:
+                    planes = dec.pic_output_tensor(cur, **kw)
+            elif download and output_bit_depth is not None:
                 planes = dec.pic_output(cur, output_bit_depth, p["crop"] if self.apply_crop else (0, 0, 0, 0), dra=p["dra"])
             elif download and p["dra"] is not None:      # the DRA post-filter belongs to the output: planes through the output kernel
                 import numpy as np

@@ -23,7 +23,10 @@ class StreamParams(C.Structure):
                 ("tile_cols", C.c_int), ("tile_rows", C.c_int), ("tile_col_w", C.c_int * abi.XGPU_MAX_TILE_COLS), ("tile_row_h", C.c_int * abi.XGPU_MAX_TILE_ROWS),
                 ("loop_filter_across_tiles", C.c_int), ("tool_affine", C.c_int), ("cu_qp_delta_area", C.c_int), ("tool_rpl", C.c_int), ("tool_pocs", C.c_int), ("tool_cm_init", C.c_int), ("tool_adcc", C.c_int),
                 ("btt", C.c_int), ("btt_log2_min_cb", C.c_int), ("btt_diff_max_14", C.c_int), ("btt_diff_max_tt", C.c_int), ("btt_diff_min_tt", C.c_int), ("rpl_in_sps", C.c_int),
-                ("suco", C.c_int), ("suco_diff_max", C.c_int), ("suco_diff_min", C.c_int)]
+                ("suco", C.c_int), ("suco_diff_max", C.c_int), ("suco_diff_min", C.c_int),
+                ("vui_signal_type", C.c_int), ("vui_full_range", C.c_int), ("vui_colour_desc", C.c_int), ("vui_colour_primaries", C.c_int),
+                ("vui_transfer_characteristics", C.c_int), ("vui_matrix_coefficients", C.c_int), ("vui_chroma_loc", C.c_int), ("vui_chroma_loc_top", C.c_int),
+                ("vui_chroma_loc_bottom", C.c_int), ("vui_extra", C.c_int)]
 
 
 class AlfAps(C.Structure):
@@ -58,7 +61,9 @@ class HostPicture(C.Structure):
                 ("dra_lut", C.POINTER(C.c_int32) * 3),
                 ("alf_on", C.c_int), ("alf", abi.AlfParams),
                 ("has_md5", C.c_int), ("md5", (C.c_uint8 * 16) * 3),
-                ("n_dmvr_sub", C.c_int), ("needs_ref_luma", C.c_int), ("n_release", C.c_int), ("release_poc", C.c_int * 32), ("batch", abi.CuBatch)]
+                ("n_dmvr_sub", C.c_int), ("needs_ref_luma", C.c_int), ("n_release", C.c_int), ("release_poc", C.c_int * 32), ("batch", abi.CuBatch),
+                ("vui_present", C.c_int), ("video_full_range_flag", C.c_int), ("colour_primaries", C.c_int), ("transfer_characteristics", C.c_int),
+                ("matrix_coefficients", C.c_int), ("chroma_sample_loc_type", C.c_int)]
 
 
 _lib = None
@@ -103,8 +108,10 @@ class StreamWriter:
     def __init__(self, width, height, bit_depth=8, max_num_ref_pics=1, qp_u_offset=0, qp_v_offset=0, deblock=True, cu_qp_delta=True,
                  log2_sub_gop=0, main=False, iqt=False, ats=False, addb=False, alpha_off=0, beta_off=0, alf=False, eipd=False, crop=(0, 0, 0, 0),
                  chroma_qp_points=None, dra_aps_id=None, htdf=False, ibc_log_max=0, admvp=False, amvr=False, hmvp=False, dmvr=False, mmvd=False,
-                 tiles=None, affine=False, qp_delta_area=0, rpl=False, pocs=False, rpl_in_sps=False, cm_init=False, adcc=False, btt=None, suco=None):
-        """chroma_qp_points: None, or (global_offset_flag, [table, ...]) with 1 (same for Cb and Cr) or 2 tables of (delta_in_minus1, delta_out) pairs"""
+                 tiles=None, affine=False, qp_delta_area=0, rpl=False, pocs=False, rpl_in_sps=False, cm_init=False, adcc=False, btt=None, suco=None, vui=None):
+        """chroma_qp_points: None, or (global_offset_flag, [table, ...]) with 1 (same for Cb and Cr) or 2 tables of (delta_in_minus1, delta_out) pairs.
+        vui: None (no VUI), or a dict with any of full_range (bool: writes the video signal type), colour=(primaries, transfer, matrix),
+        chroma_loc=(top, bottom), extra (bool: SAR, timing, an HRD set and a bitstream-restriction block around them)"""
         self.lib = load()
         sp = StreamParams(width, height, bit_depth, max_num_ref_pics, log2_sub_gop, qp_u_offset, qp_v_offset, int(deblock), int(cu_qp_delta),
                           int(main), int(iqt), int(ats), int(addb), alpha_off, beta_off, int(alf), int(eipd))
@@ -129,6 +136,16 @@ class StreamWriter:
             sp.btt, sp.btt_log2_min_cb, sp.btt_diff_max_14, sp.btt_diff_max_tt, sp.btt_diff_min_tt = 1, int(btt[0]), int(btt[1]), int(btt[2]), int(btt[3])
         if suco is not None:     # (log2_diff_ctu_size_max_suco_cb_size, log2_diff_max_suco_min_suco_cb_size)
             sp.suco, sp.suco_diff_max, sp.suco_diff_min = 1, int(suco[0]), int(suco[1])
+        if vui is not None:
+            if "full_range" in vui:
+                sp.vui_signal_type, sp.vui_full_range = 1, int(bool(vui["full_range"]))
+            if vui.get("colour") is not None:
+                sp.vui_colour_desc = 1
+                sp.vui_colour_primaries, sp.vui_transfer_characteristics, sp.vui_matrix_coefficients = (int(v) for v in vui["colour"])
+            if vui.get("chroma_loc") is not None:
+                sp.vui_chroma_loc = 1
+                sp.vui_chroma_loc_top, sp.vui_chroma_loc_bottom = (int(v) for v in vui["chroma_loc"])
+            sp.vui_extra = int(bool(vui.get("extra", False)))
         if dra_aps_id is not None:
             sp.tool_dra, sp.dra_aps_id = 1, int(dra_aps_id)
         if chroma_qp_points is not None:
@@ -323,6 +340,10 @@ def iter_stream(data, consume_batch=None, threads=1, luma_wait=False):
                     "tiles": abi.tile_grid_dict(hp.alf.tiles.contents) if hp.alf.tiles else None},
                 "md5": [bytes(hp.md5[c]) for c in range(3)] if hp.has_md5 else None,
                 "release": [hp.release_poc[i] for i in range(hp.n_release)], "batch": batch,
+                # the SPS's VUI colour description (H.273 code points; 0, 0, 2, 2, 2, 0 without a VUI): what StreamDecoder.pictures(tensor=...) converts with
+                "colour": {"vui_present": bool(hp.vui_present), "full_range": int(hp.video_full_range_flag), "colour_primaries": hp.colour_primaries,
+                           "transfer_characteristics": hp.transfer_characteristics, "matrix_coefficients": hp.matrix_coefficients,
+                           "chroma_sample_loc_type": hp.chroma_sample_loc_type},
                 # sps->tool_dmvr: the number of sub-blocks whose vectors (xgpu_batch_dmvr_mvs / the oracle's dmvr_mv_out) must be handed to
                 # dmvr_feedback() before the generator is advanced - the temporal candidates of later pictures read them
                 "n_dmvr_sub": int(hp.n_dmvr_sub), "dmvr_feedback": _feedback(lib, h),
