@@ -235,10 +235,26 @@ int  xgpu_pic_output_wait(xgpu_ctx *ctx, int ticket);
    1 BT.709, 4 FCC, 5 / 6 BT.601, 7 SMPTE 240M, 9 BT.2020 non-constant luminance; others XGPU_ERR_UNSUPPORTED) and limited / full range.
    Integer outputs (U8: 8 bit, U16: the coding depth) are fixed point: coefficients round(k * (2^D - 1) / range * 2^S), S = 27 - D, channel =
    clip((sum + 2^(S-1)) >> S, 0, 2^D - 1); float outputs evaluate the same formula in float32 with 2^D - 1 = 1, clipped to [0, 1] (F16 / BF16: that
-   value rounded to nearest even).  The exact contract: INTEGRATION.md section 8. */
+   value rounded to nearest even).
+   Video surfaces (k_output_yuv.hip), for an encoder, a display path, another GPU video library, or a model that works on Y'CbCr:
+     XGPU_OUT_NV12             H rows of W luma elements, then H/2 rows of W elements Cb0 Cr0 Cb1 Cr1 ..., all rows row_pitch apart, the chroma plane at
+                               H * row_pitch.  The samples of YUV420P at the same out_bit_depth, one for one: U8 with out_bit_depth 8, or U16 with
+                               out_bit_depth 0 (the coding depth, which must be above 8) or 9..16, value in the low bits
+     XGPU_OUT_P016             as NV12, U16 only: word = (sample at depth D) << (16 - D), D = out_bit_depth (0 = the coding depth, else 8..16) -
+                               D = 10 is P010, 12 is P012
+     XGPU_OUT_YUV444_PLANAR / _INTERLEAVED   Y, Cb, Cr at luma resolution, laid out as the RGB layouts: chroma upsampled as for RGB (upsample,
+                               chroma_loc), then U8: the 8-bit rule of xgpu_pic_output; U16: the sample (out_bit_depth 0 or the coding depth); floats:
+                               H.273's E'Y = clip((Y - yo) * fy, 0, 1), E'Cb = clip((Cb - 2^(B-1)) * fc, -0.5, 0.5), E'Cr alike, fy = float32(1 / yr),
+                               fc = float32(1 / cr) with the offset and excursions of full_range
+   These four read neither matrix nor bgr (bgr must be 0); NV12 / P016 read no chroma_loc, upsample or full_range.
+   The exact contract: INTEGRATION.md section 8a. */
 #define XGPU_OUT_YUV420P          0
 #define XGPU_OUT_RGB_PLANAR       1
 #define XGPU_OUT_RGB_INTERLEAVED  2
+#define XGPU_OUT_NV12             3
+#define XGPU_OUT_P016             4
+#define XGPU_OUT_YUV444_PLANAR    5
+#define XGPU_OUT_YUV444_INTERLEAVED 6
 #define XGPU_OUT_U8               0
 #define XGPU_OUT_U16              1
 #define XGPU_OUT_F16              2
@@ -247,15 +263,19 @@ int  xgpu_pic_output_wait(xgpu_ctx *ctx, int ticket);
 #define XGPU_UPSAMPLE_NEAREST     0
 #define XGPU_UPSAMPLE_LINEAR      1
 typedef struct xgpu_output_format {
-    int layout;                /* XGPU_OUT_YUV420P | XGPU_OUT_RGB_PLANAR | XGPU_OUT_RGB_INTERLEAVED                                 */
-    int bgr;                   /* RGB layouts: channel order B, G, R                                                                 */
-    int dtype;                 /* XGPU_OUT_U8 | _U16 | _F16 | _BF16 | _F32 (YUV420P: U8 / U16 by out_bit_depth)                      */
-    int out_bit_depth;         /* YUV420P: as xgpu_pic_output (0 = the coding depth); RGB: 0 or the coding depth                      */
+    int layout;                /* XGPU_OUT_YUV420P | _RGB_PLANAR | _RGB_INTERLEAVED | _NV12 | _P016 | _YUV444_PLANAR | _YUV444_INTERLEAVED */
+    int bgr;                   /* RGB layouts: channel order B, G, R; every other layout: 0                                          */
+    int dtype;                 /* XGPU_OUT_U8 | _U16 | _F16 | _BF16 | _F32 (YUV420P, NV12: U8 / U16 by out_bit_depth; P016: U16)     */
+    int out_bit_depth;         /* YUV420P, NV12, P016: as xgpu_pic_output (0 = the coding depth); RGB, YUV444: 0 or the coding depth */
     int matrix, full_range, chroma_loc, upsample;      /* H.273 MatrixCoefficients, video_full_range_flag, ChromaSampleLocType, XGPU_UPSAMPLE_* */
     int crop[4];               /* left, right, top, bottom luma samples - even                                                        */
     size_t row_pitch;          /* bytes between rows of a plane / of the interleaved image; 0 = tight (YUV420P: must be 0)            */
 } xgpu_output_format;
-/* bytes the format needs at d_dst (the last row tight); 0: invalid format for this context */
+/* Host only, no context: the bytes format `f` needs at d_dst for a picture of width x height (the uncropped size) at coding depth bit_depth, the last
+   row tight; 0: invalid format or size.  NV12 / P016: (H + H/2 - 1) * pitch + W * es; RGB / YUV444 planar: (3H - 1) * pitch + W * es, interleaved:
+   (H - 1) * pitch + 3W * es (W, H cropped, es the element size, pitch = row_pitch or the tight row); YUV420P: xgpu_pic_output_size's. */
+size_t xgpu_output_format_size(const xgpu_output_format *f, int width, int height, int bit_depth);
+/* xgpu_output_format_size with the context's picture size and coding depth */
 size_t xgpu_pic_output_device_size(const xgpu_ctx *ctx, const xgpu_output_format *f);
 /* Non-blocking.  d_dst: device memory of the context's device, aligned to the element size, >= xgpu_pic_output_device_size bytes (checked - with
    hipPointerGetAttributes - before anything is queued: XGPU_ERR_INVALID_ARGUMENT and no launch otherwise).  stream = NULL: the context's stream;

@@ -1,4 +1,4 @@
-"""Device-output rate: an 8K 10-bit picture converted into torch tensors by xgpu_pic_output_device (k_output_rgb / k_output), timed with torch
+"""Device-output rate: an 8K 10-bit picture converted into torch tensors by xgpu_pic_output_device (k_output_rgb / k_output / k_output_semiplanar / k_output_yuv444), timed with torch
 events on the output stream (median of --iters launches after warm-up), against the plain device copy rate of the same run
 (xgpu_measure_copy_bw).  Bytes are algorithmic: 3 bytes of samples read per pixel (luma + two quarter-size chroma planes, 16 bit) and what the
 format writes.  Prints one line per form and a JSON line; --out also writes the JSON to a file.
@@ -35,7 +35,11 @@ def main():
     forms = [("rgb_u8_planar", dict(dtype=torch.uint8), 3),
              ("rgb_u8_interleaved", dict(dtype=torch.uint8, channels_last=True), 3),
              ("rgb_f16_planar", dict(dtype=torch.float16), 6),
-             ("yuv420p_u8", dict(layout="yuv420p", dtype=torch.uint8), 1.5)]
+             ("yuv420p_u8", dict(layout="yuv420p", dtype=torch.uint8), 1.5),
+             ("nv12_u8", dict(layout="nv12", dtype=torch.uint8), 1.5),
+             ("p010", dict(layout="p016", dtype=torch.int16, out_bit_depth=10), 3),
+             ("yuv444_u8_planar", dict(layout="yuv444", dtype=torch.uint8), 3),
+             ("yuv444_f16_planar", dict(layout="yuv444", dtype=torch.float16), 6)]
     res = {"width": w, "height": h, "bit_depth": bd, "iters": a.iters, "forms": {}}
     with XgpuDecoder(w, h, bd, device=0, max_pics=2) as dec:
         pic = dec.pic_alloc()

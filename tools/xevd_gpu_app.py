@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Decode an MPEG-5 EVC Baseline bitstream on the MI355X and write planar YUV - the counterpart of the reference's sample
-application (app/xevd_app.c: -i in.evc -o out.yuv --output-bit-depth N).  usage: xevd_gpu_app.py -i in.evc -o out.yuv"""
+application (app/xevd_app.c: -i in.evc -o out.yuv --output-bit-depth N).  usage: xevd_gpu_app.py -i in.evc -o out.yuv
+--pix-fmt nv12 / p010 writes semi-planar frames instead (what a raw-video reader takes as nv12 / p010le): 8-bit samples, or 10-bit samples in the
+high bits of 16-bit words, whatever the stream's depth."""
 import argparse
 import os
 import sys
@@ -15,12 +17,19 @@ def main():
     ap.add_argument("-i", "--input", required=True)
     ap.add_argument("-o", "--output")
     ap.add_argument("--output-bit-depth", type=int, default=0, help="0 = the stream's bit depth (8 -> bytes, else 16-bit little endian)")
+    ap.add_argument("--pix-fmt", choices=("yuv420p", "nv12", "p010"), default="yuv420p",
+                    help="nv12: 8-bit semi-planar; p010: 10 bit in 16-bit little-endian words, semi-planar (both ignore --output-bit-depth)")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
     data = open(args.input, "rb").read()
     t0 = time.perf_counter()
     # crop-free output like the reference application; bit-depth conversion and plane packing run on the device (xgpu_pic_output)
-    pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth)
+    if args.pix_fmt == "yuv420p":
+        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth)
+    else:      # the same pictures as semi-planar surfaces (xgpu_pic_output_device into a torch tensor, copied to the host picture by picture)
+        import torch
+        opts = dict(layout="nv12", dtype=torch.uint8) if args.pix_fmt == "nv12" else dict(layout="p016", dtype=torch.int16, out_bit_depth=10)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts)
     dt = time.perf_counter() - t0
     if args.output:
         with open(args.output, "wb") as f:

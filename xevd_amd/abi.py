@@ -34,6 +34,7 @@ class DraLuts(C.Structure):
 
 
 OUT_YUV420P, OUT_RGB_PLANAR, OUT_RGB_INTERLEAVED = 0, 1, 2
+OUT_NV12, OUT_P016, OUT_YUV444_PLANAR, OUT_YUV444_INTERLEAVED = 3, 4, 5, 6
 OUT_U8, OUT_U16, OUT_F16, OUT_BF16, OUT_F32 = 0, 1, 2, 3, 4
 UPSAMPLE_NEAREST, UPSAMPLE_LINEAR = 0, 1
 
@@ -213,6 +214,7 @@ _EXPORTS = {
     "xgpu_pic_output_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "xgpu_pic_output_wait": (C.c_int, [C.c_void_p, C.c_int]),
     "xgpu_pic_md5": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "xgpu_output_format_size": (C.c_size_t, [C.POINTER(OutputFormat), C.c_int, C.c_int, C.c_int]),
     "xgpu_pic_output_device_size": (C.c_size_t, [C.c_void_p, C.POINTER(OutputFormat)]),
     "xgpu_pic_output_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_output_coeffs": (C.c_int, [C.POINTER(OutputFormat), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float)]),

@@ -13,7 +13,7 @@
 //
 // One workgroup per output row and plane (like k_pad); a thread converts 4 neighbouring samples per step: 8-byte reads at the
 // 2-byte-aligned crop position (gfx950 runs in unaligned-access mode), 4- or 8-byte writes.  HBM-bound, no reuse.
-#include "xgpu_internal.h"
+#include "output_common.h"
 
 struct __attribute__((packed, aligned(2))) S16x4u { int16_t a, b, c, d; };
 struct __attribute__((packed, aligned(1))) U8x4u  { uint8_t a, b, c, d; };
@@ -30,23 +30,6 @@ struct OutArgs {
     int      maxv;
     const int32_t *dra;             // [3][1024] luma / Cb / Cr inverse tables, or NULL
 };
-
-__device__ __forceinline__ int conv1(int v, int shift, int maxv, int out8)
-{
-    if (out8) return min(max((v + (shift ? 1 << (shift - 1) : 0)) >> shift, 0), 255);            // signed samples (:464-494)
-    if (shift > 0) return min(((int)(uint16_t)v + (1 << (shift - 1))) >> shift, maxv);            // unsigned samples (:519-552)
-    return shift < 0 ? (int)(uint16_t)(v << -shift) : v;
-}
-
-// v: the plane's sample; luma: the unmapped luma sample at (2y, 2x) for a chroma plane
-__device__ __forceinline__ int dra1(const int32_t *lut, int c, int v, int luma)
-{
-    if (c == 0) return (int)(int16_t)lut[min(max(v, 0), 1023)];
-    const int sv = v - 512;
-    int off = (abs(sv) * lut[c * 1024 + min(max(luma, 0), 1023)] + (1 << 8)) >> 9;
-    if (sv < 0) off = -off;
-    return (int)(int16_t)(512 + off);
-}
 
 __global__ __launch_bounds__(256) void k_output(const OutArgs p)
 {

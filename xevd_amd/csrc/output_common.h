@@ -1,0 +1,191 @@
+// output_common.h - what the output kernels share (k_output.hip, k_output_rgb.hip, k_output_yuv.hip): the per-sample depth conversion and DRA
+// mapping, the edge-clamped chroma loads and the 4:2:0 -> luma-resolution upsampling of the device-output contract (INTEGRATION.md section 8a,
+// step 2), the element types and the vector / element stores.  One version of each: a layout that is "the same samples, another place" runs
+// the same code.
+#pragma once
+#include "xgpu_internal.h"
+#include <hip/hip_fp16.h>
+
+struct __attribute__((packed, aligned(2))) S16x8u { int16_t v[8]; };
+
+// xgpu_pic_output's depth conversion (imgb_cpy_codec_to_out, app/xevd_app_util.h:465-552): to 8 bit a rounding shift of the signed sample
+// clipped to [0, 255]; to a lower depth the same on the unsigned sample clipped to maxv; to a higher depth a left shift; else a copy
+__device__ __forceinline__ int conv1(int v, int shift, int maxv, int out8)
+{
+    if (out8) return min(max((v + (shift ? 1 << (shift - 1) : 0)) >> shift, 0), 255);            // signed samples (:464-494)
+    if (shift > 0) return min(((int)(uint16_t)v + (1 << (shift - 1))) >> shift, maxv);            // unsigned samples (:519-552)
+    return shift < 0 ? (int)(uint16_t)(v << -shift) : v;
+}
+
+// DRA of one sample (xevdm_dra.c:272-355): luma through its table, chroma scaled around 512 by the factor of the unmapped co-located luma sample.
+// v: the plane's sample; luma: the unmapped luma sample at (2y, 2x) for a chroma plane
+__device__ __forceinline__ int dra1(const int32_t *lut, int c, int v, int luma)
+{
+    if (c == 0) return (int)(int16_t)lut[min(max(v, 0), 1023)];
+    const int sv = v - 512;
+    int off = (abs(sv) * lut[c * 1024 + min(max(luma, 0), 1023)] + (1 << 8)) >> 9;
+    if (sv < 0) off = -off;
+    return (int)(int16_t)(512 + off);
+}
+
+// the six chroma samples of columns j0-1 .. j0+4 of row `row` (already clamped) of one chroma plane, edge-clamped to 0 .. cw-1
+__device__ __forceinline__ void chroma_row(const RgbOutArgs &a, int c, int row, int j0, int e[6])
+{
+    const int16_t *pl = (c == 1 ? a.u : a.v) + (size_t)row * a.sc;
+    const S16x8u s = *(const S16x8u *)(pl + j0 - 2);
+    #pragma unroll
+    for (int k = 0; k < 6; k++) e[k] = s.v[k + 1];
+    if (j0 == 0) e[0] = e[1];
+    const int nv = a.cw - j0;                     // valid columns from j0 on (>= 1)
+    int last = e[1];
+    #pragma unroll
+    for (int k = 2; k < 6; k++) if (nv >= k) last = e[k];
+    #pragma unroll
+    for (int k = 2; k < 6; k++) if (k > nv) e[k] = last;
+    if (a.dra) {                                  // e[k] = the sample of column j (clamped); its DRA factor comes from luma (2 row, 2 j)
+        const int16_t *l = a.y + (size_t)(2 * row) * a.sy;
+        #pragma unroll
+        for (int k = 0; k < 6; k++) e[k] = dra1(a.dra, c, e[k], l[2 * min(max(j0 - 1 + k, 0), a.cw - 1)]);
+    }
+}
+
+template <int DT> struct OutT;
+template <> struct OutT<XGPU_OUT_U8>   { static constexpr int size = 1, is_float = 0; };
+template <> struct OutT<XGPU_OUT_U16>  { static constexpr int size = 2, is_float = 0; };
+template <> struct OutT<XGPU_OUT_F16>  { static constexpr int size = 2, is_float = 1; };
+template <> struct OutT<XGPU_OUT_BF16> { static constexpr int size = 2, is_float = 1; };
+template <> struct OutT<XGPU_OUT_F32>  { static constexpr int size = 4, is_float = 1; };
+
+template <int DT> __device__ __forceinline__ uint32_t fbits(float f)
+{
+    if (DT == XGPU_OUT_F32) return __float_as_uint(f);
+    if (DT == XGPU_OUT_F16) return (uint32_t)__half_as_ushort(__float2half_rn(f));
+    const uint32_t u = __float_as_uint(f);        // bf16, round to nearest even (f is finite, in [-0.5, 1])
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+// N elements of SZ bytes, packed into 32-bit words and stored: vector stores at `dst` (aligned) or one element at a time (first n elements)
+template <int N, int SZ> __device__ __forceinline__ void store_run(uint8_t *dst, const uint32_t (&e)[N], bool vec, int n)
+{
+    if (vec) {
+        constexpr int NW = N * SZ / 4;
+        uint32_t w[NW];
+        #pragma unroll
+        for (int i = 0; i < NW; i++) w[i] = 0;
+        #pragma unroll
+        for (int i = 0; i < N; i++) w[i * SZ / 4] |= e[i] << (8 * ((i * SZ) % 4));
+        if (NW % 4 == 0) {
+            #pragma unroll
+            for (int i = 0; i < NW; i += 4) *(uint4 *)(dst + 4 * i) = make_uint4(w[i], w[i + 1], w[i + 2], w[i + 3]);
+        } else {
+            #pragma unroll
+            for (int i = 0; i < NW; i += 2) *(uint2 *)(dst + 4 * i) = make_uint2(w[i], w[i + 1]);
+        }
+    } else {
+        #pragma unroll
+        for (int i = 0; i < N; i++) {
+            if (i >= n) break;
+            if (SZ == 1) dst[i] = (uint8_t)e[i];
+            else if (SZ == 2) ((uint16_t *)dst)[i] = (uint16_t)e[i];
+            else ((uint32_t *)dst)[i] = e[i];
+        }
+    }
+}
+
+// The body of the kernels that write three channels at luma resolution (k_output_rgb, k_output_yuv444): one lane makes 8 horizontal pixels of the
+// two luma rows that share chroma row i.  Load, edge clamp, DRA and upsampling are here, once; CONV::apply turns one pixel's (Y, Cb, Cr) at the
+// coding depth into the bits of three output elements.  PLANAR: three planes a.plane bytes apart, else the three elements of a pixel side by side.
+template <bool PLANAR, int DT, int UP, class CONV>
+__device__ __forceinline__ void output_three_channels(const RgbOutArgs &a)
+{
+    constexpr int SZ = OutT<DT>::size;
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8;
+    const int i = blockIdx.y * 4 + threadIdx.y;
+    if (x0 >= a.w || i >= a.ch) return;
+    const int j0 = x0 >> 1;
+    const int n = min(8, a.w - x0);               // pixels of this lane in the row (even)
+    const bool vec = a.aligned && n == 8;
+
+    // chroma, vertically interpolated per row parity: cv[c][parity][k], columns j0-1+k
+    int cv[2][2][6];
+    #pragma unroll
+    for (int c = 0; c < 2; c++) {
+        int r0[6];
+        chroma_row(a, c + 1, i, j0, r0);
+        if (UP == XGPU_UPSAMPLE_NEAREST) {
+            #pragma unroll
+            for (int k = 0; k < 6; k++) cv[c][0][k] = cv[c][1][k] = r0[k];
+        } else {
+            int rm[6], rp[6];
+            chroma_row(a, c + 1, max(i - 1, 0), j0, rm);
+            chroma_row(a, c + 1, min(i + 1, a.ch - 1), j0, rp);
+            #pragma unroll
+            for (int k = 0; k < 6; k++) {
+                cv[c][0][k] = a.ve[0] * rm[k] + a.ve[1] * r0[k];
+                cv[c][1][k] = a.vo[0] * r0[k] + a.vo[1] * rp[k];
+            }
+        }
+    }
+
+    #pragma unroll
+    for (int par = 0; par < 2; par++) {
+        const int row = 2 * i + par;
+        const S16x8u ly = *(const S16x8u *)(a.y + (size_t)row * a.sy + x0);
+        uint32_t ch[3][8];
+        #pragma unroll
+        for (int m = 0; m < 8; m++) {
+            int y = ly.v[m];
+            if (a.dra) y = dra1(a.dra, 0, y, 0);
+            const int jj = m >> 1;                // chroma column j0 + jj = index jj + 1
+            int cc[2];
+            #pragma unroll
+            for (int c = 0; c < 2; c++) {
+                if (UP == XGPU_UPSAMPLE_NEAREST) cc[c] = cv[c][par][jj + 1];
+                else if (m & 1) cc[c] = ((2 + a.hc) * cv[c][par][jj + 1] + (2 - a.hc) * cv[c][par][jj + 2] + 8) >> 4;
+                else            cc[c] = (a.hc * cv[c][par][jj] + (4 - a.hc) * cv[c][par][jj + 1] + 8) >> 4;
+            }
+            CONV::apply(a, y, cc[0], cc[1], ch[0][m], ch[1][m], ch[2][m]);
+        }
+        if (a.bgr) {
+            #pragma unroll
+            for (int m = 0; m < 8; m++) { const uint32_t t = ch[0][m]; ch[0][m] = ch[2][m]; ch[2][m] = t; }
+        }
+        if (PLANAR) {
+            uint8_t *d = a.dst + (size_t)row * a.pitch + (size_t)x0 * SZ;
+            #pragma unroll
+            for (int c = 0; c < 3; c++) store_run<8, SZ>(d + c * a.plane, ch[c], vec, n);
+        } else {
+            uint32_t e[24];
+            #pragma unroll
+            for (int m = 0; m < 8; m++) { e[3 * m] = ch[0][m]; e[3 * m + 1] = ch[1][m]; e[3 * m + 2] = ch[2][m]; }
+            store_run<24, SZ>(a.dst + (size_t)row * a.pitch + (size_t)x0 * 3 * SZ, e, vec, 3 * n);
+        }
+    }
+}
+
+// The launch of a kernel family built on output_three_channels: 64 lanes x 4 chroma rows per workgroup, the instance picked by layout, dtype and
+// upsampling mode.  K::launch<PLANAR, DT, UP>(a, grid, stream) launches the family's kernel of that instance.
+template <class K, bool PLANAR, int DT>
+static void launch_three_dt(const RgbOutArgs &a, int upsample, dim3 grid, hipStream_t s)
+{
+    if (upsample == XGPU_UPSAMPLE_NEAREST) K::template launch<PLANAR, DT, XGPU_UPSAMPLE_NEAREST>(a, grid, s);
+    else                                   K::template launch<PLANAR, DT, XGPU_UPSAMPLE_LINEAR>(a, grid, s);
+}
+template <class K, bool PLANAR>
+static void launch_three_layout(const RgbOutArgs &a, int dtype, int upsample, dim3 grid, hipStream_t s)
+{
+    switch (dtype) {
+    case XGPU_OUT_U8:   launch_three_dt<K, PLANAR, XGPU_OUT_U8>(a, upsample, grid, s); break;
+    case XGPU_OUT_U16:  launch_three_dt<K, PLANAR, XGPU_OUT_U16>(a, upsample, grid, s); break;
+    case XGPU_OUT_F16:  launch_three_dt<K, PLANAR, XGPU_OUT_F16>(a, upsample, grid, s); break;
+    case XGPU_OUT_BF16: launch_three_dt<K, PLANAR, XGPU_OUT_BF16>(a, upsample, grid, s); break;
+    default:            launch_three_dt<K, PLANAR, XGPU_OUT_F32>(a, upsample, grid, s); break;
+    }
+}
+template <class K>
+static void launch_three_channels(const RgbOutArgs &a, bool planar, int dtype, int upsample, hipStream_t s)
+{
+    const dim3 grid((unsigned)(((a.w + 7) / 8 + 63) / 64), (unsigned)((a.ch + 3) / 4));
+    if (planar) launch_three_layout<K, true>(a, dtype, upsample, grid, s);
+    else        launch_three_layout<K, false>(a, dtype, upsample, grid, s);
+}

@@ -410,6 +410,11 @@ static bool matrix_kr_kb(int m, double *kr, double *kb)
     }
 }
 static int elem_size(int dtype) { return dtype == XGPU_OUT_U8 ? 1 : dtype == XGPU_OUT_F32 ? 4 : 2; }
+static bool is_rgb(int layout) { return layout == XGPU_OUT_RGB_PLANAR || layout == XGPU_OUT_RGB_INTERLEAVED; }
+static bool is_yuv444(int layout) { return layout == XGPU_OUT_YUV444_PLANAR || layout == XGPU_OUT_YUV444_INTERLEAVED; }
+static bool is_semiplanar(int layout) { return layout == XGPU_OUT_NV12 || layout == XGPU_OUT_P016; }
+// the depth D the samples of YUV420P / NV12 / P016 are converted to
+static int sample_depth(const xgpu_output_format *f, int bd) { return f->out_bit_depth ? f->out_bit_depth : bd; }
 // the format alone (no picture size): 0 or a negative code, `why` says which field
 static int check_format(const xgpu_output_format *f, int bd, const char **why)
 {
@@ -418,25 +423,46 @@ static int check_format(const xgpu_output_format *f, int bd, const char **why)
     *why = "crop offsets must be even and >= 0";
     for (int i = 0; i < 4; i++) if (f->crop[i] < 0 || (f->crop[i] & 1)) return XGPU_ERR_INVALID_ARGUMENT;
     if (f->layout == XGPU_OUT_YUV420P) {
-        const int obd = f->out_bit_depth ? f->out_bit_depth : bd;
+        const int obd = sample_depth(f, bd);
         *why = "YUV420P: out_bit_depth 8..16 with dtype U8 at 8 bit, U16 above, tight rows";
         if (obd < 8 || obd > 16 || f->dtype != (obd == 8 ? XGPU_OUT_U8 : XGPU_OUT_U16) || f->row_pitch != 0) return XGPU_ERR_INVALID_ARGUMENT;
         return XGPU_OK;
     }
-    *why = "layout must be XGPU_OUT_YUV420P, _RGB_PLANAR or _RGB_INTERLEAVED";
-    if (f->layout != XGPU_OUT_RGB_PLANAR && f->layout != XGPU_OUT_RGB_INTERLEAVED) return XGPU_ERR_INVALID_ARGUMENT;
+    if (is_semiplanar(f->layout)) {
+        const int obd = sample_depth(f, bd);
+        if (f->layout == XGPU_OUT_NV12) {
+            *why = "NV12: dtype U8 with out_bit_depth 8, or U16 with out_bit_depth 9..16 (0 = a coding depth above 8)";
+            if (f->dtype == XGPU_OUT_U8 ? f->out_bit_depth != 8 : (f->dtype != XGPU_OUT_U16 || obd < 9 || obd > 16)) return XGPU_ERR_INVALID_ARGUMENT;
+        } else {
+            *why = "P016: dtype U16 with out_bit_depth 8..16 (0 = the coding depth)";
+            if (f->dtype != XGPU_OUT_U16 || obd < 8 || obd > 16) return XGPU_ERR_INVALID_ARGUMENT;
+        }
+        *why = "NV12 / P016: bgr must be 0, row_pitch a multiple of the element size";
+        if (f->bgr || f->row_pitch % (size_t)elem_size(f->dtype)) return XGPU_ERR_INVALID_ARGUMENT;
+        return XGPU_OK;
+    }
+    *why = "layout must be one of XGPU_OUT_YUV420P .. XGPU_OUT_YUV444_INTERLEAVED";
+    if (!is_rgb(f->layout) && !is_yuv444(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
     *why = "dtype must be one of XGPU_OUT_U8 .. XGPU_OUT_F32";
     if (f->dtype < XGPU_OUT_U8 || f->dtype > XGPU_OUT_F32) return XGPU_ERR_INVALID_ARGUMENT;
-    *why = "RGB: out_bit_depth must be 0 or the coding depth";
+    *why = "RGB / YUV444: out_bit_depth must be 0 or the coding depth";
     if (f->out_bit_depth != 0 && f->out_bit_depth != bd) return XGPU_ERR_INVALID_ARGUMENT;
-    *why = "bgr, full_range: 0 or 1; chroma_loc 0..5; upsample XGPU_UPSAMPLE_NEAREST or _LINEAR; row_pitch a multiple of the element size";
-    if ((f->bgr | f->full_range) & ~1 || f->chroma_loc < 0 || f->chroma_loc > 5 || (f->upsample != XGPU_UPSAMPLE_NEAREST && f->upsample != XGPU_UPSAMPLE_LINEAR) ||
-        f->row_pitch % (size_t)elem_size(f->dtype))
+    *why = "bgr, full_range: 0 or 1 (bgr: RGB layouts only); chroma_loc 0..5; upsample XGPU_UPSAMPLE_NEAREST or _LINEAR; row_pitch a multiple of the element size";
+    if ((f->bgr | f->full_range) & ~1 || (f->bgr && !is_rgb(f->layout)) || f->chroma_loc < 0 || f->chroma_loc > 5 ||
+        (f->upsample != XGPU_UPSAMPLE_NEAREST && f->upsample != XGPU_UPSAMPLE_LINEAR) || f->row_pitch % (size_t)elem_size(f->dtype))
         return XGPU_ERR_INVALID_ARGUMENT;
+    if (is_yuv444(f->layout)) return XGPU_OK;      // no matrix
     double kr, kb;
     *why = "matrix: supported MatrixCoefficients are 1, 4, 5, 6, 7 and 9";
     if (!matrix_kr_kb(f->matrix, &kr, &kb)) return XGPU_ERR_UNSUPPORTED;
     return XGPU_OK;
+}
+// luma offset and the luma / chroma excursions at coding depth bd
+static void range_terms(int bd, int full_range, int *yo, double *yr, double *cr)
+{
+    *yo = full_range ? 0 : 16 << (bd - 8);
+    *yr = full_range ? (double)((1 << bd) - 1) : (double)(219 << (bd - 8));
+    *cr = full_range ? (double)((1 << bd) - 1) : (double)(224 << (bd - 8));
 }
 int xgpu_output_coeffs(const xgpu_output_format *f, int bit_depth, int32_t coef[5], int *shift, float fcoef[5])
 {
@@ -444,12 +470,12 @@ int xgpu_output_coeffs(const xgpu_output_format *f, int bit_depth, int32_t coef[
     if (bit_depth < 8 || bit_depth > 12 || !coef || !shift || !fcoef) return XGPU_ERR_INVALID_ARGUMENT;
     const int rc = check_format(f, bit_depth, &why);
     if (rc < 0) return rc;
-    if (f->layout == XGPU_OUT_YUV420P) return XGPU_ERR_INVALID_ARGUMENT;
-    double kr, kb;
+    if (!is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+    double kr, kb, yr, cr;
+    int yo;
     matrix_kr_kb(f->matrix, &kr, &kb);
     const double kg = 1.0 - kr - kb;
-    const double yr = f->full_range ? (double)((1 << bit_depth) - 1) : (double)(219 << (bit_depth - 8));
-    const double cr = f->full_range ? (double)((1 << bit_depth) - 1) : (double)(224 << (bit_depth - 8));
+    range_terms(bit_depth, f->full_range, &yo, &yr, &cr);
     // the same expressions, term for term, as tests/colour_ref.py (a different order of the double operations could round differently)
     auto terms = [&](double m, double sc, double t[5]) {
         t[0] = m / yr * sc;
@@ -472,24 +498,35 @@ int xgpu_output_coeffs(const xgpu_output_format *f, int bit_depth, int32_t coef[
     *shift = sh;
     return XGPU_OK;
 }
-static size_t device_size(const xgpu_ctx *c, const xgpu_output_format *f, const char **why)
+static size_t format_size(const xgpu_output_format *f, int width, int height, int bd, const char **why)
 {
-    if (check_format(f, c->sp.bit_depth_luma, why) < 0) return 0;
+    *why = "picture size or bit depth out of range";
+    if (width <= 0 || height <= 0 || ((width | height) & 1) || bd < 8 || bd > 12) return 0;
+    if (check_format(f, bd, why) < 0) return 0;
     *why = "crop leaves no picture";
-    if (!valid_output(c, 8, f->crop[0], f->crop[1], f->crop[2], f->crop[3])) return 0;
-    if (f->layout == XGPU_OUT_YUV420P)
-        return xgpu_pic_output_size(c, f->out_bit_depth ? f->out_bit_depth : c->sp.bit_depth_luma, f->crop[0], f->crop[1], f->crop[2], f->crop[3]);
-    const size_t w = c->sp.width - f->crop[0] - f->crop[1], h = c->sp.height - f->crop[2] - f->crop[3], es = elem_size(f->dtype);
-    const size_t row = f->layout == XGPU_OUT_RGB_PLANAR ? w * es : 3 * w * es;
+    if (f->crop[0] + f->crop[1] >= width || f->crop[2] + f->crop[3] >= height) return 0;
+    const size_t w = width - f->crop[0] - f->crop[1], h = height - f->crop[2] - f->crop[3], es = elem_size(f->dtype);
+    if (f->layout == XGPU_OUT_YUV420P) return (w * h + 2 * (w >> 1) * (h >> 1)) * es;      // xgpu_pic_output_size
+    const bool interleaved = f->layout == XGPU_OUT_RGB_INTERLEAVED || f->layout == XGPU_OUT_YUV444_INTERLEAVED;
+    const size_t row = interleaved ? 3 * w * es : w * es;
     const size_t pitch = f->row_pitch ? f->row_pitch : row;
     *why = "row_pitch is shorter than a row";
     if (pitch < row) return 0;
-    return (f->layout == XGPU_OUT_RGB_PLANAR ? 3 * h - 1 : h - 1) * pitch + row;      // the last row need not be followed by a pitch's worth of bytes
+    const size_t rows = is_semiplanar(f->layout) ? h + h / 2 : (interleaved ? h : 3 * h);
+    return (rows - 1) * pitch + row;      // the last row need not be followed by a pitch's worth of bytes
+}
+size_t xgpu_output_format_size(const xgpu_output_format *f, int width, int height, int bit_depth)
+{
+    const char *why;
+    return format_size(f, width, height, bit_depth, &why);
+}
+static size_t device_size(const xgpu_ctx *c, const xgpu_output_format *f, const char **why)
+{
+    return format_size(f, c->sp.width, c->sp.height, c->sp.bit_depth_luma, why);
 }
 size_t xgpu_pic_output_device_size(const xgpu_ctx *c, const xgpu_output_format *f)
 {
-    const char *why;
-    return c ? device_size(c, f, &why) : 0;
+    return c ? xgpu_output_format_size(f, c->sp.width, c->sp.height, c->sp.bit_depth_luma) : 0;
 }
 int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, void *d_dst, size_t dst_size, void *stream)
 {
@@ -498,7 +535,7 @@ int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const
     const size_t need = device_size(c, f, &why);
     if (need == 0) {
         snprintf(c->err, sizeof(c->err), "pic_output_device: invalid format: %s", why);
-        return f && f->layout != XGPU_OUT_YUV420P && check_format(f, c->sp.bit_depth_luma, &why) == XGPU_ERR_UNSUPPORTED ? XGPU_ERR_UNSUPPORTED : XGPU_ERR_INVALID_ARGUMENT;
+        return f && is_rgb(f->layout) && check_format(f, c->sp.bit_depth_luma, &why) == XGPU_ERR_UNSUPPORTED ? XGPU_ERR_UNSUPPORTED : XGPU_ERR_INVALID_ARGUMENT;
     }
     const size_t es = f->layout == XGPU_OUT_YUV420P ? 1 : (size_t)elem_size(f->dtype);
     if (dst_size < need || ((uintptr_t)d_dst % es)) {
@@ -530,34 +567,58 @@ int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const
     }
     const int *cr = f->crop;
     const DevPic &p = dpic(c, pic);
+    const int bd = c->sp.bit_depth_luma;
+    const int w = c->sp.width - cr[0] - cr[1], h = c->sp.height - cr[2] - cr[3];
+    const int16_t *sy = p.y + (size_t)cr[2] * p.s_l + cr[0];      // first sample of the cropped area of every plane
+    const int16_t *su = p.u + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1), *sv = p.v + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1);
     if (f->layout == XGPU_OUT_YUV420P) {
-        launch_output(c, p, dra ? c->d_dra : NULL, f->out_bit_depth ? f->out_bit_depth : c->sp.bit_depth_luma, cr[0], cr[1], cr[2], cr[3], (uint8_t *)d_dst, false, s);
+        launch_output(c, p, dra ? c->d_dra : NULL, sample_depth(f, bd), cr[0], cr[1], cr[2], cr[3], (uint8_t *)d_dst, false, s);
+    } else if (is_semiplanar(f->layout)) {
+        SemiPlanarArgs a;
+        memset(&a, 0, sizeof(a));
+        const int obd = sample_depth(f, bd);
+        a.y = sy; a.u = su; a.v = sv;
+        a.sy = p.s_l; a.sc = p.s_c;
+        a.w = w; a.ch = h >> 1;
+        a.dst = (uint8_t *)d_dst;
+        a.pitch = f->row_pitch ? f->row_pitch : (size_t)w * es;
+        a.chroma_off = a.pitch * h;
+        a.aligned = (((uintptr_t)d_dst | a.pitch | a.chroma_off) & 15) == 0;
+        a.shift = bd - obd; a.out8 = obd == 8; a.maxv = (1 << obd) - 1;      // launch_output's conversion
+        a.lsh = f->layout == XGPU_OUT_P016 ? 16 - obd : 0;
+        a.dra = dra ? c->d_dra : NULL;
+        launch_output_semiplanar(a, f->dtype, s);
     } else {
         RgbOutArgs a;
         memset(&a, 0, sizeof(a));
-        const int bd = c->sp.bit_depth_luma;
-        a.y = p.y + (size_t)cr[2] * p.s_l + cr[0];
-        a.u = p.u + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1);
-        a.v = p.v + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1);
+        const bool planar = f->layout == XGPU_OUT_RGB_PLANAR || f->layout == XGPU_OUT_YUV444_PLANAR;
+        a.y = sy; a.u = su; a.v = sv;
         a.sy = p.s_l; a.sc = p.s_c;
-        a.w = c->sp.width - cr[0] - cr[1]; a.h = c->sp.height - cr[2] - cr[3];
+        a.w = w; a.h = h;
         a.cw = a.w >> 1; a.ch = a.h >> 1;
         a.dst = (uint8_t *)d_dst;
-        a.pitch = f->row_pitch ? f->row_pitch : (size_t)a.w * es * (f->layout == XGPU_OUT_RGB_PLANAR ? 1 : 3);
+        a.pitch = f->row_pitch ? f->row_pitch : (size_t)a.w * es * (planar ? 1 : 3);
         a.plane = a.pitch * a.h;
         a.aligned = (((uintptr_t)d_dst | a.pitch | a.plane) & 15) == 0;
         a.bgr = f->bgr;
-        (void)xgpu_output_coeffs(f, bd, a.coef, &a.shift, a.fcoef);
-        a.yo = f->full_range ? 0 : 16 << (bd - 8);
+        double yr, crr;
+        range_terms(bd, f->full_range, &a.yo, &yr, &crr);
         a.co = 1 << (bd - 1);
-        a.maxv = f->dtype == XGPU_OUT_U8 ? 255 : (1 << bd) - 1;
         // ChromaSampleLocType: horizontally co-sited (0, 2, 4) / centred (1, 3, 5); vertically centred (0, 1), top (2, 3), bottom (4, 5)
         static const int ve[3][2] = { { 1, 3 }, { 0, 4 }, { 2, 2 } }, vo[3][2] = { { 3, 1 }, { 2, 2 }, { 4, 0 } };
         a.hc = f->chroma_loc & 1;
         a.ve[0] = ve[f->chroma_loc >> 1][0]; a.ve[1] = ve[f->chroma_loc >> 1][1];
         a.vo[0] = vo[f->chroma_loc >> 1][0]; a.vo[1] = vo[f->chroma_loc >> 1][1];
         a.dra = dra ? c->d_dra : NULL;
-        launch_output_rgb(a, f->layout, f->dtype, f->upsample, s);
+        if (is_rgb(f->layout)) {
+            (void)xgpu_output_coeffs(f, bd, a.coef, &a.shift, a.fcoef);
+            a.maxv = f->dtype == XGPU_OUT_U8 ? 255 : (1 << bd) - 1;
+            launch_output_rgb(a, f->layout, f->dtype, f->upsample, s);
+        } else {
+            a.shift = bd - 8;
+            a.fcoef[0] = (float)(1.0 / yr); a.fcoef[1] = (float)(1.0 / crr);      // rounded once from double
+            launch_output_yuv444(a, f->layout, f->dtype, f->upsample, s);
+        }
     }
     HIPCHK(c, hipGetLastError());
     if (stream) {

@@ -428,7 +428,9 @@ void launch_pad(xgpu_ctx *c, const DevPic &p);
 void launch_copy_bw(xgpu_ctx *c, const void *src, void *dst, size_t bytes);
 void launch_output(xgpu_ctx *c, const DevPic &pic, const int32_t *d_dra, int out_bd, int crop_l, int crop_r, int crop_t, int crop_b, uint8_t *d_dst, bool raw16 = false,
                    hipStream_t s = nullptr);      // s = NULL: the context's stream
-// k_output_rgb.hip: the cropped picture as R'G'B' (xgpu_pic_output_device).  Everything the kernel needs, resolved on the host by xgpu_api.hip.
+// k_output_rgb.hip, k_output_yuv.hip (k_output_yuv444): the cropped picture as three channels at luma resolution - R'G'B' or Y'CbCr 4:4:4
+// (xgpu_pic_output_device).  Everything the kernels need, resolved on the host by xgpu_api.hip.  YUV444 reads no matrix: coef / maxv stay zero,
+// shift = B - 8 (the u8 rounding shift), fcoef[0] = fy = float32(1 / yr), fcoef[1] = fc = float32(1 / cr).
 struct RgbOutArgs {
     const int16_t *y, *u, *v;       // first sample of the cropped area of every plane
     int      sy, sc;                // plane strides in samples
@@ -445,6 +447,20 @@ struct RgbOutArgs {
     const int32_t *dra;             // [3][1024] DRA inverse tables, or NULL
 };
 void launch_output_rgb(const RgbOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
+void launch_output_yuv444(const RgbOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
+// k_output_yuv.hip (k_output_semiplanar): NV12 / P016 - xgpu_pic_output's samples, luma rows then rows of interleaved Cb Cr
+struct SemiPlanarArgs {
+    const int16_t *y, *u, *v;       // first sample of the cropped area of every plane
+    int      sy, sc;                // plane strides in samples
+    int      w, ch;                 // cropped luma width, chroma rows (= luma rows / 2)
+    uint8_t *dst;
+    size_t   pitch, chroma_off;     // bytes between rows, byte offset of the chroma plane (luma rows x pitch)
+    int      aligned;               // dst, pitch and chroma_off are multiples of 16 bytes: vector stores
+    int      shift, out8, maxv;     // conv1's arguments at depth D: B - D, D == 8, 2^D - 1
+    int      lsh;                   // P016: 16 - D, the sample in the high bits of the word; NV12: 0
+    const int32_t *dra;             // [3][1024] DRA inverse tables, or NULL
+};
+void launch_output_semiplanar(const SemiPlanarArgs &a, int dtype, hipStream_t s);
 void launch_md5(xgpu_ctx *c, hipStream_t s, const uint8_t *d_msg, int w, int h, uint32_t *d_digest);      // k_md5.hip: the three planes packed back to back at d_msg -> d_digest[3][4]
 void launch_test_mc(xgpu_ctx *c, const int16_t *plane, int stride, int ref_x, int ref_y, int has_dx, int has_dy,
                     int gmv_x, int gmv_y, int16_t *pred, int w, int h, int bd, int luma);

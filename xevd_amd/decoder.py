@@ -109,15 +109,21 @@ class XgpuDecoder:
         return C.byref(d), (keep, d)
 
     def pic_output_tensor(self, pic, layout="rgb", channels_last=False, dtype=None, matrix=1, full_range=False, chroma_loc=0, upsample="linear",
-                          crop=(0, 0, 0, 0), dra=None, out=None, bgr=False):
+                          crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, out_bit_depth=0):
         """The picture in device memory as a torch tensor on cuda:{device}, converted on the device (xgpu_pic_output_device) on torch's current
         stream - no host round trip.  layout "rgb": [3, H, W] (channels_last: [H, W, 3]) R'G'B' (bgr: B, G, R) with dtype torch.uint8, torch.int16 /
         torch.uint16 (values at the coding depth), torch.float16, torch.bfloat16 or torch.float32 (0..1), through `matrix` (H.273 MatrixCoefficients
         1, 4, 5, 6, 7, 9), full_range, chroma_loc (ChromaSampleLocType 0..5) and upsample "linear" / "nearest"; layout "yuv420p": the bytes of
-        pic_output (1-D, uint8 for 8-bit output - dtype torch.uint8 - else 16-bit samples at the coding depth).  crop: (left, right, top, bottom), even.
-        out: a tensor to fill instead (its strides may pad the rows: row_pitch); it is also what is returned."""
+        pic_output (1-D, uint8 for 8-bit output - dtype torch.uint8 - else 16-bit samples at the coding depth).
+        Video surfaces: layout "nv12": [H * 3 // 2, W] - H luma rows, then H / 2 rows Cb0 Cr0 Cb1 Cr1 ... - torch.uint8 (8-bit samples), or a 16-bit
+        integer type with the samples at out_bit_depth (0 = the coding depth) in the low bits; "p016": the same shape, 16-bit, sample << (16 - D) with
+        D = out_bit_depth (0 = the coding depth; 10 is P010, 12 is P012); "yuv444": [3, H, W] (channels_last: [H, W, 3]) Y, Cb, Cr at luma resolution
+        (chroma upsampled by upsample / chroma_loc as for "rgb"): torch.uint8 (8-bit samples), 16-bit integers (the coding depth) or floats - H.273's
+        E'Y in 0..1, E'Cb and E'Cr in -0.5..0.5 by full_range.  out_bit_depth: "nv12" / "p016" only; for "rgb" / "yuv444" it must be 0 or the coding depth.
+        crop: (left, right, top, bottom), even.  out: a tensor to fill instead (its strides may pad the rows: row_pitch); it is also what is returned."""
         import torch
-        dtype = torch.uint8 if dtype is None else dtype
+        if dtype is None:
+            dtype = torch.int16 if layout == "p016" else torch.uint8      # P016 has 16-bit words only
         codes = {torch.uint8: abi.OUT_U8, torch.int16: abi.OUT_U16, torch.float16: abi.OUT_F16, torch.bfloat16: abi.OUT_BF16, torch.float32: abi.OUT_F32}
         if getattr(torch, "uint16", None) is not None:
             codes[torch.uint16] = abi.OUT_U16
@@ -128,6 +134,10 @@ class XgpuDecoder:
         cl, cr, ct, cb = (int(v) for v in crop)
         w, h = self.width - cl - cr, self.height - ct - cb
         dev = torch.device("cuda", self.sp.device)
+        obd = int(out_bit_depth)
+        up = abi.UPSAMPLE_LINEAR if upsample == "linear" else abi.UPSAMPLE_NEAREST
+        if layout in ("rgb", "yuv444") and obd not in (0, self.bit_depth):
+            raise ValueError(f"{layout}: out_bit_depth must be 0 or the coding depth {self.bit_depth}, not {obd}")
         if layout == "yuv420p":
             if codes[dtype] not in (abi.OUT_U8, abi.OUT_U16):
                 raise ValueError("yuv420p: dtype torch.uint8 (8-bit output) or a 16-bit integer type (the coding depth)")
@@ -136,28 +146,43 @@ class XgpuDecoder:
             if n == 0:
                 raise ValueError(f"invalid output format: crop {crop}")
             shape, strides = (n // dtype.itemsize,), (1,)
-        elif layout == "rgb":
+        elif layout in ("nv12", "p016"):
+            if codes[dtype] != abi.OUT_U16 and (layout == "p016" or codes[dtype] != abi.OUT_U8):
+                raise ValueError(f"{layout}: dtype must be a 16-bit integer type{' or torch.uint8 (8-bit samples)' if layout == 'nv12' else ''}")
+            if codes[dtype] == abi.OUT_U8:
+                if obd not in (0, 8):
+                    raise ValueError("nv12: torch.uint8 holds 8-bit samples; out_bit_depth above 8 needs a 16-bit integer dtype")
+                obd = 8
+            shape = (h * 3 // 2, w)
+            fmt = abi.make_output_format(abi.OUT_NV12 if layout == "nv12" else abi.OUT_P016, codes[dtype], out_bit_depth=obd, crop=crop)
+            strides = None
+        elif layout in ("rgb", "yuv444"):
             shape = (h, w, 3) if channels_last else (3, h, w)
-            fmt = abi.make_output_format(abi.OUT_RGB_INTERLEAVED if channels_last else abi.OUT_RGB_PLANAR, codes[dtype], bgr=bgr, matrix=matrix, full_range=full_range,
-                                         chroma_loc=chroma_loc, upsample=abi.UPSAMPLE_LINEAR if upsample == "linear" else abi.UPSAMPLE_NEAREST, crop=crop)
+            lay = (abi.OUT_RGB_INTERLEAVED, abi.OUT_RGB_PLANAR) if layout == "rgb" else (abi.OUT_YUV444_INTERLEAVED, abi.OUT_YUV444_PLANAR)
+            fmt = abi.make_output_format(lay[0] if channels_last else lay[1], codes[dtype], bgr=bgr, matrix=matrix, full_range=full_range,
+                                         chroma_loc=chroma_loc, upsample=up, crop=crop)
             strides = None
         else:
-            raise ValueError(f"layout must be 'rgb' or 'yuv420p', not {layout!r}")
+            raise ValueError(f"layout must be 'rgb', 'yuv420p', 'nv12', 'p016' or 'yuv444', not {layout!r}")
         if out is None:
             out = torch.empty(shape, dtype=dtype, device=dev)
         if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
             raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
         st = out.stride()
-        if layout == "rgb":
+        if layout in ("rgb", "yuv444"):
             pitch = st[0] if channels_last else st[1]          # elements between rows
             if (channels_last and st[1:] != (3, 1)) or (not channels_last and (st[2] != 1 or st[0] != pitch * h)) or pitch < (3 * w if channels_last else w):
                 raise ValueError(f"out: strides {st} are not rows of {'W x 3' if channels_last else 'W'} elements {'' if channels_last else 'in planes of H rows '}")
             fmt.row_pitch = pitch * dtype.itemsize
+        elif layout in ("nv12", "p016"):
+            if st[1] != 1 or st[0] < w:
+                raise ValueError(f"out: strides {st} are not rows of W elements")
+            fmt.row_pitch = st[0] * dtype.itemsize
         elif st != strides:
             raise ValueError("out: must be contiguous")
         dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
         if self.lib.xgpu_pic_output_device_size(self.ctx, C.byref(fmt)) == 0:
-            raise ValueError(f"invalid output format (matrix {matrix}, chroma_loc {chroma_loc}, crop {crop})")
+            raise ValueError(f"invalid output format (layout {layout}, out_bit_depth {out_bit_depth}, matrix {matrix}, chroma_loc {chroma_loc}, crop {crop})")
         nbytes = (sum((n - 1) * s for n, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
         cur = torch.cuda.current_stream(dev)
         run = cur

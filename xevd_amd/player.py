@@ -154,11 +154,14 @@ class StreamDecoder:
                 self._dec.close()
                 self._dec = None
 
-    def output_order(self, output_bit_depth=None):
-        """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them"""
+    def output_order(self, output_bit_depth=None, tensor=None):
+        """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
+        pictures takes it) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape"""
         out, epoch = [], -1
-        for p, planes in self.pictures(output_bit_depth=output_bit_depth):
+        for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor):
             if p["is_idr"]:
                 epoch += 1
+            if tensor is not None:
+                planes = planes.cpu().numpy()      # (synchronises torch's current stream: the slot's tensor is complete)
             out.append(((epoch, p["poc"]), p, planes))
         return [(p, planes) for _, p, planes in sorted(out, key=lambda t: t[0])]
