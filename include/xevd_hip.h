@@ -285,6 +285,48 @@ int    xgpu_pic_output_device(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, 
 /* Host only, no context: the fixed-point coefficients the kernel uses for format `f` at coding depth `bit_depth` - coef = { cy, crv, cgu, cgv, cbu }
    with `shift` = S (integer dtypes; zeros for float dtypes), fcoef = the float32 ones (2^D - 1 = 1).  0, or a negative code for an invalid format. */
 int    xgpu_output_coeffs(const xgpu_output_format *f, int bit_depth, int32_t coef[5], int *shift, float fcoef[5]);
+/* ---- colour-managed RGB output (k_output_cm.hip): the R'G'B' of the two RGB layouts taken from the stream's colour space to the caller's.  After the
+   fixed-point Y'CbCr -> R'G'B' of the U16 form (the code at the coding depth B, whatever the output dtype): (1) linearise with the inverse of the source
+   transfer characteristic, (2) source -> destination primaries, (3) tone curve or linear_scale, clip to [0, 1], (4) re-encode with the destination
+   transfer characteristic, then the output dtype.  Transfer characteristics (H.273): 1 / 6 / 14 / 15 the BT.709 curve, 4 gamma 2.2, 5 gamma 2.8, 8 linear,
+   13 sRGB, 16 PQ (1.0 linear = 10000 cd/m2), 18 HLG (the BT.2100 OETF and its inverse: scene light); others XGPU_ERR_UNSUPPORTED.  Primaries (H.273):
+   1 BT.709, 5 BT.601 625, 6 / 7 BT.601 525 / SMPTE 240M, 9 BT.2020, 12 P3-D65 (all D65, no chromatic adaptation); others XGPU_ERR_UNSUPPORTED.
+   tone_map = 0: step 3 multiplies by linear_scale (0 means 1).  tone_map = 1: step 3 multiplies the three channels by g(Y) / Y (one IEEE float32 division), Y the luminance in the source
+   primaries, g = the display luminance of Y (PQ: 10000 Y; HLG: the BT.2100 OOTF src_peak * Y^gamma, gamma = 1.2 + 0.42 log10(src_peak / 1000); else
+   src_peak * Y) through the BT.2390 EETF from src_peak to dst_peak (identity when dst_peak >= src_peak), divided by the destination's white (10000 for PQ,
+   else dst_peak); linear_scale is not read; destination HLG is XGPU_ERR_UNSUPPORTED with tone_map.  Peaks in cd/m2, 0 = 1000 for a PQ / HLG side, 100 otherwise.
+   No powf / exp2f in the kernel: table lookups in tables made here in double precision, and float32 multiplies and adds rounded one by one - the contract,
+   operation by operation, is INTEGRATION.md section 8b; tests/colour_cm_ref.py restates it in numpy, bit for bit. */
+typedef struct xgpu_colour_transform {
+    int   src_primaries, src_transfer;      /* H.273 ColourPrimaries / TransferCharacteristics of the stream */
+    int   dst_primaries, dst_transfer;      /* of the output                                                  */
+    int   tone_map;                         /* 0 | 1                                                          */
+    float src_peak, dst_peak;               /* cd/m2, tone_map = 1 only; 0 = the default                      */
+    float linear_scale;                     /* tone_map = 0 only; 0 = 1                                       */
+} xgpu_colour_transform;
+/* A curve table: a function of v in [0, 1] sampled at 0, at the floats 2^-64 * 2^(j / 32) ... - exactly: at the float32 values whose bit pattern is
+   XGPU_CM_CURVE_U0 + (j << 18), j = 0 .. 2048 (2^-64 .. 1.0, 32 per octave) - and one repeat of the last entry.  Evaluation (section 8b): v < 2^-64:
+   k = 0, t = v * 2^64; else k = 1 + ((bits(v) - U0) >> 18), t = (bits(v) & 0x3FFFF) * 2^-18; value = T[k] + t * (T[k + 1] - T[k]). */
+#define XGPU_CM_CURVE_U0    0x1F800000u
+#define XGPU_CM_CURVE_SIZE  (64 * 32 + 3)
+typedef struct xgpu_colour_tables_t {
+    int   n_lin;                            /* 2^bit_depth                                                                            */
+    int   use_matrix, use_tone, use_encode; /* step 2 runs (primaries differ) / step 3 reads `tone` / step 4 reads `encode` (destination not linear) */
+    float lin[4096];                        /* step 1: linear light of the R'G'B' code k, k = 0 .. n_lin - 1                          */
+    float matrix[9];                        /* step 2: row-major, destination = matrix x source                                       */
+    float luma[3];                          /* step 3: Y = luma . (R, G, B) in the source primaries                                   */
+    float scale;                            /* step 3 with tone_map = 0                                                               */
+    float tone[XGPU_CM_CURVE_SIZE];         /* step 3 with tone_map = 1: g(Y), in the destination's linear range                      */
+    float encode[XGPU_CM_CURVE_SIZE];       /* step 4: the destination transfer characteristic                                        */
+} xgpu_colour_tables_t;
+/* Host only, no context: everything the kernel reads for transform `cm` on the RGB format `f` at coding depth `bit_depth`.  0, XGPU_ERR_UNSUPPORTED for a
+   transfer characteristic or primaries outside the lists above, XGPU_ERR_INVALID_ARGUMENT for the rest (a layout that is not RGB, a negative peak or scale). */
+int    xgpu_colour_tables(const xgpu_output_format *f, const xgpu_colour_transform *cm, int bit_depth, xgpu_colour_tables_t *out);
+/* xgpu_pic_output_device with the colour transform `cm` (NULL: xgpu_pic_output_device itself).  RGB layouts only - with any other layout
+   XGPU_ERR_INVALID_ARGUMENT; every refusal comes before anything is queued.  The tables are kept per context and made and uploaded again - on the stream the
+   kernel runs on, ordered like the DRA tables - only when `cm` or the depth differ from the previous call's. */
+int    xgpu_pic_output_device_cm(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm,
+                                 void *d_dst, size_t dst_size, void *stream);
 /* The picture signature on the device: the MD5 of every plane over its rows of width x 2 bytes of 16-bit samples (8-bit pictures too), as xevd_md5_imgb makes it
    (src_base/xevd_util.c:985-1002) and xevd_picbuf_check_signature compares it with the SEI (:1557-1572) - of the DRA-mapped picture when `dra` is given, which is
    what the Main decoder signs when the PPS names a DRA parameter set (src_main/xevdm.c:3256-3287).  digest[plane] = the 16 bytes of the SEI payload.  Blocking; the

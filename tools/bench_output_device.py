@@ -1,4 +1,4 @@
-"""Device-output rate: an 8K 10-bit picture converted into torch tensors by xgpu_pic_output_device (k_output_rgb / k_output / k_output_semiplanar / k_output_yuv444), timed with torch
+"""Device-output rate: an 8K 10-bit picture converted into torch tensors by xgpu_pic_output_device (k_output_rgb / k_output / k_output_semiplanar / k_output_yuv444 / k_output_cm), timed with torch
 events on the output stream (median of --iters launches after warm-up), against the plain device copy rate of the same run
 (xgpu_measure_copy_bw).  Bytes are algorithmic: 3 bytes of samples read per pixel (luma + two quarter-size chroma planes, 16 bit) and what the
 format writes.  Prints one line per form and a JSON line; --out also writes the JSON to a file.
@@ -14,6 +14,20 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def torch_transform(torch, rgb, to_srgb):
+    """PQ / BT.2020 R'G'B' [3, H, W] f32 -> linear BT.709 (1.0 = 100 cd/m2, clipped), or that re-encoded as sRGB u8: the work a caller
+    has without the fused kernel (the tone curve left out - in the caller's favour)"""
+    m1, m2, c1, c2, c3 = 2610.0 / 16384.0, 2523.0 / 4096.0 * 128.0, 3424.0 / 4096.0, 2413.0 / 4096.0 * 32.0, 2392.0 / 4096.0 * 32.0
+    mat = torch.tensor([[1.660491, -0.587641, -0.072850], [-0.124550, 1.132900, -0.008349], [-0.018151, -0.100579, 1.118730]], device=rgb.device)
+    p = rgb.pow(1.0 / m2)
+    lin = ((p - c1).clamp_min(0) / (c2 - c3 * p)).pow(1.0 / m1)
+    lin = (torch.matmul(mat, lin.reshape(3, -1)).reshape(rgb.shape) * 100.0).clamp(0, 1)
+    if not to_srgb:
+        return lin
+    enc = torch.where(lin < 0.0031308, 12.92 * lin, 1.055 * lin.pow(1.0 / 2.4) - 0.055)
+    return (enc * 255.0).round().to(torch.uint8)
 
 
 def main():
@@ -40,6 +54,14 @@ def main():
              ("p010", dict(layout="p016", dtype=torch.int16, out_bit_depth=10), 3),
              ("yuv444_u8_planar", dict(layout="yuv444", dtype=torch.uint8), 3),
              ("yuv444_f16_planar", dict(layout="yuv444", dtype=torch.float16), 6)]
+    # colour-managed forms (k_output_cm): PQ / BT.2020 -> sRGB / BT.709 through the tone curve, and -> linear BT.709.
+    # rgb_f32_planar is the plain form torch starts from.
+    hdr = dict(src_primaries=9, src_transfer=16, dst_primaries=1)
+    to_srgb, to_lin = dict(hdr, dst_transfer=13, tone_map=True), dict(hdr, dst_transfer=8, linear_scale=100.0)
+    forms += [("rgb_f32_planar", dict(dtype=torch.float32), 12)]
+    forms += [("cm_pq2020_srgb_u8_planar", dict(dtype=torch.uint8, matrix=9, colour=to_srgb), 3),
+              ("cm_pq2020_linear709_f16_planar", dict(dtype=torch.float16, matrix=9, colour=to_lin), 6),
+              ("cm_pq2020_linear709_f32_planar", dict(dtype=torch.float32, matrix=9, colour=to_lin), 12)]
     res = {"width": w, "height": h, "bit_depth": bd, "iters": a.iters, "forms": {}}
     with XgpuDecoder(w, h, bd, device=0, max_pics=2) as dec:
         pic = dec.pic_alloc()
@@ -64,6 +86,22 @@ def main():
             gbps = nbytes / (us * 1e-6) / 1e9
             res["forms"][name] = {"us": round(us, 2), "bytes": nbytes, "gbps": round(gbps, 1), "frac_copy": round(gbps / copy_gbps, 3)}
             print(f"{name:20s} {us:9.1f} us  {nbytes / 1e6:7.1f} MB  {gbps:7.1f} GB/s  {gbps / copy_gbps:5.2f} of copy ({copy_gbps:.0f} GB/s)")
+        # the same two transforms done afterwards in torch on the plain f32 RGB tensor (pow / where / matmul), timed the same way
+        rgb = dec.pic_output_tensor(pic, dtype=torch.float32, matrix=9)
+        for name, fn, wbytes in (("torch_pq2020_srgb_u8_after_f32", lambda: torch_transform(torch, rgb, True), 3),
+                                 ("torch_pq2020_linear709_f32_after_f32", lambda: torch_transform(torch, rgb, False), 12)):
+            n = max(a.iters // 10, 5)
+            for _ in range(2):
+                fn()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+            for e0, e1 in ev:
+                e0.record(s)
+                fn()
+                e1.record(s)
+            torch.cuda.synchronize()
+            us = float(np.median([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]))
+            res["forms"][name] = {"us": round(us, 2), "launches": n, "note": "excludes the plain f32 output it starts from"}
+            print(f"{name:40s} {us:9.1f} us (torch, after rgb_f32_planar)")
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

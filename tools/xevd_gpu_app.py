@@ -19,12 +19,17 @@ def main():
     ap.add_argument("--output-bit-depth", type=int, default=0, help="0 = the stream's bit depth (8 -> bytes, else 16-bit little endian)")
     ap.add_argument("--pix-fmt", choices=("yuv420p", "nv12", "p010"), default="yuv420p",
                     help="nv12: 8-bit semi-planar; p010: 10 bit in 16-bit little-endian words, semi-planar (both ignore --output-bit-depth)")
+    ap.add_argument("--to", default=None, help="write interleaved 8-bit RGB frames in this colour space instead (srgb, bt709, pq-bt2020, ...: "
+                    "StreamDecoder.COLOUR_PRESETS), converted on the device from the primaries / transfer characteristics of the stream's VUI")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
     data = open(args.input, "rb").read()
     t0 = time.perf_counter()
     # crop-free output like the reference application; bit-depth conversion and plane packing run on the device (xgpu_pic_output)
-    if args.pix_fmt == "yuv420p":
+    if args.to is not None:
+        import torch
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to)
+    elif args.pix_fmt == "yuv420p":
         pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth)
     else:      # the same pictures as semi-planar surfaces (xgpu_pic_output_device into a torch tensor, copied to the host picture by picture)
         import torch

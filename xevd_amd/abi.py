@@ -56,6 +56,40 @@ def make_output_format(layout=OUT_RGB_PLANAR, dtype=OUT_U8, bgr=False, out_bit_d
     return f
 
 
+CM_CURVE_U0, CM_CURVE_SIZE = 0x1F800000, 64 * 32 + 3
+
+
+class ColourTransform(C.Structure):
+    _fields_ = [("src_primaries", C.c_int), ("src_transfer", C.c_int), ("dst_primaries", C.c_int), ("dst_transfer", C.c_int),
+                ("tone_map", C.c_int), ("src_peak", C.c_float), ("dst_peak", C.c_float), ("linear_scale", C.c_float)]
+
+
+class ColourTables(C.Structure):
+    _fields_ = [("n_lin", C.c_int), ("use_matrix", C.c_int), ("use_tone", C.c_int), ("use_encode", C.c_int),
+                ("lin", C.c_float * 4096), ("matrix", C.c_float * 9), ("luma", C.c_float * 3), ("scale", C.c_float),
+                ("tone", C.c_float * CM_CURVE_SIZE), ("encode", C.c_float * CM_CURVE_SIZE)]
+
+
+def make_colour_transform(src_primaries=1, src_transfer=1, dst_primaries=1, dst_transfer=13, tone_map=False, src_peak=0.0, dst_peak=0.0, linear_scale=1.0):
+    """xgpu_colour_transform (include/xevd_hip.h): H.273 code points of the stream and of the output; peaks in cd/m2, 0 = the default of the transfer"""
+    t = ColourTransform()
+    t.src_primaries, t.src_transfer, t.dst_primaries, t.dst_transfer = int(src_primaries), int(src_transfer), int(dst_primaries), int(dst_transfer)
+    t.tone_map, t.src_peak, t.dst_peak, t.linear_scale = int(bool(tone_map)), float(src_peak), float(dst_peak), float(linear_scale)
+    return t
+
+
+def colour_tables(lib, fmt, cm, bit_depth):
+    """xgpu_colour_tables as numpy arrays: dict(lin, matrix [3][3], luma, scale, tone or None, encode or None, use_matrix)"""
+    t = ColourTables()
+    rc = lib.xgpu_colour_tables(C.byref(fmt), C.byref(cm), int(bit_depth), C.byref(t))
+    if rc < 0:
+        return rc
+    f32 = lambda a, n: np.frombuffer(a, np.float32, n).copy()      # noqa: E731
+    return {"lin": f32(t.lin, t.n_lin), "matrix": f32(t.matrix, 9).reshape(3, 3), "luma": f32(t.luma, 3), "scale": np.float32(t.scale),
+            "use_matrix": bool(t.use_matrix), "tone": f32(t.tone, CM_CURVE_SIZE) if t.use_tone else None,
+            "encode": f32(t.encode, CM_CURVE_SIZE) if t.use_encode else None}
+
+
 class FrameParams(C.Structure):
     _fields_ = [
         ("pic", C.c_int), ("poc", C.c_int), ("num_refp", C.c_int * 2),
@@ -218,6 +252,8 @@ _EXPORTS = {
     "xgpu_pic_output_device_size": (C.c_size_t, [C.c_void_p, C.POINTER(OutputFormat)]),
     "xgpu_pic_output_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_output_coeffs": (C.c_int, [C.POINTER(OutputFormat), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "xgpu_colour_tables": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ColourTransform), C.c_int, C.POINTER(ColourTables)]),
+    "xgpu_pic_output_device_cm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ColourTransform), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "xgpu_host_free": (None, [C.c_void_p, C.c_void_p]),
     "xgpu_batch_wait_upload": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1,6 +1,7 @@
 // xgpu_api.hip - the C ABI of include/xevd_hip.h, part 1: context, device pictures, output, frame begin / end, HIP-event kernel timing.
 // Host-side code only; kernels live in k_*.hip, the batch builder in xgpu_builder.hip, the launch sequencing in xgpu_launch.hip, the test shims in xgpu_shims.hip.
 #include "xgpu_host.h"
+#include <memory>
 
 // xevd_tbl_qp_chroma_adjust_base (src_base/xevd_tbl.c:345-354): default Baseline chroma QP mapping.
 // ... and xevd_tbl_qp_chroma_adjust_main (xevd_tbl.c:334-342): the default when sps->tool_iqt is on (xevdm.c:471-479)
@@ -119,7 +120,7 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
     c->sp = *sp;
     c->sp.chroma_qp_table[0] = c->sp.chroma_qp_table[1] = NULL;
     c->builder_threads = 1;
-    c->err[0] = 0; c->timing = 0; c->have_frame = 0; c->d_maps = NULL; c->d_dra = NULL; c->d_ctb_flag = NULL; c->stream = 0; c->up_stream = 0; c->down_stream = 0; c->side_stream = 0; c->after_inter = 0; c->have_after_inter = 0; c->where = 0; c->addb_pending = 0;
+    c->err[0] = 0; c->timing = 0; c->have_frame = 0; c->d_maps = NULL; c->d_dra = NULL; c->d_cm = NULL; c->cm_tab = NULL; c->d_ctb_flag = NULL; c->stream = 0; c->up_stream = 0; c->down_stream = 0; c->side_stream = 0; c->after_inter = 0; c->have_after_inter = 0; c->where = 0; c->addb_pending = 0;
     c->fork_ev = c->join_ev = 0;
     c->intra_small_min = getenv("XEVD_HIP_INTRA_SMALL_MIN") ? std::max(1, atoi(getenv("XEVD_HIP_INTRA_SMALL_MIN"))) : 2048;      // (k_intra.hip: launch_intra; read per context, tests set 1)
     c->addb_scalar = getenv("XEVD_HIP_ADDB_SCALAR") != NULL;
@@ -216,6 +217,8 @@ void xgpu_close(xgpu_ctx *c)
     for (int i = 0; i < 2; i++) if (c->odev_ev[i]) (void)hipEventDestroy(c->odev_ev[i]);
     for (int i = 0; i < 2; i++) { if (c->d_out[i]) (void)hipFree(c->d_out[i]); if (c->out_ready[i]) (void)hipEventDestroy(c->out_ready[i]); if (c->out_done[i]) (void)hipEventDestroy(c->out_done[i]); }
     if (c->d_dra) (void)hipFree(c->d_dra);
+    if (c->d_cm) (void)hipFree(c->d_cm);
+    delete c->cm_tab;
     if (c->d_ctb_flag) (void)hipFree(c->d_ctb_flag);
     for (auto &e : c->ev_pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : c->ev_pool) (void)hipEventDestroy(e);
@@ -528,7 +531,35 @@ size_t xgpu_pic_output_device_size(const xgpu_ctx *c, const xgpu_output_format *
 {
     return c ? xgpu_output_format_size(f, c->sp.width, c->sp.height, c->sp.bit_depth_luma) : 0;
 }
+// the colour transform's tables on the device: the host copy is kept with the (cm, depth) it was made for, and made and uploaded again - on `s`, the stream the
+// kernel runs on, which is behind every earlier reader of d_cm - only when they differ.  (cm_tab, cm_key, cm_bd) name what d_cm holds: they are set only once
+// every copy of a new set has been queued, and cleared before the first one, so a call that returns early never leaves a key without its tables.
+// The copies read pageable host memory (as upload_dra's do): hipMemcpyAsync stages such a source before it returns, so the host tables may be freed or replaced
+// by the next call without waiting for the stream.
+static const size_t CM_TONE_OFF = 4096, CM_ENC_OFF = 4096 + XGPU_CM_CURVE_SIZE, CM_FLOATS = 4096 + 2 * XGPU_CM_CURVE_SIZE;
+static bool cm_cached(const xgpu_ctx *c, const xgpu_colour_transform *cm, int bd)
+{
+    const xgpu_colour_transform &k = c->cm_key;
+    return c->cm_tab && c->cm_bd == bd && k.src_primaries == cm->src_primaries && k.src_transfer == cm->src_transfer && k.dst_primaries == cm->dst_primaries &&
+           k.dst_transfer == cm->dst_transfer && k.tone_map == cm->tone_map && k.src_peak == cm->src_peak && k.dst_peak == cm->dst_peak && k.linear_scale == cm->linear_scale;
+}
+static int upload_cm(xgpu_ctx *c, const xgpu_colour_tables_t *t, hipStream_t s)
+{
+    HIPCHK(c, hipMemcpyAsync(c->d_cm, t->lin, sizeof(float) * t->n_lin, hipMemcpyHostToDevice, s));
+    if (t->use_tone) HIPCHK(c, hipMemcpyAsync(c->d_cm + CM_TONE_OFF, t->tone, sizeof(t->tone), hipMemcpyHostToDevice, s));
+    if (t->use_encode) HIPCHK(c, hipMemcpyAsync(c->d_cm + CM_ENC_OFF, t->encode, sizeof(t->encode), hipMemcpyHostToDevice, s));
+    return XGPU_OK;
+}
+static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream);
 int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, void *d_dst, size_t dst_size, void *stream)
+{
+    return output_device(c, pic, dra, f, NULL, d_dst, dst_size, stream);
+}
+int xgpu_pic_output_device_cm(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream)
+{
+    return output_device(c, pic, dra, f, cm, d_dst, dst_size, stream);
+}
+static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream)
 {
     ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
     const char *why = "";
@@ -556,6 +587,21 @@ int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const
         snprintf(c->err, sizeof(c->err), "pic_output_device: %p is not %zu bytes of device memory on device %d", d_dst, need, c->sp.device);
         return XGPU_ERR_INVALID_ARGUMENT;
     }
+    std::unique_ptr<xgpu_colour_tables_t> cm_new;      // a new set of tables: made here, before anything is queued; uploaded and committed below
+    if (cm) {
+        const int bd = c->sp.bit_depth_luma;
+        if (!is_rgb(f->layout)) { snprintf(c->err, sizeof(c->err), "pic_output_device_cm: a colour transform needs one of the RGB layouts"); return XGPU_ERR_INVALID_ARGUMENT; }
+        if (!cm_cached(c, cm, bd)) {
+            cm_new.reset(new (std::nothrow) xgpu_colour_tables_t);
+            const int rc = cm_new ? xgpu_colour_tables(f, cm, bd, cm_new.get()) : XGPU_ERR_OUT_OF_MEMORY;
+            if (rc < 0) {
+                snprintf(c->err, sizeof(c->err), "pic_output_device_cm: transform %d/%d -> %d/%d (primaries / transfer) is not supported or its parameters are invalid",
+                         cm->src_primaries, cm->src_transfer, cm->dst_primaries, cm->dst_transfer);
+                return rc;
+            }
+            if (!c->d_cm && hipMalloc((void **)&c->d_cm, sizeof(float) * CM_FLOATS) != hipSuccess) { snprintf(c->err, sizeof(c->err), "pic_output_device_cm: cannot allocate the tables"); return XGPU_ERR_OUT_OF_MEMORY; }
+        }
+    }
     if (dra) { const int rc = upload_dra(c, dra); if (rc < 0) return rc; }
     hipStream_t s = c->stream;
     if (stream) {
@@ -564,6 +610,13 @@ int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const
         s = (hipStream_t)stream;
         HIPCHK(c, hipEventRecord(c->odev_ev[0], c->stream));      // the picture's kernels (and the DRA tables) -> the caller's stream
         HIPCHK(c, hipStreamWaitEvent(s, c->odev_ev[0], 0));
+    }
+    if (cm_new) {      // behind the wait above: after every kernel that read the previous tables
+        delete c->cm_tab;
+        c->cm_tab = NULL;      // d_cm is about to change: no key names it until all of the new set is queued
+        const int rc = upload_cm(c, cm_new.get(), s);
+        if (rc < 0) return rc;
+        c->cm_tab = cm_new.release(); c->cm_key = *cm; c->cm_bd = c->sp.bit_depth_luma;
     }
     const int *cr = f->crop;
     const DevPic &p = dpic(c, pic);
@@ -610,7 +663,22 @@ int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const
         a.ve[0] = ve[f->chroma_loc >> 1][0]; a.ve[1] = ve[f->chroma_loc >> 1][1];
         a.vo[0] = vo[f->chroma_loc >> 1][0]; a.vo[1] = vo[f->chroma_loc >> 1][1];
         a.dra = dra ? c->d_dra : NULL;
-        if (is_rgb(f->layout)) {
+        if (cm) {
+            CmOutArgs ca;
+            static_cast<RgbOutArgs &>(ca) = a;
+            xgpu_output_format f16 = *f;
+            f16.dtype = XGPU_OUT_U16;      // the code at the coding depth feeds the transform, whatever the output dtype
+            f16.row_pitch = 0;             // (the caller's pitch counts the caller's elements, not 16-bit ones)
+            (void)xgpu_output_coeffs(&f16, bd, ca.coef, &ca.shift, ca.fcoef);
+            ca.maxv = (1 << bd) - 1;
+            const xgpu_colour_tables_t &t = *c->cm_tab;
+            ca.lin = c->d_cm; ca.tone = t.use_tone ? c->d_cm + CM_TONE_OFF : NULL; ca.enc = t.use_encode ? c->d_cm + CM_ENC_OFF : NULL;
+            ca.n_lin = t.n_lin; ca.use_matrix = t.use_matrix;
+            memcpy(ca.m, t.matrix, sizeof(ca.m)); memcpy(ca.luma, t.luma, sizeof(ca.luma));
+            ca.scale = t.scale;
+            ca.outmax = f->dtype == XGPU_OUT_U8 ? 255.f : (float)((1 << bd) - 1);
+            launch_output_cm(ca, f->layout, f->dtype, f->upsample, s);
+        } else if (is_rgb(f->layout)) {
             (void)xgpu_output_coeffs(f, bd, a.coef, &a.shift, a.fcoef);
             a.maxv = f->dtype == XGPU_OUT_U8 ? 255 : (1 << bd) - 1;
             launch_output_rgb(a, f->layout, f->dtype, f->upsample, s);

@@ -341,6 +341,10 @@ struct xgpu_ctx {
     hipEvent_t      out_ready[2], out_done[2];      // conversion kernel finished (kernel stream) / copy to the host finished (download stream)
     int             out_busy[2], out_next;
     int32_t        *d_dra;            // [3][1024] DRA inverse tables of the current output call
+    float          *d_cm;             // xgpu_pic_output_device_cm: the tables of cm_tab on the device (lin[4096], tone, encode)
+    xgpu_colour_tables_t *cm_tab;     // the host's copy, made for (cm_key, cm_bd); NULL until the first call
+    xgpu_colour_transform cm_key;
+    int             cm_bd;
     hipEvent_t      odev_ev[2];       // xgpu_pic_output_device on a caller's stream: picture ready on the context stream / the caller's kernel done (created at the first call)
     xgpu_frame_params fp;
     int             have_frame;
@@ -448,6 +452,14 @@ struct RgbOutArgs {
 };
 void launch_output_rgb(const RgbOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 void launch_output_yuv444(const RgbOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
+// k_output_cm.hip: k_output_rgb's arguments (coef / shift / maxv: those of the U16 form, whatever the dtype) and the colour transform's
+struct CmOutArgs : RgbOutArgs {
+    const float *lin, *tone, *enc;  // device tables: linear light per code [n_lin]; g(Y) or NULL (scale instead); the destination curve or NULL (linear output)
+    int      n_lin, use_matrix;
+    float    m[9], luma[3], scale;  // source -> destination primaries, luminance weights of the source primaries, linear_scale
+    float    outmax;                // integer dtypes: 2^D - 1
+};
+void launch_output_cm(const CmOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 // k_output_yuv.hip (k_output_semiplanar): NV12 / P016 - xgpu_pic_output's samples, luma rows then rows of interleaved Cb Cr
 struct SemiPlanarArgs {
     const int16_t *y, *u, *v;       // first sample of the cropped area of every plane

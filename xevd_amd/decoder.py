@@ -109,7 +109,7 @@ class XgpuDecoder:
         return C.byref(d), (keep, d)
 
     def pic_output_tensor(self, pic, layout="rgb", channels_last=False, dtype=None, matrix=1, full_range=False, chroma_loc=0, upsample="linear",
-                          crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, out_bit_depth=0):
+                          crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, out_bit_depth=0, colour=None):
         """The picture in device memory as a torch tensor on cuda:{device}, converted on the device (xgpu_pic_output_device) on torch's current
         stream - no host round trip.  layout "rgb": [3, H, W] (channels_last: [H, W, 3]) R'G'B' (bgr: B, G, R) with dtype torch.uint8, torch.int16 /
         torch.uint16 (values at the coding depth), torch.float16, torch.bfloat16 or torch.float32 (0..1), through `matrix` (H.273 MatrixCoefficients
@@ -120,6 +120,10 @@ class XgpuDecoder:
         D = out_bit_depth (0 = the coding depth; 10 is P010, 12 is P012); "yuv444": [3, H, W] (channels_last: [H, W, 3]) Y, Cb, Cr at luma resolution
         (chroma upsampled by upsample / chroma_loc as for "rgb"): torch.uint8 (8-bit samples), 16-bit integers (the coding depth) or floats - H.273's
         E'Y in 0..1, E'Cb and E'Cr in -0.5..0.5 by full_range.  out_bit_depth: "nv12" / "p016" only; for "rgb" / "yuv444" it must be 0 or the coding depth.
+        colour: layout "rgb" only - dict(src_primaries, src_transfer, dst_primaries, dst_transfer, tone_map, src_peak, dst_peak, linear_scale) (the keyword
+        arguments of abi.make_colour_transform: H.273 code points, peaks in cd/m2): the R'G'B' of the stream's colour space linearised, taken to the
+        destination primaries, tone-mapped or scaled, and re-encoded with the destination transfer (8 = linear light) in the same kernel
+        (xgpu_pic_output_device_cm).
         crop: (left, right, top, bottom), even.  out: a tensor to fill instead (its strides may pad the rows: row_pitch); it is also what is returned."""
         import torch
         if dtype is None:
@@ -131,6 +135,8 @@ class XgpuDecoder:
             raise ValueError(f"unsupported output dtype {dtype}")
         if upsample not in ("linear", "nearest"):
             raise ValueError(f"upsample must be 'linear' or 'nearest', not {upsample!r}")
+        if colour is not None and layout != "rgb":
+            raise ValueError(f"colour: a colour transform needs layout 'rgb', not {layout!r}")
         cl, cr, ct, cb = (int(v) for v in crop)
         w, h = self.width - cl - cr, self.height - ct - cb
         dev = torch.device("cuda", self.sp.device)
@@ -193,8 +199,13 @@ class XgpuDecoder:
                 self._side = torch.cuda.Stream(device=dev)
             run = self._side
             run.wait_stream(cur)
-        self._chk(self.lib.xgpu_pic_output_device(self.ctx, pic, dl, C.byref(fmt), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
-                  "xgpu_pic_output_device")
+        if colour is None:
+            self._chk(self.lib.xgpu_pic_output_device(self.ctx, pic, dl, C.byref(fmt), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
+                      "xgpu_pic_output_device")
+        else:
+            cm = abi.make_colour_transform(**colour)
+            self._chk(self.lib.xgpu_pic_output_device_cm(self.ctx, pic, dl, C.byref(fmt), C.byref(cm), C.c_void_p(out.data_ptr()), nbytes,
+                                                         C.c_void_p(run.cuda_stream)), "xgpu_pic_output_device_cm")
         if run is not cur:
             cur.wait_stream(run)
         return out

@@ -75,11 +75,41 @@ class StreamDecoder:
         kw.update(options)
         return kw
 
-    def pictures(self, download=True, output_bit_depth=None, tensor=None):
+    # `to=` presets: (ColourPrimaries, TransferCharacteristics) of the output (H.273; transfer 8 = linear light)
+    COLOUR_PRESETS = {"srgb": (1, 13), "bt709": (1, 1), "linear-bt709": (1, 8), "bt2020": (9, 14), "linear-bt2020": (9, 8), "pq-bt2020": (9, 16),
+                      "hlg-bt2020": (9, 18), "p3-d65": (12, 13), "linear-p3-d65": (12, 8)}
+
+    @classmethod
+    def colour_transform(cls, colour, to):
+        """the `colour=` argument of XgpuDecoder.pic_output_tensor for a stream whose VUI says `colour` (params["colour"]) and the destination `to`: a preset
+        name of COLOUR_PRESETS, or dict(to=name, ...) with any of tone_map, src_peak, dst_peak, linear_scale.  The source side is the VUI's colour_primaries /
+        transfer_characteristics; where the VUI is absent or says 2 (unspecified): BT.709 / BT.709, as for the matrix.  tone_map defaults to on from an HDR
+        source (PQ, HLG) to an SDR-encoded destination (neither linear nor PQ / HLG), else off."""
+        opts = {"to": to} if isinstance(to, str) else dict(to)
+        name = opts.pop("to")
+        if name not in cls.COLOUR_PRESETS:
+            raise ValueError(f"to: unknown colour preset {name!r} (one of {', '.join(sorted(cls.COLOUR_PRESETS))})")
+        sp = st = 1
+        if colour["vui_present"]:
+            sp = colour["colour_primaries"] if colour["colour_primaries"] != 2 else 1
+            st = colour["transfer_characteristics"] if colour["transfer_characteristics"] != 2 else 1
+        dp, dt = cls.COLOUR_PRESETS[name]
+        cm = {"src_primaries": sp, "src_transfer": st, "dst_primaries": dp, "dst_transfer": dt, "tone_map": st in (16, 18) and dt not in (8, 16, 18)}
+        for k, v in opts.items():
+            if k not in ("tone_map", "src_peak", "dst_peak", "linear_scale"):
+                raise ValueError(f"to: unknown option {k!r}")
+            cm[k] = v
+        return cm
+
+    def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
-        current stream, by default with the colour description of the stream's VUI (tensor_options) and the SPS crop when apply_crop is set"""
+        current stream, by default with the colour description of the stream's VUI (tensor_options) and the SPS crop when apply_crop is set.
+        to="srgb" | "bt709" | "linear-bt709" | "linear-bt2020" | "pq-bt2020" | ... (colour_transform; with tensor=, layout "rgb"): the picture in that colour
+        space, from the primaries and transfer characteristics of the stream's VUI"""
+        if to is not None and tensor is None:
+            raise ValueError("to: needs tensor=dict(...)")
         q = queue.Queue(maxsize=self.prefetch)
         th = threading.Thread(target=self._producer, args=(q,), daemon=True)
         th.start()
@@ -105,6 +135,8 @@ class StreamDecoder:
             if tensor is not None:
                 kw = self.tensor_options(p, tensor)
                 kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
+                if to is not None:
+                    kw.setdefault("colour", self.colour_transform(p["colour"], to))
                 with self._lock:
                     planes = dec.pic_output_tensor(cur, **kw)
             elif download and output_bit_depth is not None:
@@ -154,11 +186,11 @@ class StreamDecoder:
                 self._dec.close()
                 self._dec = None
 
-    def output_order(self, output_bit_depth=None, tensor=None):
+    def output_order(self, output_bit_depth=None, tensor=None, to=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
-        pictures takes it) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape"""
+        pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape"""
         out, epoch = [], -1
-        for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor):
+        for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to):
             if p["is_idr"]:
                 epoch += 1
             if tensor is not None:
