@@ -20,6 +20,7 @@
  *   xgpu_pic_output               <- xevd_pull + the application's imgb_cpy_codec_to_out (crop fields xevd.c:2058-2069,
  *                                    bit-depth conversions app/xevd_app_util.h:441-552,656-700)
  *   xgpu_pic_output_device        (no counterpart: the picture as YUV or R'G'B' into the caller's device memory)
+ *   xgpu_frame_side_info          (no counterpart in the library; FFmpeg's export_mvs is the usual example: motion vectors, modes, QP of the picture decoded last)
  *
  * plus fine-grained shims with the reference's per-block function-table signatures
  * (XEVD_MC_L / XEVD_MC_C src_base/xevd_mc.h:47-49, XEVD_ITXB src_base/xevd_def.h:360, fn_recon :1466)
@@ -327,6 +328,49 @@ int    xgpu_colour_tables(const xgpu_output_format *f, const xgpu_colour_transfo
    kernel runs on, ordered like the DRA tables - only when `cm` or the depth differ from the previous call's. */
 int    xgpu_pic_output_device_cm(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm,
                                  void *d_dst, size_t dst_size, void *stream);
+/* ---- coding side information (k_side_info.hip): what the decoder knows about a picture besides its samples - motion vectors per 4x4 luma unit, the
+   reference each one points at, intra / inter / skip / IBC, QP, coded-residual flag, block edges - read out of the SCU map the in-loop filters read
+   (the reference's map_scu / map_refi / map_mv, src_base/xevd_def.h:372-438).
+   The map is per CONTEXT, not per picture: the next picture's reconstruction overwrites it.  So the information belongs to THE PICTURE DECODED LAST and is
+   taken at decoding time: `pic` must be the slot of the picture whose xgpu_frame_end came last (and returned XGPU_OK), with no xgpu_frame_begin since -
+   another slot, no picture yet, or a frame open: XGPU_ERR_INVALID_ARGUMENT, nothing queued.
+     XGPU_SIDE_BLOCKS   nine int16 planes of h_scu x w_scu (height / 4, width / 4), plane p at p * h_scu * row_pitch; unit (j, i) covers luma samples
+                        [4i, 4i + 4) x [4j, 4j + 4) of the UNCROPPED picture (crop must be 0); dtype XGPU_OUT_U16 (the element size; the values are signed):
+                          0, 1  list 0 vector x, y as the map holds it: quarter luma samples, unclipped       2, 3  list 1 vector x, y
+                          4, 5  refp_poc[refi][list] - poc of the frame parameters, saturated to int16; 0 where refi < 0 (a reference never has the
+                                picture's own POC: 0 is unambiguous)
+                          6     XGPU_MODE_INTRA 0, _INTER 1, _SKIP 2, _IBC 6 (the map cannot tell direct mode from inter: 1)
+                          7     the QP the deblocking filter reads (bits 16-22 of map_scu: qp_y - 6 * (bit_depth - 8))
+                          8     bit 0 luma cbf (map_scu bit 24), bit 1 / 2 the unit's left / top edge is a CU border or a 64-sample transform border inside a
+                                wider CU, bit 3 ats_inter != 0
+                        Intra units: vectors 0, POC planes 0.  IBC units: the block vector in planes 0 / 1 as the batch gave it - in WHOLE luma
+                        samples, not quarter samples (xgpu_cu_batch.mv of an XGPU_MODE_IBC CU) -, POC planes 0.  Affine CUs: one vector per sub-block (xevdm_set_affine_mvf).  DMVR-refined CUs: the vectors the
+                        sequence's deblocking filter reads - UNREFINED with tool_addb, refined with the baseline filter of the Main library.
+     XGPU_SIDE_FLOW_PLANAR / _INTERLEAVED   a dense motion field at luma resolution: 2 channels (x, y) per requested list (lists 1: list 0, 2: list 1, 3: both -
+                        list 0 first), [C, H, W] planar (plane k at k * H * row_pitch) or [H, W, C], H x W cropped; pixel (y, x) takes the unit
+                        ((y + crop_top) >> 2, (x + crop_left) >> 2).  Value in float32, every operation rounded on its own: v = float32(mv) * 0.25f (luma
+                        samples); with per_poc v = v / float32(dpoc), one IEEE division, dpoc the unsaturated POC difference of planes 4 / 5; a list the unit
+                        does not use (intra and IBC units included) gives +0.0.  XGPU_OUT_F16: that value rounded to nearest even.  The sign is the codec's: the
+                        reference block lies at position + v.
+   The exact contract: INTEGRATION.md section 8c; tests/side_info_ref.py restates it in numpy. */
+#define XGPU_SIDE_BLOCKS           0
+#define XGPU_SIDE_FLOW_PLANAR      1
+#define XGPU_SIDE_FLOW_INTERLEAVED 2
+typedef struct xgpu_side_format {
+    int layout;        /* XGPU_SIDE_BLOCKS | XGPU_SIDE_FLOW_PLANAR | XGPU_SIDE_FLOW_INTERLEAVED */
+    int dtype;         /* BLOCKS: XGPU_OUT_U16 (the planes are int16); FLOW: XGPU_OUT_F16 | _F32 */
+    int lists;         /* FLOW: 1 = list 0, 2 = list 1, 3 = both (BLOCKS: not read) */
+    int per_poc;       /* FLOW: 0 | 1 (BLOCKS: not read) */
+    int crop[4];       /* FLOW: left, right, top, bottom luma samples, even; BLOCKS: all 0 */
+    size_t row_pitch;  /* bytes between rows, a multiple of the element size; 0 = tight */
+} xgpu_side_format;
+/* Host only, no context: the bytes format `f` needs at d_dst for a picture of width x height (the uncropped size, multiples of 8), the last row tight; 0:
+   invalid format or size.  BLOCKS: (9 h_scu - 1) * pitch + 2 w_scu; FLOW planar: (C H - 1) * pitch + W * es, interleaved: (H - 1) * pitch + C W * es. */
+size_t xgpu_side_info_size(const xgpu_side_format *f, int width, int height);
+/* Non-blocking.  d_dst and stream as xgpu_pic_output_device takes them: device memory of the context's device, aligned to the element size, >=
+   xgpu_side_info_size bytes (checked before anything is queued); stream = NULL: the context's stream; else the kernel runs on `stream` behind the picture's
+   kernels, and the context's stream waits for it before the next picture may write the map.  Reads the map only: the picture is not touched. */
+int    xgpu_frame_side_info(xgpu_ctx *ctx, int pic, const xgpu_side_format *f, void *d_dst, size_t dst_size, void *stream);
 /* The picture signature on the device: the MD5 of every plane over its rows of width x 2 bytes of 16-bit samples (8-bit pictures too), as xevd_md5_imgb makes it
    (src_base/xevd_util.c:985-1002) and xevd_picbuf_check_signature compares it with the SEI (:1557-1572) - of the DRA-mapped picture when `dra` is given, which is
    what the Main decoder signs when the PPS names a DRA parameter set (src_main/xevdm.c:3256-3287).  digest[plane] = the 16 bytes of the SEI payload.  Blocking; the

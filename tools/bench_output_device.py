@@ -2,6 +2,8 @@
 events on the output stream (median of --iters launches after warm-up), against the plain device copy rate of the same run
 (xgpu_measure_copy_bw).  Bytes are algorithmic: 3 bytes of samples read per pixel (luma + two quarter-size chroma planes, 16 bit) and what the
 format writes.  Prints one line per form and a JSON line; --out also writes the JSON to a file.
+The side-information forms (xgpu_frame_side_info: k_side_blocks / k_side_flow) follow, on a picture decoded from a synthetic B-picture batch: 16 bytes per
+4x4 unit read + what the form writes, and the same flow made in torch from the BLOCKS tensor (repeat_interleave twice, crop, scale, cast).
 
     python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--out out/output_device.json]
 """
@@ -28,6 +30,30 @@ def torch_transform(torch, rgb, to_srgb):
         return lin
     enc = torch.where(lin < 0.0031308, 12.92 * lin, 1.055 * lin.pow(1.0 / 2.4) - 0.055)
     return (enc * 255.0).round().to(torch.uint8)
+
+
+def torch_flow(torch, blocks, crop, dtype):
+    """the dense field of lists 0 and 1 in luma samples from the BLOCKS tensor, in torch: what a caller does without k_side_flow"""
+    cl, cr, ct, cb = crop
+    v = blocks[:4]
+    used = (blocks[4:6] != 0).repeat_interleave(2, 0)
+    v = torch.where(used, v.to(torch.float32) * 0.25, torch.zeros((), device=v.device))
+    v = v.repeat_interleave(4, 1).repeat_interleave(4, 2)
+    return v[:, ct:v.shape[1] - cb, cl:v.shape[2] - cr].to(dtype).contiguous()
+
+
+def timed(torch, s, fn, n, warm=5, sleep=True):
+    for _ in range(warm):
+        fn()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    if sleep:
+        torch.cuda._sleep(int(3e8))      # the GPU waits while the host queues every timed launch: the events then bracket device time only
+    for e0, e1 in ev:
+        e0.record(s)
+        fn()
+        e1.record(s)
+    torch.cuda.synchronize()
+    return float(np.median([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]))
 
 
 def main():
@@ -63,7 +89,7 @@ def main():
               ("cm_pq2020_linear709_f16_planar", dict(dtype=torch.float16, matrix=9, colour=to_lin), 6),
               ("cm_pq2020_linear709_f32_planar", dict(dtype=torch.float32, matrix=9, colour=to_lin), 12)]
     res = {"width": w, "height": h, "bit_depth": bd, "iters": a.iters, "forms": {}}
-    with XgpuDecoder(w, h, bd, device=0, max_pics=2) as dec:
+    with XgpuDecoder(w, h, bd, device=0, max_pics=3) as dec:
         pic = dec.pic_alloc()
         dec.pic_upload(pic, planes)
         copy_gbps = dec.measure_copy_bw(1 << 30, 20)
@@ -102,6 +128,41 @@ def main():
             us = float(np.median([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]))
             res["forms"][name] = {"us": round(us, 2), "launches": n, "note": "excludes the plain f32 output it starts from"}
             print(f"{name:40s} {us:9.1f} us (torch, after rgb_f32_planar)")
+        # ---- coding side information of a decoded picture: the uploaded picture is both references of a synthetic B picture
+        from xevd_amd import synth
+        batch = synth.gen_frame(np.random.default_rng(1), w, h, bd, inter_frac=0.9, bi_frac=0.5, coded_frac=0.6, n_refs=(1, 1), qp_range=(22, 37), mv_sigma_px=8.0, oob_frac=0.05)
+        cur = dec.pic_alloc()
+        hb = dec.batch_create(batch)
+        dec.decode_picture(cur, 8, {(0, 0): (pic, 4), (0, 1): (pic, 16)}, hb, deblock=True)
+        dec.sync()
+        n_units = (w // 4) * (h // 4)
+        crop = (0, 0, 0, 0)
+        side = [("side_blocks", dict(), 18 * n_units),
+                ("side_flow_f16_both_planar", dict(kind="flow", dtype=torch.float16), 8 * w * h),
+                ("side_flow_f16_both_interleaved", dict(kind="flow", dtype=torch.float16, channels_last=True), 8 * w * h),
+                ("side_flow_f16_list0_planar", dict(kind="flow", dtype=torch.float16, lists=0), 4 * w * h),
+                ("side_flow_f32_both_planar", dict(kind="flow", dtype=torch.float32), 16 * w * h),
+                ("side_flow_f32_both_interleaved", dict(kind="flow", dtype=torch.float32, channels_last=True), 16 * w * h),
+                ("side_flow_f32_list0_planar", dict(kind="flow", dtype=torch.float32, lists=0), 8 * w * h),
+                ("side_flow_f16_both_planar_per_poc", dict(kind="flow", dtype=torch.float16, per_poc=True), 8 * w * h)]
+        for name, kw, wbytes in side:
+            out = dec.frame_side_info(cur, **kw)
+            us = timed(torch, s, lambda: dec.frame_side_info(cur, out=out, **kw), a.iters)
+            nbytes = int(16 * n_units + wbytes)
+            gbps = nbytes / (us * 1e-6) / 1e9
+            res["forms"][name] = {"us": round(us, 2), "bytes": nbytes, "written": int(wbytes), "gbps": round(gbps, 1), "write_gbps": round(wbytes / (us * 1e-6) / 1e9, 1),
+                                  "frac_copy": round(gbps / copy_gbps, 3)}
+            print(f"{name:36s} {us:9.1f} us  {nbytes / 1e6:7.1f} MB  {gbps:7.1f} GB/s  {gbps / copy_gbps:5.2f} of copy ({copy_gbps:.0f} GB/s)")
+        blocks = dec.frame_side_info(cur)
+        for name, dt in (("torch_flow_f16_both_planar_from_blocks", torch.float16), ("torch_flow_f32_both_planar_from_blocks", torch.float32)):
+            n = max(a.iters // 10, 5)
+            us = timed(torch, s, lambda: torch_flow(torch, blocks, crop, dt), n, warm=2, sleep=False)
+            res["forms"][name] = {"us": round(us, 2), "launches": n, "note": "excludes the BLOCKS export it starts from"}
+            print(f"{name:40s} {us:9.1f} us (torch, after side_blocks)")
+            kdt = torch.float16 if dt == torch.float16 else torch.float32
+            same = torch.equal(torch_flow(torch, blocks, crop, dt).view(torch.int16 if dt == torch.float16 else torch.int32),
+                               dec.frame_side_info(cur, kind="flow", dtype=kdt).view(torch.int16 if dt == torch.float16 else torch.int32))
+            res["forms"][name]["equals_kernel"] = bool(same)
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

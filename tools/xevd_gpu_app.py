@@ -21,25 +21,34 @@ def main():
                     help="nv12: 8-bit semi-planar; p010: 10 bit in 16-bit little-endian words, semi-planar (both ignore --output-bit-depth)")
     ap.add_argument("--to", default=None, help="write interleaved 8-bit RGB frames in this colour space instead (srgb, bt709, pq-bt2020, ...: "
                     "StreamDecoder.COLOUR_PRESETS), converted on the device from the primaries / transfer characteristics of the stream's VUI")
+    ap.add_argument("--side-info", default=None, metavar="FILE", help="also write the coding side information of every picture, in DECODING order: a text line "
+                    "'POC h_scu w_scu', then nine planes of h_scu x w_scu little-endian int16 (list 0 / 1 vectors, POC distances, mode, QP, flags: INTEGRATION.md 8c)")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
     data = open(args.input, "rb").read()
     t0 = time.perf_counter()
+    side = {} if args.side_info else None
     # crop-free output like the reference application; bit-depth conversion and plane packing run on the device (xgpu_pic_output)
     if args.to is not None:
         import torch
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side)
     elif args.pix_fmt == "yuv420p":
-        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth)
+        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side)
     else:      # the same pictures as semi-planar surfaces (xgpu_pic_output_device into a torch tensor, copied to the host picture by picture)
         import torch
         opts = dict(layout="nv12", dtype=torch.uint8) if args.pix_fmt == "nv12" else dict(layout="p016", dtype=torch.int16, out_bit_depth=10)
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side)
     dt = time.perf_counter() - t0
     if args.output:
         with open(args.output, "wb") as f:
             for _, frame in pics:
                 f.write(frame.tobytes())
+    if args.side_info:
+        with open(args.side_info, "wb") as f:
+            for p, _ in sorted(pics, key=lambda t: t[0]["decode_index"]):
+                b = p["side_info"]
+                f.write(f"{p['poc']} {b.shape[1]} {b.shape[2]}\n".encode())
+                f.write(b.astype("<i2").tobytes())
     print(f"{len(pics)} pictures, {len(pics) / dt:.1f} pictures/s (parse + upload + kernels + download)", file=sys.stderr)
 
 

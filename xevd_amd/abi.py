@@ -56,6 +56,25 @@ def make_output_format(layout=OUT_RGB_PLANAR, dtype=OUT_U8, bgr=False, out_bit_d
     return f
 
 
+SIDE_BLOCKS, SIDE_FLOW_PLANAR, SIDE_FLOW_INTERLEAVED = 0, 1, 2
+MODE_IBC = 6
+
+
+class SideFormat(C.Structure):
+    _fields_ = [("layout", C.c_int), ("dtype", C.c_int), ("lists", C.c_int), ("per_poc", C.c_int), ("crop", C.c_int * 4), ("row_pitch", C.c_size_t)]
+
+
+def make_side_format(layout=SIDE_BLOCKS, dtype=OUT_U16, lists=3, per_poc=False, crop=(0, 0, 0, 0), row_pitch=0):
+    """xgpu_side_format (include/xevd_hip.h): BLOCKS - nine int16 planes per 4x4 unit (dtype OUT_U16, no crop); FLOW - a dense motion field, OUT_F16 / OUT_F32,
+    lists 1 = list 0, 2 = list 1, 3 = both"""
+    f = SideFormat()
+    f.layout, f.dtype, f.lists, f.per_poc = int(layout), int(dtype), int(lists), int(per_poc)
+    for i in range(4):
+        f.crop[i] = int(crop[i])
+    f.row_pitch = int(row_pitch)
+    return f
+
+
 CM_CURVE_U0, CM_CURVE_SIZE = 0x1F800000, 64 * 32 + 3
 
 
@@ -254,6 +273,8 @@ _EXPORTS = {
     "xgpu_output_coeffs": (C.c_int, [C.POINTER(OutputFormat), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "xgpu_colour_tables": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ColourTransform), C.c_int, C.POINTER(ColourTables)]),
     "xgpu_pic_output_device_cm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ColourTransform), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_side_info_size": (C.c_size_t, [C.POINTER(SideFormat), C.c_int, C.c_int]),
+    "xgpu_frame_side_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SideFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "xgpu_host_free": (None, [C.c_void_p, C.c_void_p]),
     "xgpu_batch_wait_upload": (C.c_int, [C.c_void_p, C.c_void_p]),

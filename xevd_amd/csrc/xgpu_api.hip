@@ -120,7 +120,7 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
     c->sp = *sp;
     c->sp.chroma_qp_table[0] = c->sp.chroma_qp_table[1] = NULL;
     c->builder_threads = 1;
-    c->err[0] = 0; c->timing = 0; c->have_frame = 0; c->d_maps = NULL; c->d_dra = NULL; c->d_cm = NULL; c->cm_tab = NULL; c->d_ctb_flag = NULL; c->stream = 0; c->up_stream = 0; c->down_stream = 0; c->side_stream = 0; c->after_inter = 0; c->have_after_inter = 0; c->where = 0; c->addb_pending = 0;
+    c->err[0] = 0; c->timing = 0; c->have_frame = 0; c->side_pic = -1; c->d_maps = NULL; c->d_dra = NULL; c->d_cm = NULL; c->cm_tab = NULL; c->d_ctb_flag = NULL; c->stream = 0; c->up_stream = 0; c->down_stream = 0; c->side_stream = 0; c->after_inter = 0; c->have_after_inter = 0; c->where = 0; c->addb_pending = 0;
     c->fork_ev = c->join_ev = 0;
     c->intra_small_min = getenv("XEVD_HIP_INTRA_SMALL_MIN") ? std::max(1, atoi(getenv("XEVD_HIP_INTRA_SMALL_MIN"))) : 2048;      // (k_intra.hip: launch_intra; read per context, tests set 1)
     c->addb_scalar = getenv("XEVD_HIP_ADDB_SCALAR") != NULL;
@@ -550,6 +550,24 @@ static int upload_cm(xgpu_ctx *c, const xgpu_colour_tables_t *t, hipStream_t s)
     if (t->use_encode) HIPCHK(c, hipMemcpyAsync(c->d_cm + CM_ENC_OFF, t->encode, sizeof(t->encode), hipMemcpyHostToDevice, s));
     return XGPU_OK;
 }
+// the destination of an output into device memory must be device memory of this context's device, and the allocation must hold `need` bytes from d_dst on
+static int check_device_dst(xgpu_ctx *c, const char *what, void *d_dst, size_t need)
+{
+    HIPCHK(c, hipSetDevice(c->sp.device));
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    const hipError_t pe = hipPointerGetAttributes(&at, d_dst);
+    if (pe != hipSuccess) (void)hipGetLastError();      // an unknown (host) pointer: not an error of the runtime's state
+    void *base = NULL;
+    size_t range = 0;
+    const bool dev = pe == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->sp.device;
+    if (dev && hipMemGetAddressRange(&base, &range, d_dst) != hipSuccess) { (void)hipGetLastError(); base = NULL; }
+    if (!dev || !base || (uint8_t *)d_dst + need > (uint8_t *)base + range) {
+        snprintf(c->err, sizeof(c->err), "%s: %p is not %zu bytes of device memory on device %d", what, d_dst, need, c->sp.device);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    return XGPU_OK;
+}
 static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream);
 int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, void *d_dst, size_t dst_size, void *stream)
 {
@@ -573,20 +591,7 @@ static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const x
         snprintf(c->err, sizeof(c->err), "pic_output_device: destination of %zu bytes at %p, the format needs %zu bytes aligned to %zu", dst_size, d_dst, need, es);
         return XGPU_ERR_INVALID_ARGUMENT;
     }
-    HIPCHK(c, hipSetDevice(c->sp.device));
-    // the destination must be device memory of this context's device, and the allocation must hold `need` bytes from d_dst on
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof(at));
-    const hipError_t pe = hipPointerGetAttributes(&at, d_dst);
-    if (pe != hipSuccess) (void)hipGetLastError();      // an unknown (host) pointer: not an error of the runtime's state
-    void *base = NULL;
-    size_t range = 0;
-    const bool dev = pe == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->sp.device;
-    if (dev && hipMemGetAddressRange(&base, &range, d_dst) != hipSuccess) { (void)hipGetLastError(); base = NULL; }
-    if (!dev || !base || (uint8_t *)d_dst + need > (uint8_t *)base + range) {
-        snprintf(c->err, sizeof(c->err), "pic_output_device: %p is not %zu bytes of device memory on device %d", d_dst, need, c->sp.device);
-        return XGPU_ERR_INVALID_ARGUMENT;
-    }
+    { const int rc = check_device_dst(c, "pic_output_device", d_dst, need); if (rc < 0) return rc; }
     std::unique_ptr<xgpu_colour_tables_t> cm_new;      // a new set of tables: made here, before anything is queued; uploaded and committed below
     if (cm) {
         const int bd = c->sp.bit_depth_luma;
@@ -696,6 +701,102 @@ static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const x
     return XGPU_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ coding side information of the picture decoded last
+// the format alone and the size it needs for a picture of width x height; 0: invalid, `why` says which field
+static size_t side_size(const xgpu_side_format *f, int width, int height, const char **why)
+{
+    *why = "format is NULL";
+    if (!f) return 0;
+    *why = "picture size must be positive multiples of 8";
+    if (width <= 0 || height <= 0 || ((width | height) & 7)) return 0;
+    *why = "crop offsets must be even and >= 0";
+    for (int i = 0; i < 4; i++) if (f->crop[i] < 0 || (f->crop[i] & 1)) return 0;
+    if (f->layout == XGPU_SIDE_BLOCKS) {
+        *why = "BLOCKS: dtype XGPU_OUT_U16 (int16 planes), no crop, row_pitch a multiple of 2 and at least a row";
+        if (f->dtype != XGPU_OUT_U16 || f->crop[0] || f->crop[1] || f->crop[2] || f->crop[3] || (f->row_pitch & 1)) return 0;
+        const size_t w_scu = width >> 2, h_scu = height >> 2, row = w_scu * 2, pitch = f->row_pitch ? f->row_pitch : row;
+        if (pitch < row) return 0;
+        return (9 * h_scu - 1) * pitch + row;
+    }
+    *why = "layout must be XGPU_SIDE_BLOCKS, XGPU_SIDE_FLOW_PLANAR or XGPU_SIDE_FLOW_INTERLEAVED";
+    if (f->layout != XGPU_SIDE_FLOW_PLANAR && f->layout != XGPU_SIDE_FLOW_INTERLEAVED) return 0;
+    *why = "FLOW: dtype XGPU_OUT_F16 or XGPU_OUT_F32, lists 1..3, per_poc 0 or 1, row_pitch a multiple of the element size";
+    if ((f->dtype != XGPU_OUT_F16 && f->dtype != XGPU_OUT_F32) || f->lists < 1 || f->lists > 3 || (f->per_poc & ~1)) return 0;
+    const size_t es = (size_t)elem_size(f->dtype), ch = f->lists == 3 ? 4 : 2;
+    if (f->row_pitch % es) return 0;
+    *why = "crop leaves no picture";
+    if (f->crop[0] + f->crop[1] >= width || f->crop[2] + f->crop[3] >= height) return 0;
+    const size_t w = width - f->crop[0] - f->crop[1], h = height - f->crop[2] - f->crop[3];
+    const bool planar = f->layout == XGPU_SIDE_FLOW_PLANAR;
+    const size_t row = (planar ? w : ch * w) * es, pitch = f->row_pitch ? f->row_pitch : row;
+    *why = "row_pitch is shorter than a row";
+    if (pitch < row) return 0;
+    return ((planar ? ch * h : h) - 1) * pitch + row;
+}
+size_t xgpu_side_info_size(const xgpu_side_format *f, int width, int height)
+{
+    const char *why;
+    return side_size(f, width, height, &why);
+}
+// The SCU map is per context: it holds the side information of the picture whose xgpu_frame_end came last (c->side_pic) until the next xgpu_frame_begin -
+// the next picture's k_inter overwrites it.  Checks first, then the order of output_device: on a caller's stream the kernel runs behind the picture's kernels
+// (the side stream of k_affine / k_dmvr has been joined by then) and the context's stream waits for it before the next k_inter may write the map.
+int xgpu_frame_side_info(xgpu_ctx *c, int pic, const xgpu_side_format *f, void *d_dst, size_t dst_size, void *stream)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, d_dst != NULL);
+    if (c->have_frame || c->side_pic < 0 || pic != c->side_pic || !valid_pic(c, pic)) {
+        snprintf(c->err, sizeof(c->err), "frame_side_info: slot %d is not the picture decoded last (%s): the SCU map belongs to the picture whose xgpu_frame_end came last, until the next xgpu_frame_begin",
+                 pic, c->have_frame ? "a frame is open" : c->side_pic < 0 ? "no picture yet" : "another slot");
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    const char *why = "";
+    const size_t need = side_size(f, c->sp.width, c->sp.height, &why);
+    if (need == 0) { snprintf(c->err, sizeof(c->err), "frame_side_info: invalid format: %s", why); return XGPU_ERR_INVALID_ARGUMENT; }
+    const size_t es = (size_t)elem_size(f->dtype);
+    if (dst_size < need || ((uintptr_t)d_dst % es)) {
+        snprintf(c->err, sizeof(c->err), "frame_side_info: destination of %zu bytes at %p, the format needs %zu bytes aligned to %zu", dst_size, d_dst, need, es);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    { const int rc = check_device_dst(c, "frame_side_info", d_dst, need); if (rc < 0) return rc; }
+    hipStream_t s = c->stream;
+    if (stream) {
+        for (int i = 0; i < 2; i++)
+            if (!c->odev_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->odev_ev[i], hipEventDisableTiming));
+        s = (hipStream_t)stream;
+        HIPCHK(c, hipEventRecord(c->odev_ev[0], c->stream));      // the picture's kernels -> the caller's stream
+        HIPCHK(c, hipStreamWaitEvent(s, c->odev_ev[0], 0));
+    }
+    SideArgs a;
+    memset(&a, 0, sizeof(a));
+    a.maps = c->d_maps; a.w_scu = c->w_scu; a.h_scu = c->h_scu;
+    a.dst = (uint8_t *)d_dst;
+    a.poc = c->fp.poc;
+    for (int l = 0; l < 2; l++)
+        for (int i = 0; i < XGPU_MAX_REFS; i++) a.refp_poc[i][l] = i < c->fp.num_refp[l] ? c->fp.refp_poc[i][l] : c->fp.poc;      // (an index past the list: distance 0)
+    if (f->layout == XGPU_SIDE_BLOCKS) {
+        a.pitch = f->row_pitch ? f->row_pitch : (size_t)c->w_scu * 2;
+        a.plane = a.pitch * c->h_scu;
+        a.aligned = (((uintptr_t)d_dst | a.pitch | a.plane) & 15) == 0;
+        launch_side_blocks(a, s);
+    } else {
+        const bool planar = f->layout == XGPU_SIDE_FLOW_PLANAR;
+        const int n_lists = f->lists == 3 ? 2 : 1;
+        a.w = c->sp.width - f->crop[0] - f->crop[1]; a.h = c->sp.height - f->crop[2] - f->crop[3];
+        a.crop_l = f->crop[0]; a.crop_t = f->crop[2];
+        a.list0 = f->lists == 2 ? 1 : 0; a.per_poc = f->per_poc;
+        a.pitch = f->row_pitch ? f->row_pitch : (size_t)a.w * es * (planar ? 1 : 2 * n_lists);
+        a.plane = a.pitch * a.h;
+        a.aligned = (((uintptr_t)d_dst | a.pitch | a.plane) & 15) == 0;
+        launch_side_flow(a, planar, f->dtype, n_lists, s);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (stream) {
+        HIPCHK(c, hipEventRecord(c->odev_ev[1], s));      // the context's stream does not let the next picture's k_inter write the map before the kernel is done
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->odev_ev[1], 0));
+    }
+    return XGPU_OK;
+}
+
 // The picture signature on the device (k_md5.hip): the planes packed as the signature's message behind the picture's kernels (k_output, samples as they are), the three
 // chains on the transfer stream - the kernel stream is free for the next picture while they run -, 48 bytes to the host.  Blocking.
 int xgpu_pic_md5(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, uint8_t digest[3][16])
@@ -732,6 +833,7 @@ int xgpu_frame_begin(xgpu_ctx *c, const xgpu_frame_params *fp)
     }
     c->fp = *fp;
     c->have_frame = 1;
+    c->side_pic = -1;      // the map is about to be overwritten
     c->where = 0;
     c->pad_done = 0;
     c->addb_pending = 0;
@@ -742,7 +844,9 @@ int xgpu_frame_begin(xgpu_ctx *c, const xgpu_frame_params *fp)
 int xgpu_frame_end(xgpu_ctx *c)
 {
     ARGCHK(c, c != NULL);
+    const int was_open = c->have_frame;
     c->have_frame = 0;
+    c->side_pic = -1;
     if (c->where != 0 || c->addb_pending) {
         c->addb_pending = 0;
         snprintf(c->err, sizeof(c->err), "frame_end: the in-loop filters announced in xgpu_frame_params (deblock_on=%d alf_on=%d) were not all run",
@@ -750,5 +854,6 @@ int xgpu_frame_end(xgpu_ctx *c)
         c->where = 0;
         return XGPU_ERR_UNEXPECTED;
     }
+    if (was_open) c->side_pic = c->fp.pic;      // the SCU map now holds this picture's side information (xgpu_frame_side_info)
     return XGPU_OK;
 }

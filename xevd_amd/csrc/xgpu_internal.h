@@ -348,6 +348,7 @@ struct xgpu_ctx {
     hipEvent_t      odev_ev[2];       // xgpu_pic_output_device on a caller's stream: picture ready on the context stream / the caller's kernel done (created at the first call)
     xgpu_frame_params fp;
     int             have_frame;
+    int             side_pic;          // the slot whose xgpu_frame_end came last with no xgpu_frame_begin since: d_maps holds ITS side information (xgpu_frame_side_info); -1: none
     TileMask        no_dbk;            // tile borders the deblocking of the current picture leaves alone (set by xgpu_batch_recon)
     hipEvent_t      fork_ev, join_ev;  // k_dmvr / k_affine on the side stream beside k_inter: where they may start, where the kernel stream takes them back
     int             builder_threads;   // xgpu_set_builder_threads: host threads xgpu_batch_create spreads its per-CU passes over (default 1)
@@ -473,6 +474,20 @@ struct SemiPlanarArgs {
     const int32_t *dra;             // [3][1024] DRA inverse tables, or NULL
 };
 void launch_output_semiplanar(const SemiPlanarArgs &a, int dtype, hipStream_t s);
+// k_side_info.hip: the SCU map of the picture decoded last as nine int16 planes per unit (k_side_blocks) or as a dense motion field (k_side_flow)
+struct SideArgs {
+    const ScuRec *maps;
+    int      w_scu, h_scu;
+    uint8_t *dst;
+    size_t   pitch, plane;          // bytes between rows / between planes (BLOCKS, FLOW planar)
+    int      aligned;               // dst, pitch and plane are multiples of 16 bytes: vector stores
+    int      w, h, crop_l, crop_t;  // FLOW: the cropped size and where it starts in the picture
+    int      list0, per_poc;        // FLOW: the list of a one-list field; divide by the POC distance
+    int      poc;
+    int      refp_poc[XGPU_MAX_REFS][2];
+};
+void launch_side_blocks(const SideArgs &a, hipStream_t s);
+void launch_side_flow(const SideArgs &a, bool planar, int dtype, int n_lists, hipStream_t s);
 void launch_md5(xgpu_ctx *c, hipStream_t s, const uint8_t *d_msg, int w, int h, uint32_t *d_digest);      // k_md5.hip: the three planes packed back to back at d_msg -> d_digest[3][4]
 void launch_test_mc(xgpu_ctx *c, const int16_t *plane, int stride, int ref_x, int ref_y, int has_dx, int has_dy,
                     int gmv_x, int gmv_y, int16_t *pred, int w, int h, int bd, int luma);

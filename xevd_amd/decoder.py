@@ -190,15 +190,7 @@ class XgpuDecoder:
         if self.lib.xgpu_pic_output_device_size(self.ctx, C.byref(fmt)) == 0:
             raise ValueError(f"invalid output format (layout {layout}, out_bit_depth {out_bit_depth}, matrix {matrix}, chroma_loc {chroma_loc}, crop {crop})")
         nbytes = (sum((n - 1) * s for n, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
-        cur = torch.cuda.current_stream(dev)
-        run = cur
-        if cur.cuda_stream == 0:
-            # torch's default stream is the null stream, whose handle (0) means "the context's stream" to the C ABI: run on a side stream of torch's
-            # between two stream waits instead - the same order for everything queued on the default stream
-            if getattr(self, "_side", None) is None:
-                self._side = torch.cuda.Stream(device=dev)
-            run = self._side
-            run.wait_stream(cur)
+        cur, run = self._run_stream(dev)
         if colour is None:
             self._chk(self.lib.xgpu_pic_output_device(self.ctx, pic, dl, C.byref(fmt), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
                       "xgpu_pic_output_device")
@@ -206,6 +198,73 @@ class XgpuDecoder:
             cm = abi.make_colour_transform(**colour)
             self._chk(self.lib.xgpu_pic_output_device_cm(self.ctx, pic, dl, C.byref(fmt), C.byref(cm), C.c_void_p(out.data_ptr()), nbytes,
                                                          C.c_void_p(run.cuda_stream)), "xgpu_pic_output_device_cm")
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
+    def _run_stream(self, dev):
+        """(torch's current stream, the stream a kernel of the C ABI is queued on): torch's default stream is the null stream, whose handle (0) means "the
+        context's stream" to the C ABI - such a call runs on a side stream of torch's between two stream waits instead (the caller makes the second one)"""
+        import torch
+        cur = torch.cuda.current_stream(dev)
+        run = cur
+        if cur.cuda_stream == 0:
+            if getattr(self, "_side", None) is None:
+                self._side = torch.cuda.Stream(device=dev)
+            run = self._side
+            run.wait_stream(cur)
+        return cur, run
+
+    def frame_side_info(self, pic, kind="blocks", lists="both", dtype=None, per_poc=False, channels_last=False, crop=(0, 0, 0, 0), out=None):
+        """The coding side information of the picture decoded LAST as a torch tensor on cuda:{device}, on torch's current stream (xgpu_frame_side_info,
+        INTEGRATION.md section 8c).  `pic` must be the slot of the last decode_picture / frame_end: the SCU map it is read from is per decoder, the next
+        picture overwrites it - anything else raises XgpuError.
+        kind "blocks": [9, height / 4, width / 4] torch.int16, one entry per 4x4 luma unit of the uncropped picture - planes 0-3 the list 0 / list 1 vectors (x, y,
+        quarter samples), 4 / 5 the POC distance of each list's reference (0: list unused), 6 the mode (0 intra, 1 inter, 2 skip, 6 IBC), 7 the QP, 8 flags (bit 0
+        luma cbf, 1 / 2 left / top block edge, 3 ats_inter); crop must be 0.
+        kind "flow": a dense motion field in luma samples, [C, H, W] (channels_last: [H, W, C]), C = 2 (x, y) per list of lists = "both" | 0 | 1, dtype
+        torch.float16 (the default) or torch.float32, per_poc: divided by the POC distance; crop (left, right, top, bottom), even.
+        out: a tensor to fill instead (its strides may pad the rows); it is also what is returned."""
+        import torch
+        cl, cr, ct, cb = (int(v) for v in crop)
+        dev = torch.device("cuda", self.sp.device)
+        if kind == "blocks":
+            if dtype not in (None, torch.int16):
+                raise ValueError("blocks: dtype is torch.int16")
+            dtype = torch.int16
+            h, w = self.height // 4, self.width // 4
+            shape, planar, rows_w = (9, h, w), True, w
+            fmt = abi.make_side_format(abi.SIDE_BLOCKS, abi.OUT_U16, crop=crop)
+        elif kind == "flow":
+            dtype = torch.float16 if dtype is None else dtype
+            codes = {torch.float16: abi.OUT_F16, torch.float32: abi.OUT_F32}
+            if dtype not in codes:
+                raise ValueError(f"flow: dtype torch.float16 or torch.float32, not {dtype}")
+            if lists not in ("both", 0, 1):
+                raise ValueError(f"lists must be 'both', 0 or 1, not {lists!r}")
+            ch = 4 if lists == "both" else 2
+            h, w = self.height - ct - cb, self.width - cl - cr
+            planar = not channels_last
+            shape, rows_w = ((ch, h, w), w) if planar else ((h, w, ch), ch * w)
+            fmt = abi.make_side_format(abi.SIDE_FLOW_PLANAR if planar else abi.SIDE_FLOW_INTERLEAVED, codes[dtype],
+                                       lists=3 if lists == "both" else 1 + int(lists), per_poc=bool(per_poc), crop=crop)
+        else:
+            raise ValueError(f"kind must be 'blocks' or 'flow', not {kind!r}")
+        if self.lib.xgpu_side_info_size(C.byref(fmt), self.width, self.height) == 0:
+            raise ValueError(f"invalid side-information format (kind {kind}, lists {lists}, crop {crop})")
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
+            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+        st = out.stride()
+        pitch = st[1] if planar else st[0]          # elements between rows
+        if (planar and (st[2] != 1 or st[0] != pitch * h)) or (not planar and st[1:] != (shape[2], 1)) or pitch < rows_w:
+            raise ValueError(f"out: strides {st} are not rows of {rows_w} elements{' in planes of H rows' if planar else ''}")
+        fmt.row_pitch = pitch * dtype.itemsize
+        nbytes = (sum((n - 1) * s for n, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
+        cur, run = self._run_stream(dev)
+        self._chk(self.lib.xgpu_frame_side_info(self.ctx, pic, C.byref(fmt), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
+                  "xgpu_frame_side_info")
         if run is not cur:
             cur.wait_stream(run)
         return out

@@ -101,13 +101,16 @@ class StreamDecoder:
             cm[k] = v
         return cm
 
-    def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None):
+    def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
         current stream, by default with the colour description of the stream's VUI (tensor_options) and the SPS crop when apply_crop is set.
         to="srgb" | "bt709" | "linear-bt709" | "linear-bt2020" | "pq-bt2020" | ... (colour_transform; with tensor=, layout "rgb"): the picture in that colour
-        space, from the primaries and transfer characteristics of the stream's VUI"""
+        space, from the primaries and transfer characteristics of the stream's VUI.
+        side=dict(...) (keyword arguments of XgpuDecoder.frame_side_info, {} for the block planes): the coding side information of every picture - motion
+        vectors, modes, QP - as a torch tensor under params["side_info"] (the yielded tuple keeps its shape), taken right behind the picture's kernels, before
+        the next picture overwrites the map it is read from; kind "flow" defaults to the SPS crop when apply_crop is set"""
         if to is not None and tensor is None:
             raise ValueError("to: needs tensor=dict(...)")
         q = queue.Queue(maxsize=self.prefetch)
@@ -124,6 +127,11 @@ class StreamDecoder:
             with self._lock:
                 dec.decode_picture(cur, p["poc"], refs, hb, deblock=p["deblock_on"], pad=True, qp_u_offset=p["qp_u_offset"], qp_v_offset=p["qp_v_offset"],
                                    alpha_off=p["alpha_off"], beta_off=p["beta_off"], alf=p["alf"])
+                if side is not None:           # the SCU map is this picture's until the next frame_begin: before any other output
+                    kw = dict(side)
+                    if kw.get("kind") == "flow":
+                        kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
+                    p["side_info"] = dec.frame_side_info(cur, **kw)
                 if p["n_dmvr_sub"]:
                     p["_dmvr"][1] = dec.batch_dmvr_mvs(hb)
                     p["_dmvr"][0].set()
@@ -186,14 +194,18 @@ class StreamDecoder:
                 self._dec.close()
                 self._dec = None
 
-    def output_order(self, output_bit_depth=None, tensor=None, to=None):
+    def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
-        pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape"""
+        pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
+        side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too"""
         out, epoch = [], -1
-        for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to):
+        for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side):
             if p["is_idr"]:
                 epoch += 1
             if tensor is not None:
                 planes = planes.cpu().numpy()      # (synchronises torch's current stream: the slot's tensor is complete)
+            if side is not None:
+                p["side_info"] = p["side_info"].cpu().numpy()
+            p["decode_index"] = len(out)       # place in decoding order
             out.append(((epoch, p["poc"]), p, planes))
         return [(p, planes) for _, p, planes in sorted(out, key=lambda t: t[0])]
