@@ -18,6 +18,18 @@
 #define ORC_PI 3.14159265358979323846
 
 /* ------------------------------------------------------------------------------------------------
+ * Census (xevd_oracle.h): counters bumped where a branch is taken, so that a test can prove its inputs reach the
+ * branch it was written for.  Counting never changes a result.  g_cen_plane: the plane (0 Y, 1 U, 2 V) the
+ * block-level functions below are working for (they do not know it themselves).
+ * ---------------------------------------------------------------------------------------------- */
+static orc_census g_cen;
+static int g_cen_plane = 0;
+void orc_census_reset(void) { memset(&g_cen, 0, sizeof(g_cen)); }
+void orc_census_get(orc_census *out) { *out = g_cen; }
+int  orc_census_size(void) { return (int)sizeof(orc_census); }
+#define CEN_CLIP(arr, v, maxv) do { if ((v) < 0) g_cen.arr[0]++; else if ((v) > (maxv)) g_cen.arr[1]++; } while (0)
+
+/* ------------------------------------------------------------------------------------------------
  * interpolation filter tables.  Baseline: src_base/xevd_mc.c:80-134 (only phases 0,4,8,12 / 0,4,..,28 are
  * populated).  Main (sps_admvp_flag): src_main/xevdm_mc.c:121-175, 16 luma / 32 chroma phases.
  * ---------------------------------------------------------------------------------------------- */
@@ -92,6 +104,7 @@ static void fir_block(const int16_t *ref, int gmv_x, int gmv_y, int s_ref, int s
             int32_t s = 0;
             for (k = 0; k < ntap; k++) s += tx[k] * r[i * s_ref + j + k];
             s >>= 6;
+            CEN_CLIP(mc_clip[g_cen_plane], s, maxv);
             pred[i * s_pred + j] = (int16_t)CLIP3(0, maxv, s);
         }
     } else if (!has_dx && has_dy) {
@@ -100,6 +113,7 @@ static void fir_block(const int16_t *ref, int gmv_x, int gmv_y, int s_ref, int s
             int32_t s = 0;
             for (k = 0; k < ntap; k++) s += ty[k] * r[(i + k) * s_ref + j];
             s >>= 6;
+            CEN_CLIP(mc_clip[g_cen_plane], s, maxv);
             pred[i * s_pred + j] = (int16_t)CLIP3(0, maxv, s);
         }
     } else {
@@ -111,12 +125,14 @@ static void fir_block(const int16_t *ref, int gmv_x, int gmv_y, int s_ref, int s
         for (i = 0; i < h + ntap - 1; i++) for (j = 0; j < w; j++) {
             int32_t s = 0;
             for (k = 0; k < ntap; k++) s += tx[k] * r[i * s_ref + j + k];
+            if ((s >> shift1) != (int16_t)(s >> shift1)) g_cen.mc_stage1_wrap++;
             tmp[i * w + j] = (int16_t)(s >> shift1);          /* s16 store: wraps like the reference's buffer */
         }
         for (i = 0; i < h; i++) for (j = 0; j < w; j++) {
             int32_t s = 0;
             for (k = 0; k < ntap; k++) s += ty[k] * tmp[(i + k) * w + j];
             s = (s + off2) >> shift2;
+            CEN_CLIP(mc_clip[g_cen_plane], s, maxv);
             pred[i * s_pred + j] = (int16_t)CLIP3(0, maxv, s);
         }
         free(tmp);
@@ -151,10 +167,10 @@ static void mv_clip(int x, int y, int pic_w, int pic_h, int w, int h, const int8
     for (l = 0; l < 2; l++) {
         mv_t[l][0] = mv[l][0]; mv_t[l][1] = mv[l][1];
         if (refi[l] < 0) continue;
-        if (x + mv[l][0] < min_x) mv_t[l][0] = (int16_t)(min_x - x);
-        if (y + mv[l][1] < min_y) mv_t[l][1] = (int16_t)(min_y - y);
-        if (x + mv[l][0] + w - 4 > max_x) mv_t[l][0] = (int16_t)(max_x - x - w + 4);
-        if (y + mv[l][1] + h - 4 > max_y) mv_t[l][1] = (int16_t)(max_y - y - h + 4);
+        if (x + mv[l][0] < min_x) { mv_t[l][0] = (int16_t)(min_x - x); g_cen.mv_clip[0]++; }
+        if (y + mv[l][1] < min_y) { mv_t[l][1] = (int16_t)(min_y - y); g_cen.mv_clip[2]++; }
+        if (x + mv[l][0] + w - 4 > max_x) { mv_t[l][0] = (int16_t)(max_x - x - w + 4); g_cen.mv_clip[1]++; }
+        if (y + mv[l][1] + h - 4 > max_y) { mv_t[l][1] = (int16_t)(max_y - y - h + 4); g_cen.mv_clip[3]++; }
     }
 }
 
@@ -185,13 +201,28 @@ int orc_mc_cu(const xgpu_seq_params *sp, const orc_frame *fr, int x, int y, int 
            bits of mv<<2 set */
         ldx = ((mv[l][0] << 2) & 15) != 0;  ldy = ((mv[l][1] << 2) & 15) != 0;
         cdx = ((mv[l][0] << 2) & 31) != 0;  cdy = ((mv[l][1] << 2) & 31) != 0;
+        g_cen_plane = 0;
         orc_mc_l(rp->y, gx, gy, rp->s_l, w, dst[bidx][0], w, h, sp->bit_depth_luma, ldx, ldy, sp->tool_admvp);
+        g_cen_plane = 1;
         orc_mc_c(rp->u, gx, gy, rp->s_c, wc, dst[bidx][1], wc, hc, sp->bit_depth_chroma, cdx, cdy, sp->tool_admvp);
+        g_cen_plane = 2;
         orc_mc_c(rp->v, gx, gy, rp->s_c, wc, dst[bidx][2], wc, hc, sp->bit_depth_chroma, cdx, cdy, sp->tool_admvp);
+        g_cen_plane = 0;
         bidx++;
     }
     if (bidx == 2) {
         /* xevd_average_16b_no_clip, xevd_mc.c:145-167: average of the two already-clipped predictions */
+        {
+            const int maxl = (1 << sp->bit_depth_luma) - 1;
+            g_cen.mc_bi[0] += (uint32_t)(w * h); g_cen.mc_bi[1] += (uint32_t)(wc * hc); g_cen.mc_bi[2] += (uint32_t)(wc * hc);
+            /* the three saturated pairs of the average: 0 with 0, max with max, 0 with max (either order) */
+            for (i = 0; i < w * h; i++) {
+                const int a = pred0[0][i], c = pred1[0][i];
+                if (a == 0 && c == 0) g_cen.mc_bi_rails[0]++;
+                else if (a == maxl && c == maxl) g_cen.mc_bi_rails[1]++;
+                else if ((a == 0 && c == maxl) || (a == maxl && c == 0)) g_cen.mc_bi_rails[2]++;
+            }
+        }
         for (i = 0; i < w * h; i++)   pred0[0][i] = (int16_t)((pred0[0][i] + pred1[0][i] + 1) >> 1);
         for (i = 0; i < wc * hc; i++) pred0[1][i] = (int16_t)((pred0[1][i] + pred1[1][i] + 1) >> 1);
         for (i = 0; i < wc * hc; i++) pred0[2][i] = (int16_t)((pred0[2][i] + pred1[2][i] + 1) >> 1);
@@ -379,6 +410,9 @@ void orc_recon(const int16_t *coef, const int16_t *pred, int is_coef, int cuw, i
     for (i = 0; i < cuh; i++) for (j = 0; j < cuw; j++) {
         /* the sum is formed in 16 bits and wraps (s16 t0, xevd_recon.c:39,60) */
         int16_t t = is_coef ? (int16_t)(coef[i * cuw + j] + pred[i * cuw + j]) : pred[i * cuw + j];
+        if (is_coef && (int)t != (int)coef[i * cuw + j] + (int)pred[i * cuw + j]) g_cen.recon_wrap++;
+        if (is_coef) g_cen.recon_coded++;
+        CEN_CLIP(recon_clip, t, maxv);
         rec[i * s_rec + j] = (int16_t)CLIP3(0, maxv, t);
     }
 }
@@ -534,6 +568,7 @@ static void dmvr_process(const xgpu_seq_params *sp, const orc_frame *fr, int x, 
         const int gx = ((x << 2) + start[l][0] - (IT << 2)) << 2, gy = ((y << 2) + start[l][1] - (IT << 2)) << 2;
         const int16_t tx[2] = { (int16_t)(64 - 4 * (gx & 15)), (int16_t)(4 * (gx & 15)) }, ty[2] = { (int16_t)(64 - 4 * (gy & 15)), (int16_t)(4 * (gy & 15)) };
         bl[l] = (int16_t *)malloc(sizeof(int16_t) * (size_t)stride * (h + 2 * IT));
+        g_cen_plane = 0;
         fir_block(rp->y, gx, gy, rp->s_l, stride, bl[l], w + 2 * IT, h + 2 * IT, bd, (gx & 15) != 0, (gy & 15) != 0, 2, 4, tx, ty);
     }
     for (sy = 0; sy < h; sy += dy) for (sx = 0; sx < w; sx += dx, num++) {
@@ -590,6 +625,7 @@ static void dmvr_process(const xgpu_seq_params *sp, const orc_frame *fr, int x, 
                 buf[r * (dx + 11) + c] = rp->y[(wy + rr) * rp->s_l + wx + cc];
             }
             luma_taps(gx & 15, sp->tool_admvp, tx); luma_taps(gy & 15, sp->tool_admvp, ty);
+            g_cen_plane = 0;
             fir_block(buf + (2 + 3 + dly) * (dx + 11) + 2 + 3 + dlx, gx & 15, gy & 15, dx + 11, w, dst[l][0] + sy * w + sx, dx, dy, bd,
                       (gx & 15) != 0, (gy & 15) != 0, 8, 4, tx, ty);
             /* chroma: (dx/2 + 3) x (dy/2 + 3) window at the starting vector's chroma position, 1 sample of padding */
@@ -602,8 +638,10 @@ static void dmvr_process(const xgpu_seq_params *sp, const orc_frame *fr, int x, 
                     buf[r * (cw + 5) + c] = plane[(cy0 + rr) * rp->s_c + cx0 + cc];
                 }
                 chroma_taps(gx & 31, sp->tool_admvp, tcx); chroma_taps(gy & 31, sp->tool_admvp, tcy);
+                g_cen_plane = comp;
                 fir_block(buf + (1 + 1 + dcy) * (cw + 5) + 1 + 1 + dcx, gx & 31, gy & 31, cw + 5, w >> 1, dst[l][comp] + (sy >> 1) * (w >> 1) + (sx >> 1), cw, ch,
                           sp->bit_depth_chroma, (gx & 31) != 0, (gy & 31) != 0, 4, 5, tcx, tcy);
+                g_cen_plane = 0;
             }
         }
     }
@@ -1025,9 +1063,13 @@ static void aff_mc_list(const xgpu_seq_params *sp, const orc_pic *rp, int x, int
         const int cx = ox < hor_min ? hor_min : (ox > hor_max ? hor_max : ox), cy = oy < ver_min ? ver_min : (oy > ver_max ? ver_max : oy);
         for (h = 0; h < cuh; h += sub_h) for (w = 0; w < cuw; w += sub_w) {
             const int gx = (x + w) * 16 + cx, gy = (y + h) * 16 + cy;
+            g_cen_plane = 0;
             orc_mc_l(rp->y, gx, gy, rp->s_l, cuw, pred[0] + h * cuw + w, sub_w, sub_h, sp->bit_depth_luma, (ox & 15) != 0, (oy & 15) != 0, sp->tool_admvp);
+            g_cen_plane = 1;
             orc_mc_c(rp->u, gx, gy, rp->s_c, wc, pred[1] + (h >> 1) * wc + (w >> 1), sub_w >> 1, sub_h >> 1, sp->bit_depth_chroma, (ox & 31) != 0, (oy & 31) != 0, sp->tool_admvp);
+            g_cen_plane = 2;
             orc_mc_c(rp->v, gx, gy, rp->s_c, wc, pred[2] + (h >> 1) * wc + (w >> 1), sub_w >> 1, sub_h >> 1, sp->bit_depth_chroma, (ox & 31) != 0, (oy & 31) != 0, sp->tool_admvp);
+            g_cen_plane = 0;
         }
     }
 }
@@ -1518,11 +1560,13 @@ static void addb_line_luma(int16_t *buf, int step, int bs, int alpha, int beta, 
     int16_t p[4], q[4], po[4], qo[4];
     int i, ap, aq;
     for (i = 0; i < 4; i++) { q[i] = buf[i * step]; p[i] = buf[-(i + 1) * step]; po[i] = p[i]; qo[i] = q[i]; }
-    if (!(bs && abs(p[0] - q[0]) < alpha && abs(p[1] - p[0]) < beta && abs(q[1] - q[0]) < beta)) return;
+    if (!(bs && abs(p[0] - q[0]) < alpha && abs(p[1] - p[0]) < beta && abs(q[1] - q[0]) < beta)) { g_cen.addb_gate[0][bs][0]++; return; }
+    g_cen.addb_gate[0][bs][1]++;
     ap = abs(p[0] - p[2]) < beta;
     aq = abs(q[0] - q[2]) < beta;
     if (bs == 4) {
         const int strong = abs(p[0] - q[0]) < ((alpha >> 2) + 2);
+        g_cen.addb_bs4[0][ap && strong]++; g_cen.addb_bs4[1][aq && strong]++;
         if (ap && strong) {
             po[0] = (int16_t)((p[2] + 2 * (p[1] + p[0] + q[0]) + q[1] + 4) >> 3);
             po[1] = (int16_t)((p[2] + p[1] + p[0] + q[0] + 2) >> 2);
@@ -1536,6 +1580,10 @@ static void addb_line_luma(int16_t *buf, int step, int bs, int alpha, int beta, 
     } else {
         const int c0 = (uint8_t)(c1 + ((ap + aq) << (bd - 9 > 0 ? bd - 9 : 0)));
         const int d0 = CLIP3(-c0, c0, (4 * (q[0] - p[0]) + p[1] - q[1] + 4) >> 3);
+        g_cen.addb_apq[ap | (aq << 1)]++;
+        g_cen.addb_d0[0][d0 != ((4 * (q[0] - p[0]) + p[1] - q[1] + 4) >> 3)]++;
+        CEN_CLIP(addb_out_clip[0], p[0] + d0, maxv); CEN_CLIP(addb_out_clip[0], q[0] - d0, maxv);
+        if (c0 != c1 + ((ap + aq) << (bd - 9 > 0 ? bd - 9 : 0))) g_cen.addb_lost[2]++;
         po[0] = (int16_t)CLIP3(0, maxv, p[0] + d0);
         qo[0] = (int16_t)CLIP3(0, maxv, q[0] - d0);
         if (ap) po[1] = (int16_t)(p[1] + CLIP3(-c1, c1, (((p[2] + p[0] + q[0]) * 3) - 8 * p[1] - q[1]) >> 4));
@@ -1549,12 +1597,15 @@ static void addb_line_chroma(int16_t *buf, int step, int bs, int alpha, int beta
     const int maxv = (1 << bd) - 1;
     const int16_t p0 = buf[-step], p1 = buf[-2 * step], q0 = buf[0], q1 = buf[step];
     int po = p0, qo = q0;
-    if (!(bs && abs(p0 - q0) < alpha && abs(p1 - p0) < beta && abs(q1 - q0) < beta)) return;
+    if (!(bs && abs(p0 - q0) < alpha && abs(p1 - p0) < beta && abs(q1 - q0) < beta)) { g_cen.addb_gate[1][bs][0]++; return; }
+    g_cen.addb_gate[1][bs][1]++;
     if (bs == 4) {
         po = (2 * p1 + p0 + q1 + 2) >> 2;
         qo = (2 * q1 + q0 + p1 + 2) >> 2;
     } else {
         const int d0 = CLIP3(-c0, c0, (4 * (q0 - p0) + p1 - q1 + 4) >> 3);
+        g_cen.addb_d0[1][d0 != ((4 * (q0 - p0) + p1 - q1 + 4) >> 3)]++;
+        CEN_CLIP(addb_out_clip[1], p0 + d0, maxv); CEN_CLIP(addb_out_clip[1], q0 - d0, maxv);
         po = CLIP3(0, maxv, p0 + d0);
         qo = CLIP3(0, maxv, q0 - d0);
     }
@@ -1576,6 +1627,11 @@ static void addb_segment(const xgpu_seq_params *sp, const orc_frame *fr, const o
     int c1 = (uint8_t)(k_addb_clip[ia][bs] << (bdl - 9 > 0 ? bdl - 9 : 0));
     int i, c;
     int16_t *y = fr->cur.y + y_pel * fr->cur.s_l + x_pel;
+    if (g_dbk_planes & 1) {
+        g_cen.addb_index_a[0][ia]++; g_cen.addb_index_b[0][ib]++;
+        if (beta != (k_addb_beta[ib] << scale)) g_cen.addb_lost[0]++;
+        if (c1 != (k_addb_clip[ia][bs] << (bdl - 9 > 0 ? bdl - 9 : 0))) g_cen.addb_lost[1]++;
+    }
     for (i = 0; i < 4 && (g_dbk_planes & 1); i++)
         addb_line_luma(is_ver ? y + i * fr->cur.s_l : y + i, is_ver ? 1 : fr->cur.s_l, bs, alpha, beta, c1, bdl);
     for (c = 0; c < 2 && (g_dbk_planes & 2); c++) {
@@ -1588,6 +1644,9 @@ static void addb_segment(const xgpu_seq_params *sp, const orc_frame *fr, const o
         alpha = k_addb_alpha[ia] << scale;                    /* luma bit depth scales chroma too, xevdm_df.c:926-927 */
         beta = (uint8_t)(k_addb_beta[ib] << scale);
         c0 = (uint8_t)((k_addb_clip[ia][bs] + 1) << (bdc - 9 > 0 ? bdc - 9 : 0));
+        g_cen.addb_index_a[1][ia]++; g_cen.addb_index_b[1][ib]++;
+        if (beta != (k_addb_beta[ib] << scale)) g_cen.addb_lost[0]++;
+        if (c0 != ((k_addb_clip[ia][bs] + 1) << (bdc - 9 > 0 ? bdc - 9 : 0))) g_cen.addb_lost[1]++;
         for (i = 0; i < 2; i++)
             addb_line_chroma(is_ver ? pl + i * fr->cur.s_c : pl + i, is_ver ? 1 : fr->cur.s_c, bs, alpha, beta, c0, bdc);
     }
@@ -1598,6 +1657,10 @@ int orc_deblock_addb(const xgpu_seq_params *sp, const orc_frame *fr, const xgpu_
     const int ws = m->w_scu;
     int i, r, c, k;
     uint8_t *tmap = (b->tiles && !b->tiles->loop_filter_across_tiles) ? tile_map(b->tiles, m->w_scu, m->h_scu) : NULL;      /* xevdm_df.c:877, 1088, 1106 */
+    /* census: a 4-sample segment left unfiltered because it lies on a tile border ([0] all, [1] those inside a 64x64 area at a multiple of 64 whose
+       surroundings - 4 samples each way - lie inside the picture: the areas k_addb_alf filters through its interior path) */
+#define CEN_TILE_EDGE(px, py) do { const int ax = (px) & ~63, ay = (py) & ~63; g_cen.addb_tile_edge[0]++; \
+        if (ax > 0 && ay > 0 && ax + 68 <= sp->width && ay + 68 <= sp->height) g_cen.addb_tile_edge[1]++; } while (0)
     /* vertical edges on the 8x8 luma grid (deblock_addb_cu_ver, xevdm_df.c:1036-1135), then horizontal (:835-945) */
     for (k = 0; k < ws * m->h_scu; k++) m->map_scu[k] &= 0x7FFFFFFFu;
     /* a CU wider (taller) than 64 is passed to the CU filter as two 64-sample halves (deblock_tree, xevdm.c:1989-2037),
@@ -1609,6 +1672,8 @@ int orc_deblock_addb(const xgpu_seq_params *sp, const orc_frame *fr, const xgpu_
         for (hx = 0; hx < cw; hx += 64) {
             const int x = cx + hx, w = cw > 64 ? 64 : cw;
             const int t = (x >> 2) + (y >> 2) * ws;
+            if ((x & 7) == 0 && x > 0 && MCU_COD(m->map_scu[t - 1]) && !TB_OK(t, t - 1))
+                for (r = 0; r < h >> 2; r++) CEN_TILE_EDGE(x, y + 4 * r);
             if ((x & 7) == 0 && x > 0 && MCU_COD(m->map_scu[t - 1]) && TB_OK(t, t - 1))
                 for (r = 0; r < h >> 2; r++) addb_segment(sp, fr, m, t + r * ws, t + r * ws - 1, x, y + 4 * r, 1, alpha_off, beta_off);
             if (((x + w) & 7) == 0 && x + w < sp->width && MCU_COD(m->map_scu[t + (w >> 2)]) && TB_OK(t, t + (w >> 2)))
@@ -1623,6 +1688,8 @@ int orc_deblock_addb(const xgpu_seq_params *sp, const orc_frame *fr, const xgpu_
         for (hy = 0; hy < ch; hy += 64) {
             const int y = cy + hy;
             const int t = (x >> 2) + (y >> 2) * ws;
+            if ((y & 7) == 0 && y > 0 && !TB_OK(t, t - ws))
+                for (c = 0; c < w >> 2; c++) CEN_TILE_EDGE(x + 4 * c, y);
             if ((y & 7) == 0 && y > 0 && TB_OK(t, t - ws))
                 for (c = 0; c < w >> 2; c++) addb_segment(sp, fr, m, t + c, t + c - ws, x + 4 * c, y, 0, alpha_off, beta_off);
         }
@@ -1631,6 +1698,7 @@ int orc_deblock_addb(const xgpu_seq_params *sp, const orc_frame *fr, const xgpu_
     free(tmap);
     return 0;
 #undef TB_OK
+#undef CEN_TILE_EDGE
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -1740,6 +1808,7 @@ int orc_alf(const xgpu_seq_params *sp, const orc_pic *pic, const xgpu_alf_params
                 int cls, tr, ii, jj;
                 int16_t f[13];
                 alf_classify(o, ws, x, y, sp->bit_depth_luma, &cls, &tr);
+                g_cen.alf_class[cls]++; g_cen.alf_tr[tr]++;
                 for (i = 0; i < 13; i++) f[i] = ap->luma_coef[cls * 13 + l[tr][i]];
                 for (ii = 0; ii < 4; ii++) for (jj = 0; jj < 4; jj++) {             /* alf_filter_blk_7, :210-337 */
                     const int16_t *p = o + (y + ii) * ws + x + jj;
@@ -1749,6 +1818,7 @@ int orc_alf(const xgpu_seq_params *sp, const orc_pic *pic, const xgpu_alf_params
                             + f[7] * (p[ws - 1] + p[-ws + 1]) + f[8] * (p[ws - 2] + p[-ws + 2])
                             + f[9] * (p[3] + p[-3]) + f[10] * (p[2] + p[-2]) + f[11] * (p[1] + p[-1]) + f[12] * p[0];
                     sum = (sum + 256) >> 9;
+                    CEN_CLIP(alf_clip[0], sum, maxv);
                     pic->y[(y0 + y + ii) * pic->s_l + x0 + x + jj] = (int16_t)CLIP3(0, maxv, sum);
                 }
             }
@@ -1765,6 +1835,7 @@ int orc_alf(const xgpu_seq_params *sp, const orc_pic *pic, const xgpu_alf_params
                 int sum = f[0] * (p[2 * ws] + p[-2 * ws]) + f[1] * (p[ws + 1] + p[-ws - 1]) + f[2] * (p[ws] + p[-ws]) + f[3] * (p[ws - 1] + p[-ws + 1])
                         + f[4] * (p[2] + p[-2]) + f[5] * (p[1] + p[-1]) + f[6] * p[0];
                 sum = (sum + 256) >> 9;
+                CEN_CLIP(alf_clip[c], sum, maxv);
                 pl[((y0 >> 1) + y) * pic->s_c + (x0 >> 1) + x] = (int16_t)CLIP3(0, maxv, sum);
             }
             free(o - 3 * ws - 3);

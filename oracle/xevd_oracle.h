@@ -103,6 +103,33 @@ void orc_output_convert(const int16_t *src, int stride, int w, int h, int src_bd
 /* default chroma QP mapping table (static table of xevd_tbl.c:334-357 after xevd_tbl_derived_chroma_qp_mapping_tables, :364-426) */
 const int8_t *orc_default_chroma_qp_table(void);   /* 58 entries for qp 0..57 (8-bit) */
 
+/* ---- census ----
+   Counters the functions above bump where they take a branch (process-wide, not thread-safe: the tests run them one at a time).  They exist so that a
+   test can assert that its inputs REACH the arithmetic it was written for - the top of the ADDB tables, both rails of every clip, all ALF classes -
+   instead of assuming it.  [2] arrays of clips are { below 0, above max }. */
+typedef struct orc_census {
+    uint32_t addb_index_a[2][52], addb_index_b[2][52]; /* [luma / chroma] indexA / indexB of every 4-sample segment (chroma: per plane) */
+    uint32_t addb_gate[2][5][2];                       /* [luma / chroma][bS][skipped by the alpha-beta gate / filtered], sample lines */
+    uint32_t addb_bs4[2][2];                           /* luma bS 4, [p side / q side][weak 3-tap / strong (ap resp. aq and the (alpha >> 2) + 2 test)] */
+    uint32_t addb_apq[4];                              /* luma bS 1..3: ap | aq << 1 */
+    uint32_t addb_d0[2][2];                            /* [luma / chroma] bS 1..3: d0 inside +-c0 / clipped to it */
+    uint32_t addb_out_clip[2][2];                      /* [luma / chroma] bS 1..3: p0 + d0, q0 - d0 clipped */
+    uint32_t addb_lost[3];                             /* values that lost bits to the u8 casts: beta, c1 (luma) / c0 (chroma) from the table, luma c0 = c1 + (ap + aq) */
+    uint32_t addb_tile_edge[2];                        /* segments not filtered because they lie on a tile border: all / those in an interior 64x64 filter area */
+    uint32_t alf_class[25], alf_tr[4];                 /* luma 4x4 blocks by class and by transposition */
+    uint32_t alf_clip[3][2];                           /* [plane] filtered samples clipped */
+    uint32_t mc_clip[3][2];                            /* [plane] interpolated samples clipped (xevd_mc_{l,c}_{n0,0n,nn}) */
+    uint32_t mc_stage1_wrap;                           /* first-stage sums of the 2-D filter that did not fit the s16 intermediate */
+    uint32_t mc_bi[3];                                 /* [plane] bi-averaged samples */
+    uint32_t mc_bi_rails[3];                           /* luma bi-averaged pairs 0 + 0 / max + max / 0 + max */
+    uint32_t mv_clip[4];                               /* vectors moved by xevd_mv_clip: left / right / top / bottom threshold */
+    uint32_t recon_coded, recon_wrap;                  /* residual-added samples / sums that wrapped in s16 */
+    uint32_t recon_clip[2];                            /* reconstructed samples clipped */
+} orc_census;
+void orc_census_reset(void);
+void orc_census_get(orc_census *out);
+int  orc_census_size(void);
+
 #ifdef __cplusplus
 }
 #endif

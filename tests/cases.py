@@ -78,6 +78,10 @@ CASES = [
     ("main_i_eipd_ibc_htdf_ctu128_12b", 264, 136, 12, 1, 1, (1, 0), 0.0, {"addb": 1, "alf": 1, "inter_frac": 0.0, "eipd": 1, "htdf_qp": 28, "ibc_frac": 0.3, "log2_ctu": 7, "ats_frac": 0.5,
                                                                          "btt_frac": 0.5, "split_prob": 0.5}),
 ]
+# the ends of the ranges (tests/extreme_inputs.py; the whole set runs in tests/test_oracle_extremes.py / test_gpu_extremes.py): the ones below are also reference-made goldens
+import extreme_inputs  # noqa: E402
+GOLDEN_EXTREMES = ("x_addb_ladder_m12_p12_10b", "x_addb_ladder_m12_p12_12b", "x_alf_gratings_10b", "x_mc_checker1_main_b_10b", "x_intra_eipd_rails_8b")
+CASES += [s[:9] for s in extreme_inputs.EXTREME_CASES if s[0] in GOLDEN_EXTREMES]
 POCS = [[4, 0, 2], [12, 16, 4]]      # L1 idx 2 has the POC of L0 idx 0 -> identical-motion candidates exist
 CUR_POC = 8
 QP_OFFSETS = (1, -2)
@@ -93,6 +97,7 @@ def build_case(name, w, h, bd, admvp, iqt, n_refs, bi_frac, tools=None, seed=0, 
     inter_frac = tools.get("inter_frac", inter_frac)
     split_prob = tools.get("split_prob", split_prob)
     log2_ctu = int(tools.get("log2_ctu", 6))
+    amp, qp_range, oob_frac = tools.get("amp", amp), tuple(tools.get("qp_range", qp_range)), tools.get("oob_frac", oob_frac)
     rng = np.random.default_rng(zlib.crc32(name.encode()) % 1000 + seed)
     refs = {}
     for l in range(2):
@@ -123,14 +128,22 @@ def build_case(name, w, h, bd, admvp, iqt, n_refs, bi_frac, tools=None, seed=0, 
         n_ctu = ((w + ctu - 1) // ctu) * ((h + ctu - 1) // ctu)
         alf_params = synth.gen_alf_params(rng, n_ctu, across_tiles=int(tools.get("across_tiles", 0)),
                                           enable=tools.get("alf_enable", (1, 1, 1)))
-    return {"name": name, "w": w, "h": h, "bd": bd, "admvp": admvp, "iqt": iqt, "refs": refs, "batch": batch,
+    case = {"name": name, "w": w, "h": h, "bd": bd, "admvp": admvp, "iqt": iqt, "refs": refs, "batch": batch,
             "alf_params": alf_params, "no_deblock": int(tools.get("no_deblock", 0)), "log2_ctu": log2_ctu,
             "addb": int(tools.get("addb", 0)), "alf": int(tools.get("alf", 0)), "eipd": int(tools.get("eipd", 0)),
             "alpha_off": int(tools.get("alpha_off", 0)), "beta_off": int(tools.get("beta_off", 0))}
+    if tools.get("extreme"):      # rail-to-rail content, QPs / vectors / ALF parameters at the ends of their ranges (tests/extreme_inputs.py)
+        extreme_inputs.apply(case, tools["extreme"], seed)
+    return case
 
 
 def _start_picture(case):
-    """Intra CUs are not reconstructed on this path: start from a deterministic mid-grey picture."""
+    """What the current picture holds before its CUs are reconstructed: the case's start picture (case["start"]: three active-area planes) or, by default,
+    a deterministic mid-grey picture."""
+    if case.get("start") is not None:
+        cur = ol.Picture(case["w"], case["h"], CUR_POC, case["start"])
+        cur.pad_numpy()
+        return cur
     cur = ol.Picture(case["w"], case["h"], CUR_POC)
     for c in range(3):
         cur.bufs[c][:] = 1 << (case["bd"] - 1)

@@ -129,6 +129,9 @@ def golden_pictures(only=None):
             for c in range(3):
                 d[f"ref_{i}_{l}_{c}"] = pic.active(c)
             d[f"refpoc_{i}_{l}"] = np.array(pic.poc)
+        if cs.get("start") is not None:
+            for c in range(3):
+                d[f"start_{c}"] = cs["start"][c]
         for k, v in cs["batch"].items():
             if v is not None:
                 d["b_" + k] = np.asarray(v)

@@ -16,7 +16,10 @@ PICTURE_CASES = ["base_p_8b", "base_b_8b", "base_p_10b", "main_b_10b", "main_adm
                  "main_affine_b_10b", "main_affine_p_8b_atsinter", "main_affine_b_ctu128_10b",
                  "main_ibc_i_10b", "main_ibc_b_8b_noaddb", "main_ibc_p_ctu128_eipd_10b",
                  "main_htdf_b_10b", "main_htdf_i_8b_constrained", "main_htdf_p_ctu128_10b", "main_dmvr_b_10b", "main_dmvr_b_8b_ctu128_mixed",
-                 "base_p_12b", "base_b_12b", "main_addb_alf_12b", "main_all_tools_b_12b", "main_i_eipd_ibc_htdf_ctu128_12b"]
+                 "base_p_12b", "base_b_12b", "main_addb_alf_12b", "main_all_tools_b_12b", "main_i_eipd_ibc_htdf_ctu128_12b",
+                 # ends of the ranges (tests/extreme_inputs.py): ADDB offsets (-12, 12) x QP 0..51 on the step ladder at 10 and 12 bit, ALF coefficients at the legal limit on
+                 # gratings, 0 / max checkerboards through the Main interpolation + ADDB + ALF, all-intra EIPD reconstructed into both rails
+                 "x_addb_ladder_m12_p12_10b", "x_addb_ladder_m12_p12_12b", "x_alf_gratings_10b", "x_mc_checker1_main_b_10b", "x_intra_eipd_rails_8b"]
 
 
 def load_picture_case(name):
@@ -50,6 +53,8 @@ def load_picture_case(name):
     case = {"name": name, "w": w, "h": h, "bd": bd, "admvp": admvp, "iqt": iqt, "refs": refs, "batch": batch,
             "addb": tools[0], "alf": tools[1], "alpha_off": tools[2], "beta_off": tools[3], "no_deblock": tools[4], "log2_ctu": tools[5],
             "eipd": tools[6], "alf_params": alf_params}
+    if "start_0" in d.files:      # what the current picture holds before reconstruction (default: mid-grey)
+        case["start"] = [d[f"start_{c}"] for c in range(3)]
     expect = {"out": [d[f"out_{c}"] for c in range(3)], "pre": [d[f"pre_{c}"] for c in range(3)], "resid": d["resid"],
               "map_scu": d["map_scu"], "dmvr_mv": d["dmvr_mv"] if "dmvr_mv" in d.files else None}
     return case, expect

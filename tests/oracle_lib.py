@@ -27,6 +27,32 @@ class OrcFrame(C.Structure):
     _fields_ = [("cur", OrcPic), ("refp", (OrcPic * 2) * abi.XGPU_MAX_REFS), ("qp_u_offset", C.c_int), ("qp_v_offset", C.c_int)]
 
 
+class OrcCensus(C.Structure):
+    """orc_census of oracle/xevd_oracle.h: how often the oracle took the branches the extreme tests are written for"""
+    _fields_ = [("addb_index_a", (C.c_uint32 * 52) * 2), ("addb_index_b", (C.c_uint32 * 52) * 2), ("addb_gate", ((C.c_uint32 * 2) * 5) * 2),
+                ("addb_bs4", (C.c_uint32 * 2) * 2), ("addb_apq", C.c_uint32 * 4), ("addb_d0", (C.c_uint32 * 2) * 2), ("addb_out_clip", (C.c_uint32 * 2) * 2),
+                ("addb_lost", C.c_uint32 * 3), ("addb_tile_edge", C.c_uint32 * 2), ("alf_class", C.c_uint32 * 25), ("alf_tr", C.c_uint32 * 4),
+                ("alf_clip", (C.c_uint32 * 2) * 3), ("mc_clip", (C.c_uint32 * 2) * 3), ("mc_stage1_wrap", C.c_uint32), ("mc_bi", C.c_uint32 * 3),
+                ("mc_bi_rails", C.c_uint32 * 3), ("mv_clip", C.c_uint32 * 4), ("recon_coded", C.c_uint32), ("recon_wrap", C.c_uint32), ("recon_clip", C.c_uint32 * 2)]
+
+
+def census_reset():
+    oracle().orc_census_reset()
+
+
+def census():
+    """-> {field: numpy array (int64) or int} of the oracle's counters since the last census_reset()"""
+    lib = oracle()
+    assert lib.orc_census_size() == C.sizeof(OrcCensus), "OrcCensus and orc_census differ"
+    c = OrcCensus()
+    lib.orc_census_get(C.byref(c))
+    out = {}
+    for name, _ in OrcCensus._fields_:
+        v = getattr(c, name)
+        out[name] = int(v) if isinstance(v, int) else np.ctypeslib.as_array(v).astype(np.int64)
+    return out
+
+
 def build_oracle():
     if (not os.path.exists(ORACLE_SO) or
             os.path.getmtime(ORACLE_SO) < max(os.path.getmtime(os.path.join(ORACLE_DIR, f)) for f in ("xevd_oracle.c", "xevd_oracle.h"))):

@@ -1,0 +1,193 @@
+"""GPU suite, ends of the ranges (run with -m gpu on an MI355X): the HIP backend against the CPU oracle on the extreme cases of tests/extreme_inputs.py -
+samples on the rails, 0 / max checkerboards through every interpolation phase, QP 0..51 x ADDB slice offsets -12..12 (packed and scalar line filters),
+ALF coefficients at their legal limits on gratings / noise / checkerboards, vectors on the MV-clip thresholds - all three padded planes and the residual
+arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
+reach the branches they are for) are repeated here because this file needs only the oracle, which always ships."""
+import numpy as np
+import pytest
+
+import cases
+import extreme_inputs as xi
+import oracle_lib as ol
+from test_oracle_extremes import TILED_STREAMS_REACHING_INTERIOR_BORDERS, check_census, check_tile_census, run_oracle_with_census
+
+pytestmark = pytest.mark.gpu
+
+
+def _same(out, ref, what):
+    for c in range(3):
+        assert np.array_equal(out[c], ref.bufs[c]), f"{what} plane {c}: first differences at (row, col) {np.argwhere(out[c] != ref.bufs[c])[:4].tolist()}"
+
+
+def _check(cs, what, resid=False, **kw):
+    ref, _, _, rr = cases.run_cpu("oracle", cs)
+    if resid:
+        out, res = cases.run_gpu(cs, resid=True, **kw)
+        assert np.array_equal(res[:len(rr)], rr), f"{what}: residual arena, first differences at {np.argwhere(res[:len(rr)] != rr)[:4].ravel().tolist()}"
+    else:
+        out = cases.run_gpu(cs, **kw)
+    _same(out, ref, what)
+
+
+@pytest.mark.parametrize("spec", xi.EXTREME_CASES, ids=[s[0] for s in xi.EXTREME_CASES])
+def test_gpu_extreme_case(spec):
+    cs = cases.build_case(*spec[:9])
+    (ref, _, _, rr), cen = run_oracle_with_census(cs)
+    check_census(spec, cs, cen)
+    out, res = cases.run_gpu(cs, resid=True)
+    assert np.array_equal(res[:len(rr)], rr), f"residual arena, first differences at {np.argwhere(res[:len(rr)] != rr)[:4].ravel().tolist()}"
+    _same(out, ref, spec[0])
+
+
+_SCALAR = [s for s in xi.EXTREME_CASES if s[8].get("addb") and s[3] <= 10]
+
+
+@pytest.mark.parametrize("spec", _SCALAR, ids=[s[0] for s in _SCALAR])
+def test_gpu_extreme_case_scalar_deblocking(spec, monkeypatch):
+    """the scalar ADDB line filters (XEVD_HIP_ADDB_SCALAR is read when a context opens) where the packed ones run by default: <= 10 bit"""
+    monkeypatch.setenv("XEVD_HIP_ADDB_SCALAR", "1")
+    _check(cases.build_case(*spec[:9]), spec[0] + " (scalar ADDB)")
+
+
+@pytest.mark.parametrize("name", ["x_addb_ladder_10b", "x_alf_gratings_12b", "x_mc_checker2_base_b_8b", "x_mv_thresholds_main_10b", "x_recon_rails_10b",
+                                  "x_intra_eipd_htdf_ibc_10b", "x_dmvr_checker_10b", "x_affine_checker_10b"])
+def test_gpu_extreme_case_residual_pass_ahead(name):
+    """once per family with the residual pass queued inside the previous picture's launch (xgpu_batch_recon_ahead)"""
+    spec = next(s for s in xi.EXTREME_CASES if s[0] == name)
+    _check(cases.build_case(*spec[:9]), name + " (ahead)", ahead=True)
+
+
+# content kind x bit depth x partition depth per coding family.  split_prob low / high: k_inter's region and tile roles / its split role see the saturated windows
+FAMILIES = {
+    "base_pb": (0, 0, (2, 2), 0.4, {"inter_frac": 1.0}),
+    "main_b_addb_alf": (1, 1, (2, 2), 0.5, {"addb": 1, "alf": 1, "inter_frac": 1.0}),
+    "main_dmvr": (1, 1, (2, 2), 0.9, {"addb": 1, "inter_frac": 1.0, "dmvr_frac": 0.9, "oob_frac": 0.0}),
+    "main_affine_eif": (1, 1, (2, 2), 0.5, {"addb": 1, "alf": 1, "inter_frac": 1.0, "affine_frac": 0.9}),
+}
+CONTENT = ("noise", "checker1", "checker2", "checker4", "rows", "cols", "flat0", "flatmax", "rails_dither", "ladder", "gratings")
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+@pytest.mark.parametrize("family", sorted(FAMILIES))
+def test_gpu_content_kinds(family, bd):
+    admvp, iqt, n_refs, bi, tools = FAMILIES[family]
+    ol.census_reset()
+    for n, kind in enumerate(CONTENT):
+        for split in ((0.15, 0.85) if kind in ("noise", "checker1", "rails_dither") else ((0.15, 0.85)[(n + bd // 2) & 1],)):
+            t = dict(tools, split_prob=split, amp=40.0 if n & 1 else 2.0, extreme={"content": [kind, "noise" if n % 3 == 0 else kind], "mv": None if family == "main_affine_eif" else "small"})
+            cs = cases.build_case(f"xm_{family}_{kind}", 136, 72, bd, admvp, iqt, n_refs, bi, t, seed=n)
+            _check(cs, f"{family} {kind} {bd} bit split {split}")
+    cen = ol.census()      # over the whole sweep: saturated windows went through the interpolation and the reconstruction at both rails
+    assert (cen["mc_clip"] > 0).all() and (cen["recon_clip"] > 0).all() and (cen["mc_bi_rails"] > 0).all(), (cen["mc_clip"].tolist(), cen["recon_clip"].tolist())
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+@pytest.mark.parametrize("tools", [{"eipd": 1, "addb": 1}, {"eipd": 1, "addb": 1, "alf": 1, "htdf_qp": 27}, {"eipd": 1, "addb": 1, "htdf_qp": 40, "ibc_frac": 0.4}, {}],
+                         ids=["eipd", "eipd_htdf_alf", "eipd_htdf_ibc", "base_modes"])
+def test_gpu_all_intra_at_the_rails(tools, bd):
+    """all-intra pictures whose residuals drive the reconstruction - the neighbours of the next CU - into both rails.  (What the current picture holds beforehand
+    plays no part: every sample is written by a CU and unavailable neighbours come from the availability map.)"""
+    ol.census_reset()
+    for split in (0.2, 0.8):
+        t = dict(tools, inter_frac=0.0, amp=40.0, coded_frac=0.9, split_prob=split, btt_frac=0.5 if tools else 0.0)
+        if tools.get("alf"):
+            t["extreme"] = {"alf": ("extreme", "on")}
+        cs = cases.build_case("xm_intra", 136, 72, bd, 1 if tools else 0, 1 if tools else 0, (1, 0), 0.0, t, seed=int(split * 10))
+        _check(cs, f"all-intra {sorted(tools)} {bd} bit split {split}", resid=True)
+    cen = ol.census()
+    assert min(cen["recon_clip"]) * 200 >= cen["recon_coded"] > 0, (cen["recon_clip"].tolist(), cen["recon_coded"])      # each rail in >= 0.5 % of the coded samples
+
+
+# 5 of the 25 pairs of {-12, -6, 0, 6, 12}^2, a choice: every value occurs for alpha and for beta, with both signs against each other
+OFFSETS = [(-12, 12), (-6, -6), (0, 0), (6, -12), (12, 6)]
+# XEVD_HIP_ADDB_SCALAR selects the line filters of k_addb_alf only (k_addb alone has one form), and above 10 bit the scalar form is the default: only the
+# combinations that differ exist
+ADDB_SWEEP = [(bd, alf, 0) for bd in (8, 10, 12) for alf in (0, 1)] + [(bd, 1, 1) for bd in (8, 10)]
+
+
+@pytest.mark.parametrize("bd,alf,scalar", ADDB_SWEEP, ids=[f"{bd}b-{'k_addb_alf' if alf else 'k_addb'}-{'scalar' if sc else 'default'}" for bd, alf, sc in ADDB_SWEEP])
+def test_gpu_addb_offsets_qp_sweep(bd, alf, scalar, monkeypatch):
+    """QP 0..51 per CU x slice offsets on the step ladder and on full-range noise, 136x136 (an interior filter tile exists), ALF fused behind the filter or not"""
+    if scalar:
+        monkeypatch.setenv("XEVD_HIP_ADDB_SCALAR", "1")
+    ol.census_reset()
+    for n, (ao, bo) in enumerate(OFFSETS):
+        for content in (["ladder", "rails_dither"], ["noise", "ladder"]):
+            t = {"addb": 1, "alf": alf, "inter_frac": 0.7, "qp_range": (0, 51), "coded_frac": 0.5, "split_prob": 0.7, "alpha_off": ao, "beta_off": bo,
+                 "extreme": {"content": content, "qp": "areas", "mv": "grid8", "alf": ("extreme", "on")}}
+            cs = cases.build_case("xm_addb", 136, 136, bd, 1, 1, (2, 2), 0.5, t, seed=n)
+            _check(cs, f"ADDB offsets ({ao}, {bo}) {bd} bit {content[0]} alf {alf} scalar {scalar}")
+    cen = ol.census()      # over the sweep: the top of both tables on both planes, every bS filtered and skipped, strong and weak, all (ap, aq), the beta wrap at 12 bit
+    assert (cen["addb_index_a"][:, 51] > 0).all() and (cen["addb_index_b"][:, 51] > 0).all() and (cen["addb_index_a"][0, 46:] > 0).all()
+    assert (cen["addb_gate"][:, 1:5] > 0).all() and (cen["addb_bs4"] > 0).all() and (cen["addb_apq"] > 0).all() and (cen["addb_d0"] > 0).all(), cen["addb_gate"].tolist()
+    assert (cen["addb_lost"][0] > 0) == (bd == 12)
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+@pytest.mark.parametrize("content", ["gratings", "noise", "checker2"])
+def test_gpu_alf_parameter_kinds(content, bd):
+    """coefficient kinds x CTB flag kinds x enables, CTU 64 and 128"""
+    kinds = [("extreme", "on", (1, 1, 1)), ("extreme", "checker", (1, 1, 1)), ("single", "on", (1, 1, 1)), ("smooth", "on", (1, 1, 1)), ("single", "off", (1, 1, 1)),
+             ("extreme", "on", (1, 0, 0)), ("single", "checker", (0, 1, 1))]
+    ol.census_reset()
+    for n, (kind, ctb, enable) in enumerate(kinds):
+        for log2_ctu in ((6, 7) if n < 3 else ((6, 7)[n & 1],)):
+            t = {"alf": 1, "addb": n & 1, "no_deblock": 1 - (n & 1), "alf_enable": enable, "inter_frac": 1.0, "coded_frac": 0.2, "log2_ctu": log2_ctu, "split_prob": 0.4,
+                 "extreme": {"content": content, "mv": "grid8" if content == "gratings" else "small", "alf": (kind, ctb)}}
+            cs = cases.build_case("xm_alf", 264, 136, bd, 1, 1, (1, 1), 0.3, t, seed=n)
+            _check(cs, f"ALF {kind} flags {ctb} enable {enable} CTU {1 << log2_ctu} {content} {bd} bit")
+    cen = ol.census()
+    assert (cen["alf_clip"] > 0).all() and (cen["alf_tr"] > 0).all(), cen["alf_clip"].tolist()
+    if content == "gratings":
+        assert (cen["alf_class"] > 0).all(), cen["alf_class"].tolist()
+
+
+def test_gpu_mv_thresholds_wide_picture():
+    """the MV-clip thresholds at a width of 2112 (33 regions a row: the magic-division strip maps)"""
+    t = {"addb": 1, "inter_frac": 1.0, "split_prob": 0.6, "extreme": {"content": ["noise", "checker2"], "mv": "thresholds"}}
+    cs = cases.build_case("xm_mv_wide", 2112, 72, 8, 1, 1, (1, 1), 0.4, t)
+    (ref, _, _, _), cen = run_oracle_with_census(cs)
+    assert (cen["mv_clip"] > 0).all(), cen["mv_clip"].tolist()
+    _same(cases.run_gpu(cs), ref, "2112x72 MV thresholds")
+
+
+def test_gpu_rail_to_rail_1080p():
+    """one full-size rail-to-rail picture (k_inter's region role on saturated windows, every filter tile of k_addb_alf on 0 / max checkerboards and noise)"""
+    t = {"addb": 1, "alf": 1, "inter_frac": 1.0, "split_prob": 0.3, "extreme": {"content": ["checker1", "noise", "checker2", "rails_dither"], "mv": "small", "alf": ("extreme", "on")}}
+    cs = cases.build_case("xm_1080p", 1920, 1080, 10, 1, 1, (2, 2), 0.5, t)
+    (ref, _, _, _), cen = run_oracle_with_census(cs)
+    assert (cen["mc_clip"] > 0).all() and (cen["alf_clip"] > 0).all(), (cen["mc_clip"].tolist(), cen["alf_clip"].tolist())
+    _same(cases.run_gpu(cs), ref, "1920x1080 rail to rail")
+
+
+@pytest.mark.parametrize("scalar", [0, 1], ids=["packed", "scalar"])
+@pytest.mark.parametrize("spec", xi.TILE_CASES, ids=[s[0] for s in xi.TILE_CASES])
+def test_gpu_tile_borders_inside_interior_filter_tiles(spec, scalar, monkeypatch):
+    """uneven 2x2 / 3x2 tile grids whose CTU-aligned borders cross interior 64x64 filter tiles of k_addb_alf (the tile-border branch of
+    addb_edge_strength_rt), loop_filter_across_tiles 0 and 1, packed and scalar line filters (at 12 bit both runs take the scalar ones), rail-to-rail content"""
+    if scalar:
+        monkeypatch.setenv("XEVD_HIP_ADDB_SCALAR", "1")
+    cs = cases.build_case(*spec)
+    (ref, _, _, rr), cen = run_oracle_with_census(cs)
+    check_tile_census(spec, cs, cen)
+    out, res = cases.run_gpu(cs, resid=True)
+    assert np.array_equal(res[:len(rr)], rr), "residual arena"
+    _same(out, ref, spec[0])
+    _same(cases.run_gpu(cs, ahead=True), ref, spec[0] + " (ahead)")
+
+
+@pytest.mark.parametrize("name", sorted(n for n, hit in TILED_STREAMS_REACHING_INTERIOR_BORDERS.items() if hit))
+def test_gpu_tiled_golden_streams_scalar_deblocking(name, monkeypatch):
+    """the committed tiled streams that reach the tile-border branch inside interior filter tiles (test_which_tiled_golden_streams_reach_the_tile_border_branch) are
+    decoded with the packed filters by the stream tests; here with the scalar ones, against the pictures the reference decoder produced"""
+    import os
+    import golden_io
+    import stream_util as su
+    monkeypatch.setenv("XEVD_HIP_ADDB_SCALAR", "1")
+    d = np.load(os.path.join(golden_io.GOLDEN, f"stream_{name}.npz"))
+    got = su.decode_gpu(d["bytes"].tobytes())
+    want = su.decode_oracle(d["bytes"].tobytes())
+    assert len(got) == len(want)
+    for k, (g, w_) in enumerate(zip(got, want)):
+        for c in range(3):
+            assert np.array_equal(g[c], w_[c]), f"picture {k} plane {c}: {np.argwhere(np.asarray(g[c]) != w_[c])[:4].tolist()}"
