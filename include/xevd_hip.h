@@ -328,6 +328,40 @@ int    xgpu_colour_tables(const xgpu_output_format *f, const xgpu_colour_transfo
    kernel runs on, ordered like the DRA tables - only when `cm` or the depth differ from the previous call's. */
 int    xgpu_pic_output_device_cm(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm,
                                  void *d_dst, size_t dst_size, void *stream);
+/* ---- scaled output (k_output_scaled.hip): the picture resized to the size a model takes, converted and normalised, from the picture read once.  The source is
+   the active picture minus f->crop (even; it doubles as the region of interest), Ws x Hs luma samples; the destination is sc->width x sc->height elements per
+   channel, in one of the four three-channel layouts (XGPU_OUT_RGB_PLANAR / _INTERLEAVED, XGPU_OUT_YUV444_PLANAR / _INTERLEAVED; any other:
+   XGPU_ERR_INVALID_ARGUMENT).  Y is filtered from the luma plane, Cb and Cr straight from their half-resolution planes onto the destination grid, placed by
+   f->chroma_loc (f->upsample is not read).  Two separable passes of non-negative 14-bit integer taps, vertical first: t = (sum qy * sample + 2^10) >> 11, then
+   v = (sum qx * t + 2^16) >> 17; every source sample is DRA-mapped (when `dra` is given) and clipped to [0, 2^B - 1] first.  (Y, Cb, Cr) of the destination
+   pixel then go through the conversion of xgpu_pic_output_device (matrix, range, bgr, integer and float rules unchanged).  normalize (float dtypes only):
+   out = (v - mean[k]) * inv_std[k] after the clip, in float32, subtraction and multiplication rounded one by one, k the channel's position in the output (after
+   bgr); then the F16 / BF16 rounding.
+     XGPU_SCALE_BILINEAR   the triangle widened by the reduction ratio - the window of torch / PIL resizing with antialias=True; plain bilinear when enlarging
+     XGPU_SCALE_AREA       the box: every destination sample is the mean of the source area it covers
+   Limits: 2 <= width, height <= 16384, and per axis Ws / 64 <= width <= 8 Ws: XGPU_ERR_UNSUPPORTED outside.  normalize with an integer dtype, a non-finite mean
+   or inv_std: XGPU_ERR_INVALID_ARGUMENT.  Every refusal comes before anything is queued.  With the destination the size of the source and XGPU_UPSAMPLE_LINEAR the
+   result is xgpu_pic_output_device's, bit for bit, for every chroma_loc (R'G'B' floats: see INTEGRATION.md).  The exact contract: INTEGRATION.md section 8d;
+   tests/scale_ref.py restates it in numpy, the taps with fractions.Fraction. */
+#define XGPU_SCALE_BILINEAR 0
+#define XGPU_SCALE_AREA     1
+typedef struct xgpu_scale_params { int width, height, filter, normalize; float mean[3], inv_std[3]; } xgpu_scale_params;
+/* Host only, no context: the taps of one axis of one plane - n_plane samples, subsampling 1 (luma) or 2 (chroma), the chroma grid siting_half_luma / 2 luma
+   samples behind the luma grid (0, 1, 2; luma: 0), n_dst destination samples.  Destination sample o reads samples first[o] .. first[o] + count[o] - 1 with the
+   weights w[o * w_stride + k] (sum 16384, none negative; the rest of the row is set to 0).  Returns the widest row (w = NULL: first and count alone), or
+   XGPU_ERR_UNSUPPORTED for a size outside the limits above, XGPU_ERR_INVALID_ARGUMENT for the rest (w_stride narrower than a row included).  Integer arithmetic
+   only: no float or double takes part. */
+int    xgpu_scale_taps(int n_plane, int subsampling, int siting_half_luma, int n_dst, int filter, int32_t *first, int32_t *count, int16_t *w, int w_stride);
+/* Host only, no context: the bytes (f, sc) need at d_dst for a picture of width x height (the uncropped size) at coding depth bit_depth - xgpu_output_format_size
+   with sc->width x sc->height in the place of the cropped size; 0: refused.  xgpu_output_scaled_check: 0, or the code xgpu_pic_output_device_scaled refuses with. */
+size_t xgpu_output_scaled_size(const xgpu_output_format *f, const xgpu_scale_params *sc, int width, int height, int bit_depth);
+int    xgpu_output_scaled_check(const xgpu_output_format *f, const xgpu_scale_params *sc, int width, int height, int bit_depth);
+/* Non-blocking; d_dst, dst_size and stream as xgpu_pic_output_device takes them.  The tap tables and the intermediate of the vertical pass belong to the context:
+   the tables are made and uploaded again - on the stream the kernels run on, ordered like the DRA tables - only when the source size, the destination size, the
+   filter or chroma_loc differ from the previous call's; the intermediate grows on demand (growing it waits for the device).  Calls on different streams are ordered
+   one behind the other through the context's stream, so they never overlap on either. */
+int    xgpu_pic_output_device_scaled(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                                     void *d_dst, size_t dst_size, void *stream);
 /* ---- coding side information (k_side_info.hip): what the decoder knows about a picture besides its samples - motion vectors per 4x4 luma unit, the
    reference each one points at, intra / inter / skip / IBC, QP, coded-residual flag, block edges - read out of the SCU map the in-loop filters read
    (the reference's map_scu / map_refi / map_mv, src_base/xevd_def.h:372-438).

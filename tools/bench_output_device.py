@@ -5,7 +5,13 @@ format writes.  Prints one line per form and a JSON line; --out also writes the 
 The side-information forms (xgpu_frame_side_info: k_side_blocks / k_side_flow) follow, on a picture decoded from a synthetic B-picture batch: 16 bytes per
 4x4 unit read + what the form writes, and the same flow made in torch from the BLOCKS tensor (repeat_interleave twice, crop, scale, cast).
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--out out/output_device.json]
+The scaled leg (xgpu_pic_output_device_scaled: k_scale_vertical + k_scale_horizontal) resizes the same picture to 224x224 and to 1920x1080 f32 planar with the
+ImageNet normalise, and times next to it - same run, same stream - the route without it: the full-size f32 tensor, torch's
+interpolate(mode="bilinear", antialias=True) and the normalise in torch; and the time the measured copy rate needs for the bytes the scaled call must move (the
+picture read once, the destination written once).  The call is timed whole; the split between its two kernels is what
+rocprofv3 --kernel-trace --stats shows for `--legs scaled`.
+
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -56,6 +62,41 @@ def timed(torch, s, fn, n, warm=5, sleep=True):
     return float(np.median([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]))
 
 
+SCALED_SIZES = ((224, 224), (1080, 1920))
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def scaled_leg(torch, dec, pic, s, a, res, copy_gbps):
+    """the scaled call against full-size f32 output + F.interpolate(antialias=True) + normalise, and against the copy-rate time of its own bytes"""
+    import torch.nn.functional as F
+    w, h = a.width, a.height
+    mean = torch.tensor(MEAN, device="cuda:0").view(3, 1, 1)
+    inv = (1.0 / torch.tensor(STD, device="cuda:0")).view(3, 1, 1)
+    full = dec.pic_output_tensor(pic, dtype=torch.float32)
+    res["scaled"] = {}
+    for hd, wd in SCALED_SIZES:
+        for filt in ("bilinear", "area"):
+            kw = dict(dtype=torch.float32, size=(hd, wd), filter=filt, mean=MEAN, std=STD)
+            out = dec.pic_output_tensor(pic, **kw)
+            us = timed(torch, s, lambda: dec.pic_output_tensor(pic, out=out, **kw), a.iters)
+            nbytes = int(w * h * 3 + hd * wd * 12)
+            floor_us = nbytes / (copy_gbps * 1e9) * 1e6
+            r = {"us": round(us, 2), "bytes": nbytes, "copy_rate_us": round(floor_us, 2), "frac_copy": round(floor_us / us, 3)}
+            if filt == "bilinear":
+                def route():
+                    dec.pic_output_tensor(pic, out=full, dtype=torch.float32)
+                    return (F.interpolate(full[None], size=(hd, wd), mode="bilinear", antialias=True, align_corners=False)[0] - mean) * inv
+                n = max(a.iters // 10, 5)
+                r_us = timed(torch, s, route, n, warm=2, sleep=False)
+                diff = float((route() - out).abs().max())
+                r.update({"torch_route_us": round(r_us, 2), "speedup": round(r_us / us, 2), "max_abs_diff_vs_torch_route": diff})
+                print(f"scaled {w}x{h} -> {wd}x{hd} f32 {filt:8s} {us:9.1f} us   torch route {r_us:9.1f} us ({r_us / us:.1f}x)   copy-rate time {floor_us:7.1f} us ({floor_us / us:.2f})   max |diff| {diff:.2e}")
+            else:
+                print(f"scaled {w}x{h} -> {wd}x{hd} f32 {filt:8s} {us:9.1f} us   copy-rate time {floor_us:7.1f} us ({floor_us / us:.2f})")
+            res["scaled"][f"{wd}x{hd}_f32_planar_{filt}"] = r
+    del full
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=7680)
@@ -63,6 +104,7 @@ def main():
     ap.add_argument("--bit-depth", type=int, default=10)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--legs", choices=("all", "full", "scaled"), default="all", help="full: the full-size forms and the side information; scaled: the scaled leg alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -96,73 +138,76 @@ def main():
         res["copy_gbps"] = copy_gbps
         s = torch.cuda.Stream()      # a stream of its own: the conversion is queued on it directly (torch's default stream goes through a side stream)
         torch.cuda.set_stream(s)
-        for name, kw, wbytes in forms:
-            out = dec.pic_output_tensor(pic, **kw)
-            for _ in range(5):
-                dec.pic_output_tensor(pic, out=out, **kw)
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]
-            torch.cuda._sleep(int(3e8))      # the GPU waits while the host queues every timed launch: the events then bracket device time only
-            for e0, e1 in ev:
-                e0.record(s)
-                dec.pic_output_tensor(pic, out=out, **kw)
-                e1.record(s)
-            torch.cuda.synchronize()
-            us = float(np.median([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]))
-            nbytes = int(w * h * (3 + wbytes))
-            gbps = nbytes / (us * 1e-6) / 1e9
-            res["forms"][name] = {"us": round(us, 2), "bytes": nbytes, "gbps": round(gbps, 1), "frac_copy": round(gbps / copy_gbps, 3)}
-            print(f"{name:20s} {us:9.1f} us  {nbytes / 1e6:7.1f} MB  {gbps:7.1f} GB/s  {gbps / copy_gbps:5.2f} of copy ({copy_gbps:.0f} GB/s)")
-        # the same two transforms done afterwards in torch on the plain f32 RGB tensor (pow / where / matmul), timed the same way
-        rgb = dec.pic_output_tensor(pic, dtype=torch.float32, matrix=9)
-        for name, fn, wbytes in (("torch_pq2020_srgb_u8_after_f32", lambda: torch_transform(torch, rgb, True), 3),
-                                 ("torch_pq2020_linear709_f32_after_f32", lambda: torch_transform(torch, rgb, False), 12)):
-            n = max(a.iters // 10, 5)
-            for _ in range(2):
-                fn()
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
-            for e0, e1 in ev:
-                e0.record(s)
-                fn()
-                e1.record(s)
-            torch.cuda.synchronize()
-            us = float(np.median([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]))
-            res["forms"][name] = {"us": round(us, 2), "launches": n, "note": "excludes the plain f32 output it starts from"}
-            print(f"{name:40s} {us:9.1f} us (torch, after rgb_f32_planar)")
-        # ---- coding side information of a decoded picture: the uploaded picture is both references of a synthetic B picture
-        from xevd_amd import synth
-        batch = synth.gen_frame(np.random.default_rng(1), w, h, bd, inter_frac=0.9, bi_frac=0.5, coded_frac=0.6, n_refs=(1, 1), qp_range=(22, 37), mv_sigma_px=8.0, oob_frac=0.05)
-        cur = dec.pic_alloc()
-        hb = dec.batch_create(batch)
-        dec.decode_picture(cur, 8, {(0, 0): (pic, 4), (0, 1): (pic, 16)}, hb, deblock=True)
-        dec.sync()
-        n_units = (w // 4) * (h // 4)
-        crop = (0, 0, 0, 0)
-        side = [("side_blocks", dict(), 18 * n_units),
-                ("side_flow_f16_both_planar", dict(kind="flow", dtype=torch.float16), 8 * w * h),
-                ("side_flow_f16_both_interleaved", dict(kind="flow", dtype=torch.float16, channels_last=True), 8 * w * h),
-                ("side_flow_f16_list0_planar", dict(kind="flow", dtype=torch.float16, lists=0), 4 * w * h),
-                ("side_flow_f32_both_planar", dict(kind="flow", dtype=torch.float32), 16 * w * h),
-                ("side_flow_f32_both_interleaved", dict(kind="flow", dtype=torch.float32, channels_last=True), 16 * w * h),
-                ("side_flow_f32_list0_planar", dict(kind="flow", dtype=torch.float32, lists=0), 8 * w * h),
-                ("side_flow_f16_both_planar_per_poc", dict(kind="flow", dtype=torch.float16, per_poc=True), 8 * w * h)]
-        for name, kw, wbytes in side:
-            out = dec.frame_side_info(cur, **kw)
-            us = timed(torch, s, lambda: dec.frame_side_info(cur, out=out, **kw), a.iters)
-            nbytes = int(16 * n_units + wbytes)
-            gbps = nbytes / (us * 1e-6) / 1e9
-            res["forms"][name] = {"us": round(us, 2), "bytes": nbytes, "written": int(wbytes), "gbps": round(gbps, 1), "write_gbps": round(wbytes / (us * 1e-6) / 1e9, 1),
-                                  "frac_copy": round(gbps / copy_gbps, 3)}
-            print(f"{name:36s} {us:9.1f} us  {nbytes / 1e6:7.1f} MB  {gbps:7.1f} GB/s  {gbps / copy_gbps:5.2f} of copy ({copy_gbps:.0f} GB/s)")
-        blocks = dec.frame_side_info(cur)
-        for name, dt in (("torch_flow_f16_both_planar_from_blocks", torch.float16), ("torch_flow_f32_both_planar_from_blocks", torch.float32)):
-            n = max(a.iters // 10, 5)
-            us = timed(torch, s, lambda: torch_flow(torch, blocks, crop, dt), n, warm=2, sleep=False)
-            res["forms"][name] = {"us": round(us, 2), "launches": n, "note": "excludes the BLOCKS export it starts from"}
-            print(f"{name:40s} {us:9.1f} us (torch, after side_blocks)")
-            kdt = torch.float16 if dt == torch.float16 else torch.float32
-            same = torch.equal(torch_flow(torch, blocks, crop, dt).view(torch.int16 if dt == torch.float16 else torch.int32),
-                               dec.frame_side_info(cur, kind="flow", dtype=kdt).view(torch.int16 if dt == torch.float16 else torch.int32))
-            res["forms"][name]["equals_kernel"] = bool(same)
+        if a.legs in ("all", "scaled"):
+            scaled_leg(torch, dec, pic, s, a, res, copy_gbps)
+        if a.legs in ("all", "full"):
+            for name, kw, wbytes in forms:
+                out = dec.pic_output_tensor(pic, **kw)
+                for _ in range(5):
+                    dec.pic_output_tensor(pic, out=out, **kw)
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]
+                torch.cuda._sleep(int(3e8))      # the GPU waits while the host queues every timed launch: the events then bracket device time only
+                for e0, e1 in ev:
+                    e0.record(s)
+                    dec.pic_output_tensor(pic, out=out, **kw)
+                    e1.record(s)
+                torch.cuda.synchronize()
+                us = float(np.median([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]))
+                nbytes = int(w * h * (3 + wbytes))
+                gbps = nbytes / (us * 1e-6) / 1e9
+                res["forms"][name] = {"us": round(us, 2), "bytes": nbytes, "gbps": round(gbps, 1), "frac_copy": round(gbps / copy_gbps, 3)}
+                print(f"{name:20s} {us:9.1f} us  {nbytes / 1e6:7.1f} MB  {gbps:7.1f} GB/s  {gbps / copy_gbps:5.2f} of copy ({copy_gbps:.0f} GB/s)")
+            # the same two transforms done afterwards in torch on the plain f32 RGB tensor (pow / where / matmul), timed the same way
+            rgb = dec.pic_output_tensor(pic, dtype=torch.float32, matrix=9)
+            for name, fn, wbytes in (("torch_pq2020_srgb_u8_after_f32", lambda: torch_transform(torch, rgb, True), 3),
+                                     ("torch_pq2020_linear709_f32_after_f32", lambda: torch_transform(torch, rgb, False), 12)):
+                n = max(a.iters // 10, 5)
+                for _ in range(2):
+                    fn()
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+                for e0, e1 in ev:
+                    e0.record(s)
+                    fn()
+                    e1.record(s)
+                torch.cuda.synchronize()
+                us = float(np.median([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]))
+                res["forms"][name] = {"us": round(us, 2), "launches": n, "note": "excludes the plain f32 output it starts from"}
+                print(f"{name:40s} {us:9.1f} us (torch, after rgb_f32_planar)")
+            # ---- coding side information of a decoded picture: the uploaded picture is both references of a synthetic B picture
+            from xevd_amd import synth
+            batch = synth.gen_frame(np.random.default_rng(1), w, h, bd, inter_frac=0.9, bi_frac=0.5, coded_frac=0.6, n_refs=(1, 1), qp_range=(22, 37), mv_sigma_px=8.0, oob_frac=0.05)
+            cur = dec.pic_alloc()
+            hb = dec.batch_create(batch)
+            dec.decode_picture(cur, 8, {(0, 0): (pic, 4), (0, 1): (pic, 16)}, hb, deblock=True)
+            dec.sync()
+            n_units = (w // 4) * (h // 4)
+            crop = (0, 0, 0, 0)
+            side = [("side_blocks", dict(), 18 * n_units),
+                    ("side_flow_f16_both_planar", dict(kind="flow", dtype=torch.float16), 8 * w * h),
+                    ("side_flow_f16_both_interleaved", dict(kind="flow", dtype=torch.float16, channels_last=True), 8 * w * h),
+                    ("side_flow_f16_list0_planar", dict(kind="flow", dtype=torch.float16, lists=0), 4 * w * h),
+                    ("side_flow_f32_both_planar", dict(kind="flow", dtype=torch.float32), 16 * w * h),
+                    ("side_flow_f32_both_interleaved", dict(kind="flow", dtype=torch.float32, channels_last=True), 16 * w * h),
+                    ("side_flow_f32_list0_planar", dict(kind="flow", dtype=torch.float32, lists=0), 8 * w * h),
+                    ("side_flow_f16_both_planar_per_poc", dict(kind="flow", dtype=torch.float16, per_poc=True), 8 * w * h)]
+            for name, kw, wbytes in side:
+                out = dec.frame_side_info(cur, **kw)
+                us = timed(torch, s, lambda: dec.frame_side_info(cur, out=out, **kw), a.iters)
+                nbytes = int(16 * n_units + wbytes)
+                gbps = nbytes / (us * 1e-6) / 1e9
+                res["forms"][name] = {"us": round(us, 2), "bytes": nbytes, "written": int(wbytes), "gbps": round(gbps, 1), "write_gbps": round(wbytes / (us * 1e-6) / 1e9, 1),
+                                      "frac_copy": round(gbps / copy_gbps, 3)}
+                print(f"{name:36s} {us:9.1f} us  {nbytes / 1e6:7.1f} MB  {gbps:7.1f} GB/s  {gbps / copy_gbps:5.2f} of copy ({copy_gbps:.0f} GB/s)")
+            blocks = dec.frame_side_info(cur)
+            for name, dt in (("torch_flow_f16_both_planar_from_blocks", torch.float16), ("torch_flow_f32_both_planar_from_blocks", torch.float32)):
+                n = max(a.iters // 10, 5)
+                us = timed(torch, s, lambda: torch_flow(torch, blocks, crop, dt), n, warm=2, sleep=False)
+                res["forms"][name] = {"us": round(us, 2), "launches": n, "note": "excludes the BLOCKS export it starts from"}
+                print(f"{name:40s} {us:9.1f} us (torch, after side_blocks)")
+                kdt = torch.float16 if dt == torch.float16 else torch.float32
+                same = torch.equal(torch_flow(torch, blocks, crop, dt).view(torch.int16 if dt == torch.float16 else torch.int32),
+                                   dec.frame_side_info(cur, kind="flow", dtype=kdt).view(torch.int16 if dt == torch.float16 else torch.int32))
+                res["forms"][name]["equals_kernel"] = bool(same)
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -23,13 +23,24 @@ def main():
                     "StreamDecoder.COLOUR_PRESETS), converted on the device from the primaries / transfer characteristics of the stream's VUI")
     ap.add_argument("--side-info", default=None, metavar="FILE", help="also write the coding side information of every picture, in DECODING order: a text line "
                     "'POC h_scu w_scu', then nine planes of h_scu x w_scu little-endian int16 (list 0 / 1 vectors, POC distances, mode, QP, flags: INTEGRATION.md 8c)")
+    ap.add_argument("--size", default=None, metavar="WxH", help="write interleaved 8-bit RGB frames resized to W x H on the device instead (antialiased bilinear, "
+                    "the matrix / range / chroma siting of the stream's VUI: INTEGRATION.md 8d); with --to: not supported")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
     data = open(args.input, "rb").read()
     t0 = time.perf_counter()
     side = {} if args.side_info else None
     # crop-free output like the reference application; bit-depth conversion and plane packing run on the device (xgpu_pic_output)
-    if args.to is not None:
+    if args.size is not None:
+        import torch
+        if args.to is not None:
+            ap.error("--size: the scaled output takes no colour transform (--to)")
+        try:
+            wd, hd = (int(v) for v in args.size.lower().split("x"))
+        except ValueError:
+            ap.error(f"--size: expected WxH, not {args.size!r}")
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side)
+    elif args.to is not None:
         import torch
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side)
     elif args.pix_fmt == "yuv420p":

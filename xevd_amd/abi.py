@@ -75,6 +75,44 @@ def make_side_format(layout=SIDE_BLOCKS, dtype=OUT_U16, lists=3, per_poc=False, 
     return f
 
 
+SCALE_BILINEAR, SCALE_AREA = 0, 1
+
+
+class ScaleParams(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("filter", C.c_int), ("normalize", C.c_int), ("mean", C.c_float * 3), ("inv_std", C.c_float * 3)]
+
+
+def make_scale_params(width, height, filter=SCALE_BILINEAR, mean=None, std=None, inv_std=None):
+    """xgpu_scale_params (include/xevd_hip.h): the destination size, the filter, and - when mean or std (or inv_std) is given - the normalise
+    out = (v - mean[k]) * inv_std[k], k the channel's position in the output; inv_std = float32(1) / float32(std), one float32 division"""
+    p = ScaleParams()
+    p.width, p.height, p.filter = int(width), int(height), int(filter)
+    p.normalize = int(mean is not None or std is not None or inv_std is not None)
+    m = np.zeros(3, np.float32) if mean is None else np.broadcast_to(np.asarray(mean, np.float32), (3,))
+    if inv_std is not None:
+        i = np.broadcast_to(np.asarray(inv_std, np.float32), (3,))
+    elif std is not None:
+        i = np.float32(1) / np.broadcast_to(np.asarray(std, np.float32), (3,))
+    else:
+        i = np.ones(3, np.float32)
+    for k in range(3):
+        p.mean[k], p.inv_std[k] = float(m[k]), float(i[k])
+    return p
+
+
+def scale_taps(lib, n_plane, subsampling, siting_half_luma, n_dst, filter=SCALE_BILINEAR):
+    """xgpu_scale_taps as numpy arrays: (first [n_dst] int32, count [n_dst] int32, w [n_dst][widest] int16 - row o: count[o] weights of sum 16384, then
+    zeros), or the negative code"""
+    first, count = np.zeros(max(int(n_dst), 1), np.int32), np.zeros(max(int(n_dst), 1), np.int32)
+    pi, pc = first.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_int32))
+    widest = lib.xgpu_scale_taps(int(n_plane), int(subsampling), int(siting_half_luma), int(n_dst), int(filter), pi, pc, None, 0)
+    if widest < 0:
+        return widest
+    w = np.zeros((int(n_dst), widest), np.int16)
+    rc = lib.xgpu_scale_taps(int(n_plane), int(subsampling), int(siting_half_luma), int(n_dst), int(filter), pi, pc, w.ctypes.data_as(C.POINTER(C.c_int16)), widest)
+    return rc if rc < 0 else (first, count, w)
+
+
 CM_CURVE_U0, CM_CURVE_SIZE = 0x1F800000, 64 * 32 + 3
 
 
@@ -273,6 +311,10 @@ _EXPORTS = {
     "xgpu_output_coeffs": (C.c_int, [C.POINTER(OutputFormat), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "xgpu_colour_tables": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ColourTransform), C.c_int, C.POINTER(ColourTables)]),
     "xgpu_pic_output_device_cm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ColourTransform), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_scale_taps": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16), C.c_int]),
+    "xgpu_output_scaled_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),
+    "xgpu_output_scaled_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),
+    "xgpu_pic_output_device_scaled": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_side_info_size": (C.c_size_t, [C.POINTER(SideFormat), C.c_int, C.c_int]),
     "xgpu_frame_side_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SideFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),

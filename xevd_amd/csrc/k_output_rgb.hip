@@ -11,27 +11,8 @@
 // 8 bytes (u8 planar), 16 bytes (16-bit planar, every interleaved form but u8), three 8-byte stores (u8 interleaved: 24 bytes at 8-byte alignment);
 // otherwise, and in the last column group of a row, element by element (any element-aligned destination: frame k of a [N, 3, H, W] batch).
 // Templated over layout x dtype x upsampling mode; chroma siting, matrix, range and channel order are uniform arguments.
-// The body is output_three_channels (output_common.h), shared with k_output_yuv444; this file adds the matrix (RgbConv).
+// The body is output_three_channels (output_common.h), shared with k_output_yuv444, and the matrix is RgbConv (output_common.h too: the scaled output shares it).
 #include "output_common.h"
-
-// one pixel: three channel values (as the bits of the output element) in R, G, B order
-template <int DT> struct RgbConv {
-__device__ static __forceinline__ void apply(const RgbOutArgs &a, int y, int cb, int cr, uint32_t &r, uint32_t &g, uint32_t &b)
-{
-    const int yy = y - a.yo, u = cb - a.co, v = cr - a.co;
-    if (OutT<DT>::is_float) {
-        const float fy = a.fcoef[0] * (float)yy, fu = (float)u, fv = (float)v;
-        r = fbits<DT>(fminf(fmaxf(fy + a.fcoef[1] * fv, 0.f), 1.f));
-        g = fbits<DT>(fminf(fmaxf(fy + a.fcoef[2] * fu + a.fcoef[3] * fv, 0.f), 1.f));
-        b = fbits<DT>(fminf(fmaxf(fy + a.fcoef[4] * fu, 0.f), 1.f));
-    } else {
-        const int ty = a.coef[0] * yy + (1 << (a.shift - 1));
-        r = (uint32_t)min(max((ty + a.coef[1] * v) >> a.shift, 0), a.maxv);
-        g = (uint32_t)min(max((ty + a.coef[2] * u + a.coef[3] * v) >> a.shift, 0), a.maxv);
-        b = (uint32_t)min(max((ty + a.coef[4] * u) >> a.shift, 0), a.maxv);
-    }
-}
-};
 
 template <int LAYOUT, int DT, int UP>
 __global__ __launch_bounds__(256) void k_output_rgb(const RgbOutArgs a)

@@ -1,0 +1,161 @@
+// k_output_scaled.hip - a decoded 4:2:0 picture resized to the caller's size, converted and normalised in the caller's device memory
+// (xgpu_pic_output_device_scaled): what a model takes - 224x224, 384x640 - made from the picture read once, instead of a full-size float tensor that a chain
+// of framework kernels then shrinks.  The arithmetic is the contract of INTEGRATION.md section 8d; tests/scale_ref.py restates it in numpy, bit for bit.
+//
+// Two separable passes with non-negative 14-bit integer taps (xgpu_scale.hip), vertical first:
+//   k_scale_vertical     t = (sum qy * clip(dra(sample)) + 2^10) >> 11       the sample with 3 fraction bits, <= 32760 at 12 bit: an unsigned 16-bit intermediate
+//   k_scale_horizontal   v = (sum qx * t + 2^16) >> 17                       in [0, 2^B - 1] without a clip; then the unscaled path's CONV, the normalise, the store
+// One tile cannot hold both: at 8K -> 224 the source footprint of a 16x16 destination tile is about 600x600 samples.  Vertical first because that pass is the one
+// that reads the picture, and along rows it reads it in whole 16-byte groups.
+//
+// k_scale_vertical: one lane owns 8 neighbouring source columns of one destination row of one plane (blockIdx.z) and walks that row's taps: one 16-byte load per
+// tap row - a wave reads 1 KB of one picture row, perfectly coalesced; loads past the cropped width stay inside the padded device picture (>= 72 chroma / 144 luma
+// samples on every side) and the columns they make are never read - DRA and the clip per sample, 8 int32 accumulators, one 16-byte store.  The row index is
+// uniform per wave, so first / count / weights are scalar loads.  Neighbouring destination rows share about half their source rows (the triangle is 2 f wide):
+// those come from L2.  The intermediate is dh x (ws + 2 (ws / 2)) samples - 5 MB for 8K -> 224 rows - and stays in L2 / MALL for the second pass.
+//
+// k_scale_horizontal: a workgroup is 64 destination columns x `rows` destination rows (4; 2 or 1 when the spans are long), one wave per row, one lane per pixel.
+// Each wave stages the spans of its row of the intermediate that its 64 columns reach - Y, Cb, Cr: 16-byte loads from 8-sample-aligned starts into its own part
+// of LDS, whose size the host takes from the tap tables (dynamic shared memory: 36 KB per workgroup at 8K -> 224, under 1 KB for 8K -> 1080p) - then every lane
+// walks its taps: the weights come transposed (w[k][column]), so a wave's weight loads are neighbours; the samples are 16-bit LDS reads at a lane stride of the
+// reduction ratio.  The pixel then goes through RgbConv / YuvConv (output_common.h - for the float dtypes the F32 instance, so that the normalise sees the clipped
+// float32 before the F16 / BF16 rounding, which is what those instances do last) and is stored element by element: the lanes of a wave write neighbouring elements
+// of a row, and the destination is the small side of this kernel.  Any element-aligned destination works; there is no vector / element split to get wrong.
+//
+// Float arithmetic in this file is rounded operation by operation (no contraction into FMA): the normalise is (v - mean) * inv_std in two roundings by contract,
+// and the matrix of the float dtypes is section 8a's formula as tests/colour_ref.py evaluates it.
+#pragma clang fp contract(off)
+#include "output_common.h"
+
+__global__ __launch_bounds__(256) void k_scale_vertical(const ScaledOutArgs a)
+{
+    const int plane = blockIdx.z;
+    const int pw = plane ? a.cw : a.w;
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8;
+    const int o = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y);      // one destination row per wave
+    if (x0 >= pw || o >= a.dh) return;
+    const ScaleTaps &t = plane ? a.yc : a.yl;
+    const int16_t *src = plane == 0 ? a.y : plane == 1 ? a.u : a.v;
+    const int st = plane ? a.sc : a.sy;
+    const int first = t.first[o], cnt = t.count[o];
+    const int16_t *q = t.w + (size_t)o * t.stride;
+    int acc[8];
+    #pragma unroll
+    for (int m = 0; m < 8; m++) acc[m] = 0;
+    for (int k = 0; k < cnt; k++) {
+        const int row = first + k, qk = q[k];
+        const S16x8u s = *(const S16x8u *)(src + (size_t)row * st + x0);
+        int v[8];
+        #pragma unroll
+        for (int m = 0; m < 8; m++) v[m] = s.v[m];
+        if (a.dra) {
+            if (plane == 0) {
+                #pragma unroll
+                for (int m = 0; m < 8; m++) v[m] = dra1(a.dra, 0, v[m], 0);
+            } else {      // the factor of chroma sample (row, x) comes from the unmapped luma sample (2 row, 2 x)
+                const int16_t *l = a.y + (size_t)(2 * row) * a.sy + 2 * x0;
+                const S16x8u l0 = *(const S16x8u *)l, l1 = *(const S16x8u *)(l + 8);
+                #pragma unroll
+                for (int m = 0; m < 8; m++) v[m] = dra1(a.dra, plane, v[m], m < 4 ? l0.v[2 * m] : l1.v[2 * m - 8]);
+            }
+        }
+        #pragma unroll
+        for (int m = 0; m < 8; m++) acc[m] += qk * min(max(v[m], 0), a.smax);
+    }
+    uint16_t *d = a.mid + (plane == 0 ? (size_t)0 : (size_t)a.dh * a.mpy + (size_t)(plane - 1) * a.dh * a.mpc) + (size_t)o * (plane ? a.mpc : a.mpy) + x0;
+    uint32_t w[4];
+    #pragma unroll
+    for (int m = 0; m < 4; m++) w[m] = (uint32_t)((acc[2 * m] + (1 << 10)) >> 11) | ((uint32_t)((acc[2 * m + 1] + (1 << 10)) >> 11) << 16);
+    *(uint4 *)d = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// the span [s0, s1) of one row of the intermediate (s0 a multiple of 8) into the wave's LDS, 8 samples per lane and step
+__device__ __forceinline__ void stage_span(uint16_t *lds, const uint16_t *row, int s0, int s1)
+{
+    for (int i = threadIdx.x * 8; i < s1 - s0; i += 512) *(uint4 *)(lds + i) = *(const uint4 *)(row + s0 + i);
+}
+// destination column o of the staged row: v = (sum qx * t + 2^16) >> 17
+__device__ __forceinline__ int filter_column(const uint16_t *lds, const ScaleTaps &t, int o, int s0)
+{
+    const uint16_t *l = lds + (t.first[o] - s0);
+    const int16_t *q = t.w + o;
+    const int n = t.count[o];
+    int acc = 0;
+    for (int k = 0; k < n; k++) acc += (int)q[(size_t)k * t.stride] * (int)l[k];
+    return (acc + (1 << 16)) >> 17;
+}
+template <int SZ> __device__ __forceinline__ void store_elem(uint8_t *p, uint32_t e)
+{
+    if (SZ == 1) *p = (uint8_t)e;
+    else if (SZ == 2) *(uint16_t *)p = (uint16_t)e;
+    else *(uint32_t *)p = e;
+}
+
+template <bool PLANAR, int DT, template <int> class CONV>
+__global__ __launch_bounds__(256) void k_scale_horizontal(const ScaledOutArgs a)
+{
+    extern __shared__ uint4 lds4[];
+    constexpr int SZ = OutT<DT>::size;
+    const int oy = blockIdx.y * blockDim.y + threadIdx.y, ob = blockIdx.x * 64;
+    const int row = min(oy, a.dh - 1), ol = min(ob + 63, a.dw - 1), ox = min(ob + (int)threadIdx.x, a.dw - 1);      // lanes past the edges work on the edge, and store nothing
+    uint16_t *ly = (uint16_t *)lds4 + (size_t)threadIdx.y * (a.capy + 2 * a.capc), *lb = ly + a.capy, *lr = lb + a.capc;
+    const int y0 = a.xl.first[ob] & ~7, y1 = a.xl.first[ol] + a.xl.count[ol];
+    const int c0 = a.xc.first[ob] & ~7, c1 = a.xc.first[ol] + a.xc.count[ol];
+    const uint16_t *mb = a.mid + (size_t)a.dh * a.mpy, *mr = mb + (size_t)a.dh * a.mpc;
+    stage_span(ly, a.mid + (size_t)row * a.mpy, y0, y1);
+    stage_span(lb, mb + (size_t)row * a.mpc, c0, c1);
+    stage_span(lr, mr + (size_t)row * a.mpc, c0, c1);
+    __syncthreads();
+    const int y = filter_column(ly, a.xl, ox, y0), cb = filter_column(lb, a.xc, ox, c0), cr = filter_column(lr, a.xc, ox, c0);
+
+    uint32_t e[3];
+    if (OutT<DT>::is_float) {
+        CONV<XGPU_OUT_F32>::apply(a, y, cb, cr, e[0], e[1], e[2]);      // the clipped float32
+        if (a.bgr) { const uint32_t t = e[0]; e[0] = e[2]; e[2] = t; }
+        #pragma unroll
+        for (int k = 0; k < 3; k++) {
+            float v = __uint_as_float(e[k]);
+            if (a.normalize) v = __fmul_rn(__fsub_rn(v, a.mean[k]), a.inv_std[k]);
+            e[k] = fbits<DT>(v);
+        }
+    } else {
+        CONV<DT>::apply(a, y, cb, cr, e[0], e[1], e[2]);
+        if (a.bgr) { const uint32_t t = e[0]; e[0] = e[2]; e[2] = t; }
+    }
+    if (oy >= a.dh || ob + (int)threadIdx.x >= a.dw) return;
+    if (PLANAR) {
+        uint8_t *d = a.dst + (size_t)oy * a.pitch + (size_t)ox * SZ;
+        #pragma unroll
+        for (int k = 0; k < 3; k++) store_elem<SZ>(d + k * a.plane, e[k]);
+    } else {
+        uint8_t *d = a.dst + (size_t)oy * a.pitch + (size_t)ox * 3 * SZ;
+        #pragma unroll
+        for (int k = 0; k < 3; k++) store_elem<SZ>(d + k * SZ, e[k]);
+    }
+}
+
+template <bool PLANAR, template <int> class CONV>
+static void launch_horizontal(const ScaledOutArgs &a, int dtype, dim3 grid, dim3 block, size_t lds, hipStream_t s)
+{
+    switch (dtype) {
+    case XGPU_OUT_U8:   hipLaunchKernelGGL((k_scale_horizontal<PLANAR, XGPU_OUT_U8, CONV>), grid, block, lds, s, a); break;
+    case XGPU_OUT_U16:  hipLaunchKernelGGL((k_scale_horizontal<PLANAR, XGPU_OUT_U16, CONV>), grid, block, lds, s, a); break;
+    case XGPU_OUT_F16:  hipLaunchKernelGGL((k_scale_horizontal<PLANAR, XGPU_OUT_F16, CONV>), grid, block, lds, s, a); break;
+    case XGPU_OUT_BF16: hipLaunchKernelGGL((k_scale_horizontal<PLANAR, XGPU_OUT_BF16, CONV>), grid, block, lds, s, a); break;
+    default:            hipLaunchKernelGGL((k_scale_horizontal<PLANAR, XGPU_OUT_F32, CONV>), grid, block, lds, s, a); break;
+    }
+}
+
+void launch_output_scaled(const ScaledOutArgs &a, int layout, int dtype, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_scale_vertical, dim3((unsigned)(((a.w + 7) / 8 + 63) / 64), (unsigned)((a.dh + 3) / 4), 3), dim3(64, 4), 0, s, a);
+    // as many rows per workgroup as 48 KB of LDS hold, 4 at most (a row's spans are at most ~17 KB: 64 columns at a ratio of 64)
+    const size_t per_row = (size_t)(a.capy + 2 * a.capc) * sizeof(uint16_t);
+    int rows = 4;
+    while (rows > 1 && rows * per_row > 48 * 1024) rows >>= 1;
+    const dim3 grid((unsigned)((a.dw + 63) / 64), (unsigned)((a.dh + rows - 1) / rows)), block(64, rows);
+    const bool planar = layout == XGPU_OUT_RGB_PLANAR || layout == XGPU_OUT_YUV444_PLANAR;
+    const bool rgb = layout == XGPU_OUT_RGB_PLANAR || layout == XGPU_OUT_RGB_INTERLEAVED;
+    if (rgb) { if (planar) launch_horizontal<true, RgbConv>(a, dtype, grid, block, rows * per_row, s); else launch_horizontal<false, RgbConv>(a, dtype, grid, block, rows * per_row, s); }
+    else     { if (planar) launch_horizontal<true, YuvConv>(a, dtype, grid, block, rows * per_row, s); else launch_horizontal<false, YuvConv>(a, dtype, grid, block, rows * per_row, s); }
+}

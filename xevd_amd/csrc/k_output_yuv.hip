@@ -74,28 +74,6 @@ void launch_output_semiplanar(const SemiPlanarArgs &a, int dtype, hipStream_t s)
     else                      hipLaunchKernelGGL(k_output_semiplanar<XGPU_OUT_U16>, grid, dim3(64, 4), 0, s, a);
 }
 
-// one pixel: Y, Cb, Cr at the coding depth B -> the bits of three output elements.  u8: the 8-bit rule of xgpu_pic_output (a.shift = B - 8);
-// u16: the sample; floats: E'Y = (Y - yo) * fy in [0, 1], E'Cb = (Cb - 2^(B-1)) * fc in [-0.5, 0.5], E'Cr alike - a.fcoef[0] = fy = float32(1 / yr),
-// a.fcoef[1] = fc = float32(1 / cr), each product one float32 multiplication (nothing to contract with)
-template <int DT> struct YuvConv {
-__device__ static __forceinline__ void apply(const RgbOutArgs &a, int y, int cb, int cr, uint32_t &o0, uint32_t &o1, uint32_t &o2)
-{
-    if (OutT<DT>::is_float) {
-        o0 = fbits<DT>(fminf(fmaxf((float)(y - a.yo) * a.fcoef[0], 0.f), 1.f));
-        o1 = fbits<DT>(fminf(fmaxf((float)(cb - a.co) * a.fcoef[1], -0.5f), 0.5f));
-        o2 = fbits<DT>(fminf(fmaxf((float)(cr - a.co) * a.fcoef[1], -0.5f), 0.5f));
-    } else if (DT == XGPU_OUT_U8) {
-        o0 = (uint32_t)conv1(y, a.shift, 255, 1);
-        o1 = (uint32_t)conv1(cb, a.shift, 255, 1);
-        o2 = (uint32_t)conv1(cr, a.shift, 255, 1);
-    } else {
-        o0 = (uint32_t)(uint16_t)y;
-        o1 = (uint32_t)(uint16_t)cb;
-        o2 = (uint32_t)(uint16_t)cr;
-    }
-}
-};
-
 template <bool PLANAR, int DT, int UP>
 __global__ __launch_bounds__(256) void k_output_yuv444(const RgbOutArgs a)
 {

@@ -92,6 +92,51 @@ template <int N, int SZ> __device__ __forceinline__ void store_run(uint8_t *dst,
     }
 }
 
+// The two CONVs: one pixel's (Y, Cb, Cr) at the coding depth -> the bits of three output elements.  Here, not in k_output_rgb.hip / k_output_yuv.hip, because the
+// scaled output (k_output_scaled.hip) ends in the same conversions.
+// RgbConv - the matrix of k_output_rgb.
+// one pixel: three channel values (as the bits of the output element) in R, G, B order
+template <int DT> struct RgbConv {
+__device__ static __forceinline__ void apply(const RgbOutArgs &a, int y, int cb, int cr, uint32_t &r, uint32_t &g, uint32_t &b)
+{
+    const int yy = y - a.yo, u = cb - a.co, v = cr - a.co;
+    if (OutT<DT>::is_float) {
+        const float fy = a.fcoef[0] * (float)yy, fu = (float)u, fv = (float)v;
+        r = fbits<DT>(fminf(fmaxf(fy + a.fcoef[1] * fv, 0.f), 1.f));
+        g = fbits<DT>(fminf(fmaxf(fy + a.fcoef[2] * fu + a.fcoef[3] * fv, 0.f), 1.f));
+        b = fbits<DT>(fminf(fmaxf(fy + a.fcoef[4] * fu, 0.f), 1.f));
+    } else {
+        const int ty = a.coef[0] * yy + (1 << (a.shift - 1));
+        r = (uint32_t)min(max((ty + a.coef[1] * v) >> a.shift, 0), a.maxv);
+        g = (uint32_t)min(max((ty + a.coef[2] * u + a.coef[3] * v) >> a.shift, 0), a.maxv);
+        b = (uint32_t)min(max((ty + a.coef[4] * u) >> a.shift, 0), a.maxv);
+    }
+}
+};
+
+// YuvConv - the 4:4:4 layouts of k_output_yuv.
+// one pixel: Y, Cb, Cr at the coding depth B -> the bits of three output elements.  u8: the 8-bit rule of xgpu_pic_output (a.shift = B - 8);
+// u16: the sample; floats: E'Y = (Y - yo) * fy in [0, 1], E'Cb = (Cb - 2^(B-1)) * fc in [-0.5, 0.5], E'Cr alike - a.fcoef[0] = fy = float32(1 / yr),
+// a.fcoef[1] = fc = float32(1 / cr), each product one float32 multiplication (nothing to contract with)
+template <int DT> struct YuvConv {
+__device__ static __forceinline__ void apply(const RgbOutArgs &a, int y, int cb, int cr, uint32_t &o0, uint32_t &o1, uint32_t &o2)
+{
+    if (OutT<DT>::is_float) {
+        o0 = fbits<DT>(fminf(fmaxf((float)(y - a.yo) * a.fcoef[0], 0.f), 1.f));
+        o1 = fbits<DT>(fminf(fmaxf((float)(cb - a.co) * a.fcoef[1], -0.5f), 0.5f));
+        o2 = fbits<DT>(fminf(fmaxf((float)(cr - a.co) * a.fcoef[1], -0.5f), 0.5f));
+    } else if (DT == XGPU_OUT_U8) {
+        o0 = (uint32_t)conv1(y, a.shift, 255, 1);
+        o1 = (uint32_t)conv1(cb, a.shift, 255, 1);
+        o2 = (uint32_t)conv1(cr, a.shift, 255, 1);
+    } else {
+        o0 = (uint32_t)(uint16_t)y;
+        o1 = (uint32_t)(uint16_t)cb;
+        o2 = (uint32_t)(uint16_t)cr;
+    }
+}
+};
+
 // The body of the kernels that write three channels at luma resolution (k_output_rgb, k_output_yuv444): one lane makes 8 horizontal pixels of the
 // two luma rows that share chroma row i.  Load, edge clamp, DRA and upsampling are here, once; CONV::apply turns one pixel's (Y, Cb, Cr) at the
 // coding depth into the bits of three output elements.  PLANAR: three planes a.plane bytes apart, else the three elements of a pixel side by side.

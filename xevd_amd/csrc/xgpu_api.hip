@@ -128,6 +128,8 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
     for (int i = 0; i < 2; i++) { c->d_out[i] = NULL; c->out_caps[i] = 0; c->out_ready[i] = c->out_done[i] = 0; c->out_busy[i] = 0; }
     c->d_md5 = NULL; c->md5_ready = 0;
     c->odev_ev[0] = c->odev_ev[1] = 0;
+    c->sc_tab = NULL; c->sc_tab_cap = 0; c->sc_mid = NULL; c->sc_mid_cap = 0;
+    for (int i = 0; i < 6; i++) c->sc_key[i] = -1;
     c->out_next = 0;
     memset(c->t_ms, 0, sizeof(c->t_ms)); memset(c->t_n, 0, sizeof(c->t_n));
     // chroma QP mapping: caller table starts at qp = -6*(bdc-8); default = Baseline static table with the
@@ -219,6 +221,8 @@ void xgpu_close(xgpu_ctx *c)
     if (c->d_dra) (void)hipFree(c->d_dra);
     if (c->d_cm) (void)hipFree(c->d_cm);
     delete c->cm_tab;
+    if (c->sc_tab) (void)hipFree(c->sc_tab);
+    if (c->sc_mid) (void)hipFree(c->sc_mid);
     if (c->d_ctb_flag) (void)hipFree(c->d_ctb_flag);
     for (auto &e : c->ev_pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : c->ev_pool) (void)hipEventDestroy(e);
@@ -696,6 +700,149 @@ static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const x
     HIPCHK(c, hipGetLastError());
     if (stream) {
         HIPCHK(c, hipEventRecord(c->odev_ev[1], s));      // the context's stream does not touch the slot or the DRA tables before the kernel is done
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->odev_ev[1], 0));
+    }
+    return XGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ scaled output into device memory
+// format and scale parameters for a picture of width x height at depth bd: the bytes the destination needs, or 0 with *rc = the code and `why`
+static size_t scaled_size(const xgpu_output_format *f, const xgpu_scale_params *sc, int width, int height, int bd, int *rc, const char **why)
+{
+    *rc = XGPU_ERR_INVALID_ARGUMENT;
+    *why = "format or scale parameters are NULL";
+    if (!f || !sc) return 0;
+    *why = "picture size or bit depth out of range";
+    if (width <= 0 || height <= 0 || ((width | height) & 1) || bd < 8 || bd > 12) return 0;
+    *why = "scaled output: layout must be XGPU_OUT_RGB_PLANAR / _INTERLEAVED or XGPU_OUT_YUV444_PLANAR / _INTERLEAVED";
+    if (!is_rgb(f->layout) && !is_yuv444(f->layout)) return 0;
+    const int frc = check_format(f, bd, why);
+    if (frc < 0) { *rc = frc; return 0; }
+    *why = "crop leaves no picture";
+    if (f->crop[0] + f->crop[1] >= width || f->crop[2] + f->crop[3] >= height) return 0;
+    *why = "filter must be XGPU_SCALE_BILINEAR or XGPU_SCALE_AREA, normalize 0 or 1";
+    if ((sc->filter != XGPU_SCALE_BILINEAR && sc->filter != XGPU_SCALE_AREA) || (sc->normalize & ~1)) return 0;
+    if (sc->normalize) {
+        *why = "normalize needs a float dtype and finite mean / inv_std";
+        if (f->dtype == XGPU_OUT_U8 || f->dtype == XGPU_OUT_U16) return 0;
+        for (int k = 0; k < 3; k++) if (!std::isfinite(sc->mean[k]) || !std::isfinite(sc->inv_std[k])) return 0;
+    }
+    const int ws = width - f->crop[0] - f->crop[1], hs = height - f->crop[2] - f->crop[3];
+    *rc = XGPU_ERR_UNSUPPORTED;
+    *why = "destination size: 2..16384 per axis, between 1/64 and 8 times the source's";
+    if (sc->width < 2 || sc->width > 16384 || sc->height < 2 || sc->height > 16384) return 0;
+    if (ws > 64 * sc->width || sc->width > 8 * ws || hs > 64 * sc->height || sc->height > 8 * hs) return 0;
+    *rc = XGPU_ERR_INVALID_ARGUMENT;
+    const size_t w = sc->width, h = sc->height, es = elem_size(f->dtype);
+    const bool interleaved = f->layout == XGPU_OUT_RGB_INTERLEAVED || f->layout == XGPU_OUT_YUV444_INTERLEAVED;
+    const size_t row = interleaved ? 3 * w * es : w * es, pitch = f->row_pitch ? f->row_pitch : row;
+    *why = "row_pitch is shorter than a row";
+    if (pitch < row) return 0;
+    *rc = XGPU_OK;
+    return ((interleaved ? h : 3 * h) - 1) * pitch + row;
+}
+size_t xgpu_output_scaled_size(const xgpu_output_format *f, const xgpu_scale_params *sc, int width, int height, int bit_depth)
+{
+    int rc; const char *why;
+    return scaled_size(f, sc, width, height, bit_depth, &rc, &why);
+}
+int xgpu_output_scaled_check(const xgpu_output_format *f, const xgpu_scale_params *sc, int width, int height, int bit_depth)
+{
+    int rc; const char *why;
+    (void)scaled_size(f, sc, width, height, bit_depth, &rc, &why);
+    return rc;
+}
+int xgpu_pic_output_device_scaled(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, void *d_dst, size_t dst_size, void *stream)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    const int bd = c->sp.bit_depth_luma;
+    int src_rc; const char *why = "";
+    const size_t need = scaled_size(f, sc, c->sp.width, c->sp.height, bd, &src_rc, &why);
+    if (need == 0) { snprintf(c->err, sizeof(c->err), "pic_output_device_scaled: %s", why); return src_rc; }
+    const size_t es = (size_t)elem_size(f->dtype);
+    if (dst_size < need || ((uintptr_t)d_dst % es)) {
+        snprintf(c->err, sizeof(c->err), "pic_output_device_scaled: destination of %zu bytes at %p, the format needs %zu bytes aligned to %zu", dst_size, d_dst, need, es);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    if (dra) { ARGCHK(c, dra->luma_inv_scale_lut && dra->chroma_inv_scale_lut[0] && dra->chroma_inv_scale_lut[1]); ARGCHK(c, bd <= 10); }      // upload_dra's refusals, before anything is queued
+    { const int rc = check_device_dst(c, "pic_output_device_scaled", d_dst, need); if (rc < 0) return rc; }
+    const int *cr = f->crop;
+    const int ws = c->sp.width - cr[0] - cr[1], hs = c->sp.height - cr[2] - cr[3], wd = sc->width, hd = sc->height;
+    // the tap tables: made here, before anything is queued; uploaded and committed below (the protocol of the colour transform's tables)
+    const int key[6] = { ws, hs, wd, hd, sc->filter, f->chroma_loc };
+    const bool cached = c->sc_tab && !memcmp(key, c->sc_key, sizeof(key));
+    std::vector<uint8_t> blob;
+    ScaleTabs tb = c->sc_host;
+    if (!cached) {
+        const int rc = scale_build_tables(ws, hs, wd, hd, sc->filter, f->chroma_loc, blob, tb);
+        if (rc < 0) { snprintf(c->err, sizeof(c->err), "pic_output_device_scaled: cannot make the tap tables for %dx%d -> %dx%d", ws, hs, wd, hd); return rc; }
+    }
+    // the context's two buffers, grown on demand.  hipFree waits for the device, so no kernel of an earlier call still reads what is freed; in steady state neither runs.
+    const int mpy = (ws + 7) & ~7, mpc = ((ws >> 1) + 7) & ~7;
+    const size_t mid_need = (size_t)hd * (mpy + 2 * mpc) * sizeof(uint16_t);
+    if (c->sc_mid_cap < mid_need) {
+        if (c->sc_mid) { (void)hipFree(c->sc_mid); c->sc_mid = NULL; c->sc_mid_cap = 0; }
+        if (hipMalloc((void **)&c->sc_mid, mid_need) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "pic_output_device_scaled: cannot allocate the %zu-byte intermediate", mid_need); return XGPU_ERR_OUT_OF_MEMORY; }
+        c->sc_mid_cap = mid_need;
+    }
+    if (!cached && c->sc_tab_cap < blob.size()) {
+        if (c->sc_tab) { (void)hipFree(c->sc_tab); c->sc_tab = NULL; c->sc_tab_cap = 0; c->sc_key[0] = -1; }
+        if (hipMalloc((void **)&c->sc_tab, blob.size()) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "pic_output_device_scaled: cannot allocate the tap tables"); return XGPU_ERR_OUT_OF_MEMORY; }
+        c->sc_tab_cap = blob.size();
+    }
+    if (dra) { const int rc = upload_dra(c, dra); if (rc < 0) return rc; }
+    hipStream_t s = c->stream;
+    if (stream) {
+        for (int i = 0; i < 2; i++)
+            if (!c->odev_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->odev_ev[i], hipEventDisableTiming));
+        s = (hipStream_t)stream;
+        HIPCHK(c, hipEventRecord(c->odev_ev[0], c->stream));      // the picture's kernels, the DRA tables and every earlier output call (they all end in the context's stream) -> the caller's stream
+        HIPCHK(c, hipStreamWaitEvent(s, c->odev_ev[0], 0));
+    }
+    if (!cached) {      // behind the wait above: after every kernel that read the previous tables
+        c->sc_key[0] = -1;      // sc_tab is about to change: no key names it until the new block is queued
+        HIPCHK(c, hipMemcpyAsync(c->sc_tab, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+        memcpy(c->sc_key, key, sizeof(key));
+        c->sc_host = tb;
+    }
+    const DevPic &p = dpic(c, pic);
+    ScaledOutArgs a;
+    memset(&a, 0, sizeof(a));
+    const bool planar = f->layout == XGPU_OUT_RGB_PLANAR || f->layout == XGPU_OUT_YUV444_PLANAR;
+    a.y = p.y + (size_t)cr[2] * p.s_l + cr[0];
+    a.u = p.u + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1); a.v = p.v + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1);
+    a.sy = p.s_l; a.sc = p.s_c;
+    a.w = ws; a.h = hs; a.cw = ws >> 1; a.ch = hs >> 1;
+    a.dw = wd; a.dh = hd;
+    a.dst = (uint8_t *)d_dst;
+    a.pitch = f->row_pitch ? f->row_pitch : (size_t)wd * es * (planar ? 1 : 3);
+    a.plane = a.pitch * hd;
+    a.bgr = f->bgr;
+    double yr, crr;
+    range_terms(bd, f->full_range, &a.yo, &yr, &crr);
+    a.co = 1 << (bd - 1);
+    a.dra = dra ? c->d_dra : NULL;
+    if (is_rgb(f->layout)) {
+        (void)xgpu_output_coeffs(f, bd, a.coef, &a.shift, a.fcoef);
+        a.maxv = f->dtype == XGPU_OUT_U8 ? 255 : (1 << bd) - 1;
+    } else {
+        a.shift = bd - 8;
+        a.fcoef[0] = (float)(1.0 / yr); a.fcoef[1] = (float)(1.0 / crr);
+    }
+    ScaleTaps *taps[4] = { &a.yl, &a.yc, &a.xl, &a.xc };
+    for (int t = 0; t < 4; t++) {
+        taps[t]->first = (const int32_t *)(c->sc_tab + tb.off_first[t]); taps[t]->count = (const int32_t *)(c->sc_tab + tb.off_count[t]);
+        taps[t]->w = (const int16_t *)(c->sc_tab + tb.off_w[t]); taps[t]->stride = tb.stride[t];
+    }
+    a.mid = c->sc_mid; a.mpy = mpy; a.mpc = mpc;
+    a.smax = (1 << bd) - 1;
+    a.capy = tb.capy; a.capc = tb.capc;
+    a.normalize = sc->normalize;
+    for (int k = 0; k < 3; k++) { a.mean[k] = sc->mean[k]; a.inv_std[k] = sc->inv_std[k]; }
+    launch_output_scaled(a, f->layout, f->dtype, s);
+    HIPCHK(c, hipGetLastError());
+    if (stream) {
+        HIPCHK(c, hipEventRecord(c->odev_ev[1], s));      // the context's stream - and through it the next output call on any stream - does not touch the slot, the tables or the intermediate before the kernels are done
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->odev_ev[1], 0));
     }
     return XGPU_OK;

@@ -316,6 +316,9 @@ struct xgpu_dbatch {
     int        used;                  // kernels that read the block have been queued (xgpu_batch_recon, or a residual pass ahead)
 };
 
+// the device block of the scaled output's tap tables, as the host laid it out: per table (0 yl, 1 yc, 2 xl, 3 xc) the byte offsets of first[], count[] and w[], the
+// weights' stride, and the widest span of source samples 64 neighbouring destination columns reach (pass 2's LDS need), rounded to whole groups of 8
+struct ScaleTabs { size_t off_first[4], off_count[4], off_w[4]; int stride[4]; int capy, capc; };
 struct xgpu_ctx {
     xgpu_seq_params sp;
     int8_t          chroma_qp[2][96];  // [c][qp + 6*(bdc-8)]
@@ -345,6 +348,15 @@ struct xgpu_ctx {
     xgpu_colour_tables_t *cm_tab;     // the host's copy, made for (cm_key, cm_bd); NULL until the first call
     xgpu_colour_transform cm_key;
     int             cm_bd;
+    // xgpu_pic_output_device_scaled: the four tap tables on the device (sc_tab; made for sc_key = source size, destination size, filter, chroma_loc - all -1 until
+    // the first call) and the intermediate of the vertical pass (sc_mid, sc_mid_cap bytes, grown on demand).  Both are the context's, like d_dra and d_cm: every
+    // call that uses them is ordered behind the previous one through the context's stream (odev_ev), whichever stream it runs on.
+    uint8_t        *sc_tab;
+    size_t          sc_tab_cap;
+    int             sc_key[6];
+    ScaleTabs       sc_host;          // what sc_tab holds: offsets, strides, pass 2's spans
+    uint16_t       *sc_mid;
+    size_t          sc_mid_cap;
     hipEvent_t      odev_ev[2];       // xgpu_pic_output_device on a caller's stream: picture ready on the context stream / the caller's kernel done (created at the first call)
     xgpu_frame_params fp;
     int             have_frame;
@@ -461,6 +473,22 @@ struct CmOutArgs : RgbOutArgs {
     float    outmax;                // integer dtypes: 2^D - 1
 };
 void launch_output_cm(const CmOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
+// k_output_scaled.hip: the cropped picture resized to dw x dh and converted (xgpu_pic_output_device_scaled).  RgbOutArgs' source, destination
+// and conversion fields (w, h, cw, ch: the SOURCE size; pitch / plane: of the dw x dh destination; aligned, hc, ve, vo are not read), then the taps and the two passes'.
+struct ScaleTaps { const int32_t *first, *count; const int16_t *w; int stride; };      // one axis of one plane, on the device
+struct ScaledOutArgs : RgbOutArgs {
+    int      dw, dh;                // destination size
+    ScaleTaps yl, yc;               // vertical, luma / chroma rows: w[o * stride + k]
+    ScaleTaps xl, xc;               // horizontal, luma / chroma columns, TRANSPOSED: w[k * dw + o] (stride = dw), so that the lanes of a wave read neighbours
+    uint16_t *mid;                  // the vertical pass' output, 3 fraction bits: Y [dh][mpy], then Cb and Cr [dh][mpc]
+    int      mpy, mpc;              // its row pitches in samples, multiples of 8
+    int      smax;                  // 2^B - 1: the clip of every source sample
+    int      capy, capc;            // pass 2: samples of a Y / of a Cb or Cr row one wave stages in LDS (multiples of 8)
+    int      normalize;
+    float    mean[3], inv_std[3];   // by output position (after bgr)
+};
+void launch_output_scaled(const ScaledOutArgs &a, int layout, int dtype, hipStream_t s);
+int  scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb);      // xgpu_scale.hip
 // k_output_yuv.hip (k_output_semiplanar): NV12 / P016 - xgpu_pic_output's samples, luma rows then rows of interleaved Cb Cr
 struct SemiPlanarArgs {
     const int16_t *y, *u, *v;       // first sample of the cropped area of every plane

@@ -1,0 +1,119 @@
+// xgpu_scale.hip - the tap tables of the scaled device output (xgpu_scale_taps).  Host only, and integers only: every quantity of the
+// contract is a fraction over one common denominator, so centres, widths, weights and their sum are int64 numerators and no float or double appears anywhere.
+// tests/scale_ref.py restates the construction with fractions.Fraction; the two agree tap for tap.
+//
+// One axis of one plane: n plane samples, subsampling s (1 luma, 2 chroma), siting d = h / 2 luma samples (h = 0, 1, 2), N destination samples.
+//   r = n s / N          f = max(1, r / s) = max(1, n / N)          c(o) = ((o + 1/2) r - 1/2 - d) / s
+// Over the denominator D = 2 s N:   c(o) = C / D with C = (2 o + 1) n s - (1 + h) N,   f = F / D with F = max(D, 2 s n).
+//   BILINEAR   w(i) = max(0, 1 - |i - c| / f)                              = max(0, F - |i D - C|) / F
+//   AREA       w(i) = | [i - 1/2, i + 1/2] ^ [c - f / 2, c + f / 2] |      = max(0, min((2 i + 1) D, 2 C + F) - max((2 i - 1) D, 2 C - F)) / (2 D)
+// The common factor of a row (1 / F, 1 / (2 D)) cancels in the normalisation: a row is its integer numerators u(i) > 0 over 0 <= i < n, their sum U, and
+//   q(i) = floor(u(i) 16384 / U + 1 / 2) = (2 u(i) 16384 + U) / (2 U) in integers;   16384 - sum q goes to the largest q (the first of equals).
+#include "xgpu_internal.h"
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+static int64_t floor_div(int64_t a, int64_t b) { return a / b - ((a % b != 0) && ((a < 0) != (b < 0))); }      // b > 0
+
+int xgpu_scale_taps(int n_plane, int subsampling, int siting_half_luma, int n_dst, int filter, int32_t *first, int32_t *count, int16_t *w, int w_stride)
+{
+    const int64_t n = n_plane, s = subsampling, h = siting_half_luma, N = n_dst;
+    if (n < 1 || n > 65536 || (s != 1 && s != 2) || h < 0 || h > 2 || (filter != XGPU_SCALE_BILINEAR && filter != XGPU_SCALE_AREA) ||
+        !first || !count || (w && w_stride < 1))
+        return XGPU_ERR_INVALID_ARGUMENT;
+    if (N < 2 || N > 16384 || n * s > 64 * N || N > 8 * n * s) return XGPU_ERR_UNSUPPORTED;
+    const int64_t D = 2 * s * N, F = std::max(D, 2 * s * n);
+    std::vector<int64_t> u;
+    int widest = 0;
+    for (int64_t o = 0; o < N; o++) {
+        const int64_t C = (2 * o + 1) * n * s - (1 + h) * N;
+        // the samples that can have a positive weight: |i - c| < f (BILINEAR), |i - c| < (f + 1) / 2 (AREA) - one more on either side costs nothing
+        const int64_t reach = filter == XGPU_SCALE_BILINEAR ? F : (F + D + 1) / 2;
+        int64_t lo = std::max<int64_t>(floor_div(C - reach, D) - 1, 0), hi = std::min<int64_t>(floor_div(C + reach, D) + 1, n - 1);
+        u.clear();
+        int64_t i0 = 0, U = 0;
+        for (int64_t i = lo; i <= hi; i++) {
+            int64_t v;
+            if (filter == XGPU_SCALE_BILINEAR) {
+                const int64_t t = i * D - C;
+                v = F - (t < 0 ? -t : t);
+            } else {
+                v = std::min((2 * i + 1) * D, 2 * C + F) - std::max((2 * i - 1) * D, 2 * C - F);
+            }
+            if (v <= 0) { if (u.empty()) continue; else break; }      // the positive weights are contiguous
+            if (u.empty()) i0 = i;
+            u.push_back(v);
+            U += v;
+        }
+        if (u.empty()) {      // no sample of the plane under the window (a siting that moves the grid off the plane's end): the nearest sample alone
+            i0 = std::min<int64_t>(std::max<int64_t>(floor_div(2 * C + D, 2 * D), 0), n - 1);
+            u.push_back(1);
+            U = 1;
+        }
+        const int cnt = (int)u.size();
+        first[o] = (int32_t)i0;
+        count[o] = cnt;
+        widest = std::max(widest, cnt);
+        if (!w) continue;
+        if (cnt > w_stride) return XGPU_ERR_INVALID_ARGUMENT;
+        int16_t *q = w + (size_t)o * w_stride;
+        int64_t sum = 0, best = 0;
+        for (int k = 0; k < cnt; k++) {
+            const int64_t v = (2 * u[k] * 16384 + U) / (2 * U);
+            q[k] = (int16_t)v;
+            sum += v;
+            if (v > q[best]) best = k;
+        }
+        q[best] = (int16_t)(q[best] + (16384 - sum));
+        for (int k = cnt; k < w_stride; k++) q[k] = 0;
+    }
+    return widest;
+}
+
+// The four tables of one (source size, destination size, filter, chroma_loc) as the block the kernels read (k_output_scaled.hip): per table first[], count[] and
+// the weights - row by row for the vertical tables (0 luma rows, 1 chroma rows), transposed for the horizontal ones (2 luma columns, 3 chroma columns) -, every
+// array at a multiple of 16 bytes.  It also measures what pass 2 stages in LDS: the widest span of the intermediate that 64 neighbouring destination columns
+// reach, from an 8-sample-aligned start.  The kernel takes a workgroup's span from its first and last column, so the rows must move right monotonically: checked
+// here, for every table it is given, before anything reaches the device.
+int scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb)
+{
+    static const int vsite[3] = { 1, 0, 2 };      // ChromaSampleLocType >> 1: centred, top, bottom - in half luma samples
+    const int n[4] = { hs, hs >> 1, ws, ws >> 1 }, sub[4] = { 1, 2, 1, 2 }, site[4] = { 0, vsite[chroma_loc >> 1], 0, chroma_loc & 1 }, N[4] = { hd, hd, wd, wd };
+    blob.clear();
+    auto reserve = [&](size_t bytes) { const size_t off = (blob.size() + 15) & ~(size_t)15; blob.resize(off + bytes); return off; };
+    std::vector<int32_t> first, count;
+    std::vector<int16_t> w;
+    for (int t = 0; t < 4; t++) {
+        first.assign(N[t], 0); count.assign(N[t], 0);
+        const int widest = xgpu_scale_taps(n[t], sub[t], site[t], N[t], filter, first.data(), count.data(), NULL, 0);
+        if (widest < 0) return widest;
+        w.assign((size_t)N[t] * widest, 0);
+        const int rc = xgpu_scale_taps(n[t], sub[t], site[t], N[t], filter, first.data(), count.data(), w.data(), widest);
+        if (rc < 0) return rc;
+        for (int o = 0; o < N[t]; o++) {
+            if (first[o] < 0 || count[o] < 1 || first[o] + count[o] > n[t]) return XGPU_ERR_UNEXPECTED;
+            if (o && (first[o] < first[o - 1] || first[o] + count[o] < first[o - 1] + count[o - 1])) return XGPU_ERR_UNEXPECTED;
+        }
+        tb.off_first[t] = reserve(sizeof(int32_t) * N[t]);
+        memcpy(&blob[tb.off_first[t]], first.data(), sizeof(int32_t) * N[t]);
+        tb.off_count[t] = reserve(sizeof(int32_t) * N[t]);
+        memcpy(&blob[tb.off_count[t]], count.data(), sizeof(int32_t) * N[t]);
+        tb.off_w[t] = reserve(sizeof(int16_t) * w.size());
+        int16_t *dw = (int16_t *)&blob[tb.off_w[t]];
+        if (t < 2) {
+            memcpy(dw, w.data(), sizeof(int16_t) * w.size());
+            tb.stride[t] = widest;
+        } else {
+            for (int o = 0; o < N[t]; o++) for (int k = 0; k < widest; k++) dw[(size_t)k * N[t] + o] = w[(size_t)o * widest + k];
+            tb.stride[t] = N[t];
+            int cap = 0;
+            for (int ob = 0; ob < N[t]; ob += 64) {
+                const int ol = std::min(ob + 63, N[t] - 1);
+                cap = std::max(cap, ((first[ol] + count[ol] + 7) & ~7) - (first[ob] & ~7));
+            }
+            (t == 2 ? tb.capy : tb.capc) = cap;
+        }
+    }
+    return XGPU_OK;
+}

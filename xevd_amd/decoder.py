@@ -109,7 +109,7 @@ class XgpuDecoder:
         return C.byref(d), (keep, d)
 
     def pic_output_tensor(self, pic, layout="rgb", channels_last=False, dtype=None, matrix=1, full_range=False, chroma_loc=0, upsample="linear",
-                          crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, out_bit_depth=0, colour=None):
+                          crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, out_bit_depth=0, colour=None, size=None, filter="bilinear", mean=None, std=None):
         """The picture in device memory as a torch tensor on cuda:{device}, converted on the device (xgpu_pic_output_device) on torch's current
         stream - no host round trip.  layout "rgb": [3, H, W] (channels_last: [H, W, 3]) R'G'B' (bgr: B, G, R) with dtype torch.uint8, torch.int16 /
         torch.uint16 (values at the coding depth), torch.float16, torch.bfloat16 or torch.float32 (0..1), through `matrix` (H.273 MatrixCoefficients
@@ -124,8 +124,17 @@ class XgpuDecoder:
         arguments of abi.make_colour_transform: H.273 code points, peaks in cd/m2): the R'G'B' of the stream's colour space linearised, taken to the
         destination primaries, tone-mapped or scaled, and re-encoded with the destination transfer (8 = linear light) in the same kernel
         (xgpu_pic_output_device_cm).
-        crop: (left, right, top, bottom), even.  out: a tensor to fill instead (its strides may pad the rows: row_pitch); it is also what is returned."""
+        crop: (left, right, top, bottom), even.  out: a tensor to fill instead (its strides may pad the rows: row_pitch); it is also what is returned.
+        size=(H, W): layouts "rgb" / "yuv444" resized to H x W on the device (xgpu_pic_output_device_scaled) - the crop is the region
+        of interest, filter "bilinear" (the antialiased triangle of torch's interpolate(antialias=True)) or "area"; the chroma planes are filtered straight onto
+        the destination grid (upsample is not read).  mean / std (float dtypes; three values or one): out = (v - mean[k]) * (float32(1) / float32(std[k])), k the
+        channel's position in the output.  size=None: the unscaled call, and filter / mean / std must be left alone."""
         import torch
+        if size is not None:
+            return self._pic_output_tensor_scaled(pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour,
+                                                  size, filter, mean, std)
+        if filter != "bilinear" or mean is not None or std is not None:
+            raise ValueError("filter, mean and std belong to the scaled output: they need size=(H, W)")
         if dtype is None:
             dtype = torch.int16 if layout == "p016" else torch.uint8      # P016 has 16-bit words only
         codes = {torch.uint8: abi.OUT_U8, torch.int16: abi.OUT_U16, torch.float16: abi.OUT_F16, torch.bfloat16: abi.OUT_BF16, torch.float32: abi.OUT_F32}
@@ -198,6 +207,54 @@ class XgpuDecoder:
             cm = abi.make_colour_transform(**colour)
             self._chk(self.lib.xgpu_pic_output_device_cm(self.ctx, pic, dl, C.byref(fmt), C.byref(cm), C.c_void_p(out.data_ptr()), nbytes,
                                                          C.c_void_p(run.cuda_stream)), "xgpu_pic_output_device_cm")
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
+    def _pic_output_tensor_scaled(self, pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour, size, filter,
+                                  mean, std):
+        """pic_output_tensor with size=(H, W)"""
+        import torch
+        if layout not in ("rgb", "yuv444"):
+            raise ValueError(f"size: the scaled output has layouts 'rgb' and 'yuv444', not {layout!r}")
+        if colour is not None:
+            raise ValueError("size: the scaled output takes no colour transform")
+        if filter not in ("bilinear", "area"):
+            raise ValueError(f"filter must be 'bilinear' or 'area', not {filter!r}")
+        if int(out_bit_depth) not in (0, self.bit_depth):
+            raise ValueError(f"{layout}: out_bit_depth must be 0 or the coding depth {self.bit_depth}, not {out_bit_depth}")
+        dtype = torch.uint8 if dtype is None else dtype
+        codes = {torch.uint8: abi.OUT_U8, torch.int16: abi.OUT_U16, torch.float16: abi.OUT_F16, torch.bfloat16: abi.OUT_BF16, torch.float32: abi.OUT_F32}
+        if getattr(torch, "uint16", None) is not None:
+            codes[torch.uint16] = abi.OUT_U16
+        if dtype not in codes:
+            raise ValueError(f"unsupported output dtype {dtype}")
+        if (mean is not None or std is not None) and codes[dtype] in (abi.OUT_U8, abi.OUT_U16):
+            raise ValueError("mean / std: the normalise needs a float dtype")
+        h, w = (int(v) for v in size)
+        dev = torch.device("cuda", self.sp.device)
+        shape = (h, w, 3) if channels_last else (3, h, w)
+        lay = (abi.OUT_RGB_INTERLEAVED, abi.OUT_RGB_PLANAR) if layout == "rgb" else (abi.OUT_YUV444_INTERLEAVED, abi.OUT_YUV444_PLANAR)
+        fmt = abi.make_output_format(lay[0] if channels_last else lay[1], codes[dtype], bgr=bgr, matrix=matrix, full_range=full_range, chroma_loc=chroma_loc, crop=crop)
+        sc = abi.make_scale_params(w, h, abi.SCALE_BILINEAR if filter == "bilinear" else abi.SCALE_AREA, mean=mean, std=std)
+        if out is None:
+            if self.lib.xgpu_output_scaled_size(C.byref(fmt), C.byref(sc), self.width, self.height, self.bit_depth) == 0:
+                raise ValueError(f"invalid scaled output (layout {layout}, size {tuple(size)}, matrix {matrix}, chroma_loc {chroma_loc}, crop {crop}, mean {mean}, std {std})")
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
+            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+        st = out.stride()
+        pitch = st[0] if channels_last else st[1]          # elements between rows
+        if (channels_last and st[1:] != (3, 1)) or (not channels_last and (st[2] != 1 or st[0] != pitch * h)) or pitch < (3 * w if channels_last else w):
+            raise ValueError(f"out: strides {st} are not rows of {'W x 3' if channels_last else 'W'} elements {'' if channels_last else 'in planes of H rows '}")
+        fmt.row_pitch = pitch * dtype.itemsize
+        if self.lib.xgpu_output_scaled_size(C.byref(fmt), C.byref(sc), self.width, self.height, self.bit_depth) == 0:
+            raise ValueError(f"invalid scaled output (layout {layout}, size {tuple(size)}, matrix {matrix}, chroma_loc {chroma_loc}, crop {crop}, mean {mean}, std {std})")
+        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
+        nbytes = (sum((n - 1) * s for n, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
+        cur, run = self._run_stream(dev)
+        self._chk(self.lib.xgpu_pic_output_device_scaled(self.ctx, pic, dl, C.byref(fmt), C.byref(sc), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
+                  "xgpu_pic_output_device_scaled")
         if run is not cur:
             cur.wait_stream(run)
         return out
