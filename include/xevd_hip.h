@@ -362,6 +362,43 @@ int    xgpu_output_scaled_check(const xgpu_output_format *f, const xgpu_scale_pa
    one behind the other through the context's stream, so they never overlap on either. */
 int    xgpu_pic_output_device_scaled(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
                                      void *d_dst, size_t dst_size, void *stream);
+/* ---- regions of interest (k_output_rois.hip): n_rois rectangles of one picture, each resized to the same sc->width x sc->height, converted and normalised, as a
+   batch of images - [N, 3, H, W] or [N, H, W, 3] - from one call: two kernel launches and one upload, however many rectangles.  Image i is laid out as
+   xgpu_pic_output_device_scaled lays out its one image (the four layouts, the five dtypes, f->row_pitch) and starts rp->image_pitch * i bytes behind d_dst;
+   image_pitch 0 = tight: rows x row pitch (3 H rows planar, H interleaved); otherwise a multiple of the element size, not shorter than one image (the bytes
+   xgpu_output_scaled_size counts).  A rectangle is given in luma samples inside the picture minus f->crop; x, y, width and height are even.  It is a source of its
+   own, exactly as a crop is for the scaled output: taps end at its edge and nothing outside it reaches a result.  Rectangles may overlap and repeat.
+     XGPU_FIT_STRETCH     the rectangle fills the image: image i is, bit for bit, what xgpu_pic_output_device_scaled writes with f->crop set to rectangle i
+     XGPU_FIT_LETTERBOX   the rectangle keeps its shape: with Ws x Hs the rectangle and Wd x Hd the image, Ws Hd >= Hs Wd gives the inner size Wi = Wd,
+                          Hi = min(Hd, max(2, (2 Hs Wd + Ws) / (2 Ws))) (integer division), else Hi = Hd and Wi by the same rule with the axes exchanged; the
+                          inner part lies at ((Wd - Wi) >> 1, (Hd - Hi) >> 1) and is the scaled output of the rectangle at Wi x Hi; every other element of the
+                          image is rp->pad[k], k the channel's position in the output (after bgr, as for mean).  Float dtypes: pad[k] is a finite float32 in the
+                          domain before the normalise and goes through the same (v - mean[k]) * inv_std[k] and the F16 / BF16 rounding; integer dtypes: an
+                          integer in [0, 2^D - 1] (D = 8 for U8, else the coding depth).  pad is not read with XGPU_FIT_STRETCH.
+   xgpu_roi_inner (host only): x, y, width, height of the filtered part inside the image - what maps a detection in image i back into rectangle i.
+   Refusals, all before anything is queued; *bad_index (may be NULL) receives the index of the rectangle the refusal names, else -1:
+     XGPU_ERR_INVALID_ARGUMENT   n_rois outside 1 .. XGPU_MAX_ROIS, an odd rectangle or one that leaves the picture minus f->crop, an unknown fit, a bad pad, a bad
+                                 image_pitch, and whatever xgpu_pic_output_device_scaled refuses with this code
+     XGPU_ERR_UNSUPPORTED        sc->width or sc->height outside 2 .. 16384; a rectangle whose inner size is outside the scaled output's limits per axis
+                                 (2 <= Wi, Ws / 64 <= Wi <= 8 Ws, the height alike); a call whose intermediate - the sum over the rectangles of
+                                 Hi * (align8(Ws) + 2 * align8(Ws / 2)) * 2 bytes, align8 rounding up to a multiple of 8 - exceeds 512 MiB (bad_index: the
+                                 rectangle at which the sum passes the limit) */
+typedef struct xgpu_roi { int x, y, width, height; } xgpu_roi;
+#define XGPU_FIT_STRETCH   0
+#define XGPU_FIT_LETTERBOX 1
+#define XGPU_MAX_ROIS      1024
+typedef struct xgpu_roi_params { int fit; float pad[3]; size_t image_pitch; } xgpu_roi_params;
+int    xgpu_roi_inner(const xgpu_roi *r, const xgpu_scale_params *sc, int fit, int inner[4]);
+/* Host only, no context: 0 or the code the call refuses with / the bytes the call needs at d_dst (0: refused), for a picture of width x height at bit_depth */
+int    xgpu_output_rois_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois,
+                              int width, int height, int bit_depth, int *bad_index);
+size_t xgpu_output_rois_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois,
+                             int width, int height, int bit_depth);
+/* Non-blocking; d_dst, dst_size and stream as xgpu_pic_output_device takes them.  `rois` is host memory, read during the call.  The descriptor block and the
+   intermediate belong to the context, grow on demand (growing waits for the device) and are ordered like the scaled output's buffers; the tap tables the scaled
+   output caches are left alone. */
+int    xgpu_pic_output_device_rois(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                                   const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, void *d_dst, size_t dst_size, void *stream);
 /* ---- coding side information (k_side_info.hip): what the decoder knows about a picture besides its samples - motion vectors per 4x4 luma unit, the
    reference each one points at, intra / inter / skip / IBC, QP, coded-residual flag, block edges - read out of the SCU map the in-loop filters read
    (the reference's map_scu / map_refi / map_mv, src_base/xevd_def.h:372-438).

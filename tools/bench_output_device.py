@@ -11,7 +11,14 @@ interpolate(mode="bilinear", antialias=True) and the normalise in torch; and the
 picture read once, the destination written once).  The call is timed whole; the split between its two kernels is what
 rocprofv3 --kernel-trace --stats shows for `--legs scaled`.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled] [--out out/output_device.json]
+The rois leg (xgpu_pic_output_device_rois: k_rois_vertical + k_rois_horizontal) makes 64 images of 224x224 f32 planar, normalised, from the same picture by one
+call - (a) the 8 x 8 grid of tiles, stretched; (b) 64 seeded boxes with sides of 64..512 samples, letterboxed - and times next to it, alternating with it in the
+same run on the same stream, the route without it: 64 calls of xgpu_pic_output_device_scaled with the crop set to the rectangle (for (b) at the inner size, into
+tensors of their own; the inner rectangles of the two routes are compared).  Events bracket each whole route as the host queues it, so the time is the device's
+from the first kernel to the last, host gaps included; host_us is what the host spends queueing.  The split between the two kernels is what
+rocprofv3 --kernel-trace --stats shows for `--legs rois`.
+
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -97,6 +104,59 @@ def scaled_leg(torch, dec, pic, s, a, res, copy_gbps):
     del full
 
 
+def rois_leg(torch, dec, pic, s, a, res):
+    """one batched call against the loop of single-image calls the same pictures cost without it, alternated"""
+    import time
+    from xevd_amd import abi
+    w, h = a.width, a.height
+    size, n, pad = (224, 224), 64, 0.447
+    rng = np.random.default_rng(7)
+    boxes = []
+    for _ in range(n):
+        bw, bh = (min(int(rng.integers(32, 257)) * 2, v) for v in (w, h))
+        boxes.append((int(rng.integers(0, (w - bw) // 2 + 1)) * 2, int(rng.integers(0, (h - bh) // 2 + 1)) * 2, bw, bh))
+    kw = dict(dtype=torch.float32, mean=MEAN, std=STD)
+    res["rois"] = {}
+    for name, rois, fit in (("tiles_stretch", abi.tile_rois(w, h, (w // 8) & ~1, (h // 8) & ~1)[:n], "stretch"), ("boxes_letterbox", boxes, "letterbox")):
+        inner = [abi.roi_inner(dec.lib, r, size, abi.FIT_LETTERBOX if fit == "letterbox" else abi.FIT_STRETCH) for r in rois]
+        out = dec.pic_output_tensor(pic, size=size, rois=rois, fit=fit, pad=pad, **kw)
+        singles = [torch.empty((3, hi, wi), dtype=torch.float32, device="cuda:0") for _, _, wi, hi in inner]
+        crops = [(x, w - x - rw, y, h - y - rh) for x, y, rw, rh in rois]
+
+        def batched():
+            dec.pic_output_tensor(pic, size=size, rois=rois, fit=fit, pad=pad, out=out, **kw)
+
+        def loop():
+            for t, c in zip(singles, crops):
+                dec.pic_output_tensor(pic, size=tuple(t.shape[1:]), crop=c, out=t, **kw)
+
+        for _ in range(5):
+            batched(); loop()
+        torch.cuda.synchronize()
+        same = all(torch.equal(out[i][:, y:y + hi, x:x + wi], singles[i]) for i, (x, y, wi, hi) in enumerate(inner))
+        ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)] for k in ("batched", "loop")}
+        host = {"batched": [], "loop": []}
+        for i in range(a.iters):
+            for k, fn in (("batched", batched), ("loop", loop)):
+                e0, e1 = ev[k][i]
+                torch.cuda.synchronize()      # each route starts on an idle device: its events see its own gaps only
+                t0 = time.perf_counter()
+                e0.record(s)
+                fn()
+                e1.record(s)
+                host[k].append((time.perf_counter() - t0) * 1e6)
+        torch.cuda.synchronize()
+        r = {"n": len(rois), "size": list(size), "fit": fit, "inner_equal": bool(same)}
+        for k in ("batched", "loop"):
+            us = np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev[k]])
+            r[k] = {"us": round(float(np.median(us)), 2), "p10_us": round(float(np.percentile(us, 10)), 2), "p90_us": round(float(np.percentile(us, 90)), 2),
+                    "host_us": round(float(np.median(host[k])), 2)}
+        r["speedup"] = round(r["loop"]["us"] / r["batched"]["us"], 2)
+        print(f"rois {name:16s} {len(rois)} x {size[1]}x{size[0]} f32: one call {r['batched']['us']:9.1f} us (host {r['batched']['host_us']:8.1f})   "
+              f"loop of single calls {r['loop']['us']:9.1f} us (host {r['loop']['host_us']:8.1f})   {r['speedup']:.2f}x   inner parts equal: {same}")
+        res["rois"][name] = r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=7680)
@@ -104,7 +164,8 @@ def main():
     ap.add_argument("--bit-depth", type=int, default=10)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--legs", choices=("all", "full", "scaled"), default="all", help="full: the full-size forms and the side information; scaled: the scaled leg alone")
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois"), default="all",
+                    help="full: the full-size forms and the side information; scaled: the scaled leg alone; rois: the batched regions of interest alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -140,6 +201,8 @@ def main():
         torch.cuda.set_stream(s)
         if a.legs in ("all", "scaled"):
             scaled_leg(torch, dec, pic, s, a, res, copy_gbps)
+        if a.legs in ("all", "rois"):
+            rois_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "full"):
             for name, kw, wbytes in forms:
                 out = dec.pic_output_tensor(pic, **kw)

@@ -25,8 +25,12 @@ def main():
                     "'POC h_scu w_scu', then nine planes of h_scu x w_scu little-endian int16 (list 0 / 1 vectors, POC distances, mode, QP, flags: INTEGRATION.md 8c)")
     ap.add_argument("--size", default=None, metavar="WxH", help="write interleaved 8-bit RGB frames resized to W x H on the device instead (antialiased bilinear, "
                     "the matrix / range / chroma siting of the stream's VUI: INTEGRATION.md 8d); with --to: not supported")
+    ap.add_argument("--tiles", default=None, metavar="WxH", help="with --size: every picture as its grid of W x H tiles (the last column / row moved back inside the "
+                    "picture), each resized to --size by one call per picture (INTEGRATION.md 8e); the frames written are the tiles, row by row")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
+    if args.tiles is not None and args.size is None:
+        ap.error("--tiles: needs --size")
     data = open(args.input, "rb").read()
     t0 = time.perf_counter()
     side = {} if args.side_info else None
@@ -39,7 +43,15 @@ def main():
             wd, hd = (int(v) for v in args.size.lower().split("x"))
         except ValueError:
             ap.error(f"--size: expected WxH, not {args.size!r}")
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side)
+        rois = None
+        if args.tiles is not None:
+            from xevd_amd import abi
+            try:
+                tw, th = (int(v) for v in args.tiles.lower().split("x"))
+            except ValueError:
+                ap.error(f"--tiles: expected WxH, not {args.tiles!r}")
+            rois = lambda p: abi.tile_rois(p["width"], p["height"], tw, th)      # noqa: E731
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois)
     elif args.to is not None:
         import torch
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side)

@@ -113,6 +113,57 @@ def scale_taps(lib, n_plane, subsampling, siting_half_luma, n_dst, filter=SCALE_
     return rc if rc < 0 else (first, count, w)
 
 
+FIT_STRETCH, FIT_LETTERBOX = 0, 1
+MAX_ROIS = 1024
+
+
+class Roi(C.Structure):
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int)]
+
+
+class RoiParams(C.Structure):
+    _fields_ = [("fit", C.c_int), ("pad", C.c_float * 3), ("image_pitch", C.c_size_t)]
+
+
+def make_rois(rois):
+    """[(x, y, width, height), ...] in luma samples -> an array of xgpu_roi"""
+    a = (Roi * max(len(rois), 1))()
+    for i, r in enumerate(rois):
+        a[i].x, a[i].y, a[i].width, a[i].height = (int(v) for v in r)
+    return a
+
+
+def make_roi_params(fit=FIT_STRETCH, pad=0.0, image_pitch=0):
+    """xgpu_roi_params (include/xevd_hip.h): fit FIT_STRETCH / FIT_LETTERBOX, the letterbox's pad value - one value or three, by the channel's position in the
+    output, before the normalise - and the bytes between two images (0: tight)"""
+    p = RoiParams()
+    p.fit, p.image_pitch = int(fit), int(image_pitch)
+    v = np.broadcast_to(np.asarray(pad, np.float32), (3,))
+    for k in range(3):
+        p.pad[k] = float(v[k])
+    return p
+
+
+def roi_inner(lib, roi, size, fit=FIT_LETTERBOX):
+    """xgpu_roi_inner: (x, y, width, height) of the filtered part of rectangle roi = (x, y, width, height) inside an image of size = (H, W), or the negative code"""
+    r = make_rois([roi])
+    sc = make_scale_params(size[1], size[0])
+    inner = (C.c_int * 4)()
+    rc = lib.xgpu_roi_inner(r, C.byref(sc), int(fit), inner)
+    return rc if rc < 0 else tuple(inner)
+
+
+def tile_rois(width, height, tile_w, tile_h):
+    """the grid of tile_w x tile_h tiles (even) that covers a width x height picture, row by row: where the size is no multiple of the tile the last column / row
+    is moved back inside the picture (it overlaps its neighbour), so every tile has the same size and the tiles share one set of tap tables"""
+    tile_w, tile_h = min(int(tile_w), int(width)), min(int(tile_h), int(height))
+    if tile_w < 2 or tile_h < 2 or (tile_w | tile_h | int(width) | int(height)) & 1:
+        raise ValueError(f"tile_rois: tile {tile_w}x{tile_h} in {width}x{height}: sizes must be even and at least 2")
+    xs = [min(x, width - tile_w) for x in range(0, width, tile_w)]
+    ys = [min(y, height - tile_h) for y in range(0, height, tile_h)]
+    return [(x, y, tile_w, tile_h) for y in ys for x in xs]
+
+
 CM_CURVE_U0, CM_CURVE_SIZE = 0x1F800000, 64 * 32 + 3
 
 
@@ -315,6 +366,12 @@ _EXPORTS = {
     "xgpu_output_scaled_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),
     "xgpu_output_scaled_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),
     "xgpu_pic_output_device_scaled": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_roi_inner": (C.c_int, [C.POINTER(Roi), C.POINTER(ScaleParams), C.c_int, C.POINTER(C.c_int)]),
+    "xgpu_output_rois_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(Roi), C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(C.c_int)]),
+    "xgpu_output_rois_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(Roi), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "xgpu_pic_output_device_rois": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(Roi),
+                                              C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_side_info_size": (C.c_size_t, [C.POINTER(SideFormat), C.c_int, C.c_int]),
     "xgpu_frame_side_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SideFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),

@@ -22,6 +22,9 @@
 // float32 before the F16 / BF16 rounding, which is what those instances do last) and is stored element by element: the lanes of a wave write neighbouring elements
 // of a row, and the destination is the small side of this kernel.  Any element-aligned destination works; there is no vector / element split to get wrong.
 //
+// The lanes' work - the vertical pass of 8 columns, the staging, the column filter, the conversion with its normalise, the stores - is in output_common.h
+// (scale_vertical_lane, stage_span, filter_column, scaled_pixel, store_pixel): k_output_rois.hip runs the same functions on a batch of rectangles.
+//
 // Float arithmetic in this file is rounded operation by operation (no contraction into FMA): the normalise is (v - mean) * inv_std in two roundings by contract,
 // and the matrix of the float dtypes is section 8a's formula as tests/colour_ref.py evaluates it.
 #pragma clang fp contract(off)
@@ -35,60 +38,8 @@ __global__ __launch_bounds__(256) void k_scale_vertical(const ScaledOutArgs a)
     const int o = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y);      // one destination row per wave
     if (x0 >= pw || o >= a.dh) return;
     const ScaleTaps &t = plane ? a.yc : a.yl;
-    const int16_t *src = plane == 0 ? a.y : plane == 1 ? a.u : a.v;
-    const int st = plane ? a.sc : a.sy;
-    const int first = t.first[o], cnt = t.count[o];
-    const int16_t *q = t.w + (size_t)o * t.stride;
-    int acc[8];
-    #pragma unroll
-    for (int m = 0; m < 8; m++) acc[m] = 0;
-    for (int k = 0; k < cnt; k++) {
-        const int row = first + k, qk = q[k];
-        const S16x8u s = *(const S16x8u *)(src + (size_t)row * st + x0);
-        int v[8];
-        #pragma unroll
-        for (int m = 0; m < 8; m++) v[m] = s.v[m];
-        if (a.dra) {
-            if (plane == 0) {
-                #pragma unroll
-                for (int m = 0; m < 8; m++) v[m] = dra1(a.dra, 0, v[m], 0);
-            } else {      // the factor of chroma sample (row, x) comes from the unmapped luma sample (2 row, 2 x)
-                const int16_t *l = a.y + (size_t)(2 * row) * a.sy + 2 * x0;
-                const S16x8u l0 = *(const S16x8u *)l, l1 = *(const S16x8u *)(l + 8);
-                #pragma unroll
-                for (int m = 0; m < 8; m++) v[m] = dra1(a.dra, plane, v[m], m < 4 ? l0.v[2 * m] : l1.v[2 * m - 8]);
-            }
-        }
-        #pragma unroll
-        for (int m = 0; m < 8; m++) acc[m] += qk * min(max(v[m], 0), a.smax);
-    }
     uint16_t *d = a.mid + (plane == 0 ? (size_t)0 : (size_t)a.dh * a.mpy + (size_t)(plane - 1) * a.dh * a.mpc) + (size_t)o * (plane ? a.mpc : a.mpy) + x0;
-    uint32_t w[4];
-    #pragma unroll
-    for (int m = 0; m < 4; m++) w[m] = (uint32_t)((acc[2 * m] + (1 << 10)) >> 11) | ((uint32_t)((acc[2 * m + 1] + (1 << 10)) >> 11) << 16);
-    *(uint4 *)d = make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// the span [s0, s1) of one row of the intermediate (s0 a multiple of 8) into the wave's LDS, 8 samples per lane and step
-__device__ __forceinline__ void stage_span(uint16_t *lds, const uint16_t *row, int s0, int s1)
-{
-    for (int i = threadIdx.x * 8; i < s1 - s0; i += 512) *(uint4 *)(lds + i) = *(const uint4 *)(row + s0 + i);
-}
-// destination column o of the staged row: v = (sum qx * t + 2^16) >> 17
-__device__ __forceinline__ int filter_column(const uint16_t *lds, const ScaleTaps &t, int o, int s0)
-{
-    const uint16_t *l = lds + (t.first[o] - s0);
-    const int16_t *q = t.w + o;
-    const int n = t.count[o];
-    int acc = 0;
-    for (int k = 0; k < n; k++) acc += (int)q[(size_t)k * t.stride] * (int)l[k];
-    return (acc + (1 << 16)) >> 17;
-}
-template <int SZ> __device__ __forceinline__ void store_elem(uint8_t *p, uint32_t e)
-{
-    if (SZ == 1) *p = (uint8_t)e;
-    else if (SZ == 2) *(uint16_t *)p = (uint16_t)e;
-    else *(uint32_t *)p = e;
+    scale_vertical_lane(a, plane, plane == 0 ? a.y : plane == 1 ? a.u : a.v, a.y, t.first[o], t.count[o], t.w + (size_t)o * t.stride, x0, d);
 }
 
 template <bool PLANAR, int DT, template <int> class CONV>
@@ -109,29 +60,9 @@ __global__ __launch_bounds__(256) void k_scale_horizontal(const ScaledOutArgs a)
     const int y = filter_column(ly, a.xl, ox, y0), cb = filter_column(lb, a.xc, ox, c0), cr = filter_column(lr, a.xc, ox, c0);
 
     uint32_t e[3];
-    if (OutT<DT>::is_float) {
-        CONV<XGPU_OUT_F32>::apply(a, y, cb, cr, e[0], e[1], e[2]);      // the clipped float32
-        if (a.bgr) { const uint32_t t = e[0]; e[0] = e[2]; e[2] = t; }
-        #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float v = __uint_as_float(e[k]);
-            if (a.normalize) v = __fmul_rn(__fsub_rn(v, a.mean[k]), a.inv_std[k]);
-            e[k] = fbits<DT>(v);
-        }
-    } else {
-        CONV<DT>::apply(a, y, cb, cr, e[0], e[1], e[2]);
-        if (a.bgr) { const uint32_t t = e[0]; e[0] = e[2]; e[2] = t; }
-    }
+    scaled_pixel<DT, CONV>(a, y, cb, cr, e);
     if (oy >= a.dh || ob + (int)threadIdx.x >= a.dw) return;
-    if (PLANAR) {
-        uint8_t *d = a.dst + (size_t)oy * a.pitch + (size_t)ox * SZ;
-        #pragma unroll
-        for (int k = 0; k < 3; k++) store_elem<SZ>(d + k * a.plane, e[k]);
-    } else {
-        uint8_t *d = a.dst + (size_t)oy * a.pitch + (size_t)ox * 3 * SZ;
-        #pragma unroll
-        for (int k = 0; k < 3; k++) store_elem<SZ>(d + k * SZ, e[k]);
-    }
+    store_pixel<PLANAR, SZ>(a.dst + (size_t)oy * a.pitch, a.plane, ox, e);
 }
 
 template <bool PLANAR, template <int> class CONV>

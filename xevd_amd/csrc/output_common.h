@@ -234,3 +234,96 @@ static void launch_three_channels(const RgbOutArgs &a, bool planar, int dtype, i
     if (planar) launch_three_layout<K, true>(a, dtype, upsample, grid, s);
     else        launch_three_layout<K, false>(a, dtype, upsample, grid, s);
 }
+
+// The two passes of the scaled outputs (k_output_scaled.hip: one picture; k_output_rois.hip: a batch of rectangles) as the lanes of either kernel run them.  The
+// files that use them switch float contraction off before they include this header: the normalise and the float matrix are rounded operation by operation.
+// Vertical pass, one lane: 8 neighbouring columns from x0 of one destination row of one plane - `cnt` source rows from `first` with the weights q.  src / luma: the
+// first sample of the source rectangle in the plane / in the luma plane (the DRA factor of chroma sample (row, x) comes from the unmapped luma sample (2 row, 2 x));
+// d: where the 8 results go, t = (sum qy * clip(dra(sample)) + 2^10) >> 11
+__device__ __forceinline__ void scale_vertical_lane(const ScaledOutArgs &a, int plane, const int16_t *src, const int16_t *luma, int first, int cnt, const int16_t *q,
+                                                    int x0, uint16_t *d)
+{
+    const int st = plane ? a.sc : a.sy;
+    int acc[8];
+    #pragma unroll
+    for (int m = 0; m < 8; m++) acc[m] = 0;
+    for (int k = 0; k < cnt; k++) {
+        const int row = first + k, qk = q[k];
+        const S16x8u s = *(const S16x8u *)(src + (size_t)row * st + x0);
+        int v[8];
+        #pragma unroll
+        for (int m = 0; m < 8; m++) v[m] = s.v[m];
+        if (a.dra) {
+            if (plane == 0) {
+                #pragma unroll
+                for (int m = 0; m < 8; m++) v[m] = dra1(a.dra, 0, v[m], 0);
+            } else {
+                const int16_t *l = luma + (size_t)(2 * row) * a.sy + 2 * x0;
+                const S16x8u l0 = *(const S16x8u *)l, l1 = *(const S16x8u *)(l + 8);
+                #pragma unroll
+                for (int m = 0; m < 8; m++) v[m] = dra1(a.dra, plane, v[m], m < 4 ? l0.v[2 * m] : l1.v[2 * m - 8]);
+            }
+        }
+        #pragma unroll
+        for (int m = 0; m < 8; m++) acc[m] += qk * min(max(v[m], 0), a.smax);
+    }
+    uint32_t w[4];
+    #pragma unroll
+    for (int m = 0; m < 4; m++) w[m] = (uint32_t)((acc[2 * m] + (1 << 10)) >> 11) | ((uint32_t)((acc[2 * m + 1] + (1 << 10)) >> 11) << 16);
+    *(uint4 *)d = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// the span [s0, s1) of one row of the intermediate (s0 a multiple of 8) into the wave's LDS, 8 samples per lane and step
+__device__ __forceinline__ void stage_span(uint16_t *lds, const uint16_t *row, int s0, int s1)
+{
+    for (int i = threadIdx.x * 8; i < s1 - s0; i += 512) *(uint4 *)(lds + i) = *(const uint4 *)(row + s0 + i);
+}
+// destination column o of the staged row: v = (sum qx * t + 2^16) >> 17
+__device__ __forceinline__ int filter_column(const uint16_t *lds, const ScaleTaps &t, int o, int s0)
+{
+    const uint16_t *l = lds + (t.first[o] - s0);
+    const int16_t *q = t.w + o;
+    const int n = t.count[o];
+    int acc = 0;
+    for (int k = 0; k < n; k++) acc += (int)q[(size_t)k * t.stride] * (int)l[k];
+    return (acc + (1 << 16)) >> 17;
+}
+template <int SZ> __device__ __forceinline__ void store_elem(uint8_t *p, uint32_t e)
+{
+    if (SZ == 1) *p = (uint8_t)e;
+    else if (SZ == 2) *(uint16_t *)p = (uint16_t)e;
+    else *(uint32_t *)p = e;
+}
+// float32 v at output position k -> the bits of the element: the normalise in two roundings, then the dtype's rounding
+template <int DT> __device__ __forceinline__ uint32_t scaled_float_elem(const ScaledOutArgs &a, int k, float v)
+{
+    if (a.normalize) v = __fmul_rn(__fsub_rn(v, a.mean[k]), a.inv_std[k]);
+    return fbits<DT>(v);
+}
+// one filtered pixel (Y, Cb, Cr at the coding depth) -> the bits of its three elements in output order: CONV (for the float dtypes its F32 instance, so that the
+// normalise sees the clipped float32), bgr, the normalise, the dtype's rounding
+template <int DT, template <int> class CONV> __device__ __forceinline__ void scaled_pixel(const ScaledOutArgs &a, int y, int cb, int cr, uint32_t (&e)[3])
+{
+    if (OutT<DT>::is_float) {
+        CONV<XGPU_OUT_F32>::apply(a, y, cb, cr, e[0], e[1], e[2]);      // the clipped float32
+        if (a.bgr) { const uint32_t t = e[0]; e[0] = e[2]; e[2] = t; }
+        #pragma unroll
+        for (int k = 0; k < 3; k++) e[k] = scaled_float_elem<DT>(a, k, __uint_as_float(e[k]));
+    } else {
+        CONV<DT>::apply(a, y, cb, cr, e[0], e[1], e[2]);
+        if (a.bgr) { const uint32_t t = e[0]; e[0] = e[2]; e[2] = t; }
+    }
+}
+// the three elements of pixel ox of the destination row at `row`: three planes `plane` bytes apart, or side by side
+template <bool PLANAR, int SZ> __device__ __forceinline__ void store_pixel(uint8_t *row, size_t plane, int ox, const uint32_t (&e)[3])
+{
+    if (PLANAR) {
+        uint8_t *d = row + (size_t)ox * SZ;
+        #pragma unroll
+        for (int k = 0; k < 3; k++) store_elem<SZ>(d + k * plane, e[k]);
+    } else {
+        uint8_t *d = row + (size_t)ox * 3 * SZ;
+        #pragma unroll
+        for (int k = 0; k < 3; k++) store_elem<SZ>(d + k * SZ, e[k]);
+    }
+}

@@ -129,6 +129,7 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
     c->d_md5 = NULL; c->md5_ready = 0;
     c->odev_ev[0] = c->odev_ev[1] = 0;
     c->sc_tab = NULL; c->sc_tab_cap = 0; c->sc_mid = NULL; c->sc_mid_cap = 0;
+    c->roi_blk = NULL; c->roi_blk_cap = 0;
     for (int i = 0; i < 6; i++) c->sc_key[i] = -1;
     c->out_next = 0;
     memset(c->t_ms, 0, sizeof(c->t_ms)); memset(c->t_n, 0, sizeof(c->t_n));
@@ -223,6 +224,7 @@ void xgpu_close(xgpu_ctx *c)
     delete c->cm_tab;
     if (c->sc_tab) (void)hipFree(c->sc_tab);
     if (c->sc_mid) (void)hipFree(c->sc_mid);
+    if (c->roi_blk) (void)hipFree(c->roi_blk);
     if (c->d_ctb_flag) (void)hipFree(c->d_ctb_flag);
     for (auto &e : c->ev_pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : c->ev_pool) (void)hipEventDestroy(e);
@@ -707,31 +709,38 @@ static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const x
 
 // ------------------------------------------------------------------------------------------------ scaled output into device memory
 // format and scale parameters for a picture of width x height at depth bd: the bytes the destination needs, or 0 with *rc = the code and `why`
-static size_t scaled_size(const xgpu_output_format *f, const xgpu_scale_params *sc, int width, int height, int bd, int *rc, const char **why)
+// the part that does not look at the ratio of source and destination: what the batched output (section 8e) shares
+static bool scaled_params_ok(const xgpu_output_format *f, const xgpu_scale_params *sc, int width, int height, int bd, int *rc, const char **why)
 {
     *rc = XGPU_ERR_INVALID_ARGUMENT;
     *why = "format or scale parameters are NULL";
-    if (!f || !sc) return 0;
+    if (!f || !sc) return false;
     *why = "picture size or bit depth out of range";
-    if (width <= 0 || height <= 0 || ((width | height) & 1) || bd < 8 || bd > 12) return 0;
+    if (width <= 0 || height <= 0 || ((width | height) & 1) || bd < 8 || bd > 12) return false;
     *why = "scaled output: layout must be XGPU_OUT_RGB_PLANAR / _INTERLEAVED or XGPU_OUT_YUV444_PLANAR / _INTERLEAVED";
-    if (!is_rgb(f->layout) && !is_yuv444(f->layout)) return 0;
+    if (!is_rgb(f->layout) && !is_yuv444(f->layout)) return false;
     const int frc = check_format(f, bd, why);
-    if (frc < 0) { *rc = frc; return 0; }
+    if (frc < 0) { *rc = frc; return false; }
     *why = "crop leaves no picture";
-    if (f->crop[0] + f->crop[1] >= width || f->crop[2] + f->crop[3] >= height) return 0;
+    if (f->crop[0] + f->crop[1] >= width || f->crop[2] + f->crop[3] >= height) return false;
     *why = "filter must be XGPU_SCALE_BILINEAR or XGPU_SCALE_AREA, normalize 0 or 1";
-    if ((sc->filter != XGPU_SCALE_BILINEAR && sc->filter != XGPU_SCALE_AREA) || (sc->normalize & ~1)) return 0;
+    if ((sc->filter != XGPU_SCALE_BILINEAR && sc->filter != XGPU_SCALE_AREA) || (sc->normalize & ~1)) return false;
     if (sc->normalize) {
         *why = "normalize needs a float dtype and finite mean / inv_std";
-        if (f->dtype == XGPU_OUT_U8 || f->dtype == XGPU_OUT_U16) return 0;
-        for (int k = 0; k < 3; k++) if (!std::isfinite(sc->mean[k]) || !std::isfinite(sc->inv_std[k])) return 0;
+        if (f->dtype == XGPU_OUT_U8 || f->dtype == XGPU_OUT_U16) return false;
+        for (int k = 0; k < 3; k++) if (!std::isfinite(sc->mean[k]) || !std::isfinite(sc->inv_std[k])) return false;
     }
-    const int ws = width - f->crop[0] - f->crop[1], hs = height - f->crop[2] - f->crop[3];
     *rc = XGPU_ERR_UNSUPPORTED;
     *why = "destination size: 2..16384 per axis, between 1/64 and 8 times the source's";
-    if (sc->width < 2 || sc->width > 16384 || sc->height < 2 || sc->height > 16384) return 0;
-    if (ws > 64 * sc->width || sc->width > 8 * ws || hs > 64 * sc->height || sc->height > 8 * hs) return 0;
+    if (sc->width < 2 || sc->width > 16384 || sc->height < 2 || sc->height > 16384) return false;
+    *rc = XGPU_OK;
+    return true;
+}
+// one axis: n source samples to N destination samples is inside the limits
+static bool scale_ratio_ok(int n, int N) { return N >= 2 && n <= 64 * N && N <= 8 * n; }
+// the bytes of one sc->width x sc->height image (the last row not padded), or 0
+static size_t scaled_image_bytes(const xgpu_output_format *f, const xgpu_scale_params *sc, int *rc, const char **why)
+{
     *rc = XGPU_ERR_INVALID_ARGUMENT;
     const size_t w = sc->width, h = sc->height, es = elem_size(f->dtype);
     const bool interleaved = f->layout == XGPU_OUT_RGB_INTERLEAVED || f->layout == XGPU_OUT_YUV444_INTERLEAVED;
@@ -740,6 +749,15 @@ static size_t scaled_size(const xgpu_output_format *f, const xgpu_scale_params *
     if (pitch < row) return 0;
     *rc = XGPU_OK;
     return ((interleaved ? h : 3 * h) - 1) * pitch + row;
+}
+static size_t scaled_size(const xgpu_output_format *f, const xgpu_scale_params *sc, int width, int height, int bd, int *rc, const char **why)
+{
+    if (!scaled_params_ok(f, sc, width, height, bd, rc, why)) return 0;
+    const int ws = width - f->crop[0] - f->crop[1], hs = height - f->crop[2] - f->crop[3];
+    *rc = XGPU_ERR_UNSUPPORTED;
+    *why = "destination size: 2..16384 per axis, between 1/64 and 8 times the source's";
+    if (!scale_ratio_ok(ws, sc->width) || !scale_ratio_ok(hs, sc->height)) return 0;
+    return scaled_image_bytes(f, sc, rc, why);
 }
 size_t xgpu_output_scaled_size(const xgpu_output_format *f, const xgpu_scale_params *sc, int width, int height, int bit_depth)
 {
@@ -751,6 +769,38 @@ int xgpu_output_scaled_check(const xgpu_output_format *f, const xgpu_scale_param
     int rc; const char *why;
     (void)scaled_size(f, sc, width, height, bit_depth, &rc, &why);
     return rc;
+}
+// what the scaled outputs (one image, section 8d; a batch of rectangles, section 8e) hand their kernels alike: the picture minus f->crop, the destination of one
+// sc->width x sc->height image at d_dst, the conversion, the clip and the normalise
+static void scaled_common_args(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, void *d_dst, ScaledOutArgs &a)
+{
+    const DevPic &p = dpic(c, pic);
+    const int *cr = f->crop;
+    const int bd = c->sp.bit_depth_luma;
+    const size_t es = (size_t)elem_size(f->dtype);
+    const bool planar = f->layout == XGPU_OUT_RGB_PLANAR || f->layout == XGPU_OUT_YUV444_PLANAR;
+    a.y = p.y + (size_t)cr[2] * p.s_l + cr[0];
+    a.u = p.u + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1); a.v = p.v + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1);
+    a.sy = p.s_l; a.sc = p.s_c;
+    a.dw = sc->width; a.dh = sc->height;
+    a.dst = (uint8_t *)d_dst;
+    a.pitch = f->row_pitch ? f->row_pitch : (size_t)sc->width * es * (planar ? 1 : 3);
+    a.plane = a.pitch * sc->height;
+    a.bgr = f->bgr;
+    double yr, crr;
+    range_terms(bd, f->full_range, &a.yo, &yr, &crr);
+    a.co = 1 << (bd - 1);
+    a.dra = dra ? c->d_dra : NULL;
+    if (is_rgb(f->layout)) {
+        (void)xgpu_output_coeffs(f, bd, a.coef, &a.shift, a.fcoef);
+        a.maxv = f->dtype == XGPU_OUT_U8 ? 255 : (1 << bd) - 1;
+    } else {
+        a.shift = bd - 8;
+        a.fcoef[0] = (float)(1.0 / yr); a.fcoef[1] = (float)(1.0 / crr);
+    }
+    a.smax = (1 << bd) - 1;
+    a.normalize = sc->normalize;
+    for (int k = 0; k < 3; k++) { a.mean[k] = sc->mean[k]; a.inv_std[k] = sc->inv_std[k]; }
 }
 int xgpu_pic_output_device_scaled(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, void *d_dst, size_t dst_size, void *stream)
 {
@@ -805,44 +855,207 @@ int xgpu_pic_output_device_scaled(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra
         memcpy(c->sc_key, key, sizeof(key));
         c->sc_host = tb;
     }
-    const DevPic &p = dpic(c, pic);
     ScaledOutArgs a;
     memset(&a, 0, sizeof(a));
-    const bool planar = f->layout == XGPU_OUT_RGB_PLANAR || f->layout == XGPU_OUT_YUV444_PLANAR;
-    a.y = p.y + (size_t)cr[2] * p.s_l + cr[0];
-    a.u = p.u + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1); a.v = p.v + (size_t)(cr[2] >> 1) * p.s_c + (cr[0] >> 1);
-    a.sy = p.s_l; a.sc = p.s_c;
+    scaled_common_args(c, pic, dra, f, sc, d_dst, a);
     a.w = ws; a.h = hs; a.cw = ws >> 1; a.ch = hs >> 1;
-    a.dw = wd; a.dh = hd;
-    a.dst = (uint8_t *)d_dst;
-    a.pitch = f->row_pitch ? f->row_pitch : (size_t)wd * es * (planar ? 1 : 3);
-    a.plane = a.pitch * hd;
-    a.bgr = f->bgr;
-    double yr, crr;
-    range_terms(bd, f->full_range, &a.yo, &yr, &crr);
-    a.co = 1 << (bd - 1);
-    a.dra = dra ? c->d_dra : NULL;
-    if (is_rgb(f->layout)) {
-        (void)xgpu_output_coeffs(f, bd, a.coef, &a.shift, a.fcoef);
-        a.maxv = f->dtype == XGPU_OUT_U8 ? 255 : (1 << bd) - 1;
-    } else {
-        a.shift = bd - 8;
-        a.fcoef[0] = (float)(1.0 / yr); a.fcoef[1] = (float)(1.0 / crr);
-    }
     ScaleTaps *taps[4] = { &a.yl, &a.yc, &a.xl, &a.xc };
     for (int t = 0; t < 4; t++) {
         taps[t]->first = (const int32_t *)(c->sc_tab + tb.off_first[t]); taps[t]->count = (const int32_t *)(c->sc_tab + tb.off_count[t]);
         taps[t]->w = (const int16_t *)(c->sc_tab + tb.off_w[t]); taps[t]->stride = tb.stride[t];
     }
     a.mid = c->sc_mid; a.mpy = mpy; a.mpc = mpc;
-    a.smax = (1 << bd) - 1;
     a.capy = tb.capy; a.capc = tb.capc;
-    a.normalize = sc->normalize;
-    for (int k = 0; k < 3; k++) { a.mean[k] = sc->mean[k]; a.inv_std[k] = sc->inv_std[k]; }
     launch_output_scaled(a, f->layout, f->dtype, s);
     HIPCHK(c, hipGetLastError());
     if (stream) {
         HIPCHK(c, hipEventRecord(c->odev_ev[1], s));      // the context's stream - and through it the next output call on any stream - does not touch the slot, the tables or the intermediate before the kernels are done
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->odev_ev[1], 0));
+    }
+    return XGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ regions of interest: a batch of scaled images
+static void roi_inner(int ws, int hs, int wd, int hd, int fit, int inner[4])
+{
+    int wi = wd, hi = hd;
+    if (fit == XGPU_FIT_LETTERBOX) {
+        if ((int64_t)ws * hd >= (int64_t)hs * wd) hi = (int)std::min<int64_t>(hd, std::max<int64_t>(2, (2 * (int64_t)hs * wd + ws) / (2 * (int64_t)ws)));
+        else                                      wi = (int)std::min<int64_t>(wd, std::max<int64_t>(2, (2 * (int64_t)ws * hd + hs) / (2 * (int64_t)hs)));
+    }
+    inner[0] = (wd - wi) >> 1; inner[1] = (hd - hi) >> 1; inner[2] = wi; inner[3] = hi;
+}
+int xgpu_roi_inner(const xgpu_roi *r, const xgpu_scale_params *sc, int fit, int inner[4])
+{
+    if (!r || !sc || !inner || r->width < 1 || r->height < 1 || sc->width < 1 || sc->height < 1 || (fit != XGPU_FIT_STRETCH && fit != XGPU_FIT_LETTERBOX))
+        return XGPU_ERR_INVALID_ARGUMENT;
+    roi_inner(r->width, r->height, sc->width, sc->height, fit, inner);
+    return XGPU_OK;
+}
+// The whole of a call's argument checks, without a device: the bytes the destination needs, or 0 with *rc = the code, `why` (a buffer of 160 bytes) and *bad =
+// the rectangle it names (-1: none).  image_pitch / mid_bytes (may be NULL): the bytes between two images, and the intermediate of the call - the sum over the
+// rectangles of Hi * (align8(Ws) + 2 * align8(Ws / 2)) * 2.
+static const size_t ROIS_MID_LIMIT = (size_t)512 << 20;
+static size_t rois_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n, int width, int height, int bd,
+                        int *rc, char *why, int *bad, size_t *image_pitch, size_t *mid_bytes)
+{
+    const char *w0 = "";
+    *bad = -1;
+    if (!scaled_params_ok(f, sc, width, height, bd, rc, &w0)) { snprintf(why, 160, "%s", w0); return 0; }
+    const size_t image = scaled_image_bytes(f, sc, rc, &w0);
+    if (image == 0) { snprintf(why, 160, "%s", w0); return 0; }
+    *rc = XGPU_ERR_INVALID_ARGUMENT;
+    if (!rp || !rois) { snprintf(why, 160, "roi parameters or rectangles are NULL"); return 0; }
+    if (n < 1 || n > XGPU_MAX_ROIS) { snprintf(why, 160, "n_rois %d outside 1..%d", n, XGPU_MAX_ROIS); return 0; }
+    if (rp->fit != XGPU_FIT_STRETCH && rp->fit != XGPU_FIT_LETTERBOX) { snprintf(why, 160, "fit must be XGPU_FIT_STRETCH or XGPU_FIT_LETTERBOX"); return 0; }
+    const bool is_int = f->dtype == XGPU_OUT_U8 || f->dtype == XGPU_OUT_U16;
+    if (rp->fit == XGPU_FIT_LETTERBOX) {
+        const float top = (float)((1 << (f->dtype == XGPU_OUT_U8 ? 8 : bd)) - 1);
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(rp->pad[k]) || (is_int && (rp->pad[k] < 0.f || rp->pad[k] > top || rp->pad[k] != std::floor(rp->pad[k])))) {
+                snprintf(why, 160, "pad[%d]: a finite value, for the integer dtypes an integer in 0..%d", k, (int)top);
+                return 0;
+            }
+    }
+    const size_t es = (size_t)elem_size(f->dtype);
+    const bool interleaved = f->layout == XGPU_OUT_RGB_INTERLEAVED || f->layout == XGPU_OUT_YUV444_INTERLEAVED;
+    const size_t row = (interleaved ? 3 : 1) * (size_t)sc->width * es;
+    const size_t tight = (size_t)(interleaved ? 1 : 3) * sc->height * (f->row_pitch ? f->row_pitch : row);
+    if (rp->image_pitch && (rp->image_pitch % es || rp->image_pitch < image)) {
+        snprintf(why, 160, "image_pitch %zu: 0, or a multiple of the %zu-byte element not below the %zu bytes of one image", rp->image_pitch, es, image);
+        return 0;
+    }
+    const size_t ip = rp->image_pitch ? rp->image_pitch : tight;
+    const int ws_all = width - f->crop[0] - f->crop[1], hs_all = height - f->crop[2] - f->crop[3];
+    size_t mid = 0;
+    for (int i = 0; i < n; i++) {
+        const xgpu_roi &r = rois[i];
+        *bad = i;
+        *rc = XGPU_ERR_INVALID_ARGUMENT;
+        if ((r.x | r.y | r.width | r.height) & 1) { snprintf(why, 160, "roi %d: (%d, %d, %d, %d) is not even", i, r.x, r.y, r.width, r.height); return 0; }
+        if (r.x < 0 || r.y < 0 || r.width < 2 || r.height < 2 || r.x > ws_all - r.width || r.y > hs_all - r.height) {
+            snprintf(why, 160, "roi %d: (%d, %d, %d, %d) is not inside the %d x %d picture minus the crop", i, r.x, r.y, r.width, r.height, ws_all, hs_all);
+            return 0;
+        }
+        int in[4];
+        roi_inner(r.width, r.height, sc->width, sc->height, rp->fit, in);
+        *rc = XGPU_ERR_UNSUPPORTED;
+        if (!scale_ratio_ok(r.width, in[2]) || !scale_ratio_ok(r.height, in[3])) {
+            snprintf(why, 160, "roi %d: %d x %d to %d x %d is outside 1/64 .. 8 times per axis", i, r.width, r.height, in[2], in[3]);
+            return 0;
+        }
+        mid += (size_t)in[3] * (((r.width + 7) & ~7) + 2 * (((r.width >> 1) + 7) & ~7)) * sizeof(uint16_t);
+        if (mid > ROIS_MID_LIMIT) { snprintf(why, 160, "roi %d: the intermediate of the call passes 512 MiB here", i); return 0; }
+    }
+    *bad = -1;
+    *rc = XGPU_OK;
+    if (image_pitch) *image_pitch = ip;
+    if (mid_bytes) *mid_bytes = mid;
+    return (size_t)(n - 1) * ip + image;
+}
+int xgpu_output_rois_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, int width, int height,
+                           int bit_depth, int *bad_index)
+{
+    int rc, bad; char why[160];
+    (void)rois_size(f, sc, rp, rois, n_rois, width, height, bit_depth, &rc, why, &bad, NULL, NULL);
+    if (bad_index) *bad_index = bad;
+    return rc;
+}
+size_t xgpu_output_rois_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, int width, int height,
+                             int bit_depth)
+{
+    int rc, bad; char why[160];
+    return rois_size(f, sc, rp, rois, n_rois, width, height, bit_depth, &rc, why, &bad, NULL, NULL);
+}
+int xgpu_pic_output_device_rois(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
+                                const xgpu_roi *rois, int n, void *d_dst, size_t dst_size, void *stream)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    const int bd = c->sp.bit_depth_luma;
+    int src_rc, bad; char why[160];
+    size_t image_pitch = 0, mid_need = 0;
+    const size_t need = rois_size(f, sc, rp, rois, n, c->sp.width, c->sp.height, bd, &src_rc, why, &bad, &image_pitch, &mid_need);
+    if (need == 0) { snprintf(c->err, sizeof(c->err), "pic_output_device_rois: %s", why); return src_rc; }
+    const size_t es = (size_t)elem_size(f->dtype);
+    if (dst_size < need || ((uintptr_t)d_dst % es)) {
+        snprintf(c->err, sizeof(c->err), "pic_output_device_rois: destination of %zu bytes at %p, the %d images need %zu bytes aligned to %zu", dst_size, d_dst, n, need, es);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    if (dra) { ARGCHK(c, dra->luma_inv_scale_lut && dra->chroma_inv_scale_lut[0] && dra->chroma_inv_scale_lut[1]); ARGCHK(c, bd <= 10); }      // upload_dra's refusals, before anything is queued
+    { const int rc = check_device_dst(c, "pic_output_device_rois", d_dst, need); if (rc < 0) return rc; }
+    // the descriptor block, made here, before anything is queued: n records, then one set of tap tables per distinct (source size, inner size)
+    const int wd = sc->width, hd = sc->height;
+    std::vector<uint8_t> blk((size_t)n * sizeof(RoiDesc)), blob;
+    struct Set { int ws, hs, wi, hi; ScaleTabs tb; size_t base; };
+    std::vector<Set> sets;
+    int capy = 0, capc = 0, max_w = 0, max_ih = 0;
+    size_t mid = 0;
+    for (int i = 0; i < n; i++) {
+        const xgpu_roi &r = rois[i];
+        int in[4];
+        roi_inner(r.width, r.height, wd, hd, rp->fit, in);
+        size_t k = 0;
+        while (k < sets.size() && !(sets[k].ws == r.width && sets[k].hs == r.height && sets[k].wi == in[2] && sets[k].hi == in[3])) k++;
+        if (k == sets.size()) {
+            Set st = { r.width, r.height, in[2], in[3], {}, (blk.size() + 15) & ~(size_t)15 };
+            const int rc = scale_build_tables(r.width, r.height, in[2], in[3], sc->filter, f->chroma_loc, blob, st.tb, in[0]);
+            if (rc < 0) { snprintf(c->err, sizeof(c->err), "pic_output_device_rois: roi %d: cannot make the tap tables for %dx%d -> %dx%d", i, r.width, r.height, in[2], in[3]); return rc; }
+            if (st.base + blob.size() > 0xFFFFFFFFu) { snprintf(c->err, sizeof(c->err), "pic_output_device_rois: roi %d: the tap tables of the call pass 4 GiB here", i); return XGPU_ERR_UNSUPPORTED; }
+            blk.resize(st.base + blob.size());
+            memcpy(&blk[st.base], blob.data(), blob.size());
+            sets.push_back(st);
+        }
+        const Set &st = sets[k];
+        RoiDesc d;
+        memset(&d, 0, sizeof(d));
+        d.dst = (uint64_t)i * image_pitch;
+        d.x = r.x; d.y = r.y; d.w = r.width; d.h = r.height;
+        d.ix = in[0]; d.iy = in[1]; d.iw = in[2]; d.ih = in[3];
+        d.mid = (uint32_t)(mid / sizeof(uint16_t));
+        d.mpy = (r.width + 7) & ~7; d.mpc = ((r.width >> 1) + 7) & ~7;
+        mid += (size_t)in[3] * (d.mpy + 2 * d.mpc) * sizeof(uint16_t);
+        for (int t = 0; t < 4; t++) {
+            d.first[t] = (uint32_t)(st.base + st.tb.off_first[t]); d.count[t] = (uint32_t)(st.base + st.tb.off_count[t]); d.wt[t] = (uint32_t)(st.base + st.tb.off_w[t]);
+            d.stride[t] = st.tb.stride[t];
+        }
+        memcpy(&blk[(size_t)i * sizeof(RoiDesc)], &d, sizeof(d));
+        capy = std::max(capy, st.tb.capy); capc = std::max(capc, st.tb.capc);
+        max_w = std::max(max_w, r.width); max_ih = std::max(max_ih, in[3]);
+    }
+    // the context's two buffers, grown on demand.  hipFree waits for the device, so no kernel of an earlier call still reads what is freed; in steady state neither runs.
+    if (c->sc_mid_cap < mid_need) {
+        if (c->sc_mid) { (void)hipFree(c->sc_mid); c->sc_mid = NULL; c->sc_mid_cap = 0; }
+        if (hipMalloc((void **)&c->sc_mid, mid_need) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "pic_output_device_rois: cannot allocate the %zu-byte intermediate", mid_need); return XGPU_ERR_OUT_OF_MEMORY; }
+        c->sc_mid_cap = mid_need;
+    }
+    if (c->roi_blk_cap < blk.size()) {
+        if (c->roi_blk) { (void)hipFree(c->roi_blk); c->roi_blk = NULL; c->roi_blk_cap = 0; }
+        const size_t cap = blk.size() + blk.size() / 2;      // some room: a batch of boxes changes its tables' size from call to call
+        if (hipMalloc((void **)&c->roi_blk, cap) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "pic_output_device_rois: cannot allocate the %zu-byte descriptor block", cap); return XGPU_ERR_OUT_OF_MEMORY; }
+        c->roi_blk_cap = cap;
+    }
+    if (dra) { const int rc = upload_dra(c, dra); if (rc < 0) return rc; }
+    hipStream_t s = c->stream;
+    if (stream) {
+        for (int i = 0; i < 2; i++)
+            if (!c->odev_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->odev_ev[i], hipEventDisableTiming));
+        s = (hipStream_t)stream;
+        HIPCHK(c, hipEventRecord(c->odev_ev[0], c->stream));      // the picture's kernels, the DRA tables and every earlier output call (they all end in the context's stream) -> the caller's stream
+        HIPCHK(c, hipStreamWaitEvent(s, c->odev_ev[0], 0));
+    }
+    // behind the wait above: after every kernel that read the previous block.  (Pageable host memory: staged before the call returns, as the DRA tables are.)
+    HIPCHK(c, hipMemcpyAsync(c->roi_blk, blk.data(), blk.size(), hipMemcpyHostToDevice, s));
+    RoisOutArgs a;
+    memset(&a, 0, sizeof(a));
+    scaled_common_args(c, pic, dra, f, sc, d_dst, a);
+    a.mid = c->sc_mid;
+    a.capy = capy; a.capc = capc;
+    a.blk = c->roi_blk; a.n = n;
+    for (int k = 0; k < 3; k++) a.padv[k] = rp->fit == XGPU_FIT_LETTERBOX ? rp->pad[k] : 0.f;
+    launch_output_rois(a, f->layout, f->dtype, max_w, max_ih, s);
+    HIPCHK(c, hipGetLastError());
+    if (stream) {
+        HIPCHK(c, hipEventRecord(c->odev_ev[1], s));      // the context's stream - and through it the next output call on any stream - does not touch the slot, the block or the intermediate before the kernels are done
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->odev_ev[1], 0));
     }
     return XGPU_OK;

@@ -357,6 +357,8 @@ struct xgpu_ctx {
     ScaleTabs       sc_host;          // what sc_tab holds: offsets, strides, pass 2's spans
     uint16_t       *sc_mid;
     size_t          sc_mid_cap;
+    uint8_t        *roi_blk;          // xgpu_pic_output_device_rois: the descriptors and tap tables of the current call (its intermediate is sc_mid), ordered like sc_tab
+    size_t          roi_blk_cap;
     hipEvent_t      odev_ev[2];       // xgpu_pic_output_device on a caller's stream: picture ready on the context stream / the caller's kernel done (created at the first call)
     xgpu_frame_params fp;
     int             have_frame;
@@ -488,7 +490,29 @@ struct ScaledOutArgs : RgbOutArgs {
     float    mean[3], inv_std[3];   // by output position (after bgr)
 };
 void launch_output_scaled(const ScaledOutArgs &a, int layout, int dtype, hipStream_t s);
-int  scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb);      // xgpu_scale.hip
+// x_off: pass 2's groups of 64 destination columns start x_off columns before column 0 (a letterboxed image, whose workgroups are laid over the whole image)
+int  scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb, int x_off = 0);      // xgpu_scale.hip
+// k_output_rois.hip: several rectangles of one picture, each resized to dw x dh - stretched, or letterboxed into it - as a batch of images
+// (xgpu_pic_output_device_rois).  One record per rectangle, in the context's descriptor block in front of the tap tables it points into.
+struct __attribute__((aligned(16))) RoiDesc {
+    uint64_t dst;                   // byte offset of the image in the destination
+    int      x, y, w, h;            // the rectangle, luma samples from the first sample of the picture minus f->crop (even)
+    int      ix, iy, iw, ih;        // the filtered part inside the dw x dh image; every other element is the pad value
+    uint32_t mid;                   // first sample of its intermediate: Y [ih][mpy], then Cb and Cr [ih][mpc]
+    int      mpy, mpc;
+    uint32_t first[4], count[4], wt[4];      // byte offsets in the block of the tables 0 yl, 1 yc, 2 xl, 3 xc (laid out as ScaledOutArgs' are)
+    int      stride[4];
+    int      pad_[3];
+};
+static_assert(sizeof(RoiDesc) == 128, "RoiDesc must be 128 bytes");
+// ScaledOutArgs' picture, destination and conversion fields (y, u, v: the picture minus f->crop; dst, pitch, plane: of image 0; capy, capc: the widest of all
+// rectangles; mid: the base of all intermediates; w, h, cw, ch and the four taps are not read), then the batch's
+struct RoisOutArgs : ScaledOutArgs {
+    const uint8_t *blk;             // the descriptor block: n RoiDesc, then the tap tables
+    int      n;
+    float    padv[3];               // the pad value by output position, before the normalise (integer dtypes: the integer)
+};
+void launch_output_rois(const RoisOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s);
 // k_output_yuv.hip (k_output_semiplanar): NV12 / P016 - xgpu_pic_output's samples, luma rows then rows of interleaved Cb Cr
 struct SemiPlanarArgs {
     const int16_t *y, *u, *v;       // first sample of the cropped area of every plane

@@ -75,8 +75,9 @@ int xgpu_scale_taps(int n_plane, int subsampling, int siting_half_luma, int n_ds
 // the weights - row by row for the vertical tables (0 luma rows, 1 chroma rows), transposed for the horizontal ones (2 luma columns, 3 chroma columns) -, every
 // array at a multiple of 16 bytes.  It also measures what pass 2 stages in LDS: the widest span of the intermediate that 64 neighbouring destination columns
 // reach, from an 8-sample-aligned start.  The kernel takes a workgroup's span from its first and last column, so the rows must move right monotonically: checked
-// here, for every table it is given, before anything reaches the device.
-int scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb)
+// here, for every table it is given, before anything reaches the device.  x_off (the batched output's letterbox, k_output_rois.hip): the groups of 64 are those
+// of an image in which column 0 of the tables is column x_off.
+int scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb, int x_off)
 {
     static const int vsite[3] = { 1, 0, 2 };      // ChromaSampleLocType >> 1: centred, top, bottom - in half luma samples
     const int n[4] = { hs, hs >> 1, ws, ws >> 1 }, sub[4] = { 1, 2, 1, 2 }, site[4] = { 0, vsite[chroma_loc >> 1], 0, chroma_loc & 1 }, N[4] = { hd, hd, wd, wd };
@@ -108,9 +109,9 @@ int scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_lo
             for (int o = 0; o < N[t]; o++) for (int k = 0; k < widest; k++) dw[(size_t)k * N[t] + o] = w[(size_t)o * widest + k];
             tb.stride[t] = N[t];
             int cap = 0;
-            for (int ob = 0; ob < N[t]; ob += 64) {
-                const int ol = std::min(ob + 63, N[t] - 1);
-                cap = std::max(cap, ((first[ol] + count[ol] + 7) & ~7) - (first[ob] & ~7));
+            for (int g = -x_off; g < N[t]; g += 64) {      // the columns one workgroup filters: 64 from a multiple of 64 of the image the table's columns start x_off into
+                const int ob = std::max(g, 0), ol = std::min(g + 63, N[t] - 1);
+                if (ol >= ob) cap = std::max(cap, ((first[ol] + count[ol] + 7) & ~7) - (first[ob] & ~7));
             }
             (t == 2 ? tb.capy : tb.capc) = cap;
         }

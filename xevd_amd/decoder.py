@@ -109,7 +109,8 @@ class XgpuDecoder:
         return C.byref(d), (keep, d)
 
     def pic_output_tensor(self, pic, layout="rgb", channels_last=False, dtype=None, matrix=1, full_range=False, chroma_loc=0, upsample="linear",
-                          crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, out_bit_depth=0, colour=None, size=None, filter="bilinear", mean=None, std=None):
+                          crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, out_bit_depth=0, colour=None, size=None, filter="bilinear", mean=None, std=None,
+                          rois=None, fit="stretch", pad=0.0, snap=False):
         """The picture in device memory as a torch tensor on cuda:{device}, converted on the device (xgpu_pic_output_device) on torch's current
         stream - no host round trip.  layout "rgb": [3, H, W] (channels_last: [H, W, 3]) R'G'B' (bgr: B, G, R) with dtype torch.uint8, torch.int16 /
         torch.uint16 (values at the coding depth), torch.float16, torch.bfloat16 or torch.float32 (0..1), through `matrix` (H.273 MatrixCoefficients
@@ -128,8 +129,21 @@ class XgpuDecoder:
         size=(H, W): layouts "rgb" / "yuv444" resized to H x W on the device (xgpu_pic_output_device_scaled) - the crop is the region
         of interest, filter "bilinear" (the antialiased triangle of torch's interpolate(antialias=True)) or "area"; the chroma planes are filtered straight onto
         the destination grid (upsample is not read).  mean / std (float dtypes; three values or one): out = (v - mean[k]) * (float32(1) / float32(std[k])), k the
-        channel's position in the output.  size=None: the unscaled call, and filter / mean / std must be left alone."""
+        channel's position in the output.  size=None: the unscaled call, and filter / mean / std must be left alone.
+        rois=[(x, y, w, h), ...] (with size=): every rectangle - luma samples inside the picture minus the crop, even - resized to H x W in one call
+        (xgpu_pic_output_device_rois): [N, 3, H, W] (channels_last: [N, H, W, 3]); image i is what size= with the crop set to
+        rectangle i gives.  fit "stretch", or "letterbox": the rectangle keeps its shape inside the image (abi.roi_inner says where) and the rest is `pad` - one
+        value or three, in the output's channel order, before the normalise; integers for the integer dtypes.  snap=True rounds odd rectangles outward to even
+        and clamps them to the picture; otherwise such a rectangle raises ValueError.  out: any tensor of that shape whose images are laid out as size= lays
+        out its one image, a batch stride apart."""
         import torch
+        if rois is not None:
+            if size is None:
+                raise ValueError("rois: the batch of rectangles needs size=(H, W)")
+            return self._pic_output_tensor_rois(pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour,
+                                                size, filter, mean, std, rois, fit, pad, snap)
+        if fit != "stretch" or snap or np.any(np.asarray(pad) != 0):
+            raise ValueError("fit, pad and snap belong to rois=")
         if size is not None:
             return self._pic_output_tensor_scaled(pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour,
                                                   size, filter, mean, std)
@@ -211,9 +225,8 @@ class XgpuDecoder:
             cur.wait_stream(run)
         return out
 
-    def _pic_output_tensor_scaled(self, pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour, size, filter,
-                                  mean, std):
-        """pic_output_tensor with size=(H, W)"""
+    def _scaled_setup(self, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, bgr, out_bit_depth, colour, size, filter, mean, std):
+        """what the scaled outputs check and build alike -> (torch dtype, xgpu_output_format, xgpu_scale_params, H, W, device)"""
         import torch
         if layout not in ("rgb", "yuv444"):
             raise ValueError(f"size: the scaled output has layouts 'rgb' and 'yuv444', not {layout!r}")
@@ -232,11 +245,18 @@ class XgpuDecoder:
         if (mean is not None or std is not None) and codes[dtype] in (abi.OUT_U8, abi.OUT_U16):
             raise ValueError("mean / std: the normalise needs a float dtype")
         h, w = (int(v) for v in size)
-        dev = torch.device("cuda", self.sp.device)
-        shape = (h, w, 3) if channels_last else (3, h, w)
         lay = (abi.OUT_RGB_INTERLEAVED, abi.OUT_RGB_PLANAR) if layout == "rgb" else (abi.OUT_YUV444_INTERLEAVED, abi.OUT_YUV444_PLANAR)
         fmt = abi.make_output_format(lay[0] if channels_last else lay[1], codes[dtype], bgr=bgr, matrix=matrix, full_range=full_range, chroma_loc=chroma_loc, crop=crop)
         sc = abi.make_scale_params(w, h, abi.SCALE_BILINEAR if filter == "bilinear" else abi.SCALE_AREA, mean=mean, std=std)
+        return dtype, fmt, sc, h, w, torch.device("cuda", self.sp.device)
+
+    def _pic_output_tensor_scaled(self, pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour, size, filter,
+                                  mean, std):
+        """pic_output_tensor with size=(H, W)"""
+        import torch
+        dtype, fmt, sc, h, w, dev = self._scaled_setup(layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, bgr, out_bit_depth, colour, size, filter,
+                                                       mean, std)
+        shape = (h, w, 3) if channels_last else (3, h, w)
         if out is None:
             if self.lib.xgpu_output_scaled_size(C.byref(fmt), C.byref(sc), self.width, self.height, self.bit_depth) == 0:
                 raise ValueError(f"invalid scaled output (layout {layout}, size {tuple(size)}, matrix {matrix}, chroma_loc {chroma_loc}, crop {crop}, mean {mean}, std {std})")
@@ -255,6 +275,58 @@ class XgpuDecoder:
         cur, run = self._run_stream(dev)
         self._chk(self.lib.xgpu_pic_output_device_scaled(self.ctx, pic, dl, C.byref(fmt), C.byref(sc), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
                   "xgpu_pic_output_device_scaled")
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
+    def _pic_output_tensor_rois(self, pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour, size, filter,
+                                mean, std, rois, fit, pad, snap):
+        """pic_output_tensor with size=(H, W) and rois=[...]"""
+        import torch
+        if colour is not None:
+            raise ValueError("rois: the batch of rectangles takes no colour transform")
+        if fit not in ("stretch", "letterbox"):
+            raise ValueError(f"fit must be 'stretch' or 'letterbox', not {fit!r}")
+        dtype, fmt, sc, h, w, dev = self._scaled_setup(layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, bgr, out_bit_depth, colour, size, filter,
+                                                       mean, std)
+        rois = [tuple(int(v) for v in r) for r in rois]
+        if snap:       # outward to even, then into the picture minus the crop
+            cl, cr, ct, cb = (int(v) for v in crop)
+            pw, ph = self.width - cl - cr, self.height - ct - cb
+            snapped = []
+            for x, y, rw, rh in rois:
+                x0, y0, x1, y1 = max(x & ~1, 0), max(y & ~1, 0), min((x + rw + 1) & ~1, pw), min((y + rh + 1) & ~1, ph)
+                snapped.append((x0, y0, x1 - x0, y1 - y0))
+            rois = snapped
+        n = len(rois)
+        ra = abi.make_rois(rois)
+        rp = abi.make_roi_params(abi.FIT_LETTERBOX if fit == "letterbox" else abi.FIT_STRETCH, pad)
+        shape = (n, h, w, 3) if channels_last else (n, 3, h, w)
+
+        def refuse():
+            bad = C.c_int(-1)
+            rc = self.lib.xgpu_output_rois_check(C.byref(fmt), C.byref(sc), C.byref(rp), ra, n, self.width, self.height, self.bit_depth, C.byref(bad))
+            if rc < 0:
+                at = f"roi {bad.value} {rois[bad.value]}: " if 0 <= bad.value < n else ""
+                raise ValueError(f"invalid batch of rectangles ({rc}): {at}layout {layout}, size {tuple(size)}, fit {fit}, pad {pad}, crop {crop}, mean {mean}, std {std}, "
+                                 f"{n} rectangles")
+        if out is None:
+            refuse()
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
+            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+        st = out.stride()
+        pitch = st[1] if channels_last else st[2]          # elements between rows
+        if (channels_last and st[2:] != (3, 1)) or (not channels_last and (st[3] != 1 or st[1] != pitch * h)) or pitch < (3 * w if channels_last else w):
+            raise ValueError(f"out: strides {st} are not rows of {'W x 3' if channels_last else 'W'} elements {'' if channels_last else 'in planes of H rows '}")
+        fmt.row_pitch = pitch * dtype.itemsize
+        rp.image_pitch = st[0] * dtype.itemsize if n > 1 else 0
+        refuse()
+        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
+        nbytes = (sum((k - 1) * s for k, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
+        cur, run = self._run_stream(dev)
+        self._chk(self.lib.xgpu_pic_output_device_rois(self.ctx, pic, dl, C.byref(fmt), C.byref(sc), C.byref(rp), ra, n, C.c_void_p(out.data_ptr()), nbytes,
+                                                       C.c_void_p(run.cuda_stream)), "xgpu_pic_output_device_rois")
         if run is not cur:
             cur.wait_stream(run)
         return out

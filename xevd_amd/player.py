@@ -101,7 +101,7 @@ class StreamDecoder:
             cm[k] = v
         return cm
 
-    def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None):
+    def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -112,11 +112,18 @@ class StreamDecoder:
         vectors, modes, QP - as a torch tensor under params["side_info"] (the yielded tuple keeps its shape), taken right behind the picture's kernels, before
         the next picture overwrites the map it is read from; kind "flow" defaults to the SPS crop when apply_crop is set
         size=(H, W), mean=, std= (with tensor=, layouts "rgb" / "yuv444"): every picture resized to H x W and normalised in the same call (pic_output_tensor's
-        size / mean / std; tensor=dict(filter="area") for the box filter) - what a model takes, without a full-size tensor in between"""
+        size / mean / std; tensor=dict(filter="area") for the box filter) - what a model takes, without a full-size tensor in between
+        rois=[(x, y, w, h), ...] or a callable(params) -> such a list (with tensor= and size=; called behind the picture's kernels, so params["side_info"] is
+        there when side= is given), fit=, pad=: every picture as the batch [N, 3, H, W] of its rectangles (pic_output_tensor's rois / fit / pad;
+        tensor=dict(snap=True) for boxes a detector made)"""
         if to is not None and tensor is None:
             raise ValueError("to: needs tensor=dict(...)")
         if (size is not None or mean is not None or std is not None) and tensor is None:
             raise ValueError("size / mean / std: need tensor=dict(...)")
+        if rois is not None and (tensor is None or size is None):
+            raise ValueError("rois: need tensor=dict(...) and size=(H, W)")
+        if (fit is not None or pad is not None) and rois is None:
+            raise ValueError("fit / pad: need rois=")
         q = queue.Queue(maxsize=self.prefetch)
         th = threading.Thread(target=self._producer, args=(q,), daemon=True)
         th.start()
@@ -149,7 +156,7 @@ class StreamDecoder:
                 kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
                 if to is not None:
                     kw.setdefault("colour", self.colour_transform(p["colour"], to))
-                for k, v in (("size", size), ("mean", mean), ("std", std)):
+                for k, v in (("size", size), ("mean", mean), ("std", std), ("rois", rois(p) if callable(rois) else rois), ("fit", fit), ("pad", pad)):
                     if v is not None:
                         kw.setdefault(k, v)
                 with self._lock:
@@ -201,12 +208,12 @@ class StreamDecoder:
                 self._dec.close()
                 self._dec = None
 
-    def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None):
+    def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too"""
         out, epoch = [], -1
-        for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std):
+        for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad):
             if p["is_idr"]:
                 epoch += 1
             if tensor is not None:
