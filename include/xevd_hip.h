@@ -399,6 +399,50 @@ size_t xgpu_output_rois_size(const xgpu_output_format *f, const xgpu_scale_param
    output caches are left alone. */
 int    xgpu_pic_output_device_rois(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
                                    const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, void *d_dst, size_t dst_size, void *stream);
+/* ---- regions of interest from device memory (k_output_rois_dev.hip): xgpu_pic_output_device_rois for boxes that a detector left on the GPU.  d_boxes points
+   to `capacity` boxes in device memory (1 .. XGPU_MAX_ROIS), d_count (may be NULL: all of them) to a device int32 - the live boxes are the first
+   min(max(*d_count, 0), capacity).  The host reads neither; the call does not synchronise and nothing comes back to the host.  Descriptors and tap tables are
+   made on the device (k_rois_prepare) on `stream`, behind whatever wrote the boxes there; the two passes are section 8e's.  Image i is, bit for bit, what
+   xgpu_pic_output_device_rois writes for the rectangle `used` of box i.
+   The device cannot refuse a box, so every box is snapped (pw x ph: the picture minus f->crop):
+     XGPU_BOX_XYWH_I32   x0 = max(x & ~1, 0), x1 = min((x + w + 1) & ~1, pw), y alike
+     XGPU_BOX_XYXY_F32   a non-finite coordinate: XGPU_ROI_INVALID; else each coordinate clamped to +-2^20, x0 = max(2 * (int)floorf(x1 * 0.5f), 0),
+                         x1' = min(2 * (int)ceilf(x2 * 0.5f), pw), y alike - every step exact in float32
+   and gets a status - in d_results[i] (may be NULL; `used`, `inner` are zeros unless XGPU_ROI_OK; inner: what xgpu_roi_inner gives for `used`):
+     XGPU_ROI_OK          the image is written
+     XGPU_ROI_UNUSED      index at or above the count: no element of the image is written
+     XGPU_ROI_INVALID     a non-finite coordinate
+     XGPU_ROI_EMPTY       the snapped width or height is below 2
+     XGPU_ROI_TOO_LARGE   the snapped rectangle exceeds `bounds` (or the LDS span the call was sized for - which bounds rule out)
+     XGPU_ROI_RATIO       the inner size is outside the scaled output's limits per axis
+   For INVALID, EMPTY, TOO_LARGE and RATIO the whole image is rp->pad (through the normalise), each element written once: rp->pad is validated for both fits.
+   bounds: the largest snapped rectangle the call is sized for - the grids, the LDS of pass 2, a slot of tap tables and of the intermediate per box; 0 = the picture
+   minus the crop.  Refusals, all before anything is queued: what xgpu_pic_output_device_rois refuses that does not depend on a rectangle; an unknown box_format,
+   negative bounds or bounds beyond the picture minus the crop, capacity outside 1 .. XGPU_MAX_ROIS (XGPU_ERR_INVALID_ARGUMENT); capacity x
+   sc->height * (align8(Mw) + 2 * align8(Mw / 2)) * 2 bytes of intermediate above 512 MiB, or descriptors and table slots of 4 GiB (XGPU_ERR_UNSUPPORTED). */
+#define XGPU_BOX_XYWH_I32 0   /* xgpu_roi in device memory: x, y, width, height */
+#define XGPU_BOX_XYXY_F32 1   /* float x1, y1, x2, y2: what detectors emit */
+#define XGPU_ROI_OK        0
+#define XGPU_ROI_UNUSED    1
+#define XGPU_ROI_INVALID   2
+#define XGPU_ROI_EMPTY     3
+#define XGPU_ROI_TOO_LARGE 4
+#define XGPU_ROI_RATIO     5
+typedef struct xgpu_roi_bounds { int max_width, max_height; } xgpu_roi_bounds;   /* of a snapped rectangle; 0: the picture minus the crop */
+typedef struct xgpu_roi_result { int status; xgpu_roi used; int inner[4]; } xgpu_roi_result;   /* 9 ints */
+/* Host only, no context: 0 or the code the call refuses with / the bytes the call needs at d_dst - (capacity - 1) * image_pitch + one image; 0: refused */
+int    xgpu_output_rois_dev_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi_bounds *bounds, int box_format,
+                                  int capacity, int width, int height, int bit_depth);
+size_t xgpu_output_rois_dev_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi_bounds *bounds, int box_format,
+                                 int capacity, int width, int height, int bit_depth);
+/* Host only: the device's snapping rule on one box (an xgpu_roi or four floats) for a pic_w x pic_h picture (minus the crop): XGPU_ROI_OK, _INVALID or _EMPTY,
+   *used the rectangle (zeros unless XGPU_ROI_OK); XGPU_ERR_INVALID_ARGUMENT for an unknown format, a NULL or a picture size that is not positive and even */
+int    xgpu_roi_snap(int box_format, const void *box, int pic_w, int pic_h, xgpu_roi *used);
+/* Non-blocking.  Buffers and ordering as for xgpu_pic_output_device_rois: the context's block and intermediate (sized from bounds and capacity, grown on demand),
+   a start behind the context stream's event, the context's stream waiting at the end; stream = NULL: the context's stream. */
+int    xgpu_pic_output_device_rois_dev(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                                       const xgpu_roi_params *rp, const xgpu_roi_bounds *bounds, int box_format, const void *d_boxes, int capacity,
+                                       const int *d_count, xgpu_roi_result *d_results, void *d_dst, size_t dst_size, void *stream);
 /* ---- coding side information (k_side_info.hip): what the decoder knows about a picture besides its samples - motion vectors per 4x4 luma unit, the
    reference each one points at, intra / inter / skip / IBC, QP, coded-residual flag, block edges - read out of the SCU map the in-loop filters read
    (the reference's map_scu / map_refi / map_mv, src_base/xevd_def.h:372-438).
@@ -536,6 +580,10 @@ int xgpu_test_batch_resid(xgpu_ctx *ctx, xgpu_dbatch *db, int16_t *resid);
 int xgpu_test_build_batch(const xgpu_seq_params *sp, const xgpu_cu_batch *b, int threads, uint64_t digest[XGPU_TEST_BUILD_DIGESTS], int info[XGPU_BATCH_INFO_COUNT], double *ms);
 /* dequant + 2-D inverse transform of n blocks of one size, in place (xevd_itdq, src_base/xevd_itdq.c:494) */
 int xgpu_test_itdq(xgpu_ctx *ctx, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth);
+/* xgpu_scale_taps made by the device's row builder (the one k_rois_prepare runs, one lane per row): same arguments, same results, same return value; w_stride
+   must hold the widest row.  Blocking. */
+int xgpu_test_scale_taps_device(xgpu_ctx *ctx, int n_plane, int subsampling, int siting_half_luma, int n_dst, int filter, int32_t *first, int32_t *count,
+                                int16_t *w, int w_stride);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,12 @@ tensors of their own; the inner rectangles of the two routes are compared).  Eve
 from the first kernel to the last, host gaps included; host_us is what the host spends queueing.  The split between the two kernels is what
 rocprofv3 --kernel-trace --stats shows for `--legs rois`.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois] [--out out/output_device.json]
+The rois_dev leg (xgpu_pic_output_device_rois_dev: k_rois_prepare + the two kernels of the rois leg) takes the same two workloads with the boxes in a device
+tensor, as a detector leaves them, and alternates - same protocol as the rois leg - route A, what the host-box call needs then: boxes.cpu() (a synchronisation
+and a read-back) and xgpu_pic_output_device_rois, with route B: the device-box call on the tensor itself, max_roi set to the true maxima of the workload.  The
+split of B into its three kernels is what rocprofv3 --kernel-trace --stats shows for `--legs rois_dev`.
+
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -157,6 +162,58 @@ def rois_leg(torch, dec, pic, s, a, res):
         res["rois"][name] = r
 
 
+def rois_dev_leg(torch, dec, pic, s, a, res):
+    """boxes in device memory: read back and given to the host-box call (A) against the device-box call (B), alternated"""
+    import time
+    from xevd_amd import abi
+    w, h = a.width, a.height
+    size, n, pad = (224, 224), 64, 0.447
+    rng = np.random.default_rng(7)      # the boxes of the rois leg
+    boxes = []
+    for _ in range(n):
+        bw, bh = (min(int(rng.integers(32, 257)) * 2, v) for v in (w, h))
+        boxes.append((int(rng.integers(0, (w - bw) // 2 + 1)) * 2, int(rng.integers(0, (h - bh) // 2 + 1)) * 2, bw, bh))
+    kw = dict(dtype=torch.float32, mean=MEAN, std=STD)
+    res["rois_dev"] = {}
+    for name, rois, fit in (("tiles_stretch", abi.tile_rois(w, h, (w // 8) & ~1, (h // 8) & ~1)[:n], "stretch"), ("boxes_letterbox", boxes, "letterbox")):
+        max_roi = (max(r[3] for r in rois), max(r[2] for r in rois))
+        d_boxes = torch.tensor(rois, dtype=torch.int32, device="cuda:0")
+        out_a = dec.pic_output_tensor(pic, size=size, rois=rois, fit=fit, pad=pad, **kw)
+        out_b, results = dec.pic_output_tensor(pic, size=size, rois=d_boxes, fit=fit, pad=pad, max_roi=max_roi, results=True, **kw)
+
+        def route_a():
+            dec.pic_output_tensor(pic, size=size, rois=d_boxes.cpu().tolist(), fit=fit, pad=pad, out=out_a, **kw)
+
+        def route_b():
+            dec.pic_output_tensor(pic, size=size, rois=d_boxes, fit=fit, pad=pad, max_roi=max_roi, out=out_b, **kw)
+
+        for _ in range(5):
+            route_a(); route_b()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(out_a, out_b)) and bool((results[:, 0] == abi.ROI_OK).all())
+        ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)] for k in ("host_boxes", "device_boxes")}
+        host = {"host_boxes": [], "device_boxes": []}
+        for i in range(a.iters):
+            for k, fn in (("host_boxes", route_a), ("device_boxes", route_b)):
+                e0, e1 = ev[k][i]
+                torch.cuda.synchronize()      # each route starts on an idle device: its events see its own gaps only
+                t0 = time.perf_counter()
+                e0.record(s)
+                fn()
+                e1.record(s)
+                host[k].append((time.perf_counter() - t0) * 1e6)
+        torch.cuda.synchronize()
+        r = {"n": len(rois), "size": list(size), "fit": fit, "max_roi": list(max_roi), "images_equal": same}
+        for k in ("host_boxes", "device_boxes"):
+            us = np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev[k]])
+            r[k] = {"us": round(float(np.median(us)), 2), "p10_us": round(float(np.percentile(us, 10)), 2), "p90_us": round(float(np.percentile(us, 90)), 2),
+                    "host_us": round(float(np.median(host[k])), 2)}
+        r["speedup"] = round(r["host_boxes"]["us"] / r["device_boxes"]["us"], 2)
+        print(f"rois_dev {name:16s} {len(rois)} x {size[1]}x{size[0]} f32: boxes.cpu() + host-box call {r['host_boxes']['us']:9.1f} us (host {r['host_boxes']['host_us']:8.1f})   "
+              f"device-box call {r['device_boxes']['us']:9.1f} us (host {r['device_boxes']['host_us']:8.1f})   {r['speedup']:.2f}x   images equal: {same}")
+        res["rois_dev"][name] = r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=7680)
@@ -164,8 +221,9 @@ def main():
     ap.add_argument("--bit-depth", type=int, default=10)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois"), default="all",
-                    help="full: the full-size forms and the side information; scaled: the scaled leg alone; rois: the batched regions of interest alone")
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev"), default="all",
+                    help="full: the full-size forms and the side information; scaled: the scaled leg alone; rois: the batched regions of interest alone; "
+                         "rois_dev: the regions of interest from boxes in device memory alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -203,6 +261,8 @@ def main():
             scaled_leg(torch, dec, pic, s, a, res, copy_gbps)
         if a.legs in ("all", "rois"):
             rois_leg(torch, dec, pic, s, a, res)
+        if a.legs in ("all", "rois_dev"):
+            rois_dev_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "full"):
             for name, kw, wbytes in forms:
                 out = dec.pic_output_tensor(pic, **kw)

@@ -113,6 +113,19 @@ def scale_taps(lib, n_plane, subsampling, siting_half_luma, n_dst, filter=SCALE_
     return rc if rc < 0 else (first, count, w)
 
 
+def scale_taps_device(lib, ctx, n_plane, subsampling, siting_half_luma, n_dst, filter=SCALE_BILINEAR, extra=0):
+    """xgpu_test_scale_taps_device - scale_taps' arrays made by the device's row builder (ctx: an open context); extra: columns beyond the widest row"""
+    first, count = np.zeros(max(int(n_dst), 1), np.int32), np.zeros(max(int(n_dst), 1), np.int32)
+    pi, pc = first.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_int32))
+    widest = lib.xgpu_test_scale_taps_device(ctx, int(n_plane), int(subsampling), int(siting_half_luma), int(n_dst), int(filter), pi, pc, None, 0)
+    if widest < 0:
+        return widest
+    w = np.full((int(n_dst), widest + int(extra)), -1, np.int16)
+    rc = lib.xgpu_test_scale_taps_device(ctx, int(n_plane), int(subsampling), int(siting_half_luma), int(n_dst), int(filter), pi, pc,
+                                         w.ctypes.data_as(C.POINTER(C.c_int16)), w.shape[1])
+    return rc if rc < 0 else (first, count, w)
+
+
 FIT_STRETCH, FIT_LETTERBOX = 0, 1
 MAX_ROIS = 1024
 
@@ -151,6 +164,37 @@ def roi_inner(lib, roi, size, fit=FIT_LETTERBOX):
     inner = (C.c_int * 4)()
     rc = lib.xgpu_roi_inner(r, C.byref(sc), int(fit), inner)
     return rc if rc < 0 else tuple(inner)
+
+
+BOX_XYWH_I32, BOX_XYXY_F32 = 0, 1
+ROI_OK, ROI_UNUSED, ROI_INVALID, ROI_EMPTY, ROI_TOO_LARGE, ROI_RATIO = range(6)
+
+
+class RoiBounds(C.Structure):
+    _fields_ = [("max_width", C.c_int), ("max_height", C.c_int)]
+
+
+class RoiResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("used", Roi), ("inner", C.c_int * 4)]
+
+
+def make_roi_bounds(max_roi=None):
+    """xgpu_roi_bounds from max_roi = (H, W), the largest snapped rectangle a device-box call is sized for; None or 0: the picture minus the crop"""
+    b = RoiBounds()
+    if max_roi is not None:
+        b.max_height, b.max_width = int(max_roi[0]), int(max_roi[1])
+    return b
+
+
+def roi_snap(lib, box, pic_size, box_format=None):
+    """xgpu_roi_snap, the device's snapping rule on the host: box (x, y, w, h) of ints (BOX_XYWH_I32) or (x1, y1, x2, y2) of floats (BOX_XYXY_F32; the default
+    for a box that holds a float), pic_size = (H, W) of the picture minus the crop -> (status, (x, y, width, height)), or the negative code"""
+    if box_format is None:
+        box_format = BOX_XYXY_F32 if any(isinstance(v, (float, np.floating)) for v in box) else BOX_XYWH_I32
+    raw = (C.c_float * 4)(*[float(np.float32(v)) for v in box]) if box_format == BOX_XYXY_F32 else (C.c_int * 4)(*[int(v) for v in box])
+    used = Roi()
+    rc = lib.xgpu_roi_snap(int(box_format), raw, int(pic_size[1]), int(pic_size[0]), C.byref(used))
+    return rc if rc < 0 else (rc, (used.x, used.y, used.width, used.height))
 
 
 def tile_rois(width, height, tile_w, tile_h):
@@ -372,6 +416,11 @@ _EXPORTS = {
     "xgpu_output_rois_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(Roi), C.c_int, C.c_int, C.c_int, C.c_int]),
     "xgpu_pic_output_device_rois": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(Roi),
                                               C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_roi_snap": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(Roi)]),
+    "xgpu_output_rois_dev_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(RoiBounds)] + [C.c_int] * 5),
+    "xgpu_output_rois_dev_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(RoiBounds)] + [C.c_int] * 5),
+    "xgpu_pic_output_device_rois_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams),
+                                                  C.POINTER(RoiBounds), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_side_info_size": (C.c_size_t, [C.POINTER(SideFormat), C.c_int, C.c_int]),
     "xgpu_frame_side_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SideFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -404,6 +453,7 @@ _EXPORTS = {
     "xgpu_test_dbk": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7),
     "xgpu_test_dbk_chroma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8),
     "xgpu_test_itdq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "xgpu_test_scale_taps_device": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16), C.c_int]),
 }
 
 _lib = None

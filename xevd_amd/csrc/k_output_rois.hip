@@ -15,6 +15,9 @@
 //                       The LDS a row needs is the widest span of all rectangles (the host measures it for workgroups laid over the image, not the inner part).
 // Nothing outside a rectangle reaches a result: taps end at its edge (the tables are made for its size), and what the 16-byte loads of the vertical pass read past
 // its width lands in columns of the intermediate no tap reads - as with the crop of the single-image call.
+// The same two kernels serve xgpu_pic_output_device_rois_dev (k_output_rois_dev.hip), whose block k_rois_prepare writes on the device: there a record may have no
+// width and no inner part (a refused box: the whole image is the pad value) or be marked skip (no element is written), and grids and LDS are sized for the
+// call's bounds, not for the boxes.
 #pragma clang fp contract(off)
 #include "output_common.h"
 
@@ -40,6 +43,7 @@ __global__ __launch_bounds__(256) void k_rois_horizontal(const RoisOutArgs a)
     extern __shared__ uint4 lds4[];
     constexpr int SZ = OutT<DT>::size;
     const RoiDesc &d = ((const RoiDesc *)a.blk)[blockIdx.z];
+    if (d.skip) return;      // the device-box call: an index at or above the count - the image is not touched (uniform per workgroup)
     const int oy = blockIdx.y * blockDim.y + threadIdx.y, ob = blockIdx.x * 64, ox = ob + (int)threadIdx.x;      // in the image
     // the inner columns and rows the workgroup covers (none: c0 > c1 or r0 > r1), and this wave's inner row
     const int c0 = max(ob - d.ix, 0), c1 = min(ob + 63 - d.ix, d.iw - 1);

@@ -1,6 +1,7 @@
 // xgpu_api.hip - the C ABI of include/xevd_hip.h, part 1: context, device pictures, output, frame begin / end, HIP-event kernel timing.
 // Host-side code only; kernels live in k_*.hip, the batch builder in xgpu_builder.hip, the launch sequencing in xgpu_launch.hip, the test shims in xgpu_shims.hip.
 #include "xgpu_host.h"
+#include "scale_taps.h"
 #include <memory>
 
 // xevd_tbl_qp_chroma_adjust_base (src_base/xevd_tbl.c:345-354): default Baseline chroma QP mapping.
@@ -736,8 +737,6 @@ static bool scaled_params_ok(const xgpu_output_format *f, const xgpu_scale_param
     *rc = XGPU_OK;
     return true;
 }
-// one axis: n source samples to N destination samples is inside the limits
-static bool scale_ratio_ok(int n, int N) { return N >= 2 && n <= 64 * N && N <= 8 * n; }
 // the bytes of one sc->width x sc->height image (the last row not padded), or 0
 static size_t scaled_image_bytes(const xgpu_output_format *f, const xgpu_scale_params *sc, int *rc, const char **why)
 {
@@ -876,21 +875,35 @@ int xgpu_pic_output_device_scaled(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra
 }
 
 // ------------------------------------------------------------------------------------------------ regions of interest: a batch of scaled images
-static void roi_inner(int ws, int hs, int wd, int hd, int fit, int inner[4])
-{
-    int wi = wd, hi = hd;
-    if (fit == XGPU_FIT_LETTERBOX) {
-        if ((int64_t)ws * hd >= (int64_t)hs * wd) hi = (int)std::min<int64_t>(hd, std::max<int64_t>(2, (2 * (int64_t)hs * wd + ws) / (2 * (int64_t)ws)));
-        else                                      wi = (int)std::min<int64_t>(wd, std::max<int64_t>(2, (2 * (int64_t)ws * hd + hs) / (2 * (int64_t)hs)));
-    }
-    inner[0] = (wd - wi) >> 1; inner[1] = (hd - hi) >> 1; inner[2] = wi; inner[3] = hi;
-}
+// (the letterbox rule itself is scale_taps.h's roi_inner: k_rois_prepare runs it on the device as well)
 int xgpu_roi_inner(const xgpu_roi *r, const xgpu_scale_params *sc, int fit, int inner[4])
 {
     if (!r || !sc || !inner || r->width < 1 || r->height < 1 || sc->width < 1 || sc->height < 1 || (fit != XGPU_FIT_STRETCH && fit != XGPU_FIT_LETTERBOX))
         return XGPU_ERR_INVALID_ARGUMENT;
     roi_inner(r->width, r->height, sc->width, sc->height, fit, inner);
     return XGPU_OK;
+}
+// the pad value (read_pad: the call reads it) and the batch stride of a call: the bytes between two images, or 0 with `why`
+static size_t rois_pad_and_pitch(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, int bd, size_t image, bool read_pad, char *why)
+{
+    const bool is_int = f->dtype == XGPU_OUT_U8 || f->dtype == XGPU_OUT_U16;
+    if (read_pad) {
+        const float top = (float)((1 << (f->dtype == XGPU_OUT_U8 ? 8 : bd)) - 1);
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(rp->pad[k]) || (is_int && (rp->pad[k] < 0.f || rp->pad[k] > top || rp->pad[k] != std::floor(rp->pad[k])))) {
+                snprintf(why, 160, "pad[%d]: a finite value, for the integer dtypes an integer in 0..%d", k, (int)top);
+                return 0;
+            }
+    }
+    const size_t es = (size_t)elem_size(f->dtype);
+    const bool interleaved = f->layout == XGPU_OUT_RGB_INTERLEAVED || f->layout == XGPU_OUT_YUV444_INTERLEAVED;
+    const size_t row = (interleaved ? 3 : 1) * (size_t)sc->width * es;
+    const size_t tight = (size_t)(interleaved ? 1 : 3) * sc->height * (f->row_pitch ? f->row_pitch : row);
+    if (rp->image_pitch && (rp->image_pitch % es || rp->image_pitch < image)) {
+        snprintf(why, 160, "image_pitch %zu: 0, or a multiple of the %zu-byte element not below the %zu bytes of one image", rp->image_pitch, es, image);
+        return 0;
+    }
+    return rp->image_pitch ? rp->image_pitch : tight;
 }
 // The whole of a call's argument checks, without a device: the bytes the destination needs, or 0 with *rc = the code, `why` (a buffer of 160 bytes) and *bad =
 // the rectangle it names (-1: none).  image_pitch / mid_bytes (may be NULL): the bytes between two images, and the intermediate of the call - the sum over the
@@ -908,24 +921,8 @@ static size_t rois_size(const xgpu_output_format *f, const xgpu_scale_params *sc
     if (!rp || !rois) { snprintf(why, 160, "roi parameters or rectangles are NULL"); return 0; }
     if (n < 1 || n > XGPU_MAX_ROIS) { snprintf(why, 160, "n_rois %d outside 1..%d", n, XGPU_MAX_ROIS); return 0; }
     if (rp->fit != XGPU_FIT_STRETCH && rp->fit != XGPU_FIT_LETTERBOX) { snprintf(why, 160, "fit must be XGPU_FIT_STRETCH or XGPU_FIT_LETTERBOX"); return 0; }
-    const bool is_int = f->dtype == XGPU_OUT_U8 || f->dtype == XGPU_OUT_U16;
-    if (rp->fit == XGPU_FIT_LETTERBOX) {
-        const float top = (float)((1 << (f->dtype == XGPU_OUT_U8 ? 8 : bd)) - 1);
-        for (int k = 0; k < 3; k++)
-            if (!std::isfinite(rp->pad[k]) || (is_int && (rp->pad[k] < 0.f || rp->pad[k] > top || rp->pad[k] != std::floor(rp->pad[k])))) {
-                snprintf(why, 160, "pad[%d]: a finite value, for the integer dtypes an integer in 0..%d", k, (int)top);
-                return 0;
-            }
-    }
-    const size_t es = (size_t)elem_size(f->dtype);
-    const bool interleaved = f->layout == XGPU_OUT_RGB_INTERLEAVED || f->layout == XGPU_OUT_YUV444_INTERLEAVED;
-    const size_t row = (interleaved ? 3 : 1) * (size_t)sc->width * es;
-    const size_t tight = (size_t)(interleaved ? 1 : 3) * sc->height * (f->row_pitch ? f->row_pitch : row);
-    if (rp->image_pitch && (rp->image_pitch % es || rp->image_pitch < image)) {
-        snprintf(why, 160, "image_pitch %zu: 0, or a multiple of the %zu-byte element not below the %zu bytes of one image", rp->image_pitch, es, image);
-        return 0;
-    }
-    const size_t ip = rp->image_pitch ? rp->image_pitch : tight;
+    const size_t ip = rois_pad_and_pitch(f, sc, rp, bd, image, rp->fit == XGPU_FIT_LETTERBOX, why);
+    if (ip == 0) return 0;
     const int ws_all = width - f->crop[0] - f->crop[1], hs_all = height - f->crop[2] - f->crop[3];
     size_t mid = 0;
     for (int i = 0; i < n; i++) {
@@ -1053,6 +1050,170 @@ int xgpu_pic_output_device_rois(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, 
     a.blk = c->roi_blk; a.n = n;
     for (int k = 0; k < 3; k++) a.padv[k] = rp->fit == XGPU_FIT_LETTERBOX ? rp->pad[k] : 0.f;
     launch_output_rois(a, f->layout, f->dtype, max_w, max_ih, s);
+    HIPCHK(c, hipGetLastError());
+    if (stream) {
+        HIPCHK(c, hipEventRecord(c->odev_ev[1], s));      // the context's stream - and through it the next output call on any stream - does not touch the slot, the block or the intermediate before the kernels are done
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->odev_ev[1], 0));
+    }
+    return XGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ regions of interest from boxes in device memory
+int xgpu_roi_snap(int box_format, const void *box, int pic_w, int pic_h, xgpu_roi *used)
+{
+    if ((box_format != XGPU_BOX_XYWH_I32 && box_format != XGPU_BOX_XYXY_F32) || !box || !used || pic_w < 2 || pic_h < 2 || ((pic_w | pic_h) & 1))
+        return XGPU_ERR_INVALID_ARGUMENT;
+    memset(used, 0, sizeof(*used));
+    return roi_snap_box(box_format, box, pic_w, pic_h, used);
+}
+// What the host-box call derives from its rectangles, from the bounds alone: the slot of tap tables and of the intermediate every box gets, the block, and the
+// span of the intermediate pass 2 stages per row.
+//   tables    table t of a box has N <= Nmax rows (Nmax = sc->height for the vertical tables, sc->width for the horizontal ones) over n <= Mn plane samples
+//             (Mh, Mh / 2, Mw, Mw / 2), each row kw = floor(2 max(1, n / N)) + 2 weights wide (scale_taps.h): N kw <= max(2 N, 2 n) + 2 N <= 2 Mn + 4 Nmax.
+//   LDS span  64 neighbouring columns ob .. ol of a table of ratio r = n / N, window f = max(1, r): the first sample of ob lies above c(ob) - f, the last of ol
+//             below c(ol) + f, and c(ol) - c(ob) <= 63 r, so they span less than 63 r + 2 f + 1 samples, 14 more with the start rounded down and the end rounded
+//             up to 8: at most 65 r + 17 with r >= 1 (for r < 1, 63 r + 2 + 15 is below it too).  r is at most 64 / s by the ratio limit and at most Mn / 2
+//             (N >= 2); stretched, N = sc->width exactly, so r <= Mn / sc->width.  And no span leaves the plane: at most align8(Mn).
+//             k_rois_prepare measures every box against this and refuses (XGPU_ROI_TOO_LARGE) what would not fit.
+struct RoisDevLayout { uint32_t off_first[4], off_count[4], off_w[4]; size_t slot, tab, blk, mid_slot; int capy, capc; };
+static int rois_span_bound(int mn, int sub, int wd, bool stretch)
+{
+    const int64_t general = 65 * std::max<int64_t>(1, std::min<int64_t>(64 / sub, (mn + 1) / 2)) + 19;
+    const int64_t stretched = (65 * (int64_t)mn + wd - 1) / wd + 19;
+    const int64_t b = stretch ? std::min(general, stretched) : general;
+    return (int)std::max<int64_t>(8, std::min<int64_t>((b + 7) & ~(int64_t)7, (mn + 7) & ~7));
+}
+static void rois_dev_layout(const xgpu_scale_params *sc, int fit, int mw, int mh, int capacity, RoisDevLayout &L)
+{
+    const int mn[4] = { mh, mh >> 1, mw, mw >> 1 }, nmax[4] = { sc->height, sc->height, sc->width, sc->width };
+    size_t off = 0;
+    auto reserve = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 15) & ~(size_t)15; return (uint32_t)at; };
+    for (int t = 0; t < 4; t++) {
+        L.off_first[t] = reserve(sizeof(int32_t) * nmax[t]);
+        L.off_count[t] = reserve(sizeof(int32_t) * nmax[t]);
+        L.off_w[t] = reserve(sizeof(int16_t) * (2 * (size_t)mn[t] + 4 * (size_t)nmax[t]));
+    }
+    L.slot = off;
+    L.tab = (size_t)capacity * sizeof(RoiDesc);
+    L.blk = L.tab + (size_t)capacity * L.slot;
+    L.mid_slot = (size_t)sc->height * (((mw + 7) & ~7) + 2 * (((mw >> 1) + 7) & ~7));      // samples
+    L.capy = rois_span_bound(mw, 1, sc->width, fit == XGPU_FIT_STRETCH);
+    L.capc = rois_span_bound(mw >> 1, 2, sc->width, fit == XGPU_FIT_STRETCH);
+}
+// the call's argument checks, without a device: the bytes the destination needs, or 0 with *rc and `why`; the bounds resolved (0: the picture minus the crop)
+static size_t rois_dev_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi_bounds *bounds, int box_format,
+                            int capacity, int width, int height, int bd, int *rc, char *why, size_t *image_pitch, int *mw, int *mh)
+{
+    const char *w0 = "";
+    if (!scaled_params_ok(f, sc, width, height, bd, rc, &w0)) { snprintf(why, 160, "%s", w0); return 0; }
+    const size_t image = scaled_image_bytes(f, sc, rc, &w0);
+    if (image == 0) { snprintf(why, 160, "%s", w0); return 0; }
+    *rc = XGPU_ERR_INVALID_ARGUMENT;
+    if (!rp || !bounds) { snprintf(why, 160, "roi parameters or bounds are NULL"); return 0; }
+    if (capacity < 1 || capacity > XGPU_MAX_ROIS) { snprintf(why, 160, "capacity %d outside 1..%d", capacity, XGPU_MAX_ROIS); return 0; }
+    if (rp->fit != XGPU_FIT_STRETCH && rp->fit != XGPU_FIT_LETTERBOX) { snprintf(why, 160, "fit must be XGPU_FIT_STRETCH or XGPU_FIT_LETTERBOX"); return 0; }
+    if (box_format != XGPU_BOX_XYWH_I32 && box_format != XGPU_BOX_XYXY_F32) { snprintf(why, 160, "box_format must be XGPU_BOX_XYWH_I32 or XGPU_BOX_XYXY_F32"); return 0; }
+    const size_t ip = rois_pad_and_pitch(f, sc, rp, bd, image, true, why);      // a refused box is all pad, whatever the fit
+    if (ip == 0) return 0;
+    const int pw = width - f->crop[0] - f->crop[1], ph = height - f->crop[2] - f->crop[3];
+    if (bounds->max_width < 0 || bounds->max_height < 0 || bounds->max_width > pw || bounds->max_height > ph) {
+        snprintf(why, 160, "bounds %d x %d: 0 or at most the %d x %d picture minus the crop", bounds->max_width, bounds->max_height, pw, ph);
+        return 0;
+    }
+    *mw = bounds->max_width ? bounds->max_width : pw; *mh = bounds->max_height ? bounds->max_height : ph;
+    RoisDevLayout L;
+    rois_dev_layout(sc, rp->fit, *mw, *mh, capacity, L);
+    *rc = XGPU_ERR_UNSUPPORTED;
+    if ((size_t)capacity * L.mid_slot * sizeof(uint16_t) > ROIS_MID_LIMIT) {
+        snprintf(why, 160, "%d boxes of up to %d columns to %d rows: the intermediate of the call passes 512 MiB", capacity, *mw, sc->height);
+        return 0;
+    }
+    if (L.blk > 0xFFFFFFFFu) { snprintf(why, 160, "the tap tables of %d boxes of up to %d x %d pass 4 GiB", capacity, *mw, *mh); return 0; }
+    *rc = XGPU_OK;
+    if (image_pitch) *image_pitch = ip;
+    return (size_t)(capacity - 1) * ip + image;
+}
+int xgpu_output_rois_dev_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi_bounds *bounds, int box_format,
+                               int capacity, int width, int height, int bit_depth)
+{
+    int rc, mw, mh; char why[160];
+    (void)rois_dev_size(f, sc, rp, bounds, box_format, capacity, width, height, bit_depth, &rc, why, NULL, &mw, &mh);
+    return rc;
+}
+size_t xgpu_output_rois_dev_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi_bounds *bounds, int box_format,
+                                 int capacity, int width, int height, int bit_depth)
+{
+    int rc, mw, mh; char why[160];
+    return rois_dev_size(f, sc, rp, bounds, box_format, capacity, width, height, bit_depth, &rc, why, NULL, &mw, &mh);
+}
+int xgpu_pic_output_device_rois_dev(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
+                                    const xgpu_roi_bounds *bounds, int box_format, const void *d_boxes, int capacity, const int *d_count, xgpu_roi_result *d_results,
+                                    void *d_dst, size_t dst_size, void *stream)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL); ARGCHK(c, d_boxes != NULL);
+    const int bd = c->sp.bit_depth_luma;
+    int src_rc, mw = 0, mh = 0; char why[160];
+    size_t image_pitch = 0;
+    const size_t need = rois_dev_size(f, sc, rp, bounds, box_format, capacity, c->sp.width, c->sp.height, bd, &src_rc, why, &image_pitch, &mw, &mh);
+    if (need == 0) { snprintf(c->err, sizeof(c->err), "pic_output_device_rois_dev: %s", why); return src_rc; }
+    const size_t es = (size_t)elem_size(f->dtype);
+    if (dst_size < need || ((uintptr_t)d_dst % es)) {
+        snprintf(c->err, sizeof(c->err), "pic_output_device_rois_dev: destination of %zu bytes at %p, the %d images need %zu bytes aligned to %zu", dst_size, d_dst, capacity, need, es);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    if (dra) { ARGCHK(c, dra->luma_inv_scale_lut && dra->chroma_inv_scale_lut[0] && dra->chroma_inv_scale_lut[1]); ARGCHK(c, bd <= 10); }      // upload_dra's refusals, before anything is queued
+    { const int rc = check_device_dst(c, "pic_output_device_rois_dev", d_dst, need); if (rc < 0) return rc; }
+    // the boxes, the count and the results are device memory of 4-byte words as well - the host never reads them
+    { const int rc = check_device_dst(c, "pic_output_device_rois_dev (boxes)", const_cast<void *>(d_boxes), (size_t)capacity * 16); if (rc < 0) return rc; }
+    if (d_count) { const int rc = check_device_dst(c, "pic_output_device_rois_dev (count)", const_cast<int *>(d_count), sizeof(int)); if (rc < 0) return rc; }
+    if (d_results) { const int rc = check_device_dst(c, "pic_output_device_rois_dev (results)", d_results, (size_t)capacity * sizeof(xgpu_roi_result)); if (rc < 0) return rc; }
+    if (((uintptr_t)d_boxes | (uintptr_t)d_count | (uintptr_t)d_results) & 3) {
+        snprintf(c->err, sizeof(c->err), "pic_output_device_rois_dev: boxes, count and results must be aligned to 4 bytes");
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    RoisDevLayout L;
+    rois_dev_layout(sc, rp->fit, mw, mh, capacity, L);
+    // the context's two buffers, grown on demand (section 8e's): sized from the bounds and the capacity, so a steady stream of calls never grows them
+    const size_t mid_need = (size_t)capacity * L.mid_slot * sizeof(uint16_t);
+    if (c->sc_mid_cap < mid_need) {
+        if (c->sc_mid) { (void)hipFree(c->sc_mid); c->sc_mid = NULL; c->sc_mid_cap = 0; }
+        if (hipMalloc((void **)&c->sc_mid, mid_need) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "pic_output_device_rois_dev: cannot allocate the %zu-byte intermediate", mid_need); return XGPU_ERR_OUT_OF_MEMORY; }
+        c->sc_mid_cap = mid_need;
+    }
+    if (c->roi_blk_cap < L.blk) {
+        if (c->roi_blk) { (void)hipFree(c->roi_blk); c->roi_blk = NULL; c->roi_blk_cap = 0; }
+        if (hipMalloc((void **)&c->roi_blk, L.blk) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "pic_output_device_rois_dev: cannot allocate the %zu-byte descriptor block", L.blk); return XGPU_ERR_OUT_OF_MEMORY; }
+        c->roi_blk_cap = L.blk;
+    }
+    if (dra) { const int rc = upload_dra(c, dra); if (rc < 0) return rc; }
+    hipStream_t s = c->stream;
+    if (stream) {
+        for (int i = 0; i < 2; i++)
+            if (!c->odev_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->odev_ev[i], hipEventDisableTiming));
+        s = (hipStream_t)stream;
+        HIPCHK(c, hipEventRecord(c->odev_ev[0], c->stream));      // the picture's kernels, the DRA tables and every earlier output call (they all end in the context's stream) -> the caller's stream
+        HIPCHK(c, hipStreamWaitEvent(s, c->odev_ev[0], 0));
+    }
+    // behind the wait above: after every kernel that read the previous block
+    RoisPrepArgs p;
+    memset(&p, 0, sizeof(p));
+    p.blk = c->roi_blk; p.boxes = d_boxes; p.count = d_count; p.results = d_results;
+    p.capacity = capacity; p.box_format = box_format;
+    p.pw = c->sp.width - f->crop[0] - f->crop[1]; p.ph = c->sp.height - f->crop[2] - f->crop[3]; p.mw = mw; p.mh = mh;
+    p.wd = sc->width; p.hd = sc->height; p.fit = rp->fit; p.filter = sc->filter; p.chroma_loc = f->chroma_loc;
+    p.capy = L.capy; p.capc = L.capc;
+    p.image_pitch = image_pitch;
+    p.tab = (uint32_t)L.tab; p.slot = (uint32_t)L.slot; p.mid_slot = (uint32_t)L.mid_slot;
+    for (int t = 0; t < 4; t++) { p.off_first[t] = L.off_first[t]; p.off_count[t] = L.off_count[t]; p.off_w[t] = L.off_w[t]; }
+    launch_rois_prepare(p, s);
+    RoisOutArgs a;
+    memset(&a, 0, sizeof(a));
+    scaled_common_args(c, pic, dra, f, sc, d_dst, a);
+    a.mid = c->sc_mid;
+    a.capy = L.capy; a.capc = L.capc;
+    a.blk = c->roi_blk; a.n = capacity;
+    for (int k = 0; k < 3; k++) a.padv[k] = rp->pad[k];
+    launch_output_rois(a, f->layout, f->dtype, mw, sc->height, s);
     HIPCHK(c, hipGetLastError());
     if (stream) {
         HIPCHK(c, hipEventRecord(c->odev_ev[1], s));      // the context's stream - and through it the next output call on any stream - does not touch the slot, the block or the intermediate before the kernels are done

@@ -502,7 +502,8 @@ struct __attribute__((aligned(16))) RoiDesc {
     int      mpy, mpc;
     uint32_t first[4], count[4], wt[4];      // byte offsets in the block of the tables 0 yl, 1 yc, 2 xl, 3 xc (laid out as ScaledOutArgs' are)
     int      stride[4];
-    int      pad_[3];
+    int      skip;                  // the device-box call (k_rois_prepare): 1 = an index at or above the count - pass 2 writes no element of the image
+    int      pad_[2];
 };
 static_assert(sizeof(RoiDesc) == 128, "RoiDesc must be 128 bytes");
 // ScaledOutArgs' picture, destination and conversion fields (y, u, v: the picture minus f->crop; dst, pitch, plane: of image 0; capy, capc: the widest of all
@@ -513,6 +514,25 @@ struct RoisOutArgs : ScaledOutArgs {
     float    padv[3];               // the pad value by output position, before the normalise (integer dtypes: the integer)
 };
 void launch_output_rois(const RoisOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s);
+// k_output_rois_dev.hip: the descriptor block of k_output_rois.hip made on the device from boxes in device memory (xgpu_pic_output_device_rois_dev, INTEGRATION.md
+// section 8f).  The block: `capacity` RoiDesc, then one slot of tap tables per box at tab + i * slot - table t's first[], count[] and weights at off_first[t],
+// off_count[t], off_w[t] inside it -, every size taken from the bounds alone (rois_dev_layout, xgpu_api.hip).
+struct RoisPrepArgs {
+    uint8_t *blk;
+    const void *boxes;              // capacity boxes of box_format
+    const int *count;               // live boxes, or NULL: capacity
+    xgpu_roi_result *results;       // or NULL
+    int      capacity, box_format;
+    int      pw, ph, mw, mh;        // the picture minus the crop; the bounds
+    int      wd, hd, fit, filter, chroma_loc;
+    int      capy, capc;            // what pass 2's LDS holds per row: a wider span makes the box XGPU_ROI_TOO_LARGE
+    size_t   image_pitch;
+    uint32_t tab, slot;             // bytes: where the slots start in the block, and one slot
+    uint32_t off_first[4], off_count[4], off_w[4];
+    uint32_t mid_slot;              // samples of the intermediate per box
+};
+void launch_rois_prepare(const RoisPrepArgs &a, hipStream_t s);
+void launch_test_scale_taps(int n_plane, int subsampling, int siting, int n_dst, int filter, int32_t *first, int32_t *count, int16_t *w, int w_stride, hipStream_t s);
 // k_output_yuv.hip (k_output_semiplanar): NV12 / P016 - xgpu_pic_output's samples, luma rows then rows of interleaved Cb Cr
 struct SemiPlanarArgs {
     const int16_t *y, *u, *v;       // first sample of the cropped area of every plane

@@ -10,11 +10,10 @@
 // The common factor of a row (1 / F, 1 / (2 D)) cancels in the normalisation: a row is its integer numerators u(i) > 0 over 0 <= i < n, their sum U, and
 //   q(i) = floor(u(i) 16384 / U + 1 / 2) = (2 u(i) 16384 + U) / (2 U) in integers;   16384 - sum q goes to the largest q (the first of equals).
 #include "xgpu_internal.h"
+#include "scale_taps.h"
 #include <algorithm>
 #include <cstring>
 #include <vector>
-
-static int64_t floor_div(int64_t a, int64_t b) { return a / b - ((a % b != 0) && ((a < 0) != (b < 0))); }      // b > 0
 
 int xgpu_scale_taps(int n_plane, int subsampling, int siting_half_luma, int n_dst, int filter, int32_t *first, int32_t *count, int16_t *w, int w_stride)
 {
@@ -23,50 +22,18 @@ int xgpu_scale_taps(int n_plane, int subsampling, int siting_half_luma, int n_ds
         !first || !count || (w && w_stride < 1))
         return XGPU_ERR_INVALID_ARGUMENT;
     if (N < 2 || N > 16384 || n * s > 64 * N || N > 8 * n * s) return XGPU_ERR_UNSUPPORTED;
-    const int64_t D = 2 * s * N, F = std::max(D, 2 * s * n);
-    std::vector<int64_t> u;
+    // the row itself is scale_taps.h's, which k_rois_prepare runs on the device as well
+    ScaleAxis ax;
+    scale_axis_init(ax, n_plane, subsampling, siting_half_luma, n_dst, filter);
     int widest = 0;
-    for (int64_t o = 0; o < N; o++) {
-        const int64_t C = (2 * o + 1) * n * s - (1 + h) * N;
-        // the samples that can have a positive weight: |i - c| < f (BILINEAR), |i - c| < (f + 1) / 2 (AREA) - one more on either side costs nothing
-        const int64_t reach = filter == XGPU_SCALE_BILINEAR ? F : (F + D + 1) / 2;
-        int64_t lo = std::max<int64_t>(floor_div(C - reach, D) - 1, 0), hi = std::min<int64_t>(floor_div(C + reach, D) + 1, n - 1);
-        u.clear();
-        int64_t i0 = 0, U = 0;
-        for (int64_t i = lo; i <= hi; i++) {
-            int64_t v;
-            if (filter == XGPU_SCALE_BILINEAR) {
-                const int64_t t = i * D - C;
-                v = F - (t < 0 ? -t : t);
-            } else {
-                v = std::min((2 * i + 1) * D, 2 * C + F) - std::max((2 * i - 1) * D, 2 * C - F);
-            }
-            if (v <= 0) { if (u.empty()) continue; else break; }      // the positive weights are contiguous
-            if (u.empty()) i0 = i;
-            u.push_back(v);
-            U += v;
-        }
-        if (u.empty()) {      // no sample of the plane under the window (a siting that moves the grid off the plane's end): the nearest sample alone
-            i0 = std::min<int64_t>(std::max<int64_t>(floor_div(2 * C + D, 2 * D), 0), n - 1);
-            u.push_back(1);
-            U = 1;
-        }
-        const int cnt = (int)u.size();
-        first[o] = (int32_t)i0;
+    for (int o = 0; o < n_dst; o++) {
+        int64_t U;
+        const int cnt = scale_tap_span(ax, o, &first[o], &U);
         count[o] = cnt;
         widest = std::max(widest, cnt);
         if (!w) continue;
         if (cnt > w_stride) return XGPU_ERR_INVALID_ARGUMENT;
-        int16_t *q = w + (size_t)o * w_stride;
-        int64_t sum = 0, best = 0;
-        for (int k = 0; k < cnt; k++) {
-            const int64_t v = (2 * u[k] * 16384 + U) / (2 * U);
-            q[k] = (int16_t)v;
-            sum += v;
-            if (v > q[best]) best = k;
-        }
-        q[best] = (int16_t)(q[best] + (16384 - sum));
-        for (int k = cnt; k < w_stride; k++) q[k] = 0;
+        scale_tap_weights(ax, o, first[o], cnt, U, w + (size_t)o * w_stride, 1, w_stride);
     }
     return widest;
 }

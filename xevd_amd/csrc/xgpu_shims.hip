@@ -96,3 +96,30 @@ int xgpu_test_itdq(xgpu_ctx *c, int16_t *coef, int n_blocks, int log2w, int log2
     return XGPU_OK;
 }
 
+
+// xgpu_scale_taps through the device's row builder (k_output_rois_dev.hip): the arguments are checked by the host function itself, which also says how wide
+// the widest row is; then one lane per row on the device, and the three arrays come back
+int xgpu_test_scale_taps_device(xgpu_ctx *c, int n_plane, int subsampling, int siting_half_luma, int n_dst, int filter, int32_t *first, int32_t *count, int16_t *w,
+                                int w_stride)
+{
+    ARGCHK(c, c != NULL);
+    const int widest = xgpu_scale_taps(n_plane, subsampling, siting_half_luma, n_dst, filter, first, count, NULL, 0);
+    if (widest < 0) return widest;
+    ARGCHK(c, !w || w_stride >= widest);
+    const size_t ib = sizeof(int32_t) * (size_t)n_dst, wb = w ? sizeof(int16_t) * (size_t)n_dst * w_stride : 0;
+    uint8_t *d = NULL;
+    HIPCHK(c, hipSetDevice(c->sp.device));
+    HIPCHK(c, hipMalloc((void **)&d, 2 * ib + wb + 16));
+    HIPCHK(c, hipMemsetAsync(d, 0xFF, 2 * ib + wb, c->stream));      // nothing of the host's pass survives in what is compared
+    int32_t *df = (int32_t *)d, *dc = df + n_dst;
+    int16_t *dw = w ? (int16_t *)(dc + n_dst) : NULL;
+    launch_test_scale_taps(n_plane, subsampling, siting_half_luma, n_dst, filter, df, dc, dw, w_stride, c->stream);
+    HIPCHK(c, hipMemcpyAsync(first, df, ib, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(count, dc, ib, hipMemcpyDeviceToHost, c->stream));
+    if (w) HIPCHK(c, hipMemcpyAsync(w, dw, wb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(d);
+    int wide = 0;
+    for (int o = 0; o < n_dst; o++) wide = count[o] > wide ? count[o] : wide;
+    return wide;
+}

@@ -110,7 +110,7 @@ class XgpuDecoder:
 
     def pic_output_tensor(self, pic, layout="rgb", channels_last=False, dtype=None, matrix=1, full_range=False, chroma_loc=0, upsample="linear",
                           crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, out_bit_depth=0, colour=None, size=None, filter="bilinear", mean=None, std=None,
-                          rois=None, fit="stretch", pad=0.0, snap=False):
+                          rois=None, fit="stretch", pad=0.0, snap=False, count=None, max_roi=None, results=False):
         """The picture in device memory as a torch tensor on cuda:{device}, converted on the device (xgpu_pic_output_device) on torch's current
         stream - no host round trip.  layout "rgb": [3, H, W] (channels_last: [H, W, 3]) R'G'B' (bgr: B, G, R) with dtype torch.uint8, torch.int16 /
         torch.uint16 (values at the coding depth), torch.float16, torch.bfloat16 or torch.float32 (0..1), through `matrix` (H.273 MatrixCoefficients
@@ -135,15 +135,29 @@ class XgpuDecoder:
         rectangle i gives.  fit "stretch", or "letterbox": the rectangle keeps its shape inside the image (abi.roi_inner says where) and the rest is `pad` - one
         value or three, in the output's channel order, before the normalise; integers for the integer dtypes.  snap=True rounds odd rectangles outward to even
         and clamps them to the picture; otherwise such a rectangle raises ValueError.  out: any tensor of that shape whose images are laid out as size= lays
-        out its one image, a batch stride apart."""
+        out its one image, a batch stride apart.
+        rois=<torch tensor on the decoder's device> (with size=): the boxes a detector left on the GPU, read there (xgpu_pic_output_device_rois_dev, INTEGRATION.md
+        section 8f) - int32 [N, 4] (x, y, w, h) or float32 [N, 4] (x1, y1, x2, y2), contiguous; no host read, no synchronisation.  Every box is snapped outward to
+        even and into the picture (abi.roi_snap restates the rule); image i is what rois=[used_i] gives.  count=<int32 tensor of one element>: the first
+        min(max(count, 0), N) boxes are live, the images of the others are not touched.  max_roi=(H, W): the largest snapped box the call is sized for (default: the
+        picture minus the crop).  A box that cannot be served - a non-finite coordinate, empty after snapping, larger than max_roi, a ratio outside the scaled
+        output's limits - gives an image that is all `pad` (so pad is checked for either fit).  results=True returns (images, results): results int32 [N, 9] =
+        status (abi.ROI_OK, ROI_UNUSED, ROI_INVALID, ROI_EMPTY, ROI_TOO_LARGE, ROI_RATIO), the box used (x, y, w, h), its inner part (abi.roi_inner)."""
         import torch
         if rois is not None:
             if size is None:
                 raise ValueError("rois: the batch of rectangles needs size=(H, W)")
+            if isinstance(rois, torch.Tensor):
+                if snap:
+                    raise ValueError("snap: boxes in device memory are always snapped")
+                return self._pic_output_tensor_rois_dev(pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour,
+                                                        size, filter, mean, std, rois, fit, pad, count, max_roi, results)
+            if count is not None or max_roi is not None or results:
+                raise ValueError("count, max_roi and results belong to rois=<tensor on the device>")
             return self._pic_output_tensor_rois(pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour,
                                                 size, filter, mean, std, rois, fit, pad, snap)
-        if fit != "stretch" or snap or np.any(np.asarray(pad) != 0):
-            raise ValueError("fit, pad and snap belong to rois=")
+        if fit != "stretch" or snap or np.any(np.asarray(pad) != 0) or count is not None or max_roi is not None or results:
+            raise ValueError("fit, pad, snap, count, max_roi and results belong to rois=")
         if size is not None:
             return self._pic_output_tensor_scaled(pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour,
                                                   size, filter, mean, std)
@@ -330,6 +344,56 @@ class XgpuDecoder:
         if run is not cur:
             cur.wait_stream(run)
         return out
+
+    def _pic_output_tensor_rois_dev(self, pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour, size, filter,
+                                    mean, std, rois, fit, pad, count, max_roi, results):
+        """pic_output_tensor with size=(H, W) and rois=<tensor on the device>"""
+        import torch
+        if colour is not None:
+            raise ValueError("rois: the batch of rectangles takes no colour transform")
+        if fit not in ("stretch", "letterbox"):
+            raise ValueError(f"fit must be 'stretch' or 'letterbox', not {fit!r}")
+        dtype, fmt, sc, h, w, dev = self._scaled_setup(layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, bgr, out_bit_depth, colour, size, filter,
+                                                       mean, std)
+        if rois.device != dev or rois.dtype not in (torch.int32, torch.float32) or rois.dim() != 2 or rois.shape[1] != 4 or not rois.is_contiguous():
+            raise ValueError(f"rois: a contiguous int32 (x, y, w, h) or float32 (x1, y1, x2, y2) tensor [N, 4] on {dev}, not {tuple(rois.shape)} {rois.dtype} on "
+                             f"{rois.device}{'' if rois.is_contiguous() else ', not contiguous'}")
+        if count is not None and (not isinstance(count, torch.Tensor) or count.device != dev or count.dtype != torch.int32 or count.numel() != 1):
+            raise ValueError(f"count: an int32 tensor of one element on {dev}")
+        n = int(rois.shape[0])
+        box_format = abi.BOX_XYWH_I32 if rois.dtype == torch.int32 else abi.BOX_XYXY_F32
+        rp = abi.make_roi_params(abi.FIT_LETTERBOX if fit == "letterbox" else abi.FIT_STRETCH, pad)
+        bounds = abi.make_roi_bounds(max_roi)
+        shape = (n, h, w, 3) if channels_last else (n, 3, h, w)
+
+        def refuse():
+            rc = self.lib.xgpu_output_rois_dev_check(C.byref(fmt), C.byref(sc), C.byref(rp), C.byref(bounds), box_format, n, self.width, self.height, self.bit_depth)
+            if rc < 0:
+                raise ValueError(f"invalid batch of boxes ({rc}): layout {layout}, size {tuple(size)}, fit {fit}, pad {pad}, crop {crop}, mean {mean}, std {std}, "
+                                 f"max_roi {max_roi}, {n} boxes")
+        if out is None:
+            refuse()
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
+            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+        st = out.stride()
+        pitch = st[1] if channels_last else st[2]          # elements between rows
+        if (channels_last and st[2:] != (3, 1)) or (not channels_last and (st[3] != 1 or st[1] != pitch * h)) or pitch < (3 * w if channels_last else w):
+            raise ValueError(f"out: strides {st} are not rows of {'W x 3' if channels_last else 'W'} elements {'' if channels_last else 'in planes of H rows '}")
+        fmt.row_pitch = pitch * dtype.itemsize
+        rp.image_pitch = st[0] * dtype.itemsize if n > 1 else 0
+        refuse()
+        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
+        nbytes = (sum((k - 1) * s for k, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
+        cur, run = self._run_stream(dev)
+        res = torch.empty((n, 9), dtype=torch.int32, device=dev) if results else None
+        self._chk(self.lib.xgpu_pic_output_device_rois_dev(self.ctx, pic, dl, C.byref(fmt), C.byref(sc), C.byref(rp), C.byref(bounds), box_format,
+                                                           C.c_void_p(rois.data_ptr()), n, C.c_void_p(count.data_ptr()) if count is not None else None,
+                                                           C.c_void_p(res.data_ptr()) if results else None, C.c_void_p(out.data_ptr()), nbytes,
+                                                           C.c_void_p(run.cuda_stream)), "xgpu_pic_output_device_rois_dev")
+        if run is not cur:
+            cur.wait_stream(run)
+        return (out, res) if results else out
 
     def _run_stream(self, dev):
         """(torch's current stream, the stream a kernel of the C ABI is queued on): torch's default stream is the null stream, whose handle (0) means "the

@@ -115,7 +115,9 @@ class StreamDecoder:
         size / mean / std; tensor=dict(filter="area") for the box filter) - what a model takes, without a full-size tensor in between
         rois=[(x, y, w, h), ...] or a callable(params) -> such a list (with tensor= and size=; called behind the picture's kernels, so params["side_info"] is
         there when side= is given), fit=, pad=: every picture as the batch [N, 3, H, W] of its rectangles (pic_output_tensor's rois / fit / pad;
-        tensor=dict(snap=True) for boxes a detector made)"""
+        tensor=dict(snap=True) for boxes a detector made).  The list, or what the callable returns, may also be a torch tensor on the decoder's device - int32
+        [N, 4] xywh or float32 [N, 4] xyxy, a detector's boxes where it left them: they are read on the device, with no host read in between
+        (pic_output_tensor's rois=<tensor>; tensor=dict(count=, max_roi=) go with it)"""
         if to is not None and tensor is None:
             raise ValueError("to: needs tensor=dict(...)")
         if (size is not None or mean is not None or std is not None) and tensor is None:
@@ -217,7 +219,8 @@ class StreamDecoder:
             if p["is_idr"]:
                 epoch += 1
             if tensor is not None:
-                planes = planes.cpu().numpy()      # (synchronises torch's current stream: the slot's tensor is complete)
+                # (synchronises torch's current stream: the slot's tensor is complete); device boxes with results=True: the pair, both as arrays
+                planes = tuple(t.cpu().numpy() for t in planes) if isinstance(planes, tuple) else planes.cpu().numpy()
             if side is not None:
                 p["side_info"] = p["side_info"].cpu().numpy()
             p["decode_index"] = len(out)       # place in decoding order
