@@ -20,6 +20,7 @@
  *   xgpu_pic_output               <- xevd_pull + the application's imgb_cpy_codec_to_out (crop fields xevd.c:2058-2069,
  *                                    bit-depth conversions app/xevd_app_util.h:441-552,656-700)
  *   xgpu_pic_output_device        (no counterpart: the picture as YUV or R'G'B' into the caller's device memory)
+ *   xgpu_batch_residual           (no counterpart in the library: the prediction residual of a picture - what the reconstruction adds to the prediction - as dense planes)
  *   xgpu_frame_side_info          (no counterpart in the library; FFmpeg's export_mvs is the usual example: motion vectors, modes, QP of the picture decoded last)
  *
  * plus fine-grained shims with the reference's per-block function-table signatures
@@ -486,6 +487,44 @@ size_t xgpu_side_info_size(const xgpu_side_format *f, int width, int height);
    xgpu_side_info_size bytes (checked before anything is queued); stream = NULL: the context's stream; else the kernel runs on `stream` behind the picture's
    kernels, and the context's stream waits for it before the next picture may write the map.  Reads the map only: the picture is not touched. */
 int    xgpu_frame_side_info(xgpu_ctx *ctx, int pic, const xgpu_side_format *f, void *d_dst, size_t dst_size, void *stream);
+/* ---- the prediction residual (k_residual.hip): the third product of a decoder, next to the samples and the side information.  The residual pass of a batch
+   (dequantisation + inverse transform) leaves its output in the batch's arena on the device, where the reconstruction kernels add it to the prediction; this
+   call writes it out as dense, picture-shaped planes.  r(c, x, y) is the s16 the arena holds for component c at picture position (x, y) - exactly what is
+   added before the clip - and 0 where nothing is coded: the CU's cbf bit of c is clear; the position lies outside the TU of an ATS-inter CU; it lies in a
+   64x64 sub-block of a CU above 64 whose cbf_sub bit is clear; no CU of the batch covers it (another tile's or slice's units).  Inside a local dual tree luma
+   comes from the luma-only CUs and chroma from the chroma-only CU that closes the tree.  Every element of the destination is written (zeros included): the
+   caller does not clear it.  Values are signed; dtype XGPU_OUT_U16 names the element size, as for XGPU_SIDE_BLOCKS.
+     XGPU_RESID_YUV420            int16 (XGPU_OUT_U16 only): Y h rows of w, then Cb and Cr h / 2 rows of w / 2 each - the plane order and tight layout of
+                                  xgpu_pic_output; row_pitch is the LUMA pitch (a multiple of 4), the chroma pitch is half of it, Cb starts at h * row_pitch,
+                                  Cr at h * row_pitch + (h / 2) * (row_pitch / 2)
+     XGPU_RESID_444_PLANAR        [3, h, w], plane k at k * h * row_pitch; _INTERLEAVED: [h, w, 3].  Chroma is replicated, c[(y + crop_top) >> 1][(x + crop_left) >> 1]
+                                  - no interpolation: a residual is not an image.  XGPU_OUT_U16: the s16; XGPU_OUT_F32: float32(r) * 2^-B with B the component's
+                                  bit depth (a power of two: every value is exact); XGPU_OUT_F16: that value rounded to nearest even (|r| * 2^-8 <= 128 fits)
+     XGPU_RESID_ENERGY            [3, h_scu, w_scu] float32 (XGPU_OUT_F32 only), crop must be 0: per 4x4 luma unit - the grid of XGPU_SIDE_BLOCKS - plane 0 the
+                                  sum of |r| over its 16 luma samples, planes 1 / 2 over its 2x2 Cb / Cr samples (integers <= 2^19: exact)
+   w x h: the picture minus crop (left, right, top, bottom luma samples, even).  The exact contract: INTEGRATION.md section 8g; tests/residual_ref.py restates it
+   in numpy. */
+#define XGPU_RESID_YUV420            0
+#define XGPU_RESID_444_PLANAR        1
+#define XGPU_RESID_444_INTERLEAVED   2
+#define XGPU_RESID_ENERGY            3
+typedef struct xgpu_resid_format {
+    int layout;        /* XGPU_RESID_* */
+    int dtype;         /* YUV420: XGPU_OUT_U16; 444: XGPU_OUT_U16 | _F16 | _F32; ENERGY: XGPU_OUT_F32 */
+    int crop[4];       /* left, right, top, bottom luma samples, even; ENERGY: all 0 */
+    size_t row_pitch;  /* bytes between rows, a multiple of the element size (YUV420: of 4); 0 = tight */
+} xgpu_resid_format;
+/* Host only, no context: the bytes format `f` needs at d_dst for a picture of width x height (the uncropped size, multiples of 8), the last row tight; 0:
+   invalid format or size.  YUV420: h * pitch + (h - 1) * (pitch / 2) + w; 444 planar: (3 h - 1) * pitch + w * es, interleaved: (h - 1) * pitch + 3 w * es;
+   ENERGY: (3 h_scu - 1) * pitch + 4 w_scu. */
+size_t xgpu_resid_size(const xgpu_resid_format *f, int width, int height);
+/* Non-blocking.  Valid from the moment the batch's residual pass is queued - xgpu_batch_recon(_ahead) of db, xgpu_batch_prepare(db), or db passed as `next`
+   of xgpu_batch_recon_ahead - until xgpu_batch_destroy(db); before that: XGPU_ERR_INVALID_ARGUMENT, nothing queued.  d_dst and stream as
+   xgpu_frame_side_info takes them: device memory of the context's device, aligned to the element size, >= xgpu_resid_size bytes (checked before anything is
+   queued); a destination, pitch and plane distance that are multiples of 16 bytes take vector stores.  stream = NULL: the context's stream; else the kernel
+   runs on `stream` behind the residual pass, and the context's stream waits for it, so the batch may be destroyed right after the call.  Reads the batch
+   only: neither the picture nor the SCU map is touched. */
+int    xgpu_batch_residual(xgpu_ctx *ctx, xgpu_dbatch *db, const xgpu_resid_format *f, void *d_dst, size_t dst_size, void *stream);
 /* The picture signature on the device: the MD5 of every plane over its rows of width x 2 bytes of 16-bit samples (8-bit pictures too), as xevd_md5_imgb makes it
    (src_base/xevd_util.c:985-1002) and xevd_picbuf_check_signature compares it with the SEI (:1557-1572) - of the DRA-mapped picture when `dra` is given, which is
    what the Main decoder signs when the PPS names a DRA parameter set (src_main/xevdm.c:3256-3287).  digest[plane] = the 16 bytes of the SEI payload.  Blocking; the

@@ -23,7 +23,12 @@ tensor, as a detector leaves them, and alternates - same protocol as the rois le
 and a read-back) and xgpu_pic_output_device_rois, with route B: the device-box call on the tensor itself, max_roi set to the true maxima of the workload.  The
 split of B into its three kernels is what rocprofv3 --kernel-trace --stats shows for `--legs rois_dev`.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev] [--out out/output_device.json]
+The residual leg (xgpu_batch_residual: k_resid_planes / k_resid_energy) writes the residual of a synthetic B-picture batch of the same size as int16 4:2:0
+planes, as 4:4:4 planar int16 and float16, and as the per-unit energy.  Bytes are algorithmic: the arena bytes actually coded (2 per sample of every coded
+component block), 4 per 4x4 unit of owner map, 32 per CU record, and what the form writes.  The whole measurement - copy rate included - is repeated --repeat
+times in the one process; every run is kept.
+
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|residual] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -214,6 +219,41 @@ def rois_dev_leg(torch, dec, pic, s, a, res):
         res["rois_dev"][name] = r
 
 
+def residual_leg(torch, dec, pic, s, a, res):
+    """the four residual forms on a decoded synthetic batch, --repeat runs, each with the copy rate measured next to it"""
+    from xevd_amd import synth
+    w, h, bd = a.width, a.height, a.bit_depth
+    batch = synth.gen_frame(np.random.default_rng(1), w, h, bd, inter_frac=0.9, bi_frac=0.5, coded_frac=0.6, n_refs=(1, 1), qp_range=(22, 37), mv_sigma_px=8.0, oob_frac=0.05)
+    area = (1 << batch["log2w"].astype(np.int64)) << batch["log2h"].astype(np.int64)
+    cbf = batch["cbf"].astype(np.int64)
+    coded = int((area * (cbf & 1) + (area // 4) * ((cbf >> 1) & 1) + (area // 4) * ((cbf >> 2) & 1)).sum()) * 2      # (no ATS-inter in this batch: whole-CU blocks)
+    n_units, n_cu = (w // 4) * (h // 4), len(cbf)
+    read = coded + 4 * n_units + 32 * n_cu
+    cur = dec.pic_alloc()
+    hb = dec.batch_create(batch)
+    dec.decode_picture(cur, 8, {(0, 0): (pic, 4), (0, 1): (pic, 16)}, hb, deblock=True)
+    dec.sync()
+    forms = [("resid_yuv420_s16", dict(kind="yuv420"), 3 * w * h),
+             ("resid_444_s16_planar", dict(kind="444", dtype=torch.int16), 6 * w * h),
+             ("resid_444_f16_planar", dict(kind="444", dtype=torch.float16), 6 * w * h),
+             ("resid_energy", dict(kind="energy"), 12 * n_units)]
+    res["residual"] = {"n_cu": n_cu, "coded_arena_bytes": coded, "owner_bytes": 4 * n_units, "record_bytes": 32 * n_cu, "runs": []}
+    for rep in range(a.repeat):
+        copy_gbps = dec.measure_copy_bw(1 << 30, 20)
+        run = {"copy_gbps": copy_gbps, "forms": {}}
+        for name, kw, wbytes in forms:
+            out = dec.batch_residual(hb, **kw)
+            out = out[0] if isinstance(out, tuple) else out
+            us = timed(torch, s, lambda: dec.batch_residual(hb, out=out, **kw), a.iters)
+            nbytes = int(read + wbytes)
+            gbps = nbytes / (us * 1e-6) / 1e9
+            run["forms"][name] = {"us": round(us, 2), "bytes": nbytes, "written": int(wbytes), "gbps": round(gbps, 1), "write_gbps": round(wbytes / (us * 1e-6) / 1e9, 1),
+                                  "frac_copy": round(gbps / copy_gbps, 3)}
+            print(f"run {rep} {name:24s} {us:9.1f} us  {nbytes / 1e6:7.1f} MB  {gbps:7.1f} GB/s  {gbps / copy_gbps:5.2f} of copy ({copy_gbps:.0f} GB/s)")
+        res["residual"]["runs"].append(run)
+    dec.batch_destroy(hb)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=7680)
@@ -221,9 +261,10 @@ def main():
     ap.add_argument("--bit-depth", type=int, default=10)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev"), default="all",
+    ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "residual"), default="all",
                     help="full: the full-size forms and the side information; scaled: the scaled leg alone; rois: the batched regions of interest alone; "
-                         "rois_dev: the regions of interest from boxes in device memory alone")
+                         "rois_dev: the regions of interest from boxes in device memory alone; residual: the residual export alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -263,6 +304,8 @@ def main():
             rois_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "rois_dev"):
             rois_dev_leg(torch, dec, pic, s, a, res)
+        if a.legs in ("all", "residual"):
+            residual_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "full"):
             for name, kw, wbytes in forms:
                 out = dec.pic_output_tensor(pic, **kw)

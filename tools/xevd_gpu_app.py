@@ -23,6 +23,8 @@ def main():
                     "StreamDecoder.COLOUR_PRESETS), converted on the device from the primaries / transfer characteristics of the stream's VUI")
     ap.add_argument("--side-info", default=None, metavar="FILE", help="also write the coding side information of every picture, in DECODING order: a text line "
                     "'POC h_scu w_scu', then nine planes of h_scu x w_scu little-endian int16 (list 0 / 1 vectors, POC distances, mode, QP, flags: INTEGRATION.md 8c)")
+    ap.add_argument("--residual", default=None, metavar="FILE", help="also write the prediction residual of every picture, in DECODING order: a text line "
+                    "'POC w h', then the little-endian int16 planes Y (h x w), Cb, Cr (h/2 x w/2 each) of the uncropped picture (INTEGRATION.md 8g)")
     ap.add_argument("--size", default=None, metavar="WxH", help="write interleaved 8-bit RGB frames resized to W x H on the device instead (antialiased bilinear, "
                     "the matrix / range / chroma siting of the stream's VUI: INTEGRATION.md 8d); with --to: not supported")
     ap.add_argument("--tiles", default=None, metavar="WxH", help="with --size: every picture as its grid of W x H tiles (the last column / row moved back inside the "
@@ -34,6 +36,7 @@ def main():
     data = open(args.input, "rb").read()
     t0 = time.perf_counter()
     side = {} if args.side_info else None
+    resid = {} if args.residual else None
     # crop-free output like the reference application; bit-depth conversion and plane packing run on the device (xgpu_pic_output)
     if args.size is not None:
         import torch
@@ -51,16 +54,16 @@ def main():
             except ValueError:
                 ap.error(f"--tiles: expected WxH, not {args.tiles!r}")
             rois = lambda p: abi.tile_rois(p["width"], p["height"], tw, th)      # noqa: E731
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois, residual=resid)
     elif args.to is not None:
         import torch
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid)
     elif args.pix_fmt == "yuv420p":
-        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side)
+        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side, residual=resid)
     else:      # the same pictures as semi-planar surfaces (xgpu_pic_output_device into a torch tensor, copied to the host picture by picture)
         import torch
         opts = dict(layout="nv12", dtype=torch.uint8) if args.pix_fmt == "nv12" else dict(layout="p016", dtype=torch.int16, out_bit_depth=10)
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid)
     dt = time.perf_counter() - t0
     if args.output:
         with open(args.output, "wb") as f:
@@ -72,6 +75,12 @@ def main():
                 b = p["side_info"]
                 f.write(f"{p['poc']} {b.shape[1]} {b.shape[2]}\n".encode())
                 f.write(b.astype("<i2").tobytes())
+    if args.residual:
+        with open(args.residual, "wb") as f:
+            for p, _ in sorted(pics, key=lambda t: t[0]["decode_index"]):
+                flat, (y, _, _) = p["residual"]
+                f.write(f"{p['poc']} {y.shape[1]} {y.shape[0]}\n".encode())
+                f.write(flat.astype("<i2").tobytes())
     print(f"{len(pics)} pictures, {len(pics) / dt:.1f} pictures/s (parse + upload + kernels + download)", file=sys.stderr)
 
 

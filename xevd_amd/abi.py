@@ -75,6 +75,24 @@ def make_side_format(layout=SIDE_BLOCKS, dtype=OUT_U16, lists=3, per_poc=False, 
     return f
 
 
+RESID_YUV420, RESID_444_PLANAR, RESID_444_INTERLEAVED, RESID_ENERGY = 0, 1, 2, 3
+
+
+class ResidFormat(C.Structure):
+    _fields_ = [("layout", C.c_int), ("dtype", C.c_int), ("crop", C.c_int * 4), ("row_pitch", C.c_size_t)]
+
+
+def make_resid_format(layout=RESID_YUV420, dtype=OUT_U16, crop=(0, 0, 0, 0), row_pitch=0):
+    """xgpu_resid_format (include/xevd_hip.h): YUV420 - int16 planes Y, Cb, Cr (dtype OUT_U16); 444 planar / interleaved - OUT_U16 / OUT_F16 / OUT_F32, chroma
+    replicated; ENERGY - sum |r| per 4x4 luma unit and component, OUT_F32, no crop"""
+    f = ResidFormat()
+    f.layout, f.dtype = int(layout), int(dtype)
+    for i in range(4):
+        f.crop[i] = int(crop[i])
+    f.row_pitch = int(row_pitch)
+    return f
+
+
 SCALE_BILINEAR, SCALE_AREA = 0, 1
 
 
@@ -423,6 +441,8 @@ _EXPORTS = {
                                                   C.POINTER(RoiBounds), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_side_info_size": (C.c_size_t, [C.POINTER(SideFormat), C.c_int, C.c_int]),
     "xgpu_frame_side_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SideFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_resid_size": (C.c_size_t, [C.POINTER(ResidFormat), C.c_int, C.c_int]),
+    "xgpu_batch_residual": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ResidFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "xgpu_host_free": (None, [C.c_void_p, C.c_void_p]),
     "xgpu_batch_wait_upload": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -212,7 +212,7 @@ void xgpu_close(xgpu_ctx *c)
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     for (auto &p : c->pics) if (p.base) (void)hipFree(p.base);
     if (c->d_maps) (void)hipFree(c->d_maps);
-    for (BatchBlock &k : c->pool) { (void)hipFree(k.d_base); (void)hipHostFree(k.h_stage); (void)hipEventDestroy(k.uploaded); (void)hipEventDestroy(k.done); (void)hipEventDestroy(k.itdq_done); }
+    for (BatchBlock &k : c->pool) { (void)hipFree(k.d_base); (void)hipHostFree(k.h_stage); (void)hipEventDestroy(k.uploaded); (void)hipEventDestroy(k.done); (void)hipEventDestroy(k.itdq_done); if (k.d_chroma) (void)hipFree(k.d_chroma); }
     for (auto &h : c->pinned) (void)hipHostFree(h.p);
     c->pinned.clear();
     c->pool.clear();
@@ -1313,6 +1313,110 @@ int xgpu_frame_side_info(xgpu_ctx *c, int pic, const xgpu_side_format *f, void *
     HIPCHK(c, hipGetLastError());
     if (stream) {
         HIPCHK(c, hipEventRecord(c->odev_ev[1], s));      // the context's stream does not let the next picture's k_inter write the map before the kernel is done
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->odev_ev[1], 0));
+    }
+    return XGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the residual of a batch as picture-shaped planes
+// the format alone and the size it needs for a picture of width x height; 0: invalid, `why` says which field
+static size_t resid_size(const xgpu_resid_format *f, int width, int height, const char **why)
+{
+    *why = "format is NULL";
+    if (!f) return 0;
+    *why = "picture size must be positive multiples of 8";
+    if (width <= 0 || height <= 0 || ((width | height) & 7)) return 0;
+    *why = "crop offsets must be even and >= 0";
+    for (int i = 0; i < 4; i++) if (f->crop[i] < 0 || (f->crop[i] & 1)) return 0;
+    if (f->layout == XGPU_RESID_ENERGY) {
+        *why = "ENERGY: dtype XGPU_OUT_F32, no crop, row_pitch a multiple of 4 and at least a row";
+        if (f->dtype != XGPU_OUT_F32 || f->crop[0] || f->crop[1] || f->crop[2] || f->crop[3] || (f->row_pitch & 3)) return 0;
+        const size_t w_scu = width >> 2, h_scu = height >> 2, row = w_scu * 4, pitch = f->row_pitch ? f->row_pitch : row;
+        if (pitch < row) return 0;
+        return (3 * h_scu - 1) * pitch + row;
+    }
+    *why = "layout must be XGPU_RESID_YUV420, XGPU_RESID_444_PLANAR, XGPU_RESID_444_INTERLEAVED or XGPU_RESID_ENERGY";
+    if (f->layout != XGPU_RESID_YUV420 && f->layout != XGPU_RESID_444_PLANAR && f->layout != XGPU_RESID_444_INTERLEAVED) return 0;
+    *why = "crop leaves no picture";
+    if (f->crop[0] + f->crop[1] >= width || f->crop[2] + f->crop[3] >= height) return 0;
+    const size_t w = width - f->crop[0] - f->crop[1], h = height - f->crop[2] - f->crop[3];
+    if (f->layout == XGPU_RESID_YUV420) {
+        *why = "YUV420: dtype XGPU_OUT_U16 (int16 planes), row_pitch a multiple of 4 (the chroma pitch is half of it) and at least a row";
+        if (f->dtype != XGPU_OUT_U16 || (f->row_pitch & 3)) return 0;
+        const size_t row = w * 2, pitch = f->row_pitch ? f->row_pitch : row;
+        if (pitch < row) return 0;
+        return h * pitch + (h - 1) * (pitch / 2) + row / 2;      // Y: h rows; Cb, Cr: h / 2 rows of pitch / 2 each, the last one tight
+    }
+    *why = "444: dtype XGPU_OUT_U16, XGPU_OUT_F16 or XGPU_OUT_F32, row_pitch a multiple of the element size";
+    if (f->dtype != XGPU_OUT_U16 && f->dtype != XGPU_OUT_F16 && f->dtype != XGPU_OUT_F32) return 0;
+    const size_t es = (size_t)elem_size(f->dtype);
+    if (f->row_pitch % es) return 0;
+    const bool planar = f->layout == XGPU_RESID_444_PLANAR;
+    const size_t row = (planar ? w : 3 * w) * es, pitch = f->row_pitch ? f->row_pitch : row;
+    *why = "row_pitch is shorter than a row";
+    if (pitch < row) return 0;
+    return ((planar ? 3 * h : h) - 1) * pitch + row;
+}
+size_t xgpu_resid_size(const xgpu_resid_format *f, int width, int height)
+{
+    const char *why;
+    return resid_size(f, width, height, &why);
+}
+// The arena belongs to the batch: it holds the residual from the batch's residual pass (k_itdq, or the pass that rode in the previous picture's k_intra_itdq)
+// until the batch is destroyed.  Checks first, then the order of output_device.  The pass ran on the context's stream - or, after xgpu_batch_prepare, on the
+// side stream, and blk.itdq_done says when - so the kernel starts behind an event of the context's stream (and behind itdq_done), and the context's stream
+// waits for the kernel: xgpu_batch_destroy records blk.done there, so a block that goes back to the pool is not refilled under the kernel.
+int xgpu_batch_residual(xgpu_ctx *c, xgpu_dbatch *db, const xgpu_resid_format *f, void *d_dst, size_t dst_size, void *stream)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, db != NULL); ARGCHK(c, d_dst != NULL);
+    if (!db->used && !db->prepared) {
+        snprintf(c->err, sizeof(c->err), "batch_residual: the residual pass of this batch has not been queued: call xgpu_batch_recon(_ahead) of it, xgpu_batch_prepare, or pass it as `next` of xgpu_batch_recon_ahead first");
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    const char *why = "";
+    const size_t need = resid_size(f, c->sp.width, c->sp.height, &why);
+    if (need == 0) { snprintf(c->err, sizeof(c->err), "batch_residual: invalid format: %s", why); return XGPU_ERR_INVALID_ARGUMENT; }
+    const size_t es = (size_t)elem_size(f->dtype);
+    if (dst_size < need || ((uintptr_t)d_dst % es)) {
+        snprintf(c->err, sizeof(c->err), "batch_residual: destination of %zu bytes at %p, the format needs %zu bytes aligned to %zu", dst_size, d_dst, need, es);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    { const int rc = check_device_dst(c, "batch_residual", d_dst, need); if (rc < 0) return rc; }
+    hipStream_t s = c->stream;
+    if (stream) {
+        for (int i = 0; i < 2; i++)
+            if (!c->odev_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->odev_ev[i], hipEventDisableTiming));
+        s = (hipStream_t)stream;
+        HIPCHK(c, hipEventRecord(c->odev_ev[0], c->stream));      // the residual pass (and the batch's upload, which the context's stream has waited for) -> the caller's stream
+        HIPCHK(c, hipStreamWaitEvent(s, c->odev_ev[0], 0));
+    }
+    if (db->prepared == 1) HIPCHK(c, hipStreamWaitEvent(s, db->blk.itdq_done, 0));      // the pass is on the side stream (behind the upload)
+    ResidArgs a;
+    memset(&a, 0, sizeof(a));
+    a.owner = db->d_owner; a.cus = db->d_cus; a.resid = db->d_resid; a.w_scu = c->w_scu; a.h_scu = c->h_scu;
+    a.chroma_cus = db->d_chroma_cus; a.n_chroma_cus = db->n_chroma_cus;
+    a.dst = (uint8_t *)d_dst;
+    a.scale[0] = 1.0f / (float)(1 << c->sp.bit_depth_luma); a.scale[1] = a.scale[2] = 1.0f / (float)(1 << c->sp.bit_depth_chroma);
+    a.w = c->sp.width - f->crop[0] - f->crop[1]; a.h = c->sp.height - f->crop[2] - f->crop[3];
+    a.crop_l = f->crop[0]; a.crop_t = f->crop[2];
+    if (f->layout == XGPU_RESID_ENERGY) {
+        a.pitch = f->row_pitch ? f->row_pitch : (size_t)c->w_scu * 4;
+        a.plane = a.pitch * c->h_scu;
+        a.aligned = (((uintptr_t)d_dst | a.pitch | a.plane) & 15) == 0;
+    } else if (f->layout == XGPU_RESID_YUV420) {
+        a.pitch = f->row_pitch ? f->row_pitch : (size_t)a.w * 2;
+        a.pitch_c = a.pitch / 2;
+        a.off_c[0] = a.pitch * a.h; a.off_c[1] = a.off_c[0] + a.pitch_c * (a.h / 2);
+        a.aligned = (((uintptr_t)d_dst | a.pitch) & 15) == 0;      // then the chroma rows (8-byte stores) start at multiples of 8
+    } else {
+        a.pitch = f->row_pitch ? f->row_pitch : (size_t)a.w * es * (f->layout == XGPU_RESID_444_PLANAR ? 1 : 3);
+        a.plane = a.pitch * a.h;
+        a.aligned = (((uintptr_t)d_dst | a.pitch | a.plane) & 15) == 0;
+    }
+    launch_residual(a, f->layout, f->dtype, s);
+    HIPCHK(c, hipGetLastError());
+    if (stream) {
+        HIPCHK(c, hipEventRecord(c->odev_ev[1], s));      // the context's stream - where xgpu_batch_destroy records blk.done - does not pass the kernel
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->odev_ev[1], 0));
     }
     return XGPU_OK;

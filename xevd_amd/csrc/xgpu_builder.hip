@@ -692,6 +692,17 @@ static int batch_build(xgpu_ctx *c, const xgpu_cu_batch *b, xgpu_dbatch **out, b
     const size_t o_coef = o_iwork + align_up((int)sz_iwork, 256);
     db->stage_bytes = o_coef + sz_coef;
     auto fail = [&](int code) { xgpu_batch_destroy(c, db); return code; };
+    // local dual trees: the chroma-only CUs that carry chroma coefficients, for xgpu_batch_residual (the owner map names the luma CUs).  Kept by the batch
+    // object, not in the staging block
+    if (b->tree && !host_only) {
+        int nc = 0;
+        for (int i = 0; i < n; i++) nc += b->tree[i] == 2 && (b->cbf[i] & 6);
+        if (nc) {
+            db->h_chroma_cus = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)nc);
+            if (!db->h_chroma_cus) return fail(XGPU_ERR_OUT_OF_MEMORY);
+            for (int i = 0; i < n; i++) if (b->tree[i] == 2 && (b->cbf[i] & 6)) db->h_chroma_cus[db->n_chroma_cus++] = (uint32_t)i;
+        }
+    }
     // device layout: the uploaded arrays at the staging offsets, then the residual arena and the intra done flags
     const size_t sz_done = sizeof(uint32_t) * ((size_t)n_intra + 1);
     const size_t o_resid = align_up((int)(o_coef + sz_coef), 256), o_done = o_resid + align_up((int)sz_coef, 256);
@@ -732,6 +743,16 @@ static int batch_build(xgpu_ctx *c, const xgpu_cu_batch *b, xgpu_dbatch **out, b
             if (hipEventCreateWithFlags(&db->blk.done, hipEventDisableTiming) != hipSuccess) return fail(XGPU_ERR_UNEXPECTED);
             if (hipEventCreateWithFlags(&db->blk.itdq_done, hipEventDisableTiming) != hipSuccess) return fail(XGPU_ERR_UNEXPECTED);
         }
+    }
+    if (db->n_chroma_cus && !host_only) {
+        const size_t nb = sizeof(uint32_t) * (size_t)db->n_chroma_cus;
+        if (db->blk.chroma_cap < nb) {      // (a pooled block: hipFree waits for the kernels that read the old list)
+            if (db->blk.d_chroma) (void)hipFree(db->blk.d_chroma);
+            db->blk.d_chroma = NULL; db->blk.chroma_cap = 0;
+            if (hipMalloc((void **)&db->blk.d_chroma, nb + nb / 4) != hipSuccess) return fail(XGPU_ERR_OUT_OF_MEMORY);
+            db->blk.chroma_cap = nb + nb / 4;
+        }
+        db->d_chroma_cus = db->blk.d_chroma;
     }
     BT("block");
     db->h_stage = db->blk.h_stage;
@@ -870,6 +891,7 @@ static int batch_build(xgpu_ctx *c, const xgpu_cu_batch *b, xgpu_dbatch **out, b
     if (host_only) { *out = db; return XGPU_OK; }
     hipError_t e = hipMemcpyAsync(dbase, hs, coef_pinned ? o_coef : db->stage_bytes, hipMemcpyHostToDevice, c->up_stream);
     if (e == hipSuccess && coef_pinned) e = hipMemcpyAsync(dbase + o_coef, b->coef, sizeof(int16_t) * b->n_coef, hipMemcpyHostToDevice, c->up_stream);
+    if (e == hipSuccess && db->n_chroma_cus) e = hipMemcpyAsync(db->d_chroma_cus, db->h_chroma_cus, sizeof(uint32_t) * (size_t)db->n_chroma_cus, hipMemcpyHostToDevice, c->up_stream);
     if (e == hipSuccess) e = hipMemsetAsync(db->d_intra_done, 0, sz_done, c->up_stream);
     if (e == hipSuccess) e = hipMemsetAsync(db->d_resid, 0, sz_coef, c->up_stream);
     if (e == hipSuccess) e = hipEventRecord(db->blk.uploaded, c->up_stream);
@@ -916,6 +938,11 @@ int xgpu_test_build_batch(const xgpu_seq_params *sp, const xgpu_cu_batch *b, int
 void xgpu_batch_destroy(xgpu_ctx *c, xgpu_dbatch *db)
 {
     if (!db) return;
+    if (db->h_chroma_cus) {      // the list's upload reads it: the copy has left the host memory once `uploaded` has happened
+        if (db->blk.uploaded) (void)hipEventSynchronize(db->blk.uploaded);
+        free(db->h_chroma_cus);
+        db->h_chroma_cus = NULL;
+    }
     if (db->blk.h_stage && !db->blk.d_base && !db->blk.uploaded) { delete db; return; }      // a host-only build (xgpu_test_build_batch) that failed half way: the block is the shim's own
     // No synchronisation: kernels still queued on the context's stream keep reading the block; whoever reuses it makes the upload stream wait
     // for the `done` event those kernels signal, and the host waits for `uploaded` before it touches the staging block.
@@ -933,6 +960,7 @@ void xgpu_batch_destroy(xgpu_ctx *c, xgpu_dbatch *db)
         if (db->blk.uploaded) (void)hipEventDestroy(db->blk.uploaded);
         if (db->blk.done) (void)hipEventDestroy(db->blk.done);
         if (db->blk.itdq_done) (void)hipEventDestroy(db->blk.itdq_done);
+        if (db->blk.d_chroma) (void)hipFree(db->blk.d_chroma);
     }
     delete db;
 }

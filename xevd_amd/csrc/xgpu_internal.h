@@ -276,7 +276,8 @@ struct AlfArgs {
 // One device block + one pinned staging block of a batch.  xgpu_batch_destroy returns them to the context's pool instead of freeing:
 // hipMalloc / hipFree / hipHostMalloc synchronise the device and serialise across the threads of a process, which capped many-stream
 // decoding on one GPU (tools/bench_multistream.py) and cost a stream synchronisation per picture.
-struct BatchBlock { uint8_t *d_base; size_t d_cap; void *h_stage; size_t h_cap; hipEvent_t uploaded, done, itdq_done; };      // uploaded: the H2D copies have left the host memory; done: the reconstruction kernels have read the block
+struct BatchBlock { uint8_t *d_base; size_t d_cap; void *h_stage; size_t h_cap; hipEvent_t uploaded, done, itdq_done;      // uploaded: the H2D copies have left the host memory; done: the reconstruction kernels have read the block
+                    uint32_t *d_chroma; size_t chroma_cap; };      // the chroma-only CUs of a batch with local dual trees (xgpu_dbatch.d_chroma_cus): an allocation of its own, made for the first such batch and grown on demand
 
 struct xgpu_dbatch {
     BatchBlock blk;
@@ -314,6 +315,10 @@ struct xgpu_dbatch {
                                       // 2: it ran on the main stream with the previous picture (xgpu_batch_recon_ahead)
     int        upload_waited;         // the main stream already waits for blk.uploaded
     int        used;                  // kernels that read the block have been queued (xgpu_batch_recon, or a residual pass ahead)
+    // xgpu_batch_residual: the chroma-only CUs (local dual tree, tree == 2) that carry chroma coefficients, by batch index - the owner map names the luma CUs only.
+    // Not part of the staging block: the host's copy is freed with the batch, the device's lives in blk.d_chroma and is uploaded in front of blk.uploaded
+    uint32_t  *h_chroma_cus, *d_chroma_cus;
+    int        n_chroma_cus;
 };
 
 // the device block of the scaled output's tap tables, as the host laid it out: per table (0 yl, 1 yc, 2 xl, 3 xc) the byte offsets of first[], count[] and w[], the
@@ -560,6 +565,22 @@ struct SideArgs {
 };
 void launch_side_blocks(const SideArgs &a, hipStream_t s);
 void launch_side_flow(const SideArgs &a, bool planar, int dtype, int n_lists, hipStream_t s);
+// k_residual.hip: the residual arena of a batch as picture-shaped planes (xgpu_batch_residual)
+struct ResidArgs {
+    const uint32_t *owner;          // [h_scu * w_scu] CU of the batch over every 4x4 luma unit, 0xFFFFFFFF: none
+    const CuRec    *cus;
+    const int16_t  *resid;          // the arena: at least 8 samples, 256-byte aligned
+    int      w_scu, h_scu;
+    uint8_t *dst;
+    size_t   pitch, plane;          // bytes between rows / between the planes of 444 planar and ENERGY
+    size_t   off_c[2], pitch_c;     // YUV420: byte offsets of the Cb and Cr planes, bytes between their rows
+    int      aligned;               // dst, pitch and the plane distances allow the vector stores of every plane
+    int      w, h, crop_l, crop_t;  // the cropped size and where it starts in the picture
+    float    scale[3];              // float dtypes: 2^-B per component
+    const uint32_t *chroma_cus;     // the batch's chroma-only CUs with coded chroma (local dual tree)
+    int      n_chroma_cus;
+};
+void launch_residual(const ResidArgs &a, int layout, int dtype, hipStream_t s);
 void launch_md5(xgpu_ctx *c, hipStream_t s, const uint8_t *d_msg, int w, int h, uint32_t *d_digest);      // k_md5.hip: the three planes packed back to back at d_msg -> d_digest[3][4]
 void launch_test_mc(xgpu_ctx *c, const int16_t *plane, int stride, int ref_x, int ref_y, int has_dx, int has_dy,
                     int gmv_x, int gmv_y, int16_t *pred, int w, int h, int bd, int luma);

@@ -462,6 +462,68 @@ class XgpuDecoder:
             cur.wait_stream(run)
         return out
 
+    def batch_residual(self, h, kind="yuv420", dtype=None, channels_last=False, crop=(0, 0, 0, 0), out=None):
+        """The prediction residual of batch `h` - what the reconstruction adds to the prediction before the clip, 0 where nothing is coded - as a torch
+        tensor on cuda:{device}, on torch's current stream (xgpu_batch_residual).  Valid once the batch's residual pass is queued
+        (batch_recon / decode_picture of it, batch_prepare, or the batch passed as next_batch) and until batch_destroy, which may follow at once.
+        kind "yuv420": (flat, (Y, Cb, Cr)) - a flat torch.int16 tensor in the plane order and tight layout of pic_output, and its three views [H, W],
+        [H / 2, W / 2], [H / 2, W / 2]; kind "444": [3, H, W] (channels_last: [H, W, 3]) with chroma replicated, dtype torch.int16 (the default),
+        torch.float32 (r * 2^-bit_depth, exact) or torch.float16; kind "energy": [3, height / 4, width / 4] torch.float32, sum |r| per 4x4 luma unit and
+        component, crop must be 0.  crop (left, right, top, bottom), even.
+        out: a tensor to fill instead ("yuv420": the flat one, contiguous; else its strides may pad the rows); it is what is returned (for "yuv420": first)."""
+        import torch
+        cl, cr, ct, cb = (int(v) for v in crop)
+        dev = torch.device("cuda", self.sp.device)
+        h_, w_ = self.height - ct - cb, self.width - cl - cr
+        if kind == "yuv420":
+            if dtype not in (None, torch.int16):
+                raise ValueError("yuv420: dtype is torch.int16")
+            dtype = torch.int16
+            fmt = abi.make_resid_format(abi.RESID_YUV420, abi.OUT_U16, crop=crop)
+            shape, planar, rows_w = (h_ * w_ * 3 // 2,), None, 0
+        elif kind == "444":
+            dtype = torch.int16 if dtype is None else dtype
+            codes = {torch.int16: abi.OUT_U16, torch.float16: abi.OUT_F16, torch.float32: abi.OUT_F32}
+            if dtype not in codes:
+                raise ValueError(f"444: dtype torch.int16, torch.float16 or torch.float32, not {dtype}")
+            planar = not channels_last
+            shape, rows_w = ((3, h_, w_), w_) if planar else ((h_, w_, 3), 3 * w_)
+            fmt = abi.make_resid_format(abi.RESID_444_PLANAR if planar else abi.RESID_444_INTERLEAVED, codes[dtype], crop=crop)
+        elif kind == "energy":
+            if dtype not in (None, torch.float32):
+                raise ValueError("energy: dtype is torch.float32")
+            dtype = torch.float32
+            h_, w_ = self.height // 4, self.width // 4
+            shape, planar, rows_w = (3, h_, w_), True, w_
+            fmt = abi.make_resid_format(abi.RESID_ENERGY, abi.OUT_F32, crop=crop)
+        else:
+            raise ValueError(f"kind must be 'yuv420', '444' or 'energy', not {kind!r}")
+        if self.lib.xgpu_resid_size(C.byref(fmt), self.width, self.height) == 0:
+            raise ValueError(f"invalid residual format (kind {kind}, dtype {dtype}, crop {crop})")
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
+            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+        st = out.stride()
+        if planar is None:
+            if st != (1,):
+                raise ValueError("out: must be contiguous")
+        else:
+            pitch = st[1] if planar else st[0]          # elements between rows
+            if (planar and (st[2] != 1 or st[0] != pitch * h_)) or (not planar and st[1:] != (3, 1)) or pitch < rows_w:
+                raise ValueError(f"out: strides {st} are not rows of {rows_w} elements{' in planes of H rows' if planar else ''}")
+            fmt.row_pitch = pitch * dtype.itemsize
+        nbytes = (sum((n - 1) * s for n, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
+        cur, run = self._run_stream(dev)
+        self._chk(self.lib.xgpu_batch_residual(self.ctx, h, C.byref(fmt), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
+                  "xgpu_batch_residual")
+        if run is not cur:
+            cur.wait_stream(run)
+        if kind == "yuv420":
+            ny, nc = h_ * w_, (h_ // 2) * (w_ // 2)
+            return out, (out[:ny].view(h_, w_), out[ny:ny + nc].view(h_ // 2, w_ // 2), out[ny + nc:].view(h_ // 2, w_ // 2))
+        return out
+
     def pic_md5(self, pic, dra=None):
         """the picture signature made on the device (xgpu_pic_md5): [Y, U, V] digests of 16 bytes - the MD5 of every plane's 16-bit samples as the reference's
         xevd_md5_imgb makes it; with `dra` tables (as pic_output takes them) of the DRA-mapped picture"""

@@ -101,7 +101,8 @@ class StreamDecoder:
             cm[k] = v
         return cm
 
-    def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None):
+    def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
+                 residual=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -111,6 +112,9 @@ class StreamDecoder:
         side=dict(...) (keyword arguments of XgpuDecoder.frame_side_info, {} for the block planes): the coding side information of every picture - motion
         vectors, modes, QP - as a torch tensor under params["side_info"] (the yielded tuple keeps its shape), taken right behind the picture's kernels, before
         the next picture overwrites the map it is read from; kind "flow" defaults to the SPS crop when apply_crop is set
+        residual=dict(...) (keyword arguments of XgpuDecoder.batch_residual, {} for the int16 4:2:0 planes): the prediction residual of every picture under
+        params["residual"] - for kind "yuv420" the pair (flat tensor, (Y, Cb, Cr) views) -, taken before the picture's batch goes back to the pool; the crop
+        defaults to the SPS crop when apply_crop is set (kind "energy": no crop)
         size=(H, W), mean=, std= (with tensor=, layouts "rgb" / "yuv444"): every picture resized to H x W and normalised in the same call (pic_output_tensor's
         size / mean / std; tensor=dict(filter="area") for the box filter) - what a model takes, without a full-size tensor in between
         rois=[(x, y, w, h), ...] or a callable(params) -> such a list (with tensor= and size=; called behind the picture's kernels, so params["side_info"] is
@@ -145,6 +149,11 @@ class StreamDecoder:
                     if kw.get("kind") == "flow":
                         kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
                     p["side_info"] = dec.frame_side_info(cur, **kw)
+                if residual is not None:       # the arena is the batch's: before batch_destroy
+                    kw = dict(residual)
+                    if kw.get("kind", "yuv420") != "energy":
+                        kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
+                    p["residual"] = dec.batch_residual(hb, **kw)
                 if p["n_dmvr_sub"]:
                     p["_dmvr"][1] = dec.batch_dmvr_mvs(hb)
                     p["_dmvr"][0].set()
@@ -210,12 +219,14 @@ class StreamDecoder:
                 self._dec.close()
                 self._dec = None
 
-    def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None):
+    def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
-        side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too"""
+        side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
+        params["residual"] as numpy - for kind "yuv420" the pair (flat array, (Y, Cb, Cr) views of it)"""
         out, epoch = [], -1
-        for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad):
+        for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
+                                       residual=residual):
             if p["is_idr"]:
                 epoch += 1
             if tensor is not None:
@@ -223,6 +234,15 @@ class StreamDecoder:
                 planes = tuple(t.cpu().numpy() for t in planes) if isinstance(planes, tuple) else planes.cpu().numpy()
             if side is not None:
                 p["side_info"] = p["side_info"].cpu().numpy()
+            if residual is not None:
+                r = p["residual"]
+                if isinstance(r, tuple):      # kind "yuv420": the views again, over the host copy
+                    flat = r[0].cpu().numpy()
+                    ny, (hc, wc) = r[1][0].numel(), r[1][1].shape
+                    r = (flat, (flat[:ny].reshape(r[1][0].shape), flat[ny:ny + hc * wc].reshape(hc, wc), flat[ny + hc * wc:].reshape(hc, wc)))
+                else:
+                    r = r.cpu().numpy()
+                p["residual"] = r
             p["decode_index"] = len(out)       # place in decoding order
             out.append(((epoch, p["poc"]), p, planes))
         return [(p, planes) for _, p, planes in sorted(out, key=lambda t: t[0])]
