@@ -1,5 +1,6 @@
-// xgpu_host.h - what the host-side translation units of the backend share (xgpu_api.hip: context, pictures, output; xgpu_builder.hip: the batch builder and its
-// dependency plan; xgpu_launch.hip: the per-picture launch sequencing; xgpu_shims.hip: the fine-grained test shims).  Private to xevd_amd/csrc.
+// xgpu_host.h - what the host-side translation units of the backend share (xgpu_api.hip: context, pictures, output into host memory; xgpu_output.hip: the outputs
+// into device memory; xgpu_builder.hip: the batch builder and its dependency plan; xgpu_launch.hip: the per-picture launch sequencing; xgpu_shims.hip: the
+// fine-grained test shims).  Private to xevd_amd/csrc.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -41,6 +42,10 @@ void time_end(xgpu_ctx *c, int k, hipEvent_t a, hipEvent_t b);
         time_end(c, k, ta_, tb_);              \
     } while (0)
 
+// the DRA post-filter's inverse tables of an output call (xgpu_api.hip): what upload_dra refuses, and the upload to c->d_dra on the context's stream
+// (hidden: shared by two files of the library, not a name it exports)
+__attribute__((visibility("hidden"))) int check_dra(xgpu_ctx *c, const xgpu_dra_luts *dra);
+__attribute__((visibility("hidden"))) int upload_dra(xgpu_ctx *c, const xgpu_dra_luts *dra);
 
 // xgpu_tile_grid -> TileMask; false: not a partition of the picture's CTU grid
 inline bool tile_mask(const xgpu_ctx *c, const xgpu_tile_grid *g, TileMask &m)

@@ -11,6 +11,43 @@ import numpy as np
 from . import abi
 
 
+_DTYPE_CODES = {}      # accepted names -> {torch dtype: XGPU_OUT_* code}; each subset is made at its first use, because torch is imported inside the methods
+
+
+def _codes(*names):
+    """the torch dtypes an output accepts -> their XGPU_OUT_* codes: those called `names` in torch, or - no names - all of them (uint16 where torch has it)"""
+    codes = _DTYPE_CODES.get(names)
+    if codes is None:
+        import torch
+        every = {"uint8": abi.OUT_U8, "int16": abi.OUT_U16, "uint16": abi.OUT_U16, "float16": abi.OUT_F16, "bfloat16": abi.OUT_BF16, "float32": abi.OUT_F32}
+        codes = _DTYPE_CODES[names] = {getattr(torch, n): every[n] for n in (names or every) if getattr(torch, n, None) is not None}
+    return codes
+
+
+def _out_tensor(out, shape, dtype, dev):
+    """the tensor an output fills: `out` if it has that shape, dtype and device, a new one for None"""
+    if out is None:
+        import torch
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    if out.device != dev or out.dtype != dtype or out.shape != tuple(shape):
+        raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    return out
+
+
+_IMAGE_ROWS = ("W x 3 elements ", "W elements in planes of H rows ")      # how _row_pitch names the rows of an [h, W, 3] / [3, h, W] image
+
+
+def _row_pitch(st, planar, h, row, last, what=None):
+    """The elements between two rows of a tensor with strides st whose last three dimensions are planes [C, h, W] (planar: dense rows of `row` elements, planes of h
+    rows) or pixels [h, W, last] (rows of `row` = W * last elements); a leading image stride (a batch) is free.  `what`: how the ValueError names such rows
+    (None: as the rows of an image of the picture outputs)."""
+    s = st[-3:]
+    pitch = s[1] if planar else s[0]
+    if (planar and (s[2] != 1 or s[0] != pitch * h)) or (not planar and s[1:] != (last, 1)) or pitch < row:
+        raise ValueError(f"out: strides {st} are not rows of {what or _IMAGE_ROWS[planar]}")
+    return pitch
+
+
 class XgpuError(RuntimeError):
     pass
 
@@ -85,14 +122,7 @@ class XgpuDecoder:
         if n == 0:
             raise ValueError(f"invalid output format: bit depth {bd}, crop {crop}")
         out = np.empty(n, np.uint8)
-        dl, keep = None, None
-        if dra is not None:
-            keep = [np.ascontiguousarray(t, np.int32) for t in dra]
-            assert all(t.size == 1024 for t in keep)
-            d = abi.DraLuts()
-            d.luma_inv_scale_lut = keep[0].ctypes.data
-            d.chroma_inv_scale_lut[0], d.chroma_inv_scale_lut[1] = keep[1].ctypes.data, keep[2].ctypes.data
-            dl = C.byref(d)
+        dl, keep = self._dra_luts(dra)
         self._chk(self.lib.xgpu_pic_output(self.ctx, pic, dl, bd, *crop, out.ctypes.data, n), "xgpu_pic_output")
         return out
 
@@ -144,30 +174,30 @@ class XgpuDecoder:
         output's limits - gives an image that is all `pad` (so pad is checked for either fit).  results=True returns (images, results): results int32 [N, 9] =
         status (abi.ROI_OK, ROI_UNUSED, ROI_INVALID, ROI_EMPTY, ROI_TOO_LARGE, ROI_RATIO), the box used (x, y, w, h), its inner part (abi.roi_inner)."""
         import torch
+        if size is not None:      # every argument the scaled, ROI and device-box paths read, by its name
+            a = {"pic": pic, "layout": layout, "channels_last": channels_last, "dtype": dtype, "matrix": matrix, "full_range": full_range, "chroma_loc": chroma_loc,
+                 "crop": crop, "dra": dra, "out": out, "bgr": bgr, "out_bit_depth": out_bit_depth, "colour": colour, "size": size, "filter": filter, "mean": mean,
+                 "std": std, "rois": rois, "fit": fit, "pad": pad, "snap": snap, "count": count, "max_roi": max_roi, "results": results}
         if rois is not None:
             if size is None:
                 raise ValueError("rois: the batch of rectangles needs size=(H, W)")
             if isinstance(rois, torch.Tensor):
                 if snap:
                     raise ValueError("snap: boxes in device memory are always snapped")
-                return self._pic_output_tensor_rois_dev(pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour,
-                                                        size, filter, mean, std, rois, fit, pad, count, max_roi, results)
+                return self._pic_output_tensor_rois_dev(a)
             if count is not None or max_roi is not None or results:
                 raise ValueError("count, max_roi and results belong to rois=<tensor on the device>")
-            return self._pic_output_tensor_rois(pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour,
-                                                size, filter, mean, std, rois, fit, pad, snap)
-        if fit != "stretch" or snap or np.any(np.asarray(pad) != 0) or count is not None or max_roi is not None or results:
+            return self._pic_output_tensor_rois(a)
+        pad_set = pad != 0 if isinstance(pad, (int, float)) else np.any(np.asarray(pad) != 0)
+        if fit != "stretch" or snap or pad_set or count is not None or max_roi is not None or results:
             raise ValueError("fit, pad, snap, count, max_roi and results belong to rois=")
         if size is not None:
-            return self._pic_output_tensor_scaled(pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour,
-                                                  size, filter, mean, std)
+            return self._pic_output_tensor_scaled(a)
         if filter != "bilinear" or mean is not None or std is not None:
             raise ValueError("filter, mean and std belong to the scaled output: they need size=(H, W)")
         if dtype is None:
             dtype = torch.int16 if layout == "p016" else torch.uint8      # P016 has 16-bit words only
-        codes = {torch.uint8: abi.OUT_U8, torch.int16: abi.OUT_U16, torch.float16: abi.OUT_F16, torch.bfloat16: abi.OUT_BF16, torch.float32: abi.OUT_F32}
-        if getattr(torch, "uint16", None) is not None:
-            codes[torch.uint16] = abi.OUT_U16
+        codes = _codes()
         if dtype not in codes:
             raise ValueError(f"unsupported output dtype {dtype}")
         if upsample not in ("linear", "nearest"):
@@ -188,7 +218,7 @@ class XgpuDecoder:
             n = self.lib.xgpu_pic_output_device_size(self.ctx, C.byref(fmt))
             if n == 0:
                 raise ValueError(f"invalid output format: crop {crop}")
-            shape, strides = (n // dtype.itemsize,), (1,)
+            shape = (n // dtype.itemsize,)
         elif layout in ("nv12", "p016"):
             if codes[dtype] != abi.OUT_U16 and (layout == "p016" or codes[dtype] != abi.OUT_U8):
                 raise ValueError(f"{layout}: dtype must be a 16-bit integer type{' or torch.uint8 (8-bit samples)' if layout == 'nv12' else ''}")
@@ -198,114 +228,94 @@ class XgpuDecoder:
                 obd = 8
             shape = (h * 3 // 2, w)
             fmt = abi.make_output_format(abi.OUT_NV12 if layout == "nv12" else abi.OUT_P016, codes[dtype], out_bit_depth=obd, crop=crop)
-            strides = None
         elif layout in ("rgb", "yuv444"):
-            shape = (h, w, 3) if channels_last else (3, h, w)
             lay = (abi.OUT_RGB_INTERLEAVED, abi.OUT_RGB_PLANAR) if layout == "rgb" else (abi.OUT_YUV444_INTERLEAVED, abi.OUT_YUV444_PLANAR)
             fmt = abi.make_output_format(lay[0] if channels_last else lay[1], codes[dtype], bgr=bgr, matrix=matrix, full_range=full_range,
                                          chroma_loc=chroma_loc, upsample=up, crop=crop)
-            strides = None
         else:
             raise ValueError(f"layout must be 'rgb', 'yuv420p', 'nv12', 'p016' or 'yuv444', not {layout!r}")
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=dev)
-        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
-            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
-        st = out.stride()
         if layout in ("rgb", "yuv444"):
-            pitch = st[0] if channels_last else st[1]          # elements between rows
-            if (channels_last and st[1:] != (3, 1)) or (not channels_last and (st[2] != 1 or st[0] != pitch * h)) or pitch < (3 * w if channels_last else w):
-                raise ValueError(f"out: strides {st} are not rows of {'W x 3' if channels_last else 'W'} elements {'' if channels_last else 'in planes of H rows '}")
-            fmt.row_pitch = pitch * dtype.itemsize
-        elif layout in ("nv12", "p016"):
-            if st[1] != 1 or st[0] < w:
+            out = _out_tensor(out, (h, w, 3) if channels_last else (3, h, w), dtype, dev)
+            fmt.row_pitch = _row_pitch(out.stride(), not channels_last, h, 3 * w if channels_last else w, 3) * dtype.itemsize
+        else:
+            out = _out_tensor(out, shape, dtype, dev)
+            st = out.stride()
+            if layout == "yuv420p":
+                if st != (1,):
+                    raise ValueError("out: must be contiguous")
+            elif st[1] != 1 or st[0] < w:
                 raise ValueError(f"out: strides {st} are not rows of W elements")
-            fmt.row_pitch = st[0] * dtype.itemsize
-        elif st != strides:
-            raise ValueError("out: must be contiguous")
+            else:
+                fmt.row_pitch = st[0] * dtype.itemsize
         dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
         if self.lib.xgpu_pic_output_device_size(self.ctx, C.byref(fmt)) == 0:
             raise ValueError(f"invalid output format (layout {layout}, out_bit_depth {out_bit_depth}, matrix {matrix}, chroma_loc {chroma_loc}, crop {crop})")
-        nbytes = (sum((n - 1) * s for n, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
-        cur, run = self._run_stream(dev)
         if colour is None:
-            self._chk(self.lib.xgpu_pic_output_device(self.ctx, pic, dl, C.byref(fmt), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
-                      "xgpu_pic_output_device")
+            self._device_call("xgpu_pic_output_device", out, pic, dl, C.byref(fmt))
         else:
             cm = abi.make_colour_transform(**colour)
-            self._chk(self.lib.xgpu_pic_output_device_cm(self.ctx, pic, dl, C.byref(fmt), C.byref(cm), C.c_void_p(out.data_ptr()), nbytes,
-                                                         C.c_void_p(run.cuda_stream)), "xgpu_pic_output_device_cm")
-        if run is not cur:
-            cur.wait_stream(run)
+            self._device_call("xgpu_pic_output_device_cm", out, pic, dl, C.byref(fmt), C.byref(cm))
         return out
 
-    def _scaled_setup(self, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, bgr, out_bit_depth, colour, size, filter, mean, std):
+    def _scaled_setup(self, a):
         """what the scaled outputs check and build alike -> (torch dtype, xgpu_output_format, xgpu_scale_params, H, W, device)"""
         import torch
+        layout, colour, filter, mean, std = a["layout"], a["colour"], a["filter"], a["mean"], a["std"]
         if layout not in ("rgb", "yuv444"):
             raise ValueError(f"size: the scaled output has layouts 'rgb' and 'yuv444', not {layout!r}")
         if colour is not None:
             raise ValueError("size: the scaled output takes no colour transform")
         if filter not in ("bilinear", "area"):
             raise ValueError(f"filter must be 'bilinear' or 'area', not {filter!r}")
-        if int(out_bit_depth) not in (0, self.bit_depth):
-            raise ValueError(f"{layout}: out_bit_depth must be 0 or the coding depth {self.bit_depth}, not {out_bit_depth}")
-        dtype = torch.uint8 if dtype is None else dtype
-        codes = {torch.uint8: abi.OUT_U8, torch.int16: abi.OUT_U16, torch.float16: abi.OUT_F16, torch.bfloat16: abi.OUT_BF16, torch.float32: abi.OUT_F32}
-        if getattr(torch, "uint16", None) is not None:
-            codes[torch.uint16] = abi.OUT_U16
+        if int(a["out_bit_depth"]) not in (0, self.bit_depth):
+            raise ValueError(f"{layout}: out_bit_depth must be 0 or the coding depth {self.bit_depth}, not {a['out_bit_depth']}")
+        dtype = torch.uint8 if a["dtype"] is None else a["dtype"]
+        codes = _codes()
         if dtype not in codes:
             raise ValueError(f"unsupported output dtype {dtype}")
         if (mean is not None or std is not None) and codes[dtype] in (abi.OUT_U8, abi.OUT_U16):
             raise ValueError("mean / std: the normalise needs a float dtype")
-        h, w = (int(v) for v in size)
+        h, w = int(a["size"][0]), int(a["size"][1])
         lay = (abi.OUT_RGB_INTERLEAVED, abi.OUT_RGB_PLANAR) if layout == "rgb" else (abi.OUT_YUV444_INTERLEAVED, abi.OUT_YUV444_PLANAR)
-        fmt = abi.make_output_format(lay[0] if channels_last else lay[1], codes[dtype], bgr=bgr, matrix=matrix, full_range=full_range, chroma_loc=chroma_loc, crop=crop)
+        fmt = abi.make_output_format(lay[0] if a["channels_last"] else lay[1], codes[dtype], bgr=a["bgr"], matrix=a["matrix"], full_range=a["full_range"],
+                                     chroma_loc=a["chroma_loc"], crop=a["crop"])
         sc = abi.make_scale_params(w, h, abi.SCALE_BILINEAR if filter == "bilinear" else abi.SCALE_AREA, mean=mean, std=std)
         return dtype, fmt, sc, h, w, torch.device("cuda", self.sp.device)
 
-    def _pic_output_tensor_scaled(self, pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour, size, filter,
-                                  mean, std):
+    @staticmethod
+    def _rois_fit(a):
+        """what a batch checks before _scaled_setup -> the XGPU_FIT_* code"""
+        if a["colour"] is not None:
+            raise ValueError("rois: the batch of rectangles takes no colour transform")
+        if a["fit"] not in ("stretch", "letterbox"):
+            raise ValueError(f"fit must be 'stretch' or 'letterbox', not {a['fit']!r}")
+        return abi.FIT_LETTERBOX if a["fit"] == "letterbox" else abi.FIT_STRETCH
+
+    def _pic_output_tensor_scaled(self, a):
         """pic_output_tensor with size=(H, W)"""
-        import torch
-        dtype, fmt, sc, h, w, dev = self._scaled_setup(layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, bgr, out_bit_depth, colour, size, filter,
-                                                       mean, std)
-        shape = (h, w, 3) if channels_last else (3, h, w)
-        if out is None:
+        dtype, fmt, sc, h, w, dev = self._scaled_setup(a)
+
+        def refuse():
             if self.lib.xgpu_output_scaled_size(C.byref(fmt), C.byref(sc), self.width, self.height, self.bit_depth) == 0:
-                raise ValueError(f"invalid scaled output (layout {layout}, size {tuple(size)}, matrix {matrix}, chroma_loc {chroma_loc}, crop {crop}, mean {mean}, std {std})")
-            out = torch.empty(shape, dtype=dtype, device=dev)
-        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
-            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
-        st = out.stride()
-        pitch = st[0] if channels_last else st[1]          # elements between rows
-        if (channels_last and st[1:] != (3, 1)) or (not channels_last and (st[2] != 1 or st[0] != pitch * h)) or pitch < (3 * w if channels_last else w):
-            raise ValueError(f"out: strides {st} are not rows of {'W x 3' if channels_last else 'W'} elements {'' if channels_last else 'in planes of H rows '}")
-        fmt.row_pitch = pitch * dtype.itemsize
-        if self.lib.xgpu_output_scaled_size(C.byref(fmt), C.byref(sc), self.width, self.height, self.bit_depth) == 0:
-            raise ValueError(f"invalid scaled output (layout {layout}, size {tuple(size)}, matrix {matrix}, chroma_loc {chroma_loc}, crop {crop}, mean {mean}, std {std})")
-        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
-        nbytes = (sum((n - 1) * s for n, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
-        cur, run = self._run_stream(dev)
-        self._chk(self.lib.xgpu_pic_output_device_scaled(self.ctx, pic, dl, C.byref(fmt), C.byref(sc), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
-                  "xgpu_pic_output_device_scaled")
-        if run is not cur:
-            cur.wait_stream(run)
+                raise ValueError(f"invalid scaled output (layout {a['layout']}, size {tuple(a['size'])}, matrix {a['matrix']}, chroma_loc {a['chroma_loc']}, "
+                                 f"crop {a['crop']}, mean {a['mean']}, std {a['std']})")
+        out, planar = a["out"], not a["channels_last"]
+        if out is None:
+            refuse()      # before a tensor is made, and again with its pitch
+        out = _out_tensor(out, (3, h, w) if planar else (h, w, 3), dtype, dev)
+        fmt.row_pitch = _row_pitch(out.stride(), planar, h, w if planar else 3 * w, 3) * dtype.itemsize
+        refuse()
+        dl, self._dra_keep = self._dra_luts(a["dra"]) if a["dra"] is not None else (None, None)      # (kept until the next call: the tables are copied asynchronously)
+        self._device_call("xgpu_pic_output_device_scaled", out, a["pic"], dl, C.byref(fmt), C.byref(sc))
         return out
 
-    def _pic_output_tensor_rois(self, pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour, size, filter,
-                                mean, std, rois, fit, pad, snap):
+    def _pic_output_tensor_rois(self, a):
         """pic_output_tensor with size=(H, W) and rois=[...]"""
-        import torch
-        if colour is not None:
-            raise ValueError("rois: the batch of rectangles takes no colour transform")
-        if fit not in ("stretch", "letterbox"):
-            raise ValueError(f"fit must be 'stretch' or 'letterbox', not {fit!r}")
-        dtype, fmt, sc, h, w, dev = self._scaled_setup(layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, bgr, out_bit_depth, colour, size, filter,
-                                                       mean, std)
-        rois = [tuple(int(v) for v in r) for r in rois]
-        if snap:       # outward to even, then into the picture minus the crop
-            cl, cr, ct, cb = (int(v) for v in crop)
+        fit = self._rois_fit(a)
+        dtype, fmt, sc, h, w, dev = self._scaled_setup(a)
+        rois = [tuple(int(v) for v in r) for r in a["rois"]]
+        if a["snap"]:       # outward to even, then into the picture minus the crop
+            cl, cr, ct, cb = (int(v) for v in a["crop"])
             pw, ph = self.width - cl - cr, self.height - ct - cb
             snapped = []
             for x, y, rw, rh in rois:
@@ -314,47 +324,33 @@ class XgpuDecoder:
             rois = snapped
         n = len(rois)
         ra = abi.make_rois(rois)
-        rp = abi.make_roi_params(abi.FIT_LETTERBOX if fit == "letterbox" else abi.FIT_STRETCH, pad)
-        shape = (n, h, w, 3) if channels_last else (n, 3, h, w)
+        rp = abi.make_roi_params(fit, a["pad"])
 
         def refuse():
             bad = C.c_int(-1)
             rc = self.lib.xgpu_output_rois_check(C.byref(fmt), C.byref(sc), C.byref(rp), ra, n, self.width, self.height, self.bit_depth, C.byref(bad))
             if rc < 0:
                 at = f"roi {bad.value} {rois[bad.value]}: " if 0 <= bad.value < n else ""
-                raise ValueError(f"invalid batch of rectangles ({rc}): {at}layout {layout}, size {tuple(size)}, fit {fit}, pad {pad}, crop {crop}, mean {mean}, std {std}, "
-                                 f"{n} rectangles")
+                raise ValueError(f"invalid batch of rectangles ({rc}): {at}layout {a['layout']}, size {tuple(a['size'])}, fit {a['fit']}, pad {a['pad']}, "
+                                 f"crop {a['crop']}, mean {a['mean']}, std {a['std']}, {n} rectangles")
+        out, planar = a["out"], not a["channels_last"]
         if out is None:
-            refuse()
-            out = torch.empty(shape, dtype=dtype, device=dev)
-        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
-            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+            refuse()      # before a tensor is made, and again with its pitches
+        out = _out_tensor(out, (n, 3, h, w) if planar else (n, h, w, 3), dtype, dev)
         st = out.stride()
-        pitch = st[1] if channels_last else st[2]          # elements between rows
-        if (channels_last and st[2:] != (3, 1)) or (not channels_last and (st[3] != 1 or st[1] != pitch * h)) or pitch < (3 * w if channels_last else w):
-            raise ValueError(f"out: strides {st} are not rows of {'W x 3' if channels_last else 'W'} elements {'' if channels_last else 'in planes of H rows '}")
-        fmt.row_pitch = pitch * dtype.itemsize
+        fmt.row_pitch = _row_pitch(st, planar, h, w if planar else 3 * w, 3) * dtype.itemsize
         rp.image_pitch = st[0] * dtype.itemsize if n > 1 else 0
         refuse()
-        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
-        nbytes = (sum((k - 1) * s for k, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
-        cur, run = self._run_stream(dev)
-        self._chk(self.lib.xgpu_pic_output_device_rois(self.ctx, pic, dl, C.byref(fmt), C.byref(sc), C.byref(rp), ra, n, C.c_void_p(out.data_ptr()), nbytes,
-                                                       C.c_void_p(run.cuda_stream)), "xgpu_pic_output_device_rois")
-        if run is not cur:
-            cur.wait_stream(run)
+        dl, self._dra_keep = self._dra_luts(a["dra"]) if a["dra"] is not None else (None, None)      # (kept until the next call: the tables are copied asynchronously)
+        self._device_call("xgpu_pic_output_device_rois", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(rp), ra, n)
         return out
 
-    def _pic_output_tensor_rois_dev(self, pic, layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, dra, out, bgr, out_bit_depth, colour, size, filter,
-                                    mean, std, rois, fit, pad, count, max_roi, results):
+    def _pic_output_tensor_rois_dev(self, a):
         """pic_output_tensor with size=(H, W) and rois=<tensor on the device>"""
         import torch
-        if colour is not None:
-            raise ValueError("rois: the batch of rectangles takes no colour transform")
-        if fit not in ("stretch", "letterbox"):
-            raise ValueError(f"fit must be 'stretch' or 'letterbox', not {fit!r}")
-        dtype, fmt, sc, h, w, dev = self._scaled_setup(layout, channels_last, dtype, matrix, full_range, chroma_loc, crop, bgr, out_bit_depth, colour, size, filter,
-                                                       mean, std)
+        fit = self._rois_fit(a)
+        dtype, fmt, sc, h, w, dev = self._scaled_setup(a)
+        rois, count, results = a["rois"], a["count"], a["results"]
         if rois.device != dev or rois.dtype not in (torch.int32, torch.float32) or rois.dim() != 2 or rois.shape[1] != 4 or not rois.is_contiguous():
             raise ValueError(f"rois: a contiguous int32 (x, y, w, h) or float32 (x1, y1, x2, y2) tensor [N, 4] on {dev}, not {tuple(rois.shape)} {rois.dtype} on "
                              f"{rois.device}{'' if rois.is_contiguous() else ', not contiguous'}")
@@ -362,37 +358,27 @@ class XgpuDecoder:
             raise ValueError(f"count: an int32 tensor of one element on {dev}")
         n = int(rois.shape[0])
         box_format = abi.BOX_XYWH_I32 if rois.dtype == torch.int32 else abi.BOX_XYXY_F32
-        rp = abi.make_roi_params(abi.FIT_LETTERBOX if fit == "letterbox" else abi.FIT_STRETCH, pad)
-        bounds = abi.make_roi_bounds(max_roi)
-        shape = (n, h, w, 3) if channels_last else (n, 3, h, w)
+        rp = abi.make_roi_params(fit, a["pad"])
+        bounds = abi.make_roi_bounds(a["max_roi"])
 
         def refuse():
             rc = self.lib.xgpu_output_rois_dev_check(C.byref(fmt), C.byref(sc), C.byref(rp), C.byref(bounds), box_format, n, self.width, self.height, self.bit_depth)
             if rc < 0:
-                raise ValueError(f"invalid batch of boxes ({rc}): layout {layout}, size {tuple(size)}, fit {fit}, pad {pad}, crop {crop}, mean {mean}, std {std}, "
-                                 f"max_roi {max_roi}, {n} boxes")
+                raise ValueError(f"invalid batch of boxes ({rc}): layout {a['layout']}, size {tuple(a['size'])}, fit {a['fit']}, pad {a['pad']}, crop {a['crop']}, "
+                                 f"mean {a['mean']}, std {a['std']}, max_roi {a['max_roi']}, {n} boxes")
+        out, planar = a["out"], not a["channels_last"]
         if out is None:
-            refuse()
-            out = torch.empty(shape, dtype=dtype, device=dev)
-        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
-            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+            refuse()      # before a tensor is made, and again with its pitches
+        out = _out_tensor(out, (n, 3, h, w) if planar else (n, h, w, 3), dtype, dev)
         st = out.stride()
-        pitch = st[1] if channels_last else st[2]          # elements between rows
-        if (channels_last and st[2:] != (3, 1)) or (not channels_last and (st[3] != 1 or st[1] != pitch * h)) or pitch < (3 * w if channels_last else w):
-            raise ValueError(f"out: strides {st} are not rows of {'W x 3' if channels_last else 'W'} elements {'' if channels_last else 'in planes of H rows '}")
-        fmt.row_pitch = pitch * dtype.itemsize
+        fmt.row_pitch = _row_pitch(st, planar, h, w if planar else 3 * w, 3) * dtype.itemsize
         rp.image_pitch = st[0] * dtype.itemsize if n > 1 else 0
         refuse()
-        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
-        nbytes = (sum((k - 1) * s for k, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
-        cur, run = self._run_stream(dev)
+        dl, self._dra_keep = self._dra_luts(a["dra"]) if a["dra"] is not None else (None, None)      # (kept until the next call: the tables are copied asynchronously)
         res = torch.empty((n, 9), dtype=torch.int32, device=dev) if results else None
-        self._chk(self.lib.xgpu_pic_output_device_rois_dev(self.ctx, pic, dl, C.byref(fmt), C.byref(sc), C.byref(rp), C.byref(bounds), box_format,
-                                                           C.c_void_p(rois.data_ptr()), n, C.c_void_p(count.data_ptr()) if count is not None else None,
-                                                           C.c_void_p(res.data_ptr()) if results else None, C.c_void_p(out.data_ptr()), nbytes,
-                                                           C.c_void_p(run.cuda_stream)), "xgpu_pic_output_device_rois_dev")
-        if run is not cur:
-            cur.wait_stream(run)
+        self._device_call("xgpu_pic_output_device_rois_dev", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(rp), C.byref(bounds), box_format,
+                          C.c_void_p(rois.data_ptr()), n, C.c_void_p(count.data_ptr()) if count is not None else None,
+                          C.c_void_p(res.data_ptr()) if results else None)
         return (out, res) if results else out
 
     def _run_stream(self, dev):
@@ -407,6 +393,17 @@ class XgpuDecoder:
             run = self._side
             run.wait_stream(cur)
         return cur, run
+
+    def _device_call(self, name, out, *args):
+        """lib.<name>(ctx, *args, out's memory, the bytes it spans, stream): an output into device memory, queued on _run_stream's stream and joined to torch's
+        current stream; a negative code raises XgpuError"""
+        nbytes = out.numel() * out.element_size()      # the bytes the tensor spans from data_ptr(): all of them, or - rows or images apart - up to its last element
+        if not out.is_contiguous():
+            nbytes = (sum((n - 1) * s for n, s in zip(out.shape, out.stride())) + 1) * out.element_size()
+        cur, run = self._run_stream(out.device)
+        self._chk(getattr(self.lib, name)(self.ctx, *args, C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)), name)
+        if run is not cur:
+            cur.wait_stream(run)
 
     def frame_side_info(self, pic, kind="blocks", lists="both", dtype=None, per_poc=False, channels_last=False, crop=(0, 0, 0, 0), out=None):
         """The coding side information of the picture decoded LAST as a torch tensor on cuda:{device}, on torch's current stream (xgpu_frame_side_info,
@@ -430,7 +427,7 @@ class XgpuDecoder:
             fmt = abi.make_side_format(abi.SIDE_BLOCKS, abi.OUT_U16, crop=crop)
         elif kind == "flow":
             dtype = torch.float16 if dtype is None else dtype
-            codes = {torch.float16: abi.OUT_F16, torch.float32: abi.OUT_F32}
+            codes = _codes("float16", "float32")
             if dtype not in codes:
                 raise ValueError(f"flow: dtype torch.float16 or torch.float32, not {dtype}")
             if lists not in ("both", 0, 1):
@@ -445,21 +442,9 @@ class XgpuDecoder:
             raise ValueError(f"kind must be 'blocks' or 'flow', not {kind!r}")
         if self.lib.xgpu_side_info_size(C.byref(fmt), self.width, self.height) == 0:
             raise ValueError(f"invalid side-information format (kind {kind}, lists {lists}, crop {crop})")
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=dev)
-        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
-            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
-        st = out.stride()
-        pitch = st[1] if planar else st[0]          # elements between rows
-        if (planar and (st[2] != 1 or st[0] != pitch * h)) or (not planar and st[1:] != (shape[2], 1)) or pitch < rows_w:
-            raise ValueError(f"out: strides {st} are not rows of {rows_w} elements{' in planes of H rows' if planar else ''}")
-        fmt.row_pitch = pitch * dtype.itemsize
-        nbytes = (sum((n - 1) * s for n, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
-        cur, run = self._run_stream(dev)
-        self._chk(self.lib.xgpu_frame_side_info(self.ctx, pic, C.byref(fmt), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
-                  "xgpu_frame_side_info")
-        if run is not cur:
-            cur.wait_stream(run)
+        out = _out_tensor(out, shape, dtype, dev)
+        fmt.row_pitch = _row_pitch(out.stride(), planar, h, rows_w, shape[2], f"{rows_w} elements{' in planes of H rows' if planar else ''}") * dtype.itemsize
+        self._device_call("xgpu_frame_side_info", out, pic, C.byref(fmt))
         return out
 
     def batch_residual(self, h, kind="yuv420", dtype=None, channels_last=False, crop=(0, 0, 0, 0), out=None):
@@ -483,7 +468,7 @@ class XgpuDecoder:
             shape, planar, rows_w = (h_ * w_ * 3 // 2,), None, 0
         elif kind == "444":
             dtype = torch.int16 if dtype is None else dtype
-            codes = {torch.int16: abi.OUT_U16, torch.float16: abi.OUT_F16, torch.float32: abi.OUT_F32}
+            codes = _codes("int16", "float16", "float32")
             if dtype not in codes:
                 raise ValueError(f"444: dtype torch.int16, torch.float16 or torch.float32, not {dtype}")
             planar = not channels_last
@@ -500,25 +485,13 @@ class XgpuDecoder:
             raise ValueError(f"kind must be 'yuv420', '444' or 'energy', not {kind!r}")
         if self.lib.xgpu_resid_size(C.byref(fmt), self.width, self.height) == 0:
             raise ValueError(f"invalid residual format (kind {kind}, dtype {dtype}, crop {crop})")
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=dev)
-        if out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape):
-            raise ValueError(f"out: expected {tuple(shape)} {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
-        st = out.stride()
+        out = _out_tensor(out, shape, dtype, dev)
         if planar is None:
-            if st != (1,):
+            if out.stride() != (1,):
                 raise ValueError("out: must be contiguous")
         else:
-            pitch = st[1] if planar else st[0]          # elements between rows
-            if (planar and (st[2] != 1 or st[0] != pitch * h_)) or (not planar and st[1:] != (3, 1)) or pitch < rows_w:
-                raise ValueError(f"out: strides {st} are not rows of {rows_w} elements{' in planes of H rows' if planar else ''}")
-            fmt.row_pitch = pitch * dtype.itemsize
-        nbytes = (sum((n - 1) * s for n, s in zip(out.shape, st)) + 1) * dtype.itemsize      # the bytes the tensor spans from data_ptr()
-        cur, run = self._run_stream(dev)
-        self._chk(self.lib.xgpu_batch_residual(self.ctx, h, C.byref(fmt), C.c_void_p(out.data_ptr()), nbytes, C.c_void_p(run.cuda_stream)),
-                  "xgpu_batch_residual")
-        if run is not cur:
-            cur.wait_stream(run)
+            fmt.row_pitch = _row_pitch(out.stride(), planar, h_, rows_w, 3, f"{rows_w} elements{' in planes of H rows' if planar else ''}") * dtype.itemsize
+        self._device_call("xgpu_batch_residual", out, h, C.byref(fmt))
         if kind == "yuv420":
             ny, nc = h_ * w_, (h_ // 2) * (w_ // 2)
             return out, (out[:ny].view(h_, w_), out[ny:ny + nc].view(h_ // 2, w_ // 2), out[ny + nc:].view(h_ // 2, w_ // 2))
@@ -527,14 +500,7 @@ class XgpuDecoder:
     def pic_md5(self, pic, dra=None):
         """the picture signature made on the device (xgpu_pic_md5): [Y, U, V] digests of 16 bytes - the MD5 of every plane's 16-bit samples as the reference's
         xevd_md5_imgb makes it; with `dra` tables (as pic_output takes them) of the DRA-mapped picture"""
-        dl, keep = None, None
-        if dra is not None:
-            keep = [np.ascontiguousarray(t, np.int32) for t in dra]
-            assert all(t.size == 1024 for t in keep)
-            d = abi.DraLuts()
-            d.luma_inv_scale_lut = keep[0].ctypes.data
-            d.chroma_inv_scale_lut[0], d.chroma_inv_scale_lut[1] = keep[1].ctypes.data, keep[2].ctypes.data
-            dl = C.byref(d)
+        dl, keep = self._dra_luts(dra)
         out = np.zeros((3, 16), np.uint8)
         self._chk(self.lib.xgpu_pic_md5(self.ctx, pic, dl, out.ctypes.data), "xgpu_pic_md5")
         return [bytes(out[c]) for c in range(3)]
