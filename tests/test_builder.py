@@ -115,6 +115,36 @@ def test_builder_rejects_invalid_batches_without_a_device():
         assert lib.xgpu_test_build_batch(C.byref(sp), C.byref(cb), 2, dg, info, C.byref(ms)) == -101, field
 
 
+def test_builder_scratch_survives_refused_batches():
+    """the working arrays a caller keeps between pictures after batches that are refused half way: on one calling thread, a picture pass 1 refuses (CU outside the
+    picture), the same picture with an intra block copy CU whose source block is the CU itself (pass 1 accepts it, the dependency plan refuses it in its parallel
+    mode: 14 244 CUs, three threads), then the unmodified picture - which must come out as the committed digests"""
+    from xevd_amd import synth
+    lib = _lib()
+    name, w, h, kw, spkw = LARGE[0]
+    want = json.load(open(GOLDEN_FILE))["large_" + name]
+    b = synth.gen_frame(np.random.default_rng(11), w, h, 10, coded_frac=0.6, qp_range=(22, 37), **kw)
+    n = len(b["x"])
+    sp = abi.make_seq_params(w, h, 10, **spkw)
+
+    def refused(bad):
+        cb, keep = abi.make_cu_batch(bad)
+        dg, info, ms = (C.c_uint64 * 13)(), (C.c_int * 8)(), C.c_double()
+        return lib.xgpu_test_build_batch(C.byref(sp), C.byref(cb), threads, dg, info, C.byref(ms))
+    for threads in (1, 4, 7):
+        outside = dict(b)
+        outside["x"] = b["x"].copy()
+        outside["x"][n // 2] = 60000
+        assert refused(outside) == -101, f"{threads} builder thread(s): pass 1"
+        ibc = dict(b)
+        ibc["pred_mode"], ibc["mv"] = b["pred_mode"].copy(), b["mv"].copy()
+        ibc["pred_mode"][3 * n // 4] = abi.MODE_IBC
+        ibc["mv"].reshape(n, 4)[3 * n // 4] = 0
+        assert refused(ibc) == -101, f"{threads} builder thread(s): plan"
+        cb, keep = abi.make_cu_batch(b)
+        assert _build(lib, sp, cb, threads) == want, f"{threads} builder thread(s)"
+
+
 if __name__ == "__main__" and "--write" in sys.argv:
     lib = _lib()
     out = {"pic_" + n: picture_digests(lib, n, 1) for n in golden_io.PICTURE_CASES}

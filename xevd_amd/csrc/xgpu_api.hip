@@ -1,7 +1,7 @@
 // xgpu_api.hip - the C ABI of include/xevd_hip.h, part 1: context, host allocation, device pictures, output into host memory, the picture signature, frame begin / end,
 // HIP-event kernel timing.
-// Host-side code only; kernels live in k_*.hip, the outputs into device memory in xgpu_output.hip, the batch builder in xgpu_builder.hip, the launch sequencing in
-// xgpu_launch.hip, the test shims in xgpu_shims.hip.
+// Host-side code only; kernels live in k_*.hip, the outputs into device memory in xgpu_output.hip, the batch builder in xgpu_builder.hip (its dependency plan in
+// xgpu_intra_plan.hip), the launch sequencing in xgpu_launch.hip, the test shims in xgpu_shims.hip.
 #include "xgpu_host.h"
 
 // xevd_tbl_qp_chroma_adjust_base (src_base/xevd_tbl.c:345-354): default Baseline chroma QP mapping.
@@ -170,16 +170,7 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
         if (hipEventCreateWithFlags(&c->out_ready[i], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->out_done[i], ev_flags) != hipSuccess)
             return fail(XGPU_ERR_UNEXPECTED);
 
-    c->w_scu = sp->width >> 2; c->h_scu = sp->height >> 2;
-    const int ctu = 1 << sp->log2_ctu;
-    c->w_ctu = (sp->width + ctu - 1) / ctu; c->h_ctu = (sp->height + ctu - 1) / ctu;
-    c->s_l = align_up(XGPU_MARGIN_L + sp->width + XGPU_PAD_L, 64);
-    c->s_c = align_up(XGPU_MARGIN_C + (sp->width >> 1) + XGPU_PAD_C, 64);
-    c->rows_l = sp->height + 2 * XGPU_PAD_L;
-    c->rows_c = (sp->height >> 1) + 2 * XGPU_PAD_C;
-    c->off_u = (size_t)c->s_l * c->rows_l;
-    c->off_v = c->off_u + (size_t)c->s_c * c->rows_c;
-    c->pic_elems = c->off_v + (size_t)c->s_c * c->rows_c + 64;   // +64: slack for the 16-byte window over-read of the last row
+    ctx_geometry(c);
 
     if (hipMalloc((void **)&c->d_maps, sizeof(ScuRec) * (size_t)c->w_scu * c->h_scu) != hipSuccess) return fail(XGPU_ERR_OUT_OF_MEMORY);
     if (hipMemsetAsync(c->d_maps, 0, sizeof(ScuRec) * (size_t)c->w_scu * c->h_scu, c->stream) != hipSuccess) return fail(XGPU_ERR_UNEXPECTED);
@@ -212,7 +203,7 @@ void xgpu_close(xgpu_ctx *c)
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     for (auto &p : c->pics) if (p.base) (void)hipFree(p.base);
     if (c->d_maps) (void)hipFree(c->d_maps);
-    for (BatchBlock &k : c->pool) { (void)hipFree(k.d_base); (void)hipHostFree(k.h_stage); (void)hipEventDestroy(k.uploaded); (void)hipEventDestroy(k.done); (void)hipEventDestroy(k.itdq_done); if (k.d_chroma) (void)hipFree(k.d_chroma); }
+    for (BatchBlock &k : c->pool) block_free(k);
     for (auto &h : c->pinned) (void)hipHostFree(h.p);
     c->pinned.clear();
     c->pool.clear();

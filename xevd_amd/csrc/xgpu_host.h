@@ -1,6 +1,6 @@
 // xgpu_host.h - what the host-side translation units of the backend share (xgpu_api.hip: context, pictures, output into host memory; xgpu_output.hip: the outputs
-// into device memory; xgpu_builder.hip: the batch builder and its dependency plan; xgpu_launch.hip: the per-picture launch sequencing; xgpu_shims.hip: the
-// fine-grained test shims).  Private to xevd_amd/csrc.
+// into device memory; xgpu_builder.hip: the batch builder; xgpu_intra_plan.hip: its dependency plan; xgpu_launch.hip: the per-picture launch sequencing;
+// xgpu_shims.hip: the fine-grained test shims).  Private to xevd_amd/csrc.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -26,6 +26,16 @@
 
 
 static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+// the picture geometry of a context, from c->sp (xgpu_open, and the device-less context of xgpu_test_build_batch)
+static inline void ctx_geometry(xgpu_ctx *c)
+{
+    const int w = c->sp.width, h = c->sp.height, ctu = 1 << c->sp.log2_ctu;
+    c->w_scu = w >> 2; c->h_scu = h >> 2; c->w_ctu = (w + ctu - 1) / ctu; c->h_ctu = (h + ctu - 1) / ctu;
+    c->s_l = align_up(XGPU_MARGIN_L + w + XGPU_PAD_L, 64); c->s_c = align_up(XGPU_MARGIN_C + (w >> 1) + XGPU_PAD_C, 64);
+    c->rows_l = h + 2 * XGPU_PAD_L; c->rows_c = (h >> 1) + 2 * XGPU_PAD_C;
+    c->off_u = (size_t)c->s_l * c->rows_l; c->off_v = c->off_u + (size_t)c->s_c * c->rows_c;
+    c->pic_elems = c->off_v + (size_t)c->s_c * c->rows_c + 64;   // +64: slack for the 16-byte window over-read of the last row
+}
 static inline bool valid_pic(const xgpu_ctx *c, int pic) { return pic >= 0 && pic + 1 < (int)c->pics.size() && c->pics[pic + 1].used; }
 static inline DevPic &dpic(xgpu_ctx *c, int pic) { return c->pics[pic + 1]; }
 // ADDB directly followed by ALF runs as ONE kernel (k_addb_alf)
@@ -61,8 +71,38 @@ inline bool tile_mask(const xgpu_ctx *c, const xgpu_tile_grid *g, TileMask &m)
     return true;
 }
 
-// The batch builder: SoA batch of the ABI -> 32-byte CU records, the TB list sorted by size class and the
-// wave work items of the itdq kernel, written into ONE pinned staging block and sent with one async copy per
-// array.  (xevd_ctu_row_rec_mt's per-CU cu_init + coef_rect_to_series, xevd.c:567-676, become this pass.)
-// host_only (xgpu_test_build_batch): everything but the device - the staging block comes from malloc, nothing is uploaded; `segs` receives (offset, bytes) of
-// every array in the staging block.  The CPU suite pins the builder's output with it (digests, thread-count independence).
+// HTDF (xevdm.c:1381-1392 with xevdm_htdf_skip_condition, xevdm_recon.c:270-297): which CUs are filtered right after their reconstruction, and with which of the five
+// tables (-1: not filtered).  Such a CU - inter ones included - reads the final samples of the CUs before it and is read by the ones after it: it is a node of the
+// dependency graph next to the intra and IBC CUs
+static inline int plan_htdf_idx(const xgpu_cu_batch *b, uint32_t j)
+{
+    const int hqp = b->htdf_slice_qp;
+    const bool intra = b->pred_mode[j] == XGPU_MODE_INTRA;
+    if (hqp <= 17 || (b->tree && b->tree[j] == 2) || b->pred_mode[j] == XGPU_MODE_IBC || !((b->cbf[j] & 1) || intra)) return -1;
+    const int w = 1 << b->log2w[j], h = 1 << b->log2h[j], mn = std::min(w, h), mx = std::max(w, h);
+    if (w * h < 64 || mx >= 128 || (!intra && mn >= 32)) return -1;
+    const int qp = hqp - ((intra && w == h && mn >= 32) ? 8 : 0);
+    return std::min(std::max((qp - 20 + 4) >> 3, 0), 4);
+}
+static inline bool plan_is_node(const xgpu_cu_batch *b, uint32_t j) { return b->pred_mode[j] == XGPU_MODE_INTRA || b->pred_mode[j] == XGPU_MODE_IBC || plan_htdf_idx(b, j) >= 0; }
+// the dependency plan of a batch (xgpu_intra_plan.hip): the records of k_intra.hip's list and their waiting lists (list positions)
+struct IntraPlan {
+    std::vector<IntraRec> recs; std::vector<uint32_t> deps; bool has_ibc, has_htdf, has_right;
+    int n_levels, n_level1, n_level1_small, n_heads;      // n_heads: level-1 CUs + strand heads = the part of the list the launches range over
+    void reset() { recs.clear(); deps.clear(); n_levels = n_level1 = n_level1_small = n_heads = 0; has_ibc = has_htdf = has_right = false; }
+};
+struct PlanOut { std::vector<uint32_t> deps; bool ibc = false, htdf = false, right = false, bad = false; };      // one thread of the plan's parallel mode: its lists, the k_intra instantiations its nodes ask for
+// What a caller of the builder keeps between pictures, ONE object per calling thread: the worker threads, and working arrays of 6 - 60 MB at 8K (allocated per call they
+// go through mmap / munmap, whose TLB shootdown reaches every thread of the process).  Each is (re)initialised where a phase uses it: a refused batch leaves it usable.
+struct BuilderScratch {
+    WorkPool pool;
+    IntraPlan plan;
+    // the builder: SCU -> CU map; per 32x32 tile its one CU / any CU; k_inter's work lists; the plan's nodes in decoding order; the staging block of a host-only build
+    std::vector<uint32_t> own, tile_cu, inter_items, inter_work, nodes;
+    std::vector<uint8_t>  tile_any, host_stage;
+    // the plan: sequential mode's SCU maps; nodes in decoding order + their lists (CU indices); CU -> record, record -> successor, CU -> position, record -> first dependency
+    std::vector<uint32_t> owner_own, luma_owner, deps, succ, pos, nfirst;
+    std::vector<int> level; std::vector<IntraRec> recs; std::vector<PlanOut> outs; std::vector<int32_t> rec_of_cu; std::vector<uint8_t> member;
+};
+__attribute__((visibility("hidden"))) bool build_intra_plan(xgpu_ctx *c, const xgpu_cu_batch *b, BuilderScratch &S, const uint32_t *final_owner, int nthr);      // S.nodes -> S.plan; false: an invalid batch
+__attribute__((visibility("hidden"))) void block_free(BatchBlock &blk);      // frees what a block holds (xgpu_batch_destroy, xgpu_close)

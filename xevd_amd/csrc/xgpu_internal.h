@@ -310,6 +310,7 @@ struct xgpu_dbatch {
     int        n_intra, n_levels, n_intra_deps, n_intra_l1, n_intra_heads;      // n_intra_l1: CUs of level 1 (head of the list); n_intra_heads: + the strand heads of the data-flow launch (the strand members follow)
     uint32_t   intra_epoch, intra_tickets;
     void      *h_stage;               // pinned staging block
+    int        host_only;             // built by xgpu_test_build_batch: h_stage is the builder's scratch, the block holds nothing to free or pool
     size_t     stage_bytes;
     int        prepared;              // 1: xgpu_batch_prepare has queued the residual pass (k_itdq) on the side stream: `blk.itdq_done` says when it has finished;
                                       // 2: it ran on the main stream with the previous picture (xgpu_batch_recon_ahead)
@@ -389,8 +390,8 @@ struct xgpu_ctx {
 };
 
 // The host threads of a batch builder: workers that stay alive between pictures (a std::thread per phase and picture cost ~0.1 ms each - more than a phase of
-// the builder takes).  One pool per CALLING thread (xgpu_batch_create may run on several builder threads of one context at once): static thread_local in
-// xgpu_builder.hip.  run(n, f): f(0) on the caller, f(1) .. f(n - 1) on workers, returns when all are done.
+// the builder takes).  One pool per CALLING thread (xgpu_batch_create may run on several builder threads of one context at once): a member of the
+// builder's BuilderScratch.  run(n, f): f(0) on the caller, f(1) .. f(n - 1) on workers, returns when all are done.
 class WorkPool {
 public:
     ~WorkPool() { { std::lock_guard<std::mutex> g(mu); stop = true; } cv.notify_all(); for (std::thread &t : th) t.join(); }
