@@ -4,6 +4,7 @@
 // What is restated and how it is mapped: see the header of k_itdq.hip.
 #pragma once
 #include "xgpu_internal.h"
+#include <type_traits>
 
 typedef short v2s __attribute__((ext_vector_type(2)));
 
@@ -53,6 +54,14 @@ __device__ __forceinline__ int dot2(uint32_t a, uint32_t b, int c)
 {
     return __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, a), __builtin_bit_cast(v2s, b), c, false);
 }
+// a * b + c of two factors inside s24, full rate (the compiler's own choice for __mul24 + add here was the quarter-rate v_mad_u64_u32)
+__device__ __forceinline__ int mad24(int a, int b, int c)
+{
+    int r;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ uint32_t pack16(int lo, int hi) { return (uint32_t)(uint16_t)lo | ((uint32_t)hi << 16); }
 
 // geometry of a size class, shared with the host-side batch builder (xgpu_builder.hip)
 __host__ __device__ constexpr int itdq_group(int lw, int lh)
@@ -64,14 +73,171 @@ __host__ __device__ constexpr int itdq_group(int lw, int lh)
 
 #define ITDQ_PLANES_DWORDS 4608  // max over size classes of 2 planes x G*H*(W/2+1) dwords (16x16: 2*2304)
 #define ITDQ_LDS_DWORDS (ITDQ_PLANES_DWORDS + 2048)   // + 4096 dequantised s16 coefficients
-#define ITDQ_MAX_G 128           // TBs per work item (2x2 chroma blocks)
+#define ITDQ_MAX_G 32            // TBs per work item of the LDS form (4x8, 8x4, 8x8; the classes up to 16 samples keep up to 128 TBs in registers: itdq_small)
+#define ITDQ_TB_DWORDS (4 * ITDQ_MAX_G)               // per TB: row-pair mask, column-pair mask, the two dwords of its record
 
-// OR over the 64 lanes of the wave (every lane must take part)
-__device__ __forceinline__ uint32_t wave_or(uint32_t v)
+// Vector tuples a lane may sit out of loading (mc_filters.h: gload*_if): the value stays one register tuple from the load to its first use, so the place where the lane's
+// branch joins the wave again needs no copy that would wait for the load; a lane that sat out keeps whatever the registers held and never looks at them.
+typedef uint32_t itq_v2 __attribute__((ext_vector_type(2)));
+typedef uint32_t itq_v4 __attribute__((ext_vector_type(4)));
+typedef itq_v2 __attribute__((aligned(4))) itq_v2_u;
+typedef itq_v4 __attribute__((aligned(2))) itq_v4_u;
+typedef itq_v2 __attribute__((aligned(2))) itq_v2_s;
+template <typename T> __device__ __forceinline__ T itq_any() { T v; asm volatile("" : "=v"(v)); return v; }
+static_assert(sizeof(TbRec) == 8, "a TbRec is fetched as one 8-byte load: off | log2w, log2h, qp, log2s");
+__device__ __forceinline__ void itq_rec_if(itq_v2 &v, const TbRec *p, bool on) { if (on) v = *(const itq_v2_u *)p; }
+__device__ __forceinline__ int rec_qp(itq_v2 r) { return (int)((r.y >> 16) & 0xFF); }
+__device__ __forceinline__ int rec_log2s(itq_v2 r) { return (int)(r.y >> 24); }
+
+// Dequantisation of one coefficient (xevd_dquant, xevd_itdq.c:480-492; shift / offset :511-515; scale tables xevd_tbl.c:255-256: {..,72} with tool_iqt, {..,71} without):
+// clip16((c * mul + offset) >> shift), mul = scale[qp % 6] << (qp / 6), times 181 for a class with odd LW + LH, shift = bd - 9 + (LW + LH) / 2 (+ 8 when odd).
+// Even classes, 32 bits: qp < 96 (xgpu_builder.hip) gives mul <= 72 << 15; with |c| held to cmax = 2^23 >> (qp / 6) - which no s16 value exceeds up to qp 53 -
+// |c * mul| <= 72 * 2^23 < 2^30, so product + offset is exact in s32 and both factors fit v_mad_i32_i24.  A coefficient beyond cmax gives, held or not,
+// |c * mul| >= 40 * 2^23 > 2^(15 + shift) for every shift <= 13 (bit depths to 16): the result is clipped to the same end of the s16 range either way.
+// Odd classes keep the s64 form (c * 181 * mul needs 37 bits).
+template <bool ODD, bool IQT>
+struct ItdqScale {
+    int mul, cmax, shift, offset;
+    __device__ __forceinline__ ItdqScale(int qp, int bd, int lwh)
+    {
+        shift = bd - 9 + (lwh >> 1) + (ODD ? 8 : 0);
+        offset = shift == 0 ? 0 : 1 << (shift - 1);
+        const int q6 = (int)(((uint32_t)qp * 171u) >> 10), sidx = qp - 6 * q6;                      // qp / 6, qp % 6 for every u8
+        constexpr uint64_t scale = 40ull | 45ull << 8 | 51ull << 16 | 57ull << 24 | 64ull << 32 | (uint64_t)(IQT ? 72 : 71) << 40;
+        const int sbase = (int)((scale >> (8 * sidx)) & 0xFF);          // (a lookup: the ?: ladder was five nested divergent branches)
+        mul = sbase << q6;
+        cmax = (1 << 23) >> q6;
+    }
+    __device__ __forceinline__ int operator()(int c) const
+    {
+        if constexpr (!ODD) {
+            const int held = min(max(c, -cmax), cmax);
+            return clip16(mad24(held, mul, offset) >> shift);
+        }
+        const long long l = ((long long)(c * (ODD ? 181 : 1)) * mul + offset) >> shift;
+        return (int)min(max(l, -32768ll), 32767ll);
+    }
+};
+
+// OR of the masks of the TBs that the lanes of this wave belong to, lane t working on TB (t % (G * X)) / X: a run of min(G, max(1, 64 / X)) entries that starts at a
+// multiple of its length - independent LDS reads of wave-uniform addresses, one wait (an OR over the lanes through six dependent ds_bpermute round trips stood here).  Entries from the item's
+// count on were reset and never set.
+template <int G, int LX>
+__device__ __forceinline__ uint32_t wave_masks(const uint32_t *s_m, int t)
 {
+    constexpr int X = 1 << LX, PER = 64 / X > 1 ? 64 / X : 1, N = G < PER ? G : PER;
+    const int p0 = __builtin_amdgcn_readfirstlane(((t & ~63) % (G * X)) >> LX);
+    static_assert(G * X >= 64 ? (G % N == 0) : (64 % (G * X) == 0 && N == G), "the wave's TBs are entries [p0, p0 + N)");
+    uint32_t m = 0;
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v |= (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
+    for (int i = 0; i < N; i++) m |= s_m[p0 + i];
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
+}
+
+// wave-uniform matrix choice: DCT-II, or for ATS work items (4..32 only) DST-VII / DCT-VIII
+template <int L>
+__device__ __forceinline__ const uint32_t *itdq_matrix(int tr) { return (tr == TR_DCT2 || L < 2 || L > 5) ? k_tmp + tmp_base(L) : k_atsp[tr - 1] + atsp_base(L); }
+
+// The classes with at most 16 samples (2x2 .. 4x4, 2x8, 8x2: a quarter of a picture's work items, a twelfth of its samples): TB p of the item on lane p, the whole block
+// in registers - one load of its 8 / 16 / 32 contiguous bytes (log2s == log2w: only 64x64 sub-blocks keep a CU's stride), both stages as direct products with the
+// wave-uniform matrix pairs as scalar operands, the intermediate rounded and clipped (or split hi * 2^15 + lo) exactly like the LDS form.  No LDS, no barrier; lanes and
+// waves without a TB leave at once.
+template <int LW, int LH, bool IQT>
+__device__ __forceinline__ void itdq_small(const ItdqArgs &a, const TbWave wv)
+{
+    constexpr int W = 1 << LW, H = 1 << LH, S = W * H;
+    static_assert(S <= 16 && itdq_group(LW, LH) <= 256, "one TB per lane");
+    const int p = threadIdx.x;
+    if (p >= wv.count) return;
+    const itq_v2 rec = *(const itq_v2_u *)(a.tbs + wv.first + p);
+    const uint32_t *tmh = itdq_matrix<LH>(wv.tr_v), *tmw = itdq_matrix<LW>(wv.tr_h);
+    const bool s16_mid = IQT || wv.tr_v != TR_DCT2 || wv.tr_h != TR_DCT2;
+    uint32_t raw[S / 2];
+    if constexpr (S == 4) { const itq_v2 v = *(const itq_v2_s *)(a.coef + rec.x); raw[0] = v.x; raw[1] = v.y; }
+    else {
+#pragma unroll
+        for (int i = 0; i < S / 8; i++) {
+            const itq_v4 v = *(const itq_v4_u *)(a.coef + rec.x + 8 * i);
+            raw[4 * i] = v.x; raw[4 * i + 1] = v.y; raw[4 * i + 2] = v.z; raw[4 * i + 3] = v.w;
+        }
+    }
+    const ItdqScale<(LW + LH) & 1, IQT> dq(rec_qp(rec), a.bd, LW + LH);
+    int d[S];
+#pragma unroll
+    for (int i = 0; i < S / 2; i++) {
+        d[2 * i] = 0; d[2 * i + 1] = 0;
+        if (raw[i] != 0) { d[2 * i] = dq((int16_t)(raw[i] & 0xFFFF)); d[2 * i + 1] = dq((int16_t)(raw[i] >> 16)); }
+    }
+    // stage 1: columns j, pairs of coefficient rows; the results leave as the column pairs stage 2 multiplies
+    uint32_t mh[H][W / 2], ml[H][W / 2];
+#pragma unroll
+    for (int jj = 0; jj < W / 2; jj++) {
+        int acc[2][H];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+#pragma unroll
+            for (int n = 0; n < H; n++) acc[e][n] = 0;
+#pragma unroll
+            for (int k2 = 0; k2 < H / 2; k2++) {
+                const uint32_t vp = pack16(d[(2 * k2) * W + 2 * jj + e], d[(2 * k2 + 1) * W + 2 * jj + e]);
+#pragma unroll
+                for (int n = 0; n < H; n++) acc[e][n] = dot2(tmh[k2 * H + n], vp, acc[e][n]);
+            }
+        }
+#pragma unroll
+        for (int n = 0; n < H; n++) {
+            if (s16_mid) mh[n][jj] = pack16(clip16((acc[0][n] + 64) >> 7), clip16((acc[1][n] + 64) >> 7));      // xevdm_itdq.c ITX_SHIFT1 = 7
+            else if constexpr (!IQT) {
+                mh[n][jj] = pack16(acc[0][n] >> 15, acc[1][n] >> 15);                                         // |acc| < 2^28 -> hi in s16 range
+                ml[n][jj] = pack16(acc[0][n] & 0x7FFF, acc[1][n] & 0x7FFF);
+            }
+        }
+    }
+    // stage 2: rows
+    const int shift2 = s16_mid ? 12 - (a.bd - 8) : 7 + 12 - (a.bd - 8);
+    uint32_t out[S / 2];
+#pragma unroll
+    for (int r = 0; r < H; r++) {
+        int res[W];
+        if (s16_mid) {
+            int s[W];
+#pragma unroll
+            for (int n = 0; n < W; n++) s[n] = 1 << (shift2 - 1);
+#pragma unroll
+            for (int k2 = 0; k2 < W / 2; k2++) {
+#pragma unroll
+                for (int n = 0; n < W; n++) s[n] = dot2(tmw[k2 * W + n], mh[r][k2], s[n]);
+            }
+#pragma unroll
+            for (int n = 0; n < W; n++) res[n] = clip16(s[n] >> shift2);
+        } else if constexpr (!IQT) {
+            int sh[W], sl[W];
+#pragma unroll
+            for (int n = 0; n < W; n++) { sh[n] = 0; sl[n] = 0; }
+#pragma unroll
+            for (int k2 = 0; k2 < W / 2; k2++) {
+#pragma unroll
+                for (int n = 0; n < W; n++) { sh[n] = dot2(tmw[k2 * W + n], mh[r][k2], sh[n]); sl[n] = dot2(tmw[k2 * W + n], ml[r][k2], sl[n]); }
+            }
+            const long long add = 1ll << (shift2 - 1);
+#pragma unroll
+            for (int n = 0; n < W; n++) {
+                const long long s = (long long)sh[n] * 32768 + sl[n] + add;     // == the reference's s64 sum + rounding offset
+                res[n] = (int)min(max(s >> shift2, -32768ll), 32767ll);
+            }
+        }
+#pragma unroll
+        for (int n = 0; n < W; n += 2) out[(r * W + n) / 2] = pack16(res[n], res[n + 1]);
+    }
+    int16_t *dst = a.resid + rec.x;
+    if constexpr (S == 4) { itq_v2 v; v.x = out[0]; v.y = out[1]; *(itq_v2_s *)dst = v; }
+    else {
+#pragma unroll
+        for (int i = 0; i < S / 8; i++) {
+            itq_v4 v; v.x = out[4 * i]; v.y = out[4 * i + 1]; v.z = out[4 * i + 2]; v.w = out[4 * i + 3];
+            *(itq_v4_u *)(dst + 8 * i) = v;
+        }
+    }
 }
 
 // Sparsity masks (round 3): a coded block of a real stream holds a handful of non-zero coefficients at low frequencies.  Stage 0 records, per TB, which
@@ -82,8 +248,10 @@ __device__ __forceinline__ uint32_t wave_or(uint32_t v)
 // IQT: the sequence uses the 16-bit two-stage transforms (sps->tool_iqt) - every work item keeps a clipped s16 intermediate, so only ONE intermediate plane
 // exists in LDS (17 KB instead of 27 KB per workgroup) and the 32-bit split path is not compiled in: more workgroups per CU for a kernel that is bound by the
 // latency of its dependent loads, not by arithmetic.
+// The item is its chain of dependent round trips, so the requests come first: the TB records of all the lane's units are asked for before the mask reset and its barrier,
+// the coefficients of all units before the first dequantisation - two vector-memory waits between the item's first request and its first dot2.
 template <int LW, int LH, bool IQT>
-__device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, uint32_t *lds, uint32_t *s_rm, uint32_t *s_cm)
+__device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, uint32_t *lds, uint32_t *s_tb)
 {
     constexpr int W = 1 << LW, H = 1 << LH;
     constexpr int N1 = H > 16 ? 16 : H, C1 = H / N1;          // stage-1 outputs per lane, chunks
@@ -95,68 +263,76 @@ __device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, ui
     static_assert(2 * PLANE <= ITDQ_PLANES_DWORDS && G * W * H <= 4096 && G <= ITDQ_MAX_G, "LDS budget");
     constexpr int PLANES_DWORDS = IQT ? ITDQ_PLANES_DWORDS / 2 : ITDQ_PLANES_DWORDS;
     constexpr bool RMASK = H >= 16, CMASK = W >= 16;          // shorter transforms: the masks would cost more than the 2..4 loop rounds they can save
+    uint32_t *s_rm = s_tb, *s_cm = s_tb + ITDQ_MAX_G, *s_rec = s_tb + 2 * ITDQ_MAX_G;      // per TB: the two masks, its record (two dwords)
     const int t = threadIdx.x;
+
+    // ------------------------------------------------ stage 0: load + dequantise ---------------------------
+    // all coefficients of the G blocks in one coalesced sweep, dequantised once (ItdqScale) and parked in LDS as s16.  A lane has one or two load units (8 samples;
+    // 4 for 2x2): both units' records, then both units' coefficients are in flight together; a unit past the item's count forms no address.
+    constexpr int S = W * H, UN = S >= 8 ? 8 : 4, NU = G * S / UN, NR = (NU + 255) / 256;
+    typedef typename std::conditional<UN == 8, itq_v4, itq_v2>::type cvec;
+    bool on[NR];
+    int up[NR], uo[NR];
+    itq_v2 rec[NR];
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+        const int u = t + 256 * r;
+        up[r] = (u * UN) / S; uo[r] = (u * UN) % S;
+        on[r] = (NU % 256 == 0 || u < NU) && up[r] < wv.count;
+        rec[r] = itq_any<itq_v2>();
+        itq_rec_if(rec[r], a.tbs + wv.first + up[r], on[r]);
+    }
     if (RMASK || CMASK) {
         if (t < G) { s_rm[t] = 0; s_cm[t] = 0; }
         __syncthreads();
     }
-    // wave-uniform matrix choice: DCT-II, or for ATS work items (4..32 only) DST-VII / DCT-VIII
-    const uint32_t *tmh = (wv.tr_v == TR_DCT2 || LH < 2 || LH > 5) ? k_tmp + tmp_base(LH) : k_atsp[wv.tr_v - 1] + atsp_base(LH);
-    const uint32_t *tmw = (wv.tr_h == TR_DCT2 || LW < 2 || LW > 5) ? k_tmp + tmp_base(LW) : k_atsp[wv.tr_h - 1] + atsp_base(LW);
+    const uint32_t *tmh = itdq_matrix<LH>(wv.tr_v), *tmw = itdq_matrix<LW>(wv.tr_h);
     const bool s16_mid = IQT || wv.tr_v != TR_DCT2 || wv.tr_h != TR_DCT2;     // ATS keeps a clipped s16 intermediate like IQT (:406-421)
+    asm volatile("" :: "s"(tmh), "s"(tmw));                    // the tables' addresses now, under the records' round trip, not in front of stage 1's first row
     int16_t *ldsh = (int16_t *)lds;                            // plane 0: hi (or the IQT intermediate), plane 1: lo
     int16_t *ldsl = (int16_t *)(lds + PLANE);
     uint32_t *ldsc = lds + PLANES_DWORDS;                      // dequantised coefficients, [p][row][col] s16
-
-    // ------------------------------------------------ stage 0: load + dequantise ---------------------------
-    // all coefficients of the G blocks in one coalesced sweep (one memory round trip for the whole work item),
-    // dequantised once (xevd_dquant, xevd_itdq.c:480-492; shift/offset :511-515; scale tables xevd_tbl.c:255-256:
-    // {..,72} with tool_iqt, {..,71} without) and parked in LDS as s16
-    {
-        constexpr int S = W * H, UN = S >= 8 ? 8 : 4;           // samples per load unit
-        constexpr int odd = (LW + LH) & 1;
-        const int shift = 20 - 14 - (15 - a.bd - ((LW + LH) >> 1)) + (odd ? 8 : 0);
-        const long long offset = shift == 0 ? 0 : 1ll << (shift - 1);
-        for (int u = t; u < G * S / UN; u += 256) {
-            const int p = (u * UN) / S, o = (u * UN) % S;
-            if (p >= wv.count) break;
-            const TbRec tb = a.tbs[wv.first + p];
-            const int qp = tb.qp, sidx = qp % 6;
-            const int sbase = sidx == 0 ? 40 : sidx == 1 ? 45 : sidx == 2 ? 51 : sidx == 3 ? 57 : sidx == 4 ? 64 : (IQT ? 72 : 71);
-            const long long mul = (long long)(sbase << (qp / 6)) * (odd ? 181 : 1);
+    cvec cv[NR];
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+        cv[r] = itq_any<cvec>();
+        if (on[r]) {
             // row-major TB with row stride 2^log2s (a sub-block of a >64 CU keeps the CU's stride, xevd_itdq.c:573-584)
-            const int16_t *src = a.coef + tb.off + ((o >> LW) << tb.log2s) + (o & (W - 1));
-            uint32_t raw[UN / 2];
-            if constexpr (UN == 8) { const uint4 v = *(const uint4 *)src; raw[0] = v.x; raw[1] = v.y; raw[2] = v.z; raw[3] = v.w; }
-            else { const uint2 v = *(const uint2 *)src; raw[0] = v.x; raw[1] = v.y; }
-#pragma unroll
-            for (int i = 0; i < UN / 2; i++) {
-                if (raw[i] == 0) continue;
-                const int c0 = (int16_t)(raw[i] & 0xFFFF), c1 = (int16_t)(raw[i] >> 16);
-                const long long l0 = ((long long)c0 * mul + offset) >> shift, l1 = ((long long)c1 * mul + offset) >> shift;
-                const int v0 = (int)min(max(l0, -32768ll), 32767ll), v1 = (int)min(max(l1, -32768ll), 32767ll);
-                raw[i] = (uint32_t)(uint16_t)v0 | ((uint32_t)(uint16_t)v1 << 16);
-                if (RMASK) atomicOr(&s_rm[p], 1u << ((o + 2 * i) >> (LW + 1)));                  // row pair of this dword
-                if (CMASK) atomicOr(&s_cm[p], 1u << (((o + 2 * i) & (W - 1)) >> 1));              // column pair
-            }
-#pragma unroll
-            for (int i = 0; i < UN / 2; i++) ldsc[(p * S + o) / 2 + i] = raw[i];
+            const int16_t *src = a.coef + rec[r].x + ((uo[r] >> LW) << rec_log2s(rec[r])) + (uo[r] & (W - 1));
+            if constexpr (UN == 8) cv[r] = *(const itq_v4_u *)src; else cv[r] = *(const itq_v2_s *)src;
         }
+    }
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+        if (!on[r]) continue;
+        const int p = up[r], o = uo[r];
+        const ItdqScale<(LW + LH) & 1, IQT> dq(rec_qp(rec[r]), a.bd, LW + LH);
+        if (o == 0) { s_rec[2 * p] = rec[r].x; s_rec[2 * p + 1] = rec[r].y; }      // for stage 2's lanes, which belong to other TBs than stage 0's: an LDS read, not a second fetch
+        uint32_t raw[UN / 2];
+#pragma unroll
+        for (int i = 0; i < UN / 2; i++) raw[i] = cv[r][i];
+#pragma unroll
+        for (int i = 0; i < UN / 2; i++) {
+            if (raw[i] == 0) continue;
+            raw[i] = pack16(dq((int16_t)(raw[i] & 0xFFFF)), dq((int16_t)(raw[i] >> 16)));
+            if (RMASK) atomicOr(&s_rm[p], 1u << ((o + 2 * i) >> (LW + 1)));                  // row pair of this dword
+            if (CMASK) atomicOr(&s_cm[p], 1u << (((o + 2 * i) & (W - 1)) >> 1));              // column pair
+        }
+#pragma unroll
+        for (int i = 0; i < UN / 2; i++) ldsc[(p * S + o) / 2 + i] = raw[i];
     }
     __syncthreads();
 
     // ------------------------------------------------ stage 1: columns ------------------------------------
     uint32_t rows1 = 0;
-    if (RMASK) {
-        const int p1 = (t % (G * W)) >> LW;
-        rows1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_or((t < G * W * C1 && p1 < wv.count) ? s_rm[p1] : 0u));
-    }
+    if (RMASK) rows1 = wave_masks<G, LW>(s_rm, t);
     if (t < G * W * C1) {
         const int idx = t % (G * W);
         int chunk = t / (G * W);
         if (UNI1) chunk = __builtin_amdgcn_readfirstlane(chunk);
         const int p = idx >> LW, j = idx & (W - 1);
         const bool valid = p < wv.count;
+        const uint32_t vmask = valid ? 0xFFFFFFFFu : 0u;      // the LDS reads are unconditional (a TB past the count holds whatever was there): no branch with a wait of its own around them
         const int16_t *src = (const int16_t *)ldsc + p * (W * H) + j;
 
         int acc[N1];
@@ -165,14 +341,14 @@ __device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, ui
         if (RMASK) {
             for (uint32_t m = rows1; m; m &= m - 1) {          // the row pairs that hold a coefficient in one of this wave's TBs
                 const int k2 = __builtin_ctz(m);
-                const uint32_t vp = valid ? ((uint32_t)(uint16_t)src[(2 * k2) * W] | ((uint32_t)(uint16_t)src[(2 * k2 + 1) * W] << 16)) : 0u;
+                const uint32_t vp = pack16(src[(2 * k2) * W], src[(2 * k2 + 1) * W]) & vmask;
                 const uint32_t *row = tmh + k2 * H + chunk * N1;
 #pragma unroll
                 for (int n = 0; n < N1; n++) acc[n] = dot2(row[n], vp, acc[n]);
             }
         } else {
             for (int k2 = 0; k2 < H / 2; k2++) {
-                const uint32_t vp = valid ? ((uint32_t)(uint16_t)src[(2 * k2) * W] | ((uint32_t)(uint16_t)src[(2 * k2 + 1) * W] << 16)) : 0u;
+                const uint32_t vp = pack16(src[(2 * k2) * W], src[(2 * k2 + 1) * W]) & vmask;
                 if (__ballot(vp != 0) == 0) continue;              // both coefficient rows zero across this wave
                 const uint32_t *row = tmh + k2 * H + chunk * N1;
 #pragma unroll
@@ -197,10 +373,7 @@ __device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, ui
 
     // ------------------------------------------------ stage 2: rows ---------------------------------------
     uint32_t cols2 = 0;
-    if (CMASK) {
-        const int p2 = (t % (G * H)) >> LH;
-        cols2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_or((t < G * H * C2 && p2 < wv.count) ? s_cm[p2] : 0u));
-    }
+    if (CMASK) cols2 = wave_masks<G, LH>(s_cm, t);
     if (t < G * H * C2) {
         const int idx = t % (G * H);
         int chunk = t / (G * H);
@@ -209,7 +382,8 @@ __device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, ui
         if (p >= wv.count) return;
         // a column pair outside this TB's own mask was not written by stage 1 (it may be set for another TB of the wave): reads as zero
         const uint32_t own = CMASK ? s_cm[p] : 0xFFFFFFFFu;
-        const TbRec tb = a.tbs[wv.first + p];
+        itq_v2 tb;
+        tb.x = s_rec[2 * p]; tb.y = s_rec[2 * p + 1];
         const int shift2 = s16_mid ? 12 - (a.bd - 8) : 7 + 12 - (a.bd - 8);
         const uint32_t *inh = lds + (p * H + r) * RS;
         const uint32_t *inl = inh + PLANE;
@@ -221,7 +395,7 @@ __device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, ui
             if (CMASK) {
                 for (uint32_t m = cols2; m; m &= m - 1) {
                     const int k2 = __builtin_ctz(m);
-                    const uint32_t vp = ((own >> k2) & 1) ? inh[k2] : 0u;
+                    const uint32_t vp = inh[k2] & (0u - ((own >> k2) & 1));
                     const uint32_t *row = tmw + k2 * W + chunk * N2;
 #pragma unroll
                     for (int n = 0; n < N2; n++) s[n] = dot2(row[n], vp, s[n]);
@@ -244,8 +418,8 @@ __device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, ui
             if (CMASK) {
                 for (uint32_t m = cols2; m; m &= m - 1) {
                     const int k2 = __builtin_ctz(m);
-                    const bool mine = (own >> k2) & 1;
-                    const uint32_t vh = mine ? inh[k2] : 0u, vl = mine ? inl[k2] : 0u;
+                    const uint32_t mine = 0u - ((own >> k2) & 1);
+                    const uint32_t vh = inh[k2] & mine, vl = inl[k2] & mine;
                     const uint32_t *row = tmw + k2 * W + chunk * N2;
 #pragma unroll
                     for (int n = 0; n < N2; n++) { sh[n] = dot2(row[n], vh, sh[n]); sl[n] = dot2(row[n], vl, sl[n]); }
@@ -266,34 +440,39 @@ __device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, ui
                 res[n] = (int)min(max(s >> shift2, -32768ll), 32767ll);
             }
         }
-        int16_t *out = a.resid + tb.off + (r << tb.log2s) + chunk * N2;
+        int16_t *out = a.resid + tb.x + (r << rec_log2s(tb)) + chunk * N2;
         if constexpr (N2 >= 8) {
 #pragma unroll
             for (int n = 0; n < N2; n += 8) {
                 uint4 v;
-                v.x = (uint32_t)(uint16_t)res[n + 0] | ((uint32_t)(uint16_t)res[n + 1] << 16);
-                v.y = (uint32_t)(uint16_t)res[n + 2] | ((uint32_t)(uint16_t)res[n + 3] << 16);
-                v.z = (uint32_t)(uint16_t)res[n + 4] | ((uint32_t)(uint16_t)res[n + 5] << 16);
-                v.w = (uint32_t)(uint16_t)res[n + 6] | ((uint32_t)(uint16_t)res[n + 7] << 16);
+                v.x = pack16(res[n + 0], res[n + 1]);
+                v.y = pack16(res[n + 2], res[n + 3]);
+                v.z = pack16(res[n + 4], res[n + 5]);
+                v.w = pack16(res[n + 6], res[n + 7]);
                 *(uint4 *)(out + n) = v;
             }
         } else if constexpr (N2 == 4) {
             uint2 v;
-            v.x = (uint32_t)(uint16_t)res[0] | ((uint32_t)(uint16_t)res[1] << 16);
-            v.y = (uint32_t)(uint16_t)res[2] | ((uint32_t)(uint16_t)res[3] << 16);
+            v.x = pack16(res[0], res[1]);
+            v.y = pack16(res[2], res[3]);
             *(uint2 *)out = v;
         } else {
-            *(uint32_t *)out = (uint32_t)(uint16_t)res[0] | ((uint32_t)(uint16_t)res[1] << 16);
+            *(uint32_t *)out = pack16(res[0], res[1]);
         }
     }
 }
 
-// one work item; lds = ITDQ_LDS_DWORDS dwords (IQT: minus half the planes), s_rm / s_cm = ITDQ_MAX_G dwords each; all 256 threads of the workgroup call it
+// one work item; lds = ITDQ_LDS_DWORDS dwords (IQT: minus half the planes), s_tb = ITDQ_TB_DWORDS dwords; all 256 threads of the workgroup call it
 template <bool IQT>
-__device__ __forceinline__ void itdq_dispatch(const ItdqArgs &a, int wi, uint32_t *lds, uint32_t *s_rm, uint32_t *s_cm)
+__device__ __forceinline__ void itdq_dispatch(const ItdqArgs &a, int wi, uint32_t *lds, uint32_t *s_tb)
 {
-    const TbWave wv = a.waves[wi];
-#define CASE(lw, lh) case (lw) * 8 + (lh): itdq_item<lw, lh, IQT>(a, wv, lds, s_rm, s_cm); break;
+    // the record as three scalar loads (its u16 / u8 fields one by one came as vector loads + v_readfirstlane: a vector round trip in front of everything)
+    static_assert(sizeof(TbWave) == 12 && alignof(TbWave) == 4, "TbWave is read as three dwords");
+    const uint32_t *w = (const uint32_t *)(a.waves + wi);
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+    TbWave wv;
+    wv.first = w0; wv.count = (uint16_t)(w1 & 0xFFFF); wv.log2w = (uint8_t)(w1 >> 16); wv.log2h = (uint8_t)(w1 >> 24); wv.tr_v = (uint8_t)w2; wv.tr_h = (uint8_t)(w2 >> 8);
+#define CASE(lw, lh) case (lw) * 8 + (lh): if constexpr ((lw) + (lh) <= 4) itdq_small<lw, lh, IQT>(a, wv); else itdq_item<lw, lh, IQT>(a, wv, lds, s_tb); break;
 #define ROW(lw) CASE(lw, 1) CASE(lw, 2) CASE(lw, 3) CASE(lw, 4) CASE(lw, 5) CASE(lw, 6)
     switch (wv.log2w * 8 + wv.log2h) {
         ROW(1) ROW(2) ROW(3) ROW(4) ROW(5) ROW(6)

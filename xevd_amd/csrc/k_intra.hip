@@ -768,6 +768,10 @@ __global__ __launch_bounds__(64 * INTRA_WAVES) void k_intra(const IntraArgs a)
 //  28.8 at 1080p.)
 // (Round 3, measured and dropped: ONE launch for all levels - the level-1 CUs at the head of this launch's list, publishing flags like everybody else, strand
 // members waiting for their level-1 CUs - instead of the plain level-1 launch in front: bit-exact, 8K 2764 -> 2587 frames/s, 4K 8172 -> 7860, 1080p 10996 -> 11163.)
+// (The pass's work item since profiles/residual_item_chain.txt: the launch is (items / items in flight) x (life of an item), the life is a chain of dependent round trips, and the
+//  chain lost its first vector round trip (the item's record, now scalar loads), stage 2's second fetch of the TB records (LDS) and the six ds_bpermute of each mask union; 2001 of cfg4's
+//  7531 items (blocks of up to 16 samples) run without LDS and barriers: 60.7 -> 52.3 us at cfg4 in rocprofv3.  The share of the grid the chain is spread over, measured again
+//  behind the shorter pass, 25 / 35 / 50 / 65 / 75 %: ms per picture 0.2999 / 0.2966 / 0.2972 / 0.2993 / 0.3035 (three alternating runs each, spread of one build 0.005) - one half stays.)
 #define FUSED_WAVES 4
 // (Round 5: the residual pass alone needs 44 VGPRs, this kernel 121 - 145 because of the chain's side, so the pass rides at half its own occupancy.  Holding the kernel to
 //  96 / 80 / 64 VGPRs (amdgpu_waves_per_eu 5 / 6 / 8: 72 / 172 / 236 bytes of scratch, all in the chain's side) measured 3035 / 2740 / 2602 frames/s against 3052 at 8K, 8050 /
@@ -775,7 +779,7 @@ __global__ __launch_bounds__(64 * INTRA_WAVES) void k_intra(const IntraArgs a)
 template <int EIPD, bool IBC, bool IQT>
 __global__ __launch_bounds__(64 * FUSED_WAVES) void k_intra_itdq(const IntraArgs a, const ItdqArgs r, uint32_t n_intra_wg, uint64_t rate)
 {
-    constexpr int ITDQ_DW = (IQT ? ITDQ_LDS_DWORDS - ITDQ_PLANES_DWORDS / 2 : ITDQ_LDS_DWORDS) + 2 * ITDQ_MAX_G, INTRA_DW = (FUSED_WAVES * IntraLds<false>::WAVE + 1) / 2 + 4;
+    constexpr int ITDQ_DW = (IQT ? ITDQ_LDS_DWORDS - ITDQ_PLANES_DWORDS / 2 : ITDQ_LDS_DWORDS) + ITDQ_TB_DWORDS, INTRA_DW = (FUSED_WAVES * IntraLds<false>::WAVE + 1) / 2 + 4;
     __shared__ __attribute__((aligned(16))) uint32_t raw[ITDQ_DW > INTRA_DW ? ITDQ_DW : INTRA_DW];
     // The chain's workgroups are spread evenly over the first `span` blocks of the grid (the host passes half of it) instead of all in front: the list is sorted by
     // level and tickets are drawn in the order the workgroups start, so a level's CUs arrive about when the level before them is done - in front, 4 400 waves that
@@ -792,8 +796,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_intra_itdq(const IntraArgs
     } else {
         const int wi = (int)(blockIdx.x - before);
         if (wi >= r.n_waves) return;
-        uint32_t *s_rm = raw + ITDQ_DW - 2 * ITDQ_MAX_G;
-        itdq_dispatch<IQT>(r, wi, raw, s_rm, s_rm + ITDQ_MAX_G);
+        itdq_dispatch<IQT>(r, wi, raw, raw + ITDQ_DW - ITDQ_TB_DWORDS);
     }
 }
 

@@ -9,7 +9,8 @@
 //                         matrix entries a wave needs are wave-uniform and live in SGPRs (scalar loads from
 //                         constant memory, packed as s16 row PAIRS); two taps per v_dot2c_i32_i16; coefficient
 //                         row pairs that are zero across the whole wave are skipped (ballot) - most
-//                         high-frequency rows are; dequantisation (s64 like xevd_dquant) happens on the fly;
+//                         high-frequency rows are; dequantisation happens once, in front of it (32 bits where the class
+//                         allows, s64 like xevd_dquant otherwise: ItdqScale);
 //   transpose through LDS as packed s16 (row stride W/2+1 dwords: conflict-free column writes and row reads);
 //   stage 2 (horizontal): lane = one ROW of one TB, wave = one chunk of 16 output columns.  The reference's
 //                         non-IQT path keeps a 32-bit intermediate and a 64-bit sum: the intermediate t
@@ -19,18 +20,19 @@
 //                         IQT keeps a clipped s16 intermediate, one chain.
 // The reference's partial butterflies are an evaluation order of exact integer dot products; a direct product
 // with the same matrices is bit-identical (matrices and arithmetic pinned in tests/test_oracle_vs_ref.py).
-// No MFMA (north_star: integer butterflies, not dense contractions); bound by VALU issue on 32/64-point TBs
-// and by HBM on small ones.
+// Blocks of up to 16 samples never see LDS: a lane takes a whole TB through both stages in registers (itdq_small).
+// No MFMA (north_star: integer butterflies, not dense contractions); bound by the chain of dependent round trips of
+// a work item (its record, its TB records, its coefficients), not by arithmetic: itdq_body.h.
 #include "itdq_body.h"
 
 template <bool IQT>
 __global__ __launch_bounds__(256) void k_itdq(const ItdqArgs a)
 {
     __shared__ uint32_t lds[IQT ? ITDQ_LDS_DWORDS - ITDQ_PLANES_DWORDS / 2 : ITDQ_LDS_DWORDS];
-    __shared__ uint32_t s_rm[ITDQ_MAX_G], s_cm[ITDQ_MAX_G];      // per TB: coefficient row pairs / column pairs that are not all zero
+    __shared__ uint32_t s_tb[ITDQ_TB_DWORDS];                    // per TB: coefficient row pairs / column pairs that are not all zero, its record
     const int wi = blockIdx.x;
     if (wi >= a.n_waves) return;
-    itdq_dispatch<IQT>(a, wi, lds, s_rm, s_cm);
+    itdq_dispatch<IQT>(a, wi, lds, s_tb);
 }
 
 int itdq_group_size(int lw, int lh) { return itdq_group(lw, lh); }
