@@ -562,6 +562,12 @@ static void dmvr_process(const xgpu_seq_params *sp, const orc_frame *fr, int x, 
     int l, sx, sy, num = 0;
     mv_clip(x, y, sp->width, sp->height, w, h, refi, mv, start);
     for (l = 0; l < 2; l++) {
+        if (start[l][0] > mv[l][0]) g_cen.dmvr_start_clip[0]++;
+        if (start[l][0] < mv[l][0]) g_cen.dmvr_start_clip[1]++;
+        if (start[l][1] > mv[l][1]) g_cen.dmvr_start_clip[2]++;
+        if (start[l][1] < mv[l][1]) g_cen.dmvr_start_clip[3]++;
+    }
+    for (l = 0; l < 2; l++) {
         /* xevdm_bl_mc_l (:358-486): (w + 4) x (h + 4) samples from two samples up-left of the starting position, 2-tap { 64 - 4p, 4p } in the
            regimes of the long filters */
         const orc_pic *rp = &fr->refp[refi[l]][l];
@@ -569,36 +575,48 @@ static void dmvr_process(const xgpu_seq_params *sp, const orc_frame *fr, int x, 
         const int16_t tx[2] = { (int16_t)(64 - 4 * (gx & 15)), (int16_t)(4 * (gx & 15)) }, ty[2] = { (int16_t)(64 - 4 * (gy & 15)), (int16_t)(4 * (gy & 15)) };
         bl[l] = (int16_t *)malloc(sizeof(int16_t) * (size_t)stride * (h + 2 * IT));
         g_cen_plane = 0;
+        g_cen.dmvr_regime[0][((gx & 15) != 0) * 2 + ((gy & 15) != 0)]++;
         fir_block(rp->y, gx, gy, rp->s_l, stride, bl[l], w + 2 * IT, h + 2 * IT, bd, (gx & 15) != 0, (gy & 15) != 0, 2, 4, tx, ty);
     }
     for (sy = 0; sy < h; sy += dy) for (sx = 0; sx < w; sx += dx, num++) {
         const int16_t *c0 = bl[0] + (IT + sy) * stride + IT + sx, *c1 = bl[1] + (IT + sy) * stride + IT + sx;
         int tot[2] = { 0, 0 }, not_zero = 1, min_cost = 0, cost[9], i, k;
         int32_t ref16[2][2];
+        g_cen.dmvr_shape[(dx == 16) * 2 + (dy == 16)]++;
         for (k = 0; k < 9; k++) cost[k] = 0x7FFFFFFF;
         for (i = 0; i < IT; i++) {
             const int16_t *a0 = c0 + tot[0] + tot[1] * stride, *a1 = c1 - (tot[0] + tot[1] * stride);
-            int ox[5] = { 0, 0, 1, -1, 0 }, oy[5] = { 1, -1, 0, 0, 0 }, d[2] = { 0, 0 }, idx;
+            int ox[5] = { 0, 0, 1, -1, 0 }, oy[5] = { 1, -1, 0, 0, 0 }, d[2] = { 0, 0 }, idx, win = -1;
             for (k = 0; k < 9; k++) cost[k] = 0x7FFFFFFF;
             if (i == 0) min_cost = dmvr_cost(dx, dy, a0, a1, stride);
-            if ((i > 0 && min_cost == 0) || (i == 0 && min_cost < dx * dy)) { not_zero = 0; break; }
+            if ((i > 0 && min_cost == 0) || (i == 0 && min_cost < dx * dy)) { not_zero = 0; g_cen.dmvr_exit[i ? 2 : 0]++; break; }
             cost[CENTER] = min_cost;
             for (idx = BOTTOM; idx <= DIAG; idx++) {      /* xevd_DMVR_refine: below, above, right, left, then the diagonal between the better two */
                 const int c = dmvr_cost(dx, dy, a0 + ox[idx] + oy[idx] * stride, a1 - ox[idx] - oy[idx] * stride, stride);
                 cost[idx] = c;
-                if (idx == LEFT) { ox[DIAG] = cost[RIGHT] <= cost[LEFT] ? 1 : -1; oy[DIAG] = cost[BOTTOM] <= cost[TOP] ? 1 : -1; }
-                if (c < min_cost) { min_cost = c; d[0] = ox[idx]; d[1] = oy[idx]; }
+                if (idx == LEFT) {
+                    ox[DIAG] = cost[RIGHT] <= cost[LEFT] ? 1 : -1; oy[DIAG] = cost[BOTTOM] <= cost[TOP] ? 1 : -1;
+                    g_cen.dmvr_diag[(ox[DIAG] < 0) | (oy[DIAG] < 0) << 1]++;
+                    if (cost[RIGHT] == cost[LEFT]) g_cen.dmvr_tie[0]++;
+                    if (cost[BOTTOM] == cost[TOP]) g_cen.dmvr_tie[1]++;
+                }
+                if (c < min_cost) { min_cost = c; d[0] = ox[idx]; d[1] = oy[idx]; win = idx; }
             }
-            if (d[0] == 0 && d[1] == 0) break;
+            if (d[0] == 0 && d[1] == 0) { g_cen.dmvr_exit[i ? 3 : 1]++; break; }
+            g_cen.dmvr_win[i][win]++;
+            if (i == IT - 1) g_cen.dmvr_exit[4]++;
             tot[0] += d[0]; tot[1] += d[1];
         }
+        g_cen.dmvr_total[tot[1] + 2][tot[0] + 2]++;
         tot[0] <<= 4; tot[1] <<= 4;
         if (not_zero && min_cost == cost[CENTER]) {      /* the centre of the last round won: parametric error surface through its cross */
             const int sb[5] = { cost[CENTER], cost[LEFT], cost[TOP], cost[RIGHT], cost[BOTTOM] };
             int a;
             for (a = 0; a < 2; a++) {
                 const int64_t nu = (int64_t)((sb[1 + a] - sb[3 + a]) << 4), de = (int64_t)(sb[1 + a] + sb[3 + a] - (sb[0] << 1));
+                const int before = tot[a];
                 if (de != 0) tot[a] += (sb[1 + a] != sb[0] && sb[3 + a] != sb[0]) ? dmvr_div_q7(nu, de) : (sb[1 + a] == sb[0] ? -8 : 8);
+                g_cen.dmvr_subpel[a][de != 0 ? tot[a] - before + 8 : 17]++;
             }
         }
         for (l = 0; l < 2; l++) {
@@ -619,6 +637,14 @@ static void dmvr_process(const xgpu_seq_params *sp, const orc_frame *fr, int x, 
             const int dcx = (clip ? mvc[0] >> 3 : ref16[l][0] >> 5) - (start[l][0] >> 3), dcy = (clip ? mvc[1] >> 3 : ref16[l][1] >> 5) - (start[l][1] >> 3);
             int16_t buf[(16 + 7 + 4) * (16 + 7 + 4)], tx[8], ty[8];
             int r, c, comp;
+            if (mvc[0] > tq[0]) g_cen.dmvr_sub_clip[0]++;
+            if (mvc[0] < tq[0]) g_cen.dmvr_sub_clip[1]++;
+            if (mvc[1] > tq[1]) g_cen.dmvr_sub_clip[2]++;
+            if (mvc[1] < tq[1]) g_cen.dmvr_sub_clip[3]++;
+            g_cen.dmvr_win_off[0][abs(dlx) <= 3 ? dlx + 3 : 7]++; g_cen.dmvr_win_off[0][abs(dly) <= 3 ? dly + 3 : 7]++;
+            g_cen.dmvr_win_off[1][abs(dcx) <= 2 ? dcx + 3 : 7]++; g_cen.dmvr_win_off[1][abs(dcy) <= 2 ? dcy + 3 : 7]++;
+            g_cen.dmvr_regime[1][((gx & 15) != 0) * 2 + ((gy & 15) != 0)]++;
+            g_cen.dmvr_regime[2][((gx & 31) != 0) * 2 + ((gy & 31) != 0)]++;
             /* luma: (dx + 7) x (dy + 7) window, 2 samples of replicate padding = clamped indexing */
             for (r = 0; r < dy + 11; r++) for (c = 0; c < dx + 11; c++) {
                 const int rr = r - 2 < 0 ? 0 : (r - 2 > dy + 6 ? dy + 6 : r - 2), cc = c - 2 < 0 ? 0 : (c - 2 > dx + 6 ? dx + 6 : c - 2);
@@ -658,9 +684,9 @@ int orc_dmvr_cu(const xgpu_seq_params *sp, const orc_frame *fr, int x, int y, in
     if (refi[0] < 0 || refi[1] < 0 || w < 8 || h < 8) return 0;
     {
         const int poc_c = fr->cur.poc, poc0 = fr->refp[refi[0]][0].poc, poc1 = fr->refp[refi[1]][1].poc;
-        if (!((poc_c - poc0) * (poc_c - poc1) < 0 && abs(poc_c - poc0) == abs(poc_c - poc1))) return 0;
+        if (!((poc_c - poc0) * (poc_c - poc1) < 0 && abs(poc_c - poc0) == abs(poc_c - poc1))) { g_cen.dmvr_not_refined[0]++; return 0; }
         mv_clip(x, y, sp->width, sp->height, w, h, refi, mv, mv_t);
-        if (poc0 == poc1 && mv_t[0][0] == mv_t[1][0] && mv_t[0][1] == mv_t[1][1]) return 0;
+        if (poc0 == poc1 && mv_t[0][0] == mv_t[1][0] && mv_t[0][1] == mv_t[1][1]) { g_cen.dmvr_not_refined[1]++; return 0; }
     }
     dmvr_process(sp, fr, x, y, w, h, refi, mv, pred0, pred1, refined);
     for (i = 0; i < w * h; i++) pred0[0][i] = (int16_t)((pred0[0][i] + pred1[0][i] + 1) >> 1);

@@ -125,6 +125,20 @@ typedef struct orc_census {
     uint32_t mv_clip[4];                               /* vectors moved by xevd_mv_clip: left / right / top / bottom threshold */
     uint32_t recon_coded, recon_wrap;                  /* residual-added samples / sums that wrapped in s16 */
     uint32_t recon_clip[2];                            /* reconstructed samples clipped */
+    /* DMVR (orc_dmvr_cu / dmvr_process).  Sub-blocks are the refined 16x16 (or smaller) units; sides are left / right / top / bottom like mv_clip */
+    uint32_t dmvr_shape[4];                            /* refined sub-blocks of 8x8 / 8x16 / 16x8 / 16x16 (w x h) */
+    uint32_t dmvr_not_refined[2];                      /* flagged bi-predicted CUs of at least 8x8 left to the ordinary path: references not POC-symmetric / identical motion */
+    uint32_t dmvr_exit[5];                             /* how the search ended: early (cost < dx * dy) / centre won round 0 / cost 0 after round 0's move / centre won round 1 / moved twice */
+    uint32_t dmvr_win[2][5];                           /* [round] the winner of a round that moved: below / above / right / left / the diagonal */
+    uint32_t dmvr_diag[4];                             /* the diagonal tried, per round: (x < 0) | (y < 0) << 1 */
+    uint32_t dmvr_tie[2];                              /* rounds with right == left / below == above at the <= that picks the diagonal */
+    uint32_t dmvr_subpel[2][18];                       /* [x / y] sub-sample step -8 .. 8 at [step + 8]; [17]: denominator 0, no step */
+    uint32_t dmvr_total[5][5];                         /* [y + 2][x + 2] whole-sample displacement the search ended at */
+    uint32_t dmvr_start_clip[4];                       /* starting vectors (per list) of refined CUs moved by mv_clip */
+    uint32_t dmvr_sub_clip[4];                         /* refined vectors (per list and sub-block) clipped at the sub-block (dmvr_clip_one) */
+    uint32_t dmvr_win_off[2][8];                       /* [luma / chroma] whole-sample offset of the refined position from the window fetched at the starting vector, both axes and
+                                                          lists: -3 .. 3 at [offset + 3]; [7]: further */
+    uint32_t dmvr_regime[3][4];                        /* [bilinear (per CU and list) / luma / chroma (per sub-block and list)][(fx != 0) * 2 + (fy != 0)] */
 } orc_census;
 void orc_census_reset(void);
 void orc_census_get(orc_census *out);

@@ -33,7 +33,10 @@ class OrcCensus(C.Structure):
                 ("addb_bs4", (C.c_uint32 * 2) * 2), ("addb_apq", C.c_uint32 * 4), ("addb_d0", (C.c_uint32 * 2) * 2), ("addb_out_clip", (C.c_uint32 * 2) * 2),
                 ("addb_lost", C.c_uint32 * 3), ("addb_tile_edge", C.c_uint32 * 2), ("alf_class", C.c_uint32 * 25), ("alf_tr", C.c_uint32 * 4),
                 ("alf_clip", (C.c_uint32 * 2) * 3), ("mc_clip", (C.c_uint32 * 2) * 3), ("mc_stage1_wrap", C.c_uint32), ("mc_bi", C.c_uint32 * 3),
-                ("mc_bi_rails", C.c_uint32 * 3), ("mv_clip", C.c_uint32 * 4), ("recon_coded", C.c_uint32), ("recon_wrap", C.c_uint32), ("recon_clip", C.c_uint32 * 2)]
+                ("mc_bi_rails", C.c_uint32 * 3), ("mv_clip", C.c_uint32 * 4), ("recon_coded", C.c_uint32), ("recon_wrap", C.c_uint32), ("recon_clip", C.c_uint32 * 2),
+                ("dmvr_shape", C.c_uint32 * 4), ("dmvr_not_refined", C.c_uint32 * 2), ("dmvr_exit", C.c_uint32 * 5), ("dmvr_win", (C.c_uint32 * 5) * 2),
+                ("dmvr_diag", C.c_uint32 * 4), ("dmvr_tie", C.c_uint32 * 2), ("dmvr_subpel", (C.c_uint32 * 18) * 2), ("dmvr_total", (C.c_uint32 * 5) * 5),
+                ("dmvr_start_clip", C.c_uint32 * 4), ("dmvr_sub_clip", C.c_uint32 * 4), ("dmvr_win_off", (C.c_uint32 * 8) * 2), ("dmvr_regime", (C.c_uint32 * 4) * 3)]
 
 
 def census_reset():

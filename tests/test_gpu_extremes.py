@@ -1,7 +1,8 @@
 """GPU suite, ends of the ranges (run with -m gpu on an MI355X): the HIP backend against the CPU oracle on the extreme cases of tests/extreme_inputs.py -
 samples on the rails, 0 / max checkerboards through every interpolation phase, QP 0..51 x ADDB slice offsets -12..12 (packed and scalar line filters),
-ALF coefficients at their legal limits on gratings / noise / checkerboards, vectors on the MV-clip thresholds - all three padded planes and the residual
-arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
+ALF coefficients at their legal limits on gratings / noise / checkerboards, vectors on the MV-clip thresholds, every branch of the DMVR search (planted
+displacements, vectors on the thresholds, all sub-block shapes; also its refined vectors, and the scalar form of its prediction) - all three padded planes and the
+residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
 reach the branches they are for) are repeated here because this file needs only the oracle, which always ships."""
 import numpy as np
 import pytest
@@ -55,6 +56,63 @@ def test_gpu_extreme_case_residual_pass_ahead(name):
     """once per family with the residual pass queued inside the previous picture's launch (xgpu_batch_recon_ahead)"""
     spec = next(s for s in xi.EXTREME_CASES if s[0] == name)
     _check(cases.build_case(*spec[:9]), name + " (ahead)", ahead=True)
+
+
+# ---- DMVR: the cases of xi.DMVR_CASES (every branch of the search, test_dmvr_cases_together_reach_every_branch) - planes and residual arena in test_gpu_extreme_case above
+def _check_dmvr(cs, what, **kw):
+    """planes and refined vectors: the vectors tell a failure of the search from one of the refined prediction"""
+    ref, _, _, _ = cases.run_cpu("oracle", cs)
+    want = cases.dmvr_mvs("oracle", cs)
+    out, mvs = cases.run_gpu(cs, dmvr=True, **kw)
+    got = np.asarray(mvs).reshape(-1, 2, 2)
+    assert len(want) > 0 and got.shape == want.shape, (got.shape, want.shape)
+    assert np.array_equal(got, want), f"{what}: refined vectors, first differences at sub-blocks {sorted(set(np.argwhere(got != want)[:, 0].tolist()))[:4]}"
+    _same(out, ref, what)
+
+
+@pytest.mark.parametrize("spec", xi.DMVR_CASES, ids=[s[0] for s in xi.DMVR_CASES])
+def test_gpu_dmvr_case_vectors(spec):
+    _check_dmvr(cases.build_case(*spec[:9]), spec[0])
+
+
+@pytest.mark.parametrize("spec", xi.DMVR_CASES, ids=[s[0] for s in xi.DMVR_CASES])
+def test_gpu_dmvr_case_residual_pass_ahead(spec):
+    _check_dmvr(cases.build_case(*spec[:9]), spec[0] + " (ahead)", ahead=True)
+
+
+_DMVR_SCALAR = xi.DMVR_CASES + [s for s in xi.EXTREME_CASES if s[0] in ("x_dmvr_checker_10b", "x_dmvr_noise_8b")]
+
+
+@pytest.mark.parametrize("spec", _DMVR_SCALAR, ids=[s[0] for s in _DMVR_SCALAR])
+def test_gpu_extreme_case_scalar_dmvr(spec, monkeypatch):
+    """k_dmvr's scalar form of the refined prediction (XEVD_HIP_DMVR_SCALAR is read when a context opens).  Valid input never reaches it - the refined position lies at most
+    2 luma / 1 chroma samples from the starting vector's window (tests/test_oracle_extremes.py), the packed form covers 3 / 2 -, so it runs here or nowhere."""
+    monkeypatch.setenv("XEVD_HIP_DMVR_SCALAR", "1")
+    _check_dmvr(cases.build_case(*spec[:9]), spec[0] + " (scalar DMVR)")
+
+
+@pytest.mark.parametrize("name", ["x_dmvr_thresholds_10b", "x_dmvr_thresholds_8b_noaddb"])
+def test_gpu_dmvr_case_stored_vectors(name):
+    """the vectors the picture keeps (side-information export) against the oracle's map: the unrefined ones under ADDB, the refined ones - the baseline filter reads them - without
+    (the export hands out torch tensors: whichever test of a run needs torch first pays for its import)"""
+    import side_info_ref as sr
+    from test_gpu_side_info import decode, open_decoder, start
+    spec = next(s for s in xi.DMVR_CASES if s[0] == name)
+    cs = cases.build_case(*spec[:9])
+    _, _, maps, _ = cases.run_cpu("oracle", cs, pad=False)
+    want = sr.blocks_from_maps(maps, maps.map_scu, cs["batch"], {k: p.poc for k, p in cs["refs"].items()}, cases.CUR_POC)
+    with open_decoder(cs) as dec:
+        slots, cur, hb = start(dec, cs)
+        decode(dec, cs, slots, cur, hb)
+        got = dec.frame_side_info(cur).cpu().numpy()
+    for p in range(4):
+        assert np.array_equal(got[p], want[p]), f"{name}: vector plane {p}, first differences at 4x4 units {np.argwhere(got[p] != want[p])[:4].tolist()}"
+    # and the case tells the two apart: the oracle's map differs from the batch's own vectors exactly when the filter is the baseline one
+    b = cs["batch"]
+    own = np.zeros((maps.h_scu, maps.w_scu, 4), np.int16)
+    for i in range(len(b["x"])):
+        own[b["y"][i] >> 2:(b["y"][i] >> 2) + ((1 << b["log2h"][i]) >> 2), b["x"][i] >> 2:(b["x"][i] >> 2) + ((1 << b["log2w"][i]) >> 2)] = b["mv"][i].reshape(4)
+    assert np.array_equal(maps.map_mv.reshape(maps.h_scu, maps.w_scu, 4), own) == bool(cs["addb"])
 
 
 # content kind x bit depth x partition depth per coding family.  split_prob low / high: k_inter's region and tile roles / its split role see the saturated windows

@@ -1,5 +1,5 @@
 """The extreme cases (tests/extreme_inputs.py: rail-to-rail content, QP 0..51 x slice offsets, vectors on the MV-clip thresholds, ALF coefficients at their legal
-limits) through the CPU oracle and the REAL reference (oracle/_ref), plus the census: every case asserts that the oracle took the branches it exists for.
+limits, every branch of the DMVR search) through the CPU oracle and the REAL reference (oracle/_ref), plus the census: every case asserts that the oracle took the branches it exists for.
 
 The comparison is the one of test_picture_level_oracle_equals_reference: residual arena, pre-deblock planes, maps, final padded planes, against the reference's
 normative C path (simd=0) only - its SIMD kernels are known to diverge on out-of-range input (the level-cap comment in synth.gen_frame) and the
@@ -12,6 +12,31 @@ REQUIRE is a condition, not a measurement: it is written out below and was met b
     magnitude (Main, phase 8) and the stage-1 shift is bd - 8, so |sum >> shift| <= 112 * 255 = 28560 < 32768 at every bit depth.  Asserted to be 0.
 The wrapping 16-bit reconstruction sum is reached at 10 and 12 bit (x_recon_wrap_*: dense blocks of level 24 at high QP saturate the dequantiser and the first
 transform stage); at 8 bit it stays with the block-level tests (see the comment at the cases).
+
+DMVR (xi.DMVR_CASES: planted displacements - dmvr_pair -, mirrored / zero vectors, vectors on the clip thresholds, partitions with every sub-block shape).  The census
+over these cases together, as test_dmvr_cases_together_reach_every_branch prints it (refined sub-blocks, or events):
+  shapes 8x8 / 8x16 / 16x8 / 16x16 (w x h)           247 / 436 / 577 / 453      (8 bit 62 / 89 / 243 / 175, 10 bit 114 / 253 / 174 / 203, 12 bit 71 / 94 / 160 / 75)
+  flagged CUs with references not POC-symmetric      25
+  search ended: early / centre in round 0 / cost 0 after round 0's move / centre in round 1 / moved twice     223 / 178 / 29 / 659 / 624
+  winner below, above, right, left, diagonal         round 0: 200, 221, 211, 223, 457     round 1: 105, 119, 130, 136, 134
+  diagonal tried in quadrant ++ / -+ / +- / --       730 / 704 / 719 / 620
+  ties right == left / below == above                118 / 108
+  sub-sample step -8 .. 8, denominator 0             x: 32 17 24 29 24 35 51 53 256 63 48 41 42 26 19 20 14, 43     y: 23 12 23 30 32 32 46 74 273 72 59 35 24 23 19 13 11, 36
+  whole-sample displacement, rows y = -2 .. 2        3 33 40 41 5 / 36 87 132 88 17 / 65 119 401 114 57 / 30 95 108 63 52 / 6 34 43 33 11
+  starting vector moved by mv_clip, l / r / t / b    39 / 15 / 34 / 15
+  refined vector clipped at its sub-block            38 / 44 / 34 / 36
+  refined position from the start window, luma -2 .. 2: 712 1485 2910 1241 504; chroma -1 .. 1: 1632 4174 1046; luma +-3, chroma +-2, further: 0
+  regimes copy / vertical / horizontal / 2-D         bilinear 896 220 184 458, luma 1143 478 463 1342, chroma 534 507 484 1901
+Buckets asserted to be 0, with the reason:
+  * dmvr_not_refined[1] (the identical-motion exit of xevdm_mc's DMVR branch): it asks for poc0 == poc1, the refinement for references on opposite sides of the picture.
+  * dmvr_win_off at +-3 luma, +-2 chroma and further (the only offsets for which k_dmvr leaves its packed prediction for the scalar one): the search moves at most
+    2 samples = 32 sixteenths, and the sub-sample step of at most 8 exists only when the last round's centre won, i.e. after at most one move: 24.  floor((a + t) / 16) -
+    floor(a / 16) is at most 2 for |t| <= 32, and at most 1 with 32 in place of 16.  The clip at the sub-block moves the vector back towards the starting one (which
+    passed the same test for the whole CU), never further.  XEVD_HIP_DMVR_SCALAR therefore exists: tests/test_gpu_extremes.py runs the scalar form with it.
+dmvr_sub_clip was expected to be unreachable too - a sub-block on a threshold lies wholly in the replicated border, where the costs along that axis are equal - and the
+census refuted it: that holds when BOTH lists are on the threshold.  With one list there and the other inside the picture the costs differ along the axis, the search
+moves, and the list on the threshold is pushed past it (x_dmvr_thresholds_*: 'dmvr_sub_clip' is a required bucket, and the oracle with a clip that does nothing decodes
+those two cases differently).
 
 The census (which needs only the oracle) and the generator checks run everywhere; the comparison against the reference carries the `ref` mark and is skipped
 where oracle/_ref is not built, like tests/test_oracle_vs_ref.py.
@@ -64,7 +89,42 @@ def _recon_rails(cen, cs):
     assert min(cen["recon_clip"]) * 200 >= cen["recon_coded"] > 0, (cen["recon_clip"].tolist(), cen["recon_coded"])
 
 
+def dmvr_refined(cs):
+    """mask of the CUs the refinement runs on, from the batch and cases.POCS alone: candidates whose references lie at equal distances on either side"""
+    b = cs["batch"]
+    d0 = cases.CUR_POC - np.asarray(cases.POCS[0])[np.maximum(b["refi"][:, 0], 0)]
+    d1 = cases.CUR_POC - np.asarray(cases.POCS[1])[np.maximum(b["refi"][:, 1], 0)]
+    return xi.dmvr_candidates(b) & (d0 * d1 < 0) & (np.abs(d0) == np.abs(d1))
+
+
+def _dmvr_cu128(cen, cs):
+    b = cs["batch"]
+    shapes = set(zip(b["log2w"][dmvr_refined(cs)].tolist(), b["log2h"][dmvr_refined(cs)].tolist()))
+    assert (7, 7) in shapes and ((7, 3) in shapes or (3, 7) in shapes), sorted(shapes)      # 64 sub-blocks (isx / isy up to 28), and a strip of eight
+
+
+def _dmvr_win_off(cen, cs):
+    _all(cen["dmvr_win_off"][0][1:6], "refined position, luma samples from the starting vector's window, -2 .. 2")
+    _all(cen["dmvr_win_off"][1][2:5], "refined position, chroma samples from the starting vector's window, -1 .. 1")
+
+
 REQUIRE = {
+    "dmvr_shape": lambda cen, cs: _all(cen["dmvr_shape"], "DMVR sub-blocks of 8x8, 8x16, 16x8, 16x16"),
+    "dmvr_cu128": _dmvr_cu128,
+    "dmvr_not_refined": lambda cen, cs: _all(cen["dmvr_not_refined"][:1], "flagged bi-predicted CUs whose references are not POC-symmetric"),
+    "dmvr_exit": lambda cen, cs: _all(cen["dmvr_exit"], "DMVR search ends [early, centre in round 0, cost 0 after a move, centre in round 1, moved twice]"),
+    "dmvr_exit_zero": lambda cen, cs: _all(cen["dmvr_exit"][2:3], "DMVR searches that found cost 0 with their first move"),
+    "dmvr_win": lambda cen, cs: _all(cen["dmvr_win"], "DMVR [round] x winner [below, above, right, left, diagonal]"),
+    "dmvr_diag": lambda cen, cs: _all(cen["dmvr_diag"], "DMVR diagonal tried in every quadrant"),
+    "dmvr_tie": lambda cen, cs: _all(cen["dmvr_tie"], "DMVR ties right == left, below == above"),
+    "dmvr_subpel": lambda cen, cs: _all(cen["dmvr_subpel"][:, 1:16], "DMVR sub-sample quotients -7 .. 7 on [x, y]"),
+    "dmvr_subpel_ends": lambda cen, cs: _all(cen["dmvr_subpel"][:, [0, 16, 17]], "DMVR sub-sample steps -8, +8, denominator 0 on [x, y]"),
+    # the quotients 1, 2 and 4 are where 16 (a - b) EQUALS the divisor the first, second and third compare of the 3-bit division test it against (xi.DMVR_QUOTIENT_STEPS)
+    "dmvr_quotients": lambda cen, cs: _all(cen["dmvr_subpel"][:, [8 + 4, 8 + 2, 8 + 1]], "DMVR sub-sample steps 4, 2, 1 on [x, y]"),
+    "dmvr_start_clip": lambda cen, cs: _all(cen["dmvr_start_clip"], "starting vectors of refined CUs moved by the MV clip [left, right, top, bottom]"),
+    "dmvr_sub_clip": lambda cen, cs: _all(cen["dmvr_sub_clip"], "refined vectors clipped at the sub-block [left, right, top, bottom]"),
+    "dmvr_win_off": _dmvr_win_off,
+    "dmvr_regime": lambda cen, cs: _all(cen["dmvr_regime"], "DMVR [bilinear, luma, chroma] x [copy, vertical, horizontal, 2-D]"),
     "addb_idx_luma": lambda cen, cs: _all(cen["addb_index_a"][0], "ADDB luma indexA 0..51") or _all(cen["addb_index_b"][0], "ADDB luma indexB 0..51"),
     "addb_idx_top": _addb_idx_top,
     "addb_chroma_rows": _addb_chroma_rows,
@@ -94,6 +154,7 @@ def run_oracle_with_census(cs):
 
 def check_census(spec, cs, cen):
     assert cen["addb_lost"][1] == 0 and cen["addb_lost"][2] == 0 and cen["mc_stage1_wrap"] == 0, "a bucket the module docstring calls unreachable was reached"
+    assert cen["dmvr_not_refined"][1] == 0 and cen["dmvr_win_off"][0][[0, 6, 7]].sum() == 0 and cen["dmvr_win_off"][1][[0, 1, 5, 6, 7]].sum() == 0, "a DMVR bucket the module docstring calls unreachable was reached"
     for tag in spec[9]:
         REQUIRE[tag](cen, cs)
 
@@ -108,6 +169,7 @@ def test_every_requirement_is_carried_by_a_case():
     for bd in (8, 10, 12):      # and at every bit depth: interpolation, reconstruction and ALF clips, the top of the ADDB tables
         for tag in ("mc_clip", "recon_rails", "alf_clip", "addb_idx_top" if bd != 8 else "addb_chroma_top_rows"):
             assert any(spec[3] == bd and tag in spec[9] for spec in xi.EXTREME_CASES), (bd, tag)
+        assert any(spec[3] == bd and any(t.startswith("dmvr_") for t in spec[9]) for spec in xi.DMVR_CASES), (bd, "a DMVR tag")
 
 
 @pytest.mark.parametrize("spec", xi.EXTREME_CASES, ids=[s[0] for s in xi.EXTREME_CASES])
@@ -130,6 +192,54 @@ def test_extreme_case_oracle_equals_reference(spec):
     assert np.array_equal(ma.map_refi, mb.map_refi) and np.array_equal(ma.map_mv, mb.map_mv)
     for c in range(3):
         assert np.array_equal(a.bufs[c], b.bufs[c]), f"final plane {c}: {np.argwhere(a.bufs[c] != b.bufs[c])[:4]}"
+
+
+def dmvr_census_together():
+    """the census of the DMVR cases, summed: -> (all, {bit depth: ...}, [(case, refined mask)])"""
+    total, by_bd, built = None, {}, []
+    for spec in xi.DMVR_CASES:
+        cs = cases.build_case(*spec[:9])
+        _, cen = run_oracle_with_census(cs)
+        cen = {k: np.asarray(v) for k, v in cen.items() if k.startswith("dmvr_")}
+        total = cen if total is None else {k: total[k] + cen[k] for k in cen}
+        by_bd[spec[3]] = cen if spec[3] not in by_bd else {k: by_bd[spec[3]][k] + cen[k] for k in cen}
+        built.append((cs, dmvr_refined(cs)))
+    return total, by_bd, built
+
+
+def test_dmvr_cases_together_reach_every_branch():
+    """the conditions the DMVR cases were chosen for, over all of them (the table of the module docstring is this test's output)"""
+    total, by_bd, built = dmvr_census_together()
+    for k, v in total.items():
+        print(k, v.tolist())
+    for bd in (8, 10, 12):
+        print(bd, "bit shapes", by_bd[bd]["dmvr_shape"].tolist())
+        assert (by_bd[bd]["dmvr_shape"] >= 16).all(), (bd, by_bd[bd]["dmvr_shape"].tolist())
+    for tag in ("dmvr_exit", "dmvr_win", "dmvr_diag", "dmvr_tie", "dmvr_regime", "dmvr_start_clip", "dmvr_sub_clip", "dmvr_subpel", "dmvr_subpel_ends", "dmvr_win_off", "dmvr_not_refined"):
+        REQUIRE[tag](total, None)
+    _all(total["dmvr_total"], "DMVR whole-sample displacement [y -2 .. 2][x -2 .. 2]")      # (no single case is asked for all 25)
+    assert total["dmvr_not_refined"][1] == 0 and total["dmvr_win_off"][0][[0, 6, 7]].sum() == 0 and total["dmvr_win_off"][1][[0, 1, 5, 6, 7]].sum() == 0
+    # from the batches: ATS-inter TUs of every index at both positions, with a luma residual, and every cbf combination inside refined CUs; the strips
+    ats, cbf, shapes = set(), set(), set()
+    for cs, ref in built:
+        b = cs["batch"]
+        if b.get("ats_inter") is not None:
+            ats |= set(b["ats_inter"][ref & ((b["cbf"] & 1) != 0)].tolist())
+        cbf |= set(b["cbf"][ref].tolist())
+        shapes |= set(zip((1 << b["log2w"][ref].astype(int)).tolist(), (1 << b["log2h"][ref].astype(int)).tolist()))
+    assert ats >= {idx | pos << 4 for idx in (1, 2, 3, 4) for pos in (0, 1)}, sorted(ats)
+    assert cbf >= set(range(8)), sorted(cbf)
+    assert shapes >= {(16, 8), (32, 8), (64, 8), (8, 16), (8, 32), (8, 64), (128, 128)} and shapes & {(128, 8), (8, 128)}, sorted(shapes)
+    assert {(spec[3], spec[8].get("addb", 0)) for spec in xi.DMVR_CASES} >= {(8, 0), (8, 1), (10, 1), (12, 0), (12, 1)}      # every depth; the baseline filter reads refined vectors
+    assert any(spec[8].get("alf") for spec in xi.DMVR_CASES) and any(spec[8].get("amp") == 40.0 for spec in xi.DMVR_CASES)
+
+
+@pytest.mark.ref
+@pytest.mark.parametrize("spec", xi.DMVR_CASES, ids=[s[0] for s in xi.DMVR_CASES])
+def test_dmvr_case_vectors_oracle_equals_reference(spec):
+    cs = cases.build_case(*spec[:9])
+    a, b = cases.dmvr_mvs("oracle", cs), cases.dmvr_mvs("ref", cs)
+    assert len(a) > 0 and a.shape == b.shape and np.array_equal(a, b), f"refined vectors, first differences at sub-blocks {np.argwhere(a != b)[:4, 0].tolist()}"
 
 
 def check_tile_census(spec, cs, cen):

@@ -578,6 +578,7 @@ __device__ __forceinline__ void dmvr_block(const DmvrArgs &a, const uint4 r0, co
         dc[l][0] = (clip ? mc[0] >> 3 : r16[l][0] >> 5) - (u.st[l][0] >> 3); dc[l][1] = (clip ? mc[1] >> 3 : r16[l][1] >> 5) - (u.st[l][1] >> 3);
         packed = packed && abs(dl[l][0]) <= 3 && abs(dl[l][1]) <= 3 && abs(dc[l][0]) <= 2 && abs(dc[l][1]) <= 2;
     }
+    packed = packed && !a.force_scalar;      // XEVD_HIP_DMVR_SCALAR: tests run the scalar form where the packed one is the rule
     if (packed) dmvr_predict_packed<DX, DY>(a, u, r16, dl, dc, gxy, W, T, lane);
     else        dmvr_predict_scalar<DX, DY>(a, u, r16, W, T, lane);
 }

@@ -125,6 +125,7 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
     c->fork_ev = c->join_ev = 0;
     c->intra_small_min = getenv("XEVD_HIP_INTRA_SMALL_MIN") ? std::max(1, atoi(getenv("XEVD_HIP_INTRA_SMALL_MIN"))) : 2048;      // (k_intra.hip: launch_intra; read per context, tests set 1)
     c->addb_scalar = getenv("XEVD_HIP_ADDB_SCALAR") != NULL;
+    c->dmvr_scalar = getenv("XEVD_HIP_DMVR_SCALAR") != NULL;
     c->split_addb_alf = getenv("XEVD_HIP_SPLIT_ADDB_ALF") != NULL;      // measurement knob: ADDB and ALF as two kernels (the round-2 chain) instead of k_addb_alf
     for (int i = 0; i < 2; i++) { c->d_out[i] = NULL; c->out_caps[i] = 0; c->out_ready[i] = c->out_done[i] = 0; c->out_busy[i] = 0; }
     c->d_md5 = NULL; c->md5_ready = 0;

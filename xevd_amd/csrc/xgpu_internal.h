@@ -137,6 +137,7 @@ struct DmvrArgs {
     int16_t *out_mv;                   // [n_items][2][2] quarter-sample vectors kept for temporal prediction
     ScuRec  *maps;                     // the SCU map the deblocking filter reads, and
     int      w_scu, refined_to_map;    // whether it gets the refined vectors (baseline filter of the Main library) or keeps the unrefined ones (ADDB)
+    int      force_scalar;             // XEVD_HIP_DMVR_SCALAR: the refined prediction in its scalar form for every sub-block (the form valid input never reaches)
     RefEntry refp[XGPU_MAX_REFS][2];
 };
 
@@ -377,6 +378,7 @@ struct xgpu_ctx {
     int             order_rl;          // a batch of the picture has CUs decoded after their right-hand neighbours (xgpu_dbatch.order_rl): k_dbk's order-aware instantiation
     int             intra_small_min;   // level-1 launches with at least this many CUs of at most 16 SCUs give those 16 lanes each (k_intra_l1; XEVD_HIP_INTRA_SMALL_MIN, default 2048)
     int             addb_scalar;                       // XEVD_HIP_ADDB_SCALAR: the scalar line filters (the > 10-bit instantiation) at every bit depth - read per context, tests set it
+    int             dmvr_scalar;                       // XEVD_HIP_DMVR_SCALAR: k_dmvr's scalar form of the refined prediction for every sub-block - read per context, tests set it
     int             addb_pending, split_addb_alf;      // ADDB + ALF in one kernel: xgpu_deblock left its arguments in addb_args for xgpu_alf
     AddbArgs        addb_args;
     // timing
