@@ -946,6 +946,9 @@ static int eipd_chroma_mode(int ipm_c, int ipm_l)
 #define AFF_MAX_CU 128
 static int aff_round(int v, int shift) { return (v + (1 << (shift - 1)) - (v >= 0)) >> shift; }     /* xevdm_mv_rounding_s32, xevdm_util.c:1857-1868 */
 static int aff_clip18(int v) { return CLIP3(-(1 << 17), (1 << 17) - 1, v); }
+static int g_aff_count = 0, g_aff_path = 0;      /* census: aff_subblock runs twice per CU (prediction, map vectors), counted in the first; the path of the last CU */
+static int aff_bucket6(int v) { return v > 4 ? 5 : v; }
+static int aff_log2m2(int v) { int k = 0; while ((4 << k) < v) k++; return k; }      /* 4, 8, .. 128 -> 0 .. 5 */
 
 /* the four model deltas: xevdm_mc.c:2294-2306 (== xevdm_util.c:1891-1903) */
 static void aff_deltas(const int16_t mv[3][2], int lw, int lh, int vn, int dh[2], int dv[2])
@@ -959,7 +962,7 @@ static void aff_deltas(const int16_t mv[3][2], int lw, int lh, int vn, int dh[2]
 }
 
 /* xevdm_check_eif_applicability_uni, xevdm_util.c:2073-2097 (bounding box of a 4x4 sub-block :2041-2060, fetched lines :2062-2071) */
-static int aff_eif_applicable(const int dh[2], const int dv[2], int *mem_band)
+static int aff_eif_applicable(const int dh[2], const int dv[2], int *mem_band, int l)
 {
     const int P = 2 + AFF_BIT, one = 1 << P;
     int cx[4], cy[4], k, mx, nx, my, ny;
@@ -968,8 +971,9 @@ static int aff_eif_applicable(const int dh[2], const int dv[2], int *mem_band)
     mx = nx = my = ny = 0;
     for (k = 1; k < 4; k++) { if (cx[k] > mx) mx = cx[k]; if (cx[k] < nx) nx = cx[k]; if (cy[k] > my) my = cy[k]; if (cy[k] < ny) ny = cy[k]; }
     *mem_band = (((mx - nx + one - 1) >> P) + 2) * (((my - ny + one - 1) >> P) + 2) <= 72;
-    if (dv[1] < -one) return 0;
-    if (((dv[1] > 0 ? dv[1] : 0) + abs(dh[1])) * 5 > (1 << P)) return 0;
+    if (dv[1] < -one) { if (g_aff_count) g_cen.aff_applic[l][1]++; return 0; }
+    if (((dv[1] > 0 ? dv[1] : 0) + abs(dh[1])) * 5 > (1 << P)) { if (g_aff_count) g_cen.aff_applic[l][2]++; return 0; }
+    if (g_aff_count) g_cen.aff_applic[l][0]++;
     return 1;
 }
 
@@ -990,15 +994,19 @@ static void aff_subblock(const int16_t mv[2][3][2], const int8_t refi[2], int lw
         h = wy > 4 ? 4 : (wy == 0 ? cuh : lut[wy - 1]);
         if (w < *sub_w) *sub_w = w;
         if (h < *sub_h) *sub_h = h;
+        if (g_aff_count) { g_cen.aff_w[0][aff_bucket6(wx)]++; g_cen.aff_w[1][aff_bucket6(wy)]++; }
     }
     for (l = 0; l < 2 && apply; l++) {      /* xevdm_check_eif_applicability_bi, :2099-2125: stops at the first list that fails */
         int dh[2], dv[2], m;
         if (refi[l] < 0) continue;
         aff_deltas(mv[l], lw, lh, vn, dh, dv);
-        if (!aff_eif_applicable(dh, dv, &m)) apply = 0;
+        if (!aff_eif_applicable(dh, dv, &m, l)) apply = 0;
         mb &= m;
+        if (g_aff_count && !apply && l == 0 && refi[1] >= 0) g_cen.aff_applic_skipped++;
     }
+    if (g_aff_count && !apply && (*sub_w < 8 || *sub_h < 8)) g_cen.aff_lifted++;
     if (!apply) { if (*sub_w < 8) *sub_w = 8; if (*sub_h < 8) *sub_h = 8; }
+    if (g_aff_count) { g_cen.aff_sub[0][aff_log2m2(*sub_w)]++; g_cen.aff_sub[1][aff_log2m2(*sub_h)]++; }
     if (mem_band) *mem_band = mb;
 }
 
@@ -1017,18 +1025,23 @@ static void aff_eif_range(int x, int y, int lw, int lh, const int dh[2], const i
             const int centre = aff_round(mv_scale[c] + dh[c] * (cuw >> 1) + dv[c] * (cuh >> 1), 4);
             const int sp = spread[(c == 0 ? lw : lh) - 3];
             min_mv[c] = centre - sp; max_mv[c] = centre + sp;
+            g_cen.aff_spread[(c == 0 ? lw : lh) - 3]++;
+            g_cen.aff_range[c][min_mv[c] < min_pic[c] ? 0 : (max_mv[c] > max_pic[c] ? 1 : 2)]++;
             if (min_mv[c] < min_pic[c]) { min_mv[c] = min_pic[c]; max_mv[c] = max_pic[c] < min_pic[c] + 2 * sp ? max_pic[c] : min_pic[c] + 2 * sp; }
             else if (max_mv[c] > max_pic[c]) { max_mv[c] = max_pic[c]; min_mv[c] = min_pic[c] > max_pic[c] - 2 * sp ? min_pic[c] : max_pic[c] - 2 * sp; }
         }
+        if (min_mv[c] != aff_clip18(min_mv[c])) g_cen.aff_range_clip18[c][0]++;
+        if (max_mv[c] != aff_clip18(max_mv[c])) g_cen.aff_range_clip18[c][1]++;
         max_mv[c] = aff_clip18(max_mv[c]); min_mv[c] = aff_clip18(min_mv[c]);
     }
+    g_cen.aff_band[range_clip ? 0 : 1]++;
 }
 
 /* xevdm_eif_mc, xevdm_mc.c:2543-2604: per-sample bilinear fetch at the model's vector (1/32 sample, clamped to the range -
    xevdm_eif_bilinear_clip :2456-2499; the no-clip variant is the same when no vector leaves the range), then the 3-tap
    [-1 10 -1] enhancement filter in both directions (xevdm_eif_filter :2428-2454).  Intermediates are `pel` (s16). */
 static void aff_eif(int bw, int bh, int x, int y, const int mv_scale[2], const int dh[2], const int dv[2], const int max_mv_[2], const int min_mv_[2],
-                    const int16_t *ref, int s_ref, int16_t *dst, int s_dst, int bd, int chroma)
+                    const int16_t *ref, int s_ref, int16_t *dst, int s_dst, int bd, int chroma, int band)
 {
     int mv0[2] = { mv_scale[0], mv_scale[1] }, mx[2] = { max_mv_[0], max_mv_[1] }, mn[2] = { min_mv_[0], min_mv_[1] };
     const int shift1 = bd - 8 < 4 ? bd - 8 : 4, shift2 = 20 - bd > 8 ? 20 - bd : 8, off2 = 1 << (shift2 - 1);
@@ -1043,8 +1056,13 @@ static void aff_eif(int bw, int bh, int x, int y, const int mv_scale[2], const i
         int vx = (mv0[0] + px * dh[0] + py * dv[0]) >> 4, vy = (mv0[1] + px * dh[1] + py * dv[1]) >> 4;
         const int16_t *r;
         int fx, fy, s1, s2;
+        if (!chroma) {
+            if (vx < mn[0]) g_cen.aff_eif_clamp[0][0][band]++; else if (vx > mx[0]) g_cen.aff_eif_clamp[0][1][band]++;
+            if (vy < mn[1]) g_cen.aff_eif_clamp[1][0][band]++; else if (vy > mx[1]) g_cen.aff_eif_clamp[1][1][band]++;
+        }
         vx = vx < mn[0] ? mn[0] : (vx > mx[0] ? mx[0] : vx);
         vy = vy < mn[1] ? mn[1] : (vy > mx[1] ? mx[1] : vy);
+        if (!chroma) { g_cen.aff_eif_frac[0][vx & 31]++; g_cen.aff_eif_frac[1][vy & 31]++; if (vx < 0) g_cen.aff_eif_neg[0]++; if (vy < 0) g_cen.aff_eif_neg[1]++; }
         r = ref + (py + (vy >> 5)) * s_ref + px + (vx >> 5);
         fx = vx & 31; fy = vy & 31;
         s1 = (int16_t)(((64 - 2 * fx) * r[0] + 2 * fx * r[1]) >> shift1);
@@ -1058,6 +1076,7 @@ static void aff_eif(int bw, int bh, int x, int y, const int mv_scale[2], const i
     for (py = 0; py < bh; py++) for (px = 0; px < bw; px++) {
         const int16_t *t = tmp + (py + 1) * ts + px;
         const int16_t res = (int16_t)((-t[-ts] + t[0] * 10 - t[ts] + of3) >> sh3);
+        CEN_CLIP(aff_eif_clip[g_cen_plane], res, (1 << bd) - 1);
         dst[py * s_dst + px] = (int16_t)CLIP3(0, (1 << bd) - 1, res);
     }
     free(tmp);
@@ -1074,9 +1093,14 @@ static void aff_mc_list(const xgpu_seq_params *sp, const orc_pic *rp, int x, int
     if (sub_w < 8 || sub_h < 8) {
         int mx[2], mn[2];
         aff_eif_range(x, y, lw, lh, dh, dv, mv_scale, sp->width, sp->height, !mem_band, mx, mn);
-        aff_eif(cuw, cuh, x, y, mv_scale, dh, dv, mx, mn, rp->y, rp->s_l, pred[0], cuw, sp->bit_depth_luma, 0);
-        aff_eif(cuw >> 1, cuh >> 1, x, y, mv_scale, dh, dv, mx, mn, rp->u, rp->s_c, pred[1], wc, sp->bit_depth_chroma, 1);
-        aff_eif(cuw >> 1, cuh >> 1, x, y, mv_scale, dh, dv, mx, mn, rp->v, rp->s_c, pred[2], wc, sp->bit_depth_chroma, 1);
+        if (!mem_band) g_cen.aff_band_vn[vn == 3]++;
+        g_cen_plane = 0;
+        aff_eif(cuw, cuh, x, y, mv_scale, dh, dv, mx, mn, rp->y, rp->s_l, pred[0], cuw, sp->bit_depth_luma, 0, !mem_band);
+        g_cen_plane = 1;
+        aff_eif(cuw >> 1, cuh >> 1, x, y, mv_scale, dh, dv, mx, mn, rp->u, rp->s_c, pred[1], wc, sp->bit_depth_chroma, 1, !mem_band);
+        g_cen_plane = 2;
+        aff_eif(cuw >> 1, cuh >> 1, x, y, mv_scale, dh, dv, mx, mn, rp->v, rp->s_c, pred[2], wc, sp->bit_depth_chroma, 1, !mem_band);
+        g_cen_plane = 0;
         return;
     }
     {
@@ -1087,6 +1111,15 @@ static void aff_mc_list(const xgpu_seq_params *sp, const orc_pic *rp, int x, int
         const int ox = aff_clip18(aff_round(mv_scale[0] + dh[0] * (sub_w >> 1) + dv[0] * (sub_h >> 1), 5));
         const int oy = aff_clip18(aff_round(mv_scale[1] + dh[1] * (sub_w >> 1) + dv[1] * (sub_h >> 1), 5));
         const int cx = ox < hor_min ? hor_min : (ox > hor_max ? hor_max : ox), cy = oy < ver_min ? ver_min : (oy > ver_max ? ver_max : oy);
+        const int side[4] = { ox < hor_min, ox > hor_max, oy < ver_min, oy > ver_max };
+        int k;
+        for (k = 0; k < 4; k++) if (side[k]) { g_cen.aff_sub_mvclip[k]++; if (((k < 2 ? ox : oy) & 15) != 0) g_cen.aff_sub_mvclip_frac[k]++; }
+        if (ox != aff_round(mv_scale[0] + dh[0] * (sub_w >> 1) + dv[0] * (sub_h >> 1), 5)) g_cen.aff_sub_clip18[0]++;
+        if (oy != aff_round(mv_scale[1] + dh[1] * (sub_w >> 1) + dv[1] * (sub_h >> 1), 5)) g_cen.aff_sub_clip18[1]++;
+        g_cen.aff_sub_regime[0][((ox & 15) != 0) * 2 + ((oy & 15) != 0)]++;
+        g_cen.aff_sub_regime[1][((ox & 31) != 0) * 2 + ((oy & 31) != 0)]++;
+        if ((ox & 31) == 16) g_cen.aff_sub_luma_whole_chroma_half[0]++;
+        if ((oy & 31) == 16) g_cen.aff_sub_luma_whole_chroma_half[1]++;
         for (h = 0; h < cuh; h += sub_h) for (w = 0; w < cuw; w += sub_w) {
             const int gx = (x + w) * 16 + cx, gy = (y + h) * 16 + cy;
             g_cen_plane = 0;
@@ -1106,7 +1139,13 @@ int orc_affine_mc_cu(const xgpu_seq_params *sp, const orc_frame *fr, int x, int 
     int16_t **dst[2] = { pred0, pred1 };
     const int w = 1 << lw, h = 1 << lh;
     int sub_w, sub_h, mem_band, l, bidx = 0, i;
+    g_aff_count = 1;
     aff_subblock(mv, refi, lw, lh, vn, &sub_w, &sub_h, &mem_band);
+    g_aff_count = 0;
+    g_aff_path = !(sub_w < 8 || sub_h < 8);
+    g_cen.aff_shape[g_aff_path][lw - 3][lh - 3]++;
+    g_cen.aff_vn[vn == 3]++;
+    g_cen.aff_lists[refi[0] >= 0 ? (refi[1] >= 0 ? 2 : 0) : 1]++;
     for (l = 0; l < 2; l++) {
         if (refi[l] < 0) continue;
         aff_mc_list(sp, &fr->refp[refi[l]][l], x, y, lw, lh, mv[l], vn, sub_w, sub_h, mem_band, dst[bidx]);
@@ -1137,13 +1176,20 @@ static void affine_set_mvf(const xgpu_cu_batch *b, int i, orc_maps *m)
         aff_deltas(mv[l], lw, lh, vn, dh, dv);
         for (h = 0; h < h_cu; h += sub_h >> 2) for (w = 0; w < w_cu; w += sub_w >> 2) {
             int vx, vy;
-            if (w == 0 && h == 0) { vx = mv[l][0][0]; vy = mv[l][0][1]; }
-            else if (w + (sub_w >> 2) == w_cu && h == 0) { vx = mv[l][1][0]; vy = mv[l][1][1]; }
-            else if (w == 0 && h + (sub_h >> 2) == h_cu && vn == 3) { vx = mv[l][2][0]; vy = mv[l][2][1]; }
+            if (w == 0 && h == 0) {
+                vx = mv[l][0][0]; vy = mv[l][0][1]; g_cen.aff_mvf[0]++;
+                if ((sub_w >> 2) == w_cu && (sub_h >> 2) == h_cu) g_cen.aff_mvf_whole_cu++;
+            }
+            else if (w + (sub_w >> 2) == w_cu && h == 0) { vx = mv[l][1][0]; vy = mv[l][1][1]; g_cen.aff_mvf[1]++; }
+            else if (w == 0 && h + (sub_h >> 2) == h_cu && vn == 3) { vx = mv[l][2][0]; vy = mv[l][2][1]; g_cen.aff_mvf[2]++; }
             else {
                 const int px = (w << 2) + (sub_w >> 1), py = (h << 2) + (sub_h >> 1);
-                vx = aff_clip18(aff_round(mv[l][0][0] * (1 << AFF_BIT) + dh[0] * px + dv[0] * py, 5)) >> 2;
-                vy = aff_clip18(aff_round(mv[l][0][1] * (1 << AFF_BIT) + dh[1] * px + dv[1] * py, 5)) >> 2;
+                const int rx = aff_round(mv[l][0][0] * (1 << AFF_BIT) + dh[0] * px + dv[0] * py, 5), ry = aff_round(mv[l][0][1] * (1 << AFF_BIT) + dh[1] * px + dv[1] * py, 5);
+                vx = aff_clip18(rx) >> 2;
+                vy = aff_clip18(ry) >> 2;
+                g_cen.aff_mvf[3]++;
+                if (w == 0 && h + (sub_h >> 2) == h_cu) g_cen.aff_mvf_bl_vn2++;
+                g_cen.aff_mvf_clip18 += (uint32_t)((rx != aff_clip18(rx)) + (ry != aff_clip18(ry)));
             }
             for (yy = h; yy < h + (sub_h >> 2); yy++) for (xx = w; xx < w + (sub_w >> 2); xx++) {
                 m->map_mv[(scup + yy * m->w_scu + xx) * 4 + l * 2 + 0] = (int16_t)vx;
@@ -1282,8 +1328,11 @@ int orc_recon_batch_ex(const xgpu_seq_params *sp, const orc_frame *fr, const xgp
                 memcpy(pred[0][1] + r * (w >> 1), fr->cur.u + ((y >> 1) + (by >> 1) + r) * fr->cur.s_c + (x >> 1) + (bx >> 1), sizeof(int16_t) * (w >> 1));
                 memcpy(pred[0][2] + r * (w >> 1), fr->cur.v + ((y >> 1) + (by >> 1) + r) * fr->cur.s_c + (x >> 1) + (bx >> 1), sizeof(int16_t) * (w >> 1));
             }
-        } else if (inter && b->affine && b->affine[i])
+        } else if (inter && b->affine && b->affine[i]) {
             orc_affine_mc_cu(sp, fr, x, y, lw, lh, &b->refi[i * 2], (const int16_t (*)[3][2])&b->affine_mv[i * 12], b->affine[i], pred[0], pred[1]);
+            g_cen.aff_cbf[g_aff_path][b->cbf[i] & 7]++;
+            if (b->ats_inter && (b->ats_inter[i] & 15)) g_cen.aff_ats[g_aff_path][(b->ats_inter[i] & 15) - 1][(b->ats_inter[i] >> 4) & 1]++;
+        }
         else if (inter) {
             int done = 0;
             dmvr_done = 0;

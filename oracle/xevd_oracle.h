@@ -139,6 +139,35 @@ typedef struct orc_census {
     uint32_t dmvr_win_off[2][8];                       /* [luma / chroma] whole-sample offset of the refined position from the window fetched at the starting vector, both axes and
                                                           lists: -3 .. 3 at [offset + 3]; [7]: further */
     uint32_t dmvr_regime[3][4];                        /* [bilinear (per CU and list) / luma / chroma (per sub-block and list)][(fx != 0) * 2 + (fy != 0)] */
+    /* affine (orc_affine_mc_cu / affine_set_mvf).  [path]: 0 EIF, 1 sub-block translation.  "per list": per used list of a CU.  [axis]: 0 x, 1 y */
+    uint32_t aff_shape[2][5][5];                       /* CUs by [path][log2w - 3][log2h - 3] */
+    uint32_t aff_vn[2];                                /* CUs with 2 / 3 control points */
+    uint32_t aff_lists[3];                             /* CUs using list 0 only / list 1 only / both */
+    uint32_t aff_w[2][6];                              /* per list: [wx / wy] = 0, 1, 2, 3, 4, above 4 (the largest delta per sample along x / y, aff_subblock) */
+    uint32_t aff_sub[2][6];                            /* per CU: the resulting [sub_w / sub_h] = 4, 8, 16, 32, 64, 128 */
+    uint32_t aff_applic[2][3];                         /* per list examined, [list]: EIF applicable / dv[1] < -one / too many fetched lines */
+    uint32_t aff_applic_skipped;                       /* CUs whose list 1 was not examined because list 0 had failed */
+    uint32_t aff_lifted;                               /* CUs whose sub-block was raised to 8 (EIF not applicable, a side below 8) */
+    uint32_t aff_band[2];                              /* EIF, per list: memory band exceeded (the range is centre +- spread) / kept (the picture range) */
+    uint32_t aff_band_vn[2];                           /* ... exceeded, by control points: 2 (unreachable, tests/test_oracle_extremes.py) / 3 */
+    uint32_t aff_range[2][3];                          /* with the band exceeded, per list, [axis]: window below min_pic / above max_pic / inside */
+    uint32_t aff_spread[5];                            /* with the band exceeded, per list and axis: spread 128 / 256 / 544 / 1120 / 2272 */
+    uint32_t aff_range_clip18[2][2];                   /* EIF, per list, [axis]: min / max of the range moved by clip18 */
+    uint32_t aff_eif_clamp[2][2][2];                   /* EIF luma samples (window of (w + 2) x (h + 2)) clamped: [axis][low / high][picture range / band] */
+    uint32_t aff_eif_frac[2][32];                      /* EIF luma samples: [axis] fraction fx / fy in 1/32 */
+    uint32_t aff_eif_neg[2];                           /* EIF luma samples whose whole-sample offset is negative, [axis] */
+    uint32_t aff_eif_clip[3][2];                       /* [plane] EIF samples clipped at the end of the enhancement filter */
+    uint32_t aff_sub_mvclip[4];                        /* translation, per list: vector clipped left / right / top / bottom (as in mv_clip) */
+    uint32_t aff_sub_mvclip_frac[4];                   /* ... of which the unclipped vector had a luma fraction: the fractional filter runs with the phase-0 row of the tap table */
+    uint32_t aff_sub_clip18[2];                        /* translation, per list: [axis] vector moved by clip18 */
+    uint32_t aff_sub_regime[2][4];                     /* translation, per list: [luma / chroma][(dx != 0) * 2 + (dy != 0)] of the unclipped vector */
+    uint32_t aff_sub_luma_whole_chroma_half[2];        /* translation, per list: [axis] luma at a whole sample, chroma at a half one */
+    uint32_t aff_mvf[4];                               /* map vectors per sub-block and list: control point 0 / 1 / 2 / the formula */
+    uint32_t aff_mvf_bl_vn2;                           /* ... the bottom-left sub-block (not also the first or the top-right one) of a two-point CU: the formula */
+    uint32_t aff_mvf_clip18;                           /* map vector components moved by clip18 */
+    uint32_t aff_mvf_whole_cu;                         /* the sub-block is the whole CU: the first branch wins over the others */
+    uint32_t aff_ats[2][4][2];                         /* CUs with an ATS-inter TU: [path][idx - 1][pos] */
+    uint32_t aff_cbf[2][8];                            /* CUs by [path][cbf] */
 } orc_census;
 void orc_census_reset(void);
 void orc_census_get(orc_census *out);

@@ -7,6 +7,9 @@ coefficients, so the kernels' packed 16-bit arithmetic, clamps and table tops ar
   * ALF parameters at the largest magnitudes the reference's alf_recon_coef can leave (`alf_params`),
   * for DMVR: pairs of references displaced from one texture (`dmvr_pair`), vectors that mirror each other, vectors on the clip thresholds in one list or both,
     partitions with every sub-block shape up to the CU of 64 sub-blocks (`dmvr_partition`),
+  * for affine CUs: control points solved from target deltas for every branch of the model (`set_affine`: sub-block sizes, EIF applicability, the memory band and where its window
+    lies, clamps against band and picture range, the clip thresholds of the translation path, control points at the s16 limits, vectors of more than 4096 samples), partitions
+    with every CU shape of 8 .. 128 a side (`affine_partition`),
 and `apply` puts them into a case that cases.build_case has built (tools={"extreme": {...}}).  What each of them is FOR is asserted
 through the oracle's census (oracle_lib.census) in tests/test_oracle_extremes.py.
 """
@@ -422,6 +425,245 @@ def regenerate_batch(case, seed, gen):
     case["batch"] = b
 
 
+# ---- affine: control points built from target deltas, for every branch of the model (oracle/xevd_oracle.c: aff_subblock, aff_eif_applicable, aff_eif_range, aff_eif,
+# aff_mc_list, affine_set_mvf).  Units: a delta is the change of the vector per luma sample in 1/512 sample (quarter samples at 7 more bits: `one` = 512); a control-point
+# difference of d quarter samples across a CU side of 2^l gives the delta (d * 128) >> l, i.e. only multiples of 2^(7 - l): deltas of 1 and 3 exist on a side of 128 alone,
+# 2 from 64, 4 from 32, and a side of 8 knows 0 and multiples of 16.
+AFF_SPREAD = (128, 256, 544, 1120, 2272)      # half the width of the EIF memory band by log2 of the CU side - 3, 1/32 sample (picked here, never used for an expected value)
+
+
+def aff_diff(t, l2):
+    """the control-point difference (quarter samples) whose delta across a side of 2^l2 is t, or - where that side cannot express t - the next one away from 0"""
+    m = ((abs(int(t)) << l2) + 127) >> 7
+    return m if t >= 0 else -m
+
+
+def aff_deltas(cp, lw, lh, vn):
+    """the four deltas of one list's control points [3][2] -> (dh, dv)"""
+    dh = [((int(cp[1][0]) - int(cp[0][0])) * 128) >> lw, ((int(cp[1][1]) - int(cp[0][1])) * 128) >> lw]
+    dv = [((int(cp[2][0]) - int(cp[0][0])) * 128) >> lh, ((int(cp[2][1]) - int(cp[0][1])) * 128) >> lh] if vn == 3 else [-dh[1], dh[0]]
+    return dh, dv
+
+
+def aff_path(cps, used, lw, lh, vn):
+    """which way a CU goes, from its control points cps[list][3][2] (used[list]: the list has a reference): -> (sub_w, sub_h, eif, band_kept).  The generator needs the
+    sub-block size to aim a vector at a threshold; tests/test_builder.py checks the host builder's choice of kernel with it, after its totals were held to the census."""
+    sub_w, sub_h, apply, band = 1 << lw, 1 << lh, True, True
+    lut = (32, 16, 8, 8)
+    models = [aff_deltas(cps[l], lw, lh, vn) if used[l] else None for l in range(2)]
+    for m in models:
+        if m is None:
+            continue
+        wx, wy = max(abs(m[0][0]), abs(m[0][1])), max(abs(m[1][0]), abs(m[1][1]))
+        sub_w = min(sub_w, 4 if wx > 4 else ((1 << lw) if wx == 0 else lut[wx - 1]))
+        sub_h = min(sub_h, 4 if wy > 4 else ((1 << lh) if wy == 0 else lut[wy - 1]))
+    for m in models:
+        if m is None or not apply:
+            continue
+        (dh, dv), one = m, 512
+        cx = (0, 5 * (dh[0] + one), 5 * dv[0], 5 * (dh[0] + one) + 5 * dv[0])
+        cy = (0, 5 * dh[1], 5 * (dv[1] + one), 5 * dh[1] + 5 * (dv[1] + one))
+        band = band and (((max(cx) - min(cx) + one - 1) >> 9) + 2) * (((max(cy) - min(cy) + one - 1) >> 9) + 2) <= 72
+        if dv[1] < -one or (max(dv[1], 0) + abs(dh[1])) * 5 > one:
+            apply = False
+    if not apply:
+        sub_w, sub_h = max(sub_w, 8), max(sub_h, 8)
+    return sub_w, sub_h, sub_w < 8 or sub_h < 8, band
+
+
+def _aff_round(v, shift):
+    return (v + (1 << (shift - 1)) - (1 if v >= 0 else 0)) >> shift
+
+
+# A variant: (vn, dh, dv, (place x, place y)[, (vn, dh, dv) of list 1 where it differs]).  dh / dv: target deltas (dv is ignored for two control points).  A place says where the
+# vector at the CU's centre lies, in 1/32 sample as aff_eif_range has it:
+#   a number            that vector (+ a few 1/32 that change from CU to CU, so that every fraction occurs)
+#   'below' / 'above'   the band centre +- spread crosses the low / high end of the picture range (min_pic / max_pic) by half a spread
+#   'lo' / 'hi'         40 samples beyond that end: every sample is clamped;  'lo_edge' / 'hi_edge': on that end, so that about half of them are
+# or, in 1/16 sample, where the vector of the FIRST sub-block (the one the translation path uses for the whole CU) lies: ('min' | 'max', d) = d sixteenths past the low / high
+# clip threshold of aff_mc_list, ('at', v) = at v.
+_Z = ((320, 0), (0, 0))            # zoom 1.625 along x: the 4x4 bounding box needs 11 x 7 > 72 samples - the smallest zoom that leaves the memory band
+_ZS = ((2000, 0), (0, 0))          # zoom 4.9: the vectors of a CU spread further than the band is wide - samples clamped against it, both ends
+_SH = ((0, 0), (820, 0))           # shear along x
+_ZY = ((2000, 96), (0, -512))      # ... with about the most y change EIF admits on every CU width: 3 / 16 samples per sample of x, dv[1] = -one (every row fetches the same line) - clamps against the band along y
+_ZN = ((-2600, 40), (0, 2))        # mirrored along x
+_P9 = [(px, py) for px in (0, "below", "above") for py in (0, "below", "above")]
+AFFINE_VARIANTS = {
+    # every wx / wy of 0 .. 4 and above (a 6) with three control points - the sub-block is lut[wx] x lut[wy], also not square -, and with two (wy = wx)
+    "sizes": [(3, (a * sa, 0) if (a + b) & 1 else (0, a * sa), (0, b * sb) if a & 1 else (b * sb, 0), (0, 0)) for a, sa in ((0, 1), (1, 1), (2, -1), (3, 1), (4, -1), (6, 1))
+              for b, sb in ((0, 1), (1, -1), (2, 1), (3, -1), (4, 1), (6, -1))] + [(2, (a, 0) if a & 1 else (0, -a), None, (0, 0)) for a in (0, 1, 2, 3, 4, 6)],
+    # EIF: applicable with the band kept; both ways to fail (in list 0: list 1 is not looked at; in list 1 alone); the band exceeded x where the window lies, per axis;
+    # vectors beyond the picture range
+    "eif": [(3, (40, 10), (-12, 30), (0, 0)), (2, (60, -30), None, (0, 0)), (3, (8, 0), (0, -600), (0, 0)), (2, (-600, 0), None, (0, 0)), (3, (8, 120), (0, 0), (0, 0)),
+            (2, (8, 110), None, (0, 0)), (3, (8, 0), (0, -513), (0, 0), (3, (40, 10), (-12, 30))), (3, (40, 10), (-12, 30), (0, 0), (3, (8, 103), (0, 0))),
+            (3, (16, 0), (8, -512), (0, 0), (3, (16, 0), (8, -528))),
+            # a bounding box of exactly 9 x 8 = 72 samples, the last one inside the band: a shear that spreads the vectors of a narrow, tall CU further than the band would allow
+            (3, (0, 50), (150, 0), (0, 0)), (3, (0, -50), (-150, 0), ("below", 0))]
+           + [(3,) + _ZS + (p,) for p in _P9] + [(3,) + _ZY + (p,) for p in _P9[:3]] + [(3,) + _Z + (_P9[4],), (3,) + _SH + (_P9[8],), (3,) + _ZN + (_P9[0],)]
+           + [(3, (24, 4), (4, 24), p) for p in (("lo", 0), ("hi", "lo_edge"), (0, "lo"), ("hi_edge", "hi"), ("lo_edge", "hi_edge"), ("hi", "lo"))],
+    # the translation path (small deltas, and rotations too strong for EIF): the first sub-block's vector on, a quarter sample inside and outside each clip threshold, a
+    # sixteenth beyond (a fraction that the clip removes), and at every luma x chroma phase
+    "trans": [(vn, dh, dv, (("at", 0) if side >> 1 else (("min", "max")[side & 1], d), (("min", "max")[side & 1], d) if side >> 1 else ("at", 0)))
+              for d in (0, -4, 4, -1, 1) for side in range(4) for vn, dh, dv in ((3, (0, 0), (0, 0)), (2, (0, 4), None), (3, (300, 0), (40, 200)), (2, (40, -300), None))[(d + side) & 3:][:1]]
+             + [(3, (4, 0), (0, 2), (("at", fx), ("at", fy))) if (fx + fy) & 1 else (3, (0, 0), (0, 0), (("at", fx), ("at", fy))) for fx in (0, 16, 4) for fy in (0, 16, 9)]
+             + [(2, (3, 1), None, (("at", 16), ("at", 48))), (3, (0, 700), (-700, 0), (("at", 8), ("at", 16)))],
+}
+
+
+def set_affine(batch, kind, w, h, seed, start=0):
+    """Make the inter CUs of at least 8x8 affine, with control points solved from the target deltas of AFFINE_VARIANTS[kind], the variants in turn from CU to CU,
+    beginning with variant `start` (which shape meets which variant differs from case to case).  'limits': control points at the s16 limits, see
+    _affine_limits."""
+    n = len(batch["x"])
+    ok = (batch["pred_mode"] != MODE_INTRA) & (batch["pred_mode"] != 6) & (batch["log2w"] >= 3) & (batch["log2h"] >= 3)
+    aff = np.zeros(n, np.uint8)
+    cp = np.zeros((n, 2, 3, 2), np.int64)
+    seen, g = {}, 0
+    variants = AFFINE_VARIANTS.get(kind)
+    for i in np.nonzero(ok)[0]:
+        lw, lh = int(batch["log2w"][i]), int(batch["log2h"][i])
+        k = seen.get((lw, lh), 0)
+        seen[(lw, lh)] = k + 1
+        x, y, cuw, cuh = int(batch["x"][i]), int(batch["y"][i]), 1 << lw, 1 << lh
+        used = [bool(batch["refi"][i, l] >= 0) for l in range(2)]
+        if kind == "limits":
+            aff[i], cp[i] = _affine_limits(k + 3 * lw + 5 * lh + seed, lw, lh)
+            continue
+        if kind in ("wide", "tall"):
+            aff[i], cp[i] = _affine_far(k + lw + seed, x, lw, lw, w, 0) if kind == "wide" else _affine_far(k + lh + seed, y, lw, lh, h, 1)
+            continue
+        v = variants[(g + start) % len(variants)]
+        g += 1
+        per_list = [v[:3], v[4] if len(v) > 4 else v[:3]]
+        vn = per_list[0][0]
+        diffs = []
+        for l in range(2):
+            _, dh, dv = per_list[l]
+            if kind == "sizes" and l == 1:      # list 1 with the deltas of another variant: the sub-block is the smaller of the two
+                _, dh, dv = variants[(k * 3 + lw + 2 * lh + 5) % len(variants)][:3]
+                dv = dv if dv is not None else (0, 0)
+            d1 = (aff_diff(dh[0], lw), aff_diff(dh[1], lw))
+            d2 = (aff_diff(dv[0], lh), aff_diff(dv[1], lh)) if vn == 3 else (0, 0)
+            diffs.append((d1, d2))
+        cps = np.zeros((2, 3, 2), np.int64)
+        for l in range(2):
+            cps[l, 1], cps[l, 2] = diffs[l][0], diffs[l][1]
+        sub_w, sub_h, _, _ = aff_path(cps, used, lw, lh, vn)
+        for l in range(2):
+            dh, dv = aff_deltas(cps[l], lw, lh, vn)
+            for a in range(2):
+                pos, cu, pic, l2 = ((x, cuw, w, lw), (y, cuh, h, lh))[a]
+                place = v[3][a]
+                jit = ((k * 37 + 11 * l + 5 * a) % 257) - 128                      # +-4 samples in 1/32
+                if isinstance(place, tuple):                                       # the first sub-block's vector, 1/16 sample
+                    lo, hi = (-128 - pos) * 16, (pic + 128 - pos - cu) * 16
+                    t = {"min": lo, "max": hi, "at": (jit // 32) * 32}[place[0]] + (place[1] if l == 0 else -place[1] if place[0] != "at" else place[1])
+                    mv0 = (t * 32 - dh[a] * (sub_w >> 1) - dv[a] * (sub_h >> 1)) / 128.0
+                else:
+                    min_pic, max_pic, sp = (-pos - 128) * 32, (pic + 128 - pos - cu - 1) * 32, AFF_SPREAD[l2 - 3]
+                    t = {"below": min_pic + sp // 2, "above": max_pic - sp // 2, "lo": min_pic - 40 * 32, "hi": max_pic + 40 * 32, "lo_edge": min_pic, "hi_edge": max_pic}.get(place, place)
+                    t = t + (jit if place in (0, "lo_edge", "hi_edge") else jit // 8)
+                    mv0 = (t * 16 - dh[a] * (cuw >> 1) - dv[a] * (cuh >> 1)) / 128.0
+                d = [int(diffs[l][0][a]), int(diffs[l][1][a])]
+                m = int(np.clip(int(np.floor(mv0 + 0.5)), -32768 - min(0, *d), 32767 - max(0, *d)))
+                if isinstance(place, tuple) and place[0] != "at":                  # on the threshold to the sixteenth where the deltas allow it (a control point moves it by 4)
+                    got = _aff_round(m * 128 + dh[a] * (sub_w >> 1) + dv[a] * (sub_h >> 1), 5)
+                    m += (t - got) // 4 if (t - got) % 4 == 0 else 0
+                cps[l, 0, a], cps[l, 1, a], cps[l, 2, a] = m, m + d[0], m + d[1]
+        aff[i] = vn
+        cp[i] = cps
+    for l in range(2):
+        cp[:, l] *= (batch["refi"][:, l] >= 0)[:, None, None]
+    cp[:, :, 2] *= (aff == 3)[:, None, None]
+    assert cp.min() >= -32768 and cp.max() <= 32767
+    batch["affine"] = aff
+    batch["affine_mv"] = (cp * (aff != 0)[:, None, None, None]).astype(np.int16)
+    if batch.get("dmvr") is not None:
+        batch["dmvr"] = (batch["dmvr"] * (aff == 0)).astype(np.uint8)
+
+
+def _affine_limits(k, lw, lh):
+    """Control points at the s16 limits.  The first sub-block's centre lies inside the triangle of three control points, so its vector stays inside s16 and clip18 (18 bits at
+    1/16 sample = 16 bits at quarter samples) cannot move it; with TWO control points the model turns the y difference of the upper two into an x change along y - an
+    extrapolation: control points 0 and 1 at a limit in x and 40 quarter samples per 8 samples of width apart in y (a delta of 640, far too strong a rotation for EIF).  The
+    map vectors further down the CU leave the range the same way, and with three control points at the corner opposite control point 0 (cp1 + cp2 - cp0).
+    -> (number of control points, control points [list][3][2])"""
+    s = 1 if k & 1 else -1
+    big, opp = (32767, -32768) if s > 0 else (-32768, 32767)
+    a = s * (40 << (lw - 3))
+    kind = (k >> 1) % 5
+    if kind == 0:        # two points, x over the limit down the CU: dv[0] = -dh[1]
+        return 2, np.array([[[big, 0], [big, -a], [0, 0]], [[opp, 0], [opp, a], [0, 0]]], np.int64)
+    if kind == 1:        # two points, y over the limit: dv[1] = dh[0]
+        return 2, np.array([[[0, big], [a, big], [0, 0]], [[0, opp], [-a, opp], [0, 0]]], np.int64)
+    if kind == 2:        # three points, the far corner at twice the limit
+        return 3, np.array([[[0, 0], [big, big], [big, opp]], [[0, 0], [opp, big], [opp, opp]]], np.int64)
+    if kind == 3:        # all three at one limit: no delta, the whole CU one block 8192 samples away
+        return 3, np.array([[[big, opp]] * 3, [[opp, big]] * 3], np.int64)
+    return 3, np.array([[[big, big], [opp, big], [big, opp]], [[opp, opp], [big, opp], [opp, big]]], np.int64)      # from one limit to the other across the CU
+
+
+def _affine_far(k, pos, lw, l2, size, axis):
+    """the wide (axis 0) and the tall (axis 1) case: EIF CUs whose vectors point more than 4096 samples = 2^17 / 32 away along that axis and still into the picture - towards
+    the high end from the CUs at the low one and back; in between a few samples.  Band kept (a mild zoom along x) and exceeded (zoom 1.625, 4.9) in turn."""
+    cu = 1 << l2
+    d1 = aff_diff((24, 320, 2000)[k % 3], lw)
+    far = 4096 + 2 + (k * 5) % 12                      # samples
+    c = far if pos + cu + far + 8 < size else (-far if pos - far - 8 >= 0 else (k * 7) % 33 - 16)
+    t = [((k * 3) % 17 - 8) * 16 + k % 16, ((k * 3) % 17 - 8) * 16 + k % 16]      # the centre's vector, 1/32 sample
+    t[axis] = c * 32 + k % 32
+    dh0 = (d1 * 128) >> lw
+    m = [int(np.floor((t[0] * 16 - dh0 * ((1 << lw) >> 1)) / 128.0 + 0.5)), int(np.floor(t[1] * 16 / 128.0 + 0.5))]
+    cps = np.array([m, [m[0] + d1, m[1] + (k % 3) - 1], [m[0] + (k % 5) - 2, m[1] + (k % 7) - 3]], np.int64)
+    return 3, np.stack([cps, cps])
+
+
+# every CU shape of 8 .. 128 a side: the ones with a side of 128 take a CTU each, the others a quarter of one
+AFFINE_SHAPES_128 = ((128, 128), (128, 8), (8, 128), (128, 64), (64, 128), (128, 16), (16, 128), (128, 32), (32, 128))
+AFFINE_SHAPES_64 = tuple((a, b) for a in (8, 16, 32, 64) for b in (8, 16, 32, 64))
+
+
+def affine_partition(w, h, rot=0):
+    """dmvr_partition's sibling for CTU 128: of every four whole CTUs three hold one shape with a side of 128 each and one holds a shape of at most 64x64 per quarter (`rot` says
+    where in the two lists a picture starts and which CTU is the quartered one, so that ten pictures hold each shape at least twice); what is left at the picture's right and bottom is tiled with the widest of 8x8, 16x8, 8x16
+    ... 64x8, 8x64 that fits.  -> x, y, log2w, log2h, ctu_cu_start"""
+    xs, ys, ws, hs, start = [], [], [], [], []
+    n = big = 0
+    for cy in range(0, h, 128):
+        for cx in range(0, w, 128):
+            start.append(len(xs))
+            iw, ih = min(cx + 128, w) - cx, min(cy + 128, h) - cy
+            if iw == 128 and ih == 128:
+                if n & 3 != rot & 3:
+                    parts = [(cx, cy, 128, 128, AFFINE_SHAPES_128[(3 * rot + big) % len(AFFINE_SHAPES_128)])]
+                    big += 1
+                else:
+                    parts = [(cx + (q & 1) * 64, cy + (q >> 1) * 64, 64, 64, AFFINE_SHAPES_64[(4 * rot + q) % 16]) for q in range(4)]
+                n += 1
+            else:
+                bw = max(s for s in (8, 16, 32, 64) if iw % s == 0) if ih % 8 == 0 and ih < 128 and iw >= ih else 8
+                bh = max(s for s in (8, 16, 32, 64) if ih % s == 0) if bw == 8 else 8
+                parts = [(cx, cy, iw, ih, (bw, bh))]
+            for px, py, pw, ph, (bw, bh) in parts:
+                for by in range(py, py + ph, bh):
+                    for bx in range(px, px + pw, bw):
+                        xs.append(bx); ys.append(by); ws.append(bw); hs.append(bh)
+    start.append(len(xs))
+    return (np.array(xs, np.uint16), np.array(ys, np.uint16), np.log2(ws).astype(np.uint8), np.log2(hs).astype(np.uint8), np.array(start, np.uint32))
+
+
+def regenerate_affine_batch(case, seed, gen):
+    """Replace the case's batch by one that synth.gen_frame draws on affine_partition (gen: its keyword arguments + 'rot'); CTU 128"""
+    from xevd_amd import synth
+    gen = dict(gen)
+    rot = gen.pop("rot", 0)
+    assert case["log2_ctu"] == 7
+    old = case["batch"]
+    b = synth.gen_frame(np.random.default_rng(seed), case["w"], case["h"], case["bd"], log2_ctu=7, partition=affine_partition(case["w"], case["h"], rot), **gen)
+    b["constrained_intra_pred"] = old.get("constrained_intra_pred", 0)
+    case["batch"] = b
+
+
 PER_CU = ("x", "y", "log2w", "log2h", "pred_mode", "refi", "mv", "qp", "cbf", "coef_off", "ipm", "ats", "ats_inter", "affine", "affine_mv", "dmvr", "tree", "cbf_sub")
 
 
@@ -454,11 +696,14 @@ def set_tiles(case, col_bd, row_bd, across):
 def apply(case, spec, seed=0):
     """spec: {'content': kind | [kind per reference picture], 'start': kind, 'qp': 'areas', 'mv': 'grid8' | 'small' | 'thresholds' | 'dmvr_mirror' | 'dmvr_zero' | 'dmvr_thresholds',
               'alf': (kind, ctb), 'levels': 'dense', 'tiles': (col_bd, row_bd, across), 'dmvr_pair': kind | [kind of pair 0, of pair 1],
-              'partition': synth.gen_frame arguments for a batch on dmvr_partition }"""
+              'partition': synth.gen_frame arguments for a batch on dmvr_partition, 'affine_partition': the same on affine_partition (+ 'rot'),
+              'affine': 'sizes' | 'eif' | 'trans' | 'limits' | 'wide' | 'tall' (set_affine), 'affine_start': the first variant }"""
     w, h, bd = case["w"], case["h"], case["bd"]
     base = 7919 * (seed + 1)
     if spec.get("partition") is not None:
         regenerate_batch(case, base + 500, spec["partition"])
+    if spec.get("affine_partition") is not None:
+        regenerate_affine_batch(case, base + 500, spec["affine_partition"])
     kinds = spec.get("content")
     if kinds is not None:
         done = {}
@@ -497,6 +742,8 @@ def apply(case, spec, seed=0):
         set_mv_dmvr_zero(b)
     elif spec.get("mv") == "dmvr_thresholds":
         set_mv_dmvr_thresholds(b, w, h)
+    if spec.get("affine") is not None:      # (after the vectors: the control points are the affine CUs' own)
+        set_affine(b, spec["affine"], w, h, seed, spec.get("affine_start", 0))
     if spec.get("levels") == "dense":
         set_dense_levels(b)
     if spec.get("alf") is not None and case.get("alf_params") is not None:
@@ -514,6 +761,8 @@ def apply(case, spec, seed=0):
 _ADDB = {"addb": 1, "inter_frac": 0.7, "qp_range": (0, 51), "coded_frac": 0.5, "split_prob": 0.6}
 _DMVR = {"inter_frac": 1.0, "dmvr_frac": 0.95, "oob_frac": 0.0}
 _DGEN = {"inter_frac": 1.0, "bi_frac": 0.9, "n_refs": (2, 2), "oob_frac": 0.0, "admvp": True, "dmvr_frac": 0.95}
+_AFF = {"log2_ctu": 7, "inter_frac": 1.0, "oob_frac": 0.0}
+_AGEN = {"inter_frac": 1.0, "bi_frac": 0.5, "n_refs": (2, 2), "oob_frac": 0.0, "admvp": True, "ats_inter_frac": 0.6, "coded_frac": 0.85}
 _X_LADDER = {"content": ["ladder", "noise", "rails_dither", "ladder"], "qp": "areas", "mv": "grid8"}
 EXTREME_CASES = [
     # ADDB: QP 0..51 x slice offsets; step ladder / full-range noise / rails; with ALF behind the filter (k_addb_alf) and without (k_addb)
@@ -580,12 +829,34 @@ EXTREME_CASES = [
      ("dmvr_start_clip", "dmvr_sub_clip")),
     ("x_dmvr_shapes_ctu128_8b", 264, 136, 8, 1, 1, (2, 2), 0.9, dict(_DMVR, addb=1, alf=1, log2_ctu=7, extreme={"partition": dict(_DGEN, ats_inter_frac=0.4), "dmvr_pair": ["smooth_low", "noise"], "mv": "dmvr_mirror"}),
      ("dmvr_shape", "dmvr_cu128")),
-    ("x_affine_checker_10b", 200, 136, 10, 1, 1, (2, 2), 0.5, {"addb": 1, "inter_frac": 1.0, "affine_frac": 0.9, "split_prob": 0.3, "extreme": {"content": ["checker1", "noise", "checker2"]}}, ()),
-    ("x_affine_noise_12b", 200, 136, 12, 1, 1, (1, 1), 0.5, {"addb": 1, "alf": 1, "inter_frac": 1.0, "affine_frac": 0.9, "split_prob": 0.3, "extreme": {"content": "noise"}}, ()),
+    # affine at every branch of its model (set_affine; control points solved from target deltas), CTU 128 with every CU shape of 8 .. 128 a side (affine_partition)
+    ("x_aff_sizes_10b", 264, 264, 10, 1, 1, (2, 2), 0.5, dict(_AFF, addb=1, extreme={"affine_partition": dict(_AGEN, rot=0), "affine": "sizes"}), ("aff_sizes", "aff_mvf")),
+    ("x_aff_sizes_8b_noaddb", 264, 264, 8, 1, 1, (2, 2), 0.5, dict(_AFF, extreme={"affine_partition": dict(_AGEN, rot=1), "affine": "sizes", "content": ["noise", "checker2"]}), ("aff_sizes", "aff_mvf")),
+    ("x_aff_eif_10b", 264, 264, 10, 1, 1, (2, 2), 0.5, dict(_AFF, addb=1, alf=1, extreme={"affine_partition": dict(_AGEN, rot=2), "affine": "eif", "content": "noise"}), ("aff_applic", "aff_eif_clamp", "aff_eif_rails")),
+    ("x_aff_eif_12b", 264, 264, 12, 1, 1, (2, 2), 0.5, dict(_AFF, addb=1, extreme={"affine_partition": dict(_AGEN, rot=3), "affine": "eif", "content": ["checker2", "noise", "checker1"]}), ("aff_applic", "aff_band", "aff_eif_clamp", "aff_eif_rails")),
+    ("x_aff_eif_checker_8b_noaddb", 264, 264, 8, 1, 1, (2, 2), 0.5, dict(_AFF, extreme={"affine_partition": dict(_AGEN, rot=4), "affine": "eif", "content": ["checker1", "checker2", "checker4"]}), ("aff_applic", "aff_band", "aff_eif_clamp", "aff_eif_rails")),
+    ("x_aff_eif_checker_10b", 264, 264, 10, 1, 1, (2, 2), 0.5, dict(_AFF, addb=1, extreme={"affine_partition": dict(_AGEN, rot=5), "affine": "eif", "content": ["checker2", "checker1"]}), ("aff_applic", "aff_band", "aff_eif_clamp", "aff_eif_rails")),
+    ("x_aff_trans_10b", 264, 264, 10, 1, 1, (2, 2), 0.5, dict(_AFF, addb=1, extreme={"affine_partition": dict(_AGEN, rot=8), "affine": "trans", "content": ["noise", "checker2"]}), ("aff_sub_mvclip", "aff_sub_regime")),
+    ("x_aff_trans_amp40_12b_noaddb", 264, 264, 12, 1, 1, (2, 2), 0.5, dict(_AFF, amp=40.0, extreme={"affine_partition": dict(_AGEN, rot=9, amp=40.0, coded_frac=0.9, qp_range=(40, 51)), "affine": "trans", "content": "noise"}), ("aff_sub_mvclip", "aff_sub_regime", "recon_rails")),
+    ("x_aff_limits_8b", 264, 264, 8, 1, 1, (2, 2), 0.5, dict(_AFF, addb=1, alf=1, extreme={"affine_partition": dict(_AGEN, rot=6), "affine": "limits", "content": "noise"}), ("aff_clip18", "aff_mvf")),
+    ("x_aff_limits_10b_noaddb", 264, 264, 10, 1, 1, (2, 2), 0.5, dict(_AFF, extreme={"affine_partition": dict(_AGEN, rot=7), "affine": "limits", "content": ["noise", "checker4"]}), ("aff_clip18", "aff_mvf")),
+    ("x_affine_checker_10b", 200, 136, 10, 1, 1, (2, 2), 0.5, {"addb": 1, "inter_frac": 1.0, "affine_frac": 0.9, "split_prob": 0.3, "extreme": {"content": ["checker1", "noise", "checker2"]}}, ("aff_mvf", "aff_eif_rails", "aff_sub_mvclip", "aff_sub_regime")),
+    ("x_affine_noise_12b", 200, 136, 12, 1, 1, (1, 1), 0.5, {"addb": 1, "alf": 1, "inter_frac": 1.0, "affine_frac": 0.9, "split_prob": 0.3, "extreme": {"content": "noise"}}, ("aff_mvf", "aff_eif_rails", "aff_sub_regime")),
 ]
 
 # the cases written for the branches of the DMVR search (tests/test_oracle_extremes.py: test_dmvr_cases_together_reach_every_branch)
 DMVR_CASES = [s for s in EXTREME_CASES if "dmvr_pair" in s[8].get("extreme", {})]
+
+# the cases written for the branches of the affine model (tests/test_oracle_extremes.py: test_affine_cases_together_reach_every_branch)
+AFFINE_CASES = [s for s in EXTREME_CASES if "affine" in s[8].get("extreme", {})]
+# clip18 of the EIF range, 1/32 sample: max_pic = (width + 128 - x - cuw - 1) * 32 passes 2^17 - 1 for x < width - cuw - 3969, min_pic = (-x - 128) * 32 passes -2^17 for
+# x > 3968 - from a width of 3984 a picture has both.  That the clip decides which sample is fetched takes more: a vector of more than 4096 samples that still ends inside the
+# picture (in the replicated border every vector fetches the same values), so CUs at x >= 4096 - the smallest multiple of 64 is 4160, whose last column of CTUs holds them.  The
+# same along y: the product's 8K pictures are 4320 high.  (build_case arguments; held to the oracle and the reference like the extreme cases, one GPU test each)
+AFFINE_FAR_CASES = [
+    ("x_aff_wide_10b", 4160, 72, 10, 1, 1, (1, 1), 0.4, {"addb": 1, "inter_frac": 1.0, "oob_frac": 0.0, "split_prob": 0.6, "extreme": {"content": "noise", "affine": "wide"}}),
+    ("x_aff_tall_8b", 136, 4160, 8, 1, 1, (1, 1), 0.4, {"addb": 1, "inter_frac": 1.0, "oob_frac": 0.0, "split_prob": 0.6, "extreme": {"content": "noise", "affine": "tall"}}),
+]
 
 # ---- tile grids inside interior filter areas: pictures of at least 264x264, ADDB + ALF, CTU 64, uneven 2x2 and 3x2 grids - the CTU-aligned tile
 # borders cross the 64x64 areas k_addb_alf filters through its interior path -, loop_filter_across_tiles 0 and 1, rail-to-rail content so that a border edge filtered

@@ -36,7 +36,13 @@ class OrcCensus(C.Structure):
                 ("mc_bi_rails", C.c_uint32 * 3), ("mv_clip", C.c_uint32 * 4), ("recon_coded", C.c_uint32), ("recon_wrap", C.c_uint32), ("recon_clip", C.c_uint32 * 2),
                 ("dmvr_shape", C.c_uint32 * 4), ("dmvr_not_refined", C.c_uint32 * 2), ("dmvr_exit", C.c_uint32 * 5), ("dmvr_win", (C.c_uint32 * 5) * 2),
                 ("dmvr_diag", C.c_uint32 * 4), ("dmvr_tie", C.c_uint32 * 2), ("dmvr_subpel", (C.c_uint32 * 18) * 2), ("dmvr_total", (C.c_uint32 * 5) * 5),
-                ("dmvr_start_clip", C.c_uint32 * 4), ("dmvr_sub_clip", C.c_uint32 * 4), ("dmvr_win_off", (C.c_uint32 * 8) * 2), ("dmvr_regime", (C.c_uint32 * 4) * 3)]
+                ("dmvr_start_clip", C.c_uint32 * 4), ("dmvr_sub_clip", C.c_uint32 * 4), ("dmvr_win_off", (C.c_uint32 * 8) * 2), ("dmvr_regime", (C.c_uint32 * 4) * 3),
+                ("aff_shape", ((C.c_uint32 * 5) * 5) * 2), ("aff_vn", C.c_uint32 * 2), ("aff_lists", C.c_uint32 * 3), ("aff_w", (C.c_uint32 * 6) * 2), ("aff_sub", (C.c_uint32 * 6) * 2),
+                ("aff_applic", (C.c_uint32 * 3) * 2), ("aff_applic_skipped", C.c_uint32), ("aff_lifted", C.c_uint32), ("aff_band", C.c_uint32 * 2), ("aff_band_vn", C.c_uint32 * 2), ("aff_range", (C.c_uint32 * 3) * 2),
+                ("aff_spread", C.c_uint32 * 5), ("aff_range_clip18", (C.c_uint32 * 2) * 2), ("aff_eif_clamp", ((C.c_uint32 * 2) * 2) * 2), ("aff_eif_frac", (C.c_uint32 * 32) * 2),
+                ("aff_eif_neg", C.c_uint32 * 2), ("aff_eif_clip", (C.c_uint32 * 2) * 3), ("aff_sub_mvclip", C.c_uint32 * 4), ("aff_sub_mvclip_frac", C.c_uint32 * 4),
+                ("aff_sub_clip18", C.c_uint32 * 2), ("aff_sub_regime", (C.c_uint32 * 4) * 2), ("aff_sub_luma_whole_chroma_half", C.c_uint32 * 2), ("aff_mvf", C.c_uint32 * 4),
+                ("aff_mvf_bl_vn2", C.c_uint32), ("aff_mvf_clip18", C.c_uint32), ("aff_mvf_whole_cu", C.c_uint32), ("aff_ats", ((C.c_uint32 * 2) * 4) * 2), ("aff_cbf", (C.c_uint32 * 8) * 2)]
 
 
 def census_reset():

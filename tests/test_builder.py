@@ -220,3 +220,42 @@ def test_builder_survives_mutated_batches():
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "fuzz_builder.py"), "5", "150"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     assert r.returncode == 0 and b"done:" in r.stdout, r.stdout.decode()[-800:]
+
+
+@pytest.mark.parametrize("name", ["x_aff_sizes_10b", "x_aff_eif_checker_8b_noaddb"])
+def test_builder_affine_tile_lists_follow_the_oracle_census(name):
+    """The host sorts the affine CUs into the work lists of k_affine_eif and k_affine_sub with the header the kernels derive the path from (affine_model.h).  Held to the
+    oracle here: the path of every CU by the test side's restatement of the model (extreme_inputs.aff_path), whose totals per path and CU shape must be the oracle's census;
+    then the builder's tile list must be exactly the one that follows from those paths and the CU sizes - the EIF tiles of 16x16 first, then the translation tiles of 32x32,
+    CUs in batch order, tiles row by row -, byte for byte (AffItem: CU index, control-point index, tile origin), on one and on three builder threads."""
+    import cases
+    import extreme_inputs as xi
+    import oracle_lib as ol
+    spec = next(s for s in xi.AFFINE_CASES if s[0] == name)
+    cs = cases.build_case(*spec[:9])
+    b = cs["batch"]
+    ol.census_reset()
+    cases.run_cpu("oracle", cs, deblock=False, pad=False)
+    cen = ol.census()
+    shape = np.zeros((2, 5, 5), np.int64)
+    lists = ([], [])
+    affine = np.nonzero(b["affine"])[0]
+    for k, i in enumerate(affine):
+        lw, lh = int(b["log2w"][i]), int(b["log2h"][i])
+        _, _, eif, _ = xi.aff_path(b["affine_mv"].reshape(-1, 2, 3, 2)[i].astype(np.int64), [b["refi"][i, l] >= 0 for l in range(2)], lw, lh, int(b["affine"][i]))
+        shape[0 if eif else 1, lw - 3, lh - 3] += 1
+        step = 16 if eif else 32
+        lists[0 if eif else 1].extend((i, k, tx, ty, 0) for ty in range(0, 1 << lh, step) for tx in range(0, 1 << lw, step))
+    assert np.array_equal(shape, cen["aff_shape"]), "paths by the test side's model against the oracle's census"
+    assert len(lists[0]) > 0 and len(lists[1]) > 0
+    want = np.array(lists[0] + lists[1], dtype=[("cu", "<u4"), ("aff", "<u4"), ("tx", "<u2"), ("ty", "<u2"), ("pad", "<u4")]).tobytes()
+    h = 1469598103934665603
+    for byte in want:
+        h = ((h ^ byte) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    lib = _lib()
+    sp = abi.make_seq_params(cs["w"], cs["h"], cs["bd"], log2_ctu=cs["log2_ctu"], iqt=cs["iqt"], admvp=cs["admvp"], addb=cs["addb"], alf=cs["alf"], eipd=cs["eipd"])
+    cb, keep = abi.make_cu_batch(b)
+    for threads in (1, 3):
+        got = _build(lib, sp, cb, threads)
+        assert got[10 + 7] == len(lists[0]) + len(lists[1]), "number of affine tiles"
+        assert got[6] == f"{h:016x}", f"affine tile list, {threads} builder thread(s)"

@@ -1,8 +1,9 @@
 """GPU suite, ends of the ranges (run with -m gpu on an MI355X): the HIP backend against the CPU oracle on the extreme cases of tests/extreme_inputs.py -
 samples on the rails, 0 / max checkerboards through every interpolation phase, QP 0..51 x ADDB slice offsets -12..12 (packed and scalar line filters),
 ALF coefficients at their legal limits on gratings / noise / checkerboards, vectors on the MV-clip thresholds, every branch of the DMVR search (planted
-displacements, vectors on the thresholds, all sub-block shapes; also its refined vectors, and the scalar form of its prediction) - all three padded planes and the
-residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
+displacements, vectors on the thresholds, all sub-block shapes; also its refined vectors, and the scalar form of its prediction), every branch of the affine model
+(control points solved from target deltas: sub-block sizes, EIF applicability, the memory band and its clamps, the clip thresholds of the translation path, control points at
+the s16 limits, vectors of more than 4096 samples; also the stored sub-block vectors) - all three padded planes and the residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
 reach the branches they are for) are repeated here because this file needs only the oracle, which always ships."""
 import numpy as np
 import pytest
@@ -113,6 +114,45 @@ def test_gpu_dmvr_case_stored_vectors(name):
     for i in range(len(b["x"])):
         own[b["y"][i] >> 2:(b["y"][i] >> 2) + ((1 << b["log2h"][i]) >> 2), b["x"][i] >> 2:(b["x"][i] >> 2) + ((1 << b["log2w"][i]) >> 2)] = b["mv"][i].reshape(4)
     assert np.array_equal(maps.map_mv.reshape(maps.h_scu, maps.w_scu, 4), own) == bool(cs["addb"])
+
+
+# ---- affine: the cases of xi.AFFINE_CASES (every branch of the model, test_affine_cases_together_reach_every_branch) - planes, residual arena and census in test_gpu_extreme_case
+# above, those with ADDB at up to 10 bit also in test_gpu_extreme_case_scalar_deblocking (the sub-block vectors feed the boundary strengths)
+@pytest.mark.parametrize("spec", xi.AFFINE_CASES, ids=[s[0] for s in xi.AFFINE_CASES])
+def test_gpu_affine_case_residual_pass_ahead(spec):
+    _check(cases.build_case(*spec[:9]), spec[0] + " (ahead)", ahead=True)
+
+
+@pytest.mark.parametrize("name", ["x_aff_sizes_10b", "x_aff_sizes_8b_noaddb", "x_aff_limits_8b", "x_aff_limits_10b_noaddb"])
+def test_gpu_affine_case_stored_vectors(name):
+    """the vectors the picture keeps (side-information export) against the oracle's map: every sub-block size, control points at the s16 limits (map vectors moved by
+    clip18), two-point CUs whose bottom-left sub-block takes the formula; under ADDB and under the baseline filter.  A failure here and not in the planes is one of
+    aff_store_mvf, not of the prediction."""
+    import side_info_ref as sr
+    from test_gpu_side_info import decode, open_decoder, start
+    spec = next(s for s in xi.AFFINE_CASES if s[0] == name)
+    cs = cases.build_case(*spec[:9])
+    (_, _, maps, _), cen = run_oracle_with_census(cs)
+    assert cen["aff_mvf_bl_vn2"] > 0 and (cen["aff_mvf"] > 0).all() and ((cen["aff_mvf_clip18"] > 0) == ("limits" in name)) and (("sizes" not in name) or (cen["aff_sub"][:, :3] > 0).all())
+    want = sr.blocks_from_maps(maps, maps.map_scu, cs["batch"], {k: p.poc for k, p in cs["refs"].items()}, cases.CUR_POC)
+    with open_decoder(cs) as dec:
+        slots, cur, hb = start(dec, cs)
+        decode(dec, cs, slots, cur, hb)
+        got = dec.frame_side_info(cur).cpu().numpy()
+    for p in range(4):
+        assert np.array_equal(got[p], want[p]), f"{name}: vector plane {p}, first differences at 4x4 units {np.argwhere(got[p] != want[p])[:4].tolist()}"
+
+
+@pytest.mark.parametrize("spec", xi.AFFINE_FAR_CASES, ids=[s[0] for s in xi.AFFINE_FAR_CASES])
+def test_gpu_affine_far_vectors(spec):
+    """clip18 of the EIF range: a picture of 4160 samples along one axis, vectors of more than 4096 samples that end inside it (the wide one: 65 CTUs a row)"""
+    from test_oracle_extremes import check_far_census
+    cs = cases.build_case(*spec[:9])
+    (ref, _, _, rr), cen = run_oracle_with_census(cs)
+    check_far_census(spec, cen)
+    out, res = cases.run_gpu(cs, resid=True)
+    assert np.array_equal(res[:len(rr)], rr), "residual arena"
+    _same(out, ref, spec[0])
 
 
 # content kind x bit depth x partition depth per coding family.  split_prob low / high: k_inter's region and tile roles / its split role see the saturated windows

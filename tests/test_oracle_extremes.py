@@ -1,5 +1,5 @@
 """The extreme cases (tests/extreme_inputs.py: rail-to-rail content, QP 0..51 x slice offsets, vectors on the MV-clip thresholds, ALF coefficients at their legal
-limits, every branch of the DMVR search) through the CPU oracle and the REAL reference (oracle/_ref), plus the census: every case asserts that the oracle took the branches it exists for.
+limits, every branch of the DMVR search and of the affine model) through the CPU oracle and the REAL reference (oracle/_ref), plus the census: every case asserts that the oracle took the branches it exists for.
 
 The comparison is the one of test_picture_level_oracle_equals_reference: residual arena, pre-deblock planes, maps, final padded planes, against the reference's
 normative C path (simd=0) only - its SIMD kernels are known to diverge on out-of-range input (the level-cap comment in synth.gen_frame) and the
@@ -37,6 +37,35 @@ dmvr_sub_clip was expected to be unreachable too - a sub-block on a threshold li
 census refuted it: that holds when BOTH lists are on the threshold.  With one list there and the other inside the picture the costs differ along the axis, the search
 moves, and the list on the threshold is pushed past it (x_dmvr_thresholds_*: 'dmvr_sub_clip' is a required bucket, and the oracle with a clip that does nothing decodes
 those two cases differently).
+
+Affine (xi.AFFINE_CASES: control points solved from target deltas - set_affine -, CTU 128 with every CU shape of 8 .. 128 a side on both paths - affine_partition makes all 25,
+none is left out -, and xi.AFFINE_FAR_CASES: 4160 samples along one axis).  The census over the ten cases together, as test_affine_cases_together_reach_every_branch prints it
+(936 affine CUs, 1432 list uses):
+  CUs on the EIF / the translation path              574 / 362, every shape on both (128x128: 1 / 3); 8 bit 184 / 110, 10 bit 303 / 180, 12 bit 67 / 92
+  control points 2 / 3;  list 0 only, list 1 only, both     200 / 736;  298 / 142 / 496
+  wx of 0, 1, 2, 3, 4, above 4 (per list)            232 6 5 7 27 1155;  wy 429 9 27 6 55 906
+  sub-block width of 4 .. 128                        518 355 30 11 6 16;  height 372 408 66 27 33 30
+  EIF applicable / dv[1] < -one / fetched lines      list 0: 594 / 60 / 140, list 1: 461 / 17 / 38;  list 1 not looked at: 122;  sub-block raised to 8: 255 CUs
+  memory band exceeded / kept (EIF list uses)        246 (all with three control points) / 607
+  window below min_pic / above max_pic / inside      x 60 / 66 / 120, y 83 / 82 / 81;  spreads 128 .. 2272: 245 99 46 63 39
+  samples clamped low, high                          x: picture range 11812, 25460, band 73542, 65888;  y: picture range 26662, 16868, band 2561, 2847
+  fractions 0 .. 31 all reached (minimum 7364 samples);  negative whole-sample offsets 358407 / 370920;  final clip Y 44406 / 44321, U 12601 / 12644, V 12455 / 12306
+  translation vector clipped l / r / t / b           84 / 63 / 77 / 77, with a fraction that the clip removes 18 / 63 / 22 / 77;  moved by clip18 x / y: 33 / 33
+  regimes copy / vertical / horizontal / 2-D         luma 150 108 114 207, chroma 81 121 108 269;  luma whole with chroma half x / y: 56 / 75
+  map vectors from control point 0 / 1 / 2 / formula 1432 / 1077 / 652 / 22017;  bottom-left of a two-point CU 216;  components moved by clip18 1506;  sub-block = CU 228
+  ATS-inter idx 1 .. 4 x pos                         EIF 36 39, 36 46, 11 15, 16 17;  translation 23 30, 21 27, 10 8, 6 13
+  cbf 0 .. 7                                         EIF 94 116 11 123 3 95 13 99;  translation 59 61 12 68 12 68 8 94
+  the far cases: EIF range moved by clip18           x min 28, max 44 (4160x72);  y min 30, max 28 (136x4160);  in the ten cases above: 0
+Asserted to be 0, with the reason:
+  * aff_band_vn[0], the memory band exceeded with TWO control points.  Then dv = (-dh[1], dh[0]), and EIF runs only if dh[0] >= -one and max(dh[0], 0) + |dh[1]| <= 102
+    (5 x that <= 512).  The 4x4 bounding box (aff_eif_applicable) spans 5 (dh[0] + 512 + |dh[1]|) <= 3070 along x and 5 (|dh[1]| + dh[0] + 512) <= 3070 along y, i.e. at most
+    ((3070 + 511) >> 9) + 2 = 8 samples each way: 64 <= 72.  The band is left only by a zoom or shear along x with a small y part, which takes three control points.
+  * aff_range_clip18 in pictures of at most 264 samples: min_pic / max_pic stay below 2^17 / 32 = 4096 samples.  Both ends along both axes are reached by AFFINE_FAR_CASES:
+    max_pic passes 2^17 - 1 for x < width - cuw - 3969, min_pic passes -2^17 for x > 3968, and for the clip to decide which sample is fetched a vector of more than 4096 samples
+    has to end inside the picture (in the replicated border every vector fetches the same values): CUs at x >= 4096, so 4160 is the smallest multiple of 64.
+Mutations of the oracle's affine functions, one at a time, and the cases whose comparison with the reference catches them: profiles/affine_census.txt.  Two of the listed ones
+change no output and are caught by none: `<` against `<=` (`>` against `>=`) in the two range branches - on equality the re-anchored window IS centre +- spread, since max_pic -
+min_pic = (picture + 255 - CU) x 32 is more than any 2 x spread -, and that is also why the min / max of the re-anchored ends never picks the picture's other end.
 
 The census (which needs only the oracle) and the generator checks run everywhere; the comparison against the reference carries the `ref` mark and is skipped
 where oracle/_ref is not built, like tests/test_oracle_vs_ref.py.
@@ -108,7 +137,39 @@ def _dmvr_win_off(cen, cs):
     _all(cen["dmvr_win_off"][1][2:5], "refined position, chroma samples from the starting vector's window, -1 .. 1")
 
 
+# ---- affine: what the cases of xi.AFFINE_CASES are for (per case: the tags below; all of them together: test_affine_cases_together_reach_every_branch)
+def _aff_sizes(cen, cs):
+    _all(cen["aff_w"][:, [0, 2, 4, 5]], "affine wx / wy of 0, 2, 4, above 4")      # (1 and 3 take a side of 128 and three control points: asked of the cases together)
+    _all(cen["aff_sub"][:, :3], "affine sub-block [width, height] of 4, 8, 16")      # (32 takes a delta of 1, 64 and 128 are the whole CU: asked of the cases together)
+    _all(cen["aff_shape"].sum((1, 2)), "affine CUs on [the EIF, the translation] path")
+
+
+def _aff_applic(cen, cs):
+    _all(cen["aff_applic"], "EIF applicability per list examined [list 0, list 1] x [applicable, dv[1] < -one, fetched lines]")
+    _all([cen["aff_applic_skipped"], cen["aff_lifted"]], "list 1 not examined after list 0 failed; sub-block raised to 8")
+
+
+def _aff_band(cen, cs):
+    _all(cen["aff_band"], "EIF list uses with the memory band [exceeded, kept]")
+    _all(cen["aff_range"], "EIF band [x, y] x [below min_pic, above max_pic, inside]")
+    _all(cen["aff_spread"], "EIF band spreads 128, 256, 544, 1120, 2272")
+
+
+def _aff_clip18(cen, cs):
+    _all(cen["aff_sub_clip18"], "translation vector moved by clip18 [x, y]")
+    _all([cen["aff_mvf_clip18"]], "map vector moved by clip18")
+
+
 REQUIRE = {
+    "aff_sizes": _aff_sizes,
+    "aff_mvf": lambda cen, cs: _all(list(cen["aff_mvf"]) + [cen["aff_mvf_bl_vn2"], cen["aff_mvf_whole_cu"]], "map vectors from control point 0, 1, 2, the formula; bottom-left of two points; whole CU"),
+    "aff_applic": _aff_applic,
+    "aff_band": _aff_band,
+    "aff_eif_clamp": lambda cen, cs: _all(cen["aff_eif_clamp"], "EIF samples clamped [x, y] x [low, high] x [picture range, band]"),
+    "aff_eif_rails": lambda cen, cs: _all(cen["aff_eif_clip"], "EIF output clipped [Y, U, V] x [at 0, at max]"),
+    "aff_sub_mvclip": lambda cen, cs: _all(cen["aff_sub_mvclip"], "translation vector clipped [left, right, top, bottom]") or _all(cen["aff_sub_mvclip_frac"], "... with a fraction the clip removes"),
+    "aff_sub_regime": lambda cen, cs: _all(cen["aff_sub_regime"], "translation [luma, chroma] x [copy, vertical, horizontal, 2-D]") or _all(cen["aff_sub_luma_whole_chroma_half"], "luma whole, chroma half [x, y]"),
+    "aff_clip18": _aff_clip18,
     "dmvr_shape": lambda cen, cs: _all(cen["dmvr_shape"], "DMVR sub-blocks of 8x8, 8x16, 16x8, 16x16"),
     "dmvr_cu128": _dmvr_cu128,
     "dmvr_not_refined": lambda cen, cs: _all(cen["dmvr_not_refined"][:1], "flagged bi-predicted CUs whose references are not POC-symmetric"),
@@ -155,6 +216,7 @@ def run_oracle_with_census(cs):
 def check_census(spec, cs, cen):
     assert cen["addb_lost"][1] == 0 and cen["addb_lost"][2] == 0 and cen["mc_stage1_wrap"] == 0, "a bucket the module docstring calls unreachable was reached"
     assert cen["dmvr_not_refined"][1] == 0 and cen["dmvr_win_off"][0][[0, 6, 7]].sum() == 0 and cen["dmvr_win_off"][1][[0, 1, 5, 6, 7]].sum() == 0, "a DMVR bucket the module docstring calls unreachable was reached"
+    assert cen["aff_band_vn"][0] == 0, "an affine bucket the module docstring calls unreachable was reached"
     for tag in spec[9]:
         REQUIRE[tag](cen, cs)
 
@@ -240,6 +302,101 @@ def test_dmvr_case_vectors_oracle_equals_reference(spec):
     cs = cases.build_case(*spec[:9])
     a, b = cases.dmvr_mvs("oracle", cs), cases.dmvr_mvs("ref", cs)
     assert len(a) > 0 and a.shape == b.shape and np.array_equal(a, b), f"refined vectors, first differences at sub-blocks {np.argwhere(a != b)[:4, 0].tolist()}"
+
+
+def affine_census_together():
+    """the census of the affine cases, summed: -> (AFFINE_CASES, AFFINE_FAR_CASES, {bit depth: ... of AFFINE_CASES})"""
+    def add(a, b):
+        return b if a is None else {k: a[k] + b[k] for k in b}
+    near, far, by_bd = None, None, {}
+    for spec in xi.AFFINE_CASES + xi.AFFINE_FAR_CASES:
+        _, cen = run_oracle_with_census(cases.build_case(*spec[:9]))
+        cen = {k: np.asarray(v) for k, v in cen.items() if k.startswith("aff_")}
+        if spec in xi.AFFINE_FAR_CASES:
+            far = add(far, cen)
+        else:
+            near, by_bd[spec[3]] = add(near, cen), add(by_bd.get(spec[3]), cen)
+    return near, far, by_bd
+
+
+def test_affine_cases_together_reach_every_branch():
+    """the conditions the affine cases were chosen for, over all of them (the table of the module docstring is this test's output)"""
+    near, far, by_bd = affine_census_together()
+    for k, v in near.items():
+        print(k, v.tolist())
+    print("far cases: aff_range_clip18", far["aff_range_clip18"].tolist(), "aff_band", far["aff_band"].tolist(), "aff_eif_clamp", far["aff_eif_clamp"].tolist())
+    _all(near["aff_shape"], "affine CUs on [EIF, translation] x width 8 .. 128 x height 8 .. 128")      # affine_partition makes every shape: none is left out
+    _all(near["aff_vn"], "control points 2, 3")
+    _all(near["aff_lists"], "list 0 only, list 1 only, both")
+    _all(near["aff_w"], "[wx, wy] of 0, 1, 2, 3, 4, above")
+    _all(near["aff_sub"], "sub-block [width, height] of 4 .. 128")
+    for tag in ("aff_applic", "aff_band", "aff_eif_clamp", "aff_eif_rails", "aff_sub_mvclip", "aff_sub_regime", "aff_clip18", "aff_mvf"):
+        REQUIRE[tag](near, None)
+    _all(near["aff_eif_frac"], "EIF fractions [x, y] 0 .. 31")
+    _all(near["aff_eif_neg"], "EIF samples with a negative whole-sample offset [x, y]")
+    _all(near["aff_ats"], "affine CUs by [path] x ATS-inter idx 1 .. 4 x pos")
+    _all(near["aff_cbf"], "affine CUs by [path] x cbf 0 .. 7")
+    # clip18 of the EIF range takes a picture of more than 4096 samples along the axis (xi.AFFINE_FAR_CASES), in the others it must not happen
+    _all(far["aff_range_clip18"], "EIF range moved by clip18 [x, y] x [min, max]")
+    _all(far["aff_band"], "the far cases with the band [exceeded, kept]")
+    assert near["aff_range_clip18"].sum() == 0
+    # the band is never exceeded with two control points (argument in the module docstring)
+    assert near["aff_band_vn"][0] == 0 and far["aff_band_vn"][0] == 0 and near["aff_band_vn"][1] == near["aff_band"][0]
+    for bd in (8, 10, 12):      # every depth on the EIF path, band kept and exceeded (at 12 bit the row filter shifts by 1, at 8 and 10 by 0), and on the translation path
+        print(bd, "bit: CUs on [EIF, translation]", by_bd[bd]["aff_shape"].sum((1, 2)).tolist(), "band", by_bd[bd]["aff_band"].tolist())
+        assert (by_bd[bd]["aff_shape"].sum((1, 2)) >= 16).all() and (by_bd[bd]["aff_band"] >= 16).all() and (by_bd[bd]["aff_eif_clip"] > 0).all()
+    tools = [spec[8] for spec in xi.AFFINE_CASES]
+    assert {(spec[3], spec[8].get("addb", 0)) for spec in xi.AFFINE_CASES} >= {(8, 0), (8, 1), (10, 0), (10, 1), (12, 0), (12, 1)}      # sub-block vectors feed both deblocking filters
+    assert any(t.get("alf") for t in tools) and any(t.get("amp") == 40.0 for t in tools)
+    assert all(spec[1] <= 264 and spec[2] <= 264 and spec[9] for spec in xi.AFFINE_CASES) and 8 <= len(xi.AFFINE_CASES) <= 10
+
+
+def affine_scu_mask(cs, maps):
+    b = cs["batch"]
+    mask = np.zeros((maps.h_scu, maps.w_scu), bool)
+    for i in np.nonzero(b["affine"])[0]:
+        mask[b["y"][i] >> 2:(b["y"][i] >> 2) + ((1 << b["log2h"][i]) >> 2), b["x"][i] >> 2:(b["x"][i] >> 2) + ((1 << b["log2w"][i]) >> 2)] = True
+    return mask
+
+
+@pytest.mark.ref
+@pytest.mark.parametrize("spec", xi.AFFINE_CASES + xi.AFFINE_FAR_CASES, ids=[s[0] for s in xi.AFFINE_CASES + xi.AFFINE_FAR_CASES])
+def test_affine_case_vectors_oracle_equals_reference(spec):
+    """the vectors xevdm_set_affine_mvf leaves in the SCU map for the affine CUs - control points at the corners, the model at the other sub-blocks - and, for the far cases,
+    the planes"""
+    cs = cases.build_case(*spec[:9])
+    a, _, ma, _ = cases.run_cpu("oracle", cs)
+    b, _, mb, _ = cases.run_cpu("ref", cs, simd=0)
+    mask = affine_scu_mask(cs, ma).ravel()
+    assert mask.sum() > 0
+    va, vb = ma.map_mv[mask], mb.map_mv[mask]
+    assert np.array_equal(va, vb), f"map vectors of affine CUs, first differences at masked SCUs {np.argwhere(va != vb)[:4, 0].tolist()}"
+    assert np.array_equal(ma.map_refi[mask], mb.map_refi[mask])
+    # and they are sub-block vectors: inside some CU they differ from SCU to SCU
+    own = np.zeros((ma.h_scu * ma.w_scu, 2, 2), np.int16)
+    bt = cs["batch"]
+    for i in np.nonzero(bt["affine"])[0]:
+        sel = np.zeros((ma.h_scu, ma.w_scu), bool)
+        sel[bt["y"][i] >> 2:(bt["y"][i] >> 2) + ((1 << bt["log2h"][i]) >> 2), bt["x"][i] >> 2:(bt["x"][i] >> 2) + ((1 << bt["log2w"][i]) >> 2)] = True
+        own[sel.ravel()] = bt["affine_mv"].reshape(-1, 2, 3, 2)[i][:, 0]
+    assert not np.array_equal(own[mask], va)
+    for c in range(3):
+        assert np.array_equal(a.bufs[c], b.bufs[c]), f"final plane {c}: {np.argwhere(a.bufs[c] != b.bufs[c])[:4]}"
+
+
+@pytest.mark.parametrize("spec", xi.AFFINE_FAR_CASES, ids=[s[0] for s in xi.AFFINE_FAR_CASES])
+def test_affine_far_case_reaches_the_clip18_of_the_eif_range(spec):
+    cs = cases.build_case(*spec[:9])
+    _, cen = run_oracle_with_census(cs)
+    check_far_census(spec, cen)
+
+
+def check_far_census(spec, cen):
+    axis = 0 if spec[1] > spec[2] else 1
+    _all(cen["aff_range_clip18"][axis], f"EIF range moved by clip18 along axis {axis} [min, max]")
+    _all(cen["aff_band"], "EIF with the band [exceeded, kept]")
+    _all(cen["aff_eif_clamp"][axis], f"EIF samples clamped along axis {axis} [low, high] x [picture range, band]")
+    assert cen["aff_band_vn"][0] == 0
 
 
 def check_tile_census(spec, cs, cen):
