@@ -22,6 +22,7 @@
  *   xgpu_pic_output_device        (no counterpart: the picture as YUV or R'G'B' into the caller's device memory)
  *   xgpu_batch_residual           (no counterpart in the library: the prediction residual of a picture - what the reconstruction adds to the prediction - as dense planes)
  *   xgpu_frame_side_info          (no counterpart in the library; FFmpeg's export_mvs is the usual example: motion vectors, modes, QP of the picture decoded last)
+ *   xgpu_pic_compare              (no counterpart in the library; ffmpeg's psnr / ssim filters are the usual example: a picture against a reference, exactly)
  *
  * plus fine-grained shims with the reference's per-block function-table signatures
  * (XEVD_MC_L / XEVD_MC_C src_base/xevd_mc.h:47-49, XEVD_ITXB src_base/xevd_def.h:360, fn_recon :1466)
@@ -525,6 +526,71 @@ size_t xgpu_resid_size(const xgpu_resid_format *f, int width, int height);
    runs on `stream` behind the residual pass, and the context's stream waits for it, so the batch may be destroyed right after the call.  Reads the batch
    only: neither the picture nor the SCU map is touched. */
 int    xgpu_batch_residual(xgpu_ctx *ctx, xgpu_dbatch *db, const xgpu_resid_format *f, void *d_dst, size_t dst_size, void *stream);
+/* ---- comparing pictures (k_compare.hip): a picture of the context against another one - a slot, or 4:2:0 planes in device memory - in one pass over both:
+   per component the number of samples, the sum of squared differences, how many samples differ, the largest difference and where the first one is; an exact
+   integer SSIM; optionally the SSE of every 16x16 luma block (8x8 chroma block).  Everything is defined in integers - the SSIM in individually rounded
+   binary64 operations whose result is quantised and summed as an integer -, so the result does not depend on the device, the launch or the scheduling.
+     Samples     both pictures are read as unsigned 16-bit patterns as they lie in memory (U8: zero-extended); nothing is clipped or masked, and every integer
+                 below is exact for ANY 16-bit contents.  The coding depth B enters only through the SSIM constants.
+     Census      over the w x h plane of each component (the picture minus crop; chroma: half of it): n = w * h, sse = sum (a - r)^2, n_diff = samples with
+                 a != r, max_abs = max |a - r|, first_diff = (y << 32) | x of the first differing sample in raster order of the cropped plane, ~0: none.
+     SSIM        the 8x8-window, stride-4 integer form of x264 / ffmpeg: windows at (4i, 4j), i < (w >> 2) - 1, j < (h >> 2) - 1 (none for w < 8 or h < 8;
+                 trailing w % 4 columns and h % 4 rows lie in no window).  Per window, in integers: s1 = sum a, s2 = sum r, ss = sum (a^2 + r^2), s12 = sum a r,
+                 vars = 64 ss - s1^2 - s2^2, cov = 64 s12 - s1 s2; with L = 2^B - 1: c1 = (64 L^2 + 5000) / 10000, c2 = (9 * 64 * 63 L^2 + 5000) / 10000
+                 (integer division; B = 8: 416 and 235963).  In binary64, every operation rounded once, no fused multiply-add:
+                     num = double(2 s1 s2 + c1) * double(2 cov + c2),  den = double(s1^2 + s2^2 + c1) * double(vars + c2),
+                     q = (int64) floor(num / den * 2^30 + 0.5)
+                 (the four integers stay below 2^53: the conversions are exact).  ssim_q30 = sum of q over the windows, ssim_windows their number: identical
+                 pictures give exactly ssim_windows << 30.  ssim = 0: both fields are written as 0.
+     Block map   [3][ceil(h / 16)][ceil(w / 16)] uint64, tight: plane 0 the SSE of the 16x16 luma blocks of the cropped plane, planes 1 and 2 of the co-located
+                 8x8 Cb and Cr blocks, clipped at the plane's edge; every element is written, and those of plane c sum to sse[c].
+   Not offered: DRA (the slot's samples are compared as they are), a reference at another depth or chroma format, a reference in host memory.
+   The exact contract: INTEGRATION.md section 8h; tests/metrics_ref.py restates it in numpy. */
+#define XGPU_CMP_REF_PIC     0   /* another picture slot of the same context */
+#define XGPU_CMP_REF_YUV420  1   /* device memory in xgpu_pic_output's plane order: Y h rows of w, then Cb, Cr h/2 rows of w/2 */
+typedef struct xgpu_compare_ref {
+    int kind;            /* XGPU_CMP_REF_* */
+    int pic;             /* REF_PIC: the slot (may equal the picture compared) */
+    const void *d_yuv;   /* REF_YUV420: first luma sample of the UNCROPPED reference picture */
+    size_t size;         /* REF_YUV420: bytes available at d_yuv */
+    int dtype;           /* REF_YUV420: XGPU_OUT_U8 (only when the coding depth is 8) | XGPU_OUT_U16 */
+    size_t row_pitch;    /* REF_YUV420: LUMA pitch in bytes, 0 = tight, a multiple of 2 elements; chroma pitch = half of it;
+                            Cb at h * pitch, Cr at h * pitch + (h / 2) * (pitch / 2)  (xgpu_resid_format's YUV420 rule) */
+} xgpu_compare_ref;
+typedef struct xgpu_compare_params {
+    int crop[4];         /* left, right, top, bottom luma samples, even: applied to BOTH pictures */
+    int ssim;            /* 0 | 1 */
+    int block_map;       /* 0 | 1: also write the per-block SSE map */
+} xgpu_compare_params;
+typedef struct xgpu_compare_result {      /* written by the device; 160 bytes, every field at a multiple of its size */
+    uint64_t n[3];           /* samples compared, per component Y, Cb, Cr */
+    uint64_t sse[3];         /* sum of (a - r)^2 */
+    uint64_t n_diff[3];      /* samples with a != r */
+    uint64_t first_diff[3];  /* (y << 32) | x of the first differing sample in raster order of the cropped plane; ~0 if none */
+    uint32_t max_abs[3];     /* max |a - r| */
+    uint32_t reserved;       /* written as 0 */
+    uint64_t ssim_windows[3];
+    int64_t  ssim_q30[3];    /* sum over the windows of floor(ssim * 2^30 + 0.5) */
+} xgpu_compare_result;
+/* Host only, no context.  xgpu_compare_ref_size: the bytes a REF_YUV420 reference of width x height (the uncropped size, positive and even) spans from d_yuv,
+   the last row tight - h * pitch + (h - 1) * (pitch / 2) + (w / 2) * es; 0: an invalid reference (dtype, a pitch shorter than a row or not a multiple of 2
+   elements) or XGPU_CMP_REF_PIC, which has no memory to size.  xgpu_compare_map_size: 3 * ceil(h / 16) * ceil(w / 16) * 8 bytes for the cropped w x h; 0: invalid
+   parameters, or block_map == 0.  xgpu_compare_check: everything xgpu_pic_compare refuses without looking at a context or a pointer's memory - 0, or
+   XGPU_ERR_INVALID_ARGUMENT for a NULL, a size that is not positive and even, a depth outside 8..12, an unknown kind, a negative slot, a NULL d_yuv, U8 with
+   bit_depth != 8, a bad pitch, size < xgpu_compare_ref_size, an odd or negative crop or one that leaves nothing, ssim or block_map outside 0 | 1. */
+size_t xgpu_compare_ref_size(const xgpu_compare_ref *r, int width, int height);
+size_t xgpu_compare_map_size(const xgpu_compare_params *p, int width, int height);
+int    xgpu_compare_check(const xgpu_compare_ref *r, const xgpu_compare_params *p, int width, int height, int bit_depth);
+/* Non-blocking.  Compares slot `pic` with `ref` and writes *d_result and - with block_map - the map at d_map (map_size >= xgpu_compare_map_size bytes; else
+   d_map is not read).  d_result, d_map and a REF_YUV420 reference must be device memory of the context's device, large enough, d_result and d_map 8-byte
+   aligned, the reference aligned to its element (checked before anything is queued); a reference whose base and pitch are multiples of 16 bytes (U8: 8) is
+   read with vector loads.  Every field of the result and every map element is written by the call, on the same stream - the result by the
+   one workgroup that adds up the others' partial sums, a map element by the workgroup that owns its block: the caller clears nothing.  Both pictures are only read.  stream = NULL: the context's stream; else the kernels run on `stream` behind the
+   picture's kernels, and the context's stream waits for them.  A refused call - what xgpu_compare_check refuses, a slot that holds no picture, a frame that
+   is open (between xgpu_frame_begin and xgpu_frame_end), a pointer that fails the checks above - queues nothing, returns XGPU_ERR_INVALID_ARGUMENT and
+   leaves a message in xgpu_last_error. */
+int    xgpu_pic_compare(xgpu_ctx *ctx, int pic, const xgpu_compare_ref *ref, const xgpu_compare_params *p,
+                        xgpu_compare_result *d_result, uint64_t *d_map, size_t map_size, void *stream);
 /* The picture signature on the device: the MD5 of every plane over its rows of width x 2 bytes of 16-bit samples (8-bit pictures too), as xevd_md5_imgb makes it
    (src_base/xevd_util.c:985-1002) and xevd_picbuf_check_signature compares it with the SEI (:1557-1572) - of the DRA-mapped picture when `dra` is given, which is
    what the Main decoder signs when the PPS names a DRA parameter set (src_main/xevdm.c:3256-3287).  digest[plane] = the 16 bytes of the SEI payload.  Blocking; the

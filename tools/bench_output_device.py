@@ -28,7 +28,15 @@ planes, as 4:4:4 planar int16 and float16, and as the per-unit energy.  Bytes ar
 component block), 4 per 4x4 unit of owner map, 32 per CU record, and what the form writes.  The whole measurement - copy rate included - is repeated --repeat
 times in the one process; every run is kept.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|residual] [--out out/output_device.json]
+The compare leg (xgpu_pic_compare: k_compare_init + k_compare) compares the picture with a second slot of other random samples - every sample differs, the most
+the census has to do - as the census alone, with the SSIM, with the block map and with both, with the SSIM against the same planes as a tensor (the 16-byte
+loads and, one element into its allocation, the element loads), and with both against the picture itself.  `us` is the device time of the call (median of --iters
+launches queued behind a wait, as the full-size forms are timed); `alternated_us` the same call from an idle device, as the torch route is timed.  Next to each: (a) the time the measured copy rate
+needs for the bytes the call must read, the two pictures once; (b) what a caller does without it, alternated with the call in the same run on the same stream:
+two yuv420p tensors from xgpu_pic_output_device and per plane the SSE, the number of differing samples and the largest difference in torch (int32 temporaries;
+no SSIM: torch cannot make it exactly).  The split between the two kernels is what rocprofv3 --kernel-trace --stats shows for `--legs compare`.
+
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|residual|compare] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -254,6 +262,86 @@ def residual_leg(torch, dec, pic, s, a, res):
     dec.batch_destroy(hb)
 
 
+def torch_census(torch, a, b, w, h):
+    """per plane the SSE, the differing samples and the largest difference of two flat yuv420p int16 tensors: what a caller computes without xgpu_pic_compare"""
+    out = []
+    o = 0
+    for n in (w * h, w * h // 4, w * h // 4):
+        d = a[o:o + n].to(torch.int32) - b[o:o + n].to(torch.int32)
+        out += [(d * d).sum(), (d != 0).sum(), d.abs().max()]
+        o += n
+    return torch.stack(out)
+
+
+def compare_leg(torch, dec, pic, s, a, res, copy_gbps):
+    """xgpu_pic_compare against the copy-rate time of the two pictures and against the torch route, alternated"""
+    w, h, bd = a.width, a.height, a.bit_depth
+    rng = np.random.default_rng(3)
+    other = dec.pic_alloc()
+    dec.pic_upload(other, [rng.integers(0, 1 << bd, (h >> k, w >> k)).astype(np.int16) for k in (0, 1, 1)])
+    flat = dec.pic_output_tensor(other, layout="yuv420p", dtype=torch.int16)
+    shifted = torch.empty(flat.numel() + 8, dtype=torch.int16, device="cuda:0")[1:1 + flat.numel()]
+    shifted.copy_(flat)
+    nbytes = 2 * 3 * w * h
+    floor_us = nbytes / (copy_gbps * 1e9) * 1e6
+    out = torch.empty(20, dtype=torch.int64, device="cuda:0")
+    forms = [("census", other, dict(ssim=False)), ("census_ssim", other, dict(ssim=True)), ("census_map", other, dict(ssim=False, block_map=True)),
+             ("census_ssim_map", other, dict(ssim=True, block_map=True)), ("census_ssim_tensor_ref", flat, dict(ssim=True)),
+             ("census_ssim_tensor_ref_unaligned", shifted, dict(ssim=True)), ("census_ssim_map_identical", pic, dict(ssim=True, block_map=True))]
+    ya, yb = dec.pic_output_tensor(pic, layout="yuv420p", dtype=torch.int16), torch.empty_like(flat)
+
+    def route():
+        dec.pic_output_tensor(pic, layout="yuv420p", dtype=torch.int16, out=ya)
+        dec.pic_output_tensor(other, layout="yuv420p", dtype=torch.int16, out=yb)
+        return torch_census(torch, ya, yb, w, h)
+
+    def census_only():
+        return torch_census(torch, ya, yb, w, h)
+
+    res["compare"] = {"bytes": nbytes, "copy_rate_us": round(floor_us, 2), "forms": {}}
+    for name, ref, kw in forms:
+        def call():
+            dec.pic_compare(pic, ref, out=out, sync=False, **kw)
+        for _ in range(5):
+            call(); route()
+        torch.cuda.synchronize()
+        n = max(a.iters // 2, 5)
+        ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)] for k in ("call", "torch_route", "torch_census_only")}
+        for i in range(n):
+            for k, fn in (("call", call), ("torch_route", route), ("torch_census_only", census_only)):
+                if k != "call" and name != "census":
+                    continue      # the torch route does not depend on the form: timed once, next to the census
+                e0, e1 = ev[k][i]
+                torch.cuda.synchronize()      # each starts on an idle device
+                e0.record(s)
+                fn()
+                e1.record(s)
+        torch.cuda.synchronize()
+        alt = np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev["call"]])      # from an idle device: the launch latency is inside
+        r = {"us": round(timed(torch, s, call, a.iters), 2), "alternated_us": round(float(np.median(alt)), 2), "alternated_p10_us": round(float(np.percentile(alt, 10)), 2),
+             "alternated_p90_us": round(float(np.percentile(alt, 90)), 2)}
+        r["gbps"] = round(nbytes / (r["us"] * 1e-6) / 1e9, 1)
+        r["frac_copy"] = round(floor_us / r["us"], 3)
+        if name == "census":
+            for k in ("torch_route", "torch_census_only"):
+                t = np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev[k]])
+                res["compare"][k + "_us"] = round(float(np.median(t)), 2)
+            d = abi_dict(out)
+            want = route().cpu().numpy().reshape(3, 3)
+            res["compare"]["torch_route_agrees"] = bool([d["sse"], d["n_diff"], d["max_abs"]] == want.T.tolist())
+        r["torch_route_over_call"] = round(res["compare"]["torch_route_us"] / r["alternated_us"], 2)      # both from an idle device
+        r["torch_census_only_over_call"] = round(res["compare"]["torch_census_only_us"] / r["alternated_us"], 2)
+        print(f"compare {name:34s} {r['us']:9.1f} us  {r['gbps']:7.1f} GB/s  copy-rate time {floor_us:7.1f} us ({r['frac_copy']:.2f})   torch route {res['compare']['torch_route_us']:9.1f} us "
+              f"({r['torch_route_over_call']:.1f}x; its reductions alone {res['compare']['torch_census_only_us']:9.1f} us, {r['torch_census_only_over_call']:.1f}x)")
+        res["compare"]["forms"][name] = r
+    dec.pic_free(other)
+
+
+def abi_dict(t):
+    from xevd_amd import abi
+    return abi.compare_result_dict(t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=7680)
@@ -262,9 +350,9 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "residual"), default="all",
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "residual", "compare"), default="all",
                     help="full: the full-size forms and the side information; scaled: the scaled leg alone; rois: the batched regions of interest alone; "
-                         "rois_dev: the regions of interest from boxes in device memory alone; residual: the residual export alone")
+                         "rois_dev: the regions of interest from boxes in device memory alone; residual: the residual export alone; compare: the picture comparison alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -306,6 +394,8 @@ def main():
             rois_dev_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "residual"):
             residual_leg(torch, dec, pic, s, a, res)
+        if a.legs in ("all", "compare"):
+            compare_leg(torch, dec, pic, s, a, res, copy_gbps)
         if a.legs in ("all", "full"):
             for name, kw, wbytes in forms:
                 out = dec.pic_output_tensor(pic, **kw)

@@ -12,6 +12,95 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from xevd_amd.player import StreamDecoder      # noqa: E402
 
 
+class RefCompare:
+    """compare= of StreamDecoder for --ref: called per picture in decoding order, returns the picture's frame of the file as a tensor on the device.  The frame of
+    the picture expected next is read into pinned memory and copied on a stream of its own while the current picture decodes.  The line of a picture is
+    printed - and --expect-identical acted on - when the next picture arrives, or at the end: the result is under params["compare"] only then."""
+
+    def __init__(self, path, order, expect_identical, device):
+        self.path, self.order, self.expect_identical, self.device = path, order, expect_identical, device
+        self.n = self.epoch_start = 0
+        self.last = None           # the picture whose result has not been reported yet
+        self.ahead = None          # (frame index, tensor, event)
+        self.pinned, self.used = [None, None], [None, None]
+        self.seen = set()
+        self.n_cmp = self.n_bad = 0
+        self.sse, self.cnt, self.q, self.win = [0] * 3, [0] * 3, 0, 0
+        self.bit_depth = 8
+
+    def _upload(self, idx, nbytes, dtype):
+        import numpy as np
+        import torch
+        k = idx & 1
+        if self.used[k] is not None:
+            self.used[k].synchronize()      # the copy out of this pinned buffer is done
+        if self.pinned[k] is None or self.pinned[k].numel() * self.pinned[k].element_size() != nbytes or self.pinned[k].dtype != dtype:
+            self.pinned[k] = torch.empty(nbytes // dtype.itemsize, dtype=dtype).pin_memory()
+        raw = np.fromfile(self.path, dtype=np.uint8, count=nbytes, offset=idx * nbytes)
+        if raw.size != nbytes:
+            return None
+        self.pinned[k].view(torch.uint8).numpy()[:] = raw
+        if getattr(self, "_copy", None) is None:
+            self._copy = torch.cuda.Stream(device=self.device)
+        with torch.cuda.stream(self._copy):
+            t = self.pinned[k].to(torch.device("cuda", self.device), non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self.used[k] = ev
+        return idx, t, ev
+
+    def __call__(self, p):
+        import torch
+        self.report()
+        if p["is_idr"]:
+            self.epoch_start = self.n
+        idx = self.n if self.order == "decoding" else self.epoch_start + p["poc"]
+        self.n += 1
+        self.bit_depth = p["bit_depth"]
+        dtype = torch.uint8 if p["bit_depth"] == 8 else torch.int16
+        nbytes = p["width"] * p["height"] * 3 // 2 * dtype.itemsize
+        if idx < 0 or idx in self.seen:
+            sys.exit(f"--ref-order output: POC {p['poc']} does not count up from its IDR picture; use --ref-order decoding with a file in that order")
+        self.seen.add(idx)
+        got = self.ahead if self.ahead is not None and self.ahead[0] == idx else self._upload(idx, nbytes, dtype)
+        if got is None:
+            sys.exit(f"{self.path}: no frame {idx} of {nbytes} bytes (POC {p['poc']})")
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(got[2])
+        got[1].record_stream(cur)
+        self.ahead = self._upload(idx + 1, nbytes, dtype)      # the next picture's, in either order, more often than not
+        self.last = (p, idx)
+        return got[1]
+
+    def report(self):
+        if self.last is None:
+            return
+        (p, idx), self.last = self.last, None
+        d = p["compare"]
+        first = next((f"{'YUV'[c]}({f[1]},{f[0]})" for c, f in enumerate(d["first_diff"]) if f is not None), "-")
+        nd = sum(d["n_diff"])
+        print(f"POC {p['poc']:4d} frame {idx:4d}  PSNR-Y {d['psnr'][0]:.4f} U {d['psnr'][1]:.4f} V {d['psnr'][2]:.4f}  SSIM-Y {d['ssim'][0]:.6f}  n_diff {nd}  first {first}")
+        self.n_cmp += 1
+        self.n_bad += nd != 0
+        for c in range(3):
+            self.sse[c] += d["sse"][c]
+            self.cnt[c] += d["n"][c]
+        self.q += d["ssim_q30"][0]
+        self.win += d["ssim_windows"][0]
+        if nd and self.expect_identical:
+            sys.stdout.flush()
+            print(f"POC {p['poc']}: {nd} samples differ from frame {idx} of {self.path}, the first at {first}", file=sys.stderr)
+            sys.exit(1)
+
+    def finish(self):
+        from xevd_amd import abi
+        self.report()
+        ps = abi.psnr({"n": self.cnt, "sse": self.sse}, self.bit_depth)
+        ss = self.q / (self.win * float(1 << 30)) if self.win else float("nan")
+        print(f"{self.n_cmp} pictures compared, {self.n_bad} differ  PSNR-Y {ps[0]:.4f} U {ps[1]:.4f} V {ps[2]:.4f}  SSIM-Y {ss:.6f}")
+        sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-i", "--input", required=True)
@@ -29,8 +118,17 @@ def main():
                     "the matrix / range / chroma siting of the stream's VUI: INTEGRATION.md 8d); with --to: not supported")
     ap.add_argument("--tiles", default=None, metavar="WxH", help="with --size: every picture as its grid of W x H tiles (the last column / row moved back inside the "
                     "picture), each resized to --size by one call per picture (INTEGRATION.md 8e); the frames written are the tiles, row by row")
+    ap.add_argument("--ref", default=None, metavar="FILE.yuv", help="compare every decoded picture with this planar 4:2:0 file on the device (INTEGRATION.md 8h): frames "
+                    "of the uncropped picture at the stream's depth (8 bit: bytes, else 16-bit little endian), as -o writes them; prints PSNR, SSIM, the number "
+                    "of differing samples and the first differing position per picture, and a summary")
+    ap.add_argument("--ref-order", choices=("output", "decoding"), default="output", help="the order of the frames in --ref: output order (what -o and the reference "
+                    "application write; needs POCs that count 0, 1, 2, ... from every IDR picture) or decoding order")
+    ap.add_argument("--expect-identical", action="store_true", help="with --ref: exit with status 1 at the first picture that differs from its frame")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
+    if args.expect_identical and args.ref is None:
+        ap.error("--expect-identical: needs --ref")
+    cmp = RefCompare(args.ref, args.ref_order, args.expect_identical, args.device) if args.ref else None
     if args.tiles is not None and args.size is None:
         ap.error("--tiles: needs --size")
     data = open(args.input, "rb").read()
@@ -54,17 +152,19 @@ def main():
             except ValueError:
                 ap.error(f"--tiles: expected WxH, not {args.tiles!r}")
             rois = lambda p: abi.tile_rois(p["width"], p["height"], tw, th)      # noqa: E731
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois, residual=resid)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois, residual=resid, compare=cmp)
     elif args.to is not None:
         import torch
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp)
     elif args.pix_fmt == "yuv420p":
-        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side, residual=resid)
+        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side, residual=resid, compare=cmp)
     else:      # the same pictures as semi-planar surfaces (xgpu_pic_output_device into a torch tensor, copied to the host picture by picture)
         import torch
         opts = dict(layout="nv12", dtype=torch.uint8) if args.pix_fmt == "nv12" else dict(layout="p016", dtype=torch.int16, out_bit_depth=10)
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid, compare=cmp)
     dt = time.perf_counter() - t0
+    if cmp is not None:
+        cmp.finish()
     if args.output:
         with open(args.output, "wb") as f:
             for _, frame in pics:

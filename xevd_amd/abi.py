@@ -93,6 +93,63 @@ def make_resid_format(layout=RESID_YUV420, dtype=OUT_U16, crop=(0, 0, 0, 0), row
     return f
 
 
+CMP_REF_PIC, CMP_REF_YUV420 = 0, 1
+
+
+class CompareRef(C.Structure):
+    _fields_ = [("kind", C.c_int), ("pic", C.c_int), ("d_yuv", C.c_void_p), ("size", C.c_size_t), ("dtype", C.c_int), ("row_pitch", C.c_size_t)]
+
+
+class CompareParams(C.Structure):
+    _fields_ = [("crop", C.c_int * 4), ("ssim", C.c_int), ("block_map", C.c_int)]
+
+
+class CompareResult(C.Structure):
+    """xgpu_compare_result: 160 bytes, written by the device"""
+    _fields_ = [("n", C.c_uint64 * 3), ("sse", C.c_uint64 * 3), ("n_diff", C.c_uint64 * 3), ("first_diff", C.c_uint64 * 3), ("max_abs", C.c_uint32 * 3),
+                ("reserved", C.c_uint32), ("ssim_windows", C.c_uint64 * 3), ("ssim_q30", C.c_int64 * 3)]
+
+
+def make_compare_ref(pic=None, d_yuv=None, size=0, dtype=OUT_U16, row_pitch=0):
+    """xgpu_compare_ref (include/xevd_hip.h): a slot (pic=), or 4:2:0 planes in device memory (d_yuv= the address, size= the bytes there, dtype OUT_U8 / OUT_U16,
+    row_pitch= the luma pitch in bytes, 0 = tight)"""
+    r = CompareRef()
+    if pic is not None:
+        r.kind, r.pic = CMP_REF_PIC, int(pic)
+    else:
+        r.kind, r.d_yuv, r.size, r.dtype, r.row_pitch = CMP_REF_YUV420, d_yuv, int(size), int(dtype), int(row_pitch)
+    return r
+
+
+def make_compare_params(crop=(0, 0, 0, 0), ssim=True, block_map=False):
+    p = CompareParams()
+    for i in range(4):
+        p.crop[i] = int(crop[i])
+    p.ssim, p.block_map = int(ssim), int(block_map)
+    return p
+
+
+def compare_result_dict(res):
+    """a CompareResult, or its 160 bytes as anything numpy reads -> dict of lists of Python ints, one entry per component Y, Cb, Cr"""
+    if not isinstance(res, CompareResult):
+        res = CompareResult.from_buffer_copy(np.ascontiguousarray(res).tobytes())
+    return {k: [int(v) for v in getattr(res, k)] for k in ("n", "sse", "n_diff", "first_diff", "max_abs", "ssim_windows", "ssim_q30")}
+
+
+def psnr(result, bit_depth):
+    """host only: [Y, Cb, Cr] 10 log10(L^2 n / sse) with L = 2^bit_depth - 1 of a compare result (CompareResult or compare_result_dict's dict); inf for sse == 0"""
+    import math
+    d = result if isinstance(result, dict) else compare_result_dict(result)
+    peak = ((1 << int(bit_depth)) - 1) ** 2
+    return [math.inf if s == 0 else 10.0 * math.log10(peak * n / s) for n, s in zip(d["n"], d["sse"])]
+
+
+def ssim(result):
+    """host only: [Y, Cb, Cr] ssim_q30 / (ssim_windows 2^30) of a compare result; nan for a plane without windows (or a call with ssim off)"""
+    d = result if isinstance(result, dict) else compare_result_dict(result)
+    return [q / (n * float(1 << 30)) if n else float("nan") for q, n in zip(d["ssim_q30"], d["ssim_windows"])]
+
+
 SCALE_BILINEAR, SCALE_AREA = 0, 1
 
 
@@ -443,6 +500,10 @@ _EXPORTS = {
     "xgpu_frame_side_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SideFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_resid_size": (C.c_size_t, [C.POINTER(ResidFormat), C.c_int, C.c_int]),
     "xgpu_batch_residual": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ResidFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_compare_ref_size": (C.c_size_t, [C.POINTER(CompareRef), C.c_int, C.c_int]),
+    "xgpu_compare_map_size": (C.c_size_t, [C.POINTER(CompareParams), C.c_int, C.c_int]),
+    "xgpu_compare_check": (C.c_int, [C.POINTER(CompareRef), C.POINTER(CompareParams), C.c_int, C.c_int, C.c_int]),
+    "xgpu_pic_compare": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(CompareRef), C.POINTER(CompareParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "xgpu_host_free": (None, [C.c_void_p, C.c_void_p]),
     "xgpu_batch_wait_upload": (C.c_int, [C.c_void_p, C.c_void_p]),

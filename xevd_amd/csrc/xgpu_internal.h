@@ -364,6 +364,8 @@ struct xgpu_ctx {
     ScaleTabs       sc_host;          // what sc_tab holds: offsets, strides, pass 2's spans
     uint16_t       *sc_mid;
     size_t          sc_mid_cap;
+    unsigned long long *cmp_part;     // xgpu_pic_compare: the workgroups' partial sums of the current call (cmp_part_cap bytes, grown on demand), ordered like sc_mid
+    size_t          cmp_part_cap;
     uint8_t        *roi_blk;          // xgpu_pic_output_device_rois: the descriptors and tap tables of the current call (its intermediate is sc_mid), ordered like sc_tab
     size_t          roi_blk_cap;
     hipEvent_t      odev_ev[2];       // xgpu_pic_output_device on a caller's stream: picture ready on the context stream / the caller's kernel done (created at the first call)
@@ -584,6 +586,27 @@ struct ResidArgs {
     int      n_chroma_cus;
 };
 void launch_residual(const ResidArgs &a, int layout, int dtype, hipStream_t s);
+// k_compare.hip: a picture against a reference in one pass (xgpu_pic_compare)
+struct CompareArgs {
+    const uint16_t *a[3];           // the picture: first sample of the cropped area of every plane
+    int      sa[3];                 // its strides in samples
+    const uint8_t *r[3];            // the reference: the same, as bytes
+    size_t   pr[3];                 // bytes between its rows
+    int      r8;                    // reference elements are bytes (zero-extended), else 16-bit
+    int      vec_a[3], vec_r[3];    // the plane's cropped base and pitch allow the vector loads (16 bytes; a byte reference: 8)
+    int      w[3], h[3];            // cropped size of every plane
+    int      tiles_x[3];            // 64x32 tiles per row of tiles
+    int      tile_first[4];         // tiles of plane c: tile_first[c] .. tile_first[c + 1]
+    int      ssim, block_map;
+    long long c1, c2;               // the SSIM constants at the coding depth
+    unsigned long long *part;       // [workgroups][3][CMP_PART_WORDS]: every workgroup's sums per component, reduced into res by k_compare_finish
+    xgpu_compare_result *res;
+    uint64_t *map;                  // [3][mh][mw]
+    int      mw, mh;
+};
+#define CMP_PART_WORDS 8            // n, sse, n_diff, first_diff, windows, q, max_abs, (unused)
+int  compare_workgroups(int tiles);                 // the workgroups launch_compare starts for that many tiles
+void launch_compare(const CompareArgs &a, hipStream_t s);
 void launch_md5(xgpu_ctx *c, hipStream_t s, const uint8_t *d_msg, int w, int h, uint32_t *d_digest);      // k_md5.hip: the three planes packed back to back at d_msg -> d_digest[3][4]
 void launch_test_mc(xgpu_ctx *c, const int16_t *plane, int stride, int ref_x, int ref_y, int has_dx, int has_dy,
                     int gmv_x, int gmv_y, int16_t *pred, int w, int h, int bd, int luma);

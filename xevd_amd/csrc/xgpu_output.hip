@@ -1,7 +1,8 @@
 // xgpu_output.hip - the C ABI of include/xevd_hip.h, part 2: the outputs into device memory - the picture as it is, colour-managed, scaled, as a batch of regions of
-// interest (rectangles from the host or boxes in device memory), the coding side information and the residual - and their argument checks without a device.
+// interest (rectangles from the host or boxes in device memory), the coding side information, the residual and the comparison with a reference - and their
+// argument checks without a device.
 // Every entry point is the same skeleton: check the format -> check_dst -> (check_dra; tables, made on the host) -> grow a context buffer -> out_fork -> fill an args struct ->
-// launch -> out_join.  Host-side code only; the kernels live in k_output*.hip, k_side_info.hip and k_residual.hip.
+// launch -> out_join.  Host-side code only; the kernels live in k_output*.hip, k_side_info.hip, k_residual.hip and k_compare.hip.
 #include "xgpu_host.h"
 #include "scale_taps.h"
 #include <memory>
@@ -104,7 +105,7 @@ static bool crop_ok(const int crop[4], int width, int height, const char **why)
     *why = "crop offsets must be even and >= 0";
     for (int i = 0; i < 4; i++) if (crop[i] < 0 || (crop[i] & 1)) return false;
     *why = "crop leaves no picture";
-    return width <= 0 || (crop[0] + crop[1] < width && crop[2] + crop[3] < height);
+    return width <= 0 || ((long long)crop[0] + crop[1] < width && (long long)crop[2] + crop[3] < height);
 }
 // first sample of the cropped area of every plane
 static void cropped_planes(const DevPic &p, const int crop[4], const int16_t **y, const int16_t **u, const int16_t **v)
@@ -961,4 +962,143 @@ int xgpu_batch_residual(xgpu_ctx *c, xgpu_dbatch *db, const xgpu_resid_format *f
     }
     launch_residual(a, f->layout, f->dtype, s);
     return out_join(c, stream, s);      // the arena, before xgpu_batch_destroy's blk.done lets the block be refilled
+}
+
+// ------------------------------------------------------------------------------------------------ a picture against a reference
+// the reference alone for a picture of width x height: the bytes it spans from d_yuv (the luma pitch in *pitch), or 0 with `why`
+static size_t compare_ref_size(const xgpu_compare_ref *r, int width, int height, size_t *pitch, const char **why)
+{
+    *why = "reference is NULL";
+    if (!r) return 0;
+    *why = "picture size must be positive and even";
+    if (width <= 0 || height <= 0 || ((width | height) & 1)) return 0;
+    *why = "reference: kind must be XGPU_CMP_REF_PIC or XGPU_CMP_REF_YUV420";
+    if (r->kind != XGPU_CMP_REF_YUV420) return 0;      // (a slot has no memory to size)
+    *why = "reference: dtype must be XGPU_OUT_U8 or XGPU_OUT_U16";
+    if (r->dtype != XGPU_OUT_U8 && r->dtype != XGPU_OUT_U16) return 0;
+    const size_t es = (size_t)elem_size(r->dtype), w = width, h = height;
+    *why = "reference: row_pitch must be a multiple of 2 elements and at least a row";
+    if (r->row_pitch % (2 * es)) return 0;
+    const Rows y = rows_of(w * es, h, r->row_pitch);
+    if (!y.total) return 0;
+    if (pitch) *pitch = y.pitch;
+    return h * y.pitch + rows_of((w >> 1) * es, h, y.pitch / 2).total;      // Y: h rows of the pitch; Cb, Cr: h / 2 rows of half the pitch each, the last one tight
+}
+size_t xgpu_compare_ref_size(const xgpu_compare_ref *r, int width, int height)
+{
+    const char *why;
+    return compare_ref_size(r, width, height, NULL, &why);
+}
+static bool compare_params_ok(const xgpu_compare_params *p, int width, int height, const char **why)
+{
+    *why = "parameters are NULL";
+    if (!p) return false;
+    *why = "picture size must be positive and even";
+    if (width <= 0 || height <= 0 || ((width | height) & 1)) return false;
+    if (!crop_ok(p->crop, width, height, why)) return false;
+    *why = "ssim and block_map: 0 or 1";
+    return !((p->ssim | p->block_map) & ~1);
+}
+size_t xgpu_compare_map_size(const xgpu_compare_params *p, int width, int height)
+{
+    const char *why;
+    if (!compare_params_ok(p, width, height, &why) || !p->block_map) return 0;
+    const size_t w = width - p->crop[0] - p->crop[1], h = height - p->crop[2] - p->crop[3];
+    return 3 * ((h + 15) / 16) * ((w + 15) / 16) * sizeof(uint64_t);
+}
+static int compare_check(const xgpu_compare_ref *r, const xgpu_compare_params *p, int width, int height, int bd, const char **why)
+{
+    if (!compare_params_ok(p, width, height, why)) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "bit depth out of range";
+    if (bd < 8 || bd > 12) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "reference is NULL";
+    if (!r) return XGPU_ERR_INVALID_ARGUMENT;
+    if (r->kind == XGPU_CMP_REF_PIC) {
+        *why = "reference: the slot is negative";
+        return r->pic < 0 ? XGPU_ERR_INVALID_ARGUMENT : XGPU_OK;
+    }
+    const size_t need = compare_ref_size(r, width, height, NULL, why);
+    if (!need) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "reference: XGPU_OUT_U8 needs a coding depth of 8";
+    if (r->dtype == XGPU_OUT_U8 && bd != 8) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "reference: d_yuv is NULL or size is below xgpu_compare_ref_size";
+    if (!r->d_yuv || r->size < need) return XGPU_ERR_INVALID_ARGUMENT;
+    return XGPU_OK;
+}
+int xgpu_compare_check(const xgpu_compare_ref *r, const xgpu_compare_params *p, int width, int height, int bit_depth)
+{
+    const char *why;
+    return compare_check(r, p, width, height, bit_depth, &why);
+}
+// Checks first, then the order of output_device: on a caller's stream the kernels run behind the picture's kernels - and behind every earlier output call -,
+// and the context's stream waits for them before the next picture may write either slot.
+int xgpu_pic_compare(xgpu_ctx *c, int pic, const xgpu_compare_ref *ref, const xgpu_compare_params *p, xgpu_compare_result *d_result, uint64_t *d_map,
+                     size_t map_size, void *stream)
+{
+    static const char who[] = "pic_compare";
+    ARGCHK(c, c != NULL); ARGCHK(c, d_result != NULL);
+    const char *why = "";
+    const int bd = c->sp.bit_depth_luma;
+    if (compare_check(ref, p, c->sp.width, c->sp.height, bd, &why) < 0) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return XGPU_ERR_INVALID_ARGUMENT; }
+    const bool slot = ref->kind == XGPU_CMP_REF_PIC;
+    if (c->have_frame || !valid_pic(c, pic) || (slot && !valid_pic(c, ref->pic))) {
+        snprintf(c->err, sizeof(c->err), "%s: %s", who, c->have_frame ? "a frame is open: compare after xgpu_frame_end" : !valid_pic(c, pic) ? "the slot holds no picture"
+                                                                                                                                  : "the reference slot holds no picture");
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    const size_t es = slot ? 2 : (size_t)elem_size(ref->dtype);
+    size_t pitch = 0;
+    if (!slot) {
+        const size_t need = compare_ref_size(ref, c->sp.width, c->sp.height, &pitch, &why);
+        TRY(check_dst(c, "pic_compare: reference", (void *)ref->d_yuv, ref->size, need, es));
+    }
+    TRY(check_dst(c, "pic_compare: result", d_result, sizeof(xgpu_compare_result), sizeof(xgpu_compare_result), 8));
+    const size_t map_need = xgpu_compare_map_size(p, c->sp.width, c->sp.height);
+    if (p->block_map) {
+        ARGCHK(c, d_map != NULL);
+        TRY(check_dst(c, "pic_compare: map", d_map, map_size, map_need, 8));
+    }
+    const int *cr = p->crop;
+    const int w = c->sp.width - cr[0] - cr[1], h = c->sp.height - cr[2] - cr[3];
+    const int all_tiles = ((w + 63) / 64) * ((h + 31) / 32) + 2 * (((w >> 1) + 63) / 64) * (((h >> 1) + 31) / 32);
+    TRY(grow(c, who, &c->cmp_part, &c->cmp_part_cap, (size_t)compare_workgroups(all_tiles) * 3 * CMP_PART_WORDS * sizeof(unsigned long long), "block of partial sums"));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    CompareArgs a;
+    memset(&a, 0, sizeof(a));
+    const int16_t *pl[3];
+    const DevPic &dp = dpic(c, pic);
+    cropped_planes(dp, cr, &pl[0], &pl[1], &pl[2]);
+    if (slot) {
+        const DevPic &rp = dpic(c, ref->pic);
+        const int16_t *rl[3];
+        cropped_planes(rp, cr, &rl[0], &rl[1], &rl[2]);
+        for (int k = 0; k < 3; k++) { a.r[k] = (const uint8_t *)rl[k]; a.pr[k] = (size_t)(k ? rp.s_c : rp.s_l) * 2; }
+    } else {
+        const uint8_t *base = (const uint8_t *)ref->d_yuv;
+        const size_t hh = c->sp.height, pc = pitch / 2;
+        const size_t off_c = (size_t)(cr[2] >> 1) * pc + (size_t)(cr[0] >> 1) * es;
+        a.r[0] = base + (size_t)cr[2] * pitch + (size_t)cr[0] * es;
+        a.r[1] = base + hh * pitch + off_c;
+        a.r[2] = base + hh * pitch + (hh / 2) * pc + off_c;
+        a.pr[0] = pitch; a.pr[1] = a.pr[2] = pc;
+        a.r8 = es == 1;
+    }
+    int tiles = 0;
+    for (int k = 0; k < 3; k++) {
+        a.a[k] = (const uint16_t *)pl[k]; a.sa[k] = k ? dp.s_c : dp.s_l;
+        a.w[k] = k ? w >> 1 : w; a.h[k] = k ? h >> 1 : h;
+        a.vec_a[k] = aligned16((uintptr_t)a.a[k] | ((size_t)a.sa[k] * 2));
+        a.vec_r[k] = (((uintptr_t)a.r[k] | a.pr[k]) & (a.r8 ? 7 : 15)) == 0;
+        a.tiles_x[k] = (a.w[k] + 63) / 64;
+        a.tile_first[k] = tiles;
+        tiles += a.tiles_x[k] * ((a.h[k] + 31) / 32);
+    }
+    a.tile_first[3] = tiles;
+    a.ssim = p->ssim; a.block_map = p->block_map;
+    const long long L = (1 << bd) - 1;
+    a.c1 = (64 * L * L + 5000) / 10000; a.c2 = (9 * 64 * 63 * L * L + 5000) / 10000;
+    a.part = c->cmp_part; a.res = d_result; a.map = d_map; a.mw = (w + 15) / 16; a.mh = (h + 15) / 16;
+    launch_compare(a, s);
+    return out_join(c, stream, s);      // both slots, before the next picture's kernels may write them; the partial sums, before the next call's
 }

@@ -497,6 +497,50 @@ class XgpuDecoder:
             return out, (out[:ny].view(h_, w_), out[ny:ny + nc].view(h_ // 2, w_ // 2), out[ny + nc:].view(h_ // 2, w_ // 2))
         return out
 
+    def pic_compare(self, pic, ref, crop=(0, 0, 0, 0), ssim=True, block_map=False, out=None, sync=True):
+        """Slot `pic` against a reference, compared on the device in one pass over both on torch's current stream (xgpu_pic_compare, INTEGRATION.md section
+        8h): per component Y, Cb, Cr the samples compared, the sum of squared differences, how many samples differ, the largest difference and the first
+        differing position, and - ssim=True - the exact 8x8-window integer SSIM.
+        ref: a slot number (it may be `pic`), or the picture as a tensor on the decoder's device in pic_output's plane order - the flat tensor
+        pic_output_tensor(layout="yuv420p") returns for the uncropped picture, or any 1-D or [height * 3 // 2, pitch] tensor (rows of `pitch` elements for luma,
+        of pitch / 2 for the chroma planes behind it) of torch.uint8 (8-bit streams) or a 16-bit integer type.  crop (left, right, top, bottom), even, is
+        applied to both pictures.  block_map=True: also the SSE of every 16x16 luma block and of the co-located 8x8 chroma blocks, an int64 tensor
+        [3, ceil(H / 16), ceil(W / 16)].
+        sync=True: a dict - n, sse, n_diff, first_diff ((y, x) or None), max_abs, ssim_windows, ssim_q30 as lists of three Python ints, psnr and ssim as lists
+        of three floats (abi.psnr / abi.ssim), map: the tensor or None.  sync=False: nothing is read back - the raw result, an int64 tensor of 20 words laid
+        out as xgpu_compare_result (abi.compare_result_dict reads it), or with block_map the pair (result, map).  out: a tensor to take the raw result."""
+        import torch
+        dev = torch.device("cuda", self.sp.device)
+        if isinstance(ref, torch.Tensor):
+            codes = _codes("uint8", "int16", "uint16")
+            if ref.dtype not in codes or ref.device != dev:
+                raise ValueError(f"ref: a torch.uint8 or 16-bit integer tensor on {dev}, not {ref.dtype} on {ref.device}")
+            es = ref.element_size()
+            if ref.dim() == 1 and ref.stride() == (1,):
+                pitch, span = 0, ref.numel() * es
+            elif ref.dim() == 2 and ref.shape[0] == self.height * 3 // 2 and ref.stride(1) == 1:
+                pitch, span = ref.stride(0) * es, ((ref.shape[0] - 1) * ref.stride(0) + ref.shape[1]) * es
+            else:
+                raise ValueError(f"ref: a contiguous 1-D tensor or [{self.height * 3 // 2}, pitch] rows, not {tuple(ref.shape)} with strides {ref.stride()}")
+            r = abi.make_compare_ref(d_yuv=ref.data_ptr(), size=span, dtype=codes[ref.dtype], row_pitch=pitch)
+        else:
+            r = abi.make_compare_ref(pic=int(ref))
+        p = abi.make_compare_params(crop, ssim, block_map)
+        res = _out_tensor(out, (C.sizeof(abi.CompareResult) // 8,), torch.int64, dev)
+        if res.stride() != (1,):
+            raise ValueError("out: must be contiguous")
+        cl, cr, ct, cb = (int(v) for v in crop)
+        mshape = (3, max(-(-(self.height - ct - cb) // 16), 0), max(-(-(self.width - cl - cr) // 16), 0)) if block_map else (0,)
+        bmap = torch.empty(mshape, dtype=torch.int64, device=dev)      # (no map: no memory, the call gets NULL and 0 bytes)
+        self._device_call("xgpu_pic_compare", bmap, pic, C.byref(r), C.byref(p), C.c_void_p(res.data_ptr()))
+        if not sync:
+            return (res, bmap) if block_map else res
+        d = abi.compare_result_dict(res.cpu().numpy())
+        d["psnr"], d["ssim"] = abi.psnr(d, self.bit_depth), abi.ssim(d)
+        d["first_diff"] = [None if f == (1 << 64) - 1 else (f >> 32, f & 0xFFFFFFFF) for f in d["first_diff"]]
+        d["map"] = bmap if block_map else None
+        return d
+
     def pic_md5(self, pic, dra=None):
         """the picture signature made on the device (xgpu_pic_md5): [Y, U, V] digests of 16 bytes - the MD5 of every plane's 16-bit samples as the reference's
         xevd_md5_imgb makes it; with `dra` tables (as pic_output takes them) of the DRA-mapped picture"""

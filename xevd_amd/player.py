@@ -102,7 +102,7 @@ class StreamDecoder:
         return cm
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
-                 residual=None):
+                 residual=None, compare=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -121,7 +121,11 @@ class StreamDecoder:
         there when side= is given), fit=, pad=: every picture as the batch [N, 3, H, W] of its rectangles (pic_output_tensor's rois / fit / pad;
         tensor=dict(snap=True) for boxes a detector made).  The list, or what the callable returns, may also be a torch tensor on the decoder's device - int32
         [N, 4] xywh or float32 [N, 4] xyxy, a detector's boxes where it left them: they are read on the device, with no host read in between
-        (pic_output_tensor's rois=<tensor>; tensor=dict(count=, max_roi=) go with it)"""
+        (pic_output_tensor's rois=<tensor>; tensor=dict(count=, max_roi=) go with it)
+        compare=callable(params) -> a reference or None, or a sequence of such indexed in decoding order (shorter: the pictures past its end are not
+        compared): every picture against its reference on the device (XgpuDecoder.pic_compare: a tensor in pic_output's plane order on the decoder's device; a
+        dict(ref=..., ssim=..., block_map=...) passes pic_compare's other arguments), taken right behind the picture's kernels; the result - pic_compare's
+        dict - under params["compare"], None where there was no reference.  The crop defaults to the SPS crop when apply_crop is set"""
         if to is not None and tensor is None:
             raise ValueError("to: needs tensor=dict(...)")
         if (size is not None or mean is not None or std is not None) and tensor is None:
@@ -134,6 +138,7 @@ class StreamDecoder:
         th = threading.Thread(target=self._producer, args=(q,), daemon=True)
         th.start()
         slots, free = {}, []
+        n_decoded = [0]
 
         def decode(p):
             dec, hb = self._dec, p["batch"]
@@ -154,6 +159,15 @@ class StreamDecoder:
                     if kw.get("kind", "yuv420") != "energy":
                         kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
                     p["residual"] = dec.batch_residual(hb, **kw)
+                if compare is not None:
+                    i = n_decoded[0]
+                    ref = compare(p) if callable(compare) else compare[i] if i < len(compare) else None
+                    p["compare"] = None
+                    if ref is not None:
+                        kw = dict(ref) if isinstance(ref, dict) else {"ref": ref}
+                        kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
+                        p["compare"] = dec.pic_compare(cur, **kw)
+                n_decoded[0] += 1
                 if p["n_dmvr_sub"]:
                     p["_dmvr"][1] = dec.batch_dmvr_mvs(hb)
                     p["_dmvr"][0].set()
@@ -219,14 +233,16 @@ class StreamDecoder:
                 self._dec.close()
                 self._dec = None
 
-    def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None):
+    def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
+                     compare=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
-        params["residual"] as numpy - for kind "yuv420" the pair (flat array, (Y, Cb, Cr) views of it)"""
+        params["residual"] as numpy - for kind "yuv420" the pair (flat array, (Y, Cb, Cr) views of it); compare= (as pictures takes it, the callable and the
+        sequence in DECODING order): params["compare"], its map as a numpy array"""
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
-                                       residual=residual):
+                                       residual=residual, compare=compare):
             if p["is_idr"]:
                 epoch += 1
             if tensor is not None:
@@ -243,6 +259,8 @@ class StreamDecoder:
                 else:
                     r = r.cpu().numpy()
                 p["residual"] = r
+            if compare is not None and p["compare"] is not None and p["compare"]["map"] is not None:
+                p["compare"]["map"] = p["compare"]["map"].cpu().numpy()
             p["decode_index"] = len(out)       # place in decoding order
             out.append(((epoch, p["poc"]), p, planes))
         return [(p, planes) for _, p, planes in sorted(out, key=lambda t: t[0])]
