@@ -1212,57 +1212,99 @@ static const uint8_t k_htdf_tbl[5][16] = {
     { 0, 0, 3,  9, 19, 32, 47, 64, 81, 99, 117, 135, 154, 179, 205, 230 },
     { 0, 0, 0,  2,  6, 11, 18, 27, 38, 51,  64,  96, 128, 160, 192, 224 },
 };
+/* census of one filtered CU's look-ups, kept in locals while its windows go by and added to g_cen once per CU */
+typedef struct htdf_cen { uint32_t lut[16], edge[2], clip[2]; } htdf_cen;
 /* read_table (:176-189): small coefficients go through the table, large ones pass */
-static int htdf_lut(int z, const uint8_t *tbl, int thr, int shift, int rnd)
+static inline int htdf_lut(int z, const uint8_t *tbl, int thr, int shift, int rnd, htdf_cen *hc)
 {
     const int a = z < 0 ? -z : z;
-    const int v = a < thr ? tbl[((a + rnd) & thr) >> shift] : a;      /* (a + rnd) & thr: the reference's index mask, kept as it is */
+    int v;
+    if (a < thr) {      /* (a + rnd) & thr: the reference's index mask, kept as it is */
+        const int t = ((a + rnd) & thr) >> shift;
+        v = tbl[t];
+        hc->lut[t]++;
+    } else
+        v = a;
+    if ((unsigned)(a - thr + 1) < 2u) hc->edge[a - thr + 1]++;      /* (rare) */
     return z < 0 ? -v : v;
 }
-/* xevd_get_avail_intra, src_base/xevd_util.c:689-745: bit 0 up, 1 left, 3 right, 5 up-left, 6 up-right, 7 low-left, 8 low-right */
-static int avail_intra(const orc_maps *m, int xs, int ys, int scuw, int scuh)
+/* what the census keeps per SCU next to the maps while a batch is reconstructed (NULL without maps): the CU that wrote it, and ORC_K_* */
+enum { ORC_K_INTRA = 1, ORC_K_IBC = 2, ORC_K_INTER = 4, ORC_K_HTDF = 8 };
+static const uint32_t *g_scu_owner = NULL;
+static const uint8_t *g_scu_kind = NULL;
+/* xevd_get_avail_intra, src_base/xevd_util.c:689-745: bit 0 up, 1 left, 3 right, 5 up-left, 6 up-right, 7 low-left, 8 low-right.
+   tile_ref (census): the same bits, set where the neighbour is reconstructed and only its tile says no */
+static int avail_intra(const orc_maps *m, int xs, int ys, int scuw, int scuh, int *tile_ref)
 {
     const int k = ys * m->w_scu + xs;
-    int av = 0;
-#define AV_OK(n) (MCU_COD(m->map_scu[n]) && TILE_SAME(m, k, n))
-    if (xs > 0 && AV_OK(k - 1)) {
+    int av = 0, tr = 0;
+#define AV_OK(n, bit) (MCU_COD(m->map_scu[n]) && (TILE_SAME(m, k, n) || ((tr |= 1 << (bit)), 0)))
+    if (xs > 0 && AV_OK(k - 1, 1)) {
         av |= 1 << 1;
-        if (ys + scuh + scuw - 1 < m->h_scu && AV_OK(k + m->w_scu * (scuw + scuh) - m->w_scu - 1)) av |= 1 << 7;
+        if (ys + scuh + scuw - 1 < m->h_scu && AV_OK(k + m->w_scu * (scuw + scuh) - m->w_scu - 1, 7)) av |= 1 << 7;
     }
     if (ys > 0) {
-        if (TILE_SAME(m, k, k - m->w_scu)) av |= 1 << 0;
-        if (xs > 0 && AV_OK(k - m->w_scu - 1)) av |= 1 << 5;
-        if (xs + scuw < m->w_scu && AV_OK(k - m->w_scu + scuw)) av |= 1 << 6;
+        if (TILE_SAME(m, k, k - m->w_scu)) av |= 1 << 0; else tr |= 1 << 0;
+        if (xs > 0 && AV_OK(k - m->w_scu - 1, 5)) av |= 1 << 5;
+        if (xs + scuw < m->w_scu && AV_OK(k - m->w_scu + scuw, 6)) av |= 1 << 6;
     }
-    if (xs + scuw < m->w_scu && AV_OK(k + scuw)) {
+    if (xs + scuw < m->w_scu && AV_OK(k + scuw, 3)) {
         av |= 1 << 3;
-        if (ys + scuh + scuw - 1 < m->h_scu && AV_OK(k + m->w_scu * (scuw + scuh - 1) + scuw)) av |= 1 << 8;
+        if (ys + scuh + scuw - 1 < m->h_scu && AV_OK(k + m->w_scu * (scuw + scuh - 1) + scuw, 8)) av |= 1 << 8;
     }
 #undef AV_OK
+    *tile_ref = tr;
     return av;
 }
-static void orc_htdf(int16_t *rec, int s, int w, int h, int qp, int intra, const orc_maps *m, int xs, int ys, int constrained, int bd)
+/* census: the kinds of the CUs along one side of a filtered CU (n SCUs from (sx, sy), step along x or y) */
+static void htdf_cen_nbr(const orc_maps *m, int side, int sx, int sy, int n, int along_x, int k_cur)
+{
+    int seen = 0, i, b;
+    for (i = 0; i < n; i++) {
+        const int x = sx + (along_x ? i : 0), y = sy + (along_x ? 0 : i);
+        int kd;
+        if (x < 0 || y < 0 || x >= m->w_scu || y >= m->h_scu) kd = 4;
+        else {
+            const int q = y * m->w_scu + x, kk = g_scu_kind ? g_scu_kind[q] : 0;
+            if (!MCU_COD(m->map_scu[q]) || !TILE_SAME(m, k_cur, q)) kd = 5;
+            else kd = (kk & ORC_K_INTRA) ? 0 : (kk & ORC_K_IBC) ? 1 : (kk & ORC_K_HTDF) ? 2 : 3;
+        }
+        seen |= 1 << kd;
+    }
+    for (b = 0; b < 6; b++) if ((seen >> b) & 1) g_cen.htdf_nbr[side][b]++;
+}
+/* -> 1 when the CU was filtered */
+static int orc_htdf(int16_t *rec, int s, int w, int h, int qp, int intra, const orc_maps *m, int xs, int ys, int constrained, int bd)
 {
     const int we = w + 2, he = h + 2, k = ys * m->w_scu + xs;
     const int mn = w < h ? w : h, mxs = w > h ? w : h;
     int16_t *tb, *acc;
-    int av, i, r, c, idx, thr_log2, shift, rnd, thr;
+    int av, tile_ref, i, r, c, idx, thr_log2, shift, rnd, thr, minus8 = 0;
+    uint32_t src[3][3] = { { 0 } };
+    htdf_cen hc;
     /* xevdm_htdf_skip_condition (:270-297) */
-    if (qp <= 17 || w * h < 64 || mxs >= 128) return;
-    if (!intra) { if (mn >= 32) return; }
-    else if (w == h && mn >= 32) qp -= 8;
-    av = avail_intra(m, xs, ys, w >> 2, h >> 2);
+    if (qp <= 17) { g_cen.htdf_skip[0]++; return 0; }
+    if (w * h < 64) { g_cen.htdf_skip[1]++; return 0; }
+    if (mxs >= 128) { g_cen.htdf_skip[2]++; return 0; }
+    if (!intra) { if (mn >= 32) { g_cen.htdf_skip[3]++; return 0; } }
+    else if (w == h && mn >= 32) { qp -= 8; minus8 = 1; }
+    av = avail_intra(m, xs, ys, w >> 2, h >> 2, &tile_ref);
     tb = (int16_t *)malloc(sizeof(int16_t) * we * he);
     acc = (int16_t *)calloc((size_t)we * he, sizeof(int16_t));
     for (i = 0; i < h; i++) memcpy(tb + (i + 1) * we + 1, rec + i * s, sizeof(int16_t) * w);
     /* one sample of border: the neighbour's reconstruction where it exists (and is intra under constrained intra prediction), else the CU's own edge */
     for (i = 0; i < h; i++) {
-        tb[(i + 1) * we] = ((av >> 1) & 1) && (!constrained || MCU_IF(m->map_scu[k - 1 + (i >> 2) * m->w_scu])) ? rec[i * s - 1] : rec[i * s];
-        tb[(i + 1) * we + we - 1] = ((av >> 3) & 1) && (!constrained || MCU_IF(m->map_scu[k + (w >> 2) + (i >> 2) * m->w_scu])) ? rec[i * s + w] : rec[i * s + w - 1];
+        const int le = ((av >> 1) & 1) ? ((!constrained || MCU_IF(m->map_scu[k - 1 + (i >> 2) * m->w_scu])) ? 0 : 2) : 1;
+        const int ri = ((av >> 3) & 1) ? ((!constrained || MCU_IF(m->map_scu[k + (w >> 2) + (i >> 2) * m->w_scu])) ? 0 : 2) : 1;
+        tb[(i + 1) * we] = le == 0 ? rec[i * s - 1] : rec[i * s];
+        tb[(i + 1) * we + we - 1] = ri == 0 ? rec[i * s + w] : rec[i * s + w - 1];
+        src[0][le]++; src[2][ri]++;
     }
     for (i = 0; i < w; i++) {
-        tb[i + 1] = (av & 1) && (!constrained || MCU_IF(m->map_scu[k - m->w_scu + (i >> 2)])) ? rec[i - s] : rec[i];
+        const int up = (av & 1) ? ((!constrained || MCU_IF(m->map_scu[k - m->w_scu + (i >> 2)])) ? 0 : 2) : 1;
+        tb[i + 1] = up == 0 ? rec[i - s] : rec[i];
         tb[(he - 1) * we + i + 1] = rec[(h - 1) * s + i];
+        src[1][up]++;
     }
     tb[0] = ((av >> 5) & 1) ? rec[-1 - s] : rec[0];
     tb[we - 1] = ((av >> 6) & 1) ? rec[w - s] : rec[w - 1];
@@ -1270,23 +1312,79 @@ static void orc_htdf(int16_t *rec, int s, int w, int h, int qp, int intra, const
     tb[we - 1 + we * (he - 1)] = ((av >> 8) & 1) ? rec[w + h * s] : rec[w - 1 + (h - 1) * s];
     /* filter_block_luma (:252-268) + xevdm_htdf_filter_block (:201-250): every 2x2 window, Hadamard, table on the three AC terms, back,
        accumulated into the four samples; a sample is final once its fourth window has gone by */
-    idx = (qp - 20 + 4) >> 3; idx = idx < 0 ? 0 : (idx > 4 ? 4 : idx);
+    idx = (qp - 20 + 4) >> 3;
+    if (idx < 0) g_cen.htdf_idx_neg++;
+    idx = idx < 0 ? 0 : (idx > 4 ? 4 : idx);
     thr_log2 = k_htdf_thr_log2[idx]; shift = thr_log2 - 4; rnd = (1 << shift) >> 1; thr = (1 << thr_log2) - (1 << shift);
+    memset(&hc, 0, sizeof(hc));
     for (r = 0; r < he - 1; r++) for (c = 0; c < we - 1; c++) {
         int16_t *in = tb + r * we + c, *out = acc + r * we + c;
         const int x0 = in[0], x1 = in[1], x2 = in[we], x3 = in[we + 1];
         const int y0 = x0 + x2, y1 = x1 + x3, y2 = x0 - x2, y3 = x1 - x3;
-        const int z0 = y0 + y1, z1 = htdf_lut(y0 - y1, k_htdf_tbl[idx], thr, shift, rnd), z2 = htdf_lut(y2 + y3, k_htdf_tbl[idx], thr, shift, rnd),
-                  z3 = htdf_lut(y2 - y3, k_htdf_tbl[idx], thr, shift, rnd);
+        const int z0 = y0 + y1, z1 = htdf_lut(y0 - y1, k_htdf_tbl[idx], thr, shift, rnd, &hc), z2 = htdf_lut(y2 + y3, k_htdf_tbl[idx], thr, shift, rnd, &hc),
+                  z3 = htdf_lut(y2 - y3, k_htdf_tbl[idx], thr, shift, rnd, &hc);
         const int i0 = z0 + z2, i1 = z1 + z3, i2 = z0 - z2, i3 = z1 - z3;
+        int v;
         out[0] = (int16_t)(out[0] + ((i0 + i1) >> 2));
         out[1] = (int16_t)(out[1] + ((i0 - i1) >> 2));
         out[we] = (int16_t)(out[we] + ((i2 + i3) >> 2));
         out[we + 1] = (int16_t)(out[we + 1] + ((i2 - i3) >> 2));
-        in[0] = (int16_t)CLIP3(0, (1 << bd) - 1, (out[0] + 2) >> 2);
+        v = (out[0] + 2) >> 2;
+        in[0] = (int16_t)CLIP3(0, (1 << bd) - 1, v);
+        if (in[0] != v && r > 0 && c > 0) hc.clip[v > 0]++;      /* (rare; row and column 0 are border, not output) */
     }
     for (i = 0; i < h; i++) memcpy(rec + i * s, tb + (i + 1) * we + 1, sizeof(int16_t) * w);
     free(tb); free(acc);
+    /* census, once per CU */
+    {
+        const int scuw = w >> 2, scuh = h >> 2;
+        static const int tile_bit[7] = { 1, 0, 3, 5, 6, 7, 8 };
+        g_cen.htdf_shape[intra ? 0 : 1][ilog2(w) - 2][ilog2(h) - 2]++;
+        g_cen.htdf_table[minus8][idx]++;
+        for (i = 0; i < 9; i++) g_cen.htdf_avail[i][(av >> i) & 1]++;
+        for (i = 0; i < 3; i++) {
+            for (c = 0; c < 3; c++) g_cen.htdf_src[i][c] += src[i][c];
+            if (src[i][0] && src[i][2]) g_cen.htdf_side_mixed[i]++;
+        }
+        for (i = 0; i < 7; i++) if ((tile_ref >> tile_bit[i]) & 1) g_cen.htdf_tile_refused[i]++;
+        if (((av >> 7) & 1) && !MCU_COD(m->map_scu[k - 1 + scuh * m->w_scu])) g_cen.htdf_stale_corner[0]++;
+        if (((av >> 8) & 1) && !MCU_COD(m->map_scu[k + scuw + scuh * m->w_scu])) g_cen.htdf_stale_corner[1]++;
+        for (i = 0, c = 3 * (he - 1) * (we - 1); i < 16; i++) { g_cen.htdf_lut[idx][i] += hc.lut[i]; c -= (int)hc.lut[i]; }
+        g_cen.htdf_pass[idx] += (uint32_t)c;      /* three AC terms per window: what was not looked up passed */
+        g_cen.htdf_thr_edge[idx][0] += hc.edge[0]; g_cen.htdf_thr_edge[idx][1] += hc.edge[1];
+        g_cen.htdf_out_clip[0] += hc.clip[0]; g_cen.htdf_out_clip[1] += hc.clip[1];
+        htdf_cen_nbr(m, 0, xs - 1, ys, scuh, 0, k);
+        htdf_cen_nbr(m, 1, xs, ys - 1, scuw, 1, k);
+        htdf_cen_nbr(m, 2, xs + scuw, ys, scuh, 0, k);
+    }
+    return 1;
+}
+/* census of one IBC CU: its vector, where its source lies and what the source holds */
+static void ibc_census(const xgpu_seq_params *sp, const xgpu_cu_batch *b, int i, const orc_maps *m, int planes)
+{
+    const int x = b->x[i], y = b->y[i], w = 1 << b->log2w[i], h = 1 << b->log2h[i], bv[2] = { b->mv[i * 4], b->mv[i * 4 + 1] };
+    const int x0 = x + bv[0], y0 = y + bv[1], x1 = x0 + w - 1, y1 = y0 + h - 1, ctu = 1 << sp->log2_ctu;
+    uint32_t seen[17 * 17];
+    int n = 0, a, sx, sy, kinds = 0, q;
+    if (w > 64 || h > 64) return;      /* (no such CU in a stream: the copy is for CUs of at most 64x64) */
+    g_cen.ibc_shape[b->log2w[i] - 2][b->log2h[i] - 2]++;
+    if (planes == 1) g_cen.ibc_luma_only++;
+    for (a = 0; a < 2; a++) g_cen.ibc_bv[a][bv[a] < 0 ? 0 : (bv[a] == 0 ? 1 : 2)][bv[a] & 1]++;
+    g_cen.ibc_region[y1 < y / ctu * ctu ? 0 : (x1 < x / ctu * ctu ? 1 : 2)]++;
+    if (x1 == x - 1) g_cen.ibc_touch[0]++;
+    if (y1 == y - 1) g_cen.ibc_touch[1]++;
+    if (!g_scu_owner || x0 < 0 || y0 < 0 || (x1 >> 2) >= m->w_scu || (y1 >> 2) >= m->h_scu) return;
+    for (sy = y0 >> 2; sy <= y1 >> 2; sy++) for (sx = x0 >> 2; sx <= x1 >> 2; sx++) {
+        const uint32_t o = g_scu_owner[sy * m->w_scu + sx];
+        for (q = 0; q < n && seen[q] != o; q++) ;
+        if (q == n) seen[n++] = o;
+        kinds |= g_scu_kind[sy * m->w_scu + sx];
+    }
+    g_cen.ibc_src_cus[n == 1 ? 0 : (n <= 4 ? 1 : 2)]++;
+    if (kinds & ORC_K_INTRA) g_cen.ibc_src_kind[0]++;
+    if (kinds & ORC_K_IBC) g_cen.ibc_src_kind[1]++;
+    if (kinds & ORC_K_HTDF) g_cen.ibc_src_kind[2]++;
+    if (kinds & ORC_K_INTER) g_cen.ibc_src_kind[3]++;
 }
 
 
@@ -1306,7 +1404,11 @@ int orc_recon_batch_ex(const xgpu_seq_params *sp, const orc_frame *fr, const xgp
     int16_t refined[64][2][2];
     int dmvr_done = 0;
     uint8_t *tmap = maps ? tile_map(b->tiles, maps->w_scu, maps->h_scu) : NULL;
+    /* census only: which CU wrote an SCU and what kind it was (ORC_K_*) */
+    uint32_t *scu_owner = maps ? (uint32_t *)malloc(sizeof(uint32_t) * (size_t)maps->w_scu * maps->h_scu) : NULL;
+    uint8_t *scu_kind = maps ? (uint8_t *)calloc((size_t)maps->w_scu * maps->h_scu, 1) : NULL;
     if (maps) maps->map_tidx = tmap;
+    g_scu_owner = scu_owner; g_scu_kind = scu_kind;
     for (l = 0; l < 2; l++) for (c = 0; c < 3; c++) pred[l][c] = (int16_t *)malloc(sizeof(int16_t) * MAX_CU * MAX_CU);
     res = (int16_t *)malloc(sizeof(int16_t) * MAX_CU * MAX_CU);
 
@@ -1317,12 +1419,14 @@ int orc_recon_batch_ex(const xgpu_seq_params *sp, const orc_frame *fr, const xgp
         /* local dual tree: a luma-only (intra / IBC) or chroma-only (intra) CU - prediction, residual, HTDF and the map update per plane it has (xevd_check_luma /
            xevd_check_chroma in xevd_recon_unit, src_main/xevdm.c:1230-1405; a chroma-only CU leaves the maps alone, xevdm_set_dec_info xevdm_util.c:4241) */
         const int planes = CU_PLANES(b, i);
+        int filtered = 0;
 #define HAS_PLANE(c) ((planes >> ((c) ? 1 : 0)) & 1)
         if (b->pred_mode[i] == XGPU_MODE_IBC) {
             /* xevdm_IBC_mc, xevdm_mc.c:2040-2106: a copy out of the CURRENT picture (reconstructed, not yet filtered) at the whole-sample block
                vector mv[0]; chroma at the halved vector */
             const int bx = b->mv[i * 4], by = b->mv[i * 4 + 1];
             int r;
+            if (maps) ibc_census(sp, b, i, maps, planes);
             for (r = 0; r < h; r++) memcpy(pred[0][0] + r * w, fr->cur.y + (y + by + r) * fr->cur.s_l + x + bx, sizeof(int16_t) * w);
             for (r = 0; r < h >> 1; r++) {
                 memcpy(pred[0][1] + r * (w >> 1), fr->cur.u + ((y >> 1) + (by >> 1) + r) * fr->cur.s_c + (x >> 1) + (bx >> 1), sizeof(int16_t) * (w >> 1));
@@ -1350,6 +1454,13 @@ int orc_recon_batch_ex(const xgpu_seq_params *sp, const orc_frame *fr, const xgp
         else if (maps) {      /* xevd_recon_unit's intra branch, xevd.c:731-741 (availability needs the SCU map) */
             int16_t nb_up[2 * MAX_CU + 8], nb_le[2 * MAX_CU + 8], nb_ri[2 * MAX_CU + 8];
             const int lr = avail_lr_of(maps, x >> 2, y >> 2, w >> 2);
+            if (b->constrained_intra_pred && (planes & 1)) {      /* census: IBC CUs next to an intra CU that may only read intra neighbours */
+                int u, le = 0, up = 0;
+                for (u = 0; u < h >> 2 && x > 0; u++) le |= scu_kind[((y >> 2) + u) * maps->w_scu + (x >> 2) - 1] & ORC_K_IBC;
+                for (u = 0; u < w >> 2 && y > 0; u++) up |= scu_kind[((y >> 2) - 1) * maps->w_scu + (x >> 2) + u] & ORC_K_IBC;
+                if (le) g_cen.ibc_nbr_of_cintra[0]++;
+                if (up) g_cen.ibc_nbr_of_cintra[1]++;
+            }
             for (c = 0; c < 3; c++) {
                 const int cw = c ? w >> 1 : w, ch = c ? h >> 1 : h, s = c ? fr->cur.s_c : fr->cur.s_l;
                 const int16_t *plane = c == 0 ? fr->cur.y : (c == 1 ? fr->cur.u : fr->cur.v);
@@ -1439,9 +1550,19 @@ int orc_recon_batch_ex(const xgpu_seq_params *sp, const orc_frame *fr, const xgp
                 orc_recon(res, pred[0][c], coded, cw, ch, s, plane + (c ? (y >> 1) * s + (x >> 1) : y * s + x), sp->bit_depth_luma);
         }
         if (maps && b->htdf_slice_qp && b->pred_mode[i] != XGPU_MODE_IBC && ((b->cbf[i] & 1) || !inter) && (planes & 1))      /* xevdm.c:1381-1392 */
-            orc_htdf(fr->cur.y + y * fr->cur.s_l + x, fr->cur.s_l, w, h, b->htdf_slice_qp, !inter, maps, x >> 2, y >> 2, !inter && b->constrained_intra_pred,
-                     sp->bit_depth_luma);
-        if (maps && (planes & 1)) set_dec_info(sp, b, i, maps);
+            filtered = orc_htdf(fr->cur.y + y * fr->cur.s_l + x, fr->cur.s_l, w, h, b->htdf_slice_qp, !inter, maps, x >> 2, y >> 2, !inter && b->constrained_intra_pred,
+                                sp->bit_depth_luma);
+        else if (maps && b->htdf_slice_qp)
+            g_cen.htdf_skip[b->pred_mode[i] == XGPU_MODE_IBC ? 5 : ((planes & 1) ? 4 : 6)]++;
+        if (maps && (planes & 1)) {
+            const uint8_t kd = (uint8_t)((b->pred_mode[i] == XGPU_MODE_IBC ? ORC_K_IBC : (inter ? ORC_K_INTER : ORC_K_INTRA)) | (filtered ? ORC_K_HTDF : 0));
+            int u, v;
+            set_dec_info(sp, b, i, maps);
+            for (v = 0; v < h >> 2; v++) for (u = 0; u < w >> 2; u++) {
+                scu_owner[((y >> 2) + v) * maps->w_scu + (x >> 2) + u] = (uint32_t)i;
+                scu_kind[((y >> 2) + v) * maps->w_scu + (x >> 2) + u] = kd;
+            }
+        }
 #undef HAS_PLANE
         if (maps && inter && dmvr_done && !sp->tool_addb) {
             /* The SCU map after a refined CU.  xevdm_set_dec_info keeps both sets of vectors (map_mv refined, map_unrefined_mv not, xevdm_util.c:
@@ -1459,6 +1580,8 @@ int orc_recon_batch_ex(const xgpu_seq_params *sp, const orc_frame *fr, const xgp
     for (l = 0; l < 2; l++) for (c = 0; c < 3; c++) free(pred[l][c]);
     free(res);
     if (maps) maps->map_tidx = NULL;
+    g_scu_owner = NULL; g_scu_kind = NULL;
+    free(scu_owner); free(scu_kind);
     free(tmap);
     return 0;
 }

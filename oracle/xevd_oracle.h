@@ -168,6 +168,30 @@ typedef struct orc_census {
     uint32_t aff_mvf_whole_cu;                         /* the sub-block is the whole CU: the first branch wins over the others */
     uint32_t aff_ats[2][4][2];                         /* CUs with an ATS-inter TU: [path][idx - 1][pos] */
     uint32_t aff_cbf[2][8];                            /* CUs by [path][cbf] */
+    /* HTDF (orc_htdf, avail_intra and the call in orc_recon_batch_ex; only with maps and batch->htdf_slice_qp).  [side]: 0 left, 1 up, 2 right.  Neighbour kinds: 0 intra,
+       1 IBC, 2 inter filtered, 3 inter not filtered, 4 nothing there (picture edge), 5 there but not reconstructed yet or in another tile */
+    uint32_t htdf_shape[2][5][5];                      /* filtered CUs by [intra / inter][log2w - 2][log2h - 2] */
+    uint32_t htdf_skip[7];                             /* CUs not filtered: QP <= 17 / area < 64 / a side of 128 / inter with min >= 32 / inter without luma cbf / IBC / chroma-only tree */
+    uint32_t htdf_table[2][5];                         /* filtered CUs by [the slice QP / after the - 8 of square intra CUs of 32 and 64][table 0 .. 4] */
+    uint32_t htdf_idx_neg;                             /* ... whose index was negative before the clamp to 0 */
+    uint32_t htdf_avail[9][2];                         /* filtered CUs by availability bit 0 .. 8 [clear / set] (2 and 4 do not exist: always clear) */
+    uint32_t htdf_src[3][3];                           /* border samples by [side][the neighbour's sample / the CU's own edge: side unavailable / own edge: constrained intra refused the unit] */
+    uint32_t htdf_side_mixed[3];                       /* filtered CUs whose [side] holds both neighbours' samples and units constrained intra refused */
+    uint32_t htdf_tile_refused[7];                     /* left / up / right / up-left / up-right / low-left / low-right refused only because the neighbour lies in another tile */
+    uint32_t htdf_stale_corner[2];                     /* low-left / low-right flag set while the SCU actually read (row ys + scuh) is not reconstructed yet */
+    uint32_t htdf_lut[5][16], htdf_pass[5];            /* [table] AC terms looked up by index 0 .. 15 / passed through (a >= thr) */
+    uint32_t htdf_thr_edge[5][2];                      /* [table] AC terms with a == thr - 1 (the last one looked up) / a == thr (the first one passed) */
+    uint32_t htdf_out_clip[2];                         /* output samples clipped */
+    uint32_t htdf_nbr[3][6];                           /* filtered CUs by [side][kind of a neighbouring CU along that side] (a side with several kinds counts in each) */
+    /* IBC (the copy in orc_recon_batch_ex; needs maps) */
+    uint32_t ibc_shape[5][5];                          /* IBC CUs by [log2w - 2][log2h - 2] */
+    uint32_t ibc_luma_only;                            /* ... in a luma-only tree */
+    uint32_t ibc_bv[2][3][2];                          /* vector components by [x / y][negative / zero / positive][even / odd] */
+    uint32_t ibc_region[3];                            /* the source lies wholly in CTU rows above / wholly in CTUs to the left (not above) / reaches into the CU's own CTU */
+    uint32_t ibc_src_cus[3];                           /* distinct CUs under the luma source: 1 / 2 .. 4 / more */
+    uint32_t ibc_src_kind[4];                          /* the source holds samples of intra / IBC / HTDF-filtered / inter CUs (one CU may count in several) */
+    uint32_t ibc_touch[2];                             /* the source ends exactly at the CU's own left / top edge */
+    uint32_t ibc_nbr_of_cintra[2];                     /* intra CUs under constrained intra prediction with an IBC CU along their left / upper side */
 } orc_census;
 void orc_census_reset(void);
 void orc_census_get(orc_census *out);

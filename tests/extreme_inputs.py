@@ -10,6 +10,8 @@ coefficients, so the kernels' packed 16-bit arithmetic, clamps and table tops ar
   * for affine CUs: control points solved from target deltas for every branch of the model (`set_affine`: sub-block sizes, EIF applicability, the memory band and where its window
     lies, clamps against band and picture range, the clip thresholds of the translation path, control points at the s16 limits, vectors of more than 4096 samples), partitions
     with every CU shape of 8 .. 128 a side (`affine_partition`),
+  * for HTDF and intra block copy: partitions with every CU shape of 4 .. 128 a side in every order a split tree decodes them in, right to left included, and local dual
+    trees (`htdf_partition`); block vectors of every parity and sign into sources over many CUs, inside filtered CUs and inside other copies (`set_ibc_vectors`),
 and `apply` puts them into a case that cases.build_case has built (tools={"extreme": {...}}).  What each of them is FOR is asserted
 through the oracle's census (oracle_lib.census) in tests/test_oracle_extremes.py.
 """
@@ -664,6 +666,206 @@ def regenerate_affine_batch(case, seed, gen):
     case["batch"] = b
 
 
+# ---- HTDF and intra block copy: partitions with every filterable CU shape in every decoding order a split tree knows (htdf_partition), block vectors placed on purpose
+# (set_ibc_vectors).  The branches they are for: oracle/xevd_oracle.c orc_htdf, avail_intra and the IBC copy of orc_recon_batch_ex, census htdf_* / ibc_*.
+HTDF_BIG = ((64, 64), (64, 32), (32, 64), (64, 16), (16, 64), (64, 8), (8, 64), (64, 4), (4, 64))      # one shape per 64x64 cell
+# four shapes of at most 32 a side per 64x64 cell, one per quadrant: all sixteen, the unfilterable 4x4, 4x8 and 8x4 (area < 64) among them
+HTDF_QUADS = tuple(tuple(((4, 8, 16, 32)[i], (4, 8, 16, 32)[(i + q) % 4]) for i in range(4)) for q in range(4))
+# (64x64 twice and a cell of four 32x32: the square intra CUs of 32 and 64 are the ones filtered with the table of QP - 8)
+HTDF_CELLS = (HTDF_BIG[0], HTDF_QUADS[0], HTDF_BIG[1], HTDF_BIG[3], HTDF_QUADS[1], HTDF_BIG[2], ((32, 32),) * 4, HTDF_BIG[5], HTDF_QUADS[2], HTDF_BIG[4], HTDF_BIG[0], HTDF_BIG[7], HTDF_QUADS[3], HTDF_BIG[6],
+              HTDF_BIG[8])
+HTDF_128 = ((128, 128), (128, 64), (64, 128), (128, 32), (32, 128), (128, 16), (16, 128), (128, 8), (8, 128))      # a side of 128: never filtered
+HTDF_EDGE = ((8, 64), (8, 32), (4, 64), (8, 16), (4, 32), (8, 8), (4, 16), (4, 8), (8, 4), (4, 4))      # the last column of a picture 8 samples wider than a multiple of 64 (transposed: the last row)
+# local dual trees: the node whose luma leaves have this shape (the leaves are luma-only CUs, the node's chroma-only CU follows them)
+HTDF_DUAL_NODE = {(4, 16): (8, 16), (16, 4): (16, 8), (4, 8): (8, 8), (8, 4): (8, 8), (4, 4): (8, 8)}
+
+
+def _tile_order(px, py, pw, ph, bw, bh, mode):
+    """the blocks of bw x bh that tile a region, in the order of mode 0 rows top to bottom, each left to right / 1 columns left to right, each top to bottom (vertical cuts
+    first) / 2 columns RIGHT TO LEFT (the order sps_suco_flag gives the halves of a vertical cut) / 3 rows top to bottom, each right to left"""
+    cols, rows = list(range(px, px + pw, bw)), list(range(py, py + ph, bh))
+    if mode & 2:
+        cols = cols[::-1]
+    return [(x, y) for x in cols for y in rows] if mode in (1, 2) else [(x, y) for y in rows for x in cols]
+
+
+def htdf_partition(w, h, log2_ctu, rot=0, rtl=False, dual=False):
+    """affine_partition's sibling for the filter that follows every CU: the picture in cells of 64x64, each holding one shape with a side of 64 or four shapes of at most 32 a
+    side (HTDF_CELLS, from entry 4 * rot on), the CUs of a cell (of a quadrant) in one of the orders of _tile_order - which one changes from cell to cell; `rtl` admits the two
+    right-to-left ones, which leave a CU with its right-hand neighbours reconstructed.  With CTU 128 one of four whole CTUs holds a shape with a side of 128 (HTDF_128).  What
+    is left at the right and at the bottom (8 samples when the size is a multiple of 64 plus 8) is tiled with HTDF_EDGE (transposed along the bottom) from entry `rot` on.
+    `dual`: the leaves of 4x16, 16x4, 4x8, 8x4 and 4x4 become luma-only CUs of local dual trees (HTDF_DUAL_NODE).  -> x, y, log2w, log2h, ctu_cu_start, tree"""
+    ctu = 1 << log2_ctu
+    out, start = [], []
+    n_cell = n_ctu = n_edge = big = 0
+
+    def emit(px, py, pw, ph, shape, mode):
+        bw, bh = shape
+        if dual and shape in HTDF_DUAL_NODE and pw % HTDF_DUAL_NODE[shape][0] == 0 and ph % HTDF_DUAL_NODE[shape][1] == 0:
+            nw, nh = HTDF_DUAL_NODE[shape]
+            for nx, ny in _tile_order(px, py, pw, ph, nw, nh, mode):
+                out.extend((bx, by, bw, bh, 1) for bx, by in _tile_order(nx, ny, nw, nh, bw, bh, 0))
+                out.append((nx, ny, nw, nh, 2))
+            return
+        out.extend((bx, by, bw, bh, 0) for bx, by in _tile_order(px, py, pw, ph, bw, bh, mode))
+
+    for cy in range(0, h, ctu):
+        for cx in range(0, w, ctu):
+            start.append(len(out))
+            if log2_ctu == 7 and cx + 128 <= w and cy + 128 <= h:
+                n_ctu += 1
+                if (n_ctu - 1) & 3 == rot & 3:
+                    emit(cx, cy, 128, 128, HTDF_128[(rot + big) % len(HTDF_128)], 0)
+                    big += 1
+                    continue
+            cells = [(qx, qy) for qy in range(cy, min(cy + ctu, h), 64) for qx in range(cx, min(cx + ctu, w), 64)]
+            if rtl and len(cells) == 4 and n_ctu & 1:      # every other whole CTU of 128: the right cell of each pair first - the left one then has a whole cell as its right-hand neighbour
+                cells = [cells[1], cells[0], cells[3], cells[2]]
+            for qx, qy in cells:
+                iw, ih = min(qx + 64, w) - qx, min(qy + 64, h) - qy
+                if iw == 64 and ih == 64:
+                    cell = HTDF_CELLS[(n_cell + 4 * rot) % len(HTDF_CELLS)]
+                    mode = (n_cell + rot) % (4 if rtl else 2)
+                    n_cell += 1
+                    if isinstance(cell[0], int):
+                        emit(qx, qy, 64, 64, cell, mode)
+                    else:      # quadrants: z-order, mirrored for the right-to-left orders; which shape lies where turns with rot
+                        for q in ((1, 0, 3, 2) if mode & 2 else (0, 1, 2, 3)):
+                            emit(qx + (q & 1) * 32, qy + (q >> 1) * 32, 32, 32, cell[(q + rot) % 4], (mode + q) % (4 if rtl else 2))
+                    continue
+                cands = [s for s in HTDF_EDGE if iw % s[0] == 0 and ih % s[1] == 0] if iw <= ih else [s[::-1] for s in HTDF_EDGE if iw % s[1] == 0 and ih % s[0] == 0]
+                emit(qx, qy, iw, ih, cands[(n_edge + rot) % len(cands)], (n_edge + rot) % (4 if rtl else 2))
+                n_edge += 1
+    start.append(len(out))
+    a = np.array(out, np.int64)
+    return (a[:, 0].astype(np.uint16), a[:, 1].astype(np.uint16), np.log2(a[:, 2]).astype(np.uint8), np.log2(a[:, 3]).astype(np.uint8), np.array(start, np.uint32), a[:, 4].astype(np.uint8))
+
+
+def regenerate_htdf_batch(case, seed, gen):
+    """Replace the case's batch by one that synth.gen_frame draws on htdf_partition (gen: its keyword arguments + 'rot', 'rtl', 'dual'); the slice QP of the filter and
+    constrained intra prediction are the old batch's"""
+    from xevd_amd import synth
+    gen = dict(gen)
+    rot, rtl, dual = gen.pop("rot", 0), gen.pop("rtl", False), gen.pop("dual", False)
+    old = case["batch"]
+    b = synth.gen_frame(np.random.default_rng(seed + 31 * rot), case["w"], case["h"], case["bd"], log2_ctu=case["log2_ctu"], eipd=bool(case["eipd"]),
+                        partition=htdf_partition(case["w"], case["h"], case["log2_ctu"], rot, rtl, dual), **gen)
+    # three in four of the square CUs of 32 and 64 are intra (the QP - 8 branch); an inter CU that turns intra keeps its coefficients (there is no ATS-inter here)
+    assert b.get("ats_inter") is None
+    sq = np.nonzero((b["log2w"] == b["log2h"]) & (b["log2w"] >= 5) & (b["log2w"] <= 6))[0]
+    for k, i in enumerate(sq):
+        if k & 3 != 3:
+            b["pred_mode"][i], b["refi"][i], b["mv"][i] = MODE_INTRA, -1, 0
+    b["constrained_intra_pred"] = old.get("constrained_intra_pred", 0)
+    if old.get("htdf_slice_qp"):
+        b["htdf_slice_qp"] = old["htdf_slice_qp"]
+    case["batch"] = b
+
+
+def htdf_filtered(batch):
+    """mask of the CUs the filter runs on, from the batch alone (xevdm_htdf_skip_condition and the call in xevd_recon_unit); the test side's restatement, held to the
+    oracle's census in tests/test_builder.py"""
+    hqp = int(batch.get("htdf_slice_qp", 0) or 0)
+    w, h = 1 << batch["log2w"].astype(np.int64), 1 << batch["log2h"].astype(np.int64)
+    intra = batch["pred_mode"] == MODE_INTRA
+    tree = batch["tree"] if batch.get("tree") is not None else np.zeros(len(w), np.uint8)
+    ok = (hqp > 17) & (tree != 2) & (batch["pred_mode"] != 6) & (((batch["cbf"] & 1) != 0) | intra)
+    return ok & (w * h >= 64) & (np.maximum(w, h) < 128) & (intra | (np.minimum(w, h) < 32))
+
+
+# what a CU asks of its source, in turn from CU to CU: the first that a source satisfies is taken
+IBC_WANTS = {
+    # every parity and sign of both components (chroma copies at bv >> 1: an odd negative component rounds down, a truncating division would not); sources that end on the CU's own edges
+    "parity": ("odd_neg_x", "odd_neg_y", "odd_pos_x", "odd_pos_y", "touch_left", "touch_top", "even_neg", "even_pos_x", "even_pos_y", "odd_neg_xy", "zero_x", "zero_y"),
+    # sources over many small CUs, inside filtered CUs (read after the filter), in the CTU row above, in the CTU to the left
+    "spread": ("many", "filtered", "above", "left", "many", "touch_top", "filtered", "odd_neg_xy", "touch_left"),
+    # sources that are themselves copies
+    "chain": ("ibc", "ibc", "filtered", "many", "odd_neg_x", "ibc", "above", "left", "odd_pos_y"),
+}
+
+
+def set_ibc_vectors(batch, kind, w, h, log2_ctu, seed, frac=0.4):
+    """Turn a share of the CUs (of at most 64x64, without ATS-inter, not affine, not chroma-only) into intra-block-copy CUs like synth.add_ibc does, with a vector chosen for
+    what IBC_WANTS[kind] asks of this CU: its candidates are the vectors aimed at that property plus random ones, and a candidate is valid when every sample of its source -
+    the luma block and, for an odd component, the column / row before it that the halved chroma vector reaches - lies inside the picture, in the CU's tile, and in a CU that
+    precedes this one in the batch (xgpu_intra_plan's node_ibc refuses the batch otherwise).  A CU for which no candidate is valid stays what it was."""
+    rng = np.random.default_rng(seed)
+    n = len(batch["x"])
+    S = 1 << log2_ctu
+    ws, hs = (w + 3) >> 2, (h + 3) >> 2
+    x, y = batch["x"].astype(np.int64), batch["y"].astype(np.int64)
+    cw, ch = 1 << batch["log2w"].astype(np.int64), 1 << batch["log2h"].astype(np.int64)
+    tree = batch["tree"] if batch.get("tree") is not None else np.zeros(n, np.uint8)
+    ai, aff = batch.get("ats_inter"), batch.get("affine")
+    tiles = batch.get("tiles")
+    tile_of = np.zeros((hs, ws), np.int64)
+    if tiles is not None:
+        cxs, cys = np.arange(ws) >> (log2_ctu - 2), np.arange(hs) >> (log2_ctu - 2)
+        tile_of = (np.searchsorted(tiles["row_bd"], cys, "right") - 1)[:, None] * (len(tiles["col_bd"]) - 1) + (np.searchsorted(tiles["col_bd"], cxs, "right") - 1)[None, :]
+    owner = np.full((hs, ws), -1, np.int64)       # the CU that has written an SCU so far
+    is_ibc = np.zeros(n, bool)
+    wants = IBC_WANTS[kind]
+    pick = (rng.random(n) < frac) | (cw * ch >= 2048)      # (the few CUs of 32x64 and more: all of them)
+    k = 0
+    for i in range(n):
+        xi_, yi, wi, hi = int(x[i]), int(y[i]), int(cw[i]), int(ch[i])
+        if pick[i] and tree[i] != 2 and wi <= 64 and hi <= 64 and not (ai is not None and ai[i]) and not (aff is not None and aff[i]):
+            filt = htdf_filtered(batch)
+            my_tile = tile_of[yi >> 2, xi_ >> 2]
+
+            def source(bx, by):
+                """-> the owners under the source of vector (bx, by), or None where it is not valid"""
+                x0, y0, x1, y1 = xi_ + (bx & ~1), yi + (by & ~1), xi_ + bx + wi - 1, yi + by + hi - 1
+                if x0 < 0 or y0 < 0 or x1 >= w or y1 >= h:
+                    return None
+                o = owner[y0 >> 2:(y1 >> 2) + 1, x0 >> 2:(x1 >> 2) + 1]
+                if (o < 0).any() or (tile_of[y0 >> 2:(y1 >> 2) + 1, x0 >> 2:(x1 >> 2) + 1] != my_tile).any():
+                    return None
+                return np.unique(o)
+            cy0, cx0 = yi // S * S, xi_ // S * S
+            rand = [(int(rng.integers(-xi_, w - wi - xi_ + 1)), int(rng.integers(-yi, min(cy0 + S, h) - hi - yi + 1))) for _ in range(48)]
+            odd = (1, 3, 5, 7, 9, 13, 17, 21, 33)
+            aimed = {
+                "odd_neg_x": [(-wi - a, -b) for a in odd for b in (0, 2, 4, hi, hi + 2)], "odd_neg_y": [(-a, -hi - b) for b in odd for a in (0, 2, 4, wi)],
+                "odd_neg_xy": [(-wi - a, -hi - b) for a in odd for b in odd] + [(-a, -hi - b) for a in odd for b in odd],
+                "odd_pos_x": [(a, -hi - b) for a in odd for b in (0, 1, 2, 8)], "odd_pos_y": [(-wi - a, b) for b in odd for a in (0, 1, 2, 8, 16, 32, 64)],
+                "even_pos_x": [(a, -hi - b) for a in (2, 4, 6, 8, 16) for b in (0, 1, 2, 8)], "even_pos_y": [(-wi - a, b) for b in (2, 4, 6, 8, 16) for a in (0, 1, 2, 8, 16, 32, 64)],
+                "even_neg": [(-wi - a, -b) for a in (0, 2, 4, 8) for b in (2, 4, 8, 0)], "zero_x": [(0, -hi - b) for b in (0, 1, 2, 3, 4, 8)], "zero_y": [(-wi - a, 0) for a in (0, 1, 2, 3, 4, 8)],
+                "touch_left": [(-wi, b) for b in (0, -1, 1, -2, 3, -3, 2, -5, -4, -8)], "touch_top": [(a, -hi) for a in (0, -1, 1, -3, 3, -2, 2, 5, -5, -8, 8)],
+            }
+            want = wants[k % len(wants)]
+            best, best_score = None, 0
+            for bv in aimed.get(want, []) + rand:
+                if bv == (0, 0):
+                    continue
+                own = source(*bv)
+                if own is None:
+                    continue
+                y1, x1 = yi + bv[1] + hi - 1, xi_ + bv[0] + wi - 1
+                score = {"many": len(own) if len(own) > 4 else 0, "filtered": int(filt[own].all()), "ibc": int(is_ibc[own].any()) + int(is_ibc[own].all()),
+                         "above": int(y1 < cy0), "left": int(x1 < cx0 and y1 >= cy0)}.get(want, 1 if bv in aimed.get(want, ()) else 0)
+                if score > best_score:
+                    best, best_score = bv, score
+                    if want in aimed:
+                        break
+                elif best is None and want not in aimed:
+                    best = bv      # nothing with the property yet: any valid source
+            if best is not None:
+                k += 1
+                is_ibc[i] = True
+                batch["pred_mode"][i] = 6
+                batch["refi"][i] = -1
+                batch["mv"][i] = 0
+                batch["mv"][i, 0] = best
+                if batch.get("ats") is not None:
+                    batch["ats"][i] = 0
+                if batch.get("dmvr") is not None:
+                    batch["dmvr"][i] = 0
+        if tree[i] != 2:
+            owner[yi >> 2:(yi + hi) >> 2, xi_ >> 2:(xi_ + wi) >> 2] = i
+    return batch
+
+
 PER_CU = ("x", "y", "log2w", "log2h", "pred_mode", "refi", "mv", "qp", "cbf", "coef_off", "ipm", "ats", "ats_inter", "affine", "affine_mv", "dmvr", "tree", "cbf_sub")
 
 
@@ -697,13 +899,16 @@ def apply(case, spec, seed=0):
     """spec: {'content': kind | [kind per reference picture], 'start': kind, 'qp': 'areas', 'mv': 'grid8' | 'small' | 'thresholds' | 'dmvr_mirror' | 'dmvr_zero' | 'dmvr_thresholds',
               'alf': (kind, ctb), 'levels': 'dense', 'tiles': (col_bd, row_bd, across), 'dmvr_pair': kind | [kind of pair 0, of pair 1],
               'partition': synth.gen_frame arguments for a batch on dmvr_partition, 'affine_partition': the same on affine_partition (+ 'rot'),
-              'affine': 'sizes' | 'eif' | 'trans' | 'limits' | 'wide' | 'tall' (set_affine), 'affine_start': the first variant }"""
+              'affine': 'sizes' | 'eif' | 'trans' | 'limits' | 'wide' | 'tall' (set_affine), 'affine_start': the first variant,
+              'htdf_partition': the same on htdf_partition (+ 'rot', 'rtl', 'dual'), 'ibc': (kind of IBC_WANTS, share of the CUs) for set_ibc_vectors }"""
     w, h, bd = case["w"], case["h"], case["bd"]
     base = 7919 * (seed + 1)
     if spec.get("partition") is not None:
         regenerate_batch(case, base + 500, spec["partition"])
     if spec.get("affine_partition") is not None:
         regenerate_affine_batch(case, base + 500, spec["affine_partition"])
+    if spec.get("htdf_partition") is not None:
+        regenerate_htdf_batch(case, base + 500, spec["htdf_partition"])
     kinds = spec.get("content")
     if kinds is not None:
         done = {}
@@ -752,6 +957,8 @@ def apply(case, spec, seed=0):
         case["alf_params"] = alf_params(kind, base + 300, len(old["ctb_flag"]), enable=old["enable"], ctb=ctb, across_tiles=old["across_tiles"])
     if spec.get("tiles") is not None:
         set_tiles(case, *spec["tiles"])
+    if spec.get("ibc") is not None:      # (after the tiles: a source must precede its CU in the batch's final order)
+        set_ibc_vectors(case["batch"], spec["ibc"][0], w, h, case["log2_ctu"], base + 600, spec["ibc"][1])
     return case
 
 
@@ -763,6 +970,7 @@ _DMVR = {"inter_frac": 1.0, "dmvr_frac": 0.95, "oob_frac": 0.0}
 _DGEN = {"inter_frac": 1.0, "bi_frac": 0.9, "n_refs": (2, 2), "oob_frac": 0.0, "admvp": True, "dmvr_frac": 0.95}
 _AFF = {"log2_ctu": 7, "inter_frac": 1.0, "oob_frac": 0.0}
 _AGEN = {"inter_frac": 1.0, "bi_frac": 0.5, "n_refs": (2, 2), "oob_frac": 0.0, "admvp": True, "ats_inter_frac": 0.6, "coded_frac": 0.85}
+_HGEN = {"inter_frac": 0.5, "bi_frac": 0.3, "n_refs": (1, 1), "oob_frac": 0.0, "admvp": True, "coded_frac": 0.9}
 _X_LADDER = {"content": ["ladder", "noise", "rails_dither", "ladder"], "qp": "areas", "mv": "grid8"}
 EXTREME_CASES = [
     # ADDB: QP 0..51 x slice offsets; step ladder / full-range noise / rails; with ALF behind the filter (k_addb_alf) and without (k_addb)
@@ -842,6 +1050,30 @@ EXTREME_CASES = [
     ("x_aff_limits_10b_noaddb", 264, 264, 10, 1, 1, (2, 2), 0.5, dict(_AFF, extreme={"affine_partition": dict(_AGEN, rot=7), "affine": "limits", "content": ["noise", "checker4"]}), ("aff_clip18", "aff_mvf")),
     ("x_affine_checker_10b", 200, 136, 10, 1, 1, (2, 2), 0.5, {"addb": 1, "inter_frac": 1.0, "affine_frac": 0.9, "split_prob": 0.3, "extreme": {"content": ["checker1", "noise", "checker2"]}}, ("aff_mvf", "aff_eif_rails", "aff_sub_mvclip", "aff_sub_regime")),
     ("x_affine_noise_12b", 200, 136, 12, 1, 1, (1, 1), 0.5, {"addb": 1, "alf": 1, "inter_frac": 1.0, "affine_frac": 0.9, "split_prob": 0.3, "extreme": {"content": "noise"}}, ("aff_mvf", "aff_eif_rails", "aff_sub_regime")),
+    # HTDF at every branch (htdf_partition: every CU shape, intra and inter, in every decoding order; `rtl`: right to left as well): the slice QPs at both ends of every table's
+    # range and of the filter's own (18, 51); noise for pass-throughs, smooth content and the ladder for look-ups at small indices, rails for the output clip; a start picture
+    # unlike anything the CUs write, so that a border sample read before its owner wrote it shows; constrained intra prediction with inter and intra CUs of 4 samples along the
+    # sides of CUs of up to 64; with and without ADDB and ALF behind the filter
+    ("x_htdf_qp18_noise_8b", 264, 200, 8, 1, 1, (1, 1), 0.3, {"htdf_qp": 18, "eipd": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=0), "content": "noise", "start": "gratings"}}, ("htdf_pass", "htdf_neg")),
+    ("x_htdf_qp23_ladder_10b", 200, 136, 10, 1, 1, (1, 1), 0.3, {"htdf_qp": 23, "addb": 1, "alf": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=1, rtl=True), "content": "ladder", "start": "noise"}}, ("htdf_lut", "htdf_neg", "htdf_right")),
+    ("x_htdf_qp24_smooth_12b_ctu128", 264, 264, 12, 1, 1, (1, 1), 0.3, {"htdf_qp": 24, "log2_ctu": 7, "eipd": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=2), "start": "checker2"}}, ("htdf_lut", "htdf_minus8")),
+    ("x_htdf_qp31_rails_8b_ctu128", 264, 264, 8, 1, 1, (1, 1), 0.3, {"htdf_qp": 31, "log2_ctu": 7, "addb": 1, "amp": 40.0, "extreme": {"htdf_partition": dict(_HGEN, rot=3, rtl=True, amp=40.0), "content": "rails_dither", "start": "noise"}},
+     ("htdf_rails", "htdf_minus8", "htdf_right")),
+    ("x_htdf_qp32_cip_10b_ctu128", 264, 264, 10, 1, 1, (1, 1), 0.3, {"htdf_qp": 32, "log2_ctu": 7, "constrained_intra": 1, "eipd": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=5, rtl=True), "content": "noise", "start": "ladder"}}, ("htdf_cip_mixed", "htdf_right")),
+    ("x_htdf_qp39_cip_12b_ctu128", 264, 264, 12, 1, 1, (1, 1), 0.3, {"htdf_qp": 39, "log2_ctu": 7, "constrained_intra": 1, "addb": 1, "alf": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=9, rtl=True), "content": "ladder", "start": "noise"}},
+     ("htdf_cip_mixed", "htdf_skips", "htdf_minus8")),
+    ("x_htdf_qp40_amp40_10b", 200, 136, 10, 1, 1, (1, 1), 0.3, {"htdf_qp": 40, "amp": 40.0, "eipd": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=6, rtl=True, amp=40.0), "content": "noise", "start": "rails_dither"}}, ("htdf_rails", "htdf_pass")),
+    ("x_htdf_qp47_ladder_8b", 264, 200, 8, 1, 1, (1, 1), 0.3, {"htdf_qp": 47, "addb": 1, "alf": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=7), "content": "ladder", "start": "gratings"}}, ("htdf_lut", "htdf_minus8")),
+    ("x_htdf_qp48_noise_10b_ctu128", 264, 264, 10, 1, 1, (1, 1), 0.3, {"htdf_qp": 48, "log2_ctu": 7, "addb": 1, "eipd": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=8, rtl=True), "content": "noise", "start": "ladder"}},
+     ("htdf_pass", "htdf_minus8", "htdf_right")),
+    ("x_htdf_qp51_smooth_12b", 264, 200, 12, 1, 1, (1, 1), 0.3, {"htdf_qp": 51, "eipd": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=4), "start": "noise"}}, ("htdf_lut",)),
+    # intra block copy with vectors placed on purpose (set_ibc_vectors); the first one at a slice QP of 17, the highest that switches the filter off with the batch still asking for it
+    ("x_ibc_parity_qp17_8b", 200, 136, 8, 1, 1, (1, 1), 0.3, {"htdf_qp": 17, "eipd": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=10, inter_frac=0.3), "content": "noise", "start": "ladder", "ibc": ("parity", 0.5)}},
+     ("ibc_parity", "ibc_touch", "htdf_qp17")),
+    ("x_ibc_spread_htdf_10b_ctu128", 264, 264, 10, 1, 1, (1, 1), 0.3, {"htdf_qp": 32, "log2_ctu": 7, "addb": 1, "alf": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=11, rtl=True), "content": "noise", "start": "gratings", "ibc": ("spread", 0.4)}},
+     ("ibc_spread", "ibc_touch")),
+    ("x_ibc_chain_cip_12b", 264, 200, 12, 1, 1, (1, 1), 0.3, {"htdf_qp": 40, "constrained_intra": 1, "eipd": 1, "addb": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=12, rtl=True, inter_frac=0.3), "content": "ladder", "start": "noise", "ibc": ("chain", 0.45)}},
+     ("ibc_chain", "ibc_cip")),
 ]
 
 # the cases written for the branches of the DMVR search (tests/test_oracle_extremes.py: test_dmvr_cases_together_reach_every_branch)
@@ -849,6 +1081,16 @@ DMVR_CASES = [s for s in EXTREME_CASES if "dmvr_pair" in s[8].get("extreme", {})
 
 # the cases written for the branches of the affine model (tests/test_oracle_extremes.py: test_affine_cases_together_reach_every_branch)
 AFFINE_CASES = [s for s in EXTREME_CASES if "affine" in s[8].get("extreme", {})]
+# the cases written for the branches of the Hadamard-domain filter and of intra block copy (tests/test_oracle_extremes.py: test_htdf_cases_together_reach_every_branch,
+# test_ibc_cases_together_reach_every_branch)
+HTDF_CASES = [s for s in EXTREME_CASES if "htdf_partition" in s[8].get("extreme", {}) and "ibc" not in s[8]["extreme"]]
+IBC_CASES = [s for s in EXTREME_CASES if "ibc" in s[8].get("extreme", {})]
+# ... with an uneven tile grid, local dual trees and copies inside it.  The reference harness has neither a tile map nor dual trees, so this one is held to the oracle only, like
+# TILE_CASES below (the oracle's handling of both is pinned by the golden streams the reference decoder produced: stream_main_*tiles*, stream_main_dual_tree_*)
+HTDF_TILE_CASES = [
+    ("xt_htdf_ibc_dual_tree_8b", 264, 200, 8, 1, 1, (1, 1), 0.3, {"htdf_qp": 32, "addb": 1, "eipd": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=13, rtl=True, dual=True), "content": "noise", "start": "ladder",
+                                                                                                               "tiles": ([0, 2, 5], [0, 1, 4], 0), "ibc": ("parity", 0.3)}}),
+]
 # clip18 of the EIF range, 1/32 sample: max_pic = (width + 128 - x - cuw - 1) * 32 passes 2^17 - 1 for x < width - cuw - 3969, min_pic = (-x - 128) * 32 passes -2^17 for
 # x > 3968 - from a width of 3984 a picture has both.  That the clip decides which sample is fetched takes more: a vector of more than 4096 samples that still ends inside the
 # picture (in the replicated border every vector fetches the same values), so CUs at x >= 4096 - the smallest multiple of 64 is 4160, whose last column of CTUs holds them.  The

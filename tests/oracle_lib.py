@@ -42,7 +42,12 @@ class OrcCensus(C.Structure):
                 ("aff_spread", C.c_uint32 * 5), ("aff_range_clip18", (C.c_uint32 * 2) * 2), ("aff_eif_clamp", ((C.c_uint32 * 2) * 2) * 2), ("aff_eif_frac", (C.c_uint32 * 32) * 2),
                 ("aff_eif_neg", C.c_uint32 * 2), ("aff_eif_clip", (C.c_uint32 * 2) * 3), ("aff_sub_mvclip", C.c_uint32 * 4), ("aff_sub_mvclip_frac", C.c_uint32 * 4),
                 ("aff_sub_clip18", C.c_uint32 * 2), ("aff_sub_regime", (C.c_uint32 * 4) * 2), ("aff_sub_luma_whole_chroma_half", C.c_uint32 * 2), ("aff_mvf", C.c_uint32 * 4),
-                ("aff_mvf_bl_vn2", C.c_uint32), ("aff_mvf_clip18", C.c_uint32), ("aff_mvf_whole_cu", C.c_uint32), ("aff_ats", ((C.c_uint32 * 2) * 4) * 2), ("aff_cbf", (C.c_uint32 * 8) * 2)]
+                ("aff_mvf_bl_vn2", C.c_uint32), ("aff_mvf_clip18", C.c_uint32), ("aff_mvf_whole_cu", C.c_uint32), ("aff_ats", ((C.c_uint32 * 2) * 4) * 2), ("aff_cbf", (C.c_uint32 * 8) * 2),
+                ("htdf_shape", ((C.c_uint32 * 5) * 5) * 2), ("htdf_skip", C.c_uint32 * 7), ("htdf_table", (C.c_uint32 * 5) * 2), ("htdf_idx_neg", C.c_uint32), ("htdf_avail", (C.c_uint32 * 2) * 9),
+                ("htdf_src", (C.c_uint32 * 3) * 3), ("htdf_side_mixed", C.c_uint32 * 3), ("htdf_tile_refused", C.c_uint32 * 7), ("htdf_stale_corner", C.c_uint32 * 2),
+                ("htdf_lut", (C.c_uint32 * 16) * 5), ("htdf_pass", C.c_uint32 * 5), ("htdf_thr_edge", (C.c_uint32 * 2) * 5), ("htdf_out_clip", C.c_uint32 * 2), ("htdf_nbr", (C.c_uint32 * 6) * 3),
+                ("ibc_shape", (C.c_uint32 * 5) * 5), ("ibc_luma_only", C.c_uint32), ("ibc_bv", ((C.c_uint32 * 2) * 3) * 2), ("ibc_region", C.c_uint32 * 3), ("ibc_src_cus", C.c_uint32 * 3),
+                ("ibc_src_kind", C.c_uint32 * 4), ("ibc_touch", C.c_uint32 * 2), ("ibc_nbr_of_cintra", C.c_uint32 * 2)]
 
 
 def census_reset():

@@ -259,3 +259,39 @@ def test_builder_affine_tile_lists_follow_the_oracle_census(name):
         got = _build(lib, sp, cb, threads)
         assert got[10 + 7] == len(lists[0]) + len(lists[1]), "number of affine tiles"
         assert got[6] == f"{h:016x}", f"affine tile list, {threads} builder thread(s)"
+
+
+def _htdf_ibc_specs():
+    import extreme_inputs as xi
+    return xi.HTDF_CASES + xi.IBC_CASES + xi.HTDF_TILE_CASES
+
+
+@pytest.mark.parametrize("spec", _htdf_ibc_specs(), ids=[s[0] for s in _htdf_ibc_specs()])
+def test_builder_htdf_ibc_nodes_follow_the_oracle_census(spec):
+    """The builder accepts every HTDF / IBC case - right-to-left orders, block vectors whose sources must all precede their CU - on 1 and on 4 threads with equal arrays, and
+    the length of k_intra's list is what the oracle's census says: the intra CUs, the IBC CUs and the inter CUs the filter runs on (the filter-only nodes).  An intra CU
+    that is not filtered goes in as several parts (xgpu_intra_plan.hip, PartRule: one per 64 units of work, at most 16); in these cases those are the CUs with a side of
+    128, the chroma-only ones and - at a slice QP of 17 - all of them."""
+    import cases
+    import extreme_inputs as xi
+    import oracle_lib as ol
+    from xevd_amd.abi import MODE_INTRA
+    cs = cases.build_case(*spec[:9])
+    b = cs["batch"]
+    ol.census_reset()
+    cases.run_cpu("oracle", cs, deblock=False, pad=False)
+    cen = ol.census()
+    filt = xi.htdf_filtered(b)
+    intra, ibc = b["pred_mode"] == MODE_INTRA, b["pred_mode"] == 6
+    # the test side's restatement of the skip condition against the census
+    assert (filt & intra).sum() == cen["htdf_shape"][0].sum() and (filt & ~intra).sum() == cen["htdf_shape"][1].sum() and ibc.sum() == cen["ibc_shape"].sum()
+    area = b["log2w"].astype(np.int64) + b["log2h"].astype(np.int64)
+    parts = np.where(filt, 1, np.clip((1 << np.maximum(area - 4, 0)) * (4 if cs["eipd"] else 1) // 64, 1, 16))
+    want = int(parts[intra].sum() + cen["ibc_shape"].sum() + cen["htdf_shape"][1].sum())
+    lib = _lib()
+    sp = abi.make_seq_params(cs["w"], cs["h"], cs["bd"], log2_ctu=cs["log2_ctu"], iqt=cs["iqt"], admvp=cs["admvp"], addb=cs["addb"], alf=cs["alf"], eipd=cs["eipd"])
+    cb, keep = abi.make_cu_batch(b)
+    one, four = _build(lib, sp, cb, 1), _build(lib, sp, cb, 4)
+    assert one == four
+    assert one[10 + 3] == want, (one[10:18], want)
+    assert cen["ibc_shape"].sum() > 0 or not spec[8]["extreme"].get("ibc")

@@ -3,7 +3,10 @@ samples on the rails, 0 / max checkerboards through every interpolation phase, Q
 ALF coefficients at their legal limits on gratings / noise / checkerboards, vectors on the MV-clip thresholds, every branch of the DMVR search (planted
 displacements, vectors on the thresholds, all sub-block shapes; also its refined vectors, and the scalar form of its prediction), every branch of the affine model
 (control points solved from target deltas: sub-block sizes, EIF applicability, the memory band and its clamps, the clip thresholds of the translation path, control points at
-the s16 limits, vectors of more than 4096 samples; also the stored sub-block vectors) - all three padded planes and the residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
+the s16 limits, vectors of more than 4096 samples; also the stored sub-block vectors), every branch of the Hadamard-domain filter (xi.HTDF_CASES: every CU shape as intra and as
+filter-only inter node in every decoding order, right to left included, the slice QPs at the ends of every table's range, constrained intra prediction with sides that mix, an
+uneven tile grid with local dual trees; also with the residual pass ahead - without the ride-along launch - and twice on one decoder) and of intra block copy (xi.IBC_CASES: vectors of
+every parity and sign, sources over many CUs, inside filtered CUs and inside other copies) - all three padded planes and the residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
 reach the branches they are for) are repeated here because this file needs only the oracle, which always ships."""
 import numpy as np
 import pytest
@@ -11,7 +14,7 @@ import pytest
 import cases
 import extreme_inputs as xi
 import oracle_lib as ol
-from test_oracle_extremes import TILED_STREAMS_REACHING_INTERIOR_BORDERS, check_census, check_tile_census, run_oracle_with_census
+from test_oracle_extremes import TILED_STREAMS_REACHING_INTERIOR_BORDERS, check_census, check_htdf_tile_census, check_tile_census, run_oracle_with_census
 
 pytestmark = pytest.mark.gpu
 
@@ -153,6 +156,56 @@ def test_gpu_affine_far_vectors(spec):
     out, res = cases.run_gpu(cs, resid=True)
     assert np.array_equal(res[:len(rr)], rr), "residual arena"
     _same(out, ref, spec[0])
+
+
+# ---- HTDF and intra block copy: the cases of xi.HTDF_CASES / xi.IBC_CASES (every branch of the filter and of the copy, test_htdf_cases_together_reach_every_branch,
+# test_ibc_cases_together_reach_every_branch) - planes, residual arena and census in test_gpu_extreme_case above, those with ADDB at up to 10 bit also in
+# test_gpu_extreme_case_scalar_deblocking
+@pytest.mark.parametrize("spec", xi.HTDF_CASES + xi.IBC_CASES, ids=[s[0] for s in xi.HTDF_CASES + xi.IBC_CASES])
+def test_gpu_htdf_ibc_case_residual_pass_ahead(spec):
+    """with HTDF nodes in the batch the residual pass of the next picture does not ride along in the data-flow launch: the other way of queueing it"""
+    _check(cases.build_case(*spec[:9]), spec[0] + " (ahead)", resid=True, ahead=True)
+
+
+@pytest.mark.parametrize("name", ["x_htdf_qp32_cip_10b_ctu128", "x_ibc_chain_cip_12b"])
+def test_gpu_htdf_case_decoded_twice_on_one_decoder(name):
+    """one batch decoded twice into one picture of one decoder, the start picture uploaded again in between (as cases.run_gpu(ahead=True) does): the done flags and the
+    epoch of the data-flow launch are reused, and both pictures must be the oracle's"""
+    from xevd_amd.decoder import XgpuDecoder
+    spec = next(s for s in xi.EXTREME_CASES if s[0] == name)
+    cs = cases.build_case(*spec[:9])
+    ref, _, _, _ = cases.run_cpu("oracle", cs)
+    with XgpuDecoder(cs["w"], cs["h"], cs["bd"], log2_ctu=cs["log2_ctu"], iqt=cs["iqt"], admvp=cs["admvp"], addb=cs["addb"], alf=cs["alf"], eipd=cs["eipd"], max_pics=8) as dec:
+        slots, by_obj = {}, {}
+        for key, pic in cs["refs"].items():
+            if id(pic) not in by_obj:
+                by_obj[id(pic)] = dec.pic_alloc()
+                dec.pic_upload_padded(by_obj[id(pic)], pic.bufs)
+            slots[key] = (by_obj[id(pic)], pic.poc)
+        cur = dec.pic_alloc()
+        hb = dec.batch_create(cs["batch"])
+        outs = []
+        for _ in range(2):
+            dec.pic_upload_padded(cur, cases._start_picture(cs).bufs)
+            dec.decode_picture(cur, cases.CUR_POC, slots, hb, deblock=not cs.get("no_deblock"), pad=True, qp_u_offset=cases.QP_OFFSETS[0], qp_v_offset=cases.QP_OFFSETS[1],
+                               alpha_off=cs["alpha_off"], beta_off=cs["beta_off"], alf=cs.get("alf_params"))
+            dec.sync()
+            outs.append([np.array(p, copy=True) for p in dec.pic_download_padded(cur)])
+    _same(outs[0], ref, name + " (first decode)")
+    _same(outs[1], ref, name + " (second decode)")
+
+
+@pytest.mark.parametrize("spec", xi.HTDF_TILE_CASES, ids=[s[0] for s in xi.HTDF_TILE_CASES])
+def test_gpu_htdf_tile_case(spec):
+    """HTDF, IBC and local dual trees inside an uneven tile grid: neighbours and sources across a tile border are not available.  Against the oracle only (the reference
+    harness has no tile map)."""
+    cs = cases.build_case(*spec)
+    (ref, _, _, rr), cen = run_oracle_with_census(cs)
+    check_htdf_tile_census(cen)
+    out, res = cases.run_gpu(cs, resid=True)
+    assert np.array_equal(res[:len(rr)], rr), "residual arena"
+    _same(out, ref, spec[0])
+    _same(cases.run_gpu(cs, ahead=True), ref, spec[0] + " (ahead)")
 
 
 # content kind x bit depth x partition depth per coding family.  split_prob low / high: k_inter's region and tile roles / its split role see the saturated windows

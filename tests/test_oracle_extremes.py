@@ -1,5 +1,5 @@
 """The extreme cases (tests/extreme_inputs.py: rail-to-rail content, QP 0..51 x slice offsets, vectors on the MV-clip thresholds, ALF coefficients at their legal
-limits, every branch of the DMVR search and of the affine model) through the CPU oracle and the REAL reference (oracle/_ref), plus the census: every case asserts that the oracle took the branches it exists for.
+limits, every branch of the DMVR search, of the affine model, of the Hadamard-domain filter and of intra block copy) through the CPU oracle and the REAL reference (oracle/_ref), plus the census: every case asserts that the oracle took the branches it exists for.
 
 The comparison is the one of test_picture_level_oracle_equals_reference: residual arena, pre-deblock planes, maps, final padded planes, against the reference's
 normative C path (simd=0) only - its SIMD kernels are known to diverge on out-of-range input (the level-cap comment in synth.gen_frame) and the
@@ -66,6 +66,11 @@ Asserted to be 0, with the reason:
 Mutations of the oracle's affine functions, one at a time, and the cases whose comparison with the reference catches them: profiles/affine_census.txt.  Two of the listed ones
 change no output and are caught by none: `<` against `<=` (`>` against `>=`) in the two range branches - on equality the re-anchored window IS centre +- spread, since max_pic -
 min_pic = (picture + 255 - CU) x 32 is more than any 2 x spread -, and that is also why the min / max of the re-anchored ends never picks the picture's other end.
+
+HTDF and intra block copy (xi.HTDF_CASES, xi.IBC_CASES, xi.HTDF_TILE_CASES: every CU shape as intra and as filter-only inter node in every decoding order - htdf_partition -, the
+slice QPs at both ends of every table's range, block vectors placed on purpose - set_ibc_vectors).  The census over them, the buckets asserted empty with their arguments
+(check_htdf_empty), 65 mutations of the oracle's filter, availability and copy - all caught - and the oracle's timing against the parent: profiles/htdf_ibc_census.txt.  The output
+clip of the filter was expected to be unreachable and is not: both rails at every bit depth.
 
 The census (which needs only the oracle) and the generator checks run everywhere; the comparison against the reference carries the `ref` mark and is skipped
 where oracle/_ref is not built, like tests/test_oracle_vs_ref.py.
@@ -160,7 +165,49 @@ def _aff_clip18(cen, cs):
     _all([cen["aff_mvf_clip18"]], "map vector moved by clip18")
 
 
+# ---- HTDF and intra block copy: what the cases of xi.HTDF_CASES / xi.IBC_CASES are for (all of them together: test_htdf_cases_together_reach_every_branch, test_ibc_...)
+def htdf_table_of(cs, minus8=False):
+    """the table a slice QP selects (xevdm_htdf_filter_block: (qp - 16) >> 3 clamped to 0 .. 4), from the case alone"""
+    return min(max((int(cs["batch"]["htdf_slice_qp"]) - (8 if minus8 else 0) - 16) >> 3, 0), 4)
+
+
+def _htdf_pass(cen, cs):
+    t = htdf_table_of(cs)
+    assert cen["htdf_pass"][t] > 0 and (cen["htdf_thr_edge"][t] > 0).all(), f"table {t}: pass-throughs {cen['htdf_pass'].tolist()}, a == thr - 1 / a == thr {cen['htdf_thr_edge'].tolist()}"
+
+
+def _htdf_minus8(cen, cs):
+    t, t8 = htdf_table_of(cs), htdf_table_of(cs, True)
+    assert t8 != t and cen["htdf_table"][0][t] > 0 and cen["htdf_table"][1][t8] > 0 and (cen["htdf_lut"][t8] > 0).all(), f"one picture, two tables ({t}, {t8}): {cen['htdf_table'].tolist()}"
+    assert cen["htdf_table"][0].sum() == cen["htdf_table"][0][t] and cen["htdf_table"][1].sum() == cen["htdf_table"][1][t8]
+
+
+def _htdf_right(cen, cs):
+    assert cen["htdf_avail"][3][1] > 0 and cen["htdf_avail"][8][1] > 0 and cen["htdf_src"][2][0] > 0, "a right-to-left order: right and low-right neighbours reconstructed"
+
+
+def _ibc_parity(cen, cs):
+    bv = cen["ibc_bv"]
+    _all(bv[:, [0, 2]], "IBC vector components [x, y] x [negative, positive] x [even, odd]")
+    _all(bv[:, 1, 0], "IBC vector components of 0 [x, y]")
+    assert bv[:, 1, 1].sum() == 0      # (0 is even)
+
+
 REQUIRE = {
+    "htdf_pass": _htdf_pass,
+    "htdf_lut": lambda cen, cs: _all(cen["htdf_lut"][htdf_table_of(cs)], f"HTDF look-ups by index 0 .. 15 in table {htdf_table_of(cs)}"),
+    "htdf_neg": lambda cen, cs: _all([cen["htdf_idx_neg"], cen["htdf_table"][1][0]], "square intra CUs of 32 / 64 whose QP - 8 gives a negative index, clamped to table 0"),
+    "htdf_minus8": _htdf_minus8,
+    "htdf_right": _htdf_right,
+    "htdf_rails": lambda cen, cs: _all(cen["htdf_out_clip"], "HTDF output clipped [at 0, at max]"),
+    "htdf_skips": lambda cen, cs: _all(cen["htdf_skip"][1:5], "CUs not filtered: area < 64, a side of 128, inter with min >= 32, inter without luma cbf"),
+    "htdf_cip_mixed": lambda cen, cs: _all(cen["htdf_side_mixed"], "CUs whose [left, upper, right] side mixes neighbours' samples and units constrained intra refused") or _all(cen["htdf_src"], "border samples [side] x [source]"),
+    "htdf_qp17": lambda cen, cs: _all(cen["htdf_skip"][:1], "CUs not filtered because the slice QP is 17") or _all([int(cen["htdf_shape"].sum() == 0)], "and none filtered"),
+    "ibc_parity": _ibc_parity,
+    "ibc_touch": lambda cen, cs: _all(cen["ibc_touch"], "IBC sources that end at the CU's own [left, top] edge"),
+    "ibc_spread": lambda cen, cs: _all(cen["ibc_src_cus"], "IBC sources over 1, 2 .. 4, more CUs") or _all(cen["ibc_region"], "IBC sources in CTU rows above, in CTUs to the left, in the own CTU") or _all(cen["ibc_src_kind"], "IBC sources with intra, IBC, filtered, inter samples"),
+    "ibc_chain": lambda cen, cs: _all(cen["ibc_src_kind"][1:3], "IBC sources holding IBC / HTDF-filtered samples") or _all(cen["htdf_nbr"][:2, 1], "filtered CUs with an IBC CU on their left / upper side"),
+    "ibc_cip": lambda cen, cs: _all(cen["ibc_nbr_of_cintra"], "intra CUs under constrained intra prediction with an IBC CU along their [left, upper] side"),
     "aff_sizes": _aff_sizes,
     "aff_mvf": lambda cen, cs: _all(list(cen["aff_mvf"]) + [cen["aff_mvf_bl_vn2"], cen["aff_mvf_whole_cu"]], "map vectors from control point 0, 1, 2, the formula; bottom-left of two points; whole CU"),
     "aff_applic": _aff_applic,
@@ -217,8 +264,27 @@ def check_census(spec, cs, cen):
     assert cen["addb_lost"][1] == 0 and cen["addb_lost"][2] == 0 and cen["mc_stage1_wrap"] == 0, "a bucket the module docstring calls unreachable was reached"
     assert cen["dmvr_not_refined"][1] == 0 and cen["dmvr_win_off"][0][[0, 6, 7]].sum() == 0 and cen["dmvr_win_off"][1][[0, 1, 5, 6, 7]].sum() == 0, "a DMVR bucket the module docstring calls unreachable was reached"
     assert cen["aff_band_vn"][0] == 0, "an affine bucket the module docstring calls unreachable was reached"
+    check_htdf_empty(cen)
     for tag in spec[9]:
         REQUIRE[tag](cen, cs)
+
+
+def check_htdf_empty(cen):
+    """the HTDF / IBC buckets that must stay empty, each with its argument from the reference's code"""
+    # A low corner flag tests the SCU at row ys + scuh + scuw - 1 of the neighbouring column (xevd_get_avail_intra, xevd_util.c:700-703, :737-740), the sample comes from row
+    # ys + scuh (xevdm_htdf, xevdm_recon.c:352-368).  Both SCUs lie in ONE column, the read one above the tested one.  In a split tree two SCUs of one column are only ever
+    # parted by a horizontal cut (or a quad split), whose upper part is decoded first - SUCO reverses vertical cuts only - and unparted they are one CU: the tested SCU
+    # reconstructed implies the read one reconstructed.  So the filter never reads a sample its owner has yet to write, and the plan's "the reference reads what is there" is
+    # no race.  (A batch in an order no tree produces could fill this bucket; the builder takes such batches, tests/test_builder.py, and the cases here hold none.)
+    assert cen["htdf_stale_corner"].sum() == 0, cen["htdf_stale_corner"].tolist()
+    # table 4 after the - 8: (qp - 8 - 16) >> 3 >= 4 takes a slice QP of 56, the syntax ends at 51
+    assert cen["htdf_table"][1][4] == 0
+    # availability bits 2 and 4 are not written by xevd_get_avail_intra
+    assert cen["htdf_avail"][2][1] == 0 and cen["htdf_avail"][4][1] == 0
+    # right / low-left / low-right refused by a tile border alone: tiles are decoded in raster order, so the tile to the right and the tiles below are not reconstructed yet,
+    # and the low-left SCU of the tile to the left is only looked at when the left neighbour is available, i.e. in the CU's own tile
+    assert cen["htdf_tile_refused"][[2, 5, 6]].sum() == 0, cen["htdf_tile_refused"].tolist()
+    assert cen["ibc_bv"][:, 1, 1].sum() == 0      # a component of 0 is even
 
 
 def test_every_requirement_is_carried_by_a_case():
@@ -232,6 +298,7 @@ def test_every_requirement_is_carried_by_a_case():
         for tag in ("mc_clip", "recon_rails", "alf_clip", "addb_idx_top" if bd != 8 else "addb_chroma_top_rows"):
             assert any(spec[3] == bd and tag in spec[9] for spec in xi.EXTREME_CASES), (bd, tag)
         assert any(spec[3] == bd and any(t.startswith("dmvr_") for t in spec[9]) for spec in xi.DMVR_CASES), (bd, "a DMVR tag")
+        assert any(spec[3] == bd for spec in xi.HTDF_CASES) and any(spec[3] == bd for spec in xi.IBC_CASES), (bd, "an HTDF and an IBC case")
 
 
 @pytest.mark.parametrize("spec", xi.EXTREME_CASES, ids=[s[0] for s in xi.EXTREME_CASES])
@@ -349,6 +416,102 @@ def test_affine_cases_together_reach_every_branch():
     assert {(spec[3], spec[8].get("addb", 0)) for spec in xi.AFFINE_CASES} >= {(8, 0), (8, 1), (10, 0), (10, 1), (12, 0), (12, 1)}      # sub-block vectors feed both deblocking filters
     assert any(t.get("alf") for t in tools) and any(t.get("amp") == 40.0 for t in tools)
     assert all(spec[1] <= 264 and spec[2] <= 264 and spec[9] for spec in xi.AFFINE_CASES) and 8 <= len(xi.AFFINE_CASES) <= 10
+
+
+def htdf_ibc_census_together():
+    """the census of the HTDF, the IBC and the tiled HTDF cases, summed: -> (HTDF_CASES, IBC_CASES, HTDF_TILE_CASES, {bit depth: ... of HTDF_CASES})"""
+    def add(a, b):
+        return b if a is None else {k: a[k] + b[k] for k in b}
+    out, by_bd = [None, None, None], {}
+    for n, group in enumerate((xi.HTDF_CASES, xi.IBC_CASES, xi.HTDF_TILE_CASES)):
+        for spec in group:
+            _, cen = run_oracle_with_census(cases.build_case(*spec[:9]))
+            cen = {k: np.asarray(v) for k, v in cen.items() if k.startswith(("htdf_", "ibc_"))}
+            check_htdf_empty(cen)
+            out[n] = add(out[n], cen)
+            if n == 0:
+                by_bd[spec[3]] = add(by_bd.get(spec[3]), cen)
+    return out[0], out[1], out[2], by_bd
+
+
+HTDF_SLICE_QPS = (18, 23, 24, 31, 32, 39, 40, 47, 48, 51)      # both ends of the filter's range and of every table's
+
+
+def test_htdf_cases_together_reach_every_branch():
+    """the conditions the HTDF cases were chosen for, over all of them (profiles/htdf_ibc_census.txt holds this test's output)"""
+    htdf, ibc, tiled, by_bd = htdf_ibc_census_together()
+    for k, v in htdf.items():
+        if k.startswith("htdf_"):
+            print(k, v.tolist())
+    print("tiled case: htdf_tile_refused", tiled["htdf_tile_refused"].tolist(), "htdf_skip", tiled["htdf_skip"].tolist(), "; IBC cases: htdf_skip", ibc["htdf_skip"].tolist(), "htdf_nbr", ibc["htdf_nbr"].tolist())
+    filterable = np.array([[(4 << a) * (4 << b) >= 64 for b in range(5)] for a in range(5)])
+    narrow = np.array([[min(4 << a, 4 << b) < 32 for b in range(5)] for a in range(5)])
+    assert ((htdf["htdf_shape"][0] > 0) == filterable).all(), f"intra CUs of every filterable shape, none of 4x4, 4x8, 8x4: {htdf['htdf_shape'][0].tolist()}"
+    assert ((htdf["htdf_shape"][1] > 0) == (filterable & narrow)).all(), f"inter CUs of every filterable shape with min < 32, no other: {htdf['htdf_shape'][1].tolist()}"
+    # the 4x4-lane form of the kernel (1024 samples and more) on tall, wide and square blocks, intra; the filter-only nodes of 16x32 .. 64x16
+    for lw, lh in ((2, 4), (4, 2), (2, 3), (3, 2)):
+        assert htdf["htdf_shape"][1][lw][lh] > 0
+    _all(htdf["htdf_skip"][1:5], "CUs not filtered: area < 64, a side of 128, inter with min >= 32, inter without luma cbf")
+    _all([ibc["htdf_skip"][0], ibc["htdf_skip"][5], tiled["htdf_skip"][6]], "CUs not filtered: QP <= 17 and IBC (the IBC cases), chroma-only tree (the tiled case: the reference harness knows no dual tree)")
+    _all(htdf["htdf_table"][0], "filtered CUs by table, plain")
+    _all(htdf["htdf_table"][1][:4], "filtered CUs by table after the - 8, tables 0 .. 3")
+    _all([htdf["htdf_idx_neg"]], "index negative before the clamp")
+    _all(htdf["htdf_avail"][[0, 1, 3, 5, 6, 7, 8]], "availability bits up, left, right, up-left, up-right, low-left, low-right x [clear, set]")
+    _all(htdf["htdf_src"], "border samples [left, up, right] x [neighbour, own edge: unavailable, own edge: constrained intra]")
+    _all(htdf["htdf_side_mixed"], "CUs whose [left, up, right] side mixes neighbours and refused units")
+    _all(tiled["htdf_tile_refused"][[0, 1, 3, 4]], "left, up, up-left, up-right refused by a tile border alone")
+    _all(htdf["htdf_lut"], "look-ups [table] x index 0 .. 15")
+    _all(htdf["htdf_pass"], "pass-throughs [table]")
+    _all(htdf["htdf_thr_edge"], "[table] x [a == thr - 1, a == thr]")
+    # the output clip IS reached (rails_dither content, amp 40 residuals): the four shrunken inverse transforms of a sample do leave the range when a neighbour across
+    # the window sits on the other rail - the census refuted the guess that their mean cannot
+    _all(htdf["htdf_out_clip"], "output samples clipped [at 0, at max]")
+    _all(htdf["htdf_nbr"][:, [0, 2, 3, 4]], "filtered CUs by [side] x neighbour kind intra, inter filtered, inter unfiltered, picture edge")
+    _all(htdf["htdf_nbr"][[0, 2], 5], "filtered CUs whose [left, right] neighbour is not reconstructed yet")
+    # the CU above is decoded before the CU in every order a tree produces (horizontal cuts and quad splits go top first): "there but not available" above is a tile border
+    assert htdf["htdf_nbr"][1][5] == 0 and tiled["htdf_nbr"][1][5] > 0 and tiled["htdf_nbr"][1][5] == tiled["htdf_tile_refused"][1]
+    _all(ibc["htdf_nbr"][:, 1], "filtered CUs with an IBC CU on their [left, upper, right] side (the IBC cases)")
+    check_htdf_empty(htdf)
+    for bd in (8, 10, 12):
+        print(bd, "bit: filtered CUs [intra, inter]", by_bd[bd]["htdf_shape"].sum((1, 2)).tolist(), "clips", by_bd[bd]["htdf_out_clip"].tolist())
+        assert (by_bd[bd]["htdf_shape"].sum((1, 2)) >= 64).all()
+    _all([by_bd[8]["htdf_out_clip"].min(), by_bd[10]["htdf_out_clip"].min()], "output clip at both rails at 8 and at 10 bit")
+    specs = xi.HTDF_CASES
+    assert sorted(s[8]["htdf_qp"] for s in specs) == sorted(HTDF_SLICE_QPS)
+    assert all((s[1], s[2], s[8].get("log2_ctu", 6)) in ((264, 264, 7), (264, 200, 6), (200, 136, 6)) and s[8]["extreme"].get("start") for s in specs + xi.IBC_CASES + xi.HTDF_TILE_CASES)
+    assert sum(bool(s[8].get("constrained_intra")) for s in specs) == 2 and len(xi.HTDF_TILE_CASES) == 1 and len(specs) == 10
+    assert {(bool(s[8].get("addb")), bool(s[8].get("alf"))) for s in specs} >= {(False, False), (True, False), (True, True)}
+    assert any(s[8]["extreme"]["htdf_partition"].get("rtl") for s in specs) and any(not s[8]["extreme"]["htdf_partition"].get("rtl") for s in specs)
+
+
+def test_ibc_cases_together_reach_every_branch():
+    """the conditions the IBC cases were chosen for, over the three of them (+ the luma-only copies of the tiled case's dual trees)"""
+    _, ibc, tiled, _ = htdf_ibc_census_together()
+    for k, v in ibc.items():
+        if k.startswith("ibc_"):
+            print(k, v.tolist())
+    print("tiled case: ibc_luma_only", int(tiled["ibc_luma_only"]), "ibc_shape", tiled["ibc_shape"].tolist())
+    _all(ibc["ibc_shape"], "IBC CUs of 4 .. 64 x 4 .. 64")
+    _all([tiled["ibc_luma_only"]], "IBC CUs in a luma-only tree (the tiled case)")
+    REQUIRE["ibc_parity"](ibc, None)
+    for tag in ("ibc_touch", "ibc_spread", "ibc_chain", "ibc_cip"):
+        REQUIRE[tag](ibc, None)
+    _all(ibc["htdf_nbr"][:, 1], "an IBC CU as the left, upper, right neighbour of a filtered CU")
+    assert len(xi.IBC_CASES) == 3 and {s[3] for s in xi.IBC_CASES} == {8, 10, 12}
+
+
+@pytest.mark.parametrize("spec", xi.HTDF_TILE_CASES, ids=[s[0] for s in xi.HTDF_TILE_CASES])
+def test_htdf_tile_case_reaches_the_tile_border_branches(spec):
+    cs = cases.build_case(*spec)
+    _, cen = run_oracle_with_census(cs)
+    check_htdf_tile_census(cen)
+
+
+def check_htdf_tile_census(cen):
+    check_htdf_empty(cen)
+    _all(cen["htdf_tile_refused"][[0, 1, 3, 4]], "left, up, up-left, up-right refused by a tile border alone")
+    _all([cen["htdf_skip"][6], cen["ibc_luma_only"]], "chroma-only CUs left unfiltered; luma-only IBC CUs")
+    _all(cen["htdf_shape"][0][[0, 2], [2, 0]], "filtered luma-only CUs of 4x16 and 16x4")
 
 
 def affine_scu_mask(cs, maps):
