@@ -23,6 +23,7 @@
  *   xgpu_batch_residual           (no counterpart in the library: the prediction residual of a picture - what the reconstruction adds to the prediction - as dense planes)
  *   xgpu_frame_side_info          (no counterpart in the library; FFmpeg's export_mvs is the usual example: motion vectors, modes, QP of the picture decoded last)
  *   xgpu_pic_compare              (no counterpart in the library; ffmpeg's psnr / ssim filters are the usual example: a picture against a reference, exactly)
+ *   xgpu_pic_stats                (no counterpart in the library; ffmpeg's signalstats / histogram filters and a player's peak detection are the usual examples)
  *
  * plus fine-grained shims with the reference's per-block function-table signatures
  * (XEVD_MC_L / XEVD_MC_C src_base/xevd_mc.h:47-49, XEVD_ITXB src_base/xevd_def.h:360, fn_recon :1466)
@@ -591,6 +592,67 @@ int    xgpu_compare_check(const xgpu_compare_ref *r, const xgpu_compare_params *
    leaves a message in xgpu_last_error. */
 int    xgpu_pic_compare(xgpu_ctx *ctx, int pic, const xgpu_compare_ref *ref, const xgpu_compare_params *p,
                         xgpu_compare_result *d_result, uint64_t *d_map, size_t map_size, void *stream);
+/* ---- picture statistics (k_stats.hip): what is in ONE picture, from one pass over the slot - per component the census (n, sum, sum of squares, minimum,
+   maximum), a histogram and two percentiles of it; optionally the histogram of max(R', G', B') at luma resolution and the light level it implies (what HDR10
+   metadata calls MaxCLL and MaxFALL).  Everything is defined in integers but light_sum / light_mean, which are binary64 in a fixed order of individually
+   rounded operations: the result does not depend on the device, the launch or the scheduling.  B is the coding depth.
+     Samples     read as unsigned 16-bit patterns as they lie in the slot, as for xgpu_pic_compare; nothing is clipped or masked, and the census is exact for ANY
+                 16-bit contents.
+     Census      over the w x h plane of each component (the picture minus crop; chroma: half of it): n = w * h, sum = sum s, sum_sq = sum s^2, min, max.
+     Histogram   hist_bits != 0: [3][2^hist_bits] uint32, bin = min(s >> (B - hist_bits), 2^hist_bits - 1) (a pattern above 2^B - 1 counts in the last bin); every
+                 bin is written, and the bins of a component sum to n.
+     Percentile  pctl[c][i] = b << (B - hist_bits) for the smallest bin b with cum(b) * 10000 >= max(pctl_e4[i] * n, 1), cum(b) = the samples in bins 0 .. b,
+                 compared in 64-bit integers: the lower edge of that bin.  pctl_e4 = 0 gives the lowest occupied bin, 10000 the highest.  hist_bits = 0: 0.
+     Light       light != 0, per luma sample of the cropped picture: m = the largest of the three U16 elements xgpu_pic_output_device writes for
+                 XGPU_OUT_RGB_PLANAR, XGPU_OUT_U16, out_bit_depth 0, dra = NULL with the same matrix, full_range, chroma_loc, upsample and crop (the same code
+                 runs): a code in 0 .. 2^B - 1.  The light histogram [2^B] uint32 counts m at full resolution; light_n = w * h; light_max_code = the highest
+                 occupied code; light_pctl_code[i] = the percentile rule on this histogram; light_max = lin[light_max_code], light_pctl[i] =
+                 lin[light_pctl_code[i]], lin = xgpu_stats_lin(transfer, B): the lin table of xgpu_colour_tables, linear light in [0, 1] of a code.
+     light_sum   from the light histogram `count` alone, in binary64, every operation rounded once, nothing fused: for l = 0 .. 63, part[l] = 0 and, over
+                 k = l, l + 64, ... ascending, part[l] = part[l] + double(count[k]) * double(lin[k]); light_sum = part[0] + part[1] + ... + part[63], added left to
+                 right; light_mean = light_sum / double(light_n), one division.
+     Meaning     the scaling is the caller's: for PQ (transfer 16) 10000 * light_max is the picture's MaxCLL contribution and 10000 * light_mean its MaxFALL
+                 contribution in cd/m2; for HLG (18) lin is scene light; for the SDR curves it is relative to the display's white.
+   d_hist holds uint32 [3][2^hist_bits] (hist_bits != 0), then [2^B] for max(R', G', B') (light != 0).
+   Not offered: DRA (the slot's samples are counted as they are), a picture in host memory, and deriving src_peak inside xgpu_pic_output_device_cm - its tables
+   are made on the host: the caller reads light_pctl and passes it (times 10000 for PQ) as src_peak.
+   The exact contract: INTEGRATION.md section 8i; tests/stats_ref.py restates it in numpy. */
+typedef struct xgpu_stats_params {
+    int crop[4];        /* left, right, top, bottom luma samples, even */
+    int hist_bits;      /* 0: no histogram; else 4 .. coding depth B: 2^hist_bits bins per component */
+    int pctl_e4[2];     /* two percentiles in 1/10000, 0 .. 10000 (read when hist_bits != 0 or light != 0) */
+    int light;          /* 0 | 1: also the max(R',G',B') histogram and light level */
+    int matrix, full_range, chroma_loc, upsample;   /* light: as xgpu_output_format */
+    int transfer;       /* light: H.273 TransferCharacteristics of the stream (the list of xgpu_colour_transform) */
+} xgpu_stats_params;
+typedef struct xgpu_stats_result {        /* written by the device; 176 bytes, every field at a multiple of its size */
+    uint64_t n[3], sum[3], sum_sq[3];     /* per component Y, Cb, Cr over the cropped plane: offsets 0, 24, 48 */
+    uint32_t min[3], max[3];              /* 72, 84 */
+    uint32_t pctl[3][2];                  /* 96: bin << (B - hist_bits); 0 when hist_bits == 0 */
+    uint64_t light_n;                     /* 120; everything from here on: 0 when light == 0 */
+    double   light_sum, light_mean;       /* 128, 136 */
+    uint32_t light_max_code, light_pctl_code[2], reserved;      /* 144, 148, 156 (written as 0) */
+    float    light_max, light_pctl[2], reserved2;               /* 160, 164, 172 (written as 0) */
+} xgpu_stats_result;
+/* Host only, no context.  xgpu_stats_hist_size: (3 * 2^hist_bits (hist_bits != 0) + 2^B (light != 0)) * 4 bytes; 0: invalid parameters (what xgpu_stats_check
+   refuses without a picture size), or nothing to write.  xgpu_stats_check: everything xgpu_pic_stats refuses without looking at a context or a pointer's memory -
+   0, or XGPU_ERR_INVALID_ARGUMENT for a NULL, a size that is not positive and even, a depth outside 8..12, width * height >= 2^31, an odd or negative crop or
+   one that leaves nothing, hist_bits outside {0, 4 .. B}, a percentile outside 0 .. 10000 (where they are read), light outside 0 | 1 and - with light - a
+   full_range outside 0 | 1, a chroma_loc outside 0 .. 5 or an upsample that is neither XGPU_UPSAMPLE_NEAREST nor _LINEAR; then, with light,
+   XGPU_ERR_UNSUPPORTED for a matrix outside 1, 4, 5, 6, 7, 9 or a transfer outside xgpu_colour_transform's list.  xgpu_stats_lin: lin[k] = float32 of the linear
+   light of code k / (2^B - 1) under the inverse of `transfer`, k < 2^B, 0 behind - the lin of xgpu_colour_tables for that source transfer, bit for bit; 0,
+   XGPU_ERR_UNSUPPORTED for a transfer outside the list, XGPU_ERR_INVALID_ARGUMENT for a NULL or a depth outside 8..12. */
+size_t xgpu_stats_hist_size(const xgpu_stats_params *p, int bit_depth);
+int    xgpu_stats_check(const xgpu_stats_params *p, int width, int height, int bit_depth);
+int    xgpu_stats_lin(int transfer, int bit_depth, float lin[4096]);
+/* Non-blocking.  Takes the statistics of slot `pic` and writes *d_result and - where xgpu_stats_hist_size is not 0 - the histograms at d_hist (hist_size >=
+   xgpu_stats_hist_size bytes; else d_hist is not read).  d_result and d_hist must be device memory of the context's device, large enough, d_result 8-byte and
+   d_hist 4-byte aligned (checked before anything is queued).  Every field of the result and every histogram element is written by the call, on the same stream,
+   by the one workgroup that runs behind the others: the caller clears nothing, and a second call into the same buffers leaves the same bytes.  The picture is
+   only read.  stream = NULL: the context's stream; else the kernels run on `stream` behind the picture's kernels, and the context's stream waits for them.  A
+   refused call - what xgpu_stats_check refuses, with its code; a slot that holds no picture, a frame that is open (between xgpu_frame_begin and
+   xgpu_frame_end), a pointer that fails the checks above: XGPU_ERR_INVALID_ARGUMENT - queues nothing and leaves a message in xgpu_last_error. */
+int    xgpu_pic_stats(xgpu_ctx *ctx, int pic, const xgpu_stats_params *p, xgpu_stats_result *d_result, uint32_t *d_hist, size_t hist_size, void *stream);
 /* The picture signature on the device: the MD5 of every plane over its rows of width x 2 bytes of 16-bit samples (8-bit pictures too), as xevd_md5_imgb makes it
    (src_base/xevd_util.c:985-1002) and xevd_picbuf_check_signature compares it with the SEI (:1557-1572) - of the DRA-mapped picture when `dra` is given, which is
    what the Main decoder signs when the PPS names a DRA parameter set (src_main/xevdm.c:3256-3287).  digest[plane] = the 16 bytes of the SEI payload.  Blocking; the

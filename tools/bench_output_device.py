@@ -35,8 +35,12 @@ launches queued behind a wait, as the full-size forms are timed); `alternated_us
 needs for the bytes the call must read, the two pictures once; (b) what a caller does without it, alternated with the call in the same run on the same stream:
 two yuv420p tensors from xgpu_pic_output_device and per plane the SSE, the number of differing samples and the largest difference in torch (int32 temporaries;
 no SSIM: torch cannot make it exactly).  The split between the two kernels is what rocprofv3 --kernel-trace --stats shows for `--legs compare`.
+The stats leg (xgpu_pic_stats: k_stats, k_stats_light, k_stats_finish behind a memset) takes the statistics of three contents - uniform random, constant, a smooth
+gradient with +-2 codes of noise: the contention of the LDS histogram depends on the content - in four forms: the census alone, with 2^8 and 2^B bins, and with
+the light level.  Each is timed as the other legs are (the median of --iters calls queued behind a wait) and, alternated with it from an idle device, the torch
+route: a yuv420p tensor, then bincount, sum, min and max per plane; with light the u16 RGB tensor, amax, bincount and a gather through lin.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|residual|compare] [--out out/output_device.json]
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|residual|compare|stats] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -337,6 +341,97 @@ def compare_leg(torch, dec, pic, s, a, res, copy_gbps):
     dec.pic_free(other)
 
 
+def stats_contents(rng, w, h, bd):
+    """the three contents of the stats leg - the contention of the LDS histogram differs between them: uniform random samples, one value everywhere, and a
+    smooth diagonal gradient with +-2 codes of noise (chroma: around the middle)"""
+    top = (1 << bd) - 1
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.int32)
+    grad = ((yy + xx) * top // (h + w - 2) + rng.integers(-2, 3, (h, w))).clip(0, top).astype(np.int16)
+    gc = [((1 << (bd - 1)) + (xx[:h // 2, :w // 2] - w // 4) * (top // 4) // w + rng.integers(-2, 3, (h // 2, w // 2))).clip(0, top).astype(np.int16) for _ in range(2)]
+    return {"random": [rng.integers(0, 1 << bd, (h >> k, w >> k)).astype(np.int16) for k in (0, 1, 1)],
+            "constant": [np.full((h >> k, w >> k), v, np.int16) for k, v in zip((0, 1, 1), (3 << (bd - 3), 1 << (bd - 1), 1 << (bd - 1)))],
+            "gradient": [grad] + gc}
+
+
+def stats_leg(torch, dec, pic, s, a, res, copy_gbps):
+    """xgpu_pic_stats - census only, with 2^8 and 2^B bins, with the light level - on three contents, against the copy-rate time of the picture and against the
+    torch route (a yuv420p tensor, then bincount, sum, min and max per plane; with light the u16 RGB tensor, amax, bincount and a gather through lin), alternated"""
+    from xevd_amd import abi
+    w, h, bd = a.width, a.height, a.bit_depth
+    nbytes = 3 * w * h
+    floor_us = nbytes / (copy_gbps * 1e9) * 1e6
+    light = dict(transfer=16, matrix=9)
+    lin = torch.from_numpy(abi.stats_lin(dec.lib, 16, bd)).to("cuda:0")
+    forms = [("census", dict(hist_bits=0), "census"), ("hist_8", dict(hist_bits=8), "hist"), (f"hist_{bd}", dict(hist_bits=bd), "hist"),
+             (f"hist_{bd}_light", dict(hist_bits=bd, light=light), "light")]
+    out = torch.empty(22, dtype=torch.int64, device="cuda:0")
+    yuv = dec.pic_output_tensor(pic, layout="yuv420p", dtype=torch.int16)
+    rgb = dec.pic_output_tensor(pic, layout="rgb", dtype=torch.int16, matrix=9)
+    bounds = (0, w * h, w * h * 5 // 4, w * h * 3 // 2)
+
+    def route(kind):
+        if kind == "light":
+            dec.pic_output_tensor(pic, layout="rgb", dtype=torch.int16, matrix=9, out=rgb)
+            m = rgb.amax(dim=0).reshape(-1).to(torch.int64)
+            return torch.bincount(m, minlength=1 << bd), m.max(), lin[m].sum(dtype=torch.float64)
+        dec.pic_output_tensor(pic, layout="yuv420p", dtype=torch.int16, out=yuv)
+        r = []
+        for k in range(3):
+            pl = yuv[bounds[k]:bounds[k + 1]]
+            r.append((torch.bincount(pl.to(torch.int64), minlength=1 << bd) if kind == "hist" else None, pl.sum(dtype=torch.int64), pl.min(), pl.max()))
+        return r
+
+    res["stats"] = {"bytes": nbytes, "copy_rate_us": round(floor_us, 2), "contents": {}}
+    for cname, planes in stats_contents(np.random.default_rng(4), w, h, bd).items():
+        dec.pic_upload(pic, planes)
+        rc = res["stats"]["contents"][cname] = {"forms": {}, "torch": {}}
+        n = max(a.iters // 4, 5)
+        for kind in ("census", "hist", "light"):      # the torch routes, each from an idle device
+            for _ in range(2):
+                route(kind)
+            t = []
+            for _ in range(n):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record(s)
+                route(kind)
+                e1.record(s)
+                torch.cuda.synchronize()
+                t.append(e0.elapsed_time(e1) * 1e3)
+            rc["torch"][kind + "_us"] = round(float(np.median(t)), 2)
+        for name, kw, kind in forms:
+            def call():
+                return dec.pic_stats(pic, out=out, sync=False, **kw)
+            for _ in range(5):
+                call()
+            alt = []
+            for _ in range(n):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()      # from an idle device, as the torch route: the launch latency is inside
+                e0.record(s)
+                call()
+                e1.record(s)
+                torch.cuda.synchronize()
+                alt.append(e0.elapsed_time(e1) * 1e3)
+            r = {"us": round(timed(torch, s, call, a.iters), 2), "alternated_us": round(float(np.median(alt)), 2)}
+            r["gbps"] = round(nbytes / (r["us"] * 1e-6) / 1e9, 1)
+            r["frac_copy"] = round(floor_us / r["us"], 3)
+            r["torch_route_us"] = rc["torch"][kind + "_us"]
+            r["torch_route_over_call"] = round(r["torch_route_us"] / r["alternated_us"], 2)
+            if kind == "hist":
+                _, hist, _ = call()
+                r["torch_route_agrees"] = bool(all(torch.equal(t[0][:hist.shape[1]] if kw["hist_bits"] == bd else t[0].view(hist.shape[1], -1).sum(1), hist[k].to(torch.int64))
+                                                   for k, t in enumerate(route("hist"))))
+            if kind == "light":
+                _, _, lh = call()
+                d = abi.stats_result_dict(out.cpu().numpy())
+                th, tm, tsum = route("light")
+                r["torch_route_agrees"] = bool(torch.equal(th, lh.to(torch.int64)) and int(tm) == d["light_max_code"] and abs(float(tsum) - d["light_sum"]) <= 1e-9 * d["light_sum"])
+            print(f"stats {cname:9s} {name:18s} {r['us']:9.1f} us  {r['gbps']:7.1f} GB/s  copy-rate time {floor_us:7.1f} us ({r['frac_copy']:.2f})   from idle {r['alternated_us']:9.1f} us, "
+                  f"torch route {r['torch_route_us']:9.1f} us ({r['torch_route_over_call']:.1f}x)")
+            rc["forms"][name] = r
+
+
 def abi_dict(t):
     from xevd_amd import abi
     return abi.compare_result_dict(t.cpu().numpy())
@@ -350,9 +445,10 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "residual", "compare"), default="all",
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "residual", "compare", "stats"), default="all",
                     help="full: the full-size forms and the side information; scaled: the scaled leg alone; rois: the batched regions of interest alone; "
-                         "rois_dev: the regions of interest from boxes in device memory alone; residual: the residual export alone; compare: the picture comparison alone")
+                         "rois_dev: the regions of interest from boxes in device memory alone; residual: the residual export alone; compare: the picture comparison alone; "
+                         "stats: the picture statistics alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -396,6 +492,9 @@ def main():
             residual_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "compare"):
             compare_leg(torch, dec, pic, s, a, res, copy_gbps)
+        if a.legs in ("all", "stats"):
+            stats_leg(torch, dec, pic, s, a, res, copy_gbps)
+            dec.pic_upload(pic, planes)      # (the leg uploads its contents into the slot)
         if a.legs in ("all", "full"):
             for name, kw, wbytes in forms:
                 out = dec.pic_output_tensor(pic, **kw)

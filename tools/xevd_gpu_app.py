@@ -101,6 +101,26 @@ class RefCompare:
         sys.stdout.flush()
 
 
+def stats_options(p):
+    """stats= of StreamDecoder for --stats: the defaults of XgpuDecoder.pic_stats, and the light level where the stream's VUI names a transfer characteristic
+    the library knows"""
+    from xevd_amd import abi
+    col = p["colour"]
+    return {"light": bool(col["vui_present"]) and col["transfer_characteristics"] in abi.STATS_TRANSFERS}
+
+
+def stats_line(p):
+    """one picture's line of --stats: POC, then per component n, min, max, mean and the two percentiles, then - where it was taken - the light level: the highest
+    code of max(R', G', B') and its linear light, the two percentiles' linear light, the mean linear light"""
+    d = p["stats"]
+    parts = [f"POC {p['poc']}"]
+    for c, name in enumerate("YUV"):
+        parts.append(f"{name} n {d['n'][c]} min {d['min'][c]} max {d['max'][c]} mean {d['mean'][c]:.4f} pctl {d['pctl'][c][0]} {d['pctl'][c][1]}")
+    if d["light_hist"] is not None:
+        parts.append(f"light max {d['light_max_code']} {d['light_max']:.6f} pctl {d['light_pctl'][0]:.6f} {d['light_pctl'][1]:.6f} mean {d['light_mean']:.6f}")
+    return "  ".join(parts)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-i", "--input", required=True)
@@ -114,6 +134,9 @@ def main():
                     "'POC h_scu w_scu', then nine planes of h_scu x w_scu little-endian int16 (list 0 / 1 vectors, POC distances, mode, QP, flags: INTEGRATION.md 8c)")
     ap.add_argument("--residual", default=None, metavar="FILE", help="also write the prediction residual of every picture, in DECODING order: a text line "
                     "'POC w h', then the little-endian int16 planes Y (h x w), Cb, Cr (h/2 x w/2 each) of the uncropped picture (INTEGRATION.md 8g)")
+    ap.add_argument("--stats", default=None, metavar="FILE", help="also write the statistics of every picture, taken on the device (INTEGRATION.md 8i), in DECODING order: "
+                    "one text line 'POC p  Y n N min A max B mean M pctl P1 P99.99  U ...  V ...' of the uncropped picture, and 'light max CODE L pctl L1 L2 mean LM' "
+                    "(linear light, 0 .. 1) when the stream's VUI gives a transfer characteristic")
     ap.add_argument("--size", default=None, metavar="WxH", help="write interleaved 8-bit RGB frames resized to W x H on the device instead (antialiased bilinear, "
                     "the matrix / range / chroma siting of the stream's VUI: INTEGRATION.md 8d); with --to: not supported")
     ap.add_argument("--tiles", default=None, metavar="WxH", help="with --size: every picture as its grid of W x H tiles (the last column / row moved back inside the "
@@ -135,6 +158,7 @@ def main():
     t0 = time.perf_counter()
     side = {} if args.side_info else None
     resid = {} if args.residual else None
+    stats = stats_options if args.stats else None
     # crop-free output like the reference application; bit-depth conversion and plane packing run on the device (xgpu_pic_output)
     if args.size is not None:
         import torch
@@ -152,16 +176,16 @@ def main():
             except ValueError:
                 ap.error(f"--tiles: expected WxH, not {args.tiles!r}")
             rois = lambda p: abi.tile_rois(p["width"], p["height"], tw, th)      # noqa: E731
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois, residual=resid, compare=cmp)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois, residual=resid, compare=cmp, stats=stats)
     elif args.to is not None:
         import torch
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats)
     elif args.pix_fmt == "yuv420p":
-        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side, residual=resid, compare=cmp)
+        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side, residual=resid, compare=cmp, stats=stats)
     else:      # the same pictures as semi-planar surfaces (xgpu_pic_output_device into a torch tensor, copied to the host picture by picture)
         import torch
         opts = dict(layout="nv12", dtype=torch.uint8) if args.pix_fmt == "nv12" else dict(layout="p016", dtype=torch.int16, out_bit_depth=10)
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid, compare=cmp)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid, compare=cmp, stats=stats)
     dt = time.perf_counter() - t0
     if cmp is not None:
         cmp.finish()
@@ -181,6 +205,10 @@ def main():
                 flat, (y, _, _) = p["residual"]
                 f.write(f"{p['poc']} {y.shape[1]} {y.shape[0]}\n".encode())
                 f.write(flat.astype("<i2").tobytes())
+    if args.stats:
+        with open(args.stats, "w") as f:
+            for p, _ in sorted(pics, key=lambda t: t[0]["decode_index"]):
+                f.write(stats_line(p) + "\n")
     print(f"{len(pics)} pictures, {len(pics) / dt:.1f} pictures/s (parse + upload + kernels + download)", file=sys.stderr)
 
 

@@ -150,6 +150,61 @@ def ssim(result):
     return [q / (n * float(1 << 30)) if n else float("nan") for q, n in zip(d["ssim_q30"], d["ssim_windows"])]
 
 
+class StatsParams(C.Structure):
+    _fields_ = [("crop", C.c_int * 4), ("hist_bits", C.c_int), ("pctl_e4", C.c_int * 2), ("light", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int),
+                ("chroma_loc", C.c_int), ("upsample", C.c_int), ("transfer", C.c_int)]
+
+
+class StatsResult(C.Structure):
+    """xgpu_stats_result: 176 bytes, written by the device"""
+    _fields_ = [("n", C.c_uint64 * 3), ("sum", C.c_uint64 * 3), ("sum_sq", C.c_uint64 * 3), ("min", C.c_uint32 * 3), ("max", C.c_uint32 * 3),
+                ("pctl", (C.c_uint32 * 2) * 3), ("light_n", C.c_uint64), ("light_sum", C.c_double), ("light_mean", C.c_double),
+                ("light_max_code", C.c_uint32), ("light_pctl_code", C.c_uint32 * 2), ("reserved", C.c_uint32),
+                ("light_max", C.c_float), ("light_pctl", C.c_float * 2), ("reserved2", C.c_float)]
+
+
+STATS_TRANSFERS = (1, 4, 5, 6, 8, 13, 14, 15, 16, 18)      # the H.273 TransferCharacteristics xgpu_stats_lin knows (xgpu_colour_transform's list)
+
+
+def make_stats_params(crop=(0, 0, 0, 0), hist_bits=8, pctl_e4=(100, 9999), light=False, matrix=1, full_range=False, chroma_loc=0, upsample=UPSAMPLE_LINEAR,
+                      transfer=1):
+    """xgpu_stats_params (include/xevd_hip.h): the crop, 2^hist_bits bins per component (0: none), two percentiles in 1 / 10000; light: also the histogram of
+    max(R', G', B') and the light level, with the matrix / range / chroma siting / upsampling of xgpu_output_format and the stream's transfer characteristic"""
+    p = StatsParams()
+    for i in range(4):
+        p.crop[i] = int(crop[i])
+    p.hist_bits, p.light = int(hist_bits), int(light)
+    p.pctl_e4[0], p.pctl_e4[1] = int(pctl_e4[0]), int(pctl_e4[1])
+    p.matrix, p.full_range, p.chroma_loc, p.upsample, p.transfer = int(matrix), int(full_range), int(chroma_loc), int(upsample), int(transfer)
+    return p
+
+
+def stats_result_dict(res):
+    """a StatsResult, or its 176 bytes as anything numpy reads -> dict: n, sum, sum_sq, min, max as lists of three Python ints, pctl as three pairs, the light
+    fields as ints and floats (light_sum, light_mean: float64; light_max, light_pctl: the float32 values)"""
+    if not isinstance(res, StatsResult):
+        res = StatsResult.from_buffer_copy(np.ascontiguousarray(res).tobytes())
+    d = {k: [int(v) for v in getattr(res, k)] for k in ("n", "sum", "sum_sq", "min", "max")}
+    d["pctl"] = [[int(v) for v in row] for row in res.pctl]
+    d.update(light_n=int(res.light_n), light_sum=float(res.light_sum), light_mean=float(res.light_mean), light_max_code=int(res.light_max_code),
+             light_pctl_code=[int(v) for v in res.light_pctl_code], light_max=float(res.light_max), light_pctl=[float(v) for v in res.light_pctl])
+    return d
+
+
+def stats_moments(d):
+    """host only: ([Y, Cb, Cr] mean, [Y, Cb, Cr] population variance) of a stats result's integers as exact fractions.Fraction (float() them as needed)"""
+    from fractions import Fraction
+    mean = [Fraction(s, n) for s, n in zip(d["sum"], d["n"])]
+    return mean, [Fraction(q, n) - m * m for q, n, m in zip(d["sum_sq"], d["n"], mean)]
+
+
+def stats_lin(lib, transfer, bit_depth):
+    """xgpu_stats_lin as a float32 array of 2^bit_depth entries, or the negative code"""
+    buf = (C.c_float * 4096)()
+    rc = lib.xgpu_stats_lin(int(transfer), int(bit_depth), buf)
+    return rc if rc < 0 else np.frombuffer(buf, np.float32, 1 << int(bit_depth)).copy()
+
+
 SCALE_BILINEAR, SCALE_AREA = 0, 1
 
 
@@ -504,6 +559,10 @@ _EXPORTS = {
     "xgpu_compare_map_size": (C.c_size_t, [C.POINTER(CompareParams), C.c_int, C.c_int]),
     "xgpu_compare_check": (C.c_int, [C.POINTER(CompareRef), C.POINTER(CompareParams), C.c_int, C.c_int, C.c_int]),
     "xgpu_pic_compare": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(CompareRef), C.POINTER(CompareParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_stats_hist_size": (C.c_size_t, [C.POINTER(StatsParams), C.c_int]),
+    "xgpu_stats_check": (C.c_int, [C.POINTER(StatsParams), C.c_int, C.c_int, C.c_int]),
+    "xgpu_stats_lin": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "xgpu_pic_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(StatsParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "xgpu_host_free": (None, [C.c_void_p, C.c_void_p]),
     "xgpu_batch_wait_upload": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1,4 +1,4 @@
-// output_common.h - what the output kernels share (k_output.hip, k_output_rgb.hip, k_output_yuv.hip): the per-sample depth conversion and DRA
+// output_common.h - what the output kernels share (k_output.hip, k_output_rgb.hip, k_output_yuv.hip; k_stats.hip's light pass): the per-sample depth conversion and DRA
 // mapping, the edge-clamped chroma loads and the 4:2:0 -> luma-resolution upsampling of the device-output contract (INTEGRATION.md section 8a,
 // step 2), the element types and the vector / element stores.  One version of each: a layout that is "the same samples, another place" runs
 // the same code.
@@ -137,19 +137,13 @@ __device__ static __forceinline__ void apply(const RgbOutArgs &a, int y, int cb,
 }
 };
 
-// The body of the kernels that write three channels at luma resolution (k_output_rgb, k_output_yuv444): one lane makes 8 horizontal pixels of the
-// two luma rows that share chroma row i.  Load, edge clamp, DRA and upsampling are here, once; CONV::apply turns one pixel's (Y, Cb, Cr) at the
-// coding depth into the bits of three output elements.  PLANAR: three planes a.plane bytes apart, else the three elements of a pixel side by side.
-template <bool PLANAR, int DT, int UP, class CONV>
-__device__ __forceinline__ void output_three_channels(const RgbOutArgs &a)
+// The pixels of one lane of the kernels that work at luma resolution (k_output_rgb, k_output_yuv444; k_stats' light pass): 8 horizontal pixels from x0 of the
+// two luma rows that share chroma row i (x0 < a.w, i < a.ch).  Load, edge clamp, DRA and upsampling are here, once; CONV::apply turns one pixel's (Y, Cb, Cr) at
+// the coding depth into the bits of three output elements; sink(row, ch) takes the 3 x 8 elements of luma row `row` (those past the picture's width too).
+template <int UP, class CONV, class SINK>
+__device__ __forceinline__ void three_channel_rows(const RgbOutArgs &a, int x0, int i, SINK &&sink)
 {
-    constexpr int SZ = OutT<DT>::size;
-    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8;
-    const int i = blockIdx.y * 4 + threadIdx.y;
-    if (x0 >= a.w || i >= a.ch) return;
     const int j0 = x0 >> 1;
-    const int n = min(8, a.w - x0);               // pixels of this lane in the row (even)
-    const bool vec = a.aligned && n == 8;
 
     // chroma, vertically interpolated per row parity: cv[c][parity][k], columns j0-1+k
     int cv[2][2][6];
@@ -191,6 +185,22 @@ __device__ __forceinline__ void output_three_channels(const RgbOutArgs &a)
             }
             CONV::apply(a, y, cc[0], cc[1], ch[0][m], ch[1][m], ch[2][m]);
         }
+        sink(row, ch);
+    }
+}
+
+// The body of the kernels that write three channels at luma resolution (k_output_rgb, k_output_yuv444): one lane makes the pixels of three_channel_rows and
+// stores them.  PLANAR: three planes a.plane bytes apart, else the three elements of a pixel side by side.
+template <bool PLANAR, int DT, int UP, class CONV>
+__device__ __forceinline__ void output_three_channels(const RgbOutArgs &a)
+{
+    constexpr int SZ = OutT<DT>::size;
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8;
+    const int i = blockIdx.y * 4 + threadIdx.y;
+    if (x0 >= a.w || i >= a.ch) return;
+    const int n = min(8, a.w - x0);               // pixels of this lane in the row (even)
+    const bool vec = a.aligned && n == 8;
+    three_channel_rows<UP, CONV>(a, x0, i, [&](int row, uint32_t (&ch)[3][8]) {
         if (a.bgr) {
             #pragma unroll
             for (int m = 0; m < 8; m++) { const uint32_t t = ch[0][m]; ch[0][m] = ch[2][m]; ch[2][m] = t; }
@@ -205,7 +215,7 @@ __device__ __forceinline__ void output_three_channels(const RgbOutArgs &a)
             for (int m = 0; m < 8; m++) { e[3 * m] = ch[0][m]; e[3 * m + 1] = ch[1][m]; e[3 * m + 2] = ch[2][m]; }
             store_run<24, SZ>(a.dst + (size_t)row * a.pitch + (size_t)x0 * 3 * SZ, e, vec, 3 * n);
         }
-    }
+    });
 }
 
 // The launch of a kernel family built on output_three_channels: 64 lanes x 4 chroma rows per workgroup, the instance picked by layout, dtype and

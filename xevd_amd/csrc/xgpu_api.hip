@@ -130,7 +130,7 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
     for (int i = 0; i < 2; i++) { c->d_out[i] = NULL; c->out_caps[i] = 0; c->out_ready[i] = c->out_done[i] = 0; c->out_busy[i] = 0; }
     c->d_md5 = NULL; c->md5_ready = 0;
     c->odev_ev[0] = c->odev_ev[1] = 0;
-    c->sc_tab = NULL; c->sc_tab_cap = 0; c->sc_mid = NULL; c->sc_mid_cap = 0; c->cmp_part = NULL; c->cmp_part_cap = 0;
+    c->sc_tab = NULL; c->sc_tab_cap = 0; c->sc_mid = NULL; c->sc_mid_cap = 0; c->cmp_part = NULL; c->cmp_part_cap = 0; c->stats_blk = NULL; c->stats_lin_tc = c->stats_lin_bd = -1;
     c->roi_blk = NULL; c->roi_blk_cap = 0;
     for (int i = 0; i < 6; i++) c->sc_key[i] = -1;
     c->out_next = 0;
@@ -218,6 +218,7 @@ void xgpu_close(xgpu_ctx *c)
     if (c->sc_tab) (void)hipFree(c->sc_tab);
     if (c->sc_mid) (void)hipFree(c->sc_mid);
     if (c->cmp_part) (void)hipFree(c->cmp_part);
+    if (c->stats_blk) (void)hipFree(c->stats_blk);
     if (c->roi_blk) (void)hipFree(c->roi_blk);
     if (c->d_ctb_flag) (void)hipFree(c->d_ctb_flag);
     for (auto &e : c->ev_pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }

@@ -1,4 +1,4 @@
-// xgpu_colour.hip - host side of the colour-managed RGB output (xgpu_colour_tables, include/xevd_hip.h): the transfer characteristics of H.273 / BT.2100,
+// xgpu_colour.hip - host side of the colour-managed RGB output (xgpu_colour_tables, include/xevd_hip.h) and of the light level (xgpu_stats_lin): the transfer characteristics of H.273 / BT.2100,
 // the primaries matrices from the H.273 chromaticities, the BT.2390 EETF and the tables k_output_cm.hip reads.  Everything in double precision, rounded
 // to float32 once; no device code.  tests/colour_cm_ref.py states the same formulae in numpy float64 and compares entry by entry.
 #include "xgpu_internal.h"
@@ -121,7 +121,26 @@ float curve_x(int j)      // the sample point of entry j + 1
     return x;
 }
 
+// step 1's table at coding depth bd: linear light of the code k, k = 0 .. 2^bd - 1 (xgpu_colour_tables and xgpu_stats_lin: one construction)
+void make_lin(int cls, int bit_depth, float *lin)
+{
+    const int n = 1 << bit_depth;
+    const double maxv = (double)(n - 1);
+    for (int k = 0; k < n; k++) lin[k] = (float)tc_inverse(cls, (double)k / maxv);
+}
+
 }      // namespace
+
+bool colour_transfer_supported(int tc) { return transfer_class(tc) != 0; }
+int xgpu_stats_lin(int transfer, int bit_depth, float lin[4096])
+{
+    if (!lin || bit_depth < 8 || bit_depth > 12) return XGPU_ERR_INVALID_ARGUMENT;
+    const int cls = transfer_class(transfer);
+    if (!cls) return XGPU_ERR_UNSUPPORTED;
+    memset(lin, 0, sizeof(float) * 4096);
+    make_lin(cls, bit_depth, lin);
+    return XGPU_OK;
+}
 
 int xgpu_colour_tables(const xgpu_output_format *f, const xgpu_colour_transform *cm, int bit_depth, xgpu_colour_tables_t *out)
 {
@@ -141,8 +160,7 @@ int xgpu_colour_tables(const xgpu_output_format *f, const xgpu_colour_transform 
 
     memset(out, 0, sizeof(*out));
     out->n_lin = 1 << bit_depth;
-    const double maxv = (double)(out->n_lin - 1);
-    for (int k = 0; k < out->n_lin; k++) out->lin[k] = (float)tc_inverse(sc, (double)k / maxv);
+    make_lin(sc, bit_depth, out->lin);
 
     double s2x[9], d2x[9], x2d[9];
     rgb_to_xyz(sxy, s2x);

@@ -366,6 +366,11 @@ struct xgpu_ctx {
     size_t          sc_mid_cap;
     unsigned long long *cmp_part;     // xgpu_pic_compare: the workgroups' partial sums of the current call (cmp_part_cap bytes, grown on demand), ordered like sc_mid
     size_t          cmp_part_cap;
+    // xgpu_pic_stats: one block of STATS_BLK_BYTES, allocated at the first call and ordered like sc_mid - the accumulation block of the histograms (zeroed on
+    // the call's stream before its kernels), the lin table of (stats_lin_tc, stats_lin_bd) (-1: none; uploaded again only when they change) and the workgroups'
+    // partial sums of the current call
+    uint8_t        *stats_blk;
+    int             stats_lin_tc, stats_lin_bd;
     uint8_t        *roi_blk;          // xgpu_pic_output_device_rois: the descriptors and tap tables of the current call (its intermediate is sc_mid), ordered like sc_tab
     size_t          roi_blk_cap;
     hipEvent_t      odev_ev[2];       // xgpu_pic_output_device on a caller's stream: picture ready on the context stream / the caller's kernel done (created at the first call)
@@ -607,6 +612,34 @@ struct CompareArgs {
 #define CMP_PART_WORDS 8            // n, sse, n_diff, first_diff, windows, q, max_abs, (unused)
 int  compare_workgroups(int tiles);                 // the workgroups launch_compare starts for that many tiles
 void launch_compare(const CompareArgs &a, hipStream_t s);
+// k_stats.hip: the statistics of one picture (xgpu_pic_stats)
+#define STATS_MAX_BINS       4096   // 2^12: the bins of one histogram at most
+#define STATS_MAX_WORKGROUPS 1024   // 4 per CU: twice as many were slower with a histogram to flush
+#define STATS_PART_WORDS     8      // n, sum, sum_sq, min, max, (unused)
+#define STATS_ACC_BYTES      ((size_t)4 * STATS_MAX_BINS * sizeof(uint32_t))      // [3][nbins] and the light histogram
+#define STATS_LIN_BYTES      ((size_t)STATS_MAX_BINS * sizeof(float))
+#define STATS_PART_BYTES     ((size_t)STATS_MAX_WORKGROUPS * 3 * STATS_PART_WORDS * sizeof(unsigned long long))
+#define STATS_BLK_BYTES      (STATS_ACC_BYTES + STATS_LIN_BYTES + STATS_PART_BYTES)
+struct StatsArgs {
+    const uint16_t *a[3];           // first sample of the cropped area of every plane
+    int      sa[3];                 // its strides in samples
+    int      vec[3];                // the plane's cropped base and pitch allow the 16-byte loads
+    int      w[3], h[3];            // cropped size of every plane
+    int      tiles_x[3];            // 64x32 tiles per row of tiles
+    int      tile_first[4];         // tiles of plane c: tile_first[c] .. tile_first[c + 1]
+    int      bd, hist_bits;         // the coding depth; 0: no histogram
+    int      pctl_e4[2];
+    int      light;
+    RgbOutArgs rgb;                 // light: the U16 planar conversion of xgpu_pic_output_device (dst, pitch, plane, aligned are not read)
+    int      upsample;
+    uint32_t *acc;                  // the accumulation block: [3][2^hist_bits], then [2^bd] (zero before the launch)
+    const float *lin;               // light: [2^bd]
+    unsigned long long *part;       // [workgroups][3][STATS_PART_WORDS]
+    xgpu_stats_result *res;
+    uint32_t *hist;                 // the caller's, laid out like acc
+};
+void launch_stats(const StatsArgs &a, hipStream_t s);
+bool colour_transfer_supported(int tc);      // xgpu_colour.hip: a TransferCharacteristics code point of xgpu_colour_transform's list
 void launch_md5(xgpu_ctx *c, hipStream_t s, const uint8_t *d_msg, int w, int h, uint32_t *d_digest);      // k_md5.hip: the three planes packed back to back at d_msg -> d_digest[3][4]
 void launch_test_mc(xgpu_ctx *c, const int16_t *plane, int stride, int ref_x, int ref_y, int has_dx, int has_dy,
                     int gmv_x, int gmv_y, int16_t *pred, int w, int h, int bd, int luma);

@@ -1,8 +1,8 @@
 // xgpu_output.hip - the C ABI of include/xevd_hip.h, part 2: the outputs into device memory - the picture as it is, colour-managed, scaled, as a batch of regions of
-// interest (rectangles from the host or boxes in device memory), the coding side information, the residual and the comparison with a reference - and their
-// argument checks without a device.
+// interest (rectangles from the host or boxes in device memory), the coding side information, the residual, the comparison with a reference and the statistics
+// of one picture - and their argument checks without a device.
 // Every entry point is the same skeleton: check the format -> check_dst -> (check_dra; tables, made on the host) -> grow a context buffer -> out_fork -> fill an args struct ->
-// launch -> out_join.  Host-side code only; the kernels live in k_output*.hip, k_side_info.hip, k_residual.hip and k_compare.hip.
+// launch -> out_join.  Host-side code only; the kernels live in k_output*.hip, k_side_info.hip, k_residual.hip, k_compare.hip and k_stats.hip.
 #include "xgpu_host.h"
 #include "scale_taps.h"
 #include <memory>
@@ -285,6 +285,14 @@ static void fill_conversion(xgpu_ctx *c, const xgpu_dra_luts *dra, const xgpu_ou
         a.fcoef[0] = (float)(1.0 / yr); a.fcoef[1] = (float)(1.0 / crr);      // rounded once from double
     }
 }
+// ChromaSampleLocType: horizontally co-sited (0, 2, 4) / centred (1, 3, 5); vertically centred (0, 1), top (2, 3), bottom (4, 5)
+static void fill_siting(int chroma_loc, RgbOutArgs &a)
+{
+    static const int ve[3][2] = { { 1, 3 }, { 0, 4 }, { 2, 2 } }, vo[3][2] = { { 3, 1 }, { 2, 2 }, { 4, 0 } };
+    a.hc = chroma_loc & 1;
+    a.ve[0] = ve[chroma_loc >> 1][0]; a.ve[1] = ve[chroma_loc >> 1][1];
+    a.vo[0] = vo[chroma_loc >> 1][0]; a.vo[1] = vo[chroma_loc >> 1][1];
+}
 static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream);
 int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, void *d_dst, size_t dst_size, void *stream)
 {
@@ -358,11 +366,7 @@ static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const x
         a.dst = (uint8_t *)d_dst;
         fill_rows(a, d_dst, image_row(f, w), h, f->row_pitch);
         fill_conversion(c, dra, f, a);
-        // ChromaSampleLocType: horizontally co-sited (0, 2, 4) / centred (1, 3, 5); vertically centred (0, 1), top (2, 3), bottom (4, 5)
-        static const int ve[3][2] = { { 1, 3 }, { 0, 4 }, { 2, 2 } }, vo[3][2] = { { 3, 1 }, { 2, 2 }, { 4, 0 } };
-        a.hc = f->chroma_loc & 1;
-        a.ve[0] = ve[f->chroma_loc >> 1][0]; a.ve[1] = ve[f->chroma_loc >> 1][1];
-        a.vo[0] = vo[f->chroma_loc >> 1][0]; a.vo[1] = vo[f->chroma_loc >> 1][1];
+        fill_siting(f->chroma_loc, a);
         if (cm) {
             CmOutArgs ca;
             static_cast<RgbOutArgs &>(ca) = a;
@@ -1101,4 +1105,132 @@ int xgpu_pic_compare(xgpu_ctx *c, int pic, const xgpu_compare_ref *ref, const xg
     a.part = c->cmp_part; a.res = d_result; a.map = d_map; a.mw = (w + 15) / 16; a.mh = (h + 15) / 16;
     launch_compare(a, s);
     return out_join(c, stream, s);      // both slots, before the next picture's kernels may write them; the partial sums, before the next call's
+}
+
+// ------------------------------------------------------------------------------------------------ the statistics of one picture
+// the parameters at coding depth bd, without a picture size: 0 or a negative code - every XGPU_ERR_INVALID_ARGUMENT before XGPU_ERR_UNSUPPORTED -, `why` says which field
+static int stats_params_check(const xgpu_stats_params *p, int bd, const char **why)
+{
+    *why = "parameters are NULL";
+    if (!p) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "bit depth out of range";
+    if (bd < 8 || bd > 12) return XGPU_ERR_INVALID_ARGUMENT;
+    if (!crop_ok(p->crop, 0, 0, why)) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "hist_bits must be 0 or 4 .. the coding depth";
+    if (p->hist_bits != 0 && (p->hist_bits < 4 || p->hist_bits > bd)) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "light: 0 or 1";
+    if (p->light & ~1) return XGPU_ERR_INVALID_ARGUMENT;
+    if (p->hist_bits || p->light) {
+        *why = "pctl_e4: 0 .. 10000";
+        for (int i = 0; i < 2; i++) if (p->pctl_e4[i] < 0 || p->pctl_e4[i] > 10000) return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    if (!p->light) return XGPU_OK;
+    *why = "light: full_range 0 or 1; chroma_loc 0..5; upsample XGPU_UPSAMPLE_NEAREST or _LINEAR";
+    if ((p->full_range & ~1) || p->chroma_loc < 0 || p->chroma_loc > 5 || (p->upsample != XGPU_UPSAMPLE_NEAREST && p->upsample != XGPU_UPSAMPLE_LINEAR))
+        return XGPU_ERR_INVALID_ARGUMENT;
+    double kr, kb;
+    *why = "light: matrix: supported MatrixCoefficients are 1, 4, 5, 6, 7 and 9";
+    if (!matrix_kr_kb(p->matrix, &kr, &kb)) return XGPU_ERR_UNSUPPORTED;
+    *why = "light: transfer: supported TransferCharacteristics are 1, 4, 5, 6, 8, 13, 14, 15, 16 and 18";
+    if (!colour_transfer_supported(p->transfer)) return XGPU_ERR_UNSUPPORTED;
+    return XGPU_OK;
+}
+static size_t stats_hist_size(const xgpu_stats_params *p, int bd)
+{
+    return ((p->hist_bits ? (size_t)3 << p->hist_bits : 0) + (p->light ? (size_t)1 << bd : 0)) * sizeof(uint32_t);
+}
+size_t xgpu_stats_hist_size(const xgpu_stats_params *p, int bit_depth)
+{
+    const char *why;
+    return stats_params_check(p, bit_depth, &why) < 0 ? 0 : stats_hist_size(p, bit_depth);
+}
+static int stats_check(const xgpu_stats_params *p, int width, int height, int bd, const char **why)
+{
+    *why = "parameters are NULL";
+    if (!p) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "picture size must be positive and even, width * height below 2^31";
+    if (width <= 0 || height <= 0 || ((width | height) & 1) || (long long)width * height >= (1ll << 31)) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "bit depth out of range";
+    if (bd < 8 || bd > 12) return XGPU_ERR_INVALID_ARGUMENT;
+    if (!crop_ok(p->crop, width, height, why)) return XGPU_ERR_INVALID_ARGUMENT;
+    return stats_params_check(p, bd, why);
+}
+int xgpu_stats_check(const xgpu_stats_params *p, int width, int height, int bit_depth)
+{
+    const char *why;
+    return stats_check(p, width, height, bit_depth, &why);
+}
+// Checks first, then the order of xgpu_pic_compare.  What the call rewrites of the context's - the accumulation block, the lin table, the partial sums - is
+// queued between out_fork and out_join, behind every earlier call that read them.
+int xgpu_pic_stats(xgpu_ctx *c, int pic, const xgpu_stats_params *p, xgpu_stats_result *d_result, uint32_t *d_hist, size_t hist_size, void *stream)
+{
+    static const char who[] = "pic_stats";
+    ARGCHK(c, c != NULL); ARGCHK(c, d_result != NULL);
+    const char *why = "";
+    const int bd = c->sp.bit_depth_luma;
+    const int rc = stats_check(p, c->sp.width, c->sp.height, bd, &why);
+    if (rc < 0) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return rc; }
+    if (c->have_frame || !valid_pic(c, pic)) {
+        snprintf(c->err, sizeof(c->err), "%s: %s", who, c->have_frame ? "a frame is open: take the statistics after xgpu_frame_end" : "the slot holds no picture");
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    TRY(check_dst(c, "pic_stats: result", d_result, sizeof(xgpu_stats_result), sizeof(xgpu_stats_result), 8));
+    const size_t hist_need = stats_hist_size(p, bd);
+    if (hist_need) {
+        ARGCHK(c, d_hist != NULL);
+        TRY(check_dst(c, "pic_stats: histogram", d_hist, hist_size, hist_need, 4));
+    }
+    float lin[STATS_MAX_BINS];
+    const bool new_lin = p->light && (c->stats_lin_tc != p->transfer || c->stats_lin_bd != bd);
+    if (new_lin) TRY(xgpu_stats_lin(p->transfer, bd, lin));      // (cannot fail: the check has passed)
+    if (!c->stats_blk && hipMalloc((void **)&c->stats_blk, STATS_BLK_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(c->err, sizeof(c->err), "%s: cannot allocate the %zu-byte block of the context", who, (size_t)STATS_BLK_BYTES);
+        return XGPU_ERR_OUT_OF_MEMORY;
+    }
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    StatsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.acc = (uint32_t *)c->stats_blk;
+    a.lin = (const float *)(c->stats_blk + STATS_ACC_BYTES);
+    a.part = (unsigned long long *)(c->stats_blk + STATS_ACC_BYTES + STATS_LIN_BYTES);
+    if (new_lin) {      // behind the fork: after every kernel that read the previous table; no key names the table until the copy is queued (upload_cm's rule)
+        c->stats_lin_tc = c->stats_lin_bd = -1;
+        HIPCHK(c, hipMemcpyAsync(c->stats_blk + STATS_ACC_BYTES, lin, sizeof(float) << bd, hipMemcpyHostToDevice, s));
+        c->stats_lin_tc = p->transfer; c->stats_lin_bd = bd;
+    }
+    const int *cr = p->crop;
+    const int w = c->sp.width - cr[0] - cr[1], h = c->sp.height - cr[2] - cr[3];
+    const DevPic &dp = dpic(c, pic);
+    const int16_t *pl[3];
+    cropped_planes(dp, cr, &pl[0], &pl[1], &pl[2]);
+    int tiles = 0;
+    for (int k = 0; k < 3; k++) {
+        a.a[k] = (const uint16_t *)pl[k]; a.sa[k] = k ? dp.s_c : dp.s_l;
+        a.w[k] = k ? w >> 1 : w; a.h[k] = k ? h >> 1 : h;
+        a.vec[k] = aligned16((uintptr_t)a.a[k] | ((size_t)a.sa[k] * 2));
+        a.tiles_x[k] = (a.w[k] + 63) / 64;
+        a.tile_first[k] = tiles;
+        tiles += a.tiles_x[k] * ((a.h[k] + 31) / 32);
+    }
+    a.tile_first[3] = tiles;
+    a.bd = bd; a.hist_bits = p->hist_bits; a.pctl_e4[0] = p->pctl_e4[0]; a.pctl_e4[1] = p->pctl_e4[1];
+    a.light = p->light;
+    if (p->light) {      // the arguments of xgpu_pic_output_device for XGPU_OUT_RGB_PLANAR, XGPU_OUT_U16 without DRA
+        xgpu_output_format f;
+        memset(&f, 0, sizeof(f));
+        f.layout = XGPU_OUT_RGB_PLANAR; f.dtype = XGPU_OUT_U16;
+        f.matrix = p->matrix; f.full_range = p->full_range; f.chroma_loc = p->chroma_loc; f.upsample = p->upsample;
+        RgbOutArgs &r = a.rgb;
+        r.y = pl[0]; r.u = pl[1]; r.v = pl[2];
+        r.sy = dp.s_l; r.sc = dp.s_c;
+        r.w = w; r.h = h; r.cw = w >> 1; r.ch = h >> 1;
+        fill_conversion(c, NULL, &f, r);
+        fill_siting(p->chroma_loc, r);
+        a.upsample = p->upsample;
+    }
+    a.res = d_result; a.hist = d_hist;
+    launch_stats(a, s);
+    return out_join(c, stream, s);      // the slot, before the next picture's kernels may write it; the context's block, before the next call's
 }

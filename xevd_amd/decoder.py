@@ -541,6 +541,51 @@ class XgpuDecoder:
         d["map"] = bmap if block_map else None
         return d
 
+    def pic_stats(self, pic, crop=(0, 0, 0, 0), hist_bits=8, percentiles=(100, 9999), light=None, out=None, sync=True):
+        """What is in slot `pic`, taken on the device in one pass on torch's current stream (xgpu_pic_stats): per component Y, Cb, Cr
+        the number of samples, their sum, sum of squares, minimum and maximum, a histogram of 2^hist_bits bins (0: none; else 4 .. the coding depth) and the
+        two `percentiles` of it (in 1 / 10000: the lower edge of the bin that holds them).  crop (left, right, top, bottom), even.
+        light=dict(transfer=, matrix=1, full_range=False, chroma_loc=0, upsample="linear"): also the histogram of max(R', G', B') of every pixel - the codes
+        pic_output_tensor(layout="rgb", dtype=torch.uint16) makes with those options - and the light level under the stream's transfer characteristic (H.273).
+        sync=True: a dict - n, sum, sum_sq, min, max as lists of three Python ints, pctl as three pairs, mean and var (population variance) as lists of three
+        floats (abi.stats_moments has the exact fractions), hist: an int32 tensor [3, 2^hist_bits] on the device or None; and light_hist: an int32 tensor [2^B]
+        or None, light_n, light_max_code, light_pctl_code, light_max, light_pctl (linear light of those codes, 0 .. 1), light_sum, light_mean - all 0 without
+        light= -, and for transfer 16 (PQ) max_cll and max_fall, this picture's contributions in cd/m2.
+        sync=False: nothing is read back - (result, hist, light_hist): the raw result, an int64 tensor of 22 words laid out as xgpu_stats_result
+        (abi.stats_result_dict reads it), and the two histograms or None.  out: a tensor to take the raw result."""
+        import torch
+        dev = torch.device("cuda", self.sp.device)
+        kw = {}
+        if light is not None:
+            kw = dict(light)
+            if "transfer" not in kw:
+                raise ValueError("light: needs transfer= (H.273 TransferCharacteristics of the stream)")
+            up = kw.pop("upsample", "linear")
+            if up not in ("nearest", "linear"):
+                raise ValueError(f"light: upsample must be 'nearest' or 'linear', not {up!r}")
+            kw["upsample"] = abi.UPSAMPLE_NEAREST if up == "nearest" else abi.UPSAMPLE_LINEAR
+            if set(kw) - {"transfer", "matrix", "full_range", "chroma_loc", "upsample"}:
+                raise ValueError(f"light: unknown option in {sorted(kw)}")
+        p = abi.make_stats_params(crop, hist_bits, percentiles, light is not None, **kw)
+        res = _out_tensor(out, (C.sizeof(abi.StatsResult) // 8,), torch.int64, dev)
+        if res.stride() != (1,):
+            raise ValueError("out: must be contiguous")
+        nb, nl = (1 << int(hist_bits) if hist_bits else 0), (1 << self.bit_depth if light is not None else 0)
+        words = self.lib.xgpu_stats_hist_size(C.byref(p), self.bit_depth) // 4      # (invalid parameters: 0 - no memory, and the call says what is wrong)
+        flat = torch.empty((words,), dtype=torch.int32, device=dev)
+        self._device_call("xgpu_pic_stats", flat, pic, C.byref(p), C.c_void_p(res.data_ptr()))
+        hist = flat[:3 * nb].view(3, nb) if nb else None
+        lhist = flat[3 * nb:] if nl else None
+        if not sync:
+            return res, hist, lhist
+        d = abi.stats_result_dict(res.cpu().numpy())
+        mean, var = abi.stats_moments(d)
+        d["mean"], d["var"] = [float(m) for m in mean], [float(v) for v in var]
+        d["hist"], d["light_hist"] = hist, lhist
+        if light is not None and int(kw["transfer"]) == 16:
+            d["max_cll"], d["max_fall"] = 10000.0 * d["light_max"], 10000.0 * d["light_mean"]
+        return d
+
     def pic_md5(self, pic, dra=None):
         """the picture signature made on the device (xgpu_pic_md5): [Y, U, V] digests of 16 bytes - the MD5 of every plane's 16-bit samples as the reference's
         xevd_md5_imgb makes it; with `dra` tables (as pic_output takes them) of the DRA-mapped picture"""

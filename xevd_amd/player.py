@@ -75,6 +75,20 @@ class StreamDecoder:
         kw.update(options)
         return kw
 
+    @classmethod
+    def light_options(cls, colour, options=None):
+        """the `light=` argument of XgpuDecoder.pic_stats for a stream whose VUI says `colour` (params["colour"]): matrix, range and chroma siting as
+        tensor_options takes them, the transfer characteristic as colour_transform does (a VUI that leaves it unspecified, or none: BT.709) - `options`
+        (a dict, or True / None for none) override all"""
+        kw = cls.tensor_options({"colour": colour, "dra": None}, {})
+        del kw["dra"]
+        kw["transfer"] = 1
+        if colour["vui_present"] and colour["transfer_characteristics"] != 2:
+            kw["transfer"] = colour["transfer_characteristics"]
+        if isinstance(options, dict):
+            kw.update(options)
+        return kw
+
     # `to=` presets: (ColourPrimaries, TransferCharacteristics) of the output (H.273; transfer 8 = linear light)
     COLOUR_PRESETS = {"srgb": (1, 13), "bt709": (1, 1), "linear-bt709": (1, 8), "bt2020": (9, 14), "linear-bt2020": (9, 8), "pq-bt2020": (9, 16),
                       "hlg-bt2020": (9, 18), "p3-d65": (12, 13), "linear-p3-d65": (12, 8)}
@@ -102,7 +116,7 @@ class StreamDecoder:
         return cm
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
-                 residual=None, compare=None):
+                 residual=None, compare=None, stats=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -125,7 +139,11 @@ class StreamDecoder:
         compare=callable(params) -> a reference or None, or a sequence of such indexed in decoding order (shorter: the pictures past its end are not
         compared): every picture against its reference on the device (XgpuDecoder.pic_compare: a tensor in pic_output's plane order on the decoder's device; a
         dict(ref=..., ssim=..., block_map=...) passes pic_compare's other arguments), taken right behind the picture's kernels; the result - pic_compare's
-        dict - under params["compare"], None where there was no reference.  The crop defaults to the SPS crop when apply_crop is set"""
+        dict - under params["compare"], None where there was no reference.  The crop defaults to the SPS crop when apply_crop is set
+        stats=dict(...) (keyword arguments of XgpuDecoder.pic_stats, {} for the defaults) or a callable(params) -> such a dict or None: the statistics of every
+        picture - census, histograms, percentiles - under params["stats"] (pic_stats' dict; with sync=False its tuple of device tensors), taken right behind the
+        picture's kernels.  light=True or light=dict(...) in it adds the light level with the matrix, range, chroma siting and transfer characteristic of the
+        stream's VUI (light_options; the dict overrides them).  The crop defaults to the SPS crop when apply_crop is set"""
         if to is not None and tensor is None:
             raise ValueError("to: needs tensor=dict(...)")
         if (size is not None or mean is not None or std is not None) and tensor is None:
@@ -167,6 +185,17 @@ class StreamDecoder:
                         kw = dict(ref) if isinstance(ref, dict) else {"ref": ref}
                         kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
                         p["compare"] = dec.pic_compare(cur, **kw)
+                if stats is not None:
+                    kw = stats(p) if callable(stats) else stats
+                    p["stats"] = None
+                    if kw is not None:
+                        kw = dict(kw)
+                        kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
+                        if kw.get("light"):      # True or a dict: on top of the VUI's colour description
+                            kw["light"] = self.light_options(p["colour"], kw["light"])
+                        elif "light" in kw:
+                            kw["light"] = None
+                        p["stats"] = dec.pic_stats(cur, **kw)
                 n_decoded[0] += 1
                 if p["n_dmvr_sub"]:
                     p["_dmvr"][1] = dec.batch_dmvr_mvs(hb)
@@ -234,15 +263,15 @@ class StreamDecoder:
                 self._dec = None
 
     def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
-                     compare=None):
+                     compare=None, stats=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
         params["residual"] as numpy - for kind "yuv420" the pair (flat array, (Y, Cb, Cr) views of it); compare= (as pictures takes it, the callable and the
-        sequence in DECODING order): params["compare"], its map as a numpy array"""
+        sequence in DECODING order): params["compare"], its map as a numpy array; stats= (as pictures takes it): params["stats"], its histograms as numpy arrays"""
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
-                                       residual=residual, compare=compare):
+                                       residual=residual, compare=compare, stats=stats):
             if p["is_idr"]:
                 epoch += 1
             if tensor is not None:
@@ -261,6 +290,10 @@ class StreamDecoder:
                 p["residual"] = r
             if compare is not None and p["compare"] is not None and p["compare"]["map"] is not None:
                 p["compare"]["map"] = p["compare"]["map"].cpu().numpy()
+            if stats is not None and isinstance(p["stats"], dict):
+                for k in ("hist", "light_hist"):
+                    if p["stats"][k] is not None:
+                        p["stats"][k] = p["stats"][k].cpu().numpy()
             p["decode_index"] = len(out)       # place in decoding order
             out.append(((epoch, p["poc"]), p, planes))
         return [(p, planes) for _, p, planes in sorted(out, key=lambda t: t[0])]
