@@ -719,6 +719,16 @@ static uint8_t *tile_map(const xgpu_tile_grid *g, int w_scu, int h_scu)
         }
     return t;
 }
+/* census of one neighbour unit: `in` - its SCU k lies inside the picture -, `ok` - it is read from the picture */
+static void cen_nbr_unit(const orc_maps *m, int base, int side, int chroma, int i, int ok, int in, int scup, int k)
+{
+    g_cen.ip_nbr[base][side][chroma][ok ? 0 : (i > 0 ? 1 : 2)]++;
+    if (ok) return;
+    if (!in) g_cen.ip_unavail[0]++;
+    else if (!MCU_COD(m->map_scu[k])) g_cen.ip_unavail[1]++;
+    else if (!TILE_SAME(m, scup, k)) g_cen.ip_unavail[2]++;
+    else g_cen.ip_unavail[3]++;      /* reconstructed, in the tile: constrained intra prediction refused it */
+}
 static void intra_neighbours(const xgpu_seq_params *sp, const orc_maps *m, const int16_t *src, int s, int x_scu, int y_scu,
                              int cw, int ch, int unit, int constrained, int16_t *up, int16_t *left)
 {
@@ -726,14 +736,18 @@ static void intra_neighbours(const xgpu_seq_params *sp, const orc_maps *m, const
     const int16_t mid = (int16_t)(1 << (sp->bit_depth_luma - 1));
     int i, j;
 #define NB_OK(k) (MCU_COD(m->map_scu[k]) && (!constrained || MCU_IF(m->map_scu[k])) && TILE_SAME(m, scup, k))
-    up[-1] = (x_scu > 0 && y_scu > 0 && NB_OK(scup - ws - 1)) ? src[-s - 1] : mid;      /* AVAIL_UP_LE, xevd_util.c:722-725 */
+    const int ul_ok = x_scu > 0 && y_scu > 0 && NB_OK(scup - ws - 1);
+    up[-1] = ul_ok ? src[-s - 1] : mid;      /* AVAIL_UP_LE, xevd_util.c:722-725 */
+    g_cen.ip_corner[ul_ok ? 0 : 2]++;
     for (i = 0; i < scuw + scuh; i++) {
-        const int ok = y_scu > 0 && x_scu + i < ws && NB_OK(scup - ws + i);
+        const int in = y_scu > 0 && x_scu + i < ws, ok = in && NB_OK(scup - ws + i);
         for (j = 0; j < unit; j++) up[i * unit + j] = ok ? src[-s + i * unit + j] : mid;
+        cen_nbr_unit(m, 1, 0, unit == 2, i, ok, in, scup, scup - ws + i);
     }
     for (i = 0; i < scuh + scuw; i++) {
-        const int ok = x_scu > 0 && y_scu + i < m->h_scu && NB_OK(scup - 1 + i * ws);
+        const int in = x_scu > 0 && y_scu + i < m->h_scu, ok = in && NB_OK(scup - 1 + i * ws);
         for (j = 0; j < unit; j++) left[i * unit + j] = ok ? src[(i * unit + j) * s - 1] : mid;
+        cen_nbr_unit(m, 1, 1, unit == 2, i, ok, in, scup, scup - 1 + i * ws);
     }
     left[-1] = up[-1];
 #undef NB_OK
@@ -780,20 +794,24 @@ static void intra_neighbours_eipd(const xgpu_seq_params *sp, const orc_maps *m, 
     const int ul_ok = x_scu > 0 && y_scu > 0 && NB_OK(scup - ws - 1);
     up[-1] = ul_ok ? src[-s - 1] : (int16_t)(1 << (sp->bit_depth_luma - 1));      /* the mid value only feeds the repetition below */
     for (i = 0; i < scuw + scuh; i++) {
-        const int ok = y_scu > 0 && x_scu + i < ws && NB_OK(scup - ws + i);
+        const int in = y_scu > 0 && x_scu + i < ws, ok = in && NB_OK(scup - ws + i);
         for (j = 0; j < unit; j++) up[i * unit + j] = ok ? src[-s + i * unit + j] : up[i * unit - 1];
+        cen_nbr_unit(m, 0, 0, unit == 2, i, ok, in, scup, scup - ws + i);
+        if (i == 0) g_cen.ip_corner[ul_ok ? 0 : (ok ? 1 : 2)]++;
     }
     if (!ul_ok) up[-1] = up[0];                      /* :80-99: the part left of up[0] repeats up[0] when its unit is unavailable */
     left[-1] = up[-1];
     for (i = 0; i < scuh + scuw; i++) {
-        const int ok = x_scu > 0 && y_scu + i < m->h_scu && NB_OK(scup - 1 + i * ws);
+        const int in = x_scu > 0 && y_scu + i < m->h_scu, ok = in && NB_OK(scup - 1 + i * ws);
         for (j = 0; j < unit; j++) left[i * unit + j] = ok ? src[(i * unit + j) * s - 1] : left[i * unit - 1];
+        cen_nbr_unit(m, 0, 1, unit == 2, i, ok, in, scup, scup - 1 + i * ws);
     }
     /* the column right of the block (:123-147): decoded before the block only where SUCO runs a split right to left; starts from the sample above it */
     right[-1] = up[cw];
     for (i = 0; i < scuh + scuw; i++) {
-        const int ok = x_scu + scuw < ws && y_scu + i < m->h_scu && NB_OK(scup + scuw + i * ws);
+        const int in = x_scu + scuw < ws && y_scu + i < m->h_scu, ok = in && NB_OK(scup + scuw + i * ws);
         for (j = 0; j < unit; j++) right[i * unit + j] = ok ? src[(i * unit + j) * s + cw] : right[i * unit - 1];
+        cen_nbr_unit(m, 0, 2, unit == 2, i, ok, in, scup, scup + scuw + i * ws);
     }
 #undef NB_OK
 }
@@ -855,6 +873,12 @@ static int ang_sample(const int16_t *left, const int16_t *up, const int16_t *rig
 #define CL(v) ((v) < -1 ? -1 : ((v) > hi ? hi : (v)))
         const int v = (int16_t)((ref[CL(p - dir)] * (32 - o) + ref[CL(p)] * (64 - o) + ref[CL(p + dir)] * (32 + o) + ref[CL(p + 2 * dir)] * o + 64) >> 7);
 #undef CL
+        const int p_lo = dir > 0 ? p - 1 : p - 2, p_hi = dir > 0 ? p + 2 : p + 1;      /* the four taps span p - dir .. p + 2 dir */
+        g_cen.ip_ang_src[mode < 12 ? 0 : (mode > 24 ? 2 : 1)][ref == up ? 0 : (ref == left ? 1 : 2)]++;
+        g_cen.ip_ang_frac[o != 0]++;
+        if (p_lo < -1) g_cen.ip_ang_clamp[0]++;
+        if (p_hi > hi) g_cen.ip_ang_clamp[1]++;
+        CEN_CLIP(ip_ang_clip, v, maxv);
         return v < 0 ? 0 : (v > maxv ? maxv : v);
     }
 }
@@ -866,6 +890,7 @@ static void intra_predict_eipd(const int16_t *left, const int16_t *up, const int
     int i, j;
     if (mode == 12) { for (j = 0; j < h; j++) for (i = 0; i < w; i++) dst[j * w + i] = up[i]; return; }            /* xevd_ipred_vert */
     if (mode == 24) {                                                                                           /* xevdm_ipred_hor :153-196 */
+        g_cen.ip_hor[lr == 3 ? 2 : (lr == 2 ? 1 : 0)]++;
         for (j = 0; j < h; j++) for (i = 0; i < w; i++)
             dst[j * w + i] = lr == 3 ? (int16_t)(((left[j] * (w - i) + right[j] * (i + 1) + (w >> 1)) * k_inv_size[lw]) >> 12) : (lr == 2 ? right[j] : left[j]);
         return;
@@ -876,6 +901,7 @@ static void intra_predict_eipd(const int16_t *left, const int16_t *up, const int
         if (lr & 2) for (j = 0; j < h; j++) dc += right[j];
         for (i = 0; i < w; i++) dc += up[i];
         if (lr == 3) { hh = h << 1; lhh = lh + 1; }                       /* both columns: the mean over w + 2h samples */
+        g_cen.ip_dc[lr == 3][lw > lhh ? lw - lhh : lhh - lw]++;
         dc = ((dc + ((w + hh) >> 1)) * k_inv_size[lw > lhh ? lw - lhh : lhh - lw]) >> ((lw < lhh ? lw : lhh) + 12);
         for (i = 0; i < w * h; i++) dst[i] = (int16_t)dc;
         return;
@@ -884,6 +910,7 @@ static void intra_predict_eipd(const int16_t *left, const int16_t *up, const int
         static const int mult[6] = { 13, 17, 5, 11, 23, 47 }, shift[6] = { 7, 10, 11, 15, 19, 23 };
         const int w2 = w >> 1, h2 = h >> 1, iw = lw < 2 ? 0 : lw - 2, ih = lh < 2 ? 0 : lh - 2;
         int ch_ = 0, cv = 0, a, b, c, base;
+        g_cen.ip_plan[(lr & 2) != 0][iw][ih]++;
         if (lr & 2) {                                /* a right column: the mirror image - gradients towards the left, anchored at the bottom-right and top-left samples */
             for (i = 1; i <= w2; i++) ch_ += i * (up[w2 - i] - up[w2 + i]);
             for (j = 1; j <= h2; j++) cv += j * (right[h2 - 1 + j] - right[h2 - 1 - j]);
@@ -898,12 +925,14 @@ static void intra_predict_eipd(const int16_t *left, const int16_t *up, const int
         base = a - (h2 - 1) * c - (w2 - 1) * b + 16;
         for (j = 0; j < h; j++) for (i = 0; i < w; i++) {
             const int v = (base + j * c + ((lr & 2) ? w - 1 - i : i) * b) >> 5;
+            CEN_CLIP(ip_plan_clip, v, maxv);
             dst[j * w + i] = (int16_t)(v < 0 ? 0 : (v > maxv ? maxv : v));
         }
         return;
     }
     if (mode == 2) {                                                                                            /* xevd_ipred_bi :251-369 */
         static const int wc_tbl[6] = { -1, 341, 205, 114, 60, 31 };
+        g_cen.ip_bi_form[lr == 3 ? 2 : (lr == 2 ? 1 : 0)]++;
         if (lr == 3) {                               /* both columns: rows interpolated between them, then towards the bottom row of that from the row above */
             for (j = 0; j < h; j++) for (i = 0; i < w; i++) {
                 const int row = ((left[j] * (w - i) + right[j] * (i + 1) + (w >> 1)) * k_inv_size[lw]) >> 12;
@@ -919,11 +948,14 @@ static void intra_predict_eipd(const int16_t *left, const int16_t *up, const int
             const int a = lr == 2 ? up[-1] : up[w], b = col[h], ms = lw < lh ? lw : lh;
             const int c = w == h ? (a + b + 1) >> 1 : (((a << lw) + (b << lh)) * wc_tbl[lw > lh ? lw - lh : lh - lw] + (1 << (ms + 9))) >> (ms + 10);
             const int wt = (c << 1) - a - b;
+            g_cen.ip_bi_corner[lr == 2][w != h]++;
+            if (w != h) g_cen.ip_bi_wc[lw > lh ? lw - lh : lh - lw]++;
             for (j = 0; j < h; j++) for (i = 0; i < w; i++) {
                 const int k = lr == 2 ? w - 1 - i : i;          /* distance from the column */
                 const int px = (col[j] << lw) + (k + 1) * (a - col[j]);
                 const int py = (up[i] << lh) + (j + 1) * (b - up[i]);
                 const int v = ((px << lh) + (py << lw) + k * j * wt + (1 << (lw + lh))) >> (lw + lh + 1);
+                CEN_CLIP(ip_bi_clip, v, maxv);
                 dst[j * w + i] = (int16_t)(v < 0 ? 0 : (v > maxv ? maxv : v));
             }
         }
@@ -1454,6 +1486,21 @@ int orc_recon_batch_ex(const xgpu_seq_params *sp, const orc_frame *fr, const xgp
         else if (maps) {      /* xevd_recon_unit's intra branch, xevd.c:731-741 (availability needs the SCU map) */
             int16_t nb_up[2 * MAX_CU + 8], nb_le[2 * MAX_CU + 8], nb_ri[2 * MAX_CU + 8];
             const int lr = avail_lr_of(maps, x >> 2, y >> 2, w >> 2);
+            {      /* census: the CU by shape, tree and cbf; its modes */
+                const int ml = b->ipm ? b->ipm[i * 2] : 0, mc = b->ipm ? b->ipm[i * 2 + 1] : 0;
+                if (lw >= 2 && lw <= 7 && lh >= 2 && lh <= 7) g_cen.ip_shape[sp->tool_eipd ? 1 : 0][lw - 2][lh - 2]++;
+                g_cen.ip_tree[planes == 3 ? 0 : (planes == 1 ? 1 : 2)]++;
+                g_cen.ip_cbf[b->cbf[i] & 7]++;
+                /* (a mode out of range - a batch is data - is not counted: the arrays end at 33 / 5) */
+                if (sp->tool_eipd) {
+                    if ((planes & 1) && ml < 33) { g_cen.ip_mode_lr[ml][lr]++; g_cen.ip_mode_aspect[ml][w > h ? 0 : (w == h ? 1 : 2)]++; }
+                    if ((planes & 2) && mc < 5) { g_cen.ip_cmode_lr[mc][lr]++; if (mc == 0 && ml < 33) g_cen.ip_dm_luma[ml]++; }
+                } else {
+                    if ((planes & 1) && ml < 5) g_cen.ip_base_mode[0][ml]++;
+                    if ((planes & 2) && mc < 5) g_cen.ip_base_mode[1][mc]++;
+                    if (planes == 3 && mc != ml) g_cen.ip_base_c_differs++;
+                }
+            }
             if (b->constrained_intra_pred && (planes & 1)) {      /* census: IBC CUs next to an intra CU that may only read intra neighbours */
                 int u, le = 0, up = 0;
                 for (u = 0; u < h >> 2 && x > 0; u++) le |= scu_kind[((y >> 2) + u) * maps->w_scu + (x >> 2) - 1] & ORC_K_IBC;

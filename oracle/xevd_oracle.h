@@ -192,6 +192,34 @@ typedef struct orc_census {
     uint32_t ibc_src_kind[4];                          /* the source holds samples of intra / IBC / HTDF-filtered / inter CUs (one CU may count in several) */
     uint32_t ibc_touch[2];                             /* the source ends exactly at the CU's own left / top edge */
     uint32_t ibc_nbr_of_cintra[2];                     /* intra CUs under constrained intra prediction with an IBC CU along their left / upper side */
+    /* intra prediction (intra_neighbours / intra_neighbours_eipd, intra_predict / intra_predict_eipd, ang_sample and the intra branch of orc_recon_batch_ex; needs maps).
+       [lr]: avail_lr 0 .. 3.  [side]: 0 up, 1 left, 2 right.  [plane class]: 0 luma, 1 chroma.  Predictor counters are per predicted block (each plane is one), the
+       angular ones per sample, the neighbour ones per unit of 4 luma / 2 chroma samples */
+    uint32_t ip_shape[2][6][6];                        /* intra CUs by [Baseline / EIPD][log2w - 2][log2h - 2] */
+    uint32_t ip_mode_lr[33][4];                        /* EIPD CUs with luma by [luma mode][lr] */
+    uint32_t ip_mode_aspect[33][3];                    /* ... by [luma mode][wide / square / tall] */
+    uint32_t ip_cmode_lr[5][4];                        /* EIPD CUs with chroma by [chroma mode][lr] */
+    uint32_t ip_dm_luma[33];                           /* ... of chroma mode 0 (DM) by the luma mode it resolved to */
+    uint32_t ip_base_mode[2][5];                       /* Baseline CUs by [luma / chroma][mode] */
+    uint32_t ip_base_c_differs;                        /* Baseline CUs (all planes) whose chroma mode differs from the luma mode */
+    uint32_t ip_dc[2][8];                              /* EIPD DC blocks by [lr != 3 / lr == 3][index into the 4096 / (2^k + 1) table] */
+    uint32_t ip_plan[2][6][6];                         /* planar blocks by [left form / mirrored right form][iw][ih] (indices into mult / shift) */
+    uint32_t ip_plan_clip[2];                          /* planar samples clipped */
+    uint32_t ip_bi_form[3];                            /* bilinear blocks: left column / lr == 2 (mirrored) / lr == 3 (both columns) */
+    uint32_t ip_bi_corner[2][2];                       /* one-column bilinear blocks by [left / lr == 2][square: (a + b + 1) >> 1 / not square: wc_tbl] */
+    uint32_t ip_bi_wc[6];                              /* ... by the wc_tbl index 1 .. 5 ([0] stays empty) */
+    uint32_t ip_bi_clip[2];                            /* one-column bilinear samples clipped */
+    uint32_t ip_hor[3];                                /* mode 24 blocks: from the left column (lr 0 / 1) / from the right one (lr 2) / interpolated between the two (lr 3) */
+    uint32_t ip_ang_src[3][3];                         /* angular samples by [mode < 12 / 13 .. 23 / > 24][reference read from up / left / right] */
+    uint32_t ip_ang_frac[2];                           /* ... fraction o == 0 / o != 0 */
+    uint32_t ip_ang_clamp[2];                          /* ... with a tap position clamped at -1 / at w + h - 1 */
+    uint32_t ip_ang_clip[2];                           /* ... clipped at the end */
+    uint32_t ip_nbr[2][3][2][3];                       /* neighbour units by [EIPD builder / Baseline builder][side][plane class][available / unavailable behind an earlier unit: the
+                                                          sample before it repeated (Baseline: mid) / unavailable first unit: up takes the corner or mid, left the corner, right up[w] (Baseline: mid)] */
+    uint32_t ip_unavail[4];                            /* unavailable units by reason: outside the picture / not reconstructed yet / in another tile / refused by constrained intra prediction */
+    uint32_t ip_corner[3];                             /* the corner sample: available / not, takes up[0] read from the picture (EIPD) / not, takes mid (EIPD: up[0] unavailable as well; Baseline) */
+    uint32_t ip_tree[3];                               /* intra CUs by tree: 0 / luma only / chroma only */
+    uint32_t ip_cbf[8];                                /* intra CUs by cbf */
 } orc_census;
 void orc_census_reset(void);
 void orc_census_get(orc_census *out);

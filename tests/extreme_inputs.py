@@ -12,6 +12,8 @@ coefficients, so the kernels' packed 16-bit arithmetic, clamps and table tops ar
     with every CU shape of 8 .. 128 a side (`affine_partition`),
   * for HTDF and intra block copy: partitions with every CU shape of 4 .. 128 a side in every order a split tree decodes them in, right to left included, and local dual
     trees (`htdf_partition`); block vectors of every parity and sign into sources over many CUs, inside filtered CUs and inside other copies (`set_ibc_vectors`),
+  * for intra prediction: modes assigned without a draw on those partitions, so that every predictor meets every shape and every avail_lr it has a form for (`set_intra_modes`,
+    with avail_lr restated from batch order: `intra_avail_lr`),
 and `apply` puts them into a case that cases.build_case has built (tools={"extreme": {...}}).  What each of them is FOR is asserted
 through the oracle's census (oracle_lib.census) in tests/test_oracle_extremes.py.
 """
@@ -689,15 +691,18 @@ def _tile_order(px, py, pw, ph, bw, bh, mode):
     return [(x, y) for x in cols for y in rows] if mode in (1, 2) else [(x, y) for y in rows for x in cols]
 
 
-def htdf_partition(w, h, log2_ctu, rot=0, rtl=False, dual=False):
+def htdf_partition(w, h, log2_ctu, rot=0, rtl=False, dual=False, all128=False):
     """affine_partition's sibling for the filter that follows every CU: the picture in cells of 64x64, each holding one shape with a side of 64 or four shapes of at most 32 a
     side (HTDF_CELLS, from entry 4 * rot on), the CUs of a cell (of a quadrant) in one of the orders of _tile_order - which one changes from cell to cell; `rtl` admits the two
-    right-to-left ones, which leave a CU with its right-hand neighbours reconstructed.  With CTU 128 one of four whole CTUs holds a shape with a side of 128 (HTDF_128).  What
+    right-to-left ones, which leave a CU with its right-hand neighbours reconstructed (`rtl` = 'all': only those two).  With CTU 128 one of four whole CTUs - with `all128` every one - holds a shape with a side of 128 (HTDF_128, in turn from entry `rot` on).  What
     is left at the right and at the bottom (8 samples when the size is a multiple of 64 plus 8) is tiled with HTDF_EDGE (transposed along the bottom) from entry `rot` on.
     `dual`: the leaves of 4x16, 16x4, 4x8, 8x4 and 4x4 become luma-only CUs of local dual trees (HTDF_DUAL_NODE).  -> x, y, log2w, log2h, ctu_cu_start, tree"""
     ctu = 1 << log2_ctu
     out, start = [], []
     n_cell = n_ctu = n_edge = big = 0
+
+    def order(k):
+        return 2 + (k & 1) if rtl == "all" else k % (4 if rtl else 2)
 
     def emit(px, py, pw, ph, shape, mode):
         bw, bh = shape
@@ -714,7 +719,7 @@ def htdf_partition(w, h, log2_ctu, rot=0, rtl=False, dual=False):
             start.append(len(out))
             if log2_ctu == 7 and cx + 128 <= w and cy + 128 <= h:
                 n_ctu += 1
-                if (n_ctu - 1) & 3 == rot & 3:
+                if all128 or (n_ctu - 1) & 3 == rot & 3:
                     emit(cx, cy, 128, 128, HTDF_128[(rot + big) % len(HTDF_128)], 0)
                     big += 1
                     continue
@@ -725,16 +730,16 @@ def htdf_partition(w, h, log2_ctu, rot=0, rtl=False, dual=False):
                 iw, ih = min(qx + 64, w) - qx, min(qy + 64, h) - qy
                 if iw == 64 and ih == 64:
                     cell = HTDF_CELLS[(n_cell + 4 * rot) % len(HTDF_CELLS)]
-                    mode = (n_cell + rot) % (4 if rtl else 2)
+                    mode = order(n_cell + rot)
                     n_cell += 1
                     if isinstance(cell[0], int):
                         emit(qx, qy, 64, 64, cell, mode)
                     else:      # quadrants: z-order, mirrored for the right-to-left orders; which shape lies where turns with rot
                         for q in ((1, 0, 3, 2) if mode & 2 else (0, 1, 2, 3)):
-                            emit(qx + (q & 1) * 32, qy + (q >> 1) * 32, 32, 32, cell[(q + rot) % 4], (mode + q) % (4 if rtl else 2))
+                            emit(qx + (q & 1) * 32, qy + (q >> 1) * 32, 32, 32, cell[(q + rot) % 4], order(mode + q))
                     continue
                 cands = [s for s in HTDF_EDGE if iw % s[0] == 0 and ih % s[1] == 0] if iw <= ih else [s[::-1] for s in HTDF_EDGE if iw % s[1] == 0 and ih % s[0] == 0]
-                emit(qx, qy, iw, ih, cands[(n_edge + rot) % len(cands)], (n_edge + rot) % (4 if rtl else 2))
+                emit(qx, qy, iw, ih, cands[(n_edge + rot) % len(cands)], order(n_edge + rot))
                 n_edge += 1
     start.append(len(out))
     a = np.array(out, np.int64)
@@ -742,14 +747,14 @@ def htdf_partition(w, h, log2_ctu, rot=0, rtl=False, dual=False):
 
 
 def regenerate_htdf_batch(case, seed, gen):
-    """Replace the case's batch by one that synth.gen_frame draws on htdf_partition (gen: its keyword arguments + 'rot', 'rtl', 'dual'); the slice QP of the filter and
+    """Replace the case's batch by one that synth.gen_frame draws on htdf_partition (gen: its keyword arguments + 'rot', 'rtl', 'dual', 'all128'); the slice QP of the filter and
     constrained intra prediction are the old batch's"""
     from xevd_amd import synth
     gen = dict(gen)
-    rot, rtl, dual = gen.pop("rot", 0), gen.pop("rtl", False), gen.pop("dual", False)
+    rot, rtl, dual, all128 = gen.pop("rot", 0), gen.pop("rtl", False), gen.pop("dual", False), gen.pop("all128", False)
     old = case["batch"]
     b = synth.gen_frame(np.random.default_rng(seed + 31 * rot), case["w"], case["h"], case["bd"], log2_ctu=case["log2_ctu"], eipd=bool(case["eipd"]),
-                        partition=htdf_partition(case["w"], case["h"], case["log2_ctu"], rot, rtl, dual), **gen)
+                        partition=htdf_partition(case["w"], case["h"], case["log2_ctu"], rot, rtl, dual, all128), **gen)
     # three in four of the square CUs of 32 and 64 are intra (the QP - 8 branch); an inter CU that turns intra keeps its coefficients (there is no ATS-inter here)
     assert b.get("ats_inter") is None
     sq = np.nonzero((b["log2w"] == b["log2h"]) & (b["log2w"] >= 5) & (b["log2w"] <= 6))[0]
@@ -866,6 +871,103 @@ def set_ibc_vectors(batch, kind, w, h, log2_ctu, seed, frac=0.4):
     return batch
 
 
+# ---- intra prediction: modes assigned on purpose (set_intra_modes) on the partitions of htdf_partition.  The branches they are for: oracle/xevd_oracle.c intra_neighbours,
+# intra_neighbours_eipd, intra_predict, intra_predict_eipd, ang_sample and the intra branch of orc_recon_batch_ex, census ip_*.
+def intra_needs(lw, lh, lr):
+    """what the luma predictors whose arithmetic depends on shape and avail_lr ask of a CU, as (mode, key) in the order they are served: DC by [both columns][index into the
+    4096 / (2^k + 1) table], planar by [mirrored][shape] (mult / shift), bilinear by [left / only right / both columns][shape] (wc_tbl, the shifts), horizontal by [left / only right / both columns], and on the narrowest
+    shapes - 4x64, 64x4 - mode 17 per avail_lr: an angular mode between vertical and horizontal, whose references run past the short side at once"""
+    needs = [(0, (lr == 3, abs(lw - lh - (lr == 3)))), (1, (lr & 2, lw, lh)), (2, (2 if lr == 3 else lr & 2, lw, lh))]
+    needs.append((24, (2 if lr == 3 else lr & 2,)))
+    if abs(lw - lh) == 4:
+        needs.append((17, (lr, lw, lh)))
+    return needs
+
+
+def intra_needs_in_turn(lw, lh, lr, seed):
+    """intra_needs from entry `seed` on; a CU with a side of 128 asks for planar first - mult[5] / shift[5] are used by those few CUs alone, often one per picture"""
+    needs = intra_needs(lw, lh, lr)
+    needs = needs[seed % len(needs):] + needs[:seed % len(needs)]
+    return sorted(needs, key=lambda nd: not (nd[0] == 1 and max(lw, lh) == 7))
+
+
+def intra_avail_lr(batch, w, h, log2_ctu=6):
+    """avail_lr of every CU (xevd_check_nev_avail: bit 0 - the SCU left of the CU's first one is reconstructed and in the CU's tile -, bit 1 - the one right of its first row)
+    from batch order and positions alone: a CU is reconstructed when it comes earlier in the batch, and a chroma-only CU leaves the map alone.  The test side's restatement,
+    held to the oracle's census in tests/test_builder.py."""
+    n = len(batch["x"])
+    ws, hs = (w + 3) >> 2, (h + 3) >> 2
+    tree = batch["tree"] if batch.get("tree") is not None else np.zeros(n, np.uint8)
+    tiles = batch.get("tiles")
+    tile_of = np.zeros((hs, ws), np.int64)
+    if tiles is not None:
+        cxs, cys = np.arange(ws) >> (log2_ctu - 2), np.arange(hs) >> (log2_ctu - 2)
+        tile_of = (np.searchsorted(tiles["row_bd"], cys, "right") - 1)[:, None] * (len(tiles["col_bd"]) - 1) + (np.searchsorted(tiles["col_bd"], cxs, "right") - 1)[None, :]
+    done = np.zeros((hs, ws), bool)
+    lr = np.zeros(n, np.uint8)
+    for i in range(n):
+        xs, ys, wu, hu = int(batch["x"][i]) >> 2, int(batch["y"][i]) >> 2, (1 << int(batch["log2w"][i])) >> 2, (1 << int(batch["log2h"][i])) >> 2
+        if xs > 0 and done[ys, xs - 1] and tile_of[ys, xs - 1] == tile_of[ys, xs]:
+            lr[i] |= 1
+        if xs + wu < ws and done[ys, xs + wu] and tile_of[ys, xs + wu] == tile_of[ys, xs]:
+            lr[i] |= 2
+        if tree[i] != 2:
+            done[ys:ys + hu, xs:xs + wu] = True
+    return lr
+
+
+def set_intra_modes(batch, kind, seed, w=None, h=None, log2_ctu=6):
+    """Assign `ipm` of the intra CUs in batch order, deterministically, so that the buckets of the oracle's intra census fill (no draw: the same batch gives the same modes).
+    kind 'eipd' (33 luma / 5 chroma modes): a CU takes the first of intra_needs_in_turn that no CU before it has served; where all are served it takes the mode
+    its avail_lr has met least so far, among those the one its shape class (wide / square / tall) has met least, among those the first from mode 7 * seed + 3 on - so every avail_lr, also
+    the rare ones (2: only a right column, 3: both), and every shape class cycles through all 33 modes, from another start in every case.  The chroma mode cycles 0 .. 4 per
+    luma mode, DM (0) first: DM meets every luma mode.  A chroma-only CU keeps the luma mode its DM refers to and gets its chroma mode from the same cycle.
+    kind 'base' (the five Baseline modes for luma and chroma alike): a cycle per shape; every fourth CU gets a chroma mode that differs from its luma mode."""
+    n = len(batch["x"])
+    if w is None:
+        w, h = int((batch["x"].astype(np.int64) + (1 << batch["log2w"].astype(np.int64))).max()), int((batch["y"].astype(np.int64) + (1 << batch["log2h"].astype(np.int64))).max())
+    lr = intra_avail_lr(batch, w, h, log2_ctu)
+    tree = batch["tree"] if batch.get("tree") is not None else np.zeros(n, np.uint8)
+    ipm = np.array(batch["ipm"], np.uint8).reshape(n, 2).copy()
+    served, by_luma, by_shape = set(), {}, {}
+    met_lr, met_class = np.zeros((33, 4), np.int64), np.zeros((33, 3), np.int64)
+    order = [(m + 7 * seed + 3) % 33 for m in range(33)]
+    k = 0
+    for i in np.nonzero(batch["pred_mode"] == MODE_INTRA)[0]:
+        lw, lh = int(batch["log2w"][i]), int(batch["log2h"][i])
+        if kind == "base":
+            c = by_shape.get((lw, lh), 0)
+            by_shape[(lw, lh)] = c + 1
+            ml = (c + seed) % 5
+            ipm[i] = (ml, ml if k & 3 != 3 else (ml + 1 + (k >> 2) % 4) % 5)
+            k += 1
+            continue
+        if tree[i] != 2:
+            cls = 1 + (lw < lh) - (lw > lh)
+            needs = [nd for nd in intra_needs_in_turn(lw, lh, int(lr[i]), seed) if nd not in served]
+            if needs:
+                ml = needs[0][0]
+                served.add(needs[0])
+            else:
+                ml = min(order, key=lambda m: (met_lr[m, lr[i]], met_class[m, cls]))
+            met_lr[ml, lr[i]] += 1
+            met_class[ml, cls] += 1
+            ipm[i, 0] = ml
+        ml = int(ipm[i, 0])
+        c = by_luma.get(ml, 0)
+        by_luma[ml] = c + 1
+        ipm[i, 1] = c % 5
+    batch["ipm"] = ipm.reshape(np.asarray(batch["ipm"]).shape)
+    return batch
+
+
+def intra_parts(batch, eipd):
+    """the number of list entries k_intra's plan splits an unfiltered intra CU into (xgpu_intra_plan.hip, PartRule): one per 64 units of work, at most 16; a unit is a row of four
+    luma samples with its chroma pair (EIPD) or an SCU (Baseline)"""
+    area = batch["log2w"].astype(np.int64) + batch["log2h"].astype(np.int64)
+    return np.clip((1 << np.maximum(area - 4, 0)) * (4 if eipd else 1) // 64, 1, 16)
+
+
 PER_CU = ("x", "y", "log2w", "log2h", "pred_mode", "refi", "mv", "qp", "cbf", "coef_off", "ipm", "ats", "ats_inter", "affine", "affine_mv", "dmvr", "tree", "cbf_sub")
 
 
@@ -899,8 +1001,9 @@ def apply(case, spec, seed=0):
     """spec: {'content': kind | [kind per reference picture], 'start': kind, 'qp': 'areas', 'mv': 'grid8' | 'small' | 'thresholds' | 'dmvr_mirror' | 'dmvr_zero' | 'dmvr_thresholds',
               'alf': (kind, ctb), 'levels': 'dense', 'tiles': (col_bd, row_bd, across), 'dmvr_pair': kind | [kind of pair 0, of pair 1],
               'partition': synth.gen_frame arguments for a batch on dmvr_partition, 'affine_partition': the same on affine_partition (+ 'rot'),
-              'affine': 'sizes' | 'eif' | 'trans' | 'limits' | 'wide' | 'tall' (set_affine), 'affine_start': the first variant,
-              'htdf_partition': the same on htdf_partition (+ 'rot', 'rtl', 'dual'), 'ibc': (kind of IBC_WANTS, share of the CUs) for set_ibc_vectors }"""
+              'affine': 'sizes' | 'eif' | 'trans' | 'limits' | 'wide' | 'tall' (set_affine), 'affine_start': the first variant, 'intra_start': added to the seed of set_intra_modes,
+              'htdf_partition': the same on htdf_partition (+ 'rot', 'rtl', 'dual', 'all128'), 'ibc': (kind of IBC_WANTS, share of the CUs) for set_ibc_vectors,
+              'intra': 'eipd' | 'base' for set_intra_modes (the modes of the intra CUs, assigned last: tiles and copies are in place) }"""
     w, h, bd = case["w"], case["h"], case["bd"]
     base = 7919 * (seed + 1)
     if spec.get("partition") is not None:
@@ -959,6 +1062,8 @@ def apply(case, spec, seed=0):
         set_tiles(case, *spec["tiles"])
     if spec.get("ibc") is not None:      # (after the tiles: a source must precede its CU in the batch's final order)
         set_ibc_vectors(case["batch"], spec["ibc"][0], w, h, case["log2_ctu"], base + 600, spec["ibc"][1])
+    if spec.get("intra") is not None:
+        set_intra_modes(case["batch"], spec["intra"], seed + int(spec.get("intra_start", 0)), w, h, case["log2_ctu"])
     return case
 
 
@@ -971,6 +1076,7 @@ _DGEN = {"inter_frac": 1.0, "bi_frac": 0.9, "n_refs": (2, 2), "oob_frac": 0.0, "
 _AFF = {"log2_ctu": 7, "inter_frac": 1.0, "oob_frac": 0.0}
 _AGEN = {"inter_frac": 1.0, "bi_frac": 0.5, "n_refs": (2, 2), "oob_frac": 0.0, "admvp": True, "ats_inter_frac": 0.6, "coded_frac": 0.85}
 _HGEN = {"inter_frac": 0.5, "bi_frac": 0.3, "n_refs": (1, 1), "oob_frac": 0.0, "admvp": True, "coded_frac": 0.9}
+_IGEN = {"inter_frac": 0.0, "bi_frac": 0.3, "n_refs": (1, 1), "oob_frac": 0.0, "admvp": True, "coded_frac": 0.6}
 _X_LADDER = {"content": ["ladder", "noise", "rails_dither", "ladder"], "qp": "areas", "mv": "grid8"}
 EXTREME_CASES = [
     # ADDB: QP 0..51 x slice offsets; step ladder / full-range noise / rails; with ALF behind the filter (k_addb_alf) and without (k_addb)
@@ -1074,6 +1180,43 @@ EXTREME_CASES = [
      ("ibc_spread", "ibc_touch")),
     ("x_ibc_chain_cip_12b", 264, 200, 12, 1, 1, (1, 1), 0.3, {"htdf_qp": 40, "constrained_intra": 1, "eipd": 1, "addb": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=12, rtl=True, inter_frac=0.3), "content": "ladder", "start": "noise", "ibc": ("chain", 0.45)}},
      ("ibc_chain", "ibc_cip")),
+    # intra prediction at every predictor and launch branch (set_intra_modes on htdf_partition; the filter is off: "htdf_qp" absent).  EIPD in right-to-left orders (k_intra's
+    # instantiation with the right-column forms), EIPD left to right without and with copies, the Baseline predictors in the Baseline profile and - with copies - in a Main
+    # sequence without EIPD; all-intra pictures (every neighbour is a predicted sample) and pictures mixed with inter CUs on rails / noise references (the planar and bilinear
+    # clips, constrained intra prediction refusing units; x_ip_eipd_rtl_rails_12b: flat references at max and at 0 - a bilinear CU among neighbours at max overshoots it);
+    # residuals of amp 40, and none at all
+    ("x_ip_eipd_rtl_amp40_8b", 264, 264, 8, 1, 1, (1, 1), 0.3, {"eipd": 1, "amp": 40.0, "extreme": {"htdf_partition": dict(_IGEN, rot=0, rtl="all", amp=40.0, coded_frac=0.9), "start": "gratings", "intra": "eipd"}},
+     ("ip_right", "ip_parts_eipd", "ip_clips")),
+    ("x_ip_eipd_rtl_12b_ctu128", 264, 264, 12, 1, 1, (1, 1), 0.3, {"eipd": 1, "log2_ctu": 7, "addb": 1, "extreme": {"htdf_partition": dict(_IGEN, rot=3, rtl=True), "start": "noise", "intra": "eipd", "intra_start": 1}},
+     ("ip_modes", "ip_right", "ip_plan_mirror", "ip_bi_clip", "ip_parts_eipd")),
+    ("x_ip_eipd_rtl_nocoef_10b", 264, 200, 10, 1, 1, (1, 1), 0.3, {"eipd": 1, "extreme": {"htdf_partition": dict(_IGEN, rot=5, rtl="all", coded_frac=0.0), "start": "ladder", "intra": "eipd", "intra_start": 2}},
+     ("ip_right", "ip_nocoef")),
+    ("x_ip_eipd_rtl_cip_rails_10b", 264, 264, 10, 1, 1, (1, 1), 0.3, {"eipd": 1, "constrained_intra": 1, "addb": 1, "alf": 1, "amp": 40.0,
+                                                                  "extreme": {"htdf_partition": dict(_IGEN, rot=7, rtl="all", inter_frac=0.4, amp=40.0, coded_frac=0.9), "content": "rails_dither", "start": "noise", "intra": "eipd", "intra_start": 3}},
+     ("ip_right", "ip_cip")),
+    ("x_ip_eipd_rtl_rails_12b", 264, 200, 12, 1, 1, (1, 1), 0.3, {"eipd": 1, "amp": 40.0, "extreme": {"htdf_partition": dict(_IGEN, rot=10, rtl=True, inter_frac=0.6, amp=40.0, coded_frac=0.5), "content": ["flatmax", "flat0"], "start": "gratings", "intra": "eipd", "intra_start": 4}},
+     ("ip_plan_mirror", "ip_clips", "ip_bi_clip")),
+    ("x_ip_eipd_noise_10b_ctu128", 264, 264, 10, 1, 1, (1, 1), 0.3, {"eipd": 1, "log2_ctu": 7, "addb": 1, "extreme": {"htdf_partition": dict(_IGEN, rot=2, inter_frac=0.4), "content": "noise", "start": "ladder", "intra": "eipd", "intra_start": 5}},
+     ("ip_left_only", "ip_clips")),
+    ("x_ip_eipd_ibc_12b", 264, 200, 12, 1, 1, (1, 1), 0.3, {"eipd": 1, "extreme": {"htdf_partition": dict(_IGEN, rot=4, inter_frac=0.3), "content": "noise", "start": "gratings", "ibc": ("parity", 0.3), "intra": "eipd", "intra_start": 6}},
+     ("ip_left_only", "ip_ibc")),
+    ("x_ip_base_amp40_8b_ctu128", 264, 264, 8, 0, 0, (1, 0), 0.0, {"amp": 40.0, "log2_ctu": 7, "extreme": {"htdf_partition": dict(_IGEN, rot=0, admvp=False, n_refs=(1, 0), amp=40.0, coded_frac=0.9), "start": "noise", "intra": "base"}},
+     ("ip_base", "ip_parts_base")),
+    ("x_ip_base_cip_12b_ctu128", 264, 264, 12, 0, 0, (1, 0), 0.0, {"log2_ctu": 7, "constrained_intra": 1,
+                                                                "extreme": {"htdf_partition": dict(_IGEN, rot=19, admvp=False, n_refs=(1, 0), inter_frac=0.7), "content": "noise", "start": "ladder", "intra": "base", "intra_start": 1}},
+     ("ip_base", "ip_cip", "ip_parts_base")),
+    ("x_ip_base_mixed_10b", 264, 200, 10, 0, 0, (1, 0), 0.0, {"extreme": {"htdf_partition": dict(_IGEN, rot=14, admvp=False, n_refs=(1, 0), inter_frac=0.7), "content": "rails_dither", "start": "gratings", "intra": "base", "intra_start": 2}},
+     ("ip_base",)),
+    ("x_ip_main_noeipd_ibc_10b", 264, 200, 10, 1, 1, (1, 1), 0.3, {"addb": 1, "extreme": {"htdf_partition": dict(_IGEN, rot=9, inter_frac=0.2), "content": "noise", "start": "ladder", "ibc": ("spread", 0.3), "intra": "base", "intra_start": 3}},
+     ("ip_base", "ip_ibc")),
+    # ... and the CUs with a side of 128: every whole CTU of a 264x264 picture holds one shape of HTDF_128 (`all128`), four per picture, all nine under both sets of predictors;
+    # planar first on each (the last entry of its mult / shift tables is theirs alone)
+    ("x_ip_eipd_side128_a_8b", 264, 264, 8, 1, 1, (1, 1), 0.3, {"eipd": 1, "log2_ctu": 7, "extreme": {"htdf_partition": dict(_IGEN, rot=0, all128=True), "start": "noise", "intra": "eipd"}}, ("ip_side128",)),
+    ("x_ip_eipd_side128_b_10b", 264, 264, 10, 1, 1, (1, 1), 0.3, {"eipd": 1, "log2_ctu": 7, "addb": 1, "extreme": {"htdf_partition": dict(_IGEN, rot=4, rtl=True, all128=True), "start": "ladder", "intra": "eipd", "intra_start": 1}}, ("ip_side128",)),
+    ("x_ip_eipd_side128_c_12b", 264, 264, 12, 1, 1, (1, 1), 0.3, {"eipd": 1, "log2_ctu": 7, "amp": 40.0, "extreme": {"htdf_partition": dict(_IGEN, rot=8, all128=True, amp=40.0, coded_frac=0.9), "start": "gratings", "intra": "eipd", "intra_start": 2}}, ("ip_side128",)),
+    ("x_ip_base_side128_a_12b", 264, 264, 12, 0, 0, (1, 0), 0.0, {"log2_ctu": 7, "extreme": {"htdf_partition": dict(_IGEN, rot=0, all128=True, admvp=False, n_refs=(1, 0)), "start": "noise", "intra": "base"}}, ("ip_side128",)),
+    ("x_ip_base_side128_b_10b", 264, 264, 10, 0, 0, (1, 0), 0.0, {"log2_ctu": 7, "amp": 40.0, "extreme": {"htdf_partition": dict(_IGEN, rot=4, all128=True, admvp=False, n_refs=(1, 0), amp=40.0, coded_frac=0.9), "start": "ladder", "intra": "base", "intra_start": 1}}, ("ip_side128",)),
+    ("x_ip_base_side128_c_8b", 264, 264, 8, 0, 0, (1, 0), 0.0, {"log2_ctu": 7, "extreme": {"htdf_partition": dict(_IGEN, rot=8, all128=True, admvp=False, n_refs=(1, 0)), "start": "gratings", "intra": "base", "intra_start": 2}}, ("ip_side128",)),
 ]
 
 # the cases written for the branches of the DMVR search (tests/test_oracle_extremes.py: test_dmvr_cases_together_reach_every_branch)
@@ -1083,13 +1226,20 @@ DMVR_CASES = [s for s in EXTREME_CASES if "dmvr_pair" in s[8].get("extreme", {})
 AFFINE_CASES = [s for s in EXTREME_CASES if "affine" in s[8].get("extreme", {})]
 # the cases written for the branches of the Hadamard-domain filter and of intra block copy (tests/test_oracle_extremes.py: test_htdf_cases_together_reach_every_branch,
 # test_ibc_cases_together_reach_every_branch)
-HTDF_CASES = [s for s in EXTREME_CASES if "htdf_partition" in s[8].get("extreme", {}) and "ibc" not in s[8]["extreme"]]
-IBC_CASES = [s for s in EXTREME_CASES if "ibc" in s[8].get("extreme", {})]
+HTDF_CASES = [s for s in EXTREME_CASES if "htdf_partition" in s[8].get("extreme", {}) and "ibc" not in s[8]["extreme"] and "intra" not in s[8]["extreme"]]
+IBC_CASES = [s for s in EXTREME_CASES if "ibc" in s[8].get("extreme", {}) and "intra" not in s[8]["extreme"]]
+# the cases written for the branches of intra prediction (tests/test_oracle_extremes.py: test_intra_cases_together_reach_every_branch); the filter is off in all of them
+INTRA_CASES = [s for s in EXTREME_CASES if "intra" in s[8].get("extreme", {})]
 # ... with an uneven tile grid, local dual trees and copies inside it.  The reference harness has neither a tile map nor dual trees, so this one is held to the oracle only, like
 # TILE_CASES below (the oracle's handling of both is pinned by the golden streams the reference decoder produced: stream_main_*tiles*, stream_main_dual_tree_*)
 HTDF_TILE_CASES = [
     ("xt_htdf_ibc_dual_tree_8b", 264, 200, 8, 1, 1, (1, 1), 0.3, {"htdf_qp": 32, "addb": 1, "eipd": 1, "extreme": {"htdf_partition": dict(_HGEN, rot=13, rtl=True, dual=True), "content": "noise", "start": "ladder",
                                                                                                                "tiles": ([0, 2, 5], [0, 1, 4], 0), "ibc": ("parity", 0.3)}}),
+]
+# intra prediction inside an uneven tile grid, with local dual trees (luma-only and chroma-only CUs): neighbour units refused because they lie in another tile
+INTRA_TILE_CASES = [
+    ("xt_ip_eipd_dual_tree_10b", 264, 200, 10, 1, 1, (1, 1), 0.3, {"eipd": 1, "addb": 1, "extreme": {"htdf_partition": dict(_IGEN, rot=13, rtl=True, dual=True, inter_frac=0.2), "content": "noise", "start": "ladder",
+                                                                                              "tiles": ([0, 2, 5], [0, 1, 4], 0), "intra": "eipd", "intra_start": 7}}),
 ]
 # clip18 of the EIF range, 1/32 sample: max_pic = (width + 128 - x - cuw - 1) * 32 passes 2^17 - 1 for x < width - cuw - 3969, min_pic = (-x - 128) * 32 passes -2^17 for
 # x > 3968 - from a width of 3984 a picture has both.  That the clip decides which sample is fetched takes more: a vector of more than 4096 samples that still ends inside the

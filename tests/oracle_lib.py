@@ -47,7 +47,13 @@ class OrcCensus(C.Structure):
                 ("htdf_src", (C.c_uint32 * 3) * 3), ("htdf_side_mixed", C.c_uint32 * 3), ("htdf_tile_refused", C.c_uint32 * 7), ("htdf_stale_corner", C.c_uint32 * 2),
                 ("htdf_lut", (C.c_uint32 * 16) * 5), ("htdf_pass", C.c_uint32 * 5), ("htdf_thr_edge", (C.c_uint32 * 2) * 5), ("htdf_out_clip", C.c_uint32 * 2), ("htdf_nbr", (C.c_uint32 * 6) * 3),
                 ("ibc_shape", (C.c_uint32 * 5) * 5), ("ibc_luma_only", C.c_uint32), ("ibc_bv", ((C.c_uint32 * 2) * 3) * 2), ("ibc_region", C.c_uint32 * 3), ("ibc_src_cus", C.c_uint32 * 3),
-                ("ibc_src_kind", C.c_uint32 * 4), ("ibc_touch", C.c_uint32 * 2), ("ibc_nbr_of_cintra", C.c_uint32 * 2)]
+                ("ibc_src_kind", C.c_uint32 * 4), ("ibc_touch", C.c_uint32 * 2), ("ibc_nbr_of_cintra", C.c_uint32 * 2),
+                ("ip_shape", ((C.c_uint32 * 6) * 6) * 2), ("ip_mode_lr", (C.c_uint32 * 4) * 33), ("ip_mode_aspect", (C.c_uint32 * 3) * 33), ("ip_cmode_lr", (C.c_uint32 * 4) * 5),
+                ("ip_dm_luma", C.c_uint32 * 33), ("ip_base_mode", (C.c_uint32 * 5) * 2), ("ip_base_c_differs", C.c_uint32), ("ip_dc", (C.c_uint32 * 8) * 2),
+                ("ip_plan", ((C.c_uint32 * 6) * 6) * 2), ("ip_plan_clip", C.c_uint32 * 2), ("ip_bi_form", C.c_uint32 * 3), ("ip_bi_corner", (C.c_uint32 * 2) * 2), ("ip_bi_wc", C.c_uint32 * 6),
+                ("ip_bi_clip", C.c_uint32 * 2), ("ip_hor", C.c_uint32 * 3), ("ip_ang_src", (C.c_uint32 * 3) * 3), ("ip_ang_frac", C.c_uint32 * 2), ("ip_ang_clamp", C.c_uint32 * 2),
+                ("ip_ang_clip", C.c_uint32 * 2), ("ip_nbr", (((C.c_uint32 * 3) * 2) * 3) * 2), ("ip_unavail", C.c_uint32 * 4), ("ip_corner", C.c_uint32 * 3), ("ip_tree", C.c_uint32 * 3),
+                ("ip_cbf", C.c_uint32 * 8)]
 
 
 def census_reset():

@@ -1,7 +1,8 @@
 """The host batch builder (xgpu_batch_create's host half) without a device: xgpu_test_build_batch builds the staging block of a batch in host memory and returns a digest
 per array (CU records, CTU starts, TB records, itdq work items, intra records, dependency lists, affine tiles, control points, DMVR sub-blocks, owner map).
 Pinned here: the arrays do not depend on the number of builder threads, and they equal the committed digests (tests/golden/builder_digests.json, written by this
-file's --write with the builder whose staging blocks the GPU suite decodes bit-exactly: a refactoring of the builder must reproduce them byte for byte)."""
+file's --write with the builder whose staging blocks the GPU suite decodes bit-exactly: a refactoring of the builder must reproduce them byte for byte).  Further down the
+test side's restatements of what the builder and the oracle decide (affine paths, the filter's skip condition, avail_lr of intra CUs) are held to the oracle's census."""
 import ctypes as C
 import glob
 import json
@@ -295,3 +296,98 @@ def test_builder_htdf_ibc_nodes_follow_the_oracle_census(spec):
     assert one == four
     assert one[10 + 3] == want, (one[10:18], want)
     assert cen["ibc_shape"].sum() > 0 or not spec[8]["extreme"].get("ibc")
+
+
+def _intra_specs():
+    import extreme_inputs as xi
+    return xi.INTRA_CASES + xi.INTRA_TILE_CASES
+
+
+@pytest.mark.parametrize("spec", _intra_specs(), ids=[s[0] for s in _intra_specs()])
+def test_builder_intra_modes_and_avail_lr_follow_the_oracle_census(spec):
+    """extreme_inputs.intra_avail_lr - avail_lr of every CU from batch order and positions, the test side's restatement that set_intra_modes assigns modes with - held to the
+    oracle: the CUs by [luma mode][avail_lr] and [chroma mode][avail_lr] (Baseline: by mode) counted from the batch are the oracle's census, bucket by bucket."""
+    import cases
+    import extreme_inputs as xi
+    import oracle_lib as ol
+    from xevd_amd.abi import MODE_INTRA
+    cs = cases.build_case(*spec[:9])
+    b = cs["batch"]
+    ol.census_reset()
+    cases.run_cpu("oracle", cs, deblock=False, pad=False)
+    cen = ol.census()
+    lr = xi.intra_avail_lr(b, cs["w"], cs["h"], cs["log2_ctu"])
+    tree = b["tree"] if b.get("tree") is not None else np.zeros(len(lr), np.uint8)
+    intra = b["pred_mode"] == MODE_INTRA
+    luma, chroma = intra & (tree != 2), intra & (tree != 1)
+    if cs["eipd"]:
+        by_luma, by_chroma = np.zeros((33, 4), np.int64), np.zeros((5, 4), np.int64)
+        np.add.at(by_luma, (b["ipm"][luma, 0], lr[luma]), 1)
+        np.add.at(by_chroma, (b["ipm"][chroma, 1], lr[chroma]), 1)
+        assert np.array_equal(by_luma, cen["ip_mode_lr"]) and np.array_equal(by_chroma, cen["ip_cmode_lr"])
+        assert cen["ip_base_mode"].sum() == 0
+    else:
+        assert np.array_equal(np.bincount(b["ipm"][luma, 0], minlength=5), cen["ip_base_mode"][0]) and np.array_equal(np.bincount(b["ipm"][chroma, 1], minlength=5), cen["ip_base_mode"][1])
+        assert cen["ip_mode_lr"].sum() == 0
+    assert intra.sum() == cen["ip_shape"].sum() == cen["ip_tree"].sum() and (intra & (tree == 1)).sum() == cen["ip_tree"][1] and (intra & (tree == 2)).sum() == cen["ip_tree"][2]
+
+
+def test_builder_intra_cases_cover_the_fused_instantiations():
+    """k_intra_itdq<EIPD, IBC, IQT> - the data-flow intra launch with the next picture's residual pass riding along (xgpu_launch.hip: a next batch with coefficients, levels
+    beyond the first, no HTDF nodes; k_intra.hip launch_intra: EIPD 2 with a reconstructed right column in an EIPD sequence - always with the copy path -, else 1 / 0 by the
+    sequence, the copy path by the batch) - is taken by tests/test_gpu_extremes.py's runs of the intra cases with the residual pass ahead.  Which instantiation a case takes
+    follows from the batch.  Of the ten (EIPD 0 / 1 x copies x IQT, EIPD 2 x IQT) the cases take the five asserted below: every value of EIPD, EIPD 0 and 1 each with and
+    without copies, each transform at least once - IQT 0 only in the Baseline profile, without copies."""
+    import cases
+    import extreme_inputs as xi
+    from xevd_amd.abi import MODE_INTRA
+    lib, seen = _lib(), set()
+    for spec in xi.INTRA_CASES:
+        cs = cases.build_case(*spec[:9])
+        b = cs["batch"]
+        sp = abi.make_seq_params(cs["w"], cs["h"], cs["bd"], log2_ctu=cs["log2_ctu"], iqt=cs["iqt"], admvp=cs["admvp"], addb=cs["addb"], alf=cs["alf"], eipd=cs["eipd"])
+        cb, keep = abi.make_cu_batch(b)
+        got = _build(lib, sp, cb, 1)
+        n_waves, n_intra, n_l1 = got[10 + 2], got[10 + 3], got[10 + 4]
+        assert not b.get("htdf_slice_qp") and n_intra > n_l1 > 0, spec[0]
+        if n_waves == 0:      # nothing for a residual pass to do: the plain launch (the case without coefficients)
+            assert b["n_coef"] == 0 and spec[0] == "x_ip_eipd_rtl_nocoef_10b"
+            continue
+        right = bool((xi.intra_avail_lr(b, cs["w"], cs["h"], cs["log2_ctu"])[b["pred_mode"] == MODE_INTRA] & 2).any())
+        ibc = bool((b["pred_mode"] == 6).any())
+        seen.add((2, True, cs["iqt"]) if right and cs["eipd"] else (cs["eipd"], ibc, cs["iqt"]))
+    assert seen >= {(2, True, 1), (1, False, 1), (1, True, 1), (0, False, 0), (0, True, 1)}, sorted(seen)
+
+
+def test_builder_refuses_a_right_neighboured_cu_of_more_than_32_units():
+    """An intra CU whose right-hand neighbour is reconstructed keeps the availability of its right column in the upper half of a 64-bit mask: w + h of at most 128 samples
+    (32 units).  The reference never produces more: sps_suco_flag reverses the vertical cuts of nodes of at most 64x64 - xevdm_check_suco_cond: max(cuw, cuh) <= 1 <<
+    min(log2 CTU - ..., 6), and a binary or ternary vertical cut only where cuw > cuh - so such a CU is at most 32 wide and 64 high.  A batch that holds a larger one (here
+    the CTU of 128 cut into halves of 64x128, the right one first) is in an order no stream has, and the builder refuses it rather than decode it wrongly; the same
+    halves left to right, and quarters of 64x64 right to left, are built."""
+    from xevd_amd import synth
+    lib = _lib()
+
+    def build(xs, ys, lw, lh):
+        part = (np.array(xs, np.uint16), np.array(ys, np.uint16), np.array(lw, np.uint8), np.array(lh, np.uint8), np.array([0, len(xs)], np.uint32))
+        b = synth.gen_frame(np.random.default_rng(3), 128, 128, 10, log2_ctu=7, inter_frac=0.0, eipd=True, partition=part)
+        cb, keep = abi.make_cu_batch(b)
+        dg, info, ms = (C.c_uint64 * 13)(), (C.c_int * 8)(), C.c_double()
+        return [lib.xgpu_test_build_batch(C.byref(abi.make_seq_params(128, 128, 10, log2_ctu=7, eipd=1)), C.byref(cb), t, dg, info, C.byref(ms)) for t in (1, 3)]
+    assert build([64, 0], [0, 0], [6, 6], [7, 7]) == [-101, -101]
+    assert build([0, 64], [0, 0], [6, 6], [7, 7]) == [0, 0]
+    assert build([64, 0, 64, 0], [0, 0, 64, 64], [6, 6, 6, 6], [6, 6, 6, 6]) == [0, 0]
+
+
+def test_builder_takes_a_cu_of_4x128():
+    """No stream holds a CU of 1 : 32 (a binary cut must leave a ratio of at most 1 : 4, ALLOW_SPLIT_RATIO), but the builder checks sizes and positions, not ratios: a CTU
+    of 128 cut into 32 columns of 4x128 is built.  The census buckets only such a CU fills (tests/test_oracle_extremes.py, check_intra_empty) are dead for streams, not for
+    batches."""
+    from xevd_amd import synth
+    lib = _lib()
+    n = 32
+    part = (np.arange(n, dtype=np.uint16) * 4, np.zeros(n, np.uint16), np.full(n, 2, np.uint8), np.full(n, 7, np.uint8), np.array([0, n], np.uint32))
+    for eipd in (0, 1):
+        b = synth.gen_frame(np.random.default_rng(3), 128, 128, 10, log2_ctu=7, inter_frac=0.0, eipd=bool(eipd), partition=part)
+        cb, keep = abi.make_cu_batch(b)
+        assert _build(lib, abi.make_seq_params(128, 128, 10, log2_ctu=7, eipd=eipd), cb, 1)[10 + 3] == n * (2 if eipd else 1)      # (512 samples: two parts under EIPD, one under the Baseline predictors)

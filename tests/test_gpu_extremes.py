@@ -6,7 +6,9 @@ displacements, vectors on the thresholds, all sub-block shapes; also its refined
 the s16 limits, vectors of more than 4096 samples; also the stored sub-block vectors), every branch of the Hadamard-domain filter (xi.HTDF_CASES: every CU shape as intra and as
 filter-only inter node in every decoding order, right to left included, the slice QPs at the ends of every table's range, constrained intra prediction with sides that mix, an
 uneven tile grid with local dual trees; also with the residual pass ahead - without the ride-along launch - and twice on one decoder) and of intra block copy (xi.IBC_CASES: vectors of
-every parity and sign, sources over many CUs, inside filtered CUs and inside other copies) - all three padded planes and the residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
+every parity and sign, sources over many CUs, inside filtered CUs and inside other copies), every intra predictor under every launch form (xi.INTRA_CASES: both neighbour-staging
+schemes, the right-column forms, 1 to 16 parts per CU; also with the residual pass riding in the data-flow launch - k_intra_itdq, each value of EIPD, of copies and of IQT at least once -, through k_intra_l1's
+16-lane body, twice on one decoder, and inside a tile grid with local dual trees) - all three padded planes and the residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
 reach the branches they are for) are repeated here because this file needs only the oracle, which always ships."""
 import numpy as np
 import pytest
@@ -14,7 +16,8 @@ import pytest
 import cases
 import extreme_inputs as xi
 import oracle_lib as ol
-from test_oracle_extremes import TILED_STREAMS_REACHING_INTERIOR_BORDERS, check_census, check_htdf_tile_census, check_tile_census, run_oracle_with_census
+from test_oracle_extremes import TILED_STREAMS_REACHING_INTERIOR_BORDERS, check_census, check_htdf_tile_census, check_intra_tile_census, check_tile_census, run_oracle_with_census
+from test_oracle_extremes import INTRA_L1_CASES, INTRA_L1_LONG, intra_surely_level1
 
 pytestmark = pytest.mark.gpu
 
@@ -202,6 +205,48 @@ def test_gpu_htdf_tile_case(spec):
     cs = cases.build_case(*spec)
     (ref, _, _, rr), cen = run_oracle_with_census(cs)
     check_htdf_tile_census(cen)
+    out, res = cases.run_gpu(cs, resid=True)
+    assert np.array_equal(res[:len(rr)], rr), "residual arena"
+    _same(out, ref, spec[0])
+    _same(cases.run_gpu(cs, ahead=True), ref, spec[0] + " (ahead)")
+
+
+# ---- intra prediction: the cases of xi.INTRA_CASES (every predictor, both neighbour-staging schemes, the right-column forms; test_intra_cases_together_reach_every_branch) -
+# planes, residual arena and census in test_gpu_extreme_case above (k_intra<DEP, EIPD, IBC, HTDF> behind a plain level-1 launch), those with ADDB at up to 10 bit also in
+# test_gpu_extreme_case_scalar_deblocking.  Here the launch forms that run does not take.
+@pytest.mark.parametrize("spec", xi.INTRA_CASES, ids=[s[0] for s in xi.INTRA_CASES])
+def test_gpu_intra_case_residual_pass_ahead(spec):
+    """the next picture's residual pass rides in the data-flow intra launch (k_intra_itdq; no case here has HTDF nodes): tests/test_builder.py holds which of its
+    instantiations the cases take - each value of EIPD, of copies and of IQT at least once, five of the ten.  (The case without coefficients has no pass to ride along: it takes the plain launch twice.)"""
+    _check(cases.build_case(*spec[:9]), spec[0] + " (ahead)", resid=True, ahead=True)
+
+
+@pytest.mark.parametrize("spec", INTRA_L1_CASES, ids=[s[0] for s in INTRA_L1_CASES])
+def test_gpu_intra_case_sixteen_lanes_per_cu(spec, monkeypatch):
+    """k_intra_l1 (XEVD_HIP_INTRA_SMALL_MIN is read when a context opens): the level-1 CUs of at most 16 SCUs of the mixed Baseline cases, 16 lanes each: every such intra CU among inter
+    neighbours, 32x8, 64x4 and 4x64 among them (tests/test_oracle_extremes.py: INTRA_L1_LONG)"""
+    monkeypatch.setenv("XEVD_HIP_INTRA_SMALL_MIN", "1")
+    cs = cases.build_case(*spec[:9])
+    b = cs["batch"]
+    small = intra_surely_level1(cs) & (b["log2w"].astype(int) + b["log2h"].astype(int) <= 8)
+    shapes = set(zip((1 << b["log2w"][small].astype(int)).tolist(), (1 << b["log2h"][small].astype(int)).tolist()))
+    assert small.any() and shapes >= INTRA_L1_LONG[spec[0]], sorted(shapes)
+    _check(cs, spec[0] + " (k_intra_l1)", resid=True)
+
+
+@pytest.mark.parametrize("name", ["x_ip_eipd_rtl_12b_ctu128", "x_ip_base_mixed_10b"])
+def test_gpu_intra_case_decoded_twice_on_one_decoder(name):
+    """as test_gpu_htdf_case_decoded_twice_on_one_decoder, without the filter: an EIPD picture in a right-to-left order and a Baseline one - done flags and epoch reused"""
+    test_gpu_htdf_case_decoded_twice_on_one_decoder(name)
+
+
+@pytest.mark.parametrize("spec", xi.INTRA_TILE_CASES, ids=[s[0] for s in xi.INTRA_TILE_CASES])
+def test_gpu_intra_tile_case(spec):
+    """intra prediction inside an uneven tile grid with local dual trees: units across a tile border are not available; luma-only and chroma-only CUs.  Against the oracle
+    only (the reference harness has neither a tile map nor dual trees)."""
+    cs = cases.build_case(*spec)
+    (ref, _, _, rr), cen = run_oracle_with_census(cs)
+    check_intra_tile_census(cen)
     out, res = cases.run_gpu(cs, resid=True)
     assert np.array_equal(res[:len(rr)], rr), "residual arena"
     _same(out, ref, spec[0])

@@ -72,6 +72,11 @@ slice QPs at both ends of every table's range, block vectors placed on purpose -
 (check_htdf_empty), 65 mutations of the oracle's filter, availability and copy - all caught - and the oracle's timing against the parent: profiles/htdf_ibc_census.txt.  The output
 clip of the filter was expected to be unreachable and is not: both rails at every bit depth.
 
+Intra prediction (xi.INTRA_CASES, xi.INTRA_TILE_CASES: modes assigned on purpose - set_intra_modes - on htdf_partition's shapes, EIPD in right-to-left and left-to-right orders,
+the Baseline predictors in both profiles, all-intra and mixed pictures).  The census over them (ip_*), the buckets asserted empty with their arguments (check_intra_empty), 43
+mutations of the oracle's predictors and neighbour builders - all caught but the two clips shown to change nothing - and the oracle's timing against the parent:
+profiles/intra_census.txt.  The angular predictor's final clip was expected to be unreachable and is; the bilinear one's upper half was not expected and is reached from 10 bit on.
+
 The census (which needs only the oracle) and the generator checks run everywhere; the comparison against the reference carries the `ref` mark and is skipped
 where oracle/_ref is not built, like tests/test_oracle_vs_ref.py.
 """
@@ -193,7 +198,113 @@ def _ibc_parity(cen, cs):
     assert bv[:, 1, 1].sum() == 0      # (0 is even)
 
 
+# ---- intra prediction: what the cases of xi.INTRA_CASES are for (all of them together: test_intra_cases_together_reach_every_branch)
+def intra_part_counts(cs):
+    """the part counts of the case's intra CUs (none of them is filtered: the slice QP of the filter is 0) -> {shape: parts}"""
+    b = cs["batch"]
+    assert not b.get("htdf_slice_qp")
+    parts = xi.intra_parts(b, cs["eipd"])
+    sel = b["pred_mode"] == xi.MODE_INTRA
+    return {(1 << int(lw), 1 << int(lh)): int(p) for lw, lh, p in zip(b["log2w"][sel], b["log2h"][sel], parts[sel])}
+
+
+def _ip_modes(cen, cs):
+    _all(cen["ip_mode_lr"][:, 1], "every EIPD luma mode with only the left column")
+    _all(cen["ip_mode_aspect"], "EIPD luma mode x [wide, square, tall]")
+    _all(cen["ip_dm_luma"], "chroma DM resolved to every luma mode")
+    _all(cen["ip_cmode_lr"].sum(1), "chroma modes 0 .. 4")
+
+
+def _ip_right(cen, cs):
+    _all(cen["ip_nbr"][0][2][:, 0], "units of the right column read from the picture [luma, chroma]")
+    _all(cen["ip_mode_lr"].sum(0), "EIPD CUs with avail_lr 0, 1, 2, 3")
+    _all(cen["ip_hor"], "mode 24 from the left column, from the right one, between the two")
+    _all(cen["ip_bi_form"], "bilinear: left column, mirrored, both columns")
+    _all(cen["ip_bi_corner"][1], "mirrored bilinear on [square, not square: wc_tbl] CUs")
+    _all(cen["ip_plan"].sum((1, 2)), "planar [left form, mirrored]")
+    _all(cen["ip_dc"].sum(1), "DC over [w + h, w + 2h] samples")
+    _all(cen["ip_ang_src"][:, 2], "angular samples of modes [< 12, 13 .. 23, > 24] read from the right column")
+    _all([cen["ip_ang_src"][2][0]], "angular samples of modes > 24 read from the row above (only with a right column)")
+
+
+def _ip_left_only(cen, cs):
+    assert cen["ip_nbr"][0][2][:, 0].sum() == 0 and cen["ip_mode_lr"][:, 2:].sum() == 0, "a left-to-right order: no right column (k_intra's EIPD instantiation without the right-hand forms)"
+    _all(cen["ip_mode_lr"][:, 1], "every EIPD luma mode with only the left column")
+    _all([cen["ip_mode_lr"][:, 0].sum()], "CUs without either column")
+
+
+def _ip_base(cen, cs):
+    _all(cen["ip_base_mode"], "Baseline modes [luma, chroma] x DC, HOR, VER, UL, UR")
+    _all([cen["ip_base_c_differs"]], "Baseline CUs whose chroma mode differs")
+    _all(cen["ip_nbr"][1][:2], "Baseline builder [up, left] x [luma, chroma] x [available, unavailable later, unavailable first]")
+    _all(cen["ip_corner"][[0, 2]], "corner [available, mid]")
+    assert cen["ip_shape"][1].sum() == 0 and cen["ip_nbr"][0].sum() == 0
+
+
+def _ip_parts_eipd(cen, cs):
+    parts = intra_part_counts(cs)
+    assert parts[(16, 16)] == 1 and parts[(64, 64)] == 16 and set(parts.values()) >= {1, 2, 4, 8, 16}, parts
+
+
+def _ip_parts_base(cen, cs):
+    parts = intra_part_counts(cs)
+    assert parts[(64, 64)] == 4 and set(parts.values()) >= {1, 4} and set(parts.values()) & {8, 16}, parts
+    if (128, 128) in parts:
+        assert parts[(128, 128)] == 16
+
+
+def _ip_nocoef(cen, cs):
+    assert cen["ip_cbf"][0] == cen["ip_cbf"].sum() > 0 and cen["recon_coded"] == 0 and cs["batch"]["n_coef"] == 0, "no CU carries a coefficient: prediction, then the clip"
+
+
+def _ip_cip(cen, cs):
+    _all([cen["ip_unavail"][3]], "neighbour units refused by constrained intra prediction")
+    _all(cen["ip_nbr"][0 if cs["eipd"] else 1][:2, :, 1], "units unavailable behind an available one [up, left] x [luma, chroma]")
+
+
+def _ip_plan_mirror(cen, cs):
+    assert cs["bd"] == 12
+    _all([cen["ip_plan"][1].sum()], "planar in its mirrored form, at 12 bit")
+    _all(cen["ip_plan_clip"], "planar samples clipped [at 0, at max]")
+
+
+def intra_shapes(cs, right=None):
+    """the shapes (log2w - 2, log2h - 2) of the case's intra CUs that have luma, from the batch; right: only those with (True) / without (False) a reconstructed right column"""
+    b = cs["batch"]
+    tree = b["tree"] if b.get("tree") is not None else np.zeros(len(b["x"]), np.uint8)
+    sel = (b["pred_mode"] == xi.MODE_INTRA) & (tree != 2)
+    if right is not None:
+        sel &= ((xi.intra_avail_lr(b, cs["w"], cs["h"], cs["log2_ctu"]) & 2) != 0) == right
+    return set(zip((b["log2w"][sel].astype(int) - 2).tolist(), (b["log2h"][sel].astype(int) - 2).tolist()))
+
+
+def _ip_side128(cen, cs):
+    """four shapes of HTDF_128, one per whole CTU, each predicted - under EIPD each also by the planar predictor, whose mult[5] / shift[5] only a side of 128 reads"""
+    big = {sh for sh in intra_shapes(cs) if 5 in sh}
+    assert len(big) == 4 and big <= {(int(np.log2(w_)) - 2, int(np.log2(h_)) - 2) for w_, h_ in xi.HTDF_128}, sorted(big)
+    for lw, lh in big:
+        assert cen["ip_shape"][cs["eipd"]][lw][lh] > 0 and (not cs["eipd"] or cen["ip_plan"][0][lw][lh] > 0), (lw, lh)
+
+
+def _ip_clips(cen, cs):
+    _all(cen["ip_plan_clip"], "planar samples clipped [at 0, at max]")
+
+
 REQUIRE = {
+    "ip_modes": _ip_modes,
+    "ip_right": _ip_right,
+    "ip_left_only": _ip_left_only,
+    "ip_base": _ip_base,
+    "ip_parts_eipd": _ip_parts_eipd,
+    "ip_parts_base": _ip_parts_base,
+    "ip_nocoef": _ip_nocoef,
+    "ip_cip": _ip_cip,
+    "ip_clips": _ip_clips,
+    # (c = max + 1 takes max x 1025 / 1024 + 1 / 2 >= max + 1 from wc_tbl's 205 for 1 : 4, max x 1026 / 1024 + 1 / 2 from its 114 for 1 : 8: a depth of 10 bit at least)
+    "ip_bi_clip": lambda cen, cs: _all(cen["ip_bi_clip"][1:], "bilinear samples clipped at max"),
+    "ip_plan_mirror": _ip_plan_mirror,
+    "ip_side128": _ip_side128,
+    "ip_ibc": lambda cen, cs: _all([cen["ibc_shape"].sum(), cen["ip_shape"].sum()], "IBC CUs and intra CUs in one picture"),
     "htdf_pass": _htdf_pass,
     "htdf_lut": lambda cen, cs: _all(cen["htdf_lut"][htdf_table_of(cs)], f"HTDF look-ups by index 0 .. 15 in table {htdf_table_of(cs)}"),
     "htdf_neg": lambda cen, cs: _all([cen["htdf_idx_neg"], cen["htdf_table"][1][0]], "square intra CUs of 32 / 64 whose QP - 8 gives a negative index, clamped to table 0"),
@@ -265,8 +376,31 @@ def check_census(spec, cs, cen):
     assert cen["dmvr_not_refined"][1] == 0 and cen["dmvr_win_off"][0][[0, 6, 7]].sum() == 0 and cen["dmvr_win_off"][1][[0, 1, 5, 6, 7]].sum() == 0, "a DMVR bucket the module docstring calls unreachable was reached"
     assert cen["aff_band_vn"][0] == 0, "an affine bucket the module docstring calls unreachable was reached"
     check_htdf_empty(cen)
+    check_intra_empty(cen)
     for tag in spec[9]:
         REQUIRE[tag](cen, cs)
+
+
+def check_intra_empty(cen):
+    """the intra buckets that must stay empty, each with its argument"""
+    # The angular predictor's final clip.  Its taps 32 - o, 64 - o, 32 + o, o with 0 <= o < 32 are non-negative and sum to 128, the references are reconstructed samples or
+    # the mid value, all in 0 .. max: the sum lies in 0 .. 128 max, and (128 max + 64) >> 7 = max.  A kernel may drop this clip; the census found no sample that needs it.
+    assert cen["ip_ang_clip"].sum() == 0, cen["ip_ang_clip"].tolist()
+    # The one-column bilinear predictor below 0.  With all references >= 0, v (2wh) = h ((w - k - 1) col + (k + 1) a) + w ((h - j - 1) up + (j + 1) b) + k j (2c - a - b) + wh
+    # >= a ((k + 1) h - k j) + b ((j + 1) w - k j) > 0, because c >= 0, j < h and k < w.  (Above max it IS reached: wc_tbl rounds 1/3, 1/5 and 1/9 up, so c exceeds max
+    # where a = b = max.)
+    assert cen["ip_bi_clip"][0] == 0
+    # modes below 12 lean right: they read the row above or the right column, never the left one (ipred_ang_val's first branch)
+    assert cen["ip_ang_src"][0][1] == 0
+    # The 4096 / (2^k + 1) table beyond k = 5 and wc_tbl at 5: |log2 w - log2 h| is at most 5 for CUs of 4 .. 128 a side, and 5 takes 4x128 or 128x4.  No stream holds one:
+    # a binary cut is allowed only where it leaves a ratio of at most 1 : 4 (ALLOW_SPLIT_RATIO: block_ratio <= BLOCK_14, src_main/xevdm_util.h:110, used by
+    # xevdm_check_split_mode, xevdm_util.c:1575-1640), and a ternary cut only across the longer side.  The builder does not check ratios - it takes any power-of-two CU of
+    # 4 .. 128 a side inside the picture, 4x128 included (tests/test_builder.py, test_builder_takes_a_cu_of_4x128) -, so these entries are dead for streams, not for
+    # batches; the partition tables here end at 1 : 16 (4x64, the worst case of the 16-lane kernel's staging) and do not grow for them.  DC over both columns uses
+    # log2 (2h), where 5 is 4x64: reached.
+    assert cen["ip_dc"][:, 6:].sum() == 0 and cen["ip_dc"][0][5] == 0 and cen["ip_bi_wc"][[0, 5]].sum() == 0
+    # the Baseline builder has no right column
+    assert cen["ip_nbr"][1][2].sum() == 0
 
 
 def check_htdf_empty(cen):
@@ -482,6 +616,187 @@ def test_htdf_cases_together_reach_every_branch():
     assert sum(bool(s[8].get("constrained_intra")) for s in specs) == 2 and len(xi.HTDF_TILE_CASES) == 1 and len(specs) == 10
     assert {(bool(s[8].get("addb")), bool(s[8].get("alf"))) for s in specs} >= {(False, False), (True, False), (True, True)}
     assert any(s[8]["extreme"]["htdf_partition"].get("rtl") for s in specs) and any(not s[8]["extreme"]["htdf_partition"].get("rtl") for s in specs)
+
+
+def intra_census_together():
+    """the census of the intra cases and of the tiled one, summed: -> (INTRA_CASES, INTRA_TILE_CASES, {bit depth: ...}, {Baseline / EIPD: ...}, [(spec, case)])"""
+    def add(a, b):
+        return b if a is None else {k: a[k] + b[k] for k in b}
+    out, by_bd, by_profile, built = [None, None], {}, {}, []
+    for n, group in enumerate((xi.INTRA_CASES, xi.INTRA_TILE_CASES)):
+        for spec in group:
+            cs = cases.build_case(*spec[:9])
+            _, cen = run_oracle_with_census(cs)
+            cen = {k: np.asarray(v) for k, v in cen.items() if k.startswith("ip_")}
+            check_intra_empty(cen)
+            out[n] = add(out[n], cen)
+            if n == 0:
+                by_bd[spec[3]], by_profile[cs["eipd"]] = add(by_bd.get(spec[3]), cen), add(by_profile.get(cs["eipd"]), cen)
+            built.append((spec, cs))
+    return out[0], out[1], by_bd, by_profile, built
+
+
+# levels of k_intra's dependency plan.  A strand takes a CU of level 2 or more whose only dependency of level 2 or more has no successor yet (xgpu_intra_plan.hip, link_strands), so
+# it takes three levels at least; the mixed Baseline pictures, where seven CUs in ten are inter, give 6 and more, the all-intra ones 50 and more (but those of four CTU-sized shapes and an edge, `all128`: 19 and more)
+INTRA_MIN_LEVELS, INTRA_MIN_LEVELS_ALL_INTRA = 6, 50
+
+
+def test_intra_cases_together_reach_every_branch():
+    """the conditions the intra cases were chosen for, over all of them (profiles/intra_census.txt holds this test's output)"""
+    from test_builder import _build, _lib
+    from xevd_amd import abi
+    ip, tiled, by_bd, by_profile, built = intra_census_together()
+    for k, v in ip.items():
+        print(k, v.tolist())
+    print("tiled case: ip_unavail", tiled["ip_unavail"].tolist(), "ip_tree", tiled["ip_tree"].tolist(), "ip_mode_lr by lr", tiled["ip_mode_lr"].sum(0).tolist())
+    # CUs: every shape of 4 .. 64 a side under both sets of predictors, and sides of 128
+    # CUs: under both sets of predictors every shape of 4 .. 64 a side and the nine of HTDF_128 - 128x128, and 128 by 64, 32, 16, 8 both ways -, no other: 128 by 4 has a ratio
+    # no stream holds (check_intra_empty) and no partition table either
+    every = np.zeros((6, 6), bool)
+    every[:5, :5] = True
+    for w_, h_ in xi.HTDF_128:
+        every[int(np.log2(w_)) - 2, int(np.log2(h_)) - 2] = True
+    assert every.sum() == 34 and not every[5, 0] and not every[0, 5]
+    for p, name in enumerate(("Baseline", "EIPD")):
+        assert ((ip["ip_shape"][p] > 0) == every).all(), f"{name}: intra CUs of every shape of 4 .. 64 a side and of HTDF_128, no other: {ip['ip_shape'][p].tolist()}"
+    _all(ip["ip_mode_lr"], "EIPD luma mode 0 .. 32 x avail_lr 0 .. 3")
+    _all(ip["ip_mode_aspect"], "EIPD luma mode x [wide, square, tall]")
+    _all(ip["ip_cmode_lr"], "EIPD chroma mode 0 .. 4 x avail_lr")
+    _all(ip["ip_dm_luma"], "chroma DM resolved to every luma mode")
+    _all(ip["ip_base_mode"], "Baseline modes [luma, chroma] x 5")
+    _all([ip["ip_base_c_differs"]], "Baseline CUs whose chroma mode differs")
+    _all(ip["ip_dc"][0][:5], "DC over one column or none: table index 0 .. 4")
+    _all(ip["ip_dc"][1][:6], "DC over both columns: table index 0 .. 5")
+    # Planar, bucket by bucket.  Left form: all 34 shapes, the last row and column being mult[5] / shift[5], which only a side of 128 reads.  Mirrored form: exactly the
+    # shapes that occur with a reconstructed right column in these batches (avail_lr restated from batch order: intra_shapes), which must hold every shape of up to 32
+    # wide and 64 high - all a stream can give, because SUCO reverses the vertical cuts of nodes of at most 64x64 only (xevdm_check_suco_cond) - and may hold CUs of 64
+    # wide that htdf_partition's CTU-128 order puts left of a cell decoded before them (the builder takes them: w + h <= 128).  A side of 128 never has one: its right-hand
+    # neighbour is the next CTU, or - 64x128 and narrower - a CU of its own CTU, which htdf_partition always runs left to right and the builder would refuse
+    # (test_builder_refuses_a_right_neighboured_cu_of_more_than_32_units).
+    left_shapes, right_shapes = set(), set()
+    for spec, cs in built:
+        if spec in xi.INTRA_CASES and cs["eipd"]:
+            left_shapes |= intra_shapes(cs, right=False)
+            right_shapes |= intra_shapes(cs, right=True)
+    in_left, in_right = np.zeros((6, 6), bool), np.zeros((6, 6), bool)
+    for sh in left_shapes:
+        in_left[sh] = True
+    for sh in right_shapes:
+        in_right[sh] = True
+    assert (in_left == every).all() and in_right[:4, :5].all() and not in_right[5].any() and not in_right[:, 5].any(), (in_left.tolist(), in_right.tolist())
+    assert ((ip["ip_plan"][0] > 0) == in_left).all(), f"planar, left form, on every shape [iw][ih] that occurs without a right column - all 34: {ip['ip_plan'][0].tolist()}"
+    assert ((ip["ip_plan"][1] > 0) == in_right).all(), f"planar, mirrored, on every shape that occurs with a right column {in_right.tolist()}: {ip['ip_plan'][1].tolist()}"
+    _all(ip["ip_plan_clip"], "planar samples clipped [at 0, at max]")
+    _all(ip["ip_bi_form"], "bilinear [left, mirrored, both columns]")
+    _all(ip["ip_bi_corner"], "one-column bilinear [left, mirrored] x [square, wc_tbl]")
+    _all(ip["ip_bi_wc"][1:5], "wc_tbl index 1 .. 4")
+    _all(ip["ip_bi_clip"][1:], "bilinear samples clipped at max")
+    _all(ip["ip_hor"], "mode 24 by avail_lr 0 / 1, 2, 3")
+    src = ip["ip_ang_src"].copy()
+    src[0][1] = 1      # (asserted empty in check_intra_empty)
+    _all(src, "angular samples by [mode class] x [up, left, right]")
+    _all(ip["ip_ang_frac"], "angular fraction o == 0, o != 0")
+    _all(ip["ip_ang_clamp"], "angular tap position clamped at -1, at w + h - 1")
+    _all(ip["ip_nbr"][0], "EIPD builder [up, left, right] x [luma, chroma] x [available, repeated, nothing before it]")
+    _all(ip["ip_nbr"][1][:2], "Baseline builder [up, left] x [luma, chroma] x [available, mid behind an available unit, mid from the first unit]")
+    _all(ip["ip_unavail"][[0, 1, 3]], "units unavailable: outside the picture, not reconstructed yet, refused by constrained intra prediction")
+    _all([tiled["ip_unavail"][2]], "units unavailable: in another tile (the tiled case)")
+    assert ip["ip_unavail"][2] == 0
+    _all(ip["ip_corner"], "corner [available, takes up[0], takes mid]")
+    _all(tiled["ip_tree"], "CUs by tree 0, luma only, chroma only (the tiled case: the reference harness knows no dual tree)")
+    assert ip["ip_tree"][1:].sum() == 0
+    _all(ip["ip_cbf"], "intra CUs by cbf 0 .. 7")
+    check_intra_empty(ip)
+    for bd in (8, 10, 12):
+        print(bd, "bit: CUs [Baseline, EIPD]", by_bd[bd]["ip_shape"].sum((1, 2)).tolist(), "planar clips", by_bd[bd]["ip_plan_clip"].tolist(), "mirrored planar", int(by_bd[bd]["ip_plan"][1].sum()))
+        assert (by_bd[bd]["ip_shape"].sum((1, 2)) >= 40).all() and by_bd[bd]["ip_plan"][1].sum() > 0 and (by_bd[bd]["ip_plan_clip"] > 0).all()
+    # from the batches: the named combinations, the part counts, the depth of the plan
+    lib, seen, parts, levels = _lib(), set(), [set(), set()], {}
+    for spec, cs in built:
+        b = cs["batch"]
+        lr = xi.intra_avail_lr(b, cs["w"], cs["h"], cs["log2_ctu"])
+        sel = b["pred_mode"] == xi.MODE_INTRA
+        if cs["eipd"]:
+            seen |= set(zip(b["ipm"][sel, 0].tolist(), (1 << b["log2w"][sel].astype(int)).tolist(), (1 << b["log2h"][sel].astype(int)).tolist(), lr[sel].tolist()))
+        if spec in xi.INTRA_CASES:
+            parts[cs["eipd"]] |= set(intra_part_counts(cs).items())
+        sp = abi.make_seq_params(cs["w"], cs["h"], cs["bd"], log2_ctu=cs["log2_ctu"], iqt=cs["iqt"], admvp=cs["admvp"], addb=cs["addb"], alf=cs["alf"], eipd=cs["eipd"])
+        cb, keep = abi.make_cu_batch(b)
+        one = _build(lib, sp, cb, 1)
+        assert one == _build(lib, sp, cb, 4), spec[0]
+        levels[spec[0]] = one[10 + 5]
+        assert one[10 + 3] == int(xi.intra_parts(b, cs["eipd"])[sel].sum() + (b["pred_mode"] == 6).sum()), (spec[0], "entries of k_intra's list: the parts of the intra CUs and the copies")
+    print("levels of the plan:", levels)
+    assert (17, 4, 64, 3) in seen, "mode 17 on a 4x64 CU with both columns"
+    assert any(m == 2 and w_ != h_ and l == 2 for m, w_, h_, l in seen), "bilinear with only the right column on a CU that is not square"
+    assert {((16, 16), 1), ((64, 64), 16)} <= parts[1] and {p for _, p in parts[1]} == {1, 2, 4, 8, 16}, sorted(parts[1])
+    assert {((64, 64), 4), ((128, 128), 16)} <= parts[0] and {p for _, p in parts[0]} == {1, 2, 4, 8, 16}, sorted(parts[0])
+    assert min(levels.values()) >= INTRA_MIN_LEVELS, levels
+    assert min(levels[s[0]] for s in xi.INTRA_CASES if s[8]["extreme"]["htdf_partition"]["inter_frac"] == 0 and not s[8]["extreme"]["htdf_partition"].get("all128")) >= INTRA_MIN_LEVELS_ALL_INTRA, levels
+    specs = xi.INTRA_CASES
+    assert {(s[3], bool(s[8].get("eipd"))) for s in specs} >= {(bd, e) for bd in (8, 10, 12) for e in (False, True)}
+    assert {s[8].get("log2_ctu", 6) for s in specs if s[8].get("eipd")} == {6, 7} == {s[8].get("log2_ctu", 6) for s in specs if not s[8].get("eipd")}
+    assert all(s[1] <= 264 and s[2] <= 264 and not s[8].get("htdf_qp") and s[9] for s in specs) and len(xi.INTRA_TILE_CASES) == 1
+    gens = [s[8]["extreme"]["htdf_partition"] for s in specs]
+    assert any(g["inter_frac"] == 0 for g in gens) and any(g["inter_frac"] > 0 and s[8].get("constrained_intra") for g, s in zip(gens, specs)) and any(g["inter_frac"] > 0 and not s[8].get("constrained_intra") for g, s in zip(gens, specs))
+    assert any(g.get("amp") == 40.0 for g in gens) and sum(g["coded_frac"] == 0 for g in gens) == 1 and any(g.get("rtl") for g in gens) and any(not g.get("rtl") for g in gens)
+    assert any("ibc" in s[8]["extreme"] and s[8].get("eipd") for s in specs) and any("ibc" in s[8]["extreme"] and not s[8].get("eipd") for s in specs)
+
+
+@pytest.mark.parametrize("spec", xi.INTRA_TILE_CASES, ids=[s[0] for s in xi.INTRA_TILE_CASES])
+def test_intra_tile_case_reaches_the_tile_and_tree_branches(spec):
+    cs = cases.build_case(*spec)
+    _, cen = run_oracle_with_census(cs)
+    check_intra_tile_census(cen)
+
+
+def check_intra_tile_census(cen):
+    check_intra_empty(cen)
+    _all([cen["ip_unavail"][2]], "neighbour units refused because they lie in another tile")
+    _all(cen["ip_tree"], "intra CUs by tree 0, luma only, chroma only")
+    _all(cen["ip_mode_lr"].sum(0), "EIPD CUs with avail_lr 0, 1, 2, 3")
+
+
+def intra_surely_level1(cs):
+    """mask of the intra CUs that certainly are level 1 of k_intra's plan: no unit of the row above, of the left column or the corner - w + h samples each way - lies in an
+    intra CU that comes earlier in the batch (inter CUs are complete before the intra launches).  The plan looks at fewer units for most modes: it may find more."""
+    b = cs["batch"]
+    ws, hs = (cs["w"] + 3) >> 2, (cs["h"] + 3) >> 2
+    intra_at = np.zeros((hs, ws), bool)
+    out = np.zeros(len(b["x"]), bool)
+    for i in np.nonzero(b["pred_mode"] == xi.MODE_INTRA)[0]:
+        xs, ys, wu, hu = int(b["x"][i]) >> 2, int(b["y"][i]) >> 2, (1 << int(b["log2w"][i])) >> 2, (1 << int(b["log2h"][i])) >> 2
+        up = ys > 0 and intra_at[ys - 1, max(xs - 1, 0):min(xs + wu + hu, ws)].any()
+        le = xs > 0 and intra_at[ys:min(ys + wu + hu, hs), xs - 1].any()
+        out[i] = not (up or le)
+        intra_at[ys:ys + hu, xs:xs + wu] = True
+    return out
+
+
+# the Baseline cases without copies whose level 1 holds CUs of at most 16 SCUs (the picture of intra CUs only has one level-1 CU, its first, of 128x128: it never takes k_intra_l1)
+INTRA_L1_CASES = [s for s in xi.INTRA_CASES if not s[8].get("eipd") and "ibc" not in s[8]["extreme"] and s[8]["extreme"]["htdf_partition"]["inter_frac"] > 0]
+# level-1 CUs of at most 16 SCUs whose neighbour arrays are longer than 32 samples: the second staging pass of k_intra_l1's 16-lane body
+INTRA_L1_LONG = {"x_ip_base_cip_12b_ctu128": {(32, 8), (64, 4), (32, 4)}, "x_ip_base_mixed_10b": {(4, 64), (64, 4), (4, 32), (32, 4)}}
+
+
+@pytest.mark.parametrize("spec", INTRA_L1_CASES, ids=[s[0] for s in INTRA_L1_CASES])
+def test_intra_l1_case_holds_its_long_shapes(spec):
+    """what tests/test_gpu_extremes.py asks of the batches it sends through k_intra_l1, met here on the CPU"""
+    cs = cases.build_case(*spec[:9])
+    b = cs["batch"]
+    small = intra_surely_level1(cs) & (b["log2w"].astype(int) + b["log2h"].astype(int) <= 8)
+    shapes = set(zip((1 << b["log2w"][small].astype(int)).tolist(), (1 << b["log2h"][small].astype(int)).tolist()))
+    assert small.any() and shapes >= INTRA_L1_LONG[spec[0]] and all(w_ + h_ > 32 for w_, h_ in INTRA_L1_LONG[spec[0]]), sorted(shapes)
+    assert set().union(*INTRA_L1_LONG.values()) >= {(32, 8), (64, 4), (4, 64)} and set(INTRA_L1_LONG) == {s[0] for s in INTRA_L1_CASES}
+    # ... and the plan agrees: its level 1 (info[4], in list entries) holds at least the CUs this estimate is sure of, none of which is split into parts (at most 16 SCUs), so
+    # the launch of level 1 has n_small >= 1 - all that k_intra_l1 asks for with XEVD_HIP_INTRA_SMALL_MIN=1 in a Baseline picture without copies
+    from test_builder import _build, _lib
+    from xevd_amd import abi
+    sp = abi.make_seq_params(cs["w"], cs["h"], cs["bd"], log2_ctu=cs["log2_ctu"], iqt=cs["iqt"], admvp=cs["admvp"], addb=cs["addb"], alf=cs["alf"], eipd=cs["eipd"])
+    cb, keep = abi.make_cu_batch(b)
+    n_l1 = _build(_lib(), sp, cb, 1)[10 + 4]
+    sure = intra_surely_level1(cs)
+    assert n_l1 >= int(xi.intra_parts(b, 0)[sure].sum()) >= small.sum() > 0 and not cs["eipd"] and not (b["pred_mode"] == 6).any(), (n_l1, int(sure.sum()), int(small.sum()))
 
 
 def test_ibc_cases_together_reach_every_branch():
