@@ -747,6 +747,11 @@ int xgpu_test_batch_resid(xgpu_ctx *ctx, xgpu_dbatch *db, int16_t *resid);
 int xgpu_test_build_batch(const xgpu_seq_params *sp, const xgpu_cu_batch *b, int threads, uint64_t digest[XGPU_TEST_BUILD_DIGESTS], int info[XGPU_BATCH_INFO_COUNT], double *ms);
 /* dequant + 2-D inverse transform of n blocks of one size, in place (xevd_itdq, src_base/xevd_itdq.c:494) */
 int xgpu_test_itdq(xgpu_ctx *ctx, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth);
+/* ... naming the transform pair and the row stride.  tr_v / tr_h (vertical = first stage, horizontal = second): 0 DCT-II, 1 DST-VII, 2 DCT-VIII; DST-VII and
+   DCT-VIII come as a pair and only for blocks of 4 .. 32 a side (src_main/xevdm_itdq.c:406-421), anything else is refused.  log2s >= log2w is the log2 of the row
+   stride: `coef` holds n_blocks blocks of (h << log2s) samples, block i starting at i * (h << log2s), and the samples outside a block's columns come back untouched
+   (a 64x64 sub-block of a larger CU keeps the CU's stride, src_base/xevd_itdq.c:573-584).  A stride beyond the width needs a width of at least 8 and a block of more than 16 samples. */
+int xgpu_test_itdq_ex(xgpu_ctx *ctx, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth, int tr_v, int tr_h, int log2s);
 /* xgpu_scale_taps made by the device's row builder (the one k_rois_prepare runs, one lane per row): same arguments, same results, same return value; w_stride
    must hold the widest row.  Blocking. */
 int xgpu_test_scale_taps_device(xgpu_ctx *ctx, int n_plane, int subsampling, int siting_half_luma, int n_dst, int filter, int32_t *first, int32_t *count,

@@ -263,6 +263,11 @@ void orc_itx_pass0(const int16_t *src, int32_t *dst, int log2n, int line)
         for (k = 0; k < N; k++) s += (int64_t)tm[k * N + n] * src[k * line + j];
         if (s > 2147483647LL) s = 2147483647LL;             /* ITX_CLIP_32, xevd_itdq.c:41-45 */
         if (s < -2147483647LL - 1) s = -2147483647LL - 1;
+        {
+            const int64_t a = s < 0 ? -s : s;
+            if (s < 0 && (s & 0x7FFF)) g_cen.it_s1_negfrac++;
+            g_cen.it_s1_mag[a < (1 << 15) ? 0 : a < (1 << 24) ? 1 : a < (1 << 27) ? 2 : a < (1 << 28) ? 3 : 4]++;
+        }
         dst[j * N + n] = (int32_t)s;
     }
 }
@@ -273,14 +278,19 @@ void orc_itx_pass1(const int32_t *src, int16_t *dst, int log2n, int line, int sh
     const int64_t add = shift == 0 ? 0 : (int64_t)1 << (shift - 1);
     int j, n, k;
     for (j = 0; j < line; j++) for (n = 0; n < N; n++) {
-        int64_t s = 0;
-        for (k = 0; k < N; k++) s += (int64_t)tm[k * N + n] * src[k * line + j];
+        int64_t s = 0, mag = 0;
+        for (k = 0; k < N; k++) {
+            const int64_t v = (int64_t)tm[k * N + n] * src[k * line + j];
+            s += v; mag += v < 0 ? -v : v;
+        }
+        if (mag >= 2147483648LL) g_cen.it_s2_undef++;
         s = (s + add) >> shift;
+        if (s < -32768) g_cen.it_s2_clip[0][0]++; else if (s > 32767) g_cen.it_s2_clip[0][1]++;
         dst[j * N + n] = (int16_t)CLIP3(-32768, 32767, s);
     }
 }
 /* IQT stage (src_main/xevdm_itdq.c:423-706): s16 -> s16 with rounding shift and clip after every stage, 32-bit sums */
-static void itx_iqt(const int16_t *src, int16_t *dst, int log2n, int line, int shift)
+static void itx_iqt(const int16_t *src, int16_t *dst, int log2n, int line, int shift, uint32_t *clipped)
 {
     const int N = 1 << log2n; const int8_t *tm = orc_tm(log2n);
     const int32_t add = shift == 0 ? 0 : 1 << (shift - 1);
@@ -289,8 +299,49 @@ static void itx_iqt(const int16_t *src, int16_t *dst, int log2n, int line, int s
         int32_t s = 0;
         for (k = 0; k < N; k++) s += tm[k * N + n] * src[k * line + j];
         s = (s + add) >> shift;
+        if (s < -32768) clipped[0]++; else if (s > 32767) clipped[1]++;
         dst[j * N + n] = (int16_t)CLIP3(-32768, 32767, s);
     }
+}
+
+/* census of the residual pass: what orc_recon_batch_ex knows about the TB it hands to orc_itdq / orc_itdq_ats (kind 0 DCT-II, 1 ATS-intra, 2 TU of an ATS-inter CU;
+   sb: the sub-block index of a TB that keeps its CU's stride, -1 for a contiguous one) */
+static int g_it_kind = -1, g_it_plane = 0, g_it_sb = -1;
+static void it_census_tb(const int16_t *coef, int log2w, int log2h, int qp, int kind)
+{
+    const int W = 1 << log2w, H = 1 << log2h;
+    uint32_t rows = 0, cols = 0;
+    int nz = 0, last = 0, i, d;
+    if (g_it_kind >= 0) kind = g_it_kind;
+    g_cen.it_tb[kind][log2w - 1][log2h - 1]++;
+    g_cen.it_plane[kind][g_it_plane]++;
+    g_cen.it_qp[qp < 95 ? qp : 95]++;
+    if (g_it_sb >= 0) g_cen.it_strided[g_it_sb & 3]++;
+    for (i = 0; i < W * H; i++) {
+        if (!coef[i]) continue;
+        nz++; last = i;
+        rows |= 1u << ((i >> log2w) >> 1); cols |= 1u << ((i & (W - 1)) >> 1);
+        if (H == 64 && (i >> log2w) >= 32) g_cen.it_high[0]++;
+        if (W == 64 && (i & (W - 1)) >= 32) g_cen.it_high[1]++;
+    }
+    for (d = 0; d < 2; d++) {
+        const int n = __builtin_popcount(d ? cols : rows), all = (d ? W : H) / 2;
+        g_cen.it_nz_pairs[d][n == 0 ? 0 : n == all ? 4 : n == 1 ? 1 : n <= 4 ? 2 : 3]++;
+    }
+    if (nz == 1 && (W >= 16 || H >= 16)) {
+        const int rp = (last >> log2w) >> 1, cp = (last & (W - 1)) >> 1;
+        g_cen.it_single[rp][cp]++;
+        if (H >= 16) g_cen.it_single_dim[0][log2h - 4][rp]++;
+        if (W >= 16) g_cen.it_single_dim[1][log2w - 4][cp]++;
+    }
+}
+static void it_census_dq(int level, int64_t deq, int parity, int qp)
+{
+    const int a = level < 0 ? -level : level, cmax = (1 << 23) >> (qp / 6);
+    if (!level) return;
+    if (deq < -32768) g_cen.it_dq_clip[parity][0]++; else if (deq > 32767) g_cen.it_dq_clip[parity][1]++;
+    if (deq == 0) g_cen.it_dq_zero[parity]++;
+    if (a == cmax) g_cen.it_dq_cmax[parity][0]++; else if (a == cmax + 1) g_cen.it_dq_cmax[parity][1]++;
 }
 
 void orc_itdq(int16_t *coef, int log2w, int log2h, int qp, int bit_depth, int iqt)
@@ -307,19 +358,23 @@ void orc_itdq(int16_t *coef, int log2w, int log2h, int qp, int bit_depth, int iq
     const int64_t offset = shift == 0 ? 0 : (int64_t)1 << (shift - 1);
     const int64_t mul = (int64_t)scale * (odd ? 181 : 1);
     int i;
+    it_census_tb(coef, log2w, log2h, qp, 0);
     for (i = 0; i < n; i++) {                                   /* xevd_dquant, xevd_itdq.c:480-492 */
         int64_t lev = (coef[i] * mul + offset) >> shift;
+        it_census_dq(coef[i], lev, odd, qp);
         coef[i] = (int16_t)CLIP3(-32768, 32767, lev);
     }
     if (iqt) {                                                  /* xevdm_itrans, xevdm_itdq.c:708-716 */
         int16_t *t = (int16_t *)malloc(sizeof(int16_t) * n);
-        itx_iqt(coef, t, log2h, 1 << log2w, 7);
-        itx_iqt(t, coef, log2w, 1 << log2h, 12 - (bit_depth - 8));
+        itx_iqt(coef, t, log2h, 1 << log2w, 7, g_cen.it_s1_clip[0]);
+        itx_iqt(t, coef, log2w, 1 << log2h, 12 - (bit_depth - 8), g_cen.it_s2_clip[1]);
         free(t);
     } else {                                                    /* xevd_itrans, xevd_itdq.c:473-478 */
         int32_t *t = (int32_t *)malloc(sizeof(int32_t) * n);
+        const uint32_t undef = g_cen.it_s2_undef;
         orc_itx_pass0(coef, t, log2h, 1 << log2w);
         orc_itx_pass1(t, coef, log2w, 1 << log2h, 7 + 12 - (bit_depth - 8));
+        if (g_cen.it_s2_undef != undef) g_cen.it_undef_tb++;
         free(t);
     }
 }
@@ -353,7 +408,7 @@ const int16_t *orc_ats_tm(int type, int log2n)
 /* one ATS stage: out[j*N + n] = clip16((sum_k tm[k][n]*src[k*line+j] + rnd) >> shift).  The 4-point kernels of the
    reference use a factorised form built from three entries of the first matrix row (xevdm_itdq.c:163-190, 284-312):
    the products below are that form written as a 4x4 matrix. */
-static void ats_stage(const int16_t *src, int16_t *dst, int type, int log2n, int line, int shift)
+static void ats_stage(const int16_t *src, int16_t *dst, int type, int log2n, int line, int shift, uint32_t *clipped)
 {
     const int N = 1 << log2n;
     const int16_t *tm = orc_ats_tm(type, log2n);
@@ -376,6 +431,7 @@ static void ats_stage(const int16_t *src, int16_t *dst, int type, int log2n, int
         int32_t s = 0;
         for (k = 0; k < N; k++) s += tm[k * N + n] * src[k * line + j];
         s = (s + (1 << (shift - 1))) >> shift;
+        if (s < -32768) clipped[0]++; else if (s > 32767) clipped[1]++;
         dst[j * N + n] = (int16_t)CLIP3(-32768, 32767, s);
     }
 }
@@ -392,14 +448,18 @@ void orc_itdq_ats(int16_t *coef, int log2w, int log2h, int qp, int bit_depth, in
     const int64_t mul = (int64_t)scale * (odd ? 181 : 1);
     int16_t *t = (int16_t *)malloc(sizeof(int16_t) * n);
     int i;
+    it_census_tb(coef, log2w, log2h, qp, 1);
+    g_cen.it_ats_pair[tr_v != 0][tr_h != 0]++;
+    g_cen.it_ats_shape[tr_v != 0][tr_h != 0][log2w - 2][log2h - 2]++;
     for (i = 0; i < n; i++) {
         int64_t lev = (coef[i] * mul + offset) >> shift;
+        it_census_dq(coef[i], lev, odd, qp);
         coef[i] = (int16_t)CLIP3(-32768, 32767, lev);
     }
     /* xevdm_it_MxN_ats_intra, xevdm_itdq.c:406-421: shift_1st = 7, shift_2nd = 6 + 15 - 1 - bit_depth; type index DST7 = 1 - tr, i.e.
        xevd_tbl_tr_subset_intra = { DST7, DCT8 } (xevdm_tbl.c:51) maps tr 0 -> DST7, 1 -> DCT8 */
-    ats_stage(coef, t, tr_v ? 0 : 1, log2h, 1 << log2w, 7);
-    ats_stage(t, coef, tr_h ? 0 : 1, log2w, 1 << log2h, 20 - bit_depth);
+    ats_stage(coef, t, tr_v ? 0 : 1, log2h, 1 << log2w, 7, g_cen.it_s1_clip[1]);
+    ats_stage(t, coef, tr_h ? 0 : 1, log2w, 1 << log2h, 20 - bit_depth, g_cen.it_s2_clip[2]);
     free(t);
 }
 
@@ -1542,12 +1602,15 @@ int orc_recon_batch_ex(const xgpu_seq_params *sp, const orc_frame *fr, const xgp
                 while ((1 << l2w) < tw) l2w++;
                 while ((1 << l2h) < th) l2h++;
                 memcpy(res, b->coef + off, sizeof(int16_t) * tw * th);
+                g_it_kind = 2; g_it_plane = c;
+                if (c == 0 && (ai & 15) >= 1 && (ai & 15) <= 4) g_cen.it_ats_inter[(ai & 15) - 1][(ai >> 4) & 1][!(lw <= 5 && lh <= 5)]++;
                 if (c == 0 && lw <= 5 && lh <= 5) {
                     const int idx = ai & 15, pos = (ai >> 4) & 15, hor = idx == 2 || idx == 4;
                     const int t_h = hor ? 0 : (pos == 0), t_v = hor ? (pos == 0) : 0;      /* 1 = DCT-VIII, 0 = DST-VII */
                     orc_itdq_ats(res, l2w, l2h, b->qp[i * 3], sp->bit_depth_luma, sp->tool_iqt, t_v, t_h);
                 } else
                     orc_itdq(res, l2w, l2h, b->qp[i * 3 + c], sp->bit_depth_luma, sp->tool_iqt);
+                g_it_kind = -1; g_it_plane = 0;
                 if (resid_out) memcpy(resid_out + off, res, sizeof(int16_t) * tw * th);
                 off += (size_t)tw * th;
             }
@@ -1574,18 +1637,22 @@ int orc_recon_batch_ex(const xgpu_seq_params *sp, const orc_frame *fr, const xgp
                     const int sb = (sj << 1) | si;
                     int16_t *blk = res + sj * th * cw + si * tw;
                     if (nsx * nsy > 1 && b->cbf_sub && !((b->cbf_sub[i] >> (4 * c + sb)) & 1)) continue;
+                    g_it_plane = c;
                     if (nsx * nsy == 1) {
                         const int a = b->ats ? b->ats[i] : 0;
                         if (c == 0 && (a & 1) && !inter)      /* ats_intra_cu: luma TB of an intra CU, xevdm_itdq.c:820-829 */
                             orc_itdq_ats(res, tlw, tlh, b->qp[i * 3 + c], sp->bit_depth_luma, sp->tool_iqt, (a >> 1) & 1, (a >> 2) & 1);
                         else
                             orc_itdq(res, tlw, tlh, b->qp[i * 3 + c], sp->bit_depth_luma, sp->tool_iqt);
+                        g_it_plane = 0;
                         continue;
                     }
                     {
                         int16_t *tmp = (int16_t *)malloc(sizeof(int16_t) * tw * th);
                         for (r = 0; r < th; r++) memcpy(tmp + r * tw, blk + r * cw, sizeof(int16_t) * tw);
+                        g_it_sb = cw > tw ? sb : -1;
                         orc_itdq(tmp, tlw, tlh, b->qp[i * 3 + c], sp->bit_depth_luma, sp->tool_iqt);
+                        g_it_sb = -1; g_it_plane = 0;
                         for (r = 0; r < th; r++) memcpy(blk + r * cw, tmp + r * tw, sizeof(int16_t) * tw);
                         free(tmp);
                     }

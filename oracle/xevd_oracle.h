@@ -220,6 +220,30 @@ typedef struct orc_census {
     uint32_t ip_corner[3];                             /* the corner sample: available / not, takes up[0] read from the picture (EIPD) / not, takes mid (EIPD: up[0] unavailable as well; Baseline) */
     uint32_t ip_tree[3];                               /* intra CUs by tree: 0 / luma only / chroma only */
     uint32_t ip_cbf[8];                                /* intra CUs by cbf */
+    /* residual pass (orc_itdq / orc_itdq_ats, their stages, and the calls in orc_recon_batch_ex, which say what the TB is; a call from elsewhere counts as a contiguous luma
+       TB, DCT-II resp. ATS-intra).  [kind]: 0 DCT-II, 1 ATS-intra, 2 the TU of an ATS-inter CU (all planes, whichever matrices it takes).  [arith]: the arithmetic of the
+       two stages, 0 the 32-bit intermediate of xevd_itrans (non-IQT), 1 the clipped s16 one of xevdm_itrans (IQT), 2 ATS.  [parity]: (log2w + log2h) & 1, the odd classes
+       carry the factor 181 / 256.  Pairs: two adjacent coefficient rows (columns), the unit of the kernel's sparsity masks */
+    uint32_t it_tb[3][6][6];                           /* TBs by [kind][log2w - 1][log2h - 1] */
+    uint32_t it_plane[3][3];                           /* TBs by [kind][plane] */
+    uint32_t it_ats_pair[2][2];                        /* TBs through the ATS matrices by [vertical][horizontal], 0 DST-VII, 1 DCT-VIII */
+    uint32_t it_ats_shape[2][2][4][4];                 /* ... by [vertical][horizontal][log2w - 2][log2h - 2] */
+    uint32_t it_ats_inter[4][2][2];                    /* luma TUs of ATS-inter CUs by [idx - 1][pos][DST-VII / DCT-VIII (CU at most 32x32) / DCT-II] */
+    uint32_t it_strided[4];                            /* TBs whose row stride exceeds their width (sub-blocks of a CU above 64) by sub-block index (j << 1) | i */
+    uint32_t it_qp[96];                                /* TBs by QP (above 95: in [95]) */
+    uint32_t it_dq_clip[2][2];                         /* [parity] dequantised coefficients clipped below / above */
+    uint32_t it_dq_zero[2];                            /* [parity] non-zero levels that dequantise to 0 */
+    uint32_t it_dq_cmax[2][2];                         /* [parity] levels of magnitude 2^23 >> (qp / 6) / one beyond */
+    uint32_t it_high[2];                               /* non-zero levels at positions 32 .. 63 of a 64-point dimension, [vertical / horizontal] */
+    uint32_t it_s1_clip[2][2];                         /* first stage, [IQT / ATS]: results clipped low / high */
+    uint32_t it_s1_negfrac;                            /* first stage, non-IQT: negative intermediates with non-zero low 15 bits */
+    uint32_t it_s1_mag[5];                             /* first stage, non-IQT: intermediates of magnitude below 2^15 / 2^24 / 2^27 / 2^28 / from 2^28 */
+    uint32_t it_s2_clip[3][2];                         /* second stage, [arith]: results clipped low / high */
+    uint32_t it_s2_undef;                              /* second stage, non-IQT: output sums with sum_k |tm[k][n]| * |t[k]| >= 2^31, where the reference's 32-bit products may wrap */
+    uint32_t it_undef_tb;                              /* ... TBs holding such a sum */
+    uint32_t it_nz_pairs[2][5];                        /* TBs by the number of [row / column] pairs with a non-zero level: 0 / 1 / 2 .. 4 / 5 or more, not all / all */
+    uint32_t it_single[32][32];                        /* TBs holding one non-zero level, a side of at least 16, by [row pair][column pair] of it */
+    uint32_t it_single_dim[2][3][32];                  /* ... by [vertical / horizontal][that dimension 16 / 32 / 64][pair] */
 } orc_census;
 void orc_census_reset(void);
 void orc_census_get(orc_census *out);

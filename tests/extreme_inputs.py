@@ -968,6 +968,137 @@ def intra_parts(batch, eipd):
     return np.clip((1 << np.maximum(area - 4, 0)) * (4 if eipd else 1) // 64, 1, 16)
 
 
+# ---- the residual pass: levels on the range arguments of xevd_amd/csrc/itdq_body.h (residual_inputs.py), on every TB of a picture
+RESIDUAL_KINDS = ("single", "dense_signed", "thresholds", "mixed_item")
+RESIDUAL_KINDS_64 = ("single", "dense_signed", "single", "thresholds", "single", "mixed_item")      # a picture holds few TBs with a side of 64, and 32 pairs want a single level each
+
+
+def residual_tbs(batch):
+    """The transform blocks of a batch in the order of its coefficient arena - the test side's restatement of the builder's TB walk (xgpu_builder.hip, for_each_tb; held to
+    it in tests/test_builder.py through the work-item count) -> [(cu, plane, sub-block, log2w, log2h, log2 of the row stride, offset, (tr_v, tr_h), qp)] with the
+    kernel's transform codes 0 DCT-II, 1 DST-VII, 2 DCT-VIII"""
+    out = []
+    n = len(batch["x"])
+    ai_all, ats_all, sub_all = batch.get("ats_inter"), batch.get("ats"), batch.get("cbf_sub")
+    for i in range(n):
+        lw, lh, pm = int(batch["log2w"][i]), int(batch["log2h"][i]), int(batch["pred_mode"][i])
+        ai = int(ai_all[i]) if ai_all is not None and pm not in (MODE_INTRA, 6) else 0
+        idx, pos = ai & 15, ai >> 4
+        bw, bh = lw - (1 if idx == 1 else 2 if idx == 3 else 0), lh - (1 if idx == 2 else 2 if idx == 4 else 0)
+        nsx, nsy = (2 if lw > 6 else 1), (2 if lh > 6 else 1)
+        off = int(batch["coef_off"][i])
+        for k in range(3):
+            if not (int(batch["cbf"][i]) >> k) & 1:
+                continue
+            cl, ch = bw - (1 if k else 0), bh - (1 if k else 0)
+            tw, th = min(bw, 6) - (1 if k else 0), min(bh, 6) - (1 if k else 0)
+            tr = (0, 0)
+            if k == 0 and ai:
+                if lw <= 5 and lh <= 5:
+                    hor = idx in (2, 4)
+                    tr = ((2 if pos == 0 else 1) if hor else 1, 1 if hor else (2 if pos == 0 else 1))
+            elif k == 0 and ats_all is not None and (int(ats_all[i]) & 1) and pm == MODE_INTRA:
+                tr = (1 + ((int(ats_all[i]) >> 1) & 1), 1 + ((int(ats_all[i]) >> 2) & 1))
+            for sb in range(4):
+                if (sb & 1) >= nsx or (sb >> 1) >= nsy:
+                    continue
+                if nsx * nsy > 1 and sub_all is not None and not (int(sub_all[i]) >> (4 * k + sb)) & 1:
+                    continue
+                out.append((i, k, sb, tw, th, cl, off + (((sb >> 1) << th) << cl) + ((sb & 1) << tw), tr, int(batch["qp"][i, k])))
+            off += 1 << (cl + ch)
+    return out
+
+
+def set_residual(case, spec, seed):
+    """Every CU that can carry coefficients carries them on all its planes, and every TB gets the levels of one kind of residual_inputs (RESIDUAL_KINDS), chosen by the
+    TB's number within its class and transform pair - in runs that are whole work items of the kernel, so that mixed_item's cycle of items is the kernel's.
+    spec: {'ats': intra CUs of 4 .. 32 a side take ATS, the four type pairs in turn; 'ats_inter': inter CUs of 8 .. 64 take a TU of every idx and pos in turn;
+    'drop_sub': every other CU above 64 leaves one of its sub-blocks uncoded}.  The luma QP walks over 0 .. 51 (+ 6 (bd - 8)), the chroma QPs over 0 .. 51 + 6 (bd - 8):
+    the maps and the deblocking filters take the luma QP, the chroma TBs carry the QPs below 6 (bd - 8) (the batch holds a QP per plane).
+    Blocks of the 32-bit intermediate (no IQT, DCT-II) keep to residual_inputs' `defined` sub-kind: the picture cases are held to the reference."""
+    import residual_inputs as ri
+    b = case["batch"]
+    bd, iqt = case["bd"], case["iqt"]
+    n = len(b["x"])
+    lw, lh, pm = b["log2w"].astype(np.int64), b["log2h"].astype(np.int64), b["pred_mode"].astype(np.int64)
+    tree = b["tree"] if b.get("tree") is not None else np.zeros(n, np.uint8)
+    aff = b["affine"] if b.get("affine") is not None else np.zeros(n, np.uint8)
+    cbf = np.where(pm == 2, 0, np.where(tree == 1, 1, np.where(tree == 2, 6, 7))).astype(np.uint8)      # a skipped CU has no coefficients
+    b["cbf"] = cbf
+    ats = np.zeros(n, np.uint8)
+    if spec.get("ats"):
+        turn = {}      # the four type pairs in turn per CU shape
+        for i in np.nonzero((pm == MODE_INTRA) & (lw <= 5) & (lh <= 5) & ((cbf & 1) != 0))[0]:
+            k = turn.get((lw[i], lh[i]), seed)
+            turn[(lw[i], lh[i])] = k + 1
+            ats[i] = 1 | ((k % 4) << 1)
+    b["ats"] = ats if ats.any() else None
+    ai = np.zeros(n, np.uint8)
+    if spec.get("ats_inter"):
+        turn = {}      # every idx the shape admits at both positions in turn per CU shape
+        for i in np.nonzero((pm != MODE_INTRA) & (pm != 6) & (cbf != 0) & (lw <= 6) & (lh <= 6) & (aff == 0))[0]:
+            avail = [j + 1 for j, a in enumerate((lw[i] >= 3, lh[i] >= 3, lw[i] >= 4, lh[i] >= 4)) if a]      # xevdm_check_ats_inter_info_coded, xevdm_util.c:3565-3583
+            if avail:
+                k = turn.get((lw[i], lh[i]), 0)
+                turn[(lw[i], lh[i])] = k + 1
+                ai[i] = avail[k % len(avail)] | (((k // len(avail)) & 1) << 4)
+    b["ats_inter"] = ai if ai.any() else None
+    top = 51 + 6 * (bd - 8)
+    kk = np.arange(n, dtype=np.int64) + seed
+    b["qp"] = np.stack([6 * (bd - 8) + (kk * 7 + 3) % 52, (kk * 5 + 1) % (top + 1), (kk * 11 + 2) % (top + 1)], 1).astype(np.uint8)
+    big = (lw > 6) | (lh > 6)
+    if big.any():
+        sub = np.zeros(n, np.uint16)
+        for i in np.nonzero(big)[0]:
+            exists = [sb for sb in range(4) if (sb & 1) < (2 if lw[i] > 6 else 1) and (sb >> 1) < (2 if lh[i] > 6 else 1)]
+            for c in range(3):
+                if (cbf[i] >> c) & 1:
+                    keep = [sb for j, sb in enumerate(exists) if not (spec.get("drop_sub") and (i + c) & 1 and j == (i >> 1) % len(exists))]
+                    sub[i] |= sum(1 << sb for sb in keep) << (4 * c)
+        b["cbf_sub"] = sub
+    else:
+        b["cbf_sub"] = None
+    idx = ai & 15
+    tu = (1 << (lw - np.where(idx == 1, 1, np.where(idx == 3, 2, 0)))) * (1 << (lh - np.where(idx == 2, 1, np.where(idx == 4, 2, 0))))
+    size = tu * (cbf & 1) + (tu // 4) * ((cbf >> 1) & 1) + (tu // 4) * ((cbf >> 2) & 1)
+    b["coef_off"] = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.uint32)
+    b["n_coef"] = int(size.sum())
+    coef = np.zeros(max(b["n_coef"], 1), np.int16)
+    count, singles = {}, {}
+    for (i, k, sb, tw, th, cl, off, tr, qp) in residual_tbs(b):
+        g = ri.itdq_group(tw, th)
+        c = count.get((tw, th, tr), 0)
+        count[(tw, th, tr)] = c + 1
+        run = 4 * g if g <= 8 else g
+        kinds = RESIDUAL_KINDS if max(tw, th) < 6 else RESIDUAL_KINDS_64
+        kind = kinds[(c // run + tw + 2 * th + seed) % len(kinds)]
+        w, h = 1 << tw, 1 << th
+        if kind == "single":      # the row pair walks with the singles of this height, the column pair with those of this width (the census counts them per dimension)
+            a, d = singles.get(("h", th), 9 * seed), singles.get(("w", tw), 9 * seed + 4)
+            singles[("h", th)], singles[("w", tw)] = a + 1, d + 1
+            blk = ri.single(tw, th, [qp], bd, iqt, tr, start=c, at=((2 * a + (a // (h // 2) & 1)) % h, (2 * d + (d // (w // 2) & 1)) % w))[0]
+        else:
+            blk = ri.fill_tb(kind, c + ((c // (4 * run)) * g if g > 8 else 0), tw, th, qp, bd, iqt, tr, "defined")      # (small classes: the kind of item moves on with every round)
+        rows = off + (np.arange(h)[:, None] << cl) + np.arange(w)[None, :]
+        coef[rows] = blk
+    b["coef"] = coef
+
+
+def regenerate_residual_batch(case, seed, gen):
+    """Replace the case's batch by one that synth.gen_frame draws on htdf_partition (gen: its keyword arguments + 'rot', 'rtl', 'all128'), as drawn: set_residual then gives
+    it its coded flags, transforms, QPs and levels"""
+    from xevd_amd import synth
+    gen = dict(gen)
+    rot, rtl, all128 = gen.pop("rot", 0), gen.pop("rtl", False), gen.pop("all128", False)
+    old = case["batch"]
+    b = synth.gen_frame(np.random.default_rng(seed + 31 * rot), case["w"], case["h"], case["bd"], log2_ctu=case["log2_ctu"], eipd=bool(case["eipd"]),
+                        partition=htdf_partition(case["w"], case["h"], case["log2_ctu"], rot, rtl, False, all128), **gen)
+    b["constrained_intra_pred"] = old.get("constrained_intra_pred", 0)
+    if old.get("htdf_slice_qp"):
+        b["htdf_slice_qp"] = old["htdf_slice_qp"]
+    case["batch"] = b
+
+
 PER_CU = ("x", "y", "log2w", "log2h", "pred_mode", "refi", "mv", "qp", "cbf", "coef_off", "ipm", "ats", "ats_inter", "affine", "affine_mv", "dmvr", "tree", "cbf_sub")
 
 
@@ -1003,7 +1134,8 @@ def apply(case, spec, seed=0):
               'partition': synth.gen_frame arguments for a batch on dmvr_partition, 'affine_partition': the same on affine_partition (+ 'rot'),
               'affine': 'sizes' | 'eif' | 'trans' | 'limits' | 'wide' | 'tall' (set_affine), 'affine_start': the first variant, 'intra_start': added to the seed of set_intra_modes,
               'htdf_partition': the same on htdf_partition (+ 'rot', 'rtl', 'dual', 'all128'), 'ibc': (kind of IBC_WANTS, share of the CUs) for set_ibc_vectors,
-              'intra': 'eipd' | 'base' for set_intra_modes (the modes of the intra CUs, assigned last: tiles and copies are in place) }"""
+              'intra': 'eipd' | 'base' for set_intra_modes (the modes of the intra CUs, assigned last: tiles and copies are in place),
+              'residual_partition': synth.gen_frame arguments for a batch on htdf_partition as drawn (+ 'rot', 'rtl', 'all128'), 'residual': set_residual's spec }"""
     w, h, bd = case["w"], case["h"], case["bd"]
     base = 7919 * (seed + 1)
     if spec.get("partition") is not None:
@@ -1012,6 +1144,8 @@ def apply(case, spec, seed=0):
         regenerate_affine_batch(case, base + 500, spec["affine_partition"])
     if spec.get("htdf_partition") is not None:
         regenerate_htdf_batch(case, base + 500, spec["htdf_partition"])
+    if spec.get("residual_partition") is not None:
+        regenerate_residual_batch(case, base + 500, spec["residual_partition"])
     kinds = spec.get("content")
     if kinds is not None:
         done = {}
@@ -1054,6 +1188,8 @@ def apply(case, spec, seed=0):
         set_affine(b, spec["affine"], w, h, seed, spec.get("affine_start", 0))
     if spec.get("levels") == "dense":
         set_dense_levels(b)
+    if spec.get("residual") is not None:
+        set_residual(case, spec["residual"], seed + int(spec["residual"].get("start", 0)))
     if spec.get("alf") is not None and case.get("alf_params") is not None:
         kind, ctb = spec["alf"]
         old = case["alf_params"]
@@ -1218,6 +1354,30 @@ EXTREME_CASES = [
     ("x_ip_base_side128_b_10b", 264, 264, 10, 0, 0, (1, 0), 0.0, {"log2_ctu": 7, "amp": 40.0, "extreme": {"htdf_partition": dict(_IGEN, rot=4, all128=True, admvp=False, n_refs=(1, 0), amp=40.0, coded_frac=0.9), "start": "ladder", "intra": "base", "intra_start": 1}}, ("ip_side128",)),
     ("x_ip_base_side128_c_8b", 264, 264, 8, 0, 0, (1, 0), 0.0, {"log2_ctu": 7, "extreme": {"htdf_partition": dict(_IGEN, rot=8, all128=True, admvp=False, n_refs=(1, 0)), "start": "gratings", "intra": "base", "intra_start": 2}}, ("ip_side128",)),
 ]
+
+# ---- the residual pass at every branch of its arithmetic (set_residual on htdf_partition: every luma class of 4 .. 64 a side and every chroma class of 2 .. 32, CUs above 64 with
+# CTU 128; tests/test_oracle_extremes.py: test_residual_cases_together_reach_every_branch).  Both profiles' intermediates, ATS on intra CUs and in ATS-inter TUs with and without
+# IQT, every QP of each bit depth; x_res_ctu128_htdf_10b has HTDF nodes (the residual pass is queued on the side stream), the others none and intra CUs throughout (queued ahead,
+# it rides in the intra launch).  Above 8 bit the cases have ADDB: the luma QP walks down to 0, where the Baseline deblocking filter's chroma strength of the reference is
+# read at qp + the picture's V offset of -2, in front of its table.
+_RGEN = {"inter_frac": 0.5, "bi_frac": 0.3, "n_refs": (1, 1), "oob_frac": 0.0, "admvp": True, "coded_frac": 0.9}
+RESIDUAL_CASES = [
+    ("x_res_base_8b", 264, 200, 8, 0, 0, (1, 0), 0.0, {"extreme": {"residual_partition": dict(_RGEN, admvp=False, n_refs=(1, 0), rot=0), "residual": {}, "content": "noise", "start": "gratings"}},
+     ("it_s32", "it_high")),
+    ("x_res_ats_intra_10b", 264, 264, 10, 1, 1, (1, 1), 0.3, {"eipd": 1, "addb": 1, "extreme": {"residual_partition": dict(_RGEN, inter_frac=0.0, rot=1), "residual": {"ats": 1, "start": 1}, "start": "noise"}},
+     ("it_ats_pairs", "it_stage1_clip", "it_final_clip", "it_cmax")),
+    ("x_res_ats_inter_10b", 264, 264, 10, 1, 1, (1, 1), 0.3, {"addb": 1, "alf": 1, "extreme": {"residual_partition": dict(_RGEN, inter_frac=1.0, rot=2, rtl=True), "residual": {"ats_inter": 1, "start": 2}, "content": "noise"}},
+     ("it_ats_inter", "it_stage1_clip", "it_high")),
+    ("x_res_qp_12b", 264, 200, 12, 1, 1, (1, 1), 0.3, {"eipd": 1, "addb": 1, "extreme": {"residual_partition": dict(_RGEN, rot=3), "residual": {"ats": 1, "ats_inter": 1, "start": 3}, "content": "rails_dither", "start": "noise"}},
+     ("it_qp_12b", "it_cmax", "it_stage1_clip", "it_final_clip")),
+    ("x_res_ats_noiqt_8b", 264, 264, 8, 1, 0, (1, 1), 0.3, {"extreme": {"residual_partition": dict(_RGEN, rot=4), "residual": {"ats": 1, "ats_inter": 1, "start": 4}, "content": "noise"}},
+     ("it_ats_pairs", "it_ats_inter", "it_s32")),
+    ("x_res_ctu128_htdf_10b", 264, 264, 10, 1, 1, (1, 1), 0.3, {"log2_ctu": 7, "htdf_qp": 32, "addb": 1, "extreme": {"residual_partition": dict(_RGEN, rot=0, all128=True), "residual": {"drop_sub": 1, "start": 5}, "content": "noise"}},
+     ("it_strided", "it_high")),
+    ("x_res_ctu128_noiqt_12b", 264, 264, 12, 1, 0, (1, 1), 0.3, {"log2_ctu": 7, "eipd": 1, "addb": 1, "extreme": {"residual_partition": dict(_RGEN, rot=0, rtl=True), "residual": {"ats": 1, "start": 6}, "start": "ladder"}},
+     ("it_strided", "it_s32", "it_final_clip")),
+]
+EXTREME_CASES += RESIDUAL_CASES
 
 # the cases written for the branches of the DMVR search (tests/test_oracle_extremes.py: test_dmvr_cases_together_reach_every_branch)
 DMVR_CASES = [s for s in EXTREME_CASES if "dmvr_pair" in s[8].get("extreme", {})]

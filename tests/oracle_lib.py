@@ -53,7 +53,12 @@ class OrcCensus(C.Structure):
                 ("ip_plan", ((C.c_uint32 * 6) * 6) * 2), ("ip_plan_clip", C.c_uint32 * 2), ("ip_bi_form", C.c_uint32 * 3), ("ip_bi_corner", (C.c_uint32 * 2) * 2), ("ip_bi_wc", C.c_uint32 * 6),
                 ("ip_bi_clip", C.c_uint32 * 2), ("ip_hor", C.c_uint32 * 3), ("ip_ang_src", (C.c_uint32 * 3) * 3), ("ip_ang_frac", C.c_uint32 * 2), ("ip_ang_clamp", C.c_uint32 * 2),
                 ("ip_ang_clip", C.c_uint32 * 2), ("ip_nbr", (((C.c_uint32 * 3) * 2) * 3) * 2), ("ip_unavail", C.c_uint32 * 4), ("ip_corner", C.c_uint32 * 3), ("ip_tree", C.c_uint32 * 3),
-                ("ip_cbf", C.c_uint32 * 8)]
+                ("ip_cbf", C.c_uint32 * 8),
+                ("it_tb", ((C.c_uint32 * 6) * 6) * 3), ("it_plane", (C.c_uint32 * 3) * 3), ("it_ats_pair", (C.c_uint32 * 2) * 2), ("it_ats_shape", (((C.c_uint32 * 4) * 4) * 2) * 2),
+                ("it_ats_inter", ((C.c_uint32 * 2) * 2) * 4), ("it_strided", C.c_uint32 * 4), ("it_qp", C.c_uint32 * 96), ("it_dq_clip", (C.c_uint32 * 2) * 2), ("it_dq_zero", C.c_uint32 * 2),
+                ("it_dq_cmax", (C.c_uint32 * 2) * 2), ("it_high", C.c_uint32 * 2), ("it_s1_clip", (C.c_uint32 * 2) * 2), ("it_s1_negfrac", C.c_uint32), ("it_s1_mag", C.c_uint32 * 5),
+                ("it_s2_clip", (C.c_uint32 * 2) * 3), ("it_s2_undef", C.c_uint32), ("it_undef_tb", C.c_uint32), ("it_nz_pairs", (C.c_uint32 * 5) * 2), ("it_single", (C.c_uint32 * 32) * 32),
+                ("it_single_dim", ((C.c_uint32 * 32) * 3) * 2)]
 
 
 def census_reset():
@@ -92,6 +97,9 @@ def oracle():
         lib.orc_mc_l.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 6
         lib.orc_mc_c.argtypes = lib.orc_mc_l.argtypes
         lib.orc_itdq.argtypes = [C.c_void_p] + [C.c_int] * 5
+        lib.orc_itdq_ats.argtypes = [C.c_void_p] + [C.c_int] * 7
+        lib.orc_ats_tm.restype = C.POINTER(C.c_int16)
+        lib.orc_ats_tm.argtypes = [C.c_int, C.c_int]
         lib.orc_tm.restype = C.POINTER(C.c_int8)
         lib.orc_tm.argtypes = [C.c_int]
         lib.orc_recon.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]

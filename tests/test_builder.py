@@ -391,3 +391,42 @@ def test_builder_takes_a_cu_of_4x128():
         b = synth.gen_frame(np.random.default_rng(3), 128, 128, 10, log2_ctu=7, inter_frac=0.0, eipd=bool(eipd), partition=part)
         cb, keep = abi.make_cu_batch(b)
         assert _build(lib, abi.make_seq_params(128, 128, 10, log2_ctu=7, eipd=eipd), cb, 1)[10 + 3] == n * (2 if eipd else 1)      # (512 samples: two parts under EIPD, one under the Baseline predictors)
+
+
+def _residual_specs():
+    import extreme_inputs as xi
+    return xi.RESIDUAL_CASES
+
+
+@pytest.mark.parametrize("spec", _residual_specs(), ids=[s[0] for s in _residual_specs()])
+def test_builder_residual_work_items_follow_the_oracle_census(spec):
+    """The builder sorts the TBs by size class and transform pair and cuts each list into work items of itdq_group TBs.  Held to the oracle's per-TB census: the TBs
+    through the ATS matrices by pair and shape (it_ats_shape), the others - DCT-II - as the rest of it_tb, give the number of TBs and, summed over class and pair,
+    ceil(TBs / itdq_group) work items; and the test side's restatement of the TB walk (extreme_inputs.residual_tbs, which placed the levels) counts the same lists.  On one
+    and on four builder threads, with identical digests."""
+    import cases
+    import extreme_inputs as xi
+    import oracle_lib as ol
+    import residual_inputs as ri
+    cs = cases.build_case(*spec[:9])
+    ol.census_reset()
+    cases.run_cpu("oracle", cs, deblock=False, pad=False)
+    cen = ol.census()
+    ats = np.zeros((2, 2, 6, 6), np.int64)
+    ats[:, :, 1:5, 1:5] = cen["it_ats_shape"]
+    dct2 = cen["it_tb"].sum(0) - ats.sum((0, 1))
+    assert (dct2 >= 0).all()
+    items = sum(-(-int(n) // ri.itdq_group(lw + 1, lh + 1)) for lists in (dct2[None], ats.reshape(4, 6, 6)) for lst in lists for (lw, lh), n in np.ndenumerate(lst))
+    walk = {}
+    for (i, k, sb, tw, th, cl, off, tr, qp) in xi.residual_tbs(cs["batch"]):
+        walk[(tw, th, tr)] = walk.get((tw, th, tr), 0) + 1
+    for (tw, th, tr), n in walk.items():
+        assert n == (dct2[tw - 1, th - 1] if tr == (0, 0) else ats[tr[0] - 1, tr[1] - 1, tw - 1, th - 1]), ("TBs of a class and pair: the test side's walk against the census", tw, th, tr)
+    assert sum(walk.values()) == cen["it_tb"].sum()
+    lib = _lib()
+    sp = abi.make_seq_params(cs["w"], cs["h"], cs["bd"], log2_ctu=cs["log2_ctu"], iqt=cs["iqt"], admvp=cs["admvp"], addb=cs["addb"], alf=cs["alf"], eipd=cs["eipd"])
+    cb, keep = abi.make_cu_batch(cs["batch"])
+    one, four = _build(lib, sp, cb, 1), _build(lib, sp, cb, 4)
+    assert one[10 + 1] == cen["it_tb"].sum(), "transform blocks"
+    assert one[10 + 2] == items, "work items of the residual pass"
+    assert one == four, "one and four builder threads"

@@ -8,7 +8,10 @@ filter-only inter node in every decoding order, right to left included, the slic
 uneven tile grid with local dual trees; also with the residual pass ahead - without the ride-along launch - and twice on one decoder) and of intra block copy (xi.IBC_CASES: vectors of
 every parity and sign, sources over many CUs, inside filtered CUs and inside other copies), every intra predictor under every launch form (xi.INTRA_CASES: both neighbour-staging
 schemes, the right-column forms, 1 to 16 parts per CU; also with the residual pass riding in the data-flow launch - k_intra_itdq, each value of EIPD, of copies and of IQT at least once -, through k_intra_l1's
-16-lane body, twice on one decoder, and inside a tile grid with local dual trees) - all three padded planes and the residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
+16-lane body, twice on one decoder, and inside a tile grid with local dual trees), every branch of the residual pass (xi.RESIDUAL_CASES: levels aimed at each side of the
+dequantiser's clips, of the first stage's s16 clip and of the final clip, single levels in every row and column pair up to position 63, work items that mix dense and
+near-empty TBs, ATS on intra CUs and in ATS-inter TUs with and without IQT, every QP, sub-blocks that keep their CU's stride; also riding in the data-flow intra launch -
+k_intra_itdq's own copy of the body and tables - and twice on one decoder) - all three padded planes and the residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
 reach the branches they are for) are repeated here because this file needs only the oracle, which always ships."""
 import numpy as np
 import pytest
@@ -18,6 +21,7 @@ import extreme_inputs as xi
 import oracle_lib as ol
 from test_oracle_extremes import TILED_STREAMS_REACHING_INTERIOR_BORDERS, check_census, check_htdf_tile_census, check_intra_tile_census, check_tile_census, run_oracle_with_census
 from test_oracle_extremes import INTRA_L1_CASES, INTRA_L1_LONG, intra_surely_level1
+from test_oracle_extremes import check_residual_together, residual_census_together
 
 pytestmark = pytest.mark.gpu
 
@@ -251,6 +255,28 @@ def test_gpu_intra_tile_case(spec):
     assert np.array_equal(res[:len(rr)], rr), "residual arena"
     _same(out, ref, spec[0])
     _same(cases.run_gpu(cs, ahead=True), ref, spec[0] + " (ahead)")
+
+
+# ---- the residual pass: the cases of xi.RESIDUAL_CASES (every branch of the dequantiser and of both transform stages, test_residual_cases_together_reach_every_branch) - planes,
+# residual arena and the tags' census in test_gpu_extreme_case above, those with ADDB also in test_gpu_extreme_case_scalar_deblocking.  Here the other copy of the body and
+# its tables, and the census of the cases together.
+@pytest.mark.parametrize("spec", xi.RESIDUAL_CASES, ids=[s[0] for s in xi.RESIDUAL_CASES])
+def test_gpu_residual_case_residual_pass_ahead(spec):
+    """queued with the previous picture's kernels the residual pass rides in the data-flow intra launch: k_intra_itdq's instantiation of itdq_body.h with that translation
+    unit's own constant tables (the case with HTDF nodes takes the side stream instead).  Residual arena and planes."""
+    _check(cases.build_case(*spec[:9]), spec[0] + " (ahead)", resid=True, ahead=True)
+
+
+@pytest.mark.parametrize("name", ["x_res_ats_intra_10b", "x_res_ctu128_noiqt_12b"])
+def test_gpu_residual_case_decoded_twice_on_one_decoder(name):
+    """as test_gpu_htdf_case_decoded_twice_on_one_decoder: the second decode's residual pass runs on workgroups whose LDS the first one filled"""
+    test_gpu_htdf_case_decoded_twice_on_one_decoder(name)
+
+
+def test_gpu_residual_cases_reach_every_branch():
+    """the census assertions of tests/test_oracle_extremes.py over the residual cases together, repeated where only the oracle is needed"""
+    it, by_bd, built = residual_census_together()
+    check_residual_together(it, by_bd, built)
 
 
 # content kind x bit depth x partition depth per coding family.  split_prob low / high: k_inter's region and tile roles / its split role see the saturated windows

@@ -77,15 +77,25 @@ the Baseline predictors in both profiles, all-intra and mixed pictures).  The ce
 mutations of the oracle's predictors and neighbour builders - all caught but the two clips shown to change nothing - and the oracle's timing against the parent:
 profiles/intra_census.txt.  The angular predictor's final clip was expected to be unreachable and is; the bilinear one's upper half was not expected and is reached from 10 bit on.
 
+The residual pass (xi.RESIDUAL_CASES: set_residual puts the four block kinds of tests/residual_inputs.py - single levels, blocks whose terms all add at one output aimed at
+each side of each clip, the dequantiser's threshold levels, work items mixing dense and near-empty TBs - on every TB of htdf_partition's shapes, with ATS and ATS-inter TUs in
+turn and every QP).  Block level: the same generators through the reference's own dequantiser, transform tables and ATS stages on all 36 classes
+(test_residual_blocks_oracle_equals_reference); the blocks beyond the range on which the reference's 32-bit second stage is defined are left out, by the oracle's own
+it_s2_undef.  The census over the cases (it_*), what is asserted empty or out of reach and why: profiles/residual_census.txt.  No intermediate reaches 2^27, let alone the
+2^28 the kernel's split allows; the hold of the 32-bit dequantiser cannot be told from half its value up to 12 bit.
+
 The census (which needs only the oracle) and the generator checks run everywhere; the comparison against the reference carries the `ref` mark and is skipped
 where oracle/_ref is not built, like tests/test_oracle_vs_ref.py.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import cases
 import extreme_inputs as xi
 import oracle_lib as ol
+import residual_inputs as ri
 
 # rows of CLIP_TAB (indexA) that hold the same clip values: the classes a chroma index must be seen in
 CLIP_ROW_CLASSES = [range(17, 21), range(21, 23), range(23, 27), range(27, 31), range(31, 33), [33], [34], range(35, 37), [37], range(38, 40)] + [[i] for i in range(40, 52)]
@@ -362,6 +372,19 @@ REQUIRE = {
     "mv_clip": lambda cen, cs: _all(cen["mv_clip"], "vectors moved by the MV clip [left, right, top, bottom]"),
     "recon_rails": _recon_rails,
     "recon_wrap": lambda cen, cs: _all([cen["recon_wrap"]], "prediction + residual sums that wrapped in s16"),
+    # the residual pass (xi.RESIDUAL_CASES; what the cases reach together: test_residual_cases_together_reach_every_branch)
+    "it_s32": lambda cen, cs: _all([cen["it_s1_negfrac"], cen["it_s1_mag"][0], cen["it_s1_mag"][1], cen["it_s1_mag"][2]],
+                                   "32-bit intermediates: negative with low bits, magnitude below 2^15 / 2^24 / 2^27"),
+    "it_high": lambda cen, cs: _all(cen["it_high"], "levels at positions 32 .. 63 [vertical, horizontal]"),
+    "it_final_clip": lambda cen, cs: _all(cen["it_s2_clip"][[cs["iqt"]] + [2] * (cs["batch"].get("ats") is not None and cs["bd"] == 12)],
+                                          "final clip [low, high] of the sequence's DCT-II arithmetic, and at 12 bit (where an ATS block from 8 wide reaches it, at 10 bit one of 32 only) of ATS"),
+    "it_stage1_clip": lambda cen, cs: _all(cen["it_s1_clip"][0] if cs["batch"].get("ats") is None and cs["batch"].get("ats_inter") is None else cen["it_s1_clip"].reshape(-1),
+                                           "stage-1 clip [IQT low, high, ATS low, high]"),
+    "it_ats_pairs": lambda cen, cs: _all(cen["it_ats_pair"].reshape(-1), "ATS TBs by type pair"),
+    "it_ats_inter": lambda cen, cs: _all(cen["it_ats_inter"].sum(2).reshape(-1), "ATS-inter TUs by [idx - 1][pos]"),
+    "it_cmax": lambda cen, cs: _all(cen["it_dq_cmax"][0], "levels at 2^23 >> (qp / 6) and one beyond (even classes)"),
+    "it_qp_12b": lambda cen, cs: _all(cen["it_qp"][:76], "TBs by QP 0 .. 75"),
+    "it_strided": lambda cen, cs: _all([cen["it_strided"].sum()], "sub-blocks that keep their CU's stride"),
 }
 
 
@@ -927,3 +950,233 @@ def test_alf_extreme_coefficients_are_at_the_legal_limit():
             assert 2 * f[:-1].sum() + f[-1] == 512 and f[:-1].min() >= -512 and f[:-1].max() <= 511 and -1024 <= f[-1] <= 1023
     assert np.abs(xi.alf_params("extreme", 3, 6)["luma_coef"][:, :12]).min() >= 511
     assert xi.alf_params("smooth", 3, 6)["luma_coef"][0, 12] == -1024 and xi.alf_params("single", 3, 6)["luma_coef"][0, 12] == 1022
+
+
+# ------------------------------------------------------------------------------------------------ the residual pass
+_CEN = ol.OrcCensus()
+
+
+def _undef_count():
+    """the oracle's count of second-stage sums the reference leaves undefined, without converting the whole census"""
+    ol.oracle().orc_census_get(C.byref(_CEN))
+    return int(_CEN.it_s2_undef)
+
+
+def _clip_counts():
+    """the oracle's dequantiser clips [below, above], both parities, without converting the whole census"""
+    ol.oracle().orc_census_get(C.byref(_CEN))
+    return np.array([_CEN.it_dq_clip[0][0] + _CEN.it_dq_clip[1][0], _CEN.it_dq_clip[0][1] + _CEN.it_dq_clip[1][1]], np.int64)
+
+
+def ref_blocks(coef, lw, lh, qps, bd, iqt, tr=(0, 0)):
+    """the reference's own dequantiser and transforms on blocks of one class, through its function tables (xevd_tbl_itxb, xevdm_tbl_itx) and its ATS stage functions"""
+    lib = ol.ref()
+    lib.xevd_dquant.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_uint8]
+    w, h, n = 1 << lw, 1 << lh, 1 << (lw + lh)
+    f_itxb = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int)
+    f_itx = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int, C.c_int)
+    f_ats = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int)
+    if tr != (0, 0):
+        lib.xevdm_init_multi_tbl()
+        stage = [f_ats((f"xevdm_itrans_ats_intra_{'DST7' if t == 1 else 'DCT8'}_B{1 << l}", lib)) for t, l in ((tr[0], lh), (tr[1], lw))]
+    elif iqt:
+        itx = (C.c_void_p * 6).in_dll(lib, "xevdm_tbl_itx")
+        stage = [f_itx(itx[lh - 1]), f_itx(itx[lw - 1])]
+    else:
+        itxb = (C.c_void_p * 6).in_dll(lib, "xevd_tbl_itxb")
+        stage = [f_itxb(itxb[lh - 1]), f_itxb(itxb[lw - 1])]
+    out = np.ascontiguousarray(coef, np.int16).copy()
+    flat = out.reshape(-1)
+    t16, t32 = np.zeros(n, np.int16), np.zeros(n, np.int32)
+    for i, qp in enumerate(qps):
+        p = C.c_void_p(flat.ctypes.data + 2 * i * n)
+        shift = bd - 9 + ((lw + lh) >> 1) + 8 * ((lw + lh) & 1)
+        lib.xevd_dquant(p, lw, lh, ri.SCALE[iqt][int(qp) % 6] << (int(qp) // 6), (1 << (shift - 1)) if shift else 0, shift)
+        if tr != (0, 0):
+            stage[0](p, t16.ctypes.data_as(C.c_void_p), 7, w, 0, 0)
+            stage[1](t16.ctypes.data_as(C.c_void_p), p, 20 - bd, h, 0, 0)
+        elif iqt:
+            stage[0](p, t16.ctypes.data_as(C.c_void_p), 7, w)
+            stage[1](t16.ctypes.data_as(C.c_void_p), p, 20 - bd, h)
+        else:
+            stage[0](p, t32.ctypes.data_as(C.c_void_p), 0, w, 0)
+            stage[1](t32.ctypes.data_as(C.c_void_p), p, 27 - bd, h, 1)
+    return out
+
+
+def _pin_blocks(kind, lw, lh, bd, iqt, tr, tally=None):
+    """one generator on one class: the oracle equals the reference on every block the reference is defined on, and the oracle's counter of undefined sums is non-zero on
+    exactly the blocks that residual_inputs' model puts beyond 2^31.  -> (blocks pinned, blocks left out).
+    thresholds: per QP the dequantiser's clip counters move exactly where a level that clips fits s16 (threshold_levels skips the others); `tally` counts the
+    (class, QP, side) triples of either kind"""
+    if kind == "thresholds":      # every representable threshold level of every QP
+        blk, qps = ri.thresholds_all(lw, lh, bd, iqt, range(ri.qp_top(bd) + 1))
+        n = len(qps)
+    else:
+        n = ri.n_blocks_for(kind, lw, lh)
+        qps = ri.walk_qps(n, bd, start=lw + 2 * lh)
+        blk = ri.blocks(kind, lw, lh, qps, bd, iqt, tr)
+    s32 = not iqt and tr == (0, 0)
+    undef = np.zeros(n, bool)
+    got = np.zeros_like(blk)
+    clipped = np.zeros((n, 2), bool)
+    for i in range(n):
+        before, clips = _undef_count(), _clip_counts()
+        got[i] = ri.oracle_blocks(blk[i:i + 1], lw, lh, qps[i:i + 1], bd, iqt, tr)[0]
+        undef[i] = _undef_count() != before
+        clipped[i] = _clip_counts() != clips
+    if kind == "thresholds":
+        for qp in range(ri.qp_top(bd) + 1):
+            names = {nm for nm, _ in ri.threshold_levels(lw, lh, qp, bd, iqt)}
+            assert {"lo_clip", "lo_clip!"} & names and {"hi_clip", "hi_clip!"} & names
+            for side, nm in enumerate(("lo_clip", "hi_clip")):
+                reach = nm in names      # (else it is there as nm + "!": beyond s16, not fed)
+                assert clipped[np.asarray(qps) == qp, side].any() == reach, (lw, lh, bd, iqt, "qp", qp, nm, "reachable" if reach else "out of reach", "and the clip counter disagrees")
+                if tally is not None:
+                    tally["reach" if reach else "unreach"] += 1
+    if s32:
+        model_says = np.array([ri.model(blk[i].astype(np.int64), lw, lh, int(qps[i]), bd, iqt, tr)["undef"] >= 1 << 31 for i in range(n)])
+        assert np.array_equal(undef, model_says), (kind, lw, lh, bd, "the oracle's undefined blocks are not the ones aimed beyond 2^31", np.nonzero(undef != model_says)[0][:4])
+    else:
+        assert not undef.any()
+    keep = np.nonzero(~undef)[0]      # a condition, not a measurement: every pinned block has the counter at 0
+    exp = ref_blocks(blk[keep], lw, lh, qps[keep], bd, iqt, tr)
+    bad = np.nonzero((exp != got[keep]).reshape(len(keep), -1).any(1))[0]
+    assert bad.size == 0, (kind, lw, lh, bd, iqt, tr, "first differing block", int(keep[bad[0]]), "qp", int(qps[keep[bad[0]]]))
+    return len(keep), int(undef.sum())
+
+
+@pytest.mark.ref
+@pytest.mark.parametrize("lw", range(1, 7))
+@pytest.mark.parametrize("iqt", [0, 1])
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_residual_blocks_oracle_equals_reference(bd, iqt, lw):
+    """every block generator of residual_inputs on every class (this width, all heights) through the reference's own dequantiser and transform tables, both scale tables
+    (iqt picks the table), and through its ATS stage functions for the four type pairs on 4 .. 32: orc_itdq / orc_itdq_ats bit-exact.  Blocks aimed beyond the range on
+    which the reference's 32-bit second stage is defined are left out, and they are exactly the blocks on which the oracle's it_s2_undef moves."""
+    ol.census_reset()
+    pinned = left_out = 0
+    tally = {"reach": 0, "unreach": 0}
+    for lh in range(1, 7):
+        for kind in ri.GENERATORS:
+            a, b = _pin_blocks(kind, lw, lh, bd, iqt, (0, 0), tally)
+            pinned, left_out = pinned + a, left_out + b
+            if 2 <= lw <= 5 and 2 <= lh <= 5:
+                for tr in ri.ATS_PAIRS:
+                    a, b = _pin_blocks(kind, lw, lh, bd, iqt, tr)
+                    pinned, left_out = pinned + a, left_out + b
+    cen = ol.census()
+    print("pinned", pinned, "left out", left_out, "it_s1_mag", cen["it_s1_mag"].tolist(), "it_s2_clip", cen["it_s2_clip"].tolist(), "it_s1_clip", cen["it_s1_clip"].tolist())
+    assert (left_out > 0) == (not iqt), "the 32-bit intermediate has blocks beyond the defined range, the s16 one none"
+    _all(cen["it_dq_clip"].reshape(-1), "dequantiser clips [even, odd] x [below, above]")
+    # ... per (class, QP) the clip counters moved exactly where the first level that clips fits s16 (_pin_blocks).  Both kinds occur: every class has QPs at which levels
+    # clip, and a (class, QP) at which none does exists where even 32767 stays inside at QP 0 - never at 8 bit, from 32x32 (the odd classes: 16x32) on at 10 bit, from 8x8 at 12 bit
+    none_clips = any((32767 * ri.dq_params(lw, lh, 0, bd, iqt)[0] + ri.dq_params(lw, lh, 0, bd, iqt)[2]) >> ri.dq_params(lw, lh, 0, bd, iqt)[1] <= 32767 for lh in range(1, 7))
+    assert tally["reach"] > 0 and (tally["unreach"] > 0) == none_clips, (tally, none_clips)
+    assert bd > 8 or not none_clips
+    print("thresholds: (class, QP, side) with a level that clips", tally["reach"], "without", tally["unreach"])
+    # thresholds that no s16 level reaches are skipped by the generator, and both kinds occur.  A non-zero level dequantises to 0 where the smallest multiplier,
+    # 40 (times 181 for an odd class) at QP 0, stays below half the divisor 2^shift: classes from 32x32 at 10 bit and from 8x8 at 12 bit, the odd ones from 32x64 at 10
+    # bit and 8x16 at 12 bit, none at 8 bit.  The levels around 2^23 >> (qp / 6) fit s16 from QP 54 on, 10 and 12 bit; at 8 bit the bound is 32768 from QP 48 on, which
+    # -32768 meets and nothing passes.
+    for parity in range(2):
+        reach = any(40 * (181 if parity else 1) < 1 << (bd - 9 + ((lw + lh) >> 1) + 8 * parity - 1) for lh in range(1, 7) if (lw + lh) & 1 == parity and bd - 9 + ((lw + lh) >> 1) >= 1)
+        assert (cen["it_dq_zero"][parity] > 0) == reach, ("levels that dequantise to 0", parity, reach, cen["it_dq_zero"].tolist())
+    assert (cen["it_dq_cmax"][:, 0] > 0).all() and ((cen["it_dq_cmax"][:, 1] > 0) == (bd > 8)).all(), cen["it_dq_cmax"].tolist()
+    if 2 <= lw <= 5:
+        _all(cen["it_s1_clip"][1], "ATS stage-1 clip")
+    # The final clip is within reach where the largest second-stage sum passes 32767 after its shift: the column sum of |tm| of this width times the largest
+    # intermediate - 32768 for the s16 one (shift 20 - bd), the largest first-stage sum over all heights, 3707 * 32768, for the 32-bit one (shift 27 - bd).  Both
+    # kinds must occur over the widths and bit depths (2 wide at 8 bit is out of reach, 64 wide at 12 bit is not): asserted bucket by bucket, reachable or empty.
+    colsum = int(np.abs(ri.matrix(0, lw)).sum(0).max())
+    if iqt:
+        _all(cen["it_s1_clip"][0], "IQT stage-1 clip")
+        reach = (32768 * colsum + (1 << (19 - bd))) >> (20 - bd) > 32767
+        assert (cen["it_s2_clip"][1] > 0).all() == reach and (cen["it_s2_clip"][1].sum() > 0) == reach, ("IQT final clip", reach, cen["it_s2_clip"][1].tolist())
+    else:
+        reach = (3707 * 32768 * colsum + (1 << (26 - bd))) >> (27 - bd) > 32767
+        assert (cen["it_s2_clip"][0] > 0).all() == reach and (cen["it_s2_clip"][0].sum() > 0) == reach, ("final clip of the 32-bit intermediate", reach, cen["it_s2_clip"][0].tolist())
+        _all([cen["it_s1_negfrac"]], "negative intermediates with low bits")
+    # no intermediate of the 32-bit path reaches 2^27: the largest column sum of |xevd_tbl_tm64| is 3707, times 32768 = 121 470 976 < 134 217 728 - the kernel's
+    # "|acc| < 2^28" (itdq_body.h) has a factor of two to spare
+    assert int(np.abs(ri.matrix(0, 6)).sum(0).max()) * 32768 < 1 << 27 and cen["it_s1_mag"][3:].sum() == 0
+    if lw == 6:
+        assert (cen["it_single"] > 0).all(), "64x64: a single level in every (row pair, column pair)"
+        _all(cen["it_high"], "levels at positions 32 .. 63")
+
+
+def residual_reachable(built):
+    """[kind][log2w - 1][log2h - 1] a TB can have, from the geometry of the CUs in these batches alone: a luma TB is the CU up to 64 a side (above: 64), a chroma TB half of
+    it; ATS takes intra CUs of at most 32 a side; an ATS-inter TU is a half or a quarter of an inter CU of 8 .. 64 a side along one axis (a half needs 8, a quarter 16:
+    xevdm_check_ats_inter_info_coded)"""
+    reach = np.zeros((3, 6, 6), bool)
+    for spec, cs in built:
+        b = cs["batch"]
+        for lw, lh in {(int(a), int(c)) for a, c in zip(b["log2w"], b["log2h"])}:
+            tw, th = min(lw, 6), min(lh, 6)
+            reach[0, tw - 1, th - 1] = reach[0, tw - 2, th - 2] = True
+            if lw <= 5 and lh <= 5 and b.get("ats") is not None:
+                reach[1, lw - 1, lh - 1] = True
+            if lw <= 6 and lh <= 6 and b.get("ats_inter") is not None:
+                for uw, uh in [(lw - 1, lh)] * (lw >= 3) + [(lw - 2, lh)] * (lw >= 4) + [(lw, lh - 1)] * (lh >= 3) + [(lw, lh - 2)] * (lh >= 4):
+                    reach[2, uw - 1, uh - 1] = reach[2, uw - 2, uh - 2] = True
+    return reach
+
+
+def residual_census_together():
+    def add(a, b):
+        return b if a is None else {k: a[k] + b[k] for k in b}
+    total, by_bd, built = None, {}, []
+    for spec in xi.RESIDUAL_CASES:
+        cs = cases.build_case(*spec[:9])
+        _, cen = run_oracle_with_census(cs)
+        cen = {k: np.asarray(v) for k, v in cen.items() if k.startswith("it_")}
+        assert cen["it_s2_undef"] == 0 and cen["it_undef_tb"] == 0, (spec[0], "a picture case holds a block the reference is undefined on")
+        total, by_bd[spec[3]] = add(total, cen), add(by_bd.get(spec[3]), cen)
+        built.append((spec, cs))
+    return total, by_bd, built
+
+
+def check_residual_together(it, by_bd, built):
+    reach = residual_reachable(built)
+    # what geometry rules out: no class holds a 2 with a 64 (chroma ends at 32, luma starts at 4), ATS neither 2 nor 64, an ATS-inter TU no 64x64
+    assert not reach[:, 0, 5].any() and not reach[:, 5, 0].any() and not reach[1, 0].any() and not reach[1, :, 5].any() and not reach[2, 5, 5]
+    assert reach[0].sum() == 34 and reach[1].sum() == 16 and reach[2].sum() == 33, reach.sum((1, 2)).tolist()
+    assert ((it["it_tb"] > 0) == reach).all(), f"TBs of every reachable [kind][class], no other: {np.argwhere((it['it_tb'] > 0) != reach).tolist()}"
+    _all(it["it_plane"][0], "DCT-II TBs by plane")
+    _all(it["it_plane"][2], "ATS-inter TUs by plane")
+    assert it["it_plane"][1][0] > 0 and it["it_plane"][1][1:].sum() == 0, "ATS-intra is luma only"
+    _all(it["it_ats_shape"], "every ATS type pair at every size of 4 .. 32, square and not")
+    _all(it["it_ats_inter"], "ATS-inter TUs by [idx - 1][pos][with the ATS transforms / DCT-II (a CU side of 64)]")
+    _all(it["it_strided"], "64x64 (chroma 32x32) sub-blocks that keep their CU's stride, by index")
+    for bd, cen in by_bd.items():
+        top = 51 + 6 * (bd - 8)
+        _all(cen["it_qp"][:top + 1], f"{bd} bit: TBs at every QP of 0 .. {top}")
+        assert cen["it_qp"][top + 1:].sum() == 0
+        assert (cen["it_dq_cmax"] > 0).all() == (bd > 8), (bd, "levels at 2^23 >> (qp / 6) and one beyond, even and odd classes: from QP 54 on", cen["it_dq_cmax"].tolist())
+    _all(it["it_dq_clip"], "dequantiser clips [even, odd] x [below, above]")
+    _all(it["it_dq_zero"], "non-zero levels that dequantise to 0")
+    _all(it["it_high"], "levels at positions 32 .. 63 [vertical, horizontal]")
+    _all(it["it_s1_clip"], "stage-1 clips [IQT, ATS] x [low, high]")
+    _all([it["it_s1_negfrac"]], "negative 32-bit intermediates with non-zero low bits")
+    # the buckets the `defined` rule allows: with one term per second-stage sum (a coefficient column alone) the intermediate may reach 2^31 / 64 = 2^25, so the bucket
+    # 2^24 .. 2^27 is reached; nothing reaches 2^27 at all (test_residual_blocks_oracle_equals_reference)
+    _all(it["it_s1_mag"][:3], "32-bit intermediates below 2^15 / 2^24 / 2^27")
+    assert it["it_s1_mag"][3:].sum() == 0
+    _all(it["it_s2_clip"], "final clips [32-bit, IQT, ATS] x [low, high]")
+    _all(it["it_nz_pairs"], "TBs by non-zero [row, column] pairs: 0 / 1 / 2 .. 4 / 5 or more / all")
+    for d in range(2):
+        for k in range(3):
+            _all(it["it_single_dim"][d][k][:8 << k], f"single levels in every {'row' if d == 0 else 'column'} pair of the {16 << k}-point dimension")
+            assert it["it_single_dim"][d][k][8 << k:].sum() == 0
+
+
+def test_residual_cases_together_reach_every_branch():
+    """the conditions the residual cases were chosen for, over all of them (profiles/residual_census.txt holds this test's output)"""
+    it, by_bd, built = residual_census_together()
+    for k, v in it.items():
+        print(k, v.tolist())
+    check_residual_together(it, by_bd, built)
+    # a case without the Hadamard filter and with enough intra CUs for a data-flow intra launch (the residual pass rides in it when queued ahead), and one with the filter
+    assert any(not cs["batch"].get("htdf_slice_qp") and (cs["batch"]["pred_mode"] == 0).sum() >= 32 for _, cs in built)
+    assert any(cs["batch"].get("htdf_slice_qp") for _, cs in built)

@@ -73,19 +73,30 @@ int xgpu_test_batch_resid(xgpu_ctx *c, xgpu_dbatch *db, int16_t *resid)
     return XGPU_OK;
 }
 
-int xgpu_test_itdq(xgpu_ctx *c, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth)
+// Blocks of one size class and one transform pair through launch_itdq; block i starts at i * (h << log2s) and keeps the row stride 2^log2s.  The whole buffer goes into the
+// coefficient arena AND the residual arena, so what the kernel does not write comes back as the caller gave it.
+int xgpu_test_itdq_ex(xgpu_ctx *c, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth, int tr_v, int tr_h, int log2s)
 {
-    ARGCHK(c, c != NULL); ARGCHK(c, coef && qp && n_blocks > 0 && log2w >= 1 && log2w <= 6 && log2h >= 1 && log2h <= 6);
-    const size_t per = (size_t)1 << (log2w + log2h), nb = per * n_blocks * sizeof(int16_t);
+    ARGCHK(c, c != NULL); ARGCHK(c, coef && qp && n_blocks > 0 && log2w >= 1 && log2w <= 6 && log2h >= 1 && log2h <= 6 && bit_depth >= 8 && bit_depth <= 16);
+    ARGCHK(c, tr_v >= TR_DCT2 && tr_v <= TR_DCT8 && tr_h >= TR_DCT2 && tr_h <= TR_DCT8);
+    // the builder's rule (tr_code): DST-VII / DCT-VIII come as a pair, for TBs of 4 .. 32 a side
+    ARGCHK(c, (tr_v == TR_DCT2 && tr_h == TR_DCT2) || (tr_v != TR_DCT2 && tr_h != TR_DCT2 && log2w >= 2 && log2w <= 5 && log2h >= 2 && log2h <= 5));
+    // a row stride beyond the width: the kernel fetches 8 samples of one row at a time, so the row holds at least 8, and the classes of at most 16 samples load their
+    // block as one piece (the builder gives a stride to 64x64 / 32x32 sub-blocks only)
+    ARGCHK(c, log2s >= log2w && log2s <= 12 && (log2s == log2w || (log2w >= 3 && log2w + log2h > 4)));
+    const size_t per = (size_t)1 << (log2s + log2h), nb = per * n_blocks * sizeof(int16_t);
+    ARGCHK(c, per * n_blocks <= 0x7FFFFFFFu);
     std::vector<TbRec> tbs(n_blocks);
     std::vector<TbWave> wv;
-    for (int i = 0; i < n_blocks; i++) { tbs[i].off = (uint32_t)(per * i); tbs[i].log2w = (uint8_t)log2w; tbs[i].log2h = (uint8_t)log2h; tbs[i].qp = qp[i]; tbs[i].log2s = (uint8_t)log2w; }
+    for (int i = 0; i < n_blocks; i++) { tbs[i].off = (uint32_t)(per * i); tbs[i].log2w = (uint8_t)log2w; tbs[i].log2h = (uint8_t)log2h; tbs[i].qp = qp[i]; tbs[i].log2s = (uint8_t)log2s; }
     const int pw = itdq_group_size(log2w, log2h);
-    for (int f = 0; f < n_blocks; f += pw) wv.push_back({ (uint32_t)f, (uint16_t)std::min(pw, n_blocks - f), (uint8_t)log2w, (uint8_t)log2h, 0, 0, { 0, 0 } });
+    for (int f = 0; f < n_blocks; f += pw)
+        wv.push_back({ (uint32_t)f, (uint16_t)std::min(pw, n_blocks - f), (uint8_t)log2w, (uint8_t)log2h, (uint8_t)tr_v, (uint8_t)tr_h, { 0, 0 } });
     int16_t *dc = NULL, *dr = NULL; TbRec *dt = NULL; TbWave *dw = NULL;
     HIPCHK(c, hipMalloc((void **)&dc, nb)); HIPCHK(c, hipMalloc((void **)&dr, nb));
     HIPCHK(c, hipMalloc((void **)&dt, sizeof(TbRec) * tbs.size())); HIPCHK(c, hipMalloc((void **)&dw, sizeof(TbWave) * wv.size()));
     HIPCHK(c, hipMemcpyAsync(dc, coef, nb, hipMemcpyHostToDevice, c->stream));
+    if (log2s != log2w) HIPCHK(c, hipMemcpyAsync(dr, coef, nb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(dt, tbs.data(), sizeof(TbRec) * tbs.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(dw, wv.data(), sizeof(TbWave) * wv.size(), hipMemcpyHostToDevice, c->stream));
     ItdqArgs ia; ia.coef = dc; ia.resid = dr; ia.tbs = dt; ia.waves = dw; ia.n_waves = (int)wv.size(); ia.bd = bit_depth; ia.iqt = c->sp.tool_iqt;
@@ -95,7 +106,8 @@ int xgpu_test_itdq(xgpu_ctx *c, int16_t *coef, int n_blocks, int log2w, int log2
     (void)hipFree(dc); (void)hipFree(dr); (void)hipFree(dt); (void)hipFree(dw);
     return XGPU_OK;
 }
-
+int xgpu_test_itdq(xgpu_ctx *c, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth)
+{ return xgpu_test_itdq_ex(c, coef, n_blocks, log2w, log2h, qp, bit_depth, TR_DCT2, TR_DCT2, log2w); }
 
 // xgpu_scale_taps through the device's row builder (k_output_rois_dev.hip): the arguments are checked by the host function itself, which also says how wide
 // the widest row is; then one lane per row on the device, and the three arrays come back

@@ -766,8 +766,12 @@ class XgpuDecoder:
                                                 bit_depth), "xgpu_test_dbk_chroma")
         return plane, plane_v
 
-    def test_itdq(self, coef, log2w, log2h, qp, bit_depth):
+    def test_itdq(self, coef, log2w, log2h, qp, bit_depth, tr_v=0, tr_h=0, log2s=None):
+        """len(qp) blocks of one size class through the residual kernel.  tr_v / tr_h: 0 DCT-II, 1 DST-VII, 2 DCT-VIII (the kernel's TR_* codes); log2s: log2 of the
+        row stride (default: the width), block i then starts at i * (h << log2s) and the samples outside its columns come back untouched"""
         coef = np.ascontiguousarray(coef, np.int16).copy()
         qp = np.ascontiguousarray(qp, np.uint8)
-        self._chk(self.lib.xgpu_test_itdq(self.ctx, coef.ctypes.data, len(qp), log2w, log2h, qp.ctypes.data, bit_depth), "xgpu_test_itdq")
+        log2s = log2w if log2s is None else log2s
+        assert coef.size == len(qp) << (log2s + log2h), "n blocks of h << log2s samples"
+        self._chk(self.lib.xgpu_test_itdq_ex(self.ctx, coef.ctypes.data, len(qp), log2w, log2h, qp.ctypes.data, bit_depth, tr_v, tr_h, log2s), "xgpu_test_itdq_ex")
         return coef
