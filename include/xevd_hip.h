@@ -446,6 +446,55 @@ int    xgpu_roi_snap(int box_format, const void *box, int pic_w, int pic_h, xgpu
 int    xgpu_pic_output_device_rois_dev(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
                                        const xgpu_roi_params *rp, const xgpu_roi_bounds *bounds, int box_format, const void *d_boxes, int capacity,
                                        const int *d_count, xgpu_roi_result *d_results, void *d_dst, size_t dst_size, void *stream);
+/* ---- warped regions of interest (k_output_warp.hip): n affine maps of one picture, each giving one sc->width x sc->height image, converted and normalised like
+   the scaled output, as a batch - [N, 3, H, W] or [N, H, W, 3] - from one kernel launch and at most one upload: rotated text lines, crops aligned by a similarity
+   transform from landmarks, the rotated boxes of an oriented detector, augmentation by a small rotation, shear or flip.  The arithmetic is integer from the map to
+   the (Y, Cb, Cr) triple; the exact contract is INTEGRATION.md section 8j and tests/warp_ref.py restates it in numpy, bit for bit.
+   The source is the picture minus f->crop (even), Ws x Hs luma samples, as for the scaled output; nothing outside it reaches a result.
+   A map is six Q16 integers: destination pixel (ox, oy) reads the source at X = m[0] ox + m[1] oy + m[2], Y = m[3] ox + m[4] oy + m[5], in 1 / 65536 luma sample,
+   0 = the centre of luma sample 0 of the source.  Limits: |m[0]|, |m[1]|, |m[3]|, |m[4]| <= 64 << 16, |m[2]|, |m[5]| <= 1 << 36.
+   samples S = 1, 2 or 4 (antialiases reductions up to about S per axis): sub-position (i, j), i, j = 0 .. S - 1, lies at
+   Xij = X + ((m[0] (2i + 1 - S) + m[1] (2j + 1 - S)) >> log2(2S)) (arithmetic shift), Y alike.
+   Luma at a sub-position: Xr = (Xij + 128) >> 8 clamped to [0, (Ws - 1) << 8], ix = Xr >> 8, fx = Xr & 255, ix1 = min(ix + 1, Ws - 1), rows alike;
+   s = (256 - fx)(256 - fy) p00 + fx (256 - fy) p01 + (256 - fx) fy p10 + fx fy p11.  Cb, Cr alike from their half-resolution planes at
+   Xc = (Xij - sh * 32768 + 256) >> 9 clamped to [0, (Ws / 2 - 1) << 8], Yc with sv and Hs / 2; sh, sv are xgpu_scale_taps' siting_half_luma of f->chroma_loc.
+   Every source sample is DRA-mapped (when `dra` is given) and clipped to [0, 2^B - 1] first, as for the scaled output.
+   v = (sum of the S * S sums + (1 << (15 + 2 log2 S))) >> (16 + 2 log2 S) per component; (Y, Cb, Cr) then go through the conversion of
+   xgpu_pic_output_device_scaled (matrix, range, bgr, the five dtypes, the normalise of `sc`) unchanged.
+     XGPU_WARP_CLAMP   the rule above: the edge of the source is replicated
+     XGPU_WARP_PAD     a destination pixel whose own position (X, Y, before supersampling) has Xr < 0, Xr > (Ws - 1) << 8 or the same for Y - each before
+                       its clamp - is wp->pad[k] (xgpu_roi_params' rules: floats before the normalise, integers in [0, 2^D - 1]); no blending
+   pad is validated only where it is read: with XGPU_WARP_PAD, or with maps in device memory.  image_pitch as for xgpu_roi_params.  From `sc` the call reads
+   width, height, normalize, mean and inv_std; sc->filter must be XGPU_SCALE_BILINEAR.
+   Refusals, all before anything is queued; *bad_index (may be NULL) receives the index of the map the refusal names, else -1:
+     XGPU_ERR_INVALID_ARGUMENT   n outside 1 .. XGPU_MAX_ROIS, samples not 1, 2 or 4, an unknown border, a filter other than XGPU_SCALE_BILINEAR, a layout that
+                                 is not one of the four three-channel ones, a map outside the limits, a bad pad where it is read, a bad image_pitch, and
+                                 whatever xgpu_pic_output_device_scaled refuses with this code
+     XGPU_ERR_UNSUPPORTED        sc->width or sc->height outside 2 .. 16384 */
+typedef struct xgpu_warp_map { int64_t m[6]; } xgpu_warp_map;
+#define XGPU_WARP_CLAMP 0
+#define XGPU_WARP_PAD   1
+typedef struct xgpu_warp_params { int samples, border; float pad[3]; size_t image_pitch; } xgpu_warp_params;
+/* Host only, no context: the map of theta, which takes destination pixel centres (ox + 0.5, oy + 0.5) to continuous source coordinates (sample i covers
+   [i, i + 1)): m[0] = llround(theta[0] * 65536), m[1] alike, m[2] = llround(((theta[0] + theta[1]) * 0.5 + theta[2] - 0.5) * 65536), the second row alike -
+   double operations in exactly this order, none contracted.  A non-finite entry or a result outside the limits: XGPU_ERR_INVALID_ARGUMENT. */
+int    xgpu_warp_from_matrix(const double theta[6], xgpu_warp_map *out);
+/* Host only: the image shows the w x h box centred at (cx, cy) and turned by angle_deg (y pointing down).  With c, s the cosine and sine of
+   angle_deg * (pi / 180): theta = { w c / dst_w, -h s / dst_h, cx - (w c - h s) / 2, w s / dst_w, h c / dst_h, cy - (w s + h c) / 2 }, then xgpu_warp_from_matrix. */
+int    xgpu_warp_from_rotated_box(double cx, double cy, double w, double h, double angle_deg, int dst_w, int dst_h, xgpu_warp_map *out);
+/* Host only, no context: 0 or the code the call refuses with (maps = NULL: maps in device memory, which the host does not read) / the bytes the call needs at
+   d_dst - (n - 1) * image_pitch + one image; 0: refused - for a picture of width x height at bit_depth */
+int    xgpu_output_warp_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_warp_params *wp, const xgpu_warp_map *maps, int n,
+                              int width, int height, int bit_depth, int *bad_index);
+size_t xgpu_output_warp_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_warp_params *wp, int n, int width, int height, int bit_depth);
+/* Non-blocking; d_dst, dst_size, stream and the ordering as for xgpu_pic_output_device_rois.  maps_on_device = 0: `maps` is host memory, validated here and
+   uploaded in one copy into the context's block (which grows on demand and is ordered like the descriptor block of the regions of interest); d_status is not
+   written.  maps_on_device = 1: `maps` is an int64 [n][6] array on the context's device; the host does not read it and the call does not synchronise.  The kernel
+   checks the limits per map: a map outside them gives an image that is all wp->pad, and d_status[i] (int32 [n] on the device, may be NULL) is 1 - else 0, the
+   image is written.  Whatever a map holds, every position is clamped before it addresses memory, and the position arithmetic wraps in 64 bits. */
+int    xgpu_pic_output_device_warp(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                                   const xgpu_warp_params *wp, const xgpu_warp_map *maps, int maps_on_device, int n, int32_t *d_status, void *d_dst,
+                                   size_t dst_size, void *stream);
 /* ---- coding side information (k_side_info.hip): what the decoder knows about a picture besides its samples - motion vectors per 4x4 luma unit, the
    reference each one points at, intra / inter / skip / IBC, QP, coded-residual flag, block edges - read out of the SCU map the in-loop filters read
    (the reference's map_scu / map_refi / map_mv, src_base/xevd_def.h:372-438).

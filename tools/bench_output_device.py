@@ -23,6 +23,11 @@ tensor, as a detector leaves them, and alternates - same protocol as the rois le
 and a read-back) and xgpu_pic_output_device_rois, with route B: the device-box call on the tensor itself, max_roi set to the true maxima of the workload.  The
 split of B into its three kernels is what rocprofv3 --kernel-trace --stats shows for `--legs rois_dev`.
 
+The warp leg (xgpu_pic_output_device_warp: k_output_warp) takes the 64 boxes of the rois leg, each turned by a seeded angle, to 224x224 f32 planar, normalised,
+and alternates - the rois leg's protocol - route A, what a caller does without it: the full-size f32 R'G'B' tensor, torch's affine_grid + grid_sample(bilinear,
+border, align_corners=False) on its expand(64, ...) and the normalise, with route B: the one call, at samples = 1 and at samples = 4.  It also times the same
+boxes upright against rois= with the stretch fit: what gathering costs over the two separable passes.
+
 The residual leg (xgpu_batch_residual: k_resid_planes / k_resid_energy) writes the residual of a synthetic B-picture batch of the same size as int16 4:2:0
 planes, as 4:4:4 planar int16 and float16, and as the per-unit energy.  Bytes are algorithmic: the arena bytes actually coded (2 per sample of every coded
 component block), 4 per 4x4 unit of owner map, 32 per CU record, and what the form writes.  The whole measurement - copy rate included - is repeated --repeat
@@ -40,7 +45,7 @@ gradient with +-2 codes of noise: the contention of the LDS histogram depends on
 the light level.  Each is timed as the other legs are (the median of --iters calls queued behind a wait) and, alternated with it from an idle device, the torch
 route: a yuv420p tensor, then bincount, sum, min and max per plane; with light the u16 RGB tensor, amax, bincount and a gather through lin.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|residual|compare|stats] [--out out/output_device.json]
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|warp|residual|compare|stats] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -229,6 +234,98 @@ def rois_dev_leg(torch, dec, pic, s, a, res):
         print(f"rois_dev {name:16s} {len(rois)} x {size[1]}x{size[0]} f32: boxes.cpu() + host-box call {r['host_boxes']['us']:9.1f} us (host {r['host_boxes']['host_us']:8.1f})   "
               f"device-box call {r['device_boxes']['us']:9.1f} us (host {r['device_boxes']['host_us']:8.1f})   {r['speedup']:.2f}x   images equal: {same}")
         res["rois_dev"][name] = r
+
+
+def alternated(torch, s, routes, iters, warm=5):
+    """routes {name: fn} run in turn, `iters` rounds, each from an idle device between two events on s -> {name: {us, p10_us, p90_us, host_us}}"""
+    import time
+    for _ in range(warm):
+        for fn in routes.values():
+            fn()
+    torch.cuda.synchronize()
+    ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)] for k in routes}
+    host = {k: [] for k in routes}
+    for i in range(iters):
+        for k, fn in routes.items():
+            e0, e1 = ev[k][i]
+            torch.cuda.synchronize()      # each route starts on an idle device: its events see its own gaps only
+            t0 = time.perf_counter()
+            e0.record(s)
+            fn()
+            e1.record(s)
+            host[k].append((time.perf_counter() - t0) * 1e6)
+    torch.cuda.synchronize()
+    r = {}
+    for k in routes:
+        us = np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev[k]])
+        r[k] = {"us": round(float(np.median(us)), 2), "p10_us": round(float(np.percentile(us, 10)), 2), "p90_us": round(float(np.percentile(us, 90)), 2),
+                "host_us": round(float(np.median(host[k])), 2)}
+    return r
+
+
+def warp_leg(torch, dec, pic, s, a, res):
+    """64 rotated boxes -> 224x224 f32 planar, normalised: the full-size f32 tensor + affine_grid + grid_sample + normalise in torch (A) against the one call at
+    S = 1 and S = 4 (B), alternated; and the same boxes upright against rois= with the stretch fit - what gathering costs over the two separable passes"""
+    import math
+    import torch.nn.functional as F
+    from xevd_amd import abi
+    w, h = a.width, a.height
+    size, n = (224, 224), 64
+    hd, wd = size
+    rng = np.random.default_rng(7)      # the boxes of the rois leg ...
+    boxes = []
+    for _ in range(n):
+        bw, bh = (min(int(rng.integers(32, 257)) * 2, v) for v in (w, h))
+        boxes.append((int(rng.integers(0, (w - bw) // 2 + 1)) * 2, int(rng.integers(0, (h - bh) // 2 + 1)) * 2, bw, bh))
+    angles = np.random.default_rng(11).uniform(-180.0, 180.0, n)      # ... each with a seeded angle
+
+    def thetas(angs):
+        out = []
+        for (x, y, bw, bh), ang in zip(boxes, angs):
+            c, sn = math.cos(ang * (math.pi / 180.0)), math.sin(ang * (math.pi / 180.0))
+            cx, cy = x + bw / 2, y + bh / 2
+            out.append([bw * c / wd, -bh * sn / hd, cx - (bw * c - bh * sn) / 2, bw * sn / wd, bh * c / hd, cy - (bw * sn + bh * c) / 2])
+        return out
+
+    def grid_theta(ths):      # destination pixel centres -> source coordinates, as affine_grid's normalised matrix (align_corners=False)
+        g = [[[t[0] * wd / w, t[1] * hd / w, 2 * (t[0] * wd / 2 + t[1] * hd / 2 + t[2]) / w - 1],
+              [t[3] * wd / h, t[4] * hd / h, 2 * (t[3] * wd / 2 + t[4] * hd / 2 + t[5]) / h - 1]] for t in ths]
+        return torch.tensor(g, dtype=torch.float32, device="cuda:0")
+
+    kw = dict(dtype=torch.float32, mean=MEAN, std=STD)
+    mean = torch.tensor(MEAN, device="cuda:0").view(1, 3, 1, 1)
+    inv = (1.0 / torch.tensor(STD, device="cuda:0")).view(1, 3, 1, 1)
+    full = dec.pic_output_tensor(pic, dtype=torch.float32)
+    ths = thetas(angles)
+    maps = np.asarray([abi.warp_from_matrix(dec.lib, t) for t in ths], np.int64)
+    gt = grid_theta(ths)
+    outs = {sm: dec.pic_output_warped(pic, maps, size, samples=sm, **kw) for sm in (1, 4)}
+
+    def route_a():
+        dec.pic_output_tensor(pic, out=full, dtype=torch.float32)
+        grid = F.affine_grid(gt, (n, 3, hd, wd), align_corners=False)
+        return (F.grid_sample(full[None].expand(n, -1, -1, -1), grid, mode="bilinear", padding_mode="border", align_corners=False) - mean) * inv
+
+    routes = {"torch_route": route_a, "warp_s1": lambda: dec.pic_output_warped(pic, maps, size, samples=1, out=outs[1], **kw),
+              "warp_s4": lambda: dec.pic_output_warped(pic, maps, size, samples=4, out=outs[4], **kw)}
+    r = {"n": n, "size": list(size), "rotated": alternated(torch, s, routes, a.iters)}
+    r["rotated"]["max_abs_diff_s1_vs_torch_route"] = float((route_a() - outs[1]).abs().max())
+    r["rotated"]["speedup_s1"] = round(r["rotated"]["torch_route"]["us"] / r["rotated"]["warp_s1"]["us"], 2)
+    r["rotated"]["speedup_s4"] = round(r["rotated"]["torch_route"]["us"] / r["rotated"]["warp_s4"]["us"], 2)
+    del full
+    # the same boxes upright: the gather against the two separable passes of rois= (stretch); the results differ where a box is reduced (no antialiasing at S = 1)
+    up = np.asarray([abi.warp_from_matrix(dec.lib, t) for t in thetas(np.zeros(n))], np.int64)
+    out_w = dec.pic_output_warped(pic, up, size, **kw)
+    out_r = dec.pic_output_tensor(pic, size=size, rois=boxes, **kw)
+    routes = {"rois_stretch": lambda: dec.pic_output_tensor(pic, size=size, rois=boxes, out=out_r, **kw),
+              "warp_s1": lambda: dec.pic_output_warped(pic, up, size, samples=1, out=out_w, **kw)}
+    r["upright"] = alternated(torch, s, routes, a.iters)
+    r["upright"]["warp_over_rois"] = round(r["upright"]["warp_s1"]["us"] / r["upright"]["rois_stretch"]["us"], 2)
+    ro, up_ = r["rotated"], r["upright"]
+    print(f"warp rotated {n} x {wd}x{hd} f32: torch route {ro['torch_route']['us']:9.1f} us (host {ro['torch_route']['host_us']:8.1f})   one call S=1 {ro['warp_s1']['us']:8.1f} us "
+          f"({ro['speedup_s1']:.1f}x)   S=4 {ro['warp_s4']['us']:8.1f} us ({ro['speedup_s4']:.1f}x)   max |diff| S=1 {ro['max_abs_diff_s1_vs_torch_route']:.2e}")
+    print(f"warp upright {n} x {wd}x{hd} f32: rois stretch {up_['rois_stretch']['us']:8.1f} us   warp S=1 {up_['warp_s1']['us']:8.1f} us   ({up_['warp_over_rois']:.2f} of rois)")
+    res["warp"] = r
 
 
 def residual_leg(torch, dec, pic, s, a, res):
@@ -445,10 +542,10 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "residual", "compare", "stats"), default="all",
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "warp", "residual", "compare", "stats"), default="all",
                     help="full: the full-size forms and the side information; scaled: the scaled leg alone; rois: the batched regions of interest alone; "
-                         "rois_dev: the regions of interest from boxes in device memory alone; residual: the residual export alone; compare: the picture comparison alone; "
-                         "stats: the picture statistics alone")
+                         "rois_dev: the regions of interest from boxes in device memory alone; warp: the warped regions of interest alone; residual: the residual "
+                         "export alone; compare: the picture comparison alone; stats: the picture statistics alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -488,6 +585,8 @@ def main():
             rois_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "rois_dev"):
             rois_dev_leg(torch, dec, pic, s, a, res)
+        if a.legs in ("all", "warp"):
+            warp_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "residual"):
             residual_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "compare"):

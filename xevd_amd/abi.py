@@ -338,6 +338,61 @@ def tile_rois(width, height, tile_w, tile_h):
     return [(x, y, tile_w, tile_h) for y in ys for x in xs]
 
 
+WARP_CLAMP, WARP_PAD = 0, 1
+WARP_LIN_LIMIT, WARP_OFF_LIMIT = 64 << 16, 1 << 36      # |m[0]|, |m[1]|, |m[3]|, |m[4]| / |m[2]|, |m[5]|
+
+
+class WarpMap(C.Structure):
+    _fields_ = [("m", C.c_int64 * 6)]
+
+
+class WarpParams(C.Structure):
+    _fields_ = [("samples", C.c_int), ("border", C.c_int), ("pad", C.c_float * 3), ("image_pitch", C.c_size_t)]
+
+
+def make_warp_params(samples=1, border=WARP_CLAMP, pad=0.0, image_pitch=0):
+    """xgpu_warp_params (include/xevd_hip.h): sub-positions per axis (1, 2, 4), WARP_CLAMP / WARP_PAD, the pad value - one value or three, by the channel's
+    position in the output, before the normalise - and the bytes between two images (0: tight)"""
+    p = WarpParams()
+    p.samples, p.border, p.image_pitch = int(samples), int(border), int(image_pitch)
+    v = np.broadcast_to(np.asarray(pad, np.float32), (3,))
+    for k in range(3):
+        p.pad[k] = float(v[k])
+    return p
+
+
+def make_warp_maps(maps):
+    """[(m0 .. m5), ...] or an int64 array [N, 6] of Q16 maps -> an array of xgpu_warp_map"""
+    m = np.ascontiguousarray(maps, np.int64).reshape(-1, 6)
+    return (WarpMap * len(m)).from_buffer_copy(m.tobytes()) if len(m) else (WarpMap * 1)()
+
+
+def warp_from_matrix(lib, theta):
+    """xgpu_warp_from_matrix: theta (six floats, destination pixel centres -> continuous source coordinates) -> the six Q16 integers, or the negative code"""
+    out = WarpMap()
+    rc = lib.xgpu_warp_from_matrix((C.c_double * 6)(*[float(v) for v in theta]), C.byref(out))
+    return rc if rc < 0 else tuple(int(v) for v in out.m)
+
+
+def warp_from_rotated_box(lib, cx, cy, w, h, angle_deg, dst_size):
+    """xgpu_warp_from_rotated_box: the map that shows the w x h box centred at (cx, cy), turned by angle_deg, in an image of dst_size = (H, W); or the negative code"""
+    out = WarpMap()
+    rc = lib.xgpu_warp_from_rotated_box(float(cx), float(cy), float(w), float(h), float(angle_deg), int(dst_size[1]), int(dst_size[0]), C.byref(out))
+    return rc if rc < 0 else tuple(int(v) for v in out.m)
+
+
+def output_warp_check(lib, fmt, sc, wp, maps, n, width, height, bit_depth):
+    """xgpu_output_warp_check -> (code, bad_index); maps: make_warp_maps' array, or None for maps in device memory"""
+    bad = C.c_int(-1)
+    rc = lib.xgpu_output_warp_check(C.byref(fmt), C.byref(sc), C.byref(wp), maps, int(n), int(width), int(height), int(bit_depth), C.byref(bad))
+    return rc, bad.value
+
+
+def output_warp_size(lib, fmt, sc, wp, n, width, height, bit_depth):
+    """xgpu_output_warp_size: the bytes the batch needs, 0 = refused"""
+    return lib.xgpu_output_warp_size(C.byref(fmt), C.byref(sc), C.byref(wp), int(n), int(width), int(height), int(bit_depth))
+
+
 CM_CURVE_U0, CM_CURVE_SIZE = 0x1F800000, 64 * 32 + 3
 
 
@@ -551,6 +606,13 @@ _EXPORTS = {
     "xgpu_output_rois_dev_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(RoiBounds)] + [C.c_int] * 5),
     "xgpu_pic_output_device_rois_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams),
                                                   C.POINTER(RoiBounds), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_warp_from_matrix": (C.c_int, [C.POINTER(C.c_double), C.POINTER(WarpMap)]),
+    "xgpu_warp_from_rotated_box": (C.c_int, [C.c_double] * 5 + [C.c_int, C.c_int, C.POINTER(WarpMap)]),
+    "xgpu_output_warp_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(WarpParams), C.POINTER(WarpMap), C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(C.c_int)]),
+    "xgpu_output_warp_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(WarpParams), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "xgpu_pic_output_device_warp": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(WarpParams), C.c_void_p,
+                                              C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_side_info_size": (C.c_size_t, [C.POINTER(SideFormat), C.c_int, C.c_int]),
     "xgpu_frame_side_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SideFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_resid_size": (C.c_size_t, [C.POINTER(ResidFormat), C.c_int, C.c_int]),

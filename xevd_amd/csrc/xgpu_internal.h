@@ -371,7 +371,8 @@ struct xgpu_ctx {
     // partial sums of the current call
     uint8_t        *stats_blk;
     int             stats_lin_tc, stats_lin_bd;
-    uint8_t        *roi_blk;          // xgpu_pic_output_device_rois: the descriptors and tap tables of the current call (its intermediate is sc_mid), ordered like sc_tab
+    uint8_t        *roi_blk;          // xgpu_pic_output_device_rois: the descriptors and tap tables of the current call (its intermediate is sc_mid), ordered like sc_tab;
+                                      // xgpu_pic_output_device_warp: the host maps of the current call
     size_t          roi_blk_cap;
     hipEvent_t      odev_ev[2];       // xgpu_pic_output_device on a caller's stream: picture ready on the context stream / the caller's kernel done (created at the first call)
     xgpu_frame_params fp;
@@ -547,6 +548,20 @@ struct RoisPrepArgs {
     uint32_t mid_slot;              // samples of the intermediate per box
 };
 void launch_rois_prepare(const RoisPrepArgs &a, hipStream_t s);
+// k_output_warp.hip: n affine maps of one picture, each giving one dw x dh image (xgpu_pic_output_device_warp).  ScaledOutArgs' picture,
+// destination and conversion fields (y, u, v, w, h, cw, ch: the picture minus f->crop; dst, pitch, plane: of image 0; the taps, mid and the caps are not read),
+// then the batch's
+struct WarpOutArgs : ScaledOutArgs {
+    const int64_t *maps;            // [n][6] Q16 on the device: the context's block (host maps) or the caller's array (device maps, unchecked)
+    int32_t *status;                // device maps: [n] 0 = written, 1 = refused; or NULL
+    int      n;
+    int      ls;                    // log2 of `samples`
+    int      border;                // XGPU_WARP_CLAMP / XGPU_WARP_PAD
+    int      sh, sv;                // the chroma grid lies sh / 2, sv / 2 luma samples behind the luma grid (xgpu_scale_taps' siting_half_luma)
+    float    padv[3];               // the pad value by output position, before the normalise (integer dtypes: the integer)
+    size_t   image_pitch;           // bytes between two images
+};
+void launch_output_warp(const WarpOutArgs &a, int layout, int dtype, hipStream_t s);
 void launch_test_scale_taps(int n_plane, int subsampling, int siting, int n_dst, int filter, int32_t *first, int32_t *count, int16_t *w, int w_stride, hipStream_t s);
 // k_output_yuv.hip (k_output_semiplanar): NV12 / P016 - xgpu_pic_output's samples, luma rows then rows of interleaved Cb Cr
 struct SemiPlanarArgs {

@@ -1,5 +1,5 @@
 // xgpu_output.hip - the C ABI of include/xevd_hip.h, part 2: the outputs into device memory - the picture as it is, colour-managed, scaled, as a batch of regions of
-// interest (rectangles from the host or boxes in device memory), the coding side information, the residual, the comparison with a reference and the statistics
+// interest (rectangles from the host or boxes in device memory) or of affine maps, the coding side information, the residual, the comparison with a reference and the statistics
 // of one picture - and their argument checks without a device.
 // Every entry point is the same skeleton: check the format -> check_dst -> (check_dra; tables, made on the host) -> grow a context buffer -> out_fork -> fill an args struct ->
 // launch -> out_join.  Host-side code only; the kernels live in k_output*.hip, k_side_info.hip, k_residual.hip, k_compare.hip and k_stats.hip.
@@ -816,6 +816,134 @@ int xgpu_pic_output_device_rois_dev(xgpu_ctx *c, int pic, const xgpu_dra_luts *d
     for (int k = 0; k < 3; k++) a.padv[k] = rp->pad[k];
     launch_output_rois(a, f->layout, f->dtype, mw, sc->height, s);
     return out_join(c, stream, s);      // the slot, the DRA tables, the block and the intermediate
+}
+
+// ------------------------------------------------------------------------------------------------ warped regions of interest: a batch of affine maps
+static const int64_t WARP_LIN_LIMIT = (int64_t)64 << 16, WARP_OFF_LIMIT = (int64_t)1 << 36;
+static bool warp_map_ok(const xgpu_warp_map &m)
+{
+    for (int k = 0; k < 6; k++) {
+        const int64_t lim = (k == 2 || k == 5) ? WARP_OFF_LIMIT : WARP_LIN_LIMIT;
+        if (m.m[k] < -lim || m.m[k] > lim) return false;
+    }
+    return true;
+}
+int xgpu_warp_from_matrix(const double theta[6], xgpu_warp_map *out)
+{
+    #pragma clang fp contract(off)
+    if (!theta || !out) return XGPU_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < 6; k++) if (!std::isfinite(theta[k])) return XGPU_ERR_INVALID_ARGUMENT;
+    double v[6];
+    for (int r = 0; r < 2; r++) {
+        const double *t = theta + 3 * r;
+        v[3 * r] = t[0] * 65536.0;
+        v[3 * r + 1] = t[1] * 65536.0;
+        v[3 * r + 2] = ((t[0] + t[1]) * 0.5 + t[2] - 0.5) * 65536.0;
+    }
+    xgpu_warp_map m;
+    for (int k = 0; k < 6; k++) {
+        if (!std::isfinite(v[k]) || std::fabs(v[k]) > 1e15) return XGPU_ERR_INVALID_ARGUMENT;      // (llround of such a value is not defined; the limits are far below)
+        m.m[k] = llround(v[k]);
+    }
+    if (!warp_map_ok(m)) return XGPU_ERR_INVALID_ARGUMENT;
+    *out = m;
+    return XGPU_OK;
+}
+int xgpu_warp_from_rotated_box(double cx, double cy, double w, double h, double angle_deg, int dst_w, int dst_h, xgpu_warp_map *out)
+{
+    #pragma clang fp contract(off)
+    if (!out || dst_w < 1 || dst_h < 1 || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(w) || !std::isfinite(h) || !std::isfinite(angle_deg))
+        return XGPU_ERR_INVALID_ARGUMENT;
+    const double rad = angle_deg * (3.14159265358979323846 / 180.0), c = cos(rad), s = sin(rad);
+    const double theta[6] = { w * c / dst_w, -h * s / dst_h, cx - (w * c - h * s) / 2, w * s / dst_w, h * c / dst_h, cy - (w * s + h * c) / 2 };
+    return xgpu_warp_from_matrix(theta, out);
+}
+// The whole of a call's argument checks, without a device: the bytes the destination needs, or 0 with *rc = the code, `why` (160 bytes) and *bad = the map it
+// names (-1: none).  maps = NULL: the maps are not looked at (device maps, which the host does not read; the size, which does not depend on them); dev_maps: the
+// pad is read whatever the border
+static size_t warp_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_warp_params *wp, const xgpu_warp_map *maps, bool dev_maps, int n, int width,
+                        int height, int bd, int *rc, char *why, int *bad, size_t *image_pitch)
+{
+    const char *w0 = "";
+    *bad = -1;
+    if (!scaled_params_ok(f, sc, width, height, bd, rc, &w0)) { snprintf(why, 160, "%s", w0); return 0; }
+    const size_t image = scaled_image_bytes(f, sc, rc, &w0);
+    if (image == 0) { snprintf(why, 160, "%s", w0); return 0; }
+    *rc = XGPU_ERR_INVALID_ARGUMENT;
+    if (sc->filter != XGPU_SCALE_BILINEAR) { snprintf(why, 160, "filter must be XGPU_SCALE_BILINEAR"); return 0; }
+    if (!wp) { snprintf(why, 160, "warp parameters are NULL"); return 0; }
+    if (n < 1 || n > XGPU_MAX_ROIS) { snprintf(why, 160, "n %d outside 1..%d", n, XGPU_MAX_ROIS); return 0; }
+    if (wp->samples != 1 && wp->samples != 2 && wp->samples != 4) { snprintf(why, 160, "samples must be 1, 2 or 4"); return 0; }
+    if (wp->border != XGPU_WARP_CLAMP && wp->border != XGPU_WARP_PAD) { snprintf(why, 160, "border must be XGPU_WARP_CLAMP or XGPU_WARP_PAD"); return 0; }
+    xgpu_roi_params rp;      // the pad and the batch stride follow the rules of the regions of interest
+    rp.fit = XGPU_FIT_STRETCH; rp.image_pitch = wp->image_pitch;
+    for (int k = 0; k < 3; k++) rp.pad[k] = wp->pad[k];
+    const size_t ip = rois_pad_and_pitch(f, sc, &rp, bd, image, wp->border == XGPU_WARP_PAD || dev_maps, why);
+    if (ip == 0) return 0;
+    if (maps)
+        for (int i = 0; i < n; i++)
+            if (!warp_map_ok(maps[i])) {
+                *bad = i;
+                snprintf(why, 160, "map %d: a coefficient outside |m[0,1,3,4]| <= 64 << 16, |m[2,5]| <= 1 << 36", i);
+                return 0;
+            }
+    *rc = XGPU_OK;
+    if (image_pitch) *image_pitch = ip;
+    return (size_t)(n - 1) * ip + image;
+}
+int xgpu_output_warp_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_warp_params *wp, const xgpu_warp_map *maps, int n, int width, int height,
+                           int bit_depth, int *bad_index)
+{
+    int rc, bad; char why[160];
+    (void)warp_size(f, sc, wp, maps, maps == NULL, n, width, height, bit_depth, &rc, why, &bad, NULL);
+    if (bad_index) *bad_index = bad;
+    return rc;
+}
+size_t xgpu_output_warp_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_warp_params *wp, int n, int width, int height, int bit_depth)
+{
+    int rc, bad; char why[160];
+    return warp_size(f, sc, wp, NULL, wp && wp->border == XGPU_WARP_PAD, n, width, height, bit_depth, &rc, why, &bad, NULL);
+}
+int xgpu_pic_output_device_warp(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_warp_params *wp,
+                                const xgpu_warp_map *maps, int maps_on_device, int n, int32_t *d_status, void *d_dst, size_t dst_size, void *stream)
+{
+    static const char who[] = "pic_output_device_warp";
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL); ARGCHK(c, maps != NULL); ARGCHK(c, maps_on_device == 0 || maps_on_device == 1);
+    int src_rc, bad; char why[160];
+    size_t image_pitch = 0;
+    const size_t need = warp_size(f, sc, wp, maps_on_device ? NULL : maps, maps_on_device != 0, n, c->sp.width, c->sp.height, c->sp.bit_depth_luma, &src_rc, why, &bad, &image_pitch);
+    if (need == 0) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return src_rc; }
+    TRY(check_dst_fits(c, who, d_dst, dst_size, need, elem_size(f->dtype)));
+    if (dra) TRY(check_dra(c, dra));      // upload_dra's refusals, before anything is queued
+    TRY(check_device_dst(c, who, d_dst, need));
+    const size_t maps_bytes = (size_t)n * sizeof(xgpu_warp_map);
+    if (maps_on_device) {
+        if ((uintptr_t)maps % 8 || (d_status && (uintptr_t)d_status % 4)) { snprintf(c->err, sizeof(c->err), "%s: maps or status in device memory are not aligned", who); return XGPU_ERR_INVALID_ARGUMENT; }
+        TRY(check_device_dst(c, "pic_output_device_warp (maps)", const_cast<xgpu_warp_map *>(maps), maps_bytes));
+        if (d_status) TRY(check_device_dst(c, "pic_output_device_warp (status)", d_status, (size_t)n * sizeof(int32_t)));
+    } else {
+        TRY(grow(c, who, &c->roi_blk, &c->roi_blk_cap, maps_bytes, "block of maps"));
+    }
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    // behind the fork: after every kernel that read the previous block.  (Pageable host memory: staged before the call returns, as the DRA tables are.)
+    if (!maps_on_device) HIPCHK(c, hipMemcpyAsync(c->roi_blk, maps, maps_bytes, hipMemcpyHostToDevice, s));
+    WarpOutArgs a;
+    memset(&a, 0, sizeof(a));
+    scaled_common_args(c, pic, dra, f, sc, d_dst, a);
+    a.w = c->sp.width - f->crop[0] - f->crop[1]; a.h = c->sp.height - f->crop[2] - f->crop[3]; a.cw = a.w >> 1; a.ch = a.h >> 1;
+    a.maps = maps_on_device ? (const int64_t *)maps : (const int64_t *)c->roi_blk;
+    a.status = maps_on_device ? d_status : NULL;
+    a.n = n;
+    a.ls = wp->samples == 4 ? 2 : wp->samples == 2 ? 1 : 0;
+    a.border = wp->border;
+    a.sh = f->chroma_loc & 1;
+    a.sv = f->chroma_loc < 2 ? 1 : f->chroma_loc < 4 ? 0 : 2;
+    for (int k = 0; k < 3; k++) a.padv[k] = (wp->border == XGPU_WARP_PAD || maps_on_device) ? wp->pad[k] : 0.f;
+    a.image_pitch = image_pitch;
+    launch_output_warp(a, f->layout, f->dtype, s);
+    return out_join(c, stream, s);      // the slot, the DRA tables and the block of maps
 }
 
 // ------------------------------------------------------------------------------------------------ coding side information of the picture decoded last

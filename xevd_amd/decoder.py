@@ -381,6 +381,69 @@ class XgpuDecoder:
                           C.c_void_p(res.data_ptr()) if results else None)
         return (out, res) if results else out
 
+    def pic_output_warped(self, pic, maps, size, layout="rgb", channels_last=False, dtype=None, matrix=1, full_range=False, chroma_loc=0, crop=(0, 0, 0, 0),
+                          dra=None, bgr=False, samples=1, border="clamp", pad=0.0, mean=None, std=None, out=None, status=False):
+        """N affine maps of the picture, each giving one H x W image (size=(H, W)), converted and normalised like pic_output_tensor(size=...), as one batch
+        [N, 3, H, W] (channels_last: [N, H, W, 3]) from one kernel launch (xgpu_pic_output_device_warp): rotated boxes, crops aligned
+        by a similarity transform, flips, shears.  Integer arithmetic from the map to (Y, Cb, Cr): tests/warp_ref.py restates the result bit for bit.
+        maps: a sequence of 6-float thetas (theta takes destination pixel centres (ox + 0.5, oy + 0.5) to continuous source coordinates of the picture minus the
+        crop; abi.warp_from_matrix converts them, abi.warp_from_rotated_box makes the map of a rotated box), or a numpy int64 [N, 6] array of Q16 maps, or a
+        contiguous torch int64 [N, 6] tensor on the decoder's device - maps some kernel left there, read on the device with no host read and no
+        synchronisation; a map outside the limits then gives an image that is all `pad`, and status=True also returns the int32 [N] tensor (0 = written,
+        1 = refused).  samples 1, 2 or 4: sub-positions per axis (antialiases reductions up to about that factor).  border "clamp" replicates the picture's edge,
+        "pad" writes `pad` (one value or three, in the output's channel order, before the normalise; integers for the integer dtypes) where the pixel's centre
+        lies outside the picture.  out: a tensor of that shape whose rows may be padded and whose images may lie a batch stride apart."""
+        import torch
+        if border not in ("clamp", "pad"):
+            raise ValueError(f"border must be 'clamp' or 'pad', not {border!r}")
+        a = {"layout": layout, "colour": None, "filter": "bilinear", "mean": mean, "std": std, "out_bit_depth": 0, "dtype": dtype, "size": size,
+             "channels_last": channels_last, "bgr": bgr, "matrix": matrix, "full_range": full_range, "chroma_loc": chroma_loc, "crop": crop}
+        dtype, fmt, sc, h, w, dev = self._scaled_setup(a)
+        on_device = isinstance(maps, torch.Tensor)
+        if on_device:
+            if maps.device != dev or maps.dtype != torch.int64 or maps.dim() != 2 or maps.shape[1] != 6 or not maps.is_contiguous():
+                raise ValueError(f"maps: a contiguous int64 tensor [N, 6] on {dev}, not {tuple(maps.shape)} {maps.dtype} on {maps.device}"
+                                 f"{'' if maps.is_contiguous() else ', not contiguous'}")
+            n, ma = int(maps.shape[0]), None
+        else:
+            if status:
+                raise ValueError("status belongs to maps=<tensor on the device>")
+            if isinstance(maps, np.ndarray) and maps.dtype == np.int64:
+                if maps.ndim != 2 or maps.shape[1] != 6:
+                    raise ValueError(f"maps: an int64 array [N, 6], not {maps.shape}")
+                rows = maps
+            else:
+                rows = []
+                for i, theta in enumerate(maps):
+                    if len(theta) != 6:
+                        raise ValueError(f"maps: theta {i} has {len(theta)} entries, not 6")
+                    m = abi.warp_from_matrix(self.lib, theta)
+                    if not isinstance(m, tuple):
+                        raise ValueError(f"maps: theta {i} {tuple(float(v) for v in theta)} is not finite or leaves the limits of a map ({m})")
+                    rows.append(m)
+            n, ma = len(rows), abi.make_warp_maps(rows)
+        wp = abi.make_warp_params(samples, abi.WARP_PAD if border == "pad" else abi.WARP_CLAMP, pad)
+
+        def refuse():
+            rc, bad = abi.output_warp_check(self.lib, fmt, sc, wp, ma, n, self.width, self.height, self.bit_depth)
+            if rc < 0:
+                at = f"map {bad} {tuple(int(v) for v in rows[bad])}: " if 0 <= bad < n else ""
+                raise ValueError(f"invalid batch of maps ({rc}): {at}layout {layout}, size {tuple(size)}, samples {samples}, border {border}, pad {pad}, crop {crop}, "
+                                 f"mean {mean}, std {std}, {n} maps")
+        planar = not channels_last
+        if out is None:
+            refuse()      # before a tensor is made, and again with its pitches
+        out = _out_tensor(out, (n, 3, h, w) if planar else (n, h, w, 3), dtype, dev)
+        st = out.stride()
+        fmt.row_pitch = _row_pitch(st, planar, h, w if planar else 3 * w, 3) * dtype.itemsize
+        wp.image_pitch = st[0] * dtype.itemsize if n > 1 else 0
+        refuse()
+        dl, self._dra_keep = self._dra_luts(dra) if dra is not None else (None, None)      # (kept until the next call: the tables are copied asynchronously)
+        res = torch.empty((n,), dtype=torch.int32, device=dev) if on_device and status else None
+        self._device_call("xgpu_pic_output_device_warp", out, pic, dl, C.byref(fmt), C.byref(sc), C.byref(wp),
+                          C.c_void_p(maps.data_ptr()) if on_device else ma, int(on_device), n, C.c_void_p(res.data_ptr()) if res is not None else None)
+        return (out, res) if on_device and status else out
+
     def _run_stream(self, dev):
         """(torch's current stream, the stream a kernel of the C ABI is queued on): torch's default stream is the null stream, whose handle (0) means "the
         context's stream" to the C ABI - such a call runs on a side stream of torch's between two stream waits instead (the caller makes the second one)"""

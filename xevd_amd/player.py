@@ -116,7 +116,7 @@ class StreamDecoder:
         return cm
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
-                 residual=None, compare=None, stats=None):
+                 residual=None, compare=None, stats=None, warp=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -136,6 +136,9 @@ class StreamDecoder:
         tensor=dict(snap=True) for boxes a detector made).  The list, or what the callable returns, may also be a torch tensor on the decoder's device - int32
         [N, 4] xywh or float32 [N, 4] xyxy, a detector's boxes where it left them: they are read on the device, with no host read in between
         (pic_output_tensor's rois=<tensor>; tensor=dict(count=, max_roi=) go with it)
+        warp=[theta, ...], an int64 [N, 6] array or tensor of Q16 maps, or a callable(params) -> one of these (with tensor= and size=, called as rois= is):
+        every picture as the batch [N, 3, H, W] of its affine maps (XgpuDecoder.pic_output_warped; tensor=dict(samples=, border=, pad=, status=) go with it,
+        and pic_output_tensor's arguments that the warped output does not have must be left out).  Not together with rois=
         compare=callable(params) -> a reference or None, or a sequence of such indexed in decoding order (shorter: the pictures past its end are not
         compared): every picture against its reference on the device (XgpuDecoder.pic_compare: a tensor in pic_output's plane order on the decoder's device; a
         dict(ref=..., ssim=..., block_map=...) passes pic_compare's other arguments), taken right behind the picture's kernels; the result - pic_compare's
@@ -152,6 +155,10 @@ class StreamDecoder:
             raise ValueError("rois: need tensor=dict(...) and size=(H, W)")
         if (fit is not None or pad is not None) and rois is None:
             raise ValueError("fit / pad: need rois=")
+        if warp is not None and rois is not None:
+            raise ValueError("warp: not together with rois=")
+        if warp is not None and (tensor is None or size is None or to is not None):
+            raise ValueError("warp: needs tensor=dict(...) and size=(H, W), and takes no colour transform")
         q = queue.Queue(maxsize=self.prefetch)
         th = threading.Thread(target=self._producer, args=(q,), daemon=True)
         th.start()
@@ -214,7 +221,10 @@ class StreamDecoder:
                     if v is not None:
                         kw.setdefault(k, v)
                 with self._lock:
-                    planes = dec.pic_output_tensor(cur, **kw)
+                    if warp is not None:
+                        planes = dec.pic_output_warped(cur, warp(p) if callable(warp) else warp, **kw)
+                    else:
+                        planes = dec.pic_output_tensor(cur, **kw)
             elif download and output_bit_depth is not None:
                 planes = dec.pic_output(cur, output_bit_depth, p["crop"] if self.apply_crop else (0, 0, 0, 0), dra=p["dra"])
             elif download and p["dra"] is not None:      # the DRA post-filter belongs to the output: planes through the output kernel
@@ -263,7 +273,7 @@ class StreamDecoder:
                 self._dec = None
 
     def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
-                     compare=None, stats=None):
+                     compare=None, stats=None, warp=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
@@ -271,7 +281,7 @@ class StreamDecoder:
         sequence in DECODING order): params["compare"], its map as a numpy array; stats= (as pictures takes it): params["stats"], its histograms as numpy arrays"""
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
-                                       residual=residual, compare=compare, stats=stats):
+                                       residual=residual, compare=compare, stats=stats, warp=warp):
             if p["is_idr"]:
                 epoch += 1
             if tensor is not None:
