@@ -495,6 +495,82 @@ size_t xgpu_output_warp_size(const xgpu_output_format *f, const xgpu_scale_param
 int    xgpu_pic_output_device_warp(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
                                    const xgpu_warp_params *wp, const xgpu_warp_map *maps, int maps_on_device, int n, int32_t *d_status, void *d_dst,
                                    size_t dst_size, void *stream);
+/* ---- remapped output (k_output_remap.hip): n coordinate grids of one picture, each giving one sc->width x sc->height image whose every pixel reads the source at
+   a position of its own - lens undistortion, fisheye dewarping into virtual views, perspective maps, the previous picture pulled through a flow field - converted
+   and normalised like the scaled output, as a batch from one kernel launch.  The general case of the warp above, whose gather, conversion, normalise, layouts,
+   dtypes and ordering rules it shares; the exact contract is INTEGRATION.md section 8k and tests/remap_ref.py restates it in numpy, bit for bit.
+   Geometry and grid
+     The source is the picture minus f->crop (even), Ws x Hs luma samples, as for the warp.  Nothing outside it reaches a result.
+     A position is Q16 in 1 / 65536 luma sample.  0 is the centre of luma sample 0 of the source (the warp's convention, and OpenCV's for maps).
+     The destination is sc->width x sc->height = dw x dh, each in 2 .. 16384 (outside: XGPU_ERR_UNSUPPORTED), and there are n images, 1 .. XGPU_MAX_ROIS.
+     The grid has step_log2 = k in 0 .. 6.  Node (j, i) belongs to destination pixel (i << k, j << k).  gw = ((dw - 1) >> k) + 1 + (k > 0), and gh alike.  Rows are
+     tight.  A node is the pair (x, y) in 8 bytes.  Grid g starts grid_pitch * g bytes behind d_grid; grid_pitch 0 means tight, else a multiple of 8 not shorter
+     than one grid.  The grid always lives in device memory: a map is made once and used for every picture, the host never reads it and the call does not
+     synchronise.  The caller states grid_size in bytes; it is checked on the host against (n - 1) * pitch + gh * gw * 8.
+   Grid formats
+     XGPU_GRID_Q16_I32   int32 x, y.  A node with INT32_MIN in either coordinate is invalid.  Every other bit pattern is a valid position.
+     XGPU_GRID_F32       float x, y in luma samples.  A non-finite coordinate makes the node invalid.  Otherwise c = min(max(v, -32767.0f), 32767.0f) and
+                         q = (int32)rintf(c * 65536.0f).  Every step is exact in float32, so numpy's np.rint on float32 restates it.
+   Position of pixel (ox, oy), in int64, arithmetic shifts
+     k = 0: P = node (oy, ox).
+     k > 0: i = ox >> k, fx = ox & (2^k - 1), j and fy alike, M = 2^k.  The four nodes are P00 = (j, i), P01 = (j, i + 1), P10 = (j + 1, i), P11 = (j + 1, i + 1).
+            X = ((M - fx)(M - fy) X00 + fx (M - fy) X01 + (M - fx) fy X10 + fx fy X11 + 2^(2k - 1)) >> 2k, and Y alike.
+   Derivatives, read only when samples S > 1
+     k > 0: D0x = ((M - fy)(X01 - X00) + fy (X11 - X10) + 2^(2k - 1)) >> 2k.
+            D1x = ((M - fx)(X10 - X00) + fx (X11 - X01) + 2^(2k - 1)) >> 2k.  D0y and D1y alike.
+     k = 0: D0 = P(oy, xa + 1) - P(oy, xa) with xa = min(ox, dw - 2).
+            D1 = P(ya + 1, ox) - P(ya, ox) with ya = min(oy, dh - 2).
+   Sub-positions and sampling, S = 1, 2 or 4
+     Xij = X + ((D0x (2i + 1 - S) + D1x (2j + 1 - S)) >> log2(2S)), and Y alike.
+     From Xij on, everything is the warp's, word for word: the luma and chroma bilinear sums with Q8 fractions, the chroma offset by f->chroma_loc, DRA and the
+     clip on every source sample, the rounding shift over S x S, then the conversion and normalise of xgpu_pic_output_device_scaled.
+     sc->filter must be XGPU_SCALE_BILINEAR, as for the warp.
+   Border and invalid pixels
+     XGPU_WARP_CLAMP and XGPU_WARP_PAD are reused, with the warp's rule applied to the pixel's own (X, Y).
+     A pixel for which any node that its formulas read is invalid is `pad` in both border modes.  For S = 1 that is the one node or the four of its cell.  For
+     S > 1 and k = 0 it also covers the derivative nodes.
+     pad is validated with XGPU_WARP_PAD's rules, and always, for either grid format, since both can carry invalid nodes.
+     Every position is clamped before it becomes an index, whatever the grid holds.  No node index beyond gw - 1 or gh - 1 is ever formed.
+   An affine grid (xgpu_remap_from_warp of a map whose nodes stay inside +-32767 samples) reproduces xgpu_pic_output_device_warp bit for bit at every k and S: the
+   interpolation of an affine function is exact, and the derivatives are the map's linear part.
+   Refusals, all before anything is queued:
+     XGPU_ERR_INVALID_ARGUMENT   n outside 1 .. XGPU_MAX_ROIS, step_log2 outside 0 .. 6, an unknown grid_format or border, samples not 1, 2 or 4, a filter other
+                                 than XGPU_SCALE_BILINEAR, a layout that is not one of the four three-channel ones, a bad pad, a bad image_pitch or grid_pitch,
+                                 grid_size or dst_size too short, a grid or destination that is not device memory or not aligned (grid: 8 bytes), and whatever
+                                 xgpu_pic_output_device_scaled refuses with this code
+     XGPU_ERR_UNSUPPORTED        sc->width or sc->height outside 2 .. 16384 */
+#define XGPU_GRID_Q16_I32 0
+#define XGPU_GRID_F32     1
+typedef struct xgpu_remap_params { int grid_format, step_log2, samples, border; float pad[3]; size_t grid_pitch, image_pitch; } xgpu_remap_params;
+/* Brown-Conrady lens with OpenCV's pixel convention: the camera that took the picture (fx, fy, cx, cy and the five coefficients) and the new, undistorted camera
+   whose image is wanted (nfx, nfy, ncx, ncy) */
+typedef struct xgpu_remap_lens { double fx, fy, cx, cy, k1, k2, p1, p2, k3, nfx, nfy, ncx, ncy; } xgpu_remap_lens;
+/* Host only, no context.  The nodes per row and the rows of a grid for a dst_w x dst_h image (dst_w, dst_h >= 1; gw, gh may be NULL) / the bytes the call reads
+   at d_grid, (n - 1) * pitch + gh * gw * 8, 0: refused (from `sc` width and height, from `rp` step_log2 and grid_pitch) */
+int    xgpu_remap_grid_dims(int dst_w, int dst_h, int step_log2, int *gw, int *gh);
+size_t xgpu_remap_grid_size(const xgpu_scale_params *sc, const xgpu_remap_params *rp, int n);
+/* Host only, no context: 0 or the code the call refuses with (everything but the sizes and the memory of d_grid and d_dst) / the bytes the call needs at d_dst -
+   (n - 1) * image_pitch + one image; 0: refused - for a picture of width x height at bit_depth */
+int    xgpu_output_remap_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_remap_params *rp, int n, int width, int height, int bit_depth);
+size_t xgpu_output_remap_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_remap_params *rp, int n, int width, int height, int bit_depth);
+/* Host only: write one XGPU_GRID_Q16_I32 grid of gh * gw nodes (xgpu_remap_grid_dims; dst_w, dst_h >= 2) into host memory, which the caller uploads once.
+   Node (j, i) is evaluated at ox = i << k, oy = j << k.  A value v in luma samples becomes t = v * 65536.0, then llround(min(max(t, -2147483647.0),
+   2147483647.0)); a non-finite t makes the node invalid (INT32_MIN, INT32_MIN).  Double operations in exactly the order written, none contracted.
+     from_warp        x = m[0] ox + m[1] oy + m[2], y = m[3] ox + m[4] oy + m[5] in int64 (exact: the map must be inside the warp's limits), clamped to
+                      [-INT32_MAX, INT32_MAX]
+     from_homography  u = ox + 0.5, v = oy + 0.5, den = (h[6] * u + h[7] * v) + h[8], x = ((h[0] * u + h[1] * v) + h[2]) / den - 0.5,
+                      y = ((h[3] * u + h[4] * v) + h[5]) / den - 0.5; den <= 0 (or NaN) makes the node invalid
+     from_lens        x = (ox - ncx) / nfx, y = (oy - ncy) / nfy, r2 = x * x + y * y, rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3)),
+                      xd = (x * rad + ((2 * p1) * x) * y) + p2 * (r2 + (2 * x) * x), yd = (y * rad + p1 * (r2 + (2 * y) * y)) + ((2 * p2) * x) * y,
+                      X = fx * xd + cx, Y = fy * yd + cy
+   XGPU_ERR_INVALID_ARGUMENT: a NULL, a size below 2, step_log2 outside 0 .. 6, a map outside the warp's limits. */
+int    xgpu_remap_from_warp(const xgpu_warp_map *map, int dst_w, int dst_h, int step_log2, int32_t *grid);
+int    xgpu_remap_from_homography(const double h[9], int dst_w, int dst_h, int step_log2, int32_t *grid);
+int    xgpu_remap_from_lens(const xgpu_remap_lens *lens, int dst_w, int dst_h, int step_log2, int32_t *grid);
+/* Non-blocking; d_dst, dst_size, stream and the ordering as for xgpu_pic_output_device_warp.  d_grid: grid_size bytes of grids on the context's device, written
+   before the call on `stream` (or complete); the host does not read them and the call does not synchronise or upload anything. */
+int    xgpu_pic_output_device_remap(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                                    const xgpu_remap_params *rp, const void *d_grid, size_t grid_size, int n, void *d_dst, size_t dst_size, void *stream);
 /* ---- coding side information (k_side_info.hip): what the decoder knows about a picture besides its samples - motion vectors per 4x4 luma unit, the
    reference each one points at, intra / inter / skip / IBC, QP, coded-residual flag, block edges - read out of the SCU map the in-loop filters read
    (the reference's map_scu / map_refi / map_mv, src_base/xevd_def.h:372-438).

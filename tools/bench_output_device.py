@@ -28,6 +28,12 @@ and alternates - the rois leg's protocol - route A, what a caller does without i
 border, align_corners=False) on its expand(64, ...) and the normalise, with route B: the one call, at samples = 1 and at samples = 4.  It also times the same
 boxes upright against rois= with the stretch fit: what gathering costs over the two separable passes.
 
+The remap leg (xgpu_pic_output_device_remap: k_output_remap) undistorts the whole picture through a Brown-Conrady lens grid to u8 planar R'G'B' at its own size,
+with one node per pixel (step 0) and with a mesh (step 4), S = 1; runs the identity mesh at step 4 beside the plain xgpu_pic_output_device call of the same form,
+which is its floor; and cuts four 1920x1080 virtual views out of an equidistant fisheye at S = 4, step 4 (a float32 mesh).  Each is alternated - the rois leg's
+protocol - with the torch route: the full-size f32 R'G'B' tensor plus grid_sample(bilinear, border, align_corners=False) through a dense normalised grid made once,
+and the largest difference between the two results is recorded in code values of the u8 output (the S = 4 views antialias, grid_sample does not).
+
 The residual leg (xgpu_batch_residual: k_resid_planes / k_resid_energy) writes the residual of a synthetic B-picture batch of the same size as int16 4:2:0
 planes, as 4:4:4 planar int16 and float16, and as the per-unit energy.  Bytes are algorithmic: the arena bytes actually coded (2 per sample of every coded
 component block), 4 per 4x4 unit of owner map, 32 per CU record, and what the form writes.  The whole measurement - copy rate included - is repeated --repeat
@@ -45,7 +51,7 @@ gradient with +-2 codes of noise: the contention of the LDS histogram depends on
 the light level.  Each is timed as the other legs are (the median of --iters calls queued behind a wait) and, alternated with it from an idle device, the torch
 route: a yuv420p tensor, then bincount, sum, min and max per plane; with light the u16 RGB tensor, amax, bincount and a gather through lin.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|warp|residual|compare|stats] [--out out/output_device.json]
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|warp|remap|residual|compare|stats] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -328,6 +334,92 @@ def warp_leg(torch, dec, pic, s, a, res):
     res["warp"] = r
 
 
+def remap_leg(torch, dec, pic, s, a, res):
+    """lens undistortion of the whole picture at step 0 and step 4, the identity mesh beside the plain output, four fisheye views at S = 4 - each alternated with the
+    full-size f32 tensor + grid_sample in torch"""
+    import torch.nn.functional as F
+    from xevd_amd import abi
+    w, h = a.width, a.height
+    dev = "cuda:0"
+    kw = dict(dtype=torch.uint8)
+    full = dec.pic_output_tensor(pic, dtype=torch.float32)
+
+    def norm_grid(q16):      # Q16 positions [.., 2] -> grid_sample's normalised coordinates (align_corners=False: sample i's centre at (2 i + 1) / n - 1)
+        g = torch.from_numpy(q16.astype(np.float32) / np.float32(65536.0)).to(dev)
+        return torch.stack([(2 * g[..., 0] + 1) / w - 1, (2 * g[..., 1] + 1) / h - 1], dim=-1)
+
+    def torch_route(ngrid):
+        dec.pic_output_tensor(pic, out=full, dtype=torch.float32)
+        return F.grid_sample(full[None].expand(ngrid.shape[0], -1, -1, -1), ngrid, mode="bilinear", padding_mode="border", align_corners=False)
+
+    def diff_codes(out_u8, ngrid):      # in code values of the u8 output, image by image (the f32 batch of all views at once is large)
+        return max(float((torch_route(ngrid[i:i + 1])[0] * 255.0 - out_u8[i].float()).abs().max()) for i in range(ngrid.shape[0]))
+
+    r = {}
+    # ---- the whole picture through a lens, at its own size
+    lens = dict(fx=0.8 * w, fy=0.8 * w, cx=w / 2 - 3.3, cy=h / 2 + 2.1, k1=-0.22, k2=0.06, p1=0.0008, p2=-0.0005, k3=-0.008, nfx=0.72 * w, nfy=0.72 * w, ncx=(w - 1) / 2,
+                ncy=(h - 1) / 2)
+    g0, g4 = (torch.from_numpy(abi.remap_from_lens(dec.lib, lens, (h, w), k)).to(dev) for k in (0, 4))
+    ng = norm_grid(abi.remap_from_lens(dec.lib, lens, (h, w), 0))[None]
+    outs = {k: dec.pic_output_remapped(pic, g, (h, w), step=k, **kw) for k, g in ((0, g0), (4, g4))}
+    routes = {"torch_route": lambda: torch_route(ng), "remap_step0": lambda: dec.pic_output_remapped(pic, g0, (h, w), step=0, out=outs[0], **kw),
+              "remap_step4": lambda: dec.pic_output_remapped(pic, g4, (h, w), step=4, out=outs[4], **kw)}
+    r["lens_full_size_u8"] = alternated(torch, s, routes, a.iters)
+    e = r["lens_full_size_u8"]
+    e["grid_bytes"] = {"step0": int(g0.numel() * 4), "step4": int(g4.numel() * 4)}
+    e["max_abs_diff_codes_step0_vs_torch_route"] = diff_codes(outs[0], ng)
+    e["max_abs_diff_codes_step4_vs_step0"] = int((outs[4].int() - outs[0].int()).abs().max())
+    for k in (0, 4):
+        e[f"speedup_step{k}"] = round(e["torch_route"]["us"] / e[f"remap_step{k}"]["us"], 2)
+    print(f"remap lens {w}x{h} u8: torch route {e['torch_route']['us']:9.1f} us   step 0 {e['remap_step0']['us']:9.1f} us ({e['speedup_step0']:.1f}x)   "
+          f"step 4 {e['remap_step4']['us']:9.1f} us ({e['speedup_step4']:.1f}x)   max |diff| step 0 {e['max_abs_diff_codes_step0_vs_torch_route']:.2f} codes")
+    del g0, ng
+    # ---- the identity mesh beside the plain output of the same form: the floor
+    gi = torch.from_numpy(abi.remap_from_warp(dec.lib, (65536, 0, 0, 0, 65536, 0), (h, w), 4)).to(dev)
+    plain = dec.pic_output_tensor(pic, upsample="linear", **kw)
+    routes = {"plain_output": lambda: dec.pic_output_tensor(pic, upsample="linear", out=plain, **kw),
+              "remap_identity_step4": lambda: dec.pic_output_remapped(pic, gi, (h, w), step=4, out=outs[4], **kw)}
+    r["identity_step4_vs_plain"] = alternated(torch, s, routes, a.iters)
+    e = r["identity_step4_vs_plain"]
+    e["equal"] = bool(torch.equal(outs[4][0], plain))
+    e["remap_over_plain"] = round(e["remap_identity_step4"]["us"] / e["plain_output"]["us"], 2)
+    print(f"remap identity step 4 {e['remap_identity_step4']['us']:9.1f} us   plain output {e['plain_output']['us']:9.1f} us   ({e['remap_over_plain']:.2f} of plain, equal: {e['equal']})")
+    del outs, plain, gi, g4
+    # ---- four virtual views of an equidistant fisheye (r = f theta), 1920 x 1080, S = 4, a float32 mesh at step 4
+    vh, vw, k, n = 1080, 1920, 4, 4
+    f_fish, f_view = min(w, h) / np.pi, 0.9 * vw      # a 180-degree circle inscribed in the picture; each view about 94 degrees wide
+
+    def fisheye(ox, oy, yaw, pitch):
+        x, y, z = (ox - (vw - 1) / 2) / f_view, (oy - (vh - 1) / 2) / f_view, np.ones_like(ox, dtype=np.float64)
+        cy_, sy_, cp, sp = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch)
+        y, z = y * cp - z * sp, y * sp + z * cp
+        x, z = x * cy_ + z * sy_, -x * sy_ + z * cy_
+        rho = np.hypot(x, y)
+        rad = f_fish * np.arctan2(rho, z) / np.maximum(rho, 1e-12)
+        return np.stack([x * rad + (w - 1) / 2, y * rad + (h - 1) / 2], axis=-1)
+
+    views = [(-0.7, -0.3), (0.7, -0.3), (-0.7, 0.3), (0.7, 0.3)]
+    gh, gw = abi.remap_grid_dims(dec.lib, (vh, vw), k)
+    nx, ny = np.meshgrid(np.arange(gw, dtype=np.float64) * (1 << k), np.arange(gh, dtype=np.float64) * (1 << k))
+    mesh = torch.from_numpy(np.stack([fisheye(nx, ny, *v) for v in views]).astype(np.float32)).to(dev)
+    px, py = np.meshgrid(np.arange(vw, dtype=np.float64), np.arange(vh, dtype=np.float64))
+    dense = np.stack([fisheye(px, py, *v) for v in views])
+    ngv = norm_grid(np.rint(dense * 65536.0))
+    out_v = dec.pic_output_remapped(pic, mesh, (vh, vw), step=k, samples=4, **kw)
+    out_1 = dec.pic_output_remapped(pic, mesh, (vh, vw), step=k, samples=1, **kw)
+    routes = {"torch_route": lambda: torch_route(ngv), "remap_s4": lambda: dec.pic_output_remapped(pic, mesh, (vh, vw), step=k, samples=4, out=out_v, **kw),
+              "remap_s1": lambda: dec.pic_output_remapped(pic, mesh, (vh, vw), step=k, samples=1, out=out_1, **kw)}
+    r["fisheye_4_views_1080p_u8"] = alternated(torch, s, routes, a.iters)
+    e = r["fisheye_4_views_1080p_u8"]
+    e["max_abs_diff_codes_s1_vs_torch_route"] = diff_codes(out_1, ngv)
+    e["max_abs_diff_codes_s4_vs_torch_route"] = diff_codes(out_v, ngv)
+    e["speedup_s4"] = round(e["torch_route"]["us"] / e["remap_s4"]["us"], 2)
+    e["speedup_s1"] = round(e["torch_route"]["us"] / e["remap_s1"]["us"], 2)
+    print(f"remap fisheye {n} x {vw}x{vh} u8 step {k}: torch route {e['torch_route']['us']:9.1f} us   S=4 {e['remap_s4']['us']:9.1f} us ({e['speedup_s4']:.2f}x)   "
+          f"S=1 {e['remap_s1']['us']:9.1f} us ({e['speedup_s1']:.2f}x)   max |diff| S=1 {e['max_abs_diff_codes_s1_vs_torch_route']:.2f} codes")
+    res["remap"] = r
+
+
 def residual_leg(torch, dec, pic, s, a, res):
     """the four residual forms on a decoded synthetic batch, --repeat runs, each with the copy rate measured next to it"""
     from xevd_amd import synth
@@ -542,9 +634,9 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "warp", "residual", "compare", "stats"), default="all",
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "warp", "remap", "residual", "compare", "stats"), default="all",
                     help="full: the full-size forms and the side information; scaled: the scaled leg alone; rois: the batched regions of interest alone; "
-                         "rois_dev: the regions of interest from boxes in device memory alone; warp: the warped regions of interest alone; residual: the residual "
+                         "rois_dev: the regions of interest from boxes in device memory alone; warp: the warped regions of interest alone; remap: the remapped output alone; residual: the residual "
                          "export alone; compare: the picture comparison alone; stats: the picture statistics alone")
     a = ap.parse_args()
     import torch
@@ -587,6 +679,8 @@ def main():
             rois_dev_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "warp"):
             warp_leg(torch, dec, pic, s, a, res)
+        if a.legs in ("all", "remap"):
+            remap_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "residual"):
             residual_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "compare"):

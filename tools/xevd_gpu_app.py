@@ -141,6 +141,10 @@ def main():
                     "the matrix / range / chroma siting of the stream's VUI: INTEGRATION.md 8d); with --to: not supported")
     ap.add_argument("--tiles", default=None, metavar="WxH", help="with --size: every picture as its grid of W x H tiles (the last column / row moved back inside the "
                     "picture), each resized to --size by one call per picture (INTEGRATION.md 8e); the frames written are the tiles, row by row")
+    ap.add_argument("--remap", default=None, metavar="GRID.npy", help="with --size: every picture pulled through this coordinate grid on the device instead of resized "
+                    "(INTEGRATION.md 8k): an int32 (Q16) or float32 (luma samples) array [gh, gw, 2] or [N, gh, gw, 2] of source positions for the W x H image, "
+                    "e.g. from abi.remap_from_lens; N > 1 writes N frames per picture")
+    ap.add_argument("--remap-step", type=int, default=0, metavar="K", help="with --remap: the grid holds a node every 2^K pixels (0 .. 6; 0: one per pixel)")
     ap.add_argument("--ref", default=None, metavar="FILE.yuv", help="compare every decoded picture with this planar 4:2:0 file on the device (INTEGRATION.md 8h): frames "
                     "of the uncropped picture at the stream's depth (8 bit: bytes, else 16-bit little endian), as -o writes them; prints PSNR, SSIM, the number "
                     "of differing samples and the first differing position per picture, and a summary")
@@ -154,6 +158,8 @@ def main():
     cmp = RefCompare(args.ref, args.ref_order, args.expect_identical, args.device) if args.ref else None
     if args.tiles is not None and args.size is None:
         ap.error("--tiles: needs --size")
+    if args.remap is not None and (args.size is None or args.tiles is not None):
+        ap.error("--remap: needs --size, and not --tiles")
     data = open(args.input, "rb").read()
     t0 = time.perf_counter()
     side = {} if args.side_info else None
@@ -176,7 +182,15 @@ def main():
             except ValueError:
                 ap.error(f"--tiles: expected WxH, not {args.tiles!r}")
             rois = lambda p: abi.tile_rois(p["width"], p["height"], tw, th)      # noqa: E731
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois, residual=resid, compare=cmp, stats=stats)
+        remap = None
+        if args.remap is not None:
+            import numpy as np
+            remap = np.load(args.remap)
+            if remap.dtype not in (np.int32, np.float32):
+                ap.error(f"--remap: an int32 or float32 array, not {remap.dtype}")
+            remap = torch.from_numpy(remap).to(f"cuda:{args.device}")      # uploaded once, used for every picture
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois, residual=resid, compare=cmp, stats=stats,
+                                                                    remap=remap, remap_step=args.remap_step)
     elif args.to is not None:
         import torch
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats)

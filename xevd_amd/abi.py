@@ -393,6 +393,84 @@ def output_warp_size(lib, fmt, sc, wp, n, width, height, bit_depth):
     return lib.xgpu_output_warp_size(C.byref(fmt), C.byref(sc), C.byref(wp), int(n), int(width), int(height), int(bit_depth))
 
 
+GRID_Q16_I32, GRID_F32 = 0, 1
+GRID_INVALID = -(1 << 31)      # INT32_MIN in either coordinate of a Q16 node: the node is invalid
+
+
+class RemapParams(C.Structure):
+    _fields_ = [("grid_format", C.c_int), ("step_log2", C.c_int), ("samples", C.c_int), ("border", C.c_int), ("pad", C.c_float * 3), ("grid_pitch", C.c_size_t),
+                ("image_pitch", C.c_size_t)]
+
+
+class RemapLens(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "nfx", "nfy", "ncx", "ncy")]
+
+
+def make_remap_params(grid_format=GRID_Q16_I32, step_log2=0, samples=1, border=WARP_CLAMP, pad=0.0, grid_pitch=0, image_pitch=0):
+    """xgpu_remap_params (include/xevd_hip.h): GRID_Q16_I32 / GRID_F32, a node every 2^step_log2 pixels, sub-positions per axis (1, 2, 4), WARP_CLAMP / WARP_PAD,
+    the pad value - one value or three, by the channel's position in the output, before the normalise - and the bytes between two grids / two images (0: tight)"""
+    p = RemapParams()
+    p.grid_format, p.step_log2, p.samples, p.border = int(grid_format), int(step_log2), int(samples), int(border)
+    p.grid_pitch, p.image_pitch = int(grid_pitch), int(image_pitch)
+    v = np.broadcast_to(np.asarray(pad, np.float32), (3,))
+    for k in range(3):
+        p.pad[k] = float(v[k])
+    return p
+
+
+def remap_grid_dims(lib, dst_size, step=0):
+    """xgpu_remap_grid_dims: (gh, gw) of the grid of an image of dst_size = (H, W) with a node every 2^step pixels, or the negative code"""
+    gw, gh = C.c_int(), C.c_int()
+    rc = lib.xgpu_remap_grid_dims(int(dst_size[1]), int(dst_size[0]), int(step), C.byref(gw), C.byref(gh))
+    return rc if rc < 0 else (gh.value, gw.value)
+
+
+def remap_grid_size(lib, sc, rp, n):
+    """xgpu_remap_grid_size: the bytes the call reads at d_grid, 0 = refused"""
+    return lib.xgpu_remap_grid_size(C.byref(sc), C.byref(rp), int(n))
+
+
+def output_remap_check(lib, fmt, sc, rp, n, width, height, bit_depth):
+    """xgpu_output_remap_check: 0 or the code the call refuses with"""
+    return lib.xgpu_output_remap_check(C.byref(fmt), C.byref(sc), C.byref(rp), int(n), int(width), int(height), int(bit_depth))
+
+
+def output_remap_size(lib, fmt, sc, rp, n, width, height, bit_depth):
+    """xgpu_output_remap_size: the bytes the batch needs, 0 = refused"""
+    return lib.xgpu_output_remap_size(C.byref(fmt), C.byref(sc), C.byref(rp), int(n), int(width), int(height), int(bit_depth))
+
+
+def _remap_helper(lib, name, arg, dst_size, step):
+    dims = remap_grid_dims(lib, dst_size, step)
+    if not isinstance(dims, tuple):
+        return dims
+    grid = np.empty((*dims, 2), np.int32)
+    rc = getattr(lib, name)(arg, int(dst_size[1]), int(dst_size[0]), int(step), grid.ctypes.data_as(C.POINTER(C.c_int32)))
+    return rc if rc < 0 else grid
+
+
+def remap_from_warp(lib, m, dst_size, step=0):
+    """xgpu_remap_from_warp: the Q16 grid int32 [gh, gw, 2] of the affine map m (six Q16 integers) for an image of dst_size = (H, W), or the negative code"""
+    return _remap_helper(lib, "xgpu_remap_from_warp", make_warp_maps([m]), dst_size, step)
+
+
+def remap_from_homography(lib, h, dst_size, step=0):
+    """xgpu_remap_from_homography: the Q16 grid of the 3 x 3 matrix h (nine floats, row-major; destination pixel centres -> continuous source coordinates)"""
+    return _remap_helper(lib, "xgpu_remap_from_homography", (C.c_double * 9)(*[float(v) for v in np.asarray(h, np.float64).reshape(9)]), dst_size, step)
+
+
+def remap_from_lens(lib, lens, dst_size, step=0):
+    """xgpu_remap_from_lens: the Q16 grid that undistorts a Brown-Conrady lens; lens: a dict with fx, fy, cx, cy, the new camera nfx, nfy, ncx, ncy (default: the
+    old one) and any of k1, k2, p1, p2, k3 (default 0)"""
+    l = RemapLens()
+    d = dict(lens)
+    for k in ("fx", "fy", "cx", "cy"):
+        d.setdefault("n" + k, d[k])
+    for k, _ in RemapLens._fields_:
+        setattr(l, k, float(d.get(k, 0.0)))
+    return _remap_helper(lib, "xgpu_remap_from_lens", C.byref(l), dst_size, step)
+
+
 CM_CURVE_U0, CM_CURVE_SIZE = 0x1F800000, 64 * 32 + 3
 
 
@@ -613,6 +691,15 @@ _EXPORTS = {
     "xgpu_output_warp_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(WarpParams), C.c_int, C.c_int, C.c_int, C.c_int]),
     "xgpu_pic_output_device_warp": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(WarpParams), C.c_void_p,
                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_remap_grid_dims": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "xgpu_remap_grid_size": (C.c_size_t, [C.POINTER(ScaleParams), C.POINTER(RemapParams), C.c_int]),
+    "xgpu_output_remap_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RemapParams), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "xgpu_output_remap_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RemapParams), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "xgpu_remap_from_warp": (C.c_int, [C.POINTER(WarpMap), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "xgpu_remap_from_homography": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "xgpu_remap_from_lens": (C.c_int, [C.POINTER(RemapLens), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "xgpu_pic_output_device_remap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RemapParams), C.c_void_p,
+                                               C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_side_info_size": (C.c_size_t, [C.POINTER(SideFormat), C.c_int, C.c_int]),
     "xgpu_frame_side_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SideFormat), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_resid_size": (C.c_size_t, [C.POINTER(ResidFormat), C.c_int, C.c_int]),

@@ -337,3 +337,26 @@ template <bool PLANAR, int SZ> __device__ __forceinline__ void store_pixel(uint8
         for (int k = 0; k < 3; k++) store_elem<SZ>(d + k * SZ, e[k]);
     }
 }
+// ---- the gather of the warped and the remapped output (k_output_warp.hip, k_output_remap.hip; INTEGRATION.md sections 8j, 8k)
+// Q16 position + `add` -> Q8 (shift 8: luma) or Q8 chroma samples (shift 9), clamped to [0, top]: what every index is made from
+__device__ __forceinline__ int warp_q8(uint64_t pos, uint64_t add, int shift, int top)
+{
+    const int64_t r = (int64_t)(pos + add) >> shift;
+    return (int)min(max(r, (int64_t)0), (int64_t)top);
+}
+// sample (row, col) of plane c (inside the plane): DRA (a chroma sample by the unmapped luma at (2 row, 2 col)), then the clip
+__device__ __forceinline__ int warp_sample(const ScaledOutArgs &a, int c, const int16_t *pl, int st, int row, int col)
+{
+    int v = pl[(size_t)row * st + col];
+    if (a.dra) v = dra1(a.dra, c, v, c ? (int)a.y[(size_t)(2 * row) * a.sy + 2 * col] : 0);
+    return min(max(v, 0), a.smax);
+}
+// the bilinear sum of plane c (pw x ph samples) at the clamped Q8 position (xr, yr): below 2^16 * 2^B
+__device__ __forceinline__ uint32_t warp_bilinear(const ScaledOutArgs &a, int c, const int16_t *pl, int st, int pw, int ph, int xr, int yr)
+{
+    const int ix = xr >> 8, fx = xr & 255, ix1 = min(ix + 1, pw - 1);
+    const int iy = yr >> 8, fy = yr & 255, iy1 = min(iy + 1, ph - 1);
+    const int p00 = warp_sample(a, c, pl, st, iy, ix), p01 = warp_sample(a, c, pl, st, iy, ix1);
+    const int p10 = warp_sample(a, c, pl, st, iy1, ix), p11 = warp_sample(a, c, pl, st, iy1, ix1);
+    return (uint32_t)((256 - fx) * (256 - fy) * p00 + fx * (256 - fy) * p01 + (256 - fx) * fy * p10 + fx * fy * p11);
+}

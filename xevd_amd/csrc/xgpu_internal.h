@@ -562,6 +562,22 @@ struct WarpOutArgs : ScaledOutArgs {
     size_t   image_pitch;           // bytes between two images
 };
 void launch_output_warp(const WarpOutArgs &a, int layout, int dtype, hipStream_t s);
+// k_output_remap.hip: n coordinate grids of one picture, each giving one dw x dh image (xgpu_pic_output_device_remap).  ScaledOutArgs'
+// fields as WarpOutArgs reads them, then the batch's
+struct RemapOutArgs : ScaledOutArgs {
+    const uint8_t *grid;            // grid 0 on the device: [gh][gw] nodes of 8 bytes, (x, y) int32 Q16 or float32 luma samples; never read by the host
+    size_t   grid_pitch;            // bytes between two grids
+    int      gw, gh;                // nodes per row / rows of a grid
+    int      k;                     // step_log2: a node every 2^k pixels (0: one per pixel)
+    int      f32;                   // 1 = XGPU_GRID_F32
+    int      n;
+    int      ls;                    // log2 of `samples`
+    int      border;                // XGPU_WARP_CLAMP / XGPU_WARP_PAD
+    int      sh, sv;                // the chroma siting, as WarpOutArgs'
+    float    padv[3];               // the pad value by output position, before the normalise (integer dtypes: the integer)
+    size_t   image_pitch;           // bytes between two images
+};
+void launch_output_remap(const RemapOutArgs &a, int layout, int dtype, hipStream_t s);
 void launch_test_scale_taps(int n_plane, int subsampling, int siting, int n_dst, int filter, int32_t *first, int32_t *count, int16_t *w, int w_stride, hipStream_t s);
 // k_output_yuv.hip (k_output_semiplanar): NV12 / P016 - xgpu_pic_output's samples, luma rows then rows of interleaved Cb Cr
 struct SemiPlanarArgs {

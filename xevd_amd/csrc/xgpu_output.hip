@@ -1,5 +1,5 @@
 // xgpu_output.hip - the C ABI of include/xevd_hip.h, part 2: the outputs into device memory - the picture as it is, colour-managed, scaled, as a batch of regions of
-// interest (rectangles from the host or boxes in device memory) or of affine maps, the coding side information, the residual, the comparison with a reference and the statistics
+// interest (rectangles from the host or boxes in device memory), of affine maps or of coordinate grids, the coding side information, the residual, the comparison with a reference and the statistics
 // of one picture - and their argument checks without a device.
 // Every entry point is the same skeleton: check the format -> check_dst -> (check_dra; tables, made on the host) -> grow a context buffer -> out_fork -> fill an args struct ->
 // launch -> out_join.  Host-side code only; the kernels live in k_output*.hip, k_side_info.hip, k_residual.hip, k_compare.hip and k_stats.hip.
@@ -944,6 +944,169 @@ int xgpu_pic_output_device_warp(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, 
     a.image_pitch = image_pitch;
     launch_output_warp(a, f->layout, f->dtype, s);
     return out_join(c, stream, s);      // the slot, the DRA tables and the block of maps
+}
+
+// ------------------------------------------------------------------------------------------------ remapped output: a batch of coordinate grids in device memory
+int xgpu_remap_grid_dims(int dst_w, int dst_h, int step_log2, int *gw, int *gh)
+{
+    if (dst_w < 1 || dst_h < 1 || step_log2 < 0 || step_log2 > 6) return XGPU_ERR_INVALID_ARGUMENT;
+    if (gw) *gw = ((dst_w - 1) >> step_log2) + 1 + (step_log2 > 0);
+    if (gh) *gh = ((dst_h - 1) >> step_log2) + 1 + (step_log2 > 0);
+    return XGPU_OK;
+}
+// the bytes of one grid and (*pitch, may be NULL) between two; 0: refused, `why` (160 bytes) says which field
+static size_t remap_grid_bytes(const xgpu_scale_params *sc, const xgpu_remap_params *rp, size_t *pitch, char *why)
+{
+    int gw, gh;
+    if (!sc || !rp || sc->width < 1 || sc->height < 1 || xgpu_remap_grid_dims(sc->width, sc->height, rp->step_log2, &gw, &gh) < 0) {
+        snprintf(why, 160, "step_log2 must be 0..6");
+        return 0;
+    }
+    const size_t one = (size_t)gh * gw * 8;
+    if (rp->grid_pitch && (rp->grid_pitch % 8 || rp->grid_pitch < one)) {
+        snprintf(why, 160, "grid_pitch %zu: 0, or a multiple of 8 not below the %zu bytes of one grid of %d x %d nodes", rp->grid_pitch, one, gw, gh);
+        return 0;
+    }
+    if (pitch) *pitch = rp->grid_pitch ? rp->grid_pitch : one;
+    return one;
+}
+size_t xgpu_remap_grid_size(const xgpu_scale_params *sc, const xgpu_remap_params *rp, int n)
+{
+    char why[160]; size_t pitch = 0;
+    if (n < 1 || n > XGPU_MAX_ROIS) return 0;
+    const size_t one = remap_grid_bytes(sc, rp, &pitch, why);
+    return one ? (size_t)(n - 1) * pitch + one : 0;
+}
+// The whole of a call's argument checks that need no device: the bytes the destination needs, or 0 with *rc = the code and `why` (160 bytes)
+static size_t remap_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_remap_params *rp, int n, int width, int height, int bd, int *rc, char *why,
+                         size_t *image_pitch)
+{
+    const char *w0 = "";
+    if (!scaled_params_ok(f, sc, width, height, bd, rc, &w0)) { snprintf(why, 160, "%s", w0); return 0; }
+    const size_t image = scaled_image_bytes(f, sc, rc, &w0);
+    if (image == 0) { snprintf(why, 160, "%s", w0); return 0; }
+    *rc = XGPU_ERR_INVALID_ARGUMENT;
+    if (sc->filter != XGPU_SCALE_BILINEAR) { snprintf(why, 160, "filter must be XGPU_SCALE_BILINEAR"); return 0; }
+    if (!rp) { snprintf(why, 160, "remap parameters are NULL"); return 0; }
+    if (n < 1 || n > XGPU_MAX_ROIS) { snprintf(why, 160, "n %d outside 1..%d", n, XGPU_MAX_ROIS); return 0; }
+    if (rp->grid_format != XGPU_GRID_Q16_I32 && rp->grid_format != XGPU_GRID_F32) { snprintf(why, 160, "grid_format must be XGPU_GRID_Q16_I32 or XGPU_GRID_F32"); return 0; }
+    if (rp->samples != 1 && rp->samples != 2 && rp->samples != 4) { snprintf(why, 160, "samples must be 1, 2 or 4"); return 0; }
+    if (rp->border != XGPU_WARP_CLAMP && rp->border != XGPU_WARP_PAD) { snprintf(why, 160, "border must be XGPU_WARP_CLAMP or XGPU_WARP_PAD"); return 0; }
+    if (remap_grid_bytes(sc, rp, NULL, why) == 0) return 0;
+    xgpu_roi_params roi;      // the pad and the batch stride follow the rules of the regions of interest; either grid format can carry invalid nodes: the pad is always read
+    roi.fit = XGPU_FIT_STRETCH; roi.image_pitch = rp->image_pitch;
+    for (int k = 0; k < 3; k++) roi.pad[k] = rp->pad[k];
+    const size_t ip = rois_pad_and_pitch(f, sc, &roi, bd, image, true, why);
+    if (ip == 0) return 0;
+    *rc = XGPU_OK;
+    if (image_pitch) *image_pitch = ip;
+    return (size_t)(n - 1) * ip + image;
+}
+int xgpu_output_remap_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_remap_params *rp, int n, int width, int height, int bit_depth)
+{
+    int rc; char why[160];
+    (void)remap_size(f, sc, rp, n, width, height, bit_depth, &rc, why, NULL);
+    return rc;
+}
+size_t xgpu_output_remap_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_remap_params *rp, int n, int width, int height, int bit_depth)
+{
+    int rc; char why[160];
+    return remap_size(f, sc, rp, n, width, height, bit_depth, &rc, why, NULL);
+}
+// a helper's value in luma samples -> Q16: non-finite = invalid (INT32_MIN), else llround of the product clamped to +-INT32_MAX
+static bool remap_q16(double x, double y, int32_t *node)
+{
+    #pragma clang fp contract(off)
+    const double tx = x * 65536.0, ty = y * 65536.0;
+    if (!std::isfinite(tx) || !std::isfinite(ty)) { node[0] = node[1] = INT32_MIN; return false; }
+    node[0] = (int32_t)llround(std::min(std::max(tx, -2147483647.0), 2147483647.0));
+    node[1] = (int32_t)llround(std::min(std::max(ty, -2147483647.0), 2147483647.0));
+    return true;
+}
+int xgpu_remap_from_warp(const xgpu_warp_map *map, int dst_w, int dst_h, int step_log2, int32_t *grid)
+{
+    int gw, gh;
+    if (!map || !grid || dst_w < 2 || dst_h < 2 || xgpu_remap_grid_dims(dst_w, dst_h, step_log2, &gw, &gh) < 0 || !warp_map_ok(*map)) return XGPU_ERR_INVALID_ARGUMENT;
+    const int64_t *m = map->m;
+    for (int j = 0; j < gh; j++)
+        for (int i = 0; i < gw; i++) {      // exact in int64: |m| <= 2^36, the coordinates below 2^15
+            const int64_t ox = (int64_t)i << step_log2, oy = (int64_t)j << step_log2;
+            const int64_t x = m[0] * ox + m[1] * oy + m[2], y = m[3] * ox + m[4] * oy + m[5];
+            grid[2 * ((size_t)j * gw + i)] = (int32_t)std::min<int64_t>(std::max<int64_t>(x, -INT32_MAX), INT32_MAX);
+            grid[2 * ((size_t)j * gw + i) + 1] = (int32_t)std::min<int64_t>(std::max<int64_t>(y, -INT32_MAX), INT32_MAX);
+        }
+    return XGPU_OK;
+}
+int xgpu_remap_from_homography(const double h[9], int dst_w, int dst_h, int step_log2, int32_t *grid)
+{
+    #pragma clang fp contract(off)
+    int gw, gh;
+    if (!h || !grid || dst_w < 2 || dst_h < 2 || xgpu_remap_grid_dims(dst_w, dst_h, step_log2, &gw, &gh) < 0) return XGPU_ERR_INVALID_ARGUMENT;
+    for (int j = 0; j < gh; j++)
+        for (int i = 0; i < gw; i++) {
+            const double u = (double)((int64_t)i << step_log2) + 0.5, v = (double)((int64_t)j << step_log2) + 0.5;
+            const double den = h[6] * u + h[7] * v + h[8];
+            int32_t *node = grid + 2 * ((size_t)j * gw + i);
+            if (!(den > 0.0)) { node[0] = node[1] = INT32_MIN; continue; }
+            (void)remap_q16((h[0] * u + h[1] * v + h[2]) / den - 0.5, (h[3] * u + h[4] * v + h[5]) / den - 0.5, node);
+        }
+    return XGPU_OK;
+}
+int xgpu_remap_from_lens(const xgpu_remap_lens *l, int dst_w, int dst_h, int step_log2, int32_t *grid)
+{
+    #pragma clang fp contract(off)
+    int gw, gh;
+    if (!l || !grid || dst_w < 2 || dst_h < 2 || xgpu_remap_grid_dims(dst_w, dst_h, step_log2, &gw, &gh) < 0) return XGPU_ERR_INVALID_ARGUMENT;
+    for (int j = 0; j < gh; j++)
+        for (int i = 0; i < gw; i++) {
+            const double x = ((double)((int64_t)i << step_log2) - l->ncx) / l->nfx, y = ((double)((int64_t)j << step_log2) - l->ncy) / l->nfy;
+            const double r2 = x * x + y * y;
+            const double rad = 1.0 + r2 * (l->k1 + r2 * (l->k2 + r2 * l->k3));
+            const double xd = x * rad + 2.0 * l->p1 * x * y + l->p2 * (r2 + 2.0 * x * x);
+            const double yd = y * rad + l->p1 * (r2 + 2.0 * y * y) + 2.0 * l->p2 * x * y;
+            (void)remap_q16(l->fx * xd + l->cx, l->fy * yd + l->cy, grid + 2 * ((size_t)j * gw + i));
+        }
+    return XGPU_OK;
+}
+int xgpu_pic_output_device_remap(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_remap_params *rp,
+                                 const void *d_grid, size_t grid_size, int n, void *d_dst, size_t dst_size, void *stream)
+{
+    static const char who[] = "pic_output_device_remap";
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL); ARGCHK(c, d_grid != NULL);
+    int src_rc; char why[160];
+    size_t image_pitch = 0, grid_pitch = 0;
+    const size_t need = remap_size(f, sc, rp, n, c->sp.width, c->sp.height, c->sp.bit_depth_luma, &src_rc, why, &image_pitch);
+    if (need == 0) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return src_rc; }
+    const size_t one_grid = remap_grid_bytes(sc, rp, &grid_pitch, why), grids = (size_t)(n - 1) * grid_pitch + one_grid;
+    if (grid_size < grids || (uintptr_t)d_grid % 8) {
+        snprintf(c->err, sizeof(c->err), "%s: grid of %zu bytes at %p, the call needs %zu bytes aligned to 8", who, grid_size, d_grid, grids);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    TRY(check_dst_fits(c, who, d_dst, dst_size, need, elem_size(f->dtype)));
+    if (dra) TRY(check_dra(c, dra));      // upload_dra's refusals, before anything is queued
+    TRY(check_device_dst(c, who, d_dst, need));
+    TRY(check_device_dst(c, "pic_output_device_remap (grid)", const_cast<void *>(d_grid), grids));
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    RemapOutArgs a;
+    memset(&a, 0, sizeof(a));
+    scaled_common_args(c, pic, dra, f, sc, d_dst, a);
+    a.w = c->sp.width - f->crop[0] - f->crop[1]; a.h = c->sp.height - f->crop[2] - f->crop[3]; a.cw = a.w >> 1; a.ch = a.h >> 1;
+    a.grid = (const uint8_t *)d_grid;
+    a.grid_pitch = grid_pitch;
+    (void)xgpu_remap_grid_dims(sc->width, sc->height, rp->step_log2, &a.gw, &a.gh);
+    a.k = rp->step_log2;
+    a.f32 = rp->grid_format == XGPU_GRID_F32;
+    a.n = n;
+    a.ls = rp->samples == 4 ? 2 : rp->samples == 2 ? 1 : 0;
+    a.border = rp->border;
+    a.sh = f->chroma_loc & 1;
+    a.sv = f->chroma_loc < 2 ? 1 : f->chroma_loc < 4 ? 0 : 2;
+    for (int k = 0; k < 3; k++) a.padv[k] = rp->pad[k];
+    a.image_pitch = image_pitch;
+    launch_output_remap(a, f->layout, f->dtype, s);
+    return out_join(c, stream, s);      // the slot and the DRA tables; the grid is the caller's, ordered by the caller's stream
 }
 
 // ------------------------------------------------------------------------------------------------ coding side information of the picture decoded last

@@ -444,6 +444,64 @@ class XgpuDecoder:
                           C.c_void_p(maps.data_ptr()) if on_device else ma, int(on_device), n, C.c_void_p(res.data_ptr()) if res is not None else None)
         return (out, res) if on_device and status else out
 
+    def pic_output_remapped(self, pic, grid, size, step=0, samples=1, border="clamp", pad=None, layout="rgb", channels_last=False, dtype=None, matrix=1,
+                            full_range=False, chroma_loc=0, crop=(0, 0, 0, 0), dra=None, bgr=False, mean=None, std=None, out=None):
+        """N coordinate grids of the picture, each giving one H x W image (size=(H, W)) whose every pixel reads the picture at a position of its own, converted
+        and normalised like pic_output_tensor(size=...), as one batch [N, 3, H, W] (channels_last: [N, H, W, 3]) from one kernel launch
+        (xgpu_pic_output_device_remap): lens undistortion, fisheye views, perspective maps, a flow field.  Integer arithmetic from the
+        node to (Y, Cb, Cr): tests/remap_ref.py restates the result bit for bit.
+        grid: a torch tensor on the decoder's device, [N, gh, gw, 2] or [gh, gw, 2] (one image), (gh, gw) = abi.remap_grid_dims(lib, size, step): a node (x, y)
+        every 2^step destination pixels (step 0 .. 6; 0: one per pixel), interpolated exactly in between.  int32: Q16, 1 / 65536 luma sample, 0 = the centre of
+        sample 0 of the picture minus the crop, INT32_MIN in either coordinate = invalid (abi.remap_from_warp / _from_homography / _from_lens make such grids);
+        float32: luma samples, a non-finite coordinate = invalid.  Each grid must be contiguous; grids may lie a batch stride apart (a multiple of 8 bytes).  It is
+        read on the device with no host read and no synchronisation.  A numpy array of one of the two dtypes is uploaded first.
+        samples 1, 2 or 4: sub-positions per axis along the grid's local derivatives.  border "clamp" replicates the picture's edge, "pad" writes `pad` where
+        the pixel's position lies outside the picture; a pixel that reads an invalid node is `pad` under either (pad: one value or three, in the output's
+        channel order, before the normalise; integers for the integer dtypes; default 0).  out: as for pic_output_warped."""
+        import torch
+        if border not in ("clamp", "pad"):
+            raise ValueError(f"border must be 'clamp' or 'pad', not {border!r}")
+        a = {"layout": layout, "colour": None, "filter": "bilinear", "mean": mean, "std": std, "out_bit_depth": 0, "dtype": dtype, "size": size,
+             "channels_last": channels_last, "bgr": bgr, "matrix": matrix, "full_range": full_range, "chroma_loc": chroma_loc, "crop": crop}
+        dtype, fmt, sc, h, w, dev = self._scaled_setup(a)
+        if isinstance(grid, np.ndarray):
+            if grid.dtype not in (np.int32, np.float32):
+                raise ValueError(f"grid: an int32 (Q16) or float32 array, not {grid.dtype}")
+            grid = torch.from_numpy(np.ascontiguousarray(grid)).to(dev)
+        dims = abi.remap_grid_dims(self.lib, (h, w), step)
+        if not isinstance(dims, tuple):
+            raise ValueError(f"step must be 0..6 and size at least (1, 1), not step {step}, size {tuple(size)}")
+        if not isinstance(grid, torch.Tensor) or grid.device != dev or grid.dtype not in (torch.int32, torch.float32):
+            raise ValueError(f"grid: an int32 or float32 tensor on {dev} (or such a numpy array)")
+        if grid.dim() == 3:
+            grid = grid.unsqueeze(0)
+        one = dims[0] * dims[1] * 2
+        if grid.dim() != 4 or tuple(grid.shape[1:]) != (*dims, 2) or grid.shape[0] < 1 or grid.stride()[1:] != (dims[1] * 2, 2, 1) \
+                or (grid.shape[0] > 1 and (grid.stride(0) < one or grid.stride(0) % 2)):
+            raise ValueError(f"grid: [N, {dims[0]}, {dims[1]}, 2] for size {(h, w)} at step {step}, every grid contiguous and an even number of elements apart, not "
+                             f"{tuple(grid.shape)} with strides {grid.stride()}")
+        n = int(grid.shape[0])
+        rp = abi.make_remap_params(abi.GRID_F32 if grid.dtype == torch.float32 else abi.GRID_Q16_I32, step, samples, abi.WARP_PAD if border == "pad" else abi.WARP_CLAMP,
+                                   0.0 if pad is None else pad, grid_pitch=grid.stride(0) * 4 if n > 1 else 0)
+
+        def refuse():
+            rc = abi.output_remap_check(self.lib, fmt, sc, rp, n, self.width, self.height, self.bit_depth)
+            if rc < 0:
+                raise ValueError(f"invalid remapped output ({rc}): layout {layout}, size {tuple(size)}, step {step}, samples {samples}, border {border}, pad {pad}, "
+                                 f"crop {crop}, mean {mean}, std {std}, {n} grids")
+        planar = not channels_last
+        if out is None:
+            refuse()      # before a tensor is made, and again with its pitches
+        out = _out_tensor(out, (n, 3, h, w) if planar else (n, h, w, 3), dtype, dev)
+        st = out.stride()
+        fmt.row_pitch = _row_pitch(st, planar, h, w if planar else 3 * w, 3) * dtype.itemsize
+        rp.image_pitch = st[0] * dtype.itemsize if n > 1 else 0
+        refuse()
+        dl, self._dra_keep = self._dra_luts(dra) if dra is not None else (None, None)      # (kept until the next call: the tables are copied asynchronously)
+        self._device_call("xgpu_pic_output_device_remap", out, pic, dl, C.byref(fmt), C.byref(sc), C.byref(rp), C.c_void_p(grid.data_ptr()),
+                          abi.remap_grid_size(self.lib, sc, rp, n), n)
+        return out
+
     def _run_stream(self, dev):
         """(torch's current stream, the stream a kernel of the C ABI is queued on): torch's default stream is the null stream, whose handle (0) means "the
         context's stream" to the C ABI - such a call runs on a side stream of torch's between two stream waits instead (the caller makes the second one)"""

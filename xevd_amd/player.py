@@ -116,7 +116,7 @@ class StreamDecoder:
         return cm
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
-                 residual=None, compare=None, stats=None, warp=None):
+                 residual=None, compare=None, stats=None, warp=None, remap=None, remap_step=0):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -139,6 +139,9 @@ class StreamDecoder:
         warp=[theta, ...], an int64 [N, 6] array or tensor of Q16 maps, or a callable(params) -> one of these (with tensor= and size=, called as rois= is):
         every picture as the batch [N, 3, H, W] of its affine maps (XgpuDecoder.pic_output_warped; tensor=dict(samples=, border=, pad=, status=) go with it,
         and pic_output_tensor's arguments that the warped output does not have must be left out).  Not together with rois=
+        remap=grid, or a callable(params) -> grid (with tensor= and size=, called as warp= is): every picture as the batch [N, 3, H, W] of its coordinate grids
+        (XgpuDecoder.pic_output_remapped: an int32 Q16 or float32 tensor on the decoder's device - made once, used for every picture - or such a numpy array;
+        remap_step = its step; tensor=dict(samples=, border=, pad=) go with it).  Not together with rois= or warp=
         compare=callable(params) -> a reference or None, or a sequence of such indexed in decoding order (shorter: the pictures past its end are not
         compared): every picture against its reference on the device (XgpuDecoder.pic_compare: a tensor in pic_output's plane order on the decoder's device; a
         dict(ref=..., ssim=..., block_map=...) passes pic_compare's other arguments), taken right behind the picture's kernels; the result - pic_compare's
@@ -159,6 +162,10 @@ class StreamDecoder:
             raise ValueError("warp: not together with rois=")
         if warp is not None and (tensor is None or size is None or to is not None):
             raise ValueError("warp: needs tensor=dict(...) and size=(H, W), and takes no colour transform")
+        if remap is not None and (rois is not None or warp is not None):
+            raise ValueError("remap: not together with rois= or warp=")
+        if remap is not None and (tensor is None or size is None or to is not None):
+            raise ValueError("remap: needs tensor=dict(...) and size=(H, W), and takes no colour transform")
         q = queue.Queue(maxsize=self.prefetch)
         th = threading.Thread(target=self._producer, args=(q,), daemon=True)
         th.start()
@@ -223,6 +230,8 @@ class StreamDecoder:
                 with self._lock:
                     if warp is not None:
                         planes = dec.pic_output_warped(cur, warp(p) if callable(warp) else warp, **kw)
+                    elif remap is not None:
+                        planes = dec.pic_output_remapped(cur, remap(p) if callable(remap) else remap, step=remap_step, **kw)
                     else:
                         planes = dec.pic_output_tensor(cur, **kw)
             elif download and output_bit_depth is not None:
@@ -273,7 +282,7 @@ class StreamDecoder:
                 self._dec = None
 
     def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
-                     compare=None, stats=None, warp=None):
+                     compare=None, stats=None, warp=None, remap=None, remap_step=0):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
@@ -281,7 +290,7 @@ class StreamDecoder:
         sequence in DECODING order): params["compare"], its map as a numpy array; stats= (as pictures takes it): params["stats"], its histograms as numpy arrays"""
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
-                                       residual=residual, compare=compare, stats=stats, warp=warp):
+                                       residual=residual, compare=compare, stats=stats, warp=warp, remap=remap, remap_step=remap_step):
             if p["is_idr"]:
                 epoch += 1
             if tensor is not None:
