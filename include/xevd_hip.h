@@ -571,6 +571,47 @@ int    xgpu_remap_from_lens(const xgpu_remap_lens *lens, int dst_w, int dst_h, i
    before the call on `stream` (or complete); the host does not read them and the call does not synchronise or upload anything. */
 int    xgpu_pic_output_device_remap(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
                                     const xgpu_remap_params *rp, const void *d_grid, size_t grid_size, int n, void *d_dst, size_t dst_size, void *stream);
+/* ---- scaled video surfaces (k_output_ladder.hip): n renditions ("rungs", 1 .. XGPU_MAX_RUNGS) of one decoded picture as 4:2:0 video surfaces, each at its own
+   even width x height in its own destination, all in one layout - XGPU_OUT_YUV420P, XGPU_OUT_NV12 or XGPU_OUT_P016 (any other: XGPU_ERR_INVALID_ARGUMENT): the
+   2160p / 1080p / 720p / 360p ladder of an adaptive-bitrate transcode from one call - two kernel launches and one upload, however many rungs.
+   The source is the active picture minus f->crop (even), Ws x Hs luma samples, DRA-mapped (when `dra` is given) and clipped to [0, 2^B - 1], as for the scaled
+   output.  Luma of a rung is the scaled output's luma unchanged: rows xgpu_scale_taps(Hs, 1, 0, Hd), columns xgpu_scale_taps(Ws, 1, 0, Wd), vertical first,
+   t = (sum qy * sample + 2^10) >> 11, then v = (sum qx * t + 2^16) >> 17.  A chroma plane of Wd / 2 x Hd / 2 is filtered straight from the Ws / 2 x Hs / 2 plane by
+   the same two passes with the tables of xgpu_scale_taps_ex(Hs / 2, 2, dy, Hd / 2, 2, Dy) and (Ws / 2, 2, dx, Wd / 2, 2, Dx): (dx, dy) the siting of f->chroma_loc,
+   (Dx, Dy) that of lp->dst_chroma_loc (-1: f->chroma_loc) on the rung's own grid, in half luma samples.  No pass goes through luma resolution.  Every rung is
+   filtered from the source, so rung i of a call is what a call with that rung alone writes.  The filtered sample (coding depth B) then goes through the depth rule
+   of xgpu_pic_output to D = f->out_bit_depth (0: B) and is packed as xgpu_pic_output_device packs the layout: YUV420P tight (row_pitch 0; U8 at D = 8, else U16),
+   NV12 U8 / U16 with the value in the low bits, P016 the word shifted left by 16 - D; the dtype / out_bit_depth pairs accepted are those of xgpu_pic_output_device.
+   matrix, full_range, upsample and f->row_pitch are not read; bgr must be 0.  With a rung the size of the source and the destination siting the source's, the rung
+   is xgpu_pic_output_device's surface bit for bit (dra NULL, or tables that map inside [0, 2^B - 1]).
+   lp->filter: XGPU_SCALE_BILINEAR or XGPU_SCALE_AREA.  A rung: width, height, row_pitch (bytes between rows, 0: tight; a multiple of the element size and at least
+   a row), d_dst / dst_size (device memory of the context's device, element-aligned, at least xgpu_output_ladder_rung_size bytes).
+     XGPU_ERR_INVALID_ARGUMENT   n outside 1 .. XGPU_MAX_RUNGS, an odd rung size, an odd crop, an unknown filter, dst_chroma_loc outside -1 .. 5, a layout outside the
+                                 three, a dtype / out_bit_depth pair xgpu_pic_output_device refuses, a pitch with YUV420P or shorter than a row, a NULL, misaligned,
+                                 undersized or host destination, two rungs whose byte ranges overlap
+     XGPU_ERR_UNSUPPORTED        a rung outside 2 .. 16384 or outside Ws / 64 <= Wd <= 8 Ws per axis; intermediates of all rungs above 512 MiB together
+   Every refusal comes before anything is queued.  The exact contract: INTEGRATION.md section 8l; tests/ladder_ref.py restates it in numpy. */
+#define XGPU_MAX_RUNGS 8
+typedef struct xgpu_surface_rung { int width, height; size_t row_pitch; void *d_dst; size_t dst_size; } xgpu_surface_rung;
+typedef struct xgpu_ladder_params { int filter; int dst_chroma_loc; } xgpu_ladder_params;
+/* Host only, no context: xgpu_scale_taps for a destination with a subsampling (1, 2) and a siting (0, 1, 2 half luma samples of the destination grid) of its
+   own.  Per axis, n plane samples of subsampling s and siting d onto N samples of subsampling S and siting D: r = n s / (N S), f = max(1, r S / s),
+   c(o) = ((S o + D + 1/2) r - 1/2 - d) / s; everything behind c and f is xgpu_scale_taps'.  The limits count luma samples: N S >= 2, N <= 16384,
+   n s / 64 <= N S <= 8 n s.  dst_subsampling 1 and dst_siting_half_luma 0 give xgpu_scale_taps row for row.  Integer arithmetic only. */
+int    xgpu_scale_taps_ex(int n_plane, int subsampling, int siting_half_luma, int n_dst, int dst_subsampling, int dst_siting_half_luma, int filter,
+                          int32_t *first, int32_t *count, int16_t *w, int w_stride);
+/* Host only, no context: the bytes a rung of rung_width x rung_height needs at its d_dst - xgpu_output_format_size of the layout at that size with that pitch and
+   no crop; 0: refused.  xgpu_output_ladder_check: 0, or the code xgpu_pic_output_device_ladder refuses with for a picture of width x height (uncropped) at coding
+   depth bit_depth; it reads dst_size and does not look at d_dst. */
+size_t xgpu_output_ladder_rung_size(const xgpu_output_format *f, int rung_width, int rung_height, size_t row_pitch, int bit_depth);
+int    xgpu_output_ladder_check(const xgpu_output_format *f, const xgpu_ladder_params *lp, const xgpu_surface_rung *rungs, int n, int width, int height,
+                                int bit_depth);
+/* Non-blocking; stream as xgpu_pic_output_device takes it.  The records and the tap tables of all rungs lie in one block of the context, uploaded once per call: the
+   tables are made again only when the source size, the rung sizes, the filter or either siting differ from the previous call's (else the upload is the records
+   alone); the intermediate is the scaled output's and grows on demand (growing it waits for the device).  Ordered like the scaled output: calls on different streams
+   follow one another through the context's stream. */
+int    xgpu_pic_output_device_ladder(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_ladder_params *lp,
+                                     const xgpu_surface_rung *rungs, int n, void *stream);
 /* ---- coding side information (k_side_info.hip): what the decoder knows about a picture besides its samples - motion vectors per 4x4 luma unit, the
    reference each one points at, intra / inter / skip / IBC, QP, coded-residual flag, block edges - read out of the SCU map the in-loop filters read
    (the reference's map_scu / map_refi / map_mv, src_base/xevd_def.h:372-438).

@@ -51,7 +51,14 @@ gradient with +-2 codes of noise: the contention of the LDS histogram depends on
 the light level.  Each is timed as the other legs are (the median of --iters calls queued behind a wait) and, alternated with it from an idle device, the torch
 route: a yuv420p tensor, then bincount, sum, min and max per plane; with light the u16 RGB tensor, amax, bincount and a gather through lin.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|warp|remap|residual|compare|stats] [--out out/output_device.json]
+The ladder leg (xgpu_pic_output_device_ladder: k_ladder_vertical + k_ladder_horizontal) takes the picture to P010 rungs 3840x2160, 1920x1080, 1280x720 and
+640x360 with centre chroma siting on both sides and alternates - the rois leg's protocol - the one call with the route without it (the full-size P010 surface,
+then per rung and plane torch's interpolate(bilinear, antialias=True), rounding and repacking) and with the plain full-size surface, the floor of reading the
+picture once; four one-rung calls are alternated on their own (each makes its tap tables again: the context keeps those of one key).  `device_us` is the time
+of the kernels alone (median of --iters calls queued behind a wait).  The largest difference between each rung's planes and the torch route in float64 is
+recorded in code values; it is a record, not a test.
+
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|ladder|warp|remap|residual|compare|stats] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -267,6 +274,76 @@ def alternated(torch, s, routes, iters, warm=5):
         r[k] = {"us": round(float(np.median(us)), 2), "p10_us": round(float(np.percentile(us, 10)), 2), "p90_us": round(float(np.percentile(us, 90)), 2),
                 "host_us": round(float(np.median(host[k])), 2)}
     return r
+
+
+def ladder_leg(torch, dec, pic, s, a, res):
+    """the picture to P010 rungs 3840x2160, 1920x1080, 1280x720 and 640x360 (those inside the scaled output's limits for the picture): the one call
+    (pic_output_surfaces) against four one-rung calls, against the route without it - the full-size P010 surface, then per rung and plane
+    torch.nn.functional.interpolate(antialias=True), rounding and repacking in torch - and against the plain full-size surface as the floor, alternated.  Centre
+    siting (chroma_loc 1) on both sides, where a chroma plane is a plain plane resize, so that both routes compute the same picture; the largest difference between
+    them is reported in code values, the torch route in float64."""
+    import torch.nn.functional as F
+    w, h, bd = a.width, a.height, a.bit_depth
+    sizes = [(hh, ww) for hh, ww in ((2160, 3840), (1080, 1920), (720, 1280), (360, 640)) if h <= 64 * hh <= 512 * h and w <= 64 * ww <= 512 * w]
+    kw = dict(layout="p016", dtype=torch.int16, out_bit_depth=10, chroma_loc=1)
+    full_kw = dict(layout="p016", dtype=torch.int16, out_bit_depth=10)
+    outs = dec.pic_output_surfaces(pic, sizes, **kw)
+    singles = [dec.pic_output_surfaces(pic, [sz], **kw) for sz in sizes]
+    full = dec.pic_output_tensor(pic, **full_kw)
+
+    def planes_of(surface, hh, ww, ft):      # a P010 surface -> Y [1, 1, H, W] and Cb Cr [1, 2, H / 2, W / 2] as code values
+        v = ((surface.to(torch.int32) & 0xFFFF) >> 6).to(ft)
+        return v[:hh].view(1, 1, hh, ww), v[hh:].view(1, hh // 2, ww // 2, 2).permute(0, 3, 1, 2)
+
+    def torch_route(ft=torch.float32, pack=True):
+        dec.pic_output_tensor(pic, out=full, **full_kw)
+        y, c = planes_of(full, h, w, ft)
+        made = []
+        for hh, ww in sizes:
+            ys = F.interpolate(y, size=(hh, ww), mode="bilinear", antialias=True, align_corners=False)
+            cs = F.interpolate(c, size=(hh // 2, ww // 2), mode="bilinear", antialias=True, align_corners=False)
+            if not pack:
+                made.append((ys, cs))
+                continue
+            o = torch.empty((hh * 3 // 2, ww), dtype=torch.int16, device=full.device)
+            o[:hh] = (ys[0, 0].round().clamp(0, 1023).to(torch.int32) << 6).to(torch.int16)
+            o[hh:] = (cs[0].permute(1, 2, 0).reshape(hh // 2, ww).round().clamp(0, 1023).to(torch.int32) << 6).to(torch.int16)
+            made.append(o)
+        return made
+
+    def four_calls():
+        for sz, o in zip(sizes, singles):
+            dec.pic_output_surfaces(pic, [sz], out=o, **kw)
+
+    routes = {"torch_route": torch_route, "ladder_one_call": lambda: dec.pic_output_surfaces(pic, sizes, out=outs, **kw),
+              "full_size_surface": lambda: dec.pic_output_tensor(pic, out=full, **full_kw)}
+    r = {"sizes": [[ww, hh] for hh, ww in sizes], "layout": "p010", "chroma_loc": 1, **alternated(torch, s, routes, a.iters)}
+    # on their own: the context keeps the tap tables of one key, so each of the four calls makes its tables again - a cost of that route, not of the one call
+    r.update(alternated(torch, s, {"ladder_four_calls": four_calls}, a.iters))
+    # the kernels alone: the median of --iters calls queued behind a wait, as the full-size forms are timed
+    r["ladder_one_call"]["device_us"] = round(timed(torch, s, routes["ladder_one_call"], a.iters), 2)
+    r["ladder_four_calls"]["device_us"] = round(timed(torch, s, four_calls, a.iters), 2)
+    r["full_size_surface"]["device_us"] = round(timed(torch, s, routes["full_size_surface"], a.iters), 2)
+    read = int(w * h * 3)                                              # the 16-bit picture once
+    written = sum(hh * ww * 3 for hh, ww in sizes)                     # 16-bit surfaces
+    r["bytes_picture"], r["bytes_rungs"], r["bytes_intermediate"] = read, written, sum(2 * (hh * w + 2 * (hh // 2) * (w // 2)) for hh, ww in sizes)
+    r["speedup_over_torch_route"] = round(r["torch_route"]["us"] / r["ladder_one_call"]["us"], 2)
+    r["four_calls_over_one_call"] = round(r["ladder_four_calls"]["us"] / r["ladder_one_call"]["us"], 2)
+    r["one_call_over_full_size_surface"] = round(r["ladder_one_call"]["us"] / r["full_size_surface"]["us"], 2)
+    # the minimum traffic of the call as it is built - every rung reads the picture, writes and reads its intermediate, writes its surface - at the copy rate
+    traffic = len(sizes) * read + 2 * r["bytes_intermediate"] + written
+    r["bytes_moved_as_built"] = traffic
+    if res.get("copy_gbps"):
+        r["copy_rate_time_as_built_us"] = round(traffic / (res["copy_gbps"] * 1e9) * 1e6, 1)
+    diffs = []
+    for (ys, cs), o, (hh, ww) in zip(torch_route(torch.float64, pack=False), outs, sizes):
+        yo, co = planes_of(o, hh, ww, torch.float64)
+        diffs.append({"size": [ww, hh], "luma": round(float((ys - yo).abs().max()), 4), "chroma": round(float((cs - co).abs().max()), 4)})
+    r["max_abs_diff_codes_vs_torch_f64"] = diffs
+    print(f"ladder {len(sizes)} P010 rungs: torch route {r['torch_route']['us']:9.1f} us   one call {r['ladder_one_call']['us']:9.1f} us ({r['speedup_over_torch_route']:.2f}x)   "
+          f"four calls {r['ladder_four_calls']['us']:9.1f} us   kernels alone {r['ladder_one_call']['device_us']:8.1f} us   full-size surface {r['full_size_surface']['us']:8.1f} us   max |diff| "
+          + ", ".join(f"{d['size'][0]}x{d['size'][1]}: {d['luma']:.3f} / {d['chroma']:.3f}" for d in diffs))
+    res["ladder"] = r
 
 
 def warp_leg(torch, dec, pic, s, a, res):
@@ -634,9 +711,9 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "warp", "remap", "residual", "compare", "stats"), default="all",
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats"), default="all",
                     help="full: the full-size forms and the side information; scaled: the scaled leg alone; rois: the batched regions of interest alone; "
-                         "rois_dev: the regions of interest from boxes in device memory alone; warp: the warped regions of interest alone; remap: the remapped output alone; residual: the residual "
+                         "rois_dev: the regions of interest from boxes in device memory alone; ladder: the ladder of scaled P010 surfaces alone; warp: the warped regions of interest alone; remap: the remapped output alone; residual: the residual "
                          "export alone; compare: the picture comparison alone; stats: the picture statistics alone")
     a = ap.parse_args()
     import torch
@@ -677,6 +754,8 @@ def main():
             rois_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "rois_dev"):
             rois_dev_leg(torch, dec, pic, s, a, res)
+        if a.legs in ("all", "ladder"):
+            ladder_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "warp"):
             warp_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "remap"):

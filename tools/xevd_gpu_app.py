@@ -2,7 +2,9 @@
 """Decode an MPEG-5 EVC Baseline bitstream on the MI355X and write planar YUV - the counterpart of the reference's sample
 application (app/xevd_app.c: -i in.evc -o out.yuv --output-bit-depth N).  usage: xevd_gpu_app.py -i in.evc -o out.yuv
 --pix-fmt nv12 / p010 writes semi-planar frames instead (what a raw-video reader takes as nv12 / p010le): 8-bit samples, or 10-bit samples in the
-high bits of 16-bit words, whatever the stream's depth."""
+high bits of 16-bit words, whatever the stream's depth.
+--ladder 3840x2160,1920x1080,... also writes every picture scaled to each of these sizes on the device, in one call per picture: one file per
+rung next to -o, the size in its name (out_1920x1080.yuv), in the --pix-fmt layout."""
 import argparse
 import os
 import sys
@@ -151,8 +153,27 @@ def main():
     ap.add_argument("--ref-order", choices=("output", "decoding"), default="output", help="the order of the frames in --ref: output order (what -o and the reference "
                     "application write; needs POCs that count 0, 1, 2, ... from every IDR picture) or decoding order")
     ap.add_argument("--expect-identical", action="store_true", help="with --ref: exit with status 1 at the first picture that differs from its frame")
+    ap.add_argument("--ladder", default=None, metavar="WxH,WxH,...", help="also write every picture scaled to each of these even sizes (1 .. 8 of them) on the device, "
+                    "as --pix-fmt surfaces: one file per size next to -o, OUT_WxH.EXT; yuv420p takes --output-bit-depth (8: bytes)")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
+    lad, lad_sizes = {}, []
+    if args.ladder is not None:
+        import torch
+        if not args.output:
+            ap.error("--ladder: needs -o, whose name the files of the rungs are made from")
+        try:
+            lad_sizes = [tuple(int(v) for v in item.lower().split("x")) for item in args.ladder.split(",")]
+            assert all(len(sz) == 2 for sz in lad_sizes)
+        except (ValueError, AssertionError):
+            ap.error(f"--ladder: expected WxH,WxH,..., not {args.ladder!r}")
+        if args.pix_fmt == "nv12":
+            so = dict(dtype=torch.uint8)
+        elif args.pix_fmt == "p010":
+            so = dict(dtype=torch.int16, out_bit_depth=10)
+        else:
+            so = dict(dtype=torch.uint8) if args.output_bit_depth == 8 else dict(dtype=torch.int16, out_bit_depth=args.output_bit_depth)
+        lad = dict(surfaces=[(hh, ww) for ww, hh in lad_sizes], surface_layout="p016" if args.pix_fmt == "p010" else args.pix_fmt, surface_options=so)
     if args.expect_identical and args.ref is None:
         ap.error("--expect-identical: needs --ref")
     cmp = RefCompare(args.ref, args.ref_order, args.expect_identical, args.device) if args.ref else None
@@ -190,16 +211,16 @@ def main():
                 ap.error(f"--remap: an int32 or float32 array, not {remap.dtype}")
             remap = torch.from_numpy(remap).to(f"cuda:{args.device}")      # uploaded once, used for every picture
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois, residual=resid, compare=cmp, stats=stats,
-                                                                    remap=remap, remap_step=args.remap_step)
+                                                                    remap=remap, remap_step=args.remap_step, **lad)
     elif args.to is not None:
         import torch
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad)
     elif args.pix_fmt == "yuv420p":
-        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side, residual=resid, compare=cmp, stats=stats)
+        pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side, residual=resid, compare=cmp, stats=stats, **lad)
     else:      # the same pictures as semi-planar surfaces (xgpu_pic_output_device into a torch tensor, copied to the host picture by picture)
         import torch
         opts = dict(layout="nv12", dtype=torch.uint8) if args.pix_fmt == "nv12" else dict(layout="p016", dtype=torch.int16, out_bit_depth=10)
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid, compare=cmp, stats=stats)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid, compare=cmp, stats=stats, **lad)
     dt = time.perf_counter() - t0
     if cmp is not None:
         cmp.finish()
@@ -207,6 +228,11 @@ def main():
         with open(args.output, "wb") as f:
             for _, frame in pics:
                 f.write(frame.tobytes())
+    base, ext = os.path.splitext(args.output or "")
+    for i, (ww, hh) in enumerate(lad_sizes):
+        with open(f"{base}_{ww}x{hh}{ext}", "wb") as f:
+            for p, _ in pics:
+                f.write(p["surfaces"][i].tobytes())
     if args.side_info:
         with open(args.side_info, "wb") as f:
             for p, _ in sorted(pics, key=lambda t: t[0]["decode_index"]):

@@ -256,6 +256,46 @@ def scale_taps_device(lib, ctx, n_plane, subsampling, siting_half_luma, n_dst, f
     return rc if rc < 0 else (first, count, w)
 
 
+def scale_taps_ex(lib, n_plane, subsampling, siting_half_luma, n_dst, dst_subsampling=1, dst_siting_half_luma=0, filter=SCALE_BILINEAR):
+    """xgpu_scale_taps_ex as numpy arrays - scale_taps for a destination with a subsampling and a siting of its own (the chroma planes of a surface ladder):
+    (first, count, w) as scale_taps gives them, or the negative code"""
+    first, count = np.zeros(max(int(n_dst), 1), np.int32), np.zeros(max(int(n_dst), 1), np.int32)
+    pi, pc = first.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_int32))
+    args = (int(n_plane), int(subsampling), int(siting_half_luma), int(n_dst), int(dst_subsampling), int(dst_siting_half_luma), int(filter))
+    widest = lib.xgpu_scale_taps_ex(*args, pi, pc, None, 0)
+    if widest < 0:
+        return widest
+    w = np.zeros((int(n_dst), widest), np.int16)
+    rc = lib.xgpu_scale_taps_ex(*args, pi, pc, w.ctypes.data_as(C.POINTER(C.c_int16)), widest)
+    return rc if rc < 0 else (first, count, w)
+
+
+MAX_RUNGS = 8
+
+
+class SurfaceRung(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("row_pitch", C.c_size_t), ("d_dst", C.c_void_p), ("dst_size", C.c_size_t)]
+
+
+class LadderParams(C.Structure):
+    _fields_ = [("filter", C.c_int), ("dst_chroma_loc", C.c_int)]
+
+
+def make_ladder_params(filter=SCALE_BILINEAR, dst_chroma_loc=None):
+    """xgpu_ladder_params (include/xevd_hip.h): the filter and the chroma siting of the rungs (None: the source's, f->chroma_loc)"""
+    p = LadderParams()
+    p.filter, p.dst_chroma_loc = int(filter), -1 if dst_chroma_loc is None else int(dst_chroma_loc)
+    return p
+
+
+def make_rungs(rungs):
+    """[(width, height, row_pitch, d_dst, dst_size), ...] -> an array of xgpu_surface_rung (d_dst may be None)"""
+    arr = (SurfaceRung * max(len(rungs), 1))()
+    for i, (w, h, pitch, ptr, size) in enumerate(rungs):
+        arr[i].width, arr[i].height, arr[i].row_pitch, arr[i].d_dst, arr[i].dst_size = int(w), int(h), int(pitch), ptr, int(size)
+    return arr
+
+
 FIT_STRETCH, FIT_LETTERBOX = 0, 1
 MAX_ROIS = 1024
 
@@ -673,6 +713,11 @@ _EXPORTS = {
     "xgpu_output_scaled_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),
     "xgpu_output_scaled_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),
     "xgpu_pic_output_device_scaled": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_scale_taps_ex": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16), C.c_int]),
+    "xgpu_output_ladder_rung_size": (C.c_size_t, [C.POINTER(OutputFormat), C.c_int, C.c_int, C.c_size_t, C.c_int]),
+    "xgpu_output_ladder_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(LadderParams), C.POINTER(SurfaceRung), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "xgpu_pic_output_device_ladder": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(LadderParams), C.POINTER(SurfaceRung), C.c_int,
+                                                C.c_void_p]),
     "xgpu_roi_inner": (C.c_int, [C.POINTER(Roi), C.POINTER(ScaleParams), C.c_int, C.POINTER(C.c_int)]),
     "xgpu_output_rois_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(Roi), C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(C.c_int)]),

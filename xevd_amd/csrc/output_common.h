@@ -64,7 +64,8 @@ template <int DT> __device__ __forceinline__ uint32_t fbits(float f)
     return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
 }
 
-// N elements of SZ bytes, packed into 32-bit words and stored: vector stores at `dst` (aligned) or one element at a time (first n elements)
+// N elements of SZ bytes, packed into 32-bit words and stored: vector stores at `dst` (aligned for them: 4 bytes for a run of one word, 16 for runs of whole groups of
+// four words, 8 for the others) or one element at a time (first n elements)
 template <int N, int SZ> __device__ __forceinline__ void store_run(uint8_t *dst, const uint32_t (&e)[N], bool vec, int n)
 {
     if (vec) {
@@ -74,7 +75,9 @@ template <int N, int SZ> __device__ __forceinline__ void store_run(uint8_t *dst,
         for (int i = 0; i < NW; i++) w[i] = 0;
         #pragma unroll
         for (int i = 0; i < N; i++) w[i * SZ / 4] |= e[i] << (8 * ((i * SZ) % 4));
-        if (NW % 4 == 0) {
+        if (NW == 1) {
+            *(uint32_t *)dst = w[0];
+        } else if (NW % 4 == 0) {
             #pragma unroll
             for (int i = 0; i < NW; i += 4) *(uint4 *)(dst + 4 * i) = make_uint4(w[i], w[i + 1], w[i + 2], w[i + 3]);
         } else {

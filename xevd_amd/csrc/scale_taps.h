@@ -10,9 +10,10 @@
 
 #define XGPU_HD __host__ __device__ __forceinline__
 
-// One axis of one plane (the notation of xgpu_scale.hip): n plane samples, subsampling s, siting h half luma samples, N destination samples, over D = 2 s N.
+// One axis of one plane (the notation of xgpu_scale.hip): n plane samples, subsampling s, siting h half luma samples, N destination samples of subsampling S and
+// siting H half luma samples of the destination grid (S = 1, H = 0: a destination at luma resolution, xgpu_scale_taps), over D = 2 s N S.
 struct ScaleAxis {
-    int64_t n, s, h, N, D, F, reach;
+    int64_t n, s, h, N, S, H, D, F, reach;
     int     filter;
     int     kspan;      // the samples looked at from the first candidate of a row on: covers every sample within `reach` of the centre
     int     kw;         // no row is wider than this: floor(2 F / D) + 2
@@ -20,17 +21,21 @@ struct ScaleAxis {
 
 XGPU_HD int64_t scale_floor_div(int64_t a, int64_t b) { return a / b - ((a % b != 0) && ((a < 0) != (b < 0))); }      // b > 0
 
-XGPU_HD void scale_axis_init(ScaleAxis &ax, int n_plane, int subsampling, int siting_half_luma, int n_dst, int filter)
+XGPU_HD void scale_axis_init(ScaleAxis &ax, int n_plane, int subsampling, int siting_half_luma, int n_dst, int filter, int dst_subsampling = 1,
+                             int dst_siting_half_luma = 0)
 {
-    ax.n = n_plane; ax.s = subsampling; ax.h = siting_half_luma; ax.N = n_dst; ax.filter = filter;
-    ax.D = 2 * ax.s * ax.N;
-    ax.F = ax.D > 2 * ax.s * ax.n ? ax.D : 2 * ax.s * ax.n;
+    ax.n = n_plane; ax.s = subsampling; ax.h = siting_half_luma; ax.N = n_dst; ax.S = dst_subsampling; ax.H = dst_siting_half_luma; ax.filter = filter;
+    ax.D = 2 * ax.s * ax.N * ax.S;
+    ax.F = ax.D > 2 * ax.s * ax.S * ax.n ? ax.D : 2 * ax.s * ax.S * ax.n;
     // the samples that can have a positive weight: |i - c| < f (BILINEAR), |i - c| < (f + 1) / 2 (AREA) - one more on either side costs nothing
     ax.reach = filter == XGPU_SCALE_BILINEAR ? ax.F : (ax.F + ax.D + 1) / 2;
     // floor((C + reach) / D) + 1 - (floor((C - reach) / D) - 1) <= floor(2 reach / D) + 3 for every C
     ax.kspan = (int)(2 * ax.reach / ax.D) + 3;
     ax.kw = (int)(2 * ax.F / ax.D) + 2;
 }
+
+// the centre of destination sample o over D: C = (2 S o + H + 1) n s - (1 + h) N S
+XGPU_HD int64_t scale_centre(const ScaleAxis &ax, int o) { return (2 * ax.S * (int64_t)o + ax.H + 1) * ax.n * ax.s - (1 + ax.h) * ax.N * ax.S; }
 
 // the numerator u(i) of sample i in the row whose centre is C / D (<= 0: no weight)
 XGPU_HD int64_t scale_tap_num(const ScaleAxis &ax, int64_t C, int64_t i)
@@ -47,7 +52,7 @@ XGPU_HD int64_t scale_tap_num(const ScaleAxis &ax, int64_t C, int64_t i)
 // *U = 0: no sample of the plane lies under the window (a siting that moves the grid off the plane's end) - the nearest sample alone, with the whole weight.
 XGPU_HD int scale_tap_span(const ScaleAxis &ax, int o, int32_t *first, int64_t *U)
 {
-    const int64_t C = (2 * (int64_t)o + 1) * ax.n * ax.s - (1 + ax.h) * ax.N;
+    const int64_t C = scale_centre(ax, o);
     const int64_t l0 = scale_floor_div(C - ax.reach, ax.D) - 1;
     const int64_t lo = l0 > 0 ? l0 : 0, hi = l0 + ax.kspan < ax.n - 1 ? l0 + ax.kspan : ax.n - 1;
     int64_t i0 = 0, sum = 0;
@@ -73,7 +78,7 @@ XGPU_HD int scale_tap_span(const ScaleAxis &ax, int o, int32_t *first, int64_t *
 // zeros from cnt up to `width`.
 XGPU_HD void scale_tap_weights(const ScaleAxis &ax, int o, int32_t first, int cnt, int64_t U, int16_t *q, size_t step, int width)
 {
-    const int64_t C = (2 * (int64_t)o + 1) * ax.n * ax.s - (1 + ax.h) * ax.N;
+    const int64_t C = scale_centre(ax, o);
     int64_t sum = 0, bestv = 0;
     int best = 0;
     for (int k = 0; k < cnt; k++) {
@@ -86,7 +91,7 @@ XGPU_HD void scale_tap_weights(const ScaleAxis &ax, int o, int32_t first, int cn
     for (int k = cnt; k < width; k++) q[(size_t)k * step] = 0;
 }
 
-// one axis: n source samples to N destination samples is inside the limits of the scaled output
+// one axis: n source samples to N destination samples is inside the limits of the scaled output (both counted in luma samples)
 XGPU_HD bool scale_ratio_ok(int n, int N) { return N >= 2 && n <= 64 * (int64_t)N && N <= 8 * (int64_t)n; }
 
 // the filtered part of a ws x hs rectangle inside a wd x hd image (xgpu_roi_inner)

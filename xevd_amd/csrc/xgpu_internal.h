@@ -326,6 +326,7 @@ struct xgpu_dbatch {
 // the device block of the scaled output's tap tables, as the host laid it out: per table (0 yl, 1 yc, 2 xl, 3 xc) the byte offsets of first[], count[] and w[], the
 // weights' stride, and the widest span of source samples 64 neighbouring destination columns reach (pass 2's LDS need), rounded to whole groups of 8
 struct ScaleTabs { size_t off_first[4], off_count[4], off_w[4]; int stride[4]; int capy, capc; };
+struct ScaleAxisTab { size_t first, count, w; int stride; };      // one table in a host blob: byte offsets of first[], count[] and the weights (xgpu_scale.hip)
 struct xgpu_ctx {
     xgpu_seq_params sp;
     int8_t          chroma_qp[2][96];  // [c][qp + 6*(bdc-8)]
@@ -374,6 +375,15 @@ struct xgpu_ctx {
     uint8_t        *roi_blk;          // xgpu_pic_output_device_rois: the descriptors and tap tables of the current call (its intermediate is sc_mid), ordered like sc_tab;
                                       // xgpu_pic_output_device_warp: the host maps of the current call
     size_t          roi_blk_cap;
+    // xgpu_pic_output_device_ladder: the records and the tap tables of all rungs in one device block (lad_blk; lad_host is the host's copy, whose tables were
+    // made for lad_key = source size, rung sizes, filter, both sitings - empty until the first call); its intermediate is sc_mid.  Ordered like sc_tab.
+    uint8_t        *lad_blk;
+    size_t          lad_blk_cap;
+    std::vector<int> lad_key;
+    std::vector<uint8_t> lad_host;
+    std::vector<uint8_t> lad_sent;    // the records lad_blk holds (empty: none): a call whose records equal them uploads nothing
+    std::vector<ScaleAxisTab> lad_tabs;      // where lad_host holds the four tables of every rung: luma rows, chroma rows, luma columns, chroma columns
+    int             lad_cap;           // what lad_host's horizontal tables ask of LDS per row and plane
     hipEvent_t      odev_ev[2];       // xgpu_pic_output_device on a caller's stream: picture ready on the context stream / the caller's kernel done (created at the first call)
     xgpu_frame_params fp;
     int             have_frame;
@@ -530,6 +540,33 @@ struct RoisOutArgs : ScaledOutArgs {
     float    padv[3];               // the pad value by output position, before the normalise (integer dtypes: the integer)
 };
 void launch_output_rois(const RoisOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s);
+// k_output_ladder.hip: n renditions ("rungs") of one picture as 4:2:0 video surfaces, each at its own size (xgpu_pic_output_device_ladder, INTEGRATION.md section
+// 8l).  One record per (rung, plane) and pass, in the context's block in front of the tap tables it points into: 3 n records of the vertical pass (plane 0, 1, 2
+// of every rung), then the horizontal pass' - per rung Y, Cb, Cr (YUV420P) or Y and the interleaved Cb Cr rows (NV12 / P016: `pair`).
+int  scale_build_axis(int n, int s, int h, int N, int S, int H, int filter, bool transposed, int group, std::vector<uint8_t> &blob, ScaleAxisTab &t, int *cap);
+struct __attribute__((aligned(16))) LadderDesc {
+    uint64_t dst;                   // horizontal: the address of the plane's first element in the rung's destination
+    uint64_t pitch;                 // horizontal: bytes between two rows of the plane
+    uint32_t mid[2];                // first sample of the plane's intermediate [rows][mp] (horizontal, pair: of Cb's and of Cr's)
+    int      mp;                    // its row pitch in samples, a multiple of 8
+    int      plane;                 // vertical: the source plane, 0 Y, 1 Cb, 2 Cr
+    int      sw;                    // vertical: columns of the source plane
+    int      rows, cols;            // destination rows (both passes) and columns (horizontal) of the plane
+    int      pair;                  // horizontal: 1 = Cb and Cr of a position side by side
+    uint32_t first, count, wt;      // byte offsets in the block of the pass' table: rows (vertical, w[o * stride + k]) or columns (horizontal, transposed)
+    int      stride;
+};
+static_assert(sizeof(LadderDesc) == 64, "LadderDesc must be 64 bytes");
+#define LADDER_GROUP 4              // destination positions of one lane of the horizontal pass; a workgroup row is 64 lanes
+// ScaledOutArgs' picture fields (y, u, v, sy, sc: the picture minus f->crop; dra, smax; mid: the base of all intermediates), then the call's
+struct LadderOutArgs : ScaledOutArgs {
+    const uint8_t *blk;             // 3 n vertical records, nh horizontal records, the tap tables
+    int      n, nh;
+    int      cap;                   // horizontal: the samples of one row of one plane a wave stages in LDS (the widest of all records; a multiple of 8)
+    int      cshift, cmaxv, cout8, clsh;      // the depth rule: conv1's shift B - D, 2^D - 1, D == 8; P016's left shift 16 - D
+};
+// max_sw / max_vrows: the widest source plane and the most destination rows of the vertical records; max_cols / max_rows: of the horizontal ones
+void launch_output_ladder(const LadderOutArgs &a, int dtype, int max_sw, int max_vrows, int max_cols, int max_rows, hipStream_t s);
 // k_output_rois_dev.hip: the descriptor block of k_output_rois.hip made on the device from boxes in device memory (xgpu_pic_output_device_rois_dev, INTEGRATION.md
 // section 8f).  The block: `capacity` RoiDesc, then one slot of tap tables per box at tab + i * slot - table t's first[], count[] and weights at off_first[t],
 // off_count[t], off_w[t] inside it -, every size taken from the bounds alone (rois_dev_layout, xgpu_api.hip).

@@ -1,5 +1,5 @@
 // xgpu_output.hip - the C ABI of include/xevd_hip.h, part 2: the outputs into device memory - the picture as it is, colour-managed, scaled, as a batch of regions of
-// interest (rectangles from the host or boxes in device memory), of affine maps or of coordinate grids, the coding side information, the residual, the comparison with a reference and the statistics
+// interest (rectangles from the host or boxes in device memory), of affine maps or of coordinate grids, as a ladder of scaled video surfaces, the coding side information, the residual, the comparison with a reference and the statistics
 // of one picture - and their argument checks without a device.
 // Every entry point is the same skeleton: check the format -> check_dst -> (check_dra; tables, made on the host) -> grow a context buffer -> out_fork -> fill an args struct ->
 // launch -> out_join.  Host-side code only; the kernels live in k_output*.hip, k_side_info.hip, k_residual.hip, k_compare.hip and k_stats.hip.
@@ -675,6 +675,210 @@ int xgpu_pic_output_device_rois(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, 
     a.blk = c->roi_blk; a.n = n;
     for (int k = 0; k < 3; k++) a.padv[k] = rp->fit == XGPU_FIT_LETTERBOX ? rp->pad[k] : 0.f;
     launch_output_rois(a, f->layout, f->dtype, b.max_w, b.max_ih, s);
+    return out_join(c, stream, s);      // the slot, the DRA tables, the block and the intermediate
+}
+
+// ------------------------------------------------------------------------------------------------ scaled video surfaces: a ladder of renditions
+// ChromaSampleLocType -> the chroma grid's siting in half luma samples, horizontally and vertically (xgpu_scale_taps' siting_half_luma)
+static void chroma_siting(int loc, int *dx, int *dy)
+{
+    static const int vsite[3] = { 1, 0, 2 };      // ChromaSampleLocType >> 1: centred, top, bottom
+    *dx = loc & 1; *dy = vsite[loc >> 1];
+}
+static bool is_surface420(int layout) { return layout == XGPU_OUT_YUV420P || is_semiplanar(layout); }
+// the bytes of one rung: xgpu_output_format_size of its layout at the rung's size with the rung's pitch, no crop
+static size_t ladder_rung_size(const xgpu_output_format *f, int rw, int rh, size_t row_pitch, int bd, const char **why)
+{
+    *why = "format is NULL";
+    if (!f) return 0;
+    *why = "ladder: layout must be XGPU_OUT_YUV420P, XGPU_OUT_NV12 or XGPU_OUT_P016, bgr 0";
+    if (!is_surface420(f->layout) || f->bgr) return 0;
+    xgpu_output_format g = *f;
+    g.row_pitch = row_pitch;
+    for (int i = 0; i < 4; i++) g.crop[i] = 0;
+    return format_size(&g, rw, rh, bd, why);
+}
+size_t xgpu_output_ladder_rung_size(const xgpu_output_format *f, int rung_width, int rung_height, size_t row_pitch, int bit_depth)
+{
+    const char *why;
+    return ladder_rung_size(f, rung_width, rung_height, row_pitch, bit_depth, &why);
+}
+// the samples of one rung's intermediate for a source ws wide: hd luma rows, hd / 2 rows of either chroma plane
+static size_t ladder_mid_samples(int ws, int hd) { return (size_t)hd * align8(ws) + 2 * (size_t)(hd >> 1) * align8(ws >> 1); }
+// The whole of a call's argument checks but for the pointers, without a device: *rc = the code, `why` (160 bytes), *mid_bytes (may be NULL) the call's intermediate
+static bool ladder_ok(const xgpu_output_format *f, const xgpu_ladder_params *lp, const xgpu_surface_rung *rungs, int n, int width, int height, int bd, int *rc, char *why,
+                      size_t *mid_bytes)
+{
+    const char *w0 = "";
+    *rc = XGPU_ERR_INVALID_ARGUMENT;
+    if (!f || !lp || !rungs) { snprintf(why, 160, "format, ladder parameters or rungs are NULL"); return false; }
+    if (width <= 0 || height <= 0 || ((width | height) & 1) || bd < 8 || bd > 12) { snprintf(why, 160, "picture size or bit depth out of range"); return false; }
+    if (!is_surface420(f->layout) || f->bgr) { snprintf(why, 160, "layout must be XGPU_OUT_YUV420P, XGPU_OUT_NV12 or XGPU_OUT_P016, bgr 0"); return false; }
+    if (!crop_ok(f->crop, width, height, &w0)) { snprintf(why, 160, "%s", w0); return false; }
+    if (f->chroma_loc < 0 || f->chroma_loc > 5 || lp->dst_chroma_loc < -1 || lp->dst_chroma_loc > 5) { snprintf(why, 160, "chroma_loc 0..5, dst_chroma_loc -1..5"); return false; }
+    if (lp->filter != XGPU_SCALE_BILINEAR && lp->filter != XGPU_SCALE_AREA) { snprintf(why, 160, "filter must be XGPU_SCALE_BILINEAR or XGPU_SCALE_AREA"); return false; }
+    if (n < 1 || n > XGPU_MAX_RUNGS) { snprintf(why, 160, "n %d outside 1..%d", n, XGPU_MAX_RUNGS); return false; }
+    const int ws = width - f->crop[0] - f->crop[1], hs = height - f->crop[2] - f->crop[3];
+    size_t mid = 0;
+    for (int i = 0; i < n; i++) {
+        const xgpu_surface_rung &r = rungs[i];
+        *rc = XGPU_ERR_INVALID_ARGUMENT;
+        if ((r.width | r.height) & 1) { snprintf(why, 160, "rung %d: %d x %d is not even", i, r.width, r.height); return false; }
+        *rc = XGPU_ERR_UNSUPPORTED;
+        if (r.width < 2 || r.width > 16384 || r.height < 2 || r.height > 16384 || !scale_ratio_ok(ws, r.width) || !scale_ratio_ok(hs, r.height)) {
+            snprintf(why, 160, "rung %d: %d x %d from %d x %d: 2..16384 per axis, between 1/64 and 8 times the source's", i, r.width, r.height, ws, hs);
+            return false;
+        }
+        *rc = XGPU_ERR_INVALID_ARGUMENT;
+        const size_t need = ladder_rung_size(f, r.width, r.height, r.row_pitch, bd, &w0);
+        if (need == 0) { snprintf(why, 160, "rung %d: %s", i, w0); return false; }
+        if (r.dst_size < need) { snprintf(why, 160, "rung %d: destination of %zu bytes, the rung needs %zu", i, r.dst_size, need); return false; }
+        *rc = XGPU_ERR_UNSUPPORTED;
+        mid += ladder_mid_samples(ws, r.height) * sizeof(uint16_t);
+        if (mid > ROIS_MID_LIMIT) { snprintf(why, 160, "rung %d: the intermediate of the call passes 512 MiB here", i); return false; }
+    }
+    if (mid_bytes) *mid_bytes = mid;
+    *rc = XGPU_OK;
+    return true;
+}
+int xgpu_output_ladder_check(const xgpu_output_format *f, const xgpu_ladder_params *lp, const xgpu_surface_rung *rungs, int n, int width, int height, int bit_depth)
+{
+    int rc; char why[160];
+    (void)ladder_ok(f, lp, rungs, n, width, height, bit_depth, &rc, why, NULL);
+    return rc;
+}
+// The tap tables of a call behind the room for its records: per rung the rows of luma and chroma (vertical pass) and their columns (horizontal pass, transposed).
+// The room is 6 records per rung whatever the layout (3 vertical, up to 3 horizontal), so the tables of a key lie where they lay.
+static const size_t LADDER_RECORDS = 6;
+static int build_ladder_tables(int ws, int hs, const xgpu_surface_rung *rungs, int n, int filter, int src_loc, int dst_loc, std::vector<uint8_t> &blob,
+                               std::vector<ScaleAxisTab> &tabs, int *cap)
+{
+    int dx, dy, Dx, Dy;
+    chroma_siting(src_loc, &dx, &dy);
+    chroma_siting(dst_loc, &Dx, &Dy);
+    blob.assign((size_t)n * LADDER_RECORDS * sizeof(LadderDesc), 0);
+    tabs.assign((size_t)4 * n, ScaleAxisTab());
+    *cap = 8;
+    for (int i = 0; i < n; i++) {
+        const int wd = rungs[i].width, hd = rungs[i].height;
+        int cy = 0, cc = 0;
+        TRY(scale_build_axis(hs, 1, 0, hd, 1, 0, filter, false, 0, blob, tabs[4 * i], NULL));
+        TRY(scale_build_axis(hs >> 1, 2, dy, hd >> 1, 2, Dy, filter, false, 0, blob, tabs[4 * i + 1], NULL));
+        TRY(scale_build_axis(ws, 1, 0, wd, 1, 0, filter, true, 64 * LADDER_GROUP, blob, tabs[4 * i + 2], &cy));
+        TRY(scale_build_axis(ws >> 1, 2, dx, wd >> 1, 2, Dx, filter, true, 64 * LADDER_GROUP, blob, tabs[4 * i + 3], &cc));
+        *cap = std::max(*cap, std::max(cy, cc));
+    }
+    return blob.size() > 0xFFFFFFFFu ? XGPU_ERR_UNSUPPORTED : XGPU_OK;
+}
+int xgpu_pic_output_device_ladder(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_ladder_params *lp, const xgpu_surface_rung *rungs,
+                                  int n, void *stream)
+{
+    static const char who[] = "pic_output_device_ladder";
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic));
+    int src_rc; char why[160];
+    size_t mid_need = 0;
+    const int bd = c->sp.bit_depth_luma;
+    if (!ladder_ok(f, lp, rungs, n, c->sp.width, c->sp.height, bd, &src_rc, why, &mid_need)) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return src_rc; }
+    const size_t es = (size_t)elem_size(f->dtype);
+    size_t need[XGPU_MAX_RUNGS];
+    for (int i = 0; i < n; i++) {
+        const char *w0;
+        need[i] = ladder_rung_size(f, rungs[i].width, rungs[i].height, rungs[i].row_pitch, bd, &w0);
+        if (!rungs[i].d_dst) { snprintf(c->err, sizeof(c->err), "%s: rung %d: the destination is NULL", who, i); return XGPU_ERR_INVALID_ARGUMENT; }
+        TRY(check_dst_fits(c, who, rungs[i].d_dst, rungs[i].dst_size, need[i], es));
+        for (int k = 0; k < i; k++) {
+            const uintptr_t a0 = (uintptr_t)rungs[k].d_dst, b0 = (uintptr_t)rungs[i].d_dst;
+            if (a0 < b0 + need[i] && b0 < a0 + need[k]) { snprintf(c->err, sizeof(c->err), "%s: rungs %d and %d overlap", who, k, i); return XGPU_ERR_INVALID_ARGUMENT; }
+        }
+    }
+    if (dra) TRY(check_dra(c, dra));      // upload_dra's refusals, before anything is queued
+    for (int i = 0; i < n; i++) TRY(check_device_dst(c, who, rungs[i].d_dst, need[i]));
+    const int *cr = f->crop;
+    const int ws = c->sp.width - cr[0] - cr[1], hs = c->sp.height - cr[2] - cr[3];
+    const int dst_loc = lp->dst_chroma_loc < 0 ? f->chroma_loc : lp->dst_chroma_loc;
+    // the tap tables: made here, before anything is queued; uploaded and committed below (the protocol of the scaled output's tables)
+    std::vector<int> key = { ws, hs, lp->filter, f->chroma_loc, dst_loc, n };
+    for (int i = 0; i < n; i++) { key.push_back(rungs[i].width); key.push_back(rungs[i].height); }
+    const bool cached = c->lad_blk && key == c->lad_key;
+    std::vector<uint8_t> blob;
+    std::vector<ScaleAxisTab> tabs;
+    int cap = c->lad_cap;
+    if (!cached) {
+        const int rc = build_ladder_tables(ws, hs, rungs, n, lp->filter, f->chroma_loc, dst_loc, blob, tabs, &cap);
+        if (rc < 0) { snprintf(c->err, sizeof(c->err), "%s: cannot make the tap tables of the %d rungs from %dx%d", who, n, ws, hs); return rc; }
+    }
+    TRY(grow(c, who, &c->sc_mid, &c->sc_mid_cap, mid_need, "intermediate"));
+    if (!cached && c->lad_blk_cap < blob.size()) {
+        c->lad_key.clear();      // no key names a block that is freed
+        TRY(grow(c, who, &c->lad_blk, &c->lad_blk_cap, blob.size(), "block of records and tap tables"));
+    }
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    if (!cached) {      // behind the fork: after every kernel that read the previous block
+        c->lad_key.clear();
+        c->lad_host.swap(blob);
+        c->lad_tabs.swap(tabs);
+        c->lad_cap = cap;
+    }
+    // the records of this call: where the planes of every rung lie in the intermediate and in the destinations
+    const bool pair = is_semiplanar(f->layout);
+    const int nh = (pair ? 2 : 3) * n;
+    LadderDesc *dv = (LadderDesc *)c->lad_host.data(), *dh = dv + 3 * n;
+    memset(dv, 0, (size_t)n * LADDER_RECORDS * sizeof(LadderDesc));
+    size_t mid = 0;
+    int max_w = 0, max_h = 0;
+    for (int i = 0; i < n; i++) {
+        const int wd = rungs[i].width, hd = rungs[i].height;
+        const ScaleAxisTab *t = &c->lad_tabs[4 * i];
+        const size_t pitch = rungs[i].row_pitch ? rungs[i].row_pitch : (size_t)wd * es;      // of a luma row, and of a row of Cb Cr pairs
+        uint32_t m[3];
+        for (int p = 0; p < 3; p++) {
+            LadderDesc &d = dv[3 * i + p];
+            m[p] = d.mid[0] = (uint32_t)mid;
+            d.mp = align8(p ? ws >> 1 : ws);
+            d.plane = p; d.sw = p ? ws >> 1 : ws; d.rows = p ? hd >> 1 : hd;
+            const ScaleAxisTab &v = t[p ? 1 : 0];
+            d.first = (uint32_t)v.first; d.count = (uint32_t)v.count; d.wt = (uint32_t)v.w; d.stride = v.stride;
+            mid += (size_t)d.rows * d.mp;
+        }
+        for (int p = 0; p < (pair ? 2 : 3); p++) {
+            LadderDesc &d = dh[(pair ? 2 : 3) * i + p];
+            d.mid[0] = m[p]; d.mid[1] = m[2];
+            d.mp = align8(p ? ws >> 1 : ws);
+            d.rows = p ? hd >> 1 : hd; d.cols = p ? wd >> 1 : wd;
+            d.pair = pair && p;
+            const ScaleAxisTab &h = t[p ? 3 : 2];
+            d.first = (uint32_t)h.first; d.count = (uint32_t)h.count; d.wt = (uint32_t)h.w; d.stride = h.stride;
+            // YUV420P: Y, then Cb, then Cr, tight; NV12 / P016: hd luma rows, then hd / 2 rows of pairs at the same pitch
+            size_t off = 0;
+            if (p) off = pair ? (size_t)hd * pitch : ((size_t)wd * hd + (size_t)(p - 1) * (wd >> 1) * (hd >> 1)) * es;
+            d.dst = (uint64_t)((uintptr_t)rungs[i].d_dst + off);
+            d.pitch = pair || !p ? pitch : (size_t)(wd >> 1) * es;
+        }
+        max_w = std::max(max_w, wd); max_h = std::max(max_h, hd);
+    }
+    // at most one upload: the whole block (new tables), the records alone, or - the same rungs into the same destinations again, a transcode's steady state -
+    // nothing.  (Pageable host memory: staged before the call returns, as the DRA tables are.)
+    const size_t rec_bytes = (size_t)n * LADDER_RECORDS * sizeof(LadderDesc);
+    if (!cached || c->lad_sent.size() != rec_bytes || memcmp(c->lad_sent.data(), c->lad_host.data(), rec_bytes)) {
+        c->lad_sent.clear();      // the block is about to change
+        HIPCHK(c, hipMemcpyAsync(c->lad_blk, c->lad_host.data(), cached ? rec_bytes : c->lad_host.size(), hipMemcpyHostToDevice, s));
+        c->lad_sent.assign(c->lad_host.begin(), c->lad_host.begin() + rec_bytes);
+    }
+    c->lad_key = key;
+    LadderOutArgs a;
+    memset(&a, 0, sizeof(a));
+    cropped_planes(dpic(c, pic), cr, &a.y, &a.u, &a.v);
+    a.sy = dpic(c, pic).s_l; a.sc = dpic(c, pic).s_c;
+    a.dra = dra ? c->d_dra : NULL;
+    a.smax = (1 << bd) - 1;
+    a.mid = c->sc_mid;
+    a.blk = c->lad_blk; a.n = n; a.nh = nh; a.cap = c->lad_cap;
+    const int obd = sample_depth(f, bd);
+    a.cshift = bd - obd; a.cout8 = obd == 8; a.cmaxv = (1 << obd) - 1;      // launch_output's conversion
+    a.clsh = f->layout == XGPU_OUT_P016 ? 16 - obd : 0;
+    launch_output_ladder(a, f->dtype, ws, max_h, max_w, max_h, s);
     return out_join(c, stream, s);      // the slot, the DRA tables, the block and the intermediate
 }
 

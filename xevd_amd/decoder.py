@@ -381,6 +381,79 @@ class XgpuDecoder:
                           C.c_void_p(res.data_ptr()) if results else None)
         return (out, res) if results else out
 
+    def pic_output_surfaces(self, pic, sizes, layout="nv12", dtype=None, out_bit_depth=0, filter="bilinear", chroma_loc=0, dst_chroma_loc=None, crop=(0, 0, 0, 0),
+                            dra=None, out=None):
+        """The picture as a ladder of scaled video surfaces - one tensor per (H, W) of `sizes` (1 .. abi.MAX_RUNGS, even), all in one layout "nv12", "p016" or
+        "yuv420p" - from one call on torch's current stream (xgpu_pic_output_device_ladder): what an encoder takes for the 2160p /
+        1080p / 720p renditions of a transcode.  Shapes and dtypes are those pic_output_tensor gives the layout at that size: "nv12" / "p016" [H * 3 // 2, W]
+        (torch.uint8 for 8-bit NV12, else a 16-bit integer type; out_bit_depth 0 = the coding depth), "yuv420p" 1-D (torch.uint8: 8-bit samples, else
+        out_bit_depth or the coding depth).  Luma is the scaled output's luma; the chroma planes are filtered from the half-resolution planes straight onto the
+        rung's half-resolution grid, whose siting is dst_chroma_loc (None: chroma_loc, the source's).  filter "bilinear" (antialiased) or "area"; crop (left,
+        right, top, bottom, even) is the source.  out: a list of tensors to fill, one per size (the row stride of an "nv12" / "p016" tensor becomes the rung's
+        row_pitch; they must not overlap); it is also what is returned."""
+        import torch
+        if layout not in ("nv12", "p016", "yuv420p"):
+            raise ValueError(f"layout must be 'nv12', 'p016' or 'yuv420p', not {layout!r}")
+        if filter not in ("bilinear", "area"):
+            raise ValueError(f"filter must be 'bilinear' or 'area', not {filter!r}")
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        if not 1 <= len(sizes) <= abi.MAX_RUNGS:
+            raise ValueError(f"sizes: 1..{abi.MAX_RUNGS} renditions, not {len(sizes)}")
+        if any(h < 2 or w < 2 or (h | w) & 1 for h, w in sizes):
+            raise ValueError(f"sizes: every (H, W) must be even and at least 2, got {sizes}")
+        if out is not None and len(out) != len(sizes):
+            raise ValueError(f"out: {len(sizes)} tensors, one per size, not {len(out)}")
+        if dst_chroma_loc is not None and int(dst_chroma_loc) not in range(6):
+            raise ValueError(f"dst_chroma_loc must be None or 0..5, not {dst_chroma_loc!r}")
+        if dtype is None:
+            dtype = torch.int16 if layout == "p016" else torch.uint8      # P016 has 16-bit words only
+        codes = _codes("uint8", "int16", "uint16")
+        if dtype not in codes:
+            raise ValueError(f"{layout}: dtype must be torch.uint8 or a 16-bit integer type, not {dtype}")
+        obd = int(out_bit_depth)
+        if codes[dtype] == abi.OUT_U8:
+            if layout == "p016":
+                raise ValueError("p016: dtype must be a 16-bit integer type")
+            if obd not in (0, 8):
+                raise ValueError(f"{layout}: torch.uint8 holds 8-bit samples; out_bit_depth above 8 needs a 16-bit integer dtype")
+            obd = 8
+        lay = {"nv12": abi.OUT_NV12, "p016": abi.OUT_P016, "yuv420p": abi.OUT_YUV420P}[layout]
+        fmt = abi.make_output_format(lay, codes[dtype], out_bit_depth=obd, chroma_loc=chroma_loc, crop=crop)
+        lp = abi.make_ladder_params(abi.SCALE_BILINEAR if filter == "bilinear" else abi.SCALE_AREA, dst_chroma_loc)
+        es = dtype.itemsize
+
+        def refuse(rungs):
+            rc = self.lib.xgpu_output_ladder_check(C.byref(fmt), C.byref(lp), rungs, len(sizes), self.width, self.height, self.bit_depth)
+            if rc != 0:
+                raise ValueError(f"invalid surface ladder ({rc}: layout {layout}, sizes {sizes}, out_bit_depth {out_bit_depth}, chroma_loc {chroma_loc}, "
+                                 f"dst_chroma_loc {dst_chroma_loc}, crop {crop})")
+        tight = [self.lib.xgpu_output_ladder_rung_size(C.byref(fmt), w, h, 0, self.bit_depth) for h, w in sizes]
+        refuse(abi.make_rungs([(w, h, 0, None, n) for (h, w), n in zip(sizes, tight)]))      # before a tensor is made, and again with the pitches
+        dev = torch.device("cuda", self.sp.device)
+        outs, spec = [], []
+        for i, (h, w) in enumerate(sizes):
+            t = _out_tensor(None if out is None else out[i], (w * h * 3 // 2,) if layout == "yuv420p" else (h * 3 // 2, w), dtype, dev)
+            st, pitch = t.stride(), 0
+            if layout == "yuv420p":
+                if st != (1,):
+                    raise ValueError("out: must be contiguous")
+            elif st[1] != 1 or st[0] < w:
+                raise ValueError(f"out: strides {st} are not rows of W elements")
+            else:
+                pitch = st[0] * es
+            nbytes = (sum((n - 1) * s for n, s in zip(t.shape, st)) + 1) * es      # the bytes the tensor spans from data_ptr()
+            outs.append(t)
+            spec.append((w, h, pitch, t.data_ptr(), nbytes))
+        rungs = abi.make_rungs(spec)
+        refuse(rungs)
+        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
+        cur, run = self._run_stream(dev)
+        self._chk(self.lib.xgpu_pic_output_device_ladder(self.ctx, pic, dl, C.byref(fmt), C.byref(lp), rungs, len(sizes), C.c_void_p(run.cuda_stream)),
+                  "xgpu_pic_output_device_ladder")
+        if run is not cur:
+            cur.wait_stream(run)
+        return outs
+
     def pic_output_warped(self, pic, maps, size, layout="rgb", channels_last=False, dtype=None, matrix=1, full_range=False, chroma_loc=0, crop=(0, 0, 0, 0),
                           dra=None, bgr=False, samples=1, border="clamp", pad=0.0, mean=None, std=None, out=None, status=False):
         """N affine maps of the picture, each giving one H x W image (size=(H, W)), converted and normalised like pic_output_tensor(size=...), as one batch

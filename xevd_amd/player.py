@@ -116,7 +116,7 @@ class StreamDecoder:
         return cm
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
-                 residual=None, compare=None, stats=None, warp=None, remap=None, remap_step=0):
+                 residual=None, compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -149,7 +149,13 @@ class StreamDecoder:
         stats=dict(...) (keyword arguments of XgpuDecoder.pic_stats, {} for the defaults) or a callable(params) -> such a dict or None: the statistics of every
         picture - census, histograms, percentiles - under params["stats"] (pic_stats' dict; with sync=False its tuple of device tensors), taken right behind the
         picture's kernels.  light=True or light=dict(...) in it adds the light level with the matrix, range, chroma siting and transfer characteristic of the
-        stream's VUI (light_options; the dict overrides them).  The crop defaults to the SPS crop when apply_crop is set"""
+        stream's VUI (light_options; the dict overrides them).  The crop defaults to the SPS crop when apply_crop is set
+        surfaces=[(H, W), ...], surface_layout="nv12" | "p016" | "yuv420p": every picture as a ladder of scaled video surfaces, one tensor per size, under
+        params["surfaces"] (XgpuDecoder.pic_output_surfaces, next to whatever else was asked: the yielded tuple keeps its shape) - the renditions of a
+        transcode, where an encoder takes them.  surface_options=dict(...) passes its other arguments (dtype, out_bit_depth, filter, dst_chroma_loc);
+        chroma_loc and the DRA tables are the stream's, the crop defaults to the SPS crop when apply_crop is set"""
+        if surfaces is None and surface_options is not None:
+            raise ValueError("surface_options: needs surfaces=[(H, W), ...]")
         if to is not None and tensor is None:
             raise ValueError("to: needs tensor=dict(...)")
         if (size is not None or mean is not None or std is not None) and tensor is None:
@@ -218,6 +224,12 @@ class StreamDecoder:
                     p["_luma"][1] = dec.pic_download_padded_luma(cur)
                     p["_luma"][0].set()
                 dec.batch_destroy(hb)          # back to the pool; queued kernels keep reading it (same HIP stream)
+            if surfaces is not None:
+                opts = self.tensor_options(p, {})
+                kw = {"chroma_loc": opts["chroma_loc"], "dra": opts["dra"], "crop": p["crop"] if self.apply_crop else (0, 0, 0, 0)}
+                kw.update(surface_options or {})
+                with self._lock:
+                    p["surfaces"] = dec.pic_output_surfaces(cur, surfaces, layout=surface_layout, **kw)
             planes = None
             if tensor is not None:
                 kw = self.tensor_options(p, tensor)
@@ -282,17 +294,21 @@ class StreamDecoder:
                 self._dec = None
 
     def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
-                     compare=None, stats=None, warp=None, remap=None, remap_step=0):
+                     compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
         params["residual"] as numpy - for kind "yuv420" the pair (flat array, (Y, Cb, Cr) views of it); compare= (as pictures takes it, the callable and the
-        sequence in DECODING order): params["compare"], its map as a numpy array; stats= (as pictures takes it): params["stats"], its histograms as numpy arrays"""
+        sequence in DECODING order): params["compare"], its map as a numpy array; stats= (as pictures takes it): params["stats"], its histograms as numpy arrays;
+        surfaces= / surface_layout= / surface_options= (as pictures takes them): params["surfaces"], a list of numpy arrays"""
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
-                                       residual=residual, compare=compare, stats=stats, warp=warp, remap=remap, remap_step=remap_step):
+                                       residual=residual, compare=compare, stats=stats, warp=warp, remap=remap, remap_step=remap_step, surfaces=surfaces,
+                                       surface_layout=surface_layout, surface_options=surface_options):
             if p["is_idr"]:
                 epoch += 1
+            if surfaces is not None:      # (synchronises torch's current stream: the tensors are complete)
+                p["surfaces"] = [t.cpu().numpy() for t in p["surfaces"]]
             if tensor is not None:
                 # (synchronises torch's current stream: the slot's tensor is complete); device boxes with results=True: the pair, both as arrays
                 planes = tuple(t.cpu().numpy() for t in planes) if isinstance(planes, tuple) else planes.cpu().numpy()
