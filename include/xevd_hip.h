@@ -402,6 +402,23 @@ size_t xgpu_output_rois_size(const xgpu_output_format *f, const xgpu_scale_param
    output caches are left alone. */
 int    xgpu_pic_output_device_rois(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
                                    const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, void *d_dst, size_t dst_size, void *stream);
+/* ---- colour-managed scaled output (k_output_scaled_cm.hip): xgpu_pic_output_device_scaled and xgpu_pic_output_device_rois with the colour transform `cm` of
+   xgpu_pic_output_device_cm between the filter and the store - model-sized, normalised sRGB (or any listed destination) from a PQ / HLG / BT.2020 stream without
+   the full-size tensor.  Per destination pixel: (Y, Cb, Cr) at the coding depth as the scaled output filters them (the encoded Y'CbCr samples are filtered, not
+   linear light); the integer R'G'B' code at the coding depth (the U16 form's matrix, whatever the dtype); the transform's steps 1 to 4; integers
+   rint(q * (2^D - 1)), floats q; then bgr, the normalise and the F16 / BF16 rounding as the scaled output does them.  A letterbox pad value is written as
+   xgpu_pic_output_device_rois writes it: a value of the destination space, normalised like a pixel, never transformed.  The exact contract: INTEGRATION.md
+   section 8m; tests/scaled_cm_ref.py restates it on top of tests/scale_ref.py, tests/colour_cm_ref.py and tests/roi_ref.py.
+   cm = NULL: the plain call itself.  Destination sizes: xgpu_output_scaled_size / xgpu_output_rois_size.  Refusals, all before anything is queued, in this order:
+   the plain call's, with its codes; a layout that is not RGB: XGPU_ERR_INVALID_ARGUMENT; whatever xgpu_colour_tables returns for `cm`.  The tables are the
+   context's cache of xgpu_pic_output_device_cm: a full-size call and a scaled one with the same transform and depth upload once.
+   xgpu_output_scaled_cm_check (host only, no context): 0, or the code xgpu_pic_output_device_scaled_cm refuses with. */
+int    xgpu_output_scaled_cm_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_colour_transform *cm, int width, int height, int bit_depth);
+int    xgpu_pic_output_device_scaled_cm(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                                        const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream);
+int    xgpu_pic_output_device_rois_cm(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                                      const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size,
+                                      void *stream);
 /* ---- regions of interest from device memory (k_output_rois_dev.hip): xgpu_pic_output_device_rois for boxes that a detector left on the GPU.  d_boxes points
    to `capacity` boxes in device memory (1 .. XGPU_MAX_ROIS), d_count (may be NULL: all of them) to a device int32 - the live boxes are the first
    min(max(*d_count, 0), capacity).  The host reads neither; the call does not synchronise and nothing comes back to the host.  Descriptors and tap tables are

@@ -11,6 +11,12 @@ interpolate(mode="bilinear", antialias=True) and the normalise in torch; and the
 picture read once, the destination written once).  The call is timed whole; the split between its two kernels is what
 rocprofv3 --kernel-trace --stats shows for `--legs scaled`.
 
+The scaled_cm leg (xgpu_pic_output_device_scaled_cm / _rois_cm: the vertical passes + k_scale_horizontal_cm / k_rois_horizontal_cm) takes the picture as PQ / BT.2020
+to sRGB / BT.709 through the tone curve at three shapes - 224x224 f32 normalised, 1920x1080 u8, 64 tiles at 224x224 f32 normalised - and alternates each, from an
+idle device, with (i) the plain scaled / ROI call at the same shape: the price of the transform, and (ii) the only route without it: the full-size colour= f32
+tensor, interpolate(antialias=True) and the normalise (or the u8 rounding) in torch, with the largest difference between the two (on random samples through PQ
+that is a record of filtering encoded samples against display light, not an error bound).  device_us is the kernels alone, queued behind a wait.
+
 The rois leg (xgpu_pic_output_device_rois: k_rois_vertical + k_rois_horizontal) makes 64 images of 224x224 f32 planar, normalised, from the same picture by one
 call - (a) the 8 x 8 grid of tiles, stretched; (b) 64 seeded boxes with sides of 64..512 samples, letterboxed - and times next to it, alternating with it in the
 same run on the same stream, the route without it: 64 calls of xgpu_pic_output_device_scaled with the crop set to the rectangle (for (b) at the inner size, into
@@ -58,7 +64,7 @@ picture once; four one-rung calls are alternated on their own (each makes its ta
 of the kernels alone (median of --iters calls queued behind a wait).  The largest difference between each rung's planes and the torch route in float64 is
 recorded in code values; it is a record, not a test.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|rois|rois_dev|ladder|warp|remap|residual|compare|stats] [--out out/output_device.json]
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|rois|rois_dev|ladder|warp|remap|residual|compare|stats] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -141,6 +147,57 @@ def scaled_leg(torch, dec, pic, s, a, res, copy_gbps):
             else:
                 print(f"scaled {w}x{h} -> {wd}x{hd} f32 {filt:8s} {us:9.1f} us   copy-rate time {floor_us:7.1f} us ({floor_us / us:.2f})")
             res["scaled"][f"{wd}x{hd}_f32_planar_{filt}"] = r
+    del full
+
+
+def scaled_cm_leg(torch, dec, pic, s, a, res):
+    """the colour-managed scaled call (PQ / BT.2020 -> sRGB through the tone curve) at three shapes, each alternated with (i) the plain scaled / ROI call at the
+    same shape - the price of the transform - and (ii) the only route without it: the full-size colour= f32 tensor + F.interpolate(antialias=True) + the normalise
+    (or the u8 rounding) in torch, with the max |diff| between the two"""
+    import torch.nn.functional as F
+    from xevd_amd import abi
+    w, h = a.width, a.height
+    colour = dict(src_primaries=9, src_transfer=16, dst_primaries=1, dst_transfer=13, tone_map=True)
+    mean = torch.tensor(MEAN, device="cuda:0").view(3, 1, 1)
+    inv = (1.0 / torch.tensor(STD, device="cuda:0")).view(3, 1, 1)
+    full = dec.pic_output_tensor(pic, dtype=torch.float32, matrix=9, colour=colour)
+    tiles = abi.tile_rois(w, h, (w // 8) & ~1, (h // 8) & ~1)[:64]
+    norm = dict(mean=MEAN, std=STD)
+    shapes = (("224x224_f32_normalised", (224, 224), None, dict(dtype=torch.float32, **norm)), ("1920x1080_u8", (1080, 1920), None, dict(dtype=torch.uint8)),
+              ("64_rois_224x224_f32_normalised", (224, 224), tiles, dict(dtype=torch.float32, **norm)))
+    res["scaled_cm"] = {}
+    for name, size, rois, kw in shapes:
+        is_u8 = kw["dtype"] == torch.uint8
+        roi_kw = {} if rois is None else dict(rois=rois)
+        out = dec.pic_output_scaled_cm(pic, size, colour, matrix=9, **roi_kw, **kw)
+        plain = dec.pic_output_tensor(pic, size=size, matrix=9, **roi_kw, **kw)
+
+        def cm_call():
+            dec.pic_output_scaled_cm(pic, size, colour, matrix=9, out=out, **roi_kw, **kw)
+
+        def plain_call():
+            dec.pic_output_tensor(pic, size=size, matrix=9, out=plain, **roi_kw, **kw)
+
+        def resize(x):
+            y = F.interpolate(x[None], size=size, mode="bilinear", antialias=True, align_corners=False)[0]
+            return (y * 255.0).round().clamp(0, 255).to(torch.uint8) if is_u8 else (y - mean) * inv
+
+        def torch_route():
+            dec.pic_output_tensor(pic, out=full, dtype=torch.float32, matrix=9, colour=colour)
+            if rois is None:
+                return resize(full)
+            return torch.stack([resize(full[:, y:y + rh, x:x + rw]) for x, y, rw, rh in rois])
+
+        r = alternated(torch, s, {"cm": cm_call, "plain": plain_call}, a.iters)
+        rt = alternated(torch, s, {"cm": cm_call, "torch_route": torch_route}, max(a.iters // 10, 5), warm=2)
+        r["cm"]["device_us"], r["plain"]["device_us"] = round(timed(torch, s, cm_call, a.iters), 2), round(timed(torch, s, plain_call, a.iters), 2)      # the kernels alone
+        r["torch_route"], r["cm_beside_torch_route"] = rt["torch_route"], rt["cm"]
+        diff = float((torch_route().float() - out.float()).abs().max())
+        r.update({"vs_plain": round(r["cm"]["us"] / r["plain"]["us"], 2), "speedup_vs_torch_route": round(rt["torch_route"]["us"] / rt["cm"]["us"], 2),
+                  "max_abs_diff_vs_torch_route": diff, "diff_unit": "code values of the u8 output" if is_u8 else "normalised float"})
+        print(f"scaled_cm {name:32s} {r['cm']['us']:9.1f} us (kernels {r['cm']['device_us']:7.1f})   plain call {r['plain']['us']:9.1f} us (kernels {r['plain']['device_us']:7.1f}; {r['vs_plain']:.2f}x)   torch route {rt['torch_route']['us']:10.1f} us "
+              f"({r['speedup_vs_torch_route']:.1f}x)   max |diff| {diff:.3g}")
+        res["scaled_cm"][name] = r
     del full
 
 
@@ -711,8 +768,8 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats"), default="all",
-                    help="full: the full-size forms and the side information; scaled: the scaled leg alone; rois: the batched regions of interest alone; "
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats"), default="all",
+                    help="full: the full-size forms and the side information; scaled: the scaled leg alone; scaled_cm: the colour-managed scaled output alone; rois: the batched regions of interest alone; "
                          "rois_dev: the regions of interest from boxes in device memory alone; ladder: the ladder of scaled P010 surfaces alone; warp: the warped regions of interest alone; remap: the remapped output alone; residual: the residual "
                          "export alone; compare: the picture comparison alone; stats: the picture statistics alone")
     a = ap.parse_args()
@@ -750,6 +807,8 @@ def main():
         torch.cuda.set_stream(s)
         if a.legs in ("all", "scaled"):
             scaled_leg(torch, dec, pic, s, a, res, copy_gbps)
+        if a.legs in ("all", "scaled_cm"):
+            scaled_cm_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "rois"):
             rois_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "rois_dev"):

@@ -140,7 +140,8 @@ def main():
                     "one text line 'POC p  Y n N min A max B mean M pctl P1 P99.99  U ...  V ...' of the uncropped picture, and 'light max CODE L pctl L1 L2 mean LM' "
                     "(linear light, 0 .. 1) when the stream's VUI gives a transfer characteristic")
     ap.add_argument("--size", default=None, metavar="WxH", help="write interleaved 8-bit RGB frames resized to W x H on the device instead (antialiased bilinear, "
-                    "the matrix / range / chroma siting of the stream's VUI: INTEGRATION.md 8d); with --to: not supported")
+                    "the matrix / range / chroma siting of the stream's VUI: INTEGRATION.md 8d); with --to: resized and taken to that colour space in the same call "
+                    "(INTEGRATION.md 8m), with --tiles too")
     ap.add_argument("--tiles", default=None, metavar="WxH", help="with --size: every picture as its grid of W x H tiles (the last column / row moved back inside the "
                     "picture), each resized to --size by one call per picture (INTEGRATION.md 8e); the frames written are the tiles, row by row")
     ap.add_argument("--remap", default=None, metavar="GRID.npy", help="with --size: every picture pulled through this coordinate grid on the device instead of resized "
@@ -189,8 +190,8 @@ def main():
     # crop-free output like the reference application; bit-depth conversion and plane packing run on the device (xgpu_pic_output)
     if args.size is not None:
         import torch
-        if args.to is not None:
-            ap.error("--size: the scaled output takes no colour transform (--to)")
+        if args.to is not None and args.remap is not None:
+            ap.error("--remap: the remapped output takes no colour transform (--to)")
         try:
             wd, hd = (int(v) for v in args.size.lower().split("x"))
         except ValueError:
@@ -210,7 +211,7 @@ def main():
             if remap.dtype not in (np.int32, np.float32):
                 ap.error(f"--remap: an int32 or float32 array, not {remap.dtype}")
             remap = torch.from_numpy(remap).to(f"cuda:{args.device}")      # uploaded once, used for every picture
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), side=side, rois=rois, residual=resid, compare=cmp, stats=stats,
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), to=args.to, side=side, rois=rois, residual=resid, compare=cmp, stats=stats,
                                                                     remap=remap, remap_step=args.remap_step, **lad)
     elif args.to is not None:
         import torch

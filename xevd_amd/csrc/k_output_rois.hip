@@ -93,9 +93,14 @@ static void launch_horizontal(const RoisOutArgs &a, int dtype, dim3 grid, dim3 b
 }
 
 // max_w: the widest rectangle; max_ih: the tallest inner part
-void launch_output_rois(const RoisOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s)
+void launch_rois_vertical(const RoisOutArgs &a, int max_w, int max_ih, hipStream_t s)
 {
     hipLaunchKernelGGL(k_rois_vertical, dim3((unsigned)(((max_w + 7) / 8 + 63) / 64), (unsigned)((max_ih + 3) / 4), (unsigned)(3 * a.n)), dim3(64, 4), 0, s, a);
+}
+
+void launch_output_rois(const RoisOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s)
+{
+    launch_rois_vertical(a, max_w, max_ih, s);
     // as many rows per workgroup as 48 KB of LDS hold, 4 at most - k_output_scaled.hip's rule, on the widest span of the batch
     const size_t per_row = (size_t)(a.capy + 2 * a.capc) * sizeof(uint16_t);
     int rows = 4;

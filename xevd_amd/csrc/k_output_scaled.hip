@@ -77,9 +77,14 @@ static void launch_horizontal(const ScaledOutArgs &a, int dtype, dim3 grid, dim3
     }
 }
 
-void launch_output_scaled(const ScaledOutArgs &a, int layout, int dtype, hipStream_t s)
+void launch_scale_vertical(const ScaledOutArgs &a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_scale_vertical, dim3((unsigned)(((a.w + 7) / 8 + 63) / 64), (unsigned)((a.dh + 3) / 4), 3), dim3(64, 4), 0, s, a);
+}
+
+void launch_output_scaled(const ScaledOutArgs &a, int layout, int dtype, hipStream_t s)
+{
+    launch_scale_vertical(a, s);
     // as many rows per workgroup as 48 KB of LDS hold, 4 at most (a row's spans are at most ~17 KB: 64 columns at a ratio of 64)
     const size_t per_row = (size_t)(a.capy + 2 * a.capc) * sizeof(uint16_t);
     int rows = 4;

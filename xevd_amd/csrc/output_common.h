@@ -315,17 +315,20 @@ template <int DT> __device__ __forceinline__ uint32_t scaled_float_elem(const Sc
 }
 // one filtered pixel (Y, Cb, Cr at the coding depth) -> the bits of its three elements in output order: CONV (for the float dtypes its F32 instance, so that the
 // normalise sees the clipped float32), bgr, the normalise, the dtype's rounding
-template <int DT, template <int> class CONV> __device__ __forceinline__ void scaled_pixel(const ScaledOutArgs &a, int y, int cb, int cr, uint32_t (&e)[3])
+// what follows the conversion (k_output_scaled_cm.hip converts with the colour transform and ends here too): e = R, G, B as the integer dtype's elements or as the
+// bits of the clipped float32
+template <int DT> __device__ __forceinline__ void scaled_finish(const ScaledOutArgs &a, uint32_t (&e)[3])
 {
+    if (a.bgr) { const uint32_t t = e[0]; e[0] = e[2]; e[2] = t; }
     if (OutT<DT>::is_float) {
-        CONV<XGPU_OUT_F32>::apply(a, y, cb, cr, e[0], e[1], e[2]);      // the clipped float32
-        if (a.bgr) { const uint32_t t = e[0]; e[0] = e[2]; e[2] = t; }
         #pragma unroll
         for (int k = 0; k < 3; k++) e[k] = scaled_float_elem<DT>(a, k, __uint_as_float(e[k]));
-    } else {
-        CONV<DT>::apply(a, y, cb, cr, e[0], e[1], e[2]);
-        if (a.bgr) { const uint32_t t = e[0]; e[0] = e[2]; e[2] = t; }
     }
+}
+template <int DT, template <int> class CONV> __device__ __forceinline__ void scaled_pixel(const ScaledOutArgs &a, int y, int cb, int cr, uint32_t (&e)[3])
+{
+    CONV<OutT<DT>::is_float ? XGPU_OUT_F32 : DT>::apply(a, y, cb, cr, e[0], e[1], e[2]);      // floats: the clipped float32
+    scaled_finish<DT>(a, e);
 }
 // the three elements of pixel ox of the destination row at `row`: three planes `plane` bytes apart, or side by side
 template <bool PLANAR, int SZ> __device__ __forceinline__ void store_pixel(uint8_t *row, size_t plane, int ox, const uint32_t (&e)[3])

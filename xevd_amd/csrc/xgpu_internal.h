@@ -494,12 +494,16 @@ struct RgbOutArgs {
 void launch_output_rgb(const RgbOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 void launch_output_yuv444(const RgbOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 // k_output_cm.hip: k_output_rgb's arguments (coef / shift / maxv: those of the U16 form, whatever the dtype) and the colour transform's
-struct CmOutArgs : RgbOutArgs {
+// The transform's fields are one member, so that the scaled outputs' argument types (below) carry the same thing behind their own fields.
+struct CmParams {
     const float *lin, *tone, *enc;  // device tables: linear light per code [n_lin]; g(Y) or NULL (scale instead); the destination curve or NULL (linear output)
     int      n_lin, use_matrix;
     float    m[9], luma[3], scale;  // source -> destination primaries, luminance weights of the source primaries, linear_scale
     float    outmax;                // integer dtypes: 2^D - 1
 };
+struct CmOutArgs : RgbOutArgs { CmParams cm; };
+// the floats of a transform's tables in LDS (cm_fill_lds's layout, cm_transform.h)
+static inline size_t cm_table_floats(int n_lin, bool tone, bool enc) { return (size_t)n_lin + (tone ? XGPU_CM_CURVE_SIZE : 0) + (enc ? XGPU_CM_CURVE_SIZE : 0); }
 void launch_output_cm(const CmOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 // k_output_scaled.hip: the cropped picture resized to dw x dh and converted (xgpu_pic_output_device_scaled).  RgbOutArgs' source, destination
 // and conversion fields (w, h, cw, ch: the SOURCE size; pitch / plane: of the dw x dh destination; aligned, hc, ve, vo are not read), then the taps and the two passes'.
@@ -516,6 +520,7 @@ struct ScaledOutArgs : RgbOutArgs {
     float    mean[3], inv_std[3];   // by output position (after bgr)
 };
 void launch_output_scaled(const ScaledOutArgs &a, int layout, int dtype, hipStream_t s);
+void launch_scale_vertical(const ScaledOutArgs &a, hipStream_t s);      // its vertical pass alone (k_output_scaled_cm.hip follows it with a horizontal pass of its own)
 // x_off: pass 2's groups of 64 destination columns start x_off columns before column 0 (a letterboxed image, whose workgroups are laid over the whole image)
 int  scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb, int x_off = 0);      // xgpu_scale.hip
 // k_output_rois.hip: several rectangles of one picture, each resized to dw x dh - stretched, or letterboxed into it - as a batch of images
@@ -540,6 +545,14 @@ struct RoisOutArgs : ScaledOutArgs {
     float    padv[3];               // the pad value by output position, before the normalise (integer dtypes: the integer)
 };
 void launch_output_rois(const RoisOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s);
+void launch_rois_vertical(const RoisOutArgs &a, int max_w, int max_ih, hipStream_t s);      // its vertical pass alone
+// k_output_scaled_cm.hip: the two scaled outputs with the colour transform between the filter and the store (xgpu_pic_output_device_scaled_cm / _rois_cm,
+// INTEGRATION.md section 8m).  The vertical passes are k_scale_vertical / k_rois_vertical; the horizontal pass keeps the transform's tables in global memory (L1 / L2) and
+// only its spans in dynamic LDS.  coef / shift / maxv: those of the U16 form, whatever the dtype (CmOutArgs' rule).
+struct ScaledCmOutArgs : ScaledOutArgs { CmParams cm; };
+struct RoisCmOutArgs : RoisOutArgs { CmParams cm; };
+void launch_output_scaled_cm(const ScaledCmOutArgs &a, int layout, int dtype, hipStream_t s);
+void launch_output_rois_cm(const RoisCmOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s);
 // k_output_ladder.hip: n renditions ("rungs") of one picture as 4:2:0 video surfaces, each at its own size (xgpu_pic_output_device_ladder, INTEGRATION.md section
 // 8l).  One record per (rung, plane) and pass, in the context's block in front of the tap tables it points into: 3 n records of the vertical pass (plane 0, 1, 2
 // of every rung), then the horizontal pass' - per rung Y, Cb, Cr (YUV420P) or Y and the interleaved Cb Cr rows (NV12 / P016: `pair`).

@@ -268,6 +268,48 @@ static int upload_cm(xgpu_ctx *c, const xgpu_colour_tables_t *t, hipStream_t s)
     if (t->use_encode) HIPCHK(c, hipMemcpyAsync(c->d_cm + CM_ENC_OFF, t->encode, sizeof(t->encode), hipMemcpyHostToDevice, s));
     return XGPU_OK;
 }
+// What every call with a transform does with these tables, in three steps (xgpu_pic_output_device_cm and the scaled calls of section 8m share the cache).
+// cm_prepare, before anything is queued: the layout must be RGB; a transform the cache does not hold is made into cm_new, or refused with xgpu_colour_tables' code.
+static int cm_prepare(xgpu_ctx *c, const char *who, const xgpu_output_format *f, const xgpu_colour_transform *cm, std::unique_ptr<xgpu_colour_tables_t> &cm_new)
+{
+    const int bd = c->sp.bit_depth_luma;
+    if (!is_rgb(f->layout)) { snprintf(c->err, sizeof(c->err), "%s: a colour transform needs one of the RGB layouts", who); return XGPU_ERR_INVALID_ARGUMENT; }
+    if (cm_cached(c, cm, bd)) return XGPU_OK;
+    cm_new.reset(new (std::nothrow) xgpu_colour_tables_t);
+    const int rc = cm_new ? xgpu_colour_tables(f, cm, bd, cm_new.get()) : XGPU_ERR_OUT_OF_MEMORY;
+    if (rc < 0) {
+        snprintf(c->err, sizeof(c->err), "%s: transform %d/%d -> %d/%d (primaries / transfer) is not supported or its parameters are invalid", who,
+                 cm->src_primaries, cm->src_transfer, cm->dst_primaries, cm->dst_transfer);
+        return rc;
+    }
+    if (!c->d_cm && hipMalloc((void **)&c->d_cm, sizeof(float) * CM_FLOATS) != hipSuccess) { snprintf(c->err, sizeof(c->err), "%s: cannot allocate the tables", who); return XGPU_ERR_OUT_OF_MEMORY; }
+    return XGPU_OK;
+}
+// cm_commit, behind the fork - after every kernel that read the previous tables: a new set is uploaded on `s` and named by the key
+static int cm_commit(xgpu_ctx *c, const xgpu_colour_transform *cm, std::unique_ptr<xgpu_colour_tables_t> &cm_new, hipStream_t s)
+{
+    if (!cm_new) return XGPU_OK;
+    delete c->cm_tab;
+    c->cm_tab = NULL;      // d_cm is about to change: no key names it until all of the new set is queued
+    TRY(upload_cm(c, cm_new.get(), s));
+    c->cm_tab = cm_new.release(); c->cm_key = *cm; c->cm_bd = c->sp.bit_depth_luma;
+    return XGPU_OK;
+}
+// fill_cm: the matrix of the U16 form in `a` (the code at the coding depth feeds the transform, whatever the output dtype) and the transform of tables `t` in `p`
+static void fill_cm(xgpu_ctx *c, const xgpu_output_format *f, const xgpu_colour_tables_t &t, RgbOutArgs &a, CmParams &p)
+{
+    const int bd = c->sp.bit_depth_luma;
+    xgpu_output_format f16 = *f;
+    f16.dtype = XGPU_OUT_U16;
+    f16.row_pitch = 0;             // (the caller's pitch counts the caller's elements, not 16-bit ones)
+    (void)xgpu_output_coeffs(&f16, bd, a.coef, &a.shift, a.fcoef);
+    a.maxv = (1 << bd) - 1;
+    p.lin = c->d_cm; p.tone = t.use_tone ? c->d_cm + CM_TONE_OFF : NULL; p.enc = t.use_encode ? c->d_cm + CM_ENC_OFF : NULL;
+    p.n_lin = t.n_lin; p.use_matrix = t.use_matrix;
+    memcpy(p.m, t.matrix, sizeof(p.m)); memcpy(p.luma, t.luma, sizeof(p.luma));
+    p.scale = t.scale;
+    p.outmax = f->dtype == XGPU_OUT_U8 ? 255.f : (float)((1 << bd) - 1);
+}
 // the conversion of an RGB or YUV444 layout at the context's coding depth: range terms, matrix (RGB) or scales (YUV444: no matrix, coef / maxv stay zero), the DRA tables
 static void fill_conversion(xgpu_ctx *c, const xgpu_dra_luts *dra, const xgpu_output_format *f, RgbOutArgs &a)
 {
@@ -314,29 +356,11 @@ static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const x
     const size_t es = f->layout == XGPU_OUT_YUV420P ? 1 : (size_t)elem_size(f->dtype);
     TRY(check_dst(c, "pic_output_device", d_dst, dst_size, need, es));
     std::unique_ptr<xgpu_colour_tables_t> cm_new;      // a new set of tables: made here, before anything is queued; uploaded and committed below
-    if (cm) {
-        const int bd = c->sp.bit_depth_luma;
-        if (!is_rgb(f->layout)) { snprintf(c->err, sizeof(c->err), "pic_output_device_cm: a colour transform needs one of the RGB layouts"); return XGPU_ERR_INVALID_ARGUMENT; }
-        if (!cm_cached(c, cm, bd)) {
-            cm_new.reset(new (std::nothrow) xgpu_colour_tables_t);
-            const int rc = cm_new ? xgpu_colour_tables(f, cm, bd, cm_new.get()) : XGPU_ERR_OUT_OF_MEMORY;
-            if (rc < 0) {
-                snprintf(c->err, sizeof(c->err), "pic_output_device_cm: transform %d/%d -> %d/%d (primaries / transfer) is not supported or its parameters are invalid",
-                         cm->src_primaries, cm->src_transfer, cm->dst_primaries, cm->dst_transfer);
-                return rc;
-            }
-            if (!c->d_cm && hipMalloc((void **)&c->d_cm, sizeof(float) * CM_FLOATS) != hipSuccess) { snprintf(c->err, sizeof(c->err), "pic_output_device_cm: cannot allocate the tables"); return XGPU_ERR_OUT_OF_MEMORY; }
-        }
-    }
+    if (cm) TRY(cm_prepare(c, "pic_output_device_cm", f, cm, cm_new));
     if (dra) TRY(upload_dra(c, dra));
     hipStream_t s;
     TRY(out_fork(c, stream, &s));
-    if (cm_new) {      // behind the fork: after every kernel that read the previous tables
-        delete c->cm_tab;
-        c->cm_tab = NULL;      // d_cm is about to change: no key names it until all of the new set is queued
-        TRY(upload_cm(c, cm_new.get(), s));
-        c->cm_tab = cm_new.release(); c->cm_key = *cm; c->cm_bd = c->sp.bit_depth_luma;
-    }
+    TRY(cm_commit(c, cm, cm_new, s));
     const int *cr = f->crop;
     const DevPic &p = dpic(c, pic);
     const int bd = c->sp.bit_depth_luma;
@@ -370,17 +394,7 @@ static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const x
         if (cm) {
             CmOutArgs ca;
             static_cast<RgbOutArgs &>(ca) = a;
-            xgpu_output_format f16 = *f;
-            f16.dtype = XGPU_OUT_U16;      // the code at the coding depth feeds the transform, whatever the output dtype
-            f16.row_pitch = 0;             // (the caller's pitch counts the caller's elements, not 16-bit ones)
-            (void)xgpu_output_coeffs(&f16, bd, ca.coef, &ca.shift, ca.fcoef);
-            ca.maxv = (1 << bd) - 1;
-            const xgpu_colour_tables_t &t = *c->cm_tab;
-            ca.lin = c->d_cm; ca.tone = t.use_tone ? c->d_cm + CM_TONE_OFF : NULL; ca.enc = t.use_encode ? c->d_cm + CM_ENC_OFF : NULL;
-            ca.n_lin = t.n_lin; ca.use_matrix = t.use_matrix;
-            memcpy(ca.m, t.matrix, sizeof(ca.m)); memcpy(ca.luma, t.luma, sizeof(ca.luma));
-            ca.scale = t.scale;
-            ca.outmax = f->dtype == XGPU_OUT_U8 ? 255.f : (float)((1 << bd) - 1);
+            fill_cm(c, f, *c->cm_tab, ca, ca.cm);
             launch_output_cm(ca, f->layout, f->dtype, f->upsample, s);
         } else if (is_rgb(f->layout)) {
             launch_output_rgb(a, f->layout, f->dtype, f->upsample, s);
@@ -462,9 +476,29 @@ static void scaled_common_args(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, c
     a.normalize = sc->normalize;
     for (int k = 0; k < 3; k++) { a.mean[k] = sc->mean[k]; a.inv_std[k] = sc->inv_std[k]; }
 }
+static int output_scaled(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                         const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream);
 int xgpu_pic_output_device_scaled(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, void *d_dst, size_t dst_size, void *stream)
 {
-    static const char who[] = "pic_output_device_scaled";
+    return output_scaled(c, "pic_output_device_scaled", pic, dra, f, sc, NULL, d_dst, dst_size, stream);
+}
+int xgpu_pic_output_device_scaled_cm(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_colour_transform *cm,
+                                     void *d_dst, size_t dst_size, void *stream)
+{
+    return output_scaled(c, "pic_output_device_scaled_cm", pic, dra, f, sc, cm, d_dst, dst_size, stream);
+}
+// the plain call's checks and codes first, then the layout and the transform (cm_prepare's order)
+int xgpu_output_scaled_cm_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_colour_transform *cm, int width, int height, int bit_depth)
+{
+    const int rc = xgpu_output_scaled_check(f, sc, width, height, bit_depth);
+    if (rc < 0 || !cm) return rc;
+    if (!is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+    std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
+    return t ? xgpu_colour_tables(f, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
+}
+static int output_scaled(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                         const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream)
+{
     ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
     int src_rc; const char *why = "";
     const size_t need = scaled_size(f, sc, c->sp.width, c->sp.height, c->sp.bit_depth_luma, &src_rc, &why);
@@ -488,16 +522,19 @@ int xgpu_pic_output_device_scaled(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra
         c->sc_key[0] = -1;      // no key names a block that is freed
         TRY(grow(c, who, &c->sc_tab, &c->sc_tab_cap, blob.size(), "block of tap tables"));
     }
+    std::unique_ptr<xgpu_colour_tables_t> cm_new;
+    if (cm) TRY(cm_prepare(c, who, f, cm, cm_new));
     if (dra) TRY(upload_dra(c, dra));
     hipStream_t s;
     TRY(out_fork(c, stream, &s));
+    TRY(cm_commit(c, cm, cm_new, s));
     if (!cached) {      // behind the fork: after every kernel that read the previous tables
         c->sc_key[0] = -1;      // sc_tab is about to change: no key names it until the new block is queued
         HIPCHK(c, hipMemcpyAsync(c->sc_tab, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
         memcpy(c->sc_key, key, sizeof(key));
         c->sc_host = tb;
     }
-    ScaledOutArgs a;
+    ScaledCmOutArgs a;
     memset(&a, 0, sizeof(a));
     scaled_common_args(c, pic, dra, f, sc, d_dst, a);
     a.w = ws; a.h = hs; a.cw = ws >> 1; a.ch = hs >> 1;
@@ -508,8 +545,13 @@ int xgpu_pic_output_device_scaled(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra
     }
     a.mid = c->sc_mid; a.mpy = align8(ws); a.mpc = align8(ws >> 1);
     a.capy = tb.capy; a.capc = tb.capc;
-    launch_output_scaled(a, f->layout, f->dtype, s);
-    return out_join(c, stream, s);      // the slot, the DRA and the tap tables, the intermediate
+    if (cm) {
+        fill_cm(c, f, *c->cm_tab, a, a.cm);
+        launch_output_scaled_cm(a, f->layout, f->dtype, s);
+    } else {
+        launch_output_scaled(a, f->layout, f->dtype, s);
+    }
+    return out_join(c, stream, s);      // the slot, the DRA, colour and tap tables, the intermediate
 }
 
 // ------------------------------------------------------------------------------------------------ regions of interest: a batch of scaled images
@@ -646,10 +688,21 @@ static int build_roi_block(xgpu_ctx *c, const xgpu_output_format *f, const xgpu_
     }
     return XGPU_OK;
 }
+static int output_rois(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
+                       const xgpu_roi *rois, int n, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream);
 int xgpu_pic_output_device_rois(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
                                 const xgpu_roi *rois, int n, void *d_dst, size_t dst_size, void *stream)
 {
-    static const char who[] = "pic_output_device_rois";
+    return output_rois(c, "pic_output_device_rois", pic, dra, f, sc, rp, rois, n, NULL, d_dst, dst_size, stream);
+}
+int xgpu_pic_output_device_rois_cm(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
+                                   const xgpu_roi *rois, int n, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream)
+{
+    return output_rois(c, "pic_output_device_rois_cm", pic, dra, f, sc, rp, rois, n, cm, d_dst, dst_size, stream);
+}
+static int output_rois(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
+                       const xgpu_roi *rois, int n, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream)
+{
     ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
     int src_rc, bad; char why[160];
     size_t image_pitch = 0, mid_need = 0;
@@ -662,20 +715,28 @@ int xgpu_pic_output_device_rois(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, 
     TRY(build_roi_block(c, f, sc, rp, rois, n, image_pitch, b));
     TRY(grow(c, who, &c->sc_mid, &c->sc_mid_cap, mid_need, "intermediate"));
     TRY(grow(c, who, &c->roi_blk, &c->roi_blk_cap, b.blk.size(), "descriptor block", b.blk.size() / 2));      // some room: a batch of boxes changes its tables' size from call to call
+    std::unique_ptr<xgpu_colour_tables_t> cm_new;
+    if (cm) TRY(cm_prepare(c, who, f, cm, cm_new));
     if (dra) TRY(upload_dra(c, dra));
     hipStream_t s;
     TRY(out_fork(c, stream, &s));
+    TRY(cm_commit(c, cm, cm_new, s));
     // behind the fork: after every kernel that read the previous block.  (Pageable host memory: staged before the call returns, as the DRA tables are.)
     HIPCHK(c, hipMemcpyAsync(c->roi_blk, b.blk.data(), b.blk.size(), hipMemcpyHostToDevice, s));
-    RoisOutArgs a;
+    RoisCmOutArgs a;
     memset(&a, 0, sizeof(a));
     scaled_common_args(c, pic, dra, f, sc, d_dst, a);
     a.mid = c->sc_mid;
     a.capy = b.capy; a.capc = b.capc;
     a.blk = c->roi_blk; a.n = n;
     for (int k = 0; k < 3; k++) a.padv[k] = rp->fit == XGPU_FIT_LETTERBOX ? rp->pad[k] : 0.f;
-    launch_output_rois(a, f->layout, f->dtype, b.max_w, b.max_ih, s);
-    return out_join(c, stream, s);      // the slot, the DRA tables, the block and the intermediate
+    if (cm) {
+        fill_cm(c, f, *c->cm_tab, a, a.cm);
+        launch_output_rois_cm(a, f->layout, f->dtype, b.max_w, b.max_ih, s);
+    } else {
+        launch_output_rois(a, f->layout, f->dtype, b.max_w, b.max_ih, s);
+    }
+    return out_join(c, stream, s);      // the slot, the DRA and colour tables, the block and the intermediate
 }
 
 // ------------------------------------------------------------------------------------------------ scaled video surfaces: a ladder of renditions

@@ -159,7 +159,8 @@ class XgpuDecoder:
         size=(H, W): layouts "rgb" / "yuv444" resized to H x W on the device (xgpu_pic_output_device_scaled) - the crop is the region
         of interest, filter "bilinear" (the antialiased triangle of torch's interpolate(antialias=True)) or "area"; the chroma planes are filtered straight onto
         the destination grid (upsample is not read).  mean / std (float dtypes; three values or one): out = (v - mean[k]) * (float32(1) / float32(std[k])), k the
-        channel's position in the output.  size=None: the unscaled call, and filter / mean / std must be left alone.
+        channel's position in the output.  size=None: the unscaled call, and filter / mean / std must be left alone.  size= together with colour= raises
+        ValueError here, with and without rois=: that combination is pic_output_scaled_cm(pic, size, colour, ...).
         rois=[(x, y, w, h), ...] (with size=): every rectangle - luma samples inside the picture minus the crop, even - resized to H x W in one call
         (xgpu_pic_output_device_rois): [N, 3, H, W] (channels_last: [N, H, W, 3]); image i is what size= with the crop set to
         rectangle i gives.  fit "stretch", or "letterbox": the rectangle keeps its shape inside the image (abi.roi_inner says where) and the rest is `pad` - one
@@ -264,7 +265,7 @@ class XgpuDecoder:
         if layout not in ("rgb", "yuv444"):
             raise ValueError(f"size: the scaled output has layouts 'rgb' and 'yuv444', not {layout!r}")
         if colour is not None:
-            raise ValueError("size: the scaled output takes no colour transform")
+            raise ValueError("size: the scaled output takes no colour transform here - pic_output_scaled_cm(pic, size, colour, ...) is the call that does")
         if filter not in ("bilinear", "area"):
             raise ValueError(f"filter must be 'bilinear' or 'area', not {filter!r}")
         if int(a["out_bit_depth"]) not in (0, self.bit_depth):
@@ -286,17 +287,34 @@ class XgpuDecoder:
     def _rois_fit(a):
         """what a batch checks before _scaled_setup -> the XGPU_FIT_* code"""
         if a["colour"] is not None:
-            raise ValueError("rois: the batch of rectangles takes no colour transform")
+            raise ValueError("rois: the batch of rectangles takes no colour transform here - pic_output_scaled_cm(pic, size, colour, rois=...) is the call that does")
         if a["fit"] not in ("stretch", "letterbox"):
             raise ValueError(f"fit must be 'stretch' or 'letterbox', not {a['fit']!r}")
         return abi.FIT_LETTERBOX if a["fit"] == "letterbox" else abi.FIT_STRETCH
 
-    def _pic_output_tensor_scaled(self, a):
-        """pic_output_tensor with size=(H, W)"""
+    def _cm_check(self, fmt, cm):
+        """0, or the code xgpu_colour_tables refuses transform `cm` with on layout fmt.layout - remembered per transform: making the tables in double precision
+        costs more host time than the whole call whose arguments it checks, and a stream asks for the same transform picture after picture"""
+        memo = self.__dict__.setdefault("_cm_checked", {})
+        key = (fmt.layout, self.bit_depth, cm.src_primaries, cm.src_transfer, cm.dst_primaries, cm.dst_transfer, cm.tone_map, cm.src_peak, cm.dst_peak, cm.linear_scale)
+        if key not in memo:
+            if len(memo) >= 64:
+                memo.clear()
+            memo[key] = self.lib.xgpu_colour_tables(C.byref(fmt), C.byref(cm), self.bit_depth, C.byref(abi.ColourTables()))
+        return memo[key]
+
+    def _pic_output_tensor_scaled(self, a, cm=None):
+        """pic_output_tensor with size=(H, W); cm: pic_output_scaled_cm's xgpu_colour_transform"""
         dtype, fmt, sc, h, w, dev = self._scaled_setup(a)
 
         def refuse():
-            if self.lib.xgpu_output_scaled_size(C.byref(fmt), C.byref(sc), self.width, self.height, self.bit_depth) == 0:
+            if cm is not None:      # xgpu_output_scaled_cm_check's order: the plain call's refusals, then the layout's and the transform's
+                rc = self.lib.xgpu_output_scaled_check(C.byref(fmt), C.byref(sc), self.width, self.height, self.bit_depth) or self._cm_check(fmt, cm)
+                if rc < 0:
+                    raise ValueError(f"invalid colour-managed scaled output ({rc}): size {tuple(a['size'])}, matrix {a['matrix']}, chroma_loc {a['chroma_loc']}, "
+                                     f"crop {a['crop']}, mean {a['mean']}, std {a['std']}, transform {cm.src_primaries}/{cm.src_transfer} -> "
+                                     f"{cm.dst_primaries}/{cm.dst_transfer}")
+            elif self.lib.xgpu_output_scaled_size(C.byref(fmt), C.byref(sc), self.width, self.height, self.bit_depth) == 0:
                 raise ValueError(f"invalid scaled output (layout {a['layout']}, size {tuple(a['size'])}, matrix {a['matrix']}, chroma_loc {a['chroma_loc']}, "
                                  f"crop {a['crop']}, mean {a['mean']}, std {a['std']})")
         out, planar = a["out"], not a["channels_last"]
@@ -306,11 +324,14 @@ class XgpuDecoder:
         fmt.row_pitch = _row_pitch(out.stride(), planar, h, w if planar else 3 * w, 3) * dtype.itemsize
         refuse()
         dl, self._dra_keep = self._dra_luts(a["dra"]) if a["dra"] is not None else (None, None)      # (kept until the next call: the tables are copied asynchronously)
-        self._device_call("xgpu_pic_output_device_scaled", out, a["pic"], dl, C.byref(fmt), C.byref(sc))
+        if cm is not None:
+            self._device_call("xgpu_pic_output_device_scaled_cm", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(cm))
+        else:
+            self._device_call("xgpu_pic_output_device_scaled", out, a["pic"], dl, C.byref(fmt), C.byref(sc))
         return out
 
-    def _pic_output_tensor_rois(self, a):
-        """pic_output_tensor with size=(H, W) and rois=[...]"""
+    def _pic_output_tensor_rois(self, a, cm=None):
+        """pic_output_tensor with size=(H, W) and rois=[...]; cm: pic_output_scaled_cm's xgpu_colour_transform"""
         fit = self._rois_fit(a)
         dtype, fmt, sc, h, w, dev = self._scaled_setup(a)
         rois = [tuple(int(v) for v in r) for r in a["rois"]]
@@ -333,6 +354,10 @@ class XgpuDecoder:
                 at = f"roi {bad.value} {rois[bad.value]}: " if 0 <= bad.value < n else ""
                 raise ValueError(f"invalid batch of rectangles ({rc}): {at}layout {a['layout']}, size {tuple(a['size'])}, fit {a['fit']}, pad {a['pad']}, "
                                  f"crop {a['crop']}, mean {a['mean']}, std {a['std']}, {n} rectangles")
+            if cm is not None:      # the batch's own refusals first, then the transform's
+                rc = self._cm_check(fmt, cm)
+                if rc < 0:
+                    raise ValueError(f"invalid colour transform ({rc}): {cm.src_primaries}/{cm.src_transfer} -> {cm.dst_primaries}/{cm.dst_transfer}")
         out, planar = a["out"], not a["channels_last"]
         if out is None:
             refuse()      # before a tensor is made, and again with its pitches
@@ -342,7 +367,10 @@ class XgpuDecoder:
         rp.image_pitch = st[0] * dtype.itemsize if n > 1 else 0
         refuse()
         dl, self._dra_keep = self._dra_luts(a["dra"]) if a["dra"] is not None else (None, None)      # (kept until the next call: the tables are copied asynchronously)
-        self._device_call("xgpu_pic_output_device_rois", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(rp), ra, n)
+        if cm is not None:
+            self._device_call("xgpu_pic_output_device_rois_cm", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(rp), ra, n, C.byref(cm))
+        else:
+            self._device_call("xgpu_pic_output_device_rois", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(rp), ra, n)
         return out
 
     def _pic_output_tensor_rois_dev(self, a):
@@ -380,6 +408,32 @@ class XgpuDecoder:
                           C.c_void_p(rois.data_ptr()), n, C.c_void_p(count.data_ptr()) if count is not None else None,
                           C.c_void_p(res.data_ptr()) if results else None)
         return (out, res) if results else out
+
+    def pic_output_scaled_cm(self, pic, size, colour, rois=None, fit=None, pad=None, channels_last=False, dtype=None, matrix=1, full_range=False, chroma_loc=0,
+                             crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, filter="bilinear", mean=None, std=None, layout="rgb"):
+        """The scaled output with a colour transform (xgpu_pic_output_device_scaled_cm / _rois_cm): the picture - or, with host
+        rois=[(x, y, w, h), ...], every rectangle - resized to size=(H, W), taken from the stream's colour space to the caller's by `colour` (pic_output_tensor's
+        dict: the keyword arguments of abi.make_colour_transform), normalised by mean / std (float dtypes), on torch's current stream: [3, H, W] (channels_last:
+        [H, W, 3]), with rois [N, 3, H, W] / [N, H, W, 3].  This is where size= and colour= meet: pic_output_tensor(size=..., colour=...) keeps raising ValueError.
+        The encoded Y'CbCr samples are filtered (as in every scaled output), then each destination pixel goes through the transform of pic_output_tensor(colour=).
+        Every other argument is pic_output_tensor's with size=; fit "stretch" (None) or "letterbox" and pad belong to rois= - pad is a value of the destination
+        space, normalised like a pixel and never transformed.  layout: "rgb" only.  Boxes in device memory, warped and remapped outputs take no transform."""
+        import torch
+        if colour is None:
+            raise ValueError("colour: the colour-managed scaled output needs a transform; pic_output_tensor(size=...) is the plain one")
+        if layout != "rgb":
+            raise ValueError(f"colour: a colour transform needs layout 'rgb', not {layout!r}")
+        if isinstance(rois, torch.Tensor):
+            raise ValueError("rois: boxes in device memory take no colour transform")
+        if rois is None and (fit is not None or pad is not None):
+            raise ValueError("fit and pad belong to rois=")
+        a = {"pic": pic, "layout": layout, "channels_last": channels_last, "dtype": dtype, "matrix": matrix, "full_range": full_range, "chroma_loc": chroma_loc,
+             "crop": crop, "dra": dra, "out": out, "bgr": bgr, "out_bit_depth": 0, "colour": None, "size": size, "filter": filter, "mean": mean, "std": std,
+             "rois": rois, "fit": fit or "stretch", "pad": 0.0 if pad is None else pad, "snap": False}
+        cm = abi.make_colour_transform(**colour)
+        if rois is not None:
+            return self._pic_output_tensor_rois(a, cm)
+        return self._pic_output_tensor_scaled(a, cm)
 
     def pic_output_surfaces(self, pic, sizes, layout="nv12", dtype=None, out_bit_depth=0, filter="bilinear", chroma_loc=0, dst_chroma_loc=None, crop=(0, 0, 0, 0),
                             dra=None, out=None):

@@ -122,7 +122,8 @@ class StreamDecoder:
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
         current stream, by default with the colour description of the stream's VUI (tensor_options) and the SPS crop when apply_crop is set.
         to="srgb" | "bt709" | "linear-bt709" | "linear-bt2020" | "pq-bt2020" | ... (colour_transform; with tensor=, layout "rgb"): the picture in that colour
-        space, from the primaries and transfer characteristics of the stream's VUI.
+        space, from the primaries and transfer characteristics of the stream's VUI.  With size= (and host rois=, a list or a callable) the picture is resized and
+        transformed in one call (XgpuDecoder.pic_output_scaled_cm); boxes in device memory, warp= and remap= take no colour transform.
         side=dict(...) (keyword arguments of XgpuDecoder.frame_side_info, {} for the block planes): the coding side information of every picture - motion
         vectors, modes, QP - as a torch tensor under params["side_info"] (the yielded tuple keeps its shape), taken right behind the picture's kernels, before
         the next picture overwrites the map it is read from; kind "flow" defaults to the SPS crop when apply_crop is set
@@ -244,6 +245,8 @@ class StreamDecoder:
                         planes = dec.pic_output_warped(cur, warp(p) if callable(warp) else warp, **kw)
                     elif remap is not None:
                         planes = dec.pic_output_remapped(cur, remap(p) if callable(remap) else remap, step=remap_step, **kw)
+                    elif kw.get("colour") is not None and kw.get("size") is not None:      # size= and to= meet in a call of their own (host rois included)
+                        planes = dec.pic_output_scaled_cm(cur, **kw)
                     else:
                         planes = dec.pic_output_tensor(cur, **kw)
             elif download and output_bit_depth is not None:
