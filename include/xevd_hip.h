@@ -419,6 +419,28 @@ int    xgpu_pic_output_device_scaled_cm(xgpu_ctx *ctx, int pic, const xgpu_dra_l
 int    xgpu_pic_output_device_rois_cm(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
                                       const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size,
                                       void *stream);
+/* ---- scaled output filtered in linear light (k_output_scaled_lin.hip): the two calls above with the filter moved behind the linearisation - what a reduced PQ / HLG
+   picture needs where it has fine, high-contrast detail (averaging code values darkens it; the mean of a black and a white stripe is half the white's light).
+   Per source pixel at luma resolution: (Y, Cb, Cr) as xgpu_pic_output_device forms them (f->upsample and f->chroma_loc ARE read here: chroma is upsampled on the
+   source's own chroma plane, edge-clamped there), the integer R'G'B' code at the coding depth, L_c = lin[code_c].  Vertical pass, luma row table for all three
+   channels: T_c = sum over k ascending of float32(qy[k]) * L_c.  Horizontal pass: V_c = (sum over k ascending of float32(qx[k]) * T_c) * 2^-28.  Every multiply
+   and add is rounded to float32 on its own; an accumulator starts as the first product.  (V_R, V_G, V_B) then run the transform from its primaries matrix on
+   (steps 2 to 4), and bgr, the normalise and the F16 / BF16 rounding follow as in the scaled output.  Image i of a stretched batch is, bit for bit, the single
+   call with the crop set to rectangle i; a letterbox pad value is never transformed.  The exact contract: INTEGRATION.md section 8n; tests/scaled_lin_ref.py
+   restates it.  Destination sizes: xgpu_output_scaled_size / xgpu_output_rois_size.  The intermediate (the context's, grown on demand) is float32 at luma width:
+   3 x Hd x align8(Ws) x 4 bytes, summed over the rectangles (Hd: the inner height).
+   Refusals, all before anything is queued, in this order: the plain call's, with its codes - the batch's 512 MiB rule counts the float32 intermediate, with
+   *bad_index as xgpu_output_rois_check sets it; the single call's intermediate above 512 MiB: XGPU_ERR_UNSUPPORTED; cm = NULL: XGPU_ERR_INVALID_ARGUMENT (without
+   a transform there is no linear light); a layout that is not RGB: XGPU_ERR_INVALID_ARGUMENT; whatever xgpu_colour_tables returns for `cm`.
+   xgpu_output_scaled_lin_check / xgpu_output_rois_lin_check (host only, no context): 0, or the code the call refuses with. */
+int    xgpu_output_scaled_lin_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_colour_transform *cm, int width, int height, int bit_depth);
+int    xgpu_output_rois_lin_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois,
+                                  const xgpu_colour_transform *cm, int width, int height, int bit_depth, int *bad_index);
+int    xgpu_pic_output_device_scaled_lin(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                                         const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream);
+int    xgpu_pic_output_device_rois_lin(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
+                                       const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size,
+                                       void *stream);
 /* ---- regions of interest from device memory (k_output_rois_dev.hip): xgpu_pic_output_device_rois for boxes that a detector left on the GPU.  d_boxes points
    to `capacity` boxes in device memory (1 .. XGPU_MAX_ROIS), d_count (may be NULL: all of them) to a device int32 - the live boxes are the first
    min(max(*d_count, 0), capacity).  The host reads neither; the call does not synchronise and nothing comes back to the host.  Descriptors and tap tables are

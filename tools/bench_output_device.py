@@ -17,6 +17,11 @@ idle device, with (i) the plain scaled / ROI call at the same shape: the price o
 tensor, interpolate(antialias=True) and the normalise (or the u8 rounding) in torch, with the largest difference between the two (on random samples through PQ
 that is a record of filtering encoded samples against display light, not an error bound).  device_us is the kernels alone, queued behind a wait.
 
+The scaled_lin leg (xgpu_pic_output_device_scaled_lin / _rois_lin: k_lin_vertical + k_lin_horizontal and their batch forms) takes the same picture the same way at
+the same three shapes, filtering linear light, and alternates each with (i) the scaled_cm call of the same shape: the price of correctness, and (ii) the only
+correct route without it: the full-size linear-light f32 tensor of the source primaries, interpolate(antialias=True), then matrix, clip, sRGB encode and the
+normalise (or the u8 rounding) in torch - the tone curve left out, in the caller's favour.
+
 The rois leg (xgpu_pic_output_device_rois: k_rois_vertical + k_rois_horizontal) makes 64 images of 224x224 f32 planar, normalised, from the same picture by one
 call - (a) the 8 x 8 grid of tiles, stretched; (b) 64 seeded boxes with sides of 64..512 samples, letterboxed - and times next to it, alternating with it in the
 same run on the same stream, the route without it: 64 calls of xgpu_pic_output_device_scaled with the crop set to the rectangle (for (b) at the inner size, into
@@ -64,7 +69,7 @@ picture once; four one-rung calls are alternated on their own (each makes its ta
 of the kernels alone (median of --iters calls queued behind a wait).  The largest difference between each rung's planes and the torch route in float64 is
 recorded in code values; it is a record, not a test.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|rois|rois_dev|ladder|warp|remap|residual|compare|stats] [--out out/output_device.json]
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|rois|rois_dev|ladder|warp|remap|residual|compare|stats] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -199,6 +204,72 @@ def scaled_cm_leg(torch, dec, pic, s, a, res):
               f"({r['speedup_vs_torch_route']:.1f}x)   max |diff| {diff:.3g}")
         res["scaled_cm"][name] = r
     del full
+
+
+def scaled_lin_leg(torch, dec, pic, s, a, res):
+    """the scaled call filtered in linear light (PQ / BT.2020 -> sRGB through the tone curve) at the scaled_cm leg's three shapes, each alternated with (i) the
+    scaled_cm call of the same shape - the price of filtering light instead of code values - and (ii) the only correct route without it: the full-size linear-light
+    f32 tensor of the source primaries (400 MB at 8K) + F.interpolate(antialias=True) + matrix, clip, sRGB encode and the normalise (or the u8 rounding) in torch,
+    the tone curve left out in the caller's favour.  That route's full-size call runs on a context of its own: a context keeps the tables of one transform, and
+    two transforms taking turns on one context would make each call build its tables again.  The max |diff| against that route is taken from a call without
+    the tone curve (linear_scale 100, as torch_transform scales), so that both sides compute the same thing; for the rectangles it includes their edges, where
+    this call clamps the chroma upsampling to the rectangle and the full-size tensor does not."""
+    import torch.nn.functional as F
+    from xevd_amd import abi
+    from xevd_amd.decoder import XgpuDecoder
+    w, h = a.width, a.height
+    colour = dict(src_primaries=9, src_transfer=16, dst_primaries=1, dst_transfer=13, tone_map=True)
+    no_tone = dict(colour, tone_map=False, linear_scale=100.0)
+    to_linear = dict(src_primaries=9, src_transfer=16, dst_primaries=9, dst_transfer=8)
+    mean = torch.tensor(MEAN, device="cuda:0").view(3, 1, 1)
+    inv = (1.0 / torch.tensor(STD, device="cuda:0")).view(3, 1, 1)
+    mat = torch.tensor([[1.660491, -0.587641, -0.072850], [-0.124550, 1.132900, -0.008349], [-0.018151, -0.100579, 1.118730]], device="cuda:0")
+    dec2 = XgpuDecoder(w, h, a.bit_depth, device=0, max_pics=1)
+    pic2 = dec2.pic_alloc()
+    dec2.pic_upload(pic2, dec.pic_download(pic))
+    full = dec2.pic_output_tensor(pic2, dtype=torch.float32, matrix=9, colour=to_linear)
+    tiles = abi.tile_rois(w, h, (w // 8) & ~1, (h // 8) & ~1)[:64]
+    norm = dict(mean=MEAN, std=STD)
+    shapes = (("224x224_f32_normalised", (224, 224), None, dict(dtype=torch.float32, **norm)), ("1920x1080_u8", (1080, 1920), None, dict(dtype=torch.uint8)),
+              ("64_rois_224x224_f32_normalised", (224, 224), tiles, dict(dtype=torch.float32, **norm)))
+    res["scaled_lin"] = {}
+    for name, size, rois, kw in shapes:
+        is_u8 = kw["dtype"] == torch.uint8
+        roi_kw = {} if rois is None else dict(rois=rois)
+        out = dec.pic_output_scaled_cm(pic, size, colour, matrix=9, linear_light=True, **roi_kw, **kw)
+        cm_out = dec.pic_output_scaled_cm(pic, size, colour, matrix=9, **roi_kw, **kw)
+
+        def lin_call():
+            dec.pic_output_scaled_cm(pic, size, colour, matrix=9, out=out, linear_light=True, **roi_kw, **kw)
+
+        def cm_call():
+            dec.pic_output_scaled_cm(pic, size, colour, matrix=9, out=cm_out, **roi_kw, **kw)
+
+        def finish(x):
+            y = F.interpolate(x[None], size=size, mode="bilinear", antialias=True, align_corners=False)[0]
+            y = (torch.matmul(mat, y.reshape(3, -1)).reshape(y.shape) * 100.0).clamp(0, 1)
+            y = torch.where(y < 0.0031308, 12.92 * y, 1.055 * y.pow(1.0 / 2.4) - 0.055)
+            return (y * 255.0).round().clamp(0, 255).to(torch.uint8) if is_u8 else (y - mean) * inv
+
+        def torch_route():
+            dec2.pic_output_tensor(pic2, out=full, dtype=torch.float32, matrix=9, colour=to_linear)
+            if rois is None:
+                return finish(full)
+            return torch.stack([finish(full[:, y:y + rh, x:x + rw]) for x, y, rw, rh in rois])
+
+        r = alternated(torch, s, {"lin": lin_call, "cm": cm_call}, a.iters)
+        rt = alternated(torch, s, {"lin": lin_call, "torch_route": torch_route}, max(a.iters // 10, 5), warm=2)
+        r["lin"]["device_us"], r["cm"]["device_us"] = round(timed(torch, s, lin_call, a.iters), 2), round(timed(torch, s, cm_call, a.iters), 2)      # the kernels alone
+        r["torch_route"], r["lin_beside_torch_route"] = rt["torch_route"], rt["lin"]
+        same = dec.pic_output_scaled_cm(pic, size, no_tone, matrix=9, linear_light=True, **roi_kw, **kw)      # (after the timed loops: it changes the context's tables)
+        diff = float((torch_route().float() - same.float()).abs().max())
+        r.update({"vs_cm": round(r["lin"]["us"] / r["cm"]["us"], 2), "speedup_vs_torch_route": round(rt["torch_route"]["us"] / rt["lin"]["us"], 2),
+                  "max_abs_diff_vs_torch_route": diff, "diff_unit": "code values of the u8 output" if is_u8 else "normalised float"})
+        print(f"scaled_lin {name:32s} {r['lin']['us']:9.1f} us (kernels {r['lin']['device_us']:7.1f})   scaled_cm call {r['cm']['us']:9.1f} us (kernels {r['cm']['device_us']:7.1f}; {r['vs_cm']:.2f}x)   torch route {rt['torch_route']['us']:10.1f} us "
+              f"({r['speedup_vs_torch_route']:.1f}x)   max |diff| {diff:.3g}")
+        res["scaled_lin"][name] = r
+    del full
+    dec2.close()
 
 
 def rois_leg(torch, dec, pic, s, a, res):
@@ -768,8 +839,8 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats"), default="all",
-                    help="full: the full-size forms and the side information; scaled: the scaled leg alone; scaled_cm: the colour-managed scaled output alone; rois: the batched regions of interest alone; "
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats"), default="all",
+                    help="full: the full-size forms and the side information; scaled: the scaled leg alone; scaled_cm: the colour-managed scaled output alone; scaled_lin: the scaled output filtered in linear light alone; rois: the batched regions of interest alone; "
                          "rois_dev: the regions of interest from boxes in device memory alone; ladder: the ladder of scaled P010 surfaces alone; warp: the warped regions of interest alone; remap: the remapped output alone; residual: the residual "
                          "export alone; compare: the picture comparison alone; stats: the picture statistics alone")
     a = ap.parse_args()
@@ -809,6 +880,8 @@ def main():
             scaled_leg(torch, dec, pic, s, a, res, copy_gbps)
         if a.legs in ("all", "scaled_cm"):
             scaled_cm_leg(torch, dec, pic, s, a, res)
+        if a.legs in ("all", "scaled_lin"):
+            scaled_lin_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "rois"):
             rois_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "rois_dev"):

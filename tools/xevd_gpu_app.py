@@ -142,6 +142,8 @@ def main():
     ap.add_argument("--size", default=None, metavar="WxH", help="write interleaved 8-bit RGB frames resized to W x H on the device instead (antialiased bilinear, "
                     "the matrix / range / chroma siting of the stream's VUI: INTEGRATION.md 8d); with --to: resized and taken to that colour space in the same call "
                     "(INTEGRATION.md 8m), with --tiles too")
+    ap.add_argument("--linear-light", action="store_true", help="with --size and --to: filter the linear light of the source instead of its encoded samples "
+                    "(gamma-correct resize, INTEGRATION.md 8n), with --tiles too")
     ap.add_argument("--tiles", default=None, metavar="WxH", help="with --size: every picture as its grid of W x H tiles (the last column / row moved back inside the "
                     "picture), each resized to --size by one call per picture (INTEGRATION.md 8e); the frames written are the tiles, row by row")
     ap.add_argument("--remap", default=None, metavar="GRID.npy", help="with --size: every picture pulled through this coordinate grid on the device instead of resized "
@@ -180,6 +182,8 @@ def main():
     cmp = RefCompare(args.ref, args.ref_order, args.expect_identical, args.device) if args.ref else None
     if args.tiles is not None and args.size is None:
         ap.error("--tiles: needs --size")
+    if args.linear_light and (args.size is None or args.to is None or args.remap is not None):
+        ap.error("--linear-light: needs --size and --to, and not --remap")
     if args.remap is not None and (args.size is None or args.tiles is not None):
         ap.error("--remap: needs --size, and not --tiles")
     data = open(args.input, "rb").read()
@@ -212,7 +216,7 @@ def main():
                 ap.error(f"--remap: an int32 or float32 array, not {remap.dtype}")
             remap = torch.from_numpy(remap).to(f"cuda:{args.device}")      # uploaded once, used for every picture
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), to=args.to, side=side, rois=rois, residual=resid, compare=cmp, stats=stats,
-                                                                    remap=remap, remap_step=args.remap_step, **lad)
+                                                                    remap=remap, remap_step=args.remap_step, linear_light=args.linear_light, **lad)
     elif args.to is not None:
         import torch
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad)

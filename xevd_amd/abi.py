@@ -729,6 +729,13 @@ _EXPORTS = {
                                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_pic_output_device_rois_cm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(Roi),
                                                  C.c_int, C.POINTER(ColourTransform), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_output_scaled_lin_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(ColourTransform), C.c_int, C.c_int, C.c_int]),
+    "xgpu_output_rois_lin_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(Roi), C.c_int, C.POINTER(ColourTransform),
+                                             C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "xgpu_pic_output_device_scaled_lin": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(ColourTransform),
+                                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_pic_output_device_rois_lin": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(Roi),
+                                                  C.c_int, C.POINTER(ColourTransform), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_roi_snap": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(Roi)]),
     "xgpu_output_rois_dev_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(RoiBounds)] + [C.c_int] * 5),
     "xgpu_output_rois_dev_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(RoiBounds)] + [C.c_int] * 5),

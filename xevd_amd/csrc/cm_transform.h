@@ -37,16 +37,22 @@ __device__ __forceinline__ CmTables cm_lds_tables(const CmParams &p, const float
 {
     return { lds, lds + p.n_lin, lds + p.n_lin + (p.tone ? XGPU_CM_CURVE_SIZE : 0) };
 }
-template <int DT>
-__device__ __forceinline__ void cm_apply(const RgbOutArgs &a, const CmParams &p, const CmTables &t, int y, int cb, int cr, uint32_t &r, uint32_t &g, uint32_t &b)
+// the two halves of cm_apply.  k_output_scaled_lin.hip runs them apart, with its filter between them.
+// cm_linearise: (Y, Cb, Cr) at the coding depth -> linear light of the source primaries, R, G, B
+__device__ __forceinline__ void cm_linearise(const RgbOutArgs &a, const float *lin, int y, int cb, int cr, float &e0, float &e1, float &e2)
 {
-    const float *lin = t.lin, *tone = t.tone, *enc = t.enc;
     // the integer R'G'B' of k_output_rgb's U16 form: the code at the coding depth
     const int yy = y - a.yo, u = cb - a.co, v = cr - a.co;
     const int ty = a.coef[0] * yy + (1 << (a.shift - 1));
-    const float e0 = lin[min(max((ty + a.coef[1] * v) >> a.shift, 0), a.maxv)];
-    const float e1 = lin[min(max((ty + a.coef[2] * u + a.coef[3] * v) >> a.shift, 0), a.maxv)];
-    const float e2 = lin[min(max((ty + a.coef[4] * u) >> a.shift, 0), a.maxv)];
+    e0 = lin[min(max((ty + a.coef[1] * v) >> a.shift, 0), a.maxv)];
+    e1 = lin[min(max((ty + a.coef[2] * u + a.coef[3] * v) >> a.shift, 0), a.maxv)];
+    e2 = lin[min(max((ty + a.coef[4] * u) >> a.shift, 0), a.maxv)];
+}
+// cm_from_linear: linear light of the source primaries -> the bits of three elements of dtype DT (t.lin is not read)
+template <int DT>
+__device__ __forceinline__ void cm_from_linear(const CmParams &p, const CmTables &t, float e0, float e1, float e2, uint32_t &r, uint32_t &g, uint32_t &b)
+{
+    const float *tone = t.tone, *enc = t.enc;
     float q3[3] = { e0, e1, e2 };
     if (p.use_matrix) {
         #pragma unroll
@@ -65,4 +71,11 @@ __device__ __forceinline__ void cm_apply(const RgbOutArgs &a, const CmParams &p,
         o[c] = OutT<DT>::is_float ? fbits<DT>(q) : (uint32_t)__float2int_rn(q * p.outmax);
     }
     r = o[0]; g = o[1]; b = o[2];
+}
+template <int DT>
+__device__ __forceinline__ void cm_apply(const RgbOutArgs &a, const CmParams &p, const CmTables &t, int y, int cb, int cr, uint32_t &r, uint32_t &g, uint32_t &b)
+{
+    float e0, e1, e2;
+    cm_linearise(a, t.lin, y, cb, cr, e0, e1, e2);
+    cm_from_linear<DT>(p, t, e0, e1, e2, r, g, b);
 }

@@ -553,6 +553,13 @@ struct ScaledCmOutArgs : ScaledOutArgs { CmParams cm; };
 struct RoisCmOutArgs : RoisOutArgs { CmParams cm; };
 void launch_output_scaled_cm(const ScaledCmOutArgs &a, int layout, int dtype, hipStream_t s);
 void launch_output_rois_cm(const RoisCmOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s);
+// k_output_scaled_lin.hip: the same two outputs filtered in linear light (xgpu_pic_output_device_scaled_lin / _rois_lin).  The argument
+// types are the colour-managed ones with another intermediate: `mid` is float32, R, G, B planes [rows][mpy] one behind the other (RoiDesc::mid counts floats; mpc,
+// capc and the chroma taps are not read); hc / ve / vo are read (the chroma upsampling of the full-size output), as is `upsample`.
+void launch_output_scaled_lin(const ScaledCmOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
+void launch_output_rois_lin(const RoisCmOutArgs &a, int layout, int dtype, int upsample, int max_w, int max_ih, hipStream_t s);
+// the bytes of a workgroup's LDS one row of the horizontal pass needs at most (capy floats x 3): what one plain launch may request
+static const size_t LIN_LDS_LIMIT = 64 * 1024;
 // k_output_ladder.hip: n renditions ("rungs") of one picture as 4:2:0 video surfaces, each at its own size (xgpu_pic_output_device_ladder, INTEGRATION.md section
 // 8l).  One record per (rung, plane) and pass, in the context's block in front of the tap tables it points into: 3 n records of the vertical pass (plane 0, 1, 2
 // of every rung), then the horizontal pass' - per rung Y, Cb, Cr (YUV420P) or Y and the interleaved Cb Cr rows (NV12 / P016: `pair`).

@@ -477,7 +477,7 @@ static void scaled_common_args(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, c
     for (int k = 0; k < 3; k++) { a.mean[k] = sc->mean[k]; a.inv_std[k] = sc->inv_std[k]; }
 }
 static int output_scaled(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
-                         const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream);
+                         const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream, bool lin = false);
 int xgpu_pic_output_device_scaled(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, void *d_dst, size_t dst_size, void *stream)
 {
     return output_scaled(c, "pic_output_device_scaled", pic, dra, f, sc, NULL, d_dst, dst_size, stream);
@@ -496,13 +496,38 @@ int xgpu_output_scaled_cm_check(const xgpu_output_format *f, const xgpu_scale_pa
     std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
     return t ? xgpu_colour_tables(f, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
 }
+// the linear-light form's own refusals behind the plain call's (section 8n), without a device: the float32 intermediate, then a transform that is missing
+static const size_t ROIS_MID_LIMIT = (size_t)512 << 20;
+static size_t lin_mid_bytes(int ws, int rows) { return (size_t)3 * rows * align8(ws) * sizeof(float); }
+static int scaled_lin_refusal(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_colour_transform *cm, int width, const char **why)
+{
+    *why = "the float32 intermediate of the call passes 512 MiB";
+    if (lin_mid_bytes(width - f->crop[0] - f->crop[1], sc->height) > ROIS_MID_LIMIT) return XGPU_ERR_UNSUPPORTED;
+    *why = "filtering in linear light needs a colour transform";
+    return cm ? XGPU_OK : XGPU_ERR_INVALID_ARGUMENT;
+}
+int xgpu_pic_output_device_scaled_lin(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_colour_transform *cm,
+                                      void *d_dst, size_t dst_size, void *stream)
+{
+    return output_scaled(c, "pic_output_device_scaled_lin", pic, dra, f, sc, cm, d_dst, dst_size, stream, true);
+}
+// the plain call's checks and codes first, then the intermediate, the missing transform, the layout and the transform (cm_prepare's order)
+int xgpu_output_scaled_lin_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_colour_transform *cm, int width, int height, int bit_depth)
+{
+    int rc = xgpu_output_scaled_check(f, sc, width, height, bit_depth);
+    if (rc < 0) return rc;
+    const char *why;
+    if ((rc = scaled_lin_refusal(f, sc, cm, width, &why)) < 0) return rc;
+    return xgpu_output_scaled_cm_check(f, sc, cm, width, height, bit_depth);
+}
 static int output_scaled(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
-                         const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream)
+                         const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream, bool lin)
 {
     ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
     int src_rc; const char *why = "";
     const size_t need = scaled_size(f, sc, c->sp.width, c->sp.height, c->sp.bit_depth_luma, &src_rc, &why);
     if (need == 0) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return src_rc; }
+    if (lin && (src_rc = scaled_lin_refusal(f, sc, cm, c->sp.width, &why)) < 0) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return src_rc; }
     TRY(check_dst_fits(c, who, d_dst, dst_size, need, elem_size(f->dtype)));
     if (dra) TRY(check_dra(c, dra));      // upload_dra's refusals, before anything is queued
     TRY(check_device_dst(c, who, d_dst, need));
@@ -517,7 +542,8 @@ static int output_scaled(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_l
         const int rc = scale_build_tables(ws, hs, wd, hd, sc->filter, f->chroma_loc, blob, tb);
         if (rc < 0) { snprintf(c->err, sizeof(c->err), "%s: cannot make the tap tables for %dx%d -> %dx%d", who, ws, hs, wd, hd); return rc; }
     }
-    TRY(grow(c, who, &c->sc_mid, &c->sc_mid_cap, (size_t)hd * mid_row_samples(ws) * sizeof(uint16_t), "intermediate"));
+    if (lin && (size_t)3 * tb.capy * sizeof(float) > LIN_LDS_LIMIT) { snprintf(c->err, sizeof(c->err), "%s: a row's spans pass the LDS of one launch", who); return XGPU_ERR_UNEXPECTED; }
+    TRY(grow(c, who, &c->sc_mid, &c->sc_mid_cap, lin ? lin_mid_bytes(ws, hd) : (size_t)hd * mid_row_samples(ws) * sizeof(uint16_t), "intermediate"));
     if (!cached && c->sc_tab_cap < blob.size()) {
         c->sc_key[0] = -1;      // no key names a block that is freed
         TRY(grow(c, who, &c->sc_tab, &c->sc_tab_cap, blob.size(), "block of tap tables"));
@@ -545,7 +571,11 @@ static int output_scaled(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_l
     }
     a.mid = c->sc_mid; a.mpy = align8(ws); a.mpc = align8(ws >> 1);
     a.capy = tb.capy; a.capc = tb.capc;
-    if (cm) {
+    if (lin) {
+        fill_siting(f->chroma_loc, a);
+        fill_cm(c, f, *c->cm_tab, a, a.cm);
+        launch_output_scaled_lin(a, f->layout, f->dtype, f->upsample, s);
+    } else if (cm) {
         fill_cm(c, f, *c->cm_tab, a, a.cm);
         launch_output_scaled_cm(a, f->layout, f->dtype, s);
     } else {
@@ -584,10 +614,9 @@ static size_t rois_pad_and_pitch(const xgpu_output_format *f, const xgpu_scale_p
 }
 // The whole of a call's argument checks, without a device: the bytes the destination needs, or 0 with *rc = the code, `why` (a buffer of 160 bytes) and *bad =
 // the rectangle it names (-1: none).  image_pitch / mid_bytes (may be NULL): the bytes between two images, and the intermediate of the call - the sum over the
-// rectangles of Hi * mid_row_samples(Ws) * 2.
-static const size_t ROIS_MID_LIMIT = (size_t)512 << 20;
+// rectangles of Hi * mid_row_samples(Ws) * 2 (lin, the form filtered in linear light: of lin_mid_bytes(Ws, Hi)).
 static size_t rois_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n, int width, int height, int bd,
-                        int *rc, char *why, int *bad, size_t *image_pitch, size_t *mid_bytes)
+                        int *rc, char *why, int *bad, size_t *image_pitch, size_t *mid_bytes, bool lin = false)
 {
     const char *w0 = "";
     *bad = -1;
@@ -618,7 +647,7 @@ static size_t rois_size(const xgpu_output_format *f, const xgpu_scale_params *sc
             snprintf(why, 160, "roi %d: %d x %d to %d x %d is outside 1/64 .. 8 times per axis", i, r.width, r.height, in[2], in[3]);
             return 0;
         }
-        mid += (size_t)in[3] * mid_row_samples(r.width) * sizeof(uint16_t);
+        mid += lin ? lin_mid_bytes(r.width, in[3]) : (size_t)in[3] * mid_row_samples(r.width) * sizeof(uint16_t);
         if (mid > ROIS_MID_LIMIT) { snprintf(why, 160, "roi %d: the intermediate of the call passes 512 MiB here", i); return 0; }
     }
     *bad = -1;
@@ -646,7 +675,7 @@ size_t xgpu_output_rois_size(const xgpu_output_format *f, const xgpu_scale_param
 // rectangle and the tallest inner part, which size the launch.
 struct RoiBlock { std::vector<uint8_t> blk; int capy, capc, max_w, max_ih; };
 static int build_roi_block(xgpu_ctx *c, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n, size_t image_pitch,
-                           RoiBlock &b)
+                           RoiBlock &b, bool lin = false)      // lin: the float32 intermediate of section 8n - RoiDesc::mid counts floats
 {
     struct Set { int ws, hs, wi, hi; ScaleTabs tb; size_t base; };
     std::vector<Set> sets;
@@ -675,9 +704,9 @@ static int build_roi_block(xgpu_ctx *c, const xgpu_output_format *f, const xgpu_
         d.dst = (uint64_t)i * image_pitch;
         d.x = r.x; d.y = r.y; d.w = r.width; d.h = r.height;
         d.ix = in[0]; d.iy = in[1]; d.iw = in[2]; d.ih = in[3];
-        d.mid = (uint32_t)(mid / sizeof(uint16_t));
+        d.mid = (uint32_t)(mid / (lin ? sizeof(float) : sizeof(uint16_t)));
         d.mpy = align8(r.width); d.mpc = align8(r.width >> 1);
-        mid += (size_t)in[3] * mid_row_samples(r.width) * sizeof(uint16_t);
+        mid += lin ? lin_mid_bytes(r.width, in[3]) : (size_t)in[3] * mid_row_samples(r.width) * sizeof(uint16_t);
         for (int t = 0; t < 4; t++) {
             d.first[t] = (uint32_t)(st.base + st.tb.off_first[t]); d.count[t] = (uint32_t)(st.base + st.tb.off_count[t]); d.wt[t] = (uint32_t)(st.base + st.tb.off_w[t]);
             d.stride[t] = st.tb.stride[t];
@@ -689,7 +718,7 @@ static int build_roi_block(xgpu_ctx *c, const xgpu_output_format *f, const xgpu_
     return XGPU_OK;
 }
 static int output_rois(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
-                       const xgpu_roi *rois, int n, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream);
+                       const xgpu_roi *rois, int n, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream, bool lin = false);
 int xgpu_pic_output_device_rois(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
                                 const xgpu_roi *rois, int n, void *d_dst, size_t dst_size, void *stream)
 {
@@ -700,19 +729,38 @@ int xgpu_pic_output_device_rois_cm(xgpu_ctx *c, int pic, const xgpu_dra_luts *dr
 {
     return output_rois(c, "pic_output_device_rois_cm", pic, dra, f, sc, rp, rois, n, cm, d_dst, dst_size, stream);
 }
+int xgpu_pic_output_device_rois_lin(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
+                                    const xgpu_roi *rois, int n, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream)
+{
+    return output_rois(c, "pic_output_device_rois_lin", pic, dra, f, sc, rp, rois, n, cm, d_dst, dst_size, stream, true);
+}
+// the plain batch's checks with the float32 intermediate in its 512 MiB rule (*bad_index as xgpu_output_rois_check sets it), then the single call's order
+int xgpu_output_rois_lin_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois,
+                               const xgpu_colour_transform *cm, int width, int height, int bit_depth, int *bad_index)
+{
+    int rc, bad; char why[160];
+    (void)rois_size(f, sc, rp, rois, n_rois, width, height, bit_depth, &rc, why, &bad, NULL, NULL, true);
+    if (bad_index) *bad_index = bad;
+    if (rc < 0) return rc;
+    if (!cm || !is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+    std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
+    return t ? xgpu_colour_tables(f, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
+}
 static int output_rois(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
-                       const xgpu_roi *rois, int n, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream)
+                       const xgpu_roi *rois, int n, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream, bool lin)
 {
     ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
     int src_rc, bad; char why[160];
     size_t image_pitch = 0, mid_need = 0;
-    const size_t need = rois_size(f, sc, rp, rois, n, c->sp.width, c->sp.height, c->sp.bit_depth_luma, &src_rc, why, &bad, &image_pitch, &mid_need);
+    const size_t need = rois_size(f, sc, rp, rois, n, c->sp.width, c->sp.height, c->sp.bit_depth_luma, &src_rc, why, &bad, &image_pitch, &mid_need, lin);
     if (need == 0) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return src_rc; }
+    if (lin && !cm) { snprintf(c->err, sizeof(c->err), "%s: filtering in linear light needs a colour transform", who); return XGPU_ERR_INVALID_ARGUMENT; }
     TRY(check_dst_fits(c, who, d_dst, dst_size, need, elem_size(f->dtype)));
     if (dra) TRY(check_dra(c, dra));      // upload_dra's refusals, before anything is queued
     TRY(check_device_dst(c, who, d_dst, need));
     RoiBlock b;      // made here, before anything is queued
-    TRY(build_roi_block(c, f, sc, rp, rois, n, image_pitch, b));
+    TRY(build_roi_block(c, f, sc, rp, rois, n, image_pitch, b, lin));
+    if (lin && (size_t)3 * b.capy * sizeof(float) > LIN_LDS_LIMIT) { snprintf(c->err, sizeof(c->err), "%s: a row's spans pass the LDS of one launch", who); return XGPU_ERR_UNEXPECTED; }
     TRY(grow(c, who, &c->sc_mid, &c->sc_mid_cap, mid_need, "intermediate"));
     TRY(grow(c, who, &c->roi_blk, &c->roi_blk_cap, b.blk.size(), "descriptor block", b.blk.size() / 2));      // some room: a batch of boxes changes its tables' size from call to call
     std::unique_ptr<xgpu_colour_tables_t> cm_new;
@@ -730,7 +778,11 @@ static int output_rois(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_lut
     a.capy = b.capy; a.capc = b.capc;
     a.blk = c->roi_blk; a.n = n;
     for (int k = 0; k < 3; k++) a.padv[k] = rp->fit == XGPU_FIT_LETTERBOX ? rp->pad[k] : 0.f;
-    if (cm) {
+    if (lin) {
+        fill_siting(f->chroma_loc, a);
+        fill_cm(c, f, *c->cm_tab, a, a.cm);
+        launch_output_rois_lin(a, f->layout, f->dtype, f->upsample, b.max_w, b.max_ih, s);
+    } else if (cm) {
         fill_cm(c, f, *c->cm_tab, a, a.cm);
         launch_output_rois_cm(a, f->layout, f->dtype, b.max_w, b.max_ih, s);
     } else {

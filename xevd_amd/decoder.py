@@ -279,7 +279,7 @@ class XgpuDecoder:
         h, w = int(a["size"][0]), int(a["size"][1])
         lay = (abi.OUT_RGB_INTERLEAVED, abi.OUT_RGB_PLANAR) if layout == "rgb" else (abi.OUT_YUV444_INTERLEAVED, abi.OUT_YUV444_PLANAR)
         fmt = abi.make_output_format(lay[0] if a["channels_last"] else lay[1], codes[dtype], bgr=a["bgr"], matrix=a["matrix"], full_range=a["full_range"],
-                                     chroma_loc=a["chroma_loc"], crop=a["crop"])
+                                     chroma_loc=a["chroma_loc"], crop=a["crop"], upsample=a.get("upsample", abi.UPSAMPLE_LINEAR))      # (read by the linear-light form only)
         sc = abi.make_scale_params(w, h, abi.SCALE_BILINEAR if filter == "bilinear" else abi.SCALE_AREA, mean=mean, std=std)
         return dtype, fmt, sc, h, w, torch.device("cuda", self.sp.device)
 
@@ -303,12 +303,21 @@ class XgpuDecoder:
             memo[key] = self.lib.xgpu_colour_tables(C.byref(fmt), C.byref(cm), self.bit_depth, C.byref(abi.ColourTables()))
         return memo[key]
 
-    def _pic_output_tensor_scaled(self, a, cm=None):
-        """pic_output_tensor with size=(H, W); cm: pic_output_scaled_cm's xgpu_colour_transform"""
+    def _pic_output_tensor_scaled(self, a, cm=None, lin=False):
+        """pic_output_tensor with size=(H, W); cm: pic_output_scaled_cm's xgpu_colour_transform; lin: its linear_light"""
         dtype, fmt, sc, h, w, dev = self._scaled_setup(a)
 
         def refuse():
-            if cm is not None:      # xgpu_output_scaled_cm_check's order: the plain call's refusals, then the layout's and the transform's
+            if lin:      # xgpu_output_scaled_lin_check's order: the plain call's refusals, the intermediate's, then the layout's and the transform's
+                rc = self.lib.xgpu_output_scaled_check(C.byref(fmt), C.byref(sc), self.width, self.height, self.bit_depth)
+                if rc == 0:      # without a transform the check stops at the intermediate (-104) or at the missing transform; the transform's own answer is remembered
+                    big = self.lib.xgpu_output_scaled_lin_check(C.byref(fmt), C.byref(sc), None, self.width, self.height, self.bit_depth) == -104
+                    rc = -104 if big else self._cm_check(fmt, cm)
+                if rc < 0:
+                    raise ValueError(f"invalid linear-light scaled output ({rc}): size {tuple(a['size'])}, matrix {a['matrix']}, chroma_loc {a['chroma_loc']}, "
+                                     f"crop {a['crop']}, mean {a['mean']}, std {a['std']}, transform {cm.src_primaries}/{cm.src_transfer} -> "
+                                     f"{cm.dst_primaries}/{cm.dst_transfer}")
+            elif cm is not None:      # xgpu_output_scaled_cm_check's order: the plain call's refusals, then the layout's and the transform's
                 rc = self.lib.xgpu_output_scaled_check(C.byref(fmt), C.byref(sc), self.width, self.height, self.bit_depth) or self._cm_check(fmt, cm)
                 if rc < 0:
                     raise ValueError(f"invalid colour-managed scaled output ({rc}): size {tuple(a['size'])}, matrix {a['matrix']}, chroma_loc {a['chroma_loc']}, "
@@ -325,13 +334,13 @@ class XgpuDecoder:
         refuse()
         dl, self._dra_keep = self._dra_luts(a["dra"]) if a["dra"] is not None else (None, None)      # (kept until the next call: the tables are copied asynchronously)
         if cm is not None:
-            self._device_call("xgpu_pic_output_device_scaled_cm", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(cm))
+            self._device_call("xgpu_pic_output_device_scaled_lin" if lin else "xgpu_pic_output_device_scaled_cm", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(cm))
         else:
             self._device_call("xgpu_pic_output_device_scaled", out, a["pic"], dl, C.byref(fmt), C.byref(sc))
         return out
 
-    def _pic_output_tensor_rois(self, a, cm=None):
-        """pic_output_tensor with size=(H, W) and rois=[...]; cm: pic_output_scaled_cm's xgpu_colour_transform"""
+    def _pic_output_tensor_rois(self, a, cm=None, lin=False):
+        """pic_output_tensor with size=(H, W) and rois=[...]; cm: pic_output_scaled_cm's xgpu_colour_transform; lin: its linear_light"""
         fit = self._rois_fit(a)
         dtype, fmt, sc, h, w, dev = self._scaled_setup(a)
         rois = [tuple(int(v) for v in r) for r in a["rois"]]
@@ -350,6 +359,9 @@ class XgpuDecoder:
         def refuse():
             bad = C.c_int(-1)
             rc = self.lib.xgpu_output_rois_check(C.byref(fmt), C.byref(sc), C.byref(rp), ra, n, self.width, self.height, self.bit_depth, C.byref(bad))
+            if rc == 0 and lin:      # the 512 MiB rule on the float32 intermediate; the transform itself is checked (and remembered) below
+                rc = self.lib.xgpu_output_rois_lin_check(C.byref(fmt), C.byref(sc), C.byref(rp), ra, n, None, self.width, self.height, self.bit_depth, C.byref(bad))
+                rc = rc if bad.value >= 0 else 0
             if rc < 0:
                 at = f"roi {bad.value} {rois[bad.value]}: " if 0 <= bad.value < n else ""
                 raise ValueError(f"invalid batch of rectangles ({rc}): {at}layout {a['layout']}, size {tuple(a['size'])}, fit {a['fit']}, pad {a['pad']}, "
@@ -368,7 +380,7 @@ class XgpuDecoder:
         refuse()
         dl, self._dra_keep = self._dra_luts(a["dra"]) if a["dra"] is not None else (None, None)      # (kept until the next call: the tables are copied asynchronously)
         if cm is not None:
-            self._device_call("xgpu_pic_output_device_rois_cm", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(rp), ra, n, C.byref(cm))
+            self._device_call("xgpu_pic_output_device_rois_lin" if lin else "xgpu_pic_output_device_rois_cm", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(rp), ra, n, C.byref(cm))
         else:
             self._device_call("xgpu_pic_output_device_rois", out, a["pic"], dl, C.byref(fmt), C.byref(sc), C.byref(rp), ra, n)
         return out
@@ -410,15 +422,24 @@ class XgpuDecoder:
         return (out, res) if results else out
 
     def pic_output_scaled_cm(self, pic, size, colour, rois=None, fit=None, pad=None, channels_last=False, dtype=None, matrix=1, full_range=False, chroma_loc=0,
-                             crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, filter="bilinear", mean=None, std=None, layout="rgb"):
+                             crop=(0, 0, 0, 0), dra=None, out=None, bgr=False, filter="bilinear", mean=None, std=None, layout="rgb", linear_light=False,
+                             upsample="linear"):
         """The scaled output with a colour transform (xgpu_pic_output_device_scaled_cm / _rois_cm): the picture - or, with host
         rois=[(x, y, w, h), ...], every rectangle - resized to size=(H, W), taken from the stream's colour space to the caller's by `colour` (pic_output_tensor's
         dict: the keyword arguments of abi.make_colour_transform), normalised by mean / std (float dtypes), on torch's current stream: [3, H, W] (channels_last:
         [H, W, 3]), with rois [N, 3, H, W] / [N, H, W, 3].  This is where size= and colour= meet: pic_output_tensor(size=..., colour=...) keeps raising ValueError.
         The encoded Y'CbCr samples are filtered (as in every scaled output), then each destination pixel goes through the transform of pic_output_tensor(colour=).
         Every other argument is pic_output_tensor's with size=; fit "stretch" (None) or "letterbox" and pad belong to rois= - pad is a value of the destination
-        space, normalised like a pixel and never transformed.  layout: "rgb" only.  Boxes in device memory, warped and remapped outputs take no transform."""
+        space, normalised like a pixel and never transformed.  layout: "rgb" only.  Boxes in device memory, warped and remapped outputs take no transform.
+        linear_light=True (xgpu_pic_output_device_scaled_lin / _rois_lin): the filter runs on the linear light of the source
+        primaries instead - every source pixel is converted as pic_output_tensor converts it (upsample "linear" / "nearest" and chroma_loc select the chroma
+        upsampling; upsample is read in this form only) and linearised, the float32 values are filtered, and the rest of the transform follows.  It is what a
+        reduced PQ / HLG picture with fine, high-contrast detail needs, and costs a float32 intermediate of 3 x H x (source width) x 4 bytes."""
         import torch
+        if upsample not in ("linear", "nearest"):
+            raise ValueError(f"upsample must be 'linear' or 'nearest', not {upsample!r}")
+        if upsample != "linear" and not linear_light:
+            raise ValueError("upsample belongs to linear_light=True: the other scaled outputs filter chroma on its own grid")
         if colour is None:
             raise ValueError("colour: the colour-managed scaled output needs a transform; pic_output_tensor(size=...) is the plain one")
         if layout != "rgb":
@@ -429,11 +450,12 @@ class XgpuDecoder:
             raise ValueError("fit and pad belong to rois=")
         a = {"pic": pic, "layout": layout, "channels_last": channels_last, "dtype": dtype, "matrix": matrix, "full_range": full_range, "chroma_loc": chroma_loc,
              "crop": crop, "dra": dra, "out": out, "bgr": bgr, "out_bit_depth": 0, "colour": None, "size": size, "filter": filter, "mean": mean, "std": std,
-             "rois": rois, "fit": fit or "stretch", "pad": 0.0 if pad is None else pad, "snap": False}
+             "rois": rois, "fit": fit or "stretch", "pad": 0.0 if pad is None else pad, "snap": False,
+             "upsample": abi.UPSAMPLE_LINEAR if upsample == "linear" else abi.UPSAMPLE_NEAREST}
         cm = abi.make_colour_transform(**colour)
         if rois is not None:
-            return self._pic_output_tensor_rois(a, cm)
-        return self._pic_output_tensor_scaled(a, cm)
+            return self._pic_output_tensor_rois(a, cm, bool(linear_light))
+        return self._pic_output_tensor_scaled(a, cm, bool(linear_light))
 
     def pic_output_surfaces(self, pic, sizes, layout="nv12", dtype=None, out_bit_depth=0, filter="bilinear", chroma_loc=0, dst_chroma_loc=None, crop=(0, 0, 0, 0),
                             dra=None, out=None):

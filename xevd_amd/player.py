@@ -116,7 +116,8 @@ class StreamDecoder:
         return cm
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
-                 residual=None, compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None):
+                 residual=None, compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
+                 linear_light=False):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -124,6 +125,8 @@ class StreamDecoder:
         to="srgb" | "bt709" | "linear-bt709" | "linear-bt2020" | "pq-bt2020" | ... (colour_transform; with tensor=, layout "rgb"): the picture in that colour
         space, from the primaries and transfer characteristics of the stream's VUI.  With size= (and host rois=, a list or a callable) the picture is resized and
         transformed in one call (XgpuDecoder.pic_output_scaled_cm); boxes in device memory, warp= and remap= take no colour transform.
+        linear_light=True (with tensor=, size= and to=): that call filters the linear light of the source instead of its encoded samples
+        (pic_output_scaled_cm's linear_light; tensor=dict(upsample="nearest") goes with it) - gamma-correct resize, what a reduced HDR picture needs.
         side=dict(...) (keyword arguments of XgpuDecoder.frame_side_info, {} for the block planes): the coding side information of every picture - motion
         vectors, modes, QP - as a torch tensor under params["side_info"] (the yielded tuple keeps its shape), taken right behind the picture's kernels, before
         the next picture overwrites the map it is read from; kind "flow" defaults to the SPS crop when apply_crop is set
@@ -159,6 +162,8 @@ class StreamDecoder:
             raise ValueError("surface_options: needs surfaces=[(H, W), ...]")
         if to is not None and tensor is None:
             raise ValueError("to: needs tensor=dict(...)")
+        if linear_light and (tensor is None or size is None or to is None):
+            raise ValueError("linear_light: needs tensor=dict(...), size=(H, W) and to=")
         if (size is not None or mean is not None or std is not None) and tensor is None:
             raise ValueError("size / mean / std: need tensor=dict(...)")
         if rois is not None and (tensor is None or size is None):
@@ -246,7 +251,7 @@ class StreamDecoder:
                     elif remap is not None:
                         planes = dec.pic_output_remapped(cur, remap(p) if callable(remap) else remap, step=remap_step, **kw)
                     elif kw.get("colour") is not None and kw.get("size") is not None:      # size= and to= meet in a call of their own (host rois included)
-                        planes = dec.pic_output_scaled_cm(cur, **kw)
+                        planes = dec.pic_output_scaled_cm(cur, linear_light=bool(linear_light), **kw)
                     else:
                         planes = dec.pic_output_tensor(cur, **kw)
             elif download and output_bit_depth is not None:
@@ -297,7 +302,8 @@ class StreamDecoder:
                 self._dec = None
 
     def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
-                     compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None):
+                     compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
+                     linear_light=False):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
@@ -307,7 +313,7 @@ class StreamDecoder:
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
                                        residual=residual, compare=compare, stats=stats, warp=warp, remap=remap, remap_step=remap_step, surfaces=surfaces,
-                                       surface_layout=surface_layout, surface_options=surface_options):
+                                       surface_layout=surface_layout, surface_options=surface_options, linear_light=linear_light):
             if p["is_idr"]:
                 epoch += 1
             if surfaces is not None:      # (synchronises torch's current stream: the tensors are complete)
