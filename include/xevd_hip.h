@@ -957,6 +957,14 @@ int xgpu_test_itdq(xgpu_ctx *ctx, int16_t *coef, int n_blocks, int log2w, int lo
    stride: `coef` holds n_blocks blocks of (h << log2s) samples, block i starting at i * (h << log2s), and the samples outside a block's columns come back untouched
    (a 64x64 sub-block of a larger CU keeps the CU's stride, src_base/xevd_itdq.c:573-584).  A stride beyond the width needs a width of at least 8 and a block of more than 16 samples. */
 int xgpu_test_itdq_ex(xgpu_ctx *ctx, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth, int tr_v, int tr_h, int log2s);
+/* The same blocks through the pair form of the residual pass (two entries of the item list per workgroup, the way the pass rides in the data-flow intra launch of an IQT
+   sequence; a context without tool_iqt is refused): ceil(items / 2) workgroups.  The residual arena is filled with 0x5A5A first and comes back whole, so the samples
+   outside a block's columns - and a block nobody processed - read 0x5A5A. */
+int xgpu_test_itdq_pairs(xgpu_ctx *ctx, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth, int tr_v, int tr_h, int log2s);
+/* ... n_groups groups in one launch; groups[6 * g ..] = { n_blocks, log2w, log2h, tr_v, tr_h, log2s } of group g, each held to the rules above; qp has one entry per block
+   in group order.  Group g's blocks lie back to back from the next multiple of 64 samples behind group g - 1 (group 0 at 0), and the item list is cut group by group:
+   where a group has an odd number of items, items of two classes or two transform pairs meet in one workgroup and run one after the other. */
+int xgpu_test_itdq_pairs_mixed(xgpu_ctx *ctx, int16_t *coef, int n_groups, const int32_t *groups, const uint8_t *qp, int bit_depth);
 /* xgpu_scale_taps made by the device's row builder (the one k_rois_prepare runs, one lane per row): same arguments, same results, same return value; w_stride
    must hold the widest row.  Blocking. */
 int xgpu_test_scale_taps_device(xgpu_ctx *ctx, int n_plane, int subsampling, int siting_half_luma, int n_dst, int filter, int32_t *first, int32_t *count,

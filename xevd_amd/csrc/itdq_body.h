@@ -134,6 +134,20 @@ __device__ __forceinline__ uint32_t wave_masks(const uint32_t *s_m, int t)
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
 }
 
+// A matrix row pair's entries for one walk step.  For a pair of items the values are pinned in scalar registers in front of the two items' products: each item's products
+// stand behind a test of its own mask, and left alone the compiler sinks the scalar load into both branches - one load and one wait per item instead of one per row pair.
+// (PIN: a pair, in a class whose chunk index is wave-uniform - elsewhere the entries are vector loads.)
+template <int N, bool PIN>
+__device__ __forceinline__ void itq_row(uint32_t (&rw)[N], const uint32_t *row)
+{
+#pragma unroll
+    for (int n = 0; n < N; n++) rw[n] = row[n];
+    if constexpr (PIN) {
+#pragma unroll
+        for (int n = 0; n < N; n++) asm volatile("" : "+s"(rw[n]));
+    }
+}
+
 // wave-uniform matrix choice: DCT-II, or for ATS work items (4..32 only) DST-VII / DCT-VIII
 template <int L>
 __device__ __forceinline__ const uint32_t *itdq_matrix(int tr) { return (tr == TR_DCT2 || L < 2 || L > 5) ? k_tmp + tmp_base(L) : k_atsp[tr - 1] + atsp_base(L); }
@@ -142,25 +156,12 @@ __device__ __forceinline__ const uint32_t *itdq_matrix(int tr) { return (tr == T
 // in registers - one load of its 8 / 16 / 32 contiguous bytes (log2s == log2w: only 64x64 sub-blocks keep a CU's stride), both stages as direct products with the
 // wave-uniform matrix pairs as scalar operands, the intermediate rounded and clipped (or split hi * 2^15 + lo) exactly like the LDS form.  No LDS, no barrier; lanes and
 // waves without a TB leave at once.
+// itdq_small_tb: the products and the stores of one TB whose record and coefficients have arrived; itdq_small: the requests of the lane's TB of each of the NI items
+// (one, or the two items of a pair: k_intra_itdq), all of them in flight before the first product.
 template <int LW, int LH, bool IQT>
-__device__ __forceinline__ void itdq_small(const ItdqArgs &a, const TbWave wv)
+__device__ __forceinline__ void itdq_small_tb(const ItdqArgs &a, const itq_v2 rec, const uint32_t (&raw)[(1 << (LW + LH)) / 2], const uint32_t *tmh, const uint32_t *tmw, bool s16_mid)
 {
     constexpr int W = 1 << LW, H = 1 << LH, S = W * H;
-    static_assert(S <= 16 && itdq_group(LW, LH) <= 256, "one TB per lane");
-    const int p = threadIdx.x;
-    if (p >= wv.count) return;
-    const itq_v2 rec = *(const itq_v2_u *)(a.tbs + wv.first + p);
-    const uint32_t *tmh = itdq_matrix<LH>(wv.tr_v), *tmw = itdq_matrix<LW>(wv.tr_h);
-    const bool s16_mid = IQT || wv.tr_v != TR_DCT2 || wv.tr_h != TR_DCT2;
-    uint32_t raw[S / 2];
-    if constexpr (S == 4) { const itq_v2 v = *(const itq_v2_s *)(a.coef + rec.x); raw[0] = v.x; raw[1] = v.y; }
-    else {
-#pragma unroll
-        for (int i = 0; i < S / 8; i++) {
-            const itq_v4 v = *(const itq_v4_u *)(a.coef + rec.x + 8 * i);
-            raw[4 * i] = v.x; raw[4 * i + 1] = v.y; raw[4 * i + 2] = v.z; raw[4 * i + 3] = v.w;
-        }
-    }
     const ItdqScale<(LW + LH) & 1, IQT> dq(rec_qp(rec), a.bd, LW + LH);
     int d[S];
 #pragma unroll
@@ -240,6 +241,48 @@ __device__ __forceinline__ void itdq_small(const ItdqArgs &a, const TbWave wv)
     }
 }
 
+template <int LW, int LH, bool IQT, int NI = 1>
+__device__ __forceinline__ void itdq_small(const ItdqArgs &a, const TbWave (&wv)[NI], const int tid)
+{
+    constexpr int W = 1 << LW, H = 1 << LH, S = W * H;
+    static_assert(S <= 16 && itdq_group(LW, LH) <= 256, "one TB per lane");
+    static_assert(NI == 1 || NI == 2, "an item, or a pair of one class and one transform pair");
+    const int p = tid;
+    bool live[NI], any = false;
+#pragma unroll
+    for (int i = 0; i < NI; i++) { live[i] = p < wv[i].count; any |= live[i]; }
+    if (!any) return;
+    itq_v2 rec[NI];
+#pragma unroll
+    for (int i = 0; i < NI; i++) { rec[i] = itq_any<itq_v2>(); itq_rec_if(rec[i], a.tbs + wv[i].first + p, live[i]); }
+    const uint32_t *tmh = itdq_matrix<LH>(wv[0].tr_v), *tmw = itdq_matrix<LW>(wv[0].tr_h);
+    const bool s16_mid = IQT || wv[0].tr_v != TR_DCT2 || wv[0].tr_h != TR_DCT2;
+    constexpr int NV = S == 4 ? 1 : S / 8;
+    typedef typename std::conditional<S == 4, itq_v2, itq_v4>::type cvec;
+    cvec cv[NI][NV];
+    if (NI > 1) __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): both records, in front of both coefficient requests (see itdq_item)
+#pragma unroll
+    for (int i = 0; i < NI; i++) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) cv[i][k] = itq_any<cvec>();
+        if (live[i]) {
+            if constexpr (S == 4) cv[i][0] = *(const itq_v2_s *)(a.coef + rec[i].x);
+            else {
+#pragma unroll
+                for (int k = 0; k < NV; k++) cv[i][k] = *(const itq_v4_u *)(a.coef + rec[i].x + 8 * k);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NI; i++) {
+        if (!live[i]) continue;
+        uint32_t raw[S / 2];
+#pragma unroll
+        for (int k = 0; k < S / 2; k++) raw[k] = cv[i][k / (S == 4 ? 2 : 4)][k % (S == 4 ? 2 : 4)];
+        itdq_small_tb<LW, LH, IQT>(a, rec[i], raw, tmh, tmw, s16_mid);
+    }
+}
+
 // Sparsity masks (round 3): a coded block of a real stream holds a handful of non-zero coefficients at low frequencies.  Stage 0 records, per TB, which
 // coefficient ROW pairs and COLUMN pairs hold a non-zero value (LDS atomic OR, only for the few non-zero dwords); stage 1 then walks only the set row
 // pairs (union over the wave's TBs, a scalar bit loop - the matrix rows stay wave-uniform SGPR loads) and stage 2 only the set column pairs: a column
@@ -250,9 +293,16 @@ __device__ __forceinline__ void itdq_small(const ItdqArgs &a, const TbWave wv)
 // latency of its dependent loads, not by arithmetic.
 // The item is its chain of dependent round trips, so the requests come first: the TB records of all the lane's units are asked for before the mask reset and its barrier,
 // the coefficients of all units before the first dequantisation - two vector-memory waits between the item's first request and its first dot2.
-template <int LW, int LH, bool IQT>
-__device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, uint32_t *lds, uint32_t *s_tb)
+// NI = 2 (k_intra_itdq's residual side): two items of one class and one transform pair as ONE double-width item, in lockstep - each stage runs over both, each item
+// in its own LDS block (lds + i * ITDQ_ITEM_DWORDS) and its own per-TB arrays (s_tb + i * ITDQ_TB_DWORDS), the barriers and each matrix row pair's scalar load shared.
+// Four load units per lane in flight instead of two at the same number of waves (profiles/residual_item_pairs.txt).  The masks stay per TB of each item: the walk over
+// the row / column pairs takes the union of the two items' wave masks, and an item's products run only for the pairs of its own mask.
+template <bool IQT> constexpr int itdq_item_dwords() { return IQT ? ITDQ_LDS_DWORDS - ITDQ_PLANES_DWORDS / 2 : ITDQ_LDS_DWORDS; }
+template <int LW, int LH, bool IQT, int NI = 1>
+__device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave (&wv)[NI], uint32_t *lds, uint32_t *s_tb, const int tid)
 {
+    static_assert(NI == 1 || NI == 2, "an item, or a pair of one class and one transform pair");
+    constexpr int ITEM = itdq_item_dwords<IQT>();
     constexpr int W = 1 << LW, H = 1 << LH;
     constexpr int N1 = H > 16 ? 16 : H, C1 = H / N1;          // stage-1 outputs per lane, chunks
     constexpr int N2 = W > 16 ? 16 : W, C2 = W / N2;
@@ -263,201 +313,299 @@ __device__ __forceinline__ void itdq_item(const ItdqArgs &a, const TbWave wv, ui
     static_assert(2 * PLANE <= ITDQ_PLANES_DWORDS && G * W * H <= 4096 && G <= ITDQ_MAX_G, "LDS budget");
     constexpr int PLANES_DWORDS = IQT ? ITDQ_PLANES_DWORDS / 2 : ITDQ_PLANES_DWORDS;
     constexpr bool RMASK = H >= 16, CMASK = W >= 16;          // shorter transforms: the masks would cost more than the 2..4 loop rounds they can save
-    uint32_t *s_rm = s_tb, *s_cm = s_tb + ITDQ_MAX_G, *s_rec = s_tb + 2 * ITDQ_MAX_G;      // per TB: the two masks, its record (two dwords)
-    const int t = threadIdx.x;
+    uint32_t *s_rm[NI], *s_cm[NI], *s_rec[NI];               // per TB: the two masks, its record (two dwords)
+#pragma unroll
+    for (int i = 0; i < NI; i++) { s_rm[i] = s_tb + i * ITDQ_TB_DWORDS; s_cm[i] = s_rm[i] + ITDQ_MAX_G; s_rec[i] = s_rm[i] + 2 * ITDQ_MAX_G; }
+    const int t = tid;
 
     // ------------------------------------------------ stage 0: load + dequantise ---------------------------
     // all coefficients of the G blocks in one coalesced sweep, dequantised once (ItdqScale) and parked in LDS as s16.  A lane has one or two load units (8 samples;
     // 4 for 2x2): both units' records, then both units' coefficients are in flight together; a unit past the item's count forms no address.
     constexpr int S = W * H, UN = S >= 8 ? 8 : 4, NU = G * S / UN, NR = (NU + 255) / 256;
     typedef typename std::conditional<UN == 8, itq_v4, itq_v2>::type cvec;
-    bool on[NR];
+    bool on[NI][NR];
     int up[NR], uo[NR];
-    itq_v2 rec[NR];
+    itq_v2 rec[NI][NR];
 #pragma unroll
     for (int r = 0; r < NR; r++) {
         const int u = t + 256 * r;
         up[r] = (u * UN) / S; uo[r] = (u * UN) % S;
-        on[r] = (NU % 256 == 0 || u < NU) && up[r] < wv.count;
-        rec[r] = itq_any<itq_v2>();
-        itq_rec_if(rec[r], a.tbs + wv.first + up[r], on[r]);
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            on[i][r] = (NU % 256 == 0 || u < NU) && up[r] < wv[i].count;
+            rec[i][r] = itq_any<itq_v2>();
+            itq_rec_if(rec[i][r], a.tbs + wv[i].first + up[r], on[i][r]);
+        }
     }
     if (RMASK || CMASK) {
-        if (t < G) { s_rm[t] = 0; s_cm[t] = 0; }
+        if (t < G) {
+#pragma unroll
+            for (int i = 0; i < NI; i++) { s_rm[i][t] = 0; s_cm[i][t] = 0; }
+        }
         __syncthreads();
     }
-    const uint32_t *tmh = itdq_matrix<LH>(wv.tr_v), *tmw = itdq_matrix<LW>(wv.tr_h);
-    const bool s16_mid = IQT || wv.tr_v != TR_DCT2 || wv.tr_h != TR_DCT2;     // ATS keeps a clipped s16 intermediate like IQT (:406-421)
+    const uint32_t *tmh = itdq_matrix<LH>(wv[0].tr_v), *tmw = itdq_matrix<LW>(wv[0].tr_h);
+    const bool s16_mid = IQT || wv[0].tr_v != TR_DCT2 || wv[0].tr_h != TR_DCT2;     // ATS keeps a clipped s16 intermediate like IQT (:406-421)
     asm volatile("" :: "s"(tmh), "s"(tmw));                    // the tables' addresses now, under the records' round trip, not in front of stage 1's first row
-    int16_t *ldsh = (int16_t *)lds;                            // plane 0: hi (or the IQT intermediate), plane 1: lo
-    int16_t *ldsl = (int16_t *)(lds + PLANE);
-    uint32_t *ldsc = lds + PLANES_DWORDS;                      // dequantised coefficients, [p][row][col] s16
-    cvec cv[NR];
+    cvec cv[NI][NR];
+    // (a pair: every record here, for all lanes, before the first coefficient request.  Left to the requests' own branches, the wait for item B's record stood behind item
+    //  A's coefficient request - a lane that sat that one out cannot tell how many loads are ahead of it, so the wait was for all of them: a third round trip per pair)
+    if (NI > 1) __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0)
 #pragma unroll
-    for (int r = 0; r < NR; r++) {
-        cv[r] = itq_any<cvec>();
-        if (on[r]) {
-            // row-major TB with row stride 2^log2s (a sub-block of a >64 CU keeps the CU's stride, xevd_itdq.c:573-584)
-            const int16_t *src = a.coef + rec[r].x + ((uo[r] >> LW) << rec_log2s(rec[r])) + (uo[r] & (W - 1));
-            if constexpr (UN == 8) cv[r] = *(const itq_v4_u *)src; else cv[r] = *(const itq_v2_s *)src;
+    for (int i = 0; i < NI; i++) {
+#pragma unroll
+        for (int r = 0; r < NR; r++) {
+            cv[i][r] = itq_any<cvec>();
+            if (on[i][r]) {
+                // row-major TB with row stride 2^log2s (a sub-block of a >64 CU keeps the CU's stride, xevd_itdq.c:573-584)
+                const int16_t *src = a.coef + rec[i][r].x + ((uo[r] >> LW) << rec_log2s(rec[i][r])) + (uo[r] & (W - 1));
+                if constexpr (UN == 8) cv[i][r] = *(const itq_v4_u *)src; else cv[i][r] = *(const itq_v2_s *)src;
+            }
         }
     }
 #pragma unroll
-    for (int r = 0; r < NR; r++) {
-        if (!on[r]) continue;
-        const int p = up[r], o = uo[r];
-        const ItdqScale<(LW + LH) & 1, IQT> dq(rec_qp(rec[r]), a.bd, LW + LH);
-        if (o == 0) { s_rec[2 * p] = rec[r].x; s_rec[2 * p + 1] = rec[r].y; }      // for stage 2's lanes, which belong to other TBs than stage 0's: an LDS read, not a second fetch
-        uint32_t raw[UN / 2];
+    for (int i = 0; i < NI; i++) {
+        uint32_t *ldsc = lds + i * ITEM + PLANES_DWORDS;       // dequantised coefficients, [p][row][col] s16
 #pragma unroll
-        for (int i = 0; i < UN / 2; i++) raw[i] = cv[r][i];
+        for (int r = 0; r < NR; r++) {
+            if (!on[i][r]) continue;
+            const int p = up[r], o = uo[r];
+            const ItdqScale<(LW + LH) & 1, IQT> dq(rec_qp(rec[i][r]), a.bd, LW + LH);
+            if (o == 0) { s_rec[i][2 * p] = rec[i][r].x; s_rec[i][2 * p + 1] = rec[i][r].y; }      // for stage 2's lanes, which belong to other TBs than stage 0's: an LDS read, not a second fetch
+            uint32_t raw[UN / 2];
 #pragma unroll
-        for (int i = 0; i < UN / 2; i++) {
-            if (raw[i] == 0) continue;
-            raw[i] = pack16(dq((int16_t)(raw[i] & 0xFFFF)), dq((int16_t)(raw[i] >> 16)));
-            if (RMASK) atomicOr(&s_rm[p], 1u << ((o + 2 * i) >> (LW + 1)));                  // row pair of this dword
-            if (CMASK) atomicOr(&s_cm[p], 1u << (((o + 2 * i) & (W - 1)) >> 1));              // column pair
+            for (int k = 0; k < UN / 2; k++) raw[k] = cv[i][r][k];
+#pragma unroll
+            for (int k = 0; k < UN / 2; k++) {
+                if (raw[k] == 0) continue;
+                raw[k] = pack16(dq((int16_t)(raw[k] & 0xFFFF)), dq((int16_t)(raw[k] >> 16)));
+                if (RMASK) atomicOr(&s_rm[i][p], 1u << ((o + 2 * k) >> (LW + 1)));                  // row pair of this dword
+                if (CMASK) atomicOr(&s_cm[i][p], 1u << (((o + 2 * k) & (W - 1)) >> 1));              // column pair
+            }
+#pragma unroll
+            for (int k = 0; k < UN / 2; k++) ldsc[(p * S + o) / 2 + k] = raw[k];
         }
-#pragma unroll
-        for (int i = 0; i < UN / 2; i++) ldsc[(p * S + o) / 2 + i] = raw[i];
     }
     __syncthreads();
 
     // ------------------------------------------------ stage 1: columns ------------------------------------
-    uint32_t rows1 = 0;
-    if (RMASK) rows1 = wave_masks<G, LW>(s_rm, t);
+    uint32_t rows1[NI], rows1_any = 0;
+#pragma unroll
+    for (int i = 0; i < NI; i++) { rows1[i] = RMASK ? wave_masks<G, LW>(s_rm[i], t) : 0u; rows1_any |= rows1[i]; }
     if (t < G * W * C1) {
         const int idx = t % (G * W);
         int chunk = t / (G * W);
         if (UNI1) chunk = __builtin_amdgcn_readfirstlane(chunk);
         const int p = idx >> LW, j = idx & (W - 1);
-        const bool valid = p < wv.count;
-        const uint32_t vmask = valid ? 0xFFFFFFFFu : 0u;      // the LDS reads are unconditional (a TB past the count holds whatever was there): no branch with a wait of its own around them
-        const int16_t *src = (const int16_t *)ldsc + p * (W * H) + j;
-
-        int acc[N1];
+        bool valid[NI];
+        uint32_t vmask[NI];
+        const int16_t *src[NI];
+        int acc[NI][N1];
 #pragma unroll
-        for (int n = 0; n < N1; n++) acc[n] = 0;
+        for (int i = 0; i < NI; i++) {
+            valid[i] = p < wv[i].count;
+            vmask[i] = valid[i] ? 0xFFFFFFFFu : 0u;           // the LDS reads are unconditional (a TB past the count holds whatever was there): no branch with a wait of its own around them
+            src[i] = (const int16_t *)(lds + i * ITEM + PLANES_DWORDS) + p * (W * H) + j;
+#pragma unroll
+            for (int n = 0; n < N1; n++) acc[i][n] = 0;
+        }
         if (RMASK) {
-            for (uint32_t m = rows1; m; m &= m - 1) {          // the row pairs that hold a coefficient in one of this wave's TBs
+            for (uint32_t m = rows1_any; m; m &= m - 1) {      // the row pairs that hold a coefficient in one of this wave's TBs (of either item)
                 const int k2 = __builtin_ctz(m);
-                const uint32_t vp = pack16(src[(2 * k2) * W], src[(2 * k2 + 1) * W]) & vmask;
-                const uint32_t *row = tmh + k2 * H + chunk * N1;
+                uint32_t vp[NI];
 #pragma unroll
-                for (int n = 0; n < N1; n++) acc[n] = dot2(row[n], vp, acc[n]);
+                for (int i = 0; i < NI; i++) vp[i] = pack16(src[i][(2 * k2) * W], src[i][(2 * k2 + 1) * W]) & vmask[i];
+                uint32_t row[N1];
+                itq_row<N1, (NI > 1 && UNI1)>(row, tmh + k2 * H + chunk * N1);
+#pragma unroll
+                for (int i = 0; i < NI; i++) {
+                    if (NI > 1 && !((rows1[i] >> k2) & 1)) continue;      // the other item's row pair: nothing of this item's lies there
+#pragma unroll
+                    for (int n = 0; n < N1; n++) acc[i][n] = dot2(row[n], vp[i], acc[i][n]);
+                }
             }
         } else {
             for (int k2 = 0; k2 < H / 2; k2++) {
-                const uint32_t vp = pack16(src[(2 * k2) * W], src[(2 * k2 + 1) * W]) & vmask;
-                if (__ballot(vp != 0) == 0) continue;              // both coefficient rows zero across this wave
-                const uint32_t *row = tmh + k2 * H + chunk * N1;
+                uint32_t vp[NI];
+                bool go[NI], any = false;
 #pragma unroll
-                for (int n = 0; n < N1; n++) acc[n] = dot2(row[n], vp, acc[n]);
+                for (int i = 0; i < NI; i++) {
+                    vp[i] = pack16(src[i][(2 * k2) * W], src[i][(2 * k2 + 1) * W]) & vmask[i];
+                    go[i] = __ballot(vp[i] != 0) != 0;
+                    any |= go[i];
+                }
+                if (!any) continue;                                // both coefficient rows zero across this wave
+                uint32_t row[N1];
+                itq_row<N1, (NI > 1 && UNI1)>(row, tmh + k2 * H + chunk * N1);
+#pragma unroll
+                for (int i = 0; i < NI; i++) {
+                    if (NI > 1 && !go[i]) continue;
+#pragma unroll
+                    for (int n = 0; n < N1; n++) acc[i][n] = dot2(row[n], vp[i], acc[i][n]);
+                }
             }
         }
         // transposed store: element [p][row = chunk*N1+n][col = j] - only columns stage 2 will read (its column pair holds a coefficient)
         const int base = (p * H + chunk * N1) * (2 * RS) + j;
-        if (CMASK && !(valid && ((s_cm[p] >> (j >> 1)) & 1))) {
-        } else if (s16_mid) {
 #pragma unroll
-            for (int n = 0; n < N1; n++) ldsh[base + n * (2 * RS)] = (int16_t)clip16((acc[n] + 64) >> 7);   // xevdm_itdq.c ITX_SHIFT1 = 7
-        } else {
+        for (int i = 0; i < NI; i++) {
+            int16_t *ldsh = (int16_t *)(lds + i * ITEM);       // plane 0: hi (or the IQT intermediate), plane 1: lo
+            int16_t *ldsl = (int16_t *)(lds + i * ITEM + PLANE);
+            if (CMASK && !(valid[i] && ((s_cm[i][p] >> (j >> 1)) & 1))) {
+            } else if (s16_mid) {
 #pragma unroll
-            for (int n = 0; n < N1; n++) {
-                ldsh[base + n * (2 * RS)] = (int16_t)(acc[n] >> 15);          // |acc| < 2^28 -> hi in s16 range
-                ldsl[base + n * (2 * RS)] = (int16_t)(acc[n] & 0x7FFF);
+                for (int n = 0; n < N1; n++) ldsh[base + n * (2 * RS)] = (int16_t)clip16((acc[i][n] + 64) >> 7);   // xevdm_itdq.c ITX_SHIFT1 = 7
+            } else {
+#pragma unroll
+                for (int n = 0; n < N1; n++) {
+                    ldsh[base + n * (2 * RS)] = (int16_t)(acc[i][n] >> 15);          // |acc| < 2^28 -> hi in s16 range
+                    ldsl[base + n * (2 * RS)] = (int16_t)(acc[i][n] & 0x7FFF);
+                }
             }
         }
     }
     __syncthreads();
 
     // ------------------------------------------------ stage 2: rows ---------------------------------------
-    uint32_t cols2 = 0;
-    if (CMASK) cols2 = wave_masks<G, LH>(s_cm, t);
+    uint32_t cols2[NI], cols2_any = 0;
+#pragma unroll
+    for (int i = 0; i < NI; i++) { cols2[i] = CMASK ? wave_masks<G, LH>(s_cm[i], t) : 0u; cols2_any |= cols2[i]; }
     if (t < G * H * C2) {
         const int idx = t % (G * H);
         int chunk = t / (G * H);
         if (UNI2) chunk = __builtin_amdgcn_readfirstlane(chunk);
         const int p = idx >> LH, r = idx & (H - 1);
-        if (p >= wv.count) return;
-        // a column pair outside this TB's own mask was not written by stage 1 (it may be set for another TB of the wave): reads as zero
-        const uint32_t own = CMASK ? s_cm[p] : 0xFFFFFFFFu;
-        itq_v2 tb;
-        tb.x = s_rec[2 * p]; tb.y = s_rec[2 * p + 1];
+        bool live[NI], any_live = false;
+#pragma unroll
+        for (int i = 0; i < NI; i++) { live[i] = p < wv[i].count; any_live |= live[i]; }
+        if (!any_live) return;
+        // a column pair outside this TB's own mask was not written by stage 1 (it may be set for another TB of the wave): reads as zero.  (A pair's lane whose TB only
+        // one of the two items has runs the other item's products on zeros and stores nothing for it.)
+        uint32_t own[NI];
+        itq_v2 tb[NI];
+        const uint32_t *inh[NI], *inl[NI];
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            own[i] = CMASK ? s_cm[i][p] : 0xFFFFFFFFu;
+            if (NI > 1 && !live[i]) own[i] = 0;
+            tb[i].x = s_rec[i][2 * p]; tb[i].y = s_rec[i][2 * p + 1];
+            inh[i] = lds + i * ITEM + (p * H + r) * RS;
+            inl[i] = inh[i] + PLANE;
+        }
         const int shift2 = s16_mid ? 12 - (a.bd - 8) : 7 + 12 - (a.bd - 8);
-        const uint32_t *inh = lds + (p * H + r) * RS;
-        const uint32_t *inl = inh + PLANE;
-        int res[N2];
+        int res[NI][N2];
         if (s16_mid) {
-            int s[N2];
+            int s[NI][N2];
 #pragma unroll
-            for (int n = 0; n < N2; n++) s[n] = 1 << (shift2 - 1);
+            for (int i = 0; i < NI; i++)
+#pragma unroll
+                for (int n = 0; n < N2; n++) s[i][n] = 1 << (shift2 - 1);
             if (CMASK) {
-                for (uint32_t m = cols2; m; m &= m - 1) {
+                for (uint32_t m = cols2_any; m; m &= m - 1) {
                     const int k2 = __builtin_ctz(m);
-                    const uint32_t vp = inh[k2] & (0u - ((own >> k2) & 1));
-                    const uint32_t *row = tmw + k2 * W + chunk * N2;
+                    uint32_t vp[NI];
 #pragma unroll
-                    for (int n = 0; n < N2; n++) s[n] = dot2(row[n], vp, s[n]);
+                    for (int i = 0; i < NI; i++) vp[i] = inh[i][k2] & (0u - ((own[i] >> k2) & 1));
+                    uint32_t row[N2];
+                    itq_row<N2, (NI > 1 && UNI2)>(row, tmw + k2 * W + chunk * N2);
+#pragma unroll
+                    for (int i = 0; i < NI; i++) {
+                        if (NI > 1 && !((cols2[i] >> k2) & 1)) continue;      // the other item's column pair
+#pragma unroll
+                        for (int n = 0; n < N2; n++) s[i][n] = dot2(row[n], vp[i], s[i][n]);
+                    }
                 }
             } else {
                 for (int k2 = 0; k2 < W / 2; k2++) {
-                    const uint32_t vp = inh[k2];
-                    if (__ballot(vp != 0) == 0) continue;
-                    const uint32_t *row = tmw + k2 * W + chunk * N2;
+                    uint32_t vp[NI];
+                    bool go[NI], any = false;
 #pragma unroll
-                    for (int n = 0; n < N2; n++) s[n] = dot2(row[n], vp, s[n]);
+                    for (int i = 0; i < NI; i++) {
+                        vp[i] = inh[i][k2] & (0u - ((own[i] >> k2) & 1));      // (own is all ones here, but for a lane of a pair whose TB this item does not have)
+                        go[i] = __ballot(vp[i] != 0) != 0;
+                        any |= go[i];
+                    }
+                    if (!any) continue;
+                    uint32_t row[N2];
+                    itq_row<N2, (NI > 1 && UNI2)>(row, tmw + k2 * W + chunk * N2);
+#pragma unroll
+                    for (int i = 0; i < NI; i++) {
+                        if (NI > 1 && !go[i]) continue;
+#pragma unroll
+                        for (int n = 0; n < N2; n++) s[i][n] = dot2(row[n], vp[i], s[i][n]);
+                    }
                 }
             }
 #pragma unroll
-            for (int n = 0; n < N2; n++) res[n] = clip16(s[n] >> shift2);
-        } else {
-            int sh[N2], sl[N2];
+            for (int i = 0; i < NI; i++)
 #pragma unroll
-            for (int n = 0; n < N2; n++) { sh[n] = 0; sl[n] = 0; }
+                for (int n = 0; n < N2; n++) res[i][n] = clip16(s[i][n] >> shift2);
+        } else {
+            int sh[NI][N2], sl[NI][N2];
+#pragma unroll
+            for (int i = 0; i < NI; i++)
+#pragma unroll
+                for (int n = 0; n < N2; n++) { sh[i][n] = 0; sl[i][n] = 0; }
             if (CMASK) {
-                for (uint32_t m = cols2; m; m &= m - 1) {
+                for (uint32_t m = cols2_any; m; m &= m - 1) {
                     const int k2 = __builtin_ctz(m);
-                    const uint32_t mine = 0u - ((own >> k2) & 1);
-                    const uint32_t vh = inh[k2] & mine, vl = inl[k2] & mine;
                     const uint32_t *row = tmw + k2 * W + chunk * N2;
 #pragma unroll
-                    for (int n = 0; n < N2; n++) { sh[n] = dot2(row[n], vh, sh[n]); sl[n] = dot2(row[n], vl, sl[n]); }
+                    for (int i = 0; i < NI; i++) {
+                        const uint32_t mine = 0u - ((own[i] >> k2) & 1);
+                        const uint32_t vh = inh[i][k2] & mine, vl = inl[i][k2] & mine;
+#pragma unroll
+                        for (int n = 0; n < N2; n++) { sh[i][n] = dot2(row[n], vh, sh[i][n]); sl[i][n] = dot2(row[n], vl, sl[i][n]); }
+                    }
                 }
             } else {
                 for (int k2 = 0; k2 < W / 2; k2++) {
-                    const uint32_t vh = inh[k2], vl = inl[k2];
-                    if (__ballot((vh | vl) != 0) == 0) continue;
+                    uint32_t vh[NI], vl[NI], nz = 0;
+#pragma unroll
+                    for (int i = 0; i < NI; i++) {
+                        const uint32_t mine = 0u - ((own[i] >> k2) & 1);
+                        vh[i] = inh[i][k2] & mine; vl[i] = inl[i][k2] & mine;
+                        nz |= vh[i] | vl[i];
+                    }
+                    if (__ballot(nz != 0) == 0) continue;
                     const uint32_t *row = tmw + k2 * W + chunk * N2;
 #pragma unroll
-                    for (int n = 0; n < N2; n++) { sh[n] = dot2(row[n], vh, sh[n]); sl[n] = dot2(row[n], vl, sl[n]); }
+                    for (int i = 0; i < NI; i++)
+#pragma unroll
+                        for (int n = 0; n < N2; n++) { sh[i][n] = dot2(row[n], vh[i], sh[i][n]); sl[i][n] = dot2(row[n], vl[i], sl[i][n]); }
                 }
             }
             const long long add = 1ll << (shift2 - 1);
 #pragma unroll
-            for (int n = 0; n < N2; n++) {
-                const long long s = (long long)sh[n] * 32768 + sl[n] + add;     // == the reference's s64 sum + rounding offset
-                res[n] = (int)min(max(s >> shift2, -32768ll), 32767ll);
-            }
-        }
-        int16_t *out = a.resid + tb.x + (r << rec_log2s(tb)) + chunk * N2;
-        if constexpr (N2 >= 8) {
+            for (int i = 0; i < NI; i++)
 #pragma unroll
-            for (int n = 0; n < N2; n += 8) {
-                uint4 v;
-                v.x = pack16(res[n + 0], res[n + 1]);
-                v.y = pack16(res[n + 2], res[n + 3]);
-                v.z = pack16(res[n + 4], res[n + 5]);
-                v.w = pack16(res[n + 6], res[n + 7]);
-                *(uint4 *)(out + n) = v;
+                for (int n = 0; n < N2; n++) {
+                    const long long s = (long long)sh[i][n] * 32768 + sl[i][n] + add;     // == the reference's s64 sum + rounding offset
+                    res[i][n] = (int)min(max(s >> shift2, -32768ll), 32767ll);
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            if (NI > 1 && !live[i]) continue;
+            int16_t *out = a.resid + tb[i].x + (r << rec_log2s(tb[i])) + chunk * N2;
+            if constexpr (N2 >= 8) {
+#pragma unroll
+                for (int n = 0; n < N2; n += 8) {
+                    uint4 v;
+                    v.x = pack16(res[i][n + 0], res[i][n + 1]);
+                    v.y = pack16(res[i][n + 2], res[i][n + 3]);
+                    v.z = pack16(res[i][n + 4], res[i][n + 5]);
+                    v.w = pack16(res[i][n + 6], res[i][n + 7]);
+                    *(uint4 *)(out + n) = v;
+                }
+            } else if constexpr (N2 == 4) {
+                uint2 v;
+                v.x = pack16(res[i][0], res[i][1]);
+                v.y = pack16(res[i][2], res[i][3]);
+                *(uint2 *)out = v;
+            } else {
+                *(uint32_t *)out = pack16(res[i][0], res[i][1]);
             }
-        } else if constexpr (N2 == 4) {
-            uint2 v;
-            v.x = pack16(res[0], res[1]);
-            v.y = pack16(res[2], res[3]);
-            *(uint2 *)out = v;
-        } else {
-            *(uint32_t *)out = pack16(res[0], res[1]);
         }
     }
 }
@@ -470,14 +618,56 @@ __device__ __forceinline__ void itdq_dispatch(const ItdqArgs &a, int wi, uint32_
     static_assert(sizeof(TbWave) == 12 && alignof(TbWave) == 4, "TbWave is read as three dwords");
     const uint32_t *w = (const uint32_t *)(a.waves + wi);
     const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-    TbWave wv;
-    wv.first = w0; wv.count = (uint16_t)(w1 & 0xFFFF); wv.log2w = (uint8_t)(w1 >> 16); wv.log2h = (uint8_t)(w1 >> 24); wv.tr_v = (uint8_t)w2; wv.tr_h = (uint8_t)(w2 >> 8);
-#define CASE(lw, lh) case (lw) * 8 + (lh): if constexpr ((lw) + (lh) <= 4) itdq_small<lw, lh, IQT>(a, wv); else itdq_item<lw, lh, IQT>(a, wv, lds, s_tb); break;
+    TbWave wv[1];
+    wv[0].first = w0; wv[0].count = (uint16_t)(w1 & 0xFFFF); wv[0].log2w = (uint8_t)(w1 >> 16); wv[0].log2h = (uint8_t)(w1 >> 24); wv[0].tr_v = (uint8_t)w2; wv[0].tr_h = (uint8_t)(w2 >> 8);
+#define CASE(lw, lh) case (lw) * 8 + (lh): if constexpr ((lw) + (lh) <= 4) itdq_small<lw, lh, IQT>(a, wv, threadIdx.x); else itdq_item<lw, lh, IQT>(a, wv, lds, s_tb, threadIdx.x); break;
 #define ROW(lw) CASE(lw, 1) CASE(lw, 2) CASE(lw, 3) CASE(lw, 4) CASE(lw, 5) CASE(lw, 6)
-    switch (wv.log2w * 8 + wv.log2h) {
+    switch (wv[0].log2w * 8 + wv[0].log2h) {
         ROW(1) ROW(2) ROW(3) ROW(4) ROW(5) ROW(6)
         default: break;
     }
 #undef ROW
 #undef CASE
+}
+
+// Two adjacent entries of the item list, waves[e0] and [e0 + 1], in one workgroup (n = 2; n = 1: the entry e0 alone, in the single form): as one double-width item where they have the same class and the same transform
+// pair (the class-sorted list makes that the rule), else - and for an odd last entry - the single form, one entry after the other, each in its own LDS block.  Every entry
+// is done exactly once.  lds = 2 x itdq_item_dwords<IQT>() dwords, s_tb = 2 x ITDQ_TB_DWORDS; all 256 threads of the workgroup call it.
+template <bool IQT>
+__device__ __forceinline__ void itdq_dispatch_pair(const ItdqArgs &a, int e0, int n, uint32_t *lds, uint32_t *s_tb)
+{
+    // both records as scalar loads together (an odd last entry reads itself twice: no address past the list)
+    const bool two = n == 2 && e0 + 1 < a.n_waves;
+    const uint32_t *w = (const uint32_t *)(a.waves + e0), *x = (const uint32_t *)(a.waves + e0 + (two ? 1 : 0));
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], x0 = x[0], x1 = x[1], x2 = x[2];
+    TbWave wv[2];
+    wv[0].first = w0; wv[0].count = (uint16_t)(w1 & 0xFFFF); wv[0].log2w = (uint8_t)(w1 >> 16); wv[0].log2h = (uint8_t)(w1 >> 24); wv[0].tr_v = (uint8_t)w2; wv[0].tr_h = (uint8_t)(w2 >> 8);
+    wv[1].first = x0; wv[1].count = (uint16_t)(x1 & 0xFFFF); wv[1].log2w = (uint8_t)(x1 >> 16); wv[1].log2h = (uint8_t)(x1 >> 24); wv[1].tr_v = (uint8_t)x2; wv[1].tr_h = (uint8_t)(x2 >> 8);
+#define ROW(lw) CASE(lw, 1) CASE(lw, 2) CASE(lw, 3) CASE(lw, 4) CASE(lw, 5) CASE(lw, 6)
+    if (two && (w1 >> 16) == (x1 >> 16) && (w2 & 0xFFFFu) == (x2 & 0xFFFFu)) {
+#define CASE(lw, lh) case (lw) * 8 + (lh): if constexpr ((lw) + (lh) <= 4) itdq_small<lw, lh, IQT, 2>(a, wv, threadIdx.x); else itdq_item<lw, lh, IQT, 2>(a, wv, lds, s_tb, threadIdx.x); break;
+        switch (wv[0].log2w * 8 + wv[0].log2h) {
+            ROW(1) ROW(2) ROW(3) ROW(4) ROW(5) ROW(6)
+            default: break;
+        }
+#undef CASE
+        return;
+    }
+#pragma unroll 1
+    for (int k = 0; k < (two ? 2 : 1); k++) {
+        TbWave one[1];
+        one[0] = k ? wv[1] : wv[0];
+        // (the lane's index behind a fence: left visible, everything the 36 classes derive from it is invariant in this loop and gets hoisted in front of it - 250 VGPRs)
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        __builtin_assume(t >= 0 && t < 256);
+        uint32_t *lds_k = lds + k * itdq_item_dwords<IQT>(), *s_tb_k = s_tb + k * ITDQ_TB_DWORDS;
+#define CASE(lw, lh) case (lw) * 8 + (lh): if constexpr ((lw) + (lh) <= 4) itdq_small<lw, lh, IQT>(a, one, t); else itdq_item<lw, lh, IQT>(a, one, lds_k, s_tb_k, t); break;
+        switch (one[0].log2w * 8 + one[0].log2h) {
+            ROW(1) ROW(2) ROW(3) ROW(4) ROW(5) ROW(6)
+            default: break;
+        }
+#undef CASE
+    }
+#undef ROW
 }

@@ -760,7 +760,8 @@ __global__ __launch_bounds__(64 * INTRA_WAVES) void k_intra(const IntraArgs a)
 // k_intra_itdq - the data-flow launch of this picture and the residual pass of the NEXT picture in one grid.  The data-flow kernel is a chain of
 // dependent memory round trips (4 K waves at 8K, the SIMDs idle most of its 45 us) and the residual pass depends on nothing but its batch, so its
 // work items fill the machine under the chain: workgroups [0, n_intra_wg) run intra_body (tickets order them, whatever the dispatcher does), the rest
-// one residual work item each.  256 threads: the residual pass's workgroup shape; four CUs in flight per intra workgroup (18.6 KB of LDS either way).
+// one residual work item each (two in an IQT sequence with a long list, below).  256 threads: the residual pass's workgroup shape; four CUs in flight per intra
+// workgroup (18.6 KB of LDS for the chain; the IQT instantiations hold two residual items' blocks, 35.8 KB).
 // Measured at 8K (profiles/round3_*): 45 us + 39 us as two launches (43 + 55 when the residual pass ran beside the level-1 launch on a second stream,
 // with two cross-stream event waits of 6 us each), 64 us as one.  (Letting the level-1 launch carry a share of the work items too - it is 23 us of memory latency
 // as well - measured nothing at 25 % and 1 - 3 % slower at 35 - 70 %: that launch is short and dense enough to be slowed down by the company.)
@@ -772,14 +773,30 @@ __global__ __launch_bounds__(64 * INTRA_WAVES) void k_intra(const IntraArgs a)
 //  chain lost its first vector round trip (the item's record, now scalar loads), stage 2's second fetch of the TB records (LDS) and the six ds_bpermute of each mask union; 2001 of cfg4's
 //  7531 items (blocks of up to 16 samples) run without LDS and barriers: 60.7 -> 52.3 us at cfg4 in rocprofv3.  The share of the grid the chain is spread over, measured again
 //  behind the shorter pass, 25 / 35 / 50 / 65 / 75 %: ms per picture 0.2999 / 0.2966 / 0.2972 / 0.2993 / 0.3035 (three alternating runs each, spread of one build 0.005) - one half stays.)
+// (Two entries of the item list per residual workgroup in the IQT instantiations since profiles/residual_item_pairs.txt: itdq_dispatch_pair runs two items of one class and
+//  one transform pair in lockstep - both records, then both items' TB records, then both items' coefficients in flight together, the barriers and each matrix row pair's
+//  scalar load shared - in two LDS blocks of 17.9 KB (35.8 KB per workgroup: four workgroups per CU still fit), at the chain side's VGPR count.  The pass is NOT the pure
+//  chain of round trips the pairing was estimated on: the pair's waves live 1.8 times as long as a single item's, not 1.3 times - the counters show the same instructions per
+//  item and most of a wave's life spent among them, not in s_waitcnt - so the launch went 52.4 -> 49.3 us at cfg4, not to the ~38 us of the estimate; lists of fewer than itdq_pair_min entries keep one entry per workgroup (launch_intra).  Baseline keeps one item
+//  per workgroup: two of its 27 KB blocks would halve the workgroups per CU.)
 #define FUSED_WAVES 4
 // (Round 5: the residual pass alone needs 44 VGPRs, this kernel 121 - 145 because of the chain's side, so the pass rides at half its own occupancy.  Holding the kernel to
 //  96 / 80 / 64 VGPRs (amdgpu_waves_per_eu 5 / 6 / 8: 72 / 172 / 236 bytes of scratch, all in the chain's side) measured 3035 / 2740 / 2602 frames/s against 3052 at 8K, 8050 /
 //  6820 / 6300 against 8600 at 4K: the launch is as long as its chain, and spills lengthen every link of it.  tools/archive/r5_w.sh)
+#ifndef ITDQ_PAIRS           // 0: every residual workgroup takes one entry of the item list, as before profiles/residual_item_pairs.txt (measurement builds)
+#define ITDQ_PAIRS 1
+#endif
+#ifndef FUSED_SPAN_PCT       // share of the grid the chain's workgroups are spread over (measurement builds)
+#define FUSED_SPAN_PCT 50
+#endif
+// entries of the item list per residual workgroup: the IQT instantiations take two (itdq_dispatch_pair); Baseline's 27 KB per item would halve the workgroups per CU
+constexpr int fused_items(bool iqt) { return iqt && ITDQ_PAIRS ? 2 : 1; }
 template <int EIPD, bool IBC, bool IQT>
-__global__ __launch_bounds__(64 * FUSED_WAVES) void k_intra_itdq(const IntraArgs a, const ItdqArgs r, uint32_t n_intra_wg, uint64_t rate)
+__global__ __launch_bounds__(64 * FUSED_WAVES) void k_intra_itdq(const IntraArgs a, const ItdqArgs r, uint32_t n_intra_wg, uint64_t rate, uint32_t per_wg)
 {
-    constexpr int ITDQ_DW = (IQT ? ITDQ_LDS_DWORDS - ITDQ_PLANES_DWORDS / 2 : ITDQ_LDS_DWORDS) + ITDQ_TB_DWORDS, INTRA_DW = (FUSED_WAVES * IntraLds<false>::WAVE + 1) / 2 + 4;
+    constexpr int NI = fused_items(IQT);
+    constexpr int ITDQ_DW = NI * (itdq_item_dwords<IQT>() + ITDQ_TB_DWORDS), INTRA_DW = (FUSED_WAVES * IntraLds<false>::WAVE + 1) / 2 + 4;
+    static_assert(!IQT || 4 * ITDQ_DW <= 40 * 1024, "four workgroups per CU in 160 KB of LDS");
     __shared__ __attribute__((aligned(16))) uint32_t raw[ITDQ_DW > INTRA_DW ? ITDQ_DW : INTRA_DW];
     // The chain's workgroups are spread evenly over the first `span` blocks of the grid (the host passes half of it) instead of all in front: the list is sorted by
     // level and tickets are drawn in the order the workgroups start, so a level's CUs arrive about when the level before them is done - in front, 4 400 waves that
@@ -795,9 +812,23 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_intra_itdq(const IntraArgs
         intra_body<true, EIPD, IBC, false, FUSED_WAVES>(a, blockIdx.x, (int16_t *)raw, raw + INTRA_DW - 1);
     } else {
         const int wi = (int)(blockIdx.x - before);
-        if (wi >= r.n_waves) return;
-        itdq_dispatch<IQT>(r, wi, raw, raw + ITDQ_DW - ITDQ_TB_DWORDS);
+        if (wi >= (r.n_waves + (int)per_wg - 1) / (int)per_wg) return;
+        if constexpr (NI == 2) itdq_dispatch_pair<IQT>(r, wi * (int)per_wg, (int)per_wg, raw, raw + ITDQ_DW - 2 * ITDQ_TB_DWORDS);
+        else itdq_dispatch<IQT>(r, wi, raw, raw + ITDQ_DW - ITDQ_TB_DWORDS);
     }
+}
+
+// the pair form alone, one workgroup per two entries of the item list (xgpu_test_itdq_pairs: the tests reach every class and the sequential path without a picture)
+__global__ __launch_bounds__(256) void k_itdq_pairs(const ItdqArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t raw[2 * (itdq_item_dwords<true>() + ITDQ_TB_DWORDS)];
+    const int pi = blockIdx.x;
+    if (pi >= (a.n_waves + 1) / 2) return;
+    itdq_dispatch_pair<true>(a, 2 * pi, 2, raw, raw + 2 * itdq_item_dwords<true>());
+}
+void launch_itdq_pairs(xgpu_ctx *c, const ItdqArgs &a, hipStream_t s)
+{
+    if (a.n_waves > 0) hipLaunchKernelGGL(k_itdq_pairs, dim3((a.n_waves + 1) / 2), dim3(256), 0, s, a);
 }
 
 void upload_transform_tables_intra(const int *tm, const int16_t *ats, hipStream_t s) { upload_transform_tables_tu(tm, ats, s); }
@@ -810,13 +841,17 @@ void launch_intra(xgpu_ctx *c, const IntraArgs &a, bool dep, bool ibc, bool htdf
     right = right && c->sp.tool_eipd;                   // (the Baseline predictors have no right-hand form)
     if (next) {
         const uint32_t n_wg = (uint32_t)((a.count + FUSED_WAVES - 1) / FUSED_WAVES);
-        const dim3 g(n_wg + (uint32_t)next->n_waves), b(64 * FUSED_WAVES);
+        // entries of the item list per residual workgroup: two where the pass is the long pole of the launch.  At cfg4 (7531 items: seven rounds of the 1024 workgroups 256 CUs hold)
+        // pairs shorten the launch 52.4 -> 49.3 us; at cfg3 (4K, a quarter of the items: the launch is as long as its chain) they made the step 1.2 us LONGER (0.1059 -> 0.1072 ms,
+        // profiles/residual_item_pairs.txt), so lists below c->itdq_pair_min (4096 = four rounds; XEVD_HIP_ITDQ_PAIR_MIN, the GPU tests run small pictures with 1) keep one.
+        const uint32_t per_wg = next->n_waves >= c->itdq_pair_min ? (uint32_t)fused_items(next->iqt != 0) : 1u;
+        const dim3 g(n_wg + ((uint32_t)next->n_waves + per_wg - 1) / per_wg), b(64 * FUSED_WAVES);
         // the chain's workgroups spread evenly over the first half of the grid (k_intra_itdq)
-        const uint32_t span = std::max(n_wg, g.x / 2);
+        const uint32_t span = std::max(n_wg, (uint32_t)((uint64_t)g.x * FUSED_SPAN_PCT / 100));
         const uint64_t rate = (((uint64_t)n_wg << 32) + span - 1) / span;      // <= 2^32: every chain workgroup 0 .. n_wg - 1 is some block's, in order, inside the first `span` blocks
         // (fewer workgroups per CU by dynamic LDS, so that the pass leaves the chain's round trips more room: 4 / 3 / 2 per CU = 3166 / 3024 / 2800 frames/s at 8K, 8718 / 8607 / 8500
         //  at 4K - the launch needs the pass's occupancy as much as the chain's latency)
-#define LAUNCHF(E, I) do { if (next->iqt) hipLaunchKernelGGL((k_intra_itdq<E, I, true>), g, b, 0, c->stream, a, *next, n_wg, rate); else hipLaunchKernelGGL((k_intra_itdq<E, I, false>), g, b, 0, c->stream, a, *next, n_wg, rate); } while (0)
+#define LAUNCHF(E, I) do { if (next->iqt) hipLaunchKernelGGL((k_intra_itdq<E, I, true>), g, b, 0, c->stream, a, *next, n_wg, rate, per_wg); else hipLaunchKernelGGL((k_intra_itdq<E, I, false>), g, b, 0, c->stream, a, *next, n_wg, rate, per_wg); } while (0)
         if (right) LAUNCHF(2, true);
         else if (c->sp.tool_eipd) { if (ibc) LAUNCHF(1, true); else LAUNCHF(1, false); }
         else                 { if (ibc) LAUNCHF(0, true); else LAUNCHF(0, false); }

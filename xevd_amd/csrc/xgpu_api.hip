@@ -123,6 +123,7 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
     c->builder_threads = 1;
     c->err[0] = 0; c->timing = 0; c->have_frame = 0; c->side_pic = -1; c->d_maps = NULL; c->d_dra = NULL; c->d_cm = NULL; c->cm_tab = NULL; c->d_ctb_flag = NULL; c->stream = 0; c->up_stream = 0; c->down_stream = 0; c->side_stream = 0; c->after_inter = 0; c->have_after_inter = 0; c->where = 0; c->addb_pending = 0;
     c->fork_ev = c->join_ev = 0;
+    c->itdq_pair_min = getenv("XEVD_HIP_ITDQ_PAIR_MIN") ? std::max(1, atoi(getenv("XEVD_HIP_ITDQ_PAIR_MIN"))) : 4096;      // (k_intra.hip: launch_intra; read per context, tests set 1)
     c->intra_small_min = getenv("XEVD_HIP_INTRA_SMALL_MIN") ? std::max(1, atoi(getenv("XEVD_HIP_INTRA_SMALL_MIN"))) : 2048;      // (k_intra.hip: launch_intra; read per context, tests set 1)
     c->addb_scalar = getenv("XEVD_HIP_ADDB_SCALAR") != NULL;
     c->dmvr_scalar = getenv("XEVD_HIP_DMVR_SCALAR") != NULL;

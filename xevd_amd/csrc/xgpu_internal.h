@@ -394,6 +394,7 @@ struct xgpu_ctx {
     int             pad_done;          // the padding of the current picture has been written (by k_alf's border tiles): xgpu_pad launches nothing
     int             where;             // 0: the picture being built lives in its DPB slot, 1: in the scratch picture
     int             order_rl;          // a batch of the picture has CUs decoded after their right-hand neighbours (xgpu_dbatch.order_rl): k_dbk's order-aware instantiation
+    int             itdq_pair_min;     // data-flow launches that carry a residual pass of at least this many work items (IQT) give a residual workgroup two of them (k_intra_itdq; XEVD_HIP_ITDQ_PAIR_MIN, default 4096)
     int             intra_small_min;   // level-1 launches with at least this many CUs of at most 16 SCUs give those 16 lanes each (k_intra_l1; XEVD_HIP_INTRA_SMALL_MIN, default 2048)
     int             addb_scalar;                       // XEVD_HIP_ADDB_SCALAR: the scalar line filters (the > 10-bit instantiation) at every bit depth - read per context, tests set it
     int             dmvr_scalar;                       // XEVD_HIP_DMVR_SCALAR: k_dmvr's scalar form of the refined prediction for every sub-block - read per context, tests set it
@@ -457,6 +458,7 @@ private:
 
 // kernel launchers (one per .hip file)
 void launch_itdq(xgpu_ctx *c, const ItdqArgs &a, hipStream_t s);
+void launch_itdq_pairs(xgpu_ctx *c, const ItdqArgs &a, hipStream_t s);      // IQT only: two entries of the item list per workgroup, as k_intra_itdq's residual side takes them (k_intra.hip)
 void launch_inter(xgpu_ctx *c, const InterArgs &a);      // k_inter on the ctx stream
 void launch_test_recon(xgpu_ctx *c, const int16_t *coef, const int16_t *pred, int is_coef, int cuw, int cuh, int16_t *rec, int s_rec, int bd);
 void launch_test_dbk(xgpu_ctx *c, int16_t *buf, int16_t *buf_v, int st, int st_v, int stride, int bd, int hor, int chroma);

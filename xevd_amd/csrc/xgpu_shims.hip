@@ -109,6 +109,57 @@ int xgpu_test_itdq_ex(xgpu_ctx *c, int16_t *coef, int n_blocks, int log2w, int l
 int xgpu_test_itdq(xgpu_ctx *c, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth)
 { return xgpu_test_itdq_ex(c, coef, n_blocks, log2w, log2h, qp, bit_depth, TR_DCT2, TR_DCT2, log2w); }
 
+// Groups of blocks, each of one size class and one transform pair, through launch_itdq_pairs (two entries of the item list per workgroup, as k_intra_itdq's residual side
+// takes them): a group's blocks lie back to back from the next multiple of 64 samples behind the group before it, the item list is cut group by group, so entries of different groups meet in one workgroup wherever a group has an odd
+// number of entries.  The residual arena is filled with 0x5A5A first and comes back whole: an entry nobody ran, and the samples outside a block's columns, read 0x5A5A.
+int xgpu_test_itdq_pairs_mixed(xgpu_ctx *c, int16_t *coef, int n_groups, const int32_t *groups, const uint8_t *qp, int bit_depth)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, coef && groups && qp && n_groups > 0 && bit_depth >= 8 && bit_depth <= 16);
+    ARGCHK(c, c->sp.tool_iqt);                                // the pair form exists in the IQT instantiations only
+    std::vector<TbRec> tbs;
+    std::vector<TbWave> wv;
+    size_t total = 0;
+    for (int gi = 0; gi < n_groups; gi++) {
+        const int32_t *g = groups + 6 * gi;
+        const int n_blocks = g[0], log2w = g[1], log2h = g[2], tr_v = g[3], tr_h = g[4], log2s = g[5];
+        ARGCHK(c, n_blocks > 0 && log2w >= 1 && log2w <= 6 && log2h >= 1 && log2h <= 6);
+        ARGCHK(c, tr_v >= TR_DCT2 && tr_v <= TR_DCT8 && tr_h >= TR_DCT2 && tr_h <= TR_DCT8);
+        ARGCHK(c, (tr_v == TR_DCT2 && tr_h == TR_DCT2) || (tr_v != TR_DCT2 && tr_h != TR_DCT2 && log2w >= 2 && log2w <= 5 && log2h >= 2 && log2h <= 5));      // as xgpu_test_itdq_ex
+        ARGCHK(c, log2s >= log2w && log2s <= 12 && (log2s == log2w || (log2w >= 3 && log2w + log2h > 4)));
+        const size_t per = (size_t)1 << (log2s + log2h);
+        total = (total + 63) & ~(size_t)63;                  // a group starts at a multiple of 64 samples (the builder's arena keeps a TB aligned to its vector stores)
+        ARGCHK(c, total + per * n_blocks <= 0x7FFFFFFFu);
+        const int pw = itdq_group_size(log2w, log2h), first = (int)tbs.size();
+        for (int i = 0; i < n_blocks; i++) {
+            TbRec t; t.off = (uint32_t)(total + per * i); t.log2w = (uint8_t)log2w; t.log2h = (uint8_t)log2h; t.qp = qp[first + i]; t.log2s = (uint8_t)log2s;
+            tbs.push_back(t);
+        }
+        for (int f = 0; f < n_blocks; f += pw)
+            wv.push_back({ (uint32_t)(first + f), (uint16_t)std::min(pw, n_blocks - f), (uint8_t)log2w, (uint8_t)log2h, (uint8_t)tr_v, (uint8_t)tr_h, { 0, 0 } });
+        total += per * n_blocks;
+    }
+    const size_t nb = total * sizeof(int16_t);
+    int16_t *dc = NULL, *dr = NULL; TbRec *dt = NULL; TbWave *dw = NULL;
+    HIPCHK(c, hipMalloc((void **)&dc, nb)); HIPCHK(c, hipMalloc((void **)&dr, nb));
+    HIPCHK(c, hipMalloc((void **)&dt, sizeof(TbRec) * tbs.size())); HIPCHK(c, hipMalloc((void **)&dw, sizeof(TbWave) * wv.size()));
+    HIPCHK(c, hipMemcpyAsync(dc, coef, nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dr, 0x5A, nb, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dt, tbs.data(), sizeof(TbRec) * tbs.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dw, wv.data(), sizeof(TbWave) * wv.size(), hipMemcpyHostToDevice, c->stream));
+    ItdqArgs ia; ia.coef = dc; ia.resid = dr; ia.tbs = dt; ia.waves = dw; ia.n_waves = (int)wv.size(); ia.bd = bit_depth; ia.iqt = 1;
+    launch_itdq_pairs(c, ia, c->stream);
+    HIPCHK(c, hipMemcpyAsync(coef, dr, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(dc); (void)hipFree(dr); (void)hipFree(dt); (void)hipFree(dw);
+    return XGPU_OK;
+}
+// ... one group: the arguments of xgpu_test_itdq_ex, ceil(items / 2) workgroups
+int xgpu_test_itdq_pairs(xgpu_ctx *c, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth, int tr_v, int tr_h, int log2s)
+{
+    const int32_t g[6] = { n_blocks, log2w, log2h, tr_v, tr_h, log2s };
+    return xgpu_test_itdq_pairs_mixed(c, coef, 1, g, qp, bit_depth);
+}
+
 // xgpu_scale_taps through the device's row builder (k_output_rois_dev.hip): the arguments are checked by the host function itself, which also says how wide
 // the widest row is; then one lane per row on the device, and the three arrays come back
 int xgpu_test_scale_taps_device(xgpu_ctx *c, int n_plane, int subsampling, int siting_half_luma, int n_dst, int filter, int32_t *first, int32_t *count, int16_t *w,

@@ -1045,3 +1045,25 @@ class XgpuDecoder:
         assert coef.size == len(qp) << (log2s + log2h), "n blocks of h << log2s samples"
         self._chk(self.lib.xgpu_test_itdq_ex(self.ctx, coef.ctypes.data, len(qp), log2w, log2h, qp.ctypes.data, bit_depth, tr_v, tr_h, log2s), "xgpu_test_itdq_ex")
         return coef
+
+    def test_itdq_pairs(self, coef, log2w, log2h, qp, bit_depth, tr_v=0, tr_h=0, log2s=None):
+        """test_itdq through the pair form (two work items per workgroup, IQT contexts only); the samples outside a block's columns come back as 0x5A5A"""
+        coef = np.ascontiguousarray(coef, np.int16).copy()
+        qp = np.ascontiguousarray(qp, np.uint8)
+        log2s = log2w if log2s is None else log2s
+        assert coef.size == len(qp) << (log2s + log2h), "n blocks of h << log2s samples"
+        self._chk(self.lib.xgpu_test_itdq_pairs(self.ctx, coef.ctypes.data, len(qp), log2w, log2h, qp.ctypes.data, bit_depth, tr_v, tr_h, log2s), "xgpu_test_itdq_pairs")
+        return coef
+
+    def test_itdq_pairs_mixed(self, coef, groups, qp, bit_depth):
+        """groups: rows of (n_blocks, log2w, log2h, tr_v, tr_h, log2s), each group's blocks back to back from the next multiple of 64 samples; qp: one per block in
+        group order.  One launch of the pair form over all of them; what no block covers comes back as 0x5A5A"""
+        coef = np.ascontiguousarray(coef, np.int16).copy()
+        qp = np.ascontiguousarray(qp, np.uint8)
+        groups = np.ascontiguousarray(groups, np.int32).reshape(-1, 6)
+        total = 0
+        for n, lw, lh, _, _, ls in groups.tolist():
+            total = ((total + 63) & ~63) + (n << (ls + lh))
+        assert coef.size == total and len(qp) == int(groups[:, 0].sum())
+        self._chk(self.lib.xgpu_test_itdq_pairs_mixed(self.ctx, coef.ctypes.data, len(groups), groups.ctypes.data, qp.ctypes.data, bit_depth), "xgpu_test_itdq_pairs_mixed")
+        return coef
