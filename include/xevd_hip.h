@@ -441,6 +441,35 @@ int    xgpu_pic_output_device_scaled_lin(xgpu_ctx *ctx, int pic, const xgpu_dra_
 int    xgpu_pic_output_device_rois_lin(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc,
                                        const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size,
                                        void *stream);
+/* ---- bicubic resize (k_output_resampled.hip): the scaled output and the host-box batch with a cubic BC-spline in place of the triangle / box - the resize CLIP /
+   SigLIP, DINOv2 and most timm configurations were trained with.  Calls of their own with a parameter struct of their own: xgpu_scale_params.filter keeps its two
+   values.  Layouts, dtypes, row_pitch / image_pitch, the crop, DRA, chroma_loc, matrix, range, bgr, the normalise, stretch / letterbox and the pad value, stream
+   ordering, the limits (2 .. 16384 per axis, Ws / 64 <= Wd <= 8 Ws, 512 MiB of intermediate per batch) and every refusal are section 8d's and 8e's; an unknown
+   kernel or an antialias other than 0 / 1 is XGPU_ERR_INVALID_ARGUMENT.  Only the two passes differ (tests/resample_ref.py restates it):
+     taps     one axis of one plane in section 8d's notation, f = antialias ? max(1, n / N) : 1: the row of destination sample o is every plane sample i in
+              0 .. n - 1 with |i - c| < 2 f, weighted k((i - c) / f) with k the BC-spline of the kernel; q(i) = floor(w(i) / W * 16384 + 1/2), 16384 - sum q goes
+              to the largest q (the first of equals); negative and zero q stay in the row.  xgpu_resample_taps builds a table on the host, in integers only, as
+              xgpu_scale_taps does (same arguments and return value); a row with W <= 0 or sum |q| > 32768 makes it return XGPU_ERR_UNSUPPORTED.
+     passes   t = (sum qy * clip(dra(sample), 0, 2^B - 1) + 2^11) >> 12 (arithmetic shift), a signed 16-bit value with two fraction bits, not clipped;
+              v = clip((sum qx * t + 2^15) >> 16, 0, 2^B - 1).  (Y, Cb, Cr) then take the scaled output's conversion, bgr and normalise.
+   The intermediate (the context's, grown on demand) has the scaled output's size; image i of a batch is, bit for bit, the single call with the crop set to
+   rectangle i.  Not offered: Lanczos, boxes in device memory, the colour-managed and linear-light forms, the ladder, warp and remap. */
+#define XGPU_RESAMPLE_CATMULL_ROM 0   /* Keys a = -1/2 = BC(0, 1/2): PIL BICUBIC, torch bicubic with antialias=True */
+#define XGPU_RESAMPLE_CUBIC_075   1   /* Keys a = -3/4 = BC(0, 3/4): torch bicubic with antialias=False, OpenCV INTER_CUBIC */
+#define XGPU_RESAMPLE_MITCHELL    2   /* BC(1/3, 1/3) */
+typedef struct xgpu_resample_params { int width, height, kernel, antialias, normalize; float mean[3], inv_std[3]; } xgpu_resample_params;
+int    xgpu_resample_taps(int n_plane, int subsampling, int siting_half_luma, int n_dst, int kernel, int antialias,
+                          int32_t *first, int32_t *count, int16_t *w, int w_stride);
+size_t xgpu_output_resampled_size(const xgpu_output_format *f, const xgpu_resample_params *rs, int width, int height, int bit_depth);
+int    xgpu_output_resampled_check(const xgpu_output_format *f, const xgpu_resample_params *rs, int width, int height, int bit_depth);
+int    xgpu_pic_output_device_resampled(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_resample_params *rs,
+                                        void *d_dst, size_t dst_size, void *stream);
+int    xgpu_output_rois_resampled_check(const xgpu_output_format *f, const xgpu_resample_params *rs, const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois,
+                                        int width, int height, int bit_depth, int *bad_index);
+size_t xgpu_output_rois_resampled_size(const xgpu_output_format *f, const xgpu_resample_params *rs, const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois,
+                                       int width, int height, int bit_depth);
+int    xgpu_pic_output_device_rois_resampled(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_resample_params *rs,
+                                             const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, void *d_dst, size_t dst_size, void *stream);
 /* ---- regions of interest from device memory (k_output_rois_dev.hip): xgpu_pic_output_device_rois for boxes that a detector left on the GPU.  d_boxes points
    to `capacity` boxes in device memory (1 .. XGPU_MAX_ROIS), d_count (may be NULL: all of them) to a device int32 - the live boxes are the first
    min(max(*d_count, 0), capacity).  The host reads neither; the call does not synchronise and nothing comes back to the host.  Descriptors and tap tables are

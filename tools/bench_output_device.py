@@ -62,6 +62,11 @@ gradient with +-2 codes of noise: the contention of the LDS histogram depends on
 the light level.  Each is timed as the other legs are (the median of --iters calls queued behind a wait) and, alternated with it from an idle device, the torch
 route: a yuv420p tensor, then bincount, sum, min and max per plane; with light the u16 RGB tensor, amax, bincount and a gather through lin.
 
+The resampled leg (xgpu_pic_output_device_resampled / _rois_resampled: k_resampled_vertical + k_resampled_horizontal) takes the picture to 224x224 f32
+normalised, to 1080p u8 and to 64 tiles at 224x224 with the Catmull-Rom kernel and antialias, and alternates - the scaled_cm leg's protocol - each with the plain
+bilinear call of the same shape (the price of the window twice as wide) and with the route without it: the full-size f32 tensor, then torch's
+interpolate(bicubic, antialias=True) and the normalise or the u8 rounding.  The largest difference to that route is a record, not a test.
+
 The ladder leg (xgpu_pic_output_device_ladder: k_ladder_vertical + k_ladder_horizontal) takes the picture to P010 rungs 3840x2160, 1920x1080, 1280x720 and
 640x360 with centre chroma siting on both sides and alternates - the rois leg's protocol - the one call with the route without it (the full-size P010 surface,
 then per rung and plane torch's interpolate(bilinear, antialias=True), rounding and repacking) and with the plain full-size surface, the floor of reading the
@@ -69,7 +74,7 @@ picture once; four one-rung calls are alternated on their own (each makes its ta
 of the kernels alone (median of --iters calls queued behind a wait).  The largest difference between each rung's planes and the torch route in float64 is
 recorded in code values; it is a record, not a test.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|rois|rois_dev|ladder|warp|remap|residual|compare|stats] [--out out/output_device.json]
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|resampled|rois|rois_dev|ladder|warp|remap|residual|compare|stats] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -203,6 +208,56 @@ def scaled_cm_leg(torch, dec, pic, s, a, res):
         print(f"scaled_cm {name:32s} {r['cm']['us']:9.1f} us (kernels {r['cm']['device_us']:7.1f})   plain call {r['plain']['us']:9.1f} us (kernels {r['plain']['device_us']:7.1f}; {r['vs_plain']:.2f}x)   torch route {rt['torch_route']['us']:10.1f} us "
               f"({r['speedup_vs_torch_route']:.1f}x)   max |diff| {diff:.3g}")
         res["scaled_cm"][name] = r
+    del full
+
+
+def resampled_leg(torch, dec, pic, s, a, res):
+    """the bicubic call (Catmull-Rom, antialias) at three shapes, each alternated with (i) the plain bilinear scaled / ROI call of the same shape - the price of the
+    wider window - and (ii) the route without it: the full-size f32 tensor + F.interpolate(mode="bicubic", antialias=True) + the normalise (or the u8 rounding)
+    in torch, with the max |diff| between the two"""
+    import torch.nn.functional as F
+    from xevd_amd import abi
+    w, h = a.width, a.height
+    mean = torch.tensor(MEAN, device="cuda:0").view(3, 1, 1)
+    inv = (1.0 / torch.tensor(STD, device="cuda:0")).view(3, 1, 1)
+    full = dec.pic_output_tensor(pic, dtype=torch.float32)
+    tiles = abi.tile_rois(w, h, (w // 8) & ~1, (h // 8) & ~1)[:64]
+    norm = dict(mean=MEAN, std=STD)
+    shapes = (("224x224_f32_normalised", (224, 224), None, dict(dtype=torch.float32, **norm)), ("1920x1080_u8", (1080, 1920), None, dict(dtype=torch.uint8)),
+              ("64_rois_224x224_f32_normalised", (224, 224), tiles, dict(dtype=torch.float32, **norm)))
+    res["resampled"] = {}
+    for name, size, rois, kw in shapes:
+        is_u8 = kw["dtype"] == torch.uint8
+        roi_kw = {} if rois is None else dict(rois=rois)
+        out = dec.pic_output_resampled(pic, size, **roi_kw, **kw)
+        plain = dec.pic_output_tensor(pic, size=size, **roi_kw, **kw)
+
+        def cubic_call():
+            dec.pic_output_resampled(pic, size, out=out, **roi_kw, **kw)
+
+        def plain_call():
+            dec.pic_output_tensor(pic, size=size, out=plain, **roi_kw, **kw)
+
+        def resize(x):
+            y = F.interpolate(x[None], size=size, mode="bicubic", antialias=True, align_corners=False)[0]
+            return (y * 255.0).round().clamp(0, 255).to(torch.uint8) if is_u8 else (y - mean) * inv
+
+        def torch_route():
+            dec.pic_output_tensor(pic, out=full, dtype=torch.float32)
+            if rois is None:
+                return resize(full)
+            return torch.stack([resize(full[:, y:y + rh, x:x + rw]) for x, y, rw, rh in rois])
+
+        r = alternated(torch, s, {"bicubic": cubic_call, "plain": plain_call}, a.iters)
+        rt = alternated(torch, s, {"bicubic": cubic_call, "torch_route": torch_route}, max(a.iters // 10, 5), warm=2)
+        r["bicubic"]["device_us"], r["plain"]["device_us"] = round(timed(torch, s, cubic_call, a.iters), 2), round(timed(torch, s, plain_call, a.iters), 2)      # the kernels alone
+        r["torch_route"], r["bicubic_beside_torch_route"] = rt["torch_route"], rt["bicubic"]
+        diff = float((torch_route().float() - out.float()).abs().max())
+        r.update({"vs_plain": round(r["bicubic"]["us"] / r["plain"]["us"], 2), "speedup_vs_torch_route": round(rt["torch_route"]["us"] / rt["bicubic"]["us"], 2),
+                  "max_abs_diff_vs_torch_route": diff, "diff_unit": "code values of the u8 output" if is_u8 else "normalised float"})
+        print(f"resampled {name:32s} {r['bicubic']['us']:9.1f} us (kernels {r['bicubic']['device_us']:7.1f})   plain call {r['plain']['us']:9.1f} us (kernels {r['plain']['device_us']:7.1f}; {r['vs_plain']:.2f}x)   "
+              f"torch route {rt['torch_route']['us']:10.1f} us ({r['speedup_vs_torch_route']:.1f}x)   max |diff| {diff:.3g}")
+        res["resampled"][name] = r
     del full
 
 
@@ -839,8 +894,8 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats"), default="all",
-                    help="full: the full-size forms and the side information; scaled: the scaled leg alone; scaled_cm: the colour-managed scaled output alone; scaled_lin: the scaled output filtered in linear light alone; rois: the batched regions of interest alone; "
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "resampled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats"), default="all",
+                    help="full: the full-size forms and the side information; scaled: the scaled leg alone; scaled_cm: the colour-managed scaled output alone; scaled_lin: the scaled output filtered in linear light alone; resampled: the bicubic resize alone; rois: the batched regions of interest alone; "
                          "rois_dev: the regions of interest from boxes in device memory alone; ladder: the ladder of scaled P010 surfaces alone; warp: the warped regions of interest alone; remap: the remapped output alone; residual: the residual "
                          "export alone; compare: the picture comparison alone; stats: the picture statistics alone")
     a = ap.parse_args()
@@ -882,6 +937,8 @@ def main():
             scaled_cm_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "scaled_lin"):
             scaled_lin_leg(torch, dec, pic, s, a, res)
+        if a.legs in ("all", "resampled"):
+            resampled_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "rois"):
             rois_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "rois_dev"):

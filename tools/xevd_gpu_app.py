@@ -146,6 +146,8 @@ def main():
                     "(gamma-correct resize, INTEGRATION.md 8n), with --tiles too")
     ap.add_argument("--tiles", default=None, metavar="WxH", help="with --size: every picture as its grid of W x H tiles (the last column / row moved back inside the "
                     "picture), each resized to --size by one call per picture (INTEGRATION.md 8e); the frames written are the tiles, row by row")
+    ap.add_argument("--resample", default=None, metavar="NAME", choices=("bicubic", "catmull-rom", "cubic-0.75", "mitchell"), help="with --size: resize with this "
+                    "bicubic kernel instead of the antialiased triangle (INTEGRATION.md 8o), with --tiles too; not with --to, --linear-light or --remap")
     ap.add_argument("--remap", default=None, metavar="GRID.npy", help="with --size: every picture pulled through this coordinate grid on the device instead of resized "
                     "(INTEGRATION.md 8k): an int32 (Q16) or float32 (luma samples) array [gh, gw, 2] or [N, gh, gw, 2] of source positions for the W x H image, "
                     "e.g. from abi.remap_from_lens; N > 1 writes N frames per picture")
@@ -184,6 +186,8 @@ def main():
         ap.error("--tiles: needs --size")
     if args.linear_light and (args.size is None or args.to is None or args.remap is not None):
         ap.error("--linear-light: needs --size and --to, and not --remap")
+    if args.resample is not None and (args.size is None or args.to is not None or args.linear_light or args.remap is not None):
+        ap.error("--resample: needs --size, and not --to, --linear-light or --remap")
     if args.remap is not None and (args.size is None or args.tiles is not None):
         ap.error("--remap: needs --size, and not --tiles")
     data = open(args.input, "rb").read()
@@ -216,7 +220,7 @@ def main():
                 ap.error(f"--remap: an int32 or float32 array, not {remap.dtype}")
             remap = torch.from_numpy(remap).to(f"cuda:{args.device}")      # uploaded once, used for every picture
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), to=args.to, side=side, rois=rois, residual=resid, compare=cmp, stats=stats,
-                                                                    remap=remap, remap_step=args.remap_step, linear_light=args.linear_light, **lad)
+                                                                    remap=remap, remap_step=args.remap_step, linear_light=args.linear_light, resample=args.resample, **lad)
     elif args.to is not None:
         import torch
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad)

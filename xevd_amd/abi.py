@@ -243,6 +243,40 @@ def scale_taps(lib, n_plane, subsampling, siting_half_luma, n_dst, filter=SCALE_
     return rc if rc < 0 else (first, count, w)
 
 
+RESAMPLE_CATMULL_ROM, RESAMPLE_CUBIC_075, RESAMPLE_MITCHELL = 0, 1, 2
+RESAMPLE_KERNELS = {"catmull-rom": RESAMPLE_CATMULL_ROM, "bicubic": RESAMPLE_CATMULL_ROM, "cubic-0.75": RESAMPLE_CUBIC_075, "mitchell": RESAMPLE_MITCHELL}
+
+
+class ResampleParams(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("kernel", C.c_int), ("antialias", C.c_int), ("normalize", C.c_int), ("mean", C.c_float * 3),
+                ("inv_std", C.c_float * 3)]
+
+
+def make_resample_params(width, height, kernel=RESAMPLE_CATMULL_ROM, antialias=True, mean=None, std=None, inv_std=None):
+    """xgpu_resample_params (include/xevd_hip.h): the destination size, the cubic kernel (a RESAMPLE_* code or a name of RESAMPLE_KERNELS), antialias, and the
+    normalise of make_scale_params"""
+    sc = make_scale_params(width, height, mean=mean, std=std, inv_std=inv_std)
+    p = ResampleParams()
+    p.width, p.height, p.kernel, p.antialias, p.normalize = sc.width, sc.height, int(RESAMPLE_KERNELS.get(kernel, kernel)), int(antialias), sc.normalize
+    for k in range(3):
+        p.mean[k], p.inv_std[k] = sc.mean[k], sc.inv_std[k]
+    return p
+
+
+def resample_taps(lib, n_plane, subsampling, siting_half_luma, n_dst, kernel=RESAMPLE_CATMULL_ROM, antialias=True):
+    """xgpu_resample_taps as numpy arrays: (first [n_dst] int32, count [n_dst] int32, w [n_dst][widest] int16 - row o: count[o] weights of either sign and of
+    sum 16384, then zeros), or the negative code"""
+    first, count = np.zeros(max(int(n_dst), 1), np.int32), np.zeros(max(int(n_dst), 1), np.int32)
+    pi, pc = first.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_int32))
+    args = (int(n_plane), int(subsampling), int(siting_half_luma), int(n_dst), int(RESAMPLE_KERNELS.get(kernel, kernel)), int(antialias))
+    widest = lib.xgpu_resample_taps(*args, pi, pc, None, 0)
+    if widest < 0:
+        return widest
+    w = np.zeros((int(n_dst), widest), np.int16)
+    rc = lib.xgpu_resample_taps(*args, pi, pc, w.ctypes.data_as(C.POINTER(C.c_int16)), widest)
+    return rc if rc < 0 else (first, count, w)
+
+
 def scale_taps_device(lib, ctx, n_plane, subsampling, siting_half_luma, n_dst, filter=SCALE_BILINEAR, extra=0):
     """xgpu_test_scale_taps_device - scale_taps' arrays made by the device's row builder (ctx: an open context); extra: columns beyond the widest row"""
     first, count = np.zeros(max(int(n_dst), 1), np.int32), np.zeros(max(int(n_dst), 1), np.int32)
@@ -736,6 +770,17 @@ _EXPORTS = {
                                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_pic_output_device_rois_lin": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(Roi),
                                                   C.c_int, C.POINTER(ColourTransform), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_resample_taps": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16), C.c_int]),
+    "xgpu_output_resampled_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ResampleParams), C.c_int, C.c_int, C.c_int]),
+    "xgpu_output_resampled_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ResampleParams), C.c_int, C.c_int, C.c_int]),
+    "xgpu_pic_output_device_resampled": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ResampleParams), C.c_void_p, C.c_size_t,
+                                                   C.c_void_p]),
+    "xgpu_output_rois_resampled_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ResampleParams), C.POINTER(RoiParams), C.POINTER(Roi), C.c_int, C.c_int, C.c_int,
+                                                   C.c_int, C.POINTER(C.c_int)]),
+    "xgpu_output_rois_resampled_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ResampleParams), C.POINTER(RoiParams), C.POINTER(Roi), C.c_int, C.c_int, C.c_int,
+                                                     C.c_int]),
+    "xgpu_pic_output_device_rois_resampled": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ResampleParams), C.POINTER(RoiParams),
+                                                        C.POINTER(Roi), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_roi_snap": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(Roi)]),
     "xgpu_output_rois_dev_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(RoiBounds)] + [C.c_int] * 5),
     "xgpu_output_rois_dev_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.POINTER(RoiParams), C.POINTER(RoiBounds)] + [C.c_int] * 5),

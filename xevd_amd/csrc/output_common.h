@@ -301,6 +301,52 @@ __device__ __forceinline__ int filter_column(const uint16_t *lds, const ScaleTap
     for (int k = 0; k < n; k++) acc += (int)q[(size_t)k * t.stride] * (int)l[k];
     return (acc + (1 << 16)) >> 17;
 }
+// The two passes of the bicubic resize (k_output_resampled.hip): the weights have either sign, so the sums and the intermediate are
+// signed.  With sum |q| <= 32768 (xgpu_resample_taps refuses a table with a wider row) |sum qy * sample| <= 4095 * 2^15 < 2^27 and |t| <= 32760, an int16;
+// |sum qx * t| <= 2^15 * 32760 < 2^30: int32 accumulators hold both.
+// Vertical pass, one lane, arguments as scale_vertical_lane's: t = (sum qy * clip(dra(sample)) + 2^11) >> 12, two fraction bits, not clipped
+__device__ __forceinline__ void resample_vertical_lane(const ScaledOutArgs &a, int plane, const int16_t *src, const int16_t *luma, int first, int cnt, const int16_t *q,
+                                                       int x0, int16_t *d)
+{
+    const int st = plane ? a.sc : a.sy;
+    int acc[8];
+    #pragma unroll
+    for (int m = 0; m < 8; m++) acc[m] = 0;
+    for (int k = 0; k < cnt; k++) {
+        const int row = first + k, qk = q[k];
+        const S16x8u s = *(const S16x8u *)(src + (size_t)row * st + x0);
+        int v[8];
+        #pragma unroll
+        for (int m = 0; m < 8; m++) v[m] = s.v[m];
+        if (a.dra) {
+            if (plane == 0) {
+                #pragma unroll
+                for (int m = 0; m < 8; m++) v[m] = dra1(a.dra, 0, v[m], 0);
+            } else {
+                const int16_t *l = luma + (size_t)(2 * row) * a.sy + 2 * x0;
+                const S16x8u l0 = *(const S16x8u *)l, l1 = *(const S16x8u *)(l + 8);
+                #pragma unroll
+                for (int m = 0; m < 8; m++) v[m] = dra1(a.dra, plane, v[m], m < 4 ? l0.v[2 * m] : l1.v[2 * m - 8]);
+            }
+        }
+        #pragma unroll
+        for (int m = 0; m < 8; m++) acc[m] += qk * min(max(v[m], 0), a.smax);
+    }
+    uint32_t w[4];
+    #pragma unroll
+    for (int m = 0; m < 4; m++) w[m] = (uint32_t)(uint16_t)((acc[2 * m] + (1 << 11)) >> 12) | ((uint32_t)(uint16_t)((acc[2 * m + 1] + (1 << 11)) >> 12) << 16);
+    *(uint4 *)d = make_uint4(w[0], w[1], w[2], w[3]);
+}
+// destination column o of the staged row of signed samples: v = clip((sum qx * t + 2^15) >> 16, 0, smax)
+__device__ __forceinline__ int resample_column(const int16_t *lds, const ScaleTaps &t, int o, int s0, int smax)
+{
+    const int16_t *l = lds + (t.first[o] - s0);
+    const int16_t *q = t.w + o;
+    const int n = t.count[o];
+    int acc = 0;
+    for (int k = 0; k < n; k++) acc += (int)q[(size_t)k * t.stride] * (int)l[k];
+    return min(max((acc + (1 << 15)) >> 16, 0), smax);
+}
 template <int SZ> __device__ __forceinline__ void store_elem(uint8_t *p, uint32_t e)
 {
     if (SZ == 1) *p = (uint8_t)e;

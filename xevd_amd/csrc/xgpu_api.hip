@@ -133,6 +133,7 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
     c->odev_ev[0] = c->odev_ev[1] = 0;
     c->sc_tab = NULL; c->sc_tab_cap = 0; c->sc_mid = NULL; c->sc_mid_cap = 0; c->cmp_part = NULL; c->cmp_part_cap = 0; c->stats_blk = NULL; c->stats_lin_tc = c->stats_lin_bd = -1;
     c->roi_blk = NULL; c->roi_blk_cap = 0;
+    c->rs_blk = NULL; c->rs_blk_cap = 0; c->rs_key[0] = -1; c->rs_capy = c->rs_capc = 0;
     c->lad_blk = NULL; c->lad_blk_cap = 0; c->lad_cap = 0;
     for (int i = 0; i < 6; i++) c->sc_key[i] = -1;
     c->out_next = 0;
@@ -222,6 +223,7 @@ void xgpu_close(xgpu_ctx *c)
     if (c->cmp_part) (void)hipFree(c->cmp_part);
     if (c->stats_blk) (void)hipFree(c->stats_blk);
     if (c->roi_blk) (void)hipFree(c->roi_blk);
+    if (c->rs_blk) (void)hipFree(c->rs_blk);
     if (c->lad_blk) (void)hipFree(c->lad_blk);
     if (c->d_ctb_flag) (void)hipFree(c->d_ctb_flag);
     for (auto &e : c->ev_pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }

@@ -372,6 +372,11 @@ struct xgpu_ctx {
     // partial sums of the current call
     uint8_t        *stats_blk;
     int             stats_lin_tc, stats_lin_bd;
+    // xgpu_pic_output_device_resampled: the descriptor and the four bicubic tap tables of one picture on the device (rs_blk; made for rs_key = source size,
+    // destination size, kernel, antialias, chroma_loc - rs_key[0] = -1 until the first call), with pass 2's spans.  Its intermediate is sc_mid.  Ordered like sc_tab.
+    uint8_t        *rs_blk;
+    size_t          rs_blk_cap;
+    int             rs_key[7], rs_capy, rs_capc;
     uint8_t        *roi_blk;          // xgpu_pic_output_device_rois: the descriptors and tap tables of the current call (its intermediate is sc_mid), ordered like sc_tab;
                                       // xgpu_pic_output_device_warp: the host maps of the current call
     size_t          roi_blk_cap;
@@ -548,6 +553,10 @@ struct RoisOutArgs : ScaledOutArgs {
 };
 void launch_output_rois(const RoisOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s);
 void launch_rois_vertical(const RoisOutArgs &a, int max_w, int max_ih, hipStream_t s);      // its vertical pass alone
+// k_output_resampled.hip: the same block and arguments with bicubic tap tables (xgpu_pic_output_device_resampled / _rois_resampled): `mid`
+// holds int16 with two fraction bits, and RoiDesc::skip is not read
+void launch_output_resampled(const RoisOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s);
+int  resample_build_tables(int ws, int hs, int wd, int hd, int kernel, int antialias, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb, int x_off = 0);      // xgpu_scale.hip
 // k_output_scaled_cm.hip: the two scaled outputs with the colour transform between the filter and the store (xgpu_pic_output_device_scaled_cm / _rois_cm,
 // INTEGRATION.md section 8m).  The vertical passes are k_scale_vertical / k_rois_vertical; the horizontal pass keeps the transform's tables in global memory (L1 / L2) and
 // only its spans in dynamic LDS.  coef / shift / maxv: those of the U16 form, whatever the dtype (CmOutArgs' rule).

@@ -675,7 +675,8 @@ size_t xgpu_output_rois_size(const xgpu_output_format *f, const xgpu_scale_param
 // rectangle and the tallest inner part, which size the launch.
 struct RoiBlock { std::vector<uint8_t> blk; int capy, capc, max_w, max_ih; };
 static int build_roi_block(xgpu_ctx *c, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n, size_t image_pitch,
-                           RoiBlock &b, bool lin = false)      // lin: the float32 intermediate of section 8n - RoiDesc::mid counts floats
+                           RoiBlock &b, bool lin = false,      // lin: the float32 intermediate of section 8n - RoiDesc::mid counts floats
+                           const xgpu_resample_params *rs = NULL)      // the bicubic tables of section 8o instead of sc->filter's
 {
     struct Set { int ws, hs, wi, hi; ScaleTabs tb; size_t base; };
     std::vector<Set> sets;
@@ -691,7 +692,8 @@ static int build_roi_block(xgpu_ctx *c, const xgpu_output_format *f, const xgpu_
         while (k < sets.size() && !(sets[k].ws == r.width && sets[k].hs == r.height && sets[k].wi == in[2] && sets[k].hi == in[3])) k++;
         if (k == sets.size()) {
             Set st = { r.width, r.height, in[2], in[3], {}, (b.blk.size() + 15) & ~(size_t)15 };
-            const int rc = scale_build_tables(r.width, r.height, in[2], in[3], sc->filter, f->chroma_loc, blob, st.tb, in[0]);
+            const int rc = rs ? resample_build_tables(r.width, r.height, in[2], in[3], rs->kernel, rs->antialias, f->chroma_loc, blob, st.tb, in[0])
+                              : scale_build_tables(r.width, r.height, in[2], in[3], sc->filter, f->chroma_loc, blob, st.tb, in[0]);
             if (rc < 0) { snprintf(c->err, sizeof(c->err), "pic_output_device_rois: roi %d: cannot make the tap tables for %dx%d -> %dx%d", i, r.width, r.height, in[2], in[3]); return rc; }
             if (st.base + blob.size() > 0xFFFFFFFFu) { snprintf(c->err, sizeof(c->err), "pic_output_device_rois: roi %d: the tap tables of the call pass 4 GiB here", i); return XGPU_ERR_UNSUPPORTED; }
             b.blk.resize(st.base + blob.size());
@@ -789,6 +791,109 @@ static int output_rois(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_lut
         launch_output_rois(a, f->layout, f->dtype, b.max_w, b.max_ih, s);
     }
     return out_join(c, stream, s);      // the slot, the DRA and colour tables, the block and the intermediate
+}
+
+// ------------------------------------------------------------------------------------------------ bicubic resize of the two outputs above
+// Everything but the two passes is the scaled output's, so the checks are its checks on the same shape: rs as xgpu_scale_params (the filter is not read by what
+// runs behind this), or false for rs = NULL, an unknown kernel or an antialias that is not 0 / 1
+static bool resample_as_scale(const xgpu_resample_params *rs, xgpu_scale_params *sc)
+{
+    if (!rs || rs->kernel < XGPU_RESAMPLE_CATMULL_ROM || rs->kernel > XGPU_RESAMPLE_MITCHELL || (rs->antialias & ~1)) return false;
+    sc->width = rs->width; sc->height = rs->height; sc->filter = XGPU_SCALE_BILINEAR; sc->normalize = rs->normalize;
+    for (int k = 0; k < 3; k++) { sc->mean[k] = rs->mean[k]; sc->inv_std[k] = rs->inv_std[k]; }
+    return true;
+}
+size_t xgpu_output_resampled_size(const xgpu_output_format *f, const xgpu_resample_params *rs, int width, int height, int bit_depth)
+{
+    xgpu_scale_params sc;
+    return resample_as_scale(rs, &sc) ? xgpu_output_scaled_size(f, &sc, width, height, bit_depth) : 0;
+}
+int xgpu_output_resampled_check(const xgpu_output_format *f, const xgpu_resample_params *rs, int width, int height, int bit_depth)
+{
+    xgpu_scale_params sc;
+    return resample_as_scale(rs, &sc) ? xgpu_output_scaled_check(f, &sc, width, height, bit_depth) : XGPU_ERR_INVALID_ARGUMENT;
+}
+int xgpu_output_rois_resampled_check(const xgpu_output_format *f, const xgpu_resample_params *rs, const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois,
+                                     int width, int height, int bit_depth, int *bad_index)
+{
+    xgpu_scale_params sc;
+    if (bad_index) *bad_index = -1;
+    return resample_as_scale(rs, &sc) ? xgpu_output_rois_check(f, &sc, rp, rois, n_rois, width, height, bit_depth, bad_index) : XGPU_ERR_INVALID_ARGUMENT;
+}
+size_t xgpu_output_rois_resampled_size(const xgpu_output_format *f, const xgpu_resample_params *rs, const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois,
+                                       int width, int height, int bit_depth)
+{
+    xgpu_scale_params sc;
+    return resample_as_scale(rs, &sc) ? xgpu_output_rois_size(f, &sc, rp, rois, n_rois, width, height, bit_depth) : 0;
+}
+// Both calls.  batch = false: the single picture - the batch of one stretched rectangle, the picture minus f->crop -, whose block depends on nothing but
+// rs_key = (source size, destination size, kernel, antialias, chroma_loc) and stays on the device (rs_blk) until another key comes; a batch's block is made per
+// call and goes to roi_blk, as xgpu_pic_output_device_rois' does.  The intermediate is sc_mid.
+static int output_resampled(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_resample_params *rs,
+                            bool batch, const xgpu_roi_params *rp, const xgpu_roi *rois, int n, void *d_dst, size_t dst_size, void *stream)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    xgpu_scale_params sc;
+    if (!resample_as_scale(rs, &sc)) {
+        snprintf(c->err, sizeof(c->err), "%s: resample parameters: not NULL, kernel XGPU_RESAMPLE_CATMULL_ROM / _CUBIC_075 / _MITCHELL, antialias 0 or 1", who);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    int src_rc, bad; char why[160];
+    size_t image_pitch = 0, mid_need = 0, need;
+    if (batch) {
+        need = rois_size(f, &sc, rp, rois, n, c->sp.width, c->sp.height, c->sp.bit_depth_luma, &src_rc, why, &bad, &image_pitch, &mid_need);
+    } else {
+        const char *w0 = "";
+        need = scaled_size(f, &sc, c->sp.width, c->sp.height, c->sp.bit_depth_luma, &src_rc, &w0);
+        snprintf(why, sizeof(why), "%s", w0);
+    }
+    if (need == 0) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return src_rc; }
+    TRY(check_dst_fits(c, who, d_dst, dst_size, need, elem_size(f->dtype)));
+    if (dra) TRY(check_dra(c, dra));      // upload_dra's refusals, before anything is queued
+    TRY(check_device_dst(c, who, d_dst, need));
+    const xgpu_roi whole = { 0, 0, c->sp.width - f->crop[0] - f->crop[1], c->sp.height - f->crop[2] - f->crop[3] };
+    const xgpu_roi_params stretch = { XGPU_FIT_STRETCH, { 0.f, 0.f, 0.f }, 0 };
+    if (!batch) { rp = &stretch; rois = &whole; n = 1; mid_need = (size_t)sc.height * mid_row_samples(whole.width) * sizeof(uint16_t); }
+    const int key[7] = { whole.width, whole.height, sc.width, sc.height, rs->kernel, rs->antialias, f->chroma_loc };
+    const bool cached = !batch && c->rs_blk && !memcmp(key, c->rs_key, sizeof(key));
+    RoiBlock b;      // made here, before anything is queued
+    if (cached) { b.capy = c->rs_capy; b.capc = c->rs_capc; b.max_w = whole.width; b.max_ih = sc.height; }
+    else TRY(build_roi_block(c, f, &sc, rp, rois, n, image_pitch, b, false, rs));
+    TRY(grow(c, who, &c->sc_mid, &c->sc_mid_cap, mid_need, "intermediate"));
+    if (batch) {
+        TRY(grow(c, who, &c->roi_blk, &c->roi_blk_cap, b.blk.size(), "descriptor block", b.blk.size() / 2));
+    } else if (!cached && c->rs_blk_cap < b.blk.size()) {
+        c->rs_key[0] = -1;      // no key names a block that is freed
+        TRY(grow(c, who, &c->rs_blk, &c->rs_blk_cap, b.blk.size(), "block of tap tables"));
+    }
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    uint8_t *blk = batch ? c->roi_blk : c->rs_blk;
+    if (!cached) {      // behind the fork: after every kernel that read the previous block
+        if (!batch) c->rs_key[0] = -1;      // rs_blk is about to change: no key names it until the new block is queued
+        HIPCHK(c, hipMemcpyAsync(blk, b.blk.data(), b.blk.size(), hipMemcpyHostToDevice, s));
+        if (!batch) { memcpy(c->rs_key, key, sizeof(key)); c->rs_capy = b.capy; c->rs_capc = b.capc; }
+    }
+    RoisOutArgs a;
+    memset(&a, 0, sizeof(a));
+    scaled_common_args(c, pic, dra, f, &sc, d_dst, a);
+    a.mid = c->sc_mid;
+    a.capy = b.capy; a.capc = b.capc;
+    a.blk = blk; a.n = n;
+    for (int k = 0; k < 3; k++) a.padv[k] = rp->fit == XGPU_FIT_LETTERBOX ? rp->pad[k] : 0.f;
+    launch_output_resampled(a, f->layout, f->dtype, b.max_w, b.max_ih, s);
+    return out_join(c, stream, s);      // the slot, the DRA tables, the block and the intermediate
+}
+int xgpu_pic_output_device_resampled(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_resample_params *rs, void *d_dst, size_t dst_size,
+                                     void *stream)
+{
+    return output_resampled(c, "pic_output_device_resampled", pic, dra, f, rs, false, NULL, NULL, 0, d_dst, dst_size, stream);
+}
+int xgpu_pic_output_device_rois_resampled(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_resample_params *rs, const xgpu_roi_params *rp,
+                                          const xgpu_roi *rois, int n, void *d_dst, size_t dst_size, void *stream)
+{
+    return output_resampled(c, "pic_output_device_rois_resampled", pic, dra, f, rs, true, rp, rois, n, d_dst, dst_size, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ scaled video surfaces: a ladder of renditions

@@ -54,7 +54,10 @@ int xgpu_scale_taps(int n_plane, int subsampling, int siting_half_luma, int n_ds
 // reach, from an 8-sample-aligned start.  The kernel takes a workgroup's span from its first and last column, so the rows must move right monotonically: checked
 // here, for every table it is given, before anything reaches the device.  x_off (the batched output's letterbox, k_output_rois.hip): the groups of 64 are those
 // of an image in which column 0 of the tables is column x_off.
-int scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb, int x_off)
+// `taps`: the builder of one table - xgpu_scale_taps with the filter bound (scale_build_tables), xgpu_resample_taps with kernel and antialias bound
+// (resample_build_tables, section 8o: rows with weights of either sign, laid out and measured the same way).
+template <class TAPS>
+static int build_tables(int ws, int hs, int wd, int hd, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb, int x_off, TAPS &&taps)
 {
     static const int vsite[3] = { 1, 0, 2 };      // ChromaSampleLocType >> 1: centred, top, bottom - in half luma samples
     const int n[4] = { hs, hs >> 1, ws, ws >> 1 }, sub[4] = { 1, 2, 1, 2 }, site[4] = { 0, vsite[chroma_loc >> 1], 0, chroma_loc & 1 }, N[4] = { hd, hd, wd, wd };
@@ -64,10 +67,10 @@ int scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_lo
     std::vector<int16_t> w;
     for (int t = 0; t < 4; t++) {
         first.assign(N[t], 0); count.assign(N[t], 0);
-        const int widest = xgpu_scale_taps(n[t], sub[t], site[t], N[t], filter, first.data(), count.data(), NULL, 0);
+        const int widest = taps(n[t], sub[t], site[t], N[t], first.data(), count.data(), (int16_t *)NULL, 0);
         if (widest < 0) return widest;
         w.assign((size_t)N[t] * widest, 0);
-        const int rc = xgpu_scale_taps(n[t], sub[t], site[t], N[t], filter, first.data(), count.data(), w.data(), widest);
+        const int rc = taps(n[t], sub[t], site[t], N[t], first.data(), count.data(), w.data(), widest);
         if (rc < 0) return rc;
         for (int o = 0; o < N[t]; o++) {
             if (first[o] < 0 || count[o] < 1 || first[o] + count[o] > n[t]) return XGPU_ERR_UNEXPECTED;
@@ -94,6 +97,16 @@ int scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_lo
         }
     }
     return XGPU_OK;
+}
+int scale_build_tables(int ws, int hs, int wd, int hd, int filter, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb, int x_off)
+{
+    return build_tables(ws, hs, wd, hd, chroma_loc, blob, tb, x_off, [filter](int n, int s, int h, int N, int32_t *first, int32_t *count, int16_t *w, int stride) {
+        return xgpu_scale_taps(n, s, h, N, filter, first, count, w, stride); });
+}
+int resample_build_tables(int ws, int hs, int wd, int hd, int kernel, int antialias, int chroma_loc, std::vector<uint8_t> &blob, ScaleTabs &tb, int x_off)
+{
+    return build_tables(ws, hs, wd, hd, chroma_loc, blob, tb, x_off, [kernel, antialias](int n, int s, int h, int N, int32_t *first, int32_t *count, int16_t *w, int stride) {
+        return xgpu_resample_taps(n, s, h, N, kernel, antialias, first, count, w, stride); });
 }
 
 // One table of the surface ladder (k_output_ladder.hip) behind what `blob` holds already: first[], count[] and the weights - row by row (a vertical table) or

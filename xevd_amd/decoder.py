@@ -457,6 +457,60 @@ class XgpuDecoder:
             return self._pic_output_tensor_rois(a, cm, bool(linear_light))
         return self._pic_output_tensor_scaled(a, cm, bool(linear_light))
 
+    def pic_output_resampled(self, pic, size, kernel="catmull-rom", antialias=True, rois=None, fit=None, pad=None, layout="rgb", channels_last=False, dtype=None,
+                             matrix=1, full_range=False, chroma_loc=0, crop=(0, 0, 0, 0), dra=None, bgr=False, mean=None, std=None, out=None):
+        """The scaled output with a bicubic filter (xgpu_pic_output_device_resampled / _rois_resampled): the picture - or, with host
+        rois=[(x, y, w, h), ...], every rectangle - resized to size=(H, W) on torch's current stream: [3, H, W] (channels_last: [H, W, 3]), with rois
+        [N, 3, H, W] / [N, H, W, 3].  kernel "catmull-rom" (alias "bicubic": Keys a = -1/2, PIL's BICUBIC and torch's bicubic with antialias=True), "cubic-0.75"
+        (Keys a = -3/4: torch's bicubic with antialias=False, OpenCV's INTER_CUBIC) or "mitchell"; antialias=True widens the kernel by the reduction ratio.
+        Every other argument is pic_output_tensor's with size=; fit "stretch" (None) or "letterbox" and pad belong to rois=.  Boxes in device memory, colour
+        transforms, the ladder, warped and remapped outputs have no bicubic form; pic_output_tensor(filter=...) keeps its two names."""
+        import torch
+        if kernel not in abi.RESAMPLE_KERNELS:
+            raise ValueError(f"kernel must be one of {sorted(abi.RESAMPLE_KERNELS)}, not {kernel!r}")
+        if antialias not in (True, False, 0, 1):
+            raise ValueError(f"antialias must be True or False, not {antialias!r}")
+        if isinstance(rois, torch.Tensor):
+            raise ValueError("rois: boxes in device memory have no bicubic form")
+        if rois is None and (fit is not None or pad is not None):
+            raise ValueError("fit and pad belong to rois=")
+        a = {"pic": pic, "layout": layout, "channels_last": channels_last, "dtype": dtype, "matrix": matrix, "full_range": full_range, "chroma_loc": chroma_loc,
+             "crop": crop, "dra": dra, "out": out, "bgr": bgr, "out_bit_depth": 0, "colour": None, "size": size, "filter": "bilinear", "mean": mean, "std": std,
+             "fit": fit or "stretch"}
+        code = abi.FIT_STRETCH if rois is None else self._rois_fit(a)
+        dtype, fmt, sc, h, w, dev = self._scaled_setup(a)
+        rs = abi.make_resample_params(w, h, kernel, bool(antialias), mean=mean, std=std)
+        planar, batch = not channels_last, rois is not None
+        if batch:
+            rois = [tuple(int(v) for v in r) for r in rois]
+            n, ra, rp = len(rois), abi.make_rois(rois), abi.make_roi_params(code, 0.0 if pad is None else pad)
+
+        def refuse():
+            bad = C.c_int(-1)
+            if batch:
+                rc = self.lib.xgpu_output_rois_resampled_check(C.byref(fmt), C.byref(rs), C.byref(rp), ra, n, self.width, self.height, self.bit_depth, C.byref(bad))
+            else:
+                rc = self.lib.xgpu_output_resampled_check(C.byref(fmt), C.byref(rs), self.width, self.height, self.bit_depth)
+            if rc < 0:
+                at = f"roi {bad.value} {rois[bad.value]}: " if batch and 0 <= bad.value < n else ""
+                raise ValueError(f"invalid resampled output ({rc}): {at}layout {layout}, size {tuple(size)}, kernel {kernel}, fit {fit}, pad {pad}, matrix {matrix}, "
+                                 f"chroma_loc {chroma_loc}, crop {crop}, mean {mean}, std {std}")
+        if out is None:
+            refuse()      # before a tensor is made, and again with its pitches
+        image = (3, h, w) if planar else (h, w, 3)
+        out = _out_tensor(out, (n,) + image if batch else image, dtype, dev)
+        st = out.stride()
+        fmt.row_pitch = _row_pitch(st, planar, h, w if planar else 3 * w, 3) * dtype.itemsize
+        if batch:
+            rp.image_pitch = st[0] * dtype.itemsize if n > 1 else 0
+        refuse()
+        dl, self._dra_keep = self._dra_luts(dra) if dra is not None else (None, None)      # (kept until the next call: the tables are copied asynchronously)
+        if batch:
+            self._device_call("xgpu_pic_output_device_rois_resampled", out, pic, dl, C.byref(fmt), C.byref(rs), C.byref(rp), ra, n)
+        else:
+            self._device_call("xgpu_pic_output_device_resampled", out, pic, dl, C.byref(fmt), C.byref(rs))
+        return out
+
     def pic_output_surfaces(self, pic, sizes, layout="nv12", dtype=None, out_bit_depth=0, filter="bilinear", chroma_loc=0, dst_chroma_loc=None, crop=(0, 0, 0, 0),
                             dra=None, out=None):
         """The picture as a ladder of scaled video surfaces - one tensor per (H, W) of `sizes` (1 .. abi.MAX_RUNGS, even), all in one layout "nv12", "p016" or

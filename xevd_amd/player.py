@@ -117,7 +117,7 @@ class StreamDecoder:
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
                  residual=None, compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
-                 linear_light=False):
+                 linear_light=False, resample=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -135,6 +135,9 @@ class StreamDecoder:
         defaults to the SPS crop when apply_crop is set (kind "energy": no crop)
         size=(H, W), mean=, std= (with tensor=, layouts "rgb" / "yuv444"): every picture resized to H x W and normalised in the same call (pic_output_tensor's
         size / mean / std; tensor=dict(filter="area") for the box filter) - what a model takes, without a full-size tensor in between
+        resample="bicubic" | "catmull-rom" | "cubic-0.75" | "mitchell" or dict(kernel=, antialias=) (with tensor= and size=; host rois=, fit=, pad= go with it):
+        that resize with a bicubic filter instead (XgpuDecoder.pic_output_resampled) - the resize CLIP / SigLIP, DINOv2 and most timm models were trained
+        with.  Not together with to=, linear_light, warp=, remap= or boxes in device memory
         rois=[(x, y, w, h), ...] or a callable(params) -> such a list (with tensor= and size=; called behind the picture's kernels, so params["side_info"] is
         there when side= is given), fit=, pad=: every picture as the batch [N, 3, H, W] of its rectangles (pic_output_tensor's rois / fit / pad;
         tensor=dict(snap=True) for boxes a detector made).  The list, or what the callable returns, may also be a torch tensor on the decoder's device - int32
@@ -178,6 +181,16 @@ class StreamDecoder:
             raise ValueError("remap: not together with rois= or warp=")
         if remap is not None and (tensor is None or size is None or to is not None):
             raise ValueError("remap: needs tensor=dict(...) and size=(H, W), and takes no colour transform")
+        if resample is not None:
+            if tensor is None or size is None:
+                raise ValueError("resample: needs tensor=dict(...) and size=(H, W)")
+            if to is not None or linear_light or warp is not None or remap is not None:
+                raise ValueError("resample: the bicubic resize takes no colour transform (to=, linear_light) and has no warped or remapped form")
+            if rois is not None and not callable(rois) and not isinstance(rois, (list, tuple)):
+                raise ValueError("resample: boxes in device memory have no bicubic form - rois= a list of rectangles, or a callable that returns one")
+            resample = {"kernel": resample} if isinstance(resample, str) else dict(resample)
+            if set(resample) - {"kernel", "antialias"}:
+                raise ValueError(f"resample: a kernel name or dict(kernel=, antialias=), not the keys {sorted(set(resample) - {'kernel', 'antialias'})}")
         q = queue.Queue(maxsize=self.prefetch)
         th = threading.Thread(target=self._producer, args=(q,), daemon=True)
         th.start()
@@ -246,7 +259,9 @@ class StreamDecoder:
                     if v is not None:
                         kw.setdefault(k, v)
                 with self._lock:
-                    if warp is not None:
+                    if resample is not None:
+                        planes = dec.pic_output_resampled(cur, **resample, **kw)
+                    elif warp is not None:
                         planes = dec.pic_output_warped(cur, warp(p) if callable(warp) else warp, **kw)
                     elif remap is not None:
                         planes = dec.pic_output_remapped(cur, remap(p) if callable(remap) else remap, step=remap_step, **kw)
@@ -303,17 +318,17 @@ class StreamDecoder:
 
     def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
                      compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
-                     linear_light=False):
+                     linear_light=False, resample=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
         params["residual"] as numpy - for kind "yuv420" the pair (flat array, (Y, Cb, Cr) views of it); compare= (as pictures takes it, the callable and the
         sequence in DECODING order): params["compare"], its map as a numpy array; stats= (as pictures takes it): params["stats"], its histograms as numpy arrays;
-        surfaces= / surface_layout= / surface_options= (as pictures takes them): params["surfaces"], a list of numpy arrays"""
+        surfaces= / surface_layout= / surface_options= (as pictures takes them): params["surfaces"], a list of numpy arrays; resample= (as pictures takes it)"""
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
                                        residual=residual, compare=compare, stats=stats, warp=warp, remap=remap, remap_step=remap_step, surfaces=surfaces,
-                                       surface_layout=surface_layout, surface_options=surface_options, linear_light=linear_light):
+                                       surface_layout=surface_layout, surface_options=surface_options, linear_light=linear_light, resample=resample):
             if p["is_idr"]:
                 epoch += 1
             if surfaces is not None:      # (synchronises torch's current stream: the tensors are complete)
