@@ -470,6 +470,48 @@ size_t xgpu_output_rois_resampled_size(const xgpu_output_format *f, const xgpu_r
                                        int width, int height, int bit_depth);
 int    xgpu_pic_output_device_rois_resampled(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_resample_params *rs,
                                              const xgpu_roi_params *rp, const xgpu_roi *rois, int n_rois, void *d_dst, size_t dst_size, void *stream);
+/* ---- packed display surfaces (k_output_packed.hip): the picture as one word per pixel for a compositor or a swap chain, or as packed 4:2:2 for a capture /
+   SDI path or an encoder that takes it.  Calls of their own with a format struct of their own: xgpu_output_format keeps its seven layouts.  W x H: the picture
+   minus crop, B the coding depth, es the element size.
+     XGPU_PACKED_RGBA     H rows of W x 4 elements R G B A (bgr: B G R A), dtype U8 | U16 | F16 | BF16 | F32.  R, G, B are, bit for bit, the three elements
+                          xgpu_pic_output_device writes for XGPU_OUT_RGB_INTERLEAVED with the same dtype, matrix, full_range, chroma_loc, upsample, bgr, crop and
+                          DRA - with `cm` those of xgpu_pic_output_device_cm; out_bit_depth 0 or B.  A: integer dtypes floor(alpha * (2^D - 1) + 0.5), made once
+                          on the host in double, D = 8 for U8, else B; float dtypes: float32(alpha) through the dtype's rounding.
+     XGPU_PACKED_RGB10A2  H rows of W little-endian 32-bit words R | G << 10 | B << 20 | A << 30 (bgr: B low, R at 20); dtype and out_bit_depth 0; d_dst aligned
+                          to 4.  The channels are 10-bit codes of the integer rule above with D = 10 whatever B is: coefficients round(k * 1023 / range * 2^17),
+                          channel = clip((sum + 2^16) >> 17, 0, 1023) - on a 10-bit stream the U16 output's values.  With `cm` the code at depth B goes into the
+                          transform (as for every dtype) and the store is rint(q * 1023).  A = floor(alpha * 3 + 0.5).
+     XGPU_PACKED_YUYV     4:2:2, H rows of W x 2 elements, per pair of pixels Y0 Cb Y1 Cr; XGPU_PACKED_UYVY: Cb Y0 Cr Y1.  Luma is NV12's.  Chroma stays at half
+                          width and goes to full height: row r from the rows around i = r >> 1 of the cropped chroma plane, edge-clamped, every sample DRA-mapped
+                          first - NEAREST: row i; LINEAR: even r (ve0 * C[max(i-1, 0)] + ve1 * C[i] + 2) >> 2, odd r (vo0 * C[i] + vo1 * C[min(i+1, H/2-1)] + 2) >> 2
+                          with the vertical quarter weights of chroma_loc (centred (1,3) / (3,1), top (0,4) / (2,2), bottom (2,2) / (4,0); its horizontal bit is
+                          not read).  Every sample then takes xgpu_pic_output's depth conversion to D.  U8: out_bit_depth must be 8 (YUY2 / UYVY); U16: D =
+                          out_bit_depth (0 = B, else 8..16), word = sample << (16 - D), P016's rule (D = 10 is Y210).  bgr must be 0; matrix, full_range and
+                          alpha are not read; a transform is XGPU_ERR_INVALID_ARGUMENT.
+   A row is 4 W es (RGBA), 4 W (RGB10A2) or 2 W es (4:2:2) bytes; row_pitch (0 = tight) is a multiple of the element (of 4 for RGB10A2) and not shorter than a row;
+   the size is (H - 1) * pitch + row.  Crop, picture size and depth limits are xgpu_output_format_size's.  alpha (RGBA, RGB10A2) must be finite and in [0, 1].  An
+   unsupported matrix or transform is XGPU_ERR_UNSUPPORTED, every other refusal XGPU_ERR_INVALID_ARGUMENT, all before anything is queued.  d_dst, dst_size, stream
+   and the ordering are xgpu_pic_output_device's; the colour tables are xgpu_pic_output_device_cm's cache.  The exact contract: INTEGRATION.md section 8p;
+   tests/packed_ref.py restates it in numpy. */
+#define XGPU_PACKED_RGBA     0   /* four elements per pixel: R G B A (bgr: B G R A); dtype U8 | U16 | F16 | BF16 | F32          */
+#define XGPU_PACKED_RGB10A2  1   /* one little-endian 32-bit word per pixel: R | G << 10 | B << 20 | A << 30 (bgr: B low, R at 20) */
+#define XGPU_PACKED_YUYV     2   /* 4:2:2, per pair of pixels Y0 Cb Y1 Cr; U8 (YUY2) or U16 (Y210 / Y212 / Y216)                 */
+#define XGPU_PACKED_UYVY     3   /* Cb Y0 Cr Y1; U8 or U16                                                                        */
+typedef struct xgpu_packed_format {
+    int layout, bgr, dtype, out_bit_depth;
+    int matrix, full_range, chroma_loc, upsample;   /* as xgpu_output_format reads them */
+    int crop[4];
+    size_t row_pitch;                               /* bytes between rows; 0 = tight */
+    float alpha;                                    /* RGBA, RGB10A2: in [0, 1] */
+} xgpu_packed_format;
+/* Host only, no context.  _size: the bytes at d_dst, 0: refused.  _check: 0 or the code the call would refuse (f, cm) with.  _coeffs (RGBA, RGB10A2; no transform):
+   xgpu_output_coeffs' results for the layout - RGB10A2: D = 10, S = 17 - and alpha_code = the A element (float dtypes: the float32 bits of alpha, before the
+   dtype's rounding). */
+size_t xgpu_output_packed_size(const xgpu_packed_format *f, int width, int height, int bit_depth);
+int    xgpu_output_packed_check(const xgpu_packed_format *f, const xgpu_colour_transform *cm, int width, int height, int bit_depth);
+int    xgpu_output_packed_coeffs(const xgpu_packed_format *f, int bit_depth, int32_t coef[5], int *shift, float fcoef[5], uint32_t *alpha_code);
+int    xgpu_pic_output_device_packed(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f,
+                                     const xgpu_colour_transform *cm /* NULL: none */, void *d_dst, size_t dst_size, void *stream);
 /* ---- regions of interest from device memory (k_output_rois_dev.hip): xgpu_pic_output_device_rois for boxes that a detector left on the GPU.  d_boxes points
    to `capacity` boxes in device memory (1 .. XGPU_MAX_ROIS), d_count (may be NULL: all of them) to a device int32 - the live boxes are the first
    min(max(*d_count, 0), capacity).  The host reads neither; the call does not synchronise and nothing comes back to the host.  Descriptors and tap tables are

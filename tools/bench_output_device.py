@@ -73,8 +73,12 @@ then per rung and plane torch's interpolate(bilinear, antialias=True), rounding 
 picture once; four one-rung calls are alternated on their own (each makes its tap tables again: the context keeps those of one key).  `device_us` is the time
 of the kernels alone (median of --iters calls queued behind a wait).  The largest difference between each rung's planes and the torch route in float64 is
 recorded in code values; it is a record, not a test.
+The packed leg (xgpu_pic_output_device_packed: k_output_packed_rgb / k_output_packed_422) writes RGBA u8, RGBA f16, RGBA u8 through PQ / BT.2020 -> sRGB, 10:10:10:2,
+YUYV u8 and Y210 and alternates - the rois leg's protocol - each with the nearest call that existed before it (the interleaved RGB tensor of the dtype, NV12, P010) and
+with the torch route it replaces on top of that call (a cat with an alpha plane; shifts and ors on an int32 tensor; a row repeat and a stack).  Next to the times:
+the ratio of the bytes the two calls move, and whether the packed call takes more than that ratio of its counterpart's time beyond the spread of the run.
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|resampled|rois|rois_dev|ladder|warp|remap|residual|compare|stats] [--out out/output_device.json]
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|resampled|rois|rois_dev|ladder|warp|remap|residual|compare|stats|packed] [--out out/output_device.json]
 """
 import argparse
 import json
@@ -457,6 +461,60 @@ def alternated(torch, s, routes, iters, warm=5):
         r[k] = {"us": round(float(np.median(us)), 2), "p10_us": round(float(np.percentile(us, 10)), 2), "p90_us": round(float(np.percentile(us, 90)), 2),
                 "host_us": round(float(np.median(host[k])), 2)}
     return r
+
+
+def packed_leg(torch, dec, pic, s, a, res, copy_gbps):
+    """every packed call alternated (i) with the nearest call that existed before it - the interleaved RGB tensor of its dtype, NV12, P010 - and (ii) with the torch
+    route it replaces on top of that call; next to the times the bytes either side moves per pixel (3 read + what it writes) and whether the packed call takes
+    more than that byte ratio of its counterpart's time beyond the spread of the run (its 10th percentile against the counterpart's 90th)"""
+    w, h = a.width, a.height
+    to_srgb = dict(src_primaries=9, src_transfer=16, dst_primaries=1, dst_transfer=13, tone_map=True)
+
+    def rgba_route(kw, dt, one):      # cat with an alpha plane: a copy of the picture
+        rgb = dec.pic_output_tensor(pic, channels_last=True, dtype=dt, **kw)
+        return torch.cat([rgb, torch.full((h, w, 1), one, dtype=dt, device=rgb.device)], dim=-1)
+
+    def rgb10_route():                # three shifts and two ors on an int32 tensor
+        v = dec.pic_output_tensor(pic, channels_last=True, dtype=torch.int16).to(torch.int32)
+        return v[..., 0] | (v[..., 1] << 10) | (v[..., 2] << 20) | (-1 << 30)      # (alpha 3: the two high bits)
+
+    def yuyv_route(kw):               # a row repeat and a stack
+        nv = dec.pic_output_tensor(pic, **kw)
+        return torch.stack([nv[:h], nv[h:].repeat_interleave(2, 0)], dim=-1)
+
+    u8, f16, i16 = torch.uint8, torch.float16, torch.int16
+    p010 = dict(layout="p016", dtype=i16, out_bit_depth=10)
+    cases = [("rgba_u8", dict(layout="rgba", dtype=u8), dict(channels_last=True, dtype=u8), lambda: rgba_route({}, u8, 255), 4, 3),
+             ("rgba_f16", dict(layout="rgba", dtype=f16), dict(channels_last=True, dtype=f16), lambda: rgba_route({}, f16, 1.0), 8, 6),
+             ("rgba_u8_cm_pq2020_srgb", dict(layout="rgba", dtype=u8, matrix=9, colour=to_srgb), dict(channels_last=True, dtype=u8, matrix=9, colour=to_srgb),
+              lambda: rgba_route(dict(matrix=9, colour=to_srgb), u8, 255), 4, 3),
+             ("rgb10a2", dict(layout="rgb10a2"), dict(channels_last=True, dtype=i16), rgb10_route, 4, 6),
+             ("yuyv_u8", dict(layout="yuyv", dtype=u8), dict(layout="nv12", dtype=u8), lambda: yuyv_route(dict(layout="nv12", dtype=u8)), 2, 1.5),
+             ("y210", dict(layout="yuyv", dtype=i16, out_bit_depth=10), p010, lambda: yuyv_route(p010), 4, 3)]
+    res["packed"] = {"copy_gbps": copy_gbps, "cases": {}}
+    for name, pkw, ckw, route, wp, wc in cases:
+        out_p, out_c = dec.pic_output_packed(pic, **pkw), dec.pic_output_tensor(pic, **ckw)
+        r = alternated(torch, s, {"packed": lambda: dec.pic_output_packed(pic, out=out_p, **pkw), "counterpart": lambda: dec.pic_output_tensor(pic, out=out_c, **ckw)},
+                       a.iters)
+        rt = alternated(torch, s, {"packed": lambda: dec.pic_output_packed(pic, out=out_p, **pkw), "torch_route": route}, max(a.iters // 10, 5), warm=2)
+        r["torch_route"] = rt["torch_route"]
+        r["packed_beside_torch_route"] = rt["packed"]
+        nbytes = int(w * h * (3 + wp))
+        r["packed"].update(bytes=nbytes, gbps=round(nbytes / (r["packed"]["us"] * 1e-6) / 1e9, 1))
+        r["packed"]["frac_copy"] = round(r["packed"]["gbps"] / copy_gbps, 3)
+        r["byte_ratio"] = round((3 + wp) / (3 + wc), 3)
+        r["time_ratio"] = round(r["packed"]["us"] / r["counterpart"]["us"], 3)
+        r["over_byte_ratio_beyond_spread"] = bool(r["packed"]["p10_us"] > r["byte_ratio"] * r["counterpart"]["p90_us"])
+        r["torch_route_over_packed"] = round(rt["torch_route"]["us"] / rt["packed"]["us"], 2)
+        same = route()
+        it = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[out_p.element_size()]
+        ekw = dict(pkw, upsample="nearest") if pkw["layout"] == "yuyv" else pkw      # (the row repeat is NEAREST; the timed call is the default, LINEAR)
+        r["torch_route_equals_kernel"] = bool(torch.equal(same.contiguous().view(it), dec.pic_output_packed(pic, **ekw).view(it)))
+        res["packed"]["cases"][name] = r
+        print(f"packed {name:24s} {r['packed']['us']:8.1f} us ({r['packed']['p10_us']:.1f} - {r['packed']['p90_us']:.1f})  {r['packed']['gbps']:7.1f} GB/s "
+              f"{r['packed']['frac_copy']:.2f} of copy   counterpart {r['counterpart']['us']:8.1f} us ({r['counterpart']['p10_us']:.1f} - {r['counterpart']['p90_us']:.1f})  "
+              f"time x{r['time_ratio']:.2f} for bytes x{r['byte_ratio']:.2f}{'  OVER' if r['over_byte_ratio_beyond_spread'] else ''}   "
+              f"torch route {rt['torch_route']['us']:8.1f} us = x{r['torch_route_over_packed']:.1f}, equal {r['torch_route_equals_kernel']}")
 
 
 def ladder_leg(torch, dec, pic, s, a, res):
@@ -894,10 +952,10 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "resampled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats"), default="all",
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "resampled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats", "packed"), default="all",
                     help="full: the full-size forms and the side information; scaled: the scaled leg alone; scaled_cm: the colour-managed scaled output alone; scaled_lin: the scaled output filtered in linear light alone; resampled: the bicubic resize alone; rois: the batched regions of interest alone; "
                          "rois_dev: the regions of interest from boxes in device memory alone; ladder: the ladder of scaled P010 surfaces alone; warp: the warped regions of interest alone; remap: the remapped output alone; residual: the residual "
-                         "export alone; compare: the picture comparison alone; stats: the picture statistics alone")
+                         "export alone; compare: the picture comparison alone; stats: the picture statistics alone; packed: the packed display surfaces alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -943,6 +1001,8 @@ def main():
             rois_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "rois_dev"):
             rois_dev_leg(torch, dec, pic, s, a, res)
+        if a.legs in ("all", "packed"):
+            packed_leg(torch, dec, pic, s, a, res, copy_gbps)
         if a.legs in ("all", "ladder"):
             ladder_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "warp"):

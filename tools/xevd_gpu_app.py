@@ -3,6 +3,8 @@
 application (app/xevd_app.c: -i in.evc -o out.yuv --output-bit-depth N).  usage: xevd_gpu_app.py -i in.evc -o out.yuv
 --pix-fmt nv12 / p010 writes semi-planar frames instead (what a raw-video reader takes as nv12 / p010le): 8-bit samples, or 10-bit samples in the
 high bits of 16-bit words, whatever the stream's depth.
+--pix-fmt rgba / bgra / x2bgr10le / x2rgb10le / yuyv422 / uyvy422 / y210le writes packed display surfaces, raw frames a raw-video reader takes
+under those names; the RGB ones compose with --to.
 --ladder 3840x2160,1920x1080,... also writes every picture scaled to each of these sizes on the device, in one call per picture: one file per
 rung next to -o, the size in its name (out_1920x1080.yuv), in the --pix-fmt layout."""
 import argparse
@@ -12,6 +14,12 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from xevd_amd.player import StreamDecoder      # noqa: E402
+
+
+# --pix-fmt names of the packed display surfaces -> the keyword arguments of XgpuDecoder.pic_output_packed (dtype: torch's name)
+PACKED_PIX_FMTS = {"rgba": dict(layout="rgba", dtype="uint8"), "bgra": dict(layout="bgra", dtype="uint8"), "x2bgr10le": dict(layout="rgb10a2"),
+                   "x2rgb10le": dict(layout="bgr10a2"), "yuyv422": dict(layout="yuyv", dtype="uint8"), "uyvy422": dict(layout="uyvy", dtype="uint8"),
+                   "y210le": dict(layout="yuyv", dtype="int16", out_bit_depth=10)}
 
 
 class RefCompare:
@@ -128,8 +136,10 @@ def main():
     ap.add_argument("-i", "--input", required=True)
     ap.add_argument("-o", "--output")
     ap.add_argument("--output-bit-depth", type=int, default=0, help="0 = the stream's bit depth (8 -> bytes, else 16-bit little endian)")
-    ap.add_argument("--pix-fmt", choices=("yuv420p", "nv12", "p010"), default="yuv420p",
-                    help="nv12: 8-bit semi-planar; p010: 10 bit in 16-bit little-endian words, semi-planar (both ignore --output-bit-depth)")
+    ap.add_argument("--pix-fmt", choices=("yuv420p", "nv12", "p010") + tuple(PACKED_PIX_FMTS), default="yuv420p",
+                    help="nv12: 8-bit semi-planar; p010: 10 bit in 16-bit little-endian words, semi-planar; rgba / bgra: four bytes per pixel, alpha 255; "
+                    "x2bgr10le / x2rgb10le: one 10:10:10:2 little-endian word per pixel (R / B in the low bits), alpha 3; yuyv422 / uyvy422: packed 8-bit 4:2:2; "
+                    "y210le: packed 4:2:2, 10 bit in the high bits of 16-bit words (all ignore --output-bit-depth; the RGB ones take --to)")
     ap.add_argument("--to", default=None, help="write interleaved 8-bit RGB frames in this colour space instead (srgb, bt709, pq-bt2020, ...: "
                     "StreamDecoder.COLOUR_PRESETS), converted on the device from the primaries / transfer characteristics of the stream's VUI")
     ap.add_argument("--side-info", default=None, metavar="FILE", help="also write the coding side information of every picture, in DECODING order: a text line "
@@ -163,6 +173,8 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
     lad, lad_sizes = {}, []
+    if args.pix_fmt in PACKED_PIX_FMTS and (args.ladder is not None or args.size is not None):
+        ap.error(f"--pix-fmt {args.pix_fmt}: the packed surfaces have no scaled form (--size, --ladder)")
     if args.ladder is not None:
         import torch
         if not args.output:
@@ -221,6 +233,13 @@ def main():
             remap = torch.from_numpy(remap).to(f"cuda:{args.device}")      # uploaded once, used for every picture
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), size=(hd, wd), to=args.to, side=side, rois=rois, residual=resid, compare=cmp, stats=stats,
                                                                     remap=remap, remap_step=args.remap_step, linear_light=args.linear_light, resample=args.resample, **lad)
+    elif args.pix_fmt in PACKED_PIX_FMTS:      # one word per pixel or packed 4:2:2 (xgpu_pic_output_device_packed); --to takes the RGB ones to that colour space
+        import torch
+        opts = {k: getattr(torch, v) if k == "dtype" else v for k, v in PACKED_PIX_FMTS[args.pix_fmt].items()}
+        if args.to is not None and opts["layout"] in ("yuyv", "uyvy"):
+            ap.error(f"--to: a colour transform needs an RGB --pix-fmt, not {args.pix_fmt}")
+        pics = StreamDecoder(data, device=args.device).output_order(packed=opts, to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad)
+        pics = [(p, p["packed"]) for p, _ in pics]
     elif args.to is not None:
         import torch
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad)

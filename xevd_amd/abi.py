@@ -56,6 +56,36 @@ def make_output_format(layout=OUT_RGB_PLANAR, dtype=OUT_U8, bgr=False, out_bit_d
     return f
 
 
+PACKED_RGBA, PACKED_RGB10A2, PACKED_YUYV, PACKED_UYVY = 0, 1, 2, 3
+
+
+class PackedFormat(C.Structure):
+    _fields_ = [("layout", C.c_int), ("bgr", C.c_int), ("dtype", C.c_int), ("out_bit_depth", C.c_int),
+                ("matrix", C.c_int), ("full_range", C.c_int), ("chroma_loc", C.c_int), ("upsample", C.c_int),
+                ("crop", C.c_int * 4), ("row_pitch", C.c_size_t), ("alpha", C.c_float)]
+
+
+def make_packed_format(layout=PACKED_RGBA, dtype=OUT_U8, bgr=False, out_bit_depth=0, matrix=1, full_range=False, chroma_loc=0,
+                       upsample=UPSAMPLE_LINEAR, crop=(0, 0, 0, 0), row_pitch=0, alpha=1.0):
+    """xgpu_packed_format (include/xevd_hip.h): the packed display surfaces of xgpu_pic_output_device_packed"""
+    f = PackedFormat()
+    f.layout, f.bgr, f.dtype, f.out_bit_depth = int(layout), int(bool(bgr)), int(dtype), int(out_bit_depth)
+    f.matrix, f.full_range, f.chroma_loc, f.upsample = int(matrix), int(bool(full_range)), int(chroma_loc), int(upsample)
+    for i in range(4):
+        f.crop[i] = int(crop[i])
+    f.row_pitch, f.alpha = int(row_pitch), float(alpha)
+    return f
+
+
+def packed_coeffs(lib, fmt, bit_depth):
+    """xgpu_output_packed_coeffs -> (coef [5], shift, fcoef float32 [5], alpha_code), or the negative code"""
+    coef, shift, fcoef, alpha = (C.c_int32 * 5)(), C.c_int(), (C.c_float * 5)(), C.c_uint32()
+    rc = lib.xgpu_output_packed_coeffs(C.byref(fmt), int(bit_depth), coef, C.byref(shift), fcoef, C.byref(alpha))
+    if rc < 0:
+        return rc
+    return list(coef), shift.value, np.array(list(fcoef), np.float32), alpha.value
+
+
 SIDE_BLOCKS, SIDE_FLOW_PLANAR, SIDE_FLOW_INTERLEAVED = 0, 1, 2
 MODE_IBC = 6
 
@@ -743,6 +773,11 @@ _EXPORTS = {
     "xgpu_output_coeffs": (C.c_int, [C.POINTER(OutputFormat), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "xgpu_colour_tables": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ColourTransform), C.c_int, C.POINTER(ColourTables)]),
     "xgpu_pic_output_device_cm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ColourTransform), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_output_packed_size": (C.c_size_t, [C.POINTER(PackedFormat), C.c_int, C.c_int, C.c_int]),
+    "xgpu_output_packed_check": (C.c_int, [C.POINTER(PackedFormat), C.POINTER(ColourTransform), C.c_int, C.c_int, C.c_int]),
+    "xgpu_output_packed_coeffs": (C.c_int, [C.POINTER(PackedFormat), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "xgpu_pic_output_device_packed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PackedFormat), C.POINTER(ColourTransform), C.c_void_p, C.c_size_t,
+                                                C.c_void_p]),
     "xgpu_scale_taps": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16), C.c_int]),
     "xgpu_output_scaled_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),
     "xgpu_output_scaled_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),

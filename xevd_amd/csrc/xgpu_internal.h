@@ -660,6 +660,22 @@ struct SemiPlanarArgs {
     const int32_t *dra;             // [3][1024] DRA inverse tables, or NULL
 };
 void launch_output_semiplanar(const SemiPlanarArgs &a, int dtype, hipStream_t s);
+// k_output_packed.hip (xgpu_pic_output_device_packed).  k_output_packed_rgb: CmOutArgs (cm is read only with a transform; `plane` is not
+// read) and the A element; RGB10A2 runs the U16 instances with coef / shift / maxv (cm.outmax) of D = 10.
+struct PackedRgbArgs : CmOutArgs {
+    uint32_t alpha;                 // the bits of the A element (float dtypes: the float32 bits of alpha, rounded to the dtype in the kernel); RGB10A2: the 2-bit code
+};
+void launch_output_packed_rgb(const PackedRgbArgs &a, int layout, int dtype, int upsample, bool cm, hipStream_t s);      // not: RGBA, a float dtype, no transform
+// ... which is k_output_rgb's interleaved image at `mid` (rows mid_pitch bytes apart: a multiple of 16 that holds a multiple of 8 pixels) and this copy behind it;
+// reads a's w, h, dst, pitch, aligned and alpha
+void launch_packed_rgba_from_rgb(const PackedRgbArgs &a, int dtype, const uint8_t *mid, size_t mid_pitch, hipStream_t s);
+// k_output_packed_422: RgbOutArgs' source, size, destination, ve / vo and DRA fields (chroma_row reads them; the matrix fields and hc are not read), then
+// SemiPlanarArgs' conversion
+struct Packed422Args : RgbOutArgs {
+    int      cshift, out8, cmax;    // conv1's arguments at depth D: B - D, D == 8, 2^D - 1
+    int      lsh;                   // U16: 16 - D, the sample in the high bits of the word; U8: 0
+};
+void launch_output_packed_422(const Packed422Args &a, int dtype, bool uyvy, int upsample, hipStream_t s);
 // k_side_info.hip: the SCU map of the picture decoded last as nine int16 planes per unit (k_side_blocks) or as a dense motion field (k_side_flow)
 struct SideArgs {
     const ScuRec *maps;

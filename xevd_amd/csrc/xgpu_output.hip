@@ -1,4 +1,4 @@
-// xgpu_output.hip - the C ABI of include/xevd_hip.h, part 2: the outputs into device memory - the picture as it is, colour-managed, scaled, as a batch of regions of
+// xgpu_output.hip - the C ABI of include/xevd_hip.h, part 2: the outputs into device memory - the picture as it is, colour-managed, as a packed display surface, scaled, as a batch of regions of
 // interest (rectangles from the host or boxes in device memory), of affine maps or of coordinate grids, as a ladder of scaled video surfaces, the coding side information, the residual, the comparison with a reference and the statistics
 // of one picture - and their argument checks without a device.
 // Every entry point is the same skeleton: check the format -> check_dst -> (check_dra; tables, made on the host) -> grow a context buffer -> out_fork -> fill an args struct ->
@@ -189,18 +189,15 @@ static void range_terms(int bd, int full_range, int *yo, double *yr, double *cr)
     *yr = full_range ? (double)((1 << bd) - 1) : (double)(219 << (bd - 8));
     *cr = full_range ? (double)((1 << bd) - 1) : (double)(224 << (bd - 8));
 }
-int xgpu_output_coeffs(const xgpu_output_format *f, int bit_depth, int32_t coef[5], int *shift, float fcoef[5])
+// the matrix of a supported `matrix` at coding depth bd: fcoef = the float32 coefficients (2^D - 1 = 1) and, for integer elements of depth d (0: none - zeros),
+// coef = round(k * (2^d - 1) / range * 2^S) with S = 27 - d
+static void matrix_coeffs(int matrix, int full_range, int bit_depth, int d, int32_t coef[5], int *shift, float fcoef[5])
 {
-    const char *why;
-    if (bit_depth < 8 || bit_depth > 12 || !coef || !shift || !fcoef) return XGPU_ERR_INVALID_ARGUMENT;
-    const int rc = check_format(f, bit_depth, &why);
-    if (rc < 0) return rc;
-    if (!is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
     double kr, kb, yr, cr;
     int yo;
-    matrix_kr_kb(f->matrix, &kr, &kb);
+    matrix_kr_kb(matrix, &kr, &kb);
     const double kg = 1.0 - kr - kb;
-    range_terms(bit_depth, f->full_range, &yo, &yr, &cr);
+    range_terms(bit_depth, full_range, &yo, &yr, &cr);
     // the same expressions, term for term, as tests/colour_ref.py (a different order of the double operations could round differently)
     auto terms = [&](double m, double sc, double t[5]) {
         t[0] = m / yr * sc;
@@ -212,15 +209,24 @@ int xgpu_output_coeffs(const xgpu_output_format *f, int bit_depth, int32_t coef[
     double t[5];
     terms(1.0, 1.0, t);
     for (int i = 0; i < 5; i++) fcoef[i] = (float)t[i];
-    if (f->dtype != XGPU_OUT_U8 && f->dtype != XGPU_OUT_U16) {
+    if (!d) {
         for (int i = 0; i < 5; i++) coef[i] = 0;
         *shift = 0;
-        return XGPU_OK;
+        return;
     }
-    const int d = f->dtype == XGPU_OUT_U8 ? 8 : bit_depth, sh = 27 - d;
+    const int sh = 27 - d;
     terms((double)((1 << d) - 1), (double)(1 << sh), t);
     for (int i = 0; i < 5; i++) coef[i] = (int32_t)round(t[i]);      // half away from zero; cgu and cgv are negated rounded magnitudes
     *shift = sh;
+}
+int xgpu_output_coeffs(const xgpu_output_format *f, int bit_depth, int32_t coef[5], int *shift, float fcoef[5])
+{
+    const char *why;
+    if (bit_depth < 8 || bit_depth > 12 || !coef || !shift || !fcoef) return XGPU_ERR_INVALID_ARGUMENT;
+    const int rc = check_format(f, bit_depth, &why);
+    if (rc < 0) return rc;
+    if (!is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+    matrix_coeffs(f->matrix, f->full_range, bit_depth, f->dtype == XGPU_OUT_U8 ? 8 : f->dtype == XGPU_OUT_U16 ? bit_depth : 0, coef, shift, fcoef);
     return XGPU_OK;
 }
 static size_t format_size(const xgpu_output_format *f, int width, int height, int bd, const char **why)
@@ -401,6 +407,193 @@ static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const x
         } else {
             launch_output_yuv444(a, f->layout, f->dtype, f->upsample, s);
         }
+    }
+    return out_join(c, stream, s);      // the slot, the DRA and the colour tables
+}
+
+// ------------------------------------------------------------------------------------------------ packed display surfaces
+static bool is_packed_rgb(int layout) { return layout == XGPU_PACKED_RGBA || layout == XGPU_PACKED_RGB10A2; }
+static bool is_packed_422(int layout) { return layout == XGPU_PACKED_YUYV || layout == XGPU_PACKED_UYVY; }
+// the element of a packed layout's rows and pitch (10:10:10:2: the word) and the bytes of a row of w pixels
+static size_t packed_elem_size(const xgpu_packed_format *f) { return f->layout == XGPU_PACKED_RGB10A2 ? 4 : (size_t)elem_size(f->dtype); }
+static size_t packed_row(const xgpu_packed_format *f, size_t w) { return f->layout == XGPU_PACKED_RGB10A2 ? 4 * w : (is_packed_422(f->layout) ? 2 : 4) * w * elem_size(f->dtype); }
+// the depth D of the 4:2:2 samples
+static int packed_depth(const xgpu_packed_format *f, int bd) { return f->out_bit_depth ? f->out_bit_depth : bd; }
+// the format alone (no picture size): 0 or a negative code, `why` says which field
+static int check_packed_format(const xgpu_packed_format *f, int bd, const char **why)
+{
+    *why = "format is NULL";
+    if (!f) return XGPU_ERR_INVALID_ARGUMENT;
+    if (!crop_ok(f->crop, 0, 0, why)) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "layout must be one of XGPU_PACKED_RGBA .. XGPU_PACKED_UYVY";
+    if (!is_packed_rgb(f->layout) && !is_packed_422(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "chroma_loc 0..5; upsample XGPU_UPSAMPLE_NEAREST or _LINEAR";
+    if (f->chroma_loc < 0 || f->chroma_loc > 5 || (f->upsample != XGPU_UPSAMPLE_NEAREST && f->upsample != XGPU_UPSAMPLE_LINEAR)) return XGPU_ERR_INVALID_ARGUMENT;
+    if (is_packed_422(f->layout)) {
+        const int obd = packed_depth(f, bd);
+        *why = "YUYV / UYVY: dtype U8 with out_bit_depth 8, or U16 with out_bit_depth 8..16 (0 = the coding depth)";
+        if (f->dtype == XGPU_OUT_U8 ? f->out_bit_depth != 8 : (f->dtype != XGPU_OUT_U16 || obd < 8 || obd > 16)) return XGPU_ERR_INVALID_ARGUMENT;
+        *why = "YUYV / UYVY: bgr must be 0, row_pitch a multiple of the element size";
+        if (f->bgr || f->row_pitch % packed_elem_size(f)) return XGPU_ERR_INVALID_ARGUMENT;
+        return XGPU_OK;
+    }
+    if (f->layout == XGPU_PACKED_RGBA) {
+        *why = "RGBA: dtype must be one of XGPU_OUT_U8 .. XGPU_OUT_F32";
+        if (f->dtype < XGPU_OUT_U8 || f->dtype > XGPU_OUT_F32) return XGPU_ERR_INVALID_ARGUMENT;
+        *why = "RGBA: out_bit_depth must be 0 or the coding depth";
+        if (f->out_bit_depth != 0 && f->out_bit_depth != bd) return XGPU_ERR_INVALID_ARGUMENT;
+    } else {
+        *why = "RGB10A2: dtype and out_bit_depth must be 0";
+        if (f->dtype != 0 || f->out_bit_depth != 0) return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    *why = "bgr, full_range: 0 or 1; row_pitch a multiple of the element size (RGB10A2: of 4)";
+    if ((f->bgr | f->full_range) & ~1 || f->row_pitch % packed_elem_size(f)) return XGPU_ERR_INVALID_ARGUMENT;
+    *why = "alpha must be finite and in [0, 1]";
+    if (!(f->alpha >= 0.f && f->alpha <= 1.f)) return XGPU_ERR_INVALID_ARGUMENT;      // (a NaN fails both comparisons)
+    double kr, kb;
+    *why = "matrix: supported MatrixCoefficients are 1, 4, 5, 6, 7 and 9";
+    if (!matrix_kr_kb(f->matrix, &kr, &kb)) return XGPU_ERR_UNSUPPORTED;
+    return XGPU_OK;
+}
+// 0 with *rc = the code and `why`, or the bytes the destination needs
+static size_t packed_size(const xgpu_packed_format *f, int width, int height, int bd, int *rc, const char **why)
+{
+    *rc = XGPU_ERR_INVALID_ARGUMENT;
+    *why = "picture size or bit depth out of range";
+    if (width <= 0 || height <= 0 || ((width | height) & 1) || bd < 8 || bd > 12) return 0;
+    if ((*rc = check_packed_format(f, bd, why)) < 0) return 0;
+    *rc = XGPU_ERR_INVALID_ARGUMENT;
+    if (!crop_ok(f->crop, width, height, why)) return 0;
+    const size_t w = width - f->crop[0] - f->crop[1], h = height - f->crop[2] - f->crop[3];
+    *why = "row_pitch is shorter than a row";
+    const size_t total = rows_of(packed_row(f, w), h, f->row_pitch).total;
+    if (total) *rc = XGPU_OK;
+    return total;
+}
+size_t xgpu_output_packed_size(const xgpu_packed_format *f, int width, int height, int bit_depth)
+{
+    int rc; const char *why;
+    return packed_size(f, width, height, bit_depth, &rc, &why);
+}
+// the RGB format whose three elements the packed RGB layouts write (RGB10A2: the U16 form, whose code at the coding depth feeds a transform)
+static xgpu_output_format packed_rgb_format(const xgpu_packed_format *f)
+{
+    xgpu_output_format r;
+    memset(&r, 0, sizeof(r));
+    r.layout = XGPU_OUT_RGB_INTERLEAVED; r.bgr = f->bgr;
+    r.dtype = f->layout == XGPU_PACKED_RGB10A2 ? XGPU_OUT_U16 : f->dtype;
+    r.matrix = f->matrix; r.full_range = f->full_range; r.chroma_loc = f->chroma_loc; r.upsample = f->upsample;
+    memcpy(r.crop, f->crop, sizeof(r.crop));
+    return r;
+}
+// the plain call's checks and codes first, then the layout and the transform (cm_prepare's order)
+int xgpu_output_packed_check(const xgpu_packed_format *f, const xgpu_colour_transform *cm, int width, int height, int bit_depth)
+{
+    int rc; const char *why;
+    (void)packed_size(f, width, height, bit_depth, &rc, &why);
+    if (rc < 0 || !cm) return rc;
+    if (!is_packed_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+    const xgpu_output_format rf = packed_rgb_format(f);
+    std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
+    return t ? xgpu_colour_tables(&rf, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
+}
+// The A element.  RGBA: floor(alpha * (2^D - 1) + 0.5) in double for the integer dtypes (D = 8 for U8, else the coding depth), the float32 bits of alpha for the
+// float dtypes (the kernel rounds them to the dtype); RGB10A2: floor(alpha * 3 + 0.5)
+static uint32_t packed_alpha_code(const xgpu_packed_format *f, int bd)
+{
+    if (f->layout == XGPU_PACKED_RGBA && f->dtype != XGPU_OUT_U8 && f->dtype != XGPU_OUT_U16) {
+        uint32_t bits;
+        memcpy(&bits, &f->alpha, sizeof(bits));
+        return bits;
+    }
+    const int d = f->layout == XGPU_PACKED_RGB10A2 ? 2 : f->dtype == XGPU_OUT_U8 ? 8 : bd;
+    return (uint32_t)floor((double)f->alpha * (double)((1 << d) - 1) + 0.5);
+}
+// The matrix of the packed RGB layouts without a transform.  RGBA: xgpu_output_coeffs' of the dtype.  RGB10A2: D = 10, S = 17 whatever the coding depth B.  Its sums
+// fit int32 for B = 8 .. 12 and samples in 0 .. 2^B - 1: cy * (Y - yo) <= 1023 * 2^17 * (2^B - 1 - yo) / yr <= 1023 * 2^17 * 239 / 219 < 2^28, one chroma term
+// <= 2 (1 - k) * 1023 * 2^17 * 2^(B-1) / cr <= 1.8814 * 1023 * 2^17 * 128 / 224 < 2^28 (full range: 128 / 255), G's two chroma terms together less than that, and
+// the rounding term 2^16: every sum is below 2^29 + 2^16 in magnitude.
+int xgpu_output_packed_coeffs(const xgpu_packed_format *f, int bit_depth, int32_t coef[5], int *shift, float fcoef[5], uint32_t *alpha_code)
+{
+    const char *why;
+    if (bit_depth < 8 || bit_depth > 12 || !coef || !shift || !fcoef || !alpha_code) return XGPU_ERR_INVALID_ARGUMENT;
+    const int rc = check_packed_format(f, bit_depth, &why);
+    if (rc < 0) return rc;
+    if (!is_packed_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+    const int d = f->layout == XGPU_PACKED_RGB10A2 ? 10 : f->dtype == XGPU_OUT_U8 ? 8 : f->dtype == XGPU_OUT_U16 ? bit_depth : 0;
+    matrix_coeffs(f->matrix, f->full_range, bit_depth, d, coef, shift, fcoef);
+    *alpha_code = packed_alpha_code(f, bit_depth);
+    return XGPU_OK;
+}
+int xgpu_pic_output_device_packed(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f, const xgpu_colour_transform *cm, void *d_dst,
+                                  size_t dst_size, void *stream)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    const char *why = "";
+    int rc;
+    const int bd = c->sp.bit_depth_luma;
+    const size_t need = packed_size(f, c->sp.width, c->sp.height, bd, &rc, &why);
+    if (need == 0) {
+        snprintf(c->err, sizeof(c->err), "pic_output_device_packed: invalid format: %s", why);
+        return rc;
+    }
+    if (cm && !is_packed_rgb(f->layout)) {
+        snprintf(c->err, sizeof(c->err), "pic_output_device_packed: a colour transform needs XGPU_PACKED_RGBA or XGPU_PACKED_RGB10A2");
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    TRY(check_dst(c, "pic_output_device_packed", d_dst, dst_size, need, packed_elem_size(f)));
+    const xgpu_output_format rf = packed_rgb_format(f);      // (read by the RGB layouts only)
+    std::unique_ptr<xgpu_colour_tables_t> cm_new;      // a new set of tables: made here, before anything is queued; uploaded and committed below
+    if (cm) TRY(cm_prepare(c, "pic_output_device_packed", &rf, cm, cm_new));
+    const int w = c->sp.width - f->crop[0] - f->crop[1], h = c->sp.height - f->crop[2] - f->crop[3];
+    // RGBA in a float dtype without a transform: k_output_rgb's own interleaved image in the context's intermediate, then the copy that adds A (k_output_packed.hip
+    // says why).  Its rows hold a multiple of 8 pixels and are a multiple of 16 bytes apart, so that the copy loads whole vectors.
+    const bool two_pass = f->layout == XGPU_PACKED_RGBA && !cm && f->dtype != XGPU_OUT_U8 && f->dtype != XGPU_OUT_U16;
+    const size_t mid_pitch = two_pass ? ((size_t)3 * align8(w) * elem_size(f->dtype) + 15) & ~(size_t)15 : 0;
+    if (two_pass) TRY(grow(c, "pic_output_device_packed", &c->sc_mid, &c->sc_mid_cap, mid_pitch * h, "intermediate"));
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    TRY(cm_commit(c, cm, cm_new, s));
+    const DevPic &p = dpic(c, pic);
+    auto source_and_rows = [&](RgbOutArgs &a) {
+        cropped_planes(p, f->crop, &a.y, &a.u, &a.v);
+        a.sy = p.s_l; a.sc = p.s_c;
+        a.w = w; a.h = h;
+        a.cw = w >> 1; a.ch = h >> 1;
+        a.dst = (uint8_t *)d_dst;
+        fill_rows(a, d_dst, packed_row(f, w), h, f->row_pitch);
+        fill_siting(f->chroma_loc, a);
+    };
+    if (is_packed_422(f->layout)) {
+        Packed422Args a;
+        memset(&a, 0, sizeof(a));
+        source_and_rows(a);
+        const int obd = packed_depth(f, bd);
+        a.cshift = bd - obd; a.out8 = obd == 8; a.cmax = (1 << obd) - 1;      // launch_output's conversion
+        a.lsh = f->dtype == XGPU_OUT_U16 ? 16 - obd : 0;
+        a.dra = dra ? c->d_dra : NULL;
+        launch_output_packed_422(a, f->dtype, f->layout == XGPU_PACKED_UYVY, f->upsample, s);
+    } else {
+        PackedRgbArgs a;
+        memset(&a, 0, sizeof(a));
+        source_and_rows(a);
+        fill_conversion(c, dra, &rf, a);
+        a.alpha = packed_alpha_code(f, bd);
+        if (two_pass) {
+            RgbOutArgs r = a;      // the source, the conversion and the siting; the destination is the intermediate
+            r.dst = (uint8_t *)c->sc_mid;
+            fill_rows(r, r.dst, image_row(&rf, w), h, mid_pitch);
+            launch_output_rgb(r, XGPU_OUT_RGB_INTERLEAVED, f->dtype, f->upsample, s);
+            launch_packed_rgba_from_rgb(a, f->dtype, r.dst, mid_pitch, s);
+        } else if (cm) {
+            fill_cm(c, &rf, *c->cm_tab, a, a.cm);
+            if (f->layout == XGPU_PACKED_RGB10A2) a.cm.outmax = 1023.f;
+        } else if (f->layout == XGPU_PACKED_RGB10A2) {
+            matrix_coeffs(f->matrix, f->full_range, bd, 10, a.coef, &a.shift, a.fcoef);
+            a.maxv = 1023;
+        }
+        if (!two_pass) launch_output_packed_rgb(a, f->layout, f->dtype, f->upsample, cm != NULL, s);
     }
     return out_join(c, stream, s);      // the slot, the DRA and the colour tables
 }

@@ -258,6 +258,73 @@ class XgpuDecoder:
             self._device_call("xgpu_pic_output_device_cm", out, pic, dl, C.byref(fmt), C.byref(cm))
         return out
 
+    _PACKED_LAYOUTS = {"rgba": (abi.PACKED_RGBA, False), "bgra": (abi.PACKED_RGBA, True), "rgb10a2": (abi.PACKED_RGB10A2, False),
+                       "bgr10a2": (abi.PACKED_RGB10A2, True), "yuyv": (abi.PACKED_YUYV, False), "uyvy": (abi.PACKED_UYVY, False)}
+
+    def pic_output_packed(self, pic, layout="rgba", dtype=None, alpha=1.0, matrix=1, full_range=False, chroma_loc=0, upsample="linear", crop=(0, 0, 0, 0),
+                          dra=None, colour=None, out_bit_depth=0, out=None):
+        """The picture as a packed display surface in device memory, a torch tensor on cuda:{device}, made on the device on torch's current stream
+        (xgpu_pic_output_device_packed).  layout "rgba" / "bgra": [H, W, 4] R G B A (B G R A) in any dtype of pic_output_tensor's "rgb" -
+        the three colour elements are that call's, bit for bit, with `colour` those of its colour-managed form; A = alpha (0..1) as an integer code
+        (floor(alpha * (2^D - 1) + 0.5), D = 8 for torch.uint8, else the coding depth) or as the dtype's float.  "rgb10a2" / "bgr10a2": [H, W] torch.int32, one word
+        R | G << 10 | B << 20 | A << 30 per pixel (bgr10a2: B low, R at 20) with 10-bit codes whatever the coding depth and A = floor(alpha * 3 + 0.5); dtype and
+        out_bit_depth stay unset.  "yuyv" / "uyvy": packed 4:2:2, [H, W, 2] - pixel x holds Y and, by its parity, Cb or Cr ("uyvy": the chroma sample first) -
+        torch.uint8 (8-bit samples: YUY2 / UYVY) or a 16-bit integer type with the sample at out_bit_depth (0 = the coding depth) in the high bits of the word
+        (10: Y210); luma is NV12's, chroma keeps half width and goes to full height by upsample ("nearest": the row above; "linear": the vertical quarter
+        weights of chroma_loc); matrix, full_range, alpha are not read and colour must be None.
+        out: a tensor to fill instead, rows of that shape whose stride may pad them (row_pitch); it is also what is returned."""
+        import torch
+        if layout not in self._PACKED_LAYOUTS:
+            raise ValueError(f"layout must be one of {', '.join(map(repr, self._PACKED_LAYOUTS))}, not {layout!r}")
+        lay, bgr = self._PACKED_LAYOUTS[layout]
+        if upsample not in ("linear", "nearest"):
+            raise ValueError(f"upsample must be 'linear' or 'nearest', not {upsample!r}")
+        cl, cr, ct, cb = (int(v) for v in crop)
+        w, h = self.width - cl - cr, self.height - ct - cb
+        obd = int(out_bit_depth)
+        if lay == abi.PACKED_RGB10A2:
+            if dtype not in (None, torch.int32) or obd != 0:
+                raise ValueError(f"{layout}: the words are torch.int32; dtype and out_bit_depth stay unset")
+            dtype, code, shape, last = torch.int32, 0, (h, w), 1
+        else:
+            yuv = lay in (abi.PACKED_YUYV, abi.PACKED_UYVY)
+            if dtype is None:
+                dtype = torch.uint8
+            codes = _codes("uint8", "int16", "uint16") if yuv else _codes()
+            if dtype not in codes:
+                raise ValueError(f"{layout}: unsupported output dtype {dtype}")
+            code = codes[dtype]
+            if yuv:
+                if colour is not None:
+                    raise ValueError(f"colour: a colour transform needs one of the RGB layouts, not {layout!r}")
+                if code == abi.OUT_U8:
+                    if obd not in (0, 8):
+                        raise ValueError(f"{layout}: torch.uint8 holds 8-bit samples; out_bit_depth above 8 needs a 16-bit integer dtype")
+                    obd = 8
+            elif obd not in (0, self.bit_depth):
+                raise ValueError(f"{layout}: out_bit_depth must be 0 or the coding depth {self.bit_depth}, not {obd}")
+            last = 2 if yuv else 4
+            shape = (h, w, last)
+        fmt = abi.make_packed_format(lay, code, bgr=bgr, out_bit_depth=obd, matrix=matrix, full_range=full_range, chroma_loc=chroma_loc,
+                                     upsample=abi.UPSAMPLE_LINEAR if upsample == "linear" else abi.UPSAMPLE_NEAREST, crop=crop, alpha=alpha)
+        cm = None if colour is None else abi.make_colour_transform(**colour)
+        if w <= 0 or h <= 0:
+            raise ValueError(f"invalid packed output format: crop {crop} leaves no picture")
+        out = _out_tensor(out, shape, dtype, torch.device("cuda", self.sp.device))
+        st = out.stride()
+        if st[1:] != ((last, 1) if len(shape) == 3 else (1,)) or st[0] < w * last:
+            raise ValueError(f"out: strides {st} are not rows of W x {last} elements")
+        fmt.row_pitch = st[0] * dtype.itemsize
+        rc = self.lib.xgpu_output_packed_check(C.byref(fmt), None, self.width, self.height, self.bit_depth)
+        if rc == 0 and cm is not None:
+            rc = self._cm_check(abi.make_output_format(abi.OUT_RGB_INTERLEAVED), cm)
+        if rc < 0:
+            raise ValueError(f"invalid packed output format ({rc}): layout {layout}, dtype {dtype}, out_bit_depth {out_bit_depth}, matrix {matrix}, "
+                             f"chroma_loc {chroma_loc}, alpha {alpha}, crop {crop}, colour {colour}")
+        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
+        self._device_call("xgpu_pic_output_device_packed", out, pic, dl, C.byref(fmt), None if cm is None else C.byref(cm))
+        return out
+
     def _scaled_setup(self, a):
         """what the scaled outputs check and build alike -> (torch dtype, xgpu_output_format, xgpu_scale_params, H, W, device)"""
         import torch

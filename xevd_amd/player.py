@@ -117,7 +117,7 @@ class StreamDecoder:
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
                  residual=None, compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
-                 linear_light=False, resample=None):
+                 linear_light=False, resample=None, packed=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -160,11 +160,15 @@ class StreamDecoder:
         surfaces=[(H, W), ...], surface_layout="nv12" | "p016" | "yuv420p": every picture as a ladder of scaled video surfaces, one tensor per size, under
         params["surfaces"] (XgpuDecoder.pic_output_surfaces, next to whatever else was asked: the yielded tuple keeps its shape) - the renditions of a
         transcode, where an encoder takes them.  surface_options=dict(...) passes its other arguments (dtype, out_bit_depth, filter, dst_chroma_loc);
-        chroma_loc and the DRA tables are the stream's, the crop defaults to the SPS crop when apply_crop is set"""
+        chroma_loc and the DRA tables are the stream's, the crop defaults to the SPS crop when apply_crop is set
+        packed=dict(layout=..., ...) (keyword arguments of XgpuDecoder.pic_output_packed): every picture as a packed display surface - RGBA, 10:10:10:2, packed
+        4:2:2 - under params["packed"], next to whatever else was asked as surfaces= is.  Matrix, range, chroma siting and the DRA tables are the stream's
+        (tensor_options), the crop defaults to the SPS crop when apply_crop is set, and with to= the RGB layouts' colour= is made from the stream's VUI as it is
+        for tensor="""
         if surfaces is None and surface_options is not None:
             raise ValueError("surface_options: needs surfaces=[(H, W), ...]")
-        if to is not None and tensor is None:
-            raise ValueError("to: needs tensor=dict(...)")
+        if to is not None and tensor is None and packed is None:
+            raise ValueError("to: needs tensor=dict(...) or packed=dict(...)")
         if linear_light and (tensor is None or size is None or to is None):
             raise ValueError("linear_light: needs tensor=dict(...), size=(H, W) and to=")
         if (size is not None or mean is not None or std is not None) and tensor is None:
@@ -249,6 +253,13 @@ class StreamDecoder:
                 kw.update(surface_options or {})
                 with self._lock:
                     p["surfaces"] = dec.pic_output_surfaces(cur, surfaces, layout=surface_layout, **kw)
+            if packed is not None:
+                kw = self.tensor_options(p, packed)
+                kw.setdefault("crop", p["crop"] if self.apply_crop else (0, 0, 0, 0))
+                if to is not None and kw.get("layout", "rgba") not in ("yuyv", "uyvy"):
+                    kw.setdefault("colour", self.colour_transform(p["colour"], to))
+                with self._lock:
+                    p["packed"] = dec.pic_output_packed(cur, **kw)
             planes = None
             if tensor is not None:
                 kw = self.tensor_options(p, tensor)
@@ -318,21 +329,25 @@ class StreamDecoder:
 
     def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
                      compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
-                     linear_light=False, resample=None):
+                     linear_light=False, resample=None, packed=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
         params["residual"] as numpy - for kind "yuv420" the pair (flat array, (Y, Cb, Cr) views of it); compare= (as pictures takes it, the callable and the
         sequence in DECODING order): params["compare"], its map as a numpy array; stats= (as pictures takes it): params["stats"], its histograms as numpy arrays;
-        surfaces= / surface_layout= / surface_options= (as pictures takes them): params["surfaces"], a list of numpy arrays; resample= (as pictures takes it)"""
+        surfaces= / surface_layout= / surface_options= (as pictures takes them): params["surfaces"], a list of numpy arrays; resample= (as pictures takes it);
+        packed=dict(...) (as pictures takes it): params["packed"], a numpy array"""
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
                                        residual=residual, compare=compare, stats=stats, warp=warp, remap=remap, remap_step=remap_step, surfaces=surfaces,
-                                       surface_layout=surface_layout, surface_options=surface_options, linear_light=linear_light, resample=resample):
+                                       surface_layout=surface_layout, surface_options=surface_options, linear_light=linear_light, resample=resample,
+                                       packed=packed):
             if p["is_idr"]:
                 epoch += 1
             if surfaces is not None:      # (synchronises torch's current stream: the tensors are complete)
                 p["surfaces"] = [t.cpu().numpy() for t in p["surfaces"]]
+            if packed is not None:
+                p["packed"] = p["packed"].cpu().numpy()
             if tensor is not None:
                 # (synchronises torch's current stream: the slot's tensor is complete); device boxes with results=True: the pair, both as arrays
                 planes = tuple(t.cpu().numpy() for t in planes) if isinstance(planes, tuple) else planes.cpu().numpy()
