@@ -222,7 +222,12 @@ def test_rectangles_stretch_and_letterbox():
     try:
         tab = tables(dec, PQ_TO_SRGB, bd)
         for code, cl, fit, pad, norm in ((abi.OUT_U8, False, "stretch", None, False), (abi.OUT_F32, True, "letterbox", (0.25, 0.5, 0.75), True),
-                                         (abi.OUT_U16, False, "letterbox", 7, False)):
+                                         (abi.OUT_U16, False, "letterbox", 7, False),
+                                         # every dtype in either layout: the batch kernels' instances come from one dispatch
+                                         (abi.OUT_U8, True, "letterbox", 200, False), (abi.OUT_U16, True, "letterbox", 3, False),
+                                         (abi.OUT_F16, False, "letterbox", 0.447, True), (abi.OUT_F16, True, "letterbox", (0.25, 0.5, 0.75), False),
+                                         (abi.OUT_BF16, False, "stretch", None, False), (abi.OUT_BF16, True, "letterbox", 0.447, True),
+                                         (abi.OUT_F32, False, "stretch", None, False)):
             kw = dict(mean=MEAN, std=STD) if norm else {}
             common = dict(rois=rois, fit=fit, pad=pad, channels_last=cl, dtype=ts.torch_dtype(code), **kw)
             t = dec.pic_output_scaled_cm(pic, size, PQ_TO_SRGB, linear_light=True, **common)

@@ -2,7 +2,10 @@
 // section 8o).  One pair of kernels for both calls: the single picture is the batch of one stretched rectangle.  The pair has the shape of k_output_rois.hip's -
 // the same descriptor block (RoiDesc, then the tap tables), the same grids, the same staging of a row's spans in LDS, the same pad lanes - and differs in the
 // arithmetic alone: cubic weights have negative lobes, so the taps are signed (xgpu_resample_taps), the intermediate is int16 with two fraction bits and is not
-// clipped, and the clip to the sample range follows the second pass (output_common.h: resample_vertical_lane, resample_column).  tests/resample_ref.py restates it.
+// clipped, and the clip to the sample range follows the second pass (output_common.h: scale_vertical_lane<true>, resample_column).  tests/resample_ref.py
+// restates it.  The vertical kernel is output_resize.h's rois_vertical and the launch its launch_horizontal (the row's bytes are TriangleRow's: 16-bit samples);
+// k_resampled_horizontal keeps the text of rois_horizontal written out: as an instance of that body the 64 tiles of 224x224 at 8K measured 0.5 us (0.3 %) over
+// the written-out kernel's median, once more than that kernel's own spread of 0.48 us.
 //   k_resampled_vertical     grid (columns of the widest rectangle / 512, rows of the tallest inner part / 4, 3 n): plane blockIdx.z % 3 of rectangle blockIdx.z / 3.
 //                            One lane owns 8 neighbouring columns of one destination row: a 16-byte load per tap row, a 16-byte store.  The row index is uniform
 //                            per wave and the descriptor per workgroup, so descriptor, first / count and the weights are scalar loads.
@@ -12,22 +15,11 @@
 // The intermediate is the context's sc_mid, read here as int16; what the 16-byte loads of the vertical pass read past a rectangle's width lands in columns of
 // the intermediate that no tap reads.
 #pragma clang fp contract(off)
-#include "output_common.h"
+#include "output_resize.h"
 
 __global__ __launch_bounds__(256) void k_resampled_vertical(const RoisOutArgs a)
 {
-    const int r = blockIdx.z / 3, plane = blockIdx.z - 3 * r;
-    const RoiDesc &d = ((const RoiDesc *)a.blk)[r];
-    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8;
-    const int o = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y);      // one destination row per wave
-    if (x0 >= (plane ? d.w >> 1 : d.w) || o >= d.ih) return;
-    const int t = plane ? 1 : 0;
-    const int32_t *first = (const int32_t *)(a.blk + d.first[t]), *count = (const int32_t *)(a.blk + d.count[t]);
-    const int16_t *q = (const int16_t *)(a.blk + d.wt[t]) + (size_t)o * d.stride[t];
-    const int16_t *luma = a.y + (size_t)d.y * a.sy + d.x;
-    const int16_t *src = plane == 0 ? luma : (plane == 1 ? a.u : a.v) + (size_t)(d.y >> 1) * a.sc + (d.x >> 1);
-    int16_t *m = (int16_t *)a.mid + d.mid + (plane == 0 ? (size_t)0 : (size_t)d.ih * d.mpy + (size_t)(plane - 1) * d.ih * d.mpc) + (size_t)o * (plane ? d.mpc : d.mpy) + x0;
-    resample_vertical_lane(a, plane, src, luma, first[o], count[o], q, x0, m);
+    rois_vertical<true>(a);
 }
 
 template <bool PLANAR, int DT, template <int> class CONV>
@@ -72,30 +64,16 @@ __global__ __launch_bounds__(256) void k_resampled_horizontal(const RoisOutArgs 
     if (oy >= a.dh || ox >= a.dw) return;
     store_pixel<PLANAR, SZ>(a.dst + d.dst + (size_t)oy * a.pitch, a.plane, ox, e);
 }
-
-template <bool PLANAR, template <int> class CONV>
-static void launch_horizontal(const RoisOutArgs &a, int dtype, dim3 grid, dim3 block, size_t lds, hipStream_t s)
-{
-    switch (dtype) {
-    case XGPU_OUT_U8:   hipLaunchKernelGGL((k_resampled_horizontal<PLANAR, XGPU_OUT_U8, CONV>), grid, block, lds, s, a); break;
-    case XGPU_OUT_U16:  hipLaunchKernelGGL((k_resampled_horizontal<PLANAR, XGPU_OUT_U16, CONV>), grid, block, lds, s, a); break;
-    case XGPU_OUT_F16:  hipLaunchKernelGGL((k_resampled_horizontal<PLANAR, XGPU_OUT_F16, CONV>), grid, block, lds, s, a); break;
-    case XGPU_OUT_BF16: hipLaunchKernelGGL((k_resampled_horizontal<PLANAR, XGPU_OUT_BF16, CONV>), grid, block, lds, s, a); break;
-    default:            hipLaunchKernelGGL((k_resampled_horizontal<PLANAR, XGPU_OUT_F32, CONV>), grid, block, lds, s, a); break;
+struct ResampledHorizontal {
+    template <bool PLANAR, bool RGB, int DT> static auto kernel()
+    {
+        if constexpr (RGB) return k_resampled_horizontal<PLANAR, DT, RgbConv>; else return k_resampled_horizontal<PLANAR, DT, YuvConv>;
     }
-}
+};
 
 // max_w: the widest rectangle; max_ih: the tallest inner part
 void launch_output_resampled(const RoisOutArgs &a, int layout, int dtype, int max_w, int max_ih, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_resampled_vertical, dim3((unsigned)(((max_w + 7) / 8 + 63) / 64), (unsigned)((max_ih + 3) / 4), (unsigned)(3 * a.n)), dim3(64, 4), 0, s, a);
-    // as many rows per workgroup as 48 KB of LDS hold, 4 at most - k_output_scaled.hip's rule, on the widest span of the batch
-    const size_t per_row = (size_t)(a.capy + 2 * a.capc) * sizeof(int16_t);
-    int rows = 4;
-    while (rows > 1 && rows * per_row > 48 * 1024) rows >>= 1;
-    const dim3 grid((unsigned)((a.dw + 63) / 64), (unsigned)((a.dh + rows - 1) / rows), (unsigned)a.n), block(64, rows);
-    const bool planar = layout == XGPU_OUT_RGB_PLANAR || layout == XGPU_OUT_YUV444_PLANAR;
-    const bool rgb = layout == XGPU_OUT_RGB_PLANAR || layout == XGPU_OUT_RGB_INTERLEAVED;
-    if (rgb) { if (planar) launch_horizontal<true, RgbConv>(a, dtype, grid, block, rows * per_row, s); else launch_horizontal<false, RgbConv>(a, dtype, grid, block, rows * per_row, s); }
-    else     { if (planar) launch_horizontal<true, YuvConv>(a, dtype, grid, block, rows * per_row, s); else launch_horizontal<false, YuvConv>(a, dtype, grid, block, rows * per_row, s); }
+    hipLaunchKernelGGL(k_resampled_vertical, vertical_grid(max_w, max_ih, (unsigned)(3 * a.n)), dim3(64, 4), 0, s, a);
+    launch_horizontal<ResampledHorizontal, TriangleRow>(a, layout, dtype, (unsigned)a.n, s);      // on the widest span of the batch
 }

@@ -23,12 +23,14 @@
 // of a row, and the destination is the small side of this kernel.  Any element-aligned destination works; there is no vector / element split to get wrong.
 //
 // The lanes' work - the vertical pass of 8 columns, the staging, the column filter, the conversion with its normalise, the stores - is in output_common.h
-// (scale_vertical_lane, stage_span, filter_column, scaled_pixel, store_pixel): k_output_rois.hip runs the same functions on a batch of rectangles.
+// (scale_vertical_lane, stage_span, filter_column, scaled_pixel, store_pixel): k_output_rois.hip runs the same functions on a batch of rectangles.  The body of
+// k_scale_horizontal is output_resize.h's scale_horizontal with the row of the triangle taps and the plain pixel (k_output_scaled_cm.hip and
+// k_output_scaled_lin.hip call it with theirs), and the launch of the pass - the rows rule, the grid, the instance by layout and dtype - is launch_horizontal there.
 //
 // Float arithmetic in this file is rounded operation by operation (no contraction into FMA): the normalise is (v - mean) * inv_std in two roundings by contract,
 // and the matrix of the float dtypes is section 8a's formula as tests/colour_ref.py evaluates it.
 #pragma clang fp contract(off)
-#include "output_common.h"
+#include "output_resize.h"
 
 __global__ __launch_bounds__(256) void k_scale_vertical(const ScaledOutArgs a)
 {
@@ -45,53 +47,22 @@ __global__ __launch_bounds__(256) void k_scale_vertical(const ScaledOutArgs a)
 template <bool PLANAR, int DT, template <int> class CONV>
 __global__ __launch_bounds__(256) void k_scale_horizontal(const ScaledOutArgs a)
 {
-    extern __shared__ uint4 lds4[];
-    constexpr int SZ = OutT<DT>::size;
-    const int oy = blockIdx.y * blockDim.y + threadIdx.y, ob = blockIdx.x * 64;
-    const int row = min(oy, a.dh - 1), ol = min(ob + 63, a.dw - 1), ox = min(ob + (int)threadIdx.x, a.dw - 1);      // lanes past the edges work on the edge, and store nothing
-    uint16_t *ly = (uint16_t *)lds4 + (size_t)threadIdx.y * (a.capy + 2 * a.capc), *lb = ly + a.capy, *lr = lb + a.capc;
-    const int y0 = a.xl.first[ob] & ~7, y1 = a.xl.first[ol] + a.xl.count[ol];
-    const int c0 = a.xc.first[ob] & ~7, c1 = a.xc.first[ol] + a.xc.count[ol];
-    const uint16_t *mb = a.mid + (size_t)a.dh * a.mpy, *mr = mb + (size_t)a.dh * a.mpc;
-    stage_span(ly, a.mid + (size_t)row * a.mpy, y0, y1);
-    stage_span(lb, mb + (size_t)row * a.mpc, c0, c1);
-    stage_span(lr, mr + (size_t)row * a.mpc, c0, c1);
-    __syncthreads();
-    const int y = filter_column(ly, a.xl, ox, y0), cb = filter_column(lb, a.xc, ox, c0), cr = filter_column(lr, a.xc, ox, c0);
-
-    uint32_t e[3];
-    scaled_pixel<DT, CONV>(a, y, cb, cr, e);
-    if (oy >= a.dh || ob + (int)threadIdx.x >= a.dw) return;
-    store_pixel<PLANAR, SZ>(a.dst + (size_t)oy * a.pitch, a.plane, ox, e);
+    scale_horizontal<TriangleRow, PlainPixel<CONV>, PLANAR, DT>(a);
 }
-
-template <bool PLANAR, template <int> class CONV>
-static void launch_horizontal(const ScaledOutArgs &a, int dtype, dim3 grid, dim3 block, size_t lds, hipStream_t s)
-{
-    switch (dtype) {
-    case XGPU_OUT_U8:   hipLaunchKernelGGL((k_scale_horizontal<PLANAR, XGPU_OUT_U8, CONV>), grid, block, lds, s, a); break;
-    case XGPU_OUT_U16:  hipLaunchKernelGGL((k_scale_horizontal<PLANAR, XGPU_OUT_U16, CONV>), grid, block, lds, s, a); break;
-    case XGPU_OUT_F16:  hipLaunchKernelGGL((k_scale_horizontal<PLANAR, XGPU_OUT_F16, CONV>), grid, block, lds, s, a); break;
-    case XGPU_OUT_BF16: hipLaunchKernelGGL((k_scale_horizontal<PLANAR, XGPU_OUT_BF16, CONV>), grid, block, lds, s, a); break;
-    default:            hipLaunchKernelGGL((k_scale_horizontal<PLANAR, XGPU_OUT_F32, CONV>), grid, block, lds, s, a); break;
+struct ScaleHorizontal {
+    template <bool PLANAR, bool RGB, int DT> static auto kernel()
+    {
+        if constexpr (RGB) return k_scale_horizontal<PLANAR, DT, RgbConv>; else return k_scale_horizontal<PLANAR, DT, YuvConv>;
     }
-}
+};
 
 void launch_scale_vertical(const ScaledOutArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_scale_vertical, dim3((unsigned)(((a.w + 7) / 8 + 63) / 64), (unsigned)((a.dh + 3) / 4), 3), dim3(64, 4), 0, s, a);
+    hipLaunchKernelGGL(k_scale_vertical, vertical_grid(a.w, a.dh, 3), dim3(64, 4), 0, s, a);
 }
 
 void launch_output_scaled(const ScaledOutArgs &a, int layout, int dtype, hipStream_t s)
 {
     launch_scale_vertical(a, s);
-    // as many rows per workgroup as 48 KB of LDS hold, 4 at most (a row's spans are at most ~17 KB: 64 columns at a ratio of 64)
-    const size_t per_row = (size_t)(a.capy + 2 * a.capc) * sizeof(uint16_t);
-    int rows = 4;
-    while (rows > 1 && rows * per_row > 48 * 1024) rows >>= 1;
-    const dim3 grid((unsigned)((a.dw + 63) / 64), (unsigned)((a.dh + rows - 1) / rows)), block(64, rows);
-    const bool planar = layout == XGPU_OUT_RGB_PLANAR || layout == XGPU_OUT_YUV444_PLANAR;
-    const bool rgb = layout == XGPU_OUT_RGB_PLANAR || layout == XGPU_OUT_RGB_INTERLEAVED;
-    if (rgb) { if (planar) launch_horizontal<true, RgbConv>(a, dtype, grid, block, rows * per_row, s); else launch_horizontal<false, RgbConv>(a, dtype, grid, block, rows * per_row, s); }
-    else     { if (planar) launch_horizontal<true, YuvConv>(a, dtype, grid, block, rows * per_row, s); else launch_horizontal<false, YuvConv>(a, dtype, grid, block, rows * per_row, s); }
+    launch_horizontal<ScaleHorizontal, TriangleRow>(a, layout, dtype, 1u, s);
 }

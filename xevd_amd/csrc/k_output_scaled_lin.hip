@@ -14,6 +14,7 @@
 //     4 x 512 pixels per tap row, tens of thousands in all, and three lookups per pixel sit on the pass' critical path (DESIGN.md section 5c has the measurement
 //     against reading it from global memory; the instances that did were dropped after it).
 //   k_lin_horizontal / k_lin_rois_horizontal   V_c(ox, o) = (sum_k float(qx[ox][k]) * T_c(first[ox] + k, o)) * 2^-28, then cm_from_linear, scaled_finish, store_pixel
+//     The bodies are k_scale_horizontal's and k_rois_horizontal's (output_resize.h) with LinRow and LinPixel below.
 //     A workgroup is 64 destination columns x `rows` destination rows, one wave per row, one lane per pixel, as in k_scale_horizontal.  Each wave stages the float
 //     spans of all three channels of its row in LDS: 12 bytes per source column where the plain pass has 4.  The group stays 64 columns wide and the three
 //     channels are filtered together (one weight load and one index per tap for three products); `rows` is 4, 2 or 1 by the plain passes' 48 KB rule.  At the
@@ -22,6 +23,7 @@
 //     The tone and encode tables are read from global memory, as in k_output_scaled_cm.hip and for its reason.
 #pragma clang fp contract(off)
 #include "cm_transform.h"
+#include "output_resize.h"
 
 // the lin table a workgroup of 64 x 4 reads: copied into LDS by all of its threads
 __device__ __forceinline__ const float *lin_fill_lds(const CmParams &p, float *lds)
@@ -131,151 +133,89 @@ __global__ __launch_bounds__(256) void k_lin_rois_vertical(const RoisCmOutArgs a
     g.u = a.u + (size_t)(d.y >> 1) * a.sc + (d.x >> 1);
     g.v = a.v + (size_t)(d.y >> 1) * a.sc + (d.x >> 1);
     g.w = d.w; g.h = d.h; g.cw = d.w >> 1; g.ch = d.h >> 1;
-    const int32_t *first = (const int32_t *)(a.blk + d.first[0]), *count = (const int32_t *)(a.blk + d.count[0]);
-    const int16_t *q = (const int16_t *)(a.blk + d.wt[0]) + (size_t)o * d.stride[0];
-    lin_vertical_lane<UP>(g, lin, first[o], count[o], q, x0, (float *)a.mid + d.mid + (size_t)o * d.mpy + x0, (size_t)d.ih * d.mpy);
+    const ScaleTaps t = roi_taps(a.blk, d, 0);
+    lin_vertical_lane<UP>(g, lin, t.first[o], t.count[o], t.w + (size_t)o * t.stride, x0, (float *)a.mid + d.mid + (size_t)o * d.mpy + x0, (size_t)d.ih * d.mpy);
 }
 
-// the span [s0, s1) of one row of one channel of the intermediate (s0 a multiple of 8) into the wave's LDS, 4 floats per lane and step
-__device__ __forceinline__ void lin_stage_span(float *lds, const float *row, int s0, int s1)
-{
-    for (int i = threadIdx.x * 4; i < s1 - s0; i += 256) *(float4 *)(lds + i) = *(const float4 *)(row + s0 + i);
-}
-// destination column o of the staged row, three channels `cap` floats apart: v[c] = (sum qx * t_c) * 2^-28
-__device__ __forceinline__ void lin_filter_column(const float *lds, int cap, const ScaleTaps &t, int o, int s0, float (&v)[3])
-{
-    const float *l = lds + (t.first[o] - s0);
-    const int16_t *q = t.w + o;
-    const int n = t.count[o];
-    float acc[3] = { 0.f, 0.f, 0.f };
-    for (int k = 0; k < n; k++) {
-        const float qk = (float)q[(size_t)k * t.stride];
-        #pragma unroll
-        for (int c = 0; c < 3; c++) { const float p = qk * l[c * cap + k]; acc[c] = k ? acc[c] + p : p; }
+
+// The row of the horizontal pass (output_resize.h's ROW): the float spans of R, G, B of one row, `cap` floats apart in the wave's part of LDS, under the luma taps
+struct LinRow {
+    typedef float Value;
+    static size_t row_bytes(int capy, int) { return (size_t)3 * capy * sizeof(float); }
+    const ScaleTaps &xl;
+    float *l;
+    int cap, s0, s1;
+    __device__ __forceinline__ LinRow(void *lds, int capy, int, const ScaleTaps &xl_, const ScaleTaps &, int o0, int o1) : xl(xl_), cap(capy)
+    {
+        l = (float *)lds + (size_t)threadIdx.y * 3 * capy;
+        s0 = xl.first[o0] & ~7; s1 = xl.first[o1] + xl.count[o1];
     }
-    #pragma unroll
-    for (int c = 0; c < 3; c++) v[c] = acc[c] * 0x1p-28f;
-}
+    // the span [s0, s1) of the row of every channel (s0 a multiple of 8), 4 floats per lane and step
+    __device__ __forceinline__ void stage(const uint16_t *mid, uint32_t off, int rows, int mpy, int, int row) const
+    {
+        const float *m = (const float *)mid + off + (size_t)row * mpy;
+        #pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float *mc = m + (size_t)c * rows * mpy;
+            for (int i = threadIdx.x * 4; i < s1 - s0; i += 256) *(float4 *)(l + c * cap + i) = *(const float4 *)(mc + s0 + i);
+        }
+    }
+    // destination column o of the staged row: v[c] = (sum qx * t_c) * 2^-28
+    __device__ __forceinline__ void column(int o, int, float (&v)[3]) const
+    {
+        const float *p = l + (xl.first[o] - s0);
+        const int16_t *q = xl.w + o;
+        const int n = xl.count[o];
+        float acc[3] = { 0.f, 0.f, 0.f };
+        for (int k = 0; k < n; k++) {
+            const float qk = (float)q[(size_t)k * xl.stride];
+            #pragma unroll
+            for (int c = 0; c < 3; c++) { const float t = qk * p[c * cap + k]; acc[c] = k ? acc[c] + t : t; }
+        }
+        #pragma unroll
+        for (int c = 0; c < 3; c++) v[c] = acc[c] * 0x1p-28f;
+    }
+};
 // one filtered pixel -> the bits of its three elements in output order: the rest of the transform (for the float dtypes its F32 instance, so that the normalise
 // sees the clipped float32), then scaled_finish
-template <int DT> __device__ __forceinline__ void lin_pixel(const ScaledOutArgs &a, const CmParams &p, const float (&v)[3], uint32_t (&e)[3])
-{
-    const CmTables t = { p.lin, p.tone, p.enc };
-    cm_from_linear<OutT<DT>::is_float ? XGPU_OUT_F32 : DT>(p, t, v[0], v[1], v[2], e[0], e[1], e[2]);
-    scaled_finish<DT>(a, e);
-}
+struct LinPixel {
+    template <int DT, class A> __device__ static __forceinline__ void apply(const A &a, const float (&v)[3], uint32_t (&e)[3])
+    {
+        const CmTables t = { a.cm.lin, a.cm.tone, a.cm.enc };
+        cm_from_linear<OutT<DT>::is_float ? XGPU_OUT_F32 : DT>(a.cm, t, v[0], v[1], v[2], e[0], e[1], e[2]);
+        scaled_finish<DT>(a, e);
+    }
+};
 
 template <bool PLANAR, int DT>
 __global__ __launch_bounds__(256) void k_lin_horizontal(const ScaledCmOutArgs a)
 {
-    extern __shared__ float4 lin_span4[];
-    constexpr int SZ = OutT<DT>::size;
-    const int oy = blockIdx.y * blockDim.y + threadIdx.y, ob = blockIdx.x * 64;
-    const int row = min(oy, a.dh - 1), ol = min(ob + 63, a.dw - 1), ox = min(ob + (int)threadIdx.x, a.dw - 1);      // lanes past the edges work on the edge, and store nothing
-    float *l = (float *)lin_span4 + (size_t)threadIdx.y * 3 * a.capy;
-    const int s0 = a.xl.first[ob] & ~7, s1 = a.xl.first[ol] + a.xl.count[ol];
-    const float *m = (const float *)a.mid + (size_t)row * a.mpy;
-    #pragma unroll
-    for (int c = 0; c < 3; c++) lin_stage_span(l + c * a.capy, m + (size_t)c * a.dh * a.mpy, s0, s1);
-    __syncthreads();
-    float v[3];
-    lin_filter_column(l, a.capy, a.xl, ox, s0, v);
-    uint32_t e[3];
-    lin_pixel<DT>(a, a.cm, v, e);
-    if (oy >= a.dh || ob + (int)threadIdx.x >= a.dw) return;
-    store_pixel<PLANAR, SZ>(a.dst + (size_t)oy * a.pitch, a.plane, ox, e);
+    scale_horizontal<LinRow, LinPixel, PLANAR, DT>(a);
 }
-
-// k_rois_horizontal_cm over the float intermediate: 64 columns x `rows` rows of the IMAGE of rectangle blockIdx.z; the pad value around the inner part is written
-// as the plain call writes it - a value of the destination space, normalised like a pixel, never transformed
+// k_rois_horizontal_cm over the float intermediate
 template <bool PLANAR, int DT>
 __global__ __launch_bounds__(256) void k_lin_rois_horizontal(const RoisCmOutArgs a)
 {
-    extern __shared__ float4 lin_span4[];
-    constexpr int SZ = OutT<DT>::size;
-    const RoiDesc &d = ((const RoiDesc *)a.blk)[blockIdx.z];
-    const int oy = blockIdx.y * blockDim.y + threadIdx.y, ob = blockIdx.x * 64, ox = ob + (int)threadIdx.x;      // in the image
-    // the inner columns and rows the workgroup covers (none: c0 > c1 or r0 > r1), and this wave's inner row
-    const int c0 = max(ob - d.ix, 0), c1 = min(ob + 63 - d.ix, d.iw - 1);
-    const int r0 = max((int)(blockIdx.y * blockDim.y) - d.iy, 0), r1 = min((int)((blockIdx.y + 1) * blockDim.y) - 1 - d.iy, d.ih - 1);
-    const int row = oy - d.iy;
-    const bool row_in = row >= 0 && row < d.ih;
-    bool in = false;
-    uint32_t e[3];
-    if (c0 <= c1 && r0 <= r1) {      // uniform per workgroup
-        const ScaleTaps xl = { (const int32_t *)(a.blk + d.first[2]), (const int32_t *)(a.blk + d.count[2]), (const int16_t *)(a.blk + d.wt[2]), d.stride[2] };
-        float *l = (float *)lin_span4 + (size_t)threadIdx.y * 3 * a.capy;
-        const int s0 = xl.first[c0] & ~7, s1 = xl.first[c1] + xl.count[c1];
-        if (row_in) {                // uniform per wave: a wave stages its own row into its own part of LDS
-            const float *m = (const float *)a.mid + d.mid + (size_t)row * d.mpy;
-            #pragma unroll
-            for (int c = 0; c < 3; c++) lin_stage_span(l + c * a.capy, m + (size_t)c * d.ih * d.mpy, s0, s1);
-        }
-        __syncthreads();
-        if (row_in) {
-            const int oc = min(max(ox - d.ix, c0), c1);      // lanes beside the inner part work on its edge, and store the pad value instead
-            float v[3];
-            lin_filter_column(l, a.capy, xl, oc, s0, v);
-            lin_pixel<DT>(a, a.cm, v, e);
-            in = ox - d.ix == oc;
-        }
-    }
-    if (!in) {
-        #pragma unroll
-        for (int k = 0; k < 3; k++) e[k] = OutT<DT>::is_float ? scaled_float_elem<DT>(a, k, a.padv[k]) : (uint32_t)(int)a.padv[k];
-    }
-    if (oy >= a.dh || ox >= a.dw) return;
-    store_pixel<PLANAR, SZ>(a.dst + d.dst + (size_t)oy * a.pitch, a.plane, ox, e);
+    rois_horizontal<LinRow, LinPixel, false, PLANAR, DT>(a);
 }
-
-template <bool PLANAR> static void launch_horizontal(const ScaledCmOutArgs &a, int dtype, dim3 grid, dim3 block, size_t lds, hipStream_t s)
-{
-    switch (dtype) {
-    case XGPU_OUT_U8:   hipLaunchKernelGGL((k_lin_horizontal<PLANAR, XGPU_OUT_U8>), grid, block, lds, s, a); break;
-    case XGPU_OUT_U16:  hipLaunchKernelGGL((k_lin_horizontal<PLANAR, XGPU_OUT_U16>), grid, block, lds, s, a); break;
-    case XGPU_OUT_F16:  hipLaunchKernelGGL((k_lin_horizontal<PLANAR, XGPU_OUT_F16>), grid, block, lds, s, a); break;
-    case XGPU_OUT_BF16: hipLaunchKernelGGL((k_lin_horizontal<PLANAR, XGPU_OUT_BF16>), grid, block, lds, s, a); break;
-    default:            hipLaunchKernelGGL((k_lin_horizontal<PLANAR, XGPU_OUT_F32>), grid, block, lds, s, a); break;
-    }
-}
-template <bool PLANAR> static void launch_horizontal(const RoisCmOutArgs &a, int dtype, dim3 grid, dim3 block, size_t lds, hipStream_t s)
-{
-    switch (dtype) {
-    case XGPU_OUT_U8:   hipLaunchKernelGGL((k_lin_rois_horizontal<PLANAR, XGPU_OUT_U8>), grid, block, lds, s, a); break;
-    case XGPU_OUT_U16:  hipLaunchKernelGGL((k_lin_rois_horizontal<PLANAR, XGPU_OUT_U16>), grid, block, lds, s, a); break;
-    case XGPU_OUT_F16:  hipLaunchKernelGGL((k_lin_rois_horizontal<PLANAR, XGPU_OUT_F16>), grid, block, lds, s, a); break;
-    case XGPU_OUT_BF16: hipLaunchKernelGGL((k_lin_rois_horizontal<PLANAR, XGPU_OUT_BF16>), grid, block, lds, s, a); break;
-    default:            hipLaunchKernelGGL((k_lin_rois_horizontal<PLANAR, XGPU_OUT_F32>), grid, block, lds, s, a); break;
-    }
-}
-
-// the horizontal pass over `images` images: as many rows per workgroup as 48 KB of LDS hold, 4 at most; one row may pass 48 KB (the host has checked it against
-// LIN_LDS_LIMIT)
-template <class A> static void horizontal_lin(const A &a, int layout, int dtype, unsigned images, hipStream_t s)
-{
-    const size_t per_row = (size_t)3 * a.capy * sizeof(float);
-    int rows = 4;
-    while (rows > 1 && rows * per_row > 48 * 1024) rows >>= 1;
-    const dim3 grid((unsigned)((a.dw + 63) / 64), (unsigned)((a.dh + rows - 1) / rows), images), block(64, rows);
-    if (layout == XGPU_OUT_RGB_PLANAR) launch_horizontal<true>(a, dtype, grid, block, rows * per_row, s);
-    else                               launch_horizontal<false>(a, dtype, grid, block, rows * per_row, s);
-}
+struct LinHorizontal     { template <bool PLANAR, bool RGB, int DT> static auto kernel() { return k_lin_horizontal<PLANAR, DT>; } };
+struct LinRoisHorizontal { template <bool PLANAR, bool RGB, int DT> static auto kernel() { return k_lin_rois_horizontal<PLANAR, DT>; } };
 
 void launch_output_scaled_lin(const ScaledCmOutArgs &a, int layout, int dtype, int upsample, hipStream_t s)
 {
-    const dim3 grid((unsigned)(((a.w + 7) / 8 + 63) / 64), (unsigned)((a.dh + 3) / 4)), block(64, 4);
+    const dim3 grid = vertical_grid(a.w, a.dh, 1u), block(64, 4);
     const size_t lds = sizeof(float) * a.cm.n_lin;
     if (upsample == XGPU_UPSAMPLE_NEAREST) hipLaunchKernelGGL(k_lin_vertical<XGPU_UPSAMPLE_NEAREST>, grid, block, lds, s, a);
     else                                   hipLaunchKernelGGL(k_lin_vertical<XGPU_UPSAMPLE_LINEAR>, grid, block, lds, s, a);
-    horizontal_lin(a, layout, dtype, 1u, s);
+    launch_horizontal<LinHorizontal, LinRow>(a, layout, dtype, 1u, s);
 }
 
 // max_w: the widest rectangle; max_ih: the tallest inner part
 void launch_output_rois_lin(const RoisCmOutArgs &a, int layout, int dtype, int upsample, int max_w, int max_ih, hipStream_t s)
 {
-    const dim3 grid((unsigned)(((max_w + 7) / 8 + 63) / 64), (unsigned)((max_ih + 3) / 4), (unsigned)a.n), block(64, 4);
+    const dim3 grid = vertical_grid(max_w, max_ih, (unsigned)a.n), block(64, 4);
     const size_t lds = sizeof(float) * a.cm.n_lin;
     if (upsample == XGPU_UPSAMPLE_NEAREST) hipLaunchKernelGGL(k_lin_rois_vertical<XGPU_UPSAMPLE_NEAREST>, grid, block, lds, s, a);
     else                                   hipLaunchKernelGGL(k_lin_rois_vertical<XGPU_UPSAMPLE_LINEAR>, grid, block, lds, s, a);
-    horizontal_lin(a, layout, dtype, (unsigned)a.n, s);
+    launch_horizontal<LinRoisHorizontal, LinRow>(a, layout, dtype, (unsigned)a.n, s);
 }

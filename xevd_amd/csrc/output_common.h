@@ -1,7 +1,8 @@
 // output_common.h - what the output kernels share (k_output.hip, k_output_rgb.hip, k_output_yuv.hip; k_stats.hip's light pass): the per-sample depth conversion and DRA
 // mapping, the edge-clamped chroma loads and the 4:2:0 -> luma-resolution upsampling of the device-output contract (INTEGRATION.md section 8a,
 // step 2), the element types and the vector / element stores.  One version of each: a layout that is "the same samples, another place" runs
-// the same code.
+// the same code.  Further down: the lanes' work of the scaled outputs' two passes (the kernel bodies built on it are output_resize.h's) and the gather of the
+// warped and the remapped output.
 #pragma once
 #include "xgpu_internal.h"
 #include <hip/hip_fp16.h>
@@ -248,14 +249,21 @@ static void launch_three_channels(const RgbOutArgs &a, bool planar, int dtype, i
     else        launch_three_layout<K, false>(a, dtype, upsample, grid, s);
 }
 
-// The two passes of the scaled outputs (k_output_scaled.hip: one picture; k_output_rois.hip: a batch of rectangles) as the lanes of either kernel run them.  The
-// files that use them switch float contraction off before they include this header: the normalise and the float matrix are rounded operation by operation.
+// The lanes' work in the two passes of the scaled outputs (k_output_scaled.hip: one picture; k_output_rois.hip: a batch of rectangles; k_output_resampled.hip:
+// either with cubic taps; k_output_ladder.hip: video surfaces); output_resize.h builds the kernels' bodies on it.  The files that use them switch float contraction
+// off before they include this header: the normalise and the float matrix are rounded operation by operation.
 // Vertical pass, one lane: 8 neighbouring columns from x0 of one destination row of one plane - `cnt` source rows from `first` with the weights q.  src / luma: the
 // first sample of the source rectangle in the plane / in the luma plane (the DRA factor of chroma sample (row, x) comes from the unmapped luma sample (2 row, 2 x));
-// d: where the 8 results go, t = (sum qy * clip(dra(sample)) + 2^10) >> 11
+// d: where the 8 results go.  SIGNED picks the rounding shift and the pack, the only things the tap kinds differ in:
+//   false  the non-negative 14-bit triangle taps: t = (sum qy * clip(dra(sample)) + 2^10) >> 11, three fraction bits, <= 32760: an unsigned 16-bit intermediate
+//   true   the cubic taps of either sign: t = (sum qy * clip(dra(sample)) + 2^11) >> 12, two fraction bits, not clipped.  With
+//          sum |q| <= 32768 (xgpu_resample_taps refuses a table with a wider row) |sum qy * sample| <= 4095 * 2^15 < 2^27 and |t| <= 32760: an int16 intermediate,
+//          and int32 accumulators hold this sum as they hold the second pass' (|sum qx * t| <= 2^15 * 32760 < 2^30)
+template <bool SIGNED = false>
 __device__ __forceinline__ void scale_vertical_lane(const ScaledOutArgs &a, int plane, const int16_t *src, const int16_t *luma, int first, int cnt, const int16_t *q,
                                                     int x0, uint16_t *d)
 {
+    constexpr int SH = SIGNED ? 12 : 11;
     const int st = plane ? a.sc : a.sy;
     int acc[8];
     #pragma unroll
@@ -282,7 +290,10 @@ __device__ __forceinline__ void scale_vertical_lane(const ScaledOutArgs &a, int 
     }
     uint32_t w[4];
     #pragma unroll
-    for (int m = 0; m < 4; m++) w[m] = (uint32_t)((acc[2 * m] + (1 << 10)) >> 11) | ((uint32_t)((acc[2 * m + 1] + (1 << 10)) >> 11) << 16);
+    for (int m = 0; m < 4; m++) {
+        const int lo = (acc[2 * m] + (1 << (SH - 1))) >> SH, hi = (acc[2 * m + 1] + (1 << (SH - 1))) >> SH;
+        w[m] = SIGNED ? (uint32_t)(uint16_t)lo | ((uint32_t)(uint16_t)hi << 16) : (uint32_t)lo | ((uint32_t)hi << 16);
+    }
     *(uint4 *)d = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
@@ -300,42 +311,6 @@ __device__ __forceinline__ int filter_column(const uint16_t *lds, const ScaleTap
     int acc = 0;
     for (int k = 0; k < n; k++) acc += (int)q[(size_t)k * t.stride] * (int)l[k];
     return (acc + (1 << 16)) >> 17;
-}
-// The two passes of the bicubic resize (k_output_resampled.hip): the weights have either sign, so the sums and the intermediate are
-// signed.  With sum |q| <= 32768 (xgpu_resample_taps refuses a table with a wider row) |sum qy * sample| <= 4095 * 2^15 < 2^27 and |t| <= 32760, an int16;
-// |sum qx * t| <= 2^15 * 32760 < 2^30: int32 accumulators hold both.
-// Vertical pass, one lane, arguments as scale_vertical_lane's: t = (sum qy * clip(dra(sample)) + 2^11) >> 12, two fraction bits, not clipped
-__device__ __forceinline__ void resample_vertical_lane(const ScaledOutArgs &a, int plane, const int16_t *src, const int16_t *luma, int first, int cnt, const int16_t *q,
-                                                       int x0, int16_t *d)
-{
-    const int st = plane ? a.sc : a.sy;
-    int acc[8];
-    #pragma unroll
-    for (int m = 0; m < 8; m++) acc[m] = 0;
-    for (int k = 0; k < cnt; k++) {
-        const int row = first + k, qk = q[k];
-        const S16x8u s = *(const S16x8u *)(src + (size_t)row * st + x0);
-        int v[8];
-        #pragma unroll
-        for (int m = 0; m < 8; m++) v[m] = s.v[m];
-        if (a.dra) {
-            if (plane == 0) {
-                #pragma unroll
-                for (int m = 0; m < 8; m++) v[m] = dra1(a.dra, 0, v[m], 0);
-            } else {
-                const int16_t *l = luma + (size_t)(2 * row) * a.sy + 2 * x0;
-                const S16x8u l0 = *(const S16x8u *)l, l1 = *(const S16x8u *)(l + 8);
-                #pragma unroll
-                for (int m = 0; m < 8; m++) v[m] = dra1(a.dra, plane, v[m], m < 4 ? l0.v[2 * m] : l1.v[2 * m - 8]);
-            }
-        }
-        #pragma unroll
-        for (int m = 0; m < 8; m++) acc[m] += qk * min(max(v[m], 0), a.smax);
-    }
-    uint32_t w[4];
-    #pragma unroll
-    for (int m = 0; m < 4; m++) w[m] = (uint32_t)(uint16_t)((acc[2 * m] + (1 << 11)) >> 12) | ((uint32_t)(uint16_t)((acc[2 * m + 1] + (1 << 11)) >> 12) << 16);
-    *(uint4 *)d = make_uint4(w[0], w[1], w[2], w[3]);
 }
 // destination column o of the staged row of signed samples: v = clip((sum qx * t + 2^15) >> 16, 0, smax)
 __device__ __forceinline__ int resample_column(const int16_t *lds, const ScaleTaps &t, int o, int s0, int smax)

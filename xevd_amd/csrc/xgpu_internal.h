@@ -514,6 +514,9 @@ static inline size_t cm_table_floats(int n_lin, bool tone, bool enc) { return (s
 void launch_output_cm(const CmOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 // k_output_scaled.hip: the cropped picture resized to dw x dh and converted (xgpu_pic_output_device_scaled).  RgbOutArgs' source, destination
 // and conversion fields (w, h, cw, ch: the SOURCE size; pitch / plane: of the dw x dh destination; aligned, hc, ve, vo are not read), then the taps and the two passes'.
+// The five files of the two-pass resize outputs (this one, k_output_rois.hip, k_output_resampled.hip, k_output_scaled_cm.hip, k_output_scaled_lin.hip) share the bodies
+// of their horizontal kernels, the body of the batch vertical kernel and the launch of the horizontal pass (output_resize.h); the argument types below differ in
+// what a body's row and pixel policies read.
 struct ScaleTaps { const int32_t *first, *count; const int16_t *w; int stride; };      // one axis of one plane, on the device
 struct ScaledOutArgs : RgbOutArgs {
     int      dw, dh;                // destination size

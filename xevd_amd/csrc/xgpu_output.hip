@@ -680,22 +680,31 @@ int xgpu_pic_output_device_scaled_cm(xgpu_ctx *c, int pic, const xgpu_dra_luts *
 {
     return output_scaled(c, "pic_output_device_scaled_cm", pic, dra, f, sc, cm, d_dst, dst_size, stream);
 }
+// what a _check entry ends in: the layout, then whether the transform's tables would build (cm_prepare's order), without a device
+static int cm_dry_run(const xgpu_output_format *f, const xgpu_colour_transform *cm, int bit_depth)
+{
+    if (!is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+    std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
+    return t ? xgpu_colour_tables(f, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
+}
 // the plain call's checks and codes first, then the layout and the transform (cm_prepare's order)
 int xgpu_output_scaled_cm_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_colour_transform *cm, int width, int height, int bit_depth)
 {
     const int rc = xgpu_output_scaled_check(f, sc, width, height, bit_depth);
     if (rc < 0 || !cm) return rc;
-    if (!is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
-    std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
-    return t ? xgpu_colour_tables(f, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
+    return cm_dry_run(f, cm, bit_depth);
 }
 // the linear-light form's own refusals behind the plain call's (section 8n), without a device: the float32 intermediate, then a transform that is missing
 static const size_t ROIS_MID_LIMIT = (size_t)512 << 20;
-static size_t lin_mid_bytes(int ws, int rows) { return (size_t)3 * rows * align8(ws) * sizeof(float); }
+// the bytes of the intermediate of a ws-wide source with `rows` destination rows: 16-bit Y, Cb, Cr rows, or (lin) float32 R, G, B rows at luma width
+static size_t intermediate_bytes(int ws, int rows, bool lin)
+{
+    return lin ? (size_t)3 * rows * align8(ws) * sizeof(float) : (size_t)rows * mid_row_samples(ws) * sizeof(uint16_t);
+}
 static int scaled_lin_refusal(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_colour_transform *cm, int width, const char **why)
 {
     *why = "the float32 intermediate of the call passes 512 MiB";
-    if (lin_mid_bytes(width - f->crop[0] - f->crop[1], sc->height) > ROIS_MID_LIMIT) return XGPU_ERR_UNSUPPORTED;
+    if (intermediate_bytes(width - f->crop[0] - f->crop[1], sc->height, true) > ROIS_MID_LIMIT) return XGPU_ERR_UNSUPPORTED;
     *why = "filtering in linear light needs a colour transform";
     return cm ? XGPU_OK : XGPU_ERR_INVALID_ARGUMENT;
 }
@@ -736,7 +745,7 @@ static int output_scaled(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_l
         if (rc < 0) { snprintf(c->err, sizeof(c->err), "%s: cannot make the tap tables for %dx%d -> %dx%d", who, ws, hs, wd, hd); return rc; }
     }
     if (lin && (size_t)3 * tb.capy * sizeof(float) > LIN_LDS_LIMIT) { snprintf(c->err, sizeof(c->err), "%s: a row's spans pass the LDS of one launch", who); return XGPU_ERR_UNEXPECTED; }
-    TRY(grow(c, who, &c->sc_mid, &c->sc_mid_cap, lin ? lin_mid_bytes(ws, hd) : (size_t)hd * mid_row_samples(ws) * sizeof(uint16_t), "intermediate"));
+    TRY(grow(c, who, &c->sc_mid, &c->sc_mid_cap, intermediate_bytes(ws, hd, lin), "intermediate"));
     if (!cached && c->sc_tab_cap < blob.size()) {
         c->sc_key[0] = -1;      // no key names a block that is freed
         TRY(grow(c, who, &c->sc_tab, &c->sc_tab_cap, blob.size(), "block of tap tables"));
@@ -807,7 +816,7 @@ static size_t rois_pad_and_pitch(const xgpu_output_format *f, const xgpu_scale_p
 }
 // The whole of a call's argument checks, without a device: the bytes the destination needs, or 0 with *rc = the code, `why` (a buffer of 160 bytes) and *bad =
 // the rectangle it names (-1: none).  image_pitch / mid_bytes (may be NULL): the bytes between two images, and the intermediate of the call - the sum over the
-// rectangles of Hi * mid_row_samples(Ws) * 2 (lin, the form filtered in linear light: of lin_mid_bytes(Ws, Hi)).
+// rectangles of intermediate_bytes(Ws, Hi, lin) (lin: the form filtered in linear light).
 static size_t rois_size(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp, const xgpu_roi *rois, int n, int width, int height, int bd,
                         int *rc, char *why, int *bad, size_t *image_pitch, size_t *mid_bytes, bool lin = false)
 {
@@ -840,7 +849,7 @@ static size_t rois_size(const xgpu_output_format *f, const xgpu_scale_params *sc
             snprintf(why, 160, "roi %d: %d x %d to %d x %d is outside 1/64 .. 8 times per axis", i, r.width, r.height, in[2], in[3]);
             return 0;
         }
-        mid += lin ? lin_mid_bytes(r.width, in[3]) : (size_t)in[3] * mid_row_samples(r.width) * sizeof(uint16_t);
+        mid += intermediate_bytes(r.width, in[3], lin);
         if (mid > ROIS_MID_LIMIT) { snprintf(why, 160, "roi %d: the intermediate of the call passes 512 MiB here", i); return 0; }
     }
     *bad = -1;
@@ -901,7 +910,7 @@ static int build_roi_block(xgpu_ctx *c, const xgpu_output_format *f, const xgpu_
         d.ix = in[0]; d.iy = in[1]; d.iw = in[2]; d.ih = in[3];
         d.mid = (uint32_t)(mid / (lin ? sizeof(float) : sizeof(uint16_t)));
         d.mpy = align8(r.width); d.mpc = align8(r.width >> 1);
-        mid += lin ? lin_mid_bytes(r.width, in[3]) : (size_t)in[3] * mid_row_samples(r.width) * sizeof(uint16_t);
+        mid += intermediate_bytes(r.width, in[3], lin);
         for (int t = 0; t < 4; t++) {
             d.first[t] = (uint32_t)(st.base + st.tb.off_first[t]); d.count[t] = (uint32_t)(st.base + st.tb.off_count[t]); d.wt[t] = (uint32_t)(st.base + st.tb.off_w[t]);
             d.stride[t] = st.tb.stride[t];
@@ -911,6 +920,14 @@ static int build_roi_block(xgpu_ctx *c, const xgpu_output_format *f, const xgpu_
         b.max_w = std::max(b.max_w, r.width); b.max_ih = std::max(b.max_ih, in[3]);
     }
     return XGPU_OK;
+}
+// the batch's fields of the kernels' arguments: the intermediate, the widest spans, the block (on the device at `blk`), the pad value of a letterboxed call
+static void batch_args(xgpu_ctx *c, const RoiBlock &b, const uint8_t *blk, int n, const xgpu_roi_params *rp, RoisOutArgs &a)
+{
+    a.mid = c->sc_mid;
+    a.capy = b.capy; a.capc = b.capc;
+    a.blk = blk; a.n = n;
+    for (int k = 0; k < 3; k++) a.padv[k] = rp->fit == XGPU_FIT_LETTERBOX ? rp->pad[k] : 0.f;
 }
 static int output_rois(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
                        const xgpu_roi *rois, int n, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream, bool lin = false);
@@ -937,9 +954,7 @@ int xgpu_output_rois_lin_check(const xgpu_output_format *f, const xgpu_scale_par
     (void)rois_size(f, sc, rp, rois, n_rois, width, height, bit_depth, &rc, why, &bad, NULL, NULL, true);
     if (bad_index) *bad_index = bad;
     if (rc < 0) return rc;
-    if (!cm || !is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
-    std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
-    return t ? xgpu_colour_tables(f, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
+    return cm ? cm_dry_run(f, cm, bit_depth) : XGPU_ERR_INVALID_ARGUMENT;
 }
 static int output_rois(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_roi_params *rp,
                        const xgpu_roi *rois, int n, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream, bool lin)
@@ -969,10 +984,7 @@ static int output_rois(xgpu_ctx *c, const char *who, int pic, const xgpu_dra_lut
     RoisCmOutArgs a;
     memset(&a, 0, sizeof(a));
     scaled_common_args(c, pic, dra, f, sc, d_dst, a);
-    a.mid = c->sc_mid;
-    a.capy = b.capy; a.capc = b.capc;
-    a.blk = c->roi_blk; a.n = n;
-    for (int k = 0; k < 3; k++) a.padv[k] = rp->fit == XGPU_FIT_LETTERBOX ? rp->pad[k] : 0.f;
+    batch_args(c, b, c->roi_blk, n, rp, a);
     if (lin) {
         fill_siting(f->chroma_loc, a);
         fill_cm(c, f, *c->cm_tab, a, a.cm);
@@ -1046,7 +1058,7 @@ static int output_resampled(xgpu_ctx *c, const char *who, int pic, const xgpu_dr
     TRY(check_device_dst(c, who, d_dst, need));
     const xgpu_roi whole = { 0, 0, c->sp.width - f->crop[0] - f->crop[1], c->sp.height - f->crop[2] - f->crop[3] };
     const xgpu_roi_params stretch = { XGPU_FIT_STRETCH, { 0.f, 0.f, 0.f }, 0 };
-    if (!batch) { rp = &stretch; rois = &whole; n = 1; mid_need = (size_t)sc.height * mid_row_samples(whole.width) * sizeof(uint16_t); }
+    if (!batch) { rp = &stretch; rois = &whole; n = 1; mid_need = intermediate_bytes(whole.width, sc.height, false); }
     const int key[7] = { whole.width, whole.height, sc.width, sc.height, rs->kernel, rs->antialias, f->chroma_loc };
     const bool cached = !batch && c->rs_blk && !memcmp(key, c->rs_key, sizeof(key));
     RoiBlock b;      // made here, before anything is queued
@@ -1071,10 +1083,7 @@ static int output_resampled(xgpu_ctx *c, const char *who, int pic, const xgpu_dr
     RoisOutArgs a;
     memset(&a, 0, sizeof(a));
     scaled_common_args(c, pic, dra, f, &sc, d_dst, a);
-    a.mid = c->sc_mid;
-    a.capy = b.capy; a.capc = b.capc;
-    a.blk = blk; a.n = n;
-    for (int k = 0; k < 3; k++) a.padv[k] = rp->fit == XGPU_FIT_LETTERBOX ? rp->pad[k] : 0.f;
+    batch_args(c, b, blk, n, rp, a);
     launch_output_resampled(a, f->layout, f->dtype, b.max_w, b.max_ih, s);
     return out_join(c, stream, s);      // the slot, the DRA tables, the block and the intermediate
 }
