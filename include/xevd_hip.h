@@ -512,6 +512,47 @@ int    xgpu_output_packed_check(const xgpu_packed_format *f, const xgpu_colour_t
 int    xgpu_output_packed_coeffs(const xgpu_packed_format *f, int bit_depth, int32_t coef[5], int *shift, float fcoef[5], uint32_t *alpha_code);
 int    xgpu_pic_output_device_packed(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f,
                                      const xgpu_colour_transform *cm /* NULL: none */, void *d_dst, size_t dst_size, void *stream);
+/* ---- 3D LUT output (k_output_lut3d.hip): the R'G'B' of the two RGB layouts and of the packed RGBA / RGB10A2 surfaces through a colour transform that exists
+   only as a table - a .cube look, a camera log to display conversion, a vendor's HDR to SDR mapping, gamut mapping that is more than a clip.  Calls of their own:
+   xgpu_pic_output_device, _cm and _packed keep their kernels and their bits.  All integers (tests/lut3d_ref.py restates it in numpy):
+     input    per pixel the integer R'G'B' code c_k at the coding depth B of the U16 form (crop, DRA, chroma upsampling, matrix, range, clip to 0 .. M = 2^B - 1)
+     shaper   three tables S_k[0 .. M] of uint16 positions, p_k = S_k[c_k]; the identity is S[c] = floor((2 * 65535 * c + M) / (2 M))
+     cube     n nodes per axis, 2 <= n <= 65, three uint16 values per node, host order the .cube order: red fastest, node (r, g, b) at r + n * (g + n * b)
+     cell     q_k = p_k * (n - 1), i_k = min(q_k / 65535, n - 2), f_k = q_k - 65535 * i_k in [0, 65535]
+     tetrahedral interpolation: with the axes ordered f_a >= f_b >= f_c, V0 = node(i), V1 = V0 stepped on axis a, V2 = V1 stepped on axis b, V3 = node(i + 1);
+              per output channel s = (65535 - f_a) V0 + (f_a - f_b) V1 + (f_b - f_c) V2 + f_c V3 and v = (s + 32767) / 65535 (floor; s + 32767 < 2^32)
+     store    integer dtypes o = (v * (2^D - 1) + 32767) / 65535 with D = 8 for U8, D = B for U16 (out_bit_depth 0 or B), D = 16 for U16 with out_bit_depth 16
+              (o = v; only xgpu_pic_output_device_lut3d takes it), D = 10 for RGB10A2; float dtypes float32(v) * float32(1 / 65535), F16 / BF16 that value rounded
+              to nearest even.  bgr, alpha, row_pitch and the layouts are those of the calls without a LUT.
+   With the identity shaper and the identity cube e_i = floor((2 * 65535 * i + n - 1) / (2 (n - 1))), v = p: the U16 output is xgpu_pic_output_device's U16 RGB
+   bit for bit at every depth and the U8 output its U8 RGB at B = 8 - not at other depths (U8 is then a rescaled code at depth B, not the 8-bit matrix) and not
+   in the float dtypes (v / 65535 is not the float matrix).
+   Host-only helpers, no context, double arithmetic with + - * / and floor only, so that every host makes the same table:
+     xgpu_lut3d_from_float   n^3 x 3 floats in .cube order -> uint16 nodes floor(clip(v, 0, 1) * 65535 + 0.5), NaN -> 0
+     xgpu_lut3d_identity     the identity cube
+     xgpu_lut3d_shaper       out[k][c] for c = 0 .. M: x = c / M, t = clip((x - in_min[k]) / (in_max[k] - in_min[k]), 0, 1) (in_min / in_max NULL: 0 / 1; in_max <=
+                             in_min or not finite: XGPU_ERR_INVALID_ARGUMENT); without a curve the position is floor(t * 65535 + 0.5) - with 0 / 1 bounds the
+                             identity above -, with a curve (n_curve >= 2 rows of 3 floats, column k for channel k) u = t * (n_curve - 1), j = min(floor(u),
+                             n_curve - 2), y = clip(curve[j] + (u - j) * (curve[j + 1] - curve[j]), 0, 1), NaN -> 0, position floor(y * 65535 + 0.5)
+   A LUT lives in a context as a handle 0 .. XGPU_MAX_LUT3D - 1: xgpu_lut3d_create uploads nodes (n^3 x 3, .cube order) and shaper (3 x 2^B, NULL: the identity)
+   once and blocks until they are on the device; xgpu_lut3d_destroy waits for every queued reader first.  n outside 2 .. 65: XGPU_ERR_UNSUPPORTED; no free handle:
+   XGPU_ERR_OUT_OF_MEMORY.
+   The two output calls take xgpu_pic_output_device's / xgpu_pic_output_device_packed's format, destination (xgpu_output_format_size / xgpu_output_packed_size),
+   stream and ordering.  Refusals, all before anything is queued, in this order: the plain call's, with its codes (U16 with out_bit_depth 16 passes);
+   a layout that is not RGB (the 4:2:2 layouts): XGPU_ERR_INVALID_ARGUMENT; a handle that names no LUT: XGPU_ERR_INVALID_ARGUMENT.  xgpu_output_lut3d_check
+   (host only; exactly one of f and pf is not NULL; n stands for the handle): 0 or that code, n outside 2 .. 65: XGPU_ERR_UNSUPPORTED, last. */
+#define XGPU_MAX_LUT3D 8
+int    xgpu_lut3d_from_float(const float *rgb, int n, uint16_t *nodes);
+int    xgpu_lut3d_identity(int n, uint16_t *nodes);
+int    xgpu_lut3d_shaper(int bit_depth, const float *curve /* NULL or n_curve x 3 */, int n_curve, const float in_min[3], const float in_max[3],
+                         uint16_t *out /* 3 x 2^bit_depth */);
+int    xgpu_output_lut3d_check(const xgpu_output_format *f, const xgpu_packed_format *pf, int n, int width, int height, int bit_depth);
+int    xgpu_lut3d_create(xgpu_ctx *ctx, int n, const uint16_t *nodes, const uint16_t *shaper /* NULL: identity */, int *handle);
+int    xgpu_lut3d_destroy(xgpu_ctx *ctx, int handle);
+int    xgpu_pic_output_device_lut3d(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, int lut, void *d_dst, size_t dst_size,
+                                    void *stream);
+int    xgpu_pic_output_device_packed_lut3d(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f, int lut, void *d_dst,
+                                           size_t dst_size, void *stream);
 /* ---- regions of interest from device memory (k_output_rois_dev.hip): xgpu_pic_output_device_rois for boxes that a detector left on the GPU.  d_boxes points
    to `capacity` boxes in device memory (1 .. XGPU_MAX_ROIS), d_count (may be NULL: all of them) to a device int32 - the live boxes are the first
    min(max(*d_count, 0), capacity).  The host reads neither; the call does not synchronise and nothing comes back to the host.  Descriptors and tap tables are

@@ -77,10 +77,17 @@ The packed leg (xgpu_pic_output_device_packed: k_output_packed_rgb / k_output_pa
 YUYV u8 and Y210 and alternates - the rois leg's protocol - each with the nearest call that existed before it (the interleaved RGB tensor of the dtype, NV12, P010) and
 with the torch route it replaces on top of that call (a cat with an alpha plane; shifts and ors on an int32 tensor; a row repeat and a stack).  Next to the times:
 the ratio of the bytes the two calls move, and whether the packed call takes more than that ratio of its counterpart's time beyond the spread of the run.
+The lut3d leg (xgpu_pic_output_device_lut3d / _packed_lut3d: k_output_lut3d / k_output_packed_lut3d) writes U8 / U16 / F32 interleaved RGB, RGBA u8 and 10:10:10:2
+through a LUT of n = 17, 33, 65 and alternates - the rois leg's protocol - each with the nearest call without a LUT and with that call's colour-managed form
+(PQ / BT.2020 -> sRGB through the tone curve); then the F32 call against the route it replaces, the full-size f32 tensor + a 5-D grid_sample (trilinear, float:
+the largest difference is a record, not a test).  All of it on the random picture and on a smooth gradient.  (profiles/output_lut3d_placements_8k_10b.json was
+taken while the kernel still had its three placements of the tables side by side - the `global`, `shaper_lds` and `all_lds` columns; `shaper_lds` is the kernel
+that stayed, and profiles/output_lut3d_8k_10b.json is this leg as it is now.)
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|resampled|rois|rois_dev|ladder|warp|remap|residual|compare|stats|packed] [--out out/output_device.json]
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|resampled|rois|rois_dev|ladder|warp|remap|residual|compare|stats|packed|lut3d] [--out out/output_device.json]
 """
 import argparse
+import itertools
 import json
 import os
 import sys
@@ -515,6 +522,63 @@ def packed_leg(torch, dec, pic, s, a, res, copy_gbps):
               f"{r['packed']['frac_copy']:.2f} of copy   counterpart {r['counterpart']['us']:8.1f} us ({r['counterpart']['p10_us']:.1f} - {r['counterpart']['p90_us']:.1f})  "
               f"time x{r['time_ratio']:.2f} for bytes x{r['byte_ratio']:.2f}{'  OVER' if r['over_byte_ratio_beyond_spread'] else ''}   "
               f"torch route {rt['torch_route']['us']:8.1f} us = x{r['torch_route_over_packed']:.1f}, equal {r['torch_route_equals_kernel']}")
+
+
+def lut3d_leg(torch, dec, pic, s, a, res, copy_gbps, planes):
+    """the 3D LUT calls at n = 17, 33, 65: U8 / U16 / F32 interleaved RGB, RGBA u8 and 10:10:10:2, each alternated in one loop with
+    (i) the nearest call without a LUT and (ii) its colour-managed form (PQ / BT.2020 -> sRGB with the tone curve); then the F32 call against the torch route it
+    replaces, the full-size f32 tensor + a 5-D grid_sample (trilinear).  On the picture of random samples of the other legs - the worst case for the gather -
+    and on a smooth gradient, where neighbouring pixels share cells."""
+    import torch.nn.functional as F
+    from xevd_amd import abi
+    w, h, bd = a.width, a.height, a.bit_depth
+    top = (1 << bd) - 1
+    yy, xx = np.mgrid[0:h, 0:w]
+    cy, cx = np.mgrid[0:h // 2, 0:w // 2]
+    gradient = [(xx * top // (w - 1)).astype(np.int16), (cy * top // (h // 2 - 1)).astype(np.int16), ((cx + cy) * top // (w // 2 + h // 2 - 2)).astype(np.int16)]
+    del yy, xx, cy, cx
+    to_srgb = dict(src_primaries=9, src_transfer=16, dst_primaries=1, dst_transfer=13, tone_map=True)
+    u8, i16, f32 = torch.uint8, torch.int16, torch.float32
+    forms = [("rgb_u8", dict(channels_last=True, dtype=u8), False, 3), ("rgb_u16", dict(channels_last=True, dtype=i16), False, 6),
+             ("rgb_f32", dict(channels_last=True, dtype=f32), False, 12), ("rgba_u8", dict(layout="rgba", dtype=u8), True, 4), ("rgb10a2", dict(layout="rgb10a2"), True, 4)]
+    res["lut3d"] = {"copy_gbps": copy_gbps, "random": {}, "gradient": {}}
+    luts = {n: dec.lut3d_create(abi.lut3d_identity(dec.lib, n)) for n in (17, 33, 65)}
+    for content, pl in (("random", planes), ("gradient", gradient)):
+        dec.pic_upload(pic, pl)
+        for (form, kw, is_packed, wbytes), n in itertools.product(forms, (17, 33, 65)):
+            plain = dec.pic_output_packed if is_packed else dec.pic_output_tensor
+            out_l, out_c, out_m = dec.pic_output_lut3d(pic, luts[n], matrix=9, **kw), plain(pic, matrix=9, **kw), plain(pic, matrix=9, colour=to_srgb, **kw)
+            r = alternated(torch, s, {"lut3d": lambda: dec.pic_output_lut3d(pic, luts[n], matrix=9, out=out_l, **kw), "plain": lambda: plain(pic, matrix=9, out=out_c, **kw),
+                                      "cm_pq2020_srgb": lambda: plain(pic, matrix=9, colour=to_srgb, out=out_m, **kw)}, a.iters)
+            nbytes = int(w * h * (3 + wbytes))
+            for k in r:
+                r[k].update(gbps=round(nbytes / (r[k]["us"] * 1e-6) / 1e9, 1), frac_copy=round(nbytes / (r[k]["us"] * 1e-6) / 1e9 / copy_gbps, 3))
+            r["bytes"] = nbytes
+            res["lut3d"][content][f"{form}_n{n}"] = r
+            print(f"lut3d {content:8s} {form:8s} n {n:2d}: " + "  ".join(f"{k} {v['us']:7.1f} us ({v['p10_us']:.1f} - {v['p90_us']:.1f})" for k, v in r.items() if isinstance(v, dict)))
+            del out_l, out_c, out_m
+        # the route a LUT user has without the call: the full-size f32 tensor, then a 5-D grid_sample over the cube (trilinear, float)
+        full = dec.pic_output_tensor(pic, channels_last=True, dtype=f32, matrix=9)
+        out = dec.pic_output_lut3d(pic, luts[17], channels_last=True, dtype=f32, matrix=9)
+        for n in (17, 33, 65):
+            vol = torch.from_numpy(abi.lut3d_identity(dec.lib, n).astype(np.float32) / 65535.0).to("cuda:0").reshape(n, n, n, 3).permute(3, 0, 1, 2)[None].contiguous()
+
+            def route():
+                dec.pic_output_tensor(pic, channels_last=True, dtype=f32, matrix=9, out=full)
+                return F.grid_sample(vol, (full * 2.0 - 1.0)[None, None], mode="bilinear", padding_mode="border", align_corners=True)
+
+            rt = alternated(torch, s, {"lut3d": lambda: dec.pic_output_lut3d(pic, luts[n], channels_last=True, dtype=f32, matrix=9, out=out), "torch_route": route},
+                            max(a.iters // 10, 5), warm=2)
+            diff = float((route()[0, :, 0].permute(1, 2, 0) - out).abs().max())
+            rt["torch_route_over_lut3d"] = round(rt["torch_route"]["us"] / rt["lut3d"]["us"], 2)
+            rt["max_abs_diff_vs_torch_route"] = diff
+            res["lut3d"][content][f"torch_route_f32_n{n}"] = rt
+            print(f"lut3d {content:8s} f32 n {n:2d}: call {rt['lut3d']['us']:8.1f} us   f32 tensor + grid_sample {rt['torch_route']['us']:9.1f} us = x{rt['torch_route_over_lut3d']:.1f}   "
+                  f"max |diff| {diff:.2e}")
+        del full, out
+    for h_ in luts.values():
+        dec.lut3d_destroy(h_)
+    dec.pic_upload(pic, planes)      # (the leg uploads its contents into the slot)
 
 
 def ladder_leg(torch, dec, pic, s, a, res):
@@ -952,10 +1016,11 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "resampled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats", "packed"), default="all",
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "resampled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats", "packed", "lut3d"), default="all",
                     help="full: the full-size forms and the side information; scaled: the scaled leg alone; scaled_cm: the colour-managed scaled output alone; scaled_lin: the scaled output filtered in linear light alone; resampled: the bicubic resize alone; rois: the batched regions of interest alone; "
                          "rois_dev: the regions of interest from boxes in device memory alone; ladder: the ladder of scaled P010 surfaces alone; warp: the warped regions of interest alone; remap: the remapped output alone; residual: the residual "
-                         "export alone; compare: the picture comparison alone; stats: the picture statistics alone; packed: the packed display surfaces alone")
+                         "export alone; compare: the picture comparison alone; stats: the picture statistics alone; packed: the packed display surfaces alone; "
+                         "lut3d: the 3D LUT outputs alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -1003,6 +1068,8 @@ def main():
             rois_dev_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "packed"):
             packed_leg(torch, dec, pic, s, a, res, copy_gbps)
+        if a.legs in ("all", "lut3d"):
+            lut3d_leg(torch, dec, pic, s, a, res, copy_gbps, planes)
         if a.legs in ("all", "ladder"):
             ladder_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "warp"):

@@ -5,6 +5,7 @@ application (app/xevd_app.c: -i in.evc -o out.yuv --output-bit-depth N).  usage:
 high bits of 16-bit words, whatever the stream's depth.
 --pix-fmt rgba / bgra / x2bgr10le / x2rgb10le / yuyv422 / uyvy422 / y210le writes packed display surfaces, raw frames a raw-video reader takes
 under those names; the RGB ones compose with --to.
+--lut look.cube writes every picture through that 3D LUT: interleaved 8-bit RGB frames, or the packed RGB --pix-fmt given with it.
 --ladder 3840x2160,1920x1080,... also writes every picture scaled to each of these sizes on the device, in one call per picture: one file per
 rung next to -o, the size in its name (out_1920x1080.yuv), in the --pix-fmt layout."""
 import argparse
@@ -142,6 +143,9 @@ def main():
                     "y210le: packed 4:2:2, 10 bit in the high bits of 16-bit words (all ignore --output-bit-depth; the RGB ones take --to)")
     ap.add_argument("--to", default=None, help="write interleaved 8-bit RGB frames in this colour space instead (srgb, bt709, pq-bt2020, ...: "
                     "StreamDecoder.COLOUR_PRESETS), converted on the device from the primaries / transfer characteristics of the stream's VUI")
+    ap.add_argument("--lut", default=None, metavar="FILE.cube", help="write every picture through this 3D LUT (a .cube file; tetrahedral interpolation on the device, "
+                    "INTEGRATION.md 8q): interleaved 8-bit RGB frames, or - with --pix-fmt rgba / bgra / x2bgr10le / x2rgb10le - that packed surface; not with --to, "
+                    "--size or --ladder")
     ap.add_argument("--side-info", default=None, metavar="FILE", help="also write the coding side information of every picture, in DECODING order: a text line "
                     "'POC h_scu w_scu', then nine planes of h_scu x w_scu little-endian int16 (list 0 / 1 vectors, POC distances, mode, QP, flags: INTEGRATION.md 8c)")
     ap.add_argument("--residual", default=None, metavar="FILE", help="also write the prediction residual of every picture, in DECODING order: a text line "
@@ -175,6 +179,11 @@ def main():
     lad, lad_sizes = {}, []
     if args.pix_fmt in PACKED_PIX_FMTS and (args.ladder is not None or args.size is not None):
         ap.error(f"--pix-fmt {args.pix_fmt}: the packed surfaces have no scaled form (--size, --ladder)")
+    if args.lut is not None:
+        if args.to is not None or args.size is not None or args.ladder is not None:
+            ap.error("--lut: the 3D LUT has the full-size RGB and packed outputs only (not --to, --size, --ladder)")
+        if args.pix_fmt != "yuv420p" and PACKED_PIX_FMTS.get(args.pix_fmt, {}).get("layout") not in ("rgba", "bgra", "rgb10a2", "bgr10a2"):
+            ap.error(f"--lut: a 3D LUT needs an RGB --pix-fmt, not {args.pix_fmt}")
     if args.ladder is not None:
         import torch
         if not args.output:
@@ -238,8 +247,11 @@ def main():
         opts = {k: getattr(torch, v) if k == "dtype" else v for k, v in PACKED_PIX_FMTS[args.pix_fmt].items()}
         if args.to is not None and opts["layout"] in ("yuyv", "uyvy"):
             ap.error(f"--to: a colour transform needs an RGB --pix-fmt, not {args.pix_fmt}")
-        pics = StreamDecoder(data, device=args.device).output_order(packed=opts, to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad)
+        pics = StreamDecoder(data, device=args.device).output_order(packed=opts, to=args.to, side=side, residual=resid, compare=cmp, stats=stats, lut=args.lut, **lad)
         pics = [(p, p["packed"]) for p, _ in pics]
+    elif args.lut is not None:
+        import torch
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), lut=args.lut, side=side, residual=resid, compare=cmp, stats=stats)
     elif args.to is not None:
         import torch
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad)

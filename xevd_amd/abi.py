@@ -86,6 +86,40 @@ def packed_coeffs(lib, fmt, bit_depth):
     return list(coef), shift.value, np.array(list(fcoef), np.float32), alpha.value
 
 
+MAX_LUT3D = 8
+
+
+def lut3d_from_float(lib, rgb):
+    """xgpu_lut3d_from_float: float32 [n, n, n, 3] (or [n^3, 3]) in .cube order -> uint16 [n^3, 3], or the negative code"""
+    rgb = np.ascontiguousarray(rgb, np.float32).reshape(-1, 3)
+    n = int(round(rgb.shape[0] ** (1.0 / 3.0)))
+    if n * n * n != rgb.shape[0]:
+        raise ValueError(f"{rgb.shape[0]} nodes are no cube")
+    nodes = np.empty((n * n * n, 3), np.uint16)
+    rc = lib.xgpu_lut3d_from_float(rgb.ctypes.data_as(C.POINTER(C.c_float)), n, nodes.ctypes.data_as(C.POINTER(C.c_uint16)))
+    return rc if rc < 0 else nodes
+
+
+def lut3d_identity(lib, n):
+    """xgpu_lut3d_identity -> uint16 [n^3, 3], or the negative code"""
+    nodes = np.empty((max(int(n), 0) ** 3, 3), np.uint16)
+    rc = lib.xgpu_lut3d_identity(int(n), nodes.ctypes.data_as(C.POINTER(C.c_uint16)))
+    return rc if rc < 0 else nodes
+
+
+def lut3d_shaper(lib, bit_depth, curve=None, in_min=None, in_max=None):
+    """xgpu_lut3d_shaper -> uint16 [3, 2^bit_depth], or the negative code.  curve: None or float32 [n_curve, 3]"""
+    fp = C.POINTER(C.c_float)
+    if curve is not None:
+        curve = np.ascontiguousarray(curve, np.float32).reshape(-1, 3)
+    lo = None if in_min is None else (C.c_float * 3)(*[float(v) for v in in_min])
+    hi = None if in_max is None else (C.c_float * 3)(*[float(v) for v in in_max])
+    out = np.empty((3, 1 << max(min(int(bit_depth), 16), 0)), np.uint16)
+    rc = lib.xgpu_lut3d_shaper(int(bit_depth), None if curve is None else curve.ctypes.data_as(fp), 0 if curve is None else curve.shape[0], lo, hi,
+                               out.ctypes.data_as(C.POINTER(C.c_uint16)))
+    return rc if rc < 0 else out
+
+
 SIDE_BLOCKS, SIDE_FLOW_PLANAR, SIDE_FLOW_INTERLEAVED = 0, 1, 2
 MODE_IBC = 6
 
@@ -778,6 +812,14 @@ _EXPORTS = {
     "xgpu_output_packed_coeffs": (C.c_int, [C.POINTER(PackedFormat), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "xgpu_pic_output_device_packed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PackedFormat), C.POINTER(ColourTransform), C.c_void_p, C.c_size_t,
                                                 C.c_void_p]),
+    "xgpu_lut3d_from_float": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_uint16)]),
+    "xgpu_lut3d_identity": (C.c_int, [C.c_int, C.POINTER(C.c_uint16)]),
+    "xgpu_lut3d_shaper": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint16)]),
+    "xgpu_output_lut3d_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(PackedFormat), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "xgpu_lut3d_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_int)]),
+    "xgpu_lut3d_destroy": (C.c_int, [C.c_void_p, C.c_int]),
+    "xgpu_pic_output_device_lut3d": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_pic_output_device_packed_lut3d": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PackedFormat), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_scale_taps": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16), C.c_int]),
     "xgpu_output_scaled_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),
     "xgpu_output_scaled_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),

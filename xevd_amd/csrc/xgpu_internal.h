@@ -327,6 +327,7 @@ struct xgpu_dbatch {
 // weights' stride, and the widest span of source samples 64 neighbouring destination columns reach (pass 2's LDS need), rounded to whole groups of 8
 struct ScaleTabs { size_t off_first[4], off_count[4], off_w[4]; int stride[4]; int capy, capc; };
 struct ScaleAxisTab { size_t first, count, w; int stride; };      // one table in a host blob: byte offsets of first[], count[] and the weights (xgpu_scale.hip)
+struct Lut3dSlot { uint8_t *d; int n; };      // one 3D LUT of a context (xgpu_lut3d_create): its device block - the shaper, then the cube -, NULL = free
 struct xgpu_ctx {
     xgpu_seq_params sp;
     int8_t          chroma_qp[2][96];  // [c][qp + 6*(bdc-8)]
@@ -413,6 +414,8 @@ struct xgpu_ctx {
     double          t_ms[XGPU_K_COUNT];
     long long       t_n[XGPU_K_COUNT];
     char            err[256];
+    // xgpu_lut3d_create: the context's 3D LUTs by handle; read by the LUT output calls, which end in the context's stream like every output call
+    Lut3dSlot       lut3d[XGPU_MAX_LUT3D];
 };
 
 // The host threads of a batch builder: workers that stay alive between pictures (a std::thread per phase and picture cost ~0.1 ms each - more than a phase of
@@ -679,6 +682,18 @@ struct Packed422Args : RgbOutArgs {
     int      lsh;                   // U16: 16 - D, the sample in the high bits of the word; U8: 0
 };
 void launch_output_packed_422(const Packed422Args &a, int dtype, bool uyvy, int upsample, hipStream_t s);
+// k_output_lut3d.hip (xgpu_pic_output_device_lut3d / _packed_lut3d): k_output_rgb's arguments (coef / shift / maxv: those of the U16
+// form, whatever the dtype) and the LUT's.  One LUT is one device block: the shaper, then the cube lut3d_shaper_bytes behind it.
+struct Lut3dOutArgs : RgbOutArgs {
+    const uint16_t *shaper;         // [3][maxv + 1] positions
+    const uint2    *cube;           // n^3 records R | G << 16, B: node (r, g, b) at r + n * (g + n * b)
+    int      n;                     // nodes per axis, 2 .. 65
+    uint32_t dmax;                  // integer dtypes: 2^D - 1 of the store
+    uint32_t alpha;                 // the packed layouts' A element (PackedRgbArgs' rule)
+};
+static inline size_t lut3d_shaper_bytes(int bit_depth) { return (size_t)3 * sizeof(uint16_t) << bit_depth; }      // a multiple of 16
+void launch_output_lut3d(const Lut3dOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
+void launch_output_packed_lut3d(const Lut3dOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 // k_side_info.hip: the SCU map of the picture decoded last as nine int16 planes per unit (k_side_blocks) or as a dense motion field (k_side_flow)
 struct SideArgs {
     const ScuRec *maps;

@@ -598,6 +598,113 @@ int xgpu_pic_output_device_packed(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra
     return out_join(c, stream, s);      // the slot, the DRA and the colour tables
 }
 
+// ------------------------------------------------------------------------------------------------ 3D LUT output
+// The format the plain call's checks see: U16 with out_bit_depth 16 - the 16-bit store only this call has - as out_bit_depth 0, which has the same size.
+static xgpu_output_format lut3d_plain_format(const xgpu_output_format *f, bool *full16)
+{
+    xgpu_output_format g = *f;
+    *full16 = is_rgb(f->layout) && f->dtype == XGPU_OUT_U16 && f->out_bit_depth == 16;
+    if (*full16) g.out_bit_depth = 0;
+    return g;
+}
+// the refusals of the RGB call up to the layout, without a device: 0 with *need = the bytes at d_dst, or the code and `why`
+static int lut3d_rgb_check(const xgpu_output_format *f, int width, int height, int bd, size_t *need, bool *full16, const char **why)
+{
+    *why = "format is NULL";
+    if (!f) return XGPU_ERR_INVALID_ARGUMENT;
+    const xgpu_output_format g = lut3d_plain_format(f, full16);
+    *need = format_size(&g, width, height, bd, why);
+    if (*need == 0) return is_rgb(g.layout) && bd >= 8 && bd <= 12 && check_format(&g, bd, why) == XGPU_ERR_UNSUPPORTED ? XGPU_ERR_UNSUPPORTED : XGPU_ERR_INVALID_ARGUMENT;
+    *why = "a 3D LUT needs one of the RGB layouts";
+    return is_rgb(g.layout) ? XGPU_OK : XGPU_ERR_INVALID_ARGUMENT;
+}
+static int lut3d_packed_check(const xgpu_packed_format *f, int width, int height, int bd, size_t *need, const char **why)
+{
+    int rc;
+    *need = packed_size(f, width, height, bd, &rc, why);
+    if (*need == 0) return rc;
+    *why = "a 3D LUT needs XGPU_PACKED_RGBA or XGPU_PACKED_RGB10A2";
+    return is_packed_rgb(f->layout) ? XGPU_OK : XGPU_ERR_INVALID_ARGUMENT;
+}
+int xgpu_output_lut3d_check(const xgpu_output_format *f, const xgpu_packed_format *pf, int n, int width, int height, int bit_depth)
+{
+    if ((f != NULL) == (pf != NULL)) return XGPU_ERR_INVALID_ARGUMENT;
+    size_t need; bool full16; const char *why;
+    const int rc = f ? lut3d_rgb_check(f, width, height, bit_depth, &need, &full16, &why) : lut3d_packed_check(pf, width, height, bit_depth, &need, &why);
+    if (rc < 0) return rc;
+    return n >= 2 && n <= 65 ? XGPU_OK : XGPU_ERR_UNSUPPORTED;
+}
+static const Lut3dSlot *lut3d_slot(xgpu_ctx *c, const char *who, int lut)
+{
+    if (lut >= 0 && lut < XGPU_MAX_LUT3D && c->lut3d[lut].d) return &c->lut3d[lut];
+    snprintf(c->err, sizeof(c->err), "%s: %d names no 3D LUT of this context", who, lut);
+    return NULL;
+}
+// the source, the matrix of the U16 form (the code at the coding depth feeds the shaper, whatever the output dtype), the siting and the LUT; the destination's rows
+// are the caller's to fill
+static void fill_lut3d(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *rf, const Lut3dSlot &l, void *d_dst, Lut3dOutArgs &a)
+{
+    const int bd = c->sp.bit_depth_luma;
+    const DevPic &p = dpic(c, pic);
+    memset(&a, 0, sizeof(a));
+    cropped_planes(p, rf->crop, &a.y, &a.u, &a.v);
+    a.sy = p.s_l; a.sc = p.s_c;
+    a.w = c->sp.width - rf->crop[0] - rf->crop[1]; a.h = c->sp.height - rf->crop[2] - rf->crop[3];
+    a.cw = a.w >> 1; a.ch = a.h >> 1;
+    a.dst = (uint8_t *)d_dst;
+    xgpu_output_format f16 = *rf;
+    f16.dtype = XGPU_OUT_U16; f16.out_bit_depth = 0; f16.row_pitch = 0;
+    fill_conversion(c, dra, &f16, a);      // bgr, range terms, DRA, coef / shift / maxv of the U16 form
+    fill_siting(rf->chroma_loc, a);
+    a.shaper = (const uint16_t *)l.d;
+    a.cube = (const uint2 *)(l.d + lut3d_shaper_bytes(bd));
+    a.n = l.n;
+}
+int xgpu_pic_output_device_lut3d(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, int lut, void *d_dst, size_t dst_size, void *stream)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    const char *why = "";
+    const int bd = c->sp.bit_depth_luma;
+    size_t need; bool full16;
+    const int rc = lut3d_rgb_check(f, c->sp.width, c->sp.height, bd, &need, &full16, &why);
+    if (rc < 0) { snprintf(c->err, sizeof(c->err), "pic_output_device_lut3d: invalid format: %s", why); return rc; }
+    const Lut3dSlot *l = lut3d_slot(c, "pic_output_device_lut3d", lut);
+    if (!l) return XGPU_ERR_INVALID_ARGUMENT;
+    TRY(check_dst(c, "pic_output_device_lut3d", d_dst, dst_size, need, (size_t)elem_size(f->dtype)));
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    Lut3dOutArgs a;
+    fill_lut3d(c, pic, dra, f, *l, d_dst, a);
+    fill_rows(a, d_dst, image_row(f, a.w), a.h, f->row_pitch);
+    a.dmax = f->dtype == XGPU_OUT_U8 ? 255u : full16 ? 65535u : (1u << bd) - 1;
+    launch_output_lut3d(a, f->layout, f->dtype, f->upsample, s);
+    return out_join(c, stream, s);      // the slot, the DRA tables and the LUT
+}
+int xgpu_pic_output_device_packed_lut3d(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f, int lut, void *d_dst, size_t dst_size, void *stream)
+{
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    const char *why = "";
+    const int bd = c->sp.bit_depth_luma;
+    size_t need;
+    const int rc = lut3d_packed_check(f, c->sp.width, c->sp.height, bd, &need, &why);
+    if (rc < 0) { snprintf(c->err, sizeof(c->err), "pic_output_device_packed_lut3d: invalid format: %s", why); return rc; }
+    const Lut3dSlot *l = lut3d_slot(c, "pic_output_device_packed_lut3d", lut);
+    if (!l) return XGPU_ERR_INVALID_ARGUMENT;
+    TRY(check_dst(c, "pic_output_device_packed_lut3d", d_dst, dst_size, need, packed_elem_size(f)));
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    const xgpu_output_format rf = packed_rgb_format(f);
+    Lut3dOutArgs a;
+    fill_lut3d(c, pic, dra, &rf, *l, d_dst, a);
+    fill_rows(a, d_dst, packed_row(f, a.w), a.h, f->row_pitch);
+    a.dmax = f->layout == XGPU_PACKED_RGB10A2 ? 1023u : f->dtype == XGPU_OUT_U8 ? 255u : (1u << bd) - 1;
+    a.alpha = packed_alpha_code(f, bd);
+    launch_output_packed_lut3d(a, f->layout, f->dtype, f->upsample, s);
+    return out_join(c, stream, s);      // the slot, the DRA tables and the LUT
+}
+
 // ------------------------------------------------------------------------------------------------ scaled output into device memory
 // format and scale parameters for a picture of width x height at depth bd: the bytes the destination needs, or 0 with *rc = the code and `why`
 // the part that does not look at the ratio of source and destination: what the batched output (section 8e) shares

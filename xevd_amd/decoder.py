@@ -5,6 +5,7 @@ Mirrors, per picture, what xevd_dec_nalu does after entropy decoding (src_base/x
 Plumbing only (ctypes + numpy); all arithmetic happens in xevd_amd/libxevd_hip.so.  There is no CPU fallback.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -323,6 +324,105 @@ class XgpuDecoder:
                              f"chroma_loc {chroma_loc}, alpha {alpha}, crop {crop}, colour {colour}")
         dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
         self._device_call("xgpu_pic_output_device_packed", out, pic, dl, C.byref(fmt), None if cm is None else C.byref(cm))
+        return out
+
+    def lut3d_create(self, nodes, shaper=None):
+        """A 3D LUT of this context -> its handle (xgpu_lut3d_create).  nodes: the path of a .cube file (lut3d.load_cube: its 1D block and
+        DOMAIN_MIN / MAX become the shaper unless shaper= is given), a float array [n, n, n, 3] / [n^3, 3] in .cube order (red fastest; quantised by
+        xgpu_lut3d_from_float) or uint16 nodes of that shape.  shaper: None (the identity), uint16 [3, 2^B] positions, or dict(curve=, in_min=, in_max=) - the
+        arguments of xgpu_lut3d_shaper.  The tables are made by the library's helpers, never here."""
+        from . import lut3d
+        if isinstance(nodes, (str, os.PathLike)):
+            cube = lut3d.load_cube(nodes)
+            nodes = cube["nodes"]
+            if shaper is None:
+                shaper = cube["shaper"]
+        nodes = np.asarray(nodes)
+        if nodes.dtype != np.uint16:
+            nodes = abi.lut3d_from_float(self.lib, nodes)
+            if isinstance(nodes, int):
+                raise ValueError(f"lut3d_create: invalid cube ({nodes}): 2 .. 65 nodes per axis")
+        nodes = np.ascontiguousarray(nodes).reshape(-1, 3)
+        n = int(round(nodes.shape[0] ** (1.0 / 3.0)))
+        if n * n * n != nodes.shape[0]:
+            raise ValueError(f"lut3d_create: {nodes.shape[0]} nodes are no cube")
+        if isinstance(shaper, dict):
+            shaper = abi.lut3d_shaper(self.lib, self.bit_depth, **shaper)
+            if isinstance(shaper, int):
+                raise ValueError(f"lut3d_create: invalid shaper arguments ({shaper})")
+        sp = None
+        if shaper is not None:
+            shaper = np.ascontiguousarray(shaper)
+            if shaper.dtype != np.uint16 or shaper.shape != (3, 1 << self.bit_depth):
+                raise ValueError(f"lut3d_create: the shaper is uint16 [3, {1 << self.bit_depth}]")
+            sp = shaper.ctypes.data_as(C.POINTER(C.c_uint16))
+        h = C.c_int(-1)
+        self._chk(self.lib.xgpu_lut3d_create(self.ctx, n, nodes.ctypes.data_as(C.POINTER(C.c_uint16)), sp, C.byref(h)), "xgpu_lut3d_create")
+        return h.value
+
+    def lut3d_destroy(self, lut):
+        self._chk(self.lib.xgpu_lut3d_destroy(self.ctx, int(lut)), "xgpu_lut3d_destroy")
+
+    _LUT3D_LAYOUTS = {"rgb": None, "rgba": (abi.PACKED_RGBA, False), "bgra": (abi.PACKED_RGBA, True), "rgb10a2": (abi.PACKED_RGB10A2, False),
+                      "bgr10a2": (abi.PACKED_RGB10A2, True)}
+
+    def pic_output_lut3d(self, pic, lut, layout="rgb", channels_last=False, dtype=None, out_bit_depth=0, alpha=1.0, matrix=1, full_range=False, chroma_loc=0,
+                         upsample="linear", crop=(0, 0, 0, 0), dra=None, bgr=False, out=None):
+        """The picture through the 3D LUT `lut` (a handle of lut3d_create) as a torch tensor on cuda:{device}, made on the device on torch's current stream
+        (xgpu_pic_output_device_lut3d / _packed_lut3d).  layout "rgb": pic_output_tensor's "rgb" shapes and dtypes - out_bit_depth 16 with
+        a 16-bit integer dtype stores the LUT's 16-bit value -; "rgba" / "bgra" / "rgb10a2" / "bgr10a2": pic_output_packed's shapes, dtypes and alpha.  matrix,
+        full_range, chroma_loc, upsample, crop and dra make the R'G'B' code the LUT reads, as in those calls."""
+        import torch
+        if layout not in self._LUT3D_LAYOUTS:
+            raise ValueError(f"layout must be one of {', '.join(map(repr, self._LUT3D_LAYOUTS))}, not {layout!r}")
+        if upsample not in ("linear", "nearest"):
+            raise ValueError(f"upsample must be 'linear' or 'nearest', not {upsample!r}")
+        up = abi.UPSAMPLE_LINEAR if upsample == "linear" else abi.UPSAMPLE_NEAREST
+        cl, cr, ct, cb = (int(v) for v in crop)
+        w, h = self.width - cl - cr, self.height - ct - cb
+        if w <= 0 or h <= 0:
+            raise ValueError(f"invalid output format: crop {crop} leaves no picture")
+        dev = torch.device("cuda", self.sp.device)
+        obd = int(out_bit_depth)
+        if layout == "rgb":
+            dtype = torch.uint8 if dtype is None else dtype
+            codes = _codes()
+            if dtype not in codes:
+                raise ValueError(f"unsupported output dtype {dtype}")
+            fmt = abi.make_output_format(abi.OUT_RGB_INTERLEAVED if channels_last else abi.OUT_RGB_PLANAR, codes[dtype], bgr=bgr, out_bit_depth=obd, matrix=matrix,
+                                         full_range=full_range, chroma_loc=chroma_loc, upsample=up, crop=crop)
+            out = _out_tensor(out, (h, w, 3) if channels_last else (3, h, w), dtype, dev)
+            fmt.row_pitch = _row_pitch(out.stride(), not channels_last, h, 3 * w if channels_last else w, 3) * dtype.itemsize
+            rc = self.lib.xgpu_output_lut3d_check(C.byref(fmt), None, 2, self.width, self.height, self.bit_depth)
+            name = "xgpu_pic_output_device_lut3d"
+        else:
+            if channels_last or bgr:
+                raise ValueError(f"{layout}: channels_last and bgr belong to layout 'rgb'")
+            lay, pbgr = self._LUT3D_LAYOUTS[layout]
+            if lay == abi.PACKED_RGB10A2:
+                if dtype not in (None, torch.int32) or obd != 0:
+                    raise ValueError(f"{layout}: the words are torch.int32; dtype and out_bit_depth stay unset")
+                dtype, code, shape, last = torch.int32, 0, (h, w), 1
+            else:
+                dtype = torch.uint8 if dtype is None else dtype
+                codes = _codes()
+                if dtype not in codes:
+                    raise ValueError(f"{layout}: unsupported output dtype {dtype}")
+                code, shape, last = codes[dtype], (h, w, 4), 4
+            fmt = abi.make_packed_format(lay, code, bgr=pbgr, out_bit_depth=obd, matrix=matrix, full_range=full_range, chroma_loc=chroma_loc, upsample=up, crop=crop,
+                                         alpha=alpha)
+            out = _out_tensor(out, shape, dtype, dev)
+            st = out.stride()
+            if st[1:] != ((last, 1) if len(shape) == 3 else (1,)) or st[0] < w * last:
+                raise ValueError(f"out: strides {st} are not rows of W x {last} elements")
+            fmt.row_pitch = st[0] * dtype.itemsize
+            rc = self.lib.xgpu_output_lut3d_check(None, C.byref(fmt), 2, self.width, self.height, self.bit_depth)
+            name = "xgpu_pic_output_device_packed_lut3d"
+        if rc < 0:
+            raise ValueError(f"invalid LUT output format ({rc}): layout {layout}, dtype {dtype}, out_bit_depth {out_bit_depth}, matrix {matrix}, "
+                             f"chroma_loc {chroma_loc}, alpha {alpha}, crop {crop}")
+        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
+        self._device_call(name, out, pic, dl, C.byref(fmt), int(lut))
         return out
 
     def _scaled_setup(self, a):

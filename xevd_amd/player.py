@@ -117,7 +117,7 @@ class StreamDecoder:
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
                  residual=None, compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
-                 linear_light=False, resample=None, packed=None):
+                 linear_light=False, resample=None, packed=None, lut=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -164,7 +164,22 @@ class StreamDecoder:
         packed=dict(layout=..., ...) (keyword arguments of XgpuDecoder.pic_output_packed): every picture as a packed display surface - RGBA, 10:10:10:2, packed
         4:2:2 - under params["packed"], next to whatever else was asked as surfaces= is.  Matrix, range, chroma siting and the DRA tables are the stream's
         (tensor_options), the crop defaults to the SPS crop when apply_crop is set, and with to= the RGB layouts' colour= is made from the stream's VUI as it is
-        for tensor="""
+        for tensor=
+        lut=<path of a .cube file> | <nodes, as XgpuDecoder.lut3d_create takes them> | <a handle of that call> (with tensor=, layout "rgb", and / or packed= with
+        one of its RGB layouts): every picture through that 3D LUT (XgpuDecoder.pic_output_lut3d) - a look, a log to display or HDR to
+        SDR conversion that exists only as a table.  A path or nodes are uploaded once, at the first picture.  Not together with to=, size=, rois=, warp=,
+        remap= or surfaces=: the LUT has the full-size RGB and packed forms only"""
+        if lut is not None:
+            if tensor is None and packed is None:
+                raise ValueError("lut: needs tensor=dict(...) or packed=dict(layout=...)")
+            clash = [k for k, v in (("to", to), ("size", size), ("rois", rois), ("warp", warp), ("remap", remap), ("surfaces", surfaces)) if v is not None]
+            if clash:
+                raise ValueError(f"lut: not together with {', '.join(k + '=' for k in clash)} - the 3D LUT has the full-size RGB and packed outputs only")
+            if tensor is not None and tensor.get("layout", "rgb") != "rgb":
+                raise ValueError(f"lut: a 3D LUT needs tensor layout 'rgb', not {tensor['layout']!r}")
+            if packed is not None and packed.get("layout", "rgba") in ("yuyv", "uyvy"):
+                raise ValueError(f"lut: a 3D LUT needs one of the packed RGB layouts, not {packed['layout']!r}")
+        lut_handle = []
         if surfaces is None and surface_options is not None:
             raise ValueError("surface_options: needs surfaces=[(H, W), ...]")
         if to is not None and tensor is None and packed is None:
@@ -200,6 +215,11 @@ class StreamDecoder:
         th.start()
         slots, free = {}, []
         n_decoded = [0]
+
+        def lut_of(dec):
+            if not lut_handle:      # (under the lock) an int is a handle of dec.lut3d_create, anything else is what that call takes
+                lut_handle.append(int(lut) if isinstance(lut, int) else dec.lut3d_create(lut))
+            return lut_handle[0]
 
         def decode(p):
             dec, hb = self._dec, p["batch"]
@@ -259,7 +279,7 @@ class StreamDecoder:
                 if to is not None and kw.get("layout", "rgba") not in ("yuyv", "uyvy"):
                     kw.setdefault("colour", self.colour_transform(p["colour"], to))
                 with self._lock:
-                    p["packed"] = dec.pic_output_packed(cur, **kw)
+                    p["packed"] = dec.pic_output_packed(cur, **kw) if lut is None else dec.pic_output_lut3d(cur, lut_of(dec), **kw)
             planes = None
             if tensor is not None:
                 kw = self.tensor_options(p, tensor)
@@ -270,7 +290,9 @@ class StreamDecoder:
                     if v is not None:
                         kw.setdefault(k, v)
                 with self._lock:
-                    if resample is not None:
+                    if lut is not None:
+                        planes = dec.pic_output_lut3d(cur, lut_of(dec), **kw)
+                    elif resample is not None:
                         planes = dec.pic_output_resampled(cur, **resample, **kw)
                     elif warp is not None:
                         planes = dec.pic_output_warped(cur, warp(p) if callable(warp) else warp, **kw)
@@ -329,19 +351,19 @@ class StreamDecoder:
 
     def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
                      compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
-                     linear_light=False, resample=None, packed=None):
+                     linear_light=False, resample=None, packed=None, lut=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
         params["residual"] as numpy - for kind "yuv420" the pair (flat array, (Y, Cb, Cr) views of it); compare= (as pictures takes it, the callable and the
         sequence in DECODING order): params["compare"], its map as a numpy array; stats= (as pictures takes it): params["stats"], its histograms as numpy arrays;
         surfaces= / surface_layout= / surface_options= (as pictures takes them): params["surfaces"], a list of numpy arrays; resample= (as pictures takes it);
-        packed=dict(...) (as pictures takes it): params["packed"], a numpy array"""
+        packed=dict(...) (as pictures takes it): params["packed"], a numpy array; lut= (as pictures takes it)"""
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
                                        residual=residual, compare=compare, stats=stats, warp=warp, remap=remap, remap_step=remap_step, surfaces=surfaces,
                                        surface_layout=surface_layout, surface_options=surface_options, linear_light=linear_light, resample=resample,
-                                       packed=packed):
+                                       packed=packed, lut=lut):
             if p["is_idr"]:
                 epoch += 1
             if surfaces is not None:      # (synchronises torch's current stream: the tensors are complete)
