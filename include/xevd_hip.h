@@ -553,6 +553,50 @@ int    xgpu_pic_output_device_lut3d(xgpu_ctx *ctx, int pic, const xgpu_dra_luts 
                                     void *stream);
 int    xgpu_pic_output_device_packed_lut3d(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f, int lut, void *d_dst,
                                            size_t dst_size, void *stream);
+/* ---- dithered output (k_output_dither.hip): the integer forms of the RGB layouts, of NV12 / P016 and of the packed RGBA / RGB10A2 surfaces with an ordered
+   (Bayer) or blue-noise dither in place of the final rounding, so that an 8-bit surface from a 10- or 12-bit stream keeps its gradients.  Calls of their own:
+   every other call keeps its kernels and its bits.  INTEGRATION.md section 8r is the contract; tests/dither_ref.py restates it in numpy.
+     matrix   mh x mw ranks, uint16, row-major; mw, mh powers of two in 1 .. 128; L = 2^k levels, 1 <= k <= 14; every rank < L (no permutation required)
+     rank     of output pixel (x, y) in cropped destination coordinates: r = M[(y + phase_y) & (mh - 1)][(x + phase_x) & (mw - 1)]; all channels of a pixel
+              share it; a chroma sample of NV12 / P016 uses its chroma-plane coordinates (j, i), Cb and Cr share r
+     rule     clip(floor(v + r / L)), v the unrounded value in output code units:
+              matrix path (RGB, RGBA, RGB10A2 without a transform)   ch = clip((sum + (r << (S - k))) >> S, 0, 2^D - 1), sum the matrix' sum before its rounding
+                                                                     constant, S = 27 - D (k <= S required)
+              depth conversion (NV12, P016 with D below the coding depth)   the rounding constant 1 << (shift - 1) of either rule becomes (r << shift) >> k;
+                                                                     signedness and clip stay; with shift <= 0 the sample is the plain call's
+              with a transform (integer dtypes)                      code = min(rd(q * outmax (+) r / L), outmax): float32 product, float32 sum, rounded down
+   A 1 x 1 matrix with k = 1 and rank 1 (threshold 1/2) gives the plain calls' integers bit for bit, except with a transform, whose plain rule rounds ties to even.
+   Host-only constructors, integers only:
+     xgpu_dither_bayer   side n = 2^log2n (log2n 1 .. 7), L = n^2: for bit b of x and y, bit 2 (log2n - 1 - b) + 1 of the rank is bit b of x ^ y, bit
+                         2 (log2n - 1 - b) is bit b of y
+     xgpu_dither_blue    side n = 2^log2n (log2n 2 .. 7), L = n^2, a permutation by greedy void filling on the torus: int64 energy E = 0; tie = a permutation of
+                         0 .. n^2 - 1 (Fisher-Yates from the back, j = (s >> 33) % (i + 1) with s = s * 6364136223846793005 + 1442695040888963407 mod 2^64 before
+                         every draw, s0 = seed); for rank 0, 1, ...: the unfilled cell with the least E * n^2 + tie gets the rank, and an integer Gaussian (radius 6,
+                         wrapping, sigma^2 = 2.25, scaled by 2^20, a table by dx^2 + dy^2) centred on it is added to E
+     xgpu_dither_phase   px = ((uint32)(index * 0x9E3779B1) >> 16) & (mw - 1), py = ((uint32)(index * 0x85EBCA6B) >> 16) & (mh - 1): a phase per picture
+   A matrix lives in a context as a handle 0 .. XGPU_MAX_DITHER - 1: xgpu_dither_create uploads it once and blocks until it is on the device; xgpu_dither_destroy
+   waits for every queued reader first.  Sizes or k outside their ranges: XGPU_ERR_UNSUPPORTED; a rank >= L: XGPU_ERR_INVALID_ARGUMENT; no free handle:
+   XGPU_ERR_OUT_OF_MEMORY.
+   The two output calls take the plain calls' format, destination (xgpu_output_format_size / xgpu_output_packed_size), stream and ordering.  Refusals, all before
+   anything is queued, in this order: the plain call's, with its codes; a float dtype: XGPU_ERR_UNSUPPORTED; a layout outside RGB planar / interleaved, NV12, P016,
+   RGBA, RGB10A2: XGPU_ERR_INVALID_ARGUMENT; a transform with NV12 / P016: XGPU_ERR_INVALID_ARGUMENT (then the transform's own refusals, as the plain call has
+   them); a handle that names no matrix: XGPU_ERR_INVALID_ARGUMENT; a phase outside the matrix: XGPU_ERR_INVALID_ARGUMENT; sizes or k outside their ranges, or
+   k > S: XGPU_ERR_UNSUPPORTED.  xgpu_output_dither_check (host only; exactly one of f and pf is not NULL; mw, mh, k stand for the handle, the phase is not seen):
+   0 or that code. */
+#define XGPU_MAX_DITHER 4
+typedef struct xgpu_dither_params { int handle, phase_x, phase_y; } xgpu_dither_params;
+int    xgpu_dither_bayer(int log2n, uint16_t *rank /* n x n */);
+int    xgpu_dither_blue(int log2n, uint32_t seed, uint16_t *rank /* n x n */);
+int    xgpu_dither_phase(uint32_t index, int mw, int mh, int *px, int *py);
+int    xgpu_output_dither_check(const xgpu_output_format *f, const xgpu_packed_format *pf, const xgpu_colour_transform *cm, int mw, int mh, int k, int width,
+                                int height, int bit_depth);
+int    xgpu_dither_create(xgpu_ctx *ctx, int mw, int mh, int k, const uint16_t *rank, int *handle);
+int    xgpu_dither_destroy(xgpu_ctx *ctx, int handle);
+int    xgpu_pic_output_device_dithered(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f,
+                                       const xgpu_colour_transform *cm /* NULL: none */, const xgpu_dither_params *dp, void *d_dst, size_t dst_size, void *stream);
+int    xgpu_pic_output_device_packed_dithered(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f,
+                                              const xgpu_colour_transform *cm /* NULL: none */, const xgpu_dither_params *dp, void *d_dst, size_t dst_size,
+                                              void *stream);
 /* ---- regions of interest from device memory (k_output_rois_dev.hip): xgpu_pic_output_device_rois for boxes that a detector left on the GPU.  d_boxes points
    to `capacity` boxes in device memory (1 .. XGPU_MAX_ROIS), d_count (may be NULL: all of them) to a device int32 - the live boxes are the first
    min(max(*d_count, 0), capacity).  The host reads neither; the call does not synchronise and nothing comes back to the host.  Descriptors and tap tables are

@@ -83,8 +83,12 @@ through a LUT of n = 17, 33, 65 and alternates - the rois leg's protocol - each 
 the largest difference is a record, not a test).  All of it on the random picture and on a smooth gradient.  (profiles/output_lut3d_placements_8k_10b.json was
 taken while the kernel still had its three placements of the tables side by side - the `global`, `shaper_lds` and `all_lds` columns; `shaper_lds` is the kernel
 that stayed, and profiles/output_lut3d_8k_10b.json is this leg as it is now.)
+The dither leg (xgpu_pic_output_device_dithered / _packed_dithered: k_output_dither_rgb / k_output_dither_semiplanar) alternates - the rois leg's protocol - each
+dithered call with the plain call of the same layout, which reads and writes the same bytes: interleaved RGB u8, RGBA u8 through PQ / BT.2020 -> sRGB with the
+tone curve, NV12 u8, and 10:10:10:2 from a 12-bit picture (a second decoder; the other legs' depth is --bit-depth).  RGB u8 runs Bayer 8, blue 64 and blue 128
+side by side, the others blue 64.  Then the torch route the call replaces: the full-size f32 tensor, plus a tiled threshold tensor, floor, clamp and to(uint8).
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|resampled|rois|rois_dev|ladder|warp|remap|residual|compare|stats|packed|lut3d] [--out out/output_device.json]
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|resampled|rois|rois_dev|ladder|warp|remap|residual|compare|stats|packed|lut3d|dither] [--out out/output_device.json]
 """
 import argparse
 import itertools
@@ -581,6 +585,61 @@ def lut3d_leg(torch, dec, pic, s, a, res, copy_gbps, planes):
     dec.pic_upload(pic, planes)      # (the leg uploads its contents into the slot)
 
 
+def dither_leg(torch, dec, pic, s, a, res, copy_gbps):
+    """the dithered calls beside the plain calls of the same layout, and the torch route they replace"""
+    from xevd_amd.decoder import XgpuDecoder
+    w, h = a.width, a.height
+    to_srgb = dict(src_primaries=9, src_transfer=16, dst_primaries=1, dst_transfer=13, tone_map=True)
+    u8 = torch.uint8
+    res["dither"] = {"copy_gbps": copy_gbps, "cases": {}}
+
+    def run(name, d, p, plain, kw, mats, wbytes, phase=(5, 3)):
+        hs = {m: d.dither_create(*args) for m, args in mats.items()}
+        routes = {"plain": (lambda o=plain(p, **kw): plain(p, out=o, **kw))}
+        for m, hd in hs.items():
+            routes[m] = (lambda hd=hd, o=d.pic_output_dithered(p, hd, phase=phase, **kw): d.pic_output_dithered(p, hd, phase=phase, out=o, **kw))
+        r = alternated(torch, s, routes, a.iters)
+        nbytes = int(w * h * (3 + wbytes))
+        for k in routes:
+            r[k].update(gbps=round(nbytes / (r[k]["us"] * 1e-6) / 1e9, 1), frac_copy=round(nbytes / (r[k]["us"] * 1e-6) / 1e9 / copy_gbps, 3))
+        for m in hs:
+            r[m]["time_ratio"] = round(r[m]["us"] / r["plain"]["us"], 3)
+            r[m]["above_plain_p90"] = bool(r[m]["us"] > r["plain"]["p90_us"])
+            d.dither_destroy(hs[m])
+        r["bytes"] = nbytes
+        res["dither"]["cases"][name] = r
+        print(f"dither {name:24s} " + "  ".join(f"{k} {v['us']:7.1f} us ({v['p10_us']:.1f} - {v['p90_us']:.1f})" for k, v in r.items() if isinstance(v, dict)))
+
+    blue64 = {"blue64": ("blue", 64)}
+    run("rgb_u8", dec, pic, dec.pic_output_tensor, dict(layout="rgb", channels_last=True, dtype=u8), {"bayer8": ("bayer", 8), "blue64": ("blue", 64), "blue128": ("blue", 128)}, 3)
+    run("rgba_u8_cm_pq2020_srgb", dec, pic, dec.pic_output_packed, dict(layout="rgba", dtype=u8, matrix=9, colour=to_srgb), blue64, 4)
+    run("nv12_u8", dec, pic, dec.pic_output_tensor, dict(layout="nv12", dtype=u8), blue64, 1.5)
+    rng = np.random.default_rng(12)
+    with XgpuDecoder(w, h, 12, device=0, max_pics=2) as d12:
+        p12 = d12.pic_alloc()
+        d12.pic_upload(p12, [rng.integers(0, 1 << 12, sh).astype(np.int16) for sh in ((h, w), (h // 2, w // 2), (h // 2, w // 2))])
+        run("rgb10a2_from_12_bit", d12, p12, d12.pic_output_packed, dict(layout="rgb10a2"), blue64, 4)
+    # the route a user has without the call: the f32 tensor (400 MB at 8K), a tiled threshold tensor, floor, clamp, to(uint8)
+    hd = dec.dither_create("blue", 64)
+    from xevd_amd import abi
+    m = torch.from_numpy(abi.dither_blue(dec.lib, 6, 1).astype(np.float32) / 4096.0).to("cuda:0")
+    thr = m.repeat((h + 63) // 64, (w + 63) // 64)[:h, :w, None].contiguous()
+    full = dec.pic_output_tensor(pic, channels_last=True, dtype=torch.float32)
+    out = dec.pic_output_dithered(pic, hd, "rgb", channels_last=True)
+
+    def route():
+        dec.pic_output_tensor(pic, channels_last=True, dtype=torch.float32, out=full)
+        return (full * 255.0 + thr).floor_().clamp_(0.0, 255.0).to(u8)
+
+    rt = alternated(torch, s, {"dithered": lambda: dec.pic_output_dithered(pic, hd, "rgb", channels_last=True, out=out), "torch_route": route}, max(a.iters // 10, 5), warm=2)
+    rt["torch_route_over_dithered"] = round(rt["torch_route"]["us"] / rt["dithered"]["us"], 2)
+    rt["max_abs_diff_vs_torch_route"] = int((route().to(torch.int16) - out.to(torch.int16)).abs().max())      # (the float matrix is not the integer one: a record)
+    res["dither"]["torch_route_rgb_u8_blue64"] = rt
+    print(f"dither rgb_u8 blue64: call {rt['dithered']['us']:8.1f} us   f32 tensor + threshold, floor, clamp, to(uint8) {rt['torch_route']['us']:9.1f} us = "
+          f"x{rt['torch_route_over_dithered']:.1f}   max |diff| {rt['max_abs_diff_vs_torch_route']}")
+    dec.dither_destroy(hd)
+
+
 def ladder_leg(torch, dec, pic, s, a, res):
     """the picture to P010 rungs 3840x2160, 1920x1080, 1280x720 and 640x360 (those inside the scaled output's limits for the picture): the one call
     (pic_output_surfaces) against four one-rung calls, against the route without it - the full-size P010 surface, then per rung and plane
@@ -1016,11 +1075,11 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "resampled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats", "packed", "lut3d"), default="all",
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "resampled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats", "packed", "lut3d", "dither"), default="all",
                     help="full: the full-size forms and the side information; scaled: the scaled leg alone; scaled_cm: the colour-managed scaled output alone; scaled_lin: the scaled output filtered in linear light alone; resampled: the bicubic resize alone; rois: the batched regions of interest alone; "
                          "rois_dev: the regions of interest from boxes in device memory alone; ladder: the ladder of scaled P010 surfaces alone; warp: the warped regions of interest alone; remap: the remapped output alone; residual: the residual "
                          "export alone; compare: the picture comparison alone; stats: the picture statistics alone; packed: the packed display surfaces alone; "
-                         "lut3d: the 3D LUT outputs alone")
+                         "lut3d: the 3D LUT outputs alone; dither: the dithered outputs alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -1070,6 +1129,8 @@ def main():
             packed_leg(torch, dec, pic, s, a, res, copy_gbps)
         if a.legs in ("all", "lut3d"):
             lut3d_leg(torch, dec, pic, s, a, res, copy_gbps, planes)
+        if a.legs in ("all", "dither"):
+            dither_leg(torch, dec, pic, s, a, res, copy_gbps)
         if a.legs in ("all", "ladder"):
             ladder_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "warp"):

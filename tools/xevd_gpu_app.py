@@ -146,6 +146,10 @@ def main():
     ap.add_argument("--lut", default=None, metavar="FILE.cube", help="write every picture through this 3D LUT (a .cube file; tetrahedral interpolation on the device, "
                     "INTEGRATION.md 8q): interleaved 8-bit RGB frames, or - with --pix-fmt rgba / bgra / x2bgr10le / x2rgb10le - that packed surface; not with --to, "
                     "--size or --ladder")
+    ap.add_argument("--dither", default=None, choices=("bayer", "blue"), help="dither instead of rounding where the output has fewer bits than the stream (INTEGRATION.md "
+                    "8r): with --pix-fmt nv12 / p010 / rgba / bgra / x2bgr10le / x2rgb10le, or with --to (8-bit RGB); not with --lut, --size or --ladder")
+    ap.add_argument("--dither-size", type=int, default=None, metavar="N", help="with --dither: the side of the matrix, a power of two (default: bayer 8, blue 64)")
+    ap.add_argument("--dither-temporal", action="store_true", help="with --dither: move the matrix from picture to picture (xgpu_dither_phase of the POC)")
     ap.add_argument("--side-info", default=None, metavar="FILE", help="also write the coding side information of every picture, in DECODING order: a text line "
                     "'POC h_scu w_scu', then nine planes of h_scu x w_scu little-endian int16 (list 0 / 1 vectors, POC distances, mode, QP, flags: INTEGRATION.md 8c)")
     ap.add_argument("--residual", default=None, metavar="FILE", help="also write the prediction residual of every picture, in DECODING order: a text line "
@@ -184,6 +188,15 @@ def main():
             ap.error("--lut: the 3D LUT has the full-size RGB and packed outputs only (not --to, --size, --ladder)")
         if args.pix_fmt != "yuv420p" and PACKED_PIX_FMTS.get(args.pix_fmt, {}).get("layout") not in ("rgba", "bgra", "rgb10a2", "bgr10a2"):
             ap.error(f"--lut: a 3D LUT needs an RGB --pix-fmt, not {args.pix_fmt}")
+    dith = {}
+    if args.dither is not None:
+        if args.lut is not None or args.size is not None or args.ladder is not None:
+            ap.error("--dither: the dithered output has the full-size forms only (not --lut, --size, --ladder)")
+        if args.to is None and (args.pix_fmt not in ("nv12", "p010") and PACKED_PIX_FMTS.get(args.pix_fmt, {}).get("layout") not in ("rgba", "bgra", "rgb10a2", "bgr10a2")):
+            ap.error(f"--dither: needs --pix-fmt nv12, p010, rgba, bgra, x2bgr10le or x2rgb10le, or --to; not {args.pix_fmt}")
+        dith = dict(dither=dict(kind=args.dither, size=args.dither_size or (8 if args.dither == "bayer" else 64), temporal=args.dither_temporal))
+    elif args.dither_size is not None or args.dither_temporal:
+        ap.error("--dither-size, --dither-temporal: need --dither")
     if args.ladder is not None:
         import torch
         if not args.output:
@@ -247,20 +260,20 @@ def main():
         opts = {k: getattr(torch, v) if k == "dtype" else v for k, v in PACKED_PIX_FMTS[args.pix_fmt].items()}
         if args.to is not None and opts["layout"] in ("yuyv", "uyvy"):
             ap.error(f"--to: a colour transform needs an RGB --pix-fmt, not {args.pix_fmt}")
-        pics = StreamDecoder(data, device=args.device).output_order(packed=opts, to=args.to, side=side, residual=resid, compare=cmp, stats=stats, lut=args.lut, **lad)
+        pics = StreamDecoder(data, device=args.device).output_order(packed=opts, to=args.to, side=side, residual=resid, compare=cmp, stats=stats, lut=args.lut, **lad, **dith)
         pics = [(p, p["packed"]) for p, _ in pics]
     elif args.lut is not None:
         import torch
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), lut=args.lut, side=side, residual=resid, compare=cmp, stats=stats)
     elif args.to is not None:
         import torch
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad, **dith)
     elif args.pix_fmt == "yuv420p":
         pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side, residual=resid, compare=cmp, stats=stats, **lad)
     else:      # the same pictures as semi-planar surfaces (xgpu_pic_output_device into a torch tensor, copied to the host picture by picture)
         import torch
         opts = dict(layout="nv12", dtype=torch.uint8) if args.pix_fmt == "nv12" else dict(layout="p016", dtype=torch.int16, out_bit_depth=10)
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid, compare=cmp, stats=stats, **lad)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid, compare=cmp, stats=stats, **lad, **dith)
     dt = time.perf_counter() - t0
     if cmp is not None:
         cmp.finish()

@@ -120,6 +120,43 @@ def lut3d_shaper(lib, bit_depth, curve=None, in_min=None, in_max=None):
     return rc if rc < 0 else out
 
 
+MAX_DITHER = 4
+
+
+class DitherParams(C.Structure):
+    _fields_ = [("handle", C.c_int), ("phase_x", C.c_int), ("phase_y", C.c_int)]
+
+
+def make_dither_params(handle, phase=(0, 0)):
+    """xgpu_dither_params (include/xevd_hip.h): the matrix of a dithered output call and its phase (x, y)"""
+    d = DitherParams()
+    d.handle, d.phase_x, d.phase_y = int(handle), int(phase[0]), int(phase[1])
+    return d
+
+
+def dither_bayer(lib, log2n):
+    """xgpu_dither_bayer -> uint16 [n, n] ranks below n^2, or the negative code"""
+    n = 1 << max(min(int(log2n), 7), 0)
+    rank = np.empty((n, n), np.uint16)
+    rc = lib.xgpu_dither_bayer(int(log2n), rank.ctypes.data_as(C.POINTER(C.c_uint16)))
+    return rc if rc < 0 else rank
+
+
+def dither_blue(lib, log2n, seed=1):
+    """xgpu_dither_blue -> uint16 [n, n], a permutation of 0 .. n^2 - 1, or the negative code"""
+    n = 1 << max(min(int(log2n), 7), 0)
+    rank = np.empty((n, n), np.uint16)
+    rc = lib.xgpu_dither_blue(int(log2n), int(seed) & 0xFFFFFFFF, rank.ctypes.data_as(C.POINTER(C.c_uint16)))
+    return rc if rc < 0 else rank
+
+
+def dither_phase(lib, index, mw, mh):
+    """xgpu_dither_phase -> (phase_x, phase_y) of picture `index`, or the negative code"""
+    px, py = C.c_int(), C.c_int()
+    rc = lib.xgpu_dither_phase(int(index) & 0xFFFFFFFF, int(mw), int(mh), C.byref(px), C.byref(py))
+    return rc if rc < 0 else (px.value, py.value)
+
+
 SIDE_BLOCKS, SIDE_FLOW_PLANAR, SIDE_FLOW_INTERLEAVED = 0, 1, 2
 MODE_IBC = 6
 
@@ -820,6 +857,17 @@ _EXPORTS = {
     "xgpu_lut3d_destroy": (C.c_int, [C.c_void_p, C.c_int]),
     "xgpu_pic_output_device_lut3d": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_pic_output_device_packed_lut3d": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PackedFormat), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_dither_bayer": (C.c_int, [C.c_int, C.POINTER(C.c_uint16)]),
+    "xgpu_dither_blue": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_uint16)]),
+    "xgpu_dither_phase": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "xgpu_output_dither_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(PackedFormat), C.POINTER(ColourTransform), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_int]),
+    "xgpu_dither_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_int)]),
+    "xgpu_dither_destroy": (C.c_int, [C.c_void_p, C.c_int]),
+    "xgpu_pic_output_device_dithered": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ColourTransform), C.POINTER(DitherParams),
+                                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_pic_output_device_packed_dithered": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PackedFormat), C.POINTER(ColourTransform),
+                                                         C.POINTER(DitherParams), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_scale_taps": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16), C.c_int]),
     "xgpu_output_scaled_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),
     "xgpu_output_scaled_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),

@@ -328,6 +328,9 @@ struct xgpu_dbatch {
 struct ScaleTabs { size_t off_first[4], off_count[4], off_w[4]; int stride[4]; int capy, capc; };
 struct ScaleAxisTab { size_t first, count, w; int stride; };      // one table in a host blob: byte offsets of first[], count[] and the weights (xgpu_scale.hip)
 struct Lut3dSlot { uint8_t *d; int n; };      // one 3D LUT of a context (xgpu_lut3d_create): its device block - the shaper, then the cube -, NULL = free
+// one dither matrix of a context (xgpu_dither_create): mh rows of mw + 16 ranks - each row followed by its own first 16 entries, so that a run of up to 16 ranks
+// from any column is contiguous -, NULL = free
+struct DitherSlot { uint16_t *d; int mw, mh, k; };
 struct xgpu_ctx {
     xgpu_seq_params sp;
     int8_t          chroma_qp[2][96];  // [c][qp + 6*(bdc-8)]
@@ -416,6 +419,8 @@ struct xgpu_ctx {
     char            err[256];
     // xgpu_lut3d_create: the context's 3D LUTs by handle; read by the LUT output calls, which end in the context's stream like every output call
     Lut3dSlot       lut3d[XGPU_MAX_LUT3D];
+    // xgpu_dither_create: the context's dither matrices by handle, read by the dithered output calls under the same ordering
+    DitherSlot      dither[XGPU_MAX_DITHER];
 };
 
 // The host threads of a batch builder: workers that stay alive between pictures (a std::thread per phase and picture cost ~0.1 ms each - more than a phase of
@@ -694,6 +699,20 @@ struct Lut3dOutArgs : RgbOutArgs {
 static inline size_t lut3d_shaper_bytes(int bit_depth) { return (size_t)3 * sizeof(uint16_t) << bit_depth; }      // a multiple of 16
 void launch_output_lut3d(const Lut3dOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 void launch_output_packed_lut3d(const Lut3dOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
+// k_output_dither.hip (xgpu_pic_output_device_dithered / _packed_dithered): the matrix of one call.  Pixel (x, y) of the cropped
+// destination has rank tab[((y + py) & mhm) * stride + ((x + px) & mwm) + run] for run 0 .. 15 (DitherSlot's extended rows)
+struct DitherArgs {
+    const uint16_t *tab;
+    int      stride, mwm, mhm;      // ranks per extended row; mw - 1, mh - 1
+    int      px, py, k;             // the phase; L = 2^k levels
+};
+// the three-channel family: PackedRgbArgs (k_output_packed_rgb's, `plane` read by the planar sink) with, for the matrix path, coef / shift / maxv of the store's
+// depth D and, with a transform, cm.outmax = 2^D - 1
+struct DitherRgbArgs : PackedRgbArgs { DitherArgs di; };
+enum { DITHER_SINK_PLANAR, DITHER_SINK_INTERLEAVED, DITHER_SINK_RGBA, DITHER_SINK_RGB10A2 };
+void launch_output_dither_rgb(const DitherRgbArgs &a, int sink, int dtype, int upsample, bool cm, hipStream_t s);
+struct DitherSemiArgs : SemiPlanarArgs { DitherArgs di; };
+void launch_output_dither_semiplanar(const DitherSemiArgs &a, int dtype, hipStream_t s);
 // k_side_info.hip: the SCU map of the picture decoded last as nine int16 planes per unit (k_side_blocks) or as a dense motion field (k_side_flow)
 struct SideArgs {
     const ScuRec *maps;

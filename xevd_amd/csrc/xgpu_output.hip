@@ -1,4 +1,4 @@
-// xgpu_output.hip - the C ABI of include/xevd_hip.h, part 2: the outputs into device memory - the picture as it is, colour-managed, as a packed display surface, scaled, as a batch of regions of
+// xgpu_output.hip - the C ABI of include/xevd_hip.h, part 2: the outputs into device memory - the picture as it is, colour-managed, as a packed display surface, through a 3D LUT, dithered, scaled, as a batch of regions of
 // interest (rectangles from the host or boxes in device memory), of affine maps or of coordinate grids, as a ladder of scaled video surfaces, the coding side information, the residual, the comparison with a reference and the statistics
 // of one picture - and their argument checks without a device.
 // Every entry point is the same skeleton: check the format -> check_dst -> (check_dra; tables, made on the host) -> grow a context buffer -> out_fork -> fill an args struct ->
@@ -703,6 +703,177 @@ int xgpu_pic_output_device_packed_lut3d(xgpu_ctx *c, int pic, const xgpu_dra_lut
     a.alpha = packed_alpha_code(f, bd);
     launch_output_packed_lut3d(a, f->layout, f->dtype, f->upsample, s);
     return out_join(c, stream, s);      // the slot, the DRA tables and the LUT
+}
+
+// ------------------------------------------------------------------------------------------------ dithered output
+static bool is_int_dtype(int dtype) { return dtype == XGPU_OUT_U8 || dtype == XGPU_OUT_U16; }
+// The refusals that look at the format and the transform alone, in the contract's order: the plain call's with its codes, a float dtype, a layout without a
+// dithered form, a transform on a video surface, then the transform's own (as the plain call has them, for the layouts that take one).  0 with *need = the bytes
+// at d_dst and *s_bits = S of the matrix path (0: a path without that bound), or the code and `why`.  No device is touched.
+static int dither_format_check(const xgpu_output_format *f, const xgpu_packed_format *pf, const xgpu_colour_transform *cm, int width, int height, int bd,
+                               size_t *need, int *s_bits, const char **why)
+{
+    *s_bits = 0;
+    if (f) {
+        *need = format_size(f, width, height, bd, why);
+        if (*need == 0) return is_rgb(f->layout) && bd >= 8 && bd <= 12 && check_format(f, bd, why) == XGPU_ERR_UNSUPPORTED ? XGPU_ERR_UNSUPPORTED : XGPU_ERR_INVALID_ARGUMENT;
+        *why = "a dithered output needs an integer dtype";
+        if (!is_int_dtype(f->dtype)) return XGPU_ERR_UNSUPPORTED;
+        *why = "a dithered output needs one of the RGB layouts, NV12 or P016";
+        if (!is_rgb(f->layout) && !is_semiplanar(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+        *why = "a colour transform needs one of the RGB layouts";
+        if (cm && !is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+        if (is_rgb(f->layout) && !cm) *s_bits = 27 - (f->dtype == XGPU_OUT_U8 ? 8 : bd);
+    } else {
+        int rc;
+        *need = packed_size(pf, width, height, bd, &rc, why);
+        if (*need == 0) return rc;
+        *why = "a dithered output needs an integer dtype";
+        if (pf->layout == XGPU_PACKED_RGBA && !is_int_dtype(pf->dtype)) return XGPU_ERR_UNSUPPORTED;
+        *why = "a dithered packed output needs XGPU_PACKED_RGBA or XGPU_PACKED_RGB10A2";
+        if (!is_packed_rgb(pf->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+        if (!cm) *s_bits = 27 - (pf->layout == XGPU_PACKED_RGB10A2 ? 10 : pf->dtype == XGPU_OUT_U8 ? 8 : bd);
+    }
+    return XGPU_OK;
+}
+// the last refusal: the matrix itself, and k against S on the matrix path
+static int dither_matrix_check(int mw, int mh, int k, int s_bits, const char **why)
+{
+    *why = "dither matrix: sides are powers of two in 1 .. 128, 1 <= k <= 14, and k <= S on the matrix path";
+    auto side_ok = [](int v) { return v >= 1 && v <= 128 && !(v & (v - 1)); };
+    return side_ok(mw) && side_ok(mh) && k >= 1 && k <= 14 && (!s_bits || k <= s_bits) ? XGPU_OK : XGPU_ERR_UNSUPPORTED;
+}
+int xgpu_output_dither_check(const xgpu_output_format *f, const xgpu_packed_format *pf, const xgpu_colour_transform *cm, int mw, int mh, int k, int width,
+                             int height, int bit_depth)
+{
+    if ((f != NULL) == (pf != NULL)) return XGPU_ERR_INVALID_ARGUMENT;
+    size_t need; int s_bits; const char *why;
+    const int rc = dither_format_check(f, pf, cm, width, height, bit_depth, &need, &s_bits, &why);
+    if (rc < 0) return rc;
+    if (cm) {
+        const xgpu_output_format rf = f ? *f : packed_rgb_format(pf);
+        std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
+        const int trc = t ? xgpu_colour_tables(&rf, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
+        if (trc < 0) return trc;
+    }
+    return dither_matrix_check(mw, mh, k, s_bits, &why);
+}
+// the refusals that look at the call's matrix: the handle, the phase, the matrix against the path; the matrix in `di`
+static int dither_prepare(xgpu_ctx *c, const char *who, const xgpu_dither_params *dp, int s_bits, DitherArgs &di)
+{
+    if (!dp || dp->handle < 0 || dp->handle >= XGPU_MAX_DITHER || !c->dither[dp->handle].d) {
+        snprintf(c->err, sizeof(c->err), "%s: %d names no dither matrix of this context", who, dp ? dp->handle : -1);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    const DitherSlot &sl = c->dither[dp->handle];
+    if (dp->phase_x < 0 || dp->phase_x >= sl.mw || dp->phase_y < 0 || dp->phase_y >= sl.mh) {
+        snprintf(c->err, sizeof(c->err), "%s: phase (%d, %d) lies outside the %d x %d matrix", who, dp->phase_x, dp->phase_y, sl.mw, sl.mh);
+        return XGPU_ERR_INVALID_ARGUMENT;
+    }
+    const char *why;
+    const int rc = dither_matrix_check(sl.mw, sl.mh, sl.k, s_bits, &why);
+    if (rc < 0) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return rc; }
+    di.tab = sl.d; di.stride = sl.mw + 16; di.mwm = sl.mw - 1; di.mhm = sl.mh - 1;
+    di.px = dp->phase_x; di.py = dp->phase_y; di.k = sl.k;
+    return XGPU_OK;
+}
+int xgpu_pic_output_device_dithered(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm,
+                                    const xgpu_dither_params *dp, void *d_dst, size_t dst_size, void *stream)
+{
+    static const char who[] = "pic_output_device_dithered";
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    const char *why = "format is NULL";
+    const int bd = c->sp.bit_depth_luma;
+    size_t need; int s_bits;
+    const int rc = f ? dither_format_check(f, NULL, cm, c->sp.width, c->sp.height, bd, &need, &s_bits, &why) : XGPU_ERR_INVALID_ARGUMENT;
+    if (rc < 0) { snprintf(c->err, sizeof(c->err), "%s: invalid format: %s", who, why); return rc; }
+    std::unique_ptr<xgpu_colour_tables_t> cm_new;      // a new set of tables: made here, before anything is queued; uploaded and committed below
+    if (cm) TRY(cm_prepare(c, who, f, cm, cm_new));
+    DitherArgs di;
+    TRY(dither_prepare(c, who, dp, s_bits, di));
+    const size_t es = (size_t)elem_size(f->dtype);
+    TRY(check_dst(c, who, d_dst, dst_size, need, es));
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    TRY(cm_commit(c, cm, cm_new, s));
+    const int *cr = f->crop;
+    const DevPic &p = dpic(c, pic);
+    const int w = c->sp.width - cr[0] - cr[1], h = c->sp.height - cr[2] - cr[3];
+    if (is_semiplanar(f->layout)) {      // xgpu_pic_output_device's arguments, and the matrix
+        DitherSemiArgs a;
+        memset(&a, 0, sizeof(a));
+        const int obd = sample_depth(f, bd);
+        cropped_planes(p, cr, &a.y, &a.u, &a.v);
+        a.sy = p.s_l; a.sc = p.s_c;
+        a.w = w; a.ch = h >> 1;
+        a.dst = (uint8_t *)d_dst;
+        fill_rows(static_cast<SemiPlanarArgs &>(a), d_dst, (size_t)w * es, h, f->row_pitch, &SemiPlanarArgs::chroma_off);
+        a.shift = bd - obd; a.out8 = obd == 8; a.maxv = (1 << obd) - 1;
+        a.lsh = f->layout == XGPU_OUT_P016 ? 16 - obd : 0;
+        a.dra = dra ? c->d_dra : NULL;
+        a.di = di;
+        launch_output_dither_semiplanar(a, f->dtype, s);
+    } else {
+        DitherRgbArgs a;
+        memset(&a, 0, sizeof(a));
+        cropped_planes(p, cr, &a.y, &a.u, &a.v);
+        a.sy = p.s_l; a.sc = p.s_c;
+        a.w = w; a.h = h;
+        a.cw = w >> 1; a.ch = h >> 1;
+        a.dst = (uint8_t *)d_dst;
+        fill_rows(a, d_dst, image_row(f, w), h, f->row_pitch);
+        fill_conversion(c, dra, f, a);
+        fill_siting(f->chroma_loc, a);
+        if (cm) fill_cm(c, f, *c->cm_tab, a, a.cm);
+        a.di = di;
+        launch_output_dither_rgb(a, f->layout == XGPU_OUT_RGB_PLANAR ? DITHER_SINK_PLANAR : DITHER_SINK_INTERLEAVED, f->dtype, f->upsample, cm != NULL, s);
+    }
+    return out_join(c, stream, s);      // the slot, the DRA and the colour tables, the matrix
+}
+int xgpu_pic_output_device_packed_dithered(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f, const xgpu_colour_transform *cm,
+                                           const xgpu_dither_params *dp, void *d_dst, size_t dst_size, void *stream)
+{
+    static const char who[] = "pic_output_device_packed_dithered";
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    const char *why = "";
+    const int bd = c->sp.bit_depth_luma;
+    size_t need; int s_bits;
+    const int rc = dither_format_check(NULL, f, cm, c->sp.width, c->sp.height, bd, &need, &s_bits, &why);
+    if (rc < 0) { snprintf(c->err, sizeof(c->err), "%s: invalid format: %s", who, why); return rc; }
+    const xgpu_output_format rf = packed_rgb_format(f);
+    std::unique_ptr<xgpu_colour_tables_t> cm_new;
+    if (cm) TRY(cm_prepare(c, who, &rf, cm, cm_new));
+    DitherArgs di;
+    TRY(dither_prepare(c, who, dp, s_bits, di));
+    TRY(check_dst(c, who, d_dst, dst_size, need, packed_elem_size(f)));
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    TRY(cm_commit(c, cm, cm_new, s));
+    const DevPic &p = dpic(c, pic);
+    const int w = c->sp.width - f->crop[0] - f->crop[1], h = c->sp.height - f->crop[2] - f->crop[3];
+    DitherRgbArgs a;
+    memset(&a, 0, sizeof(a));
+    cropped_planes(p, f->crop, &a.y, &a.u, &a.v);
+    a.sy = p.s_l; a.sc = p.s_c;
+    a.w = w; a.h = h;
+    a.cw = w >> 1; a.ch = h >> 1;
+    a.dst = (uint8_t *)d_dst;
+    fill_rows(a, d_dst, packed_row(f, w), h, f->row_pitch);
+    fill_siting(f->chroma_loc, a);
+    fill_conversion(c, dra, &rf, a);
+    a.alpha = packed_alpha_code(f, bd);
+    if (cm) {      // xgpu_pic_output_device_packed's arguments
+        fill_cm(c, &rf, *c->cm_tab, a, a.cm);
+        if (f->layout == XGPU_PACKED_RGB10A2) a.cm.outmax = 1023.f;
+    } else if (f->layout == XGPU_PACKED_RGB10A2) {
+        matrix_coeffs(f->matrix, f->full_range, bd, 10, a.coef, &a.shift, a.fcoef);
+        a.maxv = 1023;
+    }
+    a.di = di;
+    launch_output_dither_rgb(a, f->layout == XGPU_PACKED_RGBA ? DITHER_SINK_RGBA : DITHER_SINK_RGB10A2, f->dtype, f->upsample, cm != NULL, s);
+    return out_join(c, stream, s);      // the slot, the DRA and the colour tables, the matrix
 }
 
 // ------------------------------------------------------------------------------------------------ scaled output into device memory

@@ -425,6 +425,124 @@ class XgpuDecoder:
         self._device_call(name, out, pic, dl, C.byref(fmt), int(lut))
         return out
 
+    def dither_create(self, kind="blue", size=64, seed=1, levels=None):
+        """A dither matrix of this context -> its handle (xgpu_dither_create).  kind "bayer": the recursive Bayer matrix of side `size`
+        (a power of two, 2 .. 128); "blue": the blue-noise permutation of that side (4 .. 128) from `seed`; both have size^2 levels and are made by the library's
+        constructors, never here.  An integer array [mh, mw] is uploaded as it is: sides powers of two in 1 .. 128, `levels` = L, a power of two in 2 .. 2^14 above
+        every rank (None: the least such power)."""
+        if isinstance(kind, str):
+            if kind not in ("bayer", "blue"):
+                raise ValueError(f"dither_create: kind must be 'bayer', 'blue' or an array of ranks, not {kind!r}")
+            n = int(size)
+            log2n = n.bit_length() - 1
+            if n < 1 or n != 1 << log2n or levels is not None:
+                raise ValueError(f"dither_create: size must be a power of two and levels unset for {kind!r}")
+            rank = abi.dither_bayer(self.lib, log2n) if kind == "bayer" else abi.dither_blue(self.lib, log2n, seed)
+            if isinstance(rank, int):
+                raise ValueError(f"dither_create: {kind!r} has no matrix of side {size} ({rank})")
+            k = 2 * log2n
+        else:
+            rank = np.asarray(kind)
+            if rank.ndim != 2 or rank.dtype.kind not in "iu" or rank.size == 0 or rank.min() < 0 or rank.max() >= 1 << 14:
+                raise ValueError("dither_create: the ranks are a non-empty integer array [mh, mw] with values in 0 .. 2^14 - 1")
+            k = max(int(rank.max()).bit_length(), 1) if levels is None else int(levels).bit_length() - 1
+            if levels is not None and (int(levels) < 2 or int(levels) != 1 << k):
+                raise ValueError(f"dither_create: levels must be a power of two in 2 .. 16384, not {levels}")
+            rank = np.ascontiguousarray(rank, np.uint16)
+        h = C.c_int(-1)
+        self._chk(self.lib.xgpu_dither_create(self.ctx, rank.shape[1], rank.shape[0], k, rank.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(h)), "xgpu_dither_create")
+        self.__dict__.setdefault("_dither_shapes", {})[h.value] = (rank.shape[1], rank.shape[0], k)
+        return h.value
+
+    def dither_destroy(self, dither):
+        self._chk(self.lib.xgpu_dither_destroy(self.ctx, int(dither)), "xgpu_dither_destroy")
+        self.__dict__.setdefault("_dither_shapes", {}).pop(int(dither), None)
+
+    def dither_shape(self, dither):
+        """(mw, mh, k) of a handle of dither_create, or None"""
+        return self.__dict__.get("_dither_shapes", {}).get(int(dither))
+
+    _DITHER_LAYOUTS = {"rgb": None, "nv12": None, "p016": None, "rgba": (abi.PACKED_RGBA, False), "bgra": (abi.PACKED_RGBA, True),
+                       "rgb10a2": (abi.PACKED_RGB10A2, False), "bgr10a2": (abi.PACKED_RGB10A2, True)}
+
+    def pic_output_dithered(self, pic, dither, layout="rgb", phase=(0, 0), colour=None, out=None, channels_last=False, dtype=None, out_bit_depth=0, alpha=1.0,
+                            matrix=1, full_range=False, chroma_loc=0, upsample="linear", crop=(0, 0, 0, 0), dra=None, bgr=False):
+        """The picture with the dither matrix `dither` (a handle of dither_create) at `phase` (x, y) in place of the final rounding, as a torch tensor on
+        cuda:{device}, made on the device on torch's current stream (xgpu_pic_output_device_dithered / _packed_dithered).  layout "rgb",
+        "nv12", "p016": pic_output_tensor's shapes and arguments, integer dtypes only; "rgba" / "bgra" / "rgb10a2" / "bgr10a2": pic_output_packed's.  colour: a
+        colour transform as those calls take it (the RGB layouts and the packed ones)."""
+        import torch
+        if layout not in self._DITHER_LAYOUTS:
+            raise ValueError(f"layout must be one of {', '.join(map(repr, self._DITHER_LAYOUTS))}, not {layout!r}")
+        if upsample not in ("linear", "nearest"):
+            raise ValueError(f"upsample must be 'linear' or 'nearest', not {upsample!r}")
+        up = abi.UPSAMPLE_LINEAR if upsample == "linear" else abi.UPSAMPLE_NEAREST
+        cl, cr, ct, cb = (int(v) for v in crop)
+        w, h = self.width - cl - cr, self.height - ct - cb
+        if w <= 0 or h <= 0:
+            raise ValueError(f"invalid output format: crop {crop} leaves no picture")
+        dev = torch.device("cuda", self.sp.device)
+        obd = int(out_bit_depth)
+        cm = None if colour is None else abi.make_colour_transform(**colour)
+        ints = _codes("uint8", "int16", "uint16")
+        packed = self._DITHER_LAYOUTS[layout]
+        if packed is None:
+            if dtype is None:
+                dtype = torch.int16 if layout == "p016" else torch.uint8
+            if dtype not in ints:
+                raise ValueError(f"{layout}: a dithered output has integer dtypes, not {dtype}")
+            code = ints[dtype]
+            if layout == "rgb":
+                fmt = abi.make_output_format(abi.OUT_RGB_INTERLEAVED if channels_last else abi.OUT_RGB_PLANAR, code, bgr=bgr, out_bit_depth=obd, matrix=matrix,
+                                             full_range=full_range, chroma_loc=chroma_loc, upsample=up, crop=crop)
+                out = _out_tensor(out, (h, w, 3) if channels_last else (3, h, w), dtype, dev)
+                fmt.row_pitch = _row_pitch(out.stride(), not channels_last, h, 3 * w if channels_last else w, 3) * dtype.itemsize
+            else:
+                if channels_last or bgr:
+                    raise ValueError(f"{layout}: channels_last and bgr belong to layout 'rgb'")
+                if code == abi.OUT_U8 and layout == "nv12":
+                    if obd not in (0, 8):
+                        raise ValueError("nv12: torch.uint8 holds 8-bit samples; out_bit_depth above 8 needs a 16-bit integer dtype")
+                    obd = 8
+                fmt = abi.make_output_format(abi.OUT_NV12 if layout == "nv12" else abi.OUT_P016, code, out_bit_depth=obd, crop=crop)
+                out = _out_tensor(out, (h * 3 // 2, w), dtype, dev)
+                st = out.stride()
+                if st[1] != 1 or st[0] < w:
+                    raise ValueError(f"out: strides {st} are not rows of W elements")
+                fmt.row_pitch = st[0] * dtype.itemsize
+            f_arg, pf_arg, name = C.byref(fmt), None, "xgpu_pic_output_device_dithered"
+        else:
+            if channels_last or bgr:
+                raise ValueError(f"{layout}: channels_last and bgr belong to layout 'rgb'")
+            lay, pbgr = packed
+            if lay == abi.PACKED_RGB10A2:
+                if dtype not in (None, torch.int32) or obd != 0:
+                    raise ValueError(f"{layout}: the words are torch.int32; dtype and out_bit_depth stay unset")
+                dtype, code, shape, last = torch.int32, 0, (h, w), 1
+            else:
+                dtype = torch.uint8 if dtype is None else dtype
+                if dtype not in ints:
+                    raise ValueError(f"{layout}: a dithered output has integer dtypes, not {dtype}")
+                code, shape, last = ints[dtype], (h, w, 4), 4
+            fmt = abi.make_packed_format(lay, code, bgr=pbgr, out_bit_depth=obd, matrix=matrix, full_range=full_range, chroma_loc=chroma_loc, upsample=up, crop=crop,
+                                         alpha=alpha)
+            out = _out_tensor(out, shape, dtype, dev)
+            st = out.stride()
+            if st[1:] != ((last, 1) if len(shape) == 3 else (1,)) or st[0] < w * last:
+                raise ValueError(f"out: strides {st} are not rows of W x {last} elements")
+            fmt.row_pitch = st[0] * dtype.itemsize
+            f_arg, pf_arg, name = None, C.byref(fmt), "xgpu_pic_output_device_packed_dithered"
+        rc = self.lib.xgpu_output_dither_check(f_arg, pf_arg, None, 1, 1, 1, self.width, self.height, self.bit_depth)
+        if rc == 0 and cm is not None:
+            rc = self._cm_check(abi.make_output_format(abi.OUT_RGB_INTERLEAVED), cm) if layout not in ("nv12", "p016") else -1
+        if rc < 0:
+            raise ValueError(f"invalid dithered output format ({rc}): layout {layout}, dtype {dtype}, out_bit_depth {out_bit_depth}, matrix {matrix}, "
+                             f"chroma_loc {chroma_loc}, alpha {alpha}, crop {crop}, colour {colour}")
+        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
+        dp = abi.make_dither_params(dither, phase)
+        self._device_call(name, out, pic, dl, f_arg if pf_arg is None else pf_arg, None if cm is None else C.byref(cm), C.byref(dp))
+        return out
+
     def _scaled_setup(self, a):
         """what the scaled outputs check and build alike -> (torch dtype, xgpu_output_format, xgpu_scale_params, H, W, device)"""
         import torch

@@ -117,7 +117,7 @@ class StreamDecoder:
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
                  residual=None, compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
-                 linear_light=False, resample=None, packed=None, lut=None):
+                 linear_light=False, resample=None, packed=None, lut=None, dither=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -168,7 +168,40 @@ class StreamDecoder:
         lut=<path of a .cube file> | <nodes, as XgpuDecoder.lut3d_create takes them> | <a handle of that call> (with tensor=, layout "rgb", and / or packed= with
         one of its RGB layouts): every picture through that 3D LUT (XgpuDecoder.pic_output_lut3d) - a look, a log to display or HDR to
         SDR conversion that exists only as a table.  A path or nodes are uploaded once, at the first picture.  Not together with to=, size=, rois=, warp=,
-        remap= or surfaces=: the LUT has the full-size RGB and packed forms only"""
+        remap= or surfaces=: the LUT has the full-size RGB and packed forms only
+        dither="blue" | "bayer" | dict(kind=, size=, seed=, temporal=True) | <a handle of XgpuDecoder.dither_create> (with tensor=, layouts "rgb", "nv12", "p016",
+        and / or packed= with one of its RGB layouts; integer dtypes): every picture with that dither matrix in place of the final rounding
+        (XgpuDecoder.pic_output_dithered; kind / size / seed as dither_create takes them, 64 and 1 by default).  The matrix is made
+        and uploaded once, at the first picture.  temporal=True moves it from picture to picture by xgpu_dither_phase(poc & 0xFFFFFFFF); without it the phase is
+        (0, 0).  to= goes with it; an option that has no dithered form (size=, rois=, warp=, remap=, resample=, surfaces=, lut=, mean=, std=, float dtypes, the
+        other layouts) raises XgpuError before decoding starts"""
+        dither_opts = None
+        if dither is not None:
+            from .decoder import XgpuError
+            if isinstance(dither, (str, int)):
+                dither_opts = {"handle": dither} if isinstance(dither, int) else {"kind": dither}
+            else:
+                dither_opts = dict(dither)
+            if set(dither_opts) - {"kind", "size", "seed", "temporal", "handle"}:
+                raise XgpuError(f"dither: a kind, a handle or dict(kind=, size=, seed=, temporal=), not the keys {sorted(dither_opts)}")
+            if "handle" not in dither_opts and dither_opts.setdefault("kind", "blue") not in ("blue", "bayer"):
+                raise XgpuError(f"dither: kind must be 'blue' or 'bayer', not {dither_opts['kind']!r}")
+            if tensor is None and packed is None:
+                raise XgpuError("dither: needs tensor=dict(...) or packed=dict(layout=...)")
+            clash = [k for k, v in (("size", size), ("mean", mean), ("std", std), ("rois", rois), ("warp", warp), ("remap", remap), ("resample", resample),
+                                    ("surfaces", surfaces), ("lut", lut), ("linear_light", linear_light or None)) if v is not None]
+            if clash:
+                raise XgpuError(f"dither: not together with {', '.join(k + '=' for k in clash)} - the dithered output has the full-size RGB, NV12 / P016 and packed RGB forms only")
+            for what, opts, layouts, first in (("tensor", tensor, ("rgb", "nv12", "p016"), "rgb"), ("packed", packed, ("rgba", "bgra", "rgb10a2", "bgr10a2"), "rgba")):
+                if opts is None:
+                    continue
+                if opts.get("layout", first) not in layouts:
+                    raise XgpuError(f"dither: {what} layout {opts['layout']!r} has no dithered form (one of {', '.join(layouts)})")
+                dt = opts.get("dtype")
+                if dt is not None and (getattr(dt, "is_floating_point", False) or "float" in str(dt)):
+                    raise XgpuError(f"dither: a dithered output has integer dtypes, not {dt}")
+                if to is not None and opts.get("layout", first) in ("nv12", "p016"):
+                    raise XgpuError("dither: to= needs an RGB layout")
         if lut is not None:
             if tensor is None and packed is None:
                 raise ValueError("lut: needs tensor=dict(...) or packed=dict(layout=...)")
@@ -220,6 +253,18 @@ class StreamDecoder:
             if not lut_handle:      # (under the lock) an int is a handle of dec.lut3d_create, anything else is what that call takes
                 lut_handle.append(int(lut) if isinstance(lut, int) else dec.lut3d_create(lut))
             return lut_handle[0]
+
+        dither_made = []
+
+        def dither_of(dec, p):      # (under the lock) -> (handle, phase) of picture p; the matrix is made at the first picture
+            if not dither_made:
+                h = dither_opts["handle"] if "handle" in dither_opts else dec.dither_create(dither_opts["kind"], dither_opts.get("size", 64), dither_opts.get("seed", 1))
+                if dec.dither_shape(h) is None:
+                    from .decoder import XgpuError
+                    raise XgpuError(f"dither: {h} names no dither matrix of this decoder")
+                dither_made.append((int(h),) + tuple(dec.dither_shape(h)[:2]))
+            h, mw, mh = dither_made[0]
+            return h, abi.dither_phase(dec.lib, p["poc"] & 0xFFFFFFFF, mw, mh) if dither_opts.get("temporal") else (0, 0)
 
         def decode(p):
             dec, hb = self._dec, p["batch"]
@@ -279,7 +324,11 @@ class StreamDecoder:
                 if to is not None and kw.get("layout", "rgba") not in ("yuyv", "uyvy"):
                     kw.setdefault("colour", self.colour_transform(p["colour"], to))
                 with self._lock:
-                    p["packed"] = dec.pic_output_packed(cur, **kw) if lut is None else dec.pic_output_lut3d(cur, lut_of(dec), **kw)
+                    if dither_opts is not None:
+                        h, ph = dither_of(dec, p)
+                        p["packed"] = dec.pic_output_dithered(cur, h, phase=ph, **kw)
+                    else:
+                        p["packed"] = dec.pic_output_packed(cur, **kw) if lut is None else dec.pic_output_lut3d(cur, lut_of(dec), **kw)
             planes = None
             if tensor is not None:
                 kw = self.tensor_options(p, tensor)
@@ -290,7 +339,10 @@ class StreamDecoder:
                     if v is not None:
                         kw.setdefault(k, v)
                 with self._lock:
-                    if lut is not None:
+                    if dither_opts is not None:
+                        h, ph = dither_of(dec, p)
+                        planes = dec.pic_output_dithered(cur, h, phase=ph, **kw)
+                    elif lut is not None:
                         planes = dec.pic_output_lut3d(cur, lut_of(dec), **kw)
                     elif resample is not None:
                         planes = dec.pic_output_resampled(cur, **resample, **kw)
@@ -351,19 +403,19 @@ class StreamDecoder:
 
     def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
                      compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
-                     linear_light=False, resample=None, packed=None, lut=None):
+                     linear_light=False, resample=None, packed=None, lut=None, dither=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
         params["residual"] as numpy - for kind "yuv420" the pair (flat array, (Y, Cb, Cr) views of it); compare= (as pictures takes it, the callable and the
         sequence in DECODING order): params["compare"], its map as a numpy array; stats= (as pictures takes it): params["stats"], its histograms as numpy arrays;
         surfaces= / surface_layout= / surface_options= (as pictures takes them): params["surfaces"], a list of numpy arrays; resample= (as pictures takes it);
-        packed=dict(...) (as pictures takes it): params["packed"], a numpy array; lut= (as pictures takes it)"""
+        packed=dict(...) (as pictures takes it): params["packed"], a numpy array; lut= and dither= (as pictures takes them)"""
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
                                        residual=residual, compare=compare, stats=stats, warp=warp, remap=remap, remap_step=remap_step, surfaces=surfaces,
                                        surface_layout=surface_layout, surface_options=surface_options, linear_light=linear_light, resample=resample,
-                                       packed=packed, lut=lut):
+                                       packed=packed, lut=lut, dither=dither):
             if p["is_idr"]:
                 epoch += 1
             if surfaces is not None:      # (synchronises torch's current stream: the tensors are complete)
