@@ -79,3 +79,18 @@ __device__ __forceinline__ void cm_apply(const RgbOutArgs &a, const CmParams &p,
     cm_linearise(a, t.lin, y, cb, cr, e0, e1, e2);
     cm_from_linear<DT>(p, t, e0, e1, e2, r, g, b);
 }
+
+// The CONV of three_channel_rows (output_common.h) with a transform, for the kernels at full size (k_output_cm, k_output_packed_rgb, k_output_dither_rgb): the
+// arguments are a CmOutArgs handed through as its base, and the tables lie at the front of dynamic LDS - the kernel calls cm_fill_lds(a.cm, cm_lds) first, every
+// thread of the workgroup, before the lanes outside the picture leave, and is launched with cm_lds_bytes.  The F32 instance gives the float32 q of every channel,
+// before a code is made of it (the dither's).
+template <int DT> struct CmConv {
+__device__ static __forceinline__ void apply(const RgbOutArgs &a0, int y, int cb, int cr, uint32_t &r, uint32_t &g, uint32_t &b)
+{
+    const CmOutArgs &a = static_cast<const CmOutArgs &>(a0);
+    extern __shared__ float cm_lds[];
+    cm_apply<DT>(a, a.cm, cm_lds_tables(a.cm, cm_lds), y, cb, cr, r, g, b);
+}
+};
+// the bytes of a transform's tables in LDS (cm_fill_lds's layout): at most 32.8 KB
+static size_t cm_lds_bytes(const CmParams &p) { return sizeof(float) * ((size_t)p.n_lin + (p.tone ? XGPU_CM_CURVE_SIZE : 0) + (p.enc ? XGPU_CM_CURVE_SIZE : 0)); }

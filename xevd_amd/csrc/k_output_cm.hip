@@ -1,7 +1,7 @@
 // k_output_cm.hip - k_output_rgb with a colour transform between the matrix and the store (xgpu_pic_output_device_cm): the R'G'B' code of the fixed-point
 // path at the coding depth -> linear light (one table lookup per channel) -> destination primaries (3x3) -> tone curve or scale, clip -> destination
 // transfer characteristic (an interpolated table lookup per channel) -> the output dtype.  Load, clamp, DRA, upsampling and the stores are
-// output_three_channels (output_common.h), untouched; this file adds the CONV.  The arithmetic is the contract of INTEGRATION.md section 8b and
+// output_three_channels (output_common.h), untouched; this file runs it with the CONV of the transform (CmConv, cm_transform.h).  The arithmetic is the contract of INTEGRATION.md section 8b and
 // tests/colour_cm_ref.py restates it bit for bit, so: no powf / exp2f / log2f, every float32 multiply and add rounded on its own (contraction into FMA is
 // switched off for this file), tables made by the host in double precision (xgpu_colour.hip).  The transform itself is cm_transform.h's, shared with
 // k_output_scaled_cm.hip.
@@ -10,16 +10,6 @@
 // (DESIGN.md section 5c has both measurements; the instances that read global memory were dropped after it).
 #pragma clang fp contract(off)
 #include "cm_transform.h"
-
-// the CONV of output_three_channels: launch_three_channels hands the CmOutArgs through as its base, and the tables lie at the front of dynamic LDS
-template <int DT> struct CmConv {
-__device__ static __forceinline__ void apply(const RgbOutArgs &a0, int y, int cb, int cr, uint32_t &r, uint32_t &g, uint32_t &b)
-{
-    const CmOutArgs &a = static_cast<const CmOutArgs &>(a0);
-    extern __shared__ float cm_lds[];
-    cm_apply<DT>(a, a.cm, cm_lds_tables(a.cm, cm_lds), y, cb, cr, r, g, b);
-}
-};
 
 template <int LAYOUT, int DT, int UP>
 __global__ __launch_bounds__(256) void k_output_cm(const CmOutArgs a)
@@ -33,8 +23,7 @@ struct CmKernels {
     template <bool PLANAR, int DT, int UP> static void launch(const RgbOutArgs &a0, dim3 grid, hipStream_t s)
     {
         const CmOutArgs &a = static_cast<const CmOutArgs &>(a0);      // launch_three_channels hands the reference through
-        const size_t lds = sizeof(float) * cm_table_floats(a.cm.n_lin, a.cm.tone != NULL, a.cm.enc != NULL);      // at most 32.8 KB
-        hipLaunchKernelGGL((k_output_cm<PLANAR ? XGPU_OUT_RGB_PLANAR : XGPU_OUT_RGB_INTERLEAVED, DT, UP>), grid, dim3(64, 4), lds, s, a);
+        hipLaunchKernelGGL((k_output_cm<PLANAR ? XGPU_OUT_RGB_PLANAR : XGPU_OUT_RGB_INTERLEAVED, DT, UP>), grid, dim3(64, 4), cm_lds_bytes(a.cm), s, a);
     }
 };
 

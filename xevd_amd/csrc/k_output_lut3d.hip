@@ -1,7 +1,7 @@
 // k_output_lut3d.hip - k_output_rgb and k_output_packed_rgb with a 3D LUT between the matrix and the store (xgpu_pic_output_device_lut3d / _packed_lut3d): the
 // R'G'B' code of the fixed-point path at the coding depth -> a per-channel shaper table -> tetrahedral interpolation between four nodes of an n x n x n cube of
-// uint16 triples -> the output dtype.  Load, clamp, DRA, upsampling and the stores are output_three_channels' / three_channel_rows' (output_common.h), untouched;
-// this file adds the CONV and, for the packed layouts, k_output_packed_rgb's sink around it.  All of the arithmetic is unsigned 32-bit integer (INTEGRATION.md
+// uint16 triples -> the output dtype.  Load, clamp, DRA, upsampling and the stores are output_common.h's, untouched: output_three_channels for the RGB layouts,
+// output_three_sinks - k_output_packed_rgb's body - for the packed ones; this file adds the CONV.  All of the arithmetic is unsigned 32-bit integer (INTEGRATION.md
 // section 8q; tests/lut3d_ref.py restates it bit for bit): the weights of a cell sum to 65535, a node is at most 65535, so every sum stays below 2^32.
 // The kernel is a gather behind a streaming read: 16 pixels per lane, per pixel three shaper reads and four 8-byte node records (R | G << 16, B | 0 << 16 - one
 // load per vertex).  The shaper (6 KB at 10 bit, 24 KB at 12) is copied into LDS by every workgroup, the cube is read from global memory through L1 / L2 at every
@@ -101,54 +101,25 @@ void launch_output_lut3d(const Lut3dOutArgs &a, int layout, int dtype, int upsam
     launch_three_channels<Lut3dKernels>(a, layout == XGPU_OUT_RGB_PLANAR, dtype, upsample, s);
 }
 
-// ---- the packed layouts: k_output_packed_rgb's sink (RGBA in every dtype in one pass - the elements are the LUT rule's, not RgbConv's; 10:10:10:2 is the U16
-// instance with dmax = 1023)
-template <int LAYOUT, int DT, int UP>
+// ---- the packed layouts: output_three_sinks' RGBA and 10:10:10:2 (RGBA in every dtype in one pass - the elements are the LUT rule's, not RgbConv's; 10:10:10:2
+// is the U16 instance with dmax = 1023)
+template <int SINK, int DT, int UP>
 __global__ __launch_bounds__(256) void k_output_packed_lut3d(const Lut3dOutArgs a)
 {
-    constexpr int SZ = OutT<DT>::size;
     extern __shared__ uint4 lut3d_lds[];
     lut3d_fill_lds(a, lut3d_lds);
-    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8;
-    const int i = blockIdx.y * 4 + threadIdx.y;
-    if (x0 >= a.w || i >= a.ch) return;
-    const int n = min(8, a.w - x0);               // pixels of this lane in the row (even)
-    const bool vec = a.aligned && n == 8;
-    const uint32_t alpha = LAYOUT == XGPU_PACKED_RGBA && OutT<DT>::is_float ? fbits<DT>(__uint_as_float(a.alpha)) : a.alpha;
-    three_channel_rows<UP, Lut3dConv<DT>>(a, x0, i, [&](int row, uint32_t (&ch)[3][8]) {
-        if (a.bgr) {
-            #pragma unroll
-            for (int m = 0; m < 8; m++) { const uint32_t t = ch[0][m]; ch[0][m] = ch[2][m]; ch[2][m] = t; }
-        }
-        if (LAYOUT == XGPU_PACKED_RGBA) {
-            uint32_t e[32];
-            #pragma unroll
-            for (int m = 0; m < 8; m++) { e[4 * m] = ch[0][m]; e[4 * m + 1] = ch[1][m]; e[4 * m + 2] = ch[2][m]; e[4 * m + 3] = alpha; }
-            store_run<32, SZ>(a.dst + (size_t)row * a.pitch + (size_t)x0 * 4 * SZ, e, vec, 4 * n);
-        } else {                                  // 10:10:10:2 - the channels are at most 1023, the alpha code at most 3
-            uint32_t e[8];
-            #pragma unroll
-            for (int m = 0; m < 8; m++) e[m] = ch[0][m] | (ch[1][m] << 10) | (ch[2][m] << 20) | (alpha << 30);
-            store_run<8, 4>(a.dst + (size_t)row * a.pitch + (size_t)x0 * 4, e, vec, n);
-        }
-    });
+    output_three_sinks<SINK, DT, UP, Lut3dConv<DT>>(a, a.alpha);
 }
 
-template <int LAYOUT, int DT>
-static void launch_packed_lut3d_up(const Lut3dOutArgs &a, int upsample, dim3 grid, hipStream_t s)
-{
-    if (upsample == XGPU_UPSAMPLE_NEAREST) hipLaunchKernelGGL((k_output_packed_lut3d<LAYOUT, DT, XGPU_UPSAMPLE_NEAREST>), grid, dim3(64, 4), lut3d_lds_bytes(a), s, a);
-    else                                   hipLaunchKernelGGL((k_output_packed_lut3d<LAYOUT, DT, XGPU_UPSAMPLE_LINEAR>), grid, dim3(64, 4), lut3d_lds_bytes(a), s, a);
-}
+struct PackedLut3dKernels {
+    template <int SINK, int DT, int UP> static void launch(const RgbOutArgs &a0, dim3 grid, hipStream_t s)
+    {
+        const Lut3dOutArgs &a = static_cast<const Lut3dOutArgs &>(a0);
+        hipLaunchKernelGGL((k_output_packed_lut3d<SINK, DT, UP>), grid, dim3(64, 4), lut3d_lds_bytes(a), s, a);
+    }
+};
+
 void launch_output_packed_lut3d(const Lut3dOutArgs &a, int layout, int dtype, int upsample, hipStream_t s)
 {
-    const dim3 grid((unsigned)(((a.w + 7) / 8 + 63) / 64), (unsigned)((a.ch + 3) / 4));
-    if (layout == XGPU_PACKED_RGB10A2) { launch_packed_lut3d_up<XGPU_PACKED_RGB10A2, XGPU_OUT_U16>(a, upsample, grid, s); return; }
-    switch (dtype) {
-    case XGPU_OUT_U8:   launch_packed_lut3d_up<XGPU_PACKED_RGBA, XGPU_OUT_U8>(a, upsample, grid, s); break;
-    case XGPU_OUT_U16:  launch_packed_lut3d_up<XGPU_PACKED_RGBA, XGPU_OUT_U16>(a, upsample, grid, s); break;
-    case XGPU_OUT_F16:  launch_packed_lut3d_up<XGPU_PACKED_RGBA, XGPU_OUT_F16>(a, upsample, grid, s); break;
-    case XGPU_OUT_BF16: launch_packed_lut3d_up<XGPU_PACKED_RGBA, XGPU_OUT_BF16>(a, upsample, grid, s); break;
-    default:            launch_packed_lut3d_up<XGPU_PACKED_RGBA, XGPU_OUT_F32>(a, upsample, grid, s); break;
-    }
+    launch_three_packed<PackedLut3dKernels>(a, layout == XGPU_PACKED_RGB10A2, dtype, upsample, s);
 }

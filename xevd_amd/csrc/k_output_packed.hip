@@ -2,9 +2,9 @@
 // RGBA in the five dtypes, or 10:10:10:2 - for a compositor or a swap chain, and packed 4:2:2 (YUYV / UYVY; 16-bit: Y210 and its kin) for capture cards, SDI
 // output and the encoders that take it.  The contract is INTEGRATION.md section 8p; tests/packed_ref.py restates it in numpy.
 //
-// k_output_packed_rgb: a new sink on three_channel_rows (output_common.h) - load, edge clamp, DRA and chroma upsampling are k_output_rgb's, the same code - with
-// RgbConv (the matrix) or, with a transform, cm_apply (cm_transform.h) as k_output_cm.hip arranges it: the tables at the front of dynamic LDS, copied by every
-// workgroup.  One lane makes 8 pixels of two luma rows; its run of a row is 32 contiguous bytes (RGBA u8, 10:10:10:2), 64 (the 16-bit dtypes) or 128 (f32),
+// k_output_packed_rgb: output_three_sinks (output_common.h) with the RGBA or the 10:10:10:2 sink - the lane, load, edge clamp, DRA, chroma upsampling and the
+// sinks are there, shared with the 3D LUT and the dither, and the first four are k_output_rgb's, the same code - with RgbConv (the matrix) or, with a transform,
+// CmConv (cm_transform.h) as k_output_cm.hip arranges it: the tables at the front of dynamic LDS, copied by every workgroup.  One lane makes 8 pixels of two luma rows; its run of a row is 32 contiguous bytes (RGBA u8, 10:10:10:2), 64 (the 16-bit dtypes) or 128 (f32),
 // written as 16-byte stores when destination and pitch are multiples of 16, element by element otherwise and in a row's last lane.  10:10:10:2 is the U16
 // instance with coef / shift / maxv of D = 10 in its arguments (with a transform: outmax = 1023) and the three codes and the alpha code or-ed into one word.
 // The integer matrix and the transform (FMA contraction off, as in k_output_cm.hip) are exact rules, so R, G, B are the bits k_output_rgb / k_output_cm write.
@@ -20,48 +20,14 @@
 #include "cm_transform.h"
 #include <type_traits>
 
-// the CONV of three_channel_rows with a transform: PackedRgbArgs is a CmOutArgs, and the tables lie at the front of dynamic LDS (k_output_cm.hip's arrangement)
-template <int DT> struct PackedCmConv {
-__device__ static __forceinline__ void apply(const RgbOutArgs &a0, int y, int cb, int cr, uint32_t &r, uint32_t &g, uint32_t &b)
-{
-    const CmOutArgs &a = static_cast<const CmOutArgs &>(a0);
-    extern __shared__ float cm_lds[];
-    cm_apply<DT>(a, a.cm, cm_lds_tables(a.cm, cm_lds), y, cb, cr, r, g, b);
-}
-};
-
-template <int LAYOUT, int DT, int UP, bool CM>
+template <int SINK, int DT, int UP, bool CM>
 __global__ __launch_bounds__(256) void k_output_packed_rgb(const PackedRgbArgs a)
 {
-    using CONV = std::conditional_t<CM, PackedCmConv<DT>, RgbConv<DT>>;
-    constexpr int SZ = OutT<DT>::size;
     if (CM) {
         extern __shared__ float cm_lds[];
         cm_fill_lds(a.cm, cm_lds);                // (every thread of the workgroup, before the lanes outside the picture leave)
     }
-    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8;
-    const int i = blockIdx.y * 4 + threadIdx.y;
-    if (x0 >= a.w || i >= a.ch) return;
-    const int n = min(8, a.w - x0);               // pixels of this lane in the row (even)
-    const bool vec = a.aligned && n == 8;
-    const uint32_t alpha = LAYOUT == XGPU_PACKED_RGBA && OutT<DT>::is_float ? fbits<DT>(__uint_as_float(a.alpha)) : a.alpha;
-    three_channel_rows<UP, CONV>(a, x0, i, [&](int row, uint32_t (&ch)[3][8]) {
-        if (a.bgr) {
-            #pragma unroll
-            for (int m = 0; m < 8; m++) { const uint32_t t = ch[0][m]; ch[0][m] = ch[2][m]; ch[2][m] = t; }
-        }
-        if (LAYOUT == XGPU_PACKED_RGBA) {
-            uint32_t e[32];
-            #pragma unroll
-            for (int m = 0; m < 8; m++) { e[4 * m] = ch[0][m]; e[4 * m + 1] = ch[1][m]; e[4 * m + 2] = ch[2][m]; e[4 * m + 3] = alpha; }
-            store_run<32, SZ>(a.dst + (size_t)row * a.pitch + (size_t)x0 * 4 * SZ, e, vec, 4 * n);
-        } else {                                  // 10:10:10:2 - the channels are clipped to 0 .. 1023, the alpha code to 0 .. 3
-            uint32_t e[8];
-            #pragma unroll
-            for (int m = 0; m < 8; m++) e[m] = ch[0][m] | (ch[1][m] << 10) | (ch[2][m] << 20) | (alpha << 30);
-            store_run<8, 4>(a.dst + (size_t)row * a.pitch + (size_t)x0 * 4, e, vec, n);
-        }
-    });
+    output_three_sinks<SINK, DT, UP, std::conditional_t<CM, CmConv<DT>, RgbConv<DT>>>(a, a.alpha);
 }
 
 // RGBA in a float dtype without a transform, second pass: the interleaved R'G'B' image k_output_rgb itself wrote to `mid` (rows mid_pitch bytes apart, a multiple
@@ -100,33 +66,18 @@ void launch_packed_rgba_from_rgb(const PackedRgbArgs &a, int dtype, const uint8_
 }
 
 // (no instance for a float dtype without a transform: the host side runs the two passes above instead)
-template <int LAYOUT, int DT, int UP>
-static void launch_packed_rgb_cm(const PackedRgbArgs &a, bool cm, dim3 grid, hipStream_t s)
-{
-    if (cm) {
-        const size_t lds = sizeof(float) * cm_table_floats(a.cm.n_lin, a.cm.tone != NULL, a.cm.enc != NULL);      // at most 32.8 KB
-        hipLaunchKernelGGL((k_output_packed_rgb<LAYOUT, DT, UP, true>), grid, dim3(64, 4), lds, s, a);
-    } else if constexpr (!OutT<DT>::is_float) {
-        hipLaunchKernelGGL((k_output_packed_rgb<LAYOUT, DT, UP, false>), grid, dim3(64, 4), 0, s, a);
+template <bool CM> struct PackedRgbKernels {
+    template <int SINK, int DT, int UP> static void launch(const RgbOutArgs &a0, dim3 grid, hipStream_t s)
+    {
+        const PackedRgbArgs &a = static_cast<const PackedRgbArgs &>(a0);      // launch_three_packed hands the reference through
+        if constexpr (CM || !OutT<DT>::is_float)
+            hipLaunchKernelGGL((k_output_packed_rgb<SINK, DT, UP, CM>), grid, dim3(64, 4), CM ? cm_lds_bytes(a.cm) : 0, s, a);
     }
-}
-template <int LAYOUT, int DT>
-static void launch_packed_rgb_up(const PackedRgbArgs &a, int upsample, bool cm, dim3 grid, hipStream_t s)
-{
-    if (upsample == XGPU_UPSAMPLE_NEAREST) launch_packed_rgb_cm<LAYOUT, DT, XGPU_UPSAMPLE_NEAREST>(a, cm, grid, s);
-    else                                   launch_packed_rgb_cm<LAYOUT, DT, XGPU_UPSAMPLE_LINEAR>(a, cm, grid, s);
-}
+};
 void launch_output_packed_rgb(const PackedRgbArgs &a, int layout, int dtype, int upsample, bool cm, hipStream_t s)
 {
-    const dim3 grid((unsigned)(((a.w + 7) / 8 + 63) / 64), (unsigned)((a.ch + 3) / 4));
-    if (layout == XGPU_PACKED_RGB10A2) { launch_packed_rgb_up<XGPU_PACKED_RGB10A2, XGPU_OUT_U16>(a, upsample, cm, grid, s); return; }
-    switch (dtype) {
-    case XGPU_OUT_U8:   launch_packed_rgb_up<XGPU_PACKED_RGBA, XGPU_OUT_U8>(a, upsample, cm, grid, s); break;
-    case XGPU_OUT_U16:  launch_packed_rgb_up<XGPU_PACKED_RGBA, XGPU_OUT_U16>(a, upsample, cm, grid, s); break;
-    case XGPU_OUT_F16:  launch_packed_rgb_up<XGPU_PACKED_RGBA, XGPU_OUT_F16>(a, upsample, cm, grid, s); break;
-    case XGPU_OUT_BF16: launch_packed_rgb_up<XGPU_PACKED_RGBA, XGPU_OUT_BF16>(a, upsample, cm, grid, s); break;
-    default:            launch_packed_rgb_up<XGPU_PACKED_RGBA, XGPU_OUT_F32>(a, upsample, cm, grid, s); break;
-    }
+    if (cm) launch_three_packed<PackedRgbKernels<true>>(a, layout == XGPU_PACKED_RGB10A2, dtype, upsample, s);
+    else    launch_three_packed<PackedRgbKernels<false>>(a, layout == XGPU_PACKED_RGB10A2, dtype, upsample, s);
 }
 
 // one sample as the bits of its output element: k_output_semiplanar's - xgpu_pic_output's conversion, the P016 shift, cut to 16 bits
@@ -195,7 +146,7 @@ static void launch_packed_422_up(const Packed422Args &a, int upsample, dim3 grid
 }
 void launch_output_packed_422(const Packed422Args &a, int dtype, bool uyvy, int upsample, hipStream_t s)
 {
-    const dim3 grid((unsigned)(((a.w + 7) / 8 + 63) / 64), (unsigned)((a.ch + 3) / 4));
+    const dim3 grid = three_channel_grid(a);
     if (dtype == XGPU_OUT_U8) { if (uyvy) launch_packed_422_up<XGPU_OUT_U8, true>(a, upsample, grid, s); else launch_packed_422_up<XGPU_OUT_U8, false>(a, upsample, grid, s); }
     else                      { if (uyvy) launch_packed_422_up<XGPU_OUT_U16, true>(a, upsample, grid, s); else launch_packed_422_up<XGPU_OUT_U16, false>(a, upsample, grid, s); }
 }

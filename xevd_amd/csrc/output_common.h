@@ -1,7 +1,9 @@
 // output_common.h - what the output kernels share (k_output.hip, k_output_rgb.hip, k_output_yuv.hip; k_stats.hip's light pass): the per-sample depth conversion and DRA
 // mapping, the edge-clamped chroma loads and the 4:2:0 -> luma-resolution upsampling of the device-output contract (INTEGRATION.md section 8a,
 // step 2), the element types and the vector / element stores.  One version of each: a layout that is "the same samples, another place" runs
-// the same code.  Further down: the lanes' work of the scaled outputs' two passes (the kernel bodies built on it are output_resize.h's) and the gather of the
+// the same code.  The kernels that write three channels at luma resolution share their bodies here too: output_three_channels (k_output_rgb, k_output_yuv444,
+// k_output_cm, k_output_lut3d), output_three_sinks with its four sinks (the packed surfaces, the 3D LUT on them, the dither) and the launch of either; so do NV12 /
+// P016 and their dithered form (output_semiplanar).  Further down: the lanes' work of the scaled outputs' two passes (the kernel bodies built on it are output_resize.h's) and the gather of the
 // warped and the remapped output.
 #pragma once
 #include "xgpu_internal.h"
@@ -222,32 +224,170 @@ __device__ __forceinline__ void output_three_channels(const RgbOutArgs &a)
     });
 }
 
-// The launch of a kernel family built on output_three_channels: 64 lanes x 4 chroma rows per workgroup, the instance picked by layout, dtype and
-// upsampling mode.  K::launch<PLANAR, DT, UP>(a, grid, stream) launches the family's kernel of that instance.
-template <class K, bool PLANAR, int DT>
-static void launch_three_dt(const RgbOutArgs &a, int upsample, dim3 grid, hipStream_t s)
+// The same body with the sink a template argument, for the kernels that are exact by rule (integer arithmetic, or float with contraction off): the packed display
+// surfaces (k_output_packed_rgb), the 3D LUT on them (k_output_packed_lut3d) and the dithered outputs (k_output_dither_rgb).  One lane of 64 x 4 makes the
+// pixels of three_channel_rows; finish(row, x0, ch) may rework a row's elements (the dither's rank step); then the bgr swap and the store of the row's 3 x 8
+// elements from pixel x0 - `vec`: vector stores, else the first n pixels element by element.  alpha: the argument struct's A element - for RGBA in a float dtype
+// the float32 bits of alpha, rounded to the dtype here; for 10:10:10:2 the 2-bit code (the channels are at most 1023 there).
+// The sinks stand in the lambda itself, not in a function of their own that it calls: through such a function - __forceinline__, same text - the dithered
+// instances took up to 12 more VGPRs and four of them lost a wave per SIMD, while this form compiles to the code of the three copies it replaces.
+// The planar and the interleaved sink are output_three_channels' lambda a second time, on purpose.  That body cannot become an instance of this one: with either
+// placement of the bgr swap the compiler allocates k_output_rgb's registers differently, and that kernel alone runs RgbConv's float matrix with FMA contraction left
+// to the compiler, so its f16 / bf16 roundings are its code generation's.  The pull request that writes RgbConv with explicit __fmaf_rn /
+// __fmul_rn lifts this: then output_three_channels is output_three_sinks<PLANAR ? OUT_SINK_PLANAR : OUT_SINK_INTERLEAVED, ...>.
+struct NoFinish { __device__ __forceinline__ void operator()(int, int, uint32_t (&)[3][8]) const {} };
+template <int SINK, int DT, int UP, class CONV, class FINISH = NoFinish>
+__device__ __forceinline__ void output_three_sinks(const RgbOutArgs &a, uint32_t alpha_bits, FINISH &&finish = FINISH())
 {
-    if (upsample == XGPU_UPSAMPLE_NEAREST) K::template launch<PLANAR, DT, XGPU_UPSAMPLE_NEAREST>(a, grid, s);
-    else                                   K::template launch<PLANAR, DT, XGPU_UPSAMPLE_LINEAR>(a, grid, s);
+    constexpr int SZ = OutT<DT>::size;
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8;
+    const int i = blockIdx.y * 4 + threadIdx.y;
+    if (x0 >= a.w || i >= a.ch) return;
+    const int n = min(8, a.w - x0);               // pixels of this lane in the row (even)
+    const bool vec = a.aligned && n == 8;
+    const uint32_t alpha = SINK == OUT_SINK_RGBA && OutT<DT>::is_float ? fbits<DT>(__uint_as_float(alpha_bits)) : alpha_bits;
+    three_channel_rows<UP, CONV>(a, x0, i, [&](int row, uint32_t (&ch)[3][8]) {
+        finish(row, x0, ch);
+        if (a.bgr) {
+            #pragma unroll
+            for (int m = 0; m < 8; m++) { const uint32_t t = ch[0][m]; ch[0][m] = ch[2][m]; ch[2][m] = t; }
+        }
+        if (SINK == OUT_SINK_PLANAR) {
+            uint8_t *d = a.dst + (size_t)row * a.pitch + (size_t)x0 * SZ;
+            #pragma unroll
+            for (int c = 0; c < 3; c++) store_run<8, SZ>(d + c * a.plane, ch[c], vec, n);
+        } else if (SINK == OUT_SINK_INTERLEAVED) {
+            uint32_t e[24];
+            #pragma unroll
+            for (int m = 0; m < 8; m++) { e[3 * m] = ch[0][m]; e[3 * m + 1] = ch[1][m]; e[3 * m + 2] = ch[2][m]; }
+            store_run<24, SZ>(a.dst + (size_t)row * a.pitch + (size_t)x0 * 3 * SZ, e, vec, 3 * n);
+        } else if (SINK == OUT_SINK_RGBA) {
+            uint32_t e[32];
+            #pragma unroll
+            for (int m = 0; m < 8; m++) { e[4 * m] = ch[0][m]; e[4 * m + 1] = ch[1][m]; e[4 * m + 2] = ch[2][m]; e[4 * m + 3] = alpha; }
+            store_run<32, SZ>(a.dst + (size_t)row * a.pitch + (size_t)x0 * 4 * SZ, e, vec, 4 * n);
+        } else {
+            uint32_t e[8];
+            #pragma unroll
+            for (int m = 0; m < 8; m++) e[m] = ch[0][m] | (ch[1][m] << 10) | (ch[2][m] << 20) | (alpha << 30);
+            store_run<8, 4>(a.dst + (size_t)row * a.pitch + (size_t)x0 * 4, e, vec, n);
+        }
+    });
 }
-template <class K, bool PLANAR>
-static void launch_three_layout(const RgbOutArgs &a, int dtype, int upsample, dim3 grid, hipStream_t s)
+
+// The launch of a kernel family built on output_three_channels or output_three_sinks: 64 lanes x 4 chroma rows per workgroup, the instance picked by layout or
+// sink, dtype and upsampling mode.  K::launch<L, DT, UP>(a, grid, stream) launches the family's kernel of that instance; L is the family's own first argument,
+// PLANAR (launch_three_channels) or an OUT_SINK_* (launch_three_packed, k_output_dither.hip).  A family that has no kernel for an instance (a float dtype of the
+// packed surfaces without a transform, of the dither) leaves its launch<> empty there.
+static dim3 three_channel_grid(const RgbOutArgs &a) { return dim3((unsigned)(((a.w + 7) / 8 + 63) / 64), (unsigned)((a.ch + 3) / 4)); }
+template <class K, auto L, int DT>
+static void launch_three_dt(const RgbOutArgs &a, int upsample, hipStream_t s)
+{
+    if (upsample == XGPU_UPSAMPLE_NEAREST) K::template launch<L, DT, XGPU_UPSAMPLE_NEAREST>(a, three_channel_grid(a), s);
+    else                                   K::template launch<L, DT, XGPU_UPSAMPLE_LINEAR>(a, three_channel_grid(a), s);
+}
+template <class K, auto L>
+static void launch_three_layout(const RgbOutArgs &a, int dtype, int upsample, hipStream_t s)
 {
     switch (dtype) {
-    case XGPU_OUT_U8:   launch_three_dt<K, PLANAR, XGPU_OUT_U8>(a, upsample, grid, s); break;
-    case XGPU_OUT_U16:  launch_three_dt<K, PLANAR, XGPU_OUT_U16>(a, upsample, grid, s); break;
-    case XGPU_OUT_F16:  launch_three_dt<K, PLANAR, XGPU_OUT_F16>(a, upsample, grid, s); break;
-    case XGPU_OUT_BF16: launch_three_dt<K, PLANAR, XGPU_OUT_BF16>(a, upsample, grid, s); break;
-    default:            launch_three_dt<K, PLANAR, XGPU_OUT_F32>(a, upsample, grid, s); break;
+    case XGPU_OUT_U8:   launch_three_dt<K, L, XGPU_OUT_U8>(a, upsample, s); break;
+    case XGPU_OUT_U16:  launch_three_dt<K, L, XGPU_OUT_U16>(a, upsample, s); break;
+    case XGPU_OUT_F16:  launch_three_dt<K, L, XGPU_OUT_F16>(a, upsample, s); break;
+    case XGPU_OUT_BF16: launch_three_dt<K, L, XGPU_OUT_BF16>(a, upsample, s); break;
+    default:            launch_three_dt<K, L, XGPU_OUT_F32>(a, upsample, s); break;
     }
 }
 template <class K>
 static void launch_three_channels(const RgbOutArgs &a, bool planar, int dtype, int upsample, hipStream_t s)
 {
-    const dim3 grid((unsigned)(((a.w + 7) / 8 + 63) / 64), (unsigned)((a.ch + 3) / 4));
-    if (planar) launch_three_layout<K, true>(a, dtype, upsample, grid, s);
-    else        launch_three_layout<K, false>(a, dtype, upsample, grid, s);
+    if (planar) launch_three_layout<K, true>(a, dtype, upsample, s);
+    else        launch_three_layout<K, false>(a, dtype, upsample, s);
 }
+// the packed sinks: RGBA in the five dtypes; 10:10:10:2 is the U16 instance, whatever `dtype` says
+template <class K>
+static void launch_three_packed(const RgbOutArgs &a, bool rgb10a2, int dtype, int upsample, hipStream_t s)
+{
+    if (rgb10a2) launch_three_dt<K, OUT_SINK_RGB10A2, XGPU_OUT_U16>(a, upsample, s);
+    else         launch_three_layout<K, OUT_SINK_RGBA>(a, dtype, upsample, s);
+}
+
+// ---- NV12 / P016 (k_output_semiplanar) and their dithered form (k_output_dither_semiplanar)
+// the matrix of a dithered call: the address of the rank of column x0 of row y (cropped destination coordinates, or chroma-plane coordinates) - DitherSlot's rows
+// are extended by their own first 16 entries, so the 8 or 16 ranks from there are contiguous at 2-byte alignment
+struct __attribute__((packed, aligned(2))) U16x8u { uint16_t v[8]; };
+__device__ __forceinline__ const U16x8u *dither_ranks(const DitherArgs &d, int x0, int y)
+{
+    return (const U16x8u *)(d.tab + (size_t)((y + d.py) & d.mhm) * d.stride + ((x0 + d.px) & d.mwm));
+}
+// conv1 with the rounding constant replaced by (r << shift) >> k; with shift <= 0 nothing is added and the sample is conv1's
+__device__ __forceinline__ int dither_conv1(int v, int shift, int maxv, int out8, int r, int k)
+{
+    if (shift <= 0) return conv1(v, shift, maxv, out8);
+    const int add = (r << shift) >> k;
+    if (out8) return min(max((v + add) >> shift, 0), 255);
+    return min(((int)(uint16_t)v + add) >> shift, maxv);
+}
+// one sample as the bits of its output element: xgpu_pic_output's conversion (DITHER: with rank r in its rounding), the P016 shift, cut to the 16 bits k_output
+// stores (a DRA-mapped sample copied at its own depth may lie outside 0 .. 2^D - 1)
+template <bool DITHER, class A> __device__ __forceinline__ uint32_t semi_elem(const A &a, int v, int r)
+{
+    int e;
+    if constexpr (DITHER) e = dither_conv1(v, a.shift, a.maxv, a.out8, r, a.di.k);
+    else                  e = conv1(v, a.shift, a.maxv, a.out8);
+    return (uint32_t)(uint16_t)(e << a.lsh);
+}
+// One lane of 64 x 4: 16 luma columns of the two luma rows that share chroma row i, and the 8 Cb and 8 Cr samples below them (k_output_yuv.hip has the account of
+// the loads and stores).  A: SemiPlanarArgs, or with DITHER DitherSemiArgs - the ranks are loaded only there.  A chroma sample's rank is that of its chroma-plane
+// position; Cb and Cr share it.
+template <int DT, bool DITHER, class A>
+__device__ __forceinline__ void output_semiplanar(const A &a)
+{
+    constexpr int SZ = OutT<DT>::size;
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 16;
+    const int i = blockIdx.y * 4 + threadIdx.y;
+    if (x0 >= a.w || i >= a.ch) return;
+    const int n = min(16, a.w - x0);              // luma columns of this lane (even) = elements of its run of the interleaved chroma row
+    const bool vec = a.aligned && n == 16;
+
+    S16x8u ly[2][2];
+    #pragma unroll
+    for (int par = 0; par < 2; par++) {
+        const int16_t *l = a.y + (size_t)(2 * i + par) * a.sy + x0;
+        ly[par][0] = *(const S16x8u *)l;
+        ly[par][1] = *(const S16x8u *)(l + 8);
+    }
+    const S16x8u cb = *(const S16x8u *)(a.u + (size_t)i * a.sc + (x0 >> 1));
+    const S16x8u cr = *(const S16x8u *)(a.v + (size_t)i * a.sc + (x0 >> 1));
+
+    uint32_t e[16];
+    U16x8u rk[2] = {};
+    if constexpr (DITHER) rk[0] = *dither_ranks(a.di, x0 >> 1, i);
+    #pragma unroll
+    for (int k = 0; k < 8; k++) {
+        int b = cb.v[k], r = cr.v[k];
+        if (a.dra) {                              // the factor of chroma column j comes from the unmapped luma sample (2i, 2j)
+            const int luma = ly[0][k >> 2].v[(2 * k) & 7];
+            b = dra1(a.dra, 1, b, luma);
+            r = dra1(a.dra, 2, r, luma);
+        }
+        e[2 * k]     = semi_elem<DITHER>(a, b, rk[0].v[k]);
+        e[2 * k + 1] = semi_elem<DITHER>(a, r, rk[0].v[k]);
+    }
+    store_run<16, SZ>(a.dst + a.chroma_off + (size_t)i * a.pitch + (size_t)x0 * SZ, e, vec, n);
+
+    #pragma unroll
+    for (int par = 0; par < 2; par++) {
+        if constexpr (DITHER) { const U16x8u *t = dither_ranks(a.di, x0, 2 * i + par); rk[0] = t[0]; rk[1] = t[1]; }
+        #pragma unroll
+        for (int m = 0; m < 16; m++) {
+            int y = ly[par][m >> 3].v[m & 7];
+            if (a.dra) y = dra1(a.dra, 0, y, 0);
+            e[m] = semi_elem<DITHER>(a, y, rk[m >> 3].v[m & 7]);
+        }
+        store_run<16, SZ>(a.dst + (size_t)(2 * i + par) * a.pitch + (size_t)x0 * SZ, e, vec, n);
+    }
+}
+static dim3 semiplanar_grid(int w, int ch) { return dim3((unsigned)(((w + 15) / 16 + 63) / 64), (unsigned)((ch + 3) / 4)); }
 
 // The lanes' work in the two passes of the scaled outputs (k_output_scaled.hip: one picture; k_output_rois.hip: a batch of rectangles; k_output_resampled.hip:
 // either with cubic taps; k_output_ladder.hip: video surfaces); output_resize.h builds the kernels' bodies on it.  The files that use them switch float contraction

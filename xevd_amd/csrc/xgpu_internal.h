@@ -506,6 +506,9 @@ struct RgbOutArgs {
     int      ve[2], vo[2];          // LINEAR: vertical quarter weights of rows (i-1, i) for even luma rows, of (i, i+1) for odd ones
     const int32_t *dra;             // [3][1024] DRA inverse tables, or NULL
 };
+// where a row's 3 x 8 elements go (output_common.h, output_three_sinks): three planes, the three elements of a pixel side by side, with the A element behind
+// them, or one 10:10:10:2 word per pixel
+enum { OUT_SINK_PLANAR, OUT_SINK_INTERLEAVED, OUT_SINK_RGBA, OUT_SINK_RGB10A2 };
 void launch_output_rgb(const RgbOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 void launch_output_yuv444(const RgbOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 // k_output_cm.hip: k_output_rgb's arguments (coef / shift / maxv: those of the U16 form, whatever the dtype) and the colour transform's
@@ -517,8 +520,6 @@ struct CmParams {
     float    outmax;                // integer dtypes: 2^D - 1
 };
 struct CmOutArgs : RgbOutArgs { CmParams cm; };
-// the floats of a transform's tables in LDS (cm_fill_lds's layout, cm_transform.h)
-static inline size_t cm_table_floats(int n_lin, bool tone, bool enc) { return (size_t)n_lin + (tone ? XGPU_CM_CURVE_SIZE : 0) + (enc ? XGPU_CM_CURVE_SIZE : 0); }
 void launch_output_cm(const CmOutArgs &a, int layout, int dtype, int upsample, hipStream_t s);
 // k_output_scaled.hip: the cropped picture resized to dw x dh and converted (xgpu_pic_output_device_scaled).  RgbOutArgs' source, destination
 // and conversion fields (w, h, cw, ch: the SOURCE size; pitch / plane: of the dw x dh destination; aligned, hc, ve, vo are not read), then the taps and the two passes'.
@@ -709,7 +710,6 @@ struct DitherArgs {
 // the three-channel family: PackedRgbArgs (k_output_packed_rgb's, `plane` read by the planar sink) with, for the matrix path, coef / shift / maxv of the store's
 // depth D and, with a transform, cm.outmax = 2^D - 1
 struct DitherRgbArgs : PackedRgbArgs { DitherArgs di; };
-enum { DITHER_SINK_PLANAR, DITHER_SINK_INTERLEAVED, DITHER_SINK_RGBA, DITHER_SINK_RGB10A2 };
 void launch_output_dither_rgb(const DitherRgbArgs &a, int sink, int dtype, int upsample, bool cm, hipStream_t s);
 struct DitherSemiArgs : SemiPlanarArgs { DitherArgs di; };
 void launch_output_dither_semiplanar(const DitherSemiArgs &a, int dtype, hipStream_t s);

@@ -229,31 +229,36 @@ int xgpu_output_coeffs(const xgpu_output_format *f, int bit_depth, int32_t coef[
     matrix_coeffs(f->matrix, f->full_range, bit_depth, f->dtype == XGPU_OUT_U8 ? 8 : f->dtype == XGPU_OUT_U16 ? bit_depth : 0, coef, shift, fcoef);
     return XGPU_OK;
 }
-static size_t format_size(const xgpu_output_format *f, int width, int height, int bd, const char **why)
+// 0 with *rc = the code and `why`, or the bytes the destination needs.  At a valid depth the format's own refusal comes first: a matrix that is not supported is
+// XGPU_ERR_UNSUPPORTED whatever the picture's size.
+static size_t format_size(const xgpu_output_format *f, int width, int height, int bd, int *rc, const char **why)
 {
+    *rc = XGPU_ERR_INVALID_ARGUMENT;
     *why = "picture size or bit depth out of range";
-    if (width <= 0 || height <= 0 || ((width | height) & 1) || bd < 8 || bd > 12) return 0;
-    if (check_format(f, bd, why) < 0) return 0;
+    if (bd < 8 || bd > 12) return 0;
+    const char *fwhy;
+    const int frc = check_format(f, bd, &fwhy);
+    if (frc == XGPU_ERR_UNSUPPORTED) *rc = frc;
+    if (width <= 0 || height <= 0 || ((width | height) & 1)) return 0;
+    if (frc < 0) { *why = fwhy; return 0; }
     if (!crop_ok(f->crop, width, height, why)) return 0;
     const size_t w = width - f->crop[0] - f->crop[1], h = height - f->crop[2] - f->crop[3];
-    if (f->layout == XGPU_OUT_YUV420P) return (w * h + 2 * (w >> 1) * (h >> 1)) * elem_size(f->dtype);      // xgpu_pic_output_size
     *why = "row_pitch is shorter than a row";
-    if (is_semiplanar(f->layout)) return rows_of(w * elem_size(f->dtype), h + h / 2, f->row_pitch).total;
-    return rows_of(image_row(f, w), image_rows(f, h), f->row_pitch).total;
+    const size_t total = f->layout == XGPU_OUT_YUV420P ? (w * h + 2 * (w >> 1) * (h >> 1)) * elem_size(f->dtype) :      // xgpu_pic_output_size
+                         is_semiplanar(f->layout) ? rows_of(w * elem_size(f->dtype), h + h / 2, f->row_pitch).total :
+                                                    rows_of(image_row(f, w), image_rows(f, h), f->row_pitch).total;
+    if (total) *rc = XGPU_OK;
+    return total;
 }
 size_t xgpu_output_format_size(const xgpu_output_format *f, int width, int height, int bit_depth)
 {
-    const char *why;
-    return format_size(f, width, height, bit_depth, &why);
-}
-static size_t device_size(const xgpu_ctx *c, const xgpu_output_format *f, const char **why)
-{
-    return format_size(f, c->sp.width, c->sp.height, c->sp.bit_depth_luma, why);
+    int rc; const char *why;
+    return format_size(f, width, height, bit_depth, &rc, &why);
 }
 size_t xgpu_pic_output_device_size(const xgpu_ctx *c, const xgpu_output_format *f)
 {
-    const char *why;
-    return c ? device_size(c, f, &why) : 0;
+    int rc; const char *why;
+    return c ? format_size(f, c->sp.width, c->sp.height, c->sp.bit_depth_luma, &rc, &why) : 0;
 }
 // the colour transform's tables on the device: the host copy is kept with the (cm, depth) it was made for, and made and uploaded again - on `s`, the stream the
 // kernel runs on, which is behind every earlier reader of d_cm - only when they differ.  (cm_tab, cm_key, cm_bd) name what d_cm holds: they are set only once
@@ -290,6 +295,13 @@ static int cm_prepare(xgpu_ctx *c, const char *who, const xgpu_output_format *f,
     }
     if (!c->d_cm && hipMalloc((void **)&c->d_cm, sizeof(float) * CM_FLOATS) != hipSuccess) { snprintf(c->err, sizeof(c->err), "%s: cannot allocate the tables", who); return XGPU_ERR_OUT_OF_MEMORY; }
     return XGPU_OK;
+}
+// what a _check entry ends in: the layout, then whether the transform's tables would build (cm_prepare's order), without a device
+static int cm_dry_run(const xgpu_output_format *f, const xgpu_colour_transform *cm, int bit_depth)
+{
+    if (!is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+    std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
+    return t ? xgpu_colour_tables(f, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
 }
 // cm_commit, behind the fork - after every kernel that read the previous tables: a new set is uploaded on `s` and named by the key
 static int cm_commit(xgpu_ctx *c, const xgpu_colour_transform *cm, std::unique_ptr<xgpu_colour_tables_t> &cm_new, hipStream_t s)
@@ -341,6 +353,31 @@ static void fill_siting(int chroma_loc, RgbOutArgs &a)
     a.ve[0] = ve[chroma_loc >> 1][0]; a.ve[1] = ve[chroma_loc >> 1][1];
     a.vo[0] = vo[chroma_loc >> 1][0]; a.vo[1] = vo[chroma_loc >> 1][1];
 }
+// the source of the cropped picture `pic`, its size and where it goes; the destination's rows are the caller's to fill
+static void fill_source(xgpu_ctx *c, int pic, const int crop[4], void *d_dst, RgbOutArgs &a)
+{
+    const DevPic &p = dpic(c, pic);
+    cropped_planes(p, crop, &a.y, &a.u, &a.v);
+    a.sy = p.s_l; a.sc = p.s_c;
+    a.w = c->sp.width - crop[0] - crop[1]; a.h = c->sp.height - crop[2] - crop[3];
+    a.cw = a.w >> 1; a.ch = a.h >> 1;
+    a.dst = (uint8_t *)d_dst;
+}
+// all of an NV12 / P016 call's arguments: source, rows and launch_output's conversion at depth D
+static void fill_semiplanar(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, void *d_dst, SemiPlanarArgs &a)
+{
+    const DevPic &p = dpic(c, pic);
+    const int bd = c->sp.bit_depth_luma, obd = sample_depth(f, bd);
+    const int w = c->sp.width - f->crop[0] - f->crop[1], h = c->sp.height - f->crop[2] - f->crop[3];
+    cropped_planes(p, f->crop, &a.y, &a.u, &a.v);
+    a.sy = p.s_l; a.sc = p.s_c;
+    a.w = w; a.ch = h >> 1;
+    a.dst = (uint8_t *)d_dst;
+    fill_rows(a, d_dst, (size_t)w * elem_size(f->dtype), h, f->row_pitch, &SemiPlanarArgs::chroma_off);
+    a.shift = bd - obd; a.out8 = obd == 8; a.maxv = (1 << obd) - 1;
+    a.lsh = f->layout == XGPU_OUT_P016 ? 16 - obd : 0;
+    a.dra = dra ? c->d_dra : NULL;
+}
 static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm, void *d_dst, size_t dst_size, void *stream);
 int xgpu_pic_output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, void *d_dst, size_t dst_size, void *stream)
 {
@@ -354,10 +391,11 @@ static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const x
 {
     ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
     const char *why = "";
-    const size_t need = device_size(c, f, &why);
+    int rc;
+    const size_t need = format_size(f, c->sp.width, c->sp.height, c->sp.bit_depth_luma, &rc, &why);
     if (need == 0) {
         snprintf(c->err, sizeof(c->err), "pic_output_device: invalid format: %s", why);
-        return f && is_rgb(f->layout) && check_format(f, c->sp.bit_depth_luma, &why) == XGPU_ERR_UNSUPPORTED ? XGPU_ERR_UNSUPPORTED : XGPU_ERR_INVALID_ARGUMENT;
+        return rc;
     }
     const size_t es = f->layout == XGPU_OUT_YUV420P ? 1 : (size_t)elem_size(f->dtype);
     TRY(check_dst(c, "pic_output_device", d_dst, dst_size, need, es));
@@ -368,33 +406,18 @@ static int output_device(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const x
     TRY(out_fork(c, stream, &s));
     TRY(cm_commit(c, cm, cm_new, s));
     const int *cr = f->crop;
-    const DevPic &p = dpic(c, pic);
-    const int bd = c->sp.bit_depth_luma;
-    const int w = c->sp.width - cr[0] - cr[1], h = c->sp.height - cr[2] - cr[3];
     if (f->layout == XGPU_OUT_YUV420P) {
-        launch_output(c, p, dra ? c->d_dra : NULL, sample_depth(f, bd), cr[0], cr[1], cr[2], cr[3], (uint8_t *)d_dst, false, s);
+        launch_output(c, dpic(c, pic), dra ? c->d_dra : NULL, sample_depth(f, c->sp.bit_depth_luma), cr[0], cr[1], cr[2], cr[3], (uint8_t *)d_dst, false, s);
     } else if (is_semiplanar(f->layout)) {
         SemiPlanarArgs a;
         memset(&a, 0, sizeof(a));
-        const int obd = sample_depth(f, bd);
-        cropped_planes(p, cr, &a.y, &a.u, &a.v);
-        a.sy = p.s_l; a.sc = p.s_c;
-        a.w = w; a.ch = h >> 1;
-        a.dst = (uint8_t *)d_dst;
-        fill_rows(a, d_dst, (size_t)w * es, h, f->row_pitch, &SemiPlanarArgs::chroma_off);
-        a.shift = bd - obd; a.out8 = obd == 8; a.maxv = (1 << obd) - 1;      // launch_output's conversion
-        a.lsh = f->layout == XGPU_OUT_P016 ? 16 - obd : 0;
-        a.dra = dra ? c->d_dra : NULL;
+        fill_semiplanar(c, pic, dra, f, d_dst, a);
         launch_output_semiplanar(a, f->dtype, s);
     } else {
         RgbOutArgs a;
         memset(&a, 0, sizeof(a));
-        cropped_planes(p, cr, &a.y, &a.u, &a.v);
-        a.sy = p.s_l; a.sc = p.s_c;
-        a.w = w; a.h = h;
-        a.cw = a.w >> 1; a.ch = a.h >> 1;
-        a.dst = (uint8_t *)d_dst;
-        fill_rows(a, d_dst, image_row(f, w), h, f->row_pitch);
+        fill_source(c, pic, cr, d_dst, a);
+        fill_rows(a, d_dst, image_row(f, a.w), a.h, f->row_pitch);
         fill_conversion(c, dra, f, a);
         fill_siting(f->chroma_loc, a);
         if (cm) {
@@ -494,8 +517,7 @@ int xgpu_output_packed_check(const xgpu_packed_format *f, const xgpu_colour_tran
     if (rc < 0 || !cm) return rc;
     if (!is_packed_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
     const xgpu_output_format rf = packed_rgb_format(f);
-    std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
-    return t ? xgpu_colour_tables(&rf, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
+    return cm_dry_run(&rf, cm, bit_depth);
 }
 // The A element.  RGBA: floor(alpha * (2^D - 1) + 0.5) in double for the integer dtypes (D = 8 for U8, else the coding depth), the float32 bits of alpha for the
 // float dtypes (the kernel rounds them to the dtype); RGB10A2: floor(alpha * 3 + 0.5)
@@ -524,6 +546,21 @@ int xgpu_output_packed_coeffs(const xgpu_packed_format *f, int bit_depth, int32_
     matrix_coeffs(f->matrix, f->full_range, bit_depth, d, coef, shift, fcoef);
     *alpha_code = packed_alpha_code(f, bit_depth);
     return XGPU_OK;
+}
+// the conversion of the packed RGB layouts (rf: packed_rgb_format's): range terms, DRA, the A element and the matrix - with a transform (the context's tables,
+// committed) the U16 form's and the transform, else that of the store's depth; 10:10:10:2 stores D = 10 whatever the coding depth
+static void fill_packed_rgb(xgpu_ctx *c, const xgpu_dra_luts *dra, const xgpu_packed_format *f, const xgpu_output_format *rf, bool cm, PackedRgbArgs &a)
+{
+    const int bd = c->sp.bit_depth_luma;
+    fill_conversion(c, dra, rf, a);
+    a.alpha = packed_alpha_code(f, bd);
+    if (cm) {
+        fill_cm(c, rf, *c->cm_tab, a, a.cm);
+        if (f->layout == XGPU_PACKED_RGB10A2) a.cm.outmax = 1023.f;
+    } else if (f->layout == XGPU_PACKED_RGB10A2) {
+        matrix_coeffs(f->matrix, f->full_range, bd, 10, a.coef, &a.shift, a.fcoef);
+        a.maxv = 1023;
+    }
 }
 int xgpu_pic_output_device_packed(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f, const xgpu_colour_transform *cm, void *d_dst,
                                   size_t dst_size, void *stream)
@@ -555,13 +592,8 @@ int xgpu_pic_output_device_packed(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra
     hipStream_t s;
     TRY(out_fork(c, stream, &s));
     TRY(cm_commit(c, cm, cm_new, s));
-    const DevPic &p = dpic(c, pic);
     auto source_and_rows = [&](RgbOutArgs &a) {
-        cropped_planes(p, f->crop, &a.y, &a.u, &a.v);
-        a.sy = p.s_l; a.sc = p.s_c;
-        a.w = w; a.h = h;
-        a.cw = w >> 1; a.ch = h >> 1;
-        a.dst = (uint8_t *)d_dst;
+        fill_source(c, pic, f->crop, d_dst, a);
         fill_rows(a, d_dst, packed_row(f, w), h, f->row_pitch);
         fill_siting(f->chroma_loc, a);
     };
@@ -578,22 +610,16 @@ int xgpu_pic_output_device_packed(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra
         PackedRgbArgs a;
         memset(&a, 0, sizeof(a));
         source_and_rows(a);
-        fill_conversion(c, dra, &rf, a);
-        a.alpha = packed_alpha_code(f, bd);
+        fill_packed_rgb(c, dra, f, &rf, cm != NULL, a);
         if (two_pass) {
             RgbOutArgs r = a;      // the source, the conversion and the siting; the destination is the intermediate
             r.dst = (uint8_t *)c->sc_mid;
             fill_rows(r, r.dst, image_row(&rf, w), h, mid_pitch);
             launch_output_rgb(r, XGPU_OUT_RGB_INTERLEAVED, f->dtype, f->upsample, s);
             launch_packed_rgba_from_rgb(a, f->dtype, r.dst, mid_pitch, s);
-        } else if (cm) {
-            fill_cm(c, &rf, *c->cm_tab, a, a.cm);
-            if (f->layout == XGPU_PACKED_RGB10A2) a.cm.outmax = 1023.f;
-        } else if (f->layout == XGPU_PACKED_RGB10A2) {
-            matrix_coeffs(f->matrix, f->full_range, bd, 10, a.coef, &a.shift, a.fcoef);
-            a.maxv = 1023;
+        } else {
+            launch_output_packed_rgb(a, f->layout, f->dtype, f->upsample, cm != NULL, s);
         }
-        if (!two_pass) launch_output_packed_rgb(a, f->layout, f->dtype, f->upsample, cm != NULL, s);
     }
     return out_join(c, stream, s);      // the slot, the DRA and the colour tables
 }
@@ -613,8 +639,9 @@ static int lut3d_rgb_check(const xgpu_output_format *f, int width, int height, i
     *why = "format is NULL";
     if (!f) return XGPU_ERR_INVALID_ARGUMENT;
     const xgpu_output_format g = lut3d_plain_format(f, full16);
-    *need = format_size(&g, width, height, bd, why);
-    if (*need == 0) return is_rgb(g.layout) && bd >= 8 && bd <= 12 && check_format(&g, bd, why) == XGPU_ERR_UNSUPPORTED ? XGPU_ERR_UNSUPPORTED : XGPU_ERR_INVALID_ARGUMENT;
+    int rc;
+    *need = format_size(&g, width, height, bd, &rc, why);
+    if (*need == 0) return rc;
     *why = "a 3D LUT needs one of the RGB layouts";
     return is_rgb(g.layout) ? XGPU_OK : XGPU_ERR_INVALID_ARGUMENT;
 }
@@ -644,20 +671,14 @@ static const Lut3dSlot *lut3d_slot(xgpu_ctx *c, const char *who, int lut)
 // are the caller's to fill
 static void fill_lut3d(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *rf, const Lut3dSlot &l, void *d_dst, Lut3dOutArgs &a)
 {
-    const int bd = c->sp.bit_depth_luma;
-    const DevPic &p = dpic(c, pic);
     memset(&a, 0, sizeof(a));
-    cropped_planes(p, rf->crop, &a.y, &a.u, &a.v);
-    a.sy = p.s_l; a.sc = p.s_c;
-    a.w = c->sp.width - rf->crop[0] - rf->crop[1]; a.h = c->sp.height - rf->crop[2] - rf->crop[3];
-    a.cw = a.w >> 1; a.ch = a.h >> 1;
-    a.dst = (uint8_t *)d_dst;
+    fill_source(c, pic, rf->crop, d_dst, a);
     xgpu_output_format f16 = *rf;
     f16.dtype = XGPU_OUT_U16; f16.out_bit_depth = 0; f16.row_pitch = 0;
     fill_conversion(c, dra, &f16, a);      // bgr, range terms, DRA, coef / shift / maxv of the U16 form
     fill_siting(rf->chroma_loc, a);
     a.shaper = (const uint16_t *)l.d;
-    a.cube = (const uint2 *)(l.d + lut3d_shaper_bytes(bd));
+    a.cube = (const uint2 *)(l.d + lut3d_shaper_bytes(c->sp.bit_depth_luma));
     a.n = l.n;
 }
 int xgpu_pic_output_device_lut3d(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, int lut, void *d_dst, size_t dst_size, void *stream)
@@ -715,8 +736,9 @@ static int dither_format_check(const xgpu_output_format *f, const xgpu_packed_fo
 {
     *s_bits = 0;
     if (f) {
-        *need = format_size(f, width, height, bd, why);
-        if (*need == 0) return is_rgb(f->layout) && bd >= 8 && bd <= 12 && check_format(f, bd, why) == XGPU_ERR_UNSUPPORTED ? XGPU_ERR_UNSUPPORTED : XGPU_ERR_INVALID_ARGUMENT;
+        int rc;
+        *need = format_size(f, width, height, bd, &rc, why);
+        if (*need == 0) return rc;
         *why = "a dithered output needs an integer dtype";
         if (!is_int_dtype(f->dtype)) return XGPU_ERR_UNSUPPORTED;
         *why = "a dithered output needs one of the RGB layouts, NV12 or P016";
@@ -752,9 +774,7 @@ int xgpu_output_dither_check(const xgpu_output_format *f, const xgpu_packed_form
     if (rc < 0) return rc;
     if (cm) {
         const xgpu_output_format rf = f ? *f : packed_rgb_format(pf);
-        std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
-        const int trc = t ? xgpu_colour_tables(&rf, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
-        if (trc < 0) return trc;
+        TRY(cm_dry_run(&rf, cm, bit_depth));
     }
     return dither_matrix_check(mw, mh, k, s_bits, &why);
 }
@@ -797,37 +817,22 @@ int xgpu_pic_output_device_dithered(xgpu_ctx *c, int pic, const xgpu_dra_luts *d
     hipStream_t s;
     TRY(out_fork(c, stream, &s));
     TRY(cm_commit(c, cm, cm_new, s));
-    const int *cr = f->crop;
-    const DevPic &p = dpic(c, pic);
-    const int w = c->sp.width - cr[0] - cr[1], h = c->sp.height - cr[2] - cr[3];
     if (is_semiplanar(f->layout)) {      // xgpu_pic_output_device's arguments, and the matrix
         DitherSemiArgs a;
         memset(&a, 0, sizeof(a));
-        const int obd = sample_depth(f, bd);
-        cropped_planes(p, cr, &a.y, &a.u, &a.v);
-        a.sy = p.s_l; a.sc = p.s_c;
-        a.w = w; a.ch = h >> 1;
-        a.dst = (uint8_t *)d_dst;
-        fill_rows(static_cast<SemiPlanarArgs &>(a), d_dst, (size_t)w * es, h, f->row_pitch, &SemiPlanarArgs::chroma_off);
-        a.shift = bd - obd; a.out8 = obd == 8; a.maxv = (1 << obd) - 1;
-        a.lsh = f->layout == XGPU_OUT_P016 ? 16 - obd : 0;
-        a.dra = dra ? c->d_dra : NULL;
+        fill_semiplanar(c, pic, dra, f, d_dst, a);
         a.di = di;
         launch_output_dither_semiplanar(a, f->dtype, s);
     } else {
         DitherRgbArgs a;
         memset(&a, 0, sizeof(a));
-        cropped_planes(p, cr, &a.y, &a.u, &a.v);
-        a.sy = p.s_l; a.sc = p.s_c;
-        a.w = w; a.h = h;
-        a.cw = w >> 1; a.ch = h >> 1;
-        a.dst = (uint8_t *)d_dst;
-        fill_rows(a, d_dst, image_row(f, w), h, f->row_pitch);
+        fill_source(c, pic, f->crop, d_dst, a);
+        fill_rows(a, d_dst, image_row(f, a.w), a.h, f->row_pitch);
         fill_conversion(c, dra, f, a);
         fill_siting(f->chroma_loc, a);
         if (cm) fill_cm(c, f, *c->cm_tab, a, a.cm);
         a.di = di;
-        launch_output_dither_rgb(a, f->layout == XGPU_OUT_RGB_PLANAR ? DITHER_SINK_PLANAR : DITHER_SINK_INTERLEAVED, f->dtype, f->upsample, cm != NULL, s);
+        launch_output_dither_rgb(a, f->layout == XGPU_OUT_RGB_PLANAR ? OUT_SINK_PLANAR : OUT_SINK_INTERLEAVED, f->dtype, f->upsample, cm != NULL, s);
     }
     return out_join(c, stream, s);      // the slot, the DRA and the colour tables, the matrix
 }
@@ -851,28 +856,14 @@ int xgpu_pic_output_device_packed_dithered(xgpu_ctx *c, int pic, const xgpu_dra_
     hipStream_t s;
     TRY(out_fork(c, stream, &s));
     TRY(cm_commit(c, cm, cm_new, s));
-    const DevPic &p = dpic(c, pic);
-    const int w = c->sp.width - f->crop[0] - f->crop[1], h = c->sp.height - f->crop[2] - f->crop[3];
     DitherRgbArgs a;
     memset(&a, 0, sizeof(a));
-    cropped_planes(p, f->crop, &a.y, &a.u, &a.v);
-    a.sy = p.s_l; a.sc = p.s_c;
-    a.w = w; a.h = h;
-    a.cw = w >> 1; a.ch = h >> 1;
-    a.dst = (uint8_t *)d_dst;
-    fill_rows(a, d_dst, packed_row(f, w), h, f->row_pitch);
+    fill_source(c, pic, f->crop, d_dst, a);
+    fill_rows(a, d_dst, packed_row(f, a.w), a.h, f->row_pitch);
     fill_siting(f->chroma_loc, a);
-    fill_conversion(c, dra, &rf, a);
-    a.alpha = packed_alpha_code(f, bd);
-    if (cm) {      // xgpu_pic_output_device_packed's arguments
-        fill_cm(c, &rf, *c->cm_tab, a, a.cm);
-        if (f->layout == XGPU_PACKED_RGB10A2) a.cm.outmax = 1023.f;
-    } else if (f->layout == XGPU_PACKED_RGB10A2) {
-        matrix_coeffs(f->matrix, f->full_range, bd, 10, a.coef, &a.shift, a.fcoef);
-        a.maxv = 1023;
-    }
+    fill_packed_rgb(c, dra, f, &rf, cm != NULL, a);      // xgpu_pic_output_device_packed's arguments
     a.di = di;
-    launch_output_dither_rgb(a, f->layout == XGPU_PACKED_RGBA ? DITHER_SINK_RGBA : DITHER_SINK_RGB10A2, f->dtype, f->upsample, cm != NULL, s);
+    launch_output_dither_rgb(a, f->layout == XGPU_PACKED_RGBA ? OUT_SINK_RGBA : OUT_SINK_RGB10A2, f->dtype, f->upsample, cm != NULL, s);
     return out_join(c, stream, s);      // the slot, the DRA and the colour tables, the matrix
 }
 
@@ -957,13 +948,6 @@ int xgpu_pic_output_device_scaled_cm(xgpu_ctx *c, int pic, const xgpu_dra_luts *
                                      void *d_dst, size_t dst_size, void *stream)
 {
     return output_scaled(c, "pic_output_device_scaled_cm", pic, dra, f, sc, cm, d_dst, dst_size, stream);
-}
-// what a _check entry ends in: the layout, then whether the transform's tables would build (cm_prepare's order), without a device
-static int cm_dry_run(const xgpu_output_format *f, const xgpu_colour_transform *cm, int bit_depth)
-{
-    if (!is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
-    std::unique_ptr<xgpu_colour_tables_t> t(new (std::nothrow) xgpu_colour_tables_t);
-    return t ? xgpu_colour_tables(f, cm, bit_depth, t.get()) : XGPU_ERR_OUT_OF_MEMORY;
 }
 // the plain call's checks and codes first, then the layout and the transform (cm_prepare's order)
 int xgpu_output_scaled_cm_check(const xgpu_output_format *f, const xgpu_scale_params *sc, const xgpu_colour_transform *cm, int width, int height, int bit_depth)
@@ -1394,7 +1378,8 @@ static size_t ladder_rung_size(const xgpu_output_format *f, int rw, int rh, size
     xgpu_output_format g = *f;
     g.row_pitch = row_pitch;
     for (int i = 0; i < 4; i++) g.crop[i] = 0;
-    return format_size(&g, rw, rh, bd, why);
+    int rc;
+    return format_size(&g, rw, rh, bd, &rc, why);
 }
 size_t xgpu_output_ladder_rung_size(const xgpu_output_format *f, int rung_width, int rung_height, size_t row_pitch, int bit_depth)
 {
