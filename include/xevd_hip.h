@@ -1106,6 +1106,11 @@ int xgpu_test_batch_resid(xgpu_ctx *ctx, xgpu_dbatch *db, int16_t *resid);
    suite pins the builder with it: the arrays do not depend on the thread count, and their digests are golden values. */
 #define XGPU_TEST_BUILD_DIGESTS 13
 int xgpu_test_build_batch(const xgpu_seq_params *sp, const xgpu_cu_batch *b, int threads, uint64_t digest[XGPU_TEST_BUILD_DIGESTS], int info[XGPU_BATCH_INFO_COUNT], double *ms);
+/* ... and k_inter's two work arrays themselves, as the builder leaves them (no device, no HIP call either): work[k] = the roles of 64x64 region k in the kernel's
+   strip order (0x100: the region lies inside one CU; else two bits per 32x32 tile q = 0 .. 3, 1: the tile lies inside one CU, 2: it holds SCUs of the batch, 0: nothing),
+   items[4 * k + q] = the CU the whole tile q lies in, 0xFFFFFFFF where there is none.  *n_work receives the number of regions.  work == items == NULL asks for
+   the count alone; one of them alone, or cap_work below the count, is XGPU_ERR_INVALID_ARGUMENT (nothing written, the count returned).  The CPU suite holds its restatement of the role rule to them (tests/mc_launch.py). */
+int xgpu_test_inter_lists(const xgpu_seq_params *sp, const xgpu_cu_batch *b, int threads, uint32_t *work, uint32_t *items, int cap_work, int *n_work);
 /* dequant + 2-D inverse transform of n blocks of one size, in place (xevd_itdq, src_base/xevd_itdq.c:494) */
 int xgpu_test_itdq(xgpu_ctx *ctx, int16_t *coef, int n_blocks, int log2w, int log2h, const uint8_t *qp, int bit_depth);
 /* ... naming the transform pair and the row stride.  tr_v / tr_h (vertical = first stage, horizontal = second): 0 DCT-II, 1 DST-VII, 2 DCT-VIII; DST-VII and

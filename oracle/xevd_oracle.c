@@ -179,7 +179,7 @@ int orc_mc_cu(const xgpu_seq_params *sp, const orc_frame *fr, int x, int y, int 
 {
     int16_t mv_t[2][2];
     int16_t **dst[2] = { pred0, pred1 };
-    int bidx = 0, l, i;
+    int bidx = 0, l, i, collapsed = 0;
     const int wc = w >> 1, hc = h >> 1;      /* 4:2:0 */
 
     mv_clip(x, y, sp->width, sp->height, w, h, refi, mv, mv_t);
@@ -192,7 +192,7 @@ int orc_mc_cu(const xgpu_seq_params *sp, const orc_frame *fr, int x, int y, int 
             /* identical-motion early-out, xevd_mc.c:512-519 (POC equality of the two reference pictures and
                equality of the CLIPPED vectors) */
             if (fr->refp[refi[0]][0].poc == fr->refp[refi[1]][1].poc &&
-                mv_t[0][0] == mv_t[1][0] && mv_t[0][1] == mv_t[1][1]) break;
+                mv_t[0][0] == mv_t[1][0] && mv_t[0][1] == mv_t[1][1]) { collapsed = 1; break; }
         }
         rp = &fr->refp[refi[l]][l];
         gx = ((x << 2) + mv_t[l][0]) << 2;      /* 1/16-pel luma units, xevd_mc.c:498-502 */
@@ -201,6 +201,21 @@ int orc_mc_cu(const xgpu_seq_params *sp, const orc_frame *fr, int x, int y, int 
            bits of mv<<2 set */
         ldx = ((mv[l][0] << 2) & 15) != 0;  ldy = ((mv[l][1] << 2) & 15) != 0;
         cdx = ((mv[l][0] << 2) & 31) != 0;  cdy = ((mv[l][1] << 2) & 31) != 0;
+        {      /* census: tap rows, regimes, the reference index, and where the luma window lies against the picture */
+            const int wx0 = (gx >> 4) - (ldx ? 3 : 0), wx1 = (gx >> 4) + w - 1 + (ldx ? 4 : 0);
+            const int wy0 = (gy >> 4) - (ldy ? 3 : 0), wy1 = (gy >> 4) + h - 1 + (ldy ? 4 : 0);
+            g_cen.mc_phase[sp->tool_admvp ? 1 : 0][(gx >> 2) & 3][(gy >> 2) & 3]++;
+            g_cen.mc_cphase[sp->tool_admvp ? 1 : 0][(gx >> 2) & 7][(gy >> 2) & 7]++;
+            g_cen.mc_regime[0][ldx * 2 + ldy]++;
+            g_cen.mc_regime[1][cdx * 2 + cdy]++;
+            if ((mv[l][0] & 7) == 4) g_cen.mc_luma_whole_chroma_half[0]++;
+            if ((mv[l][1] & 7) == 4) g_cen.mc_luma_whole_chroma_half[1]++;
+            if (refi[l] < XGPU_MAX_REFS) g_cen.mc_refi[l][refi[l]]++;
+            if (wx0 < 0) g_cen.mc_edge[0][wx1 < 0]++;
+            if (wx1 >= sp->width) g_cen.mc_edge[1][wx0 >= sp->width]++;
+            if (wy0 < 0) g_cen.mc_edge[2][wy1 < 0]++;
+            if (wy1 >= sp->height) g_cen.mc_edge[3][wy0 >= sp->height]++;
+        }
         g_cen_plane = 0;
         orc_mc_l(rp->y, gx, gy, rp->s_l, w, dst[bidx][0], w, h, sp->bit_depth_luma, ldx, ldy, sp->tool_admvp);
         g_cen_plane = 1;
@@ -210,6 +225,7 @@ int orc_mc_cu(const xgpu_seq_params *sp, const orc_frame *fr, int x, int y, int 
         g_cen_plane = 0;
         bidx++;
     }
+    if (refi[0] >= 0 || refi[1] >= 0) g_cen.mc_lists[collapsed ? 3 : (refi[0] >= 0 && refi[1] >= 0 ? 2 : (refi[0] >= 0 ? 0 : 1))]++;
     if (bidx == 2) {
         /* xevd_average_16b_no_clip, xevd_mc.c:145-167: average of the two already-clipped predictions */
         {
@@ -1541,7 +1557,16 @@ int orc_recon_batch_ex(const xgpu_seq_params *sp, const orc_frame *fr, const xgp
                 dmvr_n += (size_t)nsub;
                 dmvr_done = done;
             }
-            if (!done) orc_mc_cu(sp, fr, x, y, w, h, &b->refi[i * 2], (const int16_t (*)[2])&b->mv[i * 4], pred[0], pred[1]);
+            if (!done) {
+                const int ai_c = b->ats_inter ? b->ats_inter[i] : 0;
+                orc_mc_cu(sp, fr, x, y, w, h, &b->refi[i * 2], (const int16_t (*)[2])&b->mv[i * 4], pred[0], pred[1]);
+                /* census: the plain inter CU by shape, TU, cbf and mode */
+                if (lw >= 2 && lw <= 7 && lh >= 2 && lh <= 7) g_cen.mc_shape[lw - 2][lh - 2]++;
+                if ((ai_c & 15) <= 4) g_cen.mc_tu[ai_c & 15][(ai_c >> 4) & 1]++;
+                g_cen.mc_cbf[b->cbf[i] & 7]++;
+                if (b->pred_mode[i] == XGPU_MODE_SKIP) g_cen.mc_skip++;
+                if (b->dmvr && b->dmvr[i]) g_cen.mc_dmvr_fallback++;
+            }
         }
         else if (maps) {      /* xevd_recon_unit's intra branch, xevd.c:731-741 (availability needs the SCU map) */
             int16_t nb_up[2 * MAX_CU + 8], nb_le[2 * MAX_CU + 8], nb_ri[2 * MAX_CU + 8];

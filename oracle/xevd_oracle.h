@@ -244,6 +244,21 @@ typedef struct orc_census {
     uint32_t it_nz_pairs[2][5];                        /* TBs by the number of [row / column] pairs with a non-zero level: 0 / 1 / 2 .. 4 / 5 or more, not all / all */
     uint32_t it_single[32][32];                        /* TBs holding one non-zero level, a side of at least 16, by [row pair][column pair] of it */
     uint32_t it_single_dim[2][3][32];                  /* ... by [vertical / horizontal][that dimension 16 / 32 / 64][pair] */
+    /* translational motion compensation (orc_mc_cu and its call in orc_recon_batch_ex): the plain inter CUs - not affine, not refined by DMVR, not IBC.  "per list": per
+       list the CU is predicted from, i.e. after the identical-motion test.  Sides are left / right / top / bottom like mv_clip */
+    uint32_t mc_phase[2][4][4];                        /* per list, [Baseline / Main tap table][fx][fy]: quarter-sample fraction of the CLIPPED position (row 4 fx of k_luma_taps) */
+    uint32_t mc_cphase[2][8][8];                       /* ... eighth-sample fraction of the clipped position (row 4 fx of k_chroma_taps) */
+    uint32_t mc_regime[2][4];                          /* per list: [luma / chroma][(dx != 0) * 2 + (dy != 0)] of the UNCLIPPED vector */
+    uint32_t mc_luma_whole_chroma_half[2];             /* per list: [axis] luma at a whole sample, chroma at a half one */
+    uint32_t mc_lists[4];                              /* CUs using list 0 only / list 1 only / both / both, collapsed to list 0 by identical motion on equal POCs */
+    uint32_t mc_refi[2][XGPU_MAX_REFS];                /* per list: [list][reference index] */
+    uint32_t mc_shape[6][6];                           /* CUs by [log2w - 2][log2h - 2] */
+    uint32_t mc_edge[4][2];                            /* per list: the luma window (the block, and the filter's margin along an axis it filters) reaches over the picture's
+                                                          [side], [partly / with every sample] - the replicated border read as samples */
+    uint32_t mc_tu[5][2];                              /* CUs by ATS-inter [idx 0 .. 4][pos] */
+    uint32_t mc_cbf[8];                                /* CUs by cbf */
+    uint32_t mc_skip;                                  /* CUs in skip mode */
+    uint32_t mc_dmvr_fallback;                         /* CUs carrying the DMVR flag that are predicted here after all */
 } orc_census;
 void orc_census_reset(void);
 void orc_census_get(orc_census *out);

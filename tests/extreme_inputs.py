@@ -14,6 +14,9 @@ coefficients, so the kernels' packed 16-bit arithmetic, clamps and table tops ar
     trees (`htdf_partition`); block vectors of every parity and sign into sources over many CUs, inside filtered CUs and inside other copies (`set_ibc_vectors`),
   * for intra prediction: modes assigned without a draw on those partitions, so that every predictor meets every shape and every avail_lr it has a form for (`set_intra_modes`,
     with avail_lr restated from batch order: `intra_avail_lr`),
+  * for translational motion compensation: partitions that mix k_inter's three roles (`mc_partition`), lists, reference indices and vectors in fixed cycles per role - every
+    window alignment x whole / fractional on both axes in the region and tile roles, every pair of phases under every wave-level regime in the split role, the clip thresholds
+    and the picture's edges in every role (`set_mv_mc`) -, coded flags, ATS-inter TUs, skip mode and DMVR flags the same way (`set_mc_coding`),
 and `apply` puts them into a case that cases.build_case has built (tools={"extreme": {...}}).  What each of them is FOR is asserted
 through the oracle's census (oracle_lib.census) in tests/test_oracle_extremes.py.
 """
@@ -1099,6 +1102,319 @@ def regenerate_residual_batch(case, seed, gen):
     case["batch"] = b
 
 
+# ---- translational motion compensation at every role, window alignment and regime of k_inter (tests/mc_launch.py restates the kernel's launch side; the branches: oracle
+# census mc_*, launch census of mc_launch.census).  Partitions that mix the three roles (mc_partition), vectors assigned per CU in a fixed cycle per role (set_mv_mc), lists,
+# reference indices, coded flags, ATS-inter TUs, skip mode and DMVR flags assigned the same way (set_mc_coding).
+# A 64x64 cell: R one CU (region role) / T four of 32x32, W two of 64x32, H two of 32x64 (tile role) / Q a shape of at most 32 a side per quadrant, all sixteen in turn
+# (32x32: tile role, the others split) / L one of the long shapes (split role, CUs over two tiles)
+MC_CELLS = ("R", "Q", "R", "W", "R", "L", "R", "Q", "R", "H", "R", "T")
+MC_QUAD = tuple((a, b) for a in (4, 8, 16, 32) for b in (32, 4, 16, 8))
+MC_LONG = ((64, 16), (16, 64), (64, 8), (8, 64), (64, 4), (4, 64))
+
+
+def mc_partition(w, h, log2_ctu, rot=0, big="half", cells=MC_CELLS):
+    """htdf_partition's sibling for k_inter's roles: the picture in cells of 64x64 that take the kinds of `cells` in turn (from entry 3 * rot on).  With CTU 128 every other
+    whole CTU (`big` = 'all': every one) holds one CU with a side of 128 (HTDF_128 in turn from entry `rot` on: 128x128, 128x64 and 64x128 are whole regions).  What is left
+    of a picture 8 samples larger than a multiple of 64 is tiled like htdf_partition's (HTDF_EDGE: 8x64 and 8x32 among them, CUs of 64 and 32 a side in the ragged last
+    columns / rows).  A picture 48 larger has there what a ternary cut of a CTU leaves inside it: a strip of 16 and beside it CUs of 32x64 and 32x32 that end at the
+    picture's edge, in a 32x32 tile the picture cuts - split role for that reason alone.  -> x, y, log2w, log2h, ctu_cu_start"""
+    ctu = 1 << log2_ctu
+    out, start = [], []
+    n_cell = n_ctu = n_edge = n_big = n_quad = n_long = 0
+
+    def tile(px, py, pw, ph, bw, bh):
+        out.extend((bx, by, bw, bh) for by in range(py, py + ph, bh) for bx in range(px, px + pw, bw))
+
+    for cy in range(0, h, ctu):
+        for cx in range(0, w, ctu):
+            start.append(len(out))
+            if log2_ctu == 7 and cx + 128 <= w and cy + 128 <= h:
+                n_ctu += 1
+                if big == "all" or (n_ctu + rot) & 1:
+                    tile(cx, cy, 128, 128, *HTDF_128[(rot + n_big) % len(HTDF_128)])
+                    n_big += 1
+                    continue
+            for qy in range(cy, min(cy + ctu, h), 64):
+                for qx in range(cx, min(cx + ctu, w), 64):
+                    iw, ih = min(qx + 64, w) - qx, min(qy + 64, h) - qy
+                    if iw == 64 and ih == 64:
+                        kind = cells[(n_cell + 3 * rot) % len(cells)]
+                        n_cell += 1
+                        if kind == "Q":
+                            for q in range(4):
+                                tile(qx + (q & 1) * 32, qy + (q >> 1) * 32, 32, 32, *MC_QUAD[(n_quad + 5 * rot) % 16])
+                                n_quad += 1
+                        elif kind == "L":
+                            tile(qx, qy, 64, 64, *MC_LONG[(n_long + 2 * rot + 2) % len(MC_LONG)])
+                            n_long += 1
+                        else:
+                            tile(qx, qy, 64, 64, *{"R": (64, 64), "T": (32, 32), "W": (64, 32), "H": (32, 64)}[kind])
+                    elif (iw, ih) in ((48, 64), (64, 48)):      # a ternary cut 16 | 32 | 16 with its last part outside the picture
+                        tall = (n_edge + rot) & 1
+                        n_edge += 1
+                        if iw == 48:
+                            tile(qx, qy, 16, 64, 16, 64 if tall else 16)
+                            tile(qx + 16, qy, 32, 64, 32, 64 if tall else 32)
+                        else:
+                            tile(qx, qy, 64, 16, 64 if tall else 16, 16)
+                            tile(qx, qy + 16, 64, 32, 64 if tall else 32, 32)
+                    elif iw == 48 or ih == 48:
+                        tile(qx, qy, iw, ih, 16 if iw % 16 == 0 else 8, 16 if ih % 16 == 0 else 8)
+                    else:
+                        cands = [s for s in HTDF_EDGE if iw % s[0] == 0 and ih % s[1] == 0] if iw <= ih else [s[::-1] for s in HTDF_EDGE if iw % s[1] == 0 and ih % s[0] == 0]
+                        tile(qx, qy, iw, ih, *cands[(n_edge + rot) % len(cands)])
+                        n_edge += 1
+    start.append(len(out))
+    a = np.array(out, np.int64)
+    return (a[:, 0].astype(np.uint16), a[:, 1].astype(np.uint16), np.log2(a[:, 2]).astype(np.uint8), np.log2(a[:, 3]).astype(np.uint8), np.array(start, np.uint32))
+
+
+def regenerate_mc_batch(case, seed, gen):
+    """Replace the case's batch by one that synth.gen_frame draws on mc_partition (gen: its keyword arguments + 'rot', 'big', 'cells').  CUs of at least 32x32 are inter CUs, the
+    smaller ones mostly (intra neighbours inside split-role waves); lists, vectors, flags and levels are assigned afterwards (set_mv_mc, set_mc_coding)."""
+    from xevd_amd import synth
+    gen = dict(gen)
+    rot, big, cells = gen.pop("rot", 0), gen.pop("big", "half"), gen.pop("cells", MC_CELLS)
+    old = case["batch"]
+    b = synth.gen_frame(np.random.default_rng(seed + 31 * rot), case["w"], case["h"], case["bd"], log2_ctu=case["log2_ctu"], partition=mc_partition(case["w"], case["h"], case["log2_ctu"], rot, big, cells), **gen)
+    b["pred_mode"][(b["log2w"] >= 5) & (b["log2h"] >= 5)] = 1
+    b["constrained_intra_pred"] = old.get("constrained_intra_pred", 0)
+    case["batch"] = b
+
+
+def mc_cu_roles(batch, w, h):
+    """the first of k_inter's roles (0 region, 1 tile, 2 split) each CU has a part in, by mc_launch's restatement of the builder's rule"""
+    import mc_launch
+    work, items = mc_launch.roles(batch, w, h)
+    role = np.full(len(batch["x"]), 2, np.int64)
+    for k in range(len(work)):
+        for q in range(4):
+            i = int(items[4 * k + q])
+            if i != mc_launch.NONE:
+                role[i] = min(role[i], 0 if work[k] == mc_launch.WORK_REGION else 1)
+    return role
+
+
+def _mc_aligned_slots():
+    """The vectors of the region and tile roles, (vx, vy) in quarter samples of -32 .. 31 on both axes: the product window alignment mis 0 .. 7 x luma whole / fractional on
+    both axes x which of the two whole-sample offsets of that mis (they differ by 8 samples: cmis differs by 4) x the parity of the whole-sample y offset (whole luma with
+    whole or half chroma) - 128 vectors, ordered so that the 32 cells [mis][fx][fy] and the 32 cells [cmis][cfx][cfy] are all met as early as possible (greedy), and
+    so that two vectors in a row differ in mis and in (fx, fy).  The fractions take 1, 2, 3 in turn."""
+    slots = []
+    for k in range(128):
+        mis, fx, fy, half, ypar = k & 7, (k >> 3) & 1, (k >> 4) & 1, (k >> 5) & 1, (k >> 6) & 1
+        m = ((mis + 3) & 7) - 8 * half
+        my = 2 * ((k * 3) % 8 - 4) + ypar
+        vx, vy = 4 * m + fx * (1 + k % 3), 4 * my + fy * (1 + (k // 3) % 3)
+        cells = (("l", mis, fx, fy), ("c", ((vx >> 3) - 1) & 7, int(vx & 7 != 0), int(vy & 7 != 0)))
+        slots.append(((vx, vy), cells))
+    order, seen, last = [], set(), None
+    while slots:      # (a two-list CU takes two vectors in a row: neighbours in this order differ in alignment and in their whole / fractional pattern)
+        ok = [i for i in range(len(slots)) if last is None or (slots[i][1][0][1] != last[1] and slots[i][1][0][2:] != last[2:])] or list(range(len(slots)))
+        best = max(ok, key=lambda i: sum(c not in seen for c in slots[i][1]))
+        v, cells = slots.pop(best)
+        last = cells[0]
+        seen.update(cells)
+        order.append(v)
+    return order
+
+
+MC_ALIGNED_SLOTS = _mc_aligned_slots()
+# what the CUs inside one split-role tile may do, per axis: 0 multiples of 8 quarter samples (chroma whole too), 1 multiples of 4 (luma whole, chroma whole or half), 2 anything -
+# the wave-level H / V of mc_scu_list are ballots, so a wave without a filtering lane takes a tile in which NO vector has a fraction
+MC_TILE_LEVELS = ((2, 2), (0, 0), (2, 2), (0, 1), (1, 0), (2, 2), (1, 1), (0, 2), (2, 0), (2, 2), (1, 2), (2, 1))
+_MC_AX = ((0,), (0, 4), (0, 1, 2, 3, 4, 5, 6, 7))
+# reference indices of a two-list CU in turn: POCs 4 / 16 and 0 / 12 (not symmetric about 8), 4 / 12 and 0 / 16 (symmetric), 0 / 4 (cases.POCS)
+_MC_REF_PAIRS = ((0, 1), (1, 0), (0, 0), (1, 2), (1, 1), (0, 1))
+
+
+def set_mv_mc(batch, kind, w, h, admvp, seed=0, at=(0, 0)):
+    """Lists, reference indices and vectors of every plain inter CU, assigned in fixed cycles per role - nothing is drawn.
+    Lists: list 0 only, both, list 1 only, both, both with identical motion on equal POCs (list 0 index 0 and list 1 index 2 are one picture), in turn per role - in the split
+    role also both with ONE vector on pictures of different POCs, and both on equal POCs with vectors that differ in y alone (neither is identical motion); a CU of
+    4x4, 4x8 or 8x4 in a Main sequence takes one list (xevdm_check_bi_applicability).  Two reference indices in list 0, three in list 1.
+    Vectors, kind 'walk': region and tile role - MC_ALIGNED_SLOTS in turn per role and list use; list 1 of a two-list CU takes the next one, which has another alignment and another
+    whole / fractional pattern than list 0's.  Split role - every pair of eighth-sample phases the
+    tile's levels admit (MC_TILE_LEVELS by tile, for CUs inside one tile) in turn, whole-sample offsets of -4 .. 3 chroma samples.
+    'thresholds': every region- and tile-role CU and every other split-role CU has its first list on, one quarter sample inside or outside the threshold of xevd_mv_clip on
+    the left / right / top / bottom in turn (set_mv_thresholds' values), the other component and the other CUs as 'walk'.
+    'edges': every other CU per role has its first list's block 1 .. 6 samples over the picture's left / right / top / bottom edge in turn."""
+    n = len(batch["x"])
+    role = mc_cu_roles(batch, w, h)
+    aff = batch.get("affine")
+    refi = np.full((n, 2), -1, np.int8)
+    mv = np.zeros((n, 2, 2), np.int64)
+    n_cu, n_pair, taken = [seed, seed + 1, seed + 2], seed, [0, 0]
+    queue = [list(MC_ALIGNED_SLOTS[a % 128:] + MC_ALIGNED_SLOTS[:a % 128]) for a in at]      # `at`: where in the cycle the region and the tile role begin - a case goes on where another stopped
+    t_level = {}
+    tiles_x = (w + 31) >> 5
+
+    def take(r):
+        taken[r] += 1
+        queue[r].append(queue[r].pop(0))
+        return queue[r][-1]
+
+    for i in range(n):
+        pm = int(batch["pred_mode"][i])
+        if pm == MODE_INTRA or pm == 6 or (aff is not None and aff[i]):
+            continue
+        r = int(role[i])
+        x, y, lw, lh = int(batch["x"][i]), int(batch["y"][i]), int(batch["log2w"][i]), int(batch["log2h"][i])
+        cw, ch = 1 << lw, 1 << lh
+        c = n_cu[r]
+        n_cu[r] += 1
+        # 4 / 5 (split role): the two halves of the identical-motion test on their own - one vector on pictures of different POCs, equal POCs with vectors that agree in x only
+        lists = (0, 2, 1, 2, 3, 4, 2, 5)[c % 8] if r == 2 else (2, 0, 2, 1, 2, 3)[c % 6]      # (region and tile role: few CUs, more of them with two lists)
+        if admvp and cw + ch <= 12:
+            lists = c & 1
+        almost, lists = lists, (2 if lists > 3 else lists)
+        used = [lists != 1, lists != 0]
+        if lists == 3 or almost == 5:
+            refi[i] = (0, 2)
+        elif lists == 2:
+            refi[i] = _MC_REF_PAIRS[n_pair % len(_MC_REF_PAIRS)]
+            n_pair += 1
+        else:
+            refi[i, lists] = (c // 5 + c) % (2 if lists == 0 else 3)
+        first = 0 if used[0] else 1
+        special = kind != "walk" and (c % 2 == 0 or (r < 2 and kind == "thresholds"))
+        if r < 2:
+            if special:      # the first list's vector is made below: its other component from a cycle of its own, so that MC_ALIGNED_SLOTS is walked by the other vectors alone
+                vs = [((c * 5) % 64 - 32, (c * 11 + 7) % 64 - 32)] * 2
+                if used[0] and used[1] and lists != 3:
+                    vs[1] = take(r)
+            elif used[0] and used[1] and lists != 3:
+                vs = [take(r), take(r)]
+            else:
+                v0 = take(r)
+                vs = [v0, v0]
+        else:
+            inside = (x >> 5) == ((x + cw - 1) >> 5) and (y >> 5) == ((y + ch - 1) >> 5)
+            lv = MC_TILE_LEVELS[(((y >> 5) * tiles_x + (x >> 5)) * 5 + seed) % len(MC_TILE_LEVELS)] if inside else (2, 2)
+            vs = []
+            for l in range(2):
+                t = t_level.get(lv, 7 * seed)
+                t_level[lv] = t + 1
+                ax, ay = _MC_AX[lv[0]], _MC_AX[lv[1]]
+                vs.append((8 * ((t * 3 + t // 64) % 8 - 4) + ax[t % len(ax)], 8 * ((t * 5 + t // 64 + 2) % 8 - 4) + ay[(t // len(ax)) % len(ay)]))
+        if lists == 3 or almost == 4:
+            vs = [vs[0], vs[0]]
+        elif almost == 5:
+            vs = [vs[0], (vs[0][0], vs[0][1] + (8, 4, 4 + (c & 3))[lv[1]])]      # (within what the tile's level admits)
+        if special:
+            side, out = ((c // 2) % 4, (1, 0, 1, -1)[(c // 8) % 4]) if r == 2 or kind != "thresholds" else (c % 4, (1, 0, 1, -1)[(c // 4) % 4])
+            d = -out if side in (0, 2) else out      # one quarter sample outside (the clip moves it) twice, on the threshold, one inside
+            v = list(vs[first])
+            if kind == "thresholds":
+                thr = (-512 - 4 * x, ((w - 1 + 128) << 2) - 4 * x - 4 * cw + 4, -512 - 4 * y, ((h - 1 + 128) << 2) - 4 * y - 4 * ch + 4)[side]
+                v[side >> 1] = thr + d
+            else:
+                e = 1 + (c // 8) % 6
+                v[side >> 1] = (4 * (-e - x), 4 * (w - x - cw + e), 4 * (-e - y), 4 * (h - y - ch + e))[side] + (v[side >> 1] & 3)
+            vs[first] = tuple(v)
+            if lists == 3 or almost == 4:
+                vs = [vs[first], vs[first]]
+        for l in range(2):
+            if used[l]:
+                mv[i, l] = vs[l]
+    assert mv.min() >= -32768 and mv.max() <= 32767
+    batch["refi"], batch["mv"] = refi, mv.astype(np.int16)
+    return tuple(taken)
+
+
+_MC_CHAIN = {}
+
+
+def mc_chain_start(name):
+    """Where the cycles of the region and the tile role begin in case `name` of MC_CASES: (place in MC_ALIGNED_SLOTS of the region role, of the tile role, place in their
+    cycles of ATS-inter TUs) = what the cases before it in MC_CASES took, so that the few CUs these roles have per picture walk ONE cycle over the pictures together.  Found by
+    building the case before (once per process); the first case, and a case that is not in the list, begin at 0."""
+    if name not in _MC_CHAIN:
+        k = next((k for k, s in enumerate(MC_CASES) if s[0] == name), 0)
+        if k == 0:
+            _MC_CHAIN[name] = (0, 0, 0, 0)
+        else:
+            import cases
+            before = cases.build_case(*MC_CASES[k - 1][:9])
+            _MC_CHAIN[name] = tuple(int(a + t) for a, t in zip(before["mc_at"], before["mc_taken"]))
+    return _MC_CHAIN[name]
+
+
+def set_mc_coding(case, seed=0, tu_at=(0, 0)):
+    """Coded flags, ATS-inter TUs, skip mode and DMVR flags of the plain inter CUs in fixed cycles per role (so that each role meets every cbf, every TU index and position,
+    skipped CUs and flagged ones), and a coefficient arena to match - every coded TB a few small levels at low positions (drawn: the residual pass has its own cases).
+      cbf        7, 0, 1, 6, 3, 4, 5, 2 in turn; a skipped CU (every seventh) has none
+      ATS-inter  (Main with ATS) every other CU with coefficients and at most 64 a side (region and tile role: seven in eight): the indices its shape admits in turn, both positions
+      DMVR flag  (Main) two-list CUs of at least 8x8: every other one whose references are not POC-symmetric (predicted by k_inter after all), in the split role every fourth
+                 symmetric one (k_dmvr's: a refined neighbour inside a split-role wave); every fifth one-list CU (the flag alone changes nothing)"""
+    b, w, h, bd = case["batch"], case["w"], case["h"], case["bd"]
+    main = bool(case["admvp"])
+    n = len(b["x"])
+    rng = np.random.default_rng(seed + 77)
+    role = mc_cu_roles(b, w, h)
+    lw, lh, pm = b["log2w"].astype(np.int64), b["log2h"].astype(np.int64), b["pred_mode"].astype(np.int64)
+    inter = (pm != MODE_INTRA) & (pm != 6)
+    cbf, ai, dm = b["cbf"].copy(), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    poc = {k: p.poc for k, p in case["refs"].items()}
+    import mc_launch
+    cur = mc_launch.CUR_POC
+    cnt, cnt_tu, cnt_dm = [seed, seed + 3, seed + 5], [tu_at[0], tu_at[1], 0], [0, 0, 0, 0]      # tu_at: where the region and the tile role's TU cycles begin
+    for i in np.nonzero(inter)[0]:
+        r = int(role[i])
+        c = cnt[r]
+        cnt[r] += 1
+        cbf[i] = (7, 0, 1, 6, 3, 4, 5, 2)[c % 8]
+        if c % 7 == 3:
+            b["pred_mode"][i], cbf[i] = 2, 0
+        if main and case["iqt"] and cbf[i] and lw[i] <= 6 and lh[i] <= 6 and (c // 8 + c) % 2 == 0:
+            avail = [j + 1 for j, a in enumerate((lw[i] >= 3, lh[i] >= 3, lw[i] >= 4, lh[i] >= 4)) if a]
+            if avail:
+                k = cnt_tu[r]
+                cnt_tu[r] += 1
+                ai[i] = avail[k % len(avail)] | (((k // len(avail)) & 1) << 4)
+        elif main and case["iqt"] and r < 2 and cbf[i] and lw[i] <= 6 and lh[i] <= 6 and c % 4 != 1:      # (region and tile role: few CUs - three in four, index and position walk together)
+            k = cnt_tu[r]
+            cnt_tu[r] += 1
+            ai[i] = (1 + k % 4) | (((k // 4) & 1) << 4)
+        two = b["refi"][i, 0] >= 0 and b["refi"][i, 1] >= 0
+        if main and two and lw[i] >= 3 and lh[i] >= 3:
+            p0, p1 = poc[(int(b["refi"][i, 0]), 0)], poc[(int(b["refi"][i, 1]), 1)]
+            sym = (cur - p0) * (cur - p1) < 0 and abs(cur - p0) == abs(cur - p1)
+            k = cnt_dm[2 * int(sym) + (r == 2)]
+            cnt_dm[2 * int(sym) + (r == 2)] += 1
+            dm[i] = (k % 2 == 0) if not sym else (r == 2 and k % 4 == 1)
+        elif main and not two:
+            dm[i] = c % 5 == 4
+    b["cbf"] = cbf
+    b["ats_inter"] = ai if ai.any() else None
+    b["dmvr"] = dm if dm.any() else None
+    big = (lw > 6) | (lh > 6)
+    if big.any():      # every sub-block of a coded plane of a CU above 64 is coded
+        sub = np.zeros(n, np.uint16)
+        for i in np.nonzero(big)[0]:
+            m = sum(1 << sb for sb in range(4) if (sb & 1) < (2 if lw[i] > 6 else 1) and (sb >> 1) < (2 if lh[i] > 6 else 1))
+            sub[i] = sum(m << (4 * k) for k in range(3) if (cbf[i] >> k) & 1)
+        b["cbf_sub"] = sub
+    else:
+        b["cbf_sub"] = None
+    idx = ai & 15
+    tu = (1 << (lw - np.where(idx == 1, 1, np.where(idx == 3, 2, 0)))) * (1 << (lh - np.where(idx == 2, 1, np.where(idx == 4, 2, 0))))
+    size = tu * (cbf & 1) + (tu // 4) * ((cbf >> 1) & 1) + (tu // 4) * ((cbf >> 2) & 1)
+    b["coef_off"] = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.uint32)
+    b["n_coef"] = int(size.sum())
+    coef = np.zeros(max(b["n_coef"], 1), np.int16)
+    for (i, k, sb, tw, th, cl, off, tr, qp) in residual_tbs(b):
+        # a level of 1 or 2 where the quantiser step is large: the sum stays well inside the sample range and a wrong predicted sample shows behind it
+        l2 = tw + th
+        gain = (np.array([40, 45, 51, 57, 64, 71])[qp % 6] << (qp // 6)) * (181 if l2 & 1 else 1) / 2.0 ** (6 - (15 - bd - (l2 >> 1)) + 8 * (l2 & 1))
+        cap = int(np.clip(np.floor(0.25 * (1 << bd) / gain), 1, 8))
+        for _ in range(1 + (i + k) % 4):
+            px, py = int(rng.integers(0, min(1 << tw, 6))), int(rng.integers(0, min(1 << th, 6)))
+            coef[off + (py << cl) + px] = int(rng.integers(1, cap + 1)) * (1 if rng.random() < 0.5 else -1)
+    b["coef"] = coef
+    return (cnt_tu[0] - tu_at[0], cnt_tu[1] - tu_at[1])
+
+
 PER_CU = ("x", "y", "log2w", "log2h", "pred_mode", "refi", "mv", "qp", "cbf", "coef_off", "ipm", "ats", "ats_inter", "affine", "affine_mv", "dmvr", "tree", "cbf_sub")
 
 
@@ -1135,7 +1451,9 @@ def apply(case, spec, seed=0):
               'affine': 'sizes' | 'eif' | 'trans' | 'limits' | 'wide' | 'tall' (set_affine), 'affine_start': the first variant, 'intra_start': added to the seed of set_intra_modes,
               'htdf_partition': the same on htdf_partition (+ 'rot', 'rtl', 'dual', 'all128'), 'ibc': (kind of IBC_WANTS, share of the CUs) for set_ibc_vectors,
               'intra': 'eipd' | 'base' for set_intra_modes (the modes of the intra CUs, assigned last: tiles and copies are in place),
-              'residual_partition': synth.gen_frame arguments for a batch on htdf_partition as drawn (+ 'rot', 'rtl', 'all128'), 'residual': set_residual's spec }"""
+              'residual_partition': synth.gen_frame arguments for a batch on htdf_partition as drawn (+ 'rot', 'rtl', 'all128'), 'residual': set_residual's spec,
+              'mc_partition': the same on mc_partition (+ 'rot', 'big'), with 'mv': 'mc_walk' | 'mc_thresholds' | 'mc_edges' (set_mv_mc, then set_mc_coding), 'mc_start': where
+              their cycles begin (the cycles of the region and tile roles go on from case to case: mc_chain_start) }"""
     w, h, bd = case["w"], case["h"], case["bd"]
     base = 7919 * (seed + 1)
     if spec.get("partition") is not None:
@@ -1146,6 +1464,8 @@ def apply(case, spec, seed=0):
         regenerate_htdf_batch(case, base + 500, spec["htdf_partition"])
     if spec.get("residual_partition") is not None:
         regenerate_residual_batch(case, base + 500, spec["residual_partition"])
+    if spec.get("mc_partition") is not None:
+        regenerate_mc_batch(case, base + 500, spec["mc_partition"])
     kinds = spec.get("content")
     if kinds is not None:
         done = {}
@@ -1184,6 +1504,10 @@ def apply(case, spec, seed=0):
         set_mv_dmvr_zero(b)
     elif spec.get("mv") == "dmvr_thresholds":
         set_mv_dmvr_thresholds(b, w, h)
+    elif spec.get("mv") in ("mc_walk", "mc_thresholds", "mc_edges"):
+        case["mc_at"] = at = mc_chain_start(case["name"])
+        case["mc_taken"] = set_mv_mc(b, spec["mv"][3:], w, h, case["admvp"], seed + int(spec.get("mc_start", 0)), at[:2])
+        case["mc_taken"] += set_mc_coding(case, seed + int(spec.get("mc_start", 0)), at[2:])
     if spec.get("affine") is not None:      # (after the vectors: the control points are the affine CUs' own)
         set_affine(b, spec["affine"], w, h, seed, spec.get("affine_start", 0))
     if spec.get("levels") == "dense":
@@ -1378,6 +1702,36 @@ RESIDUAL_CASES = [
      ("it_strided", "it_s32", "it_final_clip")),
 ]
 EXTREME_CASES += RESIDUAL_CASES
+
+# ---- translational motion compensation at every role, window alignment and regime of k_inter (mc_partition, set_mv_mc, set_mc_coding; tests/test_oracle_extremes.py:
+# test_mc_cases_together_reach_every_branch, the launch side of the census: tests/mc_launch.py).  CTU 64 and 128, 8 / 10 / 12 bit, both tap tables, with and without ADDB / ALF.
+# The references of the two lists are different full-range noise pictures and the start picture is unlike both: the region and tile roles leave out the chunks of their LDS
+# windows that a whole-sample component does not need, and what is left out keeps what it held - the other list's window, the previous region's, the start of the launch.  A
+# chunk left out by mistake then delivers samples that are WRONG; between two smooth or two equal references it would deliver nearly the right ones, which is why neither
+# is acceptable here.  One case has 0 / max checkerboards and rails instead, for the clips of the interpolation in these roles.
+_MGEN = {"inter_frac": 0.85, "bi_frac": 0.0, "n_refs": (2, 3), "oob_frac": 0.0, "coded_frac": 0.6, "qp_range": (20, 38)}
+_MREQ = ("mcr_roles", "mcr_windows", "mcr_lanes", "mcr_coding")
+MC_CASES = [
+    ("x_mcr_walk_main_10b", 264, 264, 10, 1, 1, (2, 3), 0.5, {"addb": 1, "alf": 1, "extreme": {"mc_partition": dict(_MGEN, admvp=True, rot=0), "content": "noise", "start": "gratings", "mv": "mc_walk"}},
+     _MREQ + ("mcr_second_list", "mcr_dmvr_fallback", "mcr_identical")),
+    ("x_mcr_walk_main_8b_aligned", 256, 256, 8, 1, 1, (2, 3), 0.5, {"addb": 1, "extreme": {"mc_partition": dict(_MGEN, admvp=True, rot=0, cells=("R", "T", "Q", "R", "W", "L", "R", "H")), "content": "noise", "start": "ladder", "mv": "mc_walk", "mc_start": 8}},
+     ("mcr_roles", "mcr_windows", "mcr_second_list", "mcr_coding", "mcr_dmvr_fallback", "mcr_identical")),
+    ("x_mcr_walk_base_8b", 264, 200, 8, 0, 0, (2, 3), 0.5, {"extreme": {"mc_partition": dict(_MGEN, rot=1), "content": "noise", "start": "ladder", "mv": "mc_walk", "mc_start": 1}},
+     ("mcr_roles", "mcr_lanes", "mcr_coding", "mcr_identical")),
+    ("x_mcr_walk_main_12b_ctu128", 264, 264, 12, 1, 1, (2, 3), 0.5, {"log2_ctu": 7, "addb": 1, "extreme": {"mc_partition": dict(_MGEN, admvp=True, rot=0), "content": "noise", "start": "gratings", "mv": "mc_walk", "mc_start": 2}},
+     ("mcr_roles", "mcr_lanes", "mcr_dmvr_fallback", "mcr_identical", "mcr_big")),
+    ("x_mcr_thresholds_main_8b_ctu128", 264, 264, 8, 1, 1, (2, 3), 0.5, {"log2_ctu": 7, "extreme": {"mc_partition": dict(_MGEN, admvp=True, rot=2), "content": ["checker1", "rails_dither", "checker2", "rows", "cols"], "start": "noise", "mv": "mc_thresholds", "mc_start": 3}},
+     ("mcr_roles", "mcr_lanes", "mcr_second_list", "mcr_clip", "mc_clip", "mcr_big", "mcr_dmvr_fallback")),
+    ("x_mcr_edges_base_10b_ctu128", 264, 264, 10, 0, 0, (2, 3), 0.5, {"log2_ctu": 7, "extreme": {"mc_partition": dict(_MGEN, rot=4, big="all"), "content": "noise", "start": "gratings", "mv": "mc_edges", "mc_start": 4}},
+     ("mcr_lanes", "mcr_coding", "mcr_edges", "mcr_big", "mcr_identical")),
+    ("x_mcr_thresholds_base_12b", 264, 264, 12, 0, 0, (2, 3), 0.5, {"extreme": {"mc_partition": dict(_MGEN, rot=5), "content": "noise", "start": "ladder", "mv": "mc_thresholds", "mc_start": 5}},
+     _MREQ + ("mcr_clip",)),
+    ("x_mcr_edges_main_8b_ragged", 240, 240, 8, 1, 1, (2, 3), 0.5, {"addb": 1, "alf": 1, "extreme": {"mc_partition": dict(_MGEN, admvp=True, rot=3), "content": "noise", "start": "ladder", "mv": "mc_edges", "mc_start": 6}},
+     ("mcr_roles", "mcr_edges", "mcr_ragged", "mcr_dmvr_fallback")),
+    ("x_mcr_walk_main_10b_ctu128_noaddb", 264, 264, 10, 1, 1, (2, 3), 0.5, {"log2_ctu": 7, "extreme": {"mc_partition": dict(_MGEN, admvp=True, rot=8, big="all"), "content": "noise", "start": "gratings", "mv": "mc_walk", "mc_start": 7}},
+     ("mcr_big", "mcr_identical")),
+]
+EXTREME_CASES += MC_CASES
 
 # the cases written for the branches of the DMVR search (tests/test_oracle_extremes.py: test_dmvr_cases_together_reach_every_branch)
 DMVR_CASES = [s for s in EXTREME_CASES if "dmvr_pair" in s[8].get("extreme", {})]

@@ -58,7 +58,10 @@ class OrcCensus(C.Structure):
                 ("it_ats_inter", ((C.c_uint32 * 2) * 2) * 4), ("it_strided", C.c_uint32 * 4), ("it_qp", C.c_uint32 * 96), ("it_dq_clip", (C.c_uint32 * 2) * 2), ("it_dq_zero", C.c_uint32 * 2),
                 ("it_dq_cmax", (C.c_uint32 * 2) * 2), ("it_high", C.c_uint32 * 2), ("it_s1_clip", (C.c_uint32 * 2) * 2), ("it_s1_negfrac", C.c_uint32), ("it_s1_mag", C.c_uint32 * 5),
                 ("it_s2_clip", (C.c_uint32 * 2) * 3), ("it_s2_undef", C.c_uint32), ("it_undef_tb", C.c_uint32), ("it_nz_pairs", (C.c_uint32 * 5) * 2), ("it_single", (C.c_uint32 * 32) * 32),
-                ("it_single_dim", ((C.c_uint32 * 32) * 3) * 2)]
+                ("it_single_dim", ((C.c_uint32 * 32) * 3) * 2),
+                ("mc_phase", ((C.c_uint32 * 4) * 4) * 2), ("mc_cphase", ((C.c_uint32 * 8) * 8) * 2), ("mc_regime", (C.c_uint32 * 4) * 2), ("mc_luma_whole_chroma_half", C.c_uint32 * 2),
+                ("mc_lists", C.c_uint32 * 4), ("mc_refi", (C.c_uint32 * abi.XGPU_MAX_REFS) * 2), ("mc_shape", (C.c_uint32 * 6) * 6), ("mc_edge", (C.c_uint32 * 2) * 4),
+                ("mc_tu", (C.c_uint32 * 2) * 5), ("mc_cbf", C.c_uint32 * 8), ("mc_skip", C.c_uint32), ("mc_dmvr_fallback", C.c_uint32)]
 
 
 def census_reset():

@@ -2,7 +2,8 @@
 per array (CU records, CTU starts, TB records, itdq work items, intra records, dependency lists, affine tiles, control points, DMVR sub-blocks, owner map).
 Pinned here: the arrays do not depend on the number of builder threads, and they equal the committed digests (tests/golden/builder_digests.json, written by this
 file's --write with the builder whose staging blocks the GPU suite decodes bit-exactly: a refactoring of the builder must reproduce them byte for byte).  Further down the
-test side's restatements of what the builder and the oracle decide (affine paths, the filter's skip condition, avail_lr of intra CUs) are held to the oracle's census."""
+test side's restatements of what the builder and the oracle decide (affine paths, the filter's skip condition, avail_lr of intra CUs) are held to the oracle's census, and the
+restatement of k_inter's roles (tests/mc_launch.py) to the builder's own two arrays (xgpu_test_inter_lists)."""
 import ctypes as C
 import glob
 import json
@@ -430,3 +431,56 @@ def test_builder_residual_work_items_follow_the_oracle_census(spec):
     assert one[10 + 1] == cen["it_tb"].sum(), "transform blocks"
     assert one[10 + 2] == items, "work items of the residual pass"
     assert one == four, "one and four builder threads"
+
+
+# ---- k_inter's work arrays themselves (xgpu_test_inter_lists) against the test side's restatement of inter_work_lists (tests/mc_launch.py: roles), which the launch side of the
+# motion-compensation census stands on: the motion-compensation cases, a picture with local dual trees in a tile grid (chroma-only CUs are ignored), and a picture of 65 regions
+# a row (more than one strip)
+def _role_specs():
+    import extreme_inputs as xi
+    return [s[:9] for s in xi.MC_CASES] + [s[:9] for s in xi.HTDF_TILE_CASES] + [xi.AFFINE_FAR_CASES[0][:9]] + [s[:9] for s in xi.EXTREME_CASES if s[0] in ("x_mc_checker2_base_b_8b", "x_htdf_qp32_cip_10b_ctu128")]
+
+
+@pytest.mark.parametrize("spec", _role_specs(), ids=[s[0] for s in _role_specs()])
+def test_inter_role_restatement_equals_the_builders_arrays(spec):
+    import cases
+    import mc_launch as ml
+    cs = cases.build_case(*spec)
+    work, items = ml.roles(cs["batch"], cs["w"], cs["h"])
+    assert len(work) == ((cs["w"] + 63) >> 6) * ((cs["h"] + 63) >> 6) and len(items) == 4 * len(work)
+    for threads in (1, 4):
+        got_work, got_items = ml.builder_lists(cs, threads)
+        assert np.array_equal(got_work, work), f"{threads} builder thread(s): roles of regions {np.nonzero(got_work != work)[0][:8].tolist()}"
+        assert np.array_equal(got_items, items), f"{threads} builder thread(s): items {np.nonzero(got_items != items)[0][:8].tolist()}"
+    # second check: digest 13 of xgpu_test_build_batch is the FNV-1a of the role array as it lies in the staging block
+    sp = abi.make_seq_params(cs["w"], cs["h"], cs["bd"], log2_ctu=cs["log2_ctu"], iqt=cs["iqt"], admvp=cs["admvp"], addb=cs["addb"], alf=cs["alf"], eipd=cs["eipd"])
+    cb, keep = abi.make_cu_batch(cs["batch"])
+    h = 1469598103934665603
+    for byte in work.astype("<u4").tobytes():
+        h = ((h ^ byte) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    assert _build(_lib(), sp, cb, 1)[-1] == f"{h:016x}"
+    # and every role the kernel reads an item for has one: a region entry four times the same CU, a tile-role wave a CU, the others none
+    for k, kinds in enumerate(work):
+        own = items[4 * k:4 * k + 4]
+        if kinds == ml.WORK_REGION:
+            assert own[0] != ml.NONE and (own == own[0]).all()
+        else:
+            assert all((own[q] != ml.NONE) == (((int(kinds) >> (2 * q)) & 3) == 1) for q in range(4))
+
+
+def test_inter_lists_shim_counts_and_refuses_too_little_room():
+    """xgpu_test_inter_lists: both arrays NULL asks for the count alone; one alone, or room for fewer regions than the picture has, is an invalid argument and writes nothing"""
+    import cases
+    import extreme_inputs as xi
+    cs = cases.build_case(*xi.MC_CASES[0][:9])
+    lib = abi.load()
+    sp = abi.make_seq_params(cs["w"], cs["h"], cs["bd"], log2_ctu=cs["log2_ctu"], iqt=cs["iqt"], admvp=cs["admvp"], addb=cs["addb"], alf=cs["alf"], eipd=cs["eipd"])
+    cb, keep = abi.make_cu_batch(cs["batch"])
+    n = C.c_int(0)
+    regions = ((cs["w"] + 63) >> 6) * ((cs["h"] + 63) >> 6)
+    assert lib.xgpu_test_inter_lists(C.byref(sp), C.byref(cb), 1, None, None, 0, C.byref(n)) == 0 and n.value == regions
+    work, items = (C.c_uint32 * regions)(*([0xA5A5A5A5] * regions)), (C.c_uint32 * (4 * regions))(*([0xA5A5A5A5] * (4 * regions)))
+    n.value = 0
+    assert lib.xgpu_test_inter_lists(C.byref(sp), C.byref(cb), 1, work, items, regions - 1, C.byref(n)) == -101 and n.value == regions
+    assert lib.xgpu_test_inter_lists(C.byref(sp), C.byref(cb), 1, work, None, regions, C.byref(n)) == -101
+    assert all(v == 0xA5A5A5A5 for v in work) and all(v == 0xA5A5A5A5 for v in items)

@@ -11,7 +11,10 @@ schemes, the right-column forms, 1 to 16 parts per CU; also with the residual pa
 16-lane body, twice on one decoder, and inside a tile grid with local dual trees), every branch of the residual pass (xi.RESIDUAL_CASES: levels aimed at each side of the
 dequantiser's clips, of the first stage's s16 clip and of the final clip, single levels in every row and column pair up to position 63, work items that mix dense and
 near-empty TBs, ATS on intra CUs and in ATS-inter TUs with and without IQT, every QP, sub-blocks that keep their CU's stride; also riding in the data-flow intra launch -
-k_intra_itdq's own copy of the body and tables - and twice on one decoder) - all three padded planes and the residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
+k_intra_itdq's own copy of the body and tables - and twice on one decoder), every role, window alignment and regime of k_inter's translational path (xi.MC_CASES: whole-region
+CUs, CUs of one or two tiles and CUs down to 4x4 with lists, vectors, flags and TUs in fixed cycles per role, between different noise references over a start picture unlike
+both - a chunk left out of a window by mistake reads samples that are wrong; also the SCU maps, the residual pass ahead, twice on one decoder and behind a picture of other
+content) - all three padded planes and the residual arena, bit-exact.  tests/test_oracle_extremes.py pins the oracle to the reference on the same cases and seeds; the census assertions (that the inputs
 reach the branches they are for) are repeated here because this file needs only the oracle, which always ships."""
 import numpy as np
 import pytest
@@ -277,6 +280,141 @@ def test_gpu_residual_cases_reach_every_branch():
     """the census assertions of tests/test_oracle_extremes.py over the residual cases together, repeated where only the oracle is needed"""
     it, by_bd, built = residual_census_together()
     check_residual_together(it, by_bd, built)
+
+
+# ---- translational motion compensation: the cases of xi.MC_CASES (every role, window alignment and regime of k_inter, test_mc_cases_together_reach_every_branch; the launch
+# side of their census is tests/mc_launch.py) - planes, residual arena and the tags' census under the default launch in test_gpu_extreme_case above, those with ADDB also in
+# test_gpu_extreme_case_scalar_deblocking.  Here the SCU maps, the other way of queueing the residual pass, and what a second picture finds in LDS and in the owner map.
+def _mc_expected(cs):
+    """the oracle's picture, residual arena and SCU maps (as the side-information export shows them) of a case"""
+    import side_info_ref as sr
+    ref, _, maps, rr = cases.run_cpu("oracle", cs)
+    return ref, rr, sr.blocks_from_maps(maps, maps.map_scu, cs["batch"], {k: p.poc for k, p in cs["refs"].items()}, cases.CUR_POC)
+
+
+def _mc_picture(dec, cur):
+    """what a decode left in picture `cur`: (SCU maps through the side-information export, padded planes)"""
+    got = dec.frame_side_info(cur).cpu().numpy()
+    return got, [np.array(p, copy=True) for p in dec.pic_download_padded(cur)]
+
+
+def _mc_same_maps(got, want, what):
+    from test_gpu_side_info import PLANE_NAMES
+    for p in range(len(PLANE_NAMES)):
+        assert np.array_equal(got[p], want[p]), f"{what}: map plane {PLANE_NAMES[p]}, first differences at 4x4 units {np.argwhere(got[p] != want[p])[:4].tolist()}"
+
+
+@pytest.mark.parametrize("spec", xi.MC_CASES, ids=[s[0] for s in xi.MC_CASES])
+def test_gpu_mc_case_scu_maps(spec):
+    """what k_inter's map update leaves per SCU - vectors (the unclipped ones), reference POC distances, mode with the skip flag, QP, luma cbf inside the ATS-inter TU only, CU
+    edges - through the side-information export, against the oracle's maps; and the planes of that decode"""
+    from test_gpu_side_info import decode, open_decoder, start
+    cs = cases.build_case(*spec[:9])
+    ref, _, want = _mc_expected(cs)
+    with open_decoder(cs) as dec:
+        slots, cur, hb = start(dec, cs)
+        decode(dec, cs, slots, cur, hb)
+        got, out = _mc_picture(dec, cur)
+    _mc_same_maps(got, want, spec[0])
+    _same(out, ref, spec[0])
+
+
+@pytest.mark.parametrize("spec", xi.MC_CASES, ids=[s[0] for s in xi.MC_CASES])
+def test_gpu_mc_case_residual_pass_ahead(spec):
+    """the residual pass queued with the previous picture's kernels (xgpu_batch_recon_ahead; what cases.run_gpu(ahead=True) does, the decoder left open): k_inter then finds
+    the whole residual arena written before it starts.  Planes, residual arena and SCU maps of the picture whose pass ran ahead, and of the one in front of it."""
+    from test_gpu_side_info import decode, open_decoder, start
+    cs = cases.build_case(*spec[:9])
+    ref, rr, want = _mc_expected(cs)
+    with open_decoder(cs) as dec:
+        slots, cur, hb = start(dec, cs)
+        hb2 = dec.batch_create(cs["batch"])
+        dec.decode_picture(cur, cases.CUR_POC, slots, hb, deblock=not cs.get("no_deblock"), pad=True, qp_u_offset=cases.QP_OFFSETS[0], qp_v_offset=cases.QP_OFFSETS[1],
+                           alpha_off=cs.get("alpha_off", 0), beta_off=cs.get("beta_off", 0), alf=cs.get("alf_params"), next_batch=hb2)
+        dec.sync()
+        got0, out0 = _mc_picture(dec, cur)
+        dec.pic_upload_padded(cur, cases._start_picture(cs).bufs)
+        decode(dec, cs, slots, cur, hb2)
+        dec.sync()
+        got, out = _mc_picture(dec, cur)
+        res = dec.batch_resid(hb2, cs["batch"]["n_coef"])
+    _mc_same_maps(got0, want, spec[0] + " (the picture in front)")
+    _same(out0, ref, spec[0] + " (the picture in front)")
+    assert np.array_equal(res[:len(rr)], rr), f"{spec[0]} (ahead): residual arena, first differences at {np.argwhere(res[:len(rr)] != rr)[:4].ravel().tolist()}"
+    _mc_same_maps(got, want, spec[0] + " (ahead)")
+    _same(out, ref, spec[0] + " (ahead)")
+
+
+@pytest.mark.parametrize("name", ["x_mcr_walk_main_10b", "x_mcr_thresholds_base_12b"])
+def test_gpu_mc_case_decoded_twice_on_one_decoder(name):
+    """one batch decoded twice into one picture of one decoder, the start picture uploaded again in between: the second decode's workgroups find the first one's windows in LDS
+    (what a chunk left out by mistake would read), the batch's owner map and items in place, and the picture's SCU maps filled - k_inter leaves the vector words of
+    DMVR-refined CUs to k_dmvr.  Planes and SCU maps after each decode."""
+    from test_gpu_side_info import decode, open_decoder, start
+    spec = next(s for s in xi.MC_CASES if s[0] == name)
+    cs = cases.build_case(*spec[:9])
+    ref, _, want = _mc_expected(cs)
+    seen = []
+    with open_decoder(cs) as dec:
+        slots, cur, hb = start(dec, cs)
+        for _ in range(2):
+            dec.pic_upload_padded(cur, cases._start_picture(cs).bufs)
+            decode(dec, cs, slots, cur, hb)
+            dec.sync()
+            seen.append(_mc_picture(dec, cur))
+    for (got, out), what in zip(seen, ("first decode", "second decode")):
+        _mc_same_maps(got, want, f"{name} ({what})")
+        _same(out, ref, f"{name} ({what})")
+
+
+@pytest.mark.parametrize("name", ["x_mcr_walk_main_8b_aligned", "x_mcr_walk_main_10b"])
+def test_gpu_mc_case_after_a_picture_of_other_content(name):
+    """a case decoded behind another picture of the same sequence (the same case drawn with another seed: other references, other vectors, other flags and TUs, its cycles
+    elsewhere) on one decoder, into the same picture slot, whose SCU maps that picture has just filled: planes and maps bit-identical to decoding it first, and the oracle's.
+    Both cases have all three roles; the second one has DMVR-flagged CUs, of whose map records k_inter writes a part only."""
+    from test_gpu_side_info import decode, open_decoder, start, upload_refs
+    spec = next(s for s in xi.MC_CASES if s[0] == name)
+    cs, other = cases.build_case(*spec[:9]), cases.build_case(*spec[:9], seed=1)
+    assert not np.array_equal(cs["batch"]["mv"], other["batch"]["mv"]) and not np.array_equal(cs["refs"][(0, 0)].bufs[0], other["refs"][(0, 0)].bufs[0])
+    ref, _, want = _mc_expected(cs)
+    ref_other, _, want_other = _mc_expected(other)
+    assert any(not np.array_equal(want[p], want_other[p]) for p in range(4)), "the two pictures' maps differ"
+    with open_decoder(cs) as dec:
+        slots, cur, hb = start(dec, cs)
+        decode(dec, cs, slots, cur, hb)
+        dec.sync()
+        first_maps, first = _mc_picture(dec, cur)
+    with open_decoder(cs) as dec:
+        slots = upload_refs(dec, other)
+        cur = dec.pic_alloc()
+        hb_other, hb = dec.batch_create(other["batch"]), dec.batch_create(cs["batch"])
+        dec.pic_upload_padded(cur, cases._start_picture(other).bufs)
+        decode(dec, other, slots, cur, hb_other)
+        dec.sync()
+        before_maps, before = _mc_picture(dec, cur)
+        by_obj = {}
+        for key, pic in cs["refs"].items():      # the same slots, the other pictures
+            if id(pic) not in by_obj:
+                by_obj[id(pic)] = slots[key][0]
+                dec.pic_upload_padded(slots[key][0], pic.bufs)
+            slots[key] = (by_obj[id(pic)], pic.poc)
+        dec.pic_upload_padded(cur, cases._start_picture(cs).bufs)
+        decode(dec, cs, slots, cur, hb)
+        dec.sync()
+        second_maps, second = _mc_picture(dec, cur)
+    _mc_same_maps(before_maps, want_other, name + " (the picture before)")
+    _same(before, ref_other, name + " (the picture before)")
+    for c in range(3):
+        assert np.array_equal(second[c], first[c]), f"plane {c}: decoded second differs from decoded first at {np.argwhere(second[c] != first[c])[:4].tolist()}"
+    assert np.array_equal(second_maps, first_maps), f"SCU maps: decoded second differs from decoded first in planes {sorted(set(np.argwhere(second_maps != first_maps)[:, 0].tolist()))}"
+    _mc_same_maps(second_maps, want, name + " (decoded second)")
+    _same(second, ref, name + " (decoded second)")
+
+
+def test_gpu_mc_cases_reach_every_branch():
+    """the census assertions of tests/test_oracle_extremes.py over the motion-compensation cases together, repeated where only the oracle is needed"""
+    from test_oracle_extremes import check_mc_together, mc_census_together
+    check_mc_together(*mc_census_together())
 
 
 # content kind x bit depth x partition depth per coding family.  split_prob low / high: k_inter's region and tile roles / its split role see the saturated windows

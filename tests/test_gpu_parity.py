@@ -40,6 +40,36 @@ def test_gpu_mc_blocks_golden(decs, fname):
         assert np.array_equal(out.ravel(), d["pred"][off:off + w * h]), (bd, admvp, luma, has_dx, has_dy, w, h, gx, gy)
 
 
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_gpu_mc_blocks_every_phase_pair_on_checkerboards(decs, bd):
+    """xgpu_test_mc_l / xgpu_test_mc_c against orc_mc_l / orc_mc_c (which tests/test_oracle_vs_ref.py pins to the reference's functions) on 0 / max checkerboards of period 1
+    and 2 - the largest overshoot the taps can produce, both rails of every clip: all 16 pairs of quarter-sample luma phases and all 64 pairs of eighth-sample chroma phases,
+    i.e. every row of both tap tables the translational path can index (the goldens above hold 12 .. 24 pairs per table and depth).  A whole-sample phase runs as a copy
+    and - what a vector whose fraction the MV clip removed takes - through the filter with the phase-0 row."""
+    import ctypes as C
+    import oracle_lib as ol
+    orc = ol.oracle()
+    maxv = (1 << bd) - 1
+    yy, xx = np.mgrid[0:96, 0:160]
+    walked = {(admvp, luma): set() for admvp in (0, 1) for luma in (0, 1)}
+    for period in (1, 2):
+        plane = np.ascontiguousarray((((xx // period) + (yy // period)) & 1) * maxv, np.int16)
+        for admvp in (0, 1):
+            for luma, w, h, prec, step in ((1, 8, 8, 4, 4), (0, 4, 4, 5, 4)):
+                n = 1 << prec
+                for fx in range(0, n, step):
+                    for fy in range(0, n, step):
+                        for has_dx in ((0, 1) if fx == 0 else (1,)):
+                            for has_dy in ((0, 1) if fy == 0 else (1,)):
+                                gx, gy = (40 << prec) + fx, (40 << prec) + fy      # sample 40 of a 160 x 96 plane: the window and whatever the loads round it up to stay inside
+                                got = decs[(admvp, 0)].test_mc(plane, 0, 0, has_dx, has_dy, gx, gy, w, h, bd, bool(luma))
+                                want = np.zeros((h, w), np.int16)
+                                (orc.orc_mc_l if luma else orc.orc_mc_c)(plane.ctypes.data_as(C.c_void_p), gx, gy, 160, w, want.ctypes.data_as(C.c_void_p), w, h, bd, has_dx, has_dy, admvp)
+                                assert np.array_equal(got, want), (bd, admvp, luma, period, fx, fy, has_dx, has_dy)
+                                walked[(admvp, luma)].add((fx, fy))
+    assert all(len(v) == (16 if luma else 64) for (admvp, luma), v in walked.items()), {k: len(v) for k, v in walked.items()}
+
+
 @pytest.mark.parametrize("fname", ["blocks_itdq.npz", "blocks_itdq_12b.npz"])
 def test_gpu_itdq_blocks_golden(decs, fname):
     d = np.load(os.path.join(golden_io.GOLDEN, fname))

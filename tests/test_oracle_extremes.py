@@ -84,6 +84,12 @@ turn and every QP).  Block level: the same generators through the reference's ow
 it_s2_undef.  The census over the cases (it_*), what is asserted empty or out of reach and why: profiles/residual_census.txt.  No intermediate reaches 2^27, let alone the
 2^28 the kernel's split allows; the hold of the 32-bit dequantiser cannot be told from half its value up to 12 bit.
 
+Translational motion compensation (xi.MC_CASES: nine pictures on mc_partition with lists, vectors, flags and TUs assigned in fixed cycles per role of k_inter - set_mv_mc,
+set_mc_coding).  Two censuses: the oracle's mc_* (tap rows, regimes, lists, shapes, edges, TUs) and the launch side of tests/mc_launch.py (roles, window alignments, left-out
+chunks, lane predicates under wave ballots), which restates the builder's role rule and is held to the builder's arrays in tests/test_builder.py.  Over the cases together every
+cell is reached or asserted 0 with its reason (check_mc_together); totals, what the older cases never reached and both mutation tables: profiles/mc_census.txt.  The
+identical-motion test "never true" changes no output - equal POCs are one picture, and the average of a prediction with itself is the prediction -; its two halves are caught.
+
 The census (which needs only the oracle) and the generator checks run everywhere; the comparison against the reference carries the `ref` mark and is skipped
 where oracle/_ref is not built, like tests/test_oracle_vs_ref.py.
 """
@@ -94,6 +100,7 @@ import pytest
 
 import cases
 import extreme_inputs as xi
+import mc_launch as ml
 import oracle_lib as ol
 import residual_inputs as ri
 
@@ -300,7 +307,78 @@ def _ip_clips(cen, cs):
     _all(cen["ip_plan_clip"], "planar samples clipped [at 0, at max]")
 
 
+def mc_launch_census(cs):
+    """the launch side of the motion-compensation census (tests/mc_launch.py), once per built case"""
+    if "_mc_launch" not in cs:
+        cs["_mc_launch"] = ml.census(cs)
+    return cs["_mc_launch"]
+
+
+def _mcr_roles(cen, cs):
+    lc = mc_launch_census(cs)
+    _all(lc["role"], "k_inter work units in the [region, tile, split] role")
+    _all(lc["role_lists"][:, 2], "CUs predicted from two lists in the [region, tile, split] role")
+    _all(lc["role_lists"][:, :2].sum(1), "CUs predicted from one list in the [region, tile, split] role")
+
+
+def _mcr_windows(cen, cs):
+    lc = mc_launch_census(cs)
+    for r, role in enumerate(("region", "tile")):      # both arrangements of the horizontal pass (odd = mis & 1), and what wanted() leaves out in every whole / fractional combination
+        for key, what in (("win_l", "luma"), ("win_c", "chroma")):
+            _all(lc[key][r].sum((1, 2)).reshape(4, 2).sum(0), f"{role} role, {what} windows at an [even, odd] alignment")
+            _all(lc[key][r].sum((0, 2)), f"{role} role, {what} windows with x [whole, fractional]")
+            _all(lc[key][r].sum((0, 1)), f"{role} role, {what} windows with y [whole, fractional]")
+
+
+def _mcr_lanes(cen, cs):
+    lc = mc_launch_census(cs)
+    _all(lc["lane_l"].sum(1), "split-role lanes in luma waves of every [H V] (the nine cells [wave][lane]: the cases together)")
+    _all(lc["lane_l"].sum(0), "split-role lanes by their own [fx fy]")
+    _all(lc["lane_c"].sum(1), "split-role lanes in chroma waves of every [H V]")
+    _all(lc["mixed_wave"], "split-role waves with [several CUs, one- and two-list CUs, lanes without a plain inter CU]")
+
+
+def _mcr_coding(cen, cs):
+    _all(cen["mc_cbf"], "plain inter CUs by cbf 0 .. 7")
+    _all([cen["mc_skip"]], "skipped CUs")
+    if cs["admvp"] and cs["iqt"]:
+        _all(cen["mc_tu"][1:], "plain inter CUs by ATS-inter idx 1 .. 4 x pos")
+        lc = mc_launch_census(cs)
+        _all(lc["role_tu"][:, 1:].sum(2)[lc["role"] > 0], "... every idx in each role the case has")
+
+
+def _mcr_second_list(cen, cs):
+    sl = mc_launch_census(cs)["second_list"]
+    _all(np.stack([sl[:, 0, 0] + sl[:, 1, 1], sl[:, 0, 1] + sl[:, 1, 0]], 1), "[region, tile] units whose two lists have [the same, another] luma fy")
+
+
+def _mcr_clip(cen, cs):
+    lc = mc_launch_census(cs)
+    _all(cen["mv_clip"], "vectors moved by the MV clip [left, right, top, bottom]")
+    _all(lc["role_clip"].sum(1), "... in the [region, tile, split] role")
+    _all(cen["mc_edge"][:, 1], "windows wholly over the picture's [left, right, top, bottom] edge")
+
+
+def _mcr_edges(cen, cs):
+    lc = mc_launch_census(cs)
+    _all(cen["mc_edge"][:, 0], "windows partly over the picture's [left, right, top, bottom] edge")
+    _all(lc["role_edge"].sum(0), "requests over the picture's [left, right, top, bottom] edge")
+    _all(lc["role_edge"].sum(1)[lc["role"] > 0], "... in each role the case has")
+
+
 REQUIRE = {
+    # translational motion compensation in k_inter's roles (xi.MC_CASES; what the cases reach together: test_mc_cases_together_reach_every_branch)
+    "mcr_roles": _mcr_roles,
+    "mcr_windows": _mcr_windows,
+    "mcr_lanes": _mcr_lanes,
+    "mcr_coding": _mcr_coding,
+    "mcr_second_list": _mcr_second_list,
+    "mcr_clip": _mcr_clip,
+    "mcr_edges": _mcr_edges,
+    "mcr_dmvr_fallback": lambda cen, cs: _all([cen["mc_dmvr_fallback"], cen["dmvr_not_refined"][0]], "DMVR-flagged CUs predicted by the translational path, two-list ones on references that are not POC-symmetric"),
+    "mcr_identical": lambda cen, cs: _all(cen["mc_lists"], "plain inter CUs using list 0, list 1, both, both collapsed by identical motion on equal POCs"),
+    "mcr_big": lambda cen, cs: _all([cen["mc_shape"][5].sum() + cen["mc_shape"][:, 5].sum()], "plain inter CUs with a side of 128"),
+    "mcr_ragged": lambda cen, cs: _all(mc_launch_census(cs)["partial_tile_big"], "tiles cut by the picture's [right, bottom] edge inside a CU of at least 32x32"),
     "ip_modes": _ip_modes,
     "ip_right": _ip_right,
     "ip_left_only": _ip_left_only,
@@ -478,6 +556,101 @@ def test_extreme_case_oracle_equals_reference(spec):
     assert np.array_equal(ma.map_refi, mb.map_refi) and np.array_equal(ma.map_mv, mb.map_mv)
     for c in range(3):
         assert np.array_equal(a.bufs[c], b.bufs[c]), f"final plane {c}: {np.argwhere(a.bufs[c] != b.bufs[c])[:4]}"
+
+
+def mc_census_together(specs=None):
+    """the oracle's mc_* census and the launch census (tests/mc_launch.py) of the motion-compensation cases, summed: -> (oracle side, launch side, [built case])"""
+    arith, launch, built = None, None, []
+    for spec in (xi.MC_CASES if specs is None else specs):
+        cs = cases.build_case(*spec[:9])
+        _, cen = run_oracle_with_census(cs)
+        lc = mc_launch_census(cs)
+        # the two sides agree on which CUs take this path and from which lists: the restatement of "plain", of the clip and of the identical-motion test holds
+        assert lc["n_plain"] == cen["mc_shape"].sum() and np.array_equal(lc["lists"], cen["mc_lists"]), (spec[0], lc["n_plain"], lc["lists"].tolist(), cen["mc_lists"].tolist())
+        cen = {k: np.asarray(v) for k, v in cen.items() if k.startswith("mc_") or k in ("mv_clip", "dmvr_not_refined")}
+        lc = {k: np.asarray(v) for k, v in lc.items()}
+        arith = cen if arith is None else {k: arith[k] + cen[k] for k in cen}
+        launch = lc if launch is None else {k: launch[k] + lc[k] for k in lc}
+        built.append(cs)
+    return arith, launch, built
+
+
+def check_mc_together(a, lc, built):
+    """every cell of the two censuses over xi.MC_CASES: reached, or unreachable - asserted 0, with the reason"""
+    for tab in range(2):      # every row of k_luma_taps / k_chroma_taps this path can index, in both tables (the Baseline tables hold a filter for each quarter / eighth sample too)
+        _all(a["mc_phase"][tab], f"luma quarter-sample phases [fx][fy], {('Baseline', 'Main')[tab]} table")
+        _all(a["mc_cphase"][tab], f"chroma eighth-sample phases [fx][fy], {('Baseline', 'Main')[tab]} table")
+    _all(a["mc_regime"], "[luma, chroma] x [copy, vertical, horizontal, 2-D]")
+    _all(a["mc_luma_whole_chroma_half"], "luma whole, chroma half [x, y]")
+    _all(a["mc_lists"], "list 0 only, list 1 only, both, both collapsed by identical motion")
+    # The reference index only selects an entry of the picture table (s_ref[index * 2 + list]): cases.POCS gives a case two pictures in list 0 and three in list 1 -
+    # index 2 of list 1 is list 0's index 0, the pair with equal POCs.  The entries beyond hold no picture in these cases.
+    _all(a["mc_refi"][0][:2], "list 0 indices 0, 1")
+    _all(a["mc_refi"][1][:3], "list 1 indices 0, 1, 2")
+    assert a["mc_refi"][0][2:].sum() == 0 and a["mc_refi"][1][3:].sum() == 0
+    # 4x128 and 128x4: no split tree makes them (a binary cut is allowed up to a ratio of 1 : 4, a ternary one only across the longer side - check_intra_empty has the
+    # lines of the reference), and mc_partition has no such shape
+    shape_ok = np.ones((6, 6), bool)
+    shape_ok[0, 5] = shape_ok[5, 0] = False
+    _all(a["mc_shape"][shape_ok], "plain inter CUs of every shape of 4 .. 128 a side")
+    assert a["mc_shape"][~shape_ok].sum() == 0
+    _all(a["mc_edge"], "luma windows over the picture's [left, right, top, bottom] edge [partly, wholly]")
+    _all(a["mc_tu"][1:], "ATS-inter idx 1 .. 4 x pos")
+    # a position without an index: ats_inter_info is idx | pos << 4 and idx 0 means no TU - set_mc_coding writes a position only with an index, as the parser does
+    assert a["mc_tu"][0][0] > 0 and a["mc_tu"][0][1] == 0
+    _all(a["mc_cbf"], "cbf 0 .. 7")
+    _all([a["mc_skip"], a["mc_dmvr_fallback"], a["dmvr_not_refined"][0]], "skipped CUs, DMVR-flagged CUs predicted here, two-list ones on references that are not POC-symmetric")
+    _all(a["mv_clip"], "vectors moved by the clip")
+    # ---- the launch side
+    _all(lc["role"], "units by role")
+    _all(lc["role_lists"], "[role] x lists")
+    # A region (a tile) lies inside one CU only if the CU is at least 64 (32) a side; mc_partition's CUs of 64 and more a side lie on the 64 grid inside the picture, so
+    # they are whole regions and leave nothing to the other roles - but for the CUs of 32x32, 32x64 and 64x32 that a ternary cut puts at an offset of 16 into the ragged
+    # edge of x_mcr_edges_main_8b_ragged (split role) - and CUs of 32 a side on the 32 grid are whole tiles
+    region_ok, tile_ok, split_ok = np.zeros((6, 6), bool), np.zeros((6, 6), bool), shape_ok.copy()
+    region_ok[4:, 4:] = True
+    tile_ok[3:, 3:] = True
+    tile_ok[4:, 4:] = False
+    split_ok[3:, 3:] = False
+    split_ok[3, 3] = split_ok[3, 4] = split_ok[4, 3] = True
+    for r, ok in enumerate((region_ok, tile_ok, split_ok)):
+        _all(lc["role_shape"][r][ok], f"CU shapes of role {r}")
+        assert lc["role_shape"][r][~ok].sum() == 0, (r, lc["role_shape"][r].tolist())
+    _all(lc["win_l"], "[region, tile] x [mis][fx][fy]")
+    _all(lc["win_c"], "[region, tile] x [cmis][cfx][cfy]")
+    _all(lc["second_list"], "[region, tile] x [list 0 fy][list 1 fy]")
+    # a lane that filters in a direction makes the ballot of its wave true: lane & ~wave != 0 cannot be
+    ok = np.array([[(lane & ~wave) == 0 for lane in range(4)] for wave in range(4)])
+    _all(lc["lane_l"][ok], "split-role lanes [wave][lane], luma")
+    _all(lc["lane_c"][ok], "split-role lanes [wave][lane], chroma")
+    assert lc["lane_l"][~ok].sum() == 0 and lc["lane_c"][~ok].sum() == 0
+    _all(lc["mixed_wave"], "mixed waves")
+    _all(lc["partial_tile"], "tiles cut by the picture's [right, bottom] edge")
+    _all(lc["partial_tile_big"], "... inside a CU of at least 32x32")
+    _all(lc["role_clip"], "[role] x vectors moved by the clip [left, right, top, bottom]")
+    _all(lc["role_edge"], "[role] x requests over the picture's [left, right, top, bottom] edge")
+    _all(lc["role_tu"][:, 1:], "[role] x ATS-inter idx 1 .. 4 x pos")
+    assert (lc["role_tu"][:, 0, 0] > 0).all() and lc["role_tu"][:, 0, 1].sum() == 0      # (as mc_tu[0][1])
+    _all(lc["role_cbf"], "[role] x cbf")
+    _all(lc["role_skip"], "[role] skipped CUs")
+    # the cycles of the region and tile role go on from case to case where the one before stopped (xi.mc_chain_start)
+    at = np.zeros(4, np.int64)
+    for spec, cs in zip(xi.MC_CASES, built):
+        assert tuple(at) == tuple(cs["mc_at"]), (spec[0], at.tolist(), cs["mc_at"])
+        at += cs["mc_taken"]
+    assert ml.CUR_POC == cases.CUR_POC
+    tools = {(spec[3], spec[4], spec[8].get("log2_ctu", 6)) for spec in xi.MC_CASES}
+    assert {t[:2] for t in tools} >= {(bd, tab) for bd in (8, 10, 12) for tab in (0, 1)} and {t[1:] for t in tools} == {(tab, ctu) for tab in (0, 1) for ctu in (6, 7)}
+    assert {(spec[8].get("addb", 0), spec[8].get("alf", 0)) for spec in xi.MC_CASES} >= {(0, 0), (1, 0), (1, 1)}
+    assert all(spec[1] <= 264 and spec[2] <= 264 and spec[9] for spec in xi.MC_CASES)
+
+
+def test_mc_cases_together_reach_every_branch():
+    """the conditions the motion-compensation cases were chosen for, over all of them (profiles/mc_census.txt holds this test's output)"""
+    a, lc, built = mc_census_together()
+    for k, v in list(a.items()) + list(lc.items()):
+        print(k, np.asarray(v).tolist())
+    check_mc_together(a, lc, built)
 
 
 def dmvr_census_together():

@@ -413,7 +413,7 @@ void batch_info_fill(const xgpu_dbatch *db, int info[XGPU_BATCH_INFO_COUNT])
     info[0] = db->n_cu; info[1] = db->n_tb; info[2] = db->n_waves; info[3] = db->n_intra; info[4] = db->n_intra_l1; info[5] = db->n_levels; info[6] = db->n_dmvr; info[7] = db->n_aff_eif + db->n_aff_sub;
 }
 // host_only (xgpu_test_build_batch): everything but the device - the staging block is the caller's scratch, nothing is uploaded; *layout receives where the arrays lie
-int batch_build(xgpu_ctx *c, const xgpu_cu_batch *b, xgpu_dbatch **out, bool host_only, StageLayout *layout)
+int batch_build(xgpu_ctx *c, const xgpu_cu_batch *b, xgpu_dbatch **out, bool host_only, StageLayout *layout, const BuilderScratch **scratch_out = nullptr)
 {
     ARGCHK(c, c != NULL); ARGCHK(c, b != NULL && out != NULL);
     *out = NULL;
@@ -432,6 +432,7 @@ int batch_build(xgpu_ctx *c, const xgpu_cu_batch *b, xgpu_dbatch **out, bool hos
     const int n = b->n_cu;
     Build B = { c, b, scratch, n, std::max(1, std::min(c->builder_threads, std::max(1, n / 4096))) };
     BuilderScratch &S = B.S; const IntraPlan &plan = S.plan;
+    if (scratch_out) *scratch_out = &scratch;      // (xgpu_test_inter_lists: the calling thread's own object, valid until its next build)
     if (const int rc = B.pass1()) return rc;
     BT("pass 1");
     B.paint_owner_map();
@@ -515,6 +516,38 @@ int xgpu_test_build_batch(const xgpu_seq_params *sp, const xgpu_cu_batch *b, int
             digest[k] = h;
         }
         if (info) batch_info_fill(db, info);
+        xgpu_batch_destroy(c, db);
+    }
+    delete c;
+    return rc;
+}
+
+// Test shim (no device, no HIP call), beside xgpu_test_build_batch: the two arrays inter_work_lists() leaves for k_inter, copied out as they are - work[k]: the roles of
+// region k in strip order, items[4 * k + q]: the CU the whole tile q of region k lies in (0xFFFFFFFF: none).  *n_work receives the number of regions; with
+// work == items == NULL only the count is returned; one of them alone, or room for fewer than that many regions (cap_work), is an invalid argument (the count is still returned).  tests/mc_launch.py holds its restatement of the role rule to these arrays.
+int xgpu_test_inter_lists(const xgpu_seq_params *sp, const xgpu_cu_batch *b, int threads, uint32_t *work, uint32_t *items, int cap_work, int *n_work)
+{
+    if (!sp || !b || !n_work || threads < 1 || threads > 64 || (work == NULL) != (items == NULL) || cap_work < 0) return XGPU_ERR_INVALID_ARGUMENT;
+    if (sp->width <= 0 || sp->height <= 0 || (sp->width & 7) || (sp->height & 7) || sp->log2_ctu < 5 || sp->log2_ctu > 7) return XGPU_ERR_INVALID_ARGUMENT;
+    xgpu_ctx *c = new xgpu_ctx();
+    c->sp = *sp; c->sp.chroma_qp_table[0] = c->sp.chroma_qp_table[1] = NULL;
+    c->builder_threads = threads; c->err[0] = 0;
+    c->stream = c->up_stream = c->down_stream = c->side_stream = 0;
+    ctx_geometry(c);
+    xgpu_dbatch *db = NULL;
+    StageLayout L;
+    const BuilderScratch *S = nullptr;
+    int rc = batch_build(c, b, &db, true, &L, &S);
+    if (rc == XGPU_OK) {
+        const size_t n = S->inter_work.size();
+        *n_work = (int)n;
+        if (work) {
+            if ((size_t)cap_work < n || S->inter_items.size() != 4 * n) rc = XGPU_ERR_INVALID_ARGUMENT;      // too little room: the count is returned, nothing is written
+            else {
+                memcpy(work, S->inter_work.data(), n * sizeof(uint32_t));
+                memcpy(items, S->inter_items.data(), 4 * n * sizeof(uint32_t));
+            }
+        }
         xgpu_batch_destroy(c, db);
     }
     delete c;
