@@ -597,6 +597,73 @@ int    xgpu_pic_output_device_dithered(xgpu_ctx *ctx, int pic, const xgpu_dra_lu
 int    xgpu_pic_output_device_packed_dithered(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f,
                                               const xgpu_colour_transform *cm /* NULL: none */, const xgpu_dither_params *dp, void *d_dst, size_t dst_size,
                                               void *stream);
+/* ---- overlaid output (k_output_overlay.hip): the integer forms of the RGB layouts, of NV12 / P016 and of the packed RGBA / RGB10A2 surfaces with a list of
+   layers - bitmaps in device memory, boxes from the host, boxes a detector left in device memory - alpha-blended over the plain call's picture, in the output's
+   own code domain, all in integers.  Calls of their own: every other call keeps its kernels and its bits.  INTEGRATION.md section 8s is the contract;
+   tests/overlay_ref.py restates it in numpy.
+     positions   cropped destination coordinates (the W x H image the call writes); they may be negative or beyond the image, what falls outside is clipped
+     per pixel   a layer yields a colour (R, G, B in 0 .. 255) and an alpha A8:
+                 RGBA8 / BGRA8   the bitmap's pixel (straight alpha)
+                 A8              colour's RGB, A8 = (m * colour[3] + 127) / 255 with m the mask byte
+                 BOX             a pixel of the unclipped rectangle whose distance to the nearest side (0 at the side) is below `thickness` takes `colour`,
+                                 every other pixel of it `fill` (fill alpha 0: nothing)
+                 effective alpha a = (A8 * opacity + 127) / 255; every division is a floor division of non-negative integers
+     order       the device boxes in index order, then the host layers in list order, each onto the result of those before it
+     blend       M = the element maximum (255 for U8, 2^D - 1 for U16 at depth D, 1023 for 10:10:10:2), v = the plain call's element or the previous layer's
+                 result; a == 0: the element is left alone; else cD = (c8 * M + 127) / 255, out = (min(max(v, 0), M) * (255 - a) + cD * a + 127) / 255.
+                 The A element of RGBA and the two alpha bits of 10:10:10:2 stay the call's constant; bgr swaps the layer's colour as it swaps the picture's;
+                 no transform is applied to a layer: its colour is a code of the destination
+     NV12/P016   blend in Y'CbCr on the D-bit sample, before P016's left shift.  The colour goes through the forward matrix of the format's matrix / full_range
+                 (xgpu_overlay_coeffs): S = 28 - D, m[i][j] = round(k[i][j] * range_i / 255 * 2^S), range = 219 << (D - 8) (luma), 224 << (D - 8) (chroma) or
+                 2^D - 1 (full range); component = offset_i + ((m[i] . (R, G, B) + 2^(S-1)) >> S) clipped to [0, M].  Luma blends as above.  Chroma sample (j, i)
+                 covers luma pixels (2j .. 2j+1, 2i .. 2i+1); per layer A = the sum of the four a, C = the sum of a_k * c_k (c_k: the converted chroma of pixel
+                 k), out = (min(max(v, 0), M) * (1020 - A) + C + 510) / 1020; A == 0 leaves the sample alone; Cb and Cr share A.
+     device boxes (xgpu_overlay_boxes, optional): `capacity` boxes of box_format at d_boxes, the live ones the first min(max(*d_count, 0), capacity) (d_count NULL:
+                 all).  Snapping (xgpu_overlay_box_snap): XYWH_I32 - skipped if w < 1 or h < 1, else [clamp(x), clamp(x + w)) and y alike, clamp to +-2^20;
+                 XYXY_F32 - skipped if a coordinate is not finite, else each clamped to +-2^20, x0 = (int)floorf(x1), x1' = (int)ceilf(x2), y alike; skipped if
+                 empty.  Box i is a BOX layer of opacity 255 with colour palette[((label % n) + n) % n] (label 0 without d_labels), fill the same RGB with
+                 fill_alpha.  The host reads none of the arrays; the call does not synchronise.  Bitmaps and boxes are read on `stream`.
+   The two output calls take the plain calls' format, destination, stream and ordering.  Refusals, all before anything is queued, in this order: the plain call's,
+   with its codes; a float dtype: XGPU_ERR_UNSUPPORTED; a layout outside RGB planar / interleaved, NV12, P016, RGBA, RGB10A2: XGPU_ERR_INVALID_ARGUMENT; a
+   transform with NV12 / P016: XGPU_ERR_INVALID_ARGUMENT (then the transform's own refusals; for NV12 / P016 a matrix outside the supported list:
+   XGPU_ERR_UNSUPPORTED, full_range outside 0 / 1: XGPU_ERR_INVALID_ARGUMENT); then the layers: more than XGPU_MAX_OVERLAY_LAYERS, an unknown kind, a size,
+   position, opacity, thickness, pitch, n_palette, capacity, box_format or fill_alpha outside its range, a bitmap or box pointer that is NULL or misaligned:
+   XGPU_ERR_INVALID_ARGUMENT.  xgpu_output_overlay_check (host only; exactly one of f and pf is not NULL) returns 0 or that code and does not look at the
+   pointers' memory; the calls also refuse a bitmap that is not (height - 1) * pitch + width * bpp bytes of device memory of the context's device, and box arrays
+   that are not device memory of it. */
+#define XGPU_MAX_OVERLAY_LAYERS 16
+#define XGPU_MAX_OVERLAY_BOXES  256
+#define XGPU_OVL_RGBA8 0   /* bitmap, 4 bytes per pixel R G B A, straight alpha */
+#define XGPU_OVL_BGRA8 1   /* bitmap, B G R A */
+#define XGPU_OVL_A8    2   /* bitmap, 1 byte per pixel: coverage of `colour` (text, glyphs, subtitle masks) */
+#define XGPU_OVL_BOX   3   /* no pixels: a frame `thickness` wide in `colour`, interior in `fill` */
+typedef struct xgpu_overlay_layer {
+    int kind, x, y, width, height;      /* |x|, |y| <= 1 << 20; width, height 1 .. 16384 */
+    int opacity;                        /* 0 .. 255, multiplies every alpha of the layer */
+    const void *d_pixels; size_t pitch; /* bitmaps: device memory of the context's device; pitch 0 = tight; RGBA8 / BGRA8: pointer and pitch multiples of 4 */
+    uint8_t colour[4], fill[4];         /* R G B A.  A8: colour; BOX: frame colour and interior (fill alpha 0 = none) */
+    int thickness;                      /* BOX: >= 1 */
+} xgpu_overlay_layer;
+typedef struct xgpu_overlay_boxes {
+    int box_format;                     /* XGPU_BOX_XYWH_I32 or XGPU_BOX_XYXY_F32 */
+    const void *d_boxes;                /* capacity boxes of 16 bytes, aligned to 4 */
+    int capacity;                       /* 1 .. XGPU_MAX_OVERLAY_BOXES */
+    const int32_t *d_count;             /* or NULL: all of them */
+    const int32_t *d_labels;            /* one per box, or NULL: label 0 */
+    uint8_t palette[16][4]; int n_palette;      /* R G B A; 1 .. 16 */
+    int thickness;                      /* >= 1 */
+    int fill_alpha;                     /* 0 .. 255, 0 = no interior */
+} xgpu_overlay_boxes;
+int    xgpu_overlay_coeffs(const xgpu_output_format *f /* NV12 / P016 */, int bit_depth, int32_t m[9], int32_t offsets[3], int *shift);
+int    xgpu_overlay_box_snap(int box_format, const void *box, int rect[4] /* x0, y0, x1, y1 */);      /* 1: live, 0: skipped, or a negative code */
+int    xgpu_output_overlay_check(const xgpu_output_format *f, const xgpu_packed_format *pf, const xgpu_colour_transform *cm, const xgpu_overlay_layer *layers,
+                                 int n_layers, const xgpu_overlay_boxes *boxes, int width, int height, int bit_depth);
+int    xgpu_pic_output_device_overlaid(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f,
+                                       const xgpu_colour_transform *cm /* NULL: none */, const xgpu_overlay_layer *layers, int n_layers,
+                                       const xgpu_overlay_boxes *boxes /* NULL: none */, void *d_dst, size_t dst_size, void *stream);
+int    xgpu_pic_output_device_packed_overlaid(xgpu_ctx *ctx, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f,
+                                              const xgpu_colour_transform *cm /* NULL: none */, const xgpu_overlay_layer *layers, int n_layers,
+                                              const xgpu_overlay_boxes *boxes /* NULL: none */, void *d_dst, size_t dst_size, void *stream);
 /* ---- regions of interest from device memory (k_output_rois_dev.hip): xgpu_pic_output_device_rois for boxes that a detector left on the GPU.  d_boxes points
    to `capacity` boxes in device memory (1 .. XGPU_MAX_ROIS), d_count (may be NULL: all of them) to a device int32 - the live boxes are the first
    min(max(*d_count, 0), capacity).  The host reads neither; the call does not synchronise and nothing comes back to the host.  Descriptors and tap tables are

@@ -88,7 +88,11 @@ dithered call with the plain call of the same layout, which reads and writes the
 tone curve, NV12 u8, and 10:10:10:2 from a 12-bit picture (a second decoder; the other legs' depth is --bit-depth).  RGB u8 runs Bayer 8, blue 64 and blue 128
 side by side, the others blue 64.  Then the torch route the call replaces: the full-size f32 tensor, plus a tiled threshold tensor, floor, clamp and to(uint8).
 
-    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|resampled|rois|rois_dev|ladder|warp|remap|residual|compare|stats|packed|lut3d|dither] [--out out/output_device.json]
+The overlay leg (xgpu_pic_output_device_overlaid / _packed_overlaid: k_output_overlay_rgb / k_output_overlay_semiplanar) alternates, in one run per layout, the
+plain call with the overlaid call over no layer, a 512 x 256 logo, a full-size BGRA subtitle plane that is 95 % transparent, and 16 / 64 / 256 boxes read from
+device memory; then the torch routes on the written RGB tensor that the calls replace (slice and blend; boxes.cpu() and a loop of slices).
+
+    python tools/bench_output_device.py [--width 7680 --height 4320 --bit-depth 10 --iters 100] [--legs all|full|scaled|scaled_cm|scaled_lin|resampled|rois|rois_dev|ladder|warp|remap|residual|compare|stats|packed|lut3d|dither|overlay] [--out out/output_device.json]
 """
 import argparse
 import itertools
@@ -640,6 +644,89 @@ def dither_leg(torch, dec, pic, s, a, res, copy_gbps):
     dec.dither_destroy(hd)
 
 
+def overlay_leg(torch, dec, pic, s, a, res, copy_gbps):
+    """the overlaid calls beside the plain calls of the same layout in the same run - no layer, a logo, a full-size subtitle plane,
+    16 / 64 / 256 boxes from device memory - and the torch routes they replace"""
+    w, h = a.width, a.height
+    to_srgb = dict(src_primaries=9, src_transfer=16, dst_primaries=1, dst_transfer=13, tone_map=True)
+    u8 = torch.uint8
+    rng = np.random.default_rng(31)
+    logo = torch.from_numpy(rng.integers(0, 256, (min(256, h), min(512, w), 4)).astype(np.uint8)).to("cuda:0")
+    plane = np.zeros((h, w, 4), np.uint8)      # subtitles: 95 % of the plane transparent, two opaque-ish bands of text-like coverage near the bottom
+    band = slice(h - h // 20, h)
+    plane[band, :, :3] = 255
+    plane[band, :, 3] = rng.integers(0, 256, (h // 20, w)).astype(np.uint8)
+    plane = torch.from_numpy(plane).to("cuda:0")
+    res["overlay"] = {"copy_gbps": copy_gbps, "cases": {}}
+    sets = {"none": dict(layers=[]), "logo_512x256": dict(layers=[dict(image=logo, x=w - logo.shape[1] - 64, y=64)]),
+            "subtitle_plane_bgra": dict(layers=[dict(image=plane, order="bgra")])}
+    pal = [(255, 0, 0, 255), (0, 255, 0, 255), (0, 0, 255, 255), (255, 255, 0, 255)]
+    box_arrays = {}
+    for n in (16, 64, 256):
+        bx = np.stack([rng.integers(0, w - 64, n), rng.integers(0, h - 64, n), rng.integers(32, max(w // 8, 64), n), rng.integers(32, max(h // 8, 64), n)], axis=1).astype(np.int32)
+        box_arrays[n] = torch.from_numpy(bx).to("cuda:0")
+        sets[f"boxes_{n}"] = dict(boxes=dict(tensor=box_arrays[n], count=torch.tensor([n], dtype=torch.int32, device="cuda:0"),
+                                             labels=torch.from_numpy(rng.integers(0, 4, n).astype(np.int32)).to("cuda:0"), palette=pal, thickness=4, fill_alpha=0))
+
+    def run(name, plain, kw, wbytes):
+        routes = {"plain": (lambda o=plain(pic, **kw): plain(pic, out=o, **kw))}
+        for k, ov in sets.items():
+            routes[k] = (lambda ov=ov, o=dec.pic_output_overlaid(pic, **ov, **kw): dec.pic_output_overlaid(pic, out=o, **ov, **kw))
+        r = alternated(torch, s, routes, a.iters)
+        nbytes = int(w * h * (3 + wbytes))
+        for k in routes:
+            r[k].update(gbps=round(nbytes / (r[k]["us"] * 1e-6) / 1e9, 1))
+        for k in sets:
+            r[k]["time_ratio"] = round(r[k]["us"] / r["plain"]["us"], 3)
+            r[k]["above_plain_p90"] = bool(r[k]["us"] > r["plain"]["p90_us"])
+        r["bytes"] = nbytes
+        res["overlay"]["cases"][name] = r
+        print(f"overlay {name:24s} " + "  ".join(f"{k} {v['us']:7.1f} us ({v['p10_us']:.1f} - {v['p90_us']:.1f})" for k, v in r.items() if isinstance(v, dict)))
+
+    run("rgb_u8", dec.pic_output_tensor, dict(layout="rgb", channels_last=True, dtype=u8), 3)
+    run("rgba_u8", dec.pic_output_packed, dict(layout="rgba", dtype=u8), 4)
+    run("rgba_u8_cm_pq2020_srgb", dec.pic_output_packed, dict(layout="rgba", dtype=u8, matrix=9, colour=to_srgb), 4)
+    run("nv12_u8", dec.pic_output_tensor, dict(layout="nv12", dtype=u8), 1.5)
+    run("p010", dec.pic_output_tensor, dict(layout="p016", dtype=torch.int16, out_bit_depth=10), 3)
+
+    # the routes a user has without the calls, on the interleaved RGB u8 tensor: slice and blend in float (logo, subtitle plane); boxes.cpu() and a loop of slices
+    out = dec.pic_output_tensor(pic, layout="rgb", channels_last=True, dtype=u8)
+    kw = dict(layout="rgb", channels_last=True, dtype=u8)
+
+    def blend(img, x, y):
+        hh, ww = img.shape[:2]
+        dst = out[y:y + hh, x:x + ww].to(torch.float32)
+        al = img[..., 3:4].to(torch.float32) / 255.0
+        out[y:y + hh, x:x + ww] = (dst * (1.0 - al) + img[..., :3].to(torch.float32) * al + 0.5).to(u8)
+
+    def torch_logo():
+        dec.pic_output_tensor(pic, out=out, **kw)
+        blend(logo, w - logo.shape[1] - 64, 64)
+
+    plane_rgba = plane[..., (2, 1, 0, 3)].contiguous()
+
+    def torch_plane():
+        dec.pic_output_tensor(pic, out=out, **kw)
+        blend(plane_rgba, 0, 0)
+
+    def torch_boxes(n):
+        dec.pic_output_tensor(pic, out=out, **kw)
+        col = torch.tensor(pal, dtype=u8, device="cuda:0")[:, :3]
+        for i, (x, y, bw, bh) in enumerate(box_arrays[n].cpu().tolist()):      # the round trip the device-box call avoids
+            x1, y1, c = min(x + bw, w), min(y + bh, h), col[i & 3]
+            out[y:y + 4, x:x1] = c; out[max(y1 - 4, y):y1, x:x1] = c; out[y:y1, x:x + 4] = c; out[y:y1, max(x1 - 4, x):x1] = c
+
+    o2 = dec.pic_output_overlaid(pic, **kw)
+    routes = {"call_logo": lambda: dec.pic_output_overlaid(pic, out=o2, **sets["logo_512x256"], **kw), "torch_logo": torch_logo,
+              "call_plane": lambda: dec.pic_output_overlaid(pic, out=o2, **sets["subtitle_plane_bgra"], **kw), "torch_plane": torch_plane}
+    for n in (16, 64, 256):
+        routes[f"call_boxes_{n}"] = lambda n=n: dec.pic_output_overlaid(pic, out=o2, **sets[f"boxes_{n}"], **kw)
+        routes[f"torch_boxes_{n}"] = lambda n=n: torch_boxes(n)
+    rt = alternated(torch, s, routes, max(a.iters // 10, 5), warm=2)
+    res["overlay"]["torch_routes_rgb_u8"] = rt
+    print("overlay torch routes: " + "  ".join(f"{k} {v['us']:.1f} us (host {v['host_us']:.1f})" for k, v in rt.items()))
+
+
 def ladder_leg(torch, dec, pic, s, a, res):
     """the picture to P010 rungs 3840x2160, 1920x1080, 1280x720 and 640x360 (those inside the scaled output's limits for the picture): the one call
     (pic_output_surfaces) against four one-rung calls, against the route without it - the full-size P010 surface, then per rung and plane
@@ -1075,11 +1162,11 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=3, help="residual leg: runs of the whole measurement in this process")
-    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "resampled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats", "packed", "lut3d", "dither"), default="all",
+    ap.add_argument("--legs", choices=("all", "full", "scaled", "scaled_cm", "scaled_lin", "resampled", "rois", "rois_dev", "ladder", "warp", "remap", "residual", "compare", "stats", "packed", "lut3d", "dither", "overlay"), default="all",
                     help="full: the full-size forms and the side information; scaled: the scaled leg alone; scaled_cm: the colour-managed scaled output alone; scaled_lin: the scaled output filtered in linear light alone; resampled: the bicubic resize alone; rois: the batched regions of interest alone; "
                          "rois_dev: the regions of interest from boxes in device memory alone; ladder: the ladder of scaled P010 surfaces alone; warp: the warped regions of interest alone; remap: the remapped output alone; residual: the residual "
                          "export alone; compare: the picture comparison alone; stats: the picture statistics alone; packed: the packed display surfaces alone; "
-                         "lut3d: the 3D LUT outputs alone; dither: the dithered outputs alone")
+                         "lut3d: the 3D LUT outputs alone; dither: the dithered outputs alone; overlay: the overlaid outputs alone")
     a = ap.parse_args()
     import torch
     from xevd_amd.decoder import XgpuDecoder
@@ -1131,6 +1218,8 @@ def main():
             lut3d_leg(torch, dec, pic, s, a, res, copy_gbps, planes)
         if a.legs in ("all", "dither"):
             dither_leg(torch, dec, pic, s, a, res, copy_gbps)
+        if a.legs in ("all", "overlay"):
+            overlay_leg(torch, dec, pic, s, a, res, copy_gbps)
         if a.legs in ("all", "ladder"):
             ladder_leg(torch, dec, pic, s, a, res)
         if a.legs in ("all", "warp"):

@@ -150,6 +150,10 @@ def main():
                     "8r): with --pix-fmt nv12 / p010 / rgba / bgra / x2bgr10le / x2rgb10le, or with --to (8-bit RGB); not with --lut, --size or --ladder")
     ap.add_argument("--dither-size", type=int, default=None, metavar="N", help="with --dither: the side of the matrix, a power of two (default: bayer 8, blue 64)")
     ap.add_argument("--dither-temporal", action="store_true", help="with --dither: move the matrix from picture to picture (xgpu_dither_phase of the POC)")
+    ap.add_argument("--overlay", action="append", default=None, metavar="FILE.npy:X:Y[:OPACITY]", help="blend this bitmap over every picture on the device (INTEGRATION.md "
+                    "8s), repeatable, in the order given: an [h, w, 4] uint8 RGBA array with straight alpha, its top left corner at (X, Y) of the picture (either may be "
+                    "negative), OPACITY 0 .. 255 (default 255); with --pix-fmt nv12 / p010 / rgba / bgra / x2bgr10le / x2rgb10le, with --to, or alone (interleaved 8-bit "
+                    "RGB frames); not with --dither, --lut, --size or --ladder")
     ap.add_argument("--side-info", default=None, metavar="FILE", help="also write the coding side information of every picture, in DECODING order: a text line "
                     "'POC h_scu w_scu', then nine planes of h_scu x w_scu little-endian int16 (list 0 / 1 vectors, POC distances, mode, QP, flags: INTEGRATION.md 8c)")
     ap.add_argument("--residual", default=None, metavar="FILE", help="also write the prediction residual of every picture, in DECODING order: a text line "
@@ -197,6 +201,34 @@ def main():
         dith = dict(dither=dict(kind=args.dither, size=args.dither_size or (8 if args.dither == "bayer" else 64), temporal=args.dither_temporal))
     elif args.dither_size is not None or args.dither_temporal:
         ap.error("--dither-size, --dither-temporal: need --dither")
+    ovl = {}
+    if args.overlay:
+        import numpy as np
+        import torch
+        if args.dither is not None or args.lut is not None or args.size is not None or args.ladder is not None:
+            ap.error("--overlay: the overlaid output has the full-size forms only (not --dither, --lut, --size, --ladder)")
+        if args.pix_fmt not in ("yuv420p", "nv12", "p010") and PACKED_PIX_FMTS.get(args.pix_fmt, {}).get("layout") not in ("rgba", "bgra", "rgb10a2", "bgr10a2"):
+            ap.error(f"--overlay: needs --pix-fmt nv12, p010, rgba, bgra, x2bgr10le or x2rgb10le, --to, or no --pix-fmt (8-bit RGB); not {args.pix_fmt}")
+        layers = []
+        for item in args.overlay:
+            # X, Y and OPACITY are split from the right, so that FILE may hold colons: four fields if the last three are integers, else three
+            def ints(fields):
+                try:
+                    return [int(v) for v in fields]
+                except ValueError:
+                    return None
+            four, three = item.rsplit(":", 3), item.rsplit(":", 2)
+            if len(four) == 4 and ints(four[1:]) is not None:
+                name, (x, y, opacity) = four[0], ints(four[1:])
+            elif len(three) == 3 and ints(three[1:]) is not None:
+                name, (x, y), opacity = three[0], ints(three[1:]), 255
+            else:
+                ap.error(f"--overlay: expected FILE.npy:X:Y[:OPACITY], not {item!r}")
+            img = np.load(name)
+            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 4:
+                ap.error(f"--overlay: {name} is not an [h, w, 4] uint8 array")
+            layers.append(dict(image=torch.from_numpy(np.ascontiguousarray(img)).to(f"cuda:{args.device}"), x=x, y=y, opacity=opacity))      # uploaded once
+        ovl = dict(overlay=dict(layers=layers))
     if args.ladder is not None:
         import torch
         if not args.output:
@@ -260,20 +292,23 @@ def main():
         opts = {k: getattr(torch, v) if k == "dtype" else v for k, v in PACKED_PIX_FMTS[args.pix_fmt].items()}
         if args.to is not None and opts["layout"] in ("yuyv", "uyvy"):
             ap.error(f"--to: a colour transform needs an RGB --pix-fmt, not {args.pix_fmt}")
-        pics = StreamDecoder(data, device=args.device).output_order(packed=opts, to=args.to, side=side, residual=resid, compare=cmp, stats=stats, lut=args.lut, **lad, **dith)
+        pics = StreamDecoder(data, device=args.device).output_order(packed=opts, to=args.to, side=side, residual=resid, compare=cmp, stats=stats, lut=args.lut, **lad, **dith, **ovl)
         pics = [(p, p["packed"]) for p, _ in pics]
     elif args.lut is not None:
         import torch
         pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), lut=args.lut, side=side, residual=resid, compare=cmp, stats=stats)
     elif args.to is not None:
         import torch
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad, **dith)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), to=args.to, side=side, residual=resid, compare=cmp, stats=stats, **lad, **dith, **ovl)
+    elif args.pix_fmt == "yuv420p" and ovl:      # the layers over the stream's own R'G'B' (matrix, range and siting of its VUI)
+        import torch
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=dict(layout="rgb", channels_last=True, dtype=torch.uint8), side=side, residual=resid, compare=cmp, stats=stats, **ovl)
     elif args.pix_fmt == "yuv420p":
         pics = StreamDecoder(data, device=args.device).output_order(output_bit_depth=args.output_bit_depth, side=side, residual=resid, compare=cmp, stats=stats, **lad)
     else:      # the same pictures as semi-planar surfaces (xgpu_pic_output_device into a torch tensor, copied to the host picture by picture)
         import torch
         opts = dict(layout="nv12", dtype=torch.uint8) if args.pix_fmt == "nv12" else dict(layout="p016", dtype=torch.int16, out_bit_depth=10)
-        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid, compare=cmp, stats=stats, **lad, **dith)
+        pics = StreamDecoder(data, device=args.device).output_order(tensor=opts, side=side, residual=resid, compare=cmp, stats=stats, **lad, **dith, **ovl)
     dt = time.perf_counter() - t0
     if cmp is not None:
         cmp.finish()

@@ -157,6 +157,62 @@ def dither_phase(lib, index, mw, mh):
     return rc if rc < 0 else (px.value, py.value)
 
 
+MAX_OVERLAY_LAYERS, MAX_OVERLAY_BOXES = 16, 256
+OVL_RGBA8, OVL_BGRA8, OVL_A8, OVL_BOX = 0, 1, 2, 3
+
+
+class OverlayLayer(C.Structure):
+    _fields_ = [("kind", C.c_int), ("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int), ("opacity", C.c_int),
+                ("d_pixels", C.c_void_p), ("pitch", C.c_size_t), ("colour", C.c_uint8 * 4), ("fill", C.c_uint8 * 4), ("thickness", C.c_int)]
+
+
+class OverlayBoxes(C.Structure):
+    _fields_ = [("box_format", C.c_int), ("d_boxes", C.c_void_p), ("capacity", C.c_int), ("d_count", C.c_void_p), ("d_labels", C.c_void_p),
+                ("palette", (C.c_uint8 * 4) * 16), ("n_palette", C.c_int), ("thickness", C.c_int), ("fill_alpha", C.c_int)]
+
+
+def make_overlay_layer(kind, x, y, width, height, opacity=255, d_pixels=0, pitch=0, colour=(255, 255, 255, 255), fill=(0, 0, 0, 0), thickness=1):
+    """xgpu_overlay_layer (include/xevd_hip.h): one layer of an overlaid output call"""
+    l = OverlayLayer()
+    l.kind, l.x, l.y, l.width, l.height, l.opacity = int(kind), int(x), int(y), int(width), int(height), int(opacity)
+    l.d_pixels, l.pitch, l.thickness = int(d_pixels) or None, int(pitch), int(thickness)
+    for i in range(4):
+        l.colour[i], l.fill[i] = int(colour[i]), int(fill[i])
+    return l
+
+
+def make_overlay_boxes(box_format, d_boxes, capacity, d_count=0, d_labels=0, palette=((255, 0, 0, 255),), thickness=2, fill_alpha=0, n_palette=None):
+    """xgpu_overlay_boxes (include/xevd_hip.h): the boxes in device memory of an overlaid output call"""
+    b = OverlayBoxes()
+    b.box_format, b.d_boxes, b.capacity = int(box_format), int(d_boxes) or None, int(capacity)
+    b.d_count, b.d_labels = int(d_count) or None, int(d_labels) or None
+    for i, p in enumerate(list(palette)[:16]):
+        for k in range(4):
+            b.palette[i][k] = int(p[k])
+    b.n_palette = len(palette) if n_palette is None else int(n_palette)
+    b.thickness, b.fill_alpha = int(thickness), int(fill_alpha)
+    return b
+
+
+def overlay_coeffs(lib, fmt, bit_depth):
+    """xgpu_overlay_coeffs -> (m [9], offsets [3], shift), or the negative code"""
+    m, off, shift = (C.c_int32 * 9)(), (C.c_int32 * 3)(), C.c_int()
+    rc = lib.xgpu_overlay_coeffs(C.byref(fmt), int(bit_depth), m, off, C.byref(shift))
+    return rc if rc < 0 else (list(m), list(off), shift.value)
+
+
+def overlay_box_snap(lib, box, box_format=None):
+    """xgpu_overlay_box_snap, the device's snapping rule on the host: box (x, y, w, h) of ints (BOX_XYWH_I32) or (x1, y1, x2, y2) of floats (BOX_XYXY_F32; the
+    default for a float box) -> (x0, y0, x1, y1), None for a skipped box, or the negative code"""
+    raw = np.ascontiguousarray(box)
+    if box_format is None:
+        box_format = BOX_XYXY_F32 if raw.dtype.kind == "f" else BOX_XYWH_I32
+    raw = raw.astype(np.float32 if box_format == BOX_XYXY_F32 else np.int32)
+    r = (C.c_int * 4)()
+    rc = lib.xgpu_overlay_box_snap(int(box_format), raw.ctypes.data_as(C.c_void_p), r)
+    return rc if rc < 0 else (tuple(r) if rc else None)
+
+
 SIDE_BLOCKS, SIDE_FLOW_PLANAR, SIDE_FLOW_INTERLEAVED = 0, 1, 2
 MODE_IBC = 6
 
@@ -868,6 +924,14 @@ _EXPORTS = {
                                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_pic_output_device_packed_dithered": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PackedFormat), C.POINTER(ColourTransform),
                                                          C.POINTER(DitherParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_overlay_coeffs": (C.c_int, [C.POINTER(OutputFormat), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "xgpu_overlay_box_snap": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "xgpu_output_overlay_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(PackedFormat), C.POINTER(ColourTransform), C.POINTER(OverlayLayer), C.c_int,
+                                            C.POINTER(OverlayBoxes), C.c_int, C.c_int, C.c_int]),
+    "xgpu_pic_output_device_overlaid": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OutputFormat), C.POINTER(ColourTransform), C.POINTER(OverlayLayer),
+                                                  C.c_int, C.POINTER(OverlayBoxes), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "xgpu_pic_output_device_packed_overlaid": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PackedFormat), C.POINTER(ColourTransform),
+                                                         C.POINTER(OverlayLayer), C.c_int, C.POINTER(OverlayBoxes), C.c_void_p, C.c_size_t, C.c_void_p]),
     "xgpu_scale_taps": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16), C.c_int]),
     "xgpu_output_scaled_size": (C.c_size_t, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),
     "xgpu_output_scaled_check": (C.c_int, [C.POINTER(OutputFormat), C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int]),

@@ -137,6 +137,7 @@ int xgpu_open(const xgpu_seq_params *sp, xgpu_ctx **out)
     c->lad_blk = NULL; c->lad_blk_cap = 0; c->lad_cap = 0;
     for (Lut3dSlot &l : c->lut3d) { l.d = NULL; l.n = 0; }
     for (DitherSlot &d : c->dither) { d.d = NULL; d.mw = d.mh = d.k = 0; }
+    c->ovl_blk = NULL; c->ovl_blk_cap = 0;
     for (int i = 0; i < 6; i++) c->sc_key[i] = -1;
     c->out_next = 0;
     memset(c->t_ms, 0, sizeof(c->t_ms)); memset(c->t_n, 0, sizeof(c->t_n));
@@ -229,6 +230,7 @@ void xgpu_close(xgpu_ctx *c)
     if (c->lad_blk) (void)hipFree(c->lad_blk);
     for (Lut3dSlot &l : c->lut3d) if (l.d) (void)hipFree(l.d);
     for (DitherSlot &d : c->dither) if (d.d) (void)hipFree(d.d);
+    if (c->ovl_blk) (void)hipFree(c->ovl_blk);
     if (c->d_ctb_flag) (void)hipFree(c->d_ctb_flag);
     for (auto &e : c->ev_pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : c->ev_pool) (void)hipEventDestroy(e);

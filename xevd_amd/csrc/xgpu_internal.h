@@ -421,6 +421,9 @@ struct xgpu_ctx {
     Lut3dSlot       lut3d[XGPU_MAX_LUT3D];
     // xgpu_dither_create: the context's dither matrices by handle, read by the dithered output calls under the same ordering
     DitherSlot      dither[XGPU_MAX_DITHER];
+    // the overlaid output calls' device boxes (an OvlBlock written by k_overlay_prepare, read by the call's kernel; grown on demand, ordered like sc_tab)
+    uint8_t        *ovl_blk;
+    size_t          ovl_blk_cap;
 };
 
 // The host threads of a batch builder: workers that stay alive between pictures (a std::thread per phase and picture cost ~0.1 ms each - more than a phase of
@@ -713,6 +716,46 @@ struct DitherRgbArgs : PackedRgbArgs { DitherArgs di; };
 void launch_output_dither_rgb(const DitherRgbArgs &a, int sink, int dtype, int upsample, bool cm, hipStream_t s);
 struct DitherSemiArgs : SemiPlanarArgs { DitherArgs di; };
 void launch_output_dither_semiplanar(const DitherSemiArgs &a, int dtype, hipStream_t s);
+// k_output_overlay.hip (xgpu_pic_output_device_overlaid / _packed_overlaid): the layers of one call.  A layer is the unclipped
+// rectangle [x0, x1) x [y0, y1) in cropped destination coordinates; colour / fill: R | G << 8 | B << 16 | A << 24.
+struct OvlLayer {
+    int      x0, y0, x1, y1;
+    int      kind, opacity, thickness;
+    uint32_t colour, fill;
+    uint32_t pitch;                 // bitmaps: bytes between two rows
+    const uint8_t *pix;             // bitmaps: the pixel of (x0, y0)
+};
+// the device boxes of a call in the context's block, written by k_overlay_prepare: box i is a BOX layer [x0, x1) x [y0, y1) in `colour`; a skipped box is all zeros
+struct OvlBox { int x0, y0, x1, y1; uint32_t colour; };
+struct OvlBlock { int count, pad_[3]; OvlBox box[XGPU_MAX_OVERLAY_BOXES]; };
+struct OvlArgs {
+    const OvlBlock *boxes;          // or NULL: no device boxes
+    int      n;                     // host layers
+    int      maxv;                  // M, the element maximum
+    int      box_thickness, box_fill_alpha;
+    int      m[9], off[3], s;       // NV12 / P016: the forward matrix, the offsets and S (xgpu_overlay_coeffs)
+    OvlLayer layer[XGPU_MAX_OVERLAY_LAYERS];
+};
+// the three-channel family: PackedRgbArgs as k_output_packed_rgb reads them; the surfaces: SemiPlanarArgs
+struct OverlayRgbArgs : PackedRgbArgs { OvlArgs ov; };
+struct OverlaySemiArgs : SemiPlanarArgs { OvlArgs ov; };
+void launch_output_overlay_rgb(const OverlayRgbArgs &a, int sink, int dtype, int upsample, bool cm, hipStream_t s);
+void launch_output_overlay_semiplanar(const OverlaySemiArgs &a, int dtype, hipStream_t s);
+struct OvlPrepArgs {
+    OvlBlock *blk;
+    const void *boxes;              // capacity boxes of box_format
+    const int32_t *count, *labels;  // or NULL
+    int      capacity, box_format, n_palette;
+    int      pw, ph;                // the image: a box that misses it is skipped
+    uint32_t palette[16];
+};
+void launch_overlay_prepare(const OvlPrepArgs &a, hipStream_t s);
+// xgpu_overlay.hip: the host side of those calls that needs no device
+void   overlay_forward_matrix(double kr, double kb, int full_range, int d, int32_t m[9], int32_t off[3], int *shift);
+int    overlay_layers_check(const xgpu_overlay_layer *layers, int n, const xgpu_overlay_boxes *boxes, const char **why);
+size_t overlay_layer_bytes(const xgpu_overlay_layer &l);
+void   overlay_fill_args(const xgpu_overlay_layer *layers, int n, const xgpu_overlay_boxes *boxes, const OvlBlock *blk, int maxv, OvlArgs &o);
+void   overlay_fill_prepare(const xgpu_overlay_boxes *boxes, OvlBlock *blk, int pw, int ph, OvlPrepArgs &p);
 // k_side_info.hip: the SCU map of the picture decoded last as nine int16 planes per unit (k_side_blocks) or as a dense motion field (k_side_flow)
 struct SideArgs {
     const ScuRec *maps;

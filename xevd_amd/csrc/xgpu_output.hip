@@ -867,6 +867,173 @@ int xgpu_pic_output_device_packed_dithered(xgpu_ctx *c, int pic, const xgpu_dra_
     return out_join(c, stream, s);      // the slot, the DRA and the colour tables, the matrix
 }
 
+// ------------------------------------------------------------------------------------------------ overlaid output
+// The refusals that look at the format and the transform alone, in the contract's order: the plain call's with its codes, a float dtype, a layout without an
+// overlaid form, a transform on a video surface, a video surface whose matrix / full_range give no forward matrix.  0 with *need = the bytes at d_dst and
+// *maxv = M, or the code and `why`.  No device is touched.
+static int overlay_format_check(const xgpu_output_format *f, const xgpu_packed_format *pf, const xgpu_colour_transform *cm, int width, int height, int bd,
+                                size_t *need, int *maxv, const char **why)
+{
+    int rc;
+    if (f) {
+        *need = format_size(f, width, height, bd, &rc, why);
+        if (*need == 0) return rc;
+        *why = "an overlaid output needs an integer dtype";
+        if (!is_int_dtype(f->dtype)) return XGPU_ERR_UNSUPPORTED;
+        *why = "an overlaid output needs one of the RGB layouts, NV12 or P016";
+        if (!is_rgb(f->layout) && !is_semiplanar(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+        *why = "a colour transform needs one of the RGB layouts";
+        if (cm && !is_rgb(f->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+        if (is_semiplanar(f->layout)) {
+            double kr, kb;
+            *why = "NV12 / P016: full_range must be 0 or 1";
+            if (f->full_range & ~1) return XGPU_ERR_INVALID_ARGUMENT;
+            *why = "matrix: supported MatrixCoefficients are 1, 4, 5, 6, 7 and 9";
+            if (!matrix_kr_kb(f->matrix, &kr, &kb)) return XGPU_ERR_UNSUPPORTED;
+            *maxv = (1 << sample_depth(f, bd)) - 1;
+        } else {
+            *maxv = f->dtype == XGPU_OUT_U8 ? 255 : (1 << bd) - 1;
+        }
+    } else {
+        *need = packed_size(pf, width, height, bd, &rc, why);
+        if (*need == 0) return rc;
+        *why = "an overlaid output needs an integer dtype";
+        if (pf->layout == XGPU_PACKED_RGBA && !is_int_dtype(pf->dtype)) return XGPU_ERR_UNSUPPORTED;
+        *why = "an overlaid packed output needs XGPU_PACKED_RGBA or XGPU_PACKED_RGB10A2";
+        if (!is_packed_rgb(pf->layout)) return XGPU_ERR_INVALID_ARGUMENT;
+        *maxv = pf->layout == XGPU_PACKED_RGB10A2 ? 1023 : pf->dtype == XGPU_OUT_U8 ? 255 : (1 << bd) - 1;
+    }
+    return XGPU_OK;
+}
+int xgpu_overlay_coeffs(const xgpu_output_format *f, int bit_depth, int32_t m[9], int32_t offsets[3], int *shift)
+{
+    const char *why;
+    if (bit_depth < 8 || bit_depth > 12 || !m || !offsets || !shift) return XGPU_ERR_INVALID_ARGUMENT;
+    const int rc = check_format(f, bit_depth, &why);
+    if (rc < 0) return rc;
+    if (!is_semiplanar(f->layout) || (f->full_range & ~1)) return XGPU_ERR_INVALID_ARGUMENT;
+    double kr, kb;
+    if (!matrix_kr_kb(f->matrix, &kr, &kb)) return XGPU_ERR_UNSUPPORTED;
+    overlay_forward_matrix(kr, kb, f->full_range, sample_depth(f, bit_depth), m, offsets, shift);
+    return XGPU_OK;
+}
+int xgpu_output_overlay_check(const xgpu_output_format *f, const xgpu_packed_format *pf, const xgpu_colour_transform *cm, const xgpu_overlay_layer *layers,
+                              int n_layers, const xgpu_overlay_boxes *boxes, int width, int height, int bit_depth)
+{
+    if ((f != NULL) == (pf != NULL)) return XGPU_ERR_INVALID_ARGUMENT;
+    size_t need; int maxv; const char *why;
+    const int rc = overlay_format_check(f, pf, cm, width, height, bit_depth, &need, &maxv, &why);
+    if (rc < 0) return rc;
+    if (cm) {
+        const xgpu_output_format rf = f ? *f : packed_rgb_format(pf);
+        TRY(cm_dry_run(&rf, cm, bit_depth));
+    }
+    return overlay_layers_check(layers, n_layers, boxes, &why);
+}
+// the refusals that look at the call's layers and boxes: the arguments, then the memory behind every pointer; then the block of the device boxes
+static int overlay_prepare(xgpu_ctx *c, const char *who, const xgpu_overlay_layer *layers, int n, const xgpu_overlay_boxes *boxes)
+{
+    const char *why;
+    const int rc = overlay_layers_check(layers, n, boxes, &why);
+    if (rc < 0) { snprintf(c->err, sizeof(c->err), "%s: %s", who, why); return rc; }
+    char what[96];      // which pointer a refusal is about: "<who>: the bitmap of layer 3", "<who>: d_boxes"
+    for (int i = 0; i < n; i++)
+        if (layers[i].kind != XGPU_OVL_BOX) {
+            snprintf(what, sizeof(what), "%s: the bitmap of layer %d", who, i);
+            TRY(check_device_dst(c, what, (void *)layers[i].d_pixels, overlay_layer_bytes(layers[i])));
+        }
+    if (boxes) {
+        snprintf(what, sizeof(what), "%s: d_boxes", who);
+        TRY(check_device_dst(c, what, (void *)boxes->d_boxes, (size_t)boxes->capacity * 16));
+        snprintf(what, sizeof(what), "%s: d_count", who);
+        if (boxes->d_count) TRY(check_device_dst(c, what, (void *)boxes->d_count, sizeof(int32_t)));
+        snprintf(what, sizeof(what), "%s: d_labels", who);
+        if (boxes->d_labels) TRY(check_device_dst(c, what, (void *)boxes->d_labels, (size_t)boxes->capacity * sizeof(int32_t)));
+        TRY(grow(c, who, &c->ovl_blk, &c->ovl_blk_cap, sizeof(OvlBlock), "block of the device boxes"));
+    }
+    return XGPU_OK;
+}
+// behind the fork: the device boxes into the context's block, on the call's stream; the layers as the kernels read them
+static void overlay_queue(xgpu_ctx *c, const xgpu_overlay_layer *layers, int n, const xgpu_overlay_boxes *boxes, int w, int h, int maxv, OvlArgs &o, hipStream_t s)
+{
+    if (boxes) {
+        OvlPrepArgs p;
+        overlay_fill_prepare(boxes, (OvlBlock *)c->ovl_blk, w, h, p);
+        launch_overlay_prepare(p, s);
+    }
+    overlay_fill_args(layers, n, boxes, (const OvlBlock *)c->ovl_blk, maxv, o);
+}
+int xgpu_pic_output_device_overlaid(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_output_format *f, const xgpu_colour_transform *cm,
+                                    const xgpu_overlay_layer *layers, int n_layers, const xgpu_overlay_boxes *boxes, void *d_dst, size_t dst_size, void *stream)
+{
+    static const char who[] = "pic_output_device_overlaid";
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    const char *why = "format is NULL";
+    const int bd = c->sp.bit_depth_luma;
+    size_t need; int maxv;
+    const int rc = f ? overlay_format_check(f, NULL, cm, c->sp.width, c->sp.height, bd, &need, &maxv, &why) : XGPU_ERR_INVALID_ARGUMENT;
+    if (rc < 0) { snprintf(c->err, sizeof(c->err), "%s: invalid format: %s", who, why); return rc; }
+    std::unique_ptr<xgpu_colour_tables_t> cm_new;      // a new set of tables: made here, before anything is queued; uploaded and committed below
+    if (cm) TRY(cm_prepare(c, who, f, cm, cm_new));
+    TRY(overlay_prepare(c, who, layers, n_layers, boxes));
+    TRY(check_dst(c, who, d_dst, dst_size, need, (size_t)elem_size(f->dtype)));
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    TRY(cm_commit(c, cm, cm_new, s));
+    if (is_semiplanar(f->layout)) {      // xgpu_pic_output_device's arguments, and the layers
+        OverlaySemiArgs a;
+        memset(&a, 0, sizeof(a));
+        fill_semiplanar(c, pic, dra, f, d_dst, a);
+        overlay_queue(c, layers, n_layers, boxes, a.w, 2 * a.ch, maxv, a.ov, s);
+        double kr, kb;
+        matrix_kr_kb(f->matrix, &kr, &kb);
+        overlay_forward_matrix(kr, kb, f->full_range, sample_depth(f, bd), a.ov.m, a.ov.off, &a.ov.s);
+        launch_output_overlay_semiplanar(a, f->dtype, s);
+    } else {
+        OverlayRgbArgs a;
+        memset(&a, 0, sizeof(a));
+        fill_source(c, pic, f->crop, d_dst, a);
+        fill_rows(a, d_dst, image_row(f, a.w), a.h, f->row_pitch);
+        fill_conversion(c, dra, f, a);
+        fill_siting(f->chroma_loc, a);
+        if (cm) fill_cm(c, f, *c->cm_tab, a, a.cm);
+        overlay_queue(c, layers, n_layers, boxes, a.w, a.h, maxv, a.ov, s);
+        launch_output_overlay_rgb(a, f->layout == XGPU_OUT_RGB_PLANAR ? OUT_SINK_PLANAR : OUT_SINK_INTERLEAVED, f->dtype, f->upsample, cm != NULL, s);
+    }
+    return out_join(c, stream, s);      // the slot, the DRA and the colour tables, the block of the device boxes
+}
+int xgpu_pic_output_device_packed_overlaid(xgpu_ctx *c, int pic, const xgpu_dra_luts *dra, const xgpu_packed_format *f, const xgpu_colour_transform *cm,
+                                           const xgpu_overlay_layer *layers, int n_layers, const xgpu_overlay_boxes *boxes, void *d_dst, size_t dst_size,
+                                           void *stream)
+{
+    static const char who[] = "pic_output_device_packed_overlaid";
+    ARGCHK(c, c != NULL); ARGCHK(c, valid_pic(c, pic)); ARGCHK(c, d_dst != NULL);
+    const char *why = "";
+    const int bd = c->sp.bit_depth_luma;
+    size_t need; int maxv;
+    const int rc = overlay_format_check(NULL, f, cm, c->sp.width, c->sp.height, bd, &need, &maxv, &why);
+    if (rc < 0) { snprintf(c->err, sizeof(c->err), "%s: invalid format: %s", who, why); return rc; }
+    const xgpu_output_format rf = packed_rgb_format(f);
+    std::unique_ptr<xgpu_colour_tables_t> cm_new;
+    if (cm) TRY(cm_prepare(c, who, &rf, cm, cm_new));
+    TRY(overlay_prepare(c, who, layers, n_layers, boxes));
+    TRY(check_dst(c, who, d_dst, dst_size, need, packed_elem_size(f)));
+    if (dra) TRY(upload_dra(c, dra));
+    hipStream_t s;
+    TRY(out_fork(c, stream, &s));
+    TRY(cm_commit(c, cm, cm_new, s));
+    OverlayRgbArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_source(c, pic, f->crop, d_dst, a);
+    fill_rows(a, d_dst, packed_row(f, a.w), a.h, f->row_pitch);
+    fill_siting(f->chroma_loc, a);
+    fill_packed_rgb(c, dra, f, &rf, cm != NULL, a);      // xgpu_pic_output_device_packed's arguments
+    overlay_queue(c, layers, n_layers, boxes, a.w, a.h, maxv, a.ov, s);
+    launch_output_overlay_rgb(a, f->layout == XGPU_PACKED_RGBA ? OUT_SINK_RGBA : OUT_SINK_RGB10A2, f->dtype, f->upsample, cm != NULL, s);
+    return out_join(c, stream, s);      // the slot, the DRA and the colour tables, the block of the device boxes
+}
+
 // ------------------------------------------------------------------------------------------------ scaled output into device memory
 // format and scale parameters for a picture of width x height at depth bd: the bytes the destination needs, or 0 with *rc = the code and `why`
 // the part that does not look at the ratio of source and destination: what the batched output (section 8e) shares

@@ -465,12 +465,10 @@ class XgpuDecoder:
     _DITHER_LAYOUTS = {"rgb": None, "nv12": None, "p016": None, "rgba": (abi.PACKED_RGBA, False), "bgra": (abi.PACKED_RGBA, True),
                        "rgb10a2": (abi.PACKED_RGB10A2, False), "bgr10a2": (abi.PACKED_RGB10A2, True)}
 
-    def pic_output_dithered(self, pic, dither, layout="rgb", phase=(0, 0), colour=None, out=None, channels_last=False, dtype=None, out_bit_depth=0, alpha=1.0,
-                            matrix=1, full_range=False, chroma_loc=0, upsample="linear", crop=(0, 0, 0, 0), dra=None, bgr=False):
-        """The picture with the dither matrix `dither` (a handle of dither_create) at `phase` (x, y) in place of the final rounding, as a torch tensor on
-        cuda:{device}, made on the device on torch's current stream (xgpu_pic_output_device_dithered / _packed_dithered, INTEGRATION.md section 8r).  layout "rgb",
-        "nv12", "p016": pic_output_tensor's shapes and arguments, integer dtypes only; "rgba" / "bgra" / "rgb10a2" / "bgr10a2": pic_output_packed's.  colour: a
-        colour transform as those calls take it (the RGB layouts and the packed ones)."""
+    def _int_output_setup(self, word, layout, colour, out, channels_last, dtype, out_bit_depth, alpha, matrix, full_range, chroma_loc, upsample, crop, bgr):
+        """what the dithered and the overlaid output share: the layouts of _DITHER_LAYOUTS in integer dtypes -> (the tensor to fill, its xgpu_output_format or
+        None, its xgpu_packed_format or None, the transform or None, the entry point's name, the torch dtype); word: the entry points' last word, "dithered" or "overlaid", which the messages use too"""
+        what = f"a {word}" if word[0] not in "aeiou" else f"an {word}"
         import torch
         if layout not in self._DITHER_LAYOUTS:
             raise ValueError(f"layout must be one of {', '.join(map(repr, self._DITHER_LAYOUTS))}, not {layout!r}")
@@ -490,7 +488,7 @@ class XgpuDecoder:
             if dtype is None:
                 dtype = torch.int16 if layout == "p016" else torch.uint8
             if dtype not in ints:
-                raise ValueError(f"{layout}: a dithered output has integer dtypes, not {dtype}")
+                raise ValueError(f"{layout}: {what} output has integer dtypes, not {dtype}")
             code = ints[dtype]
             if layout == "rgb":
                 fmt = abi.make_output_format(abi.OUT_RGB_INTERLEAVED if channels_last else abi.OUT_RGB_PLANAR, code, bgr=bgr, out_bit_depth=obd, matrix=matrix,
@@ -505,12 +503,14 @@ class XgpuDecoder:
                         raise ValueError("nv12: torch.uint8 holds 8-bit samples; out_bit_depth above 8 needs a 16-bit integer dtype")
                     obd = 8
                 fmt = abi.make_output_format(abi.OUT_NV12 if layout == "nv12" else abi.OUT_P016, code, out_bit_depth=obd, crop=crop)
+                if word == "overlaid":      # the layers' colours go through the forward matrix of these two; the samples themselves never read them
+                    fmt.matrix, fmt.full_range = int(matrix), int(bool(full_range))
                 out = _out_tensor(out, (h * 3 // 2, w), dtype, dev)
                 st = out.stride()
                 if st[1] != 1 or st[0] < w:
                     raise ValueError(f"out: strides {st} are not rows of W elements")
                 fmt.row_pitch = st[0] * dtype.itemsize
-            f_arg, pf_arg, name = C.byref(fmt), None, "xgpu_pic_output_device_dithered"
+            f_arg, pf_arg, name = C.byref(fmt), None, f"xgpu_pic_output_device_{word}"
         else:
             if channels_last or bgr:
                 raise ValueError(f"{layout}: channels_last and bgr belong to layout 'rgb'")
@@ -522,7 +522,7 @@ class XgpuDecoder:
             else:
                 dtype = torch.uint8 if dtype is None else dtype
                 if dtype not in ints:
-                    raise ValueError(f"{layout}: a dithered output has integer dtypes, not {dtype}")
+                    raise ValueError(f"{layout}: {what} output has integer dtypes, not {dtype}")
                 code, shape, last = ints[dtype], (h, w, 4), 4
             fmt = abi.make_packed_format(lay, code, bgr=pbgr, out_bit_depth=obd, matrix=matrix, full_range=full_range, chroma_loc=chroma_loc, upsample=up, crop=crop,
                                          alpha=alpha)
@@ -531,7 +531,18 @@ class XgpuDecoder:
             if st[1:] != ((last, 1) if len(shape) == 3 else (1,)) or st[0] < w * last:
                 raise ValueError(f"out: strides {st} are not rows of W x {last} elements")
             fmt.row_pitch = st[0] * dtype.itemsize
-            f_arg, pf_arg, name = None, C.byref(fmt), "xgpu_pic_output_device_packed_dithered"
+            f_arg, pf_arg, name = None, C.byref(fmt), f"xgpu_pic_output_device_packed_{word}"
+        return out, (fmt if pf_arg is None else None), (fmt if pf_arg is not None else None), cm, name, dtype
+
+    def pic_output_dithered(self, pic, dither, layout="rgb", phase=(0, 0), colour=None, out=None, channels_last=False, dtype=None, out_bit_depth=0, alpha=1.0,
+                            matrix=1, full_range=False, chroma_loc=0, upsample="linear", crop=(0, 0, 0, 0), dra=None, bgr=False):
+        """The picture with the dither matrix `dither` (a handle of dither_create) at `phase` (x, y) in place of the final rounding, as a torch tensor on
+        cuda:{device}, made on the device on torch's current stream (xgpu_pic_output_device_dithered / _packed_dithered, INTEGRATION.md section 8r).  layout "rgb",
+        "nv12", "p016": pic_output_tensor's shapes and arguments, integer dtypes only; "rgba" / "bgra" / "rgb10a2" / "bgr10a2": pic_output_packed's.  colour: a
+        colour transform as those calls take it (the RGB layouts and the packed ones)."""
+        out, f, pf, cm, name, dtype = self._int_output_setup("dithered", layout, colour, out, channels_last, dtype, out_bit_depth, alpha, matrix, full_range, chroma_loc,
+                                                             upsample, crop, bgr)
+        f_arg, pf_arg = (C.byref(f), None) if pf is None else (None, C.byref(pf))
         rc = self.lib.xgpu_output_dither_check(f_arg, pf_arg, None, 1, 1, 1, self.width, self.height, self.bit_depth)
         if rc == 0 and cm is not None:
             rc = self._cm_check(abi.make_output_format(abi.OUT_RGB_INTERLEAVED), cm) if layout not in ("nv12", "p016") else -1
@@ -541,6 +552,95 @@ class XgpuDecoder:
         dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
         dp = abi.make_dither_params(dither, phase)
         self._device_call(name, out, pic, dl, f_arg if pf_arg is None else pf_arg, None if cm is None else C.byref(cm), C.byref(dp))
+        return out
+
+    def _overlay_layers(self, layers, dev):
+        """layer dicts -> (the xgpu_overlay_layer array or None, their count, the tensors it points into)"""
+        import torch
+        layers = list(layers or ())
+        if len(layers) > abi.MAX_OVERLAY_LAYERS:
+            raise ValueError(f"layers: at most {abi.MAX_OVERLAY_LAYERS}, not {len(layers)}")
+        arr, keep = (abi.OverlayLayer * max(len(layers), 1))(), []
+        for i, l in enumerate(layers):
+            l = dict(l)
+            if ("image" in l) == ("box" in l):
+                raise ValueError(f"layers[{i}]: one of image= and box=")
+            opacity = l.pop("opacity", 255)
+            if "box" in l:
+                x, y, w, h = (int(v) for v in l.pop("box"))
+                colour, fill, thickness = l.pop("colour", (255, 255, 255, 255)), l.pop("fill", (0, 0, 0, 0)), l.pop("thickness", 1)
+                arr[i] = abi.make_overlay_layer(abi.OVL_BOX, x, y, w, h, opacity, colour=colour, fill=fill, thickness=thickness)
+            else:
+                img = l.pop("image")
+                order = l.pop("order", "rgba")
+                if order not in ("rgba", "bgra"):
+                    raise ValueError(f"layers[{i}]: order must be 'rgba' or 'bgra', not {order!r}")
+                if not isinstance(img, torch.Tensor) or img.device != dev or img.dtype != torch.uint8 or img.dim() not in (2, 3) or (img.dim() == 3 and img.shape[2] != 4) or img.numel() == 0:
+                    raise ValueError(f"layers[{i}]: image is a torch.uint8 tensor [h, w, 4] or [h, w] on {dev}")
+                bpp = 4 if img.dim() == 3 else 1
+                st = img.stride()
+                if (bpp == 4 and st[1:] != (4, 1)) or (bpp == 1 and st[1] != 1) or st[0] < img.shape[1] * bpp:
+                    raise ValueError(f"layers[{i}]: strides {st} are not rows of pixels")
+                kind = abi.OVL_A8 if bpp == 1 else abi.OVL_BGRA8 if order == "bgra" else abi.OVL_RGBA8
+                arr[i] = abi.make_overlay_layer(kind, l.pop("x", 0), l.pop("y", 0), img.shape[1], img.shape[0], opacity, d_pixels=img.data_ptr(), pitch=st[0],
+                                                colour=l.pop("colour", (255, 255, 255, 255)))
+                keep.append(img)
+            if l:
+                raise ValueError(f"layers[{i}]: unknown keys {sorted(l)}")
+        return (arr if layers else None), len(layers), keep
+
+    def _overlay_boxes(self, boxes, dev):
+        """boxes dict -> (xgpu_overlay_boxes or None, the tensors it points into)"""
+        import torch
+        if boxes is None:
+            return None, []
+        b = dict(boxes)
+        t = b.pop("tensor")
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dim() != 2 or t.shape[1] != 4 or t.dtype not in (torch.int32, torch.float32) or not t.is_contiguous():
+            raise ValueError(f"boxes: tensor is a contiguous [n, 4] torch.int32 (x, y, w, h) or torch.float32 (x1, y1, x2, y2) tensor on {dev}")
+        keep, ptr = [t], {}
+        for key in ("count", "labels"):
+            v = b.pop(key, None)
+            if v is not None:
+                if not isinstance(v, torch.Tensor) or v.device != dev or v.dtype != torch.int32 or not v.is_contiguous() or v.numel() < (1 if key == "count" else t.shape[0]):
+                    raise ValueError(f"boxes: {key} is a contiguous torch.int32 tensor on {dev}" + (" with one label per box" if key == "labels" else ""))
+                keep.append(v)
+            ptr[key] = 0 if v is None else v.data_ptr()
+        ob = abi.make_overlay_boxes(abi.BOX_XYXY_F32 if t.dtype == torch.float32 else abi.BOX_XYWH_I32, t.data_ptr(), t.shape[0], ptr["count"], ptr["labels"],
+                                    palette=b.pop("palette", ((255, 0, 0, 255),)), thickness=b.pop("thickness", 2), fill_alpha=b.pop("fill_alpha", 0))
+        if b:
+            raise ValueError(f"boxes: unknown keys {sorted(b)}")
+        return ob, keep
+
+    def pic_output_overlaid(self, pic, layers=None, boxes=None, layout="rgb", colour=None, out=None, channels_last=False, dtype=None, out_bit_depth=0, alpha=1.0,
+                            matrix=1, full_range=False, chroma_loc=0, upsample="linear", crop=(0, 0, 0, 0), dra=None, bgr=False):
+        """The picture with `layers` alpha-blended over it, as a torch tensor on cuda:{device}, made on the device on torch's current stream
+        (xgpu_pic_output_device_overlaid / _packed_overlaid).  layout "rgb", "nv12", "p016": pic_output_tensor's shapes and arguments,
+        integer dtypes only; "rgba" / "bgra" / "rgb10a2" / "bgr10a2": pic_output_packed's.  colour: a colour transform as those calls take it (the RGB layouts and
+        the packed ones); the layers' colours are codes of the destination and are not transformed.
+        layers: at most 16 dicts, blended in list order, positions in the cropped W x H image (they may lie partly or wholly outside) -
+          dict(image=<torch.uint8 cuda tensor [h, w, 4] or [h, w]>, x=0, y=0, opacity=255, order="rgba" | "bgra", colour=(r, g, b, a)): a bitmap with straight
+          alpha, or - [h, w] - the coverage of `colour`;
+          dict(box=(x, y, w, h), thickness=1, colour=(r, g, b, a), fill=(r, g, b, a), opacity=255): a frame in `colour`, its interior in `fill`.
+        boxes: dict(tensor=<[n, 4] torch.int32 x, y, w, h | torch.float32 x1, y1, x2, y2>, count=<int32 tensor or None>, labels=<int32 [n] or None>,
+          palette=[(r, g, b, a), ...], thickness=2, fill_alpha=0): at most 256 boxes a detector left on the device, painted before the layers; the host reads none
+          of the tensors and nothing synchronises.
+        The tensors of layers and boxes are read on torch's current stream; the decoder keeps references to them until its next overlaid call."""
+        out, f, pf, cm, name, dtype = self._int_output_setup("overlaid", layout, colour, out, channels_last, dtype, out_bit_depth, alpha, matrix, full_range, chroma_loc,
+                                                             upsample, crop, bgr)
+        f_arg, pf_arg = (C.byref(f), None) if pf is None else (None, C.byref(pf))
+        arr, n, keep = self._overlay_layers(layers, out.device)
+        ob, keep_b = self._overlay_boxes(boxes, out.device)
+        b_arg = None if ob is None else C.byref(ob)
+        rc = self.lib.xgpu_output_overlay_check(f_arg, pf_arg, None, arr, n, b_arg, self.width, self.height, self.bit_depth)
+        if rc == 0 and cm is not None:
+            rc = self._cm_check(abi.make_output_format(abi.OUT_RGB_INTERLEAVED), cm) if layout not in ("nv12", "p016") else -1
+        if rc < 0:
+            raise ValueError(f"invalid overlaid output ({rc}): layout {layout}, dtype {dtype}, out_bit_depth {out_bit_depth}, matrix {matrix}, "
+                             f"chroma_loc {chroma_loc}, alpha {alpha}, crop {crop}, colour {colour}, {n} layers, boxes {None if boxes is None else tuple(boxes['tensor'].shape)}")
+        dl, self._dra_keep = self._dra_luts(dra)      # (kept until the next call: the tables are copied asynchronously)
+        self._overlay_keep = keep + keep_b
+        self._device_call(name, out, pic, dl, f_arg if pf_arg is None else pf_arg, None if cm is None else C.byref(cm), arr, n, b_arg)
         return out
 
     def _scaled_setup(self, a):

@@ -117,7 +117,7 @@ class StreamDecoder:
 
     def pictures(self, download=True, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None,
                  residual=None, compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
-                 linear_light=False, resample=None, packed=None, lut=None, dither=None):
+                 linear_light=False, resample=None, packed=None, lut=None, dither=None, overlay=None):
         """generator of (params, planes or None) in DECODING order; planes = [Y, U, V] int16 arrays of the active area, or - with
         output_bit_depth (0 = the coding depth) - the bytes of one .yuv frame, converted and packed on the device, or - with
         tensor=dict(...) (keyword arguments of XgpuDecoder.pic_output_tensor, {} for the defaults) - a torch tensor on the GPU converted on torch's
@@ -174,7 +174,32 @@ class StreamDecoder:
         (XgpuDecoder.pic_output_dithered; kind / size / seed as dither_create takes them, 64 and 1 by default).  The matrix is made
         and uploaded once, at the first picture.  temporal=True moves it from picture to picture by xgpu_dither_phase(poc & 0xFFFFFFFF); without it the phase is
         (0, 0).  to= goes with it; an option that has no dithered form (size=, rois=, warp=, remap=, resample=, surfaces=, lut=, mean=, std=, float dtypes, the
-        other layouts) raises XgpuError before decoding starts"""
+        other layouts) raises XgpuError before decoding starts
+        overlay=dict(layers=[...], boxes=dict(...)) or a callable(params) -> such a dict or None (with tensor=, layouts "rgb", "nv12", "p016", and / or packed=
+        with one of its RGB layouts; integer dtypes; called behind the picture's kernels as rois= is): every picture with those layers alpha-blended over it
+        (XgpuDecoder.pic_output_overlaid) - a logo, a subtitle plane, the boxes a detector left on the device.  to= goes with it (the
+        layers are codes of the destination); an option that has no overlaid form (dither=, lut=, size=, rois=, warp=, remap=, resample=, surfaces=, mean=,
+        std=, float dtypes, the other layouts) raises XgpuError before decoding starts"""
+        if overlay is not None:
+            from .decoder import XgpuError
+            if not callable(overlay) and (not isinstance(overlay, dict) or set(overlay) - {"layers", "boxes"}):
+                raise XgpuError("overlay: dict(layers=, boxes=) or a callable(params) that returns one")
+            if tensor is None and packed is None:
+                raise XgpuError("overlay: needs tensor=dict(...) or packed=dict(layout=...)")
+            clash = [k for k, v in (("dither", dither), ("lut", lut), ("size", size), ("mean", mean), ("std", std), ("rois", rois), ("warp", warp), ("remap", remap),
+                                    ("resample", resample), ("surfaces", surfaces), ("linear_light", linear_light or None)) if v is not None]
+            if clash:
+                raise XgpuError(f"overlay: not together with {', '.join(k + '=' for k in clash)} - the overlaid output has the full-size RGB, NV12 / P016 and packed RGB forms only")
+            for what, opts, layouts, first in (("tensor", tensor, ("rgb", "nv12", "p016"), "rgb"), ("packed", packed, ("rgba", "bgra", "rgb10a2", "bgr10a2"), "rgba")):
+                if opts is None:
+                    continue
+                if opts.get("layout", first) not in layouts:
+                    raise XgpuError(f"overlay: {what} layout {opts['layout']!r} has no overlaid form (one of {', '.join(layouts)})")
+                dt = opts.get("dtype")
+                if dt is not None and (getattr(dt, "is_floating_point", False) or "float" in str(dt)):
+                    raise XgpuError(f"overlay: an overlaid output has integer dtypes, not {dt}")
+                if to is not None and opts.get("layout", first) in ("nv12", "p016"):
+                    raise XgpuError("overlay: to= needs an RGB layout")
         dither_opts = None
         if dither is not None:
             from .decoder import XgpuError
@@ -266,6 +291,13 @@ class StreamDecoder:
             h, mw, mh = dither_made[0]
             return h, abi.dither_phase(dec.lib, p["poc"] & 0xFFFFFFFF, mw, mh) if dither_opts.get("temporal") else (0, 0)
 
+        overlay_last = [None, None]      # (picture, what the callable returned for it): one call per picture, and nothing of it in the picture's params
+
+        def overlay_of(p):          # the layers and boxes of picture p as pic_output_overlaid's keyword arguments
+            if overlay_last[0] is not p:
+                overlay_last[:] = [p, (overlay(p) if callable(overlay) else overlay) or {}]
+            return {k: overlay_last[1].get(k) for k in ("layers", "boxes")}
+
         def decode(p):
             dec, hb = self._dec, p["batch"]
             if p["is_idr"]:
@@ -324,7 +356,9 @@ class StreamDecoder:
                 if to is not None and kw.get("layout", "rgba") not in ("yuyv", "uyvy"):
                     kw.setdefault("colour", self.colour_transform(p["colour"], to))
                 with self._lock:
-                    if dither_opts is not None:
+                    if overlay is not None:
+                        p["packed"] = dec.pic_output_overlaid(cur, **overlay_of(p), **kw)
+                    elif dither_opts is not None:
                         h, ph = dither_of(dec, p)
                         p["packed"] = dec.pic_output_dithered(cur, h, phase=ph, **kw)
                     else:
@@ -339,7 +373,9 @@ class StreamDecoder:
                     if v is not None:
                         kw.setdefault(k, v)
                 with self._lock:
-                    if dither_opts is not None:
+                    if overlay is not None:
+                        planes = dec.pic_output_overlaid(cur, **overlay_of(p), **kw)
+                    elif dither_opts is not None:
                         h, ph = dither_of(dec, p)
                         planes = dec.pic_output_dithered(cur, h, phase=ph, **kw)
                     elif lut is not None:
@@ -403,19 +439,19 @@ class StreamDecoder:
 
     def output_order(self, output_bit_depth=None, tensor=None, to=None, side=None, size=None, mean=None, std=None, rois=None, fit=None, pad=None, residual=None,
                      compare=None, stats=None, warp=None, remap=None, remap_step=0, surfaces=None, surface_layout="nv12", surface_options=None,
-                     linear_light=False, resample=None, packed=None, lut=None, dither=None):
+                     linear_light=False, resample=None, packed=None, lut=None, dither=None, overlay=None):
         """all pictures in output order (ascending POC inside every IDR period), as xevd_pull's bumping delivers them; with tensor=dict(...) (as
         pictures takes it, `to` too) every picture is converted on the device and copied to the host as it arrives: numpy arrays of the tensors' shape;
         side=dict(...) (as pictures takes it): params["side_info"] of every picture, as a numpy array too; residual=dict(...) (as pictures takes it):
         params["residual"] as numpy - for kind "yuv420" the pair (flat array, (Y, Cb, Cr) views of it); compare= (as pictures takes it, the callable and the
         sequence in DECODING order): params["compare"], its map as a numpy array; stats= (as pictures takes it): params["stats"], its histograms as numpy arrays;
         surfaces= / surface_layout= / surface_options= (as pictures takes them): params["surfaces"], a list of numpy arrays; resample= (as pictures takes it);
-        packed=dict(...) (as pictures takes it): params["packed"], a numpy array; lut= and dither= (as pictures takes them)"""
+        packed=dict(...) (as pictures takes it): params["packed"], a numpy array; lut=, dither= and overlay= (as pictures takes them)"""
         out, epoch = [], -1
         for p, planes in self.pictures(output_bit_depth=output_bit_depth, tensor=tensor, to=to, side=side, size=size, mean=mean, std=std, rois=rois, fit=fit, pad=pad,
                                        residual=residual, compare=compare, stats=stats, warp=warp, remap=remap, remap_step=remap_step, surfaces=surfaces,
                                        surface_layout=surface_layout, surface_options=surface_options, linear_light=linear_light, resample=resample,
-                                       packed=packed, lut=lut, dither=dither):
+                                       packed=packed, lut=lut, dither=dither, overlay=overlay):
             if p["is_idr"]:
                 epoch += 1
             if surfaces is not None:      # (synchronises torch's current stream: the tensors are complete)
